@@ -19,11 +19,20 @@ Inputs (mel, HuBERT, speaker one-hots) are resident in HBM before the timed regi
 on-device Philox generator.  Batch rows / chains never couple, so only the timing contract's barrier +
 max-reduce (and the chain mode's output gather) use RCCL.
 
-Rank 0 prints ONE JSON line: metric/value (motion frames/s, whole job), and at N=1 in batch mode, measured outside the
-timed region: the rooflines of the dominant HBM-bound and the largest MFMA-bound kernel instantiation (HIP-event timed on
-the context stream during one extra instrumented single-stream step), the window-chain latencies of config 4 (first /
-chained window at 1 chain and at 16 batched chains) and the CPU baselines (the oracle port on the host cores: a bounded
-sample of this workload, and BASELINE config 1 in full).
+Rank 0 prints ONE JSON line: metric/value (motion frames/s, whole job) and ms_per_step.  A plain run does nothing else: set-up,
+--warmup untimed steps, --steps timed steps, the line.
+
+  --full   also measures, beside the headline: the shader clock / socket power of the timed region, the host's own launch cost
+           per step (batch mode), and at N=1 in batch mode, outside the timed region: the rooflines of the dominant HBM-bound and
+           the largest MFMA-bound kernel instantiation (HIP-event timed on the context stream during one extra instrumented
+           single-stream step), the bf16 end-to-end error against the reference golden, the window-chain latencies of config 4
+           (first / chained window at 1 chain and at 16 batched chains) and the CPU baselines (the oracle port on the host cores:
+           a bounded sample of this workload, and BASELINE config 1 in full).  --no-roofline / --no-chain-latency /
+           --no-cpu-baseline drop single legs of it.
+  --dump-outputs DIR   after the timed steps, rank 0 writes what the last timed step returned as DIR/samples.npy (float32;
+           [clips, frames, channels], or [1, frames, channels] in chain mode).  Above 60 MiB it keeps a fixed, seeded sample of
+           whole clips (rows of dim 0; frames of dim 1 when dim 0 is 1), in their original order.  Inputs, weights and noise
+           seeds depend only on the arguments, so two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -43,6 +52,8 @@ import torch  # noqa: E402
 
 MFMA_PEAK_TFLOPS = {"bf16": 2500.0, "fp32": 157.3}     # dense, MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0                                  # HBM3E spec (6.3 TB/s is the measured copy ceiling)
+DUMP_BUDGET_BYTES = 60 * 2**20                         # --dump-outputs: larger outputs are written as a seeded sample
+DUMP_SAMPLE_SEED = 20240101
 
 
 def parse():
@@ -58,12 +69,39 @@ def parse():
     ap.add_argument("--stream-frames", type=int, default=9000, help="chain mode: length of the feature stream")
     ap.add_argument("--chains", type=int, default=32, help="chain mode: independent chains the stream is cut into (all ranks together)")
     ap.add_argument("--inputs-on-rank0", action="store_true", help="chain mode: only rank 0 holds the feature stream; it is broadcast (RCCL) first")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-chain-latency", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the measurements beside the headline (telemetry, launch cost, "
+                                                             "roofline, chain latencies, CPU baselines); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's output to DIR/samples.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline step")
+    ap.add_argument("--no-chain-latency", action="store_true", help="with --full: skip the window-chain latencies")
     ap.add_argument("--cpu-batch", type=int, default=8, help="clips in the CPU-baseline sample of this workload")
     ap.add_argument("--cpu-config1-steps", type=int, default=1000, help="steps of BASELINE configs[0]'s 1000-step loop timed on the host (1000 = in full)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+def dump_outputs(out: torch.Tensor, out_dir: str) -> dict:
+    """--dump-outputs: the last timed step's samples as out_dir/samples.npy, float32.  Above DUMP_BUDGET_BYTES only a fixed,
+    seeded subset of whole clips (dim 0, or dim 1 when dim 0 is 1) is written, sorted so it keeps the original order."""
+    import numpy as np
+    x = out.detach().float()
+    axis = 0 if x.shape[0] > 1 else 1
+    n = x.shape[axis]
+    per_row = x.numel() // n * 4
+    keep = min(n, DUMP_BUDGET_BYTES // per_row)
+    rows = None
+    if keep < n:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+        x = x.index_select(axis, torch.from_numpy(rows).to(x.device))
+    arr = np.ascontiguousarray(x.cpu().numpy(), dtype=np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "samples.npy"), arr)
+    return {"dir": out_dir, "samples": {"shape": list(arr.shape), "dtype": "float32", "full_shape": list(out.shape),
+                                        "sampled_axis": axis if rows is not None else None,
+                                        "sample": None if rows is None else f"{keep} of {n}, numpy default_rng({DUMP_SAMPLE_SEED}) choice, sorted"}}
 
 
 def cpu_baseline(cfg, sd, n_clips: int, full_batch: int):
@@ -329,8 +367,10 @@ def main():
         out = step(-1 - i)
     sync_barrier()
     lat, enq = [], []
-    tele = GpuTelemetry(local_rank, pci_bus_id=GpuTelemetry.pci_bus_id_of(local_rank))
-    tele.start()                                  # shader clock / socket power of this rank's GPU, sampled over the timed region only
+    tele = None
+    if args.full:
+        tele = GpuTelemetry(local_rank, pci_bus_id=GpuTelemetry.pci_bus_id_of(local_rank))
+        tele.start()                              # shader clock / socket power of this rank's GPU, sampled over the timed region only
     t0 = time.perf_counter()
     for i in range(args.steps):
         s0 = time.perf_counter()
@@ -343,11 +383,13 @@ def main():
             lat.append(time.perf_counter() - s0)
     sync_barrier()
     dt = time.perf_counter() - t0
-    tele.stop()
+    if tele is not None:
+        tele.stop()
     if out is not None:
         assert torch.isfinite(out).all(), "non-finite samples"
         if mode == "chain":
             assert tuple(out.shape) == (1, args.stream_frames, Cc)
+    dumped = dump_outputs(out, args.dump_outputs) if (args.dump_outputs and rank == 0 and out is not None) else None
     if dist is not None:
         tmax = torch.tensor([dt], device=dev if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -395,9 +437,9 @@ def main():
     result["host_enqueue_ms_per_step"] = 1e3 * statistics.median(enq)
     result["host_enqueue_note"] = ("wall time for this rank's host thread to return from one step() call, before any device sync (median); "
                                    "it INCLUDES the time hipLaunchKernel blocks while the device queues are full (rocprofv3 --hip-trace of this "
-                                   "command: most launches return in 2 - 8 us, a few block for tens of ms) — host_launch_cost_ms_per_step is the "
-                                   "host's own cost")
-    if mode == "batch" and B > 0:
+                                   "command: most launches return in 2 - 8 us, a few block for tens of ms) — host_launch_cost_ms_per_step (--full) is "
+                                   "the host's own cost")
+    if args.full and mode == "batch" and B > 0:
         # the host's own launch cost, without back-pressure: single evaluations enqueued on an IDLE device (a few hundred launches each, far
         # below the queue depth), timed until the call returns; x 25 (or 1000) evaluations per step
         tt_ = torch.full((B,), 500, dtype=torch.long, device=dev)
@@ -418,14 +460,17 @@ def main():
                                            "back-pressure): what the launch thread itself costs per step")
         model._cond_key = None
     result["host_affinity"] = pin
-    result["telemetry"] = tele.summary()
+    if tele is not None:
+        result["telemetry"] = tele.summary()
+    if dumped is not None:
+        result["dump_outputs"] = dumped
     if lat:
         result["p50_step_latency_ms"] = 1e3 * statistics.median(lat)
         result["step_latency_note"] = f"wall time of one step of this mode on rank 0, median over {len(lat)} steps"
     if dist is not None:
         result["collective_backend"] = dist.get_backend()
 
-    single = rank == 0 and world == 1 and mode == "batch"
+    single = args.full and rank == 0 and world == 1 and mode == "batch"
     lib = _lib.lib()
     if single and not args.no_roofline:
         _lib.check(lib.dsh_profile_enable(model._h, 1))

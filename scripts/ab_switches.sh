@@ -8,7 +8,7 @@ OUT=gpurun_out/${TAG}_ab_switches.txt
 run() {   # label, env assignments...
   local label="$1"; shift
   local line
-  line=$(env "$@" timeout 200 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-chain-latency 2>/dev/null | tail -1 |
+  line=$(env "$@" timeout 200 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-chain-latency 2>/dev/null | tail -1 |
          python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%9.1f frames/s  %7.2f ms/step' % (d['value'], d['ms_per_step']))")
   printf "%-58s %s\n" "$label" "$line" | tee -a $OUT
 }

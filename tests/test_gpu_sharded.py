@@ -240,11 +240,11 @@ def test_bench_at_world_size_8_on_one_device(mode, extra):
     """The launcher, rendezvous, barrier + max-reduce and (chain mode) the output gather at the world size the driver's scaling run
     uses: EIGHT ranks started by `python bench.py --gpus 8`, all sharing this box's one GPU (DSH_BENCH_OVERSUBSCRIBE, gloo because
     RCCL refuses several ranks per device).  Every rank pins itself to NUMA-local cores (host_affinity in the line) and the line
-    carries the host enqueue time per step."""
+    carries the host enqueue time per step and (--full) the telemetry of the timed region."""
     env = dict(os.environ, DSH_BENCH_OVERSUBSCRIBE="1", DSH_BENCH_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--mode", mode, "--steps", "1", "--warmup", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--mode", mode, "--steps", "1", "--warmup", "0", "--full",
            "--no-cpu-baseline", "--no-roofline", "--no-chain-latency"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
