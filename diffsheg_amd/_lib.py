@@ -59,6 +59,7 @@ SYMBOLS = {
     "dsh_sample_num_steps": (C.c_int64, [C.POINTER(SamplerOptsC), C.c_int32]),
     "dsh_sample": (C.c_int, [_P, C.POINTER(SamplerOptsC), _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int64, _P]),
     "dsh_sample_set_row_keys": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int32]),
+    "dsh_set_guidance_scale": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32]),
     "dsh_diffusion_table": (C.c_int32, [C.c_int32, C.c_int32, C.c_char_p, C.POINTER(C.c_double), C.c_int32]),
     "dsh_timestep_map": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "dsh_jump_schedule": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),

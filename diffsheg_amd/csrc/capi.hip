@@ -1,5 +1,6 @@
 // extern "C" surface of libdiffsheg_hip.so — see include/diffsheg_hip.h for the contract.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,7 +27,51 @@ struct dsh_ctx {
     dsh::Profiler prof;
     bool finalized = false;
     bool owns_stream = false;
+    // guidance scales (dsh_set_guidance_scale): device buffer read by the mix kernels, n values (0 = the config's cond_scale, held as one);
+    // the doubling decision is kept on the host
+    float* gs_dev = nullptr;
+    int gs_cap = 0, gs_n = 0;
+    bool gs_dbl = false;
+    ~dsh_ctx() {
+        den.reset();                                   // (the instances hold gs_dev)
+        if (gs_dev) (void)hipFree(gs_dev);
+    }
 };
+
+// n scales (n = 0: the config's cond_scale) -> the context's device buffer, in stream order, and the denoiser's doubling decision
+static int set_guidance(dsh_ctx* ctx, const float* scales, int n) {
+    DSH_REQUIRE(n >= 0 && (n == 0 || scales), "dsh_set_guidance_scale: null scale array");
+    const std::vector<float> v = n ? std::vector<float>(scales, scales + n) : std::vector<float>{ctx->cfg.cond_scale};
+    bool any = false;
+    for (float x : v) {
+        DSH_REQUIRE(std::isfinite(x), "dsh_set_guidance_scale: scales must be finite");
+        any = any || x != 1.0f;
+    }
+    DSH_REQUIRE(!(any && n > 0 && !ctx->cfg.classifier_free), "dsh_set_guidance_scale: the weights are not classifier-free (no null_cond_emb): the scale must be 1");
+    const int m = (int)v.size();
+    if (m > ctx->gs_cap) {
+        // (one allocation covers every batch up to 1024 clips: the address stays fixed for the life of the context in practice)
+        const int cap = std::max(m, 1024);
+        DSH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        DSH_HIP_CHECK(hipDeviceSynchronize());         // (sub-batch / twin streams of an earlier run may still read the old buffer)
+        float* p = nullptr;
+        DSH_HIP_CHECK(hipMalloc((void**)&p, (size_t)cap * sizeof(float)));
+        if (ctx->gs_dev) (void)hipFree(ctx->gs_dev);
+        ctx->gs_dev = p; ctx->gs_cap = cap;
+    }
+    // (in stream order: evaluations enqueued earlier on the context stream still read the old values; no host sync)
+    if (int e = dsh::launch_store_values_f32(ctx->gs_dev, v.data(), m, ctx->stream)) return e;
+    const bool dbl = ctx->cfg.classifier_free && any;
+    if (int e = ctx->den->set_guidance(ctx->gs_dev, m > 1 ? 1 : 0, dbl)) return e;
+    ctx->gs_n = n; ctx->gs_dbl = dbl;
+    return 0;
+}
+
+// per-clip scales must match the batch being evaluated / sampled
+static int check_guidance(const dsh_ctx* ctx) {
+    DSH_REQUIRE(ctx->gs_n <= 1 || ctx->gs_n == ctx->den->batch, "dsh_set_guidance_scale: per-clip scales do not match the batch of set_condition()");
+    return 0;
+}
 
 #define API_BEGIN try {
 #define API_END                                                                       \
@@ -71,6 +116,7 @@ int dsh_create(const dsh_model_config* c, void* hip_stream, dsh_ctx** out) {
     ctx->prof.st = ctx->stream;
     ctx->den->prof = &ctx->prof;
     ctx->sampler->prof = &ctx->prof;
+    if (int e = set_guidance(ctx, nullptr, 0)) { dsh_destroy(ctx); return e; }
     *out = ctx;
     return 0;
     API_END
@@ -137,6 +183,7 @@ int dsh_eval(dsh_ctx* ctx, const float* x, const int64_t* t, const float* c1, co
         for (int b = 1; b < B; ++b) uni = uni && th[b] == th[0];
         ctx->den->t_uniform = uni && dsh::emb_dedup_enabled();
     }
+    if (int e = check_guidance(ctx)) return e;
     return ctx->den->eval(x, t, c1, c2, eps);
     API_END
 }
@@ -204,10 +251,18 @@ int dsh_sample_set_row_keys(dsh_ctx* ctx, const uint64_t* keys_host, int32_t n) 
     API_END
 }
 
+int dsh_set_guidance_scale(dsh_ctx* ctx, const float* scales_host, int32_t n) {
+    API_BEGIN
+    DSH_REQUIRE(ctx, "null context");
+    return set_guidance(ctx, scales_host, n);
+    API_END
+}
+
 int dsh_sample(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t init_from_x, const float* gt,
                const uint8_t* mask, int32_t masked, const float* noise_stack, int64_t n_draws, float* trace) {
     API_BEGIN
     DSH_REQUIRE(ctx && opts, "null argument");
+    if (int e = check_guidance(ctx)) return e;
     return ctx->sampler->run(ctx->den.get(), to_opts(opts), x, init_from_x != 0, gt, mask, masked != 0, noise_stack,
                              n_draws, trace);
     API_END

@@ -15,14 +15,13 @@ namespace dsh {
 struct ModelConfig {
     int dim_pose = 129, expression_dim = 103, style_dim = 4;
     int classifier_free = 1;
-    float cond_scale = 1.25f;
+    float cond_scale = 1.25f;      // the context's guidance scale until dsh_set_guidance_scale() changes it (capi.hip)
     int latent_dim = 512, ff_size = 1024, num_layers = 8, num_heads = 8;
     int audio_dim = 128, aud_latent_dim = 256, hubert_dim = 1024, hubert_enc_dim = 128;
     int precision = 0;   // 0 = fp32 (exact-fp32 MFMA), 1 = bf16 storage + bf16 MFMA, fp32 accumulate
     // 1: the model is ONE MotionTransformer over all dim_pose + expression_dim channels (runner.py:46-57, opt.unidiffuser =
     // False, model_base transformer_encoder): no encoder_aud, audio_proj on the 128 mel features, no expression -> gesture flow
     int single_transformer = 0;
-    int cfg_active() const { return classifier_free && cond_scale != 1.0f; }
     int channels() const { return dim_pose + expression_dim; }
     int time_embed_dim() const { return 4 * latent_dim; }
 };
@@ -74,6 +73,11 @@ class DenoiserBase {
     virtual size_t weight_bytes() const = 0;
     // debug taps (device -> caller device buffer, fp32): "aud_feat" [B,T,128], "expr_x0" [B,T,E]
     virtual int debug_copy(const std::string& what, float* out) = 0;
+    // Classifier-free guidance of the next evaluations (transformer.py:537, :586): eps = u + s_b (k - u) with s_b = scale[b * scale_row] for clip b
+    // (device fp32, read by the mix kernels when they run: a captured graph follows the buffer's contents), scale_row 0 = one value for the batch.
+    // doubled = evaluate the null half at all (classifier-free weights and some s_b != 1); a clip at exactly 1 in a doubled batch takes k.  Grows
+    // the token-row workspace the first time a doubled batch is asked for.  The scale buffer must outlive every evaluation that reads it.
+    virtual int set_guidance(const float* scale, int scale_row, bool doubled) = 0;
     // Sub-batch streams.  Large batches are conditioned as several independent sub-batches, each with its own instance (shared
     // weights) and stream.  eval() forks / joins them around ONE evaluation; a sampling loop can do better: clips never interact,
     // so it drives every sub-batch through ALL its steps on that sub-batch's stream and joins once at the end (sampler.hip).

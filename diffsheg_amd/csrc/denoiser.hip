@@ -26,7 +26,7 @@ namespace {
 template <typename T>
 class Denoiser final : public DenoiserBase {
   public:
-    Denoiser(const ModelConfig& c, hipStream_t s) : cfg(c), st(s) {
+    Denoiser(const ModelConfig& c, hipStream_t s) : cfg(c), st(s), gs_dbl(c.classifier_free && c.cond_scale != 1.0f) {
         const char* t2 = getenv("DSH_TL2");
         tl2_on = !(t2 && atoi(t2) == 0);          // LDS-DMA token-per-lane kernels (tl2.hip); DSH_TL2=0: first generation
         tl2_all = t2 && atoi(t2) == 2;            // DSH_TL2=2: also for the HBM-bound (residual) instantiations
@@ -77,7 +77,7 @@ class Denoiser final : public DenoiserBase {
     // second instance on another stream that shares (does not own) the finalized weights; own workspace
     Denoiser(const Denoiser& o, hipStream_t s)
         : cfg(o.cfg), st(s), wbytes(o.wbytes), finalized(o.finalized), aud_te0(o.aud_te0), aud_te2(o.aud_te2),
-          aud_film(o.aud_film), aud_stream(o.aud_stream), aud_ap_bias(o.aud_ap_bias), aud_bias(o.aud_bias), aud_film_g(o.aud_film_g), aud_film_b(o.aud_film_b), aud(o.aud), exp_(o.exp_), ges_(o.ges_), tl2_on(o.tl2_on), tl2_all(o.tl2_all), ffn_fuse(o.ffn_fuse), ffn_ver(o.ffn_ver), hilo(o.hilo), tls_on(o.tls_on), tl2_hl(o.tl2_hl), f32_bits(o.f32_bits), f32_min_rows(o.f32_min_rows), f32_fuse(o.f32_fuse), dbg_skip(o.dbg_skip), ffn_sty(o.ffn_sty), tls_rows(o.tls_rows), rev_on(o.rev_on) {
+          aud_film(o.aud_film), aud_stream(o.aud_stream), aud_ap_bias(o.aud_ap_bias), aud_bias(o.aud_bias), aud_film_g(o.aud_film_g), aud_film_b(o.aud_film_b), aud(o.aud), exp_(o.exp_), ges_(o.ges_), tl2_on(o.tl2_on), tl2_all(o.tl2_all), ffn_fuse(o.ffn_fuse), ffn_ver(o.ffn_ver), hilo(o.hilo), tls_on(o.tls_on), tl2_hl(o.tl2_hl), f32_bits(o.f32_bits), f32_min_rows(o.f32_min_rows), f32_fuse(o.f32_fuse), dbg_skip(o.dbg_skip), ffn_sty(o.ffn_sty), tls_rows(o.tls_rows), rev_on(o.rev_on), gs(o.gs), gs_row(o.gs_row), gs_dbl(o.gs_dbl) {
         for (Encoder* E : {&exp_, &ges_}) { E->pid_part = nullptr; E->pid_part_s = nullptr; E->hub = nullptr; E->film_tab = nullptr; E->aproj_buf = nullptr; }
     }
     DenoiserBase* clone_shared(hipStream_t s) override { return finalized ? new Denoiser(*this, s) : nullptr; }
@@ -85,6 +85,7 @@ class Denoiser final : public DenoiserBase {
     ~Denoiser() override {
         for (void* p : allocs) (void)hipFree(p);
         for (void* p : ws_allocs) (void)hipFree(p);
+        for (void* p : row_allocs) (void)hipFree(p);
         if (lvl_slots) (void)hipFree(lvl_slots);
     }
 
@@ -112,6 +113,12 @@ class Denoiser final : public DenoiserBase {
     int adopt_level_slots(char* slots, size_t stride, int n) override { lvl_borrowed = slots; lvl_borrowed_stride = stride; lvl_borrowed_n = n; return 0; }
     int eval_level(const float* x, const int64_t* t, const float* c1, const float* c2, float* eps, int mode, const int64_t* level) override;
     double issued_flops_per_eval() const override { return flops_last_eval; }
+    int set_guidance(const float* scale, int scale_row, bool doubled) override {
+        DSH_REQUIRE(!doubled || cfg.classifier_free, "guidance needs classifier-free weights (null_cond_emb)");
+        DSH_REQUIRE(!doubled || scale, "a doubled batch needs its guidance scales");
+        gs = scale; gs_row = scale_row ? 1 : 0; gs_dbl = doubled;
+        return row_buffers();                              // (an unconditioned instance sizes them at its first set_condition)
+    }
     size_t weight_bytes() const override { return wbytes; }
     int debug_copy(const std::string& what, float* out) override;
 
@@ -182,6 +189,11 @@ class Denoiser final : public DenoiserBase {
 
     // ---- workspace (grow-only) ----
     int capB = 0, capT = 0;
+    // guidance (set_guidance): scale of clip b = gs[b * gs_row]; gs_dbl = the null half is evaluated.  ws_dbl: the M-row buffers
+    // (row_allocs) hold both halves — from the first time a doubled batch is asked for, never shrunk
+    const float* gs = nullptr; int gs_row = 0; bool gs_dbl = false, ws_dbl = false;
+    std::vector<void*> row_allocs;
+    int row_buffers();
     float *audio_f = nullptr, *h = nullptr, *o = nullptr, *expr_x0 = nullptr, *film_aud_tab = nullptr, *aud_feat_f = nullptr;
     T *temb = nullptr, *hid = nullptr, *semb = nullptr, *pid_in = nullptr, *audio256 = nullptr,
       *x_in = nullptr, *h16 = nullptr, *n = nullptr, *y = nullptr, *s = nullptr, *qkv = nullptr, *U = nullptr,
@@ -639,7 +651,7 @@ int Denoiser<T>::encoder_from(const std::map<std::string, HostTensor>& w, const 
         if (int e = upload_f32(&E.pe, pe->data.data(), pe->numel())) return e;
     }
     const float* null_emb = nullptr;
-    if (cfg.cfg_active()) {
+    if (cfg.classifier_free) {          // (whatever the scale at creation: the context may start guiding later, set_guidance)
         const HostTensor* ne = find(w, p + "null_cond_emb"); if (!ne) return -1;
         DSH_REQUIRE((int)ne->numel() == P, "null_cond_emb shape mismatch");
         null_emb = ne->data.data();
@@ -728,22 +740,27 @@ int Denoiser<T>::ensure_workspace(int B, int T_) {
     if (B <= capB && T_ <= capT) return 0;
     DSH_HIP_CHECK(hipStreamSynchronize(st));
     for (void* p : ws_allocs) (void)hipFree(p);
-    ws_allocs.clear();
+    for (void* p : row_allocs) (void)hipFree(p);
+    ws_allocs.clear(); row_allocs.clear();
     capB = std::max(B, capB); capT = std::max(T_, capT);
+    ws_dbl = ws_dbl || gs_dbl;
     // rows padded to the 128-token block of tl_linear (it does not bounds-check rows)
     // (+128: a cond-half launch starts at row r0 = B*T, which is not block aligned)
     // (the token-per-lane path keeps the two CFG halves in separately block-aligned row ranges: rows [0, Mc) and
     //  [round_up(Mc, 128), +Mc), so that a half-only launch never touches the other half)
     // (256: the K = 512 LDS-DMA kernels own 256 tokens per block)
-    const size_t Bc = capB, Mc = (size_t)round_up(capB * capT, 256) + 256, M = (size_t)round_up(capB * capT, 256) * (cfg.cfg_active() ? 2 : 1) + 256;
+    // M-row buffers (both CFG halves once a doubled batch has been asked for) go to row_allocs: row_buffers() re-allocates them alone
+    const size_t Bc = capB, Mc = (size_t)round_up(capB * capT, 256) + 256, M = (size_t)round_up(capB * capT, 256) * (ws_dbl ? 2 : 1) + 256;
     const int D = cfg.latent_dim, TE = cfg.time_embed_dim(), F = cfg.ff_size, L = cfg.num_layers;
     const int cinp = std::max(exp_.cin_p, ges_.cin_p);      // (exp_ is empty in single-transformer mode)
     const int Ppmax = ges_.layers[0].Pp;
     auto& P = ws_allocs;
+    auto& R = row_allocs;
 #define WS(ptr, nelem) if (int e = dalloc(&ptr, (nelem), P)) return e
+#define WR(ptr, nelem) if (int e = dalloc(&ptr, (nelem), R)) return e
     WS(audio_f, Mc * cfg.audio_dim);
-    WS(h, M * D);
-    WS(o, M * cinp);
+    WR(h, M * D);
+    WR(o, M * cinp);
     WS(expr_x0, Mc * expr_ld());
     DSH_HIP_CHECK(hipMemsetAsync(expr_x0, 0, Mc * expr_ld() * sizeof(float), st));   // (the pad columns are never written)
     WS(expr16, Mc * 128);
@@ -760,16 +777,16 @@ int Denoiser<T>::ensure_workspace(int B, int T_) {
     WS(film_small, Bc * (size_t)ges_.film.N);
     WS(audio256, Mc * 2 * cfg.audio_dim);
     if (tl_path()) { WS(aproj_rm, Mc * cfg.aud_latent_dim); WS(hub_rm, Mc * cfg.hubert_enc_dim); WS(h0, Mc * D); }
-    if (tl_path() && capT > 96) { WS(qkv_rm, M * 3 * D); WS(y_rm, M * D); }
+    if (tl_path() && capT > 96) { WR(qkv_rm, M * 3 * D); WR(y_rm, M * D); }
     WS(x_in, Mc * cinp);
-    if (sizeof(T) != 4) { WS(h16, M * D); WS(hlo, M * D); }
-    WS(n, M * D);
-    WS(y, M * D);
-    WS(s, M * D);
-    WS(qkv, M * 3 * D);
+    if (sizeof(T) != 4) { WR(h16, M * D); WR(hlo, M * D); }
+    WR(n, M * D);
+    WR(y, M * D);
+    WR(s, M * D);
+    WR(qkv, M * 3 * D);
     WS(U, Mc * Ppmax);
-    WS(g, M * F);
-    WS(y2, M * D);
+    WR(g, M * F);
+    WR(y2, M * D);
     WS(col, Mc * 3 * cfg.hubert_dim);
     WS(z, Mc * cfg.hubert_enc_dim);
     for (Encoder* E : encs()) {
@@ -781,6 +798,35 @@ int Denoiser<T>::ensure_workspace(int B, int T_) {
     }
     lvl_n = 0;                                   // the timestep cache is laid out for one (B, T)
 #undef WS
+#undef WR
+    return 0;
+}
+
+// a doubled batch asked for while the M-row buffers hold one CFG half: re-allocate those alone (scratch of one evaluation; the
+// conditioning in the other buffers is kept), never shrunk
+template <typename T>
+int Denoiser<T>::row_buffers() {
+    if (ws_dbl || !gs_dbl || capB == 0) return 0;
+    DSH_HIP_CHECK(hipStreamSynchronize(st));
+    for (void* p : row_allocs) (void)hipFree(p);
+    row_allocs.clear();
+    ws_dbl = true;
+    const size_t M = (size_t)round_up(capB * capT, 256) * 2 + 256;
+    const int D = cfg.latent_dim, F = cfg.ff_size;
+    const int cinp = std::max(exp_.cin_p, ges_.cin_p);
+    auto& R = row_allocs;
+#define WR(ptr, nelem) if (int e = dalloc(&ptr, (nelem), R)) return e
+    WR(h, M * D);
+    WR(o, M * cinp);
+    if (tl_path() && capT > 96) { WR(qkv_rm, M * 3 * D); WR(y_rm, M * D); }
+    if (sizeof(T) != 4) { WR(h16, M * D); WR(hlo, M * D); }
+    WR(n, M * D);
+    WR(y, M * D);
+    WR(s, M * D);
+    WR(qkv, M * 3 * D);
+    WR(g, M * F);
+    WR(y2, M * D);
+#undef WR
     return 0;
 }
 
@@ -952,7 +998,9 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
     const int B = batch, fr = frames, D = cfg.latent_dim, C = cfg.channels();
     const bool tlp = E.layers[0].tl;
     // token-per-lane path: tiled activations; the conditional half starts at the next 256-row block after the null half
-    const int Mc = B * fr, has_null = cfg.cfg_active() ? 1 : 0, r0 = has_null ? (tlp ? round_up(Mc, 256) : Mc) : 0;
+    // classifier-free guidance: the null half is evaluated when some clip's scale is not 1 (set_guidance, transformer.py:537)
+    const int Mc = B * fr, has_null = gs_dbl ? 1 : 0, r0 = has_null ? (tlp ? round_up(Mc, 256) : Mc) : 0;
+    DSH_REQUIRE(!has_null || (ws_dbl && E.layers[0].null_const && gs), "doubled batch without null constants / doubled workspace / scales");
     const int M = r0 + Mc;
     const int film_ld = E.film.N;
     T* const aproj = E.aproj_buf;
@@ -1095,14 +1143,14 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
         // both halves and every output tile back to back (one wave per SIMD, 320 registers), where the three launches it replaces spread the
         // same work over the chip.  Off unless DSH_OUT_FUSE=1.
         flops_acc += 2.0 * M * (double)E.out_tl.N * D;
-        return launch_tl_out_mix(h16, E.out_tl.wf, E.out_tl.b, E.out_tl.N, Mc, r0, has_null, fr, w, c0, C, cfg.cond_scale, eps, x, c1, c2,
+        return launch_tl_out_mix(h16, E.out_tl.wf, E.out_tl.b, E.out_tl.N, Mc, r0, has_null, fr, w, c0, C, gs, gs_row, eps, x, c1, c2,
                                  want_x0 ? expr_x0 : nullptr, want_x0 ? expr16 : nullptr, st);
     }
     if (tlp) {
         if (int e = tl(E.out_tl, 0, h16, M, ACT_NONE, nullptr, nullptr, 0, 0, fr, B, nullptr, o, nullptr, nullptr, 0,
                        nullptr, nullptr, nullptr, 0, 0x7fffffff, E.cin_p)) return e;
     } else if (int e = gemm(E.out, hT(), D, M, ACT_NONE, false, nullptr, 0, 0, o, E.cin_p, nullptr, 0)) return e;
-    if (int e = launch_cfg_mix(o, E.cin_p, Mc, r0, fr, w, has_null, cfg.cond_scale, eps, C, c0, x, C, c1, c2,
+    if (int e = launch_cfg_mix(o, E.cin_p, Mc, r0, fr, w, has_null, gs, gs_row, eps, C, c0, x, C, c1, c2,
                                want_x0 ? expr_x0 : nullptr, expr_ld(), st)) return e;
     // tiled bf16 copy of the expression x0, zero padded to 128 columns: last segment of the gesture encoder's concat rows
     if (want_x0 && tlp) return launch_tile_rows_bf16<float>(expr_x0, expr_ld(), Mc, w, expr16, 128, st);
@@ -1456,6 +1504,7 @@ class DualDenoiser final : public DenoiserBase {
         // everything already enqueued on the evaluating stream (the conditioning copies) precedes the twin's work
         DSH_HIP_CHECK(hipEventRecord(twin_ev_, st_));
         DSH_HIP_CHECK(hipStreamWaitEvent(twin_stream_, twin_ev_, 0));
+        if (int e = twin_->set_guidance(gs_, gs_row_, gs_dbl_)) return e;
         if (!twin_cond_ok_) {
             if (int e = twin_->set_part(0)) return e;
             if (int e = twin_->set_condition(cond_.B, cond_.T, cond_.audio, cond_.pid, cond_.hubert)) return e;
@@ -1513,6 +1562,13 @@ class DualDenoiser final : public DenoiserBase {
         return f;
     }
     size_t weight_bytes() const override { return inst_[0]->weight_bytes(); }
+    // every instance that evaluates sees the context's scales: a sub-batch instance its clips' slice (per-clip scales), the gesture twin all
+    int set_guidance(const float* scale, int scale_row, bool doubled) override {
+        gs_ = scale; gs_row_ = scale_row ? 1 : 0; gs_dbl_ = doubled;
+        for (int i = 0; i < (int)inst_.size(); ++i) { if (int e = push_guidance(i, split_now_)) return e; }
+        if (twin_) { if (int e = twin_->set_guidance(gs_, gs_row_, gs_dbl_)) return e; }
+        return 0;
+    }
     int debug_copy(const std::string& what, float* out) override {
         DSH_REQUIRE(split_now_ == 1, "debug taps are only available on single-stream (small-batch) evaluations");
         return inst_[0]->debug_copy(what, out);
@@ -1559,6 +1615,7 @@ class DualDenoiser final : public DenoiserBase {
             inst_.emplace_back(c);
         }
         split_now_ = ns;
+        for (int i = 0; i < ns; ++i) { if (int e = push_guidance(i, ns)) return e; }
         inst_[0]->prof = prof;
         if (ns == 1) return inst_[0]->set_condition(cond_.B, cond_.T, cond_.audio, cond_.pid, cond_.hubert);
         DSH_HIP_CHECK(hipEventRecord(ev_fork_, st_));
@@ -1576,7 +1633,13 @@ class DualDenoiser final : public DenoiserBase {
         }
         return 0;
     }
+    // instance i of an ns-way split: the scales of its clips (first_clip(i, ns) onwards) when they are per clip
+    int push_guidance(int i, int ns) {
+        const int b0 = (gs_row_ && ns > 1 && i < ns && cond_.B > 0) ? first_clip(i, ns) : 0;
+        return inst_[i]->set_guidance(gs_ ? gs_ + b0 : nullptr, gs_row_, gs_dbl_);
+    }
     std::vector<std::unique_ptr<DenoiserBase>> inst_;      // [0] owns the weights; the others share them
+    const float* gs_ = nullptr; int gs_row_ = 0; bool gs_dbl_ = false;   // the context's guidance (set_guidance)
     ModelConfig cfg_;
     hipStream_t st_;
     std::vector<hipStream_t> streams_;

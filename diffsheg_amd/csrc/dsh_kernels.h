@@ -52,7 +52,8 @@ int launch_temb_rows(const int64_t* t, int B, int dim, T* out, int ldo, hipStrea
 template <typename T>
 int launch_pack_cols(const float* x, int ldx, int M, int c0, int w, int wpad, float scale, T* out, int ldo, float* outf,
                      int ldof, hipStream_t s);
-int launch_cfg_mix(const float* o, int ldo, int Mc, int cond_row0, int frames, int w, int has_null, float cond_scale,
+// (guidance scale of clip b: scale[b * scale_row], device fp32; scale_row 0 = one value for the batch, 1 = one per clip)
+int launch_cfg_mix(const float* o, int ldo, int Mc, int cond_row0, int frames, int w, int has_null, const float* scale, int scale_row,
                    float* eps, int lde, int c0, const float* x, int ldx, const float* c1, const float* c2, float* x0,
                    int ldx0, hipStream_t s);
 
@@ -174,10 +175,11 @@ int launch_tl_aud_tail(const void* Y, const float* X2, const void* Wst, const fl
                        void* ap_out0 = nullptr, void* ap_out1 = nullptr);
 // round 6 (tl_out.hip): the `out` head for both CFG halves + CFG mix (+ x0 = c1 x - c2 eps and its tiled bf16 copy) in one launch;
 // hi = hi plane of the residual stream (null half at rows [0, Mc), conditional half at [row1, row1 + Mc)), wfrag / bias = the `out` Linear
-// in fragment order padded to n_out_padded (128 or 160) rows, eps / x [Mc, C] with the encoder's w channels at column c0
+// in fragment order padded to n_out_padded (128 or 160) rows, eps / x [Mc, C] with the encoder's w channels at column c0; guidance scales
+// as launch_cfg_mix
 int launch_tl_out_mix(const void* hi, const void* wfrag, const float* bias, int n_out_padded, int Mc, int row1, int has_null, int frames, int w,
-                      int c0, int C, float cond_scale, float* eps, const float* x, const float* c1, const float* c2, float* x0, void* x0_tiled,
-                      hipStream_t s);
+                      int c0, int C, const float* scale, int scale_row, float* eps, const float* x, const float* c1, const float* c2, float* x0,
+                      void* x0_tiled, hipStream_t s);
 // audio_proj of up to two motion encoders from the row-major bf16 [Mc, 256] operand straight into their tiled [Mc, 256] concat operands
 // (tl_embed.hip); wfrag = tl_aud_pack_audio_proj per encoder (128 KB apart), bias [n_enc][256]
 int launch_tl_aproj(const void* x256, const void* wfrag, const float* bias, int n_enc, void* out0, void* out1, int Mc, hipStream_t s);
@@ -242,6 +244,8 @@ struct DdpmStepArgs {
 };
 int launch_ddpm_step(const DdpmStepArgs& a, hipStream_t s);
 int launch_fill_i64(int64_t* p, int64_t v, size_t n, hipStream_t s);
+// p[0, n) = host[0, n) in stream order (values passed as launch arguments: the host array may be reused at once, no sync)
+int launch_store_values_f32(float* p, const float* host, int n, hipStream_t s);
 int launch_fill_f32(float* p, float v, size_t n, hipStream_t s);
 int launch_fill_step(int64_t* t, float* c1, float* c2, int64_t* level, int64_t tv, float c1v, float c2v, int64_t lv, int n, hipStream_t s);
 struct LevelCopyArgs {

@@ -265,9 +265,11 @@ template int launch_pack_cols<bf16>(const float*, int, int, int, int, int, float
 
 // ------------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------------
-// eps[b,t,c0+c] = o_u + s (o_c - o_u)   (o rows: [0,Mc) unconditional, [cond_row0, cond_row0+Mc) conditional; has_null==0: copy)
+// eps[b,t,c0+c] = o_u + s_b (o_c - o_u)   (o rows: [0,Mc) unconditional, [cond_row0, cond_row0+Mc) conditional; has_null==0: copy)
+// s_b = scale[b * scale_row] (device: read when the kernel runs, so a captured graph follows the context's guidance buffer); a clip whose
+// scale is exactly 1 takes o_c itself (u + 1 (k - u) is not k in fp32)
 // x0[r,c] = c1[b] * x[b,t,c0+c] - c2[b] * eps   (optional; expression branch feeding the gesture concat)
-__global__ void cfg_mix_kernel(const float* o, int ldo, int cond_row0, int frames, int w, int has_null, float cond_scale,
+__global__ void cfg_mix_kernel(const float* o, int ldo, int cond_row0, int frames, int w, int has_null, const float* scale, int scale_row,
                                float* eps, int lde, int c0, const float* x, int ldx, const float* c1, const float* c2,
                                float* x0, int ldx0) {
     const int row = blockIdx.x;
@@ -277,7 +279,10 @@ __global__ void cfg_mix_kernel(const float* o, int ldo, int cond_row0, int frame
         if (has_null) {
             const float u = o[(size_t)row * ldo + c];
             const float k = o[(size_t)(row + cond_row0) * ldo + c];
-            e = __fadd_rn(u, __fmul_rn(cond_scale, __fsub_rn(k, u)));
+            // (the scale is read behind the two loads, not hoisted in front of them: its latency overlaps theirs)
+            asm volatile("" ::: "memory");
+            const float cs = scale[(size_t)b * scale_row];
+            e = cs == 1.0f ? k : __fadd_rn(u, __fmul_rn(cs, __fsub_rn(k, u)));
         } else {
             e = o[(size_t)row * ldo + c];
         }
@@ -289,10 +294,11 @@ __global__ void cfg_mix_kernel(const float* o, int ldo, int cond_row0, int frame
         }
     }
 }
-int launch_cfg_mix(const float* o, int ldo, int Mc, int cond_row0, int frames, int w, int has_null, float cond_scale,
+int launch_cfg_mix(const float* o, int ldo, int Mc, int cond_row0, int frames, int w, int has_null, const float* scale, int scale_row,
                    float* eps, int lde, int c0, const float* x, int ldx, const float* c1, const float* c2, float* x0,
                    int ldx0, hipStream_t s) {
-    hipLaunchKernelGGL(cfg_mix_kernel, dim3(Mc), dim3(128), 0, s, o, ldo, cond_row0, frames, w, has_null, cond_scale, eps, lde,
+    DSH_REQUIRE(!has_null || scale, "cfg_mix: a doubled batch needs its guidance scales");
+    hipLaunchKernelGGL(cfg_mix_kernel, dim3(Mc), dim3(128), 0, s, o, ldo, cond_row0, frames, w, has_null, scale, scale_row, eps, lde,
                        c0, x, ldx, c1, c2, x0, ldx0);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;

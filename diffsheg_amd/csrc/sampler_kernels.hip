@@ -131,6 +131,21 @@ int launch_fill_f32(float* p, float v, size_t n, hipStream_t s) {
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }
+// host values -> device in stream order without a host sync: 64 values per launch travel as the kernel's by-value argument
+struct F32x64 { float v[64]; };
+__global__ void store_values_kernel(float* p, F32x64 v, int n) {
+    if ((int)threadIdx.x < n) p[threadIdx.x] = v.v[threadIdx.x];
+}
+int launch_store_values_f32(float* p, const float* host, int n, hipStream_t s) {
+    for (int i = 0; i < n; i += 64) {
+        F32x64 v{};
+        const int k = std::min(64, n - i);
+        for (int j = 0; j < k; ++j) v.v[j] = host[i + j];
+        hipLaunchKernelGGL(store_values_kernel, dim3(1), dim3(64), 0, s, p + i, v, k);
+        DSH_HIP_CHECK(hipGetLastError());
+    }
+    return 0;
+}
 
 // one launch for the per-step scalars of an evaluation: t, the two x0 coefficients and the spaced level (timestep-cache slot)
 __global__ void fill_step_kernel(int64_t* t, float* c1, float* c2, int64_t* level, int64_t tv, float c1v, float c2v, int64_t lv, int n) {

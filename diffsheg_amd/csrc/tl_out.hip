@@ -22,7 +22,7 @@ struct TlOutArgs {
     const void* W;            // `out` in fragment order [32 NTO, 512]
     const float* bias;        // [32 NTO]
     int Mc, row1, has_null, frames, w, c0, C;   // conditional half at rows [row1, row1 + Mc); w real output columns at column c0 of the [., C] tensors
-    float cond_scale;
+    const float* scale; int scale_row;   // guidance scale of clip b: scale[b * scale_row] (device; exactly 1: the conditional output itself)
     float* eps;               // [Mc, C] fp32
     const float* x; const float* c1; const float* c2;   // x0 = c1[clip] x - c2[clip] eps (x0 == null: off)
     float* x0; void* x0t;     // [Mc, w] fp32 row-major and tiled bf16 [Mc, 128] (zero padded)
@@ -40,6 +40,8 @@ __global__ __launch_bounds__(256, 1) void tl_out_mix_kernel(TlOutArgs p) {
     const int lane_off = ml * 32 + h * 16;
     float* slab = reinterpret_cast<float*>(smem) + (size_t)wave * 32 * LDW;
     const char* wl = reinterpret_cast<const char*>(p.W) + lane * 16;
+    // every accumulator element of a lane belongs to token ml of the wave's 32: that token's clip scale (rows past Mc: the last clip's)
+    const float cs = p.has_null ? p.scale[(size_t)(min(tb * 32 + ml, p.Mc - 1) / p.frames) * p.scale_row] : 1.f;
     f32x16 mix[NTO];
     // one CFG half: the 32 fragments of its rows, then the NTO tiles (weights 8 fragments at a time: the loads of a whole tile in flight
     // at once cost 128 registers next to the 128 of the row fragments)
@@ -74,9 +76,9 @@ __global__ __launch_bounds__(256, 1) void tl_out_mix_kernel(TlOutArgs p) {
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (g == 3) {
                 if constexpr (HALF == 0) mix[nt] = acc;
-                else if (p.has_null) {
+                else if (p.has_null && cs != 1.0f) {
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) mix[nt][e] = __fadd_rn(mix[nt][e], __fmul_rn(p.cond_scale, __fsub_rn(acc[e], mix[nt][e])));
+                    for (int e = 0; e < 16; ++e) mix[nt][e] = __fadd_rn(mix[nt][e], __fmul_rn(cs, __fsub_rn(acc[e], mix[nt][e])));
                 } else mix[nt] = acc;
             }
         });
@@ -133,16 +135,17 @@ __global__ __launch_bounds__(256, 1) void tl_out_mix_kernel(TlOutArgs p) {
 }
 
 int launch_tl_out_mix(const void* hi, const void* wfrag, const float* bias, int n_out_padded, int Mc, int row1, int has_null, int frames, int w,
-                      int c0, int C, float cond_scale, float* eps, const float* x, const float* c1, const float* c2, float* x0, void* x0_tiled,
-                      hipStream_t s) {
+                      int c0, int C, const float* scale, int scale_row, float* eps, const float* x, const float* c1, const float* c2, float* x0,
+                      void* x0_tiled, hipStream_t s) {
     DSH_REQUIRE(hi && wfrag && bias && eps && Mc > 0 && frames > 0 && w > 0 && w <= n_out_padded, "tl_out_mix: null operand");
     DSH_REQUIRE(n_out_padded == 128 || n_out_padded == 160, "tl_out_mix: instantiated for 4 or 5 output tiles (103 / 129 channels)");
     DSH_REQUIRE(!has_null || row1 % 32 == 0, "tl_out_mix: the conditional half starts on a 32-row boundary");
+    DSH_REQUIRE(!has_null || scale, "tl_out_mix: a doubled batch needs its guidance scales");
     DSH_REQUIRE(!x0 || (x && c1 && c2), "tl_out_mix: x0 needs x, c1, c2");
     DSH_REQUIRE(!x0_tiled || (x0 && n_out_padded == 128), "tl_out_mix: the tiled x0 copy is 128 columns wide");
     TlOutArgs a;
     a.H = hi; a.W = wfrag; a.bias = bias; a.Mc = Mc; a.row1 = row1; a.has_null = has_null; a.frames = frames; a.w = w; a.c0 = c0; a.C = C;
-    a.cond_scale = cond_scale; a.eps = eps; a.x = x; a.c1 = c1; a.c2 = c2; a.x0 = x0; a.x0t = x0_tiled;
+    a.scale = scale; a.scale_row = scale_row; a.eps = eps; a.x = x; a.c1 = c1; a.c2 = c2; a.x0 = x0; a.x0t = x0_tiled;
     const dim3 grid(ceil_div(Mc, 128)), block(256);
     if (n_out_padded == 128) {
         constexpr int lds = 4 * 32 * (4 * 32 + 4) * 4;

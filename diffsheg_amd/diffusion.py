@@ -7,15 +7,16 @@ libdiffsheg_hip.so (csrc/sampler.hip) with no host syncs per step.
 
 Differences a caller can observe, all loud:
   * the model must be a :class:`diffsheg_amd.model.UniDiffuser` (epsilon prediction, FIXED_SMALL var);
-  * ``denoised_fn`` / ``cond_fn`` / ``pre_seq`` / ``transl_req`` and an ``opt.cond_scale`` other than the model
-    handle's raise NotImplementedError (``same_overlap_noisy``, ``eta != 0`` and ``fix_head_var`` are built: the
+  * ``denoised_fn`` / ``cond_fn`` / ``pre_seq`` / ``transl_req`` raise NotImplementedError (``same_overlap_noisy``, ``eta != 0`` and ``fix_head_var`` are built: the
     saved noisy tails live in the native context, eta adds one draw per DDIM step, fix_head_var is a no-op of
     the reference's own sampling code — see ``_run``);
   * Gaussian noise comes from ``noise_source`` (any object with ``randn(shape) -> Tensor``, consumed in
     the reference's draw order — this is how parity tests inject identical noise) or, if None, from the
     on-device Philox generator seeded by ``seed`` / ``torch.initial_seed()``; ``row_keys`` (one integer per
     batch row) additionally gives every row its own Philox stream, so that a chain draws the same noise in
-    whatever batch / on whatever rank it is sampled (the sharded long-audio path).
+    whatever batch / on whatever rank it is sampled (the sharded long-audio path);
+  * the guidance scale is ``opt.cond_scale`` as in the reference (ignored for weights without ``classifier_free``), or the
+    loops' ``cond_scale=`` keyword (a float, or one value per batch row), which wins over ``opt``; either holds for the call only.
 """
 from __future__ import annotations
 
@@ -27,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .model import UniDiffuser
+from .model import UniDiffuser, normalize_guidance_scale
 
 _TABLES = ["betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_recip_alphas_cumprod",
            "sqrt_recipm1_alphas_cumprod", "posterior_variance", "posterior_log_variance_clipped",
@@ -126,7 +127,7 @@ class GaussianDiffusion:
                                  int(bool(getattr(o, "same_overlap_noisy", False))), int(clip_idx), float(eta))
 
     def _run(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0,
-             noise_source=None, seed=None, return_trace=False, row_keys=None):
+             noise_source=None, seed=None, return_trace=False, row_keys=None, cond_scale=None):
         if not isinstance(model, UniDiffuser):
             raise TypeError("model must be a diffsheg_amd.model.UniDiffuser (no generic-callable / CPU fallback)")
         if denoised_fn is not None or cond_fn is not None:
@@ -148,11 +149,20 @@ class GaussianDiffusion:
         if son and kind != 0:
             raise NotImplementedError("same_overlap_noisy only exists in the DDIM loop (gaussian_diffusion.py:1040-1060)")
         clip_idx = int(y.get("clip_idx", 0)) if son else 0
-        cs = getattr(self.opt, "cond_scale", None)
-        if cs is not None and float(cs) != float(model.cfg.cond_scale):
-            raise NotImplementedError(f"opt.cond_scale={cs} differs from the scale baked into the model handle "
-                                      f"({model.cfg.cond_scale}): build the UniDiffuser with get_config(..., cond_scale={cs})")
         B, T, Cc = (int(s) for s in shape)
+        # guidance scale (transformer.py:537, :586): the keyword wins over opt.cond_scale; without classifier-free weights the
+        # reference never reads opt.cond_scale, and an explicit scale other than 1 is an error
+        gs = normalize_guidance_scale(cond_scale)
+        if gs is None:
+            gs = normalize_guidance_scale(getattr(self.opt, "cond_scale", None))
+            if not model.cfg.classifier_free:
+                gs = None
+        elif not model.cfg.classifier_free:
+            if any(v != 1.0 for v in gs):
+                raise ValueError(f"cond_scale={list(gs)}: the weights are not classifier-free (no null_cond_emb), only 1 is possible")
+            gs = None
+        if gs is not None and len(gs) not in (1, B):
+            raise ValueError(f"cond_scale needs one value or one per batch row ({B}), got {len(gs)}")
         dev = model.device
         model._maybe_set_condition(model_kwargs["audio_emb"], model_kwargs["person_id"], model_kwargs.get("add_cond"))
         if (B, T) != (model.batch, model.frames) or Cc != model.cfg.net_dim_pose:
@@ -198,6 +208,10 @@ class GaussianDiffusion:
             raise ValueError(f"row_keys needs one key per batch row ({B}), got {len(row_keys)}")
         nk = 0 if (row_keys is None or noise_source is not None) else B
         karr = (C.c_uint64 * max(nk, 1))(*([int(k) & 0xFFFFFFFFFFFFFFFF for k in row_keys] if nk else [0]))
+        prev_gs = model.guidance_scale
+        set_gs = gs is not None and gs != prev_gs
+        if set_gs:
+            model.set_guidance_scale(gs)
         cur = model._enter()
         try:
             _lib.check(lib.dsh_sample_set_row_keys(model._h, karr, nk), "dsh_sample_set_row_keys")
@@ -212,6 +226,8 @@ class GaussianDiffusion:
                 raise
         finally:
             model._exit(cur)
+            if set_gs:                                   # (sticky in the context, like the keys: the model's own setting comes back)
+                model.set_guidance_scale(prev_gs)
         self._keep = (gt, mask, stack)          # consumed asynchronously on the stream
         if son:
             # gaussian_diffusion.py:1155-1157: the loop returns the dict of the last step plus the saved tails.  The tails live

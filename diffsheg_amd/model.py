@@ -12,7 +12,9 @@ for device memory and the stream handle.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Iterator, Optional
+import math
+import numbers
+from typing import Dict, Iterator, Optional, Tuple
 
 import torch
 
@@ -29,6 +31,34 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 def _dev_f32(t: torch.Tensor, device: torch.device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+def normalize_guidance_scale(scale) -> Optional[Tuple[float, ...]]:
+    """Guidance-scale argument -> ``None`` (the config's ``cond_scale``) or a tuple of float32-representable values: one value for the
+    whole batch (a float, a 0-d tensor / array) or one per batch row (a sequence, a 1-D tensor / array).  Raises ``ValueError`` on an
+    empty or multi-dimensional argument and on a non-finite value."""
+    if scale is None:
+        return None
+    if isinstance(scale, torch.Tensor):
+        scale = scale.detach().to("cpu", torch.float64)
+        vals = [float(scale)] if scale.dim() == 0 else (scale.tolist() if scale.dim() == 1 else None)
+    elif isinstance(scale, numbers.Real):
+        vals = [float(scale)]
+    elif hasattr(scale, "ndim") and getattr(scale, "ndim") == 0:        # numpy scalar / 0-d array
+        vals = [float(scale)]
+    else:
+        try:
+            vals = [float(v) for v in scale]
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"cond_scale must be a float or a sequence of floats, got {type(scale).__name__}") from e
+    if vals is None:
+        raise ValueError("cond_scale must be a scalar or one value per batch row (1-D)")
+    if not vals:
+        raise ValueError("cond_scale: empty sequence")
+    vals = torch.tensor(vals, dtype=torch.float64).to(torch.float32).tolist()      # (what the kernels will read)
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError(f"cond_scale must be finite (in float32), got {vals}")
+    return tuple(vals)
 
 
 class UniDiffuser:
@@ -59,6 +89,7 @@ class UniDiffuser:
         self._h = h
         self._cond_key = None
         self._cond_keep = None
+        self._guidance = None                  # set_guidance_scale(): None = the config's cond_scale
         self._dummy = torch.zeros(1, device=self.device)
         self.load_state_dict(state_dict)
 
@@ -153,6 +184,29 @@ class UniDiffuser:
                 or self._cond_key[1] != vers):
             self.set_condition(audio_emb, person_id, hub)
             self._cond_key = (src, vers)
+
+    # ---- classifier-free guidance ---------------------------------------------------------------
+    def set_guidance_scale(self, scale=None) -> None:
+        """Guidance scale of every following evaluation and sampling loop (sticky, like the reference's ``opt.cond_scale``, which
+        transformer.py:537 / :586 read on every forward): a float for the whole batch, a sequence / 1-D tensor of one value per batch
+        row, or ``None`` for the config's ``cond_scale``.  Per-row values must match the batch of the next call.  Weights without
+        ``classifier_free`` take only 1."""
+        vals = normalize_guidance_scale(scale)
+        if vals is not None and not self.cfg.classifier_free and any(v != 1.0 for v in vals):
+            raise ValueError(f"cond_scale={list(vals)}: the weights are not classifier-free (no null_cond_emb), only 1 is possible")
+        n = 0 if vals is None else len(vals)
+        arr = (C.c_float * max(n, 1))(*(vals or (1.0,)))
+        cur = self._enter()
+        try:
+            _lib.check(self._lib.dsh_set_guidance_scale(self._h, arr, n), "dsh_set_guidance_scale")
+        finally:
+            self._exit(cur)
+        self._guidance = vals
+
+    @property
+    def guidance_scale(self) -> Optional[Tuple[float, ...]]:
+        """The current setting: ``None`` (the config's ``cond_scale``) or the tuple given to :meth:`set_guidance_scale`."""
+        return self._guidance
 
     # ---- boundary 1 -----------------------------------------------------------------------------
     def __call__(self, x, timesteps, sqrt_alphas=None, audio_emb=None, length=None, person_id=None, add_cond=None,

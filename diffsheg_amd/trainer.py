@@ -8,6 +8,7 @@ Training, metrics, BVH/JSON writers, HuBERT extraction and checkpoint I/O are ou
 """
 from __future__ import annotations
 
+import numbers
 import os
 
 import argparse
@@ -82,9 +83,12 @@ class DDPMTrainer:
         self.diffusion_ddim_val = SpacedDiffusion(use_timesteps=space_timesteps(self.diffusion_steps, "ddim25"),
                                                   rescale_timesteps=False, **kw)
 
-    def generate_batch(self, audio_emb, p_id, dim_pose, add_cond={}, inpaint_dict=None, **sampler_kw):
+    def generate_batch(self, audio_emb, p_id, dim_pose, add_cond={}, inpaint_dict=None, cond_scale=None, **sampler_kw):
         """ddpm_show_trainer.py:163-198.  ``sampler_kw`` (noise_source= / seed=) is this build's
-        noise-injection hook; the reference draws from the global torch RNG."""
+        noise-injection hook; the reference draws from the global torch RNG.  ``cond_scale`` (a float, or one value per batch
+        row) overrides ``opt.cond_scale`` for this batch."""
+        if cond_scale is not None:
+            sampler_kw["cond_scale"] = cond_scale
         audio_emb = audio_emb.to(self.device)
         B, T = len(audio_emb), audio_emb.shape[1]
         cur_len = torch.full((B,), T, dtype=torch.long, device=self.device)
@@ -99,13 +103,15 @@ class DDPMTrainer:
     # ---- H2: arbitrary-length chain ---------------------------------------------------------
     def sample_arbitrary_len(self, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor],
                              noise_source_for_window=None, seed: Optional[int] = None,
-                             motions: Optional[torch.Tensor] = None, row_keys: Optional[Sequence[int]] = None) -> torch.Tensor:
+                             motions: Optional[torch.Tensor] = None, row_keys: Optional[Sequence[int]] = None,
+                             cond_scale=None) -> torch.Tensor:
         """The per-video body of test_arbitrary_len (ddpm_show_trainer.py:864-906): windows of n_poses
         with stride n_poses-overlap_len; window k>0 out-paints from the last overlap_len frames of
         window k-1 (sequential chain).  Output stays on the device (the reference copies every window
         to the host).  ``opt.fix_very_first`` (ddpm_show_trainer.py:885-888): window 0 is out-painted too, from the
         LAST overlap_len frames of the first ground-truth window of ``motions`` (standardised, [B, N, C]) — the
-        reference's indexing, kept as is.  Batch rows are independent chains of equal length."""
+        reference's indexing, kept as is.  Batch rows are independent chains of equal length.  ``cond_scale`` (a float, or one
+        value per chain) is the guidance scale of every window of the chains (default: ``opt.cond_scale``)."""
         opt = self.opt
         n_poses, L, C = int(opt.n_poses), int(opt.overlap_len), int(opt.net_dim_pose)
         step = n_poses - L
@@ -141,6 +147,8 @@ class DDPMTrainer:
                 kw["seed"] = window_seed(seed, ii)
             if row_keys is not None:
                 kw["row_keys"] = row_keys          # Philox: one stream per (window, chain): key = hash(seed, window), counter high words = chain id
+            if cond_scale is not None:
+                kw["cond_scale"] = cond_scale
             outputs = self.generate_batch(a, p_id, C, cnd, inpaint_dict, **kw)
             if son:
                 previous_noisy_tail, outputs = outputs["saved_noisy_tail"], outputs["sample"]
@@ -207,7 +215,8 @@ def broadcast_stream(t: Optional[torch.Tensor], device, src: int = 0, group=None
 
 def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[torch.Tensor], p_id: torch.Tensor,
                                  add_cond: Optional[Dict[str, torch.Tensor]], n_segments: int, seed: int = 0, group=None,
-                                 inputs_on_rank0_only: bool = False, max_chains_per_batch: int = 64) -> Optional[torch.Tensor]:
+                                 inputs_on_rank0_only: bool = False, max_chains_per_batch: int = 64,
+                                 cond_scale: Optional[float] = None) -> Optional[torch.Tensor]:
     """BASELINE config 4: one long feature stream ``[1, N, ...]`` sampled on all ranks of ``group``.
 
     Windows of ONE chain are sequential (window k needs the final sample of window k-1 at every denoising step,
@@ -217,8 +226,11 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
     Each rank owns a contiguous run of segments (:func:`shard_range`), samples equally long ones together as a batched
     chain (batch row = chain), and rank 0 gathers the frames (RCCL gather, 8.4 MB for 9000 frames).  There is no other
     collective on the data path.  Noise: on-device Philox, key = hash(seed, window index), counter high words = segment id, so every chain is
-    sampled identically whatever the world size or batching.  Returns ``[1, N, C]`` on rank 0, ``None`` elsewhere.
+    sampled identically whatever the world size or batching.  ``cond_scale``: one guidance scale for the whole stream (default:
+    ``opt.cond_scale``).  Returns ``[1, N, C]`` on rank 0, ``None`` elsewhere.
     """
+    if cond_scale is not None and not isinstance(cond_scale, numbers.Real):
+        raise ValueError("sample_arbitrary_len_sharded takes one scalar cond_scale for its stream")
     import torch.distributed as dist
     opt = trainer.opt
     n_poses, L, C = int(opt.n_poses), int(opt.overlap_len), int(opt.net_dim_pose)
@@ -246,7 +258,7 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
             chunk = ids[c0:c0 + max_chains_per_batch]
             a = torch.cat([audio_emb[:, segs[i].start:segs[i].stop] for i in chunk], 0)
             cnd = {k: torch.cat([v[:, segs[i].start:segs[i].stop] for i in chunk], 0) for k, v in add_cond.items()}
-            out = trainer.sample_arbitrary_len(a, pid[:1].expand(len(chunk), -1), cnd, seed=seed, row_keys=chunk)
+            out = trainer.sample_arbitrary_len(a, pid[:1].expand(len(chunk), -1), cnd, seed=seed, row_keys=chunk, cond_scale=cond_scale)
             for j, i in enumerate(chunk):
                 local[i] = out[j]
     loc = torch.cat([local[i] for i in mine], 0) if len(mine) else torch.zeros(0, C, device=dev)

@@ -42,7 +42,7 @@ typedef struct dsh_model_config {
     int32_t expression_dim;  /* expression channels (103 / 51)           */
     int32_t style_dim;       /* one-hot speaker width (4 / 30)           */
     int32_t classifier_free; /* model has null_cond_emb                  */
-    float   cond_scale;      /* CFG scale; != 1 doubles the batch inside */
+    float   cond_scale;      /* initial CFG scale (dsh_set_guidance_scale) */
     int32_t latent_dim;      /* 512  */
     int32_t ff_size;         /* 1024 */
     int32_t num_layers;      /* 8    */
@@ -108,7 +108,7 @@ int dsh_set_condition(dsh_ctx* ctx, int32_t batch, int32_t frames, const float* 
  * timesteps (what _WrappedModel passes); c1/c2 are sqrt(1/abar_t), sqrt(1/abar_t - 1) per sample
  * (gaussian_diffusion.py:527-532).  All device pointers; asynchronous on the context stream. */
 int dsh_eval(dsh_ctx* ctx, const float* x, const int64_t* t, const float* c1, const float* c2, float* eps);
-/* GEMM + attention flops actually launched by the last dsh_eval (work skipped is not counted). */
+/* GEMM + attention flops actually launched by the last dsh_eval (work skipped is not counted; a doubled CFG batch counts both halves). */
 double dsh_eval_flops(const dsh_ctx* ctx);
 /* Per-kernel-class HIP-event timing on the context stream (bench.py roofline leg).  enable=1 resets and
  * starts recording; dsh_profile_read synchronises and returns, per class, the summed milliseconds, launch
@@ -144,6 +144,14 @@ int dsh_sample(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t ini
  * whatever batch, stream split or rank it is sampled in (sharded test_arbitrary_len, ddpm_show_trainer.py:743-750:
  * the reference instead draws from each rank's global torch RNG).  Sticky until changed; frames*channels % 4 == 0. */
 int dsh_sample_set_row_keys(dsh_ctx* ctx, const uint64_t* keys_host, int32_t n);
+/* Classifier-free guidance scale of dsh_eval and dsh_sample (transformer.py:537, :586: eps = u + s_b (k - u) for clip b, in both motion
+ * encoders; the expression x0 the gesture encoder reads is built from the mixed expression eps).  Host array of n entries: n = 0 restores
+ * the config's cond_scale, n = 1 sets one value for the whole batch, n = B one value per clip (checked against the batch of
+ * dsh_set_condition when dsh_eval / dsh_sample run: -1 on a mismatch).  Sticky until changed; copied in stream order into a device
+ * buffer the context owns, which the kernels (and captured graphs) read when they run.  The null half is evaluated (the batch doubled)
+ * only when the weights are classifier_free and some scale != 1; a clip at exactly 1 inside a doubled batch returns k itself.  Mixed
+ * batches pay the full doubling.  -1 on a non-finite value, and on any value != 1 when the weights are not classifier_free. */
+int dsh_set_guidance_scale(dsh_ctx* ctx, const float* scales_host, int32_t n);
 
 /* ---- schedule / table introspection (host; parity tests for S1-S3) ---------------------------- */
 /* name in {betas, alphas_cumprod, alphas_cumprod_prev, sqrt_recip_alphas_cumprod,
