@@ -251,6 +251,14 @@ int dsh_sample_set_row_keys(dsh_ctx* ctx, const uint64_t* keys_host, int32_t n) 
     API_END
 }
 
+int dsh_sample_set_tail_blend(dsh_ctx* ctx, int32_t on) {
+    API_BEGIN
+    DSH_REQUIRE(ctx, "null context");
+    ctx->sampler->set_tail_blend(on);
+    return 0;
+    API_END
+}
+
 int dsh_set_guidance_scale(dsh_ctx* ctx, const float* scales_host, int32_t n) {
     API_BEGIN
     DSH_REQUIRE(ctx, "null context");
@@ -740,6 +748,25 @@ int dsh_inv_standardize(void* hip_stream, const float* x, int64_t n, int32_t cha
     API_BEGIN
     DSH_REQUIRE(x && y && mean && stdv && n >= 0 && channels > 0, "invalid argument");
     return dsh::launch_affine_cols(x, (size_t)n, channels, mean, stdv, y, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_ddim_step(void* hip_stream, float* x, const float* eps, const float* gt, const uint8_t* mask, const float* noise2,
+                     int32_t B, int32_t frames, int32_t channels, float c1, float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev,
+                     int32_t overlap_len, int32_t blend, int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi) {
+    API_BEGIN
+    DSH_REQUIRE(x && eps && B > 0 && frames > 0 && channels > 0, "invalid argument");
+    DSH_REQUIRE(!mask || (gt && noise2), "ddim_step: a mask needs gt and noise2");
+    DSH_REQUIRE(overlap_len >= 0 && overlap_len <= frames, "ddim_step: 0 <= overlap_len <= frames");
+    DSH_REQUIRE(!tail_blend || 2 * (int64_t)overlap_len <= frames, "ddim_step: tail_blend needs 2 * overlap_len <= frames");
+    DSH_REQUIRE(c_lo >= 0 && c_hi <= channels, "ddim_step: channel range outside [0, channels]");
+    dsh::DdimStepArgs a;
+    a.x = x; a.eps = eps; a.x0_out = nullptr; a.c1 = c1; a.c2 = c2; a.sqrt_ab_prev = sqrt_ab_prev; a.sqrt_1m_ab_prev = sqrt_1m_ab_prev;
+    a.coef_eps = sqrt_1m_ab_prev; a.sigma = 0.f; a.noise1 = nullptr;
+    a.mask = mask; a.gt = gt; a.noise2 = noise2; a.blend = (mask && blend) ? 1 : 0; a.tail_blend = (a.blend && tail_blend) ? 1 : 0;
+    a.clip = clip; a.overlap_len = overlap_len; a.frames = frames; a.channels = channels; a.n = (size_t)B * frames * channels;
+    a.tail_in = nullptr; a.tail_out = nullptr; a.c_lo = c_lo; a.c_hi = c_hi;
+    return dsh::launch_ddim_step(a, reinterpret_cast<hipStream_t>(hip_stream));
     API_END
 }
 

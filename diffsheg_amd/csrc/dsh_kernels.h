@@ -223,6 +223,7 @@ struct DdimStepArgs {
     const float* gt;       // [n]
     const float* noise2;   // [n] N(0,1) for the gt branch
     int blend;             // 1: linear cross-fade on the first overlap_len frames
+    int tail_blend = 0;    // 1 (with blend): the mirrored cross-fade on the last overlap_len frames (windows pinned at both ends; 2 overlap_len <= frames)
     int clip;              // clamp x0 to [-1,1] before re-deriving eps (clip_denoised)
     int overlap_len, frames, channels;
     size_t n;

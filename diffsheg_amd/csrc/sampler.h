@@ -37,6 +37,9 @@ class Sampler {
     // Philox mode: per-row keys (one per batch row; empty = one stream for the whole batch).  A chain keyed by its
     // global id draws the same noise whatever batch / rank it is sampled in (sharded long-audio path).
     int set_row_keys(const uint64_t* keys_host, int n);
+    // windows pinned at both ends (in-betweening / seam repair): the DDIM step's cross-fade also runs, mirrored, on the last
+    // overlap_len frames (sampler_kernels.hip).  Sticky like the row keys; 0 = the reference's head-only fade.
+    void set_tail_blend(int on) { tail_blend = on != 0; }
     int run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_from_x, const float* gt, const uint8_t* mask,
             bool masked, const float* noise_stack, int64_t n_draws, float* trace);
 
@@ -51,6 +54,7 @@ class Sampler {
     int64_t* tbuf = nullptr; int64_t* lvlbuf = nullptr;
     DiffusionTables tb; int tb_steps = -1, tb_resp = -1;
     uint64_t* row_keys = nullptr; int n_row_keys = 0, cap_row_keys = 0;
+    bool tail_blend = false;
     // --same_overlap_noisy: the noisy tail x[..., -L:, :] saved after every DDIM step, one slot per spaced level; persists
     // across sample() calls like the reference's self.saved_noisy_tail (the dict the next window receives IS this object)
     float* tails = nullptr; float* tail_tmp = nullptr; size_t tails_blc = 0; int tails_levels = 0;

@@ -18,6 +18,13 @@
 
 namespace dsh {
 
+// torch.linspace(0, 1, L)[k] in fp32: symmetric formula start + step*k / end - step*(L-1-k)
+__device__ __forceinline__ float linspace01(int L, int k) {
+    if (L == 1) return 0.f;
+    const float step = __fdiv_rn(1.0f, (float)(L - 1));
+    return (k < L / 2) ? __fmul_rn(step, (float)k) : __fsub_rn(1.0f, __fmul_rn(step, (float)(L - 1 - k)));
+}
+
 __global__ void ddim_step_kernel(DdimStepArgs a) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const int tc = a.frames * a.channels;
@@ -44,15 +51,14 @@ __global__ void ddim_step_kernel(DdimStepArgs a) {
                 g = t < a.overlap_len ? a.tail_in[(b * a.overlap_len + t) * a.channels + c] : a.gt[i];
             } else g = __fadd_rn(__fmul_rn(a.sqrt_ab_prev, a.gt[i]), __fmul_rn(a.sqrt_1m_ab_prev, a.noise2[i]));
             if (a.blend) {
-                if (t < a.overlap_len) {
-                    // torch.linspace(0, 1, L)[t] in fp32: symmetric formula start + step*t / end - step*(L-1-t)
-                    const int L = a.overlap_len;
-                    float w;
-                    if (L == 1) w = 0.f;
-                    else {
-                        const float step = __fdiv_rn(1.0f, (float)(L - 1));
-                        w = (t < L / 2) ? __fmul_rn(step, (float)t) : __fsub_rn(1.0f, __fmul_rn(step, (float)(L - 1 - t)));
-                    }
+                const int L = a.overlap_len;
+                if (t < L) {
+                    const float w = linspace01(L, t);
+                    g = __fadd_rn(__fmul_rn(g, __fsub_rn(1.0f, w)), __fmul_rn(s, w));
+                } else if (a.tail_blend && t >= a.frames - L) {
+                    // mirrored fade of a window pinned at both ends: the head's weights in reverse order (the same fp32 values),
+                    // w'[j] = linspace(0, 1, L)[L - 1 - j], j = t - (frames - L); disjoint from the head's frames (2 L <= frames)
+                    const float w = linspace01(L, L - 1 - (t - (a.frames - L)));
                     g = __fadd_rn(__fmul_rn(g, __fsub_rn(1.0f, w)), __fmul_rn(s, w));
                 }
             }

@@ -16,7 +16,9 @@ Differences a caller can observe, all loud:
     batch row) additionally gives every row its own Philox stream, so that a chain draws the same noise in
     whatever batch / on whatever rank it is sampled (the sharded long-audio path);
   * the guidance scale is ``opt.cond_scale`` as in the reference (ignored for weights without ``classifier_free``), or the
-    loops' ``cond_scale=`` keyword (a float, or one value per batch row), which wins over ``opt``; either holds for the call only.
+    loops' ``cond_scale=`` keyword (a float, or one value per batch row), which wins over ``opt``; either holds for the call only;
+  * ``ddim_sample_loop(..., tail_blend=True)`` mirrors the ``addBlend`` cross-fade onto the last ``overlap_len`` frames, for a mask
+    that pins both ends of a window (``DDPMTrainer.sample_inbetween``, seam repair); off by default.
 """
 from __future__ import annotations
 
@@ -127,7 +129,7 @@ class GaussianDiffusion:
                                  int(bool(getattr(o, "same_overlap_noisy", False))), int(clip_idx), float(eta))
 
     def _run(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0,
-             noise_source=None, seed=None, return_trace=False, row_keys=None, cond_scale=None):
+             noise_source=None, seed=None, return_trace=False, row_keys=None, cond_scale=None, tail_blend=False):
         if not isinstance(model, UniDiffuser):
             raise TypeError("model must be a diffsheg_amd.model.UniDiffuser (no generic-callable / CPU fallback)")
         if denoised_fn is not None or cond_fn is not None:
@@ -148,8 +150,16 @@ class GaussianDiffusion:
         son = bool(getattr(self.opt, "same_overlap_noisy", False))
         if son and kind != 0:
             raise NotImplementedError("same_overlap_noisy only exists in the DDIM loop (gaussian_diffusion.py:1040-1060)")
+        tail_blend = bool(tail_blend)
+        if tail_blend and kind != 0:
+            raise TypeError("tail_blend is an argument of the DDIM loops only")
+        if tail_blend and son:
+            raise NotImplementedError("tail_blend with same_overlap_noisy: the saved noisy tails describe a window chain, not a window "
+                                      "pinned at both ends")
         clip_idx = int(y.get("clip_idx", 0)) if son else 0
         B, T, Cc = (int(s) for s in shape)
+        if tail_blend and 2 * int(getattr(self.opt, "overlap_len", 0)) > T:
+            raise ValueError(f"tail_blend: the head and the tail fade overlap (2 * overlap_len = {2 * int(self.opt.overlap_len)} > {T} frames)")
         # guidance scale (transformer.py:537, :586): the keyword wins over opt.cond_scale; without classifier-free weights the
         # reference never reads opt.cond_scale, and an explicit scale other than 1 is an error
         gs = normalize_guidance_scale(cond_scale)
@@ -215,6 +225,8 @@ class GaussianDiffusion:
         cur = model._enter()
         try:
             _lib.check(lib.dsh_sample_set_row_keys(model._h, karr, nk), "dsh_sample_set_row_keys")
+            if tail_blend:
+                _lib.check(lib.dsh_sample_set_tail_blend(model._h, 1), "dsh_sample_set_tail_blend")
             try:
                 _lib.check(lib.dsh_sample(model._h, C.byref(opts), x.data_ptr(), int(init),
                                           None if gt is None else gt.data_ptr(), None if not masked else mask.data_ptr(),
@@ -224,6 +236,9 @@ class GaussianDiffusion:
                 if nk:                                   # the keys are sticky in the native context: do not leak them into the next call
                     lib.dsh_sample_set_row_keys(model._h, (C.c_uint64 * 1)(0), 0)
                 raise
+            finally:
+                if tail_blend:                           # sticky as well: the next call is the reference's head-only fade again
+                    lib.dsh_sample_set_tail_blend(model._h, 0)
         finally:
             model._exit(cur)
             if set_gs:                                   # (sticky in the context, like the keys: the model's own setting comes back)
@@ -251,7 +266,9 @@ class GaussianDiffusion:
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, **kw):
-        """gaussian_diffusion.py:1106-1159 (dispatches to the harmonize schedule when a mask is set)."""
+        """gaussian_diffusion.py:1106-1159 (dispatches to the harmonize schedule when a mask is set).  ``tail_blend=True`` (keyword,
+        not in the reference) adds the mirrored cross-fade on the last ``overlap_len`` frames, for masks that pin both ends of the
+        window (dsh_sample_set_tail_blend); the default is the reference's loop."""
         if not self._respacing:
             raise NotImplementedError("ddim_sample_loop needs a SpacedDiffusion('ddimK') (trainers use 'ddim25')")
         return self._run(0, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta, **kw)

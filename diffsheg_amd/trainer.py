@@ -156,8 +156,43 @@ class DDPMTrainer:
         return torch.cat(outs, dim=1)
 
 
+    # ---- motion in-betweening: one window pinned at both ends ---------------------------------
+    def sample_inbetween(self, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor],
+                         head: torch.Tensor, tail: torch.Tensor, *, tail_blend: bool = True, seed: Optional[int] = None,
+                         row_keys: Optional[Sequence[int]] = None, noise_source=None, cond_scale=None) -> torch.Tensor:
+        """"Here are two clips and the audio between them, fill the gap": ``audio_emb [B, T, 128]`` (+ ``add_cond``) conditions one
+        window, whose first ``L = opt.overlap_len`` frames are pinned to ``head`` and whose last ``L`` to ``tail`` (both ``[B, L, C]``,
+        standardised motion; ``2 L < T``); the frames in between are sampled.  This is the reference's own out-painting loop
+        (``ddim_sample_loop`` on a mask, gaussian_diffusion.py:1034-1056, RePaint schedule :1106-1159; ``jump_length``,
+        ``jump_n_sample``, ``no_resample``, ``no_repaint`` act as in a chained window) on a mask that is True at both ends.
+        With ``tail_blend=False`` it is exactly that loop: generated motion is cross-faded into the pinned frames on the head side
+        only (``addBlend``).  ``tail_blend=True`` (default) adds the mirrored fade on the last ``L`` frames.  Needs ``opt.ddim``
+        (mask-present DDPM is not built).  Returns the window ``[B, T, C]`` on the device; no host sync."""
+        opt = self.opt
+        L, C = int(opt.overlap_len), int(opt.net_dim_pose)
+        if not getattr(opt, "ddim", True):
+            raise NotImplementedError("sample_inbetween needs opt.ddim (mask-present DDPM sampling is not built)")
+        B, T = int(audio_emb.shape[0]), int(audio_emb.shape[1])
+        if L <= 0 or 2 * L >= T:
+            raise ValueError(f"sample_inbetween needs 0 < 2 * overlap_len < T (overlap_len = {L}, T = {T})")
+        if tuple(head.shape) != (B, L, C) or tuple(tail.shape) != (B, L, C):
+            raise ValueError(f"head / tail must be [B, overlap_len, C] = {(B, L, C)}, got {tuple(head.shape)} / {tuple(tail.shape)}")
+        gt = torch.zeros(B, T, C, device=self.device)
+        gt[:, :L] = head.to(self.device)
+        gt[:, T - L:] = tail.to(self.device)
+        mask = torch.zeros(B, T, C, dtype=torch.bool, device=self.device)
+        mask[:, :L] = True
+        mask[:, T - L:] = True
+        kw = {"tail_blend": bool(tail_blend)}
+        for k, v in (("seed", seed), ("row_keys", row_keys), ("noise_source", noise_source), ("cond_scale", cond_scale)):
+            if v is not None:
+                kw[k] = v
+        out = self.generate_batch(audio_emb, p_id, C, add_cond, {"gt": gt, "outpainting_mask": mask, "outpainting_mask_any": True}, **kw)
+        return out["sample"] if isinstance(out, dict) else out
+
     def sample_arbitrary_len_sharded(self, *args, **kw) -> Optional[torch.Tensor]:
-        """Long stream -> independent chains over the ranks -> gather on rank 0 (module-level function below)."""
+        """Long stream -> independent chains over the ranks -> gather on rank 0 -> optionally the seams between the chains
+        re-sampled as in-betweening windows (module-level function below)."""
         return sample_arbitrary_len_sharded(self, *args, **kw)
 
 
@@ -172,8 +207,9 @@ def shard_range(n_items: int, rank: int, world: int) -> range:
 
 def split_segments(n_frames: int, n_segments: int, n_poses: int, overlap_len: int) -> List[range]:
     """Cut a long feature stream into ``n_segments`` contiguous, independently-chained segments whose
-    lengths are whole numbers of window strides where possible.  Seams between segments are not
-    out-painted (each segment starts with an un-masked window), exactly like separate test videos."""
+    lengths are whole numbers of window strides where possible.  Each segment starts with an un-masked
+    window, exactly like separate test videos: the chains themselves do not out-paint across the seams
+    (``sample_arbitrary_len_sharded(seam_repair=True)`` closes them afterwards, :func:`seam_windows`)."""
     step = n_poses - overlap_len
     n_strides = max(1, (n_frames - overlap_len) // step) if n_frames > n_poses else 1
     n_segments = max(1, min(n_segments, n_strides))
@@ -184,6 +220,61 @@ def split_segments(n_frames: int, n_segments: int, n_poses: int, overlap_len: in
         segs.append(range(start, end))
         start = end
     return segs
+
+
+# Philox key of the seam windows: window_seed(seed, SEAM_WINDOW).  Chains use window indices 0, 1, 2, ... (one per n_poses - overlap_len
+# frames of a segment), so no chain of a stream shorter than 2^40 strides can reach this index.
+SEAM_WINDOW = 1 << 40
+
+
+def seam_windows(segs: Sequence[range], n_poses: int) -> List[range]:
+    """Seam ``s`` is the boundary ``p = segs[s + 1].start`` between segments ``s`` and ``s + 1``; its window is the ``n_poses`` frames
+    ``[p - n_poses // 2, p - n_poses // 2 + n_poses)``: first ``overlap_len`` frames from the left chain, last from the right."""
+    return [range(sg.start - n_poses // 2, sg.start - n_poses // 2 + n_poses) for sg in segs[1:]]
+
+
+def _seam_windows_fit(segs: Sequence[range], n_poses: int) -> bool:
+    wins = seam_windows(segs, n_poses)
+    if not wins:
+        return True
+    return wins[0].start >= segs[0].start and wins[-1].stop <= segs[-1].stop and all(a.stop <= b.start for a, b in zip(wins[:-1], wins[1:]))
+
+
+def split_segments_for_repair(n_frames: int, n_segments: int, n_poses: int, overlap_len: int) -> List[range]:
+    """:func:`split_segments`, with the segment count lowered until the seam windows are pairwise disjoint and inside the stream
+    (always true when every segment has at least ``n_poses`` frames; a one-stride segment has ``n_poses - overlap_len``).  The
+    result of :func:`split_segments` is returned unchanged whenever its seam windows already fit."""
+    while True:
+        segs = split_segments(n_frames, n_segments, n_poses, overlap_len)
+        if _seam_windows_fit(segs, n_poses):
+            return segs
+        n_segments = len(segs) - 1
+
+
+def _repair_seams(trainer: "DDPMTrainer", stream: torch.Tensor, offset: int, seams: Sequence[int], segs: Sequence[range],
+                  audio_emb: torch.Tensor, add_cond: Dict[str, torch.Tensor], pid: torch.Tensor, seed: int, max_rows: int,
+                  cond_scale, tail_blend: bool) -> None:
+    """Re-sample the windows of the seams ``seams`` (global indices) in place in ``stream [n, C]``, which holds frames
+    ``[offset, offset + n)`` of the whole stream: one batched in-betweening window per ``max_rows`` seams (row = seam), conditioning
+    and pinned frames gathered with one index tensor, result scattered back with the same one.  Key = (seed, SEAM_WINDOW), counter
+    high words = global seam index: a seam's noise does not depend on the rank or the batch it is sampled in."""
+    if not seams:
+        return
+    opt = trainer.opt
+    n_poses, L = int(opt.n_poses), int(opt.overlap_len)
+    wins = seam_windows(segs, n_poses)
+    dev = stream.device
+    key = window_seed(seed, SEAM_WINDOW)
+    for c0 in range(0, len(seams), max_rows):
+        chunk = list(seams[c0:c0 + max_rows])
+        idx = torch.tensor([wins[s].start for s in chunk], device=dev).unsqueeze(1) + torch.arange(n_poses, device=dev).unsqueeze(0)
+        a = audio_emb[0][idx.to(audio_emb.device)]                           # (conditioning may still live on the host: it is moved per window)
+        cnd = {k: v[0][idx.to(v.device)] for k, v in add_cond.items()}
+        loc = idx - offset
+        win = stream[loc]                                                   # [rows, n_poses, C]
+        out = trainer.sample_inbetween(a, pid[:1].expand(len(chunk), -1), cnd, win[:, :L], win[:, n_poses - L:], tail_blend=tail_blend,
+                                       seed=key, row_keys=chunk, cond_scale=cond_scale)
+        stream.index_copy_(0, loc.reshape(-1), out.reshape(-1, out.shape[-1]).to(stream.dtype))
 
 
 def _collectives_active(group=None) -> bool:
@@ -216,18 +307,34 @@ def broadcast_stream(t: Optional[torch.Tensor], device, src: int = 0, group=None
 def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[torch.Tensor], p_id: torch.Tensor,
                                  add_cond: Optional[Dict[str, torch.Tensor]], n_segments: int, seed: int = 0, group=None,
                                  inputs_on_rank0_only: bool = False, max_chains_per_batch: int = 64,
-                                 cond_scale: Optional[float] = None) -> Optional[torch.Tensor]:
+                                 cond_scale: Optional[float] = None, seam_repair: bool = False,
+                                 seam_tail_blend: bool = True) -> Optional[torch.Tensor]:
     """BASELINE config 4: one long feature stream ``[1, N, ...]`` sampled on all ranks of ``group``.
 
     Windows of ONE chain are sequential (window k needs the final sample of window k-1 at every denoising step,
     ddpm_show_trainer.py:891-893), so the stream is cut into ``n_segments`` independent chains
-    (:func:`split_segments`; seams are not out-painted, exactly like separate test videos, which is how the reference
-    itself parallelises: DistributedSampler over videos, one chain per rank, ddpm_show_trainer.py:743-750,924-931).
+    (:func:`split_segments`; every chain starts from an un-masked window, exactly like separate test videos, which is how the
+    reference itself parallelises: DistributedSampler over videos, one chain per rank, ddpm_show_trainer.py:743-750,924-931).
+    By default the returned stream therefore has a motion discontinuity at every segment boundary; ``seam_repair=True`` closes
+    them (below).
     Each rank owns a contiguous run of segments (:func:`shard_range`), samples equally long ones together as a batched
     chain (batch row = chain), and rank 0 gathers the frames (RCCL gather, 8.4 MB for 9000 frames).  There is no other
     collective on the data path.  Noise: on-device Philox, key = hash(seed, window index), counter high words = segment id, so every chain is
     sampled identically whatever the world size or batching.  ``cond_scale``: one guidance scale for the whole stream (default:
     ``opt.cond_scale``).  Returns ``[1, N, C]`` on rank 0, ``None`` elsewhere.
+
+    ``seam_repair=True`` (needs ``opt.ddim``, ``0 < 2 * overlap_len < n_poses``): after the chains, the ``n_poses`` frames around
+    every segment boundary (:func:`seam_windows`) are re-sampled as an in-betweening window (:meth:`DDPMTrainer.sample_inbetween`):
+    first ``overlap_len`` frames pinned to the left chain's output, last ``overlap_len`` to the right chain's, the frames in between
+    drawn from the stream's own conditioning of that window, the whole window written back.  ``seam_tail_blend`` is that call's
+    ``tail_blend``.  All seams of a rank are ONE batched window (chunked by ``max_chains_per_batch``).  Seam windows have to be
+    pairwise disjoint and inside the stream; the segment count is lowered until they are (:func:`split_segments_for_repair`: only
+    when some segment is shorter than ``n_poses`` frames, e.g. ``(9000, 256)`` or ``(400, 8)`` for SHOW), so the chains of a
+    repaired stream may differ from the default mode's for such counts.  A seam whose two segments live on the same rank is
+    repaired there before the gather (no new collective); the ``world - 1`` seams between ranks are repaired on rank 0 after it.
+    Noise: key = hash(seed, :data:`SEAM_WINDOW`), counter high words = global seam index; windows are disjoint, so the repaired
+    stream is the same whatever the world size, the rank that ran a seam, or the batching.  Frames outside the seam windows are
+    those of the default mode, bit for bit.
     """
     if cond_scale is not None and not isinstance(cond_scale, numbers.Real):
         raise ValueError("sample_arbitrary_len_sharded takes one scalar cond_scale for its stream")
@@ -246,7 +353,12 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
     if audio_emb.shape[0] != 1:
         raise ValueError("sample_arbitrary_len_sharded takes ONE stream [1, N, ...]; batch several streams by calling it per stream")
     N = int(audio_emb.shape[1])
-    segs = split_segments(N, n_segments, n_poses, L)
+    if seam_repair:
+        if not getattr(opt, "ddim", True) or L <= 0 or 2 * L >= n_poses:
+            raise ValueError("seam_repair needs opt.ddim and 0 < 2 * overlap_len < n_poses")
+        segs = split_segments_for_repair(N, n_segments, n_poses, L)
+    else:
+        segs = split_segments(N, n_segments, n_poses, L)
     mine = shard_range(len(segs), rank, world)
     pid = p_id if p_id.dim() == 2 else p_id.unsqueeze(0)
     by_len: Dict[int, List[int]] = {}
@@ -262,11 +374,21 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
             for j, i in enumerate(chunk):
                 local[i] = out[j]
     loc = torch.cat([local[i] for i in mine], 0) if len(mine) else torch.zeros(0, C, device=dev)
+    if seam_repair and len(mine) > 1:
+        # seams inside this rank's run of segments (seam s lies between segments s and s + 1)
+        _repair_seams(trainer, loc, segs[mine[0]].start, list(mine)[:-1], segs, audio_emb, add_cond, pid, seed, max_chains_per_batch,
+                      cond_scale, seam_tail_blend)
     sizes = [sum(len(segs[i]) for i in shard_range(len(segs), r, world)) for r in range(world)]
     parts = gather_outputs(loc, sizes, group)
     if parts is None:
         return None
-    return torch.cat(parts, 0).unsqueeze(0)
+    full = torch.cat(parts, 0)
+    if seam_repair and world > 1:
+        # seams between two ranks' runs: one more batch, on rank 0
+        last = [shard_range(len(segs), r, world) for r in range(world)]
+        between = [r[-1] for r in last if len(r) and r[-1] < len(segs) - 1]
+        _repair_seams(trainer, full, 0, between, segs, audio_emb, add_cond, pid, seed, max_chains_per_batch, cond_scale, seam_tail_blend)
+    return full.unsqueeze(0)
 
 
 def gather_outputs(local: torch.Tensor, world_sizes: Sequence[int], group=None) -> Optional[List[torch.Tensor]]:

@@ -144,6 +144,14 @@ int dsh_sample(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t ini
  * whatever batch, stream split or rank it is sampled in (sharded test_arbitrary_len, ddpm_show_trainer.py:743-750:
  * the reference instead draws from each rank's global torch RNG).  Sticky until changed; frames*channels % 4 == 0. */
 int dsh_sample_set_row_keys(dsh_ctx* ctx, const uint64_t* keys_host, int32_t n);
+/* Windows pinned at BOTH ends (motion in-betweening, seam repair of multi-chain streams): the reference cross-fades generated motion
+ * into the pinned frames on the first overlap_len frames only (addBlend, gaussian_diffusion.py:1051-1054).  on != 0 adds the mirror
+ * image on the last overlap_len frames of every DDIM step the head fade runs in (add_blend set, noise weight < 0.2):
+ *   g[t] = g[t] (1 - w'[j]) + s[t] w'[j],  j = t - (frames - L),  w'[j] = linspace(0, 1, L)[L - 1 - j]   (fp32, individually rounded)
+ * before the mask select, so the last pinned frame is kept exactly (weight 0) and the fade grows towards the re-sampled middle.
+ * on = 0 (the default) is the reference's loop, bit for bit.  Sticky until changed.  dsh_sample then returns -1 when
+ * 2 * overlap_len > frames, and with same_overlap_noisy (the saved noisy tails describe a window chain). */
+int dsh_sample_set_tail_blend(dsh_ctx* ctx, int32_t on);
 /* Classifier-free guidance scale of dsh_eval and dsh_sample (transformer.py:537, :586: eps = u + s_b (k - u) for clip b, in both motion
  * encoders; the expression x0 the gesture encoder reads is built from the mixed expression eps).  Host array of n entries: n = 0 restores
  * the config's cond_scale, n = 1 sets one value for the whole batch, n = B one value per clip (checked against the batch of
@@ -235,6 +243,13 @@ int dsh_op_linear_attention_bf16(void* hip_stream, const void* qkv, int32_t nb, 
 /* out = LayerNorm(x[M,D]) * gamma + beta */
 int dsh_op_layernorm(void* hip_stream, const float* x, int32_t M, int32_t D, const float* gamma, const float* beta,
                      float* out);
+/* one launch of the sampler's fused DDIM step (eta = 0) on caller-supplied device buffers [B, frames, channels]: x in/out, eps the
+ * model output; mask (bytes, null = no RePaint blend) with gt and noise2 (the N(0,1) of the noised gt); blend / tail_blend as
+ * dsh_sampler_opts.add_blend (at a faded step) / dsh_sample_set_tail_blend; [c_lo, c_hi) restricts the update to a channel
+ * range (0, 0 = all).  Asynchronous on hip_stream. */
+int dsh_op_ddim_step(void* hip_stream, float* x, const float* eps, const float* gt, const uint8_t* mask, const float* noise2,
+                     int32_t B, int32_t frames, int32_t channels, float c1, float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev,
+                     int32_t overlap_len, int32_t blend, int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi);
 /* standard normals from the on-device Philox generator */
 int dsh_op_philox_randn(void* hip_stream, float* out, int64_t n, uint64_t seed, uint64_t offset);
 /* the per-row streams dsh_sample draws from after dsh_sample_set_row_keys: out[rows, n_row] (device), row b = key `seed`,
