@@ -69,6 +69,7 @@ SYMBOLS = {
     "dsh_op_gemm": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "dsh_op_gemm_f32_pro": (C.c_int, [_P, C.c_int32] + [_P, C.c_int32, C.c_int32] * 4 + [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     "dsh_debug_last_tl_variant": (C.c_int32, []),
+    "dsh_debug_launch_counts": (C.c_int32, [C.POINTER(C.c_int64), C.c_int32, C.c_int32]),
     "dsh_op_tl_linear": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     "dsh_op_tl2_ffn": (C.c_int, [_P] * 12 + [C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32]),
     "dsh_op_cross_attention": (C.c_int, [_P, C.POINTER(CrossAttnWeightsC), _P, _P, _P] + [C.c_int32] * 7 + [_P]),
@@ -79,6 +80,20 @@ SYMBOLS = {
     "dsh_op_philox_randn": (C.c_int, [_P, _P, C.c_int64, C.c_uint64, C.c_uint64]),
     "dsh_op_philox_randn_rows": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
+
+# index -> name of the entries of dsh_debug_launch_counts (include/diffsheg_hip.h); the last four are values, not counts
+LAUNCH_FAMILIES = ("tl1", "tl2_loop", "tl2_roll", "tl2_roll_hl", "tl4", "tls", "ffn_fused", "ffn_fused_sty", "attn_mfma", "attn_rowmajor",
+                   "gemm_f32_fewrow", "gemm_f32_tiled", "gemm_f32_pro", "eval_streams", "sample_streams", "sample_graph", "sample_pipe")
+
+
+def launch_counts(reset: bool = False) -> dict:
+    """Test helper: launches per kernel family since the last reset (host-side counters of the library), by name."""
+    arr = (C.c_int64 * len(LAUNCH_FAMILIES))()
+    n = lib().dsh_debug_launch_counts(arr, len(LAUNCH_FAMILIES), int(reset))
+    if n != len(LAUNCH_FAMILIES):
+        raise DshError(f"dsh_debug_launch_counts reports {n} entries, this binding knows {len(LAUNCH_FAMILIES)}")
+    return dict(zip(LAUNCH_FAMILIES, arr))
+
 
 _lib = None
 

@@ -73,6 +73,8 @@ static int check_guidance(const dsh_ctx* ctx) {
     return 0;
 }
 
+namespace dsh { std::atomic<long long> g_launch_counts[LC_COUNT]; }
+
 #define API_BEGIN try {
 #define API_END                                                                       \
     } catch (const std::exception& e) {                                               \
@@ -356,6 +358,14 @@ int dsh_op_gemm_f32_pro(void* hip_stream, int32_t pro, const float* x0, int32_t 
 }
 
 int32_t dsh_debug_last_tl_variant(void) { return dsh::g_tl_last_variant; }
+
+int32_t dsh_debug_launch_counts(int64_t* out, int32_t cap, int32_t reset) {
+    for (int i = 0; i < dsh::LC_COUNT; ++i) {
+        const long long v = reset ? dsh::g_launch_counts[i].exchange(0, std::memory_order_relaxed) : dsh::g_launch_counts[i].load(std::memory_order_relaxed);
+        if (out && i < cap) out[i] = (int64_t)v;
+    }
+    return dsh::LC_COUNT;
+}
 
 int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W, const float* bias, const float* R,
                      float* Cf, void* Ct, int32_t M, int32_t N, int32_t act, const float* gamma, const float* beta,

@@ -41,6 +41,9 @@ class DenoiserBase {
     virtual int set_condition(int B, int T, const float* audio, const float* person_id, const float* hubert) = 0;
     // eps[B,T,C] = model(x[B,T,C], t[B]) with c1/c2 [B] (device fp32) feeding the expression x0
     virtual int eval(const float* x, const int64_t* t, const float* c1, const float* c2, float* eps) = 0;
+    // 0 if a batch of B clips of T frames can be evaluated, else -1 with the limit in the error text.  set_condition() asks before it
+    // touches any state or queues any launch, so a refused shape leaves the context exactly as it was.
+    virtual int check_shape(int /*B*/, int /*T*/) const { return 0; }
     // Timestep-level cache.  In every sampling loop all rows of an evaluation share one timestep, and part of an evaluation
     // does not depend on x at all: the time / speaker / FiLM embeddings, encoder_aud and audio_proj are functions of
     // (condition, t) only (transformer.py:730-739, :555-559, :574).  Loops that revisit levels (the out-painting jump schedule:

@@ -94,6 +94,18 @@ class Denoiser final : public DenoiserBase {
     int eval(const float* x, const int64_t* t, const float* c1, const float* c2, float* eps) override {
         return eval_level(x, t, c1, c2, eps, 0, nullptr);
     }
+    // bf16 token-per-lane path: the StylizationBlock launches stage the FiLM rows of every clip a token block touches — at most 4 clips per
+    // 32-token block (tl_small.hip) or 6 per 128-token block (tl_linear.hip).  Windows of 11 frames and more fit one of the two at any batch,
+    // shorter ones up to 6 clips; 7 and more clips of 10 frames or fewer fit neither.  (fp32 has no such limit: gemm_f32_pro.hip reads the
+    // FiLM row of each token's clip from memory.)
+    int check_shape(int B, int T_) const override {
+        if (!tl_path() || B <= 0 || T_ <= 0) return 0;
+        if ((tls_on && tls_film_clips_ok(T_, B)) || tl_linear_film_clips_ok(T_, B)) return 0;
+        set_last_error("unsupported shape: the bf16 path evaluates windows of " + std::to_string(T_) + " frames in batches of at most 6 clips (got " +
+                       std::to_string(B) + "); batches of 7 and more clips need windows of at least " + (tls_on ? "11" : "26") +
+                       " frames (FiLM rows staged per token block) - split the batch, or use the fp32 path");
+        return -1;
+    }
     int level_cache_prepare(int n_levels) override;
     int set_condition_light(int B, int T_, const float* audio, const float* person_id) override;
     int set_part(int p) override {
@@ -416,7 +428,11 @@ class Denoiser final : public DenoiserBase {
             else if (L.Kp == 512) tls_limit = 6144;
             else tls_limit = Rlo ? 3072 : 4096;
         }
-        if (tls_on && L.wf && M <= tls_limit && (pro == 0 || pro == 2 || (L.fd && L.fc))) {
+        // A StylizationBlock launch the first-generation kernel cannot take (more than six clips per 128-token block: clips shorter than 26
+        // frames at batch >= 7) stays on the window-chain kernels beyond their row limit wherever those can stage its FiLM rows (clips of 11
+        // frames and more): slower than a whole-chip kernel, but it exists.  What neither family covers is refused up front by check_shape().
+        const bool tl1_ok = pro != 2 || tl_linear_film_clips_ok(fr > 0 ? fr : 1, bmod > 0 ? bmod : 1);
+        if (tls_on && L.wf && (M <= tls_limit || !tl1_ok) && (pro == 0 || pro == 2 || (L.fd && L.fc))) {
             TlArgs b = a;
             b.W = L.wf;
             if (pro == 1 || pro == 3) { b.bias = L.fd; b.row_const = L.fc; }
@@ -836,6 +852,7 @@ int Denoiser<T>::set_condition_light(int B, int T_, const float* audio, const fl
     DSH_REQUIRE(finalized, "weights not finalized");
     DSH_REQUIRE(B > 0 && T_ > 0, "batch and frames must be positive");
     DSH_REQUIRE(audio && person_id, "null conditioning pointer");
+    if (int e = check_shape(B, T_)) return e;
     if (int e = ensure_workspace(B, T_)) return e;
     batch = B; frames = T_;
     lvl_n = 0;                               // cached x-independent results belong to the previous condition
@@ -1064,10 +1081,14 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
             if (prof) prof->begin(PROF_ATTN);
             if (dbg_skip & 8) {
             } else if (fr <= 96) {
+                count_launch(LC_ATTN_MFMA);
                 if (int e = launch_linear_attention_tiled(qkv, nb, B, r0, fr, D, y, st, M >= 4096 ? next_rev() : 0)) return e;
             } else {
                 // windows longer than the MFMA kernel's 96-frame tile (non-default n_poses): row-major VALU kernel
                 // between two layout conversions per CFG half
+                // (its row-major scratch exists only for windows of more than 96 frames, ensure_workspace: the two limits move together or not at all)
+                DSH_REQUIRE(qkv_rm && y_rm, "row-major attention fallback without its scratch buffers (allocated for windows of more than 96 frames)");
+                count_launch(LC_ATTN_ROWMAJOR);
                 for (int hf = 0; hf <= has_null; ++hf) {
                     const size_t ro = hf ? (size_t)r0 : 0, rm = (size_t)hf * Mc;
                     if (int e = launch_untile_rows_bf16(qkv + ro * 3 * D, 3 * D, Mc, 3 * D, qkv_rm + rm * 3 * D, 3 * D, st)) return e;
@@ -1342,6 +1363,7 @@ class DualDenoiser final : public DenoiserBase {
     int finalize(const std::map<std::string, HostTensor>& w) override { return inst_[0]->finalize(w); }
     int set_condition(int B, int T, const float* audio, const float* person_id, const float* hubert) override {
         DSH_REQUIRE(B > 0 && T > 0 && audio && person_id && hubert, "set_condition: null conditioning pointer / empty batch");
+        if (int e = inst_[0]->check_shape(B, T)) return e;          // (before any state changes: a refused shape leaves the previous condition usable)
         // The split (one stream vs sub-batches on several) may change between evals (profiler on/off), which re-runs the
         // per-instance set_condition: the conditioning is therefore copied into context-owned buffers, so the caller's
         // tensors only need to stay valid until this call's work on the context stream has been enqueued (stream order).
@@ -1373,6 +1395,7 @@ class DualDenoiser final : public DenoiserBase {
         const int ns = (loop_unsplit_ && split_now_ == 1) ? 1 : want_split(cond_.B, cond_.T);
         if (ns != split_now_) { if (int e = apply_condition(ns)) return e; }   // e.g. the profiler was switched on in between
         for (auto& in : inst_) in->t_uniform = t_uniform;
+        note_launch_value(LC_EVAL_STREAMS, ns);
         if (ns == 1) return inst_[0]->eval(x, t, c1, c2, eps);
         const int C = cfg_.channels();
         DSH_HIP_CHECK(hipEventRecord(ev_fork_, st_));

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include <string>
 
 namespace dsh {
@@ -77,6 +78,33 @@ const char* last_error_cstr();
             return -1;                                                                          \
         }                                                                                       \
     } while (0)
+
+// ---- test helper (dsh_debug_launch_counts, capi.hip): launches per kernel family --------------
+// Host-side relaxed counters, bumped by the host launchers next to the launch they issue; no kernel and no launch argument knows
+// about them.  The indices are part of the C ABI (include/diffsheg_hip.h): append, never renumber.
+enum LaunchFamily {
+    LC_TL1 = 0,            // first-generation token-per-lane Linear (tl_linear.hip)
+    LC_TL2_LOOP,           // tl2 round-2 loop (also its out-of-phase-epilogue form)
+    LC_TL2_ROLL,           // tl2 rolling loop
+    LC_TL2_ROLL_HL,        // tl2 rolling loop on hi / lo residual planes
+    LC_TL4,                // tl4 LDS-tiled Linear
+    LC_TLS,                // window-chain 32-token kernels (tl_small.hip)
+    LC_FFN_FUSED,          // fused FFN launch (tl3_ffn / tl2_ffn), every form
+    LC_FFN_FUSED_STY,      // ... of which with the attention branch's StylizationBlock as first stage
+    LC_ATTN_MFMA,          // bf16 layers: MFMA tiled attention
+    LC_ATTN_ROWMAJOR,      // bf16 layers: row-major attention between two layout conversions (windows of more than 96 frames)
+    LC_GEMM_F32_FEWROW,    // fp32 K-split GEMM for a few hundred rows (gemm.hip)
+    LC_GEMM_F32_TILED,     // fp32 tiled GEMM (gemm.hip)
+    LC_GEMM_F32_PRO,       // fp32 Linear with its front / software-pipelined main loop (gemm_f32_pro.hip)
+    LC_EVAL_STREAMS,       // (value, not a count) sub-batch streams of the last dsh_eval
+    LC_SAMPLE_STREAMS,     // (value) sub-batch streams of the last dsh_sample
+    LC_SAMPLE_GRAPH,       // (value) 1 if the last dsh_sample replayed captured graphs
+    LC_SAMPLE_PIPE,        // (value) 1 if the last dsh_sample ran the two-encoder pipeline
+    LC_COUNT
+};
+extern std::atomic<long long> g_launch_counts[LC_COUNT];
+inline void count_launch(int family) { g_launch_counts[family].fetch_add(1, std::memory_order_relaxed); }
+inline void note_launch_value(int index, long long v) { g_launch_counts[index].store(v, std::memory_order_relaxed); }
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline int round_up(int a, int b) { return ceil_div(a, b) * b; }

@@ -90,10 +90,15 @@ struct TlArgs {
 };
 // pro: 0 = plain rows, 1 = LayerNorm, 2 = LayerNorm -> FiLM -> SiLU (StylizationBlock), 3 = concat + LayerNorm (feat_proj.0)
 int launch_tl_linear(const TlArgs& a, int pro, hipStream_t s);
+// the FiLM prologue (pro 2) of launch_tl_linear stages the folded rows of at most TL_MAXCLIP = 6 clips per 128-token block: true when a
+// launch over `bmod` clips of `frames` frames stays within that (clips of 26 frames and more at any batch, shorter ones up to 6 clips)
+bool tl_linear_film_clips_ok(int frames, int bmod);
 // window-chain batches (tl_small.hip): 32 tokens per block, one tile per wave, weights straight from the fragment-ordered copy
 // (a.W as for launch_tl2_linear; pro 1 / 3: a.bias = d, a.row_const = c of the folded LayerNorm).  Rows = frames * bmod, or two
 // CFG halves of that many rows with the second one starting at row M - frames * bmod.
 bool tls_linear_supported(const TlArgs& a, int pro);
+// their FiLM prologue (pro 2) stages at most TLS_MAXCLIP = 4 clips per 32-token block: clips of 11 frames and more at any batch, shorter ones up to 4 clips
+bool tls_film_clips_ok(int frames, int bmod);
 int launch_tls_linear(const TlArgs& a, int pro, hipStream_t s);
 int tl_weight_src_row(int r);
 // device-side application of the same row permutation to a bf16 [N, K] weight (test / bench helper of capi.hip)

@@ -531,6 +531,7 @@ static int launch_gemm_t(const GemmArgs& a, hipStream_t s) {
                 DSH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_ksplit_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, KS_LDS));
                 ks_attr = true;
             }
+            count_launch(LC_GEMM_F32_FEWROW);
             hipLaunchKernelGGL((gemm_nt_ksplit_kernel<T>), dim3(ceil_div(a.N, 32), ceil_div(a.M, 32)), dim3(64 * KS_NW), KS_LDS, s, a);
             DSH_HIP_CHECK(hipGetLastError());
             return 0;
@@ -574,6 +575,7 @@ static int launch_gemm_t(const GemmArgs& a, hipStream_t s) {
     GemmArgs b = a;
     b.nt_n = ceil_div(a.N, sh.bn);
     b.nt_m = ceil_div(a.M, sh.bm);
+    if (sizeof(T) == 4) count_launch(LC_GEMM_F32_TILED);
     if (variant == 0) {
         hipLaunchKernelGGL((gemm_nt_kernel<T, 0, 2, 2>), dim3(b.nt_n, b.nt_m), dim3(256), gemm_lds_bytes(2, 2), s, b);
     } else {

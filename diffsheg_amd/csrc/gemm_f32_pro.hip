@@ -796,6 +796,7 @@ int launch_gemm_f32_pro(const GemmProArgs& a, hipStream_t s) {
     //  pass costs 9.5 us with 128 instead of 256 threads, and their VALU work costs the MFMA waves of the same SIMD as much as it did inside
     //  their own instruction streams, 61.9 vs 50.0 us without a front.  Off unless DSH_GP_WS=1.)
     static const int ws_on = [] { const char* e = getenv("DSH_GP_WS"); return e ? atoi(e) : 0; }();
+    count_launch(LC_GEMM_F32_PRO);
     if (a.pro == 2 && dma && ws_on && !a.stats && !a.stats_out) {
         static bool ws_attr = false;
         if (!ws_attr) { DSH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_sty_ws_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, GP_LDS)); ws_attr = true; }

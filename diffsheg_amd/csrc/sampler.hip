@@ -258,6 +258,9 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
     DSH_REQUIRE(!(tail_blend && o.same_overlap_noisy), "tail_blend with same_overlap_noisy: the saved noisy tails describe a window chain, not a window pinned at both ends");
     DSH_REQUIRE(!tail_blend || (o.overlap_len >= 0 && 2 * (int64_t)o.overlap_len <= den->frames), "tail_blend: the head and the tail fade overlap (2 * overlap_len > frames)");
     const int B = den->batch;
+    // loop_begin() marks the batch as deliberately unsplit; the mark is taken back on EVERY way out of this function (an argument error or a
+    // failed launch below must not leave the context answering later evaluations as if a loop were still running)
+    struct LoopScope { DenoiserBase* d; ~LoopScope() { (void)d->loop_end(); } } loop_scope{den};
     if (int e = den->loop_begin(o.kind)) return e;          // (may re-condition a mid-size batch as one batch: the two encoder chains replace the sub-batch streams)
     den->t_uniform = emb_dedup_enabled();   // every evaluation of a sampling loop runs the whole batch at ONE timestep (launch_fill_step below)
     const size_t n = (size_t)B * den->frames * channels;
@@ -599,13 +602,16 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
     return 0;
     };
     const int rc = loop();
+    note_launch_value(LC_SAMPLE_STREAMS, (long long)subs.size());
+    note_launch_value(LC_SAMPLE_GRAPH, (graph_exec[0] || graph_exec[1] || graph_exec[2]) ? 1 : 0);
+    note_launch_value(LC_SAMPLE_PIPE, pipe ? 1 : 0);
     if (pipe) {
-        // the gesture chain joins the context stream on every exit path; both instances go back to whole evaluations
+        // both instances go back to whole evaluations (host state: before anything that can fail), and the gesture chain joins the context
+        // stream on every exit path
+        (void)den->pipe_end();
         DSH_HIP_CHECK(hipEventRecord(ev_pG, sG));
         DSH_HIP_CHECK(hipStreamWaitEvent(st, ev_pG, 0));
-        (void)den->pipe_end();
     }
-    (void)den->loop_end();
     if (split)
         for (size_t i = 1; i < subs.size(); ++i) {
             DSH_HIP_CHECK(hipEventRecord(ev_sub[2 * i + 1], subs[i].s));

@@ -1258,6 +1258,7 @@ int launch_tl2_linear(const TlArgs& a, int pro, hipStream_t s) {
         variant = 2;
     }
     g_tl_last_variant = variant;
+    count_launch(variant == 1 ? LC_TL2_ROLL : variant == 2 ? LC_TL2_ROLL_HL : LC_TL2_LOOP);
     hipLaunchKernelGGL(fn, grid, block, lds, s, b);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
@@ -1283,6 +1284,7 @@ int launch_tl2_ffn(const Tl2FfnArgs& a, hipStream_t s) {
     }
     Tl2FfnArgs b = a;
     tl_stagger_config(0, &b.stag_groups, &b.stag_sleep);
+    count_launch(LC_FFN_FUSED);
     if (a.clk) hipLaunchKernelGGL(tl2_ffn_kernel<true>, dim3(ceil_div(a.M, TL_TOK)), dim3(256), FFN_LDS, s, b);
     else hipLaunchKernelGGL(tl2_ffn_kernel<false>, dim3(ceil_div(a.M, TL_TOK)), dim3(256), FFN_LDS, s, b);
     DSH_HIP_CHECK(hipGetLastError());

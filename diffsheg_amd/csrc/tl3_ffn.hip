@@ -924,6 +924,8 @@ int launch_tl3_ffn(const Tl2FfnArgs& a, hipStream_t s) {
     Tl2FfnArgs b = a;
     tl_stagger_config(0, &b.stag_groups, &b.stag_sleep);
     const dim3 grid(ceil_div(a.M, TL_TOK)), block(256);
+    count_launch(LC_FFN_FUSED);
+    if (a.Y) count_launch(LC_FFN_FUSED_STY);
 #define F3_LAUNCH(PB, HLV) do { if (pc == 2) hipLaunchKernelGGL((tl3_ffn_kernel<PB, HLV, 2>), grid, block, F3_LDS, s, b); \
                                 else if (pc == 1) hipLaunchKernelGGL((tl3_ffn_kernel<PB, HLV, 1>), grid, block, F3_LDS, s, b); \
                                 else hipLaunchKernelGGL((tl3_ffn_kernel<PB, HLV, 0>), grid, block, F3_LDS, s, b); } while (0)

@@ -400,6 +400,7 @@ int launch_tl4_linear(const TlArgs& a, int pro, hipStream_t s) {
     DSH_REQUIRE(b.nstages >= 4, "tl4_linear: K too small for the stage ring");
     const int v = tl4_variant();
     g_tl_last_variant = v == 0 ? 4 : 5;
+    count_launch(LC_TL4);
     return launch_variant(v, b, mode, a.M, s);
 }
 

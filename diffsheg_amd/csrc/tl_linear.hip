@@ -366,6 +366,8 @@ __global__ __launch_bounds__(256, (KD == 512 ? 2 : 1)) void tl_linear_kernel(TlA
     }
 }
 
+bool tl_linear_film_clips_ok(int frames, int bmod) { return frames > 0 && bmod > 0 && std::min((TL_TOK - 1) / frames + 2, bmod) <= TL_MAXCLIP; }
+
 int launch_tl_linear(const TlArgs& a, int pro, hipStream_t s) {
     g_tl_last_variant = 10;
     DSH_REQUIRE(a.M > 0 && a.N > 0 && a.N % 32 == 0, "tl_linear: N must be a positive multiple of 32");
@@ -379,7 +381,7 @@ int launch_tl_linear(const TlArgs& a, int pro, hipStream_t s) {
     // launch holds few clips (the B = 1 window chain and its tail windows), long clips at any batch
     DSH_REQUIRE(pro != 2 || (a.film && a.frames > 0 && a.bmod > 0 && a.film_ld % 4 == 0 && a.film_off % 4 == 0),
                 "tl_linear: FiLM prologue needs the folded film table");
-    DSH_REQUIRE(pro != 2 || std::min((TL_TOK - 1) / a.frames + 2, a.bmod) <= TL_MAXCLIP,
+    DSH_REQUIRE(pro != 2 || tl_linear_film_clips_ok(a.frames, a.bmod),
                 "tl_linear: FiLM prologue: too many clips per 128-token block (clips shorter than 26 frames need batch <= 6)");
     DSH_REQUIRE(pro != 2 || a.K == 512, "tl_linear: FiLM prologue is instantiated for K = 512");
     // N is split over grid.y only when the token blocks alone cannot fill the chip (window-chain batches)
@@ -453,6 +455,7 @@ int launch_tl_linear(const TlArgs& a, int pro, hipStream_t s) {
         }
     }
     DSH_REQUIRE(fn != nullptr, "tl_linear: this (prologue, residual, outputs, activation) combination is not instantiated");
+    count_launch(LC_TL1);
     hipLaunchKernelGGL(fn, grid, block, lds, s, b);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;

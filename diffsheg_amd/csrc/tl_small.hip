@@ -279,13 +279,15 @@ tls_kern_t tls_pick(const TlArgs& a, int pro) {
 }  // namespace
 
 // a.W must be the FRAGMENT-ORDERED weight (tl2_frag_index); pro 1 / 3: a.bias = d, a.row_const = c of the folded LayerNorm
+bool tls_film_clips_ok(int frames, int bmod) { return frames > 0 && bmod > 0 && std::min(31 / frames + 2, bmod) <= TLS_MAXCLIP; }
+
 bool tls_linear_supported(const TlArgs& a, int pro) {
     if (a.M <= 0 || a.N <= 0 || a.N % 128 != 0 || !a.bias || !a.X || !a.W) return false;
     if (a.frames <= 0 || a.bmod <= 0) return false;
     const int Mc = a.frames * a.bmod;
     if (a.M != Mc && !(a.M > Mc && (a.M - Mc) % 32 == 0 && a.M - Mc >= Mc)) return false;    // one range of rows, or two CFG halves
     if ((pro == 1 || pro == 3) && !a.row_const) return false;
-    if (pro == 2 && !(a.film && a.film_ld % 4 == 0 && a.film_off % 4 == 0 && std::min(31 / a.frames + 2, a.bmod) <= TLS_MAXCLIP)) return false;
+    if (pro == 2 && !(a.film && a.film_ld % 4 == 0 && a.film_off % 4 == 0 && tls_film_clips_ok(a.frames, a.bmod))) return false;
     if (pro == 3 && !(a.X1 && a.X2 && a.kreal > 896 - 1 && a.kreal <= 1024)) return false;
     return tls_pick(a, pro) != nullptr;
 }
@@ -310,6 +312,7 @@ int launch_tls_linear(const TlArgs& a, int pro, hipStream_t s) {
     b.tls_tb1 = a.M > Mc ? (a.M - Mc) / 32 : 0;
     const int nblocks = a.M > Mc ? 2 * nbh : nbh;
     const int lds = (a.K / 16) * 1024 + (pro == 2 ? TLS_MAXCLIP * 4096 : 0);
+    count_launch(LC_TLS);
     hipLaunchKernelGGL(fn, dim3(nblocks, a.N / 128), dim3(256), lds, s, b);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;

@@ -165,9 +165,11 @@ class UniDiffuser:
             raise ValueError(f"person_id must be [B,{self.cfg.style_dim}]")
         a, p, hb = (_dev_f32(t, self.device) for t in (audio_emb, person_id, hubert))
         cur = self._enter()
-        _lib.check(self._lib.dsh_set_condition(self._h, B, T, a.data_ptr(), p.data_ptr(), hb.data_ptr()),
-                   "dsh_set_condition")
-        self._exit(cur)
+        try:
+            _lib.check(self._lib.dsh_set_condition(self._h, B, T, a.data_ptr(), p.data_ptr(), hb.data_ptr()),
+                       "dsh_set_condition")
+        finally:
+            self._exit(cur)                    # (also when the call is refused: the caller's stream stays ordered after the context's)
         self._cond_keep = (a, p, hb)           # (the library copies them in stream order; kept for the allocator's sake)
         self.batch, self.frames = B, T
 
@@ -229,9 +231,11 @@ class UniDiffuser:
         c2 = _dev_f32(sqrt_alphas[1].reshape(B, -1)[:, 0], self.device)
         out = torch.empty_like(xd)
         cur = self._enter()
-        _lib.check(self._lib.dsh_eval(self._h, xd.data_ptr(), td.data_ptr(), c1.data_ptr(), c2.data_ptr(),
-                                      out.data_ptr()), "dsh_eval")
-        self._exit(cur)
+        try:
+            _lib.check(self._lib.dsh_eval(self._h, xd.data_ptr(), td.data_ptr(), c1.data_ptr(), c2.data_ptr(),
+                                          out.data_ptr()), "dsh_eval")
+        finally:
+            self._exit(cur)
         return out
 
     # ---- introspection -----------------------------------------------------------------------------

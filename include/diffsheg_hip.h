@@ -101,7 +101,14 @@ int64_t dsh_weight_bytes(const dsh_ctx* ctx);
  * Runs hubert_encoder and pid_embed once; must be called before dsh_eval / dsh_sample and again
  * whenever the conditioning or (B,T) changes.  The three tensors are copied into context-owned
  * buffers in stream order: they may be freed / overwritten as soon as the call has returned,
- * provided that happens on (or is ordered after) the context stream. */
+ * provided that happens on (or is ordered after) the context stream.
+ * Shape limit (bf16 precision only): windows of 10 frames or fewer are evaluated in batches of at most 6 clips.  The
+ * StylizationBlock launches stage the FiLM rows of every clip a token block touches: at most 4 clips per 32-token block
+ * (window-chain kernels) or 6 per 128-token block (first-generation kernels), so min(31 / T + 2, B) <= 4 or
+ * min(127 / T + 2, B) <= 6 must hold (integer division) - true for every T >= 11 and for every B <= 6.  A batch outside that
+ * (B >= 7 with T <= 10) is refused HERE with -1, before any state changes and before any launch: the previous condition stays
+ * usable, and dsh_eval / dsh_sample never see such a shape.  Split such a batch of chain tail windows into calls of at most 6
+ * clips, or use fp32, which has no such limit.  (With DSH_TLS=0 or DSH_HILO=0 only the 128-token rule applies: B >= 7 needs T >= 26.) */
 int dsh_set_condition(dsh_ctx* ctx, int32_t batch, int32_t frames, const float* audio_emb, const float* person_id,
                       const float* hubert);
 /* eps[B,T,C] = UniDiffuser(x[B,T,C], t[B]; sqrt_alphas = (c1[B], c2[B])).  t holds ORIGINAL-scale
@@ -133,7 +140,13 @@ int64_t dsh_sample_num_steps(const dsh_sampler_opts* opts, int32_t masked);
  * [n_draws, B*T*C] for DSH_NOISE_STACK, else NULL.  trace (device, nullable): [n_steps, B*T*C],
  * receives the sample after every step.  Asynchronous on the context stream.  (Large batches are sampled as two or three
  * independent sub-batches, each running the whole loop on an internal stream forked from and joined to the context stream:
- * for the caller everything stays ordered on the context stream, and the result is bit-identical to one stream.) */
+ * for the caller everything stays ordered on the context stream.  A clip's result does not depend on the sub-batch it was sampled
+ * in as long as the sub-batch and the whole batch run the same kernels: bit-identical to one stream whenever both are on the same
+ * side of the fused-FFN limit of 8192 token rows per launch (CFG-doubled rows included) - always with classifier-free guidance, where
+ * a split batch (>= 12288 clip rows) and its halves are all above it.  Without doubling (guidance scale 1) a batch of 12288 .. 16383
+ * rows is above the limit and its halves are below: the halves round the FFN hidden layer to bf16, the unsplit batch keeps it in
+ * fp32, and the two agree to bf16 round-off only.  fp32 precision: always bit-identical.
+ * Shapes: see dsh_set_condition - a shape it accepts is never refused here.) */
 int dsh_sample(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t init_from_x, const float* gt,
                const uint8_t* mask, int32_t masked, const float* noise_stack, int64_t n_draws, float* trace);
 /* DSH_NOISE_PHILOX only: give every batch row its own generator key (host array of n = B entries; n = 0 restores
@@ -209,6 +222,18 @@ int dsh_op_gemm_f32_pro(void* hip_stream, int32_t pro, const float* x0, int32_t 
  * 10 = tl_linear (first generation), 11 = tl_small (window chain); -1 before any launch.  Lets the bit-identity tests assert that the
  * kernel they mean to check is the one that ran. */
 int32_t dsh_debug_last_tl_variant(void);
+/* Test helper: launches issued by this process since the last reset, per kernel family (host-side counters: no kernel and no launch
+ * argument knows about them).  Copies min(cap, n) entries into out (nullable), zeroes all of them afterwards when reset != 0, returns n.
+ * Fixed indices (new ones are appended):
+ *    0 tl_linear (first generation)        1 tl2 round-2 loop                    2 tl2 rolling loop
+ *    3 tl2 rolling loop on hi / lo planes  4 tl4 LDS-tiled                       5 tl_small (window chain)
+ *    6 fused FFN launch (tl3_ffn / tl2_ffn)            7 ... of which with the attention branch's StylizationBlock as first stage
+ *    8 bf16 layers: MFMA tiled attention               9 bf16 layers: row-major attention fallback (windows of more than 96 frames)
+ *   10 fp32 few-row (K-split) GEMM        11 fp32 tiled GEMM                    12 gemm_f32_pro
+ *  and four VALUES rather than counts: 13 sub-batch streams of the last dsh_eval, 14 sub-batch streams of the last dsh_sample,
+ *   15 whether the last dsh_sample replayed captured graphs, 16 whether it ran the two-encoder pipeline. */
+#define DSH_LAUNCH_COUNT_ENTRIES 17
+int32_t dsh_debug_launch_counts(int64_t* out, int32_t cap, int32_t reset);
 int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W, const float* bias, const float* R,
                      float* Cf, void* Ct, int32_t M, int32_t N, int32_t act, const float* gamma, const float* beta,
                      const float* film, int32_t frames, int32_t nb, int32_t K);

@@ -30,6 +30,23 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.dsh_version()
 
 
+def test_launch_counters_match_the_header_and_reset():
+    """dsh_debug_launch_counts: the binding's names cover exactly the entries the header documents, a short buffer is not overrun,
+    and a reset zeroes every entry (host-side counters: no GPU needed)."""
+    import ctypes as C
+    hdr = open(os.path.join(ROOT, "include", "diffsheg_hip.h")).read()
+    n_hdr = int(re.search(r"#define DSH_LAUNCH_COUNT_ENTRIES (\d+)", hdr).group(1))
+    assert n_hdr == len(_lib.LAUNCH_FAMILIES)
+    for i, name in [(0, "tl_linear"), (5, "tl_small"), (6, "fused FFN"), (12, "gemm_f32_pro")]:
+        assert re.search(rf"\b{i} {re.escape(name)}", hdr), (i, name)
+    lib = _lib.lib()
+    assert lib.dsh_debug_launch_counts(None, 0, 1) == n_hdr
+    short = (C.c_int64 * 4)(7, 7, 7, 7)
+    assert lib.dsh_debug_launch_counts(short, 2, 0) == n_hdr
+    assert list(short) == [0, 0, 7, 7]
+    assert set(_lib.launch_counts().values()) == {0}
+
+
 def test_native_tables_match_reference_goldens():
     full, sp = golden("tables_ddpm1000.npz"), golden("tables_ddim25.npz")
     for k in full.files:
