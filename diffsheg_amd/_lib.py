@@ -49,6 +49,7 @@ SYMBOLS = {
     "dsh_finalize_weights": (C.c_int, [_P]),
     "dsh_weight_bytes": (C.c_int64, [_P]),
     "dsh_set_condition": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "dsh_set_condition_ragged": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P]),
     "dsh_eval": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "dsh_eval_flops": (C.c_double, [_P]),
     "dsh_profile_enable": (C.c_int, [_P, C.c_int32]),
@@ -75,6 +76,7 @@ SYMBOLS = {
     "dsh_op_cross_attention": (C.c_int, [_P, C.POINTER(CrossAttnWeightsC), _P, _P, _P] + [C.c_int32] * 7 + [_P]),
     "dsh_op_linear_attention": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "dsh_op_linear_attention_bf16": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "dsh_op_linear_attention_ragged": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P]),
     "dsh_op_layernorm": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "dsh_op_ddim_step": (C.c_int, [_P] * 6 + [C.c_int32] * 3 + [C.c_float] * 4 + [C.c_int32] * 6),
     "dsh_op_philox_randn": (C.c_int, [_P, _P, C.c_int64, C.c_uint64, C.c_uint64]),

@@ -11,6 +11,13 @@
 // lane-locally (no cross-lane traffic), keeps column c of A (hd registers), and the per-frame
 // k / q rows are broadcast through a 64-float LDS row.  Softmax over channels is a wavefront
 // (hd=64) or 16-lane (hd=16) butterfly.  All math is fp32; storage type T is fp32 or bf16.
+//
+// Ragged batches (RAG = true instantiations): clip b of a padded batch [B, frames, ...] has len[b % lmod] <= frames valid frames
+// (lmod = clips per CFG half: both halves of a clip share its length).  Frames >= len are excluded from the time-softmax of K
+// (max and sum) and from k^T v by SELECTION — their K reads as -inf, their V as 0, whatever the padded rows hold — so A[b,h] is
+// what the clip gives evaluated alone at T = len.  Clip base addresses keep the padded stride, and every one of the `frames`
+// query rows is still answered (padded rows get finite, unspecified values that nothing downstream mixes into valid rows).
+// RAG = false is the code as it was: same instructions, `lens` is never read.
 #include <stdlib.h>
 
 #include "dsh_common.h"
@@ -34,19 +41,20 @@ __device__ __forceinline__ float group_sum(float v) {
     return v;
 }
 
-template <typename T, int HD>
+template <bool RAG, typename T, int HD>
 __global__ __launch_bounds__(64) void linear_attention_kernel(const T* __restrict__ qkv, int ldq, int frames, int D,
-                                                              T* __restrict__ y, int ldy) {
+                                                              T* __restrict__ y, int ldy, const int* __restrict__ lens, int lmod) {
     __shared__ float bc[2][64];
     const int lane = threadIdx.x;
     const int b = blockIdx.y;
     const int c = blockIdx.x * 64 + lane;
     const int g0 = (lane / HD) * HD;             // first lane of this lane's head
     const T* base = qkv + (size_t)b * frames * ldq;
+    const int len = RAG ? lens[b % lmod] : frames;   // frames that enter the K softmax and k^T v (block-uniform)
 
     // ---- pass 1: online max / sum of K[:, c] over time ------------------------------------------
     float m = -INFINITY, ssum = 0.f;
-    for (int t = 0; t < frames; ++t) {
+    for (int t = 0; t < len; ++t) {
         const float kv = to_f32<T>(base[(size_t)t * ldq + D + c]);
         const float mn = fmaxf(m, kv);
         ssum = ssum * expf(m - mn) + expf(kv - mn);
@@ -58,7 +66,7 @@ __global__ __launch_bounds__(64) void linear_attention_kernel(const T* __restric
     float A[HD];
 #pragma unroll
     for (int d = 0; d < HD; ++d) A[d] = 0.f;
-    for (int t = 0; t < frames; ++t) {
+    for (int t = 0; t < len; ++t) {
         const float kh = expf(to_f32<T>(base[(size_t)t * ldq + D + c]) - m) * inv;
         const float v = to_f32<T>(base[(size_t)t * ldq + 2 * D + c]);
         bc[t & 1][lane] = kh;
@@ -152,15 +160,16 @@ int launch_linear_cross_attention(const float* q, int ldq, int nbatch, int frame
 // dependent global-load round trip per frame and pass; at chain batch sizes (two blocks on the whole chip for encoder_aud) that
 // was 111 us per launch — 5 % of a batch-1 evaluation.
 // (TM = 48 for the 34-frame windows of the fp32 parity configuration: 160 instead of 256 column registers)
-template <typename T, int HD, int TM = 96>
+template <bool RAG, typename T, int HD, int TM = 96>
 __global__ __launch_bounds__(64) void linear_attention_pre_kernel(const T* __restrict__ qkv, int ldq, int frames, int D,
-                                                                  T* __restrict__ y, int ldy) {
+                                                                  T* __restrict__ y, int ldy, const int* __restrict__ lens, int lmod) {
     __shared__ float bc[2][64];
     const int lane = threadIdx.x;
     const int b = blockIdx.y;
     const int c = blockIdx.x * 64 + lane;
     const int g0 = (lane / HD) * HD;
     const T* base = qkv + (size_t)b * frames * ldq;
+    const int len = RAG ? lens[b % lmod] : frames;
     float kr[TM], vr[TM];
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
@@ -170,17 +179,17 @@ __global__ __launch_bounds__(64) void linear_attention_pre_kernel(const T* __res
     }
     float m = -INFINITY;
 #pragma unroll
-    for (int t = 0; t < TM; ++t) m = fmaxf(m, t < frames ? kr[t] : -INFINITY);
+    for (int t = 0; t < TM; ++t) m = fmaxf(m, t < len ? kr[t] : -INFINITY);
     float ssum = 0.f;
 #pragma unroll
-    for (int t = 0; t < TM; ++t) { kr[t] = t < frames ? expf(kr[t] - m) : 0.f; ssum += kr[t]; }
+    for (int t = 0; t < TM; ++t) { kr[t] = t < len ? expf(kr[t] - m) : 0.f; ssum += kr[t]; }
     const float inv = 1.0f / ssum;
     float A[HD];
 #pragma unroll
     for (int d = 0; d < HD; ++d) A[d] = 0.f;
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
-        if (t < frames) {                                   // uniform
+        if (t < len) {                                      // uniform
             bc[t & 1][lane] = kr[t] * inv;
             __syncthreads();
             const float* row = &bc[t & 1][g0];
@@ -226,11 +235,13 @@ __global__ __launch_bounds__(64) void linear_attention_pre_kernel(const T* __res
 // Same math as the VALU kernels (exact fp32 products, fp32 accumulation), another summation order.
 __device__ __forceinline__ float at_silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f)); }   // (as gemm_f32_pro.hip)
 
-template <int TM>
-__global__ __launch_bounds__(64) void linear_attention_f32_mfma_kernel(const float* __restrict__ qkv, int ldq, int T, int D, float* __restrict__ y, int ldy) {
+template <bool RAG, int TM>
+__global__ __launch_bounds__(64) void linear_attention_f32_mfma_kernel(const float* __restrict__ qkv, int ldq, int T, int D, float* __restrict__ y, int ldy,
+                                                                       const int* __restrict__ lens, int lmod) {
     constexpr int NS = TM / 2, NTT = (TM + 31) / 32;
     const int lane = threadIdx.x, i = lane & 31, hh = lane >> 5;
     const int b = blockIdx.y, head = blockIdx.x;
+    const int len = RAG ? lens[b % lmod] : T;
     const float* base = qkv + (size_t)b * T * ldq + head * 64;
     // ---- K, V: frame 2 s + hh, channels i and 32 + i -----------------------------------------------------------------------------
     float kr[NS][2], vr[NS][2];
@@ -257,7 +268,7 @@ __global__ __launch_bounds__(64) void linear_attention_f32_mfma_kernel(const flo
     for (int c = 0; c < 2; ++c) {
         float m = -INFINITY;
 #pragma unroll
-        for (int sx = 0; sx < NS; ++sx) { if (2 * sx + hh >= T) kr[sx][c] = -INFINITY; m = fmaxf(m, kr[sx][c]); }
+        for (int sx = 0; sx < NS; ++sx) { if (2 * sx + hh >= len) { kr[sx][c] = -INFINITY; if (RAG) vr[sx][c] = 0.f; } m = fmaxf(m, kr[sx][c]); }
         m = fmaxf(m, __shfl_xor(m, 32, 64));
         float sum = 0.f;
 #pragma unroll
@@ -277,7 +288,7 @@ __global__ __launch_bounds__(64) void linear_attention_f32_mfma_kernel(const flo
             for (int r = 0; r < 16; ++r) aA[dt][ct][r] = 0.f;
 #pragma unroll
     for (int sx = 0; sx < NS; ++sx) {
-        if (2 * sx < T) {                                       // (uniform)
+        if (2 * sx < len) {                                     // (uniform)
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -345,14 +356,16 @@ __global__ __launch_bounds__(64) void linear_attention_f32_mfma_kernel(const flo
 // exchanged through 6 KB of LDS (two-pass: mean, then sum (y - mean)^2), and the transform is applied to the output registers ONCE per
 // element, in a launch whose matrix pipe has slack, instead of by each of the eight N tiles of the Linear's row block (gemm_f32_pro.hip, PRO 2:
 // matrix pipe busy 0.40).  The Linear then runs front-less.  film: per-sample rows [scale'(D) | shift'(D)] with the LayerNorm affine folded in.
-template <int TM>
+template <bool RAG, int TM>
 __global__ __launch_bounds__(512) void linear_attention_f32_mfma_sty_kernel(const float* __restrict__ qkv, int ldq, int T, int D, float* __restrict__ y, int ldy,
-                                                                            const float* __restrict__ film, int film_ld, int film_off, int bmod) {
+                                                                            const float* __restrict__ film, int film_ld, int film_off, int bmod,
+                                                                            const int* __restrict__ lens, int lmod) {
     constexpr int NS = TM / 2, NTT = (TM + 31) / 32;
     __shared__ float red[2][NTT * 32][8];
     const int lane = threadIdx.x & 63, i = lane & 31, hh = lane >> 5;
     const int head = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.x;
+    const int len = RAG ? lens[b % lmod] : T;
     const float* base = qkv + (size_t)b * T * ldq + head * 64;
     float kr[NS][2], vr[NS][2];
 #pragma unroll
@@ -376,7 +389,7 @@ __global__ __launch_bounds__(512) void linear_attention_f32_mfma_sty_kernel(cons
     for (int c = 0; c < 2; ++c) {
         float m = -INFINITY;
 #pragma unroll
-        for (int sx = 0; sx < NS; ++sx) { if (2 * sx + hh >= T) kr[sx][c] = -INFINITY; m = fmaxf(m, kr[sx][c]); }
+        for (int sx = 0; sx < NS; ++sx) { if (2 * sx + hh >= len) { kr[sx][c] = -INFINITY; if (RAG) vr[sx][c] = 0.f; } m = fmaxf(m, kr[sx][c]); }
         m = fmaxf(m, __shfl_xor(m, 32, 64));
         float sum = 0.f;
 #pragma unroll
@@ -395,7 +408,7 @@ __global__ __launch_bounds__(512) void linear_attention_f32_mfma_sty_kernel(cons
             for (int r = 0; r < 16; ++r) aA[dt][ct][r] = 0.f;
 #pragma unroll
     for (int sx = 0; sx < NS; ++sx) {
-        if (2 * sx < T) {
+        if (2 * sx < len) {
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -520,11 +533,13 @@ constexpr int AT_MAT = 64 * AT_TROW;         // one 64-channel matrix
 __device__ __forceinline__ uint32_t pack2_bf16(float lo, float hi) { return pack_bf16_pair(lo, hi); }
 __device__ __forceinline__ float bfbits_to_f32(uint16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
 
+template <bool RAG>
 __global__ __launch_bounds__(64) void linear_attention_mfma_kernel(const uint16_t* __restrict__ qkv, int ldq, int T, int D,
-                                                                   uint16_t* __restrict__ y, int ldy) {
+                                                                   uint16_t* __restrict__ y, int ldy, const int* __restrict__ lens, int lmod) {
     __shared__ __attribute__((aligned(16))) char lds[2 * AT_MAT];
     const int lane = threadIdx.x, i = lane & 31, h = lane >> 5;
     const int b = blockIdx.y, head = blockIdx.x;
+    const int len = RAG ? lens[b % lmod] : T;
     const uint16_t* base = qkv + (size_t)b * T * ldq + head * 64;
 
     // ---- K and V columns.  Every (clamped, unconditional) column load of BOTH matrices is issued before
@@ -541,14 +556,14 @@ __global__ __launch_bounds__(64) void linear_attention_mfma_kernel(const uint16_
         float m = -INFINITY;
 #pragma unroll
         for (int t = 0; t < AT_TMAX; ++t) {
-            const float x = (t < T) ? __builtin_bit_cast(float, rawk[t] << 16) : -INFINITY;
+            const float x = (t < len) ? __builtin_bit_cast(float, rawk[t] << 16) : -INFINITY;
             rawk[t] = __builtin_bit_cast(uint32_t, x);
             m = fmaxf(m, x);
         }
         float ssum = 0.f;
 #pragma unroll
         for (int t = 0; t < AT_TMAX; ++t) {
-            const float e = (t < T) ? __expf(__builtin_bit_cast(float, rawk[t]) - m) : 0.f;
+            const float e = (t < len) ? __expf(__builtin_bit_cast(float, rawk[t]) - m) : 0.f;
             rawk[t] = __builtin_bit_cast(uint32_t, e);
             ssum += e;
         }
@@ -561,7 +576,7 @@ __global__ __launch_bounds__(64) void linear_attention_mfma_kernel(const uint16_
         char* vt = lds + AT_MAT + lane * AT_TROW;
 #pragma unroll
         for (int t = 0; t < AT_TMAX; t += 2) {
-            const uint32_t lo = (t < T) ? rawv[t] : 0u, hi = (t + 1 < T) ? rawv[t + 1] : 0u;
+            const uint32_t lo = (t < len) ? rawv[t] : 0u, hi = (t + 1 < len) ? rawv[t + 1] : 0u;
             *reinterpret_cast<uint32_t*>(vt + t * 2) = lo | (hi << 16);
         }
     }
@@ -668,11 +683,13 @@ __global__ __launch_bounds__(64) void linear_attention_mfma_kernel(const uint16_
 
 // Same algorithm on the TILED bf16 layout of the token-per-lane Linears (tl_linear.hip): element (token, n) of a
 // [M, Wd] tensor lives at ((token >> 5) * (Wd >> 4) + (n >> 4)) * 512 + (token & 31) * 16 + (n & 15).
+template <bool RAG>
 __global__ __launch_bounds__(64, 2) void linear_attention_tiled_kernel(const uint16_t* __restrict__ qkv, int half_batches, int half_row0,
-                                                                    int T, int D, uint16_t* __restrict__ y, int rev) {
+                                                                    int T, int D, uint16_t* __restrict__ y, int rev, const int* __restrict__ lens) {
     __shared__ __attribute__((aligned(16))) char lds[2 * AT_MAT];
     const int lane = threadIdx.x, i = lane & 31, h = lane >> 5;
     const int b = rev ? (int)gridDim.y - 1 - (int)blockIdx.y : (int)blockIdx.y, head = blockIdx.x;     // rev: clips in descending order (tl_block_index)
+    const int len = RAG ? lens[b < half_batches ? b : b - half_batches] : T;                           // (both CFG halves of a clip share its length)
     const int tok0 = b < half_batches ? b * T : half_row0 + (b - half_batches) * T;
     const int KTQ = (3 * D) >> 4;                               // 16-feature tiles per token block of qkv
     auto tok_off = [&](int t, int ktiles) -> size_t { const int tg = tok0 + t; return ((size_t)(tg >> 5) * ktiles) * 512 + (tg & 31) * 16; };
@@ -714,7 +731,7 @@ __global__ __launch_bounds__(64, 2) void linear_attention_tiled_kernel(const uin
 #pragma unroll
             for (int j = 0; j < 12; ++j) {
                 const uint32_t w = rk[j][c >> 1];
-                const float x = fr[j] < T ? __builtin_bit_cast(float, (c & 1) ? (w & 0xffff0000u) : (w << 16)) : -INFINITY;
+                const float x = fr[j] < len ? __builtin_bit_cast(float, (c & 1) ? (w & 0xffff0000u) : (w << 16)) : -INFINITY;
                 e[c][j] = x;
                 m = fmaxf(m, x);
             }
@@ -749,8 +766,10 @@ __global__ __launch_bounds__(64, 2) void linear_attention_tiled_kernel(const uin
             for (int pp = 0; pp < 6; ++pp) {
                 *reinterpret_cast<uint32_t*>(kt + toff[pp]) = pack2_bf16(e[c][2 * pp] * inv, e[c][2 * pp + 1] * inv);
                 const uint32_t w0 = rv[2 * pp][c >> 1], w1 = rv[2 * pp + 1][c >> 1];
-                const uint32_t lo = (c & 1) ? (w0 >> 16) : (w0 & 0xffffu), hi = (c & 1) ? (w1 >> 16) : (w1 & 0xffffu);
-                // (frames >= T hold a clamped, finite duplicate of frame T - 1: their softmax weight above is exactly 0)
+                uint32_t lo = (c & 1) ? (w0 >> 16) : (w0 & 0xffffu), hi = (c & 1) ? (w1 >> 16) : (w1 & 0xffffu);
+                // (frames >= T hold a clamped, finite duplicate of frame T - 1: their softmax weight above is exactly 0;
+                //  ragged: frames >= len are the caller's padding, whatever it holds — read as 0 by selection)
+                if (RAG) { lo = fr[2 * pp] < len ? lo : 0u; hi = fr[2 * pp + 1] < len ? hi : 0u; }
                 *reinterpret_cast<uint32_t*>(vt + toff[pp]) = lo | (hi << 16);
             }
         }
@@ -856,24 +875,36 @@ __global__ __launch_bounds__(64, 2) void linear_attention_tiled_kernel(const uin
     }
 }
 
+// no lengths -> the RAG = false instantiation (the kernel as it was); lengths -> its length-aware twin
+template <typename... P, typename... A>
+static void at_launch(void (*plain)(P...), void (*ragged)(P...), bool rag, dim3 grid, dim3 block, hipStream_t s, A... a) {
+    void (*k)(P...) = rag ? ragged : plain;
+    hipLaunchKernelGGL(k, grid, block, 0, s, a...);
+}
+#define AT_K(name, ...) name<false, __VA_ARGS__>, name<true, __VA_ARGS__>
+#define AT_K0(name) name<false>, name<true>
+
 int launch_linear_attention_tiled(const void* qkv, int nbatch, int half_batches, int half_row0, int frames, int D, void* y,
-                                  hipStream_t s, int rev) {
+                                  hipStream_t s, int rev, const int* lens) {
     DSH_REQUIRE(D % 64 == 0 && frames > 0 && frames <= AT_TMAX, "linear_attention_tiled: needs 64-channel heads and <= 96 frames");
-    hipLaunchKernelGGL(linear_attention_tiled_kernel, dim3(D / 64, nbatch), dim3(64), 0, s, reinterpret_cast<const uint16_t*>(qkv),
-                       half_batches, half_row0, frames, D, reinterpret_cast<uint16_t*>(y), rev);
+    at_launch(AT_K0(linear_attention_tiled_kernel), lens != nullptr, dim3(D / 64, nbatch), dim3(64), s, reinterpret_cast<const uint16_t*>(qkv),
+              half_batches, half_row0, frames, D, reinterpret_cast<uint16_t*>(y), rev, lens);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 template <typename T>
 int launch_linear_attention(const T* qkv, int ldq, int nbatch, int frames, int D, int head_dim, T* y, int ldy,
-                            hipStream_t s) {
+                            hipStream_t s, const int* lens, int lmod) {
     DSH_REQUIRE(D % 64 == 0, "linear_attention: latent width must be a multiple of 64");
     DSH_REQUIRE(head_dim == 64 || head_dim == 16, "linear_attention: head_dim must be 64 or 16");
+    DSH_REQUIRE(!lens || lmod > 0, "linear_attention: per-clip lengths need the number of clips they describe");
+    const bool rag = lens != nullptr;
+    if (!rag) lmod = 1;
     dim3 grid(D / 64, nbatch);
     if (sizeof(T) == 2 && head_dim == 64 && frames <= AT_TMAX && ldq % 4 == 0 && ldy % 4 == 0) {
-        hipLaunchKernelGGL(linear_attention_mfma_kernel, grid, dim3(64), 0, s, reinterpret_cast<const uint16_t*>(qkv), ldq,
-                           frames, D, reinterpret_cast<uint16_t*>(y), ldy);
+        at_launch(AT_K0(linear_attention_mfma_kernel), rag, grid, dim3(64), s, reinterpret_cast<const uint16_t*>(qkv), ldq,
+                  frames, D, reinterpret_cast<uint16_t*>(y), ldy, lens, lmod);
         DSH_HIP_CHECK(hipGetLastError());
         return 0;
     }
@@ -884,23 +915,23 @@ int launch_linear_attention(const T* qkv, int ldq, int nbatch, int frames, int D
     if (f32_mfma && sizeof(T) == 4 && head_dim == 64 && frames <= 96 && ldq % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)qkv % 16) == 0 && ((uintptr_t)y % 16) == 0) {
         const float* qf = reinterpret_cast<const float*>(qkv);
         float* yf = reinterpret_cast<float*>(y);
-        if (frames <= 32) hipLaunchKernelGGL((linear_attention_f32_mfma_kernel<32>), grid, dim3(64), 0, s, qf, ldq, frames, D, yf, ldy);
-        else if (frames <= 36) hipLaunchKernelGGL((linear_attention_f32_mfma_kernel<36>), grid, dim3(64), 0, s, qf, ldq, frames, D, yf, ldy);   // (BEAT: 34 frames, 232 registers)
-        else if (frames <= 64) hipLaunchKernelGGL((linear_attention_f32_mfma_kernel<64>), grid, dim3(64), 0, s, qf, ldq, frames, D, yf, ldy);
-        else hipLaunchKernelGGL((linear_attention_f32_mfma_kernel<96>), grid, dim3(64), 0, s, qf, ldq, frames, D, yf, ldy);
+        if (frames <= 32) at_launch(AT_K(linear_attention_f32_mfma_kernel, 32), rag, grid, dim3(64), s, qf, ldq, frames, D, yf, ldy, lens, lmod);
+        else if (frames <= 36) at_launch(AT_K(linear_attention_f32_mfma_kernel, 36), rag, grid, dim3(64), s, qf, ldq, frames, D, yf, ldy, lens, lmod);   // (BEAT: 34 frames, 232 registers)
+        else if (frames <= 64) at_launch(AT_K(linear_attention_f32_mfma_kernel, 64), rag, grid, dim3(64), s, qf, ldq, frames, D, yf, ldy, lens, lmod);
+        else at_launch(AT_K(linear_attention_f32_mfma_kernel, 96), rag, grid, dim3(64), s, qf, ldq, frames, D, yf, ldy, lens, lmod);
         DSH_HIP_CHECK(hipGetLastError());
         return 0;
     }
     if (head_dim == 64 && frames <= 48)
-        hipLaunchKernelGGL((linear_attention_pre_kernel<T, 64, 48>), grid, dim3(64), 0, s, qkv, ldq, frames, D, y, ldy);
+        at_launch(AT_K(linear_attention_pre_kernel, T, 64, 48), rag, grid, dim3(64), s, qkv, ldq, frames, D, y, ldy, lens, lmod);
     else if (head_dim == 64 && frames <= 96)
-        hipLaunchKernelGGL((linear_attention_pre_kernel<T, 64, 96>), grid, dim3(64), 0, s, qkv, ldq, frames, D, y, ldy);
+        at_launch(AT_K(linear_attention_pre_kernel, T, 64, 96), rag, grid, dim3(64), s, qkv, ldq, frames, D, y, ldy, lens, lmod);
     else if (head_dim == 64)
-        hipLaunchKernelGGL((linear_attention_kernel<T, 64>), grid, dim3(64), 0, s, qkv, ldq, frames, D, y, ldy);
+        at_launch(AT_K(linear_attention_kernel, T, 64), rag, grid, dim3(64), s, qkv, ldq, frames, D, y, ldy, lens, lmod);
     else if (frames <= 96)
-        hipLaunchKernelGGL((linear_attention_pre_kernel<T, 16>), grid, dim3(64), 0, s, qkv, ldq, frames, D, y, ldy);
+        at_launch(AT_K(linear_attention_pre_kernel, T, 16), rag, grid, dim3(64), s, qkv, ldq, frames, D, y, ldy, lens, lmod);
     else
-        hipLaunchKernelGGL((linear_attention_kernel<T, 16>), grid, dim3(64), 0, s, qkv, ldq, frames, D, y, ldy);
+        at_launch(AT_K(linear_attention_kernel, T, 16), rag, grid, dim3(64), s, qkv, ldq, frames, D, y, ldy, lens, lmod);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -911,17 +942,20 @@ bool linear_attention_sty_f32_supported(int frames, int D, int head_dim, int ldq
     return on && D == 512 && head_dim == 64 && frames > 0 && frames <= 64 && ldq % 4 == 0 && ldy % 4 == 0;
 }
 int launch_linear_attention_sty_f32(const float* qkv, int ldq, int nbatch, int frames, int D, float* s_out, int ldy, const float* film, int film_ld, int film_off,
-                                    int bmod, hipStream_t s) {
+                                    int bmod, hipStream_t s, const int* lens, int lmod) {
     DSH_REQUIRE(linear_attention_sty_f32_supported(frames, D, 64, ldq, ldy) && film && bmod > 0 && film_ld % 4 == 0 && film_off % 4 == 0, "linear_attention_sty: unsupported shape");
     DSH_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)s_out % 16) == 0 && ((uintptr_t)film % 16) == 0, "linear_attention_sty: 16-byte alignment");
+    DSH_REQUIRE(!lens || lmod > 0, "linear_attention_sty: per-clip lengths need the number of clips they describe");
+    const bool rag = lens != nullptr;
+    if (!rag) lmod = 1;
     const dim3 grid(nbatch);
-    if (frames <= 32) hipLaunchKernelGGL((linear_attention_f32_mfma_sty_kernel<32>), grid, dim3(512), 0, s, qkv, ldq, frames, D, s_out, ldy, film, film_ld, film_off, bmod);
-    else if (frames <= 36) hipLaunchKernelGGL((linear_attention_f32_mfma_sty_kernel<36>), grid, dim3(512), 0, s, qkv, ldq, frames, D, s_out, ldy, film, film_ld, film_off, bmod);
-    else hipLaunchKernelGGL((linear_attention_f32_mfma_sty_kernel<64>), grid, dim3(512), 0, s, qkv, ldq, frames, D, s_out, ldy, film, film_ld, film_off, bmod);
+    if (frames <= 32) at_launch(AT_K(linear_attention_f32_mfma_sty_kernel, 32), rag, grid, dim3(512), s, qkv, ldq, frames, D, s_out, ldy, film, film_ld, film_off, bmod, lens, lmod);
+    else if (frames <= 36) at_launch(AT_K(linear_attention_f32_mfma_sty_kernel, 36), rag, grid, dim3(512), s, qkv, ldq, frames, D, s_out, ldy, film, film_ld, film_off, bmod, lens, lmod);
+    else at_launch(AT_K(linear_attention_f32_mfma_sty_kernel, 64), rag, grid, dim3(512), s, qkv, ldq, frames, D, s_out, ldy, film, film_ld, film_off, bmod, lens, lmod);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }
-template int launch_linear_attention<float>(const float*, int, int, int, int, int, float*, int, hipStream_t);
-template int launch_linear_attention<bf16>(const bf16*, int, int, int, int, int, bf16*, int, hipStream_t);
+template int launch_linear_attention<float>(const float*, int, int, int, int, int, float*, int, hipStream_t, const int*, int);
+template int launch_linear_attention<bf16>(const bf16*, int, int, int, int, int, bf16*, int, hipStream_t, const int*, int);
 
 }  // namespace dsh

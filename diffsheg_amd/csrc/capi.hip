@@ -169,6 +169,14 @@ int dsh_set_condition(dsh_ctx* ctx, int32_t batch, int32_t frames, const float* 
     API_END
 }
 
+int dsh_set_condition_ragged(dsh_ctx* ctx, int32_t batch, int32_t frames_pad, const int32_t* lengths_host, const float* audio_emb,
+                             const float* person_id, const float* hubert) {
+    API_BEGIN
+    DSH_REQUIRE(ctx, "null context");
+    return ctx->den->set_condition_ragged(batch, frames_pad, lengths_host, audio_emb, person_id, hubert);
+    API_END
+}
+
 int dsh_eval(dsh_ctx* ctx, const float* x, const int64_t* t, const float* c1, const float* c2, float* eps) {
     API_BEGIN
     DSH_REQUIRE(ctx && t, "null context / timestep tensor");
@@ -709,14 +717,11 @@ int dsh_op_linear_attention(void* hip_stream, const float* qkv, int32_t nb, int3
     API_END
 }
 
-int dsh_op_linear_attention_bf16(void* hip_stream, const void* qkv, int32_t nb, int32_t frames, int32_t D, int32_t head_dim,
-                                 void* y) {
-    API_BEGIN
-    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    if (head_dim == 64 && frames <= 96) {
-        // the product kernel works on the tiled layout of the token-per-lane Linears: convert in scratch (test helper).
-        // The batch is split into two halves with a block-aligned gap between them, like the CFG halves of the denoiser.
-        const int nh = (nb + 1) / 2, M0 = nh * frames, r0 = dsh::round_up(M0, 128), M1 = (nb - nh) * frames;
+// the product kernel works on the tiled layout of the token-per-lane Linears: convert in scratch (test helper).
+// The batch is split into two halves (nh clips, then the rest) with a block-aligned gap between them, like the CFG halves of the denoiser.
+static int attn_tiled_via_scratch(hipStream_t s, const void* qkv, int nb, int nh, int frames, int D, void* y, const int* lens) {
+    {
+        const int M0 = nh * frames, r0 = dsh::round_up(M0, 128), M1 = (nb - nh) * frames;
         const size_t Mp = (size_t)r0 + dsh::round_up(M1 > 0 ? M1 : 1, 128) + 128;
         static void* sc[2] = {nullptr, nullptr}; static size_t cap[2] = {0, 0};
         const size_t need[2] = {Mp * 3 * D * 2, Mp * D * 2};
@@ -726,13 +731,40 @@ int dsh_op_linear_attention_bf16(void* hip_stream, const void* qkv, int32_t nb, 
         char* tq = reinterpret_cast<char*>(sc[0]); char* ty = reinterpret_cast<char*>(sc[1]);
         if (int e = dsh::launch_tile_rows_bf16<dsh::bf16>(q, 3 * D, M0, 3 * D, tq, 3 * D, s)) return e;
         if (M1 > 0) { if (int e = dsh::launch_tile_rows_bf16<dsh::bf16>(q + (size_t)M0 * 3 * D, 3 * D, M1, 3 * D, tq + (size_t)r0 * 3 * D * 2, 3 * D, s)) return e; }
-        if (int e = dsh::launch_linear_attention_tiled(tq, nb, nh, r0, frames, D, ty, s)) return e;
+        if (int e = dsh::launch_linear_attention_tiled(tq, nb, nh, r0, frames, D, ty, s, 0, lens)) return e;
         if (int e = dsh::launch_untile_rows_bf16(ty, D, M0, D, y, D, s)) return e;
         if (M1 > 0) { if (int e = dsh::launch_untile_rows_bf16(ty + (size_t)r0 * D * 2, D, M1, D, reinterpret_cast<dsh::bf16*>(y) + (size_t)M0 * D, D, s)) return e; }
         return 0;
     }
+}
+
+int dsh_op_linear_attention_bf16(void* hip_stream, const void* qkv, int32_t nb, int32_t frames, int32_t D, int32_t head_dim,
+                                 void* y) {
+    API_BEGIN
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    if (head_dim == 64 && frames <= 96) return attn_tiled_via_scratch(s, qkv, nb, (nb + 1) / 2, frames, D, y, nullptr);
     return dsh::launch_linear_attention<dsh::bf16>(reinterpret_cast<const dsh::bf16*>(qkv), 3 * D, nb, frames, D, head_dim,
                                                    reinterpret_cast<dsh::bf16*>(y), D, s);
+    API_END
+}
+
+int dsh_op_linear_attention_ragged(void* hip_stream, int32_t dtype, int32_t variant, const void* qkv, int32_t nb, int32_t frames, int32_t D,
+                                   int32_t head_dim, void* y, const int32_t* lens_dev, int32_t n_lens, const float* film) {
+    API_BEGIN
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    DSH_REQUIRE(qkv && y && nb > 0 && frames > 0 && (dtype == 0 || dtype == 1) && variant >= 0 && variant <= 2, "linear_attention_ragged: invalid argument");
+    DSH_REQUIRE(!lens_dev || (n_lens > 0 && (nb == n_lens || nb == 2 * n_lens)), "linear_attention_ragged: nb must be n_lens or 2 * n_lens (CFG-doubled)");
+    const int lm = lens_dev ? n_lens : nb;
+    if (variant == 2) {
+        DSH_REQUIRE(dtype == 0 && film, "linear_attention_ragged: variant 2 is the fp32 kernel with the StylizationBlock front (needs film)");
+        return dsh::launch_linear_attention_sty_f32(reinterpret_cast<const float*>(qkv), 3 * D, nb, frames, D, reinterpret_cast<float*>(y), D, film, 2 * D, 0, lm, s,
+                                                    lens_dev, lm);
+    }
+    if (dtype == 0)
+        return dsh::launch_linear_attention<float>(reinterpret_cast<const float*>(qkv), 3 * D, nb, frames, D, head_dim, reinterpret_cast<float*>(y), D, s, lens_dev, lm);
+    if (variant == 0 && head_dim == 64 && frames <= 96) return attn_tiled_via_scratch(s, qkv, nb, lm, frames, D, y, lens_dev);
+    return dsh::launch_linear_attention<dsh::bf16>(reinterpret_cast<const dsh::bf16*>(qkv), 3 * D, nb, frames, D, head_dim,
+                                                   reinterpret_cast<dsh::bf16*>(y), D, s, lens_dev, lm);
     API_END
 }
 

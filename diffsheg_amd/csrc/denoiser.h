@@ -39,6 +39,20 @@ class DenoiserBase {
     virtual int finalize(const std::map<std::string, HostTensor>& w) = 0;
     // step-invariant conditioning: audio [B,T,128] fp32, person_id [B,S] fp32, hubert [B,T,1024] fp32 (device)
     virtual int set_condition(int B, int T, const float* audio, const float* person_id, const float* hubert) = 0;
+    // Ragged batches: clip b of the padded batch [B, T, ...] has lengths[b] <= T valid frames.  Frames [0, lengths[b]) of every output are what
+    // the clip gives evaluated alone at T = lengths[b], whatever the padded frames of any input hold; padded output frames are unspecified.
+    // Only two operations of the model couple frames of a clip: the linear attention (time-softmax of K, k^T v) and the two k = 3 convolutions
+    // of hubert_encoder — those read the lengths, everything else is per token and runs on the padded rows as it stands.  So regime decisions
+    // (sub-batch split, kernel families, check_shape) and the flop count keep using B x T.
+    //   set_condition_ragged(): lengths_host [B] int32 (host); -1 before any state changes on a length < 1 or > T.  set_condition() = all full.
+    //   set_lengths(): what a per-stream instance reads — device int32 [its clips], owned by the context, null = all full; takes effect
+    //   with the instance's next set_condition() / set_condition_light() (hubert_encoder and encoder_aud's attention depend on it).
+    //   lengths_host(): the current condition's lengths (null = all full), for the sampler's per-row noise streams and final zeroing.
+    virtual int set_condition_ragged(int /*B*/, int /*T*/, const int32_t* /*lengths_host*/, const float* /*audio*/, const float* /*person_id*/,
+                                     const float* /*hubert*/) { return -1; }
+    virtual int set_lengths(const int* /*lens_dev*/) { return 0; }
+    virtual const int32_t* lengths_host() const { return nullptr; }
+    virtual const int* lengths_dev() const { return nullptr; }
     // eps[B,T,C] = model(x[B,T,C], t[B]) with c1/c2 [B] (device fp32) feeding the expression x0
     virtual int eval(const float* x, const int64_t* t, const float* c1, const float* c2, float* eps) = 0;
     // 0 if a batch of B clips of T frames can be evaluated, else -1 with the limit in the error text.  set_condition() asks before it

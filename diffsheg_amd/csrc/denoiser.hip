@@ -108,6 +108,8 @@ class Denoiser final : public DenoiserBase {
     }
     int level_cache_prepare(int n_levels) override;
     int set_condition_light(int B, int T_, const float* audio, const float* person_id) override;
+    int set_lengths(const int* lens_dev) override { lens = lens_dev; return 0; }
+    const int* lengths_dev() const override { return lens; }
     int set_part(int p) override {
         DSH_REQUIRE(p >= 0 && p <= 2 && (p == 0 || !cfg.single_transformer), "set_part: 0 whole / 1 expression / 2 gesture (UniDiffuser only)");
         part = p;
@@ -201,6 +203,7 @@ class Denoiser final : public DenoiserBase {
 
     // ---- workspace (grow-only) ----
     int capB = 0, capT = 0;
+    const int* lens = nullptr;       // ragged batch: valid frames per clip (device, context-owned, [batch]); null = every clip is `frames` long
     // guidance (set_guidance): scale of clip b = gs[b * gs_row]; gs_dbl = the null half is evaluated.  ws_dbl: the M-row buffers
     // (row_allocs) hold both halves — from the first time a doubled batch is asked for, never shrunk
     const float* gs = nullptr; int gs_row = 0; bool gs_dbl = false, ws_dbl = false;
@@ -471,7 +474,7 @@ class Denoiser final : public DenoiserBase {
         if (int e = launch_pack_cols<T>(audio_f, DA, Mc_, 0, DA, DA, 2.0f, (T*)nullptr, 0, aud_x2, DA, st)) return e;
         if (int e = launch_ln_rows<T>(aud_x2, DA, Mc_, DA, nullptr, 0, aud.sa_ln.g, aud.sa_ln.b, n, DA, st)) return e;
         if (int e = gemm(aud.qkv, n, DA, Mc_, ACT_NONE, false, nullptr, 0, 0, nullptr, 0, qkv, 3 * DA)) return e;
-        return launch_linear_attention<T>(qkv, 3 * DA, batch, frames, DA, DA / cfg.num_heads, aud_y, DA, st);
+        return launch_linear_attention<T>(qkv, 3 * DA, batch, frames, DA, DA / cfg.num_heads, aud_y, DA, st, lens, batch);
     }
     int prep_encoder(Encoder& E);
     int run_encoder(Encoder& E, const float* x, int c0, int w, const float* expr, int expr_w, const float* c1,
@@ -908,9 +911,11 @@ int Denoiser<T>::set_condition(int B, int T_, const float* audio, const float* p
     const int Mc = B * T_, HE = cfg.hubert_enc_dim, HD_ = cfg.hubert_dim;
     for (Encoder* E : encs()) {
         // hubert_encoder over time, zero padded per window
-        if (int e = launch_im2col3_rows<float, T>(hubert, HD_, B, T_, HD_, col, 3 * HD_, st)) return e;
+        // (ragged: frames >= the clip's length read as zero in BOTH passes — the caller's padding, and conv1's output there, which
+        //  BatchNorm + GELU make non-zero even on a zero input)
+        if (int e = launch_im2col3_rows<float, T>(hubert, HD_, B, T_, HD_, col, 3 * HD_, st, lens)) return e;
         if (int e = gemm(E->conv1, col, 3 * HD_, Mc, ACT_GELU, false, nullptr, 0, 0, nullptr, 0, z, HE)) return e;
-        if (int e = launch_im2col3_rows<T, T>(z, HE, B, T_, HE, col, 3 * HE, st)) return e;
+        if (int e = launch_im2col3_rows<T, T>(z, HE, B, T_, HE, col, 3 * HE, st, lens)) return e;
         if (tl_path()) {
             if (int e = gemm(E->conv2, col, 3 * HE, Mc, ACT_NONE, false, nullptr, 0, 0, nullptr, 0, hub_rm, HE)) return e;
             if (int e = launch_tile_rows_bf16<T>(hub_rm, HE, Mc, HE, E->hub, HE, st)) return e;
@@ -931,7 +936,7 @@ int Denoiser<T>::run_block_tail(const Layer& L, int M, int D, int nbatch, int fr
     if (!y_in) {
         if (int e = gemm(L.qkv, n, D, M, ACT_NONE, false, nullptr, 0, 0, nullptr, 0, qkv, 3 * D)) return e;
         if (prof) prof->begin(PROF_ATTN);
-        if (int e = launch_linear_attention<T>(qkv, 3 * D, nbatch, fr, D, D / cfg.num_heads, y, D, st)) return e;
+        if (int e = launch_linear_attention<T>(qkv, 3 * D, nbatch, fr, D, D / cfg.num_heads, y, D, st, lens, batch)) return e;
         if (prof) prof->end(4.0 * M * (double)D * (D / cfg.num_heads));
         flops_acc += 4.0 * M * (double)D * (D / cfg.num_heads);
     }
@@ -966,8 +971,8 @@ int Denoiser<T>::run_block_tail_fused(const Layer& L, int M, int D, int nbatch, 
     const bool attn_sty = (fb & 10) == 10 && linear_attention_sty_f32_supported(fr, D, D / cfg.num_heads, 3 * D, D);
     if (prof) prof->begin(PROF_ATTN);
     if (attn_sty) {
-        if (int e = launch_linear_attention_sty_f32(reinterpret_cast<const float*>(qkv), 3 * D, nbatch, fr, D, reinterpret_cast<float*>(s), D, film, film_ld, film_off0, bmod, st)) return e;
-    } else if (int e = launch_linear_attention<T>(qkv, 3 * D, nbatch, fr, D, D / cfg.num_heads, y, D, st)) return e;
+        if (int e = launch_linear_attention_sty_f32(reinterpret_cast<const float*>(qkv), 3 * D, nbatch, fr, D, reinterpret_cast<float*>(s), D, film, film_ld, film_off0, bmod, st, lens, batch)) return e;
+    } else if (int e = launch_linear_attention<T>(qkv, 3 * D, nbatch, fr, D, D / cfg.num_heads, y, D, st, lens, batch)) return e;
     if (prof) prof->end(4.0 * M * (double)D * (D / cfg.num_heads));
     flops_acc += 4.0 * M * (double)D * (D / cfg.num_heads);
     if (attn_sty) {
@@ -1082,7 +1087,7 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
             if (dbg_skip & 8) {
             } else if (fr <= 96) {
                 count_launch(LC_ATTN_MFMA);
-                if (int e = launch_linear_attention_tiled(qkv, nb, B, r0, fr, D, y, st, M >= 4096 ? next_rev() : 0)) return e;
+                if (int e = launch_linear_attention_tiled(qkv, nb, B, r0, fr, D, y, st, M >= 4096 ? next_rev() : 0, lens)) return e;
             } else {
                 // windows longer than the MFMA kernel's 96-frame tile (non-default n_poses): row-major VALU kernel
                 // between two layout conversions per CFG half
@@ -1093,7 +1098,7 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
                     const size_t ro = hf ? (size_t)r0 : 0, rm = (size_t)hf * Mc;
                     if (int e = launch_untile_rows_bf16(qkv + ro * 3 * D, 3 * D, Mc, 3 * D, qkv_rm + rm * 3 * D, 3 * D, st)) return e;
                 }
-                if (int e = launch_linear_attention<T>(qkv_rm, 3 * D, nb, fr, D, D / cfg.num_heads, y_rm, D, st)) return e;
+                if (int e = launch_linear_attention<T>(qkv_rm, 3 * D, nb, fr, D, D / cfg.num_heads, y_rm, D, st, lens, B)) return e;
                 for (int hf = 0; hf <= has_null; ++hf) {
                     const size_t ro = hf ? (size_t)r0 : 0, rm = (size_t)hf * Mc;
                     if (int e = launch_tile_rows_bf16<T>(y_rm + rm * D, D, Mc, D, y + ro * D, D, st)) return e;
@@ -1351,6 +1356,7 @@ class DualDenoiser final : public DenoiserBase {
         for (hipStream_t st : streams_) (void)hipStreamDestroy(st);
         for (hipEvent_t ev : events_) (void)hipEventDestroy(ev);
         if (cond_buf_) (void)hipFree(cond_buf_);
+        if (len_buf_) (void)hipFree(len_buf_);
         for (Prefetch& f : pf_) {
             f.prep.reset();
             if (f.stream) (void)hipStreamDestroy(f.stream);
@@ -1362,7 +1368,24 @@ class DualDenoiser final : public DenoiserBase {
     }
     int finalize(const std::map<std::string, HostTensor>& w) override { return inst_[0]->finalize(w); }
     int set_condition(int B, int T, const float* audio, const float* person_id, const float* hubert) override {
+        return condition(B, T, nullptr, audio, person_id, hubert);
+    }
+    int set_condition_ragged(int B, int T, const int32_t* lengths_host, const float* audio, const float* person_id, const float* hubert) override {
+        DSH_REQUIRE(lengths_host, "set_condition_ragged: null lengths");
+        return condition(B, T, lengths_host, audio, person_id, hubert);
+    }
+    const int32_t* lengths_host() const override { return lens_ ? lens_host_.data() : nullptr; }
+    const int* lengths_dev() const override { return lens_; }
+    int condition(int B, int T, const int32_t* lengths_host, const float* audio, const float* person_id, const float* hubert) {
         DSH_REQUIRE(B > 0 && T > 0 && audio && person_id && hubert, "set_condition: null conditioning pointer / empty batch");
+        if (lengths_host) {
+            for (int b = 0; b < B; ++b)
+                if (lengths_host[b] < 1 || lengths_host[b] > T) {
+                    set_last_error("set_condition_ragged: clip " + std::to_string(b) + " has length " + std::to_string(lengths_host[b]) +
+                                   ", valid lengths are 1 .. " + std::to_string(T) + " (the padded frame count)");
+                    return -1;
+                }
+        }
         if (int e = inst_[0]->check_shape(B, T)) return e;          // (before any state changes: a refused shape leaves the previous condition usable)
         // The split (one stream vs sub-batches on several) may change between evals (profiler on/off), which re-runs the
         // per-instance set_condition: the conditioning is therefore copied into context-owned buffers, so the caller's
@@ -1385,6 +1408,20 @@ class DualDenoiser final : public DenoiserBase {
         DSH_HIP_CHECK(hipMemcpyAsync(a, audio, na * sizeof(float), hipMemcpyDeviceToDevice, st_));
         DSH_HIP_CHECK(hipMemcpyAsync(p, person_id, np * sizeof(float), hipMemcpyDeviceToDevice, st_));
         DSH_HIP_CHECK(hipMemcpyAsync(h, hubert, nh * sizeof(float), hipMemcpyDeviceToDevice, st_));
+        // per-clip lengths: context-owned like the conditioning, read by the kernels when they run; instance i of a split sees `lens_ + its first clip`
+        if (lengths_host) {
+            if ((size_t)B > len_cap_) {
+                DSH_HIP_CHECK(hipStreamSynchronize(st_));
+                if (len_buf_) (void)hipFree(len_buf_);
+                len_buf_ = nullptr; len_cap_ = 0;
+                DSH_HIP_CHECK(hipMalloc((void**)&len_buf_, (size_t)B * sizeof(int)));
+                len_cap_ = (size_t)B;
+            }
+            lens_host_.assign(lengths_host, lengths_host + B);
+            // (pageable host source: staged before the call returns)
+            DSH_HIP_CHECK(hipMemcpyAsync(len_buf_, lens_host_.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, st_));
+            lens_ = len_buf_;
+        } else lens_ = nullptr;
         cond_ = {B, T, a, p, h};
         batch = B; frames = T;
         return apply_condition((B == sticky_B_ && T == sticky_T_ && pipe_possible()) ? 1 : want_split(B, T));
@@ -1473,6 +1510,7 @@ class DualDenoiser final : public DenoiserBase {
             // the slots) precedes the side stream's work
             DSH_HIP_CHECK(hipEventRecord(f.ev_fork, main_st));
             DSH_HIP_CHECK(hipStreamWaitEvent(f.stream, f.ev_fork, 0));
+            if (int e = f.prep->set_lengths(lens_ ? lens_ + b0 : nullptr)) return e;
             if (int e = f.prep->set_condition_light(nb, cond_.T, cond_.audio + (size_t)b0 * cond_.T * cfg_.audio_dim, cond_.pid + (size_t)b0 * cfg_.style_dim)) return e;
             if (int e = f.prep->adopt_level_slots(slots, stride, nslots)) return e;
             f.levels = n_levels; f.nb = nb;
@@ -1530,6 +1568,7 @@ class DualDenoiser final : public DenoiserBase {
         if (int e = twin_->set_guidance(gs_, gs_row_, gs_dbl_)) return e;
         if (!twin_cond_ok_) {
             if (int e = twin_->set_part(0)) return e;
+            if (int e = twin_->set_lengths(lens_)) return e;
             if (int e = twin_->set_condition(cond_.B, cond_.T, cond_.audio, cond_.pid, cond_.hubert)) return e;
             twin_cond_ok_ = true;
         }
@@ -1640,13 +1679,14 @@ class DualDenoiser final : public DenoiserBase {
         split_now_ = ns;
         for (int i = 0; i < ns; ++i) { if (int e = push_guidance(i, ns)) return e; }
         inst_[0]->prof = prof;
-        if (ns == 1) return inst_[0]->set_condition(cond_.B, cond_.T, cond_.audio, cond_.pid, cond_.hubert);
+        if (ns == 1) { if (int e = inst_[0]->set_lengths(lens_)) return e; return inst_[0]->set_condition(cond_.B, cond_.T, cond_.audio, cond_.pid, cond_.hubert); }
         DSH_HIP_CHECK(hipEventRecord(ev_fork_, st_));
         for (int i = 0; i < ns; ++i) {
             const int b0 = first_clip(i, ns), nb = first_clip(i + 1, ns) - b0;
             const size_t ft = (size_t)b0 * cond_.T;
             hipStream_t si = i == 0 ? st_ : streams_[i - 1];
             if (i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(si, ev_fork_, 0));
+            if (int e = inst_[i]->set_lengths(lens_ ? lens_ + b0 : nullptr)) return e;
             if (int e = inst_[i]->set_condition(nb, cond_.T, cond_.audio + ft * cfg_.audio_dim, cond_.pid + (size_t)b0 * cfg_.style_dim,
                                                 cond_.hubert + ft * cfg_.hubert_dim)) return e;
             if (i > 0) {
@@ -1670,6 +1710,9 @@ class DualDenoiser final : public DenoiserBase {
     hipEvent_t ev_fork_ = nullptr;
     Cond cond_;
     float* cond_buf_ = nullptr;                            // context-owned copy of [audio | person_id | hubert]
+    int* len_buf_ = nullptr; size_t len_cap_ = 0;          // ... and of the per-clip lengths of a ragged condition
+    const int* lens_ = nullptr;                            // len_buf_ while the current condition is ragged, else null
+    std::vector<int32_t> lens_host_;
     size_t cond_cap_ = 0;
     // side-stream producers of the x-independent head (level_prefetch): [0] the whole batch / sub-batch 0, [i] sub-batch i
     struct Prefetch {

@@ -46,7 +46,7 @@ template <typename T>
 int launch_concat_ln_rows(const ConcatSegs& sg, int M, const float* gamma, const float* beta, T* out, int ldo, int Ppad,
                           hipStream_t s);
 template <typename TI, typename T>
-int launch_im2col3_rows(const TI* x, int ldx, int B, int frames, int Cin, T* out, int ldo, hipStream_t s);
+int launch_im2col3_rows(const TI* x, int ldx, int B, int frames, int Cin, T* out, int ldo, hipStream_t s, const int* lens = nullptr);
 template <typename T>
 int launch_temb_rows(const int64_t* t, int B, int dim, T* out, int ldo, hipStream_t s);
 template <typename T>
@@ -196,9 +196,11 @@ int launch_interp_time(const float* x, int B, int Tin, int C, float* y, int Tout
 int launch_affine_cols(const float* x, size_t n, int C, const float* mean, const float* stdv, float* y, hipStream_t s);
 
 // linear ("efficient") self-attention core: y = softmax_ch(Q) (softmax_time(K)^T V)   (transformer.py:122-128)
+// lens (device int32, nullable): ragged batch — clip b has lens[b % lmod] valid frames out of `frames` (the padded stride); frames beyond
+// them enter neither the K softmax nor k^T v.  Null: every frame is valid, the launch is the one it always was.
 template <typename T>
 int launch_linear_attention(const T* qkv, int ldq, int nbatch, int frames, int D, int head_dim, T* y, int ldy,
-                            hipStream_t s);
+                            hipStream_t s, const int* lens = nullptr, int lmod = 0);
 // cross-attention core (LinearTemporalCrossAttention, transformer.py:146-166): q [B,T,D] (ldq), kv [B,N,2D] = (k | v) (ldkv), fp32
 int launch_linear_cross_attention(const float* q, int ldq, int nbatch, int frames, const float* kv, int ldkv, int frames_kv, int D,
                                   int head_dim, float* y, int ldy, hipStream_t s);
@@ -207,9 +209,10 @@ int launch_silu_f32(const float* x, float* y, size_t n, hipStream_t s);
 // half_row0 + (b - half_batches) * frames
 bool linear_attention_sty_f32_supported(int frames, int D, int head_dim, int ldq, int ldy);
 int launch_linear_attention_sty_f32(const float* qkv, int ldq, int nbatch, int frames, int D, float* s_out, int ldy, const float* film, int film_ld, int film_off,
-                                    int bmod, hipStream_t s);
+                                    int bmod, hipStream_t s, const int* lens = nullptr, int lmod = 0);
+// (lens: one entry per clip of a CFG half, [half_batches])
 int launch_linear_attention_tiled(const void* qkv, int nbatch, int half_batches, int half_row0, int frames, int D, void* y,
-                                  hipStream_t s, int rev = 0);
+                                  hipStream_t s, int rev = 0, const int* lens = nullptr);
 
 // ---- sampler element-wise kernels (sampler_kernels.hip) ------------------------------------
 struct DdimStepArgs {
@@ -262,7 +265,9 @@ int launch_level_copy(const LevelCopyArgs& a, hipStream_t s);
 // Philox4x32-10 + Box-Muller standard normals; element i uses counter (offset + i/4)
 int launch_philox_randn(float* out, size_t n, uint64_t seed, uint64_t offset, hipStream_t s);
 // per-row streams: row b of `rows` x n_row values uses key `seed`, counter = (in-row quad index, row_keys[b]) (device array)
+// row_lens (device, nullable): ragged rows — row b advances by row_lens[b] * channels / 4 counters per draw instead of `offset`
+int launch_zero_padded_frames(float* x, const int* lens, int B, int frames, int channels, hipStream_t s);
 int launch_philox_randn_rows(float* out, int rows, size_t n_row, uint64_t seed, uint64_t offset, const uint64_t* row_keys,
-                             hipStream_t s);
+                             hipStream_t s, const int* row_lens = nullptr, uint64_t draw = 0, int channels = 0);
 
 }  // namespace dsh

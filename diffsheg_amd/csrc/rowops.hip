@@ -193,14 +193,17 @@ template int launch_concat_ln_rows<bf16>(const ConcatSegs&, int, const float*, c
 
 // ------------------------------------------------------------------------------------------------
 // out[(b,t), tap*Cin + c] = x[b, t + tap - 1, c]  (zero outside the window: padding=1 per sample)
+// lens (nullable): clip b of the padded batch ends at frame lens[b] — source frames beyond it read as zero (by selection, whatever they hold),
+// which is the zero padding the clip's convolution sees when it is run alone at that length
 template <typename TI, typename T>
-__global__ void im2col3_rows_kernel(const TI* x, int ldx, int B, int frames, int Cin, T* out, int ldo) {
+__global__ void im2col3_rows_kernel(const TI* x, int ldx, int B, int frames, int Cin, T* out, int ldo, const int* lens) {
     const int row = blockIdx.x;
     const int b = row / frames, t = row % frames;
+    const int len = lens ? lens[b] : frames;
     T* orow = out + (size_t)row * ldo;
     for (int tap = 0; tap < 3; ++tap) {
         const int ts = t + tap - 1;
-        const bool ok = ts >= 0 && ts < frames;
+        const bool ok = ts >= 0 && ts < len;
         const TI* xr = x + ((size_t)b * frames + (ok ? ts : 0)) * ldx;
         for (int c = threadIdx.x; c < Cin; c += blockDim.x)
             orow[tap * Cin + c] = ok ? from_f32<T>(to_f32<TI>(xr[c])) : from_f32<T>(0.f);
@@ -208,14 +211,14 @@ __global__ void im2col3_rows_kernel(const TI* x, int ldx, int B, int frames, int
 }
 
 template <typename TI, typename T>
-int launch_im2col3_rows(const TI* x, int ldx, int B, int frames, int Cin, T* out, int ldo, hipStream_t s) {
-    hipLaunchKernelGGL((im2col3_rows_kernel<TI, T>), dim3(B * frames), dim3(256), 0, s, x, ldx, B, frames, Cin, out, ldo);
+int launch_im2col3_rows(const TI* x, int ldx, int B, int frames, int Cin, T* out, int ldo, hipStream_t s, const int* lens) {
+    hipLaunchKernelGGL((im2col3_rows_kernel<TI, T>), dim3(B * frames), dim3(256), 0, s, x, ldx, B, frames, Cin, out, ldo, lens);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }
-template int launch_im2col3_rows<float, float>(const float*, int, int, int, int, float*, int, hipStream_t);
-template int launch_im2col3_rows<float, bf16>(const float*, int, int, int, int, bf16*, int, hipStream_t);
-template int launch_im2col3_rows<bf16, bf16>(const bf16*, int, int, int, int, bf16*, int, hipStream_t);
+template int launch_im2col3_rows<float, float>(const float*, int, int, int, int, float*, int, hipStream_t, const int*);
+template int launch_im2col3_rows<float, bf16>(const float*, int, int, int, int, bf16*, int, hipStream_t, const int*);
+template int launch_im2col3_rows<bf16, bf16>(const bf16*, int, int, int, int, bf16*, int, hipStream_t, const int*);
 
 // ------------------------------------------------------------------------------------------------
 // temb[b, j] = cos(t_b f_j) (j < half), sin(t_b f_{j-half}) (j >= half); f_j = exp(-ln(1e4) j / half)

@@ -258,6 +258,13 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
     DSH_REQUIRE(!(tail_blend && o.same_overlap_noisy), "tail_blend with same_overlap_noisy: the saved noisy tails describe a window chain, not a window pinned at both ends");
     DSH_REQUIRE(!tail_blend || (o.overlap_len >= 0 && 2 * (int64_t)o.overlap_len <= den->frames), "tail_blend: the head and the tail fade overlap (2 * overlap_len > frames)");
     const int B = den->batch;
+    // ragged batch (set_condition_ragged): per-clip frame counts of the padded batch, host and device copies owned by the context
+    const int32_t* len_h = den->lengths_host();
+    const int* len_d = den->lengths_dev();
+    // (both address the last overlap_len frames of the PADDED window, which a short clip does not reach)
+    DSH_REQUIRE(!len_h || (!o.same_overlap_noisy && !tail_blend), "per-clip lengths cannot be combined with same_overlap_noisy or the tail blend");
+    if (len_h && o.noise_mode == 1 && n_row_keys == B)
+        for (int b = 0; b < B; ++b) DSH_REQUIRE(((int64_t)len_h[b] * channels) % 4 == 0, "row keys on a ragged batch: length * channels must be a multiple of 4 for every clip");
     // loop_begin() marks the batch as deliberately unsplit; the mark is taken back on EVERY way out of this function (an argument error or a
     // failed launch below must not leave the context answering later evaluations as if a loop were still running)
     struct LoopScope { DenoiserBase* d; ~LoopScope() { (void)d->loop_end(); } } loop_scope{den};
@@ -335,7 +342,9 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
     // ... and its values for one sub-batch (device pointer; scratch = a full-size buffer the sub-batch owns its slice of)
     auto noise_for = [&](int64_t idx, const Sub& u, float* scratch, const float** out) -> int {
         if (o.noise_mode == 0) { *out = noise_stack + (size_t)idx * n + u.off; return 0; }
-        if (per_row) { if (int e = launch_philox_randn_rows(scratch + u.off, u.nb, row_n, o.seed, (uint64_t)idx * quads, row_keys + u.b0, u.s)) return e; }
+        // (ragged: every row advances by its own size per draw, so a clip draws the same noise padded as sampled alone)
+        if (per_row) { if (int e = launch_philox_randn_rows(scratch + u.off, u.nb, row_n, o.seed, (uint64_t)idx * quads, row_keys + u.b0, u.s,
+                                                            len_d ? len_d + u.b0 : nullptr, (uint64_t)idx, channels)) return e; }
         else if (int e = launch_philox_randn(scratch + u.off, u.cnt, o.seed, (uint64_t)idx * quads + u.off / 4, u.s)) return e;
         *out = scratch + u.off;
         return 0;
@@ -618,6 +627,9 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
             DSH_HIP_CHECK(hipStreamWaitEvent(st, ev_sub[2 * i + 1], 0));
         }
     if (graph_exec[0] || graph_exec[1] || graph_exec[2]) { DSH_HIP_CHECK(hipStreamSynchronize(st)); drop_graph(); }
+    // ragged batch: the loop ran on the padded rows; its result is defined as exactly 0 beyond every clip's length (one launch behind the join,
+    // whatever regime the loop ran in; rows of `trace` keep the padded frames' values)
+    if (rc == 0 && len_d) return launch_zero_padded_frames(x, len_d, B, den->frames, channels, st);
     return rc;
 }
 

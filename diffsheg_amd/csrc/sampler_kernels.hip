@@ -204,14 +204,21 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint
 // HIGH words of the 128-bit Philox counter (they are zero in the whole-tensor mode) and the counter offset + quad index INSIDE
 // the row in the low words — so a chain's noise does not depend on which batch / rank it is sampled in, and two (seed, row key)
 // pairs share a stream only if both components are equal (round 2 XORed the row key into the seed: (s + 1) ^ 0 == s ^ 1).
+// row_lens != null (ragged batch, with row_keys): row b holds row_lens[b] valid frames of `channels` values in front of its padding and
+// advances by ITS OWN size per draw — counter = draw * (row_lens[b] * channels / 4) + quad index inside the row — which is the stream the
+// clip draws from when it is sampled alone at that length.  (Padded positions run on into the next draw's counters; nothing reads them.)
 __global__ void philox_randn_kernel(float* out, size_t n, uint64_t seed, uint64_t offset, const uint64_t* __restrict__ row_keys,
-                                    size_t row_quads) {
+                                    size_t row_quads, const int* __restrict__ row_lens, uint64_t draw, int channels) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const size_t nquad = (n + 3) / 4;
     for (size_t qd = (size_t)blockIdx.x * blockDim.x + threadIdx.x; qd < nquad; qd += stride) {
         uint64_t ctr = offset + qd, rk = 0;
         const uint64_t key = seed;
-        if (row_keys) { const size_t b = qd / row_quads; ctr = offset + (qd - b * row_quads); rk = row_keys[b]; }
+        if (row_keys) {
+            const size_t b = qd / row_quads;
+            ctr = (row_lens ? draw * ((uint64_t)row_lens[b] * (uint64_t)channels / 4) : offset) + (qd - b * row_quads);
+            rk = row_keys[b];
+        }
         uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)rk, (uint32_t)(rk >> 32)};
         uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
 #pragma unroll
@@ -240,15 +247,32 @@ __global__ void philox_randn_kernel(float* out, size_t n, uint64_t seed, uint64_
 }
 int launch_philox_randn(float* out, size_t n, uint64_t seed, uint64_t offset, hipStream_t s) {
     hipLaunchKernelGGL(philox_randn_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, s, out, n, seed, offset,
-                       (const uint64_t*)nullptr, (size_t)1);
+                       (const uint64_t*)nullptr, (size_t)1, (const int*)nullptr, (uint64_t)0, 0);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }
 int launch_philox_randn_rows(float* out, int rows, size_t n_row, uint64_t seed, uint64_t offset, const uint64_t* row_keys,
-                             hipStream_t s) {
+                             hipStream_t s, const int* row_lens, uint64_t draw, int channels) {
     DSH_REQUIRE(rows > 0 && n_row % 4 == 0 && row_keys, "philox_randn_rows: row length must be a multiple of 4");
+    DSH_REQUIRE(!row_lens || channels > 0, "philox_randn_rows: per-row lengths need the channel count");
     const size_t n = (size_t)rows * n_row;
-    hipLaunchKernelGGL(philox_randn_kernel, dim3(grid_for(n / 4)), dim3(256), 0, s, out, n, seed, offset, row_keys, n_row / 4);
+    hipLaunchKernelGGL(philox_randn_kernel, dim3(grid_for(n / 4)), dim3(256), 0, s, out, n, seed, offset, row_keys, n_row / 4, row_lens, draw, channels);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ragged batch: x[b, t, :] = 0 for t >= lens[b] (the padded frames of a sampling loop's result)
+__global__ void zero_padded_frames_kernel(float* __restrict__ x, const int* __restrict__ lens, size_t n, int frames, int channels) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x, row_n = (size_t)frames * channels;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const size_t b = i / row_n;
+        if ((i - b * row_n) / channels >= (size_t)lens[b]) x[i] = 0.f;
+    }
+}
+int launch_zero_padded_frames(float* x, const int* lens, int B, int frames, int channels, hipStream_t s) {
+    DSH_REQUIRE(x && lens && B > 0 && frames > 0 && channels > 0, "zero_padded_frames: invalid argument");
+    const size_t n = (size_t)B * frames * channels;
+    hipLaunchKernelGGL(zero_padded_frames_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, lens, n, frames, channels);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }

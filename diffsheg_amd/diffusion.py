@@ -17,6 +17,8 @@ Differences a caller can observe, all loud:
     whatever batch / on whatever rank it is sampled (the sharded long-audio path);
   * the guidance scale is ``opt.cond_scale`` as in the reference (ignored for weights without ``classifier_free``), or the
     loops' ``cond_scale=`` keyword (a float, or one value per batch row), which wins over ``opt``; either holds for the call only;
+  * ``model_kwargs['length']`` with an entry ``< T`` makes the batch ragged (``UniDiffuser.set_condition(lengths=)``): every row is
+    sampled as the clip alone at its length (with ``row_keys``: from the same noise), padded frames of the result are exactly 0;
   * ``ddim_sample_loop(..., tail_blend=True)`` mirrors the ``addBlend`` cross-fade onto the last ``overlap_len`` frames, for a mask
     that pins both ends of a window (``DDPMTrainer.sample_inbetween``, seam repair); off by default.
 """
@@ -30,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .model import UniDiffuser, normalize_guidance_scale
+from .model import UniDiffuser, normalize_guidance_scale, normalize_lengths
 
 _TABLES = ["betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_recip_alphas_cumprod",
            "sqrt_recipm1_alphas_cumprod", "posterior_variance", "posterior_log_variance_clipped",
@@ -174,7 +176,14 @@ class GaussianDiffusion:
         if gs is not None and len(gs) not in (1, B):
             raise ValueError(f"cond_scale needs one value or one per batch row ({B}), got {len(gs)}")
         dev = model.device
-        model._maybe_set_condition(model_kwargs["audio_emb"], model_kwargs["person_id"], model_kwargs.get("add_cond"))
+        # clips of different lengths in one padded batch (model_kwargs['length'] with an entry < T): both options below address the last
+        # overlap_len frames of the PADDED window, which a short clip does not reach — refused before anything is conditioned
+        lens = normalize_lengths(model_kwargs.get("length"), B, T)
+        if lens is not None and (son or tail_blend):
+            raise NotImplementedError("per-clip lengths cannot be combined with same_overlap_noisy or tail_blend")
+        if lens is not None and row_keys is not None and noise_source is None and any((v * Cc) % 4 for v in lens):
+            raise ValueError("row_keys on a ragged batch: length * channels must be a multiple of 4 for every clip")
+        model._maybe_set_condition(model_kwargs["audio_emb"], model_kwargs["person_id"], model_kwargs.get("add_cond"), lens)
         if (B, T) != (model.batch, model.frames) or Cc != model.cfg.net_dim_pose:
             raise ValueError(f"shape {tuple(shape)} does not match the conditioning")
         gt = mask = None

@@ -61,6 +61,23 @@ def normalize_guidance_scale(scale) -> Optional[Tuple[float, ...]]:
     return tuple(vals)
 
 
+def normalize_lengths(length, batch: int, frames: int) -> Optional[Tuple[int, ...]]:
+    """Per-clip frame counts of a padded batch ``[batch, frames, ...]`` -> ``None`` (every clip is ``frames`` long: also what ``None``
+    and the reference's ``cur_len = T`` tensors mean) or a tuple of ``batch`` ints in ``1 .. frames`` with at least one entry
+    ``< frames``.  Raises ``ValueError`` on a wrong count or a length outside that range.  (The values are read on the host: a device
+    tensor costs one sync per call.)"""
+    if length is None:
+        return None
+    if isinstance(length, torch.Tensor):
+        length = length.detach().to("cpu").reshape(-1).tolist()
+    vals = [int(v) for v in length]
+    if len(vals) != batch:
+        raise ValueError(f"length needs one entry per batch row ({batch}), got {len(vals)}")
+    if any(v < 1 or v > frames for v in vals):
+        raise ValueError(f"length: every clip needs 1 .. {frames} frames (the padded frame count), got {vals}")
+    return None if all(v == frames for v in vals) else tuple(vals)
+
+
 class UniDiffuser:
     """MI355X UniDiffuser: ``encoder_aud`` + ``encoder_exp`` + ``encoder_ges`` behind one C handle."""
     _UNIDIFFUSER = True
@@ -89,6 +106,7 @@ class UniDiffuser:
         self._h = h
         self._cond_key = None
         self._cond_keep = None
+        self.lengths = None                    # per-clip frame counts of a ragged condition (set_condition(lengths=))
         self._guidance = None                  # set_guidance_scale(): None = the config's cond_scale
         self._dummy = torch.zeros(1, device=self.device)
         self.load_state_dict(state_dict)
@@ -148,9 +166,13 @@ class UniDiffuser:
             cur.wait_stream(self._stream)
 
     # ---- conditioning ------------------------------------------------------------------------
-    def set_condition(self, audio_emb: torch.Tensor, person_id: torch.Tensor, hubert: torch.Tensor) -> None:
-        """Upload the step-invariant conditioning and run hubert_encoder / pid_embed once."""
+    def set_condition(self, audio_emb: torch.Tensor, person_id: torch.Tensor, hubert: torch.Tensor, lengths=None) -> None:
+        """Upload the step-invariant conditioning and run hubert_encoder / pid_embed once.  ``lengths`` (one frame count per clip,
+        ``1 .. T``): the batch is ragged — clip ``b`` is the first ``lengths[b]`` frames of its padded row, and those frames of every
+        following evaluation / sampling loop are what the clip gives alone at that length, whatever the padded frames of any input
+        hold (``dsh_set_condition_ragged``).  ``None`` or all equal to ``T``: every clip is full, the path it always was."""
         B, T = int(audio_emb.shape[0]), int(audio_emb.shape[1])
+        lens = normalize_lengths(lengths, B, T)
         if person_id.dim() == 1:                                   # transformer.py:502-503
             person_id = person_id.unsqueeze(0)
         if person_id.shape[0] != B:
@@ -166,14 +188,19 @@ class UniDiffuser:
         a, p, hb = (_dev_f32(t, self.device) for t in (audio_emb, person_id, hubert))
         cur = self._enter()
         try:
-            _lib.check(self._lib.dsh_set_condition(self._h, B, T, a.data_ptr(), p.data_ptr(), hb.data_ptr()),
-                       "dsh_set_condition")
+            if lens is None:
+                _lib.check(self._lib.dsh_set_condition(self._h, B, T, a.data_ptr(), p.data_ptr(), hb.data_ptr()),
+                           "dsh_set_condition")
+            else:
+                _lib.check(self._lib.dsh_set_condition_ragged(self._h, B, T, (C.c_int32 * B)(*lens), a.data_ptr(), p.data_ptr(),
+                                                              hb.data_ptr()), "dsh_set_condition_ragged")
         finally:
             self._exit(cur)                    # (also when the call is refused: the caller's stream stays ordered after the context's)
         self._cond_keep = (a, p, hb)           # (the library copies them in stream order; kept for the allocator's sake)
         self.batch, self.frames = B, T
+        self.lengths = lens                    # None: every clip is full
 
-    def _maybe_set_condition(self, audio_emb, person_id, add_cond) -> None:
+    def _maybe_set_condition(self, audio_emb, person_id, add_cond, length=None) -> None:
         if "pretrain_aud_feat" not in (add_cond or {}):
             raise ValueError("add_cond['pretrain_aud_feat'] (HuBERT features) is required (addHubert=True)")
         hub = add_cond["pretrain_aud_feat"]
@@ -182,10 +209,12 @@ class UniDiffuser:
         # so data_ptr alone would alias stale conditioning.
         src = (audio_emb, person_id, hub)
         vers = tuple(t._version for t in src)
+        # (the lengths are part of the condition; compared by value: callers build a fresh `length` tensor per call)
+        lens = normalize_lengths(length, int(audio_emb.shape[0]), int(audio_emb.shape[1]))
         if (self._cond_key is None or any(a is not b for a, b in zip(self._cond_key[0], src))
-                or self._cond_key[1] != vers):
-            self.set_condition(audio_emb, person_id, hub)
-            self._cond_key = (src, vers)
+                or self._cond_key[1] != vers or self._cond_key[2] != lens):
+            self.set_condition(audio_emb, person_id, hub, lens)
+            self._cond_key = (src, vers, lens)
 
     # ---- classifier-free guidance ---------------------------------------------------------------
     def set_guidance_scale(self, scale=None) -> None:
@@ -221,7 +250,7 @@ class UniDiffuser:
             raise NotImplementedError(f"pe_type={pe_type!r}: only the default 'pe_sinu' path is built")
         if sqrt_alphas is None or len(sqrt_alphas) != 2:
             raise ValueError("sqrt_alphas=[sqrt_recip_alphas_cumprod_t, sqrt_recipm1_alphas_cumprod_t] is required")
-        self._maybe_set_condition(audio_emb, person_id, add_cond)
+        self._maybe_set_condition(audio_emb, person_id, add_cond, length)
         B, T, Cc = x.shape
         if (B, T) != (self.batch, self.frames) or Cc != self.cfg.net_dim_pose:
             raise ValueError(f"x shape {tuple(x.shape)} does not match conditioning ({self.batch},{self.frames},{self.cfg.net_dim_pose})")

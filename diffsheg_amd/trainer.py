@@ -19,7 +19,7 @@ import torch
 from .config import DiffSHEGConfig
 from .diffusion import (GaussianDiffusion, ModelMeanType, ModelVarType, SpacedDiffusion, get_named_beta_schedule,
                         space_timesteps)
-from .model import UniDiffuser
+from .model import UniDiffuser, normalize_guidance_scale
 
 
 def sampler_namespace(cfg: DiffSHEGConfig, **over) -> argparse.Namespace:
@@ -67,6 +67,40 @@ def get_windows(x, size: int, step: int):
     return out
 
 
+def window_lengths(n_frames: int, size: int, step: int) -> List[int]:
+    """Frame counts of the windows :func:`get_windows` cuts a stream of ``n_frames`` frames into (window ``i`` starts at
+    ``i * step``): full windows, then the stream's own shorter tail."""
+    if n_frames <= size:
+        return [n_frames]
+    win_num = (n_frames - (size - step)) / float(step)
+    out = [size] * int(win_num)
+    if win_num - int(win_num) != 0:
+        out.append(n_frames - int(win_num) * step)
+    return out
+
+
+# bf16 batches of 7 and more clips need windows of at least this many frames (UniDiffuser.set_condition: FiLM rows staged per token block).
+# A ragged window batch whose rows are all short tails is padded up to it; the rows keep their lengths.
+MIN_PAD_FRAMES, MIN_PAD_BATCH = 11, 7
+
+
+def ragged_window_plan(chain_frames: Sequence[int], size: int, step: int) -> List[dict]:
+    """Window batches of chains of different lengths sampled together.  Chain ``b`` gets exactly the windows
+    :func:`get_windows` gives a stream of ``chain_frames[b]`` frames; batch ``i`` of the plan holds window ``i`` of every chain that
+    has one: ``{"rows": chain indices, "start": i * step, "lengths": frames of each row's window, "frames": padded frame count}``.
+    ``frames`` is the longest row, or :data:`MIN_PAD_FRAMES` when :data:`MIN_PAD_BATCH` or more rows are all shorter than that."""
+    per = [window_lengths(int(n), size, step) for n in chain_frames]
+    plan = []
+    for i in range(max(len(w) for w in per)):
+        rows = [b for b, w in enumerate(per) if i < len(w)]
+        lens = [per[b][i] for b in rows]
+        pad = max(lens)
+        if len(rows) >= MIN_PAD_BATCH and pad < MIN_PAD_FRAMES:
+            pad = MIN_PAD_FRAMES
+        plan.append({"rows": rows, "start": i * step, "lengths": lens, "frames": pad})
+    return plan
+
+
 class DDPMTrainer:
     """Sampling half of DDPMTrainer_show / DDPMTrainer_beat (ddpm_show_trainer.py:40-90)."""
 
@@ -83,15 +117,20 @@ class DDPMTrainer:
         self.diffusion_ddim_val = SpacedDiffusion(use_timesteps=space_timesteps(self.diffusion_steps, "ddim25"),
                                                   rescale_timesteps=False, **kw)
 
-    def generate_batch(self, audio_emb, p_id, dim_pose, add_cond={}, inpaint_dict=None, cond_scale=None, **sampler_kw):
+    def generate_batch(self, audio_emb, p_id, dim_pose, add_cond={}, inpaint_dict=None, cond_scale=None, lengths=None, **sampler_kw):
         """ddpm_show_trainer.py:163-198.  ``sampler_kw`` (noise_source= / seed=) is this build's
         noise-injection hook; the reference draws from the global torch RNG.  ``cond_scale`` (a float, or one value per batch
-        row) overrides ``opt.cond_scale`` for this batch."""
+        row) overrides ``opt.cond_scale`` for this batch.  ``lengths`` (one frame count per row, ``1 .. T``): clips of different
+        lengths padded to ``T`` frames — row ``b`` is sampled as its first ``lengths[b]`` frames alone, the padded frames of the
+        result are 0 (the reference always passes ``cur_len = T``, which is the default)."""
         if cond_scale is not None:
             sampler_kw["cond_scale"] = cond_scale
         audio_emb = audio_emb.to(self.device)
         B, T = len(audio_emb), audio_emb.shape[1]
-        cur_len = torch.full((B,), T, dtype=torch.long, device=self.device)
+        if lengths is None:
+            cur_len = torch.full((B,), T, dtype=torch.long)          # (host tensor: the loops read its values, a device tensor would cost a sync)
+        else:
+            cur_len = torch.tensor([int(v) for v in lengths], dtype=torch.long)
         model_kwargs = {"audio_emb": audio_emb, "length": cur_len, "person_id": p_id, "add_cond": add_cond,
                         "y": inpaint_dict, "pe_type": getattr(self.opt, "PE", "pe_sinu")}
         if getattr(self.opt, "ddim", True):
@@ -104,14 +143,23 @@ class DDPMTrainer:
     def sample_arbitrary_len(self, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor],
                              noise_source_for_window=None, seed: Optional[int] = None,
                              motions: Optional[torch.Tensor] = None, row_keys: Optional[Sequence[int]] = None,
-                             cond_scale=None) -> torch.Tensor:
+                             cond_scale=None, lengths: Optional[Sequence[int]] = None):
         """The per-video body of test_arbitrary_len (ddpm_show_trainer.py:864-906): windows of n_poses
         with stride n_poses-overlap_len; window k>0 out-paints from the last overlap_len frames of
         window k-1 (sequential chain).  Output stays on the device (the reference copies every window
         to the host).  ``opt.fix_very_first`` (ddpm_show_trainer.py:885-888): window 0 is out-painted too, from the
         LAST overlap_len frames of the first ground-truth window of ``motions`` (standardised, [B, N, C]) — the
         reference's indexing, kept as is.  Batch rows are independent chains of equal length.  ``cond_scale`` (a float, or one
-        value per chain) is the guidance scale of every window of the chains (default: ``opt.cond_scale``)."""
+        value per chain) is the guidance scale of every window of the chains (default: ``opt.cond_scale``).
+
+        ``lengths`` (one frame count per chain): chains of DIFFERENT lengths — ``audio_emb`` / ``add_cond`` / ``motions`` are
+        ``[B, N_max, ...]``, chain ``b`` is their first ``lengths[b]`` frames (what lies behind is never read into a valid frame).
+        Every chain is sampled exactly as alone: its own window list (:func:`ragged_window_plan`), its next window out-painted from
+        ITS last ``overlap_len`` valid frames, with ``row_keys`` its own noise.  Returns a LIST of ``[lengths[b], C]`` tensors
+        (not a padded tensor); ``opt.same_overlap_noisy`` is refused."""
+        if lengths is not None:
+            return self._sample_arbitrary_len_ragged(audio_emb, p_id, add_cond, [int(v) for v in lengths], noise_source_for_window, seed,
+                                                     motions, row_keys, cond_scale)
         opt = self.opt
         n_poses, L, C = int(opt.n_poses), int(opt.overlap_len), int(opt.net_dim_pose)
         step = n_poses - L
@@ -155,6 +203,75 @@ class DDPMTrainer:
             outs.append(outputs if ii == len(audio_list) - 1 else outputs[:, :step])
         return torch.cat(outs, dim=1)
 
+
+    def _sample_arbitrary_len_ragged(self, audio_emb, p_id, add_cond, lengths: List[int], noise_source_for_window, seed, motions,
+                                     row_keys, cond_scale) -> List[torch.Tensor]:
+        opt = self.opt
+        n_poses, L, C = int(opt.n_poses), int(opt.overlap_len), int(opt.net_dim_pose)
+        step = n_poses - L
+        B, N_max = int(audio_emb.shape[0]), int(audio_emb.shape[1])
+        if len(lengths) != B or any(n < 1 or n > N_max for n in lengths):
+            raise ValueError(f"lengths needs one frame count in 1 .. {N_max} per chain ({B}), got {lengths}")
+        if bool(getattr(opt, "same_overlap_noisy", False)):
+            raise NotImplementedError("same_overlap_noisy with per-chain lengths: the saved noisy tails address the padded window")
+        add_cond = add_cond or {}
+        fix_first = bool(getattr(opt, "fix_very_first", False)) and L > 0
+        if fix_first and motions is None:
+            raise ValueError("fix_very_first needs the ground-truth motions of the clip")
+        if fix_first and min(lengths) < L:
+            raise ValueError(f"fix_very_first pins overlap_len = {L} frames of every chain's first window: chains need at least that many frames, got {lengths}")
+        pid = p_id if p_id.dim() == 2 else p_id.unsqueeze(0)
+        if pid.shape[0] == 1:
+            pid = pid.expand(B, -1)
+        gs = normalize_guidance_scale(cond_scale)              # None / one value / one per chain
+        if gs is not None and len(gs) not in (1, B):
+            raise ValueError(f"cond_scale needs one value or one per chain ({B}), got {len(gs)}")
+
+        def cut(t: torch.Tensor, rows: List[int], start: int, frames: int) -> torch.Tensor:
+            w = t[rows, start:start + frames]
+            if w.shape[1] < frames:                      # (a batch of short tails padded beyond the longest stream)
+                w = torch.cat([w, w.new_zeros((w.shape[0], frames - w.shape[1]) + tuple(w.shape[2:]))], 1)
+            return w
+
+        pieces: List[List[torch.Tensor]] = [[] for _ in range(B)]
+        tails: List[Optional[torch.Tensor]] = [None] * B       # chain -> its last overlap_len valid frames so far
+        plan = ragged_window_plan(lengths, n_poses, step)
+        n_win = [len(window_lengths(n, n_poses, step)) for n in lengths]
+        for ii, wb in enumerate(plan):
+            rows, lens, T = wb["rows"], wb["lengths"], wb["frames"]
+            a = cut(audio_emb, rows, wb["start"], T)
+            cnd = {k: cut(v, rows, wb["start"], T) for k, v in add_cond.items()}
+            inpaint_dict = {}
+            if L > 0:
+                gt = torch.zeros(len(rows), T, C, device=self.device)
+                mask = torch.zeros(len(rows), T, C, dtype=torch.bool, device=self.device)
+                inpaint_dict["outpainting_mask_any"] = ii > 0 or fix_first
+                if ii == 0 and fix_first:
+                    mask[:, :L] = True
+                    for r, b in enumerate(rows):         # (the reference's indexing: the LAST overlap_len frames of the chain's first window)
+                        gt[r, :L] = motions[b, lens[r] - L:lens[r]].to(self.device)
+                elif ii > 0:
+                    mask[:, :L] = True
+                    gt[:, :L] = torch.stack([tails[b] for b in rows], 0)
+                inpaint_dict["gt"], inpaint_dict["outpainting_mask"] = gt, mask
+            kw = {}
+            if noise_source_for_window is not None:
+                kw["noise_source"] = noise_source_for_window(ii)
+            elif seed is not None:
+                kw["seed"] = window_seed(seed, ii)
+            if row_keys is not None:
+                kw["row_keys"] = [row_keys[b] for b in rows]
+            if gs is not None:
+                kw["cond_scale"] = gs[0] if len(gs) == 1 else [gs[b] for b in rows]
+            if any(n != T for n in lens):
+                kw["lengths"] = lens
+            out = self.generate_batch(a, pid[rows], C, cnd, inpaint_dict, **kw)
+            for r, b in enumerate(rows):
+                n = lens[r]
+                if L > 0:
+                    tails[b] = out[r, n - L:n]
+                pieces[b].append(out[r, :n] if ii == n_win[b] - 1 else out[r, :step])
+        return [torch.cat(p, 0) for p in pieces]
 
     # ---- motion in-betweening: one window pinned at both ends ---------------------------------
     def sample_inbetween(self, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor],
@@ -308,7 +425,7 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
                                  add_cond: Optional[Dict[str, torch.Tensor]], n_segments: int, seed: int = 0, group=None,
                                  inputs_on_rank0_only: bool = False, max_chains_per_batch: int = 64,
                                  cond_scale: Optional[float] = None, seam_repair: bool = False,
-                                 seam_tail_blend: bool = True) -> Optional[torch.Tensor]:
+                                 seam_tail_blend: bool = True, ragged: bool = False) -> Optional[torch.Tensor]:
     """BASELINE config 4: one long feature stream ``[1, N, ...]`` sampled on all ranks of ``group``.
 
     Windows of ONE chain are sequential (window k needs the final sample of window k-1 at every denoising step,
@@ -335,6 +452,11 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
     Noise: key = hash(seed, :data:`SEAM_WINDOW`), counter high words = global seam index; windows are disjoint, so the repaired
     stream is the same whatever the world size, the rank that ran a seam, or the batching.  Frames outside the seam windows are
     those of the default mode, bit for bit.
+
+    ``ragged=True``: a rank's chains are sampled together whatever their lengths (``sample_arbitrary_len(lengths=...)``, chunked by
+    ``max_chains_per_batch``) instead of one chain batch per distinct length after another — the number of sequential windows is that
+    of the longest chain, not the sum over the distinct lengths.  Every chain is still the chain sampled alone with its id as row key;
+    the seam repair runs behind the chains as before.  Default ``False``: the grouping by length, bit for bit.
     """
     if cond_scale is not None and not isinstance(cond_scale, numbers.Real):
         raise ValueError("sample_arbitrary_len_sharded takes one scalar cond_scale for its stream")
@@ -365,7 +487,22 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
     for si in mine:
         by_len.setdefault(len(segs[si]), []).append(si)
     local: Dict[int, torch.Tensor] = {}
-    for ids in by_len.values():
+    if ragged:
+        ids = list(mine)
+        for c0 in range(0, len(ids), max_chains_per_batch):
+            chunk = ids[c0:c0 + max_chains_per_batch]
+            lens = [len(segs[i]) for i in chunk]
+
+            def stack(v: torch.Tensor) -> torch.Tensor:          # [chains, longest, ...], zero padded behind every chain
+                out = v.new_zeros((len(chunk), max(lens)) + tuple(v.shape[2:]))
+                for j, i in enumerate(chunk):
+                    out[j, :lens[j]] = v[0, segs[i].start:segs[i].stop]
+                return out
+            outs = trainer.sample_arbitrary_len(stack(audio_emb), pid[:1].expand(len(chunk), -1), {k: stack(v) for k, v in add_cond.items()},
+                                                seed=seed, row_keys=chunk, cond_scale=cond_scale, lengths=lens)
+            for j, i in enumerate(chunk):
+                local[i] = outs[j]
+    for ids in ([] if ragged else by_len.values()):
         for c0 in range(0, len(ids), max_chains_per_batch):
             chunk = ids[c0:c0 + max_chains_per_batch]
             a = torch.cat([audio_emb[:, segs[i].start:segs[i].stop] for i in chunk], 0)

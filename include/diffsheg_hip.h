@@ -111,6 +111,24 @@ int64_t dsh_weight_bytes(const dsh_ctx* ctx);
  * clips, or use fp32, which has no such limit.  (With DSH_TLS=0 or DSH_HILO=0 only the 128-token rule applies: B >= 7 needs T >= 26.) */
 int dsh_set_condition(dsh_ctx* ctx, int32_t batch, int32_t frames, const float* audio_emb, const float* person_id,
                       const float* hubert);
+/* Clips of different lengths in one batch.  The tensors are padded to frames_pad frames per clip ([B,frames_pad,...], as above) and
+ * lengths_host[b] (HOST int32, 1 .. frames_pad) is the number of valid frames of clip b.  Definition: frames [0, lengths[b]) of every
+ * output of dsh_eval / dsh_sample equal what the same clip gives evaluated / sampled ALONE at T = lengths[b]; they never depend on what
+ * the padded frames of any input hold (finite values).  Frames >= lengths[b] of dsh_sample's result are exactly 0 (rows of `trace` are
+ * not zeroed); of dsh_eval's output they are unspecified, finite for finite inputs.  (The reference has no such mode: with length < T
+ * it masks encoder_aud only, transformer.py:563, :744, and never calls itself that way.)
+ * The lengths are part of the condition (hubert_encoder and encoder_aud's hoisted attention depend on them): they are copied into a
+ * context-owned device buffer which the attention kernels and the two hubert_encoder convolutions read when they run.  Everything else in
+ * the model is per token and runs on all B x frames_pad rows: the regime decisions (graphs / pipeline / sub-batch streams, kernel
+ * families, the shape limit above) and dsh_eval_flops keep using B x frames_pad — padded rows are computed and discarded.
+ * dsh_set_condition keeps its meaning (every clip full) and clears the lengths.
+ * With dsh_sample_set_row_keys, row b advances its Philox stream by lengths[b] * channels / 4 counters per draw (its own size), so a clip
+ * draws the same noise padded as alone; lengths[b] * channels % 4 == 0 is then required.  The whole-batch stream and noise stacks are
+ * addressed by the padded shape as before.
+ * -1 before any state changes (the previous condition stays usable) on a length < 1 or > frames_pad; dsh_sample returns -1 with lengths set
+ * together with same_overlap_noisy or dsh_sample_set_tail_blend (both address the last overlap_len frames of the padded window). */
+int dsh_set_condition_ragged(dsh_ctx* ctx, int32_t batch, int32_t frames_pad, const int32_t* lengths_host, const float* audio_emb,
+                             const float* person_id, const float* hubert);
 /* eps[B,T,C] = UniDiffuser(x[B,T,C], t[B]; sqrt_alphas = (c1[B], c2[B])).  t holds ORIGINAL-scale
  * timesteps (what _WrappedModel passes); c1/c2 are sqrt(1/abar_t), sqrt(1/abar_t - 1) per sample
  * (gaussian_diffusion.py:527-532).  All device pointers; asynchronous on the context stream. */
@@ -265,6 +283,14 @@ int dsh_op_linear_attention(void* hip_stream, const float* qkv, int32_t nb, int3
 /* same on bf16 storage (uint16 bits in/out); head_dim 64 and frames <= 96 take the MFMA kernel. */
 int dsh_op_linear_attention_bf16(void* hip_stream, const void* qkv, int32_t nb, int32_t frames, int32_t D, int32_t head_dim,
                                  void* y);
+/* The same cores on a ragged batch: clip b has lens_dev[b % n_lens] valid frames (device int32; nb = n_lens, or 2 * n_lens for a
+ * CFG-doubled batch whose halves share the lengths); frames beyond them enter neither the K softmax nor k^T v, every query row is still
+ * answered.  lens_dev = NULL: the plain launch.  dtype 0 fp32 / 1 bf16 (uint16 bits).  variant 0: the kernel the denoiser's dispatch
+ * selects for the shape (bf16, head_dim 64, <= 96 frames: the tiled MFMA kernel through scratch conversions); 1: bf16 on the row-major
+ * kernels; 2: fp32 with the StylizationBlock front in the launch (D = 512, head_dim 64, <= 64 frames): y = SiLU(LN(attention) scale' +
+ * shift') with film [n_lens, 2D] = (scale' | shift') per clip (LayerNorm affine folded in by the caller). */
+int dsh_op_linear_attention_ragged(void* hip_stream, int32_t dtype, int32_t variant, const void* qkv, int32_t nb, int32_t frames, int32_t D,
+                                   int32_t head_dim, void* y, const int32_t* lens_dev, int32_t n_lens, const float* film);
 /* out = LayerNorm(x[M,D]) * gamma + beta */
 int dsh_op_layernorm(void* hip_stream, const float* x, int32_t M, int32_t D, const float* gamma, const float* beta,
                      float* out);
