@@ -81,7 +81,18 @@ SYMBOLS = {
     "dsh_op_ddim_step": (C.c_int, [_P] * 6 + [C.c_int32] * 3 + [C.c_float] * 4 + [C.c_int32] * 6),
     "dsh_op_philox_randn": (C.c_int, [_P, _P, C.c_int64, C.c_uint64, C.c_uint64]),
     "dsh_op_philox_randn_rows": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "dsh_fgd_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
+    "dsh_fgd_destroy": (C.c_int, [_P]),
+    "dsh_fgd_load_tensor": (C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), C.c_int32]),
+    "dsh_fgd_finalize": (C.c_int, [_P]),
+    "dsh_fgd_debug_num_layers": (C.c_int32, [_P]),
+    "dsh_fgd_debug_packed_layer": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P]),
+    "dsh_fgd_encode": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
+    "dsh_batch_metrics_result_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "dsh_op_batch_metrics": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
 }
+
+METRICS_HEADER = 5      # DSH_METRICS_HEADER: 8-byte words in front of the per-group diversity values of dsh_op_batch_metrics
 
 # index -> name of the entries of dsh_debug_launch_counts (include/diffsheg_hip.h); the last four are values, not counts
 LAUNCH_FAMILIES = ("tl1", "tl2_loop", "tl2_roll", "tl2_roll_hl", "tl4", "tls", "ffn_fused", "ffn_fused_sty", "attn_mfma", "attn_rowmajor",

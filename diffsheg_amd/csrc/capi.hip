@@ -10,6 +10,7 @@
 
 #include "../../include/diffsheg_hip.h"
 #include "denoiser.h"
+#include "fgd.h"
 #include "sampler.h"
 
 namespace dsh {
@@ -833,6 +834,69 @@ int dsh_op_philox_randn_rows(void* hip_stream, float* out, int32_t rows, int64_t
     if (ce != hipSuccess) dsh::set_last_error(std::string("hipMemcpyAsync failed: ") + hipGetErrorString(ce));
     else if (se != hipSuccess) { dsh::set_last_error(std::string("philox_randn_rows: hipStreamSynchronize failed: ") + hipGetErrorString(se)); if (rc == 0) rc = -2; }
     return rc;
+    API_END
+}
+
+// ---- validation metrics: FGD pose encoder + per-batch metrics (pose_encoder.hip, metrics.hip) ----------------------
+struct dsh_fgd {
+    std::unique_ptr<dsh::FgdEncoder> enc;
+};
+
+int dsh_fgd_create(int32_t n_poses, int32_t dim, int32_t vae_length, void* hip_stream, dsh_fgd** out) {
+    API_BEGIN
+    DSH_REQUIRE(out, "null argument");
+    DSH_REQUIRE(dim > 0 && vae_length > 0 && vae_length % 4 == 0, "dsh_fgd_create: dim must be positive and vae_length a positive multiple of 4");
+    DSH_REQUIRE(n_poses >= 12, "dsh_fgd_create: n_poses too small for the four convolutions (kernel 3, 3, 4 / stride 2, 3)");
+    auto h = std::make_unique<dsh_fgd>();
+    h->enc.reset(new dsh::FgdEncoder(n_poses, dim, vae_length, reinterpret_cast<hipStream_t>(hip_stream)));
+    *out = h.release();
+    return 0;
+    API_END
+}
+
+int dsh_fgd_destroy(dsh_fgd* h) {
+    API_BEGIN
+    delete h;
+    return 0;
+    API_END
+}
+
+int32_t dsh_fgd_debug_num_layers(const dsh_fgd* h) { return h ? h->enc->num_layers() : -1; }
+
+int dsh_fgd_debug_packed_layer(const dsh_fgd* h, int32_t index, int32_t* dims3, float* W, float* bias) {
+    API_BEGIN
+    DSH_REQUIRE(h, "null handle");
+    return h->enc->packed_layer(index, dims3, W, bias);
+    API_END
+}
+
+int dsh_fgd_load_tensor(dsh_fgd* h, const char* name, const float* host_data, const int64_t* shape, int32_t ndim) {
+    API_BEGIN
+    DSH_REQUIRE(h && name && (shape || ndim == 0) && ndim >= 0, "null argument");
+    return h->enc->load(name, host_data, shape, ndim);
+    API_END
+}
+
+int dsh_fgd_finalize(dsh_fgd* h) {
+    API_BEGIN
+    DSH_REQUIRE(h, "null handle");
+    return h->enc->finalize();
+    API_END
+}
+
+int dsh_fgd_encode(dsh_fgd* h, const float* x, int32_t batch, int32_t frames, float* latents) {
+    API_BEGIN
+    DSH_REQUIRE(h, "null handle");
+    return h->enc->encode(x, batch, frames, latents);
+    API_END
+}
+
+int64_t dsh_batch_metrics_result_bytes(int32_t B, int32_t T, int32_t C, int32_t b_div) { return dsh::batch_metrics_result_bytes(B, T, C, b_div); }
+
+int dsh_op_batch_metrics(void* hip_stream, const float* outputs, const float* motions, int32_t B, int32_t T, int32_t C, int32_t joint_dim,
+                         int32_t b_div, void* result_dev) {
+    API_BEGIN
+    return dsh::launch_batch_metrics(outputs, motions, B, T, C, joint_dim, b_div, result_dev, reinterpret_cast<hipStream_t>(hip_stream));
     API_END
 }
 

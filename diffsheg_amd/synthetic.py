@@ -47,3 +47,15 @@ class SeededNoise:
     def randn(self, shape) -> torch.Tensor:
         self.count += 1
         return _TORCH_RANDN(*tuple(shape), generator=self.gen)
+
+
+def make_motion_pair(cfg, batch: int, seed: int, frames: int | None = None):
+    """Two related standardised-motion batches ``[batch, frames, net_dim_pose]`` (CPU fp32) for the validation-metric tests:
+    ``motions = x`` ~ N(0, 1) and ``outputs = 0.8 x + 0.3 noise``, so that MSE, PCK (neither 0 nor 1), diversity and the Frechet
+    distance of their latents are all non-trivial.  Returns ``(outputs, motions)``."""
+    T = int(frames if frames is not None else cfg.n_poses)
+    g = torch.Generator(device="cpu")
+    g.manual_seed(int(seed))
+    x = torch.randn(batch, T, cfg.net_dim_pose, generator=g)
+    n = torch.randn(batch, T, cfg.net_dim_pose, generator=g)
+    return (0.8 * x + 0.3 * n).contiguous(), x.contiguous()

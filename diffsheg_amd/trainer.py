@@ -4,7 +4,9 @@ window chain of ``test_arbitrary_len`` / ``test_custom_aud``
 ddpm_beat_trainer.py:185-220, :932-1039), plus the sharding of independent chains over ranks
 (the reference shards test videos with a DistributedSampler, ddpm_show_trainer.py:743-750).
 
-Training, metrics, BVH/JSON writers, HuBERT extraction and checkpoint I/O are out of scope.
+The validation loop's tail (ddpm_show_trainer.py:440-583: FGD encoder, MSE / PCK / diversity meters) is ``validate_batch`` /
+``validation_summary`` on top of :mod:`diffsheg_amd.metrics`.  Training, BVH/JSON writers, HuBERT extraction and checkpoint saving
+are out of scope.
 """
 from __future__ import annotations
 
@@ -116,6 +118,9 @@ class DDPMTrainer:
         # the reference hard-codes 'ddim25' here (ddpm_show_trainer.py:73, ddpm_beat_trainer.py:76)
         self.diffusion_ddim_val = SpacedDiffusion(use_timesteps=space_timesteps(self.diffusion_steps, "ddim25"),
                                                   rescale_timesteps=False, **kw)
+        # validation (ddpm_show_trainer.py:440-583): eval_model = a metrics.HalfEmbeddingNet, or None for no FGD (--no_fgd)
+        self.eval_model = eval_model
+        self.reset_validation()
 
     def generate_batch(self, audio_emb, p_id, dim_pose, add_cond={}, inpaint_dict=None, cond_scale=None, lengths=None, **sampler_kw):
         """ddpm_show_trainer.py:163-198.  ``sampler_kw`` (noise_source= / seed=) is this build's
@@ -138,6 +143,94 @@ class DDPMTrainer:
                                                             progress=True, model_kwargs=model_kwargs, **sampler_kw)
         return self.diffusion.p_sample_loop(self.encoder, (B, T, dim_pose), clip_denoised=False, progress=True,
                                             model_kwargs=model_kwargs, **sampler_kw)
+
+    # ---- validation loop tail: FGD encoder + MSE / PCK / diversity (ddpm_show_trainer.py:440-583) -----------------------
+    def reset_validation(self) -> None:
+        """Fresh meters (the reference creates them at the top of every validation pass)."""
+        self._val_batches: List[dict] = []
+
+    def load_fid_net(self, path: str, map_location="cpu"):
+        """ddpm_show_trainer.py:294-306: the FGD autoencoder from ``checkpoint['model_state']`` or ``['state_dict']``, with or without
+        a ``module.`` prefix, as ``self.eval_model`` (a :class:`diffsheg_amd.metrics.HalfEmbeddingNet` on this trainer's device)."""
+        from .metrics import HalfEmbeddingNet
+        checkpoint = torch.load(path, map_location=map_location)
+        state_dict = checkpoint["model_state"] if "model_state" in checkpoint else checkpoint["state_dict"]
+        self.eval_model = HalfEmbeddingNet(self.opt, state_dict, device=self.device)
+        return self.eval_model
+
+    @property
+    def pck_joint_dim(self) -> int:
+        """Trailing "joint" axis of the PCK: SHOW views the tensors as [B, T, C, 1], BEAT as [B, T, C / 3, 3]."""
+        return 1 if getattr(self.opt, "dataset_name", "talkshow") == "talkshow" else 3
+
+    def validate_batch(self, audio_emb, motions, p_id, add_cond={}, lengths=None, **sampler_kw) -> torch.Tensor:
+        """One iteration of the reference's validation loop behind the data loader (ddpm_show_trainer.py:493-550): the reference's
+        ``inpaint_dict`` (with ``opt.overlap_len > 0`` the first ``overlap_len`` frames are pinned to ``motions``), ``generate_batch``,
+        both sides through ``eval_model`` (first ``n_poses`` frames; skipped when it is ``None``), MSE / PCK / diversity.  Everything
+        stays on the device and nothing synchronises: the batch's few numbers and its latents are fetched by
+        :meth:`validation_summary`.  Returns the samples ``[B, T, C]`` — bit-identical to ``generate_batch`` alone with the same
+        arguments.  ``sampler_kw`` as for :meth:`generate_batch` (``seed=``, ``noise_source=``, ``cond_scale=``, ...)."""
+        from .metrics import batch_metrics
+        if lengths is not None:
+            raise ValueError("validate_batch takes full clips only: the FGD encoder is defined for n_poses frames, and MSE / PCK / "
+                             "diversity of padded frames would be meaningless (score ragged batches clip by clip)")
+        opt = self.opt
+        C_, L = int(opt.net_dim_pose), int(opt.overlap_len)
+        motions = motions.to(device=self.device, dtype=torch.float32)
+        if motions.shape[0] < 2:
+            raise ValueError("validate_batch needs at least two clips: the reference's diversity divides by B_div (B_div - 1)")
+        if self.eval_model is not None and motions.shape[1] < self.eval_model.n_poses:
+            raise ValueError(f"clips have {motions.shape[1]} frames, the FGD encoder needs n_poses = {self.eval_model.n_poses}")
+        inpaint_dict = {}
+        if L > 0:
+            mask = torch.zeros_like(motions, dtype=torch.bool)
+            mask[..., :L, :] = True
+            inpaint_dict = {"gt": motions, "outpainting_mask": mask, "outpainting_mask_any": True}
+        outputs = self.generate_batch(audio_emb, p_id, C_, add_cond, inpaint_dict, **sampler_kw)
+        if isinstance(outputs, dict):
+            outputs = outputs["sample"]
+        rec = batch_metrics(outputs, motions, self.pck_joint_dim)
+        if self.eval_model is not None:
+            rec["latent_out"] = self.eval_model(outputs)
+            rec["latent_ori"] = self.eval_model(motions)
+        self._val_batches.append(rec)
+        return outputs
+
+    def validation_summary(self, group=None) -> Dict[str, float]:
+        """End of a validation pass (ddpm_show_trainer.py:552-571): one device-to-host copy of every batch's few numbers (and the
+        latents), the meters, the Frechet distance of all latents of this rank, and — in an initialised process group — the
+        reference's ``all_reduce`` of every meter (FGD is computed per rank and averaged through its meter, as there).  Returns
+        ``{"MSE", "PCK", "Diversity"}`` and, with an ``eval_model``, ``"FGD"``; the meters stay readable as ``self.val_meters``."""
+        import torch.distributed as dist
+        from .metrics import AverageMeter, frechet_distance
+        if not self._val_batches:
+            raise ValueError("validation_summary: no validate_batch call since the last reset_validation")
+        meters = {k: AverageMeter(k) for k in ("diversity", "pck", "mse", "fgd")}
+        # one small tensor per batch: [mse, pck, diversity per group ...], gathered in a single copy
+        flat = torch.cat([torch.cat([r["mse"].reshape(1), r["pck"].reshape(1), r["diversity"]]) for r in self._val_batches]).cpu().tolist()
+        pos = 0
+        for r in self._val_batches:
+            n_groups = int(r["diversity"].numel())
+            mse_val, pck_val = flat[pos], flat[pos + 1]
+            for d in flat[pos + 2:pos + 2 + n_groups]:
+                meters["diversity"].update(d, r["b_div"])
+            meters["mse"].update(mse_val, r["batch"])
+            meters["pck"].update(pck_val, r["batch"])
+            pos += 2 + n_groups
+        has_fgd = "latent_out" in self._val_batches[0]
+        if has_fgd:
+            lat_out = torch.cat([r["latent_out"] for r in self._val_batches]).cpu().numpy()
+            lat_ori = torch.cat([r["latent_ori"] for r in self._val_batches]).cpu().numpy()
+            meters["fgd"].update(frechet_distance(lat_out, lat_ori))
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            for k, m in meters.items():
+                if k != "fgd" or has_fgd:
+                    m.all_reduce(group)
+        self.val_meters = meters
+        out = {"MSE": meters["mse"].avg, "PCK": meters["pck"].avg, "Diversity": meters["diversity"].avg}
+        if has_fgd:
+            out["FGD"] = meters["fgd"].avg
+        return out
 
     # ---- H2: arbitrary-length chain ---------------------------------------------------------
     def sample_arbitrary_len(self, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor],

@@ -189,3 +189,96 @@ def make_cross_attention_state_dict(seed: int, latent_dim: int = 512, aud_latent
                          ("proj_out.out_layers.2", (D, D))):
         sd[name + ".weight"], sd[name + ".bias"] = lin(n, k)
     return sd
+
+
+# ---- FGD autoencoder (HalfEmbeddingNet, models/motion_autoencoder.py:192-204) --------------------------------------------
+FID_VAE_LENGTH = 300          # runner.py:170,222: vae_length on both datasets
+
+
+def fid_dims(cfg_or_opt) -> Tuple[int, int, int]:
+    """``(n_poses, net_dim_pose, vae_length)`` from a :class:`DiffSHEGConfig` or a reference-style ``opt`` namespace."""
+    return (int(cfg_or_opt.n_poses), int(cfg_or_opt.net_dim_pose), int(getattr(cfg_or_opt, "vae_length", FID_VAE_LENGTH)))
+
+
+def fid_conv_frames(n_poses: int) -> List[int]:
+    """Frames after net.0 .. net.3 of PoseEncoderConv (kernel 3, 3, 4 / stride 2, 3; no padding)."""
+    t1, t2 = n_poses - 2, n_poses - 4
+    t3 = (t2 - 4) // 2 + 1
+    return [t1, t2, t3, t3 - 2]
+
+
+def fid_out_net_layout(n_poses: int, base: int) -> Tuple[List[int], List[int], List[int]]:
+    """``(widths, linear indices, batch-norm indices)`` of ``pose_encoder.out_net`` (motion_autoencoder.py:48-83): ``widths[i]`` ->
+    ``widths[i + 1]`` is the Linear at ``out_net.<linear[i]>``, followed by the BatchNorm1d at ``out_net.<bn[i]>`` (-1: none).  The
+    34-frame network has three Linears, the 88- and 64-frame ones four."""
+    flat = fid_conv_frames(n_poses)[3] * base
+    if n_poses == 34:
+        return [flat, 4 * base, 2 * base, base], [0, 3, 6], [1, 4, -1]
+    return [flat, 12 * base, 4 * base, 2 * base, base], [0, 2, 5, 8], [1, 3, 6, -1]
+
+
+def _batchnorm(prefix: str, n: int) -> List[Spec]:
+    return [(f"{prefix}.weight", (n,), "ln_w"), (f"{prefix}.bias", (n,), "ln_b"), (f"{prefix}.running_mean", (n,), "bn_mean"),
+            (f"{prefix}.running_var", (n,), "bn_var"), (f"{prefix}.num_batches_tracked", (), "counter")]
+
+
+def _conv(prefix: str, out_c: int, in_c: int, k: int, kind: str) -> List[Spec]:
+    return [(f"{prefix}.weight", (out_c, in_c, k), kind), (f"{prefix}.bias", (out_c,), "fid_bias")]
+
+
+def fid_state_dict_spec(cfg_or_opt) -> List[Spec]:
+    """All ``HalfEmbeddingNet`` state-dict entries in the reference's registration order: ``pose_encoder.*`` (what the FGD latent
+    uses, ``fc_logvar`` excepted) and ``decoder.*`` (loaded with ``strict=True`` by the reference, never evaluated)."""
+    n_poses, dim, base = fid_dims(cfg_or_opt)
+    s: List[Spec] = []
+    chans = [(dim, base, 3), (base, 2 * base, 3), (2 * base, 2 * base, 4)]
+    for i, (cin, cout, k) in enumerate(chans):
+        s += _conv(f"pose_encoder.net.{i}.0", cout, cin, k, "fid_leaky") + _batchnorm(f"pose_encoder.net.{i}.1", cout)
+    s += _conv("pose_encoder.net.3", base, 2 * base, 3, "fid_linear")
+    widths, lin, bn = fid_out_net_layout(n_poses, base)
+    for i, li in enumerate(lin):
+        s += [(f"pose_encoder.out_net.{li}.weight", (widths[i + 1], widths[i]), "fid_linear"),
+              (f"pose_encoder.out_net.{li}.bias", (widths[i + 1],), "fid_bias")]
+        if bn[i] >= 0:
+            s += _batchnorm(f"pose_encoder.out_net.{bn[i]}", widths[i + 1])
+    for name in ("fc_mu", "fc_logvar"):
+        s += [(f"pose_encoder.{name}.weight", (base, base), "fid_linear"), (f"pose_encoder.{name}.bias", (base,), "fid_bias")]
+    d = base // 8
+    s += [("decoder.pre_net.0.weight", (2 * base, base), "fid_linear"), ("decoder.pre_net.0.bias", (2 * base,), "fid_bias")]
+    s += _batchnorm("decoder.pre_net.1", 2 * base)
+    s += [("decoder.pre_net.3.weight", (d * n_poses, 2 * base), "fid_linear"), ("decoder.pre_net.3.bias", (d * n_poses,), "fid_bias")]
+    s += _conv("decoder.net.0", d, base, 3, "fid_linear")[:1] + [("decoder.net.0.bias", (base,), "fid_bias")] + _batchnorm("decoder.net.1", base)
+    s += _conv("decoder.net.3", base, base, 3, "fid_linear") + _batchnorm("decoder.net.4", base)
+    s += _conv("decoder.net.6", 2 * base, base, 3, "fid_linear") + _conv("decoder.net.7", dim, 2 * base, 3, "fid_linear")
+    return s
+
+
+def make_synthetic_fid_state_dict(cfg_or_opt, seed: int = 4321) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded fp32 CPU ``HalfEmbeddingNet.state_dict()`` under the reference's key names (loads with ``strict=True``), every tensor
+    from its own generator keyed by (seed, name).  Weights are N(0, gain^2 / fan_in) — variance preserving, gain sqrt(2 / 1.04) in
+    front of a LeakyReLU(0.2) — so that the latents are O(1) and the Frechet distance of the two related inputs of
+    tests/golden/make_golden_metrics.py is ~40 (torch's default init gives |z| ~ 0.25 and an FGD of ~2e-4, useless for a relative gate);
+    BatchNorm affine and running statistics are non-trivial."""
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    for key, shape, kind in fid_state_dict_spec(cfg_or_opt):
+        g = _gen(seed, key)
+        if kind in ("fid_linear", "fid_leaky"):
+            fan_in = 1
+            for s_ in shape[1:]:
+                fan_in *= s_
+            gain = math.sqrt(2.0 / 1.04) if kind == "fid_leaky" else 1.0
+            t = torch.randn(shape, generator=g) * (gain / math.sqrt(fan_in))
+        elif kind == "fid_bias":
+            t = 0.1 * torch.randn(shape, generator=g)
+        elif kind == "ln_w":
+            t = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        elif kind in ("ln_b", "bn_mean"):
+            t = 0.1 * torch.randn(shape, generator=g)
+        elif kind == "bn_var":
+            t = 0.5 + torch.rand(shape, generator=g)
+        elif kind == "counter":
+            t = torch.zeros((), dtype=torch.int64)
+        else:  # pragma: no cover
+            raise AssertionError(kind)
+        sd[key] = t.contiguous()
+    return sd

@@ -308,6 +308,52 @@ int dsh_op_philox_randn(void* hip_stream, float* out, int64_t n, uint64_t seed, 
 int dsh_op_philox_randn_rows(void* hip_stream, float* out, int32_t rows, int64_t n_row, uint64_t seed, uint64_t offset,
                              const uint64_t* row_keys_host);
 
+/* ---- validation metrics (trainers/ddpm_show_trainer.py:440-583, ddpm_beat_trainer.py:489-644) ------------------------- */
+/* The FGD pose encoder: HalfEmbeddingNet.forward = PoseEncoderConv in eval() mode (models/motion_autoencoder.py:38-100, 192-204), fp32 on
+ * the exact-fp32 matrix pipe.  A handle of its own, independent of a dsh_ctx context (an eval model is another network with other weights), bound
+ * to one (device, stream), not thread-safe.  n_poses = frames per clip the network is built for (88, 64 and 34 have an out_net in the
+ * reference; every other length is built like 88 / 64: four Linears behind the flatten), dim = channels per frame (any width),
+ * vae_length = the reference's `base` (300), a multiple of 4.  hip_stream as for dsh_create (NULL: a stream of its own).  No device is
+ * touched before dsh_fgd_finalize. */
+typedef struct dsh_fgd dsh_fgd;
+int dsh_fgd_create(int32_t n_poses, int32_t dim, int32_t vae_length, void* hip_stream, dsh_fgd** out);
+int dsh_fgd_destroy(dsh_fgd* h);
+/* Weights by the state-dict key names of HalfEmbeddingNet (fp32 host memory, copied): pose_encoder.net.{0,1,2}.0.{weight,bias} (Conv1d
+ * [out, in, k]), pose_encoder.net.{0,1,2}.1.{weight,bias,running_mean,running_var} (BatchNorm1d), pose_encoder.net.3.{weight,bias},
+ * pose_encoder.out_net.<i>.* (Linears and BatchNorms at the reference's indices), pose_encoder.fc_mu.{weight,bias}.  decoder.*,
+ * pose_encoder.fc_logvar.* and *.num_batches_tracked are accepted and ignored (the reference loads them and forward() never uses them).
+ * -1 on an unknown key or a shape other than the network's. */
+int dsh_fgd_load_tensor(dsh_fgd* h, const char* name, const float* host_data, const int64_t* shape, int32_t ndim);
+/* Builds the device layout: eval-mode BatchNorm folded into the conv / Linear in front of it (fp64), conv weights repacked to
+ * [out, k * in] (tap-major, channel minor: the implicit-GEMM row of channels-last activations), the first Linear's columns permuted from
+ * the reference's channel-major flatten (c * frames + t) to channels-last (t * vae_length + c), every K padded with zeros to 32 floats.
+ * -1 naming the first missing key. */
+int dsh_fgd_finalize(dsh_fgd* h);
+/* Test helper, host only (runs without a GPU): layer `index` exactly as dsh_fgd_finalize would upload it, once every tensor is loaded and
+ * before dsh_fgd_finalize (which releases the staged copies).  Layers 0 .. 3 are the convolutions, then the out_net Linears, fc_mu last
+ * (dsh_fgd_debug_num_layers).  dims3 = {N, K, K padded}; W [N, K padded] and bias [N] are nullable host buffers. */
+int32_t dsh_fgd_debug_num_layers(const dsh_fgd* h);
+int dsh_fgd_debug_packed_layer(const dsh_fgd* h, int32_t index, int32_t* dims3, float* W, float* bias);
+/* latents[B, vae_length] = mu(x[:, :n_poses, :]) for x [B, frames, dim] (device fp32), frames >= n_poses: only the first n_poses frames
+ * of each clip are read (outputs[:, :88, :] in the reference), whatever the rest holds.  Asynchronous on the handle's stream; -1 (nothing
+ * launched) when frames < n_poses.  A larger batch than any before grows the handle's buffers, which waits for the stream once. */
+int dsh_fgd_encode(dsh_fgd* h, const float* x, int32_t batch, int32_t frames, float* latents);
+
+/* MSE, PCK and diversity of one validation batch (ddpm_show_trainer.py:516-550) from outputs / motions [B, T, C] (device fp32) in three
+ * launches on hip_stream; nothing synchronises, fixed-order reductions (two runs: identical bits).
+ *   diff = outputs - motions;  MSE = mean(diff^2) (fp64 accumulation);
+ *   PCK  = mean over the B T C / joint_dim joints of [sqrt(sum_j diff_j^2) < 0.5], fp32 as numpy computes it: joint_dim 1 = per element
+ *          (SHOW: unsqueeze(-1)), 3 = per consecutive channel triplet (BEAT: reshape(B, T, C / 3, 3)); C % joint_dim == 0;
+ *   diversity of group g (clips [g b_div, (g + 1) b_div), g < B / b_div: the incomplete last group is dropped, as in the reference)
+ *          = 2 / (b_div (b_div - 1)) * sum_{i<j} mean_e |o_i[e] - o_j[e]|.  The reference uses b_div = min(50, B); 2 <= b_div <= min(B, 128).
+ * result_dev: device buffer of dsh_batch_metrics_result_bytes(B, T, C, b_div) bytes, 8-byte aligned, 8-byte words:
+ *   [0] double  sum diff^2          [1] int64  PCK count (joints below 0.5)      [2] double MSE       [3] double PCK
+ *   [4] int64   groups = B / b_div  [5 .. 5 + groups) double diversity per group;   everything behind is scratch (block partials). */
+#define DSH_METRICS_HEADER 5
+int64_t dsh_batch_metrics_result_bytes(int32_t B, int32_t T, int32_t C, int32_t b_div);
+int dsh_op_batch_metrics(void* hip_stream, const float* outputs, const float* motions, int32_t B, int32_t T, int32_t C, int32_t joint_dim,
+                         int32_t b_div, void* result_dev);
+
 #ifdef __cplusplus
 }
 #endif
