@@ -95,6 +95,7 @@ SYMBOLS = {
 METRICS_HEADER = 5      # DSH_METRICS_HEADER: 8-byte words in front of the per-group diversity values of dsh_op_batch_metrics
 
 # index -> name of the entries of dsh_debug_launch_counts (include/diffsheg_hip.h); the last four are values, not counts
+# (indices 4 and 7 are retired: their kernel forms were removed, the counts stay 0; the names keep the indices fixed)
 LAUNCH_FAMILIES = ("tl1", "tl2_loop", "tl2_roll", "tl2_roll_hl", "tl4", "tls", "ffn_fused", "ffn_fused_sty", "attn_mfma", "attn_rowmajor",
                    "gemm_f32_fewrow", "gemm_f32_tiled", "gemm_f32_pro", "eval_streams", "sample_streams", "sample_graph", "sample_pipe")
 

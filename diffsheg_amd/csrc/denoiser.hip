@@ -28,56 +28,50 @@ class Denoiser final : public DenoiserBase {
   public:
     Denoiser(const ModelConfig& c, hipStream_t s) : cfg(c), st(s), gs_dbl(c.classifier_free && c.cond_scale != 1.0f) {
         const char* t2 = getenv("DSH_TL2");
-        tl2_on = !(t2 && atoi(t2) == 0);          // LDS-DMA token-per-lane kernels (tl2.hip); DSH_TL2=0: first generation
-        tl2_all = t2 && atoi(t2) == 2;            // DSH_TL2=2: also for the HBM-bound (residual) instantiations
+        sw.tl2_on = !(t2 && atoi(t2) == 0);          // LDS-DMA token-per-lane kernels (tl2.hip); DSH_TL2=0: first generation
+        sw.tl2_all = t2 && atoi(t2) == 2;            // DSH_TL2=2: also for the HBM-bound (residual) instantiations
         const char* ff = getenv("DSH_FFN_FUSE");
-        ffn_fuse = tl2_on && !(ff && atoi(ff) == 0);
+        sw.ffn_fuse = sw.tl2_on && !(ff && atoi(ff) == 0);
         // alternate the row order of consecutive token-per-lane launches (tl_block_index, tl_common.h): measured 613.2 -> 609.6 ms per
         // step on three streams, 687 -> 673 ms on one (round 4); DSH_REV=0 disables it
         const char* rv = getenv("DSH_REV");
-        rev_on = !(rv && atoi(rv) == 0);
+        sw.rev_on = !(rv && atoi(rv) == 0);
         const char* fv = getenv("DSH_FFN_V");     // fused FFN kernel generation: 3 (default, tl3_ffn.hip) or 2 (tl2.hip); fixes the weight stream order
-        ffn_ver = (fv && atoi(fv) == 2) ? 2 : 3;
+        sw.ffn_ver = (fv && atoi(fv) == 2) ? 2 : 3;
         // residual stream of the token-per-lane path as two bf16 planes (hi = the old bf16 shadow, lo = bf16(h - hi); tl_common.h)
         // instead of fp32 + shadow: 4 instead of 6 bytes per value written by every residual-carrying launch.  DSH_HILO=0: fp32.
         const char* hl = getenv("DSH_HILO");
-        hilo = ffn_ver == 3 && !tl2_all && !(hl && atoi(hl) == 0);
+        sw.hilo = sw.ffn_ver == 3 && !sw.tl2_all && !(hl && atoi(hl) == 0);
         // window-chain batches: 32-token blocks, one tile per wave (tl_small.hip) up to a few thousand token rows per launch; DSH_TLS=0: off
         const char* ts = getenv("DSH_TLS");
         const char* tr = getenv("DSH_TLS_ROWS");
-        tls_on = tl2_on && hilo && !(ts && atoi(ts) == 0);
+        sw.tls_on = sw.tl2_on && sw.hilo && !(ts && atoi(ts) == 0);
         const char* sk = getenv("DSH_DBG_SKIP");   // bench experiment only (results are garbage): skip launches of a layer, bit 0 feat_proj.1, 1 feat_proj.3,
-        dbg_skip = sk ? atoi(sk) : 0;              // 2 q|k|v, 3 attention, 4 StylizationBlock (attention branch), 5 fused FFN — what each launch costs the STEP
-        if (dbg_skip || getenv("DSH_SPLIT_AT")) {
+        sw.dbg_skip = sk ? atoi(sk) : 0;              // 2 q|k|v, 3 attention, 4 StylizationBlock (attention branch), 5 fused FFN — what each launch costs the STEP
+        if (sw.dbg_skip || getenv("DSH_SPLIT_AT")) {
             static bool warned = false;
-            if (!warned) { fprintf(stderr, "[diffsheg_hip] WARNING: bench-only switches are set (DSH_DBG_SKIP=%d%s): %s\n", dbg_skip, getenv("DSH_SPLIT_AT") ? ", DSH_SPLIT_AT" : "",
-                                   dbg_skip ? "launches are skipped, results are GARBAGE" : "sub-batch boundaries are moved"); warned = true; }
+            if (!warned) { fprintf(stderr, "[diffsheg_hip] WARNING: bench-only switches are set (DSH_DBG_SKIP=%d%s): %s\n", sw.dbg_skip, getenv("DSH_SPLIT_AT") ? ", DSH_SPLIT_AT" : "",
+                                   sw.dbg_skip ? "launches are skipped, results are GARBAGE" : "sub-batch boundaries are moved"); warned = true; }
         }
-        // the attention branch's StylizationBlock as the first stage of the fused FFN launch (tl3_ffn_kernel<..., STY>): bit-identical, built and
-        // measured in round 5 — 577.3 ms per 950-clip step against 557.7 with the separate launch (profiles/r05_k_ab_ffn_sty.txt; the fused launch
-        // 753 us against 486 + 182): with every CU in the stage at once its 16 phases run at the HBM wall (2.9 k cycles per phase, like pass B)
-        // instead of in the shadow of other CUs' compute phases.  Off unless DSH_FFN_STY=1.
-        const char* fs = getenv("DSH_FFN_STY");
-        ffn_sty = fs && atoi(fs) != 0;
         const char* th = getenv("DSH_TL2_HL");
-        tl2_hl = tl2_on && hilo && !(th && atoi(th) == 0);
-        if (tr && atoi(tr) > 0) tls_rows = atoi(tr);
+        sw.tl2_hl = sw.tl2_on && sw.hilo && !(th && atoi(th) == 0);
+        if (tr && atoi(tr) > 0) sw.tls_rows = atoi(tr);
         // fp32 parity path (round 6): LayerNorm folded into q|k|v and feat_proj.1 with the row moments taken in the GEMM's own staging, the
         // StylizationBlock front (LN -> FiLM -> SiLU) in the A-operand staging of its Linear (gemm_f32_pro.hip) instead of four row kernels per
         // layer.  DSH_F32_FUSE=0: the separate row kernels of rounds 1 - 5.
         const char* f3 = getenv("DSH_F32_FUSE");
         // Bits (measurement): 1 folded LayerNorms, 2 StylizationBlock fronts, 4 the front-less Linears on the same software-pipelined main loop,
         // 8 (with 2) the attention branch's StylizationBlock front inside the attention launch (attention.hip) instead of its Linear's staging.
-        f32_bits = (std::is_same<T, float>::value && c.latent_dim == 512) ? (f3 ? atoi(f3) & 15 : 15) : 0;
-        f32_fuse = f32_bits != 0;
+        sw.f32_bits = (std::is_same<T, float>::value && c.latent_dim == 512) ? (f3 ? atoi(f3) & 15 : 15) : 0;
+        sw.f32_fuse = sw.f32_bits != 0;
         // ... above the few-row GEMM's range only (gemm.hip: K split over the waves of a block up to DSH_GEMM_KSPLIT = 512 rows — at 34 rows the 64 x 64
         // tile launches measured 3.50 vs 2.62 ms per configs[0] evaluation); DSH_GEMM_KSPLIT=0, the reproducible mode, puts every batch size on them
-        { const char* ks = getenv("DSH_GEMM_KSPLIT"); f32_min_rows = ks ? atoi(ks) : 512; }
+        { const char* ks = getenv("DSH_GEMM_KSPLIT"); sw.f32_min_rows = ks ? atoi(ks) : 512; }
     }
     // second instance on another stream that shares (does not own) the finalized weights; own workspace
     Denoiser(const Denoiser& o, hipStream_t s)
         : cfg(o.cfg), st(s), wbytes(o.wbytes), finalized(o.finalized), aud_te0(o.aud_te0), aud_te2(o.aud_te2),
-          aud_film(o.aud_film), aud_stream(o.aud_stream), aud_ap_bias(o.aud_ap_bias), aud_bias(o.aud_bias), aud_film_g(o.aud_film_g), aud_film_b(o.aud_film_b), aud(o.aud), exp_(o.exp_), ges_(o.ges_), tl2_on(o.tl2_on), tl2_all(o.tl2_all), ffn_fuse(o.ffn_fuse), ffn_ver(o.ffn_ver), hilo(o.hilo), tls_on(o.tls_on), tl2_hl(o.tl2_hl), f32_bits(o.f32_bits), f32_min_rows(o.f32_min_rows), f32_fuse(o.f32_fuse), dbg_skip(o.dbg_skip), ffn_sty(o.ffn_sty), tls_rows(o.tls_rows), rev_on(o.rev_on), gs(o.gs), gs_row(o.gs_row), gs_dbl(o.gs_dbl) {
+          aud_film(o.aud_film), aud_stream(o.aud_stream), aud_ap_bias(o.aud_ap_bias), aud_bias(o.aud_bias), aud_film_g(o.aud_film_g), aud_film_b(o.aud_film_b), aud(o.aud), exp_(o.exp_), ges_(o.ges_), sw(o.sw), gs(o.gs), gs_row(o.gs_row), gs_dbl(o.gs_dbl) {
         for (Encoder* E : {&exp_, &ges_}) { E->pid_part = nullptr; E->pid_part_s = nullptr; E->hub = nullptr; E->film_tab = nullptr; E->aproj_buf = nullptr; }
     }
     DenoiserBase* clone_shared(hipStream_t s) override { return finalized ? new Denoiser(*this, s) : nullptr; }
@@ -100,9 +94,9 @@ class Denoiser final : public DenoiserBase {
     // FiLM row of each token's clip from memory.)
     int check_shape(int B, int T_) const override {
         if (!tl_path() || B <= 0 || T_ <= 0) return 0;
-        if ((tls_on && tls_film_clips_ok(T_, B)) || tl_linear_film_clips_ok(T_, B)) return 0;
+        if ((sw.tls_on && tls_film_clips_ok(T_, B)) || tl_linear_film_clips_ok(T_, B)) return 0;
         set_last_error("unsupported shape: the bf16 path evaluates windows of " + std::to_string(T_) + " frames in batches of at most 6 clips (got " +
-                       std::to_string(B) + "); batches of 7 and more clips need windows of at least " + (tls_on ? "11" : "26") +
+                       std::to_string(B) + "); batches of 7 and more clips need windows of at least " + (sw.tls_on ? "11" : "26") +
                        " frames (FiLM rows staged per token block) - split the batch, or use the fp32 path");
         return -1;
     }
@@ -182,24 +176,26 @@ class Denoiser final : public DenoiserBase {
     int notify_at = 0, tl_launches = 0;
 
     Lin aud_te0, aud_te2, aud_film;
-    T* aud_stream = nullptr; float* aud_ap_bias = nullptr; bool aproj_in_tail = false; float* aud_bias = nullptr; float* aud_film_g = nullptr; float* aud_film_b = nullptr;   // fused encoder_aud tail (tl_aud.hip; bf16 path)
+    T* aud_stream = nullptr; float* aud_ap_bias = nullptr; bool aproj_done = false; float* aud_bias = nullptr; float* aud_film_g = nullptr; float* aud_film_b = nullptr;   // fused encoder_aud tail (tl_aud.hip; bf16 path)
     Layer aud;
     Encoder exp_, ges_;
-    bool tl2_on = true, tl2_all = false, ffn_fuse = true;
-    int ffn_ver = 3;
-    bool hilo = false;
-    bool tls_on = false;
-    bool tl2_hl = false;                 // residual-carrying launches on the rolling LDS-DMA loop (round 5)
-    int f32_bits = 0, f32_min_rows = 512;
-    int f32_now() const { return batch * frames > f32_min_rows ? f32_bits : 0; }   // the bits that apply to the current condition's batch
-    bool f32_fuse = false;               // fp32 path: LayerNorm / StylizationBlock fronts inside the GEMM launches (round 6, gemm_f32_pro.hip)
-    int expr_ld() const { return f32_fuse ? round_up(cfg.expression_dim, 32) : cfg.expression_dim; }   // row stride of expr_x0 (zero padded to whole K tiles for the fused concat)
-    int dbg_skip = 0;
-    bool ffn_sty = false;                // the attention branch's StylizationBlock as the first stage of the fused FFN launch (round 5, off)
-    static constexpr size_t FFN_STREAM_OFF = (size_t)16 * 16384;   // elements of L.ffn_stream in front of the FFN's own 80 chunks
-    int tls_rows = 0;                // DSH_TLS_ROWS: one row limit for every instantiation (0: the measured per-instantiation limits in tl())
-    bool rev_on = false; int rev_ctr = 0;
-    int next_rev() { return rev_on ? (rev_ctr++ & 1) : 0; }
+    // the switches read from the environment once, at construction (a clone takes its parent's)
+    struct Switches {
+        bool tl2_on = true, tl2_all = false, ffn_fuse = true;
+        int ffn_ver = 3;
+        bool hilo = false;
+        bool tls_on = false;
+        bool tl2_hl = false;             // residual-carrying launches on the rolling LDS-DMA loop (round 5)
+        int f32_bits = 0, f32_min_rows = 512;
+        bool f32_fuse = false;           // fp32 path: LayerNorm / StylizationBlock fronts inside the GEMM launches (round 6, gemm_f32_pro.hip)
+        int dbg_skip = 0;
+        int tls_rows = 0;                // DSH_TLS_ROWS: one row limit for every instantiation (0: the measured per-instantiation limits in tl())
+        bool rev_on = false;
+    } sw;
+    int f32_now() const { return batch * frames > sw.f32_min_rows ? sw.f32_bits : 0; }   // the bits that apply to the current condition's batch
+    int expr_ld() const { return sw.f32_fuse ? round_up(cfg.expression_dim, 32) : cfg.expression_dim; }   // row stride of expr_x0 (zero padded to whole K tiles for the fused concat)
+    int rev_ctr = 0;
+    int next_rev() { return sw.rev_on ? (rev_ctr++ & 1) : 0; }
 
     // ---- workspace (grow-only) ----
     int capB = 0, capT = 0;
@@ -225,7 +221,7 @@ class Denoiser final : public DenoiserBase {
     float* aud_x2 = nullptr;         // [Mc, 128] fp32: 2 * mel features (encoder_aud's residual input)
     T* aud_y = nullptr;              // [Mc, 128]: its self-attention output, in front of sa_block.proj_out
     float* h0 = nullptr;             // row-major joint_embed output, seed of the tiled residual stream (token-per-lane path)
-    T* hlo = nullptr;                // lo plane of the residual stream (hilo; the hi plane is h16)
+    T* hlo = nullptr;                // lo plane of the residual stream (sw.hilo; the hi plane is h16)
     bool tl_path() const { return !ges_.layers.empty() && ges_.layers[0].tl; }
     std::vector<Encoder*> encs() { return cfg.single_transformer ? std::vector<Encoder*>{&ges_} : std::vector<Encoder*>{&exp_, &ges_}; }
 
@@ -350,7 +346,7 @@ class Denoiser final : public DenoiserBase {
         flops_acc += fl;
         if (prof) prof->begin(PROF_GEMM);
         int rc;
-        if ((f32_bits & 4) && sizeof(T) == 4 && M > f32_min_rows && L.N % 4 == 0 && res_mod == 0 && !act_after && L.b && !(Cf && Ct) && (Cf || Ct) &&
+        if ((sw.f32_bits & 4) && sizeof(T) == 4 && M > sw.f32_min_rows && L.N % 4 == 0 && res_mod == 0 && !act_after && L.b && !(Cf && Ct) && (Cf || Ct) &&
             lda % 4 == 0 && (!R || ldr % 4 == 0) && (Cf ? ldcf : ldct) % 4 == 0) {
             // (above the few-row kernels' range: the software-pipelined 64 x 64 main loop of gemm_f32_pro.hip, 5 - 11 % faster per launch at M = 8704)
             GemmProArgs q = one_seg(reinterpret_cast<const float*>(A), lda, L.Kp);
@@ -423,7 +419,7 @@ class Denoiser final : public DenoiserBase {
         // 2816, whole-chip kernel vs this family, us): StylizationBlock 19.7 / 20.1 vs 11.8 / 15.9; ffn.linear1 10.5 / 13.4 vs < 8.7 / 13.2;
         // ffn.linear2 13.0 / 12.5 vs 10.7 / 15.4; q|k|v 13.7 / 17.5 vs 14.2 / 21.5; feat_proj.1 14.0 / 15.3 vs 12.2 / 16.0; feat_proj.3
         // 10.4 / 12.1 vs 8.9 / 11.2.  DSH_TLS_ROWS=n replaces all six limits by n.
-        int tls_limit = tls_rows;
+        int tls_limit = sw.tls_rows;
         if (tls_limit <= 0) {
             if (pro == 2) tls_limit = 6144;
             else if (pro == 1) tls_limit = 2560;
@@ -435,7 +431,7 @@ class Denoiser final : public DenoiserBase {
         // frames at batch >= 7) stays on the window-chain kernels beyond their row limit wherever those can stage its FiLM rows (clips of 11
         // frames and more): slower than a whole-chip kernel, but it exists.  What neither family covers is refused up front by check_shape().
         const bool tl1_ok = pro != 2 || tl_linear_film_clips_ok(fr > 0 ? fr : 1, bmod > 0 ? bmod : 1);
-        if (tls_on && L.wf && (M <= tls_limit || !tl1_ok) && (pro == 0 || pro == 2 || (L.fd && L.fc))) {
+        if (sw.tls_on && L.wf && (M <= tls_limit || !tl1_ok) && (pro == 0 || pro == 2 || (L.fd && L.fc))) {
             TlArgs b = a;
             b.W = L.wf;
             if (pro == 1 || pro == 3) { b.bias = L.fd; b.row_const = L.fc; }
@@ -446,8 +442,8 @@ class Denoiser final : public DenoiserBase {
         // (the rolling kernel's FiLM prologue stages at most 10 clips per 256-token block and its asm stores take 32-bit plane offsets:
         //  windows of 26 .. 28 frames at whole-chip batch, or planes of 4 GiB and more, stay on the first-generation kernel)
         const bool hl2_fits = (pro != 2 || std::min(255 / (fr > 0 ? fr : 1) + 2, bmod > 0 ? bmod : 1) <= 10) && (size_t)M * L.N * 2 < ((size_t)1 << 32);
-        const bool hl2 = tl2_hl && Rlo && L.wf && !small && hl2_fits && ((pro == 2 && L.Kp == 512 && M >= 128 * 256) || (pro == 0 && L.Kp == 1024 && M >= 128 * 128));
-        const bool use2 = !small && tl2_on && L.wf && (((!R || tl2_all) && !Rlo) || hl2);
+        const bool hl2 = sw.tl2_hl && Rlo && L.wf && !small && hl2_fits && ((pro == 2 && L.Kp == 512 && M >= 128 * 256) || (pro == 0 && L.Kp == 1024 && M >= 128 * 128));
+        const bool use2 = !small && sw.tl2_on && L.wf && (((!R || sw.tl2_all) && !Rlo) || hl2);
         if (use2) {
             a.W = L.wf;
             if (pro == 1 || pro == 3) {
@@ -519,7 +515,7 @@ int Denoiser<T>::layer_from(const std::map<std::string, HostTensor>& w, const st
         {
             const HostTensor *g0 = find(w, p + ".feat_proj.0.weight"), *b0 = find(w, p + ".feat_proj.0.bias");
             if (!g0 || !b0) return -1;
-            const bool fold = L.tl || (f32_fuse && D == 512);
+            const bool fold = L.tl || (sw.f32_fuse && D == 512);
             if (int e = lin_from(w, p + ".feat_proj.1", L.f1, 2 * D, P, L.tl, L.tl ? 1024 : 0, false, fold ? g0->data.data() : nullptr,
                                  fold ? b0->data.data() : nullptr)) return e;
         }
@@ -564,33 +560,29 @@ int Denoiser<T>::layer_from(const std::map<std::string, HostTensor>& w, const st
         std::memcpy(&B3[2 * D], bv->data.data(), sizeof(float) * D);
         const HostTensor *lg = find(w, p + ".sa_block.norm.weight"), *lb = find(w, p + ".sa_block.norm.bias");
         if (!lg || !lb) return -1;
-        const bool fold = L.tl || (f32_fuse && D == 512);
+        const bool fold = L.tl || (sw.f32_fuse && D == 512);
         if (int e = make_lin(L.qkv, W3.data(), B3.data(), 3 * D, D, L.tl, 0, false, fold ? lg->data.data() : nullptr,
                              fold ? lb->data.data() : nullptr)) return e;
     }
-    if (int e = sty_from(w, p + ".sa_block.proj_out", L.sty1, D, L.tl, L.tl)) return e;
+    if (int e = sty_from(w, p + ".sa_block.proj_out", L.sty1, D, L.tl)) return e;
     if (int e = lin_from(w, p + ".ffn.linear1", L.ffn1, F, D, L.tl, 0, L.tl)) return e;
     if (int e = lin_from(w, p + ".ffn.linear2", L.ffn2, D, F, L.tl, 0, L.tl)) return e;
     if (int e = sty_from(w, p + ".ffn.proj_out", L.sty2, D, L.tl, L.tl)) return e;
     if (L.tl) {
         // weight stream of the fused FFN kernel, 32 KB chunks in the order its phases consume them (tl_pack_ffn_stream, tl3_ffn.hip):
         //   W1 tile j (GEMM1) at chunk c1(j) = j ? 2 j - 1 : 0 | K chunk j of W2 (GEMM2) as fragments (output tile ot, k step ks) at
-        //   (2 ot + ks) KB, at chunk c2(j) = j < 31 ? 2 j + 2 : 63 | W3 from chunk 64 in the order of the kernel generation (ffn_ver)
-        //   (round 5) in FRONT of them the 16 weight tiles of the attention branch's StylizationBlock Linear, which the fused launch runs as its
-        //   first stage (tl3_ffn_kernel<..., STY>); the plain FFN launch starts FFN_STREAM_OFF elements into the stream
+        //   (2 ot + ks) KB, at chunk c2(j) = j < 31 ? 2 j + 2 : 63 | W3 from chunk 64 in the order of the kernel generation (sw.ffn_ver)
         constexpr size_t CH = 16384;                       // bf16 elements per 32 KB chunk
-        std::vector<T> st((size_t)(16 + 64 + 16) * CH);
+        std::vector<T> st((size_t)(64 + 16) * CH);
         static_assert(sizeof(T) == 2 || sizeof(T) == 4, "element type");
         if (sizeof(T) == 2) {
-            // (the 16 chunks in front are only filled when the default-off fused attention-branch stage is enabled, DSH_FFN_STY=1)
-            if (ffn_sty) tl_pack_sty_tiles(reinterpret_cast<const uint16_t*>(L.sty1.out.hperm.data()), reinterpret_cast<uint16_t*>(st.data()));
-            tl_pack_ffn_stream(ffn_ver, reinterpret_cast<const uint16_t*>(L.ffn1.hperm.data()), reinterpret_cast<const uint16_t*>(L.ffn2.hperm.data()),
-                               reinterpret_cast<const uint16_t*>(L.sty2.out.hperm.data()), reinterpret_cast<uint16_t*>(st.data()) + FFN_STREAM_OFF);
+            tl_pack_ffn_stream(sw.ffn_ver, reinterpret_cast<const uint16_t*>(L.ffn1.hperm.data()), reinterpret_cast<const uint16_t*>(L.ffn2.hperm.data()),
+                               reinterpret_cast<const uint16_t*>(L.sty2.out.hperm.data()), reinterpret_cast<uint16_t*>(st.data()));
         }
         if (int e = dalloc(&L.ffn_stream, st.size(), allocs)) return e;
         DSH_HIP_CHECK(hipMemcpy(L.ffn_stream, st.data(), st.size() * sizeof(T), hipMemcpyHostToDevice));
         wbytes += st.size() * sizeof(T);
-        L.ffn1.hperm = std::vector<T>(); L.ffn2.hperm = std::vector<T>(); L.sty2.out.hperm = std::vector<T>(); L.sty1.out.hperm = std::vector<T>();
+        L.ffn1.hperm = std::vector<T>(); L.ffn2.hperm = std::vector<T>(); L.sty2.out.hperm = std::vector<T>();
     }
     return 0;
 }
@@ -683,7 +675,7 @@ int Denoiser<T>::encoder_from(const std::map<std::string, HostTensor>& w, const 
         film_p.push_back(lp + ".sa_block.proj_out");
         film_p.push_back(lp + ".ffn.proj_out");
     }
-    if (E.layers[0].tl || f32_fuse) {
+    if (E.layers[0].tl || sw.f32_fuse) {
         if (int e = dalloc(&E.film_g, (size_t)2 * cfg.num_layers * D, allocs)) return e;
         if (int e = dalloc(&E.film_b, (size_t)2 * cfg.num_layers * D, allocs)) return e;
         for (int l = 0; l < cfg.num_layers; ++l)
@@ -1005,7 +997,7 @@ int Denoiser<T>::prep_encoder(Encoder& E) {
     if (int e = gemm(E.film, semb, TE, R, ACT_NONE, false, nullptr, 0, 0, film_small, film_ld, nullptr, 0)) return e;
     if (int e = launch_film_expand(film_small, film_ld, t_uniform ? spk_idx : nullptr, E.film_tab, B, 2 * cfg.num_layers, D, E.film_g, E.film_b,
                                    (E.layers[0].tl || (f32_now() & 2)) ? 1 : 0, st)) return e;
-    if (E.layers[0].tl && aproj_in_tail) return 0;        // audio_proj was a stage of the encoder_aud launch (tl_aud.hip)
+    if (E.layers[0].tl && aproj_done) return 0;        // prep_audio ran audio_proj of both encoders in one launch (tl_embed.hip)
     if (E.layers[0].tl) {
         // (K = E.aproj.K: [audio | aud_feat] under UniDiffuser, the 128 mel features of the left half for a single transformer)
         if (int e = gemm(E.aproj, audio256, 2 * cfg.audio_dim, Mc, ACT_NONE, false, nullptr, 0, 0, nullptr, 0, aproj_rm, cfg.aud_latent_dim)) return e;
@@ -1031,7 +1023,7 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
     T* hc16 = sizeof(T) == 4 ? nullptr : h16 + (size_t)r0 * D;
     const char* jfe = getenv("DSH_JOINT_FUSE");          // (read per evaluation: the tests flip it inside one process)
     const bool joint_fuse = !(jfe && atoi(jfe) == 0);
-    if (tlp && hilo && joint_fuse && E.joint_wf) {
+    if (tlp && sw.hilo && joint_fuse && E.joint_wf) {
         // round 6: joint_embed + bias + PE + CFG-null constant + plane split in ONE launch from the tiled bf16 channels of x (tl_embed.hip)
         if (int e = launch_tile_rows_bf16<float>(x + c0, C, Mc, w, x_in, E.joint_nf * 16, st)) return e;
         if (int e = launch_tl_joint(x_in, E.joint_nf, E.joint_wf, E.joint.b, E.pe, fr, has_null ? E.layers[0].null_const : nullptr, Mc, r0, h16, hlo, st)) return e;
@@ -1040,7 +1032,7 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
         if (int e = launch_pack_cols<T>(x, C, Mc, c0, w, E.cin_p, 1.0f, x_in, E.cin_p, nullptr, 0, st)) return e;
         // null half = cond half + feat_proj_0(null_cond_emb); one pass seeds the tiled fp32 stream and its bf16 shadow
         if (int e = gemm(E.joint, x_in, E.cin_p, Mc, ACT_NONE, false, E.pe, D, fr, h0, D, nullptr, 0)) return e;
-        if (int e = launch_seed_stream(h0, Mc, D, E.layers[0].null_const, has_null, r0, h, h16, st, hilo ? hlo : nullptr)) return e;
+        if (int e = launch_seed_stream(h0, Mc, D, E.layers[0].null_const, has_null, r0, h, h16, st, sw.hilo ? hlo : nullptr)) return e;
     } else {
         if (int e = launch_pack_cols<T>(x, C, Mc, c0, w, E.cin_p, 1.0f, x_in, E.cin_p, nullptr, 0, st)) return e;
         if (int e = gemm(E.joint, x_in, E.cin_p, Mc, ACT_NONE, false, E.pe, D, fr, hc, D, nullptr, D)) return e;
@@ -1056,11 +1048,11 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
         if (!L.tl && !(f32_now() & 1)) { if (int e = launch_concat_ln_rows<T>(sg, Mc, L.ln0.g, L.ln0.b, U, L.Pp, L.Pp, st)) return e; }
         if (L.tl) {
             // feat_proj.0 LayerNorm over the un-materialised concat is the register prologue of feat_proj.1
-            if (!(dbg_skip & 1)) if (int e = tl(L.f1, 3, hc16, Mc, ACT_SILU, &L.ln0, nullptr, 0, 0, fr, B, nullptr, nullptr, g, nullptr, 0,
+            if (!(sw.dbg_skip & 1)) if (int e = tl(L.f1, 3, hc16, Mc, ACT_SILU, &L.ln0, nullptr, 0, 0, fr, B, nullptr, nullptr, g, nullptr, 0,
                            aproj, E.hub, expr ? expr16 : nullptr, L.P)) return e;
-            if (hilo) {
+            if (sw.hilo) {
                 T* hlc = hlo + (size_t)r0 * D;
-                if (!(dbg_skip & 2)) if (int e = tl(L.f3, 0, g, Mc, ACT_NONE, nullptr, nullptr, 0, 0, fr, B, reinterpret_cast<const float*>(hc16), nullptr, hc16, nullptr, 0,
+                if (!(sw.dbg_skip & 2)) if (int e = tl(L.f3, 0, g, Mc, ACT_NONE, nullptr, nullptr, 0, 0, fr, B, reinterpret_cast<const float*>(hc16), nullptr, hc16, nullptr, 0,
                                nullptr, nullptr, nullptr, 0, 0x7fffffff, 0, hlc, hlc)) return e;
             } else if (int e = tl(L.f3, 0, g, Mc, ACT_NONE, nullptr, nullptr, 0, 0, fr, B, hc, hc, hc16, nullptr, 0)) return e;
         } else if (f32_now() & 1) {
@@ -1082,9 +1074,9 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
             // the CFG-null constant of the NEXT layer is folded into this layer's last epilogue (layer 0:
             // seed_stream above), so no row kernel touches h between the GEMMs.
             const int nb = B * (1 + has_null), hr0 = has_null ? r0 : 0x7fffffff;
-            if (!(dbg_skip & 4)) if (int e = tl(L.qkv, 1, h16, M, ACT_NONE, &L.sa_ln, nullptr, 0, 0, fr, B, nullptr, nullptr, qkv, nullptr, 0)) return e;
+            if (!(sw.dbg_skip & 4)) if (int e = tl(L.qkv, 1, h16, M, ACT_NONE, &L.sa_ln, nullptr, 0, 0, fr, B, nullptr, nullptr, qkv, nullptr, 0)) return e;
             if (prof) prof->begin(PROF_ATTN);
-            if (dbg_skip & 8) {
+            if (sw.dbg_skip & 8) {
             } else if (fr <= 96) {
                 count_launch(LC_ATTN_MFMA);
                 if (int e = launch_linear_attention_tiled(qkv, nb, B, r0, fr, D, y, st, M >= 4096 ? next_rev() : 0, lens)) return e;
@@ -1107,37 +1099,31 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
             const double afl = 4.0 * Mc * (1 + has_null) * (double)D * (D / cfg.num_heads);
             if (prof) prof->end(afl);
             flops_acc += afl;
-            // round 5: at whole-chip token counts the attention branch's StylizationBlock is the first stage of the fused FFN launch
-            // (tl3_ffn_kernel<..., STY>, DSH_FFN_STY=0: separate launch as before)
-            const bool sty_fused = ffn_sty && hilo && ffn_fuse && ffn_ver == 3 && L.ffn_stream && tl3_ffn_supported(M, fr, B, true);
-            if (sty_fused) {
-            } else if (hilo) {
-                if (!(dbg_skip & 16)) if (int e = tl(L.sty1.out, 2, y, M, ACT_NONE, &L.sty1.ln, E.film_tab, film_ld, l * 4 * D, fr, B, reinterpret_cast<const float*>(h16), nullptr, h16,
+            if (sw.hilo) {
+                if (!(sw.dbg_skip & 16)) if (int e = tl(L.sty1.out, 2, y, M, ACT_NONE, &L.sty1.ln, E.film_tab, film_ld, l * 4 * D, fr, B, reinterpret_cast<const float*>(h16), nullptr, h16,
                                nullptr, 0, nullptr, nullptr, nullptr, 0, hr0, 0, hlo, hlo)) return e;
             } else if (int e = tl(L.sty1.out, 2, y, M, ACT_NONE, &L.sty1.ln, E.film_tab, film_ld, l * 4 * D, fr, B, h, h, h16, nullptr, 0,
                                   nullptr, nullptr, nullptr, 0, hr0)) return e;
             const float* next_const = (has_null && l + 1 < cfg.num_layers) ? E.layers[l + 1].null_const : nullptr;
-            if (ffn_fuse && L.ffn_stream && (ffn_ver == 3 ? tl3_ffn_supported(M, fr, B, hilo) : tl2_ffn_supported(M, fr, B))) {
+            if (sw.ffn_fuse && L.ffn_stream && (sw.ffn_ver == 3 ? tl3_ffn_supported(M, fr, B, sw.hilo) : tl2_ffn_supported(M, fr, B))) {
                 // ffn.linear1 -> GELU -> ffn.linear2 -> StylizationBlock -> + h in ONE kernel: hidden and y2 stay in registers
                 Tl2FfnArgs c;
-                c.X = h16; c.Wffn = L.ffn_stream + FFN_STREAM_OFF; c.b1 = L.ffn1.b; c.b2 = L.ffn2.b; c.b3 = L.sty2.out.b;
-                c.Y = nullptr; c.bs1 = nullptr; c.film_off1 = 0;
+                c.X = h16; c.Wffn = L.ffn_stream; c.b1 = L.ffn1.b; c.b2 = L.ffn2.b; c.b3 = L.sty2.out.b;
                 c.film = E.film_tab; c.film_ld = film_ld; c.film_off = l * 4 * D + 2 * D; c.frames = fr; c.bmod = B; c.half_row0 = hr0;
                 c.R = h; c.Cf = h; c.Ct = h16; c.row_const = next_const; c.n_const_rows = Mc; c.M = M; c.trace = nullptr; c.clk = nullptr;
                 c.Rhi = nullptr; c.Rlo = nullptr; c.Clo = nullptr;
-                if (hilo) { c.R = nullptr; c.Cf = nullptr; c.Rhi = h16; c.Rlo = hlo; c.Clo = hlo; }
-                if (sty_fused) { c.X = nullptr; c.Y = y; c.bs1 = L.sty1.out.b; c.film_off1 = l * 4 * D; c.Wffn = L.ffn_stream; }
+                if (sw.hilo) { c.R = nullptr; c.Cf = nullptr; c.Rhi = h16; c.Rlo = hlo; c.Clo = hlo; }
                 c.rev = next_rev();
-                const double fl = 2.0 * M * (double)(2.0 * D * cfg.ff_size + (double)D * D) + (sty_fused ? 2.0 * M * (double)D * D : 0.0);
+                const double fl = 2.0 * M * (double)(2.0 * D * cfg.ff_size + (double)D * D);
                 // (hi / lo planes: the input IS the hi plane of the residual; tl3_ffn_kernel re-reads it for 6 of the 16 Linear3 tiles only)
                 static const bool ffn_keep_hi = [] {
                     const char* e = getenv("DSH_FFN_PB"); const char* pc = getenv("DSH_FFN_PC");
                     return (!e || (atoi(e) & 1)) && (!pc || atoi(pc) == 1);
                 }();
-                const double by = (double)M * (hilo ? (D * 2 + D * 2 + D * 2 * (ffn_keep_hi ? 6.0 / 16 : 1.0) + D * 4) : (D * 2 + D * 4 * 2 + D * 2)) + (double)(2.0 * D * cfg.ff_size + (double)D * D) * 2;
+                const double by = (double)M * (sw.hilo ? (D * 2 + D * 2 + D * 2 * (ffn_keep_hi ? 6.0 / 16 : 1.0) + D * 4) : (D * 2 + D * 4 * 2 + D * 2)) + (double)(2.0 * D * cfg.ff_size + (double)D * D) * 2;
                 flops_acc += fl;
                 if (prof) prof->begin(PROF_TL_FFN);
-                const int rc = (dbg_skip & 32) ? 0 : (ffn_ver == 3 ? launch_tl3_ffn(c, st) : launch_tl2_ffn(c, st));
+                const int rc = (sw.dbg_skip & 32) ? 0 : (sw.ffn_ver == 3 ? launch_tl3_ffn(c, st) : launch_tl2_ffn(c, st));
                 if (prof) prof->end(fl, by);
                 if (notify_ev && ++tl_launches == notify_at) DSH_HIP_CHECK(hipEventRecord(notify_ev, st));
                 if (rc) return rc;
@@ -1145,7 +1131,7 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
             }
             if (int e = tl(L.ffn1, 0, h16, M, ACT_GELU, nullptr, nullptr, 0, 0, fr, B, nullptr, nullptr, g, nullptr, 0)) return e;
             if (int e = tl(L.ffn2, 0, g, M, ACT_NONE, nullptr, nullptr, 0, 0, fr, B, nullptr, nullptr, y2, nullptr, 0)) return e;
-            if (hilo) {
+            if (sw.hilo) {
                 if (int e = tl(L.sty2.out, 2, y2, M, ACT_NONE, &L.sty2.ln, E.film_tab, film_ld, l * 4 * D + 2 * D, fr, B, reinterpret_cast<const float*>(h16), nullptr,
                                h16, next_const, Mc, nullptr, nullptr, nullptr, 0, hr0, 0, hlo, hlo)) return e;
             } else if (int e = tl(L.sty2.out, 2, y2, M, ACT_NONE, &L.sty2.ln, E.film_tab, film_ld, l * 4 * D + 2 * D, fr, B, h, h, h16,
@@ -1160,17 +1146,6 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
             if (int e = run_block_tail(L, M, D, B * (1 + has_null), fr, E.film_tab, film_ld, l * 4 * D, B, h, h16_out(), hT())) return e;
             if (int e = gemm(L.sty2.out, s, D, M, ACT_NONE, false, h, D, 0, h, D, h16_out(), D)) return e;
         }
-    }
-    const char* ofe = getenv("DSH_OUT_FUSE");           // (read per evaluation: the tests flip it inside one process)
-    if (tlp && hilo && E.out_tl.wf && (E.out_tl.N == 128 || E.out_tl.N == 160) && (ofe && atoi(ofe) != 0)) {
-        // round 6: out head of both halves + CFG mix + expression x0 (+ its tiled copy) in ONE launch (tl_out.hip).  Built, bit-identical
-        // (test_fused_output_head_is_bit_identical) and measured SLOWER in every regime — 530.3 vs 528.8 ms per 950-clip step, 11.5 k vs
-        // 11.96 k frames/s on the 32-chain stream, 91.7 k vs 92.4 k at 100 clips (profiles/r06_r_*, r06_s_*): one wave per 32 tokens runs
-        // both halves and every output tile back to back (one wave per SIMD, 320 registers), where the three launches it replaces spread the
-        // same work over the chip.  Off unless DSH_OUT_FUSE=1.
-        flops_acc += 2.0 * M * (double)E.out_tl.N * D;
-        return launch_tl_out_mix(h16, E.out_tl.wf, E.out_tl.b, E.out_tl.N, Mc, r0, has_null, fr, w, c0, C, gs, gs_row, eps, x, c1, c2,
-                                 want_x0 ? expr_x0 : nullptr, want_x0 ? expr16 : nullptr, st);
     }
     if (tlp) {
         if (int e = tl(E.out_tl, 0, h16, M, ACT_NONE, nullptr, nullptr, 0, 0, fr, B, nullptr, o, nullptr, nullptr, 0,
@@ -1203,24 +1178,19 @@ int Denoiser<T>::prep_audio(const int64_t* t) {
         if (!aud_hoist()) { if (int e = aud_front()) return e; }
         if (int e = launch_film_fold(film_aud_tab, aud_film.N, Ra, 2, DA, aud_film_g, aud_film_b, st)) return e;
         flops_acc += 2.0 * Mc * (2.0 * DA * DA + 2.0 * DA * cfg.ff_size);
-        // ... and, on the token-per-lane path, audio_proj([mel | aud_feat]) of both motion encoders straight into their tiled concat operands
-        const char* ape = getenv("DSH_APROJ_FUSE");
-        // (built and measured: 533.5 / 539.3 vs 533.6 / 535.0 ms per 950-clip step, profiles/r06_n_ab_aproj_fuse.txt — the two small GEMMs hide
-        //  under the other sub-batch streams, the longer launch does not; DSH_APROJ_FUSE=1 turns it on)
-        aproj_in_tail = aud_ap_bias && tl_path() && (ape && atoi(ape) != 0);
-        if (aproj_in_tail) flops_acc += 2.0 * 2.0 * Mc * 256.0 * 256.0;
-        if (int e = launch_tl_aud_tail(aud_y, aud_x2, aud_stream, aud_bias, film_aud_tab, aud_film.N, Ra, fr, Mc, aud_feat_f, audio256 + DA, 2 * DA, st,
-                                       aproj_in_tail ? 2 : 0, aud_ap_bias, exp_.aproj_buf, ges_.aproj_buf)) return e;
-        // audio_proj of both motion encoders as ONE token-per-lane launch writing the tiled operands (instead of 2 x (GEMM + tile_rows))
+        if (int e = launch_tl_aud_tail(aud_y, aud_x2, aud_stream, aud_bias, film_aud_tab, aud_film.N, Ra, fr, Mc, aud_feat_f, audio256 + DA, 2 * DA, st)) return e;
+        // on the token-per-lane path, audio_proj([mel | aud_feat]) of both motion encoders as ONE launch writing their tiled concat operands
+        // (instead of 2 x (GEMM + tile_rows))
+        aproj_done = false;
         const char* a2 = getenv("DSH_APROJ_TL");
-        if (!aproj_in_tail && aud_ap_bias && tl_path() && !(a2 && atoi(a2) == 0)) {
+        if (aud_ap_bias && tl_path() && !(a2 && atoi(a2) == 0)) {
             if (int e = launch_tl_aproj(audio256, aud_stream + (size_t)18 * 16384, aud_ap_bias, 2, exp_.aproj_buf, ges_.aproj_buf, Mc, st)) return e;
             flops_acc += 2.0 * 2.0 * Mc * 256.0 * 256.0;
-            aproj_in_tail = true;                          // (prep_encoder skips its own audio_proj)
+            aproj_done = true;                          // (prep_encoder skips its own audio_proj)
         }
         return 0;
     }
-    aproj_in_tail = false;
+    aproj_done = false;
     float* ha = h;                       // [Mc,128] fp32 residual stream of encoder_aud (reuses h)
     T* ha16 = sizeof(T) == 4 ? nullptr : h16;
     const T* haA = sizeof(T) == 4 ? reinterpret_cast<const T*>(ha) : ha16;
@@ -1351,20 +1321,17 @@ class DualDenoiser final : public DenoiserBase {
         twin_.reset();
         if (twin_stream_) (void)hipStreamDestroy(twin_stream_);
         if (twin_ev_) (void)hipEventDestroy(twin_ev_);
-        for (Prefetch& f : pf_) f.prep.reset();              // the side instances borrow the sub-batch instances' slots and weights
+        pf_.prep.reset();                                    // the side instance borrows the whole-batch instance's slots and weights
         while (inst_.size() > 1) inst_.pop_back();
         for (hipStream_t st : streams_) (void)hipStreamDestroy(st);
         for (hipEvent_t ev : events_) (void)hipEventDestroy(ev);
         if (cond_buf_) (void)hipFree(cond_buf_);
         if (len_buf_) (void)hipFree(len_buf_);
-        for (Prefetch& f : pf_) {
-            f.prep.reset();
-            if (f.stream) (void)hipStreamDestroy(f.stream);
-            for (hipEvent_t ev : f.lvl_ev) (void)hipEventDestroy(ev);
-            if (f.ev_fork) (void)hipEventDestroy(f.ev_fork);
-            if (f.ev_done) (void)hipEventDestroy(f.ev_done);
-            if (f.t_dev) (void)hipFree(f.t_dev);
-        }
+        if (pf_.stream) (void)hipStreamDestroy(pf_.stream);
+        for (hipEvent_t ev : pf_.lvl_ev) (void)hipEventDestroy(ev);
+        if (pf_.ev_fork) (void)hipEventDestroy(pf_.ev_fork);
+        if (pf_.ev_done) (void)hipEventDestroy(pf_.ev_done);
+        if (pf_.t_dev) (void)hipFree(pf_.t_dev);
     }
     int finalize(const std::map<std::string, HostTensor>& w) override { return inst_[0]->finalize(w); }
     int set_condition(int B, int T, const float* audio, const float* person_id, const float* hubert) override {
@@ -1392,8 +1359,7 @@ class DualDenoiser final : public DenoiserBase {
         // tensors only need to stay valid until this call's work on the context stream has been enqueued (stream order).
         const size_t na = (size_t)B * T * cfg_.audio_dim, np = (size_t)B * cfg_.style_dim, nh = (size_t)B * T * cfg_.hubert_dim;
         // the prefetch instance reads the previous conditioning on its own stream: order the overwrite behind it
-        for (Prefetch& f : pf_)
-            if (f.busy) { DSH_HIP_CHECK(hipStreamWaitEvent(st_, f.ev_done, 0)); f.busy = false; }
+        if (pf_.busy) { DSH_HIP_CHECK(hipStreamWaitEvent(st_, pf_.ev_done, 0)); pf_.busy = false; }
         if (twin_busy_) { DSH_HIP_CHECK(hipEventRecord(twin_ev_, twin_stream_)); DSH_HIP_CHECK(hipStreamWaitEvent(st_, twin_ev_, 0)); twin_busy_ = false; }
         twin_cond_ok_ = false;
         if (!inst_.empty()) (void)inst_[0]->set_part(0);
@@ -1472,21 +1438,17 @@ class DualDenoiser final : public DenoiserBase {
     // side stream, ahead of the loop, into the main instance's cache slots.  At launch-bound batch sizes the main chain keeps a
     // handful of CUs busy, so the side stream runs beside it: the 27 launches (0.28 ms at B = 1) leave every evaluation's
     // critical path, also for schedules that visit each level once (the first window of a chain).  DSH_LEVEL_PREFETCH=0: off.
-    int level_prefetch(const int64_t* t_values_host, int n_levels, const int* order, int n_order, int begin, int sub = -1) override {
+    int level_prefetch(const int64_t* t_values_host, int n_levels, const int* order, int n_order, int begin) override {
         if (n_levels <= 0 || n_order < 0 || !t_values_host || (n_order > 0 && !order)) return -1;
-        // whole batch on one stream (sub < 0) or sub-batch `sub` of a split batch: the instance that evaluates, its stream, its clips
-        if (sub < 0 ? (split_now_ != 1) : (sub >= split_now_ || split_now_ < 2)) return -1;
-        const int mi = sub < 0 ? 0 : sub;
-        DenoiserBase* main = inst_[mi].get();
-        hipStream_t main_st = mi == 0 ? st_ : streams_[mi - 1];
-        const int b0 = sub < 0 ? 0 : first_clip(sub, split_now_), nb = sub < 0 ? cond_.B : first_clip(sub + 1, split_now_) - b0;
-        if ((int)pf_.size() <= mi) pf_.resize(mi + 1);
-        Prefetch& f = pf_[mi];
+        if (split_now_ != 1) return -1;                                     // the whole batch on one stream only
+        DenoiserBase* main = inst_[0].get();
+        const int nb = cond_.B;
+        Prefetch& f = pf_;
         if (begin) {
             f.active = false;
             const char* off = getenv("DSH_LEVEL_PREFETCH");
             if (off && atoi(off) == 0) return -1;
-            if (sub < 0 ? (level_cache_prepare(n_levels) != 0) : (main->level_cache_prepare(n_levels) != 0)) return -1;
+            if (level_cache_prepare(n_levels) != 0) return -1;
             char* slots = nullptr; size_t stride = 0; int nslots = 0;
             if (main->level_slots(&slots, &stride, &nslots) != 0 || nslots < n_levels) return -1;
             if (!f.prep) {
@@ -1508,10 +1470,10 @@ class DualDenoiser final : public DenoiserBase {
             }
             // everything already enqueued on the evaluating stream (the conditioning copies, the previous run's last restore from
             // the slots) precedes the side stream's work
-            DSH_HIP_CHECK(hipEventRecord(f.ev_fork, main_st));
+            DSH_HIP_CHECK(hipEventRecord(f.ev_fork, st_));
             DSH_HIP_CHECK(hipStreamWaitEvent(f.stream, f.ev_fork, 0));
-            if (int e = f.prep->set_lengths(lens_ ? lens_ + b0 : nullptr)) return e;
-            if (int e = f.prep->set_condition_light(nb, cond_.T, cond_.audio + (size_t)b0 * cond_.T * cfg_.audio_dim, cond_.pid + (size_t)b0 * cfg_.style_dim)) return e;
+            if (int e = f.prep->set_lengths(lens_)) return e;
+            if (int e = f.prep->set_condition_light(nb, cond_.T, cond_.audio, cond_.pid)) return e;
             if (int e = f.prep->adopt_level_slots(slots, stride, nslots)) return e;
             f.levels = n_levels; f.nb = nb;
             f.active = true;
@@ -1532,27 +1494,13 @@ class DualDenoiser final : public DenoiserBase {
         f.busy = true;
         return 0;
     }
-    int level_prefetch_cancel(int sub = -1) override {
-        const int mi = sub < 0 ? 0 : sub;
-        if (mi >= (int)pf_.size()) return 0;
-        Prefetch& f = pf_[mi];
-        // whatever the side stream has queued — including the part of a level_prefetch() call that failed midway, which never reached its
-        // own ev_done record — is ordered in front of the evaluating stream's inline fallback
-        if (f.stream && f.ev_done) {
-            DSH_HIP_CHECK(hipEventRecord(f.ev_done, f.stream));
-            DSH_HIP_CHECK(hipStreamWaitEvent(mi == 0 ? st_ : streams_[mi - 1], f.ev_done, 0));
-        }
-        f.busy = false;
-        f.active = false;
-        return 0;
-    }
     // ---- pipelined small-batch loop (denoiser.h): the gesture-side twin of the whole-batch instance -----------------------------
     int pipe_begin(DenoiserBase** twin, hipStream_t* stream) override {
         const char* off = getenv("DSH_PIPE");
         if ((off && atoi(off) == 0) || cfg_.single_transformer || cond_.B <= 0 || split_now_ != 1 || !twin || !stream) return -1;
         // (DDIM loops: the twin restores its head from the slots the prefetch run fills; loops without a timestep cache — DDPM — compute it)
         char* slots = nullptr; size_t stride = 0; int nslots = 0;
-        const bool have_slots = !pf_.empty() && pf_[0].active && inst_[0]->level_slots(&slots, &stride, &nslots) == 0;
+        const bool have_slots = pf_.active && inst_[0]->level_slots(&slots, &stride, &nslots) == 0;
         if (!twin_) {
             // (default priority: a lowest-priority gesture stream was measured — single clip 16.6 -> 77 ms, profiles/r06b_ar_ab_twin_stream_priority.txt)
             DSH_HIP_CHECK(hipStreamCreateWithFlags(&twin_stream_, hipStreamNonBlocking));
@@ -1601,14 +1549,13 @@ class DualDenoiser final : public DenoiserBase {
     int loop_end() override { loop_unsplit_ = false; return 0; }
     int gesture_channels() const override { return cfg_.single_transformer ? -1 : cfg_.dim_pose; }
     int level_wait_stream(int level, hipStream_t s) override {
-        DSH_REQUIRE(!pf_.empty() && level >= 0 && level < (int)pf_[0].lvl_ev.size(), "level_wait_stream: level out of range");
-        DSH_HIP_CHECK(hipStreamWaitEvent(s, pf_[0].lvl_ev[level], 0));
+        DSH_REQUIRE(level >= 0 && level < (int)pf_.lvl_ev.size(), "level_wait_stream: level out of range");
+        DSH_HIP_CHECK(hipStreamWaitEvent(s, pf_.lvl_ev[level], 0));
         return 0;
     }
-    int level_wait(int level, int sub = -1) override {
-        const int mi = sub < 0 ? 0 : sub;
-        DSH_REQUIRE(mi < (int)pf_.size() && level >= 0 && level < (int)pf_[mi].lvl_ev.size(), "level_wait: level out of range");
-        DSH_HIP_CHECK(hipStreamWaitEvent(mi == 0 ? st_ : streams_[mi - 1], pf_[mi].lvl_ev[level], 0));
+    int level_wait(int level) override {
+        DSH_REQUIRE(level >= 0 && level < (int)pf_.lvl_ev.size(), "level_wait: level out of range");
+        DSH_HIP_CHECK(hipStreamWaitEvent(st_, pf_.lvl_ev[level], 0));
         return 0;
     }
     int eval_level(const float* x, const int64_t* t, const float* c1, const float* c2, float* eps, int mode, const int64_t* level) override {
@@ -1714,7 +1661,7 @@ class DualDenoiser final : public DenoiserBase {
     const int* lens_ = nullptr;                            // len_buf_ while the current condition is ragged, else null
     std::vector<int32_t> lens_host_;
     size_t cond_cap_ = 0;
-    // side-stream producers of the x-independent head (level_prefetch): [0] the whole batch / sub-batch 0, [i] sub-batch i
+    // side-stream producer of the x-independent head of the whole batch (level_prefetch)
     struct Prefetch {
         std::unique_ptr<DenoiserBase> prep;                // shared weights, own workspace, conditioned with mel features + speaker only
         hipStream_t stream = nullptr;
@@ -1724,7 +1671,7 @@ class DualDenoiser final : public DenoiserBase {
         bool busy = false, active = false;
         int levels = 0, nb = 0;
     };
-    std::vector<Prefetch> pf_;
+    Prefetch pf_;
     std::unique_ptr<DenoiserBase> twin_;                   // gesture-side twin of inst_[0] for the pipelined small-batch loop (pipe_begin)
     hipStream_t twin_stream_ = nullptr; hipEvent_t twin_ev_ = nullptr; bool twin_cond_ok_ = false, twin_busy_ = false;
     size_t pipe_rows_ = 64499;                             // DDIM loops below this many token rows: one batch, two encoder streams (loop_begin)

@@ -84,13 +84,13 @@ const char* last_error_cstr();
 // about them.  The indices are part of the C ABI (include/diffsheg_hip.h): append, never renumber.
 enum LaunchFamily {
     LC_TL1 = 0,            // first-generation token-per-lane Linear (tl_linear.hip)
-    LC_TL2_LOOP,           // tl2 round-2 loop (also its out-of-phase-epilogue form)
+    LC_TL2_LOOP,           // tl2 round-2 loop
     LC_TL2_ROLL,           // tl2 rolling loop
     LC_TL2_ROLL_HL,        // tl2 rolling loop on hi / lo residual planes
-    LC_TL4,                // tl4 LDS-tiled Linear
+    LC_RETIRED_4,          // retired (a removed kernel class): always 0
     LC_TLS,                // window-chain 32-token kernels (tl_small.hip)
     LC_FFN_FUSED,          // fused FFN launch (tl3_ffn / tl2_ffn), every form
-    LC_FFN_FUSED_STY,      // ... of which with the attention branch's StylizationBlock as first stage
+    LC_RETIRED_7,          // retired (a removed form of the fused FFN launch): always 0
     LC_ATTN_MFMA,          // bf16 layers: MFMA tiled attention
     LC_ATTN_ROWMAJOR,      // bf16 layers: row-major attention between two layout conversions (windows of more than 96 frames)
     LC_GEMM_F32_FEWROW,    // fp32 K-split GEMM for a few hundred rows (gemm.hip)

@@ -107,11 +107,7 @@ int launch_tl_permute_weight(const void* W, int N, int K, void* dst, hipStream_t
 // ---- second generation (tl2.hip): LDS-DMA weight stream from FRAGMENT-ORDERED weights -------------------------------
 // same arguments as launch_tl_linear, except that a.W is the fragment-ordered copy of the weight (tl2_frag_index)
 int launch_tl2_linear(const TlArgs& a, int pro, hipStream_t s);
-// fourth form (tl4.hip, round 6): weights AND activations through an LDS ring, 64 x 128 outputs per wave; instantiated for feat_proj.1
-// (pro 3), feat_proj.3 on hi / lo planes (pro 0, K = 1024) and q|k|v (pro 1); same arguments and bit-identical results
 extern int g_tl_last_variant;          // test helper (dsh_debug_last_tl_variant): family the last token-per-lane Linear launch selected
-bool tl4_linear_supported(const TlArgs& a, int pro);
-int launch_tl4_linear(const TlArgs& a, int pro, hipStream_t s);
 // element index of stored row n (inside 32-row tile nt; rows pi-permuted as for tl_linear) / column k of a [N, K] weight
 size_t tl2_frag_index(int K, int nt, int n, int k);
 // FFN branch of a decoder layer in one launch: h <- h + Sty(GELU(h16 W1^T + b1) W2^T + b2)   (transformer.py:169-181)
@@ -128,10 +124,6 @@ struct Tl2FfnArgs {
     int stag_groups, stag_sleep;         // first-round start stagger (set by the launcher): block b < 256 sleeps (b % groups) * sleep * 8 k cycles
     int rev;                             // 1: token blocks in descending order (tl_block_index, tl_common.h)
     const void* Rhi; const void* Rlo; void* Clo;   // hi / lo planes of the residual stream (tl3_ffn_kernel only): Rhi != null replaces R / Cf
-    // round 5 (plane form only): Y != null -> the attention branch's StylizationBlock runs as a first stage of the launch (tl3_ffn.hip, STY):
-    // Y = bf16 tiled attention output [M, 512], bs1 = bias of its Linear, film_off1 = offset of its folded FiLM rows in `film`; Wffn then
-    // starts with its 16 weight tiles (tl_pack_ffn_stream version 4), X is not read, and Rhi / Rlo are updated in place (Ct = Rhi, Clo = Rlo)
-    const void* Y; const float* bs1; int film_off1;
 };
 void tl_stagger_config(int which, int* groups, int* sleep);   // DSH_STAGGER (tl2.hip)
 bool tl2_ffn_supported(int M, int frames, int bmod);
@@ -142,9 +134,6 @@ bool tl3_ffn_supported(int M, int frames, int bmod, bool planes);   // the gate 
 // the 80-chunk weight stream of the fused FFN kernels from pi-permuted row-major bf16 weights ([1024,512], [512,1024], [512,512]);
 // version 2: tl2_ffn_kernel, 3: tl3_ffn_kernel; `st` receives 80 * 16384 elements
 void tl_pack_ffn_stream(int version, const uint16_t* w1p, const uint16_t* w2p, const uint16_t* w3p, uint16_t* st);
-// the 16 chunks of the attention branch's StylizationBlock Linear ([512,512], pi-permuted rows) in front of a version-3 stream: tile t in
-// fragment order = chunk t; `st16` receives 16 * 16384 elements
-void tl_pack_sty_tiles(const uint16_t* wsp, uint16_t* st16);
 
 // ---- tiled-layout helpers (rowops.hip).  bf16 tiles: 32 tokens x 16 features; fp32: lane-native 32 x 32 blocks ----
 // row-major [M, w] (ld, element type TS = float or bf16) -> bf16 tiled [Mpad, Wd]; columns >= w are zero filled
@@ -172,19 +161,9 @@ int launch_tl_joint(const void* x_tiled, int nf, const void* wfrag, const float*
 // [Mc,128] row-major, Wst = tl_aud_pack_stream, bias = [proj_out(sa) 128 | linear1 1024 | linear2 128 | proj_out(ffn) 128], film = FOLDED rows
 // [A1 | B1 | A2 | B2] (128 each) of embedding row (token / frames) % bmod
 void tl_aud_pack_stream(const float* ws1, const float* w1, const float* w2, const float* ws2, uint16_t* st);
-void tl_aud_pack_audio_proj(const float* w, uint16_t* st);     // audio_proj [256,256] -> 4 more chunks per motion encoder behind the 18
-// n_ap > 0: audio_proj([mel | aud_feat]) of n_ap motion encoders as further stages (bias_ap [n_ap][256]; tiled bf16 outputs [Mc, 256]);
-// out_b must then be the right half of a [Mc, 256] bf16 buffer whose left half holds the mel features (ld_b = 256)
+void tl_aud_pack_audio_proj(const float* w, uint16_t* st);     // audio_proj [256,256] -> 4 chunks per motion encoder behind the 18 (read by launch_tl_aproj)
 int launch_tl_aud_tail(const void* Y, const float* X2, const void* Wst, const float* bias, const float* film, int film_ld, int bmod, int frames,
-                       int Mc, float* out_f, void* out_b, int ld_b, hipStream_t s, int n_ap = 0, const float* bias_ap = nullptr,
-                       void* ap_out0 = nullptr, void* ap_out1 = nullptr);
-// round 6 (tl_out.hip): the `out` head for both CFG halves + CFG mix (+ x0 = c1 x - c2 eps and its tiled bf16 copy) in one launch;
-// hi = hi plane of the residual stream (null half at rows [0, Mc), conditional half at [row1, row1 + Mc)), wfrag / bias = the `out` Linear
-// in fragment order padded to n_out_padded (128 or 160) rows, eps / x [Mc, C] with the encoder's w channels at column c0; guidance scales
-// as launch_cfg_mix
-int launch_tl_out_mix(const void* hi, const void* wfrag, const float* bias, int n_out_padded, int Mc, int row1, int has_null, int frames, int w,
-                      int c0, int C, const float* scale, int scale_row, float* eps, const float* x, const float* c1, const float* c2, float* x0,
-                      void* x0_tiled, hipStream_t s);
+                       int Mc, float* out_f, void* out_b, int ld_b, hipStream_t s);
 // audio_proj of up to two motion encoders from the row-major bf16 [Mc, 256] operand straight into their tiled [Mc, 256] concat operands
 // (tl_embed.hip); wfrag = tl_aud_pack_audio_proj per encoder (128 KB apart), bias [n_enc][256]
 int launch_tl_aproj(const void* x256, const void* wfrag, const float* bias, int n_enc, void* out0, void* out1, int Mc, hipStream_t s);

@@ -417,34 +417,15 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
         }
     }
     const int twin_mode = o.kind == 0 ? 2 : 0;
-    // sub-batch streams: the x-independent head of an evaluation (time / speaker / FiLM embeddings, encoder_aud, audio_proj: 23 small
-    // dependent launches, each of which waits ~50 - 90 us for a free CU beside the other sub-batches' 100-us blocks) is computed by a
-    // side instance per sub-batch, one evaluation ahead of its first use (round 4; the window-chain regime has done this since
-    // round 2).  Falls back to the inline timestep cache for schedules that revisit levels, or to plain evaluations.
-    bool split_cache = false, split_pf = false;
+    // sub-batch streams: the inline timestep cache for schedules that revisit levels, else plain evaluations
+    bool split_cache = false;
     if (split && o.kind == 0) {
         std::vector<int> cnt(o.respacing, 0);
         int evals = 0, distinct = 0;
-        for (const SamplerStep& sp : steps) if (sp.kind != STEP_UNDO) { ++evals; if (cnt[sp.level]++ == 0) { ++distinct; order.push_back(sp.level); } }
+        for (const SamplerStep& sp : steps) if (sp.kind != STEP_UNDO) { ++evals; if (cnt[sp.level]++ == 0) ++distinct; }
         const char* lc = getenv("DSH_LEVEL_CACHE");
         const bool cache_on = !(lc && atoi(lc) == 0);
-        // (measured on the 950-clip batch, round 4: 628.7 / 629.5 ms per step with the side streams against 624.8 / 624.6 without — at
-        //  this size the chip is throughput-bound, three more streams only add contention — so it is opt-in: DSH_SPLIT_PREFETCH=1)
-        const char* sp_e = getenv("DSH_SPLIT_PREFETCH");
-        if (sp_e && atoi(sp_e) != 0 && cache_on && st != nullptr && !order.empty()) {
-            tv.resize(o.respacing);
-            for (int k = 0; k < o.respacing; ++k) tv[k] = (int64_t)tb.tmap[k];
-            split_pf = true;
-            size_t started = 0;
-            for (; started < subs.size() && split_pf; ++started) split_pf = den->level_prefetch(tv.data(), o.respacing, order.data(), 1, 1, (int)started) == 0;
-            if (split_pf) { pf_next = 1; level_seen.assign(o.respacing, 0); }
-            else {
-                // a later sub-batch could not start its side stream: the ones already started have a level evaluation queued that
-                // writes the very cache slot the inline fallback below fills — order the sub-batch streams behind them and end those runs
-                for (size_t i = 0; i < started; ++i) if (int e = den->level_prefetch_cancel((int)i)) return e;
-            }
-        }
-        if (!split_pf && evals > distinct && cache_on) {
+        if (evals > distinct && cache_on) {
             split_cache = true;
             for (const Sub& u : subs) split_cache = split_cache && u.d->level_cache_prepare(o.respacing) == 0;
             if (split_cache) level_seen.assign(o.respacing, 0);
@@ -497,28 +478,17 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
             } else {
                 // every sub-batch on its own stream; at the very first evaluation sub-batch i + 1 starts a few launches behind
                 // sub-batch i (so that the kernel sequences are out of phase from the start); afterwards the streams run free
-                size_t want = pf_next;
-                if (split_pf && !level_seen[k]) {                       // first use: queue the next new level on every side stream
-                    size_t pos = 0;
-                    while (pos < order.size() && order[pos] != k) ++pos;
-                    want = std::max(pf_next, std::min(order.size(), pos + 2));
-                }
                 for (size_t i = 0; i < subs.size(); ++i) {
                     const Sub& u = subs[i];
                     if (int e = launch_fill_step(tbuf + u.b0, c1buf + u.b0, c2buf + u.b0, lvlbuf + i, (int64_t)tb.tmap[k], c1, c2, (int64_t)k, u.nb, u.s)) return e;
                     if (first_eval && i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(u.s, ev_sub[2 * (i - 1)], 0));
                     u.d->notify_after_launches((first_eval && i + 1 < subs.size()) ? ev_sub[2 * i] : nullptr, lag);
-                    if (split_pf && !level_seen[k]) {
-                        if (want > pf_next) { if (int e = den->level_prefetch(tv.data(), o.respacing, order.data() + pf_next, (int)(want - pf_next), 0, (int)i)) return e; }
-                        if (int e = den->level_wait(k, (int)i)) return e;
-                    }
-                    const int smode = split_pf ? 2 : split_cache ? (level_seen[k] ? 2 : 1) : 0;
+                    const int smode = split_cache ? (level_seen[k] ? 2 : 1) : 0;
                     u.d->t_uniform = den->t_uniform;
                     if (int e = u.d->eval_level(x + u.off, tbuf + u.b0, c1buf + u.b0, c2buf + u.b0, eps + u.off, smode, lvlbuf + i)) return e;
                     u.d->notify_after_launches(nullptr, 0);
                 }
-                if (split_cache || split_pf) level_seen[k] = 1;
-                pf_next = want;
+                if (split_cache) level_seen[k] = 1;
                 first_eval = false;
                 ++n_eval;
             }

@@ -236,16 +236,16 @@ int dsh_op_gemm_f32_pro(void* hip_stream, int32_t pro, const float* x0, int32_t 
  * of feat_proj.0 (transformer.py:304-312), LayerNorm over its first `frames` (= real width, 896 .. 1024) columns, gamma / beta
  * [1024] zero beyond them. */
 /* Test helper: which kernel family the LAST token-per-lane Linear launch of this process selected — 0 = tl2 round-2 loop, 1 = tl2 rolling
- * loop, 2 = tl2 rolling loop on hi / lo residual planes, 3 = tl2 out-of-phase epilogues, 4 = tl4 LDS-tiled (8 waves), 5 = tl4 (4 waves),
- * 10 = tl_linear (first generation), 11 = tl_small (window chain); -1 before any launch.  Lets the bit-identity tests assert that the
- * kernel they mean to check is the one that ran. */
+ * loop, 2 = tl2 rolling loop on hi / lo residual planes, 10 = tl_linear (first generation), 11 = tl_small (window chain); -1 before any
+ * launch.  Values 3, 4 and 5 are retired (kernel forms that were removed) and never returned.  Lets the bit-identity tests assert that
+ * the kernel they mean to check is the one that ran. */
 int32_t dsh_debug_last_tl_variant(void);
 /* Test helper: launches issued by this process since the last reset, per kernel family (host-side counters: no kernel and no launch
  * argument knows about them).  Copies min(cap, n) entries into out (nullable), zeroes all of them afterwards when reset != 0, returns n.
  * Fixed indices (new ones are appended):
  *    0 tl_linear (first generation)        1 tl2 round-2 loop                    2 tl2 rolling loop
- *    3 tl2 rolling loop on hi / lo planes  4 tl4 LDS-tiled                       5 tl_small (window chain)
- *    6 fused FFN launch (tl3_ffn / tl2_ffn)            7 ... of which with the attention branch's StylizationBlock as first stage
+ *    3 tl2 rolling loop on hi / lo planes  4 retired, always 0                   5 tl_small (window chain)
+ *    6 fused FFN launch (tl3_ffn / tl2_ffn)            7 retired, always 0
  *    8 bf16 layers: MFMA tiled attention               9 bf16 layers: row-major attention fallback (windows of more than 96 frames)
  *   10 fp32 few-row (K-split) GEMM        11 fp32 tiled GEMM                    12 gemm_f32_pro
  *  and four VALUES rather than counts: 13 sub-batch streams of the last dsh_eval, 14 sub-batch streams of the last dsh_sample,

@@ -18,8 +18,6 @@ run "DSH_HILO=0 (fp32 residual stream + bf16 shadow)" DSH_HILO=0
 run "DSH_FFN_V=2 (round-3 fused FFN kernel; implies fp32 stream)" DSH_FFN_V=2
 run "DSH_REV=0 (every launch walks the rows in one order)" DSH_REV=0
 run "DSH_STAGGER=4,3 (first-round start stagger)" DSH_STAGGER=4,3
-run "DSH_SPLIT_PREFETCH=1 (x-independent head on side streams)" DSH_SPLIT_PREFETCH=1
-run "DSH_TL2_PP=1 (deferred-epilogue q|k|v kernel)" DSH_TL2_PP=1
 run "DSH_DUAL=2" DSH_DUAL=2
 run "DSH_DUAL=4" DSH_DUAL=4
 run "DSH_DUAL=0 (one stream)" DSH_DUAL=0

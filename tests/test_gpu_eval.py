@@ -279,34 +279,6 @@ def test_bad_arguments_raise():
               add_cond={"pretrain_aud_feat": inp["pretrain_aud_feat"]}, pe_type="learnable")
 
 
-def test_fused_attention_branch_stage_is_bit_identical_to_the_separate_launch(monkeypatch):
-    """Round 5: at whole-chip token counts the StylizationBlock of the attention branch runs as the first stage of the fused FFN launch
-    (tl3_ffn_kernel<..., STY>; DSH_FFN_STY, read when a context is created).  Same arithmetic operation for operation as the separate
-    launch it replaces (tl2_linear_kernel<512, 2, ..., ROLL, HL>): a whole UniDiffuser evaluation at B = 100 (17 600 token rows: fused FFN,
-    two sub-batch streams) must agree BIT FOR BIT between the two forms."""
-    import torch
-    from diffsheg_amd.config import get_config
-    from diffsheg_amd.model import UniDiffuser
-    from diffsheg_amd.synthetic import make_inputs
-    from util import synthetic_sd
-    cfg = get_config("show")
-    B = 100
-    inp = make_inputs(cfg, B, seed=21)
-    t = torch.full((B,), 560, dtype=torch.long)
-    shape_e = (B, cfg.n_poses, cfg.expression_dim)
-    outs = {}
-    for sty in ("0", "1"):
-        monkeypatch.setenv("DSH_FFN_STY", sty)
-        model = UniDiffuser(cfg, synthetic_sd("show"), device="cuda:0", precision="bf16")
-        eps = model(inp["x_T"].cuda(), t.cuda(), sqrt_alphas=[torch.full(shape_e, 4.9), torch.full(shape_e, 4.8)], audio_emb=inp["audio_emb"].cuda(),
-                    length=None, person_id=inp["person_id"].cuda(), add_cond={"pretrain_aud_feat": inp["pretrain_aud_feat"].cuda()}, pe_type="pe_sinu", y={})
-        torch.cuda.synchronize()
-        outs[sty] = eps.cpu()
-        del model
-    assert torch.isfinite(outs["1"]).all()
-    assert torch.equal(outs["0"], outs["1"]), float((outs["0"] - outs["1"]).abs().max())
-
-
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
 def test_embeddings_on_distinct_rows_change_nothing(prec, monkeypatch):
     """Round 6: with one timestep for the whole batch the time / speaker / FiLM embedding Linears (transformer.py:446-457, :77) run on the
@@ -359,22 +331,6 @@ def test_fused_encoder_aud_tail_matches_reference_tap(monkeypatch):
     e1, e0, d = max_abs(taps["1"], want) / scale, max_abs(taps["0"], want) / scale, max_abs(taps["1"], taps["0"]) / scale
     print(f"[encoder_aud tail] fused vs reference {e1:.2e}, six launches vs reference {e0:.2e}, fused vs six launches {d:.2e} (of range {scale:.2f})")
     assert e1 < 2e-2 and e1 < 1.5 * e0 + 2e-3
-
-
-@pytest.mark.parametrize("B,T", [(3, 88), (2, 30)])
-def test_fused_output_head_is_bit_identical(B, T, monkeypatch):
-    """Round 6: `out` of both CFG halves + CFG mix + expression x0 (+ its tiled bf16 copy) in one launch (tl_out.hip) performs the arithmetic of
-    the three launches it replaces operation for operation (bias-seeded accumulators in ascending k, the same rounded mix / x0 expressions):
-    the whole evaluation — the gesture half sees the expression x0 through the tiled copy — must agree bit for bit (DSH_OUT_FUSE=1 turns the fused launch on; it is off by default: measured slower)."""
-    cfg = get_config("show")
-    model = gpu_model("show", "bf16")
-    inp = make_inputs(cfg, B, frames=T, seed=5 + B)
-    outs = {}
-    for sw in ("1", "0"):
-        monkeypatch.setenv("DSH_OUT_FUSE", sw)
-        outs[sw] = _call(model, cfg, inp, 360, 2.1, 1.9).cpu()
-    assert torch.isfinite(outs["1"]).all()
-    assert torch.equal(outs["0"], outs["1"])
 
 
 @pytest.mark.parametrize("switch", ["DSH_JOINT_FUSE", "DSH_APROJ_TL", "DSH_AUD_HOIST"])

@@ -144,26 +144,21 @@ def test_row_moments_travel_from_the_producer_to_the_stylization_launch(M, offse
 def test_lds_dma_and_register_staging_give_identical_results(tmp_path):
     """The operands reach LDS by DMA (default) or through the staging registers (DSH_GP_DMA=0): the arithmetic is the same operation for
     operation — including the order in which the row moments are accumulated — so the outputs are bit-identical (fresh processes: the switches
-    are read once).  The StylizationBlock launch with specialised producer waves (DSH_GP_WS=1; measured slower, off by default) accumulates its
-    row moments in another order: fp32 round-off apart."""
+    are read once)."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = []
-    for dma, ws in (("1", "0"), ("0", "0"), ("1", "1")):
-        f = str(tmp_path / f"gp_dma_{dma}_{ws}.pt")
-        r = subprocess.run([sys.executable, os.path.join(root, "tests", "gp_dma_worker.py"), f], env=dict(os.environ, DSH_GP_DMA=dma, DSH_GP_WS=ws), capture_output=True, text=True,
+    for dma in ("1", "0"):
+        f = str(tmp_path / f"gp_dma_{dma}.pt")
+        r = subprocess.run([sys.executable, os.path.join(root, "tests", "gp_dma_worker.py"), f], env=dict(os.environ, DSH_GP_DMA=dma), capture_output=True, text=True,
                            timeout=600)
         assert r.returncode == 0 and "GP_DMA_WORKER_OK" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])
         res.append(torch.load(f))
     for k in ("pro0", "pro1", "pro2"):
         assert torch.isfinite(res[0][k]).all()
         assert torch.equal(res[0][k], res[1][k]), (k, float((res[0][k] - res[1][k]).abs().max()))
-    assert torch.equal(res[0]["pro0"], res[2]["pro0"]) and torch.equal(res[0]["pro1"], res[2]["pro1"])
-    d = float((res[0]["pro2"] - res[2]["pro2"]).abs().max())
-    print(f"[StylizationBlock launch, producer waves vs four-wave form] max |d| = {d:.2e}")
-    assert d < 2e-5 * max(1.0, float(res[0]["pro2"].abs().max())), d
 
 
 @pytest.mark.parametrize("ds,B,T", [("beat", 16, 34), ("beat", 256, 34), ("show", 8, 88), ("show", 21, 30)])

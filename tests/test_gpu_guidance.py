@@ -218,22 +218,6 @@ def test_per_row_scales_masked_window():
     _per_row_vs_uniform(model, inp, lambda: _ddim(model, inp, y={"gt": gt, "outpainting_mask": mask}))
 
 
-def test_fused_output_head_per_row_bit_identical(monkeypatch):
-    model = _model("bf16", 1.25)
-    inp = make_inputs(model.cfg, 3, seed=6)
-    model.set_guidance_scale(_scales(3))
-    monkeypatch.setenv("DSH_OUT_FUSE", "0")
-    a = _eval(model, inp)
-    monkeypatch.setenv("DSH_OUT_FUSE", "1")
-    b = _eval(model, inp)
-    model.set_guidance_scale([1.0, 2.0, 1.0])
-    c = _eval(model, inp)
-    monkeypatch.setenv("DSH_OUT_FUSE", "0")
-    d = _eval(model, inp)
-    model.set_guidance_scale(None)
-    assert torch.equal(a, b) and torch.equal(c, d)
-
-
 # ---- 4. rows at 1 inside a doubled batch -----------------------------------------------------------------------------------
 def test_rows_at_one_match_unguided_oracle():
     model = _model("fp32", 1.25)

@@ -333,7 +333,6 @@ def test_rolling_main_loop_is_bit_identical(K, N, pro, act, monkeypatch):
     tile t - 1 inside tile t; DSH_TL2_ROLL, default on) issues the same MFMAs in the same order and evaluates the same epilogue
     expressions as the round-2 loop: every output bit must agree — on more than one round of blocks and with a ragged last block."""
     monkeypatch.setenv("DSH_TL2", "1")
-    monkeypatch.setenv("DSH_TL4", "0")
     # at least 128 token blocks (256 tokens at K = 512, 128 at K = 1024): below that the launcher splits N over grid.y and keeps the
     # round-2 loop for both settings (advisor finding, round 5: the test compared that kernel with itself); ragged last block
     Mv = (256 * 130 + 77) if K == 512 else (128 * 130 + 50)
@@ -434,7 +433,6 @@ def test_rolling_hilo_kernels_match_the_first_generation_bit_for_bit(K, N, pro, 
     (tl_linear_kernel<..., HL>): same accumulator start (bias + CFG-null constant), same MFMA order, hl_accumulate / hl_split — every bit
     of both planes must agree (the op returns hi as Ct and hi + lo as Cf)."""
     monkeypatch.setenv("DSH_HILO", "1")
-    monkeypatch.setenv("DSH_TL4", "0")
     # at least 128 token blocks, so that every block runs SEVERAL tiles: the steady state of the rolling loop (tile<HAS_PREV = true>: the
     # epilogue of tile t - 1 inside tile t, residual fragments one tile ahead, asm stores, the counted wait with the residual loads in it)
     # is what the model runs at whole-chip batch (advisor finding, round 5: with 6 - 12 token blocks every block computed ONE tile)
