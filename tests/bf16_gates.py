@@ -1,0 +1,300 @@
+"""Gates for the bf16 kernel tests, derived from the arithmetic and never from a kernel's output (plain torch, CPU).
+
+A bf16 kernel that accumulates exact bf16 products in fp32 and stores the result rounded to nearest even can differ from the fp64
+value of the same expression by at most
+    half a bf16 ulp of the result  (the store)
+  + K * 2^-23 * sum_k |x_k w_k|    (accum_bound: worst case of an fp32 accumulation in ANY order; 2^-23 rather than 2^-24 because the
+                                    matrix pipe need not round to nearest internally).
+assert_rounded / assert_close_f32 check exactly that on EVERY element and name the worst one with its position inside the 32 x 32
+tile, its clip and its frame, so that a routing fault locates itself.
+
+Chains with an internal bf16 rounding point (LayerNorm + FiLM + SiLU prologue, the FFN's hidden and SiLU outputs, the attention's
+k^ / A / q^) cannot be bounded that way: a value that sits on a rounding boundary flips with the last bit of the arithmetic in front
+of it, and one flip moves the output by ulp(operand) * |w|.  Their slack is CALIBRATED on the CPU: the chain is evaluated in fp64 and
+in fp32 with the same documented rounding points (and the documented 1e-4 approximation of the fast GELU as a uniform perturbation;
+the kernel's polynomial is not copied), and
+    slack    = MARGIN * max |fp32 chain - fp64 chain|          (one number per test, applied to every element)
+    rms gate = MARGIN * rms (fp32 chain - fp64 chain) + rms of the output rounding.
+MARGIN = 3: both differences are maxima of the same distribution of rounding flips; the kernel additionally carries the error of the
+hardware exp / rcp and its own order of the LayerNorm statistics.
+
+Where ONE rounded operand feeds the Linear directly (LayerNorm [+ FiLM + SiLU] prologue -> Linear) the realised maximum is a lottery:
+an operand row of 512 values sees ~0.1 .. 1 flips, and the maximum over the test is decided by whether one of the few elements with
+|s| >= 2 (ulp 2^-6, against 2^-9 for the typical element) is among them - the kernel and the CPU chain flip different elements, and on
+an MI355X the kernel's maximum was 1.0 .. 924 x the calibration at the five (T, batch) shapes of the op test (the table below).  Those chains therefore
+add flip_bound: the effect of one flip of the row's coarsest operand on the output's largest weight, max_k ulp(s_mk) * max_k |w_nk|
+(2.7e-3 at these operands; a dropped k-term is 4e-2 .. 4e-1).  It is computed from the fp64 operands, not from any kernel output.
+
+Observed on an MI355X, kernel / calibration (maximum of |out - fp64 chain|, the bf16 store's own half ulp taken off, over the maximum of
+|fp32 chain - fp64 chain|); the gates allow MARGIN = 3, plus flip_bound where noted:
+  fused FFN (v3-hilo, v3, v2)             300 rows: max 1.06, rms 1.02        1000 rows: max 1.47, rms 1.04
+  bf16 attention (nb, T)                  (5, 88) 0.19   (3, 34) 0.04   (2, 96) 0.86   (4, 11) 0.00   (2, 30) 0.46
+  LN + FiLM + SiLU -> Linear (pro 2),     (1000 rows, T 88, 7 clips) 1.73   (1000, 30, 6) 3.55   (1000, 34, 5) 1.00
+    both generations, fp32 and hi / lo    (300, 64, 3) 226 and (44, 11, 4) 924: the CPU chain has no flip at all in these rows (calibration
+                                          8.1e-7 / 6.9e-7), the kernel one of 1.8e-4 / 6.3e-4 - at most 0.68 of flip_bound, which carries
+                                          these chains (the kernel's maximum is 2.0e-3 .. 2.3e-3 at the 1000-row shapes)
+  LN -> Linear, normalise-first (pro 1,   (1000, 88, 7) 3.89   (300, 64, 3) 3.41 - its statistics are E[x^2] - mean^2 of fp32 sums, more
+    first generation)                     flips than torch's LayerNorm; with flip_bound the worst element uses 0.84 of its allowance
+Every mutant of test_bf16_gates_cpu.py is rejected with these gates.
+
+The input builders below restate the generator sequences of the op tests in test_gpu_ops.py, so that test_bf16_gates_cpu.py checks the
+gates on the very operands the GPU tests use.
+"""
+import torch
+import torch.nn.functional as F
+
+MARGIN = 3.0
+GELU_APPROX = 1e-4          # tl_common.h documents 9.5e-5 for gelu_fast against the erf form
+_ACTS = {0: lambda v: v, 1: F.silu, 2: F.gelu}
+
+
+# ---- elementary gates ----------------------------------------------------------------------------------------------------------------
+def ulp_bf16(v):
+    """2^(floor(log2 |v|) - 7) in fp64; |v| below the smallest normal (2^-126, 0 included) takes the denormal spacing 2^-133."""
+    a = torch.as_tensor(v, dtype=torch.float64).abs()
+    _, e = torch.frexp(a.clamp_min(2.0 ** -126))              # a = m 2^e, m in [0.5, 1): floor(log2 a) = e - 1
+    return torch.ldexp(torch.ones_like(a), e - 8)
+
+
+def accum_bound(absx, absw, K):
+    """K * 2^-23 * (|X| @ |W|^T): worst-case error of accumulating the K exact products of a row in fp32, in any order."""
+    return K * 2.0 ** -23 * (absx.double().abs() @ absw.double().abs().T)
+
+
+def _locate(err, allow, frames, nb):
+    excess = err - allow
+    excess = torch.where(torch.isnan(excess), torch.full_like(excess, float("inf")), excess)
+    i = int(excess.argmax())
+    ncol = err.shape[-1]
+    r, c = i // ncol, i % ncol
+    msg = f"worst element row {r} col {c} (row % 32 = {r % 32}, col % 32 = {c % 32}"
+    if frames:
+        msg += f", clip {(r // frames) % max(nb, 1)}, frame {r % frames}"
+    return r, c, msg + ")"
+
+
+def _check(out, ref64, allow, what, frames, nb):
+    o = out.detach().cpu().double().reshape(-1, out.shape[-1])
+    ref = ref64.detach().cpu().double().reshape(o.shape)
+    allow = allow.reshape(o.shape) if allow.dim() else allow.expand(o.shape)
+    err = (o - ref).abs()
+    bad = ~(err <= allow)                                      # NaN / Inf in the output fail
+    if bool(bad.any()):
+        r, c, where = _locate(err, allow, frames, nb)
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements outside the gate; {where}: out {float(o[r, c])!r} "
+                             f"ref {float(ref[r, c])!r} |diff| {float(err[r, c]):.3e} allowed {float(allow[r, c]):.3e}")
+    return float((err / allow.clamp_min(1e-300)).max())
+
+
+def assert_rounded(out_bf16, ref64, slack=0.0, what="bf16 output", frames=0, nb=0):
+    """Every element: |out - ref| <= 0.5 ulp_bf16(max(|out|, |ref|)) + slack.  Returns the largest |diff| / allowance."""
+    o = out_bf16.detach().cpu().double()
+    r = ref64.detach().cpu().double().reshape(o.shape)
+    big = torch.maximum(o.abs(), r.abs())
+    big = torch.where(torch.isfinite(big), big, torch.zeros_like(big))
+    allow = 0.5 * ulp_bf16(big) + torch.as_tensor(slack, dtype=torch.float64)
+    return _check(out_bf16, ref64, allow.reshape(-1, o.shape[-1]), what, frames, nb)
+
+
+def assert_close_f32(out_f32, ref64, slack, what="fp32 output", frames=0, nb=0):
+    """Every element: |out - ref| <= slack (the fp32 store itself is inside accum_bound for every K >= 2)."""
+    o = out_f32.detach().cpu().double()
+    allow = torch.as_tensor(slack, dtype=torch.float64)
+    if allow.dim():
+        allow = allow.reshape(-1, o.shape[-1])
+    return _check(out_f32, ref64, allow, what, frames, nb)
+
+
+def assert_rms(out, ref64, gate, what="rms"):
+    rms = float((out.detach().cpu().double() - ref64.double()).pow(2).mean().sqrt())
+    assert rms <= gate, f"{what}: rms error {rms:.3e} above the gate {gate:.3e}"
+    return rms / gate
+
+
+def bf16_rounding_rms(ref64):
+    """rms of the round-to-nearest bf16 store of ref: ulp / sqrt(12) per element."""
+    return float((ulp_bf16(ref64) ** 2 / 12.0).mean().sqrt())
+
+
+def calibrate(chain32, chain64, margin=MARGIN):
+    """(slack, rms gate without output rounding) of a chain with internal bf16 rounding points: margin * (max, rms) of the difference
+    between its fp32 and its fp64 evaluation."""
+    d = chain32.double() - chain64.double()
+    return margin * float(d.abs().max()), margin * float(d.pow(2).mean().sqrt())
+
+
+def flip_bound(s, W):
+    """One rounding flip of the coarsest bf16 operand of row m, met by the largest weight of output n: max_k ulp(s_mk) * max_k |w_nk|."""
+    return ulp_bf16(s).max(dim=1, keepdim=True).values * W.double().abs().max(dim=1).values[None, :]
+
+
+def prologue_slack(t, Mv, T, nb, pro, act, ref64, **kw):
+    """Slack of a LayerNorm [+ FiLM + SiLU] -> bf16 -> Linear chain: MARGIN x calibration + one worst-placed flip.  Returns (slack, cal)."""
+    cal = float((tl_chain(t, Mv, T, nb, pro, act, torch.float32, **kw).double() - ref64).abs().max())
+    return MARGIN * cal + flip_bound(tl_prologue(t, Mv, T, nb, pro, torch.float64, **kw), t["W"]), cal
+
+
+SILU_LIP = 1.1             # max |d silu / dx| = 1.0998: a pre-activation slack s becomes SILU_LIP * s behind a SiLU (GELU: 1.13)
+GELU_LIP = 1.13
+
+
+def silu_hw(y):
+    """Allowance for the hardware exp and rcp of a SiLU epilogue: 2^-18 |y| (two ~1 ulp fp32 transcendentals and the multiply, with
+    room; assumed, not measured - the exact-operand tests record the observed maximum)."""
+    return 2.0 ** -18 * y.double().abs()
+
+
+def hilo_slack(R, ref):
+    """Residual stream as hi / lo bf16 planes (tl_common.h): lo = bf16(h - hi) leaves <= 2^-17 relative per store - once when the op
+    splits R, once when the kernel splits its fp32 result."""
+    return 2.0 ** -17 * (R.double().abs() + ref.double().abs())
+
+
+def rne(x, dt):
+    return x.bfloat16().to(dt)
+
+
+def truncate_bf16(x):
+    """fp -> bf16 by dropping the low 16 bits of the fp32 pattern (the store mutant)."""
+    return (x.float().contiguous().view(torch.int32) & -65536).view(torch.float32).bfloat16()
+
+
+# ---- token-per-lane Linear (test_tl_linear_all_denoiser_variants) -------------------------------------------------------------------
+def tl_inputs(K, N, pro, res, Mv, T, nb):
+    """The operands of test_tl_linear_all_denoiser_variants (same generator, same order), on the CPU."""
+    M = (Mv + 127) // 128 * 128
+    g = torch.Generator().manual_seed(K + N + pro)
+    t = {"X": (torch.randn(M, K, generator=g) * 1.5 + 0.3).bfloat16(), "W": (torch.randn(N, K, generator=g) / K ** 0.5).bfloat16(),
+         "b": torch.randn(N, generator=g)}
+    t["R"] = torch.randn(M, N, generator=g) if res else None
+    t["gam"] = 1 + 0.1 * torch.randn(K, generator=g)
+    t["bet"] = 0.1 * torch.randn(K, generator=g)
+    t["film"] = 0.3 * torch.randn(nb, 2 * K, generator=g)
+    return t
+
+
+def tl_prologue(t, Mv, T, nb, pro, dt, kreal=None, film_rows=None):
+    """The bf16 operand rows the Linear multiplies: X itself (pro 0), or LayerNorm (pro 1 / 3) [+ FiLM + SiLU (pro 2)] rounded to bf16.
+    film_rows: clip index per row (default (row // T) % nb)."""
+    K = t["X"].shape[1]
+    kreal = kreal or K
+    x = t["X"][:Mv].to(dt)
+    if pro == 0:
+        return x
+    xr = x[:, :kreal]
+    y = F.layer_norm(xr, (kreal,), t["gam"][:kreal].to(dt), t["bet"][:kreal].to(dt), 1e-5)
+    if pro == 2:
+        rows = torch.arange(Mv)
+        f = t["film"].to(dt)[(rows // T) % nb if film_rows is None else film_rows]
+        y = F.silu(y * (1 + f[:, :K]) + f[:, K:])
+    out = torch.zeros(Mv, K, dtype=dt)
+    out[:, :kreal] = rne(y, dt)
+    return out
+
+
+def tl_chain(t, Mv, T, nb, pro, act, dt, kreal=None, reverse=False, gelu_noise=None, **kw):
+    """prologue -> Linear -> activation -> + residual in dtype dt; reverse: the K order of the accumulation flipped."""
+    xin = tl_prologue(t, Mv, T, nb, pro, dt, kreal, **kw)
+    W = t["W"].to(dt)
+    y = (xin.flip(1) @ W.flip(1).T if reverse else xin @ W.T) + t["b"].to(dt)
+    y = _ACTS[act](y)
+    if act == 2 and gelu_noise is not None:
+        y = y + gelu_noise.to(dt)
+    if t["R"] is not None:
+        y = y + t["R"][:Mv].to(dt)
+    return y
+
+
+def gelu_noise(shape, seed=1):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.rand(shape, generator=g) * 2 - 1) * GELU_APPROX
+
+
+def tl_folded(t, Mv, pro, act, kreal=None):
+    """The folded-LayerNorm Linear of the second generation, from the operands the op helper builds:
+    W' = bf16(gamma * W), c = sum_k W', d = b + W beta, y = rstd (x W'^T - mean c) + d, in fp64; and the slack of its fp32 evaluation.
+      * x W'^T: accum_bound, scaled by rstd;
+      * mean (an fp32 sum of K values): K 2^-23 mean|x|, times rstd |c|, plus the fp32 rounding of c;
+      * rstd: the variance is E[x^2] - mean^2 of fp32 sums, K 2^-23 (E[x^2] + mean^2) absolute, i.e. half of that over var relative
+        on rstd, plus 2^-22 for the hardware rsq — times |y - d| (the cancellation term of the large-mean test:
+        it grows with mean^2 / var);
+      * four fp32 roundings of the epilogue on |rstd S|, |rstd mean c|, |d|.
+    Returns (reference of the pre-activation, slack of the pre-activation, reference after the activation)."""
+    K = t["X"].shape[1]
+    kreal = kreal or K
+    x = t["X"][:Mv].double()
+    Wf = (t["W"].float() * t["gam"].float()).bfloat16().double()
+    Wf[:, kreal:] = 0
+    c = Wf.sum(1).float().double()
+    d = (t["b"].double() + t["W"].double()[:, :kreal] @ t["bet"].double()[:kreal]).float().double()
+    xr = x[:, :kreal]
+    mean = xr.mean(-1, keepdim=True)
+    ex2 = (xr * xr).mean(-1, keepdim=True)
+    var = ex2 - mean * mean
+    rstd = 1 / torch.sqrt(var + 1e-5)
+    S = xr @ Wf[:, :kreal].T
+    y = rstd * (S - mean * c) + d
+    eps = 2.0 ** -23
+    rel_rstd = 0.5 * K * eps * (ex2 + mean * mean) / var + 2 * eps
+    slack = (rstd * (accum_bound(xr, Wf[:, :kreal], K) + c.abs() * (K * eps * xr.abs().mean(-1, keepdim=True) + eps * mean.abs()))
+             + rel_rstd * (y - d).abs() + 4 * eps * (rstd * (S.abs() + (mean * c).abs()) + d.abs()))
+    return y, slack, _ACTS[act](y)
+
+
+# ---- fused FFN (test_tl2_ffn_fused_matches_reference) ---------------------------------------------------------------------------------
+def ffn_inputs(Mv, T, nb, n_const):
+    D, Fh = 512, 1024
+    M = (Mv + 127) // 128 * 128
+    g = torch.Generator().manual_seed(Mv + T)
+    t = {"X": (torch.randn(M, D, generator=g) * 1.2 + 0.2).bfloat16(), "H": torch.randn(M, D, generator=g),
+         "W1": (torch.randn(Fh, D, generator=g) / D ** 0.5).bfloat16(), "W2": (torch.randn(D, Fh, generator=g) / Fh ** 0.5).bfloat16(),
+         "W3": (torch.randn(D, D, generator=g) / D ** 0.5).bfloat16()}
+    t["b1"], t["b2"], t["b3"] = (0.3 * torch.randn(n, generator=g) for n in (Fh, D, D))
+    t["gam"] = 1 + 0.1 * torch.randn(D, generator=g)
+    t["bet"] = 0.1 * torch.randn(D, generator=g)
+    t["film"] = 0.3 * torch.randn(nb, 2 * D, generator=g)
+    t["rc"] = torch.randn(D, generator=g)
+    return t
+
+
+def ffn_chain(t, Mv, T, nb, n_const, dt, reverse=False, noise=None, film_rows=None, w3=None, b3=None):
+    """linear1 -> GELU -> bf16 -> linear2 -> LayerNorm -> FiLM -> SiLU -> bf16 -> linear3 -> + H (+ row constant), in dtype dt."""
+    D = 512
+    mm = (lambda a, w: a.flip(1) @ w.flip(1).T) if reverse else (lambda a, w: a @ w.T)
+    hid = F.gelu(mm(t["X"][:Mv].to(dt), t["W1"].to(dt)) + t["b1"].to(dt))
+    if noise is not None:
+        hid = hid + noise.to(dt)
+    hid = rne(hid, dt)
+    y2 = mm(hid, t["W2"].to(dt)) + t["b2"].to(dt)
+    rows = torch.arange(Mv)
+    f = t["film"].to(dt)[(rows // T) % nb if film_rows is None else film_rows]
+    s_ = F.silu(F.layer_norm(y2, (D,), t["gam"].to(dt), t["bet"].to(dt), 1e-5) * (1 + f[:, :D]) + f[:, D:])
+    W3 = t["W3"].to(dt) if w3 is None else w3.to(dt)
+    bb = t["b3"].to(dt) if b3 is None else b3.to(dt)
+    y = mm(rne(s_, dt), W3) + bb + t["H"][:Mv].to(dt)
+    if n_const:
+        y[:n_const] += t["rc"].to(dt)
+    return y
+
+
+# ---- bf16 linear attention (test_linear_attention_bf16_mfma) ------------------------------------------------------------------------
+def attn_inputs(nb, T):
+    g = torch.Generator().manual_seed(T + nb)
+    return (torch.randn(nb, T, 3 * 512, generator=g) * 2).bfloat16()
+
+
+def attn_chain(qkv, dt, lens=None, hd=64, rounded=True):
+    """y = softmax_channels(q) (softmax_time(k)^T v) per head; with `rounded`, k^, A = k^T v and q^ are rounded to bf16 as the MFMA
+    kernels do.  lens: frames per clip that enter the time-softmax (rows behind them are excluded by selection)."""
+    nb, T, D3 = qkv.shape
+    D = D3 // 3
+    H = D // hd
+    r = (lambda v: rne(v, dt)) if rounded else (lambda v: v)
+    out = torch.zeros(nb, T, D, dtype=dt)
+    for b in range(nb):
+        n = T if lens is None else lens[b % len(lens)]
+        q, k, v = (qkv[b, :, i * D:(i + 1) * D].to(dt).view(T, H, hd) for i in range(3))
+        kh = r(k[:n].softmax(dim=0))
+        A = r(torch.einsum("nhd,nhl->hdl", kh, v[:n]))
+        out[b] = torch.einsum("nhd,hdl->nhl", r(q.softmax(dim=-1)), A).reshape(T, D)
+    return out
