@@ -794,6 +794,41 @@ int dsh_inv_standardize(void* hip_stream, const float* x, int64_t n, int32_t cha
     API_END
 }
 
+static int check_rotation_args(const char* what, const void* x, int64_t ld_x, int64_t rows, int32_t joints, const void* m0, const void* s0,
+                               const void* m1, const void* s1, const int32_t* lengths_dev, int32_t frames) {
+    DSH_REQUIRE(joints >= 1, std::string(what) + ": joints must be at least 1");
+    DSH_REQUIRE(ld_x >= 3 * (int64_t)joints, std::string(what) + ": input stride below 3 * joints");
+    DSH_REQUIRE(m0 && s0 && m1 && s1, std::string(what) + ": null statistics pointer");
+    DSH_REQUIRE(x && rows >= 0, std::string(what) + ": null input or negative row count");
+    DSH_REQUIRE(!lengths_dev || (frames >= 1 && rows % frames == 0), std::string(what) + ": lengths need frames >= 1 dividing rows");
+    return 0;
+}
+
+int dsh_axis_angle_to_euler(void* hip_stream, const float* x, int64_t ld_x, int64_t rows, int32_t joints, const float* mean_aa,
+                            const float* std_aa, const float* mean_e, const float* std_e, float* y_std, int64_t ld_std, float* y_deg,
+                            int64_t ld_deg, const int32_t* lengths_dev, int32_t frames) {
+    API_BEGIN
+    if (int e = check_rotation_args("dsh_axis_angle_to_euler", x, ld_x, rows, joints, mean_aa, std_aa, mean_e, std_e, lengths_dev, frames)) return e;
+    DSH_REQUIRE(y_std || y_deg, "dsh_axis_angle_to_euler: both outputs null");
+    DSH_REQUIRE((!y_std || ld_std >= 3 * (int64_t)joints) && (!y_deg || ld_deg >= 3 * (int64_t)joints),
+                "dsh_axis_angle_to_euler: output stride below 3 * joints");
+    return dsh::launch_axis_angle_to_euler(x, ld_x, rows, joints, mean_aa, std_aa, mean_e, std_e, y_std, ld_std, y_deg, ld_deg, lengths_dev,
+                                           frames, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_euler_to_axis_angle(void* hip_stream, const float* x, int64_t ld_x, int64_t rows, int32_t joints, const float* mean_e,
+                            const float* std_e, const float* mean_aa, const float* std_aa, float* y, int64_t ld_y,
+                            const int32_t* lengths_dev, int32_t frames) {
+    API_BEGIN
+    if (int e = check_rotation_args("dsh_euler_to_axis_angle", x, ld_x, rows, joints, mean_e, std_e, mean_aa, std_aa, lengths_dev, frames)) return e;
+    DSH_REQUIRE(y, "dsh_euler_to_axis_angle: both outputs null (there is one)");
+    DSH_REQUIRE(ld_y >= 3 * (int64_t)joints, "dsh_euler_to_axis_angle: output stride below 3 * joints");
+    return dsh::launch_euler_to_axis_angle(x, ld_x, rows, joints, mean_e, std_e, mean_aa, std_aa, y, ld_y, lengths_dev, frames,
+                                           reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
 int dsh_op_ddim_step(void* hip_stream, float* x, const float* eps, const float* gt, const uint8_t* mask, const float* noise2,
                      int32_t B, int32_t frames, int32_t channels, float c1, float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev,
                      int32_t overlap_len, int32_t blend, int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi) {

@@ -173,6 +173,14 @@ int launch_untile_rows_hilo(const void* hi, const void* lo, int Wd, int M, int w
 
 int launch_interp_time(const float* x, int B, int Tin, int C, float* y, int Tout, hipStream_t s);
 int launch_affine_cols(const float* x, size_t n, int C, const float* mean, const float* stdv, float* y, hipStream_t s);
+// BEAT results tail (rotation.hip): standardised axis-angle <-> standardised Euler 'XYZ' degrees per joint triple, rows addressed by a stride
+// (elements), optional per-clip lengths (device int32, `frames` rows per clip: rows behind a clip's length are written as zeros)
+int launch_axis_angle_to_euler(const float* x, long long ldx, long long rows, int joints, const float* mean_aa, const float* std_aa,
+                               const float* mean_e, const float* std_e, float* y_std, long long ld_std, float* y_deg, long long ld_deg,
+                               const int* lengths, int frames, hipStream_t s);
+int launch_euler_to_axis_angle(const float* x, long long ldx, long long rows, int joints, const float* mean_e, const float* std_e,
+                               const float* mean_aa, const float* std_aa, float* y, long long ldy, const int* lengths, int frames,
+                               hipStream_t s);
 
 // linear ("efficient") self-attention core: y = softmax_ch(Q) (softmax_time(K)^T V)   (transformer.py:122-128)
 // lens (device int32, nullable): ragged batch — clip b has lens[b % lmod] valid frames out of `frames` (the padded stride); frames beyond

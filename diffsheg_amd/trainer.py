@@ -5,8 +5,10 @@ ddpm_beat_trainer.py:185-220, :932-1039), plus the sharding of independent chain
 (the reference shards test videos with a DistributedSampler, ddpm_show_trainer.py:743-750).
 
 The validation loop's tail (ddpm_show_trainer.py:440-583: FGD encoder, MSE / PCK / diversity meters) is ``validate_batch`` /
-``validation_summary`` on top of :mod:`diffsheg_amd.metrics`.  Training, BVH/JSON writers, HuBERT extraction and checkpoint saving
-are out of scope.
+``validation_summary`` on top of :mod:`diffsheg_amd.metrics`.  The BEAT results tail (ddpm_beat_trainer.py:1044-1060: gesture channels
+from standardised axis-angle to the standardised Euler degrees the reference saves and scores) is the ``pose_rep="euler"`` keyword of
+the sampling entry points, on :func:`diffsheg_amd.glue.axis_angle_to_euler`.  Training, BVH/JSON writers, HuBERT extraction and
+checkpoint saving are out of scope.
 """
 from __future__ import annotations
 
@@ -120,14 +122,58 @@ class DDPMTrainer:
                                                   rescale_timesteps=False, **kw)
         # validation (ddpm_show_trainer.py:440-583): eval_model = a metrics.HalfEmbeddingNet, or None for no FGD (--no_fgd)
         self.eval_model = eval_model
+        self.pose_stats = None
         self.reset_validation()
 
-    def generate_batch(self, audio_emb, p_id, dim_pose, add_cond={}, inpaint_dict=None, cond_scale=None, lengths=None, **sampler_kw):
+    # ---- BEAT results tail: gesture channels as the reference's standardised Euler angles (ddpm_beat_trainer.py:1044-1060) ----
+    def set_pose_stats(self, stats) -> None:
+        """The dataset's pose statistics (a :class:`diffsheg_amd.glue.PoseStats`, or ``None`` to drop them), placed on this trainer's
+        device.  Needed by ``pose_rep="euler"`` and :meth:`from_euler`; they change nothing else."""
+        from .glue import PoseStats
+        if stats is not None and not isinstance(stats, PoseStats):
+            raise ValueError(f"set_pose_stats takes a glue.PoseStats, got {type(stats).__name__}")
+        self.pose_stats = stats.to(self.device) if stats is not None else None
+
+    def _euler_requested(self, pose_rep: str) -> bool:
+        """``pose_rep`` of the sampling entry points: ``"axis_angle"`` (default) is the sampler's own representation, untouched."""
+        if pose_rep == "axis_angle":
+            return False
+        if pose_rep != "euler":
+            raise ValueError(f'pose_rep must be "axis_angle" or "euler", got {pose_rep!r}')
+        if getattr(self.opt, "dataset_name", "talkshow") == "talkshow":
+            raise ValueError('pose_rep="euler" is the BEAT results tail: SHOW results are SMPL-X parameters (glue.inv_standardize)')
+        if not getattr(self.opt, "axis_angle", True):
+            raise ValueError('pose_rep="euler" needs opt.axis_angle: without it the gesture channels already are Euler angles')
+        if getattr(self, "pose_stats", None) is None:
+            raise ValueError('pose_rep="euler" needs the pose statistics: call set_pose_stats first')
+        return True
+
+    def _gesture_split(self) -> int:
+        return int(getattr(self.opt, "split_pos", self.encoder.cfg.split_pos))
+
+    def _to_euler(self, motion: torch.Tensor, lengths=None) -> torch.Tensor:
+        from .glue import axis_angle_to_euler
+        return axis_angle_to_euler(motion, self.pose_stats, split_pos=self._gesture_split(), lengths=lengths)
+
+    def from_euler(self, pose: torch.Tensor, lengths=None) -> torch.Tensor:
+        """The inverse helper for ``motions``, ``head`` and ``tail``: ``[..., C]`` frames whose gesture channels are standardised Euler
+        degrees (what ``pose_rep="euler"`` returns, or BVH poses normalised with the Euler statistics) -> the sampler's standardised
+        axis-angle gesture channels (datasets/beat.py:376-401), expression channels unchanged; on the device.  ``lengths`` as for
+        :func:`diffsheg_amd.glue.euler_to_axis_angle`."""
+        from .glue import euler_to_axis_angle
+        self._euler_requested("euler")
+        return euler_to_axis_angle(pose.to(self.device), self.pose_stats, split_pos=self._gesture_split(), lengths=lengths)
+
+    def generate_batch(self, audio_emb, p_id, dim_pose, add_cond={}, inpaint_dict=None, cond_scale=None, lengths=None,
+                       pose_rep: str = "axis_angle", **sampler_kw):
         """ddpm_show_trainer.py:163-198.  ``sampler_kw`` (noise_source= / seed=) is this build's
         noise-injection hook; the reference draws from the global torch RNG.  ``cond_scale`` (a float, or one value per batch
         row) overrides ``opt.cond_scale`` for this batch.  ``lengths`` (one frame count per row, ``1 .. T``): clips of different
         lengths padded to ``T`` frames — row ``b`` is sampled as its first ``lengths[b]`` frames alone, the padded frames of the
-        result are 0 (the reference always passes ``cur_len = T``, which is the default)."""
+        result are 0 (the reference always passes ``cur_len = T``, which is the default).  ``pose_rep="euler"`` (BEAT): the gesture
+        channels of the returned sample are the reference's standardised Euler degrees, the expression channels are untouched and
+        padded frames stay 0; the default returns the sampler's result as it is, with no extra launch."""
+        euler = self._euler_requested(pose_rep)
         if cond_scale is not None:
             sampler_kw["cond_scale"] = cond_scale
         audio_emb = audio_emb.to(self.device)
@@ -139,10 +185,16 @@ class DDPMTrainer:
         model_kwargs = {"audio_emb": audio_emb, "length": cur_len, "person_id": p_id, "add_cond": add_cond,
                         "y": inpaint_dict, "pe_type": getattr(self.opt, "PE", "pe_sinu")}
         if getattr(self.opt, "ddim", True):
-            return self.diffusion_ddim_val.ddim_sample_loop(self.encoder, (B, T, dim_pose), clip_denoised=False,
-                                                            progress=True, model_kwargs=model_kwargs, **sampler_kw)
-        return self.diffusion.p_sample_loop(self.encoder, (B, T, dim_pose), clip_denoised=False, progress=True,
-                                            model_kwargs=model_kwargs, **sampler_kw)
+            out = self.diffusion_ddim_val.ddim_sample_loop(self.encoder, (B, T, dim_pose), clip_denoised=False,
+                                                           progress=True, model_kwargs=model_kwargs, **sampler_kw)
+        else:
+            out = self.diffusion.p_sample_loop(self.encoder, (B, T, dim_pose), clip_denoised=False, progress=True,
+                                               model_kwargs=model_kwargs, **sampler_kw)
+        if not euler:
+            return out
+        if isinstance(out, dict):               # (same_overlap_noisy: the saved noisy tail stays in the sampler's representation)
+            return dict(out, sample=self._to_euler(out["sample"], lengths))
+        return self._to_euler(out, lengths)
 
     # ---- validation loop tail: FGD encoder + MSE / PCK / diversity (ddpm_show_trainer.py:440-583) -----------------------
     def reset_validation(self) -> None:
@@ -236,7 +288,7 @@ class DDPMTrainer:
     def sample_arbitrary_len(self, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor],
                              noise_source_for_window=None, seed: Optional[int] = None,
                              motions: Optional[torch.Tensor] = None, row_keys: Optional[Sequence[int]] = None,
-                             cond_scale=None, lengths: Optional[Sequence[int]] = None):
+                             cond_scale=None, lengths: Optional[Sequence[int]] = None, pose_rep: str = "axis_angle"):
         """The per-video body of test_arbitrary_len (ddpm_show_trainer.py:864-906): windows of n_poses
         with stride n_poses-overlap_len; window k>0 out-paints from the last overlap_len frames of
         window k-1 (sequential chain).  Output stays on the device (the reference copies every window
@@ -249,10 +301,15 @@ class DDPMTrainer:
         ``[B, N_max, ...]``, chain ``b`` is their first ``lengths[b]`` frames (what lies behind is never read into a valid frame).
         Every chain is sampled exactly as alone: its own window list (:func:`ragged_window_plan`), its next window out-painted from
         ITS last ``overlap_len`` valid frames, with ``row_keys`` its own noise.  Returns a LIST of ``[lengths[b], C]`` tensors
-        (not a padded tensor); ``opt.same_overlap_noisy`` is refused."""
+        (not a padded tensor); ``opt.same_overlap_noisy`` is refused.
+
+        ``pose_rep="euler"`` (BEAT, after :meth:`set_pose_stats`): the chain is sampled as always and the gesture channels of the
+        finished result (of every result of the list form) are converted to the reference's standardised Euler degrees."""
+        euler = self._euler_requested(pose_rep)
         if lengths is not None:
-            return self._sample_arbitrary_len_ragged(audio_emb, p_id, add_cond, [int(v) for v in lengths], noise_source_for_window, seed,
+            outs = self._sample_arbitrary_len_ragged(audio_emb, p_id, add_cond, [int(v) for v in lengths], noise_source_for_window, seed,
                                                      motions, row_keys, cond_scale)
+            return [self._to_euler(o) for o in outs] if euler else outs
         opt = self.opt
         n_poses, L, C = int(opt.n_poses), int(opt.overlap_len), int(opt.net_dim_pose)
         step = n_poses - L
@@ -294,7 +351,8 @@ class DDPMTrainer:
             if son:
                 previous_noisy_tail, outputs = outputs["saved_noisy_tail"], outputs["sample"]
             outs.append(outputs if ii == len(audio_list) - 1 else outputs[:, :step])
-        return torch.cat(outs, dim=1)
+        full = torch.cat(outs, dim=1)
+        return self._to_euler(full) if euler else full
 
 
     def _sample_arbitrary_len_ragged(self, audio_emb, p_id, add_cond, lengths: List[int], noise_source_for_window, seed, motions,
@@ -518,7 +576,8 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
                                  add_cond: Optional[Dict[str, torch.Tensor]], n_segments: int, seed: int = 0, group=None,
                                  inputs_on_rank0_only: bool = False, max_chains_per_batch: int = 64,
                                  cond_scale: Optional[float] = None, seam_repair: bool = False,
-                                 seam_tail_blend: bool = True, ragged: bool = False) -> Optional[torch.Tensor]:
+                                 seam_tail_blend: bool = True, ragged: bool = False,
+                                 pose_rep: str = "axis_angle") -> Optional[torch.Tensor]:
     """BASELINE config 4: one long feature stream ``[1, N, ...]`` sampled on all ranks of ``group``.
 
     Windows of ONE chain are sequential (window k needs the final sample of window k-1 at every denoising step,
@@ -550,7 +609,11 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
     ``max_chains_per_batch``) instead of one chain batch per distinct length after another — the number of sequential windows is that
     of the longest chain, not the sum over the distinct lengths.  Every chain is still the chain sampled alone with its id as row key;
     the seam repair runs behind the chains as before.  Default ``False``: the grouping by length, bit for bit.
+
+    ``pose_rep="euler"`` (BEAT, after ``trainer.set_pose_stats``): chains, gather and seam repair run in the sampler's axis-angle
+    representation as always; rank 0 converts the gesture channels of the finished stream to the reference's standardised Euler degrees.
     """
+    euler = trainer._euler_requested(pose_rep)
     if cond_scale is not None and not isinstance(cond_scale, numbers.Real):
         raise ValueError("sample_arbitrary_len_sharded takes one scalar cond_scale for its stream")
     import torch.distributed as dist
@@ -618,7 +681,8 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
         last = [shard_range(len(segs), r, world) for r in range(world)]
         between = [r[-1] for r in last if len(r) and r[-1] < len(segs) - 1]
         _repair_seams(trainer, full, 0, between, segs, audio_emb, add_cond, pid, seed, max_chains_per_batch, cond_scale, seam_tail_blend)
-    return full.unsqueeze(0)
+    full = full.unsqueeze(0)
+    return trainer._to_euler(full) if euler else full
 
 
 def gather_outputs(local: torch.Tensor, world_sizes: Sequence[int], group=None) -> Optional[List[torch.Tensor]]:

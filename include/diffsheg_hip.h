@@ -208,6 +208,31 @@ int dsh_interp_time(void* hip_stream, const float* x, int32_t batch, int32_t fra
 /* y = x * std[c] + mean[c] over n contiguous fp32 values with `channels` innermost (datasets/show.py:157-162). */
 int dsh_inv_standardize(void* hip_stream, const float* x, int64_t n, int32_t channels, const float* mean, const float* stdv,
                         float* y);
+/* BEAT results tail (trainers/ddpm_beat_trainer.py:1044-1060, :1318-1333, :811-817): the gesture channels of a sampled result are
+ * standardised axis-angle vectors (--axis_angle); what the reference saves, scores and writes to BVH are standardised Euler 'XYZ' angles
+ * in degrees.  Per row r < rows and joint j < joints, on the three values x[r * ld_x + 3 j ..]:
+ *   v = x * std_aa + mean_aa -> quaternion -> rotation matrix -> Euler XYZ (datasets/rotation_converter.py:204-233, :251-280, :342-381)
+ *   -> degrees -> y_deg[r * ld_deg + 3 j ..];  (deg - mean_e) / std_e -> y_std[r * ld_std + 3 j ..].
+ * fp32, the reference's order of operations, accurate transcendentals.  One deviation: the asin argument is clamped to [-1, 1], so a joint
+ * at gimbal lock gives +-90 degrees where the reference's fp32 run gives NaN when R02 rounds past 1.  Either output may be NULL (not
+ * both).  Strides are in elements and >= 3 * joints: ld_x = 192, joints = 47 reads the gesture columns of a BEAT [B, T, 192] result in
+ * place; columns behind 3 * joints are neither read nor written.  The four statistics are device fp32 [3 * joints].
+ * lengths_dev (nullable, device int32 [rows / frames]; rows % frames == 0): row r belongs to clip r / frames at frame r % frames; rows at
+ * frames >= lengths_dev[clip] are written as exact zeros in both outputs and never read (the ragged sampler's convention: padded frames
+ * of a result are 0 - converting a zero pad would otherwise give -mean_e / std_e).  Asynchronous on hip_stream; a result does not depend
+ * on the launch geometry.  -1: joints < 1, a stride below 3 * joints, a null input or statistics pointer, both outputs null, rows < 0,
+ * lengths with frames < 1 or rows % frames != 0. */
+int dsh_axis_angle_to_euler(void* hip_stream, const float* x, int64_t ld_x, int64_t rows, int32_t joints, const float* mean_aa,
+                            const float* std_aa, const float* mean_e, const float* std_e, float* y_std, int64_t ld_std, float* y_deg,
+                            int64_t ld_deg, const int32_t* lengths_dev, int32_t frames);
+/* The inverse, the direction the dataset takes from BVH Euler data to its axis-angle targets (datasets/beat.py:376-401):
+ *   deg = x * std_e + mean_e -> radians -> Rx Ry Rz (rotation_converter.py:147-173) -> quaternion (the candidate with the largest |q|
+ *   component, 0.1 floor in the denominator, :44-103) -> axis-angle (:12-40; the angle may exceed pi, as in the reference)
+ *   -> (aa - mean_aa) / std_aa -> y[r * ld_y + 3 j ..].
+ * Strides, statistics, lengths_dev and refusals as above. */
+int dsh_euler_to_axis_angle(void* hip_stream, const float* x, int64_t ld_x, int64_t rows, int32_t joints, const float* mean_e,
+                            const float* std_e, const float* mean_aa, const float* std_aa, float* y, int64_t ld_y,
+                            const int32_t* lengths_dev, int32_t frames);
 
 /* ---- unit kernels (device pointers; used by the kernel-level parity tests) -------------------- */
 /* C[M,N] = act(A[M,K] W[N,K]^T + bias) (+ R); dtype 0: fp32 operands, 1: bf16 operands (uint16 bits).
