@@ -50,6 +50,7 @@ SYMBOLS = {
     "dsh_weight_bytes": (C.c_int64, [_P]),
     "dsh_set_condition": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P]),
     "dsh_set_condition_ragged": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P]),
+    "dsh_set_modality": (C.c_int, [_P, C.c_int32, _P]),
     "dsh_eval": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "dsh_eval_flops": (C.c_double, [_P]),
     "dsh_profile_enable": (C.c_int, [_P, C.c_int32]),

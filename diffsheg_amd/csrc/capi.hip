@@ -195,7 +195,21 @@ int dsh_eval(dsh_ctx* ctx, const float* x, const int64_t* t, const float* c1, co
         ctx->den->t_uniform = uni && dsh::emb_dedup_enabled();
     }
     if (int e = check_guidance(ctx)) return e;
-    return ctx->den->eval(x, t, c1, c2, eps);
+    if (int e = ctx->den->eval(x, t, c1, c2, eps)) return e;
+    // one modality alone: the inactive encoder's columns of eps are 0 (it was not launched)
+    if (const int mod = ctx->den->modality) {
+        const int g = ctx->den->gesture_channels(), Cc = ctx->cfg.channels();
+        DSH_REQUIRE(g > 0 && g < Cc && eps, "a partial modality needs the UniDiffuser's two encoders");
+        return dsh::launch_fill_cols(eps, Cc, (size_t)ctx->den->batch * ctx->den->frames, mod == 1 ? 0 : g, mod == 1 ? g : Cc, nullptr, 0, ctx->stream);
+    }
+    return 0;
+    API_END
+}
+
+int dsh_set_modality(dsh_ctx* ctx, int32_t modality, const float* expression) {
+    API_BEGIN
+    DSH_REQUIRE(ctx, "null context");
+    return ctx->den->set_modality(modality, expression);
     API_END
 }
 

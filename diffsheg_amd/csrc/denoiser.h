@@ -119,6 +119,21 @@ class DenoiserBase {
     virtual int loop_begin(int /*kind*/) { return 0; }
     virtual int loop_end() { return 0; }
     virtual int gesture_channels() const { return -1; }          // channels [0, g) belong to the gesture encoder, [g, C) to the expression encoder
+    // One modality alone (UniDiffuser only).  Part of the condition: set_condition(_ragged) resets it to 0, set_modality() follows it.
+    //   0 both: the joint evaluation.  1 expression: encoder_aud + encoder_exp run, no gesture-encoder launch is issued.  2 gesture:
+    //   encoder_aud + encoder_ges run, and the gesture encoder reads `expression` [B, T, E] (device fp32, standardised, the clean track)
+    //   wherever the joint evaluation reads the expression encoder's x0 estimate; the expression encoder is not launched.
+    // The track is copied into context-owned memory in stream order and packed once (launch_pack_expr_track) into every evaluating
+    // instance's expr_x0 / expr16 — a sub-batch instance takes its own clips' rows.  Every decision taken by token rows (sub-batch split,
+    // kernel families, graph and timestep-cache range) stays that of the joint run of the same (B, T), so the active columns of a partial
+    // evaluation are the joint evaluation's, bit for bit, given the same expression input.  Distinct from the pipelined loop's transient
+    // set_part(): that loop is not entered while a modality is set.  -1 before any state changes on an unknown value, a single-transformer
+    // model, no condition, or modality 2 without a track.
+    //   modality_track(): the context-owned copy of the track while the modality is 2 (what the sampler writes into the expression columns
+    //   of its result), else null.
+    virtual int set_modality(int /*modality*/, const float* /*expression*/) { return -1; }
+    virtual const float* modality_track() const { return nullptr; }
+    int modality = 0;
     // second instance sharing the finalized weights, working on another stream (null if not supported / not finalized)
     virtual DenoiserBase* clone_shared(hipStream_t) { return nullptr; }
     // record `ev` on this instance's stream after the n-th token-per-lane launch of every eval (phase offset of a twin)

@@ -109,6 +109,17 @@ class Denoiser final : public DenoiserBase {
         part = p;
         return 0;
     }
+    // one modality alone (denoiser.h): what this instance launches from now on; modality 2 with a track packs its clips' rows [batch, frames, E]
+    // into expr_x0 / expr16 on this instance's stream (the prefetch instance, which never evaluates an encoder, is given no track)
+    int set_modality(int m, const float* track) override {
+        DSH_REQUIRE(m >= 0 && m <= 2 && (m == 0 || !cfg.single_transformer), "set_modality: 0 both / 1 expression / 2 gesture (UniDiffuser only)");
+        if (m == 2 && track) {
+            DSH_REQUIRE(conditioned && expr_x0, "set_condition() must precede set_modality()");
+            if (int e = launch_pack_expr_track(track, cfg.expression_dim, batch, frames, lens, expr_x0, expr_ld(), tl_path() ? expr16 : nullptr, st)) return e;
+        }
+        modality = m;
+        return 0;
+    }
     int import_expr(DenoiserBase* src_, hipStream_t s) override {
         Denoiser<T>* src = dynamic_cast<Denoiser<T>*>(src_);
         DSH_REQUIRE(src && src != this && src->batch == batch && src->frames == frames && expr_x0 && src->expr_x0, "import_expr: incompatible instances");
@@ -405,7 +416,7 @@ class Denoiser final : public DenoiserBase {
                           (Cf ? (double)M * L.N * 4 : 0.0) + (Ct ? (double)M * L.N * 2 : 0.0) + (Clo ? (double)M * L.N * 2 : 0.0);
         int cls = PROF_TL_QKV;
         if (pro == 2) cls = PROF_TL_STY;
-        else if (pro == 3) cls = PROF_TL_FEAT1;
+        else if (pro == 3) cls = cat3 ? PROF_TL_FEAT1_EXPR : PROF_TL_FEAT1;
         else if (L.Kp == 1024) cls = R ? PROF_TL_FEAT3 : PROF_TL_FFN2;
         else if (pro == 0) cls = PROF_TL_FFN1;
         a.trace = nullptr;
@@ -480,6 +491,7 @@ class Denoiser final : public DenoiserBase {
     char* lvl_borrowed = nullptr; size_t lvl_borrowed_stride = 0; int lvl_borrowed_n = 0;   // prefetch instance: the main instance's slots
     bool light_cond = false;         // set_condition_light(): no hubert features -> only mode 3 may run
     int part = 0;                    // 0 whole evaluation / 1 expression encoder only / 2 gesture encoder only (pipelined small-batch loop, denoiser.h)
+    int active() const { return part != 0 ? part : modality; }   // the encoder this evaluation runs: the pipeline's transient part, else the condition's modality
     int level_copy(const int64_t* level, int restore);
 };
 
@@ -1184,8 +1196,11 @@ int Denoiser<T>::prep_audio(const int64_t* t) {
         aproj_done = false;
         const char* a2 = getenv("DSH_APROJ_TL");
         if (aud_ap_bias && tl_path() && !(a2 && atoi(a2) == 0)) {
-            if (int e = launch_tl_aproj(audio256, aud_stream + (size_t)18 * 16384, aud_ap_bias, 2, exp_.aproj_buf, ges_.aproj_buf, Mc, st)) return e;
-            flops_acc += 2.0 * 2.0 * Mc * 256.0 * 256.0;
+            // (one modality alone: the active encoder's audio_proj only — encoder e's fragments at + e * 128 KB, its bias at + e * 256)
+            const int me = modality == 2 ? 1 : 0, ne = modality == 0 ? 2 : 1;
+            if (int e = launch_tl_aproj(audio256, aud_stream + (size_t)18 * 16384 + (size_t)me * 65536, aud_ap_bias + me * 256, ne,
+                                        me ? ges_.aproj_buf : exp_.aproj_buf, ges_.aproj_buf, Mc, st)) return e;
+            flops_acc += ne * 2.0 * Mc * 256.0 * 256.0;
             aproj_done = true;                          // (prep_encoder skips its own audio_proj)
         }
         return 0;
@@ -1231,7 +1246,7 @@ int Denoiser<T>::level_copy(const int64_t* level, int restore) {
     LevelCopyArgs a;
     a.nseg = 0;
     for (size_t i = 0; i < es.size(); ++i) {
-        if (part != 0 && (int)i != part - 1) continue;      // (a partial evaluation touches its own encoder's share only; es = {exp, ges})
+        if (active() != 0 && (int)i != active() - 1) continue;      // (a partial evaluation touches its own encoder's share only; es = {exp, ges})
         a.work[a.nseg] = reinterpret_cast<char*>(es[i]->film_tab); a.bytes[a.nseg] = film; a.off[a.nseg] = i * (film + ap); ++a.nseg;
         a.work[a.nseg] = reinterpret_cast<char*>(es[i]->aproj_buf); a.bytes[a.nseg] = ap; a.off[a.nseg] = i * (film + ap) + film; ++a.nseg;
     }
@@ -1250,7 +1265,7 @@ int Denoiser<T>::eval_level(const float* x, const int64_t* t, const float* c1, c
     tl_launches = 0;
     if (mode == 3) {
         if (int e = prep_audio(t)) return e;
-        for (Encoder* E : encs()) { if (int e = prep_encoder(*E)) return e; }
+        for (Encoder* E : encs()) { if (active() == 0 || E == (active() == 1 ? &exp_ : &ges_)) { if (int e = prep_encoder(*E)) return e; } }
         return level_copy(level, 0);
     }
     if (mode == 2) {
@@ -1258,7 +1273,7 @@ int Denoiser<T>::eval_level(const float* x, const int64_t* t, const float* c1, c
     } else {
         // (a partial evaluation computes the shared head — timestep embedding, encoder_aud — and its own encoder's share)
         if (int e = prep_audio(t)) return e;
-        for (Encoder* E : encs()) { if (part == 0 || E == (part == 1 ? &exp_ : &ges_)) { if (int e = prep_encoder(*E)) return e; } }
+        for (Encoder* E : encs()) { if (active() == 0 || E == (active() == 1 ? &exp_ : &ges_)) { if (int e = prep_encoder(*E)) return e; } }
         if (mode == 1) { if (int e = level_copy(level, 0)) return e; }
     }
     // ---- expression, then gesture conditioned on the expression x0 estimate (transformer.py:741-768)
@@ -1266,8 +1281,9 @@ int Denoiser<T>::eval_level(const float* x, const int64_t* t, const float* c1, c
     if (cfg.single_transformer) {
         if (int e = run_encoder(ges_, x, 0, cfg.channels(), nullptr, 0, c1, c2, eps, false)) return e;
     } else {
-        if (part != 2) { if (int e = run_encoder(exp_, x, G_, E_, nullptr, 0, c1, c2, eps, true)) return e; }
-        if (part != 1) { if (int e = run_encoder(ges_, x, 0, G_, expr_x0, E_, c1, c2, eps, false)) return e; }
+        // (one modality alone: the gesture encoder reads the given track, packed into expr_x0 / expr16 by set_modality)
+        if (active() != 2) { if (int e = run_encoder(exp_, x, G_, E_, nullptr, 0, c1, c2, eps, true)) return e; }
+        if (active() != 1) { if (int e = run_encoder(ges_, x, 0, G_, expr_x0, E_, c1, c2, eps, false)) return e; }
     }
     flops_last_eval = flops_acc;
     return 0;
@@ -1327,6 +1343,7 @@ class DualDenoiser final : public DenoiserBase {
         for (hipEvent_t ev : events_) (void)hipEventDestroy(ev);
         if (cond_buf_) (void)hipFree(cond_buf_);
         if (len_buf_) (void)hipFree(len_buf_);
+        if (track_buf_) (void)hipFree(track_buf_);
         if (pf_.stream) (void)hipStreamDestroy(pf_.stream);
         for (hipEvent_t ev : pf_.lvl_ev) (void)hipEventDestroy(ev);
         if (pf_.ev_fork) (void)hipEventDestroy(pf_.ev_fork);
@@ -1363,6 +1380,11 @@ class DualDenoiser final : public DenoiserBase {
         if (twin_busy_) { DSH_HIP_CHECK(hipEventRecord(twin_ev_, twin_stream_)); DSH_HIP_CHECK(hipStreamWaitEvent(st_, twin_ev_, 0)); twin_busy_ = false; }
         twin_cond_ok_ = false;
         if (!inst_.empty()) (void)inst_[0]->set_part(0);
+        // the modality is part of the condition: a new condition is a joint one until set_modality() says otherwise
+        mod_ = 0; modality = 0;
+        for (auto& in : inst_) (void)in->set_modality(0, nullptr);
+        if (pf_.prep) (void)pf_.prep->set_modality(0, nullptr);
+        if (twin_) (void)twin_->set_modality(0, nullptr);
         if (na + np + nh > cond_cap_) {
             DSH_HIP_CHECK(hipStreamSynchronize(st_));
             if (cond_buf_) (void)hipFree(cond_buf_);
@@ -1392,6 +1414,28 @@ class DualDenoiser final : public DenoiserBase {
         batch = B; frames = T;
         return apply_condition((B == sticky_B_ && T == sticky_T_ && pipe_possible()) ? 1 : want_split(B, T));
     }
+    int set_modality(int m, const float* expression) override {
+        DSH_REQUIRE(m >= 0 && m <= 2, "set_modality: unknown modality (0 both / 1 expression / 2 gesture)");
+        DSH_REQUIRE(m == 0 || !cfg_.single_transformer, "set_modality: a single MotionTransformer has no separate expression / gesture encoders");
+        DSH_REQUIRE(cond_.B > 0, "set_condition() must precede set_modality()");
+        DSH_REQUIRE(m != 2 || expression, "set_modality: the gesture modality needs the expression track [B, T, expression_dim]");
+        if (m == 2) {
+            // context-owned copy, in stream order like the other conditioning tensors: a re-split re-packs from it (apply_condition), and the
+            // sampler writes it into the expression columns of its result
+            const size_t ne = (size_t)cond_.B * cond_.T * cfg_.expression_dim;
+            if (ne > track_cap_) {
+                DSH_HIP_CHECK(hipDeviceSynchronize());
+                if (track_buf_) (void)hipFree(track_buf_);
+                track_buf_ = nullptr; track_cap_ = 0;
+                DSH_HIP_CHECK(hipMalloc((void**)&track_buf_, ne * sizeof(float)));
+                track_cap_ = ne;
+            }
+            DSH_HIP_CHECK(hipMemcpyAsync(track_buf_, expression, ne * sizeof(float), hipMemcpyDeviceToDevice, st_));
+        }
+        mod_ = m; modality = m;
+        return push_modality(split_now_);
+    }
+    const float* modality_track() const override { return mod_ == 2 ? track_buf_ : nullptr; }
     int eval(const float* x, const int64_t* t, const float* c1, const float* c2, float* eps) override {
         DSH_REQUIRE(cond_.B > 0, "set_condition() must precede eval()");
         inst_[0]->prof = prof;
@@ -1473,6 +1517,7 @@ class DualDenoiser final : public DenoiserBase {
             DSH_HIP_CHECK(hipEventRecord(f.ev_fork, st_));
             DSH_HIP_CHECK(hipStreamWaitEvent(f.stream, f.ev_fork, 0));
             if (int e = f.prep->set_lengths(lens_)) return e;
+            if (int e = f.prep->set_modality(mod_, nullptr)) return e;           // (fills the active encoder's share of every slot only)
             if (int e = f.prep->set_condition_light(nb, cond_.T, cond_.audio, cond_.pid)) return e;
             if (int e = f.prep->adopt_level_slots(slots, stride, nslots)) return e;
             f.levels = n_levels; f.nb = nb;
@@ -1498,6 +1543,7 @@ class DualDenoiser final : public DenoiserBase {
     int pipe_begin(DenoiserBase** twin, hipStream_t* stream) override {
         const char* off = getenv("DSH_PIPE");
         if ((off && atoi(off) == 0) || cfg_.single_transformer || cond_.B <= 0 || split_now_ != 1 || !twin || !stream) return -1;
+        if (mod_ != 0) return -1;                                            // one modality alone: one chain, nothing to pipeline
         // (DDIM loops: the twin restores its head from the slots the prefetch run fills; loops without a timestep cache — DDPM — compute it)
         char* slots = nullptr; size_t stride = 0; int nslots = 0;
         const bool have_slots = pf_.active && inst_[0]->level_slots(&slots, &stride, &nslots) == 0;
@@ -1579,8 +1625,20 @@ class DualDenoiser final : public DenoiserBase {
         return 0;
     }
     int debug_copy(const std::string& what, float* out) override {
-        DSH_REQUIRE(split_now_ == 1, "debug taps are only available on single-stream (small-batch) evaluations");
-        return inst_[0]->debug_copy(what, out);
+        if (split_now_ == 1) return inst_[0]->debug_copy(what, out);
+        // sub-batch streams: every instance copies its own clips' rows on its own stream, joined into the context stream
+        const int w = what == "aud_feat" ? cfg_.audio_dim : cfg_.expression_dim;
+        DSH_HIP_CHECK(hipEventRecord(ev_fork_, st_));
+        for (int i = 0; i < split_now_; ++i) {
+            hipStream_t si = i == 0 ? st_ : streams_[i - 1];
+            if (i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(si, ev_fork_, 0));
+            if (int e = inst_[i]->debug_copy(what, out + (size_t)first_clip(i, split_now_) * cond_.T * w)) return e;
+            if (i > 0) {
+                DSH_HIP_CHECK(hipEventRecord(ev_join_[i - 1], si));
+                DSH_HIP_CHECK(hipStreamWaitEvent(st_, ev_join_[i - 1], 0));
+            }
+        }
+        return 0;
     }
 
   private:
@@ -1626,7 +1684,11 @@ class DualDenoiser final : public DenoiserBase {
         split_now_ = ns;
         for (int i = 0; i < ns; ++i) { if (int e = push_guidance(i, ns)) return e; }
         inst_[0]->prof = prof;
-        if (ns == 1) { if (int e = inst_[0]->set_lengths(lens_)) return e; return inst_[0]->set_condition(cond_.B, cond_.T, cond_.audio, cond_.pid, cond_.hubert); }
+        if (ns == 1) {
+            if (int e = inst_[0]->set_lengths(lens_)) return e;
+            if (int e = inst_[0]->set_condition(cond_.B, cond_.T, cond_.audio, cond_.pid, cond_.hubert)) return e;
+            return mod_ ? push_modality(1) : 0;
+        }
         DSH_HIP_CHECK(hipEventRecord(ev_fork_, st_));
         for (int i = 0; i < ns; ++i) {
             const int b0 = first_clip(i, ns), nb = first_clip(i + 1, ns) - b0;
@@ -1641,6 +1703,26 @@ class DualDenoiser final : public DenoiserBase {
                 DSH_HIP_CHECK(hipStreamWaitEvent(st_, ev_join_[i - 1], 0));
             }
         }
+        return mod_ ? push_modality(ns) : 0;
+    }
+    // the condition's modality to the ns evaluating instances (each packs its own clips' rows of the given track on its own stream, forked
+    // from and joined into the context stream), to the prefetch instance and (unused: the pipelined loop is not entered) the twin
+    int push_modality(int ns) {
+        const size_t row = (size_t)cond_.T * cfg_.expression_dim;
+        const float* tr = mod_ == 2 ? track_buf_ : nullptr;
+        if (ns > 1 && tr) DSH_HIP_CHECK(hipEventRecord(ev_fork_, st_));
+        for (int i = 0; i < (int)inst_.size(); ++i) {
+            if (i >= ns || !tr) { if (int e = inst_[i]->set_modality(mod_, nullptr)) return e; continue; }
+            hipStream_t si = i == 0 ? st_ : streams_[i - 1];
+            if (i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(si, ev_fork_, 0));
+            if (int e = inst_[i]->set_modality(mod_, tr + (size_t)(ns > 1 ? first_clip(i, ns) : 0) * row)) return e;
+            if (i > 0) {
+                DSH_HIP_CHECK(hipEventRecord(ev_join_[i - 1], si));
+                DSH_HIP_CHECK(hipStreamWaitEvent(st_, ev_join_[i - 1], 0));
+            }
+        }
+        if (pf_.prep) { if (int e = pf_.prep->set_modality(mod_, nullptr)) return e; }
+        if (twin_) { if (int e = twin_->set_modality(mod_, nullptr)) return e; }
         return 0;
     }
     // instance i of an ns-way split: the scales of its clips (first_clip(i, ns) onwards) when they are per clip
@@ -1661,6 +1743,8 @@ class DualDenoiser final : public DenoiserBase {
     const int* lens_ = nullptr;                            // len_buf_ while the current condition is ragged, else null
     std::vector<int32_t> lens_host_;
     size_t cond_cap_ = 0;
+    int mod_ = 0;                                          // the condition's modality (set_modality): 0 both / 1 expression / 2 gesture
+    float* track_buf_ = nullptr; size_t track_cap_ = 0;    // context-owned copy of the given expression track [B, T, E] (modality 2)
     // side-stream producer of the x-independent head of the whole batch (level_prefetch)
     struct Prefetch {
         std::unique_ptr<DenoiserBase> prep;                // shared weights, own workspace, conditioned with mel features + speaker only

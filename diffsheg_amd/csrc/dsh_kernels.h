@@ -140,6 +140,11 @@ void tl_pack_ffn_stream(int version, const uint16_t* w1p, const uint16_t* w2p, c
 template <typename TS>
 int launch_tile_rows_bf16(const TS* src, int ld, int M, int w, void* dst, int Wd, hipStream_t s);
 int launch_untile_rows_bf16(const void* src, int Wd, int M, int w, void* dst_bf16, int ld, hipStream_t s);
+// the given expression track of a gesture-only condition [B frames, E] fp32 -> fp32 rows x0 [.., ld] (pad columns zero) and, x16 != null, the
+// tiled bf16 operand [.., 128] exactly as launch_tile_rows_bf16 rounds it; lens != null: frames beyond a clip's length are written as zero
+int launch_pack_expr_track(const float* src, int E, int B, int frames, const int* lens, float* x0, int ld, void* x16, hipStream_t s);
+// columns [c_lo, c_hi) of dst [M, C] <- src [M, src_ld] (its first c_hi - c_lo columns), or 0 when src is null
+int launch_fill_cols(float* dst, int C, size_t M, int c_lo, int c_hi, const float* src, int src_ld, hipStream_t s);
 int launch_tile_rows_f32(const float* src, int ld, int M, float* dst, int Wd, hipStream_t s);
 int launch_untile_rows_f32(const float* src, int Wd, int M, float* dst, int ld, hipStream_t s);
 // FiLM table rows [scale | shift] -> folded [A | B] coefficients of the token-per-lane StylizationBlock prologue (in place)

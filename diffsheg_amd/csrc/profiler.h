@@ -12,6 +12,7 @@ namespace dsh {
 enum ProfClass : int {
     PROF_GEMM = 0, PROF_ATTN = 1, PROF_ROWOPS = 2, PROF_SAMPLER = 3,
     PROF_TL_QKV = 4, PROF_TL_STY = 5, PROF_TL_FFN1 = 6, PROF_TL_FFN2 = 7, PROF_TL_FEAT1 = 8, PROF_TL_FEAT3 = 9, PROF_RESERVED10 = 10, PROF_TL_FFN = 11,
+    PROF_TL_FEAT1_EXPR = 12,   // feat_proj.1 over the gesture encoder's concat form (fourth segment = the expression x0): no launch in an expression-only run
     PROF_NCLASS = 16
 };
 
@@ -34,7 +35,8 @@ inline const ProfClassInfo& prof_class_info(int cls, bool fp32) {
         {"tl_linear_kernel<1024, 0, true, 3, 0>", "feat_proj.3 + residual"},
         none,   // (slot of the round-1 chained kernel, removed: superseded by the fused FFN)
         {"tl2_ffn_kernel<false>", "ffn.linear1 -> GELU -> ffn.linear2 -> StylizationBlock(ffn) -> + h (one launch)"},
-        none, none, none, none};
+        {"tl2_linear_kernel<1024, 3, false, 2, 1, false> [+ expression segment]", "gesture encoder: feat_proj concat with the expression x0 segment + LayerNorm (folded) + Linear + SiLU"},
+        none, none, none};
     static const ProfClassInfo gemm32 = {"gemm_f32_pro_kernel<PRO> + gemm_nt_kernel<float, 1, MI, NJ>", "fp32 path: every Linear (exact-fp32 v_mfma_f32_32x32x2_f32, 64 x 64 tiles; round 6: the large launches on the software-pipelined LDS-DMA loop of gemm_f32_pro.hip, LayerNorms folded in, the FFN branch's StylizationBlock front in the operand staging)"};
     static const ProfClassInfo attn32 = {"linear_attention_f32_mfma(_sty)_kernel<TM>", "fp32 path: linear self-attention core on the exact-fp32 matrix pipe (round 6; with the attention branch's StylizationBlock front behind it for windows of up to 64 frames)"};
     static const ProfClassInfo ffn3 = {"tl3_ffn_kernel<false>", "ffn.linear1 -> GELU -> ffn.linear2 -> StylizationBlock(ffn) -> + h (one launch; tl3_ffn.hip)"};

@@ -374,6 +374,65 @@ int launch_tile_rows_bf16(const TS* src, int ld, int M, int w, void* dst, int Wd
 template int launch_tile_rows_bf16<float>(const float*, int, int, int, void*, int, hipStream_t);
 template int launch_tile_rows_bf16<bf16>(const bf16*, int, int, int, void*, int, hipStream_t);
 
+// Given expression track of a gesture-only condition (denoiser.h, set_modality): src [M = B frames, E] fp32 -> what the expression encoder
+// leaves behind for the gesture encoder's concat, in one launch: the fp32 rows x0 [M, ld] (columns E .. ld zero) and, on the bf16 path, the
+// tiled bf16 operand x16 [round_up(M, 32), 128] with the rounding and layout of tile_rows_bf16_kernel (Wd = 128).  lens != null (ragged
+// condition): frames >= lens[b] of clip b are written as zero whatever the caller's padding holds.
+__global__ void pack_expr_track_kernel(const float* __restrict__ src, int E, int M, int frames, const int* __restrict__ lens, float* x0, int ld,
+                                       char* x16, size_t nchunk) {
+    for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < nchunk; c += (size_t)gridDim.x * blockDim.x) {
+        const size_t tile = c >> 6;
+        const int j = (int)(c & 63), m = j >> 1, hh = j & 1;
+        const size_t tb = tile >> 3;
+        const int kt = (int)(tile & 7);
+        const size_t t = tb * 32 + m;
+        const int n0 = kt * 16 + hh * 8;
+        bool live = t < (size_t)M;
+        if (live && lens) { const size_t b = t / (size_t)frames; live = (int)(t - b * frames) < lens[b]; }
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = (live && n0 + i < E) ? src[t * E + n0 + i] : 0.f;
+        if (t < (size_t)M) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) if (n0 + i < ld) x0[t * ld + n0 + i] = v[i];
+        }
+        if (x16) {
+            tu32x4 o;
+            o.x = tile_pack2(v[0], v[1]); o.y = tile_pack2(v[2], v[3]); o.z = tile_pack2(v[4], v[5]); o.w = tile_pack2(v[6], v[7]);
+            *reinterpret_cast<tu32x4*>(x16 + c * 16) = o;
+        }
+    }
+}
+int launch_pack_expr_track(const float* src, int E, int B, int frames, const int* lens, float* x0, int ld, void* x16, hipStream_t s) {
+    DSH_REQUIRE(src && x0 && B > 0 && frames > 0 && E > 0 && E <= ld && ld <= 128, "pack_expr_track: the expression width must fit the 128-column concat segment");
+    const int M = B * frames;
+    const size_t nchunk = (size_t)ceil_div(M, 32) * 8 * 64;
+    const int blocks = (int)std::min<size_t>((nchunk + 255) / 256, 16384);
+    hipLaunchKernelGGL(pack_expr_track_kernel, dim3(blocks), dim3(256), 0, s, src, E, M, frames, lens, x0, ld, reinterpret_cast<char*>(x16), nchunk);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// dst[r, c] for c in [c_lo, c_hi) of M rows of C columns <- src[r * src_ld + (c - c_lo)], or 0 when src is null: the inactive columns of a
+// one-modality result (eps of dsh_eval, the final sample of dsh_sample)
+__global__ void fill_cols_kernel(float* __restrict__ dst, int C, size_t M, int c_lo, int c_hi, const float* __restrict__ src, int src_ld) {
+    const int w = c_hi - c_lo;
+    const size_t n = M * (size_t)w, stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const size_t r = i / (size_t)w;
+        const int c = (int)(i - r * w);
+        dst[r * C + c_lo + c] = src ? src[r * src_ld + c] : 0.f;
+    }
+}
+int launch_fill_cols(float* dst, int C, size_t M, int c_lo, int c_hi, const float* src, int src_ld, hipStream_t s) {
+    DSH_REQUIRE(dst && M > 0 && 0 <= c_lo && c_lo < c_hi && c_hi <= C && (!src || src_ld >= c_hi - c_lo), "fill_cols: invalid column window");
+    const size_t n = M * (size_t)(c_hi - c_lo);
+    const int blocks = (int)std::min<size_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(fill_cols_kernel, dim3(blocks), dim3(256), 0, s, dst, C, M, c_lo, c_hi, src, src_ld);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 __global__ void untile_rows_bf16_kernel(const char* src, int Wd, int M, int w, uint16_t* dst, int ld, size_t nchunk) {
     const int KT = Wd >> 4;
     for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < nchunk; c += (size_t)gridDim.x * blockDim.x) {

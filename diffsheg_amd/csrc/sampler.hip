@@ -258,6 +258,13 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
     DSH_REQUIRE(!(tail_blend && o.same_overlap_noisy), "tail_blend with same_overlap_noisy: the saved noisy tails describe a window chain, not a window pinned at both ends");
     DSH_REQUIRE(!tail_blend || (o.overlap_len >= 0 && 2 * (int64_t)o.overlap_len <= den->frames), "tail_blend: the head and the tail fade overlap (2 * overlap_len > frames)");
     const int B = den->batch;
+    // One modality alone (denoiser.h, set_modality): the loop advances the active encoder's column window [w_lo, w_hi) only — every step launch
+    // of every regime takes it — and its result holds 0 (expression mode) or the given track (gesture mode) in the other columns.  Noise
+    // addressing stays that of the full-width row, so an active column receives the value it receives in the joint run.
+    const int mod = den->modality, gcols = den->gesture_channels();
+    DSH_REQUIRE(mod == 0 || (gcols > 0 && gcols < channels), "a partial modality needs the UniDiffuser's two encoders");
+    DSH_REQUIRE(mod == 0 || !o.same_overlap_noisy, "same_overlap_noisy with a partial modality: the saved noisy tails describe all channels");
+    const int w_lo = mod == 1 ? gcols : 0, w_hi = mod == 0 ? 0 : (mod == 1 ? channels : gcols);      // (0, 0: all columns)
     // ragged batch (set_condition_ragged): per-clip frame counts of the padded batch, host and device copies owned by the context
     const int32_t* len_h = den->lengths_host();
     const int* len_d = den->lengths_dev();
@@ -403,13 +410,13 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
         // the two encoders' chains on two streams: every evaluation restores its head from the slots the prefetch run fills (mode 2), no
         // per-step trace of the whole sample, no saved noisy tails (both need all channels of a step at once)
         gch = den->gesture_channels();
-        if (prefetched && !trace && !son && nz1G && n <= capG_n && gch > 0 && gch < channels && den->pipe_begin(&twin, &sG) == 0) {
+        if (mod == 0 && prefetched && !trace && !son && nz1G && n <= capG_n && gch > 0 && gch < channels && den->pipe_begin(&twin, &sG) == 0) {
             pipe = true;
             for (hipEvent_t* e : {&ev_pE, &ev_pC, &ev_pG}) if (!*e) DSH_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
         }
     }
     // DDPM loops have no timestep cache (every level is visited once, 1000 of them): each chain computes its own head
-    if (!pipe && o.kind == 1 && !split && small_pf && !trace && nz1G && n <= capG_n) {
+    if (mod == 0 && !pipe && o.kind == 1 && !split && small_pf && !trace && nz1G && n <= capG_n) {
         gch = den->gesture_channels();
         if (gch > 0 && gch < channels && den->pipe_begin(&twin, &sG) == 0) {
             pipe = true;
@@ -450,7 +457,7 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
             for (const Sub& u : subs) {
                 const float* z;
                 if (int e = noise_for(idx, u, nz1, &z)) return e;
-                if (int e = launch_undo_step(x + u.off, z, sqrtf(1.0f - beta), sqrtf(beta), u.cnt, u.s)) return e;
+                if (int e = launch_undo_step(x + u.off, z, sqrtf(1.0f - beta), sqrtf(beta), u.cnt, u.s, channels, w_lo, w_hi)) return e;
             }
         } else {
             const float c1 = (float)tb.c1[k], c2 = (float)tb.c2[k];
@@ -547,7 +554,7 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
                     if (int e = eval_step_twin(twin, sG, x, n_eval - 1, use_graph, twin_mode)) return e;
                     if (int e = ddim_update(Sub{twin, sG, 0, B, 0, n}, nz1G, nz_etaG, 0, gch)) return e;
                 } else
-                for (const Sub& u : subs) { if (int e = ddim_update(u, nz1, nz_eta, 0, 0)) return e; }
+                for (const Sub& u : subs) { if (int e = ddim_update(u, nz1, nz_eta, w_lo, w_hi)) return e; }
             } else {
                 const int64_t idx = next_draw();
                 auto ddpm_update = [&](const Sub& u, float* sc, int c_lo, int c_hi) -> int {
@@ -570,7 +577,7 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
                     if (int e = eval_step_twin(twin, sG, x, n_eval - 1, use_graph, twin_mode)) return e;
                     if (int e = ddpm_update(Sub{twin, sG, 0, B, 0, n}, nz1G, 0, gch)) return e;
                 } else
-                for (const Sub& u : subs) { if (int e = ddpm_update(u, nz1, 0, 0)) return e; }
+                for (const Sub& u : subs) { if (int e = ddpm_update(u, nz1, w_lo, w_hi)) return e; }
             }
         }
         if (trace)
@@ -599,6 +606,14 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
     if (graph_exec[0] || graph_exec[1] || graph_exec[2]) { DSH_HIP_CHECK(hipStreamSynchronize(st)); drop_graph(); }
     // ragged batch: the loop ran on the padded rows; its result is defined as exactly 0 beyond every clip's length (one launch behind the join,
     // whatever regime the loop ran in; rows of `trace` keep the padded frames' values)
+    // one modality alone: the inactive columns of the result are defined — 0, or the given track bit for bit — whatever x held there (one launch
+    // behind the join, like the ragged zeroing that follows it)
+    if (rc == 0 && mod == 1) { if (int e = launch_fill_cols(x, channels, (size_t)B * den->frames, 0, gcols, nullptr, 0, st)) return e; }
+    if (rc == 0 && mod == 2) {
+        const float* track = den->modality_track();
+        DSH_REQUIRE(track != nullptr, "gesture modality without its expression track");
+        if (int e = launch_fill_cols(x, channels, (size_t)B * den->frames, gcols, channels, track, channels - gcols, st)) return e;
+    }
     if (rc == 0 && len_d) return launch_zero_padded_frames(x, len_d, B, den->frames, channels, st);
     return rc;
 }

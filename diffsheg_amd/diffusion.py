@@ -19,6 +19,8 @@ Differences a caller can observe, all loud:
     loops' ``cond_scale=`` keyword (a float, or one value per batch row), which wins over ``opt``; either holds for the call only;
   * ``model_kwargs['length']`` with an entry ``< T`` makes the batch ragged (``UniDiffuser.set_condition(lengths=)``): every row is
     sampled as the clip alone at its length (with ``row_keys``: from the same noise), padded frames of the result are exactly 0;
+  * ``model_kwargs['modality']`` (``"expression"`` / ``"gesture"``, the latter with ``model_kwargs['expression']`` = the given track) samples
+    one encoder's channels alone (``UniDiffuser.set_condition(modality=)``): the other columns of the result are 0 / the given track;
   * ``ddim_sample_loop(..., tail_blend=True)`` mirrors the ``addBlend`` cross-fade onto the last ``overlap_len`` frames, for a mask
     that pins both ends of a window (``DDPMTrainer.sample_inbetween``, seam repair); off by default.
 """
@@ -32,7 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .model import UniDiffuser, normalize_guidance_scale, normalize_lengths
+from .model import UniDiffuser, normalize_guidance_scale, normalize_lengths, normalize_modality
 
 _TABLES = ["betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_recip_alphas_cumprod",
            "sqrt_recipm1_alphas_cumprod", "posterior_variance", "posterior_log_variance_clipped",
@@ -183,7 +185,10 @@ class GaussianDiffusion:
             raise NotImplementedError("per-clip lengths cannot be combined with same_overlap_noisy or tail_blend")
         if lens is not None and row_keys is not None and noise_source is None and any((v * Cc) % 4 for v in lens):
             raise ValueError("row_keys on a ragged batch: length * channels must be a multiple of 4 for every clip")
-        model._maybe_set_condition(model_kwargs["audio_emb"], model_kwargs["person_id"], model_kwargs.get("add_cond"), lens)
+        # one modality alone (model_kwargs['modality'] / ['expression'], UniDiffuser.set_condition): refused like the rest, before conditioning
+        modality, expression = model_kwargs.get("modality", "both"), model_kwargs.get("expression")
+        normalize_modality(modality, expression, B, T, model.cfg.expression_dim, model.cfg.unidiffuser, son)
+        model._maybe_set_condition(model_kwargs["audio_emb"], model_kwargs["person_id"], model_kwargs.get("add_cond"), lens, modality, expression)
         if (B, T) != (model.batch, model.frames) or Cc != model.cfg.net_dim_pose:
             raise ValueError(f"shape {tuple(shape)} does not match the conditioning")
         gt = mask = None

@@ -78,6 +78,46 @@ def normalize_lengths(length, batch: int, frames: int) -> Optional[Tuple[int, ..
     return None if all(v == frames for v in vals) else tuple(vals)
 
 
+MODALITIES = {"both": 0, "expression": 1, "gesture": 2}      # the numbers of dsh_set_modality (include/diffsheg_hip.h)
+
+
+def normalize_modality(modality="both", expression=None, batch: Optional[int] = None, frames: Optional[int] = None,
+                       expression_dim: Optional[int] = None, unidiffuser: bool = True, same_overlap_noisy: bool = False) -> int:
+    """``modality`` / ``expression`` arguments -> 0 (both), 1 (expression) or 2 (gesture).  ``modality`` is one of the names of
+    :data:`MODALITIES`, its number, or ``None`` (both).  Raises ``ValueError`` on an unknown value; on a partial modality for the
+    single-``MotionTransformer`` model (``unidiffuser=False``) or together with ``same_overlap_noisy`` (the saved noisy tails describe
+    all channels); on ``"gesture"`` without an ``expression`` track or with one that is not a floating-point ``[batch, frames,
+    expression_dim]`` tensor (each dimension checked where given); and on a track given with any other modality."""
+    if modality is None:
+        m = 0
+    elif isinstance(modality, str):
+        if modality not in MODALITIES:
+            raise ValueError(f"modality must be one of {sorted(MODALITIES)}, got {modality!r}")
+        m = MODALITIES[modality]
+    elif isinstance(modality, numbers.Integral) and not isinstance(modality, bool):
+        m = int(modality)
+        if m not in MODALITIES.values():
+            raise ValueError(f"modality must be 0 (both), 1 (expression) or 2 (gesture), got {m}")
+    else:
+        raise ValueError(f"modality must be one of {sorted(MODALITIES)}, got {modality!r}")
+    if m != 0 and not unidiffuser:
+        raise ValueError("a partial modality needs the UniDiffuser: a single MotionTransformer has no separate expression / gesture encoders")
+    if m != 0 and same_overlap_noisy:
+        raise ValueError("same_overlap_noisy with a partial modality: the saved noisy tails describe all channels")
+    if m != 2:
+        if expression is not None:
+            raise ValueError('an expression track is only read with modality="gesture"')
+        return m
+    if expression is None:
+        raise ValueError('modality="gesture" needs the expression track: expression=[B, T, expression_dim]')
+    if not isinstance(expression, torch.Tensor) or not torch.is_floating_point(expression) or expression.dim() != 3:
+        raise ValueError("expression must be a floating-point tensor [B, T, expression_dim]")
+    want = (batch, frames, expression_dim)
+    if any(w is not None and int(w) != int(g) for w, g in zip(want, expression.shape)):
+        raise ValueError(f"expression must be [B, T, expression_dim] = {want}, got {tuple(expression.shape)}")
+    return m
+
+
 class UniDiffuser:
     """MI355X UniDiffuser: ``encoder_aud`` + ``encoder_exp`` + ``encoder_ges`` behind one C handle."""
     _UNIDIFFUSER = True
@@ -107,6 +147,7 @@ class UniDiffuser:
         self._cond_key = None
         self._cond_keep = None
         self.lengths = None                    # per-clip frame counts of a ragged condition (set_condition(lengths=))
+        self.modality = 0                      # 0 both / 1 expression / 2 gesture: part of the condition (set_condition(modality=))
         self._guidance = None                  # set_guidance_scale(): None = the config's cond_scale
         self._dummy = torch.zeros(1, device=self.device)
         self.load_state_dict(state_dict)
@@ -166,13 +207,22 @@ class UniDiffuser:
             cur.wait_stream(self._stream)
 
     # ---- conditioning ------------------------------------------------------------------------
-    def set_condition(self, audio_emb: torch.Tensor, person_id: torch.Tensor, hubert: torch.Tensor, lengths=None) -> None:
+    def set_condition(self, audio_emb: torch.Tensor, person_id: torch.Tensor, hubert: torch.Tensor, lengths=None, modality="both",
+                      expression: Optional[torch.Tensor] = None) -> None:
         """Upload the step-invariant conditioning and run hubert_encoder / pid_embed once.  ``lengths`` (one frame count per clip,
         ``1 .. T``): the batch is ragged — clip ``b`` is the first ``lengths[b]`` frames of its padded row, and those frames of every
         following evaluation / sampling loop are what the clip gives alone at that length, whatever the padded frames of any input
-        hold (``dsh_set_condition_ragged``).  ``None`` or all equal to ``T``: every clip is full, the path it always was."""
+        hold (``dsh_set_condition_ragged``).  ``None`` or all equal to ``T``: every clip is full, the path it always was.
+
+        ``modality`` (``"both"`` / ``"expression"`` / ``"gesture"``, part of the condition): one encoder alone (``dsh_set_modality``).
+        ``"expression"`` launches no gesture-encoder kernel: the expression columns of every result are the joint run's, the gesture
+        columns 0.  ``"gesture"`` needs ``expression`` ``[B, T, expression_dim]`` (standardised, the clean track), which the gesture
+        encoder reads at every step in place of the expression encoder's estimate; the expression encoder is not launched, the
+        expression columns of an evaluation are 0 and those of a sampled result are the track itself.  Tensors keep their full
+        width; the inactive columns of ``x``, ``gt``, the mask and the noise are never read."""
         B, T = int(audio_emb.shape[0]), int(audio_emb.shape[1])
         lens = normalize_lengths(lengths, B, T)
+        mod = normalize_modality(modality, expression, B, T, self.cfg.expression_dim, self.cfg.unidiffuser)
         if person_id.dim() == 1:                                   # transformer.py:502-503
             person_id = person_id.unsqueeze(0)
         if person_id.shape[0] != B:
@@ -186,6 +236,7 @@ class UniDiffuser:
         if person_id.shape[1] != self.cfg.style_dim:
             raise ValueError(f"person_id must be [B,{self.cfg.style_dim}]")
         a, p, hb = (_dev_f32(t, self.device) for t in (audio_emb, person_id, hubert))
+        ex = _dev_f32(expression, self.device) if mod == 2 else None
         cur = self._enter()
         try:
             if lens is None:
@@ -194,27 +245,35 @@ class UniDiffuser:
             else:
                 _lib.check(self._lib.dsh_set_condition_ragged(self._h, B, T, (C.c_int32 * B)(*lens), a.data_ptr(), p.data_ptr(),
                                                               hb.data_ptr()), "dsh_set_condition_ragged")
+            self.modality = 0                  # (a new condition is a joint one)
+            if mod != 0:
+                _lib.check(self._lib.dsh_set_modality(self._h, mod, _ptr(ex)), "dsh_set_modality")
+                self.modality = mod
         finally:
             self._exit(cur)                    # (also when the call is refused: the caller's stream stays ordered after the context's)
-        self._cond_keep = (a, p, hb)           # (the library copies them in stream order; kept for the allocator's sake)
+        self._cond_keep = (a, p, hb, ex)       # (the library copies them in stream order; kept for the allocator's sake)
         self.batch, self.frames = B, T
         self.lengths = lens                    # None: every clip is full
 
-    def _maybe_set_condition(self, audio_emb, person_id, add_cond, length=None) -> None:
+    def _maybe_set_condition(self, audio_emb, person_id, add_cond, length=None, modality="both", expression=None) -> None:
         if "pretrain_aud_feat" not in (add_cond or {}):
             raise ValueError("add_cond['pretrain_aud_feat'] (HuBERT features) is required (addHubert=True)")
         hub = add_cond["pretrain_aud_feat"]
         # Identity + in-place-version check on the caller's tensor objects.  The objects themselves are
         # kept alive in the key: a freed tensor's address can be handed to a new tensor of the same shape,
         # so data_ptr alone would alias stale conditioning.
-        src = (audio_emb, person_id, hub)
+        B, T = int(audio_emb.shape[0]), int(audio_emb.shape[1])
+        mod = normalize_modality(modality, expression, B, T, self.cfg.expression_dim, self.cfg.unidiffuser)
+        # (the modality and the given track are part of the condition: the track by identity and version like the others)
+        src = (audio_emb, person_id, hub) + ((expression,) if mod == 2 else ())
         vers = tuple(t._version for t in src)
         # (the lengths are part of the condition; compared by value: callers build a fresh `length` tensor per call)
         lens = normalize_lengths(length, int(audio_emb.shape[0]), int(audio_emb.shape[1]))
-        if (self._cond_key is None or any(a is not b for a, b in zip(self._cond_key[0], src))
-                or self._cond_key[1] != vers or self._cond_key[2] != lens):
-            self.set_condition(audio_emb, person_id, hub, lens)
-            self._cond_key = (src, vers, lens)
+        if (self._cond_key is None or len(self._cond_key[0]) != len(src) or any(a is not b for a, b in zip(self._cond_key[0], src))
+                or self._cond_key[1] != vers or self._cond_key[2] != lens or self._cond_key[3] != mod):
+            self._cond_key = None              # (a refused call below leaves the native condition as it was, whatever it is now)
+            self.set_condition(audio_emb, person_id, hub, lens, mod, expression if mod == 2 else None)
+            self._cond_key = (src, vers, lens, mod)
 
     # ---- classifier-free guidance ---------------------------------------------------------------
     def set_guidance_scale(self, scale=None) -> None:
@@ -241,16 +300,16 @@ class UniDiffuser:
 
     # ---- boundary 1 -----------------------------------------------------------------------------
     def __call__(self, x, timesteps, sqrt_alphas=None, audio_emb=None, length=None, person_id=None, add_cond=None,
-                 pe_type="pe_sinu", y=None) -> torch.Tensor:
-        return self.forward(x, timesteps, sqrt_alphas, audio_emb, length, person_id, add_cond, pe_type, y)
+                 pe_type="pe_sinu", y=None, modality="both", expression=None) -> torch.Tensor:
+        return self.forward(x, timesteps, sqrt_alphas, audio_emb, length, person_id, add_cond, pe_type, y, modality, expression)
 
     def forward(self, x, timesteps, sqrt_alphas, audio_emb, length, person_id, add_cond=None, pe_type="pe_sinu",
-                y=None) -> torch.Tensor:
+                y=None, modality="both", expression=None) -> torch.Tensor:
         if pe_type not in ("pe_sinu",):
             raise NotImplementedError(f"pe_type={pe_type!r}: only the default 'pe_sinu' path is built")
         if sqrt_alphas is None or len(sqrt_alphas) != 2:
             raise ValueError("sqrt_alphas=[sqrt_recip_alphas_cumprod_t, sqrt_recipm1_alphas_cumprod_t] is required")
-        self._maybe_set_condition(audio_emb, person_id, add_cond, length)
+        self._maybe_set_condition(audio_emb, person_id, add_cond, length, modality, expression)
         B, T, Cc = x.shape
         if (B, T) != (self.batch, self.frames) or Cc != self.cfg.net_dim_pose:
             raise ValueError(f"x shape {tuple(x.shape)} does not match conditioning ({self.batch},{self.frames},{self.cfg.net_dim_pose})")

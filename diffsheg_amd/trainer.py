@@ -23,7 +23,7 @@ import torch
 from .config import DiffSHEGConfig
 from .diffusion import (GaussianDiffusion, ModelMeanType, ModelVarType, SpacedDiffusion, get_named_beta_schedule,
                         space_timesteps)
-from .model import UniDiffuser, normalize_guidance_scale
+from .model import UniDiffuser, normalize_guidance_scale, normalize_modality
 
 
 def sampler_namespace(cfg: DiffSHEGConfig, **over) -> argparse.Namespace:
@@ -165,14 +165,17 @@ class DDPMTrainer:
         return euler_to_axis_angle(pose.to(self.device), self.pose_stats, split_pos=self._gesture_split(), lengths=lengths)
 
     def generate_batch(self, audio_emb, p_id, dim_pose, add_cond={}, inpaint_dict=None, cond_scale=None, lengths=None,
-                       pose_rep: str = "axis_angle", **sampler_kw):
+                       pose_rep: str = "axis_angle", modality="both", expression=None, **sampler_kw):
         """ddpm_show_trainer.py:163-198.  ``sampler_kw`` (noise_source= / seed=) is this build's
         noise-injection hook; the reference draws from the global torch RNG.  ``cond_scale`` (a float, or one value per batch
         row) overrides ``opt.cond_scale`` for this batch.  ``lengths`` (one frame count per row, ``1 .. T``): clips of different
         lengths padded to ``T`` frames — row ``b`` is sampled as its first ``lengths[b]`` frames alone, the padded frames of the
         result are 0 (the reference always passes ``cur_len = T``, which is the default).  ``pose_rep="euler"`` (BEAT): the gesture
         channels of the returned sample are the reference's standardised Euler degrees, the expression channels are untouched and
-        padded frames stay 0; the default returns the sampler's result as it is, with no extra launch."""
+        padded frames stay 0; the default returns the sampler's result as it is, with no extra launch.  ``modality`` /
+        ``expression`` (:meth:`UniDiffuser.set_condition`): ``"expression"`` samples the face alone (gesture columns of the result 0),
+        ``"gesture"`` samples gestures for the given expression track ``[B, T, expression_dim]`` (expression columns = the track);
+        ``inpaint_dict`` is honoured on the active columns only."""
         euler = self._euler_requested(pose_rep)
         if cond_scale is not None:
             sampler_kw["cond_scale"] = cond_scale
@@ -184,6 +187,10 @@ class DDPMTrainer:
             cur_len = torch.tensor([int(v) for v in lengths], dtype=torch.long)
         model_kwargs = {"audio_emb": audio_emb, "length": cur_len, "person_id": p_id, "add_cond": add_cond,
                         "y": inpaint_dict, "pe_type": getattr(self.opt, "PE", "pe_sinu")}
+        if (expression is not None or modality not in (None, "both", 0)) and normalize_modality(
+                modality, expression, B, T, self.encoder.cfg.expression_dim, self.encoder.cfg.unidiffuser,
+                bool(getattr(self.opt, "same_overlap_noisy", False))) != 0:
+            model_kwargs["modality"], model_kwargs["expression"] = modality, expression
         if getattr(self.opt, "ddim", True):
             out = self.diffusion_ddim_val.ddim_sample_loop(self.encoder, (B, T, dim_pose), clip_denoised=False,
                                                            progress=True, model_kwargs=model_kwargs, **sampler_kw)
@@ -223,6 +230,8 @@ class DDPMTrainer:
         :meth:`validation_summary`.  Returns the samples ``[B, T, C]`` — bit-identical to ``generate_batch`` alone with the same
         arguments.  ``sampler_kw`` as for :meth:`generate_batch` (``seed=``, ``noise_source=``, ``cond_scale=``, ...)."""
         from .metrics import batch_metrics
+        if normalize_modality(sampler_kw.get("modality", "both"), None) != 0:
+            raise ValueError("validate_batch scores both modalities: MSE / PCK / diversity and the FGD encoder are defined on all channels")
         if lengths is not None:
             raise ValueError("validate_batch takes full clips only: the FGD encoder is defined for n_poses frames, and MSE / PCK / "
                              "diversity of padded frames would be meaningless (score ragged batches clip by clip)")
@@ -288,7 +297,8 @@ class DDPMTrainer:
     def sample_arbitrary_len(self, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor],
                              noise_source_for_window=None, seed: Optional[int] = None,
                              motions: Optional[torch.Tensor] = None, row_keys: Optional[Sequence[int]] = None,
-                             cond_scale=None, lengths: Optional[Sequence[int]] = None, pose_rep: str = "axis_angle"):
+                             cond_scale=None, lengths: Optional[Sequence[int]] = None, pose_rep: str = "axis_angle",
+                             modality="both", expression=None):
         """The per-video body of test_arbitrary_len (ddpm_show_trainer.py:864-906): windows of n_poses
         with stride n_poses-overlap_len; window k>0 out-paints from the last overlap_len frames of
         window k-1 (sequential chain).  Output stays on the device (the reference copies every window
@@ -304,16 +314,23 @@ class DDPMTrainer:
         (not a padded tensor); ``opt.same_overlap_noisy`` is refused.
 
         ``pose_rep="euler"`` (BEAT, after :meth:`set_pose_stats`): the chain is sampled as always and the gesture channels of the
-        finished result (of every result of the list form) are converted to the reference's standardised Euler degrees."""
+        finished result (of every result of the list form) are converted to the reference's standardised Euler degrees.
+
+        ``modality`` / ``expression``: one modality alone for every window of the chains (:meth:`generate_batch`).  The track of
+        ``"gesture"`` is ``[B, N, E]``, ``[N, E]`` (one track for every chain) or, with ``lengths``, a list of ``[lengths[b], E]``
+        tensors; it is cut into windows exactly like the audio.  The overlap hand-off, ``fix_very_first`` and the out-painting mask
+        act on the active columns only; ``opt.same_overlap_noisy`` is refused."""
         euler = self._euler_requested(pose_rep)
+        expression = self._chain_track(modality, expression, int(audio_emb.shape[0]), int(audio_emb.shape[1]), lengths)
         if lengths is not None:
             outs = self._sample_arbitrary_len_ragged(audio_emb, p_id, add_cond, [int(v) for v in lengths], noise_source_for_window, seed,
-                                                     motions, row_keys, cond_scale)
+                                                     motions, row_keys, cond_scale, modality, expression)
             return [self._to_euler(o) for o in outs] if euler else outs
         opt = self.opt
         n_poses, L, C = int(opt.n_poses), int(opt.overlap_len), int(opt.net_dim_pose)
         step = n_poses - L
         audio_list = get_windows(audio_emb, n_poses, step)
+        expr_list = get_windows(expression, n_poses, step) if expression is not None else [None] * len(audio_list)
         cond_list = get_windows(add_cond, n_poses, step) if add_cond not in (None, {}) else [{}] * len(audio_list)
         fix_first = bool(getattr(opt, "fix_very_first", False)) and L > 0
         if fix_first and motions is None:
@@ -323,7 +340,7 @@ class DDPMTrainer:
         outputs = None
         son = bool(getattr(opt, "same_overlap_noisy", False))     # ddpm_beat_trainer.py:1006,1022-1028
         previous_noisy_tail = None
-        for ii, (a, cnd) in enumerate(zip(audio_list, cond_list)):
+        for ii, (a, cnd, ex) in enumerate(zip(audio_list, cond_list, expr_list)):
             inpaint_dict = {"clip_idx": ii} if son else {}
             if L > 0:
                 B, T = a.shape[0], a.shape[1]
@@ -347,6 +364,8 @@ class DDPMTrainer:
                 kw["row_keys"] = row_keys          # Philox: one stream per (window, chain): key = hash(seed, window), counter high words = chain id
             if cond_scale is not None:
                 kw["cond_scale"] = cond_scale
+            if ex is not None or modality not in (None, "both", 0):
+                kw["modality"], kw["expression"] = modality, ex
             outputs = self.generate_batch(a, p_id, C, cnd, inpaint_dict, **kw)
             if son:
                 previous_noisy_tail, outputs = outputs["saved_noisy_tail"], outputs["sample"]
@@ -355,8 +374,27 @@ class DDPMTrainer:
         return self._to_euler(full) if euler else full
 
 
+    def _chain_track(self, modality, expression, B: int, N: int, lengths) -> Optional[torch.Tensor]:
+        """The ``expression`` argument of the chain entry points -> ``None`` (no gesture-only run) or the padded track ``[B, N, E]``."""
+        if expression is None and modality in (None, "both", 0):
+            return None                                  # the joint run: nothing to validate, nothing changes
+        E = self.encoder.cfg.expression_dim
+        if isinstance(expression, (list, tuple)):
+            if len(expression) != B or lengths is None or any(tuple(t.shape) != (int(n), E) for t, n in zip(expression, lengths)):
+                raise ValueError(f"expression as a list needs lengths= and one [lengths[b], {E}] tensor per chain")
+            pad = expression[0].new_zeros(B, N, E)
+            for b, t in enumerate(expression):
+                pad[b, :t.shape[0]] = t
+            expression = pad
+        elif isinstance(expression, torch.Tensor) and expression.dim() == 2:
+            expression = expression.unsqueeze(0).expand(B, -1, -1)
+        if normalize_modality(modality, expression, B, N, E, self.encoder.cfg.unidiffuser,
+                              bool(getattr(self.opt, "same_overlap_noisy", False))) != 2:
+            return None
+        return expression
+
     def _sample_arbitrary_len_ragged(self, audio_emb, p_id, add_cond, lengths: List[int], noise_source_for_window, seed, motions,
-                                     row_keys, cond_scale) -> List[torch.Tensor]:
+                                     row_keys, cond_scale, modality="both", expression=None) -> List[torch.Tensor]:
         opt = self.opt
         n_poses, L, C = int(opt.n_poses), int(opt.overlap_len), int(opt.net_dim_pose)
         step = n_poses - L
@@ -416,6 +454,9 @@ class DDPMTrainer:
                 kw["cond_scale"] = gs[0] if len(gs) == 1 else [gs[b] for b in rows]
             if any(n != T for n in lens):
                 kw["lengths"] = lens
+            if expression is not None or modality not in (None, "both", 0):
+                kw["modality"] = modality
+                kw["expression"] = cut(expression, rows, wb["start"], T).contiguous() if expression is not None else None
             out = self.generate_batch(a, pid[rows], C, cnd, inpaint_dict, **kw)
             for r, b in enumerate(rows):
                 n = lens[r]
@@ -427,7 +468,8 @@ class DDPMTrainer:
     # ---- motion in-betweening: one window pinned at both ends ---------------------------------
     def sample_inbetween(self, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor],
                          head: torch.Tensor, tail: torch.Tensor, *, tail_blend: bool = True, seed: Optional[int] = None,
-                         row_keys: Optional[Sequence[int]] = None, noise_source=None, cond_scale=None) -> torch.Tensor:
+                         row_keys: Optional[Sequence[int]] = None, noise_source=None, cond_scale=None, modality="both",
+                         expression=None) -> torch.Tensor:
         """"Here are two clips and the audio between them, fill the gap": ``audio_emb [B, T, 128]`` (+ ``add_cond``) conditions one
         window, whose first ``L = opt.overlap_len`` frames are pinned to ``head`` and whose last ``L`` to ``tail`` (both ``[B, L, C]``,
         standardised motion; ``2 L < T``); the frames in between are sampled.  This is the reference's own out-painting loop
@@ -435,7 +477,8 @@ class DDPMTrainer:
         ``jump_n_sample``, ``no_resample``, ``no_repaint`` act as in a chained window) on a mask that is True at both ends.
         With ``tail_blend=False`` it is exactly that loop: generated motion is cross-faded into the pinned frames on the head side
         only (``addBlend``).  ``tail_blend=True`` (default) adds the mirrored fade on the last ``L`` frames.  Needs ``opt.ddim``
-        (mask-present DDPM is not built).  Returns the window ``[B, T, C]`` on the device; no host sync."""
+        (mask-present DDPM is not built).  Returns the window ``[B, T, C]`` on the device; no host sync.  ``modality`` /
+        ``expression`` ``[B, T, E]`` as for :meth:`generate_batch`: the pinned frames act on the active columns only."""
         opt = self.opt
         L, C = int(opt.overlap_len), int(opt.net_dim_pose)
         if not getattr(opt, "ddim", True):
@@ -455,6 +498,8 @@ class DDPMTrainer:
         for k, v in (("seed", seed), ("row_keys", row_keys), ("noise_source", noise_source), ("cond_scale", cond_scale)):
             if v is not None:
                 kw[k] = v
+        if expression is not None or modality not in (None, "both", 0):
+            kw["modality"], kw["expression"] = modality, expression
         out = self.generate_batch(audio_emb, p_id, C, add_cond, {"gt": gt, "outpainting_mask": mask, "outpainting_mask_any": True}, **kw)
         return out["sample"] if isinstance(out, dict) else out
 
@@ -521,7 +566,7 @@ def split_segments_for_repair(n_frames: int, n_segments: int, n_poses: int, over
 
 def _repair_seams(trainer: "DDPMTrainer", stream: torch.Tensor, offset: int, seams: Sequence[int], segs: Sequence[range],
                   audio_emb: torch.Tensor, add_cond: Dict[str, torch.Tensor], pid: torch.Tensor, seed: int, max_rows: int,
-                  cond_scale, tail_blend: bool) -> None:
+                  cond_scale, tail_blend: bool, modality="both", expression: Optional[torch.Tensor] = None) -> None:
     """Re-sample the windows of the seams ``seams`` (global indices) in place in ``stream [n, C]``, which holds frames
     ``[offset, offset + n)`` of the whole stream: one batched in-betweening window per ``max_rows`` seams (row = seam), conditioning
     and pinned frames gathered with one index tensor, result scattered back with the same one.  Key = (seed, SEAM_WINDOW), counter
@@ -540,8 +585,10 @@ def _repair_seams(trainer: "DDPMTrainer", stream: torch.Tensor, offset: int, sea
         cnd = {k: v[0][idx.to(v.device)] for k, v in add_cond.items()}
         loc = idx - offset
         win = stream[loc]                                                   # [rows, n_poses, C]
+        ex = expression[0][idx.to(expression.device)].contiguous() if expression is not None else None
         out = trainer.sample_inbetween(a, pid[:1].expand(len(chunk), -1), cnd, win[:, :L], win[:, n_poses - L:], tail_blend=tail_blend,
-                                       seed=key, row_keys=chunk, cond_scale=cond_scale)
+                                       seed=key, row_keys=chunk, cond_scale=cond_scale,
+                                       **({} if modality in (None, "both", 0) else {"modality": modality, "expression": ex}))
         stream.index_copy_(0, loc.reshape(-1), out.reshape(-1, out.shape[-1]).to(stream.dtype))
 
 
@@ -577,7 +624,8 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
                                  inputs_on_rank0_only: bool = False, max_chains_per_batch: int = 64,
                                  cond_scale: Optional[float] = None, seam_repair: bool = False,
                                  seam_tail_blend: bool = True, ragged: bool = False,
-                                 pose_rep: str = "axis_angle") -> Optional[torch.Tensor]:
+                                 pose_rep: str = "axis_angle", modality="both",
+                                 expression: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """BASELINE config 4: one long feature stream ``[1, N, ...]`` sampled on all ranks of ``group``.
 
     Windows of ONE chain are sequential (window k needs the final sample of window k-1 at every denoising step,
@@ -612,6 +660,9 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
 
     ``pose_rep="euler"`` (BEAT, after ``trainer.set_pose_stats``): chains, gather and seam repair run in the sampler's axis-angle
     representation as always; rank 0 converts the gesture channels of the finished stream to the reference's standardised Euler degrees.
+
+    ``modality`` / ``expression``: one modality alone for the chains and the seam repair (:meth:`DDPMTrainer.sample_arbitrary_len`).  The
+    track of ``"gesture"`` is ``[1, N, E]`` (or ``[N, E]``); with ``inputs_on_rank0_only`` it is broadcast with the audio.
     """
     euler = trainer._euler_requested(pose_rep)
     if cond_scale is not None and not isinstance(cond_scale, numbers.Real):
@@ -628,9 +679,15 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
         dist.broadcast_object_list(keys, 0, group=group)
         audio_emb = broadcast_stream(audio_emb, dev, 0, group)
         add_cond = {k: broadcast_stream(add_cond[k] if rank == 0 else None, dev, 0, group) for k in keys[0]}
+        has_track = [expression is not None if rank == 0 else None]
+        dist.broadcast_object_list(has_track, 0, group=group)
+        if has_track[0]:
+            expression = broadcast_stream((expression if expression.dim() == 3 else expression.unsqueeze(0)) if rank == 0 else None, dev, 0, group)
     if audio_emb.shape[0] != 1:
         raise ValueError("sample_arbitrary_len_sharded takes ONE stream [1, N, ...]; batch several streams by calling it per stream")
     N = int(audio_emb.shape[1])
+    expression = trainer._chain_track(modality, expression, 1, N, None)          # None, or [1, N, E]
+    mkw = {} if modality in (None, "both", 0) else {"modality": modality}
     if seam_repair:
         if not getattr(opt, "ddim", True) or L <= 0 or 2 * L >= n_poses:
             raise ValueError("seam_repair needs opt.ddim and 0 < 2 * overlap_len < n_poses")
@@ -655,7 +712,8 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
                     out[j, :lens[j]] = v[0, segs[i].start:segs[i].stop]
                 return out
             outs = trainer.sample_arbitrary_len(stack(audio_emb), pid[:1].expand(len(chunk), -1), {k: stack(v) for k, v in add_cond.items()},
-                                                seed=seed, row_keys=chunk, cond_scale=cond_scale, lengths=lens)
+                                                seed=seed, row_keys=chunk, cond_scale=cond_scale, lengths=lens,
+                                                **(dict(mkw, expression=stack(expression)) if expression is not None else mkw))
             for j, i in enumerate(chunk):
                 local[i] = outs[j]
     for ids in ([] if ragged else by_len.values()):
@@ -663,14 +721,16 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
             chunk = ids[c0:c0 + max_chains_per_batch]
             a = torch.cat([audio_emb[:, segs[i].start:segs[i].stop] for i in chunk], 0)
             cnd = {k: torch.cat([v[:, segs[i].start:segs[i].stop] for i in chunk], 0) for k, v in add_cond.items()}
-            out = trainer.sample_arbitrary_len(a, pid[:1].expand(len(chunk), -1), cnd, seed=seed, row_keys=chunk, cond_scale=cond_scale)
+            ex = torch.cat([expression[:, segs[i].start:segs[i].stop] for i in chunk], 0) if expression is not None else None
+            out = trainer.sample_arbitrary_len(a, pid[:1].expand(len(chunk), -1), cnd, seed=seed, row_keys=chunk, cond_scale=cond_scale,
+                                               **(dict(mkw, expression=ex) if ex is not None else mkw))
             for j, i in enumerate(chunk):
                 local[i] = out[j]
     loc = torch.cat([local[i] for i in mine], 0) if len(mine) else torch.zeros(0, C, device=dev)
     if seam_repair and len(mine) > 1:
         # seams inside this rank's run of segments (seam s lies between segments s and s + 1)
         _repair_seams(trainer, loc, segs[mine[0]].start, list(mine)[:-1], segs, audio_emb, add_cond, pid, seed, max_chains_per_batch,
-                      cond_scale, seam_tail_blend)
+                      cond_scale, seam_tail_blend, modality, expression)
     sizes = [sum(len(segs[i]) for i in shard_range(len(segs), r, world)) for r in range(world)]
     parts = gather_outputs(loc, sizes, group)
     if parts is None:
@@ -680,7 +740,8 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
         # seams between two ranks' runs: one more batch, on rank 0
         last = [shard_range(len(segs), r, world) for r in range(world)]
         between = [r[-1] for r in last if len(r) and r[-1] < len(segs) - 1]
-        _repair_seams(trainer, full, 0, between, segs, audio_emb, add_cond, pid, seed, max_chains_per_batch, cond_scale, seam_tail_blend)
+        _repair_seams(trainer, full, 0, between, segs, audio_emb, add_cond, pid, seed, max_chains_per_batch, cond_scale, seam_tail_blend,
+                      modality, expression)
     full = full.unsqueeze(0)
     return trainer._to_euler(full) if euler else full
 

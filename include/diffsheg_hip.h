@@ -129,6 +129,27 @@ int dsh_set_condition(dsh_ctx* ctx, int32_t batch, int32_t frames, const float* 
  * together with same_overlap_noisy or dsh_sample_set_tail_blend (both address the last overlap_len frames of the padded window). */
 int dsh_set_condition_ragged(dsh_ctx* ctx, int32_t batch, int32_t frames_pad, const int32_t* lengths_host, const float* audio_emb,
                              const float* person_id, const float* hubert);
+/* One modality alone.  modality: 0 both (the joint evaluation, the default), 1 expression, 2 gesture.  Definition:
+ *   1  encoder_aud and encoder_exp run; no gesture-encoder launch is issued.  dsh_eval writes the expression columns [dim_pose, C) of eps
+ *      exactly as the joint evaluation does and 0 to the gesture columns; dsh_sample returns the joint run's expression columns and
+ *      exactly 0 in the gesture columns.
+ *   2  encoder_aud and encoder_ges run, and the gesture encoder reads `expression` [B,T,expression_dim] (device fp32, standardised, the
+ *      clean track) wherever the joint evaluation reads the expression encoder's x0 estimate, at every step; the expression encoder is
+ *      not launched.  dsh_eval writes the gesture columns of eps and 0 to the expression columns; dsh_sample returns the sampled gesture
+ *      columns and the given track, bit for bit, in the expression columns.  Given the joint evaluation's own estimate (dsh_debug_copy
+ *      "expr_x0") the gesture columns are the joint evaluation's, bit for bit.
+ * Tensors keep their full width [B,T,C] in every mode; the inactive columns of x, gt, mask and the noise are never read, and the result
+ * never depends on what x held there.  Noise addressing (draw order, Philox counters, row keys, noise-stack offsets) and every decision
+ * taken by token rows (sub-batch streams, kernel families, graph and timestep-cache range) stay those of the joint run of the same
+ * (B, T); only the two-stream encoder pipeline is not entered: there is one chain.  dsh_eval_flops and the profiler count what was launched.
+ * Lifetime: part of the condition.  Call it after dsh_set_condition / dsh_set_condition_ragged, which reset the modality to 0 — every call
+ * sequence without it is unchanged.  `expression` is copied into context-owned memory in stream order (like the conditioning tensors)
+ * and packed once per condition; with lengths set, frames beyond a clip's length are read as zero.  `expression` is ignored unless
+ * modality is 2.
+ * -1 before any state changes (the previous condition and modality stay usable) on an unknown value, on a single_transformer context
+ * (modality != 0), before any dsh_set_condition, and on modality 2 with a null track.  dsh_sample returns -1 on same_overlap_noisy
+ * with a partial modality (the saved noisy tails describe all channels); `trace` is allowed, inactive columns of its rows are unspecified. */
+int dsh_set_modality(dsh_ctx* ctx, int32_t modality, const float* expression);
 /* eps[B,T,C] = UniDiffuser(x[B,T,C], t[B]; sqrt_alphas = (c1[B], c2[B])).  t holds ORIGINAL-scale
  * timesteps (what _WrappedModel passes); c1/c2 are sqrt(1/abar_t), sqrt(1/abar_t - 1) per sample
  * (gaussian_diffusion.py:527-532).  All device pointers; asynchronous on the context stream. */
