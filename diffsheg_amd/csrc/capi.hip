@@ -684,6 +684,120 @@ int dsh_op_tl2_ffn(void* hip_stream, const void* X, const float* Hres, const voi
     API_END
 }
 
+// ---- fused front of the bf16 path (tl_aud.hip, tl_embed.hip): test helpers over ROW-MAJOR operands in natural order.  Like dsh_op_tl_linear they
+// build the kernels' operands with the PRODUCTION packers in per-call scratch, cache nothing and free the scratch after a stream sync.  What
+// the launchers themselves refuse (null rows / outputs, ld_b, nf, row1) is passed through to them unchecked.
+namespace {
+struct OpScratch {
+    std::vector<void*> p;
+    ~OpScratch() { for (void* q : p) (void)hipFree(q); }
+    int alloc(void** out, size_t bytes) { DSH_HIP_CHECK(hipMalloc(out, bytes)); p.push_back(*out); return 0; }
+    int upload(void** out, const void* host, size_t bytes) {
+        if (int e = alloc(out, bytes)) return e;
+        DSH_HIP_CHECK(hipMemcpy(*out, host, bytes, hipMemcpyHostToDevice));
+        return 0;
+    }
+};
+int fetch_f32(std::vector<float>& dst, const float* dev, size_t n) {
+    dst.resize(n);
+    DSH_HIP_CHECK(hipMemcpy(dst.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+}  // namespace
+
+int dsh_op_tl_aud_tail(void* hip_stream, const void* Y, const float* X2, const float* ws1, const float* bs1, const float* w1, const float* b1,
+                       const float* w2, const float* b2, const float* ws2, const float* bs2, const float* g1, const float* be1, const float* g2,
+                       const float* be2, const float* film, int32_t frames, int32_t nb, int32_t Mc, float* out_f, void* out_b, int32_t ld_b) {
+    API_BEGIN
+    DSH_REQUIRE(ws1 && bs1 && w1 && b1 && w2 && b2 && ws2 && bs2 && g1 && be1 && g2 && be2 && film && nb > 0, "dsh_op_tl_aud_tail: null weight / FiLM operand");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    constexpr int DA = 128, F = 1024;
+    OpScratch scratch;
+    DSH_HIP_CHECK(hipStreamSynchronize(s));
+    std::vector<float> hs1, h1, h2, hs2, bb, part, gg, be;
+    if (int e = fetch_f32(hs1, ws1, (size_t)DA * DA)) return e;
+    if (int e = fetch_f32(h1, w1, (size_t)F * DA)) return e;
+    if (int e = fetch_f32(h2, w2, (size_t)DA * F)) return e;
+    if (int e = fetch_f32(hs2, ws2, (size_t)DA * DA)) return e;
+    std::vector<uint16_t> st((size_t)18 * 16384);
+    dsh::tl_aud_pack_stream(hs1.data(), h1.data(), h2.data(), hs2.data(), st.data());
+    // stacked biases [proj_out(sa) | linear1 | linear2 | proj_out(ffn)] and LayerNorm affines [block 1 | block 2], as Denoiser::finalize holds them
+    const float* bsrc[4] = {bs1, b1, b2, bs2}; const int bn[4] = {DA, F, DA, DA};
+    for (int i = 0; i < 4; ++i) { if (int e = fetch_f32(part, bsrc[i], bn[i])) return e; bb.insert(bb.end(), part.begin(), part.end()); }
+    const float* gsrc[2] = {g1, g2}; const float* esrc[2] = {be1, be2};
+    for (int i = 0; i < 2; ++i) {
+        if (int e = fetch_f32(part, gsrc[i], DA)) return e; gg.insert(gg.end(), part.begin(), part.end());
+        if (int e = fetch_f32(part, esrc[i], DA)) return e; be.insert(be.end(), part.begin(), part.end());
+    }
+    void *wst = nullptr, *dbias = nullptr, *dg = nullptr, *db = nullptr, *fsc = nullptr;
+    if (int e = scratch.upload(&wst, st.data(), st.size() * 2)) return e;
+    if (int e = scratch.upload(&dbias, bb.data(), bb.size() * 4)) return e;
+    if (int e = scratch.upload(&dg, gg.data(), gg.size() * 4)) return e;
+    if (int e = scratch.upload(&db, be.data(), be.size() * 4)) return e;
+    const int film_ld = 4 * DA;
+    const size_t fbytes = (size_t)nb * film_ld * 4;
+    if (int e = scratch.alloc(&fsc, fbytes)) return e;
+    DSH_HIP_CHECK(hipMemcpyAsync(fsc, film, fbytes, hipMemcpyDeviceToDevice, s));
+    if (int e = dsh::launch_film_fold(reinterpret_cast<float*>(fsc), film_ld, nb, 2, DA, reinterpret_cast<const float*>(dg), reinterpret_cast<const float*>(db), s)) return e;
+    const int rc = dsh::launch_tl_aud_tail(Y, X2, wst, reinterpret_cast<const float*>(dbias), reinterpret_cast<const float*>(fsc), film_ld, nb, frames, Mc,
+                                           out_f, out_b, ld_b, s);
+    DSH_HIP_CHECK(hipStreamSynchronize(s));      // the per-call scratch is released on return
+    return rc;
+    API_END
+}
+
+int dsh_op_tl_aproj(void* hip_stream, const void* X, const float* W, const float* bias, int32_t n_enc, void* out0, void* out1, int32_t Mc) {
+    API_BEGIN
+    DSH_REQUIRE(W && bias && (n_enc == 1 || n_enc == 2) && Mc > 0, "dsh_op_tl_aproj: null weight, or not one or two encoders");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    OpScratch scratch;
+    DSH_HIP_CHECK(hipStreamSynchronize(s));
+    std::vector<float> hw;
+    if (int e = fetch_f32(hw, W, (size_t)n_enc * 256 * 256)) return e;
+    std::vector<uint16_t> st((size_t)n_enc * 65536);
+    for (int e = 0; e < n_enc; ++e) dsh::tl_aud_pack_audio_proj(hw.data() + (size_t)e * 65536, st.data() + (size_t)e * 65536);   // encoder e at + e * 128 KB
+    void *wf = nullptr, *t0 = nullptr, *t1 = nullptr;
+    if (int e = scratch.upload(&wf, st.data(), st.size() * 2)) return e;
+    const size_t tbytes = (size_t)dsh::round_up(Mc, 32) * 256 * 2;       // tiled outputs: whole 32-row blocks (the kernel stores into the padding rows)
+    if (out0) { if (int e = scratch.alloc(&t0, tbytes)) return e; }
+    if (out1) { if (int e = scratch.alloc(&t1, tbytes)) return e; }
+    int rc = dsh::launch_tl_aproj(X, wf, bias, n_enc, t0, t1, Mc, s);
+    if (!rc) rc = dsh::launch_untile_rows_bf16(t0, 256, Mc, 256, out0, 256, s);
+    if (!rc && n_enc == 2) rc = dsh::launch_untile_rows_bf16(t1, 256, Mc, 256, out1, 256, s);
+    DSH_HIP_CHECK(hipStreamSynchronize(s));
+    return rc;
+    API_END
+}
+
+int dsh_op_tl_joint(void* hip_stream, const float* x, int32_t ldx, int32_t c0, int32_t w, const float* Wj, const float* bias, const float* pe,
+                    int32_t frames, const float* cnull, int32_t Mc, int32_t row1, float* h_out) {
+    API_BEGIN
+    DSH_REQUIRE(x && Wj && h_out && w > 0 && c0 >= 0 && c0 + w <= ldx && Mc > 0, "dsh_op_tl_joint: null x / weight / output, or a channel slice outside the row");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    OpScratch scratch;
+    DSH_HIP_CHECK(hipStreamSynchronize(s));
+    const int nf = dsh::ceil_div(w, 16), Mp = dsh::round_up(Mc, 32);
+    std::vector<float> hw;
+    if (int e = fetch_f32(hw, Wj, (size_t)512 * w)) return e;
+    std::vector<uint16_t> fr((size_t)512 * nf * 16);
+    dsh::tl_joint_pack_weight(hw.data(), w, nf, fr.data());
+    void *wf = nullptr, *xt = nullptr, *hi = nullptr, *lo = nullptr;
+    if (int e = scratch.upload(&wf, fr.data(), fr.size() * 2)) return e;
+    if (int e = scratch.alloc(&xt, (size_t)Mp * nf * 16 * 2)) return e;
+    if (int e = dsh::launch_tile_rows_bf16<float>(x + c0, ldx, Mc, w, xt, nf * 16, s)) return e;      // as Denoiser::run_encoder does
+    // planes: the null half's blocks at row 0, the conditional half's at row1 (CFG) — rows the kernel does not write come back as 0
+    const int rows = (cnull ? std::max(row1, 0) : 0) + Mp;
+    if (int e = scratch.alloc(&hi, (size_t)rows * 512 * 2)) return e;
+    if (int e = scratch.alloc(&lo, (size_t)rows * 512 * 2)) return e;
+    DSH_HIP_CHECK(hipMemsetAsync(hi, 0, (size_t)rows * 512 * 2, s));
+    DSH_HIP_CHECK(hipMemsetAsync(lo, 0, (size_t)rows * 512 * 2, s));
+    int rc = dsh::launch_tl_joint(xt, nf, wf, bias, pe, frames, cnull, Mc, row1, hi, lo, s);
+    if (!rc) rc = dsh::launch_untile_rows_hilo(hi, lo, 512, rows, 512, h_out, 512, s);
+    DSH_HIP_CHECK(hipStreamSynchronize(s));
+    return rc;
+    API_END
+}
+
 int dsh_op_cross_attention(void* hip_stream, const dsh_cross_attn_weights* w, const float* x, const float* xf, const float* emb,
                            int32_t B, int32_t T, int32_t N, int32_t D, int32_t L, int32_t E, int32_t num_head, float* y) {
     API_BEGIN

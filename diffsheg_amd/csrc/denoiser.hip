@@ -635,15 +635,12 @@ int Denoiser<T>::encoder_from(const std::map<std::string, HostTensor>& w, const 
         const HostTensor* jw = find(w, p + "joint_embed.weight"); if (!jw) return -1;
         const int nf = ceil_div(cin, 16);
         if (nf == 7 || nf == 9) {
-            const int Kj = nf * 16;
-            std::vector<T> fr((size_t)D * Kj);
-            for (int r = 0; r < D; ++r) {
-                const int sr = (r & ~31) + tl_weight_src_row(r & 31);
-                for (int k = 0; k < Kj; ++k) fr[tl2_frag_index(Kj, r >> 5, r & 31, k)] = from_f32<T>(k < cin ? jw->data[(size_t)sr * cin + k] : 0.f);
-            }
+            DSH_REQUIRE((int64_t)jw->numel() == (int64_t)D * cin, "joint_embed weight shape");
+            std::vector<uint16_t> fr((size_t)D * nf * 16);                 // (bf16 path only: T = bf16)
+            tl_joint_pack_weight(jw->data.data(), cin, nf, fr.data());
             if (int e = dalloc(&E.joint_wf, fr.size(), allocs)) return e;
-            DSH_HIP_CHECK(hipMemcpy(E.joint_wf, fr.data(), fr.size() * sizeof(T), hipMemcpyHostToDevice));
-            wbytes += fr.size() * sizeof(T);
+            DSH_HIP_CHECK(hipMemcpy(E.joint_wf, fr.data(), fr.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            wbytes += fr.size() * sizeof(uint16_t);
             E.joint_nf = nf;
         }
     }

@@ -160,6 +160,7 @@ int launch_seed_stream(const float* h0, int Mc, int D, const float* c, int has_n
                        void* hlo = nullptr);      // hlo != null: the stream is seeded as (h16 = hi, hlo = lo) planes and h is not written
 // round 6 (tl_embed.hip): the same seed straight from the tiled bf16 channels of x — joint_embed + bias + PE + null constant + plane split
 // in one launch; x_tiled [Mc, 16 nf] (nf = 7 or 9), wfrag = fragment-ordered [512, 16 nf] weight
+void tl_joint_pack_weight(const float* w, int cin, int nf, uint16_t* fr);     // joint_embed [512, cin] fp32 -> wfrag (512 * 16 nf bf16)
 int launch_tl_joint(const void* x_tiled, int nf, const void* wfrag, const float* bias, const float* pe, int frames, const float* cnull,
                     int Mc, int row1, void* hi, void* lo, hipStream_t s);
 // round 6 (tl_aud.hip): encoder_aud behind its attention (two StylizationBlocks + FFN at D = 128) in one launch; Y bf16 [Mc,128] and X2 fp32

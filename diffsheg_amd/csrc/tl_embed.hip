@@ -96,6 +96,16 @@ __global__ __launch_bounds__(256, 2) void tl_joint_kernel(TlJointArgs p) {
     });
 }
 
+// joint_embed [512, cin] (row-major fp32) as the seed's weight operand: rows pi-permuted inside every 32-row tile, K zero-padded to 16 nf
+// columns, fragment order (tl2_frag_index), values rounded to bf16; `fr` receives 512 * 16 nf elements
+void tl_joint_pack_weight(const float* w, int cin, int nf, uint16_t* fr) {
+    const int Kj = nf * 16;
+    for (int r = 0; r < 512; ++r) {
+        const int sr = (r & ~31) + tl_weight_src_row(r & 31);
+        for (int k = 0; k < Kj; ++k) fr[tl2_frag_index(Kj, r >> 5, r & 31, k)] = f32_to_bf16(k < cin ? w[(size_t)sr * cin + k] : 0.f).v;
+    }
+}
+
 // x_tiled: bf16 tiled [Mc, 16 nf] (launch_tile_rows_bf16 of the encoder's channels of x), nf = 7 (K <= 112) or 9 (K <= 144)
 int launch_tl_joint(const void* x_tiled, int nf, const void* wfrag, const float* bias, const float* pe, int frames, const float* cnull,
                     int Mc, int row1, void* hi, void* lo, hipStream_t s) {

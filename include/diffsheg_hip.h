@@ -308,6 +308,24 @@ int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W
 int dsh_op_tl2_ffn(void* hip_stream, const void* X, const float* Hres, const void* W1, const float* b1, const void* W2, const float* b2,
                    const void* W3, const float* b3, const float* gamma, const float* beta, const float* film, int32_t frames, int32_t nb,
                    const float* row_const, int32_t n_const_rows, float* Cf, void* Ct, int32_t M);
+/* Fused front of the bf16 path, one kernel each (test helpers like the two above: row-major device operands in natural order, packed with
+ * the library's own packers in per-call scratch, nothing cached).
+ * encoder_aud behind its attention (models/transformer.py:730-739): h = X2 + Ls1(SiLU(LN(Y; g1, be1) (1 + scale1) + shift1)),
+ *   y2 = GELU(bf16(h) w1^T + b1) w2^T + b2, out = h + Ls2(SiLU(LN(y2; g2, be2) (1 + scale2) + shift2)); out_f fp32 [Mc,128], out_b = bf16(out)
+ *   with leading dimension ld_b.  Y bf16 [Mc,128], X2 fp32 [Mc,128]; ws1 / ws2 [128,128], w1 [1024,128], w2 [128,1024] and their biases fp32
+ *   (torch layouts); film [nb, 512] = (scale1 | shift1 | scale2 | shift2) of embedding row (row / frames) % nb. */
+int dsh_op_tl_aud_tail(void* hip_stream, const void* Y, const float* X2, const float* ws1, const float* bs1, const float* w1, const float* b1,
+                       const float* w2, const float* b2, const float* ws2, const float* bs2, const float* g1, const float* be1, const float* g2,
+                       const float* be2, const float* film, int32_t frames, int32_t nb, int32_t Mc, float* out_f, void* out_b, int32_t ld_b);
+/* audio_proj of one or two motion encoders: out_e = bf16(X W[e]^T + bias[e]); X bf16 [Mc,256], W fp32 [n_enc,256,256], bias fp32 [n_enc,256],
+ * out0 / out1 bf16 row-major [Mc,256] (out1 null for n_enc == 1). */
+int dsh_op_tl_aproj(void* hip_stream, const void* X, const float* W, const float* bias, int32_t n_enc, void* out0, void* out1, int32_t Mc);
+/* Layer-0 seed: h = bf16(x[:, c0 : c0 + w]) bf16(Wj)^T + bias + pe[row % frames], as hi + lo planes read back in fp32.  x fp32 [Mc, ldx],
+ * Wj fp32 [512, w] (w in 97 .. 112 or 129 .. 144), pe fp32 [frames, 512].  cnull == null: h_out [round_up(Mc, 32), 512], rows [0, Mc) = h.
+ * cnull [512]: h_out [row1 + round_up(Mc, 32), 512], rows [0, Mc) = h + cnull (CFG-null half), rows [row1, row1 + Mc) = h; row1 a
+ * multiple of 32, >= Mc.  Rows no kernel block covers come back as 0; the padding rows of a covered block are unspecified. */
+int dsh_op_tl_joint(void* hip_stream, const float* x, int32_t ldx, int32_t c0, int32_t w, const float* Wj, const float* bias, const float* pe,
+                    int32_t frames, const float* cnull, int32_t Mc, int32_t row1, float* h_out);
 /* LinearTemporalCrossAttention (models/transformer.py:133-166; the `transformer_decoder` layer's ca_block): device fp32
  * weights under the module's own parameter names.  y = x + proj_out(softmax_ch(Wq LN(x)) (softmax_N(Wk tn(xf))^T Wv tn(xf)), emb),
  * x [B,T,D], xf [B,N,L], emb [B,E] (the raw embedding: proj_out.emb_layers applies SiLU first), y [B,T,D]. */

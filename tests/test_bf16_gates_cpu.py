@@ -286,6 +286,124 @@ def test_attention_mutants_are_rejected(attn):
     _record("attn/padded_frame", float((mut[:, :21].double() - rold[:, :21]).abs().max()) < 2e-2 * max(1.0, float(rold.abs().max())))
 
 
+# ---- fused encoder_aud tail (D = 128) --------------------------------------------------------------------------------------------------------------
+AUD_SHAPES = [(300, 88, 4), (44, 11, 4), (290, 34, 9)]
+_AUD = {}
+
+
+def _aud(shape):
+    if shape not in _AUD:
+        t = G.aud_inputs(*shape)
+        _AUD[shape] = (t,) + G.aud_gates(t, *shape)
+    return _AUD[shape]
+
+
+@pytest.mark.parametrize("shape", AUD_SHAPES)
+@pytest.mark.parametrize("reverse", [False, True])
+def test_aud_tail_emulation_passes(shape, reverse):
+    t, ref, slack, rms, cal, st = _aud(shape)
+    Mc, T, nb = shape
+    y = G.aud_chain(t, Mc, T, nb, torch.float32, reverse=reverse, noise=G.gelu_noise((Mc, 1024), seed=2 + reverse))
+    assert G.assert_close_f32(y, ref, slack) <= 1.0
+    assert G.assert_rounded(y.bfloat16(), ref, slack) <= 1.0
+    assert G.assert_rms(y, ref, rms) <= 1.0
+    assert G.assert_rms(y.bfloat16(), ref, rms + G.bf16_rounding_rms(ref)) <= 1.0
+    # the gate is a fraction of a percent of the output range (the whole-model test of the aud_feat tap allows 2 %)
+    assert float(slack.max()) < 5e-3 * float(ref.max() - ref.min())
+
+
+@pytest.mark.parametrize("shape", AUD_SHAPES)
+@pytest.mark.parametrize("mutant", ["film_neighbour_one_row", "w2_kstep", "film_block1_for_block2", "residual_x", "truncate"])
+def test_aud_tail_mutants_are_rejected(shape, mutant):
+    t, ref, slack, rms, cal, st = _aud(shape)
+    Mc, T, nb = shape
+    kw, m = {}, t
+    if mutant == "film_neighbour_one_row":          # ONE row (the last frame of clip 0) takes the next clip's FiLM row
+        rows = torch.arange(Mc)
+        fr = (rows // T) % nb
+        fr[T - 1] = 1
+        kw["film_rows"] = fr
+    elif mutant == "w2_kstep":                      # one 16-wide k step of linear2 (hidden features 336 .. 351) left out
+        W2 = t["W2"].clone(); W2[:, 336:352] = 0
+        m = dict(t, W2=W2)
+    elif mutant == "film_block1_for_block2":
+        m = dict(t, film=torch.cat([t["film"][:, :256], t["film"][:, :256]], 1))
+    elif mutant == "residual_x":
+        kw["final_res"] = "x"
+    y = G.aud_chain(m, Mc, T, nb, torch.float64, **kw)
+    if mutant == "truncate":
+        # one flip of s2 is worth more than an ulp of the output, so no single element gives a truncating store away against the fp64
+        # chain, and its rms (ulp / sqrt(3) in place of ulp / sqrt(12)) lands on the rms gate: the store is checked against the kernel's
+        # own fp32 output instead, exactly
+        G.assert_store_is_rne(y.float().bfloat16(), y.float())
+        assert _rejected(G.assert_store_is_rne, G.truncate_bf16(y.float()), y.float())
+        return
+    assert _rejected(G.assert_close_f32, y.float(), ref, slack, frames=T, nb=nb)
+    assert _rejected(G.assert_rounded, y.bfloat16(), ref, slack, frames=T, nb=nb)
+    bad = int(((y - ref).abs() > slack).sum())
+    assert bad > (100 if mutant == "film_neighbour_one_row" else 1000), bad     # one row of 128 / most of the tensor
+    if mutant != "film_neighbour_one_row":          # every row is wrong: the rms gate alone rejects it
+        assert _rejected(G.assert_rms, y.float(), ref, rms)
+
+
+def test_ln_raw_moment_slack_grows_with_the_offset_only():
+    """The widening of the large-offset test is nothing at offset 0 beside the calibrated gate and follows mean^2 / var."""
+    t, ref, slack, rms, cal, st = _aud((300, 88, 4))
+    A2 = (t["g2"] * (1 + t["film"][:, 256:384]))[(torch.arange(300) // 88) % 4]
+    w0 = G.ln_raw_moment_slack(st["y2"], A2, t["Ws2"])
+    w100 = G.ln_raw_moment_slack(st["y2"] - 100.0, A2, t["Ws2"])
+    assert float(w0.max()) < 1e-2 * G.MARGIN * cal
+    r = st["y2"].double()
+    growth = (1 + (r.mean(-1) - 100) ** 2 / r.var(-1, unbiased=False)) / (1 + r.mean(-1) ** 2 / r.var(-1, unbiased=False))
+    assert torch.allclose(w100.max(-1).values / w0.max(-1).values, growth, rtol=1e-2)
+
+
+# ---- audio_proj ----------------------------------------------------------------------------------------------------------------------------------------
+def test_aproj_emulation_passes_and_the_other_encoders_bias_is_rejected():
+    t = G.aproj_inputs(129, 2)
+    for e in (0, 1):
+        ref = G.aproj_ref(t, e)
+        slack = G.accum_bound(t["X"], t["W"][e], 256)
+        for reverse in (False, True):
+            assert G.assert_rounded(G.aproj_ref(t, e, torch.float32, reverse=reverse).bfloat16(), ref, slack) <= 1.0
+    ref, slack = G.aproj_ref(t, 1), G.accum_bound(t["X"], t["W"][1], 256)
+    assert _rejected(G.assert_rounded, G.aproj_ref(t, 1, bias_of=0).bfloat16(), ref, slack)
+    assert _rejected(G.assert_rounded, G.truncate_bf16(ref), ref, slack)
+
+
+# ---- layer-0 seed --------------------------------------------------------------------------------------------------------------------------------------
+JOINT_CASES = [(103, 44, 11), (141, 290, 34)]
+
+
+@pytest.mark.parametrize("w,Mc,T", JOINT_CASES)
+def test_joint_emulation_passes(w, Mc, T):
+    t = G.joint_inputs(w, Mc, T, ldx=w + 40, c0=17)
+    refs, slacks = G.joint_ref(t, Mc, T), G.joint_slack(t, Mc, T)
+    for reverse in (False, True):
+        outs = G.joint_ref(t, Mc, T, torch.float32, reverse=reverse, planes=True)
+        for o, r, s in zip(outs, refs, slacks):
+            assert G.assert_close_f32(o, r, s) <= 1.0
+    assert float(slacks[1].max()) < 5e-4          # (2^-17 of a value of a few units and 144 x 2^-23 of ~10 in products)
+
+
+@pytest.mark.parametrize("w,Mc,T", JOINT_CASES)
+@pytest.mark.parametrize("mutant", ["pe_modulus", "null_on_cond", "last_fragment", "lo_dropped"])
+def test_joint_mutants_are_rejected(w, Mc, T, mutant):
+    t = G.joint_inputs(w, Mc, T, ldx=w + 40, c0=17)
+    (rc, rn), (sc, sn) = G.joint_ref(t, Mc, T), G.joint_slack(t, Mc, T)
+    if mutant == "pe_modulus":                    # PE row = row % (frames + 1)
+        mc, mn = G.joint_ref(t, Mc, T, pe_mod=T + 1)
+    elif mutant == "null_on_cond":                # the null constant reaches the conditional half as well
+        mc, mn = rn, rn
+    elif mutant == "last_fragment":               # columns >= 16 (nf - 1) left out
+        mc, mn = G.joint_ref(t, Mc, T, kdrop=16 * ((w + 15) // 16 - 1))
+    else:
+        mc, mn = rc.bfloat16().double(), rn.bfloat16().double()
+    assert _rejected(G.assert_close_f32, mc.float(), rc, sc, frames=T, nb=Mc // T)
+    if mutant != "null_on_cond":
+        assert _rejected(G.assert_close_f32, mn.float(), rn, sn, frames=T, nb=Mc // T)
+
+
 # ---- elementary properties -----------------------------------------------------------------------------------------------------------------------
 def test_ulp_and_bound_definitions():
     v = torch.tensor([1.0, 1.5, 2.0, 0.75, 255.0, 256.0, 0.0, 1e-45, -3.0])
