@@ -14,8 +14,10 @@
 //          film_expand_kernel, fold = 1).
 //
 // These replace ln_rows / concat_ln_rows / ln_film_silu_rows + gemm_nt_kernel<float>: four row kernels and their 2 x M x K x 4 bytes round trips per
-// layer.  Moments are one-pass SHIFTED sums (sum (x - x0), sum (x - x0)^2 with x0 = the row's first element): as robust against a large row mean
-// as the two-pass form of the row kernels, to fp32 round-off.
+// layer.  Moments are one-pass SHIFTED sums (sum (x - x0), sum (x - x0)^2) with x0 = the mean of the row's first K tile (32 columns).  A shift
+// near the row mean keeps the var = E[(x - x0)^2] - (mean - x0)^2 cancellation at fp32 round-off, like the two-pass form of the row kernels; the
+// row's first ELEMENT as the shift (the first form) did that for a whole-row offset only: one outlier channel in column 0 put the shift |x[0]|
+// away from the mean and cost rstd two to three orders of magnitude (4e-5 .. 2e-4 relative at x[0] = 60 .. 1e4).
 //   PRO 0  y = act(x W^T + b) (+ residual): the same main loop without a front (feat_proj.3, ffn.linear1 / 2 of the fp32 path).
 // Tile = gemm_nt_kernel<float, 1, 1, 1, 2>'s (gemm.hip): 64 x 64, four waves, exact-fp32 v_mfma_f32_32x32x2_f32, double-buffered LDS stages; the main
 // loop is software-pipelined (below).
@@ -105,9 +107,18 @@ __global__ __launch_bounds__(256) void gemm_f32_pro_kernel(GemmProArgs p) {
     };
 
     float x0[2] = {0.f, 0.f}, s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
-    if (PRO != 0)
+    if (PRO == 1 || (PRO == 2 && !p.stats)) {
+        // shift = mean of the row's first K tile (this thread's 16-byte chunk of it, then the eight staging lanes of the row): any constant is
+        // algebraically exact, and a mean of 32 columns cannot be dominated by one outlier channel the way x[0] can
 #pragma unroll
-    for (int i = 0; i < 2; ++i) x0[i] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.seg[0]) + (size_t)arow[i] * p.seg_ld[0] * 4);
+        for (int i = 0; i < 2; ++i) {
+            const g32x4 v = load_a(i);
+            float t = (v.x + v.y) + (v.z + v.w);
+#pragma unroll
+            for (int o = 1; o < 8; o <<= 1) t += __shfl_xor(t, o, 64);
+            x0[i] = t * (1.0f / 32.0f);
+        }
+    }
     auto moments = [&](const g32x4& v, int i) {
         const float a = v.x - x0[i], b = v.y - x0[i], c = v.z - x0[i], d = v.w - x0[i];
         s1[i] += (a + b) + (c + d);

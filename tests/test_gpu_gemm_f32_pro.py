@@ -2,7 +2,12 @@
 (diffsheg_amd/csrc/gemm_f32_pro.hip) vs an fp64 restatement of models/transformer.py:86-97 (StylizationBlock),
 :119-125 (sa_block.norm + q|k|v) and :284-289, :304-312 (feat_proj.0 LayerNorm over the concat + feat_proj.1),
 called through the C ABI (dsh_op_gemm_f32_pro); and the whole evaluation with the fused launches against the
-separate row kernels of rounds 1 - 5 (DSH_F32_FUSE=0)."""
+separate row kernels of rounds 1 - 5 (DSH_F32_FUSE=0).
+
+Every comparison with fp64 is gated on every element by tests/f32_gates.py (MARGIN x the fp32 evaluation's own distance from fp64; where a
+test had a range-fraction tolerance before, the smaller of the two holds).  The shared case list of f32_gates.py (small-shape grid, concat
+segments, input families, clip layouts, group moments) runs in two fresh worker processes, one per operand path (DSH_GP_DMA = 1 / 0):
+each run is gated against fp64, the two are compared bit for bit, and the guard rows around every buffer are checked."""
 import ctypes as C
 
 import pytest
@@ -14,18 +19,23 @@ from diffsheg_amd import _lib  # noqa: E402
 from diffsheg_amd.config import get_config  # noqa: E402
 from diffsheg_amd.synthetic import make_inputs  # noqa: E402
 from util import max_abs, synthetic_sd  # noqa: E402
+import f32_gates as G  # noqa: E402
 
 
 def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def _fold(W, b, gamma, beta, Kp):
-    """LN(x) W^T + b = rstd (x W'^T - mean c) + d with W' = gamma (.) W (zero padded to Kp columns), c = W' 1, d = b + W beta."""
-    N, K = W.shape
-    Wf = torch.zeros(N, Kp, dtype=torch.float64)
-    Wf[:, :K] = W.double() * gamma.double()
-    return Wf.float(), Wf.float().double().sum(1).float(), (b.double() + W.double() @ beta.double()).float()
+_fold = G.fold
+
+
+def _derived(t, out, old_tol, what):
+    """Gate `out` on every element with the smaller of the derived allowance and the tolerance the test had before; prints kernel / calibration."""
+    ref, allow, cal = G.gate(t)
+    r, _ = G.ratio(t, out)
+    allow = float(allow.max())
+    print(f"[{what}] kernel / calibration = {r:.2f} (calibration {cal:.2e}, gate {min(allow, old_tol):.2e}, previous tolerance {old_tol:.2e})")
+    G.assert_close_f32(out.cpu()[:t["M"]], ref[:t["M"]], min(allow, old_tol), what, frames=t.get("frames", 0), nb=t.get("nb", 0))
 
 
 @pytest.mark.parametrize("M,N,widths,k_real,act,offset", [
@@ -71,6 +81,9 @@ def test_folded_layernorm_linear_matches_fp64(M, N, widths, k_real, act, offset)
     tol = 3e-5 * max(1.0, ref.abs().max().item()) * (1.0 if offset == 0.0 else 20.0)
     print(f"[fold M={M} N={N} K={K} P={k_real} offset={offset}] max err {err:.2e} (|ref| max {ref.abs().max().item():.2f})")
     assert err < tol, err
+    t = {"kind": "pro1", "M": M, "N": N, "K": K, "k_real": k_real, "act": act, "X": X, "Xp": torch.nn.functional.pad(X, (0, K - k_real)), "W": W, "b": b,
+         "gamma": gamma, "beta": beta, "Wf": Wf, "fc": fc, "fd": fd}
+    _derived(t, out, tol, f"fold M={M} N={N} K={K} P={k_real} offset={offset}")
 
 
 @pytest.mark.parametrize("M,N,K,frames,nb,offset", [(8704, 512, 512, 34, 256, 0.0), (2 * 264 + 5, 512, 512, 88, 3, 0.0), (77, 128, 128, 11, 7, 0.0),
@@ -99,6 +112,10 @@ def test_stylization_block_linear_matches_fp64(M, N, K, frames, nb, offset):
     err = (out.cpu().double() - ref).abs().max().item()
     print(f"[sty M={M} N={N} K={K}] max err {err:.2e} (|ref| max {ref.abs().max().item():.2f})")
     assert err < 3e-5 * max(1.0, ref.abs().max().item()), err
+    t = G.pro2_finish({"kind": "pro2", "M": M, "N": N, "K": K, "frames": frames, "nb": nb, "film_off": off, "stat_groups": 0, "act": 0, "X": y, "gamma": gamma,
+                       "beta": beta, "scale": scale, "shift": shift, "W": W, "b": b, "R": R})
+    assert torch.equal(t["film"][:, off:off + 2 * K], film[:, off:off + 2 * K])
+    _derived(t, out, 3e-5 * max(1.0, ref.abs().max().item()), f"sty M={M} N={N} K={K} offset={offset}")
 
 
 @pytest.mark.parametrize("M,offset", [(8704, 0.0), (300 + 11, 30.0)])
@@ -139,26 +156,77 @@ def test_row_moments_travel_from_the_producer_to_the_stylization_launch(M, offse
     e_ref, e_ab = (outs[0] - ref).abs().max().item(), (outs[0] - outs[1]).abs().max().item()
     print(f"[moments side channel M={M} offset={offset}] vs fp64 {e_ref:.2e}, vs own-moments launch {e_ab:.2e}")
     assert e_ref < 5e-5 * max(1.0, ref.abs().max().item()) and e_ab < 2e-5 * max(1.0, ref.abs().max().item())
+    prod = {"kind": "pro0", "M": M, "N": D, "K": K1, "act": 0, "X": a, "W": W2, "b": b2, "R": None, "stats_out": True, "alias": False}
+    t = G.pro2_finish({"kind": "side", "prod": prod, "M": M, "N": D, "K": D, "frames": frames, "nb": nb, "film_off": 0, "stat_groups": 0, "act": 0,
+                       "X": torch.zeros(M, D), "gamma": gamma, "beta": beta, "scale": scale, "shift": shift, "W": W3, "b": b3, "R": R})
+    scale_ = max(1.0, ref.abs().max().item())
+    _derived(dict(t), outs[1], 5e-5 * scale_, f"moments side channel M={M} offset={offset}: launch with its own moments")
+    t["stat_groups"] = D // 32
+    _derived(t, outs[0], 5e-5 * scale_, f"moments side channel M={M} offset={offset}: launch with the producer's group moments")
+    _derived(prod, y2d, 5e-5 * max(1.0, y2.abs().max().item()), f"moments side channel M={M} offset={offset}: producer")
+    sref, a_mean, a_m2 = G.stats_gate(prod)
+    got = st.cpu().double()
+    assert float((got[..., 0] - sref[..., 0]).abs().max()) <= a_mean and float((got[..., 1] - sref[..., 1]).abs().max()) <= a_m2
 
 
-def test_lds_dma_and_register_staging_give_identical_results(tmp_path):
-    """The operands reach LDS by DMA (default) or through the staging registers (DSH_GP_DMA=0): the arithmetic is the same operation for
-    operation — including the order in which the row moments are accumulated — so the outputs are bit-identical (fresh processes: the switches
-    are read once)."""
+@pytest.fixture(scope="module")
+def worker_runs(tmp_path_factory):
+    """The shared case list through both operand paths: one fresh child process per value of DSH_GP_DMA (the switch is read once per
+    process), each under a timeout.  {"1": outputs, "0": outputs}."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = []
+    tmp = tmp_path_factory.mktemp("gp_dma")
+    res = {}
     for dma in ("1", "0"):
-        f = str(tmp_path / f"gp_dma_{dma}.pt")
+        f = str(tmp / f"gp_dma_{dma}.pt")
         r = subprocess.run([sys.executable, os.path.join(root, "tests", "gp_dma_worker.py"), f], env=dict(os.environ, DSH_GP_DMA=dma), capture_output=True, text=True,
                            timeout=600)
         assert r.returncode == 0 and "GP_DMA_WORKER_OK" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])
-        res.append(torch.load(f))
+        res[dma] = torch.load(f)
+    return res
+
+
+def test_lds_dma_and_register_staging_give_identical_results(worker_runs):
+    """The operands reach LDS by DMA (default) or through the staging registers (DSH_GP_DMA=0): the arithmetic is the same operation for
+    operation — including the order in which the row moments are accumulated — so the outputs are bit-identical (fresh processes: the switches
+    are read once).  Every launch of the shared case list, guard rows included; the PRO 1 launch carries a real fold and is compared with fp64."""
+    res = [worker_runs["1"], worker_runs["0"]]
     for k in ("pro0", "pro1", "pro2"):
-        assert torch.isfinite(res[0][k]).all()
-        assert torch.equal(res[0][k], res[1][k]), (k, float((res[0][k] - res[1][k]).abs().max()))
+        assert torch.isfinite(res[0]["legacy"][k]).all()
+        assert torch.equal(res[0]["legacy"][k], res[1]["legacy"][k]), (k, float((res[0]["legacy"][k] - res[1]["legacy"][k]).abs().max()))
+    ref = res[0]["legacy"]["pro1_ref64"]
+    err = (res[0]["legacy"]["pro1"].double() - ref).abs().max().item()
+    assert err < 3e-5 * max(1.0, ref.abs().max().item()), err
+    assert set(res[0]) == set(res[1]) == set(G.CASES) | {"legacy"}
+    differ = [(n, k) for n in G.CASES for k in res[0][n] if not torch.equal(res[0][n][k], res[1][n][k])]
+    assert not differ, differ[:20]
+
+
+@pytest.mark.parametrize("name", list(G.CASES))
+def test_case_list_against_fp64_on_both_operand_paths(name, worker_runs):
+    """One case of f32_gates.CASES: each operand path gated against fp64 on every element, group moments against the fp64 moments of the
+    fp64 rows, and the guard rows behind M untouched (the NaN rows behind the inputs would show as NaN in the output)."""
+    t = G.case(name)
+    M = t["M"]
+    for dma in ("1", "0"):
+        out = worker_runs[dma][name]
+        for k, v in out.items():
+            assert bool((v[M:] == G.SENTINEL).all()), f"{name} dma={dma}: rows behind M of {k} were written"
+        r, cal = G.ratio(t, out["y"])
+        print(f"[{name} dma={dma}] kernel / calibration = {r:.2f} (calibration {cal:.2e})")
+        G.check(t, out["y"], f"{name} dma={dma}")
+        prod = t["prod"] if t["kind"] == "side" else t if t["kind"] == "pro0" and t["stats_out"] else None
+        if t["kind"] == "side":
+            r2, cal2 = G.ratio(prod, out["y2"])
+            print(f"[{name} dma={dma}] producer kernel / calibration = {r2:.2f} (calibration {cal2:.2e})")
+            G.check(prod, out["y2"], f"{name} producer dma={dma}")
+        if prod is not None:
+            sref, a_mean, a_m2 = G.stats_gate(prod)
+            d = (out["stats"][:M].double() - sref[:M]).abs()
+            print(f"[{name} dma={dma}] group moments: mean {float(d[..., 0].max()):.2e} of {a_mean:.2e}, M2 {float(d[..., 1].max()):.2e} of {a_m2:.2e}")
+            assert float(d[..., 0].max()) <= a_mean and float(d[..., 1].max()) <= a_m2, f"{name} dma={dma}: group moments outside the gate"
 
 
 @pytest.mark.parametrize("ds,B,T", [("beat", 16, 34), ("beat", 256, 34), ("show", 8, 88), ("show", 21, 30)])
