@@ -87,6 +87,27 @@ SYMBOLS = {
     "dsh_op_ddim_step": (C.c_int, [_P] * 6 + [C.c_int32] * 3 + [C.c_float] * 4 + [C.c_int32] * 6),
     "dsh_op_philox_randn": (C.c_int, [_P, _P, C.c_int64, C.c_uint64, C.c_uint64]),
     "dsh_op_philox_randn_rows": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "dsh_op_philox_randn_rows_ragged": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                                                  C.c_uint64, C.c_int32]),
+    "dsh_op_ddim_step_full": (C.c_int, [_P] * 10 + [C.c_int32] * 3 + [C.c_float] * 6 + [C.c_int32] * 6),
+    "dsh_op_ddpm_step": (C.c_int, [_P] * 5 + [C.c_int64] + [C.c_float] * 5 + [C.c_int32] * 4),
+    "dsh_op_undo_step": (C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "dsh_op_level_copy": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, _P, C.c_int64, _P, C.c_int32]),
+    "dsh_op_fill_step": (C.c_int, [_P] * 5 + [C.c_int64, C.c_float, C.c_float, C.c_int64, C.c_int32]),
+    "dsh_op_store_values_f32": (C.c_int, [_P, _P, C.POINTER(C.c_float), C.c_int32]),
+    "dsh_op_zero_padded_frames": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    "dsh_op_fill_cols": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32]),
+    "dsh_op_temb": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
+    "dsh_op_cfg_mix": (C.c_int, [_P, _P] + [C.c_int32] * 6 + [_P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int32]),
+    "dsh_op_im2col3": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    "dsh_op_film_fold": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "dsh_op_film_expand": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
+    "dsh_op_gather_rows": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    "dsh_op_seed_stream": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "dsh_op_pack_expr_track": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P]),
+    "dsh_op_layernorm_pre": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int32]),
+    "dsh_op_ln_film_silu": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
+    "dsh_op_concat_ln": (C.c_int, [_P, C.c_int32] + [_P, C.c_int32, C.c_int32] * 4 + [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32]),
     "dsh_fgd_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
     "dsh_fgd_destroy": (C.c_int, [_P]),
     "dsh_fgd_load_tensor": (C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), C.c_int32]),

@@ -1000,6 +1000,255 @@ int dsh_op_philox_randn_rows(void* hip_stream, float* out, int32_t rows, int64_t
     API_END
 }
 
+// ---- one entry per small kernel of the sampler and around the denoiser (test helpers; include/diffsheg_hip.h) -------
+int dsh_op_philox_randn_rows_ragged(void* hip_stream, float* out, int32_t rows, int64_t n_row, uint64_t seed, uint64_t offset,
+                                    const uint64_t* row_keys_host, const int32_t* row_lens_host, uint64_t draw, int32_t channels) {
+    API_BEGIN
+    DSH_REQUIRE(out && rows > 0 && n_row > 0 && row_keys_host, "invalid argument");
+    if (row_lens_host)
+        for (int b = 0; b < rows; ++b)
+            DSH_REQUIRE(row_lens_host[b] >= 0 && channels > 0 && (int64_t)row_lens_host[b] * channels <= n_row, "philox_randn_rows_ragged: a row length outside its row");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    OpScratch scratch;
+    void *kd = nullptr, *ld = nullptr;
+    if (int e = scratch.upload(&kd, row_keys_host, (size_t)rows * sizeof(uint64_t))) return e;
+    if (row_lens_host) { if (int e = scratch.upload(&ld, row_lens_host, (size_t)rows * sizeof(int32_t))) return e; }
+    const int rc = dsh::launch_philox_randn_rows(out, rows, (size_t)n_row, seed, offset, reinterpret_cast<const uint64_t*>(kd), s,
+                                                 reinterpret_cast<const int*>(ld), draw, channels);
+    DSH_HIP_CHECK(hipStreamSynchronize(s));          // the scratch arrays are released on return
+    return rc;
+    API_END
+}
+
+int dsh_op_ddim_step_full(void* hip_stream, float* x, const float* eps, float* x0_out, const float* gt, const uint8_t* mask, const float* noise2,
+                          const float* noise1, const float* tail_in, float* tail_out, int32_t B, int32_t frames, int32_t channels, float c1,
+                          float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev, float coef_eps, float sigma, int32_t overlap_len, int32_t blend,
+                          int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi) {
+    API_BEGIN
+    DSH_REQUIRE(x && eps && B > 0 && frames > 0 && channels > 0, "invalid argument");
+    DSH_REQUIRE(!mask || (gt && noise2), "ddim_step: a mask needs gt and noise2");
+    DSH_REQUIRE(overlap_len >= 0 && overlap_len <= frames, "ddim_step: 0 <= overlap_len <= frames");
+    DSH_REQUIRE(!tail_blend || 2 * (int64_t)overlap_len <= frames, "ddim_step: tail_blend needs 2 * overlap_len <= frames");
+    DSH_REQUIRE(c_lo >= 0 && c_hi <= channels, "ddim_step: channel range outside [0, channels]");
+    DSH_REQUIRE(!tail_in || mask, "ddim_step: tail_in replaces the noised gt of a masked step (needs a mask)");
+    dsh::DdimStepArgs a;
+    a.x = x; a.eps = eps; a.x0_out = x0_out; a.c1 = c1; a.c2 = c2; a.sqrt_ab_prev = sqrt_ab_prev; a.sqrt_1m_ab_prev = sqrt_1m_ab_prev;
+    a.coef_eps = coef_eps; a.sigma = sigma; a.noise1 = noise1;
+    a.mask = mask; a.gt = gt; a.noise2 = noise2; a.blend = (mask && blend) ? 1 : 0; a.tail_blend = (a.blend && tail_blend) ? 1 : 0;
+    a.clip = clip; a.overlap_len = overlap_len; a.frames = frames; a.channels = channels; a.n = (size_t)B * frames * channels;
+    a.tail_in = tail_in; a.tail_out = tail_out; a.c_lo = c_lo; a.c_hi = c_hi;
+    return dsh::launch_ddim_step(a, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_ddpm_step(void* hip_stream, float* x, const float* eps, const float* noise, float* x0_out, int64_t n, float c1, float c2, float coef1,
+                     float coef2, float sigma, int32_t clip, int32_t channels, int32_t c_lo, int32_t c_hi) {
+    API_BEGIN
+    DSH_REQUIRE(x && eps && noise && n >= 0, "invalid argument");
+    DSH_REQUIRE(c_hi <= c_lo || (channels > 0 && c_lo >= 0 && c_hi <= channels), "ddpm_step: a channel range needs the channel count and must lie inside it");
+    dsh::DdpmStepArgs a;
+    a.x = x; a.eps = eps; a.noise = noise; a.x0_out = x0_out; a.c1 = c1; a.c2 = c2; a.coef1 = coef1; a.coef2 = coef2; a.sigma = sigma;
+    a.clip = clip; a.n = (size_t)n; a.channels = channels; a.c_lo = c_lo; a.c_hi = c_hi;
+    return dsh::launch_ddpm_step(a, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_undo_step(void* hip_stream, float* x, const float* noise, float sqrt_1m_beta, float sqrt_beta, int64_t n, int32_t channels,
+                     int32_t c_lo, int32_t c_hi) {
+    API_BEGIN
+    DSH_REQUIRE(x && noise && n >= 0, "invalid argument");
+    return dsh::launch_undo_step(x, noise, sqrt_1m_beta, sqrt_beta, (size_t)n, reinterpret_cast<hipStream_t>(hip_stream), channels, c_lo, c_hi);
+    API_END
+}
+
+int dsh_op_level_copy(void* hip_stream, void* const* work_dev, const int64_t* bytes, const int64_t* off, int32_t nseg, void* slots, int64_t stride,
+                      const int64_t* level_dev, int32_t restore) {
+    API_BEGIN
+    DSH_REQUIRE(nseg >= 0 && nseg <= 4 && (nseg == 0 || (work_dev && bytes && off)) && slots && level_dev && stride >= 0, "level_copy: invalid argument");
+    dsh::LevelCopyArgs a{};
+    for (int i = 0; i < nseg; ++i) {
+        DSH_REQUIRE(bytes[i] >= 0 && off[i] >= 0 && off[i] + bytes[i] <= stride && (bytes[i] == 0 || work_dev[i]), "level_copy: a range outside its slot");
+        a.work[i] = reinterpret_cast<char*>(work_dev[i]); a.bytes[i] = (size_t)bytes[i]; a.off[i] = (size_t)off[i];
+    }
+    a.nseg = nseg; a.slots = reinterpret_cast<char*>(slots); a.stride = (size_t)stride; a.level = level_dev; a.restore = restore;
+    return dsh::launch_level_copy(a, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_fill_step(void* hip_stream, int64_t* t, float* c1, float* c2, int64_t* level, int64_t tv, float c1v, float c2v, int64_t lv, int32_t n) {
+    API_BEGIN
+    DSH_REQUIRE(t && c1 && c2 && level && n > 0, "fill_step: invalid argument");
+    return dsh::launch_fill_step(t, c1, c2, level, tv, c1v, c2v, lv, n, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_store_values_f32(void* hip_stream, float* p, const float* host, int32_t n) {
+    API_BEGIN
+    DSH_REQUIRE(p && host && n >= 0, "store_values_f32: invalid argument");
+    return dsh::launch_store_values_f32(p, host, n, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_zero_padded_frames(void* hip_stream, float* x, const int32_t* lens_dev, int32_t B, int32_t frames, int32_t channels) {
+    API_BEGIN
+    return dsh::launch_zero_padded_frames(x, lens_dev, B, frames, channels, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_fill_cols(void* hip_stream, float* dst, int32_t C, int64_t M, int32_t c_lo, int32_t c_hi, const float* src, int32_t src_ld) {
+    API_BEGIN
+    return dsh::launch_fill_cols(dst, C, (size_t)M, c_lo, c_hi, src, src_ld, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_temb(void* hip_stream, int32_t dtype, const int64_t* t_dev, int32_t B, int32_t dim, void* out, int32_t ldo) {
+    API_BEGIN
+    DSH_REQUIRE(t_dev && out && B > 0 && dim >= 2 && dim % 2 == 0 && ldo >= dim && (dtype == 0 || dtype == 1), "temb: invalid argument");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    if (dtype == 0) return dsh::launch_temb_rows<float>(t_dev, B, dim, reinterpret_cast<float*>(out), ldo, s);
+    return dsh::launch_temb_rows<dsh::bf16>(t_dev, B, dim, reinterpret_cast<dsh::bf16*>(out), ldo, s);
+    API_END
+}
+
+int dsh_op_cfg_mix(void* hip_stream, const float* o, int32_t ldo, int32_t Mc, int32_t cond_row0, int32_t frames, int32_t w, int32_t has_null,
+                   const float* scale, int32_t scale_row, float* eps, int32_t lde, int32_t c0, const float* x, int32_t ldx, const float* c1,
+                   const float* c2, float* x0, int32_t ldx0) {
+    API_BEGIN
+    DSH_REQUIRE(o && eps && Mc > 0 && frames > 0 && w > 0 && ldo >= w && c0 >= 0 && lde >= c0 + w, "cfg_mix: invalid argument");
+    DSH_REQUIRE(!has_null || cond_row0 >= Mc, "cfg_mix: the conditional half starts behind the unconditional one");
+    DSH_REQUIRE(!x0 || (x && c1 && c2 && ldx >= c0 + w && ldx0 >= w), "cfg_mix: the x0 branch needs x, c1 and c2");
+    return dsh::launch_cfg_mix(o, ldo, Mc, cond_row0, frames, w, has_null, scale, scale_row, eps, lde, c0, x, ldx, c1, c2, x0, ldx0,
+                               reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_im2col3(void* hip_stream, int32_t dtype_in, int32_t dtype_out, const void* x, int32_t ldx, int32_t B, int32_t frames, int32_t Cin,
+                   void* out, int32_t ldo, const int32_t* lens_dev) {
+    API_BEGIN
+    DSH_REQUIRE(x && out && B > 0 && frames > 0 && Cin > 0 && ldx >= Cin && ldo >= 3 * Cin, "im2col3: invalid argument");
+    DSH_REQUIRE((dtype_in == 0 || dtype_in == 1) && (dtype_out == 0 || dtype_out == 1) && !(dtype_in == 1 && dtype_out == 0),
+                "im2col3: fp32 -> fp32, fp32 -> bf16 or bf16 -> bf16");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    if (dtype_in == 0 && dtype_out == 0)
+        return dsh::launch_im2col3_rows<float, float>(reinterpret_cast<const float*>(x), ldx, B, frames, Cin, reinterpret_cast<float*>(out), ldo, s, lens_dev);
+    if (dtype_in == 0)
+        return dsh::launch_im2col3_rows<float, dsh::bf16>(reinterpret_cast<const float*>(x), ldx, B, frames, Cin, reinterpret_cast<dsh::bf16*>(out), ldo, s, lens_dev);
+    return dsh::launch_im2col3_rows<dsh::bf16, dsh::bf16>(reinterpret_cast<const dsh::bf16*>(x), ldx, B, frames, Cin, reinterpret_cast<dsh::bf16*>(out), ldo, s, lens_dev);
+    API_END
+}
+
+int dsh_op_film_fold(void* hip_stream, float* tab, int32_t ld, int32_t B, int32_t nblk, int32_t D, const float* gamma, const float* beta) {
+    API_BEGIN
+    DSH_REQUIRE(tab && gamma && beta && B > 0 && nblk > 0 && D > 0 && (int64_t)ld >= 2 * (int64_t)D * nblk, "film_fold: invalid argument");
+    return dsh::launch_film_fold(tab, ld, B, nblk, D, gamma, beta, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_film_expand(void* hip_stream, const float* src, int32_t ld, const int32_t* idx_dev, float* dst, int32_t B, int32_t nblk, int32_t D,
+                       const float* gamma, const float* beta, int32_t fold) {
+    API_BEGIN
+    DSH_REQUIRE(src && dst && B > 0 && nblk > 0 && D > 0 && (int64_t)ld >= 2 * (int64_t)D * nblk && (!fold || (gamma && beta)), "film_expand: invalid argument");
+    return dsh::launch_film_expand(src, ld, idx_dev, dst, B, nblk, D, gamma, beta, fold, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_gather_rows(void* hip_stream, const float* src, int32_t ld, const int32_t* idx_dev, float* dst, int32_t ldd, int32_t B, int32_t w) {
+    API_BEGIN
+    DSH_REQUIRE(src && idx_dev && dst && B > 0 && w > 0 && ld >= w && ldd >= w, "gather_rows: invalid argument");
+    return dsh::launch_gather_rows_f32(src, ld, idx_dev, dst, ldd, B, w, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_seed_stream(void* hip_stream, const float* h0, int32_t Mc, int32_t D, const float* c, int32_t has_null, int32_t row1, int32_t hilo,
+                       float* h_out, void* h16_out, void* lo_out) {
+    API_BEGIN
+    DSH_REQUIRE(h0 && h16_out && Mc > 0 && D > 0 && D % 32 == 0 && (hilo ? lo_out != nullptr : h_out != nullptr), "seed_stream: null operand or output");
+    DSH_REQUIRE(!has_null || row1 >= 0, "seed_stream: negative row1");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    OpScratch scratch;
+    // tiled planes: the null half's blocks at row 0, the conditional half's at row1 — rows the kernel does not write come back as 0
+    const int rows = (has_null ? row1 : 0) + dsh::round_up(Mc, 32);
+    void *h = nullptr, *h16 = nullptr, *lo = nullptr;
+    if (int e = scratch.alloc(&h16, (size_t)rows * D * 2)) return e;
+    DSH_HIP_CHECK(hipMemsetAsync(h16, 0, (size_t)rows * D * 2, s));
+    if (hilo) {
+        if (int e = scratch.alloc(&lo, (size_t)rows * D * 2)) return e;
+        DSH_HIP_CHECK(hipMemsetAsync(lo, 0, (size_t)rows * D * 2, s));
+    } else {
+        if (int e = scratch.alloc(&h, (size_t)rows * D * 4)) return e;
+        DSH_HIP_CHECK(hipMemsetAsync(h, 0, (size_t)rows * D * 4, s));
+    }
+    int rc = dsh::launch_seed_stream(h0, Mc, D, c, has_null, row1, reinterpret_cast<float*>(h), h16, s, lo);
+    if (!rc && h) rc = dsh::launch_untile_rows_f32(reinterpret_cast<const float*>(h), D, rows, h_out, D, s);
+    if (!rc) rc = dsh::launch_untile_rows_bf16(h16, D, rows, D, h16_out, D, s);
+    if (!rc && lo) rc = dsh::launch_untile_rows_bf16(lo, D, rows, D, lo_out, D, s);
+    DSH_HIP_CHECK(hipStreamSynchronize(s));
+    return rc;
+    API_END
+}
+
+int dsh_op_pack_expr_track(void* hip_stream, const float* src, int32_t E, int32_t B, int32_t frames, const int32_t* lens_dev, float* x0, int32_t ld,
+                           void* x16_out, void* tiler_out) {
+    API_BEGIN
+    DSH_REQUIRE(src && x0 && B > 0 && frames > 0, "pack_expr_track: invalid argument");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    OpScratch scratch;
+    const int M = B * frames, Mp = dsh::round_up(M, 32);
+    void *x16 = nullptr, *tl = nullptr;
+    if (x16_out) { if (int e = scratch.alloc(&x16, (size_t)Mp * 128 * 2)) return e; }
+    int rc = dsh::launch_pack_expr_track(src, E, B, frames, lens_dev, x0, ld, x16, s);
+    if (!rc && x16) rc = dsh::launch_untile_rows_bf16(x16, 128, M, 128, x16_out, 128, s);
+    if (!rc && tiler_out) {            // the production tiler on the x0 rows just written: what the header promises x16 to equal
+        if (int e = scratch.alloc(&tl, (size_t)Mp * 128 * 2)) return e;
+        rc = dsh::launch_tile_rows_bf16<float>(x0, ld, M, ld, tl, 128, s);
+        if (!rc) rc = dsh::launch_untile_rows_bf16(tl, 128, M, 128, tiler_out, 128, s);
+    }
+    DSH_HIP_CHECK(hipStreamSynchronize(s));
+    return rc;
+    API_END
+}
+
+int dsh_op_layernorm_pre(void* hip_stream, int32_t dtype, float* h, int32_t ldh, int32_t M, int32_t D, const float* pre_add, int32_t n_pre_rows,
+                         const float* gamma, const float* beta, void* out, int32_t ldo) {
+    API_BEGIN
+    DSH_REQUIRE(h && gamma && beta && out && M > 0 && D > 0 && ldh >= D && ldo >= D && (dtype == 0 || dtype == 1), "layernorm_pre: invalid argument");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    if (dtype == 0) return dsh::launch_ln_rows<float>(h, ldh, M, D, pre_add, n_pre_rows, gamma, beta, reinterpret_cast<float*>(out), ldo, s);
+    return dsh::launch_ln_rows<dsh::bf16>(h, ldh, M, D, pre_add, n_pre_rows, gamma, beta, reinterpret_cast<dsh::bf16*>(out), ldo, s);
+    API_END
+}
+
+int dsh_op_ln_film_silu(void* hip_stream, int32_t variant, const void* y, int32_t ldy, int32_t M, int32_t D, const float* gamma, const float* beta,
+                        const float* film, int32_t film_ld, int32_t film_off, int32_t frames, int32_t bmod, void* out, int32_t ldo) {
+    API_BEGIN
+    DSH_REQUIRE(y && gamma && beta && film && out && M > 0 && D > 0 && ldy >= D && ldo >= D && frames > 0 && bmod > 0 && film_off >= 0 &&
+                film_ld >= film_off + 2 * D && variant >= 0 && variant <= 2, "ln_film_silu: invalid argument");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    if (variant == 0)
+        return dsh::launch_ln_film_silu_rows<float, float>(reinterpret_cast<const float*>(y), ldy, M, D, gamma, beta, film, film_ld, film_off, frames, bmod,
+                                                           reinterpret_cast<float*>(out), ldo, s);
+    if (variant == 1)
+        return dsh::launch_ln_film_silu_rows<float, dsh::bf16>(reinterpret_cast<const float*>(y), ldy, M, D, gamma, beta, film, film_ld, film_off, frames, bmod,
+                                                               reinterpret_cast<dsh::bf16*>(out), ldo, s);
+    return dsh::launch_ln_film_silu_rows<dsh::bf16, dsh::bf16>(reinterpret_cast<const dsh::bf16*>(y), ldy, M, D, gamma, beta, film, film_ld, film_off, frames,
+                                                               bmod, reinterpret_cast<dsh::bf16*>(out), ldo, s);
+    API_END
+}
+
+int dsh_op_concat_ln(void* hip_stream, int32_t dtype, const float* p0, int32_t ld0, int32_t w0, const void* p1, int32_t ld1, int32_t w1,
+                     const void* p2, int32_t ld2, int32_t w2, const float* p3, int32_t ld3, int32_t w3, int32_t M, const float* gamma,
+                     const float* beta, void* out, int32_t ldo, int32_t Ppad) {
+    API_BEGIN
+    DSH_REQUIRE(p0 && p1 && p2 && (w3 == 0 || p3) && gamma && beta && out && M > 0 && (dtype == 0 || dtype == 1), "concat_ln: invalid argument");
+    DSH_REQUIRE(w0 > 0 && w1 > 0 && w2 > 0 && w3 >= 0 && ld0 >= w0 && ld1 >= w1 && ld2 >= w2 && ld3 >= w3 && Ppad >= w0 + w1 + w2 + w3 && ldo >= Ppad,
+                "concat_ln: segment widths, leading dimensions and the padded width");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    dsh::ConcatSegs sg{p0, ld0, w0, p1, ld1, w1, p2, ld2, w2, p3, ld3, w3};
+    if (dtype == 0) return dsh::launch_concat_ln_rows<float>(sg, M, gamma, beta, reinterpret_cast<float*>(out), ldo, Ppad, s);
+    return dsh::launch_concat_ln_rows<dsh::bf16>(sg, M, gamma, beta, reinterpret_cast<dsh::bf16*>(out), ldo, Ppad, s);
+    API_END
+}
+
 // ---- validation metrics: FGD pose encoder + per-batch metrics (pose_encoder.hip, metrics.hip) ----------------------
 struct dsh_fgd {
     std::unique_ptr<dsh::FgdEncoder> enc;

@@ -47,6 +47,23 @@ template <typename T> __host__ __device__ inline T from_f32(float x);
 template <> __host__ __device__ inline float from_f32<float>(float x) { return x; }
 template <> __host__ __device__ inline bf16 from_f32<bf16>(float x) { return f32_to_bf16(x); }
 
+// One individually rounded fp32 operation each, for the kernels that promise the bits of an aten op sequence.  The toolchain's
+// __fmul_rn / __fadd_rn / __fsub_rn are plain * + - in its headers, compiled with the device default of contraction on, and the
+// compiler fuses them into FMAs where it sees fit (it did in s + sigma * noise of the DDIM step and in all of the DDPM step); an
+// operation compiled with contraction off is never fused, whatever its neighbours allow.
+__device__ __forceinline__ float rn_mul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float rn_add(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float rn_sub(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
 enum Act : int { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2 };
 
 __device__ inline float silu_f(float x) { return x / (1.0f + expf(-x)); }

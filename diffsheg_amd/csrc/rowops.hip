@@ -285,15 +285,15 @@ __global__ void cfg_mix_kernel(const float* o, int ldo, int cond_row0, int frame
             // (the scale is read behind the two loads, not hoisted in front of them: its latency overlaps theirs)
             asm volatile("" ::: "memory");
             const float cs = scale[(size_t)b * scale_row];
-            e = cs == 1.0f ? k : __fadd_rn(u, __fmul_rn(cs, __fsub_rn(k, u)));
+            e = cs == 1.0f ? k : rn_add(u, rn_mul(cs, rn_sub(k, u)));
         } else {
             e = o[(size_t)row * ldo + c];
         }
         eps[(size_t)row * lde + c0 + c] = e;
         if (x0) {
-            const float a = __fmul_rn(c1[b], x[(size_t)row * ldx + c0 + c]);
-            const float bb = __fmul_rn(c2[b], e);
-            x0[(size_t)row * ldx0 + c] = __fsub_rn(a, bb);
+            const float a = rn_mul(c1[b], x[(size_t)row * ldx + c0 + c]);
+            const float bb = rn_mul(c2[b], e);
+            x0[(size_t)row * ldx0 + c] = rn_sub(a, bb);
         }
     }
 }
@@ -702,7 +702,7 @@ int launch_interp_time(const float* x, int B, int Tin, int C, float* y, int Tout
 __global__ void affine_cols_kernel(const float* x, size_t n, int C, const float* mean, const float* stdv, float* y) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % (size_t)C);
-        y[i] = __fadd_rn(__fmul_rn(x[i], stdv[c]), mean[c]);
+        y[i] = rn_add(rn_mul(x[i], stdv[c]), mean[c]);
     }
 }
 

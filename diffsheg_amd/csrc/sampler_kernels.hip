@@ -6,7 +6,7 @@
 //   undo_step   x <- sqrt(1-beta) x + sqrt(beta) n                   :464-473
 //   ddpm_step   mean = coef1 x0 + coef2 x;  x <- mean + sigma n      :598-600, :747-773
 //
-// Every product / sum is an individually rounded fp32 op (__fmul_rn/__fadd_rn: no FMA contraction),
+// Every product / sum is an individually rounded fp32 op (rn_mul / rn_add / rn_sub of dsh_common.h: compiled with contraction off, so never fused into an FMA),
 // in the reference's operation order, so the update itself is bit-identical to the aten sequence
 // given identical inputs.  Scalars arrive pre-rounded exactly as the reference rounds them
 // (fp64 table -> fp32 at gather, gaussian_diffusion.py:1514; sqrt taken in fp32 where the
@@ -18,11 +18,13 @@
 
 namespace dsh {
 
-// torch.linspace(0, 1, L)[k] in fp32: symmetric formula start + step*k / end - step*(L-1-k)
+// torch.linspace(0, 1, L)[k] in fp32: symmetric formula start + step*k / end - step*(L-1-k).  The second half is ONE rounding in torch
+// (its kernels are built with contraction on: end - step * m is an FMA), so it is an explicit fmaf here; with two roundings
+// the weights differ from torch's at L = 10, 14, 15, 16, 18, ...
 __device__ __forceinline__ float linspace01(int L, int k) {
     if (L == 1) return 0.f;
     const float step = __fdiv_rn(1.0f, (float)(L - 1));
-    return (k < L / 2) ? __fmul_rn(step, (float)k) : __fsub_rn(1.0f, __fmul_rn(step, (float)(L - 1 - k)));
+    return (k < L / 2) ? rn_mul(step, (float)k) : fmaf(-step, (float)(L - 1 - k), 1.0f);
 }
 
 __global__ void ddim_step_kernel(DdimStepArgs a) {
@@ -33,12 +35,12 @@ __global__ void ddim_step_kernel(DdimStepArgs a) {
         if (ranged) { const int cc = (int)(i % (size_t)a.channels); if (cc < a.c_lo || cc >= a.c_hi) continue; }
         const float x = a.x[i];
         const float e = a.eps[i];
-        const float c1x = __fmul_rn(a.c1, x);
-        float x0 = __fsub_rn(c1x, __fmul_rn(a.c2, e));
+        const float c1x = rn_mul(a.c1, x);
+        float x0 = rn_sub(c1x, rn_mul(a.c2, e));
         if (a.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-        const float e2 = __fdiv_rn(__fsub_rn(c1x, x0), a.c2);
-        float s = __fadd_rn(__fmul_rn(x0, a.sqrt_ab_prev), __fmul_rn(a.coef_eps, e2));
-        if (a.noise1) s = __fadd_rn(s, __fmul_rn(a.sigma, a.noise1[i]));
+        const float e2 = __fdiv_rn(rn_sub(c1x, x0), a.c2);
+        float s = rn_add(rn_mul(x0, a.sqrt_ab_prev), rn_mul(a.coef_eps, e2));
+        if (a.noise1) s = rn_add(s, rn_mul(a.sigma, a.noise1[i]));
         if (a.x0_out) a.x0_out[i] = x0;
         const int t = (int)((i % (size_t)tc) / (size_t)a.channels);
         if (a.mask) {
@@ -49,17 +51,17 @@ __global__ void ddim_step_kernel(DdimStepArgs a) {
                 const size_t b = i / (size_t)tc;
                 const int c = (int)(i % (size_t)a.channels);
                 g = t < a.overlap_len ? a.tail_in[(b * a.overlap_len + t) * a.channels + c] : a.gt[i];
-            } else g = __fadd_rn(__fmul_rn(a.sqrt_ab_prev, a.gt[i]), __fmul_rn(a.sqrt_1m_ab_prev, a.noise2[i]));
+            } else g = rn_add(rn_mul(a.sqrt_ab_prev, a.gt[i]), rn_mul(a.sqrt_1m_ab_prev, a.noise2[i]));
             if (a.blend) {
                 const int L = a.overlap_len;
                 if (t < L) {
                     const float w = linspace01(L, t);
-                    g = __fadd_rn(__fmul_rn(g, __fsub_rn(1.0f, w)), __fmul_rn(s, w));
+                    g = rn_add(rn_mul(g, rn_sub(1.0f, w)), rn_mul(s, w));
                 } else if (a.tail_blend && t >= a.frames - L) {
                     // mirrored fade of a window pinned at both ends: the head's weights in reverse order (the same fp32 values),
                     // w'[j] = linspace(0, 1, L)[L - 1 - j], j = t - (frames - L); disjoint from the head's frames (2 L <= frames)
                     const float w = linspace01(L, L - 1 - (t - (a.frames - L)));
-                    g = __fadd_rn(__fmul_rn(g, __fsub_rn(1.0f, w)), __fmul_rn(s, w));
+                    g = rn_add(rn_mul(g, rn_sub(1.0f, w)), rn_mul(s, w));
                 }
             }
             s = a.mask[i] ? g : s;
@@ -89,7 +91,7 @@ __global__ void undo_step_kernel(float* x, const float* noise, float sa, float s
     const bool ranged = c_hi > c_lo;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         if (ranged) { const int cc = (int)(i % (size_t)channels); if (cc < c_lo || cc >= c_hi) continue; }
-        x[i] = __fadd_rn(__fmul_rn(sa, x[i]), __fmul_rn(sb, noise[i]));
+        x[i] = rn_add(rn_mul(sa, x[i]), rn_mul(sb, noise[i]));
     }
 }
 int launch_undo_step(float* x, const float* noise, float sqrt_1m_beta, float sqrt_beta, size_t n, hipStream_t s, int channels, int c_lo, int c_hi) {
@@ -105,12 +107,12 @@ __global__ void ddpm_step_kernel(DdpmStepArgs a) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
         if (ranged) { const int cc = (int)(i % (size_t)a.channels); if (cc < a.c_lo || cc >= a.c_hi) continue; }
         const float x = a.x[i];
-        float x0 = __fsub_rn(__fmul_rn(a.c1, x), __fmul_rn(a.c2, a.eps[i]));
+        float x0 = rn_sub(rn_mul(a.c1, x), rn_mul(a.c2, a.eps[i]));
         if (a.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-        const float mean = __fadd_rn(__fmul_rn(a.coef1, x0), __fmul_rn(a.coef2, x));
+        const float mean = rn_add(rn_mul(a.coef1, x0), rn_mul(a.coef2, x));
         if (a.x0_out) a.x0_out[i] = x0;
         // reference: mean + nonzero_mask * exp(0.5*logvar) * noise  (left-to-right products)
-        a.x[i] = __fadd_rn(mean, __fmul_rn(a.sigma, a.noise[i]));
+        a.x[i] = rn_add(mean, rn_mul(a.sigma, a.noise[i]));
     }
 }
 int launch_ddpm_step(const DdpmStepArgs& a, hipStream_t s) {

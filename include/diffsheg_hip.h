@@ -372,6 +372,84 @@ int dsh_op_philox_randn(void* hip_stream, float* out, int64_t n, uint64_t seed, 
 int dsh_op_philox_randn_rows(void* hip_stream, float* out, int32_t rows, int64_t n_row, uint64_t seed, uint64_t offset,
                              const uint64_t* row_keys_host);
 
+/* ---- one entry per small kernel of the sampler and around the denoiser (test helpers) --------------------------------------------
+ * Device pointers in natural row-major order unless a name ends in _host; tiled results are read back through the library's own
+ * untile launches into row-major buffers; nothing is cached.  Asynchronous on hip_stream unless stated.  -1 on a refused argument. */
+/* dsh_op_philox_randn_rows with the ragged form the sampling loop uses: row_lens_host (nullable, [rows]) and channels > 0 make row b
+ * advance by row_lens_host[b] * channels / 4 counters per draw (counter = draw * that + quad inside the row; `offset` is then unused).
+ * Refuses a length whose row_lens * channels exceeds n_row.  Synchronises the stream. */
+int dsh_op_philox_randn_rows_ragged(void* hip_stream, float* out, int32_t rows, int64_t n_row, uint64_t seed, uint64_t offset,
+                                    const uint64_t* row_keys_host, const int32_t* row_lens_host, uint64_t draw, int32_t channels);
+/* dsh_op_ddim_step with every field of the step: x0_out (nullable) receives pred_xstart; coef_eps multiplies the re-derived eps and
+ * sigma * noise1 is added when noise1 != NULL (the eta branch; eta = 0: coef_eps = sqrt_1m_ab_prev, noise1 = NULL); tail_in / tail_out
+ * [B, overlap_len, channels] (nullable) are the saved noisy tail of --same_overlap_noisy.  Refusals of dsh_op_ddim_step, and tail_in
+ * without a mask. */
+int dsh_op_ddim_step_full(void* hip_stream, float* x, const float* eps, float* x0_out, const float* gt, const uint8_t* mask, const float* noise2,
+                          const float* noise1, const float* tail_in, float* tail_out, int32_t B, int32_t frames, int32_t channels, float c1,
+                          float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev, float coef_eps, float sigma, int32_t overlap_len, int32_t blend,
+                          int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi);
+/* x0 = c1 x - c2 eps (clamped when clip); x <- coef1 x0 + coef2 x + sigma noise on n values; [c_lo, c_hi) of `channels` restricts the
+ * update (c_hi <= c_lo: all); x0_out nullable. */
+int dsh_op_ddpm_step(void* hip_stream, float* x, const float* eps, const float* noise, float* x0_out, int64_t n, float c1, float c2, float coef1,
+                     float coef2, float sigma, int32_t clip, int32_t channels, int32_t c_lo, int32_t c_hi);
+/* x <- sqrt_1m_beta x + sqrt_beta noise; a channel range needs the channel count. */
+int dsh_op_undo_step(void* hip_stream, float* x, const float* noise, float sqrt_1m_beta, float sqrt_beta, int64_t n, int32_t channels,
+                     int32_t c_lo, int32_t c_hi);
+/* Timestep-cache copy: nseg <= 4 byte ranges (host arrays: device pointers work_dev[i], bytes[i], off[i]; multiples of 16) between the work
+ * buffers and slots + *level_dev * stride + off[i]; restore 0 saves, 1 restores.  Refuses a range that leaves its slot. */
+int dsh_op_level_copy(void* hip_stream, void* const* work_dev, const int64_t* bytes, const int64_t* off, int32_t nseg, void* slots, int64_t stride,
+                      const int64_t* level_dev, int32_t restore);
+/* t[0, n) = tv, c1[0, n) = c1v, c2[0, n) = c2v, *level = lv in one launch. */
+int dsh_op_fill_step(void* hip_stream, int64_t* t, float* c1, float* c2, int64_t* level, int64_t tv, float c1v, float c2v, int64_t lv, int32_t n);
+/* p[0, n) = host[0, n) in stream order (64 values per launch travel as kernel arguments). */
+int dsh_op_store_values_f32(void* hip_stream, float* p, const float* host, int32_t n);
+/* x[b, t, :] = 0 for t >= lens_dev[b]; x [B, frames, channels]. */
+int dsh_op_zero_padded_frames(void* hip_stream, float* x, const int32_t* lens_dev, int32_t B, int32_t frames, int32_t channels);
+/* columns [c_lo, c_hi) of dst [M, C] <- the first c_hi - c_lo columns of src [M, src_ld], or 0 when src is NULL. */
+int dsh_op_fill_cols(void* hip_stream, float* dst, int32_t C, int64_t M, int32_t c_lo, int32_t c_hi, const float* src, int32_t src_ld);
+/* timestep_embedding (models/transformer.py:42-59): out[b, :dim] = (cos(t_b f_j) | sin(t_b f_j)), f_j = exp(-ln(1e4) j / (dim / 2)) in fp32;
+ * t_dev int64 [B]; dtype 0: fp32 out, 1: bf16 out (uint16 bits); ldo >= dim. */
+int dsh_op_temb(void* hip_stream, int32_t dtype, const int64_t* t_dev, int32_t B, int32_t dim, void* out, int32_t ldo);
+/* classifier-free mix: eps[r, c0 + c] = u + s_b (k - u), u = o[r, c], k = o[r + cond_row0, c], s_b = scale[b * scale_row], b = r / frames
+ * (s_b == 1: k itself; has_null == 0: a copy of o[r, c]), r < Mc, c < w; x0 (nullable) [Mc, ldx0] = c1[b] x[r, c0 + c] - c2[b] eps. */
+int dsh_op_cfg_mix(void* hip_stream, const float* o, int32_t ldo, int32_t Mc, int32_t cond_row0, int32_t frames, int32_t w, int32_t has_null,
+                   const float* scale, int32_t scale_row, float* eps, int32_t lde, int32_t c0, const float* x, int32_t ldx, const float* c1,
+                   const float* c2, float* x0, int32_t ldx0);
+/* Conv1d(k = 3, padding = 1) patches: out[(b, t), tap * Cin + c] = x[b, t + tap - 1, c], zero outside [0, len_b); lens_dev nullable (len_b =
+ * frames).  dtype 0 fp32 / 1 bf16: fp32 -> fp32, fp32 -> bf16, bf16 -> bf16. */
+int dsh_op_im2col3(void* hip_stream, int32_t dtype_in, int32_t dtype_out, const void* x, int32_t ldx, int32_t B, int32_t frames, int32_t Cin,
+                   void* out, int32_t ldo, const int32_t* lens_dev);
+/* FiLM rows [scale(D) | shift(D)] x nblk per clip -> [A | B], A = gamma (1 + scale), B = beta (1 + scale) + shift; gamma / beta [nblk, D].
+ * film_fold: in place on tab [B, ld].  film_expand: dst[b] = fold(src[idx_dev[b]]) (idx_dev NULL: identity; fold 0: plain copy); D % 4 == 0. */
+int dsh_op_film_fold(void* hip_stream, float* tab, int32_t ld, int32_t B, int32_t nblk, int32_t D, const float* gamma, const float* beta);
+int dsh_op_film_expand(void* hip_stream, const float* src, int32_t ld, const int32_t* idx_dev, float* dst, int32_t B, int32_t nblk, int32_t D,
+                       const float* gamma, const float* beta, int32_t fold);
+/* dst[b, :w] = src[idx_dev[b], :w]. */
+int dsh_op_gather_rows(void* hip_stream, const float* src, int32_t ld, const int32_t* idx_dev, float* dst, int32_t ldd, int32_t B, int32_t w);
+/* Layer-0 seed of the residual stream from h0 [Mc, D]: rows [0, Mc) = h0 + c (has_null) or h0, rows [row1, row1 + Mc) = h0 (has_null; row1 a
+ * multiple of 32, >= Mc).  Outputs row-major [R, D], R = (has_null ? row1 : 0) + round_up(Mc, 32); rows the kernel does not write come back
+ * as 0.  hilo 0: h_out fp32 and h16_out = bf16(h); hilo 1: h16_out = hi plane, lo_out = bf16(h - hi), h_out untouched.  Synchronises. */
+int dsh_op_seed_stream(void* hip_stream, const float* h0, int32_t Mc, int32_t D, const float* c, int32_t has_null, int32_t row1, int32_t hilo,
+                       float* h_out, void* h16_out, void* lo_out);
+/* Given expression track src [B frames, E] -> x0 [B frames, ld] (pad columns zero; frames >= lens_dev[b] zero) and, x16_out != NULL, the bf16
+ * operand [B frames, 128] read back row-major; tiler_out (nullable, same shape): the library's bf16 tiler applied to the x0 rows just
+ * written, which x16_out is documented to equal bit for bit.  E <= ld <= 128.  Synchronises. */
+int dsh_op_pack_expr_track(void* hip_stream, const float* src, int32_t E, int32_t B, int32_t frames, const int32_t* lens_dev, float* x0, int32_t ld,
+                           void* x16_out, void* tiler_out);
+/* ln_rows with its constant fold: h[r] += pre_add for r < n_pre_rows (h in/out; pre_add nullable), out = LayerNorm(h) gamma + beta;
+ * dtype 0 fp32 / 1 bf16 output. */
+int dsh_op_layernorm_pre(void* hip_stream, int32_t dtype, float* h, int32_t ldh, int32_t M, int32_t D, const float* pre_add, int32_t n_pre_rows,
+                         const float* gamma, const float* beta, void* out, int32_t ldo);
+/* StylizationBlock front on rows: out = SiLU(LN(y) (1 + scale) + shift), (scale | shift) = film[(r / frames) % bmod, film_off ..];
+ * variant 0: fp32 -> fp32, 1: fp32 -> bf16, 2: bf16 -> bf16. */
+int dsh_op_ln_film_silu(void* hip_stream, int32_t variant, const void* y, int32_t ldy, int32_t M, int32_t D, const float* gamma, const float* beta,
+                        const float* film, int32_t film_ld, int32_t film_off, int32_t frames, int32_t bmod, void* out, int32_t ldo);
+/* LayerNorm over the virtual concat row [p0 (fp32, w0) | p1 (w1) | p2 (w2) | p3 (fp32, w3, may be 0)]; p1 / p2 and out have the element type
+ * of dtype (0 fp32 / 1 bf16); columns [P, Ppad) of out are written as zero. */
+int dsh_op_concat_ln(void* hip_stream, int32_t dtype, const float* p0, int32_t ld0, int32_t w0, const void* p1, int32_t ld1, int32_t w1,
+                     const void* p2, int32_t ld2, int32_t w2, const float* p3, int32_t ld3, int32_t w3, int32_t M, const float* gamma,
+                     const float* beta, void* out, int32_t ldo, int32_t Ppad);
+
 /* ---- validation metrics (trainers/ddpm_show_trainer.py:440-583, ddpm_beat_trainer.py:489-644) ------------------------- */
 /* The FGD pose encoder: HalfEmbeddingNet.forward = PoseEncoderConv in eval() mode (models/motion_autoencoder.py:38-100, 192-204), fp32 on
  * the exact-fp32 matrix pipe.  A handle of its own, independent of a dsh_ctx context (an eval model is another network with other weights), bound

@@ -33,6 +33,7 @@ def test_inv_standardize_and_split():
     mean, std = torch.randn(232, generator=g), torch.rand(232, generator=g) + 0.5
     got = inv_standardize(x.cuda(), mean, std).cpu()
     assert torch.allclose(got, x * std + mean, rtol=1e-6, atol=1e-6)
+    assert torch.equal(got, x * std + mean)                   # two rounded fp32 ops, as torch evaluates it: not one fused multiply-add
     ges, exp = split_motion(got, 129)
     assert ges.shape[-1] == 129 and exp.shape[-1] == 103
 
