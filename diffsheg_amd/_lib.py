@@ -61,6 +61,7 @@ SYMBOLS = {
     "dsh_sample_num_steps": (C.c_int64, [C.POINTER(SamplerOptsC), C.c_int32]),
     "dsh_sample": (C.c_int, [_P, C.POINTER(SamplerOptsC), _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int64, _P]),
     "dsh_sample_set_row_keys": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int32]),
+    "dsh_sample_set_row_seeds": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int32]),
     "dsh_sample_set_tail_blend": (C.c_int, [_P, C.c_int32]),
     "dsh_set_guidance_scale": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32]),
     "dsh_diffusion_table": (C.c_int32, [C.c_int32, C.c_int32, C.c_char_p, C.POINTER(C.c_double), C.c_int32]),
@@ -89,6 +90,11 @@ SYMBOLS = {
     "dsh_op_philox_randn_rows": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "dsh_op_philox_randn_rows_ragged": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
                                                   C.c_uint64, C.c_int32]),
+    "dsh_op_philox_randn_rows_seeded": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), _P]),
+    "dsh_op_philox_randn_rows_ragged_seeded": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
+                                                         C.POINTER(C.c_int32), C.c_uint64, C.c_int32, _P]),
+    "dsh_op_chain_handoff": (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32), _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "dsh_op_chain_save_tail": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P, C.POINTER(C.c_int32), _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     "dsh_op_ddim_step_full": (C.c_int, [_P] * 10 + [C.c_int32] * 3 + [C.c_float] * 6 + [C.c_int32] * 6),
     "dsh_op_ddpm_step": (C.c_int, [_P] * 5 + [C.c_int64] + [C.c_float] * 5 + [C.c_int32] * 4),
     "dsh_op_undo_step": (C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),

@@ -276,6 +276,13 @@ int dsh_sample_set_row_keys(dsh_ctx* ctx, const uint64_t* keys_host, int32_t n) 
     API_END
 }
 
+int dsh_sample_set_row_seeds(dsh_ctx* ctx, const uint64_t* seeds_host, int32_t n) {
+    API_BEGIN
+    DSH_REQUIRE(ctx, "null context");
+    return ctx->sampler->set_row_seeds(seeds_host, n);
+    API_END
+}
+
 int dsh_sample_set_tail_blend(dsh_ctx* ctx, int32_t on) {
     API_BEGIN
     DSH_REQUIRE(ctx, "null context");
@@ -1017,6 +1024,66 @@ int dsh_op_philox_randn_rows_ragged(void* hip_stream, float* out, int32_t rows, 
                                                  reinterpret_cast<const int*>(ld), draw, channels);
     DSH_HIP_CHECK(hipStreamSynchronize(s));          // the scratch arrays are released on return
     return rc;
+    API_END
+}
+
+int dsh_op_philox_randn_rows_seeded(void* hip_stream, float* out, int32_t rows, int64_t n_row, uint64_t seed, uint64_t offset,
+                                    const uint64_t* row_keys_host, const uint64_t* row_seeds_dev) {
+    return dsh_op_philox_randn_rows_ragged_seeded(hip_stream, out, rows, n_row, seed, offset, row_keys_host, nullptr, 0, 0, row_seeds_dev);
+}
+
+int dsh_op_philox_randn_rows_ragged_seeded(void* hip_stream, float* out, int32_t rows, int64_t n_row, uint64_t seed, uint64_t offset,
+                                           const uint64_t* row_keys_host, const int32_t* row_lens_host, uint64_t draw, int32_t channels,
+                                           const uint64_t* row_seeds_dev) {
+    API_BEGIN
+    DSH_REQUIRE(out && rows > 0 && n_row > 0 && row_keys_host, "invalid argument");
+    if (row_lens_host)
+        for (int b = 0; b < rows; ++b)
+            DSH_REQUIRE(row_lens_host[b] >= 0 && channels > 0 && (int64_t)row_lens_host[b] * channels <= n_row, "philox_randn_rows_ragged_seeded: a row length outside its row");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    OpScratch scratch;
+    void *kd = nullptr, *ld = nullptr;
+    if (int e = scratch.upload(&kd, row_keys_host, (size_t)rows * sizeof(uint64_t))) return e;
+    if (row_lens_host) { if (int e = scratch.upload(&ld, row_lens_host, (size_t)rows * sizeof(int32_t))) return e; }
+    const int rc = dsh::launch_philox_randn_rows(out, rows, (size_t)n_row, seed, offset, reinterpret_cast<const uint64_t*>(kd), s,
+                                                 reinterpret_cast<const int*>(ld), draw, channels, row_seeds_dev);
+    DSH_HIP_CHECK(hipStreamSynchronize(s));          // the scratch arrays are released on return
+    return rc;
+    API_END
+}
+
+// ---- window hand-off of live chains (streaming.py: StreamPool) ----------------------------------
+namespace {
+// the host copy of a slot index list: every entry inside the table and, where rows are written, no slot twice
+int check_slots(const int32_t* slot_idx_host, int32_t R, int32_t S, bool distinct, const char* what) {
+    DSH_REQUIRE(R == 0 || slot_idx_host, std::string(what) + ": the host copy of the slot indices is required");
+    for (int r = 0; r < R; ++r) {
+        DSH_REQUIRE(slot_idx_host[r] >= 0 && slot_idx_host[r] < S, std::string(what) + ": slot index outside the table");
+        if (distinct)
+            for (int q = 0; q < r; ++q) DSH_REQUIRE(slot_idx_host[q] != slot_idx_host[r], std::string(what) + ": a slot is written twice");
+    }
+    return 0;
+}
+}  // namespace
+
+int dsh_op_chain_handoff(void* hip_stream, const float* tails, int32_t S, const int32_t* slot_idx_host, const int32_t* slot_idx_dev,
+                         int32_t R, int32_t T, int32_t L, int32_t C, float* gt, uint8_t* mask) {
+    API_BEGIN
+    DSH_REQUIRE(R >= 0 && S > 0, "chain_handoff: invalid argument");
+    if (int e = check_slots(slot_idx_host, R, S, false, "chain_handoff")) return e;
+    return dsh::launch_chain_handoff(tails, S, slot_idx_dev, R, T, L, C, gt, mask, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_chain_save_tail(void* hip_stream, const float* x, const int32_t* lens_host, const int32_t* lens_dev, const int32_t* slot_idx_host,
+                           const int32_t* slot_idx_dev, int32_t R, int32_t T, int32_t L, int32_t C, float* tails, int32_t S) {
+    API_BEGIN
+    DSH_REQUIRE(R >= 0 && S > 0, "chain_save_tail: invalid argument");
+    DSH_REQUIRE((lens_host == nullptr) == (lens_dev == nullptr), "chain_save_tail: per-row lengths need their host and their device copy");
+    if (int e = check_slots(slot_idx_host, R, S, true, "chain_save_tail")) return e;
+    if (lens_host)
+        for (int r = 0; r < R; ++r) DSH_REQUIRE(lens_host[r] >= L && lens_host[r] <= T, "chain_save_tail: a row length outside overlap_len .. frames");
+    return dsh::launch_chain_save_tail(x, lens_dev, slot_idx_dev, S, R, T, L, C, tails, reinterpret_cast<hipStream_t>(hip_stream));
     API_END
 }
 

@@ -261,6 +261,11 @@ int launch_philox_randn(float* out, size_t n, uint64_t seed, uint64_t offset, hi
 // row_lens (device, nullable): ragged rows — row b advances by row_lens[b] * channels / 4 counters per draw instead of `offset`
 int launch_zero_padded_frames(float* x, const int* lens, int B, int frames, int channels, hipStream_t s);
 int launch_philox_randn_rows(float* out, int rows, size_t n_row, uint64_t seed, uint64_t offset, const uint64_t* row_keys,
-                             hipStream_t s, const int* row_lens = nullptr, uint64_t draw = 0, int channels = 0);
+                             hipStream_t s, const int* row_lens = nullptr, uint64_t draw = 0, int channels = 0,
+                             const uint64_t* row_seeds = nullptr);      // (device, nullable: row b's Philox key in place of `seed`)
+// window hand-off of live chains on a slot table tails [S, L, C]: gt [R, T, C] <- (tails[slot_idx[r]] | 0), mask [R, T, C] <- (1 | 0) ...
+int launch_chain_handoff(const float* tails, int S, const int* slot_idx, int R, int T, int L, int C, float* gt, uint8_t* mask, hipStream_t s);
+// ... and tails[slot_idx[r]] <- the last L valid frames of x [R, T, C] (lens nullable: every row has T).  slot_idx / lens: device arrays.
+int launch_chain_save_tail(const float* x, const int* lens, const int* slot_idx, int S, int R, int T, int L, int C, float* tails, hipStream_t s);
 
 }  // namespace dsh

@@ -37,6 +37,11 @@ class Sampler {
     // Philox mode: per-row keys (one per batch row; empty = one stream for the whole batch).  A chain keyed by its
     // global id draws the same noise whatever batch / rank it is sampled in (sharded long-audio path).
     int set_row_keys(const uint64_t* keys_host, int n);
+    // Philox mode, beside the row keys: row b draws from the key seeds_host[b] in place of SamplerOpts.seed (every draw of run(): x_T,
+    // the steps' randn_like, the RePaint blend's gt noise, the undo steps, the eta scratch; main chain and gesture-side twin alike), so
+    // rows of one batch may stand at different windows of their chains.  Needs the row keys set and n equal to their count (-1 before
+    // any state changes otherwise); sticky like the keys, n = 0 clears it, and so does every set_row_keys (the seeds belong to that key set).
+    int set_row_seeds(const uint64_t* seeds_host, int n);
     // windows pinned at both ends (in-betweening / seam repair): the DDIM step's cross-fade also runs, mirrored, on the last
     // overlap_len frames (sampler_kernels.hip).  Sticky like the row keys; 0 = the reference's head-only fade.
     void set_tail_blend(int on) { tail_blend = on != 0; }
@@ -54,6 +59,7 @@ class Sampler {
     int64_t* tbuf = nullptr; int64_t* lvlbuf = nullptr;
     DiffusionTables tb; int tb_steps = -1, tb_resp = -1;
     uint64_t* row_keys = nullptr; int n_row_keys = 0, cap_row_keys = 0;
+    uint64_t* row_seeds = nullptr; int n_row_seeds = 0, cap_row_seeds = 0;
     bool tail_blend = false;
     // --same_overlap_noisy: the noisy tail x[..., -L:, :] saved after every DDIM step, one slot per spaced level; persists
     // across sample() calls like the reference's self.saved_noisy_tail (the dict the next window receives IS this object)

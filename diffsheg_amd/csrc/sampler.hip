@@ -136,6 +136,7 @@ Sampler::~Sampler() {
     for (hipEvent_t e : ev_sub) (void)hipEventDestroy(e);
     for (void* p : bufs) (void)hipFree(p);
     if (row_keys) (void)hipFree(row_keys);
+    if (row_seeds) (void)hipFree(row_seeds);
     if (tails) (void)hipFree(tails);
     if (tail_tmp) (void)hipFree(tail_tmp);
     if (nz_eta) (void)hipFree(nz_eta);
@@ -144,6 +145,7 @@ Sampler::~Sampler() {
 int Sampler::set_row_keys(const uint64_t* keys_host, int n) {
     DSH_REQUIRE(n >= 0 && (n == 0 || keys_host), "set_row_keys: null key array");
     n_row_keys = 0;
+    n_row_seeds = 0;               // (per-row seeds belong to the key set they were given for)
     if (n == 0) return 0;
     if (n > cap_row_keys) {
         DSH_HIP_CHECK(hipStreamSynchronize(st));
@@ -155,6 +157,24 @@ int Sampler::set_row_keys(const uint64_t* keys_host, int n) {
     DSH_HIP_CHECK(hipMemcpyAsync(row_keys, keys_host, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     DSH_HIP_CHECK(hipStreamSynchronize(st));       // keys_host is pageable caller memory
     n_row_keys = n;
+    return 0;
+}
+
+int Sampler::set_row_seeds(const uint64_t* seeds_host, int n) {
+    DSH_REQUIRE(n >= 0 && (n == 0 || seeds_host), "set_row_seeds: null seed array");
+    DSH_REQUIRE(n == 0 || (n_row_keys > 0 && n == n_row_keys), "set_row_seeds: needs the row keys set first, and one seed per row key");
+    n_row_seeds = 0;
+    if (n == 0) return 0;
+    if (n > cap_row_seeds) {
+        DSH_HIP_CHECK(hipStreamSynchronize(st));
+        if (row_seeds) (void)hipFree(row_seeds);
+        row_seeds = nullptr; cap_row_seeds = 0;
+        DSH_HIP_CHECK(hipMalloc((void**)&row_seeds, (size_t)n * sizeof(uint64_t)));
+        cap_row_seeds = n;
+    }
+    DSH_HIP_CHECK(hipMemcpyAsync(row_seeds, seeds_host, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    DSH_HIP_CHECK(hipStreamSynchronize(st));       // seeds_host is pageable caller memory
+    n_row_seeds = n;
     return 0;
 }
 
@@ -302,6 +322,7 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
     DSH_REQUIRE(n_row_keys == 0 || o.noise_mode != 1 || (n_row_keys == B && (n / B) % 4 == 0),
                 "row keys were set for a different batch size (or frames*channels is not a multiple of 4)");
     const bool per_row = o.noise_mode == 1 && n_row_keys == B;
+    const uint64_t* seeds_d = (per_row && n_row_seeds == B) ? row_seeds : nullptr;      // (set_row_seeds: always the row keys' count)
     // --same_overlap_noisy state
     const size_t blc = (size_t)B * o.overlap_len * channels;
     const bool son = o.same_overlap_noisy != 0 && o.kind == 0;
@@ -351,7 +372,8 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
         if (o.noise_mode == 0) { *out = noise_stack + (size_t)idx * n + u.off; return 0; }
         // (ragged: every row advances by its own size per draw, so a clip draws the same noise padded as sampled alone)
         if (per_row) { if (int e = launch_philox_randn_rows(scratch + u.off, u.nb, row_n, o.seed, (uint64_t)idx * quads, row_keys + u.b0, u.s,
-                                                            len_d ? len_d + u.b0 : nullptr, (uint64_t)idx, channels)) return e; }
+                                                            len_d ? len_d + u.b0 : nullptr, (uint64_t)idx, channels,
+                                                            seeds_d ? seeds_d + u.b0 : nullptr)) return e; }
         else if (int e = launch_philox_randn(scratch + u.off, u.cnt, o.seed, (uint64_t)idx * quads + u.off / 4, u.s)) return e;
         *out = scratch + u.off;
         return 0;

@@ -209,15 +209,19 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint
 // row_lens != null (ragged batch, with row_keys): row b holds row_lens[b] valid frames of `channels` values in front of its padding and
 // advances by ITS OWN size per draw — counter = draw * (row_lens[b] * channels / 4) + quad index inside the row — which is the stream the
 // clip draws from when it is sampled alone at that length.  (Padded positions run on into the next draw's counters; nothing reads them.)
+// row_seeds != null (with row_keys): row b uses the Philox key row_seeds[b] in place of `seed`; counter and row key as above — rows of one
+// batch may then stand at different windows of their chains (key = hash(base seed, window index), live sessions batched together).
 __global__ void philox_randn_kernel(float* out, size_t n, uint64_t seed, uint64_t offset, const uint64_t* __restrict__ row_keys,
-                                    size_t row_quads, const int* __restrict__ row_lens, uint64_t draw, int channels) {
+                                    size_t row_quads, const int* __restrict__ row_lens, uint64_t draw, int channels,
+                                    const uint64_t* __restrict__ row_seeds) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const size_t nquad = (n + 3) / 4;
     for (size_t qd = (size_t)blockIdx.x * blockDim.x + threadIdx.x; qd < nquad; qd += stride) {
         uint64_t ctr = offset + qd, rk = 0;
-        const uint64_t key = seed;
+        uint64_t key = seed;
         if (row_keys) {
             const size_t b = qd / row_quads;
+            if (row_seeds) key = row_seeds[b];
             ctr = (row_lens ? draw * ((uint64_t)row_lens[b] * (uint64_t)channels / 4) : offset) + (qd - b * row_quads);
             rk = row_keys[b];
         }
@@ -249,16 +253,16 @@ __global__ void philox_randn_kernel(float* out, size_t n, uint64_t seed, uint64_
 }
 int launch_philox_randn(float* out, size_t n, uint64_t seed, uint64_t offset, hipStream_t s) {
     hipLaunchKernelGGL(philox_randn_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, s, out, n, seed, offset,
-                       (const uint64_t*)nullptr, (size_t)1, (const int*)nullptr, (uint64_t)0, 0);
+                       (const uint64_t*)nullptr, (size_t)1, (const int*)nullptr, (uint64_t)0, 0, (const uint64_t*)nullptr);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }
 int launch_philox_randn_rows(float* out, int rows, size_t n_row, uint64_t seed, uint64_t offset, const uint64_t* row_keys,
-                             hipStream_t s, const int* row_lens, uint64_t draw, int channels) {
+                             hipStream_t s, const int* row_lens, uint64_t draw, int channels, const uint64_t* row_seeds) {
     DSH_REQUIRE(rows > 0 && n_row % 4 == 0 && row_keys, "philox_randn_rows: row length must be a multiple of 4");
     DSH_REQUIRE(!row_lens || channels > 0, "philox_randn_rows: per-row lengths need the channel count");
     const size_t n = (size_t)rows * n_row;
-    hipLaunchKernelGGL(philox_randn_kernel, dim3(grid_for(n / 4)), dim3(256), 0, s, out, n, seed, offset, row_keys, n_row / 4, row_lens, draw, channels);
+    hipLaunchKernelGGL(philox_randn_kernel, dim3(grid_for(n / 4)), dim3(256), 0, s, out, n, seed, offset, row_keys, n_row / 4, row_lens, draw, channels, row_seeds);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -275,6 +279,57 @@ int launch_zero_padded_frames(float* x, const int* lens, int B, int frames, int 
     DSH_REQUIRE(x && lens && B > 0 && frames > 0 && channels > 0, "zero_padded_frames: invalid argument");
     const size_t n = (size_t)B * frames * channels;
     hipLaunchKernelGGL(zero_padded_frames_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, lens, n, frames, channels);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- window hand-off of live chains on a slot table tails[S, L, C] (fp32): row r of a window batch belongs to slot slot_idx[r] ----
+// (the host refuses an index outside [0, S) and a length outside [L, T] before the launch; the kernels skip such a row all the same,
+//  so that no address outside the table or the window is ever formed)
+// gt[r, :L] = tails[slot_idx[r]], gt[r, L:] = 0; mask[r, :L] = 1, mask[r, L:] = 0: the inpaint dictionary of a chained window
+__global__ void chain_handoff_kernel(const float* __restrict__ tails, const int* __restrict__ slot_idx, int S, size_t n, int T, int L, int C,
+                                     float* __restrict__ gt, uint8_t* __restrict__ mask) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x, row_n = (size_t)T * C;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const size_t r = i / row_n, in_row = i - r * row_n;
+        const int t = (int)(in_row / C), c = (int)(in_row - (size_t)t * C);
+        const int slot = slot_idx[r];
+        const bool head = t < L;
+        float g = 0.f;
+        if (head && slot >= 0 && slot < S) g = tails[((size_t)slot * L + t) * C + c];
+        gt[i] = g;
+        mask[i] = head ? 1 : 0;
+    }
+}
+int launch_chain_handoff(const float* tails, int S, const int* slot_idx, int R, int T, int L, int C, float* gt, uint8_t* mask, hipStream_t s) {
+    DSH_REQUIRE(R >= 0 && S > 0 && C > 0, "chain_handoff: invalid argument");
+    DSH_REQUIRE(L >= 1 && L < T, "chain_handoff: needs 1 <= overlap_len < frames");
+    if (R == 0) return 0;
+    DSH_REQUIRE(tails && slot_idx && gt && mask, "chain_handoff: null pointer");
+    const size_t n = (size_t)R * T * C;
+    hipLaunchKernelGGL(chain_handoff_kernel, dim3(grid_for(n)), dim3(256), 0, s, tails, slot_idx, S, n, T, L, C, gt, mask);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+// tails[slot_idx[r]] = x[r, n_r - L : n_r], n_r = lens[r] (ragged batch) or T
+__global__ void chain_save_tail_kernel(const float* __restrict__ x, const int* __restrict__ lens, const int* __restrict__ slot_idx, int S, size_t n,
+                                       int T, int L, int C, float* __restrict__ tails) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x, row_n = (size_t)L * C;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const size_t r = i / row_n, in_row = i - r * row_n;
+        const int slot = slot_idx[r];
+        const int nr = lens ? lens[r] : T;
+        if (slot < 0 || slot >= S || nr < L || nr > T) continue;
+        tails[(size_t)slot * row_n + in_row] = x[(r * T + (size_t)(nr - L)) * C + in_row];
+    }
+}
+int launch_chain_save_tail(const float* x, const int* lens, const int* slot_idx, int S, int R, int T, int L, int C, float* tails, hipStream_t s) {
+    DSH_REQUIRE(R >= 0 && S > 0 && C > 0, "chain_save_tail: invalid argument");
+    DSH_REQUIRE(L >= 1 && L < T, "chain_save_tail: needs 1 <= overlap_len < frames");
+    if (R == 0) return 0;
+    DSH_REQUIRE(x && slot_idx && tails, "chain_save_tail: null pointer");
+    const size_t n = (size_t)R * L * C;
+    hipLaunchKernelGGL(chain_save_tail_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, lens, slot_idx, S, n, T, L, C, tails);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -14,7 +14,9 @@ Differences a caller can observe, all loud:
     the reference's draw order — this is how parity tests inject identical noise) or, if None, from the
     on-device Philox generator seeded by ``seed`` / ``torch.initial_seed()``; ``row_keys`` (one integer per
     batch row) additionally gives every row its own Philox stream, so that a chain draws the same noise in
-    whatever batch / on whatever rank it is sampled (the sharded long-audio path);
+    whatever batch / on whatever rank it is sampled (the sharded long-audio path); ``row_seeds`` (with ``row_keys``, one integer
+    per batch row) gives every row its own Philox key in place of ``seed``, so rows of one batch may stand at different windows of
+    their chains (``dsh_sample_set_row_seeds``; :class:`diffsheg_amd.streaming.StreamPool`);
   * the guidance scale is ``opt.cond_scale`` as in the reference (ignored for weights without ``classifier_free``), or the
     loops' ``cond_scale=`` keyword (a float, or one value per batch row), which wins over ``opt``; either holds for the call only;
   * ``model_kwargs['length']`` with an entry ``< T`` makes the batch ragged (``UniDiffuser.set_condition(lengths=)``): every row is
@@ -133,7 +135,8 @@ class GaussianDiffusion:
                                  int(bool(getattr(o, "same_overlap_noisy", False))), int(clip_idx), float(eta))
 
     def _run(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0,
-             noise_source=None, seed=None, return_trace=False, row_keys=None, cond_scale=None, tail_blend=False):
+             noise_source=None, seed=None, return_trace=False, row_keys=None, cond_scale=None, tail_blend=False,
+             row_seeds=None):
         if not isinstance(model, UniDiffuser):
             raise TypeError("model must be a diffsheg_amd.model.UniDiffuser (no generic-callable / CPU fallback)")
         if denoised_fn is not None or cond_fn is not None:
@@ -230,7 +233,11 @@ class GaussianDiffusion:
         # Philox noise: optional per-row generator keys (a chain's global id), see dsh_sample_set_row_keys
         if row_keys is not None and len(row_keys) != B:
             raise ValueError(f"row_keys needs one key per batch row ({B}), got {len(row_keys)}")
+        if row_seeds is not None and (row_keys is None or len(row_seeds) != B):
+            raise ValueError(f"row_seeds needs row_keys and one seed per batch row ({B})")
         nk = 0 if (row_keys is None or noise_source is not None) else B
+        ns = nk if row_seeds is not None else 0
+        sarr = (C.c_uint64 * max(ns, 1))(*([int(k) & 0xFFFFFFFFFFFFFFFF for k in row_seeds] if ns else [0]))
         karr = (C.c_uint64 * max(nk, 1))(*([int(k) & 0xFFFFFFFFFFFFFFFF for k in row_keys] if nk else [0]))
         prev_gs = model.guidance_scale
         set_gs = gs is not None and gs != prev_gs
@@ -238,7 +245,9 @@ class GaussianDiffusion:
             model.set_guidance_scale(gs)
         cur = model._enter()
         try:
-            _lib.check(lib.dsh_sample_set_row_keys(model._h, karr, nk), "dsh_sample_set_row_keys")
+            _lib.check(lib.dsh_sample_set_row_keys(model._h, karr, nk), "dsh_sample_set_row_keys")      # (also drops earlier row seeds)
+            if ns:
+                _lib.check(lib.dsh_sample_set_row_seeds(model._h, sarr, ns), "dsh_sample_set_row_seeds")
             if tail_blend:
                 _lib.check(lib.dsh_sample_set_tail_blend(model._h, 1), "dsh_sample_set_tail_blend")
             try:

@@ -175,7 +175,8 @@ class DDPMTrainer:
         padded frames stay 0; the default returns the sampler's result as it is, with no extra launch.  ``modality`` /
         ``expression`` (:meth:`UniDiffuser.set_condition`): ``"expression"`` samples the face alone (gesture columns of the result 0),
         ``"gesture"`` samples gestures for the given expression track ``[B, T, expression_dim]`` (expression columns = the track);
-        ``inpaint_dict`` is honoured on the active columns only."""
+        ``inpaint_dict`` is honoured on the active columns only.  ``row_seeds=`` (in ``sampler_kw``, with ``row_keys=``): one Philox key
+        per row in place of ``seed=`` — rows at different windows of their chains in one batch (:mod:`diffsheg_amd.streaming`)."""
         euler = self._euler_requested(pose_rep)
         if cond_scale is not None:
             sampler_kw["cond_scale"] = cond_scale

@@ -196,6 +196,15 @@ int dsh_sample(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t ini
  * whatever batch, stream split or rank it is sampled in (sharded test_arbitrary_len, ddpm_show_trainer.py:743-750:
  * the reference instead draws from each rank's global torch RNG).  Sticky until changed; frames*channels % 4 == 0. */
 int dsh_sample_set_row_keys(dsh_ctx* ctx, const uint64_t* keys_host, int32_t n);
+/* DSH_NOISE_PHILOX with row keys only: give every batch row its own Philox KEY as well (host array of n entries).  Row b then draws
+ * from key seeds_host[b] wherever the loop uses opts->seed - x_T, every step's randn_like, the noise of the RePaint blend's gt, the undo
+ * steps and the eta draws, on every stream the loop runs on - with the counter unchanged (draw index and position inside the row in
+ * the low words, keys[b] in the high words; ragged rows advance by their own size as before).  A chain's window k is sampled with
+ * the key hash(base seed, k), so rows standing at DIFFERENT windows of their chains (live sessions batched together) each draw exactly
+ * what they draw alone in a call whose opts->seed is that hash.  Needs the row keys set, and n equal to their count: -1 before any state
+ * changes otherwise.  Sticky like the keys; n = 0 clears it, and so does every dsh_sample_set_row_keys call (the seeds belong to the key
+ * set they were given for: set the keys first, then the seeds).  Without row seeds every value is what it was, bit for bit. */
+int dsh_sample_set_row_seeds(dsh_ctx* ctx, const uint64_t* seeds_host, int32_t n);
 /* Windows pinned at BOTH ends (motion in-betweening, seam repair of multi-chain streams): the reference cross-fades generated motion
  * into the pinned frames on the first overlap_len frames only (addBlend, gaussian_diffusion.py:1051-1054).  on != 0 adds the mirror
  * image on the last overlap_len frames of every DDIM step the head fade runs in (add_blend set, noise weight < 0.2):
@@ -380,6 +389,26 @@ int dsh_op_philox_randn_rows(void* hip_stream, float* out, int32_t rows, int64_t
  * Refuses a length whose row_lens * channels exceeds n_row.  Synchronises the stream. */
 int dsh_op_philox_randn_rows_ragged(void* hip_stream, float* out, int32_t rows, int64_t n_row, uint64_t seed, uint64_t offset,
                                     const uint64_t* row_keys_host, const int32_t* row_lens_host, uint64_t draw, int32_t channels);
+/* dsh_op_philox_randn_rows with the per-row Philox keys of dsh_sample_set_row_seeds: row_seeds_dev (DEVICE array [rows], nullable) gives
+ * row b the key row_seeds_dev[b] in place of `seed`; NULL is dsh_op_philox_randn_rows itself.  Synchronises the stream. */
+int dsh_op_philox_randn_rows_seeded(void* hip_stream, float* out, int32_t rows, int64_t n_row, uint64_t seed, uint64_t offset,
+                                    const uint64_t* row_keys_host, const uint64_t* row_seeds_dev);
+/* ... and its ragged sibling: dsh_op_philox_randn_rows_ragged with row_seeds_dev (DEVICE array [rows], nullable). */
+int dsh_op_philox_randn_rows_ragged_seeded(void* hip_stream, float* out, int32_t rows, int64_t n_row, uint64_t seed, uint64_t offset,
+                                           const uint64_t* row_keys_host, const int32_t* row_lens_host, uint64_t draw, int32_t channels,
+                                           const uint64_t* row_seeds_dev);
+/* Window hand-off of live chains on a device-resident slot table tails [S, L, C] (fp32, standardised motion: slot s holds the last
+ * L = overlap_len frames of the window its chain sampled last).  Row r of a window batch belongs to slot slot_idx[r]; the index list is
+ * given twice, as the host copy the call validates and the device copy the kernel reads (the kernel skips a row whose device index is
+ * outside the table).  One launch each, plain loads and stores, any C, any T > L >= 1, asynchronous on hip_stream; R = 0 launches nothing.
+ * -1 before any launch on L < 1, L >= T, a slot index outside [0, S) and - where slots are written - a slot named twice.
+ * dsh_op_chain_handoff builds the reference's inpaint dictionary of a chained window (ddpm_show_trainer.py:889-893):
+ *   gt [R, T, C]: gt[r, :L] = tails[slot_idx[r]], other frames 0;  mask [R, T, C] uint8: 1 on the first L frames, 0 elsewhere. */
+int dsh_op_chain_handoff(void* hip_stream, const float* tails, int32_t S, const int32_t* slot_idx_host, const int32_t* slot_idx_dev,
+                         int32_t R, int32_t T, int32_t L, int32_t C, float* gt, uint8_t* mask);
+/* tails[slot_idx[r]] = x[r, n_r - L : n_r] for x [R, T, C], n_r = lens[r] (host and device copy, both or neither; L <= n_r <= T) or T. */
+int dsh_op_chain_save_tail(void* hip_stream, const float* x, const int32_t* lens_host, const int32_t* lens_dev, const int32_t* slot_idx_host,
+                           const int32_t* slot_idx_dev, int32_t R, int32_t T, int32_t L, int32_t C, float* tails, int32_t S);
 /* dsh_op_ddim_step with every field of the step: x0_out (nullable) receives pred_xstart; coef_eps multiplies the re-derived eps and
  * sigma * noise1 is added when noise1 != NULL (the eta branch; eta = 0: coef_eps = sqrt_1m_ab_prev, noise1 = NULL); tail_in / tail_out
  * [B, overlap_len, channels] (nullable) are the saved noisy tail of --same_overlap_noisy.  Refusals of dsh_op_ddim_step, and tail_in
