@@ -43,6 +43,9 @@ _P = C.c_void_p
 SYMBOLS = {
     "dsh_last_error": (C.c_char_p, []),
     "dsh_version": (C.c_char_p, []),
+    "dsh_switch_count": (C.c_int32, []),
+    "dsh_switch_info": (C.c_int, [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_char_p)]),
+    "dsh_switch_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "dsh_create": (C.c_int, [C.POINTER(ModelConfigC), _P, C.POINTER(_P)]),
     "dsh_destroy": (C.c_int, [_P]),
     "dsh_load_tensor": (C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), C.c_int32]),

@@ -22,6 +22,7 @@
 
 #include "dsh_common.h"
 #include "dsh_kernels.h"
+#include "switches.h"
 
 namespace dsh {
 
@@ -911,8 +912,7 @@ int launch_linear_attention(const T* qkv, int ldq, int nbatch, int frames, int D
     // (fp32 path, 64-channel heads: the loop form was 62 us per launch at the config-2 batch — 10 % of its step — against
     //  a few microseconds of data; with the columns preloaded the launch is one memory round trip plus the arithmetic)
     // round 6: fp32, 64-channel heads: both products on the exact-fp32 matrix pipe (DSH_ATTN_F32_MFMA=0: the VALU kernels below)
-    static const int f32_mfma = [] { const char* e = getenv("DSH_ATTN_F32_MFMA"); return e ? atoi(e) : 1; }();
-    if (f32_mfma && sizeof(T) == 4 && head_dim == 64 && frames <= 96 && ldq % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)qkv % 16) == 0 && ((uintptr_t)y % 16) == 0) {
+    if (switch_int(SW_ATTN_F32_MFMA) && sizeof(T) == 4 && head_dim == 64 && frames <= 96 && ldq % 4 == 0 && ldy % 4 == 0 && ((uintptr_t)qkv % 16) == 0 && ((uintptr_t)y % 16) == 0) {
         const float* qf = reinterpret_cast<const float*>(qkv);
         float* yf = reinterpret_cast<float*>(y);
         if (frames <= 32) at_launch(AT_K(linear_attention_f32_mfma_kernel, 32), rag, grid, dim3(64), s, qf, ldq, frames, D, yf, ldy, lens, lmod);
@@ -937,7 +937,7 @@ int launch_linear_attention(const T* qkv, int ldq, int nbatch, int frames, int D
 }
 // fp32, D = 512, eight 64-channel heads, T <= 96: attention core + the StylizationBlock front behind it in one launch (see the kernel above)
 bool linear_attention_sty_f32_supported(int frames, int D, int head_dim, int ldq, int ldy) {
-    static const int on = [] { const char* e = getenv("DSH_ATTN_STY"); return e ? atoi(e) : 1; }();
+    const bool on = switch_int(SW_ATTN_STY) != 0;
     // (up to 64 frames: the 96-frame instantiation spills at eight waves per block — longer windows keep the two launches)
     return on && D == 512 && head_dim == 64 && frames > 0 && frames <= 64 && ldq % 4 == 0 && ldy % 4 == 0;
 }

@@ -397,30 +397,76 @@ int32_t dsh_debug_launch_counts(int64_t* out, int32_t cap, int32_t reset) {
     return dsh::LC_COUNT;
 }
 
+// ---- op-level entries: test / bench helpers over ROW-MAJOR operands.  Each builds the kernels' operands in per-call scratch, caches nothing
+// (a cache keyed on a pointer would alias when the caller's allocator reuses the address) and frees the scratch after a stream sync.
+namespace {
+struct OpScratch {
+    std::vector<void*> p;
+    ~OpScratch() { for (void* q : p) (void)hipFree(q); }
+    int alloc(void** out, size_t bytes) { DSH_HIP_CHECK(hipMalloc(out, bytes)); p.push_back(*out); return 0; }
+    int upload(void** out, const void* host, size_t bytes) {
+        if (int e = alloc(out, bytes)) return e;
+        DSH_HIP_CHECK(hipMemcpy(*out, host, bytes, hipMemcpyHostToDevice));
+        return 0;
+    }
+    // zeroed 64-bit words for a bench hook of the token-per-lane kernels (block timeline: 4 per block, phase probe: 8 per block)
+    int words(unsigned long long** out, size_t n, hipStream_t s) {
+        if (int e = alloc(reinterpret_cast<void**>(out), n * 8)) return e;
+        DSH_HIP_CHECK(hipMemsetAsync(*out, 0, n * 8, s));
+        return 0;
+    }
+};
+int fetch_f32(std::vector<float>& dst, const float* dev, size_t n) {
+    dst.resize(n);
+    DSH_HIP_CHECK(hipMemcpy(dst.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+int fetch_words(std::vector<unsigned long long>& dst, const unsigned long long* dev, size_t n, hipStream_t s) {
+    dst.resize(n);
+    DSH_HIP_CHECK(hipStreamSynchronize(s));
+    DSH_HIP_CHECK(hipMemcpy(dst.data(), dev, n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+// DSH_TL_TRACE: one line per block — index, three 100 MHz time stamps, then the two halves of the fourth word; skip_idle leaves out
+// the slots no block wrote (the Linear's upper bound on its grid)
+int dump_tl_trace(const char* path, const unsigned long long* dev, size_t nblk, bool skip_idle, hipStream_t s) {
+    std::vector<unsigned long long> ht;
+    if (int e = fetch_words(ht, dev, nblk * 4, s)) return e;
+    if (FILE* f = fopen(path, "w")) {
+        for (size_t i = 0; i < nblk; ++i)
+            if (!skip_idle || ht[4 * i]) fprintf(f, "%zu %llu %llu %llu %llu %llu\n", i, ht[4 * i], ht[4 * i + 1], ht[4 * i + 2], ht[4 * i + 3] & 0xffffffffull, ht[4 * i + 3] >> 32);
+        fclose(f);
+    }
+    return 0;
+}
+// DSH_TL_PROBE: one line per block — index and the first `nwords` of its 8 probe words (Linear 7, fused FFN 8)
+int dump_tl_probe(const char* path, const unsigned long long* dev, size_t npb, int nwords, hipStream_t s) {
+    std::vector<unsigned long long> hp;
+    if (int e = fetch_words(hp, dev, npb * 8, s)) return e;
+    if (FILE* f = fopen(path, "w")) {
+        for (size_t i = 0; i < npb; ++i) {
+            fprintf(f, "%zu", i);
+            for (int k = 0; k < nwords; ++k) fprintf(f, " %llu", hp[8 * i + k]);
+            fprintf(f, "\n");
+        }
+        fclose(f);
+    }
+    return 0;
+}
+}  // namespace
+
 int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W, const float* bias, const float* R,
                      float* Cf, void* Ct, int32_t M, int32_t N, int32_t act, const float* gamma, const float* beta,
                      const float* film, int32_t frames, int32_t nb, int32_t K) {
     API_BEGIN
     DSH_REQUIRE(X && W && M > 0 && N > 0 && N % 32 == 0 && (K == 512 || K == 1024), "invalid argument");
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    // Test / bench helper over ROW-MAJOR operands: the weight rows are pi-permuted and the row tensors converted to /
-    // from the kernel's tiled layouts in per-call scratch buffers (finalize() / the denoiser do this once, or never
-    // leave the tiled layout).  Nothing is cached across calls (a cache keyed on the weight pointer would alias when the
-    // caller's allocator reuses the address): the scratch is freed after a stream sync at the end of the call.
+    // The weight rows are pi-permuted and the row tensors converted to / from the kernel's tiled layouts in the per-call scratch
+    // (finalize() / the denoiser do this once, or never leave the tiled layout).
     // DSH_TL_RAW=1 (timing loops only): every operand is passed through untouched as if already permuted / tiled / folded.
-    struct Scratch {
-        std::vector<void*> p;
-        ~Scratch() { for (void* q : p) (void)hipFree(q); }
-    } scratch;
-    auto salloc = [&](void** out, size_t bytes) -> int {
-        DSH_HIP_CHECK(hipMalloc(out, bytes));
-        scratch.p.push_back(*out);
-        return 0;
-    };
-    const char* raw_e = getenv("DSH_TL_RAW");
-    const bool raw = raw_e && atoi(raw_e) != 0;
-    const char* g2_e = getenv("DSH_TL2");
-    const bool gen2 = !(g2_e && atoi(g2_e) == 0);   // second-generation (LDS-DMA) kernels unless DSH_TL2=0
+    OpScratch scratch;
+    const bool raw = dsh::switch_int(dsh::SW_TL_RAW) != 0;
+    const bool gen2 = dsh::switch_int(dsh::SW_TL2) != 0;   // second-generation (LDS-DMA) kernels unless DSH_TL2=0
     const size_t Mp = (size_t)dsh::round_up(M, 256) + 256;
     const float *fold_c = nullptr, *fold_d = nullptr;
     dsh::TlArgs a;
@@ -431,7 +477,7 @@ int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W
     DSH_REQUIRE(pro != 3 || (K == 1024 && frames > 896 - 1 && frames <= 1024), "tl_linear pro 3: K = 1024, frames = real concat width (896 .. 1024)");
     if (!raw) {
         void *wperm = nullptr, *tx = nullptr, *tr = nullptr, *tcf = nullptr, *tct = nullptr;
-        if (int e = salloc(&wperm, (size_t)N * K * 2)) return e;
+        if (int e = scratch.alloc(&wperm, (size_t)N * K * 2)) return e;
         if (int e = dsh::launch_tl_permute_weight(W, N, K, wperm, s)) return e;
         a.W = wperm;
         if (gen2) {      // fragment order for the LDS-DMA kernels (host round trip: this is a test helper)
@@ -456,8 +502,8 @@ int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W
                     hc[dsh::tl_weight_src_row(r)] = (float)c; hd[dsh::tl_weight_src_row(r)] = (float)d;   // natural feature order
                 }
                 void *dc = nullptr, *dd = nullptr;
-                if (int e = salloc(&dc, N * 4)) return e;
-                if (int e = salloc(&dd, N * 4)) return e;
+                if (int e = scratch.alloc(&dc, N * 4)) return e;
+                if (int e = scratch.alloc(&dd, N * 4)) return e;
                 DSH_HIP_CHECK(hipMemcpy(dc, hc.data(), N * 4, hipMemcpyHostToDevice));
                 DSH_HIP_CHECK(hipMemcpy(dd, hd.data(), N * 4, hipMemcpyHostToDevice));
                 fold_c = reinterpret_cast<const float*>(dc); fold_d = reinterpret_cast<const float*>(dd);
@@ -472,42 +518,41 @@ int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W
             const dsh::bf16* xb = reinterpret_cast<const dsh::bf16*>(X);
             const int offs[4] = {0, 512, 768, 896}, wid[4] = {512, 256, 128, 128};
             for (int i = 0; i < 4; ++i) {
-                if (int e = salloc(&tcat[i], Mp * wid[i] * 2)) return e;
+                if (int e = scratch.alloc(&tcat[i], Mp * wid[i] * 2)) return e;
                 if (int e = dsh::launch_tile_rows_bf16<dsh::bf16>(xb + offs[i], K, M, wid[i], tcat[i], wid[i], s)) return e;
             }
             a.X = tcat[0];
         } else {
-            if (int e = salloc(&tx, Mp * K * 2)) return e;
+            if (int e = scratch.alloc(&tx, Mp * K * 2)) return e;
             if (int e = dsh::launch_tile_rows_bf16<dsh::bf16>(reinterpret_cast<const dsh::bf16*>(X), K, M, K, tx, K, s)) return e;
             a.X = tx;
         }
         // DSH_HILO=1 (tests of the hi / lo residual planes, tl_common.h): a residual-carrying call with both outputs runs the plane
         // instantiation — R is split into (hi, lo) planes, Cf comes back as hi + lo and Ct as the hi plane
-        { const char* he = getenv("DSH_HILO"); hilo = he && atoi(he) != 0 && R && Cf && Ct && act == 0 && ((pro == 2 && K == 512) || (pro == 0 && K == 1024)); }
+        hilo = dsh::hilo_op() && R && Cf && Ct && act == 0 && ((pro == 2 && K == 512) || (pro == 0 && K == 1024));
         if (hilo) {
-            if (int e = salloc(&tr, Mp * N * 2)) return e;
-            if (int e = salloc(&trl, Mp * N * 2)) return e;
+            if (int e = scratch.alloc(&tr, Mp * N * 2)) return e;
+            if (int e = scratch.alloc(&trl, Mp * N * 2)) return e;
             if (int e = dsh::launch_tile_rows_hilo(R, N, M, N, tr, trl, N, s)) return e;
-            if (int e = salloc(&tct, Mp * N * 2)) return e;
-            if (int e = salloc(&tcl, Mp * N * 2)) return e;
+            if (int e = scratch.alloc(&tct, Mp * N * 2)) return e;
+            if (int e = scratch.alloc(&tcl, Mp * N * 2)) return e;
             a.R = reinterpret_cast<const float*>(tr); a.Rlo = trl; a.Cf = nullptr; a.Ct = tct; a.Clo = tcl;
         } else {
-        if (R) { if (int e = salloc(&tr, Mp * N * 4)) return e;
+        if (R) { if (int e = scratch.alloc(&tr, Mp * N * 4)) return e;
                  if (int e = dsh::launch_tile_rows_f32(R, N, M, reinterpret_cast<float*>(tr), N, s)) return e;
                  a.R = reinterpret_cast<const float*>(tr); }
-        if (Cf) { if (int e = salloc(&tcf, Mp * N * 4)) return e; a.Cf = reinterpret_cast<float*>(tcf); }
-        if (Ct) { if (int e = salloc(&tct, Mp * N * 2)) return e; a.Ct = tct; }
+        if (Cf) { if (int e = scratch.alloc(&tcf, Mp * N * 4)) return e; a.Cf = reinterpret_cast<float*>(tcf); }
+        if (Ct) { if (int e = scratch.alloc(&tct, Mp * N * 2)) return e; a.Ct = tct; }
         }
     }
     a.ldx = K; a.K = K; a.bias = bias; a.ldr = N; a.ldcf = N; a.cf_rowmajor = 0; a.ldct = N; a.half_row0 = 0x7fffffff;
     a.M = M; a.N = N; a.act = act; a.gamma = gamma; a.beta = beta; a.film_ld = 2 * K; a.film_off = 0;
     a.frames = frames > 0 ? frames : 1; a.bmod = nb > 0 ? nb : 1; a.row_const = nullptr; a.n_const_rows = 0;
-    a.rev = 0; a.X1 = nullptr; a.ld1 = 0; a.X2 = nullptr; a.ld2 = 0; a.X3 = nullptr; a.ld3 = 0; a.kreal = K; { const char* e = getenv("DSH_TL_DBG"); a.dbg = e ? atoi(e) : 0; }
+    a.rev = 0; a.X1 = nullptr; a.ld1 = 0; a.X2 = nullptr; a.ld2 = 0; a.X3 = nullptr; a.ld3 = 0; a.kreal = K; a.dbg = (int)dsh::switch_int(dsh::SW_TL_DBG);
     if (pro == 3) { a.ldx = 512; a.X1 = tcat[1]; a.ld1 = 256; a.X2 = tcat[2]; a.ld2 = 128; a.X3 = tcat[3]; a.ld3 = 128; a.kreal = frames; }
     if (raw && R && Cf && Ct && act == 0 && ((pro == 2 && K == 512) || (pro == 0 && K == 1024))) {
         // timing mode, DSH_HILO=1: the residual-carrying launch on hi / lo planes — R is taken as the hi plane, Cf's buffer as the lo plane (in / out)
-        const char* he = getenv("DSH_HILO");
-        if (he && atoi(he) != 0) { a.Rlo = Cf; a.Clo = Cf; a.Cf = nullptr; }
+        if (dsh::hilo_op()) { a.Rlo = Cf; a.Clo = Cf; a.Cf = nullptr; }
     }
     if (pro == 3 && raw) {     // timing mode: the caller's [Mp, 1024] buffer is cut into four segment buffers of the right sizes (contents are garbage anyway)
         const char* xb = reinterpret_cast<const char*>(X);
@@ -520,61 +565,43 @@ int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W
     if (pro == 2 && !raw) {   // the kernel takes the folded coefficient table: fold a scratch copy of the caller's [scale | shift] rows
         void* fsc = nullptr;
         const size_t fbytes = (size_t)a.bmod * 2 * K * 4;
-        if (int e = salloc(&fsc, fbytes)) return e;
+        if (int e = scratch.alloc(&fsc, fbytes)) return e;
         DSH_HIP_CHECK(hipMemcpyAsync(fsc, film, fbytes, hipMemcpyDeviceToDevice, s));
         if (int e = dsh::launch_film_fold(reinterpret_cast<float*>(fsc), 2 * K, a.bmod, 1, K, gamma, beta, s)) return e;
         a.film = reinterpret_cast<const float*>(fsc);
     }
-    static unsigned long long* clk_dev = nullptr;
-    const char* clk_e = getenv("DSH_TL_CLK");
+    // bench hooks (per-call scratch like everything else; each reads back after a stream sync)
+    unsigned long long *clk_dev = nullptr, *trace_dev = nullptr, *probe_dev = nullptr;
+    const long clk_mode = dsh::switch_int(dsh::SW_TL_CLK);
     a.clk = nullptr;
-    if (clk_e && atoi(clk_e)) {
-        if (!clk_dev) DSH_HIP_CHECK(hipMalloc(&clk_dev, 32));
+    if (clk_mode) {
+        if (int e = scratch.alloc(reinterpret_cast<void**>(&clk_dev), 32)) return e;
         a.clk = clk_dev;
     }
-    static unsigned long long* trace_dev = nullptr; static size_t trace_cap = 0;
-    const char* tr_e = getenv("DSH_TL_TRACE");        // bench only: block timeline -> file named by the variable (synchronises)
+    const char* tr_e = dsh::switch_str(dsh::SW_TL_TRACE);        // block timeline -> file named by the variable
     a.trace = nullptr;
     const size_t nblk = (size_t)dsh::ceil_div(M, 128) * 64;          // upper bound on blocks (grid.x * grid.y)
     if (tr_e && *tr_e) {
-        if (trace_cap < nblk) { if (trace_dev) (void)hipFree(trace_dev); DSH_HIP_CHECK(hipMalloc(&trace_dev, nblk * 32)); trace_cap = nblk; }
-        DSH_HIP_CHECK(hipMemsetAsync(trace_dev, 0, nblk * 32, s));
+        if (int e = scratch.words(&trace_dev, nblk * 4, s)) return e;
         a.trace = trace_dev;
     }
-    static unsigned long long* probe_dev = nullptr; static size_t probe_cap = 0;
-    const char* pb_e = getenv("DSH_TL_PROBE");        // bench only: per-block phase probe of the gen-2 kernels -> file (synchronises)
+    const char* pb_e = dsh::switch_str(dsh::SW_TL_PROBE);        // per-block phase probe of the gen-2 kernels -> file
     const size_t npb = (size_t)dsh::ceil_div(M, 128);
-    if (gen2 && pb_e && *pb_e) {
-        if (probe_cap < npb) { if (probe_dev) (void)hipFree(probe_dev); DSH_HIP_CHECK(hipMalloc(&probe_dev, npb * 64)); probe_cap = npb; }
-        DSH_HIP_CHECK(hipMemsetAsync(probe_dev, 0, npb * 64, s));
+    const bool probe = gen2 && pb_e && *pb_e;
+    if (probe) {
+        if (int e = scratch.words(&probe_dev, npb * 8, s)) return e;
         a.clk = probe_dev;
     }
     if (int e = gen2 ? dsh::launch_tl2_linear(a, pro, s) : dsh::launch_tl_linear(a, pro, s)) return e;
-    if (gen2 && pb_e && *pb_e) {
-        std::vector<unsigned long long> hp(npb * 8);
-        DSH_HIP_CHECK(hipStreamSynchronize(s));
-        DSH_HIP_CHECK(hipMemcpy(hp.data(), probe_dev, npb * 64, hipMemcpyDeviceToHost));
-        if (FILE* f = fopen(pb_e, "w")) {
-            for (size_t i = 0; i < npb; ++i)
-                fprintf(f, "%zu %llu %llu %llu %llu %llu %llu %llu\n", i, hp[8 * i], hp[8 * i + 1], hp[8 * i + 2], hp[8 * i + 3], hp[8 * i + 4], hp[8 * i + 5], hp[8 * i + 6]);
-            fclose(f);
+    if (probe) { if (int e = dump_tl_probe(pb_e, probe_dev, npb, 7, s)) return e; }
+    if (a.trace) { if (int e = dump_tl_trace(tr_e, trace_dev, nblk, true, s)) return e; }
+    if (clk_dev && !probe) {
+        DSH_HIP_CHECK(hipStreamSynchronize(s));      // (the probe words are scratch of this call)
+        if (clk_mode == 2) {   // 2: read back and print
+            unsigned long long hv[4];
+            DSH_HIP_CHECK(hipMemcpy(hv, clk_dev, 32, hipMemcpyDeviceToHost));
+            fprintf(stderr, "[tl clock probe] block 0: %llu shader cycles in %.2f us -> %.3f GHz; barrier-parked cycles (wave 0) %llu\n", hv[0], hv[1] / 100.0, hv[0] / (hv[1] * 10.0), hv[2]);
         }
-        a.clk = nullptr;
-    }
-    if (a.trace) {
-        std::vector<unsigned long long> ht(nblk * 4);
-        DSH_HIP_CHECK(hipStreamSynchronize(s));
-        DSH_HIP_CHECK(hipMemcpy(ht.data(), trace_dev, nblk * 32, hipMemcpyDeviceToHost));
-        if (FILE* f = fopen(tr_e, "w")) {
-            for (size_t i = 0; i < nblk; ++i)
-                if (ht[4 * i]) fprintf(f, "%zu %llu %llu %llu %llu %llu\n", i, ht[4 * i], ht[4 * i + 1], ht[4 * i + 2], ht[4 * i + 3] & 0xffffffffull, ht[4 * i + 3] >> 32);
-            fclose(f);
-        }
-    }
-    if (a.clk && atoi(clk_e) == 2) {   // 2: read back and print (synchronises)
-        unsigned long long hv[4];
-        DSH_HIP_CHECK(hipMemcpy(hv, clk_dev, 32, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[tl clock probe] block 0: %llu shader cycles in %.2f us -> %.3f GHz; barrier-parked cycles (wave 0) %llu\n", hv[0], hv[1] / 100.0, hv[0] / (hv[1] * 10.0), hv[2]);
     }
     if (!raw) {
         if (hilo) { if (int e = dsh::launch_untile_rows_hilo(a.Ct, a.Clo, N, M, N, Cf, N, s)) return e; }
@@ -593,16 +620,14 @@ int dsh_op_tl2_ffn(void* hip_stream, const void* X, const float* Hres, const voi
     DSH_REQUIRE(X && Hres && W1 && b1 && W2 && b2 && W3 && b3 && gamma && beta && film && Cf && Ct && M > 0 && frames > 0 && nb > 0, "invalid argument");
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
     constexpr int D = 512, F = 1024;
-    struct Scratch { std::vector<void*> p; ~Scratch() { for (void* q : p) (void)hipFree(q); } } scratch;
-    auto salloc = [&](void** out, size_t bytes) -> int { DSH_HIP_CHECK(hipMalloc(out, bytes)); scratch.p.push_back(*out); return 0; };
+    OpScratch scratch;
     // weight stream (see tl2.hip / Denoiser::layer_from): built on the host from the caller's row-major bf16 weights
     std::vector<uint16_t> h1((size_t)F * D), h2((size_t)D * F), h3((size_t)D * D);
     DSH_HIP_CHECK(hipStreamSynchronize(s));
     DSH_HIP_CHECK(hipMemcpy(h1.data(), W1, h1.size() * 2, hipMemcpyDeviceToHost));
     DSH_HIP_CHECK(hipMemcpy(h2.data(), W2, h2.size() * 2, hipMemcpyDeviceToHost));
     DSH_HIP_CHECK(hipMemcpy(h3.data(), W3, h3.size() * 2, hipMemcpyDeviceToHost));
-    const char* ver_e = getenv("DSH_FFN_V");          // 2: tl2_ffn_kernel, 3 (default): tl3_ffn_kernel (K-outer head of Linear3)
-    const int ver = (ver_e && atoi(ver_e) == 2) ? 2 : 3;
+    const int ver = dsh::ffn_generation();            // 2: tl2_ffn_kernel, 3 (default): tl3_ffn_kernel (K-outer head of Linear3)
     constexpr size_t CH = 16384;
     std::vector<uint16_t> st((size_t)80 * CH), p1(h1.size()), p2(h2.size()), p3(h3.size());
     for (int r = 0; r < F; ++r) std::copy(h1.begin() + (size_t)dsh::tl_weight_src_row(r) * D, h1.begin() + (size_t)(dsh::tl_weight_src_row(r) + 1) * D, p1.begin() + (size_t)r * D);
@@ -611,16 +636,16 @@ int dsh_op_tl2_ffn(void* hip_stream, const void* X, const float* Hres, const voi
     dsh::tl_pack_ffn_stream(ver, p1.data(), p2.data(), p3.data(), st.data());
     void *wst = nullptr, *tx = nullptr, *tr = nullptr, *tcf = nullptr, *tct = nullptr, *fsc = nullptr;
     const size_t Mp = (size_t)dsh::round_up(M, 128) + 128;
-    if (int e = salloc(&wst, st.size() * 2)) return e;
+    if (int e = scratch.alloc(&wst, st.size() * 2)) return e;
     DSH_HIP_CHECK(hipMemcpy(wst, st.data(), st.size() * 2, hipMemcpyHostToDevice));
-    if (int e = salloc(&tx, Mp * D * 2)) return e;
-    if (int e = salloc(&tr, Mp * D * 4)) return e;
-    if (int e = salloc(&tcf, Mp * D * 4)) return e;
-    if (int e = salloc(&tct, Mp * D * 2)) return e;
+    if (int e = scratch.alloc(&tx, Mp * D * 2)) return e;
+    if (int e = scratch.alloc(&tr, Mp * D * 4)) return e;
+    if (int e = scratch.alloc(&tcf, Mp * D * 4)) return e;
+    if (int e = scratch.alloc(&tct, Mp * D * 2)) return e;
     if (int e = dsh::launch_tile_rows_bf16<dsh::bf16>(reinterpret_cast<const dsh::bf16*>(X), D, M, D, tx, D, s)) return e;
     if (int e = dsh::launch_tile_rows_f32(Hres, D, M, reinterpret_cast<float*>(tr), D, s)) return e;
     const size_t fbytes = (size_t)nb * 2 * D * 4;
-    if (int e = salloc(&fsc, fbytes)) return e;
+    if (int e = scratch.alloc(&fsc, fbytes)) return e;
     DSH_HIP_CHECK(hipMemcpyAsync(fsc, film, fbytes, hipMemcpyDeviceToDevice, s));
     if (int e = dsh::launch_film_fold(reinterpret_cast<float*>(fsc), 2 * D, nb, 1, D, gamma, beta, s)) return e;
     dsh::Tl2FfnArgs a;
@@ -629,60 +654,35 @@ int dsh_op_tl2_ffn(void* hip_stream, const void* X, const float* Hres, const voi
     a.Ct = tct; a.row_const = row_const; a.n_const_rows = n_const_rows; a.M = M; a.trace = nullptr; a.clk = nullptr; a.rev = 0;
     a.Rhi = nullptr; a.Rlo = nullptr; a.Clo = nullptr;
     // DSH_HILO=1 (generation 3 only): residual stream as hi / lo planes — the residual of this call is split, Cf comes back as hi + lo
-    const char* hl_e = getenv("DSH_HILO");
-    const bool hilo = ver == 3 && hl_e && atoi(hl_e) != 0;
+    const bool hilo = ver == 3 && dsh::hilo_op();
     void *trh = nullptr, *trl = nullptr, *tcl = nullptr;
     if (hilo) {
-        if (int e = salloc(&trh, Mp * D * 2)) return e;
-        if (int e = salloc(&trl, Mp * D * 2)) return e;
-        if (int e = salloc(&tcl, Mp * D * 2)) return e;
+        if (int e = scratch.alloc(&trh, Mp * D * 2)) return e;
+        if (int e = scratch.alloc(&trl, Mp * D * 2)) return e;
+        if (int e = scratch.alloc(&tcl, Mp * D * 2)) return e;
         if (int e = dsh::launch_tile_rows_hilo(Hres, D, M, D, trh, trl, D, s)) return e;
         a.R = nullptr; a.Cf = nullptr; a.Rhi = trh; a.Rlo = trl; a.Clo = tcl;
         // DSH_FFN_X_IS_HI=1: the input IS the hi plane of the residual, as in the denoiser's layers (X is ignored) — the form
         // DSH_FFN_PC=3 keeps in registers
-        const char* xh_e = getenv("DSH_FFN_X_IS_HI");
-        if (xh_e && atoi(xh_e) != 0) a.X = trh;
+        if (dsh::switch_int(dsh::SW_FFN_X_IS_HI) != 0) a.X = trh;
     }
-    static unsigned long long* probe_dev = nullptr; static size_t probe_cap = 0;
-    const char* pb_e = getenv("DSH_TL_PROBE");
+    // bench hooks: phase probe and block timeline, one slot per 128-token block
+    unsigned long long *probe_dev = nullptr, *trace_dev = nullptr;
+    const size_t nblk = (size_t)dsh::ceil_div(M, 128);
+    const char* pb_e = dsh::switch_str(dsh::SW_TL_PROBE);
     if (pb_e && *pb_e) {
-        const size_t npb = (size_t)dsh::ceil_div(M, 128);
-        if (probe_cap < npb) { if (probe_dev) (void)hipFree(probe_dev); DSH_HIP_CHECK(hipMalloc(&probe_dev, npb * 64)); probe_cap = npb; }
-        DSH_HIP_CHECK(hipMemsetAsync(probe_dev, 0, npb * 64, s));
+        if (int e = scratch.words(&probe_dev, nblk * 8, s)) return e;
         a.clk = probe_dev;
     }
-    static unsigned long long* trace_dev = nullptr; static size_t trace_cap = 0;
-    const char* tr_e = getenv("DSH_TL_TRACE");
-    const size_t nblk = (size_t)dsh::ceil_div(M, 128);
+    const char* tr_e = dsh::switch_str(dsh::SW_TL_TRACE);
     if (tr_e && *tr_e) {
-        if (trace_cap < nblk) { if (trace_dev) (void)hipFree(trace_dev); DSH_HIP_CHECK(hipMalloc(&trace_dev, nblk * 32)); trace_cap = nblk; }
-        DSH_HIP_CHECK(hipMemsetAsync(trace_dev, 0, nblk * 32, s));
+        if (int e = scratch.words(&trace_dev, nblk * 4, s)) return e;
         a.trace = trace_dev;
     }
-    const char* rep_e = getenv("DSH_FFN_REPEAT");     // bench only: launch the kernel this many extra times (results unchanged: R != Cf)
-    const int reps = 1 + (rep_e ? atoi(rep_e) : 0);
+    const int reps = 1 + (int)dsh::switch_int(dsh::SW_FFN_REPEAT);     // bench only: launch the kernel this many extra times (results unchanged: R != Cf)
     for (int i = 0; i < reps; ++i) { if (int e = (ver == 3 ? dsh::launch_tl3_ffn(a, s) : dsh::launch_tl2_ffn(a, s))) return e; }
-    if (a.trace) {
-        std::vector<unsigned long long> ht(nblk * 4);
-        DSH_HIP_CHECK(hipStreamSynchronize(s));
-        DSH_HIP_CHECK(hipMemcpy(ht.data(), trace_dev, nblk * 32, hipMemcpyDeviceToHost));
-        if (FILE* f = fopen(tr_e, "w")) {
-            for (size_t i = 0; i < nblk; ++i)
-                fprintf(f, "%zu %llu %llu %llu %llu %llu\n", i, ht[4 * i], ht[4 * i + 1], ht[4 * i + 2], ht[4 * i + 3] & 0xffffffffull, ht[4 * i + 3] >> 32);
-            fclose(f);
-        }
-    }
-    if (a.clk) {
-        const size_t npb = (size_t)dsh::ceil_div(M, 128);
-        std::vector<unsigned long long> hp(npb * 8);
-        DSH_HIP_CHECK(hipStreamSynchronize(s));
-        DSH_HIP_CHECK(hipMemcpy(hp.data(), probe_dev, npb * 64, hipMemcpyDeviceToHost));
-        if (FILE* f = fopen(pb_e, "w")) {
-            for (size_t i = 0; i < npb; ++i)
-                fprintf(f, "%zu %llu %llu %llu %llu %llu %llu %llu %llu\n", i, hp[8 * i], hp[8 * i + 1], hp[8 * i + 2], hp[8 * i + 3], hp[8 * i + 4], hp[8 * i + 5], hp[8 * i + 6], hp[8 * i + 7]);
-            fclose(f);
-        }
-    }
+    if (a.trace) { if (int e = dump_tl_trace(tr_e, trace_dev, nblk, false, s)) return e; }
+    if (a.clk) { if (int e = dump_tl_probe(pb_e, probe_dev, nblk, 8, s)) return e; }
     if (hilo) { if (int e = dsh::launch_untile_rows_hilo(a.Ct, a.Clo, D, M, D, Cf, D, s)) return e; }
     else if (int e = dsh::launch_untile_rows_f32(a.Cf, D, M, Cf, D, s)) return e;
     if (int e = dsh::launch_untile_rows_bf16(a.Ct, D, M, D, Ct, D, s)) return e;
@@ -691,27 +691,8 @@ int dsh_op_tl2_ffn(void* hip_stream, const void* X, const float* Hres, const voi
     API_END
 }
 
-// ---- fused front of the bf16 path (tl_aud.hip, tl_embed.hip): test helpers over ROW-MAJOR operands in natural order.  Like dsh_op_tl_linear they
-// build the kernels' operands with the PRODUCTION packers in per-call scratch, cache nothing and free the scratch after a stream sync.  What
+// ---- fused front of the bf16 path (tl_aud.hip, tl_embed.hip): operands in natural order, built with the PRODUCTION packers.  What
 // the launchers themselves refuse (null rows / outputs, ld_b, nf, row1) is passed through to them unchecked.
-namespace {
-struct OpScratch {
-    std::vector<void*> p;
-    ~OpScratch() { for (void* q : p) (void)hipFree(q); }
-    int alloc(void** out, size_t bytes) { DSH_HIP_CHECK(hipMalloc(out, bytes)); p.push_back(*out); return 0; }
-    int upload(void** out, const void* host, size_t bytes) {
-        if (int e = alloc(out, bytes)) return e;
-        DSH_HIP_CHECK(hipMemcpy(*out, host, bytes, hipMemcpyHostToDevice));
-        return 0;
-    }
-};
-int fetch_f32(std::vector<float>& dst, const float* dev, size_t n) {
-    dst.resize(n);
-    DSH_HIP_CHECK(hipMemcpy(dst.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-}  // namespace
-
 int dsh_op_tl_aud_tail(void* hip_stream, const void* Y, const float* X2, const float* ws1, const float* bs1, const float* w1, const float* b1,
                        const float* w2, const float* b2, const float* ws2, const float* bs2, const float* g1, const float* be1, const float* g2,
                        const float* be2, const float* film, int32_t frames, int32_t nb, int32_t Mc, float* out_f, void* out_b, int32_t ld_b) {
@@ -811,8 +792,8 @@ int dsh_op_cross_attention(void* hip_stream, const dsh_cross_attn_weights* w, co
     DSH_REQUIRE(w && x && xf && emb && y && B > 0 && T > 0 && N > 0, "invalid argument");
     DSH_REQUIRE(D % 64 == 0 && L % 32 == 0 && E % 32 == 0 && num_head > 0 && D % num_head == 0, "cross_attention: D % 64, L % 32, E % 32");
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    struct Scratch { std::vector<void*> p; ~Scratch() { for (void* q : p) (void)hipFree(q); } } scratch;
-    auto salloc = [&](float** out, size_t n) -> int { void* q; DSH_HIP_CHECK(hipMalloc(&q, n * sizeof(float))); scratch.p.push_back(q); *out = reinterpret_cast<float*>(q); return 0; };
+    OpScratch scratch;
+    auto salloc = [&](float** out, size_t n) -> int { return scratch.alloc(reinterpret_cast<void**>(out), n * sizeof(float)); };
     const int M = B * T, Mk = B * N;
     float *n1, *q, *nf, *kv, *att, *se, *film, *sy;
     if (int e = salloc(&n1, (size_t)M * D)) return e;
@@ -859,10 +840,10 @@ static int attn_tiled_via_scratch(hipStream_t s, const void* qkv, int nb, int nh
     {
         const int M0 = nh * frames, r0 = dsh::round_up(M0, 128), M1 = (nb - nh) * frames;
         const size_t Mp = (size_t)r0 + dsh::round_up(M1 > 0 ? M1 : 1, 128) + 128;
-        static void* sc[2] = {nullptr, nullptr}; static size_t cap[2] = {0, 0};
-        const size_t need[2] = {Mp * 3 * D * 2, Mp * D * 2};
-        for (int i = 0; i < 2; ++i)
-            if (cap[i] < need[i]) { if (sc[i]) (void)hipFree(sc[i]); DSH_HIP_CHECK(hipMalloc(&sc[i], need[i])); cap[i] = need[i]; }
+        OpScratch scratch;
+        void* sc[2] = {nullptr, nullptr};
+        if (int e = scratch.alloc(&sc[0], Mp * 3 * D * 2)) return e;
+        if (int e = scratch.alloc(&sc[1], Mp * D * 2)) return e;
         const dsh::bf16* q = reinterpret_cast<const dsh::bf16*>(qkv);
         char* tq = reinterpret_cast<char*>(sc[0]); char* ty = reinterpret_cast<char*>(sc[1]);
         if (int e = dsh::launch_tile_rows_bf16<dsh::bf16>(q, 3 * D, M0, 3 * D, tq, 3 * D, s)) return e;
@@ -870,6 +851,7 @@ static int attn_tiled_via_scratch(hipStream_t s, const void* qkv, int nb, int nh
         if (int e = dsh::launch_linear_attention_tiled(tq, nb, nh, r0, frames, D, ty, s, 0, lens)) return e;
         if (int e = dsh::launch_untile_rows_bf16(ty, D, M0, D, y, D, s)) return e;
         if (M1 > 0) { if (int e = dsh::launch_untile_rows_bf16(ty + (size_t)r0 * D * 2, D, M1, D, reinterpret_cast<dsh::bf16*>(y) + (size_t)M0 * D, D, s)) return e; }
+        DSH_HIP_CHECK(hipStreamSynchronize(s));      // the per-call scratch is released on return
         return 0;
     }
 }

@@ -9,6 +9,7 @@
 #include "dsh_common.h"
 #include "dsh_kernels.h"
 #include "profiler.h"
+#include "switches.h"
 
 namespace dsh {
 
@@ -148,7 +149,7 @@ class DenoiserBase {
 };
 
 // DSH_EMB_DEDUP=0 (A/B switch): the embedding Linears run on every clip's row as before round 6
-inline bool emb_dedup_enabled() { const char* e = getenv("DSH_EMB_DEDUP"); return !(e && atoi(e) == 0); }
+inline bool emb_dedup_enabled() { return switch_int(SW_EMB_DEDUP) != 0; }
 
 DenoiserBase* make_denoiser(const ModelConfig& cfg, hipStream_t stream);
 

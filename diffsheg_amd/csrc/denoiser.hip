@@ -27,46 +27,40 @@ template <typename T>
 class Denoiser final : public DenoiserBase {
   public:
     Denoiser(const ModelConfig& c, hipStream_t s) : cfg(c), st(s), gs_dbl(c.classifier_free && c.cond_scale != 1.0f) {
-        const char* t2 = getenv("DSH_TL2");
-        sw.tl2_on = !(t2 && atoi(t2) == 0);          // LDS-DMA token-per-lane kernels (tl2.hip); DSH_TL2=0: first generation
-        sw.tl2_all = t2 && atoi(t2) == 2;            // DSH_TL2=2: also for the HBM-bound (residual) instantiations
-        const char* ff = getenv("DSH_FFN_FUSE");
-        sw.ffn_fuse = sw.tl2_on && !(ff && atoi(ff) == 0);
+        // (raw inputs: the table of switches.h, read here once per context)
+        const long t2 = switch_int(SW_TL2);
+        sw.tl2_on = t2 != 0;                         // LDS-DMA token-per-lane kernels (tl2.hip); DSH_TL2=0: first generation
+        sw.tl2_all = t2 == 2;                        // DSH_TL2=2: also for the HBM-bound (residual) instantiations
+        sw.ffn_fuse = sw.tl2_on && switch_int(SW_FFN_FUSE) != 0;
         // alternate the row order of consecutive token-per-lane launches (tl_block_index, tl_common.h): measured 613.2 -> 609.6 ms per
         // step on three streams, 687 -> 673 ms on one (round 4); DSH_REV=0 disables it
-        const char* rv = getenv("DSH_REV");
-        sw.rev_on = !(rv && atoi(rv) == 0);
-        const char* fv = getenv("DSH_FFN_V");     // fused FFN kernel generation: 3 (default, tl3_ffn.hip) or 2 (tl2.hip); fixes the weight stream order
-        sw.ffn_ver = (fv && atoi(fv) == 2) ? 2 : 3;
+        sw.rev_on = switch_int(SW_REV) != 0;
+        sw.ffn_ver = ffn_generation();            // fused FFN kernel generation: 3 (default, tl3_ffn.hip) or 2 (tl2.hip); fixes the weight stream order
         // residual stream of the token-per-lane path as two bf16 planes (hi = the old bf16 shadow, lo = bf16(h - hi); tl_common.h)
         // instead of fp32 + shadow: 4 instead of 6 bytes per value written by every residual-carrying launch.  DSH_HILO=0: fp32.
-        const char* hl = getenv("DSH_HILO");
-        sw.hilo = sw.ffn_ver == 3 && !sw.tl2_all && !(hl && atoi(hl) == 0);
+        sw.hilo = sw.ffn_ver == 3 && !sw.tl2_all && hilo_denoiser();
         // window-chain batches: 32-token blocks, one tile per wave (tl_small.hip) up to a few thousand token rows per launch; DSH_TLS=0: off
-        const char* ts = getenv("DSH_TLS");
-        const char* tr = getenv("DSH_TLS_ROWS");
-        sw.tls_on = sw.tl2_on && sw.hilo && !(ts && atoi(ts) == 0);
-        const char* sk = getenv("DSH_DBG_SKIP");   // bench experiment only (results are garbage): skip launches of a layer, bit 0 feat_proj.1, 1 feat_proj.3,
-        sw.dbg_skip = sk ? atoi(sk) : 0;              // 2 q|k|v, 3 attention, 4 StylizationBlock (attention branch), 5 fused FFN — what each launch costs the STEP
-        if (sw.dbg_skip || getenv("DSH_SPLIT_AT")) {
+        sw.tls_on = sw.tl2_on && sw.hilo && switch_int(SW_TLS) != 0;
+        // bench experiment only (results are garbage): skip launches of a layer, bit 0 feat_proj.1, 1 feat_proj.3,
+        sw.dbg_skip = (int)switch_int(SW_DBG_SKIP);   // 2 q|k|v, 3 attention, 4 StylizationBlock (attention branch), 5 fused FFN — what each launch costs the STEP
+        const bool split_at = switch_present_now(SW_SPLIT_AT);
+        if (sw.dbg_skip || split_at) {
             static bool warned = false;
-            if (!warned) { fprintf(stderr, "[diffsheg_hip] WARNING: bench-only switches are set (DSH_DBG_SKIP=%d%s): %s\n", sw.dbg_skip, getenv("DSH_SPLIT_AT") ? ", DSH_SPLIT_AT" : "",
+            if (!warned) { fprintf(stderr, "[diffsheg_hip] WARNING: bench-only switches are set (DSH_DBG_SKIP=%d%s): %s\n", sw.dbg_skip, split_at ? ", DSH_SPLIT_AT" : "",
                                    sw.dbg_skip ? "launches are skipped, results are GARBAGE" : "sub-batch boundaries are moved"); warned = true; }
         }
-        const char* th = getenv("DSH_TL2_HL");
-        sw.tl2_hl = sw.tl2_on && sw.hilo && !(th && atoi(th) == 0);
-        if (tr && atoi(tr) > 0) sw.tls_rows = atoi(tr);
+        sw.tl2_hl = sw.tl2_on && sw.hilo && switch_int(SW_TL2_HL) != 0;
+        if (const long tr = switch_positive(SW_TLS_ROWS)) sw.tls_rows = (int)tr;
         // fp32 parity path (round 6): LayerNorm folded into q|k|v and feat_proj.1 with the row moments taken in the GEMM's own staging, the
         // StylizationBlock front (LN -> FiLM -> SiLU) in the A-operand staging of its Linear (gemm_f32_pro.hip) instead of four row kernels per
         // layer.  DSH_F32_FUSE=0: the separate row kernels of rounds 1 - 5.
-        const char* f3 = getenv("DSH_F32_FUSE");
         // Bits (measurement): 1 folded LayerNorms, 2 StylizationBlock fronts, 4 the front-less Linears on the same software-pipelined main loop,
         // 8 (with 2) the attention branch's StylizationBlock front inside the attention launch (attention.hip) instead of its Linear's staging.
-        sw.f32_bits = (std::is_same<T, float>::value && c.latent_dim == 512) ? (f3 ? atoi(f3) & 15 : 15) : 0;
+        sw.f32_bits = (std::is_same<T, float>::value && c.latent_dim == 512) ? f32_fuse_bits() : 0;
         sw.f32_fuse = sw.f32_bits != 0;
         // ... above the few-row GEMM's range only (gemm.hip: K split over the waves of a block up to DSH_GEMM_KSPLIT = 512 rows — at 34 rows the 64 x 64
         // tile launches measured 3.50 vs 2.62 ms per configs[0] evaluation); DSH_GEMM_KSPLIT=0, the reproducible mode, puts every batch size on them
-        { const char* ks = getenv("DSH_GEMM_KSPLIT"); sw.f32_min_rows = ks ? atoi(ks) : 512; }
+        sw.f32_min_rows = gemm_ksplit_rows_context();
     }
     // second instance on another stream that shares (does not own) the finalized weights; own workspace
     Denoiser(const Denoiser& o, hipStream_t s)
@@ -475,7 +469,7 @@ class Denoiser final : public DenoiserBase {
     int run_block_tail(const Layer& L, int M, int D, int nbatch, int frames, const float* film, int film_ld, int film_off0,
                        int bmod, float* hres, T* h16o, const T* hA_after_sty1, const float* res_in = nullptr, const T* y_in = nullptr);
     int prep_audio(const int64_t* t);
-    static bool aud_hoist() { static const bool on = [] { const char* e = getenv("DSH_AUD_HOIST"); return !(e && atoi(e) == 0); }(); return on; }
+    static bool aud_hoist() { return switch_int(SW_AUD_HOIST) != 0; }      // (latched per process: switches.h)
     int aud_front() {
         const int DA = cfg.audio_dim, Mc_ = batch * frames;
         if (int e = launch_pack_cols<T>(audio_f, DA, Mc_, 0, DA, DA, 2.0f, (T*)nullptr, 0, aud_x2, DA, st)) return e;
@@ -1030,8 +1024,7 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
     // h = joint_embed(x) + PE[:T]; the CFG halves start identical
     float* hc = h + (size_t)r0 * D;           // (r0 is a multiple of 32 on the tiled path: same offset arithmetic)
     T* hc16 = sizeof(T) == 4 ? nullptr : h16 + (size_t)r0 * D;
-    const char* jfe = getenv("DSH_JOINT_FUSE");          // (read per evaluation: the tests flip it inside one process)
-    const bool joint_fuse = !(jfe && atoi(jfe) == 0);
+    const bool joint_fuse = switch_int(SW_JOINT_FUSE) != 0;          // (read per evaluation: the tests flip it inside one process)
     if (tlp && sw.hilo && joint_fuse && E.joint_wf) {
         // round 6: joint_embed + bias + PE + CFG-null constant + plane split in ONE launch from the tiled bf16 channels of x (tl_embed.hip)
         if (int e = launch_tile_rows_bf16<float>(x + c0, C, Mc, w, x_in, E.joint_nf * 16, st)) return e;
@@ -1125,10 +1118,7 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
                 c.rev = next_rev();
                 const double fl = 2.0 * M * (double)(2.0 * D * cfg.ff_size + (double)D * D);
                 // (hi / lo planes: the input IS the hi plane of the residual; tl3_ffn_kernel re-reads it for 6 of the 16 Linear3 tiles only)
-                static const bool ffn_keep_hi = [] {
-                    const char* e = getenv("DSH_FFN_PB"); const char* pc = getenv("DSH_FFN_PC");
-                    return (!e || (atoi(e) & 1)) && (!pc || atoi(pc) == 1);
-                }();
+                static const bool ffn_keep_hi = ffn_keeps_hi_plane();
                 const double by = (double)M * (sw.hilo ? (D * 2 + D * 2 + D * 2 * (ffn_keep_hi ? 6.0 / 16 : 1.0) + D * 4) : (D * 2 + D * 4 * 2 + D * 2)) + (double)(2.0 * D * cfg.ff_size + (double)D * D) * 2;
                 flops_acc += fl;
                 if (prof) prof->begin(PROF_TL_FFN);
@@ -1180,8 +1170,7 @@ int Denoiser<T>::prep_audio(const int64_t* t) {
     if (int e = gemm(aud_te0, temb, D, Ra, ACT_SILU, false, nullptr, 0, 0, nullptr, 0, hid, TE)) return e;
     if (int e = gemm(aud_te2, hid, TE, Ra, ACT_SILU, false, nullptr, 0, 0, nullptr, 0, semb, TE)) return e;
     if (int e = gemm(aud_film, semb, TE, Ra, ACT_NONE, false, nullptr, 0, 0, film_aud_tab, aud_film.N, nullptr, 0)) return e;
-    const char* afe = getenv("DSH_AUD_FUSE");          // (read per evaluation: the tests flip it inside one process)
-    const bool aud_fuse = !(afe && atoi(afe) == 0);
+    const bool aud_fuse = switch_int(SW_AUD_FUSE) != 0;          // (read per evaluation: the tests flip it inside one process)
     if (aud_stream && aud_fuse) {
         // round 6: everything behind the attention in ONE launch (tl_aud.hip) from the per-condition x = 2 audio and attention output
         if (!aud_hoist()) { if (int e = aud_front()) return e; }
@@ -1191,8 +1180,7 @@ int Denoiser<T>::prep_audio(const int64_t* t) {
         // on the token-per-lane path, audio_proj([mel | aud_feat]) of both motion encoders as ONE launch writing their tiled concat operands
         // (instead of 2 x (GEMM + tile_rows))
         aproj_done = false;
-        const char* a2 = getenv("DSH_APROJ_TL");
-        if (aud_ap_bias && tl_path() && !(a2 && atoi(a2) == 0)) {
+        if (aud_ap_bias && tl_path() && switch_int(SW_APROJ_TL) != 0) {
             // (one modality alone: the active encoder's audio_proj only — encoder e's fragments at + e * 128 KB, its bias at + e * 256)
             const int me = modality == 2 ? 1 : 0, ne = modality == 0 ? 2 : 1;
             if (int e = launch_tl_aproj(audio256, aud_stream + (size_t)18 * 16384 + (size_t)me * 65536, aud_ap_bias + me * 256, ne,
@@ -1312,22 +1300,16 @@ class DualDenoiser final : public DenoiserBase {
   public:
     DualDenoiser(DenoiserBase* primary, const ModelConfig& c, hipStream_t s) : cfg_(c), st_(s) {
         inst_.emplace_back(primary);
-        const char* e = getenv("DSH_DUAL");
-        nsplit_ = e ? std::max(1, std::min(8, atoi(e) == 1 ? 2 : atoi(e))) : 3;      // 0 / 1-> off is "0"; n >= 2: at most n streams
-        if (e && atoi(e) == 0) nsplit_ = 1;
-        const char* l = getenv("DSH_DUAL_LAG");
-        lag_ = l ? atoi(l) : 3;
+        nsplit_ = dual_streams();                            // off is "0"; n >= 2: at most n streams
+        lag_ = (int)switch_int(SW_DUAL_LAG);
         // fp32 parity path: one GEMM launch of the config-2 batch (8704 rows) is only 1 - 3 rounds of co-resident tiles, so the
         // second stream's launches fill the partial last rounds (+1.5 % measured); bf16: from 12288 rows (want_split)
         // fp32 path: two streams from 4096 rows, three from 8700 (the 256-clip BEAT batch of configs[1]: 8704 rows = 17 x 512, every
         // Linear a 1.06 / 2.1 / 3.2-round launch of 64 x 64 tiles whose tail another sub-batch fills; measured 24.8 k -> 25.1 k frames/s)
         if (c.precision == 0) { min_rows_ = 4096; rows_per_stream_ = 2900; }
-        const char* rs = getenv("DSH_DUAL_ROWS");
-        if (rs && atoi(rs) > 0) rows_per_stream_ = (size_t)atoi(rs);
-        const char* mr = getenv("DSH_DUAL_MIN_ROWS");
-        if (mr && atoi(mr) > 0) min_rows_ = (size_t)atoi(mr);
-        const char* pr = getenv("DSH_PIPE_ROWS");
-        if (pr) pipe_rows_ = (size_t)atol(pr);
+        if (const long rs = switch_positive(SW_DUAL_ROWS)) rows_per_stream_ = (size_t)rs;
+        if (const long mr = switch_positive(SW_DUAL_MIN_ROWS)) min_rows_ = (size_t)mr;
+        pipe_rows_ = pipe_rows_context();
     }
     ~DualDenoiser() override {
         (void)hipDeviceSynchronize();                        // side streams may still be running a level ahead of an aborted loop
@@ -1487,8 +1469,7 @@ class DualDenoiser final : public DenoiserBase {
         Prefetch& f = pf_;
         if (begin) {
             f.active = false;
-            const char* off = getenv("DSH_LEVEL_PREFETCH");
-            if (off && atoi(off) == 0) return -1;
+            if (switch_int(SW_LEVEL_PREFETCH) == 0) return -1;
             if (level_cache_prepare(n_levels) != 0) return -1;
             char* slots = nullptr; size_t stride = 0; int nslots = 0;
             if (main->level_slots(&slots, &stride, &nslots) != 0 || nslots < n_levels) return -1;
@@ -1538,8 +1519,7 @@ class DualDenoiser final : public DenoiserBase {
     }
     // ---- pipelined small-batch loop (denoiser.h): the gesture-side twin of the whole-batch instance -----------------------------
     int pipe_begin(DenoiserBase** twin, hipStream_t* stream) override {
-        const char* off = getenv("DSH_PIPE");
-        if ((off && atoi(off) == 0) || cfg_.single_transformer || cond_.B <= 0 || split_now_ != 1 || !twin || !stream) return -1;
+        if (switch_int(SW_PIPE) == 0 || cfg_.single_transformer || cond_.B <= 0 || split_now_ != 1 || !twin || !stream) return -1;
         if (mod_ != 0) return -1;                                            // one modality alone: one chain, nothing to pipeline
         // (DDIM loops: the twin restores its head from the slots the prefetch run fills; loops without a timestep cache — DDPM — compute it)
         char* slots = nullptr; size_t stride = 0; int nslots = 0;
@@ -1656,7 +1636,7 @@ class DualDenoiser final : public DenoiserBase {
     int first_clip(int i, int ns) const {
         static const std::vector<int> at = [] {
             std::vector<int> v;
-            if (const char* e = getenv("DSH_SPLIT_AT")) { for (const char* p = e; *p;) { v.push_back(atoi(p)); while (*p && *p != ',') ++p; if (*p == ',') ++p; } }
+            if (const char* e = switch_str(SW_SPLIT_AT)) { for (const char* p = e; *p;) { v.push_back(atoi(p)); while (*p && *p != ',') ++p; if (*p == ',') ++p; } }
             return v;
         }();
         if ((int)at.size() == ns - 1 && i > 0 && i < ns) {
@@ -1755,15 +1735,14 @@ class DualDenoiser final : public DenoiserBase {
     Prefetch pf_;
     std::unique_ptr<DenoiserBase> twin_;                   // gesture-side twin of inst_[0] for the pipelined small-batch loop (pipe_begin)
     hipStream_t twin_stream_ = nullptr; hipEvent_t twin_ev_ = nullptr; bool twin_cond_ok_ = false, twin_busy_ = false;
-    size_t pipe_rows_ = 64499;                             // DDIM loops below this many token rows: one batch, two encoder streams (loop_begin)
+    size_t pipe_rows_ = 0;                                 // DDIM loops below this many token rows: one batch, two encoder streams (loop_begin)
     int sticky_B_ = 0, sticky_T_ = 0;                      // shape whose last loop ran unsplit: set_condition conditions it as one batch
     bool loop_unsplit_ = false;                            // a sampling loop is running this batch unsplit on purpose (its evaluations must not re-split it)
     bool pipe_possible() const {
         // (the pipelined loop restores every head from the slots a side-stream prefetch run fills: all three switches must be on)
-        for (const char* k : {"DSH_PIPE", "DSH_LEVEL_PREFETCH", "DSH_LEVEL_CACHE"}) { const char* v = getenv(k); if (v && atoi(v) == 0) return false; }
-        return !cfg_.single_transformer && !(prof && prof->on);
+        return pipe_switches_on() && !cfg_.single_transformer && !(prof && prof->on);
     }
-    int nsplit_ = 2, split_now_ = 1, lag_ = 3;
+    int nsplit_ = 1, split_now_ = 1, lag_ = 0;             // (nsplit_, lag_, pipe_rows_: from the switches, in the constructor)
     size_t min_rows_ = 12288;                              // batches below this many token rows run on one stream
     size_t rows_per_stream_ = 21500;                       // streams = rows / this (at least two, at most DSH_DUAL): three from 64 500 rows
 };

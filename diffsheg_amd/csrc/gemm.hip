@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "dsh_common.h"
+#include "switches.h"
 
 namespace dsh {
 
@@ -510,9 +511,7 @@ static int launch_gemm_t(const GemmArgs& a, hipStream_t s) {
     DSH_REQUIRE((a.lda * sizeof(T)) % 16 == 0 && (a.ldw * sizeof(T)) % 16 == 0, "gemm leading dims must be 16-byte multiples");
     DSH_REQUIRE(((uintptr_t)a.A % 16) == 0 && ((uintptr_t)a.W % 16) == 0, "gemm operands must be 16-byte aligned");
     // M <= 16: weight streaming (activation rows staged in LDS as fp32: up to 16 x 2048 x 4 bytes)
-    static int gemv_on = -1;
-    if (gemv_on < 0) { const char* e = getenv("DSH_GEMV"); gemv_on = e ? atoi(e) : 1; }
-    if (gemv_on && a.M <= GV_MMAX && (size_t)(a.M <= 4 ? 4 : 16) * a.K * sizeof(float) <= 128 * 1024) {
+    if (switch_int(SW_GEMV) && a.M <= GV_MMAX && (size_t)(a.M <= 4 ? 4 : 16) * a.K * sizeof(float) <= 128 * 1024) {
         static bool gv_attr = false;
         if (!gv_attr) {
             DSH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_rows_kernel<T, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
@@ -522,10 +521,9 @@ static int launch_gemm_t(const GemmArgs& a, hipStream_t s) {
         return launch_gemv_t<T>(a, s);
     }
     // fp32, a few hundred rows at most: K split over the waves of a 32 x 32-tile block (gemm_nt_ksplit_kernel); DSH_GEMM_KSPLIT=n
-    // sets the row limit (default 512; 0: off)
+    // sets the row limit (0: off)
     if constexpr (sizeof(T) == 4) {
-        static const int ks_rows = [] { const char* e = getenv("DSH_GEMM_KSPLIT"); return e ? atoi(e) : 512; }();
-        if (a.M <= ks_rows) {
+        if (a.M <= gemm_ksplit_rows()) {
             static bool ks_attr = false;
             if (!ks_attr) {
                 DSH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_ksplit_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, KS_LDS));
@@ -539,10 +537,9 @@ static int launch_gemm_t(const GemmArgs& a, hipStream_t s) {
     }
     static int variant = -1, tile_sel = 1;
     if (variant < 0) {
-        const char* e = getenv("DSH_GEMM_VARIANT");
-        variant = e ? atoi(e) : 1;
-        const char* ts = getenv("DSH_GEMM_TILE");        // 0: always 128 x 128; 2 / 3 / 4: always 128 x 64 / 64 x 64 / 64 x 32 (measurement)
-        tile_sel = ts ? atoi(ts) : 1;
+        variant = (int)switch_int(SW_GEMM_VARIANT);
+        // DSH_GEMM_TILE 0: always 128 x 128; 2 / 3 / 4: always 128 x 64 / 64 x 64 / 64 x 32 (measurement)
+        tile_sel = (int)switch_int(SW_GEMM_TILE);
         DSH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<T, 0, 2, 2>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, gemm_lds_bytes(2, 2)));
         DSH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<T, 1, 2, 2>),

@@ -26,6 +26,7 @@
 
 #include "dsh_common.h"
 #include "dsh_kernels.h"
+#include "switches.h"
 
 namespace dsh {
 
@@ -585,14 +586,12 @@ int launch_gemm_f32_pro(const GemmProArgs& a, hipStream_t s) {
         attr = true;
     }
     // operands through LDS-DMA (buffer addressing: 32-bit byte offsets) unless DSH_GP_DMA=0
-    static const int dma_on = [] { const char* e = getenv("DSH_GP_DMA"); return e ? atoi(e) : 1; }();
-    bool dma = dma_on && (size_t)a.N * a.ldw * 4 < ((size_t)1 << 31);
+    bool dma = switch_int(SW_GP_DMA) != 0 && (size_t)a.N * a.ldw * 4 < ((size_t)1 << 31);
     for (int i = 0; i < (a.pro == 1 ? 4 : 1); ++i) dma = dma && (!a.seg[i] || (size_t)a.M * a.seg_ld[i] * 4 < ((size_t)1 << 31));
     GemmProArgs b = a;
     {   // bench-only: DSH_GP_ABL drops parts of the register-staged main loop (DSH_GP_DMA=0, front-less launches) — results are garbage
         static const int abl = [] {
-            const char* e = getenv("DSH_GP_ABL");
-            const int v = e ? atoi(e) : 0;
+            const int v = (int)switch_int(SW_GP_ABL);
             if (v) fprintf(stderr, "[diffsheg_hip] WARNING: DSH_GP_ABL=%d is set: fp32 GEMM launches skip parts of their main loop, results are GARBAGE\n", v);
             return v;
         }();

@@ -6,6 +6,8 @@
 
 #include <vector>
 
+#include "switches.h"
+
 namespace dsh {
 
 // 0-3: kernel families; 4-9: the token-per-lane Linear instantiations the denoiser launches
@@ -41,7 +43,7 @@ inline const ProfClassInfo& prof_class_info(int cls, bool fp32) {
     static const ProfClassInfo attn32 = {"linear_attention_f32_mfma(_sty)_kernel<TM>", "fp32 path: linear self-attention core on the exact-fp32 matrix pipe (round 6; with the attention branch's StylizationBlock front behind it for windows of up to 64 frames)"};
     static const ProfClassInfo ffn3 = {"tl3_ffn_kernel<false>", "ffn.linear1 -> GELU -> ffn.linear2 -> StylizationBlock(ffn) -> + h (one launch; tl3_ffn.hip)"};
     if (cls < 0 || cls >= PROF_NCLASS) return none;
-    if (cls == PROF_TL_FFN) { const char* fv = getenv("DSH_FFN_V"); if (!(fv && atoi(fv) == 2)) return ffn3; }   // (as Denoiser reads it)
+    if (cls == PROF_TL_FFN && ffn_generation() == 3) return ffn3;
     if (fp32 && cls == PROF_ATTN) return attn32;
     return (fp32 && cls == PROF_GEMM) ? gemm32 : tab[cls];
 }

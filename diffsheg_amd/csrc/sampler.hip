@@ -396,9 +396,8 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
     int64_t step_idx = 0;
     // graphs only where launches dominate (a few thousand token rows), never while profiling events are recorded,
     // and never on the legacy NULL stream (it cannot be captured)
-    static const size_t graph_rows = [] { const char* e = getenv("DSH_GRAPH_ROWS"); return e ? (size_t)atol(e) : (size_t)4096; }();
-    const bool small = (size_t)B * den->frames <= graph_rows;
-    const bool use_graph = st != nullptr && small && !(prof && prof->on) && getenv("DSH_NO_GRAPH") == nullptr;
+    const bool small = (size_t)B * den->frames <= (size_t)switch_int(SW_GRAPH_ROWS);
+    const bool use_graph = st != nullptr && small && !(prof && prof->on) && !switch_present(SW_NO_GRAPH);
     int n_eval = 0;
     drop_graph();
     // timestep cache (denoiser.h): worth it when the schedule revisits levels (out-painting jump schedule: 63 evaluations
@@ -409,15 +408,13 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
     std::vector<int64_t> tv;             // level -> model timestep
     size_t pf_next = 0;                  // order[0 .. pf_next) have been handed to the prefetch stream
     // (the side-stream head and the two-stream encoder pipeline also pay above the graph range, up to where batches are split over sub-batch
-    //  streams: DSH_PIPE_ROWS, default below)
-    static const size_t pipe_rows = [] { const char* e = getenv("DSH_PIPE_ROWS"); return e ? (size_t)atol(e) : (size_t)64499; }();
-    const bool small_pf = (size_t)B * den->frames <= pipe_rows;
+    //  streams: DSH_PIPE_ROWS)
+    const bool small_pf = (size_t)B * den->frames <= pipe_rows();
     if ((small || small_pf) && o.kind == 0 && !split) {
         std::vector<int> cnt(o.respacing, 0);
         int evals = 0, distinct = 0;
         for (const SamplerStep& sp : steps) if (sp.kind != STEP_UNDO) { ++evals; if (cnt[sp.level]++ == 0) { ++distinct; order.push_back(sp.level); } }
-        const char* lc = getenv("DSH_LEVEL_CACHE");
-        const bool cache_on = !(lc && atoi(lc) == 0);
+        const bool cache_on = switch_int(SW_LEVEL_CACHE) != 0;
         // side-stream prefetch of every scheduled level (also pays for schedules without repeats); else the inline cache
         // (one level is queued now, the others one evaluation ahead of their first use: the host never runs far in front of
         //  the main chain, and the main chain never waits for the host to finish queueing 25 levels)
@@ -452,15 +449,13 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
         std::vector<int> cnt(o.respacing, 0);
         int evals = 0, distinct = 0;
         for (const SamplerStep& sp : steps) if (sp.kind != STEP_UNDO) { ++evals; if (cnt[sp.level]++ == 0) ++distinct; }
-        const char* lc = getenv("DSH_LEVEL_CACHE");
-        const bool cache_on = !(lc && atoi(lc) == 0);
-        if (evals > distinct && cache_on) {
+        if (evals > distinct && switch_int(SW_LEVEL_CACHE) != 0) {
             split_cache = true;
             for (const Sub& u : subs) split_cache = split_cache && u.d->level_cache_prepare(o.respacing) == 0;
             if (split_cache) level_seen.assign(o.respacing, 0);
         }
     }
-    const int lag = [] { const char* l = getenv("DSH_DUAL_LAG"); return l ? atoi(l) : 3; }();
+    const int lag = (int)switch_int(SW_DUAL_LAG);
     bool first_eval = true;
     for (const SamplerStep& sp : steps) {
         const int k = sp.level;

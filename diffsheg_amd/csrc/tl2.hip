@@ -30,6 +30,7 @@
 #include "dsh_common.h"
 #include "dsh_kernels.h"
 #include "tl_common.h"
+#include "switches.h"
 
 namespace dsh {
 
@@ -948,7 +949,7 @@ void tl_stagger_config(int which, int* groups, int* sleep) {
     struct Cfg { int g = 0, sl = 0, mask = 7; };
     static const Cfg cfg = [] {                       // (a magic static: contexts launching from several host threads race on nothing)
         Cfg c;
-        if (const char* e = getenv("DSH_STAGGER")) { int a = 0, b = 0, m = 7; const int n = sscanf(e, "%d,%d,%d", &a, &b, &m); if (n >= 2) { c.g = a; c.sl = b; if (n >= 3) c.mask = m; } }
+        if (const char* e = switch_str(SW_STAGGER)) { int a = 0, b = 0, m = 7; const int n = sscanf(e, "%d,%d,%d", &a, &b, &m); if (n >= 2) { c.g = a; c.sl = b; if (n >= 3) c.mask = m; } }
         return c;
     }();
     const bool on = cfg.g > 1 && ((cfg.mask >> which) & 1);
@@ -983,7 +984,7 @@ int launch_tl2_linear(const TlArgs& a, int pro, hipStream_t s) {
     if (mblocks < 128) { tpb = 1; while (tpb < ntiles && mblocks * ceil_div(ntiles, tpb) > 256) ++tpb; }
     TlArgs b = a;
     b.tiles_per_block = tpb;
-    { const char* re = getenv("DSH_TL2_ROT"); b.rot = (re && atoi(re) != 0) ? 1 : 0; }      // rotated weight-stream order per block (rolling loop only); read per launch
+    b.rot = switch_int(SW_TL2_ROT) != 0 ? 1 : 0;      // rotated weight-stream order per block (rolling loop only); read per launch
     tl_stagger_config(pro == 1 ? 1 : 2, &b.stag_groups, &b.stag_sleep);
     if (mblocks < 256) { b.stag_groups = 0; b.stag_sleep = 0; }
     const dim3 grid(mblocks, ceil_div(ntiles, tpb)), block(a.K == 512 ? 512 : 256);
@@ -1033,15 +1034,13 @@ int launch_tl2_linear(const TlArgs& a, int pro, hipStream_t s) {
     DSH_REQUIRE(fn != nullptr || a.Rlo, "tl2_linear: this (prologue, residual, outputs, activation) combination is not instantiated");
     // rolling main loop (round 5) for the MFMA-bound bf16-out instantiations the step runs at whole-chip token counts: q|k|v (folded
     // LayerNorm) and feat_proj.1 (folded concat-LayerNorm, SiLU).  DSH_TL2_ROLL=0: the round-2 loop.  Results are bit-identical (same MFMA order, same epilogue expressions).
-    const char* roll_e = getenv("DSH_TL2_ROLL");       // (read per launch: the op-level tests flip it inside one process)
-    const bool roll_on = !(roll_e && atoi(roll_e) == 0);
+    const bool roll_on = switch_int(SW_TL2_ROLL) != 0;       // (read per launch: the op-level tests flip it inside one process)
     if (roll_on && !has_r && out == 2 && !b.clk && tpb == ntiles && ntiles >= 2) {
         kern_t rf = nullptr;
         if (a.K == 512 && pro == 1 && a.act == ACT_NONE) rf = tl2_linear_kernel<512, 1, false, 2, ACT_NONE, false, true>;
         else if (a.K == 1024 && pro == 3 && a.act == ACT_SILU) {
             // trailing all-zero fragments of the concat row are not multiplied (DSH_TL2_KSKIP=0: all 64)
-            const char* ke = getenv("DSH_TL2_KSKIP");
-            const int nz = (ke && atoi(ke) == 0) ? 0 : (1024 - round_up(a.kreal, 16)) / 16;
+            const int nz = switch_int(SW_TL2_KSKIP) == 0 ? 0 : (1024 - round_up(a.kreal, 16)) / 16;
             rf = nz >= 8 ? (kern_t)tl2_linear_kernel<1024, 3, false, 2, ACT_SILU, false, true, false, 8>
                : nz >= 1 ? (kern_t)tl2_linear_kernel<1024, 3, false, 2, ACT_SILU, false, true, false, 1> : (kern_t)tl2_linear_kernel<1024, 3, false, 2, ACT_SILU, false, true>;
         }

@@ -29,6 +29,7 @@
 #include "dsh_common.h"
 #include "dsh_kernels.h"
 #include "tl_common.h"
+#include "switches.h"
 
 namespace dsh {
 
@@ -748,12 +749,10 @@ int launch_tl3_ffn(const Tl2FfnArgs& a, hipStream_t s) {
     // first half of their phase — measured and rejected (profiles/r05_e_ffn_block_timeline.txt: pass B 35.3 k -> 38.6 k cycles; the phase
     // tops it was meant to relieve take 1.7 k of those cycles, the time goes into waiting for the residual fragments, which the early
     // epilogue needs half a phase sooner).  (Read per launch: the op-level tests flip it inside one process.)
-    const char* pc_e = getenv("DSH_FFN_PC");
-    const int pc = pc_e ? std::min(2, std::max(0, atoi(pc_e))) : 1;
+    const int pc = ffn_pc();
     // DSH_FFN_PB (with DSH_FFN_PC=1, hi / lo planes; default 1): bit 0 = the hi plane of the residual kept in registers — only where the
     // kernel's input IS that plane, as in the denoiser's layers; bit 1 = the pass-B residual requested one phase earlier
-    const char* pb_e = getenv("DSH_FFN_PB");
-    int pb = (pc == 1 && a.Rhi) ? (pb_e ? (atoi(pb_e) & 3) : 1) : 0;
+    int pb = (pc == 1 && a.Rhi) ? ffn_pb() : 0;
     if (reinterpret_cast<const void*>(a.X) != reinterpret_cast<const void*>(a.Rhi)) pb &= ~1;
     static const bool attr = [] {
         auto set = [](const void* f) { return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, F3_LDS) == hipSuccess; };

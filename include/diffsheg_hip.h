@@ -83,6 +83,20 @@ typedef struct dsh_sampler_opts {
 const char* dsh_last_error(void);
 const char* dsh_version(void);
 
+/* ---- runtime switches (the DSH_* environment variables; csrc/switches.h holds the one table) -- no GPU needed -------------------- */
+/* dsh_switch_count(): entries of the table.
+ * dsh_switch_info(i, ...): entry i — the variable's name, its default as text, when it is read (0 PROCESS: latched by the first read in
+ *   the process; 1 CONTEXT: at dsh_create; 2 CALL: on every call that uses it), its class (0 product, 1 A/B with bit-identical arms,
+ *   2 A/B with round-off between the arms, 3 bench only: results may be garbage) and one line of meaning; static strings, any output
+ *   pointer may be null.  Returns the kind (0 integer, 1 present-or-absent, 2 string), -1 for an index outside the table.
+ * dsh_switch_read(name, &is_set, &value): the switch as the library itself reads it now — the latched value of a PROCESS entry (this
+ *   read latches it if nothing has yet), a fresh look otherwise; value = atoi of the text, the entry's default when unset.  `name`
+ *   may also be one of the library's derivations over the switches (dual_streams, ffn_generation, ffn_pc, ffn_pb, hilo_denoiser,
+ *   hilo_op, pipe_switches_on, ...: kSwitchDerived in switches.h): value = what the library derives, is_set = 0.  -1: unknown name. */
+int32_t dsh_switch_count(void);
+int dsh_switch_info(int32_t i, const char** name, const char** default_text, int32_t* when, int32_t* cls, const char** help);
+int dsh_switch_read(const char* name, int32_t* is_set, int64_t* value);
+
 /* ---- lifecycle ------------------------------------------------------------------------------ */
 /* `hip_stream` is a hipStream_t (NULL = default stream) on the current device. */
 int dsh_create(const dsh_model_config* cfg, void* hip_stream, dsh_ctx** out);

@@ -12,23 +12,11 @@ pytestmark = pytest.mark.gpu
 from diffsheg_amd.config import get_config  # noqa: E402
 from diffsheg_amd.synthetic import make_inputs  # noqa: E402
 from oracle import denoiser_ref  # noqa: E402
-from util import golden, gpu_model, max_abs, synthetic_sd  # noqa: E402
+from util import HOIST_CASE, eval_call as _call, golden, gpu_model, hoist_latched as _hoist_latched, max_abs, synthetic_sd  # noqa: E402
 
 FP32_ATOL = 1e-3
 # bf16 path, one evaluation, |eps| ~ 3.5: ~3x the error measured on MI355X (max 1.9e-2, rms 5e-3; printed by the tests)
 BF16_MAX, BF16_RMS = 6e-2, 1.5e-2
-
-
-def _call(model, cfg, inp, t, c1, c2):
-    B, T = inp["x_T"].shape[:2]
-    shape_e = (B, T, cfg.expression_dim)
-    c1t = c1 if torch.is_tensor(c1) else torch.full((B,), float(c1))
-    c2t = c2 if torch.is_tensor(c2) else torch.full((B,), float(c2))
-    sa = [c1t.view(B, 1, 1).expand(shape_e), c2t.view(B, 1, 1).expand(shape_e)]
-    tt = t if torch.is_tensor(t) else torch.full((B,), int(t), dtype=torch.long)
-    return model(inp["x_T"].cuda(), tt.cuda(), sqrt_alphas=sa, audio_emb=inp["audio_emb"].cuda(),
-                 length=torch.full((B,), T), person_id=inp["person_id"].cuda(),
-                 add_cond={"pretrain_aud_feat": inp["pretrain_aud_feat"].cuda()}, pe_type="pe_sinu", y={})
 
 
 @pytest.mark.parametrize("ds", ["beat", "show"])
@@ -333,19 +321,19 @@ def test_fused_encoder_aud_tail_matches_reference_tap(monkeypatch):
     assert e1 < 2e-2 and e1 < 1.5 * e0 + 2e-3
 
 
-@pytest.mark.parametrize("switch", ["DSH_JOINT_FUSE", "DSH_APROJ_TL", "DSH_AUD_HOIST"])
+@pytest.mark.parametrize("switch", ["DSH_JOINT_FUSE", "DSH_APROJ_TL"])
 def test_round6_token_per_lane_launches_agree_with_the_launches_they_replace(switch, monkeypatch):
     """Round 6: the layer-0 seed (joint_embed + PE + CFG-null constant + plane split, tl_embed.hip) and audio_proj as token-per-lane
-    launches, and encoder_aud's front computed once per condition, against the GEMM + row-kernel sequences of round 5 (switch = 0) on the
-    bf16 path: the same bf16 operands, fp32 accumulation in ascending k, the same epilogue expressions — the whole evaluation agrees to
-    fp32 round-off of the intermediate tensors (the seed and the hoist: bit for bit)."""
+    launches against the GEMM + row-kernel sequences of round 5 (switch = 0) on the bf16 path: the same bf16 operands, fp32 accumulation
+    in ascending k, the same epilogue expressions — the whole evaluation agrees to fp32 round-off of the intermediate tensors (the
+    seed: bit for bit)."""
     cfg = get_config("show")
     model = gpu_model("show", "bf16")
-    inp = make_inputs(cfg, 3, frames=88, seed=41)
+    inp = HOIST_CASE.inputs(cfg)
     outs = {}
     for sw in ("1", "0"):
         monkeypatch.setenv(switch, sw)
-        outs[sw] = _call(model, cfg, inp, 720, 3.3, 3.1).cpu()
+        outs[sw] = _call(model, cfg, inp, *HOIST_CASE.args).cpu()
     d = max_abs(outs["0"], outs["1"])
     print(f"[{switch}] max |eps(new) - eps(round-5 launches)| = {d:.3e}")
     assert torch.isfinite(outs["1"]).all()
@@ -355,3 +343,25 @@ def test_round6_token_per_lane_launches_agree_with_the_launches_they_replace(swi
         assert d < BF16_MAX
     else:
         assert torch.equal(outs["0"], outs["1"])
+
+
+def test_aud_hoist_agrees_with_the_front_recomputed_in_every_evaluation(tmp_path):
+    """Round 6: encoder_aud's timestep-independent front computed once per condition against the same launches in every evaluation
+    (DSH_AUD_HOIST=0), bf16 path, the batch of the test above: bit for bit.
+
+    DSH_AUD_HOIST is latched by the first read in a process (PROCESS in csrc/switches.h), so flipping it here would compare one arm
+    with itself: this process evaluates the arm its library has latched, a fresh worker process (tests/aud_hoist_worker.py) the other."""
+    import os
+    import subprocess
+    import sys
+    cfg = get_config("show")
+    mine = str(_hoist_latched())
+    other = "0" if mine == "1" else "1"
+    outs = {mine: _call(gpu_model("show", "bf16"), cfg, HOIST_CASE.inputs(cfg), *HOIST_CASE.args).cpu()}
+    f = str(tmp_path / "aud_hoist.pt")
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "aud_hoist_worker.py"), f],
+                       env=dict(os.environ, DSH_AUD_HOIST=other), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "AUD_HOIST_WORKER_OK" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])
+    outs[other] = torch.load(f)
+    assert torch.isfinite(outs["1"]).all()
+    assert torch.equal(outs["0"], outs["1"])
