@@ -126,6 +126,25 @@ SYMBOLS = {
     "dsh_fgd_encode": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "dsh_batch_metrics_result_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "dsh_op_batch_metrics": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "dsh_mel_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
+    "dsh_mel_destroy": (C.c_int, [_P]),
+    "dsh_mel_num_frames": (C.c_int64, [_P, C.c_int64]),
+    "dsh_mel_debug_tables": (C.c_int, [_P, C.POINTER(C.c_int32), _P, _P]),
+    "dsh_mel_compute": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P]),
+    "dsh_resample_poly_len": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "dsh_op_resample_poly": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    "dsh_op_softmax_attention": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "dsh_hubert_create": (C.c_int, [_P, _P, C.POINTER(_P)]),
+    "dsh_hubert_destroy": (C.c_int, [_P]),
+    "dsh_hubert_load_tensor": (C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), C.c_int32]),
+    "dsh_hubert_finalize": (C.c_int, [_P]),
+    "dsh_hubert_debug_packed": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P]),
+    "dsh_hubert_num_frames": (C.c_int64, [_P, C.c_int64]),
+    "dsh_hubert_set_chunk_pass": (C.c_int, [_P, C.c_int32]),
+    "dsh_hubert_encode": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P]),
+    "dsh_op_pos_conv": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "dsh_op_conv0_ln_gelu": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "dsh_op_conv_ln_gelu": (C.c_int, [_P, _P] + [C.c_int32] * 6 + [_P, _P, _P, _P, _P]),
 }
 
 METRICS_HEADER = 5      # DSH_METRICS_HEADER: 8-byte words in front of the per-group diversity values of dsh_op_batch_metrics

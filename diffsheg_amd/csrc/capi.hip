@@ -10,7 +10,9 @@
 
 #include "../../include/diffsheg_hip.h"
 #include "denoiser.h"
+#include "audio_front.h"
 #include "fgd.h"
+#include "hubert.h"
 #include "sampler.h"
 
 namespace dsh {
@@ -1358,6 +1360,164 @@ int dsh_op_batch_metrics(void* hip_stream, const float* outputs, const float* mo
                          int32_t b_div, void* result_dev) {
     API_BEGIN
     return dsh::launch_batch_metrics(outputs, motions, B, T, C, joint_dim, b_div, result_dev, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+// ---- audio front: mel spectrogram, polyphase resampler, softmax attention core (audio_front.hip) ----------------------
+struct dsh_mel {
+    std::unique_ptr<dsh::MelFront> m;
+};
+
+int dsh_mel_create(int32_t sr, int32_t n_fft, int32_t hop, int32_t n_mels, void* hip_stream, dsh_mel** out) {
+    API_BEGIN
+    DSH_REQUIRE(out, "null argument");
+    DSH_REQUIRE(sr > 0 && n_fft >= 32 && n_fft % 32 == 0 && n_fft <= 16384, "dsh_mel_create: n_fft must be a multiple of 32, at most 16384");
+    DSH_REQUIRE(hop >= 4 && hop % 4 == 0, "dsh_mel_create: hop must be a positive multiple of 4 (16-byte frame starts)");
+    DSH_REQUIRE(n_mels >= 4 && n_mels % 4 == 0 && n_mels <= 1024, "dsh_mel_create: n_mels must be a multiple of 4, at most 1024");
+    auto h = std::make_unique<dsh_mel>();
+    h->m.reset(new dsh::MelFront(sr, n_fft, hop, n_mels, reinterpret_cast<hipStream_t>(hip_stream)));
+    *out = h.release();
+    return 0;
+    API_END
+}
+
+int dsh_mel_destroy(dsh_mel* h) {
+    API_BEGIN
+    delete h;
+    return 0;
+    API_END
+}
+
+int64_t dsh_mel_num_frames(const dsh_mel* h, int64_t len) { return h ? h->m->num_frames(len) : -1; }
+
+int dsh_mel_debug_tables(const dsh_mel* h, int32_t* dims3, float* dft, float* fb) {
+    API_BEGIN
+    DSH_REQUIRE(h, "null handle");
+    if (dims3) { dims3[0] = h->m->bins(); dims3[1] = h->m->n_fft(); dims3[2] = h->m->n_mels(); }
+    if (dft) memcpy(dft, h->m->dft().data(), h->m->dft().size() * sizeof(float));
+    if (fb) memcpy(fb, h->m->fb().data(), h->m->fb().size() * sizeof(float));
+    return 0;
+    API_END
+}
+
+int dsh_mel_compute(dsh_mel* h, const float* wave, int32_t batch, int64_t len, float* mel) {
+    API_BEGIN
+    DSH_REQUIRE(h, "null handle");
+    return h->m->compute(wave, batch, len, mel);
+    API_END
+}
+
+int64_t dsh_resample_poly_len(int64_t n, int32_t up, int32_t down) { return n >= 0 && up > 0 && down > 0 ? dsh::resample_poly_len(n, up, down) : -1; }
+
+int dsh_op_resample_poly(void* hip_stream, const float* x, int32_t batch, int64_t n, int32_t up, int32_t down, const float* taps_dev, int32_t n_taps,
+                         float* y) {
+    API_BEGIN
+    return dsh::launch_resample_poly(x, batch, n, up, down, taps_dev, n_taps, y, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_softmax_attention(void* hip_stream, const float* qkv, int32_t B, int32_t M, int32_t H, float* out) {
+    API_BEGIN
+    return dsh::launch_softmax_attention(qkv, B, M, H, out, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+// ---- HuBERT encoder (hubert.hip) ----------------------------------------------------------------------------------------
+struct dsh_hubert {
+    std::unique_ptr<dsh::HubertEncoder> enc;
+};
+
+int dsh_hubert_create(const dsh_hubert_config* cfg, void* hip_stream, dsh_hubert** out) {
+    API_BEGIN
+    DSH_REQUIRE(cfg && out, "null argument");
+    dsh::HubertConfig c{};
+    c.hidden = cfg->hidden; c.layers = cfg->layers; c.heads = cfg->heads; c.intermediate = cfg->intermediate;
+    for (int i = 0; i < 7; ++i) { c.conv_dim[i] = cfg->conv_dim[i]; c.conv_kernel[i] = cfg->conv_kernel[i]; c.conv_stride[i] = cfg->conv_stride[i]; }
+    c.pos_kernel = cfg->pos_kernel; c.pos_groups = cfg->pos_groups; c.ln_eps = cfg->ln_eps;
+    if (int e = dsh::HubertEncoder::validate(c)) return e;
+    auto h = std::make_unique<dsh_hubert>();
+    h->enc.reset(new dsh::HubertEncoder(c, reinterpret_cast<hipStream_t>(hip_stream)));
+    *out = h.release();
+    return 0;
+    API_END
+}
+
+int dsh_hubert_destroy(dsh_hubert* h) {
+    API_BEGIN
+    delete h;
+    return 0;
+    API_END
+}
+
+int dsh_hubert_load_tensor(dsh_hubert* h, const char* name, const float* host_data, const int64_t* shape, int32_t ndim) {
+    API_BEGIN
+    DSH_REQUIRE(h && name && (shape || ndim == 0) && ndim >= 0, "null argument");
+    return h->enc->load(name, host_data, shape, ndim);
+    API_END
+}
+
+int dsh_hubert_finalize(dsh_hubert* h) {
+    API_BEGIN
+    DSH_REQUIRE(h, "null handle");
+    return h->enc->finalize();
+    API_END
+}
+
+int dsh_hubert_debug_packed(const dsh_hubert* h, int32_t kind, int32_t layer, int32_t* dims2, float* W, float* bias, float* fc) {
+    API_BEGIN
+    DSH_REQUIRE(h, "null handle");
+    return h->enc->debug_packed(kind, layer, dims2, W, bias, fc);
+    API_END
+}
+
+int64_t dsh_hubert_num_frames(const dsh_hubert* h, int64_t n) { return h ? h->enc->num_frames(n) : -1; }
+
+int dsh_hubert_set_chunk_pass(dsh_hubert* h, int32_t rows) {
+    API_BEGIN
+    DSH_REQUIRE(h && rows >= 1, "dsh_hubert_set_chunk_pass: a handle and at least one row per pass");
+    h->enc->set_chunk_pass(rows);
+    return 0;
+    API_END
+}
+
+int dsh_hubert_encode(dsh_hubert* h, const float* x, int32_t batch, int64_t n, float* out) {
+    API_BEGIN
+    DSH_REQUIRE(h, "null handle");
+    return h->enc->encode(x, batch, n, out);
+    API_END
+}
+
+int dsh_op_pos_conv(void* hip_stream, const float* h, int32_t B, int32_t M, int32_t hidden, int32_t groups, int32_t pos_kernel, const float* W,
+                    const float* bias, float* out) {
+    API_BEGIN
+    return dsh::launch_pos_conv(h, B, M, hidden, groups, pos_kernel, W, bias, out, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_conv0_ln_gelu(void* hip_stream, const float* x, int32_t B, int64_t n, int32_t C, int32_t k, int32_t stride, const float* W, const float* bias,
+                         const float* gamma, const float* beta, float* y) {
+    API_BEGIN
+    DSH_REQUIRE(k >= 1 && stride >= 1 && n >= k, "dsh_op_conv0_ln_gelu: the signal is shorter than the kernel");
+    return dsh::launch_conv0_ln_gelu(x, B, n, (int)((n - k) / stride + 1), C, k, stride, W, bias, gamma, beta, y, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_conv_ln_gelu(void* hip_stream, const float* x, int32_t B, int32_t L, int32_t Cin, int32_t Cout, int32_t k, int32_t stride, const float* W,
+                        const float* bias, const float* gamma, const float* beta, float* y) {
+    API_BEGIN
+    DSH_REQUIRE(x && W && bias && gamma && beta && y, "dsh_op_conv_ln_gelu: null pointer");
+    DSH_REQUIRE(B >= 1 && k >= 1 && stride >= 1 && L >= k && Cin % 32 == 0 && Cout % 32 == 0 && Cin > 0 && Cout > 0,
+                "dsh_op_conv_ln_gelu: channel counts must be multiples of 32 and the clip at least one kernel long");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    const int Lo = (L - k) / stride + 1;
+    DSH_REQUIRE((long long)B * Lo < (1ll << 31), "dsh_op_conv_ln_gelu: batch too large");
+    dsh::ConvGemmArgs a{};
+    a.X = x; a.x_clip = (long long)L * Cin; a.x_step = stride * Cin;
+    a.W = W; a.ldw = k * Cin; a.bias = bias;
+    a.Y = y; a.y_clip = (long long)Lo * Cout;
+    a.Tout = Lo; a.M = B * Lo; a.N = Cout; a.Kreal = k * Cin; a.Kp = k * Cin;
+    if (int e = dsh::launch_conv_gemm_f32(a, s)) return e;
+    return dsh::launch_ln_act_rows(y, (long long)B * Lo, Cout, gamma, beta, 1e-5f, 1, y, s);
     API_END
 }
 

@@ -466,6 +466,23 @@ class DDPMTrainer:
                 pieces[b].append(out[r, :n] if ii == n_win[b] - 1 else out[r, :step])
         return [torch.cat(p, 0) for p in pieces]
 
+    # ---- a speech signal in, motion out -------------------------------------------------------
+    def sample_custom_audio(self, wave16k, p_id: torch.Tensor, frontend, **kw):
+        """``test_custom_aud`` (ddpm_show_trainer.py:944-1100) for a 16 kHz signal: ``frontend.features(wave16k)`` (an
+        :class:`diffsheg_amd.audio.AudioFrontEnd`: mel ``[N, 128]`` and HuBERT ``[N, 1024]`` on the device) followed by
+        :meth:`sample_arbitrary_len`; ``kw`` (``seed=``, ``pose_rep=``, ``modality=``, ``cond_scale=`` ...) passes through.  A list of
+        signals is sampled as chains of different lengths (the ``lengths=`` form: a list of results).  The reference's ``.wav`` branch
+        hands HuBERT the 22 050 Hz signal of ``librosa.load`` as if it were 16 kHz; this call takes a 16 kHz signal, the ``.npy``
+        branch and what the model was trained on."""
+        if isinstance(wave16k, (list, tuple)):
+            feats = [frontend.features(w) for w in wave16k]
+            lengths = [int(m.shape[0]) for m, _ in feats]
+            mel = torch.nn.utils.rnn.pad_sequence([m for m, _ in feats], batch_first=True)
+            hub = torch.nn.utils.rnn.pad_sequence([h for _, h in feats], batch_first=True)
+            return self.sample_arbitrary_len(mel, p_id, {"pretrain_aud_feat": hub}, lengths=lengths, **kw)
+        mel, hub = frontend.features(wave16k)
+        return self.sample_arbitrary_len(mel[None], p_id, {"pretrain_aud_feat": hub[None]}, **kw)
+
     # ---- motion in-betweening: one window pinned at both ends ---------------------------------
     def sample_inbetween(self, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor],
                          head: torch.Tensor, tail: torch.Tensor, *, tail_blend: bool = True, seed: Optional[int] = None,

@@ -539,6 +539,107 @@ int64_t dsh_batch_metrics_result_bytes(int32_t B, int32_t T, int32_t C, int32_t 
 int dsh_op_batch_metrics(void* hip_stream, const float* outputs, const float* motions, int32_t B, int32_t T, int32_t C, int32_t joint_dim,
                          int32_t b_div, void* result_dev);
 
+/* ---- audio front (trainers/ddpm_show_trainer.py:944-1100, test_custom_aud) -------------------------------------------------- */
+/* The mel spectrogram test_custom_aud computes: librosa.feature.melspectrogram(y, sr, hop_length = hop, n_mels)[..., :-1] (power 2, no
+ * logarithm, center = True with reflect padding, periodic Hann window of n_fft samples, Slaney filterbank from 0 to sr / 2 with Slaney
+ * normalisation), fp32 on the exact-fp32 matrix pipe.  The reference's call is (18000, 2048, 1200, 128).  A handle of its own, bound to one
+ * (device, stream), not thread-safe; hip_stream as for dsh_create (NULL: a stream of its own).  n_fft a multiple of 32, hop and n_mels
+ * multiples of 4.  Creating the handle builds two tables on the host in fp64 and stores them as fp32; no device is touched before the first
+ * dsh_mel_compute.
+ *   dft [2 (n_fft / 2 + 1), n_fft]   row k = w[i] cos(2 pi k i / n_fft), row n_fft / 2 + 1 + k = w[i] sin(2 pi k i / n_fft),
+ *                                    w[i] = 0.5 - 0.5 cos(2 pi i / n_fft); the angle is reduced exactly, (k i) mod n_fft, before cos / sin
+ *   fb  [n_mels, n_fft / 2 + 1]      mel(f) = 3 f / 200 below 1000 Hz, 15 + 27 ln(f / 1000) / ln 6.4 above; n_mels + 2 points m_i equally
+ *                                    spaced in mel from 0 to sr / 2; fb[i, k] = max(0, min((f_k - m_i) / (m_{i+1} - m_i),
+ *                                    (m_{i+2} - f_k) / (m_{i+2} - m_{i+1}))) * 2 / (m_{i+2} - m_i) at f_k = k sr / n_fft */
+typedef struct dsh_mel dsh_mel;
+int dsh_mel_create(int32_t sr, int32_t n_fft, int32_t hop, int32_t n_mels, void* hip_stream, dsh_mel** out);
+int dsh_mel_destroy(dsh_mel* h);
+/* Frames of a signal of len samples: len / hop (of the 1 + len / hop centred frames the reference drops the last), or -1 when
+ * len < n_fft / 2 + 1 (the reflect padding needs that many samples) or len < hop (no frame). */
+int64_t dsh_mel_num_frames(const dsh_mel* h, int64_t len);
+/* Test helper, host only (runs without a GPU): dims3 = {n_fft / 2 + 1, n_fft, n_mels} and the two tables above (nullable host buffers). */
+int dsh_mel_debug_tables(const dsh_mel* h, int32_t* dims3, float* dft, float* fb);
+/* mel[B, N, n_mels] (N = dsh_mel_num_frames(len)) from wave [B, len], both device fp32, mel 16-byte aligned.  Frame j is samples
+ * [hop j - n_fft / 2, hop j + n_fft / 2) of the reflect-padded signal.  Four launches on the handle's stream, asynchronous: reflect padding,
+ * the windowed DFT as an implicit GEMM over overlapping rows (K = n_fft), the power spectrum re^2 + im^2, the filterbank GEMM.  Fixed
+ * summation order; a row's result does not depend on B; a silent input gives exact zeros.  -1 (nothing launched) when dsh_mel_num_frames
+ * is -1, on a null pointer or B < 1.  A larger B x len than any before grows the handle's buffers, which waits for the stream once. */
+int dsh_mel_compute(dsh_mel* h, const float* wave, int32_t batch, int64_t len, float* mel);
+
+/* scipy.signal.resample_poly(x, up, down, window = taps / up) for caller-supplied FIR taps (an odd number, gain included, DEVICE fp32):
+ * zero-stuff by up, filter, decimate by down, the taps centred, zeros outside the signal:
+ *   y[b, j] = sum_k taps[k] x[b, (j down + (n_taps - 1) / 2 - k) / up]  over the k for which the index is an integer in [0, n), k ascending,
+ * for j < dsh_resample_poly_len(n, up, down) = ceil(n up / down).  up / down are used as given (reduce them by their gcd first, as scipy
+ * does).  x [B, n], y [B, n_out] device fp32.  One lane per output sample, about n_taps / up products each. */
+int64_t dsh_resample_poly_len(int64_t n, int32_t up, int32_t down);
+int dsh_op_resample_poly(void* hip_stream, const float* x, int32_t batch, int64_t n, int32_t up, int32_t down, const float* taps_dev, int32_t n_taps,
+                         float* y);
+
+/* Softmax multi-head attention core with 64-wide heads and no mask, fp32 on the exact-fp32 matrix pipe:
+ *   out[b, t, 64 h + d] = sum_s softmax_s(q[b, t, h] . k[b, s, h]) v[b, s, 64 h + d],   qkv [B, M, 3 H 64] = (q | k | v) per row, q already
+ * scaled; out [B, M, H 64]; both device fp32, 16-byte aligned.  One wave per (b, h, 32 queries), keys in tiles of 32 with an online maximum
+ * and sum (logits of any size), keys >= M of the last tile weigh exactly 0.  Fixed order: row b does not depend on B. */
+int dsh_op_softmax_attention(void* hip_stream, const float* qkv, int32_t B, int32_t M, int32_t H, float* out);
+
+/* The HuBERT encoder of the hubert-large family (transformers' HubertModel with feat_extract_norm = "layer", conv_bias = True,
+ * do_stable_layer_norm = True, feat_proj_layer_norm = True), fp32 on the exact-fp32 matrix pipe: the `pretrain_aud_feat` test_custom_aud computes
+ * from a 16 kHz signal.  A handle of its own, bound to one (device, stream), not thread-safe; hip_stream as for dsh_create.  No device is
+ * touched before dsh_hubert_finalize.  Supported (dsh_hubert_create gives -1 otherwise, before any device work): hidden / heads == 64,
+ * hidden <= 1024, every conv_dim a multiple of 32 (at most 1024), (hidden / pos_groups) % 32 == 0, pos_kernel even, hidden and intermediate
+ * multiples of 32, ln_eps == 1e-5 (the folded-LayerNorm launch has that value built in).  hubert-large: hidden 1024, 24 layers, 16 heads,
+ * intermediate 4096, conv_dim 512 x 7, conv_kernel (10, 3, 3, 3, 3, 2, 2), conv_stride (5, 2, 2, 2, 2, 2, 2), pos_kernel 128, pos_groups 16. */
+typedef struct dsh_hubert_config {
+    int32_t hidden, layers, heads, intermediate;
+    int32_t conv_dim[7], conv_kernel[7], conv_stride[7];
+    int32_t pos_kernel, pos_groups;
+    float ln_eps;
+} dsh_hubert_config;
+typedef struct dsh_hubert dsh_hubert;
+int dsh_hubert_create(const dsh_hubert_config* cfg, void* hip_stream, dsh_hubert** out);
+int dsh_hubert_destroy(dsh_hubert* h);
+/* Weights by the state-dict keys of HubertModel (fp32 host memory, copied):
+ *   feature_extractor.conv_layers.{i}.conv.{weight [out, in, k], bias}, .layer_norm.{weight, bias}           i = 0 .. 6 (in = 1 for i = 0)
+ *   feature_projection.layer_norm.{weight, bias}, feature_projection.projection.{weight [hidden, conv_dim[6]], bias}
+ *   encoder.pos_conv_embed.conv.bias and the weight-norm pair, in either spelling: conv.weight_g [1, 1, k] / conv.weight_v
+ *   [hidden, hidden / groups, k] (transformers 4.31) or conv.parametrizations.weight.original0 / original1 (current)
+ *   encoder.layers.{l}.attention.{q,k,v,out}_proj.{weight, bias}, .layer_norm.*, .feed_forward.{intermediate_dense, output_dense}.*,
+ *   .final_layer_norm.*;  encoder.layer_norm.{weight, bias}
+ * masked_spec_embed and lm_head.* are accepted and ignored.  -1 on an unknown key or a shape other than the configuration's. */
+int dsh_hubert_load_tensor(dsh_hubert* h, const char* name, const float* host_data, const int64_t* shape, int32_t ndim);
+/* Builds the device layout in fp64 on the host: the positional conv weight w[o, i, k] = g[k] v[o, i, k] / |v[:, :, k]|_2 (norm over (o, i) per
+ * tap); conv weights repacked to [out, k * in], tap-major; each layer's first LayerNorm folded into ONE q|k|v weight [3 hidden, hidden] whose q
+ * rows (weight and bias) carry the 1 / 8 of the 64-wide heads; final_layer_norm folded into intermediate_dense; the feature projection's
+ * LayerNorm folded into the projection.  Folds in the pro 1 convention of dsh_op_gemm_f32_pro: W' = gamma (.) W, b' = b + W beta, fc = row sums
+ * of W' as rounded to fp32.  -1 naming the first missing key. */
+int dsh_hubert_finalize(dsh_hubert* h);
+/* Test helper, host only (runs without a GPU), before dsh_hubert_finalize: one Linear / convolution as it would be uploaded.  kind 0: conv
+ * `layer` (0 .. 6), 1: feature projection, 2: positional conv ([hidden, k * hidden / groups], tap-major), 3: q|k|v of `layer`, 4: out_proj,
+ * 5: intermediate_dense, 6: output_dense.  dims2 = {N, K}; W [N, K], bias [N], fc [N] (zeros for the kinds without a fold); all nullable. */
+int dsh_hubert_debug_packed(const dsh_hubert* h, int32_t kind, int32_t layer, int32_t* dims2, float* W, float* bias, float* fc);
+/* Frames of n samples: L_i = (L_{i-1} - k_i) / s_i + 1 through the seven convolutions ((n - 400) / 320 + 1 at the large strides), or -1 when n is
+ * shorter than the receptive field (400). */
+int64_t dsh_hubert_num_frames(const dsh_hubert* h, int64_t n);
+/* Batch rows the convolution stack processes per pass (default 4; its activations are 131 MB per 20 s row at the large widths).  The pass size
+ * never changes a bit of the result. */
+int dsh_hubert_set_chunk_pass(dsh_hubert* h, int32_t rows);
+/* out[B, M, hidden] (M = dsh_hubert_num_frames(n)) = last_hidden_state of x [B, n], a signal the caller has already normalised (zero mean,
+ * unit variance over the utterance); both device fp32, out 16-byte aligned.  Asynchronous on the handle's stream.  Every reduction has a fixed
+ * order and there are no atomics: row b has the same bits whatever B and the pass size are.  -1 (nothing launched) when n is shorter than the
+ * receptive field, on a null pointer or B < 1.  A larger B x n than any before grows the handle's buffers, which waits for the stream once. */
+int dsh_hubert_encode(dsh_hubert* h, const float* x, int32_t batch, int64_t n, float* out);
+/* The encoder's new kernels on row-major operands (op tests).
+ * dsh_op_pos_conv: out[b, t, o] = h[b, t, o] + GELU(bias[o] + sum_{tap, i} W[o, tap cg + i] h[b, t + tap - k / 2, g cg + i]), cg = hidden / groups,
+ *   g = o / cg: Conv1d(hidden, hidden, k, padding k / 2, groups) with its last output frame dropped (k even); frames outside [0, M) count as
+ *   zeros and are never loaded.  h, out [B, M, hidden] (not aliased), W [hidden, k cg].
+ * dsh_op_conv0_ln_gelu: y [B, (n - k) / stride + 1, C] = GELU(LayerNorm_C(Conv1d(1, C, k, stride)(x [B, n]))), W [C, k].
+ * dsh_op_conv_ln_gelu: the same for channels-last x [B, L, Cin] and W [Cout, k Cin] tap-major: implicit GEMM + a LayerNorm / GELU row pass. */
+int dsh_op_pos_conv(void* hip_stream, const float* h, int32_t B, int32_t M, int32_t hidden, int32_t groups, int32_t pos_kernel, const float* W,
+                    const float* bias, float* out);
+int dsh_op_conv0_ln_gelu(void* hip_stream, const float* x, int32_t B, int64_t n, int32_t C, int32_t k, int32_t stride, const float* W, const float* bias,
+                         const float* gamma, const float* beta, float* y);
+int dsh_op_conv_ln_gelu(void* hip_stream, const float* x, int32_t B, int32_t L, int32_t Cin, int32_t Cout, int32_t k, int32_t stride, const float* W,
+                        const float* bias, const float* gamma, const float* beta, float* y);
+
 #ifdef __cplusplus
 }
 #endif
