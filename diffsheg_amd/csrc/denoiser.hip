@@ -1364,26 +1364,14 @@ class DualDenoiser final : public DenoiserBase {
         for (auto& in : inst_) (void)in->set_modality(0, nullptr);
         if (pf_.prep) (void)pf_.prep->set_modality(0, nullptr);
         if (twin_) (void)twin_->set_modality(0, nullptr);
-        if (na + np + nh > cond_cap_) {
-            DSH_HIP_CHECK(hipStreamSynchronize(st_));
-            if (cond_buf_) (void)hipFree(cond_buf_);
-            cond_buf_ = nullptr; cond_cap_ = 0;
-            DSH_HIP_CHECK(hipMalloc(&cond_buf_, (na + np + nh) * sizeof(float)));
-            cond_cap_ = na + np + nh;
-        }
+        if (na + np + nh > cond_cap_) { if (int e = grow_device_buffer(cond_buf_, cond_cap_, na + np + nh, st_)) return e; }
         float* a = cond_buf_; float* p = a + na; float* h = p + np;
         DSH_HIP_CHECK(hipMemcpyAsync(a, audio, na * sizeof(float), hipMemcpyDeviceToDevice, st_));
         DSH_HIP_CHECK(hipMemcpyAsync(p, person_id, np * sizeof(float), hipMemcpyDeviceToDevice, st_));
         DSH_HIP_CHECK(hipMemcpyAsync(h, hubert, nh * sizeof(float), hipMemcpyDeviceToDevice, st_));
         // per-clip lengths: context-owned like the conditioning, read by the kernels when they run; instance i of a split sees `lens_ + its first clip`
         if (lengths_host) {
-            if ((size_t)B > len_cap_) {
-                DSH_HIP_CHECK(hipStreamSynchronize(st_));
-                if (len_buf_) (void)hipFree(len_buf_);
-                len_buf_ = nullptr; len_cap_ = 0;
-                DSH_HIP_CHECK(hipMalloc((void**)&len_buf_, (size_t)B * sizeof(int)));
-                len_cap_ = (size_t)B;
-            }
+            if ((size_t)B > len_cap_) { if (int e = grow_device_buffer(len_buf_, len_cap_, (size_t)B, st_)) return e; }
             lens_host_.assign(lengths_host, lengths_host + B);
             // (pageable host source: staged before the call returns)
             DSH_HIP_CHECK(hipMemcpyAsync(len_buf_, lens_host_.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, st_));
@@ -1402,13 +1390,8 @@ class DualDenoiser final : public DenoiserBase {
             // context-owned copy, in stream order like the other conditioning tensors: a re-split re-packs from it (apply_condition), and the
             // sampler writes it into the expression columns of its result
             const size_t ne = (size_t)cond_.B * cond_.T * cfg_.expression_dim;
-            if (ne > track_cap_) {
-                DSH_HIP_CHECK(hipDeviceSynchronize());
-                if (track_buf_) (void)hipFree(track_buf_);
-                track_buf_ = nullptr; track_cap_ = 0;
-                DSH_HIP_CHECK(hipMalloc((void**)&track_buf_, ne * sizeof(float)));
-                track_cap_ = ne;
-            }
+            // (the whole device: the sub-batch instances read the track on their own streams)
+            if (ne > track_cap_) { if (int e = grow_device_buffer(track_buf_, track_cap_, ne, st_, true)) return e; }
             DSH_HIP_CHECK(hipMemcpyAsync(track_buf_, expression, ne * sizeof(float), hipMemcpyDeviceToDevice, st_));
         }
         mod_ = m; modality = m;
@@ -1424,24 +1407,13 @@ class DualDenoiser final : public DenoiserBase {
         note_launch_value(LC_EVAL_STREAMS, ns);
         if (ns == 1) return inst_[0]->eval(x, t, c1, c2, eps);
         const int C = cfg_.channels();
-        DSH_HIP_CHECK(hipEventRecord(ev_fork_, st_));
-        for (int i = 0; i < ns; ++i) {
+        return fork_join(ns, [&](int i, hipStream_t si) -> int {
             const int b0 = first_clip(i, ns);
             const size_t off = (size_t)b0 * cond_.T * C;
-            hipStream_t si = i == 0 ? st_ : streams_[i - 1];
-            if (i > 0) {
-                DSH_HIP_CHECK(hipStreamWaitEvent(si, ev_fork_, 0));
-                DSH_HIP_CHECK(hipStreamWaitEvent(si, ev_lag_[i - 1], 0));      // a few launches behind sub-batch i - 1
-            }
-            if (i + 1 < ns) inst_[i]->notify_after_launches(ev_lag_[i], lag_);
-            else inst_[i]->notify_after_launches(nullptr, 0);
-            if (int e = inst_[i]->eval(x + off, t + b0, c1 + b0, c2 + b0, eps + off)) return e;
-            if (i > 0) {
-                DSH_HIP_CHECK(hipEventRecord(ev_join_[i - 1], si));
-                DSH_HIP_CHECK(hipStreamWaitEvent(st_, ev_join_[i - 1], 0));
-            }
-        }
-        return 0;
+            if (i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(si, ev_lag_[i - 1], 0));      // a few launches behind sub-batch i - 1
+            inst_[i]->notify_after_launches(i + 1 < ns ? ev_lag_[i] : nullptr, i + 1 < ns ? lag_ : 0);
+            return inst_[i]->eval(x + off, t + b0, c1 + b0, c2 + b0, eps + off);
+        });
     }
     int sub_count() const override { return (cond_.B > 0 && (split_now_ == 1 || want_split(cond_.B, cond_.T) == split_now_)) ? split_now_ : 1; }
     int sub_get(int i, DenoiserBase** inst, hipStream_t* stream, int* first, int* n) override {
@@ -1483,13 +1455,7 @@ class DualDenoiser final : public DenoiserBase {
             }
             while ((int)f.lvl_ev.size() < n_levels) { hipEvent_t ev; DSH_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); f.lvl_ev.push_back(ev); }
             const size_t need = (size_t)n_levels * (nb + 1);
-            if (need > f.t_cap) {
-                DSH_HIP_CHECK(hipStreamSynchronize(f.stream));
-                if (f.t_dev) (void)hipFree(f.t_dev);
-                f.t_dev = nullptr; f.t_cap = 0;
-                DSH_HIP_CHECK(hipMalloc((void**)&f.t_dev, need * sizeof(int64_t)));
-                f.t_cap = need;
-            }
+            if (need > f.t_cap) { if (int e = grow_device_buffer(f.t_dev, f.t_cap, need, f.stream)) return e; }
             // everything already enqueued on the evaluating stream (the conditioning copies, the previous run's last restore from
             // the slots) precedes the side stream's work
             DSH_HIP_CHECK(hipEventRecord(f.ev_fork, st_));
@@ -1605,17 +1571,9 @@ class DualDenoiser final : public DenoiserBase {
         if (split_now_ == 1) return inst_[0]->debug_copy(what, out);
         // sub-batch streams: every instance copies its own clips' rows on its own stream, joined into the context stream
         const int w = what == "aud_feat" ? cfg_.audio_dim : cfg_.expression_dim;
-        DSH_HIP_CHECK(hipEventRecord(ev_fork_, st_));
-        for (int i = 0; i < split_now_; ++i) {
-            hipStream_t si = i == 0 ? st_ : streams_[i - 1];
-            if (i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(si, ev_fork_, 0));
-            if (int e = inst_[i]->debug_copy(what, out + (size_t)first_clip(i, split_now_) * cond_.T * w)) return e;
-            if (i > 0) {
-                DSH_HIP_CHECK(hipEventRecord(ev_join_[i - 1], si));
-                DSH_HIP_CHECK(hipStreamWaitEvent(st_, ev_join_[i - 1], 0));
-            }
-        }
-        return 0;
+        return fork_join(split_now_, [&](int i, hipStream_t) -> int {
+            return inst_[i]->debug_copy(what, out + (size_t)first_clip(i, split_now_) * cond_.T * w);
+        });
     }
 
   private:
@@ -1646,6 +1604,21 @@ class DualDenoiser final : public DenoiserBase {
         }
         return (int)((int64_t)cond_.B * i / ns);
     }
+    // One fork / join of the sub-batch streams around f(i, stream of instance i) for i in [0, ns): instance 0 works on the context stream, every
+    // other on its own behind all the context stream holds so far, and the context stream goes on behind each of them.
+    template <typename F> int fork_join(int ns, F&& f) {
+        DSH_HIP_CHECK(hipEventRecord(ev_fork_, st_));
+        for (int i = 0; i < ns; ++i) {
+            hipStream_t si = i == 0 ? st_ : streams_[i - 1];
+            if (i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(si, ev_fork_, 0));
+            if (int e = f(i, si)) return e;
+            if (i > 0) {
+                DSH_HIP_CHECK(hipEventRecord(ev_join_[i - 1], si));
+                DSH_HIP_CHECK(hipStreamWaitEvent(st_, ev_join_[i - 1], 0));
+            }
+        }
+        return 0;
+    }
     int apply_condition(int ns) {
         while ((int)inst_.size() < ns) {
             hipStream_t st; hipEvent_t lag, join;
@@ -1666,20 +1639,13 @@ class DualDenoiser final : public DenoiserBase {
             if (int e = inst_[0]->set_condition(cond_.B, cond_.T, cond_.audio, cond_.pid, cond_.hubert)) return e;
             return mod_ ? push_modality(1) : 0;
         }
-        DSH_HIP_CHECK(hipEventRecord(ev_fork_, st_));
-        for (int i = 0; i < ns; ++i) {
-            const int b0 = first_clip(i, ns), nb = first_clip(i + 1, ns) - b0;
-            const size_t ft = (size_t)b0 * cond_.T;
-            hipStream_t si = i == 0 ? st_ : streams_[i - 1];
-            if (i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(si, ev_fork_, 0));
-            if (int e = inst_[i]->set_lengths(lens_ ? lens_ + b0 : nullptr)) return e;
-            if (int e = inst_[i]->set_condition(nb, cond_.T, cond_.audio + ft * cfg_.audio_dim, cond_.pid + (size_t)b0 * cfg_.style_dim,
-                                                cond_.hubert + ft * cfg_.hubert_dim)) return e;
-            if (i > 0) {
-                DSH_HIP_CHECK(hipEventRecord(ev_join_[i - 1], si));
-                DSH_HIP_CHECK(hipStreamWaitEvent(st_, ev_join_[i - 1], 0));
-            }
-        }
+        if (int e = fork_join(ns, [&](int i, hipStream_t) -> int {
+                const int b0 = first_clip(i, ns), nb = first_clip(i + 1, ns) - b0;
+                const size_t ft = (size_t)b0 * cond_.T;
+                if (int e = inst_[i]->set_lengths(lens_ ? lens_ + b0 : nullptr)) return e;
+                return inst_[i]->set_condition(nb, cond_.T, cond_.audio + ft * cfg_.audio_dim, cond_.pid + (size_t)b0 * cfg_.style_dim,
+                                               cond_.hubert + ft * cfg_.hubert_dim);
+            })) return e;
         return mod_ ? push_modality(ns) : 0;
     }
     // the condition's modality to the ns evaluating instances (each packs its own clips' rows of the given track on its own stream, forked
@@ -1687,17 +1653,9 @@ class DualDenoiser final : public DenoiserBase {
     int push_modality(int ns) {
         const size_t row = (size_t)cond_.T * cfg_.expression_dim;
         const float* tr = mod_ == 2 ? track_buf_ : nullptr;
-        if (ns > 1 && tr) DSH_HIP_CHECK(hipEventRecord(ev_fork_, st_));
-        for (int i = 0; i < (int)inst_.size(); ++i) {
-            if (i >= ns || !tr) { if (int e = inst_[i]->set_modality(mod_, nullptr)) return e; continue; }
-            hipStream_t si = i == 0 ? st_ : streams_[i - 1];
-            if (i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(si, ev_fork_, 0));
-            if (int e = inst_[i]->set_modality(mod_, tr + (size_t)(ns > 1 ? first_clip(i, ns) : 0) * row)) return e;
-            if (i > 0) {
-                DSH_HIP_CHECK(hipEventRecord(ev_join_[i - 1], si));
-                DSH_HIP_CHECK(hipStreamWaitEvent(st_, ev_join_[i - 1], 0));
-            }
-        }
+        auto pack = [&](int i, hipStream_t) -> int { return inst_[i]->set_modality(mod_, tr + (size_t)(ns > 1 ? first_clip(i, ns) : 0) * row); };
+        if (tr) { if (int e = ns > 1 ? fork_join(ns, pack) : pack(0, st_)) return e; }
+        for (int i = tr ? ns : 0; i < (int)inst_.size(); ++i) { if (int e = inst_[i]->set_modality(mod_, nullptr)) return e; }
         if (pf_.prep) { if (int e = pf_.prep->set_modality(mod_, nullptr)) return e; }
         if (twin_) { if (int e = twin_->set_modality(mod_, nullptr)) return e; }
         return 0;

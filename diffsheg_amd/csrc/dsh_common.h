@@ -96,6 +96,19 @@ const char* last_error_cstr();
         }                                                                                       \
     } while (0)
 
+// Replace the device buffer `p` (capacity `cap`, in elements) by one of `n` elements; the contents are not kept.  Waits first for
+// whatever may still read the old buffer: the work queued on `s`, or on the whole device when `whole_device` (readers on other streams).
+// On failure p is null and cap 0.  The caller decides when to grow (`if (n > cap)`).
+template <typename T, typename Cap>
+inline int grow_device_buffer(T*& p, Cap& cap, size_t n, hipStream_t s, bool whole_device = false) {
+    DSH_HIP_CHECK(whole_device ? hipDeviceSynchronize() : hipStreamSynchronize(s));
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    DSH_HIP_CHECK(hipMalloc((void**)&p, n * sizeof(T)));
+    cap = (Cap)n;
+    return 0;
+}
+
 // ---- test helper (dsh_debug_launch_counts, capi.hip): launches per kernel family --------------
 // Host-side relaxed counters, bumped by the host launchers next to the launch they issue; no kernel and no launch argument knows
 // about them.  The indices are part of the C ABI (include/diffsheg_hip.h): append, never renumber.

@@ -49,14 +49,59 @@ class Sampler {
             bool masked, const float* noise_stack, int64_t n_draws, float* trace);
 
   private:
+    // One set of the device buffers a chain works in: the noise scratch of a step's two draws, the per-step scalars an evaluation reads
+    // (timestep, the two input scales, the level's cache slot: one per batch row, 8 level words) and the hipGraphs of one evaluation, one per
+    // timestep-cache mode (denoiser.h: 0 plain, 1 compute + save level, 2 restore level).  Replayed in launch-bound (small-batch /
+    // window-chain) runs: all pointers are fixed for a run, only the scalars' contents change between steps.
+    struct ChainBufs {
+        float *nz1 = nullptr, *nz_eta = nullptr, *c1 = nullptr, *c2 = nullptr;
+        int64_t *t = nullptr, *lvl = nullptr;
+        hipGraph_t graph[3] = {}; hipGraphExec_t graph_exec[3] = {};
+    };
+    // One stream that advances some columns of some rows through every step of a run.  Three ways of filling it (run()):
+    //   whole batch            the context's denoiser and stream, all clips, the active modality's columns, bufs[0]
+    //   sub-batch i            sub_get(i)'s instance and stream, its clips, the same columns, bufs[0] at its clips' offset (lvl: word i)
+    //   pipelined loop E / G   the context's denoiser and stream on the expression columns with bufs[0] / the gesture-side twin and its
+    //                          stream on the gesture columns, one step behind, with bufs[1]
+    struct Chain {
+        DenoiserBase* d; hipStream_t s;
+        int b0, nb; size_t off, cnt;        // clips [b0, b0 + nb) = elements [off, off + cnt) of x / eps / gt / mask / the noise scratch
+        int c_lo, c_hi;                     // the columns its updates write (0, 0: all)
+        float *nz1, *nz_eta;                // full-size scratch (the chain uses its element range): the gt / undo / DDPM draw, the eta != 0 draw
+        int64_t* t; float *c1, *c2; int64_t* lvl;      // its rows of the per-step scalars, its level word
+        ChainBufs* own;                     // the set these come from: holds its evaluation graphs
+    };
+    // (sampler.hip) one run()'s arguments, constants and chains; its regime, decided before the first step; what one step's launches share
+    struct Run; struct LoopPlan; struct StepConsts;
+    // run() = argument checks, then these in order; finish() joins the chains whatever loop() returned
     int ensure(size_t n, int B);
+    int prepare(Run& r);
+    int make_chains(Run& r);
+    LoopPlan plan(const Run& r) const;
+    int loop(Run& r, const LoopPlan& p);
+    int finish(Run& r, int rc);
+    // loop() = x_T, setup(), then per step: evaluate(), and update() of every chain (pipelined: E, gesture_follow(), G)
+    int setup(Run& r, const LoopPlan& p);
+    StepConsts step_consts(Run& r, const SamplerStep& sp);
+    int noise_for(const Run& r, int64_t idx, const Chain& c, float* scratch, const float** out);
+    int evaluate(Run& r, const LoopPlan& p, const StepConsts& sc);
+    int eval_step(const Chain& c, float* x, int n_eval, bool use_graph, int mode);
+    int gesture_follow(Run& r, const LoopPlan& p, const StepConsts& sc);
+    int update(Run& r, const Chain& c, const StepConsts& sc);
+    int ddim_update(Run& r, const Chain& c, const StepConsts& sc);
+    int ddpm_update(Run& r, const Chain& c, const StepConsts& sc);
+    static void drop_graphs(ChainBufs& b);
+    void drop_graph();                     // every chain's
+    bool replayed() const { return bufs[0].graph_exec[0] || bufs[0].graph_exec[1] || bufs[0].graph_exec[2]; }
     hipStream_t st;
     int channels;
-    std::vector<void*> bufs;
+    std::vector<void*> pool;              // ensure()'s allocations
     size_t cap_n = 0; int cap_b = 0;
-    float *eps = nullptr, *nz1 = nullptr, *c1buf = nullptr, *c2buf = nullptr;
-    float* nz_eta = nullptr; size_t cap_eta = 0;      // Philox scratch of the step's own randn_like (eta != 0 only)
-    int64_t* tbuf = nullptr; int64_t* lvlbuf = nullptr;
+    float* eps = nullptr;
+    // [0] the whole batch / the sub-batches / the expression chain; [1] the gesture chain of the pipelined loop, its noise scratch sized for
+    // the batches that loop serves (cap_n2).  bufs[0].nz_eta is grown on demand (cap_eta): Philox runs with eta != 0 only.
+    ChainBufs bufs[2];
+    size_t cap_n2 = 0, cap_eta = 0;
     DiffusionTables tb; int tb_steps = -1, tb_resp = -1;
     uint64_t* row_keys = nullptr; int n_row_keys = 0, cap_row_keys = 0;
     uint64_t* row_seeds = nullptr; int n_row_seeds = 0, cap_row_seeds = 0;
@@ -64,19 +109,8 @@ class Sampler {
     // --same_overlap_noisy: the noisy tail x[..., -L:, :] saved after every DDIM step, one slot per spaced level; persists
     // across sample() calls like the reference's self.saved_noisy_tail (the dict the next window receives IS this object)
     float* tails = nullptr; float* tail_tmp = nullptr; size_t tails_blc = 0; int tails_levels = 0;
-    // hipGraph replay of one denoiser evaluation for launch-bound (small-batch / window-chain) runs
-    // (one graph per timestep-cache mode, denoiser.h: 0 plain, 1 compute + save level, 2 restore level)
-    hipGraphExec_t graph_exec[3] = {nullptr, nullptr, nullptr};
-    hipGraph_t graph[3] = {nullptr, nullptr, nullptr};
-    void drop_graph();
-    int eval_step(DenoiserBase* den, float* x, int n_eval, bool use_graph, int mode);
-    // pipelined small-batch loop (denoiser.h: set_part / pipe_begin): the gesture encoder's chain on its own stream, one step behind the
-    // expression encoder's — its own per-step scalars, noise scratch and evaluation graph
-    float *nz1G = nullptr, *nz_etaG = nullptr, *c1bufG = nullptr, *c2bufG = nullptr;
-    int64_t* tbufG = nullptr; int64_t* lvlbufG = nullptr; size_t capG_n = 0;
-    hipGraphExec_t graph_execG = nullptr; hipGraph_t graphG = nullptr;
+    // pipelined small-batch loop (denoiser.h: set_part / pipe_begin)
     hipEvent_t ev_pE = nullptr, ev_pC = nullptr, ev_pG = nullptr;       // E_k done / E_k's expression estimate copied / gesture chain done
-    int eval_step_twin(DenoiserBase* twin, hipStream_t s, float* x, int n_eval, bool use_graph, int mode);
     // free-running sub-batch streams of large batches (run(): one fork before the loop, one join after it)
     hipEvent_t ev_fork = nullptr;
     std::vector<hipEvent_t> ev_sub;      // [2 i] = "sub-batch i has queued its first launches" (stagger), [2 i + 1] = "sub-batch i done"

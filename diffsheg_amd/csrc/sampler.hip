@@ -129,17 +129,53 @@ int64_t sampler_num_steps(const SamplerOpts& o, bool masked) {
     return (int64_t)steps.size();
 }
 
+// One run()'s arguments, what is derived from them once, its chains and the loop's running state; the parts of run() share it by reference.
+enum LevelCache { CACHE_NONE, CACHE_INLINE, CACHE_PREFETCH, CACHE_SUBS };
+struct Sampler::Run {
+    DenoiserBase* den; const SamplerOpts& o; float* x; bool init_from_x; const float* gt; const uint8_t* mask; bool masked;
+    const float* noise_stack; int64_t n_draws; float* trace;
+    int B = 0; size_t n = 0, row_n = 0;                  // clips, values, values per clip
+    int mod = 0, gcols = 0, w_lo = 0, w_hi = 0;          // modality, gesture columns, the active column window (0, 0: all)
+    const int* len_d = nullptr;                          // ragged batch: per-clip frame counts (device)
+    std::vector<SamplerStep> steps;
+    bool per_row = false; const uint64_t* seeds_d = nullptr; uint64_t quads = 0;      // Philox addressing
+    bool son = false, tail_gt = false; size_t blc = 0;   // --same_overlap_noisy state
+    std::vector<Chain> chains;                           // the whole batch, or its sub-batches
+    Chain E{}, G{};                                      // pipelined loop (piped): chains[0] on the expression columns, the twin on the gesture columns
+    LevelCache cache = CACHE_NONE; bool piped = false;   // what setup() obtained of the plan
+    std::vector<char> level_seen;
+    std::vector<int64_t> tv; int lag = 0;                // level -> model timestep; DSH_DUAL_LAG
+    size_t pf_next = 0;                                  // order[0 .. pf_next) have been handed to the prefetch stream
+    int64_t draw = 0, step_idx = 0; int n_eval = 0;
+    int64_t next_draw() { return draw++; }               // draw index: advanced once per draw, whatever the regime
+};
+
+// The regime of a run, decided from its arguments before anything is queued.  It states what the loop asks of the denoiser; setup()
+// asks, and falls back where the denoiser refuses (prefetch -> inline cache -> none; pipeline -> one chain).
+struct Sampler::LoopPlan {
+    bool split = false, graph = false;   // sub-batch streams; evaluations replayed from hipGraphs
+    LevelCache cache = CACHE_NONE;       // timestep cache: inline, filled ahead by the side-stream prefetch, or inline per sub-batch
+    bool inline_ok = false;              // ... a refused prefetch falls back to the inline cache (the schedule revisits levels)
+    bool pipe = false;                   // the two encoders' chains on two streams
+    std::vector<int> order;              // DDIM: the schedule's levels in first-use order
+};
+
+// what the launches of one step share
+struct Sampler::StepConsts {
+    StepKind kind; int k; int eval_idx;                  // spaced level; index of the step's evaluation in the run (-1: undo step)
+    int64_t t; float c1, c2;                             // model timestep and the input scales of the evaluation
+    int64_t idx, idx2;                                   // draws: the step's own N(0,1) (undo / DDPM noise, DDIM randn_like); the noised gt's (-1: none)
+    float undo_a, undo_b, coef1, coef2;                  // undo step; DDPM step (with sigma)
+    float sqrt_ab_prev, sqrt_1m_ab_prev, coef_eps, sigma;
+};
+
 Sampler::~Sampler() {
     drop_graph();
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     for (hipEvent_t e : {ev_pE, ev_pC, ev_pG}) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_sub) (void)hipEventDestroy(e);
-    for (void* p : bufs) (void)hipFree(p);
-    if (row_keys) (void)hipFree(row_keys);
-    if (row_seeds) (void)hipFree(row_seeds);
-    if (tails) (void)hipFree(tails);
-    if (tail_tmp) (void)hipFree(tail_tmp);
-    if (nz_eta) (void)hipFree(nz_eta);
+    for (void* p : pool) (void)hipFree(p);
+    for (void* p : {(void*)row_keys, (void*)row_seeds, (void*)tails, (void*)tail_tmp, (void*)bufs[0].nz_eta}) if (p) (void)hipFree(p);
 }
 
 int Sampler::set_row_keys(const uint64_t* keys_host, int n) {
@@ -147,13 +183,7 @@ int Sampler::set_row_keys(const uint64_t* keys_host, int n) {
     n_row_keys = 0;
     n_row_seeds = 0;               // (per-row seeds belong to the key set they were given for)
     if (n == 0) return 0;
-    if (n > cap_row_keys) {
-        DSH_HIP_CHECK(hipStreamSynchronize(st));
-        if (row_keys) (void)hipFree(row_keys);
-        row_keys = nullptr; cap_row_keys = 0;
-        DSH_HIP_CHECK(hipMalloc((void**)&row_keys, (size_t)n * sizeof(uint64_t)));
-        cap_row_keys = n;
-    }
+    if (n > cap_row_keys) { if (int e = grow_device_buffer(row_keys, cap_row_keys, (size_t)n, st)) return e; }
     DSH_HIP_CHECK(hipMemcpyAsync(row_keys, keys_host, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     DSH_HIP_CHECK(hipStreamSynchronize(st));       // keys_host is pageable caller memory
     n_row_keys = n;
@@ -165,107 +195,411 @@ int Sampler::set_row_seeds(const uint64_t* seeds_host, int n) {
     DSH_REQUIRE(n == 0 || (n_row_keys > 0 && n == n_row_keys), "set_row_seeds: needs the row keys set first, and one seed per row key");
     n_row_seeds = 0;
     if (n == 0) return 0;
-    if (n > cap_row_seeds) {
-        DSH_HIP_CHECK(hipStreamSynchronize(st));
-        if (row_seeds) (void)hipFree(row_seeds);
-        row_seeds = nullptr; cap_row_seeds = 0;
-        DSH_HIP_CHECK(hipMalloc((void**)&row_seeds, (size_t)n * sizeof(uint64_t)));
-        cap_row_seeds = n;
-    }
+    if (n > cap_row_seeds) { if (int e = grow_device_buffer(row_seeds, cap_row_seeds, (size_t)n, st)) return e; }
     DSH_HIP_CHECK(hipMemcpyAsync(row_seeds, seeds_host, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     DSH_HIP_CHECK(hipStreamSynchronize(st));       // seeds_host is pageable caller memory
     n_row_seeds = n;
     return 0;
 }
 
-void Sampler::drop_graph() {
-    if (graph_execG) { (void)hipGraphExecDestroy(graph_execG); graph_execG = nullptr; }
-    if (graphG) { (void)hipGraphDestroy(graphG); graphG = nullptr; }
+void Sampler::drop_graphs(ChainBufs& b) {
     for (int m = 0; m < 3; ++m) {
-        if (graph_exec[m]) { (void)hipGraphExecDestroy(graph_exec[m]); graph_exec[m] = nullptr; }
-        if (graph[m]) { (void)hipGraphDestroy(graph[m]); graph[m] = nullptr; }
+        if (b.graph_exec[m]) { (void)hipGraphExecDestroy(b.graph_exec[m]); b.graph_exec[m] = nullptr; }
+        if (b.graph[m]) { (void)hipGraphDestroy(b.graph[m]); b.graph[m] = nullptr; }
     }
 }
+void Sampler::drop_graph() { drop_graphs(bufs[1]); drop_graphs(bufs[0]); }
 
-// One denoiser evaluation eps = model(x, t, c1, c2).  At small batch an eval is ~170 launches of a few
+// One denoiser evaluation eps = model(x, t, c1, c2) of a chain, on its stream.  At small batch an eval is ~170 launches of a few
 // microseconds each, i.e. launch / dependency bound: the first eval of a run executes eagerly (also warms one-time
 // kernel attribute setup), later ones are stream-captured into a hipGraph once per cache mode and replayed.
-// All pointers (x, tbuf, c1buf, c2buf, lvlbuf, eps, the denoiser workspace and its timestep-cache slots) are fixed for
-// the duration of a run; only the CONTENTS of tbuf/c1buf/c2buf/lvlbuf change between steps, so one graph per mode
-// (0 plain, 1 compute + save level, 2 restore level) serves every step.
-int Sampler::eval_step(DenoiserBase* den, float* x, int n_eval, bool use_graph, int mode) {
-    if (!use_graph || n_eval == 0) return den->eval_level(x, tbuf, c1buf, c2buf, eps, mode, lvlbuf);
-    if (!graph_exec[mode]) {
-        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+// All pointers (x, the chain's scalars, eps, the denoiser workspace and its timestep-cache slots) are fixed for
+// the duration of a run; only the CONTENTS of the scalars change between steps, so one graph per mode serves every step.
+// A failed capture or instantiation drops the chain's graphs and evaluates eagerly.
+int Sampler::eval_step(const Chain& c, float* x, int n_eval, bool use_graph, int mode) {
+    auto eager = [&]() -> int { return c.d->eval_level(x + c.off, c.t, c.c1, c.c2, eps + c.off, mode, c.lvl); };
+    if (!use_graph || n_eval == 0) return eager();
+    ChainBufs& g = *c.own;
+    if (!g.graph_exec[mode]) {
+        if (hipStreamBeginCapture(c.s, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); return eager(); }
+        const int rc = eager();
+        hipError_t e = hipStreamEndCapture(c.s, &g.graph[mode]);
+        const bool captured = rc == 0 && e == hipSuccess && g.graph[mode] != nullptr;
+        if (!captured || hipGraphInstantiate(&g.graph_exec[mode], g.graph[mode], nullptr, nullptr, 0) != hipSuccess) {
             (void)hipGetLastError();
-            return den->eval_level(x, tbuf, c1buf, c2buf, eps, mode, lvlbuf);
-        }
-        const int rc = den->eval_level(x, tbuf, c1buf, c2buf, eps, mode, lvlbuf);
-        hipError_t e = hipStreamEndCapture(st, &graph[mode]);
-        if (rc != 0 || e != hipSuccess || graph[mode] == nullptr) {
-            (void)hipGetLastError();
-            drop_graph();
-            return rc != 0 ? rc : den->eval_level(x, tbuf, c1buf, c2buf, eps, mode, lvlbuf);
-        }
-        if (hipGraphInstantiate(&graph_exec[mode], graph[mode], nullptr, nullptr, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            drop_graph();
-            return den->eval_level(x, tbuf, c1buf, c2buf, eps, mode, lvlbuf);
+            drop_graphs(g);
+            return rc != 0 ? rc : eager();
         }
     }
-    DSH_HIP_CHECK(hipGraphLaunch(graph_exec[mode], st));
-    return 0;
-}
-
-// the gesture-side evaluation of the pipelined loop (mode 2: head restored from the timestep cache), on the twin's stream
-int Sampler::eval_step_twin(DenoiserBase* twin, hipStream_t s, float* x, int n_eval, bool use_graph, int mode) {
-    if (!use_graph || n_eval == 0) return twin->eval_level(x, tbufG, c1bufG, c2bufG, eps, mode, lvlbufG);
-    if (!graph_execG) {
-        if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            (void)hipGetLastError();
-            return twin->eval_level(x, tbufG, c1bufG, c2bufG, eps, mode, lvlbufG);
-        }
-        const int rc = twin->eval_level(x, tbufG, c1bufG, c2bufG, eps, mode, lvlbufG);
-        hipError_t e = hipStreamEndCapture(s, &graphG);
-        if (rc != 0 || e != hipSuccess || graphG == nullptr) {
-            (void)hipGetLastError();
-            if (graphG) { (void)hipGraphDestroy(graphG); graphG = nullptr; }
-            return rc != 0 ? rc : twin->eval_level(x, tbufG, c1bufG, c2bufG, eps, mode, lvlbufG);
-        }
-        if (hipGraphInstantiate(&graph_execG, graphG, nullptr, nullptr, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipGraphDestroy(graphG); graphG = nullptr; graph_execG = nullptr;
-            return twin->eval_level(x, tbufG, c1bufG, c2bufG, eps, mode, lvlbufG);
-        }
-    }
-    DSH_HIP_CHECK(hipGraphLaunch(graph_execG, s));
+    DSH_HIP_CHECK(hipGraphLaunch(g.graph_exec[mode], c.s));
     return 0;
 }
 
 int Sampler::ensure(size_t n, int B) {
     if (n <= cap_n && B <= cap_b) return 0;
     DSH_HIP_CHECK(hipStreamSynchronize(st));
-    for (void* p : bufs) (void)hipFree(p);
-    bufs.clear();
+    for (void* p : pool) (void)hipFree(p);
+    pool.clear();
     cap_n = std::max(n, cap_n); cap_b = std::max(B, cap_b);
     auto alloc = [&](void** p, size_t bytes) -> int {
-        DSH_HIP_CHECK(hipMalloc(p, bytes)); bufs.push_back(*p); return 0; };
+        DSH_HIP_CHECK(hipMalloc(p, bytes)); pool.push_back(*p); return 0; };
+    auto scalars = [&](ChainBufs& b) -> int {
+        if (int e = alloc((void**)&b.t, cap_b * sizeof(int64_t))) return e;
+        if (int e = alloc((void**)&b.c1, cap_b * sizeof(float))) return e;
+        if (int e = alloc((void**)&b.c2, cap_b * sizeof(float))) return e;
+        return alloc((void**)&b.lvl, 8 * sizeof(int64_t));                       // one per sub-batch stream
+    };
     if (int e = alloc((void**)&eps, cap_n * sizeof(float))) return e;
-    if (int e = alloc((void**)&nz1, cap_n * sizeof(float))) return e;
-    if (int e = alloc((void**)&tbuf, cap_b * sizeof(int64_t))) return e;
-    if (int e = alloc((void**)&c1buf, cap_b * sizeof(float))) return e;
-    if (int e = alloc((void**)&c2buf, cap_b * sizeof(float))) return e;
-    if (int e = alloc((void**)&lvlbuf, 8 * sizeof(int64_t))) return e;          // one per sub-batch stream
+    if (int e = alloc((void**)&bufs[0].nz1, cap_n * sizeof(float))) return e;
+    if (int e = scalars(bufs[0])) return e;
     // (pipelined loop: the gesture chain's own scalars and noise scratch, sized for the batches that loop serves — below the sub-batch split's
     //  three-stream range — whatever larger batch this context has also sampled)
-    capG_n = std::min(cap_n, (size_t)100000 * channels);
-    if (int e = alloc((void**)&nz1G, capG_n * sizeof(float))) return e;
-    if (int e = alloc((void**)&nz_etaG, capG_n * sizeof(float))) return e;
-    if (int e = alloc((void**)&tbufG, cap_b * sizeof(int64_t))) return e;
-    if (int e = alloc((void**)&c1bufG, cap_b * sizeof(float))) return e;
-    if (int e = alloc((void**)&c2bufG, cap_b * sizeof(float))) return e;
-    if (int e = alloc((void**)&lvlbufG, 8 * sizeof(int64_t))) return e;
+    cap_n2 = std::min(cap_n, (size_t)100000 * channels);
+    if (int e = alloc((void**)&bufs[1].nz1, cap_n2 * sizeof(float))) return e;
+    if (int e = alloc((void**)&bufs[1].nz_eta, cap_n2 * sizeof(float))) return e;
+    return scalars(bufs[1]);
+}
+
+// what run() needs beside its arguments: the schedule, the coefficient tables, the buffers, the noise addressing, the saved noisy tails
+int Sampler::prepare(Run& r) {
+    const SamplerOpts& o = r.o;
+    DenoiserBase* den = r.den;
+    const int B = r.B; const size_t n = r.n;
+    std::string err;
+    if (plan_steps(o, r.masked, r.steps, err)) { set_last_error(err); return -1; }
+    const int64_t need = sampler_num_draws(o, r.masked, r.init_from_x);
+    if (o.noise_mode == 0) DSH_REQUIRE(r.noise_stack != nullptr && r.n_draws >= need, "noise stack shorter than the loop's draw count");
+    // tables are cached per (steps, respacing)
+    const int resp = o.kind == 1 ? 0 : o.respacing;
+    if (tb_steps != o.diffusion_steps || tb_resp != resp) {
+        if (make_tables(o.diffusion_steps, resp, tb, err)) { set_last_error(err); return -1; }
+        tb_steps = o.diffusion_steps; tb_resp = resp;
+    }
+    if (int e = ensure(n, B)) return e;
+    if (o.kind == 0 && o.eta != 0.f && o.noise_mode == 1 && cap_eta < n) { if (int e = grow_device_buffer(bufs[0].nz_eta, cap_eta, n, st)) return e; }
+    DSH_REQUIRE(n_row_keys == 0 || o.noise_mode != 1 || (n_row_keys == B && (n / B) % 4 == 0),
+                "row keys were set for a different batch size (or frames*channels is not a multiple of 4)");
+    r.per_row = o.noise_mode == 1 && n_row_keys == B;
+    r.seeds_d = (r.per_row && n_row_seeds == B) ? row_seeds : nullptr;      // (set_row_seeds: always the row keys' count)
+    r.quads = r.per_row ? (n / B) / 4 : (n + 3) / 4;
+    // --same_overlap_noisy state
+    r.blc = (size_t)B * o.overlap_len * channels;
+    r.son = o.same_overlap_noisy != 0 && o.kind == 0;
+    if (r.son) {
+        DSH_REQUIRE(o.overlap_len > 0 && o.overlap_len <= den->frames, "same_overlap_noisy needs 0 < overlap_len <= frames");
+        if (tails_blc != r.blc || tails_levels != o.respacing) {
+            DSH_REQUIRE(o.clip_idx == 0 || !r.masked, "same_overlap_noisy: the saved noisy tails belong to a different batch / overlap shape");
+            // (the pair grows together; its shape is recorded once both exist)
+            size_t got = 0;
+            tails_blc = 0; tails_levels = 0;
+            if (int e = grow_device_buffer(tails, got, r.blc * o.respacing, st)) return e;
+            if (int e = grow_device_buffer(tail_tmp, got, r.blc, st)) return e;
+            DSH_HIP_CHECK(hipMemsetAsync(tails, 0, r.blc * o.respacing * sizeof(float), st));
+            tails_blc = r.blc; tails_levels = o.respacing;
+        }
+    }
+    r.tail_gt = r.son && r.masked && o.clip_idx > 0;
     return 0;
+}
+
+// The chains of a run.  Large batches: every sub-batch runs the WHOLE loop on its own stream, forked from the context stream here and
+// joined into it in finish(); else the whole batch on the context stream.
+int Sampler::make_chains(Run& r) {
+    DenoiserBase* den = r.den;
+    ChainBufs& b = bufs[0];
+    r.lag = (int)switch_int(SW_DUAL_LAG);
+    const int ns = (prof && prof->on) ? 1 : den->sub_count();
+    if (!(ns > 1 && r.row_n % 4 == 0)) {
+        r.chains.push_back(Chain{den, st, 0, r.B, 0, r.n, r.w_lo, r.w_hi, b.nz1, b.nz_eta, b.t, b.c1, b.c2, b.lvl, &b});
+        return 0;
+    }
+    for (int i = 0; i < ns; ++i) {
+        Chain c{nullptr, nullptr, 0, 0, 0, 0, r.w_lo, r.w_hi, b.nz1, b.nz_eta, nullptr, nullptr, nullptr, b.lvl + i, &b};
+        if (int e = den->sub_get(i, &c.d, &c.s, &c.b0, &c.nb)) return e;
+        c.off = (size_t)c.b0 * r.row_n; c.cnt = (size_t)c.nb * r.row_n;
+        c.t = b.t + c.b0; c.c1 = b.c1 + c.b0; c.c2 = b.c2 + c.b0;
+        r.chains.push_back(c);
+    }
+    if (!ev_fork) DSH_HIP_CHECK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+    while (ev_sub.size() < 2 * r.chains.size()) { hipEvent_t e; DSH_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ev_sub.push_back(e); }
+    DSH_HIP_CHECK(hipEventRecord(ev_fork, st));
+    for (size_t i = 1; i < r.chains.size(); ++i) DSH_HIP_CHECK(hipStreamWaitEvent(r.chains[i].s, ev_fork, 0));
+    return 0;
+}
+
+Sampler::LoopPlan Sampler::plan(const Run& r) const {
+    const SamplerOpts& o = r.o;
+    LoopPlan p;
+    const bool profiling = prof && prof->on;
+    const size_t rows = (size_t)r.B * r.den->frames;
+    p.split = r.chains.size() > 1;
+    // graphs only where launches dominate (a few thousand token rows), never while profiling events are recorded,
+    // and never on the legacy NULL stream (it cannot be captured); sub-batch streams evaluate eagerly
+    const bool small = rows <= (size_t)switch_int(SW_GRAPH_ROWS);
+    p.graph = st != nullptr && small && !profiling && !switch_present(SW_NO_GRAPH) && !p.split;
+    // (the side-stream head and the two-stream encoder pipeline also pay above the graph range, up to where batches are split over sub-batch
+    //  streams: DSH_PIPE_ROWS)
+    const bool small_pf = rows <= pipe_rows();
+    // timestep cache (denoiser.h): worth it when the schedule revisits levels (out-painting jump schedule: 63 evaluations
+    // over 16 levels).  DSH_LEVEL_CACHE=0 disables it.
+    const bool cache_on = switch_int(SW_LEVEL_CACHE) != 0;
+    int evals = 0, distinct = 0;
+    if (o.kind == 0) {
+        std::vector<int> cnt(o.respacing, 0);
+        for (const SamplerStep& sp : r.steps) if (sp.kind != STEP_UNDO) { ++evals; if (cnt[sp.level]++ == 0) { ++distinct; p.order.push_back(sp.level); } }
+    }
+    const int gch = r.gcols;
+    if ((small || small_pf) && o.kind == 0 && !p.split) {
+        // side-stream prefetch of every scheduled level (also pays for schedules without repeats); else the inline cache
+        p.inline_ok = evals > distinct && cache_on;
+        if (cache_on && st != nullptr && !profiling && !p.order.empty()) p.cache = CACHE_PREFETCH;
+        else if (p.inline_ok) p.cache = CACHE_INLINE;
+        // the two encoders' chains on two streams: every evaluation restores its head from the slots the prefetch run fills (mode 2), no
+        // per-step trace of the whole sample, no saved noisy tails (both need all channels of a step at once)
+        p.pipe = r.mod == 0 && p.cache == CACHE_PREFETCH && !r.trace && !r.son && bufs[1].nz1 && r.n <= cap_n2 && gch > 0 && gch < channels;
+    }
+    // DDPM loops have no timestep cache (every level is visited once, 1000 of them): each chain computes its own head
+    if (r.mod == 0 && !p.pipe && o.kind == 1 && !p.split && small_pf && !r.trace && bufs[1].nz1 && r.n <= cap_n2) p.pipe = gch > 0 && gch < channels;
+    // sub-batch streams: the inline timestep cache for schedules that revisit levels, else plain evaluations
+    if (p.split && o.kind == 0 && evals > distinct && cache_on) p.cache = CACHE_SUBS;
+    return p;
+}
+
+// What the plan calls for, asked of the denoiser in this order: graphs of the previous run dropped, the prefetch run begun (one level is
+// queued now, the others one evaluation ahead of their first use: the host never runs far in front of the main chain, and the main chain
+// never waits for the host to finish queueing 25 levels) or the cache slots prepared, the gesture-side twin started.
+int Sampler::setup(Run& r, const LoopPlan& p) {
+    DenoiserBase* den = r.den;
+    const SamplerOpts& o = r.o;
+    drop_graph();
+    r.cache = p.cache;
+    if (r.cache == CACHE_PREFETCH) {
+        r.tv.resize(o.respacing);
+        for (int k = 0; k < o.respacing; ++k) r.tv[k] = (int64_t)tb.tmap[k];
+        if (den->level_prefetch(r.tv.data(), o.respacing, p.order.data(), 1, 1) == 0) r.pf_next = 1;
+        else r.cache = p.inline_ok ? CACHE_INLINE : CACHE_NONE;
+    }
+    if (r.cache == CACHE_INLINE && den->level_cache_prepare(o.respacing) != 0) r.cache = CACHE_NONE;
+    for (const Chain& c : r.chains) if (r.cache == CACHE_SUBS && c.d->level_cache_prepare(o.respacing) != 0) r.cache = CACHE_NONE;
+    if (r.cache != CACHE_NONE) r.level_seen.assign(o.respacing, 0);
+    // (a DDIM twin restores its head from the slots of the prefetch run)
+    ChainBufs& g = bufs[1];
+    r.G = Chain{nullptr, nullptr, 0, r.B, 0, r.n, 0, r.gcols, g.nz1, g.nz_eta, g.t, g.c1, g.c2, g.lvl, &g};
+    if (p.pipe && (o.kind == 1 || r.cache == CACHE_PREFETCH) && den->pipe_begin(&r.G.d, &r.G.s) == 0) {
+        r.piped = true;
+        r.E = r.chains[0]; r.E.c_lo = r.gcols; r.E.c_hi = channels;
+        for (hipEvent_t* e : {&ev_pE, &ev_pC, &ev_pG}) if (!*e) DSH_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    return 0;
+}
+
+// the values of draw `idx` for one chain (device pointer; scratch = a full-size buffer the chain owns its element range of)
+int Sampler::noise_for(const Run& r, int64_t idx, const Chain& c, float* scratch, const float** out) {
+    const SamplerOpts& o = r.o;
+    if (o.noise_mode == 0) { *out = r.noise_stack + (size_t)idx * r.n + c.off; return 0; }
+    // (ragged: every row advances by its own size per draw, so a clip draws the same noise padded as sampled alone)
+    if (r.per_row) { if (int e = launch_philox_randn_rows(scratch + c.off, c.nb, r.row_n, o.seed, (uint64_t)idx * r.quads, row_keys + c.b0, c.s,
+                                                          r.len_d ? r.len_d + c.b0 : nullptr, (uint64_t)idx, channels,
+                                                          r.seeds_d ? r.seeds_d + c.b0 : nullptr)) return e; }
+    else if (int e = launch_philox_randn(scratch + c.off, c.cnt, o.seed, (uint64_t)idx * r.quads + c.off / 4, c.s)) return e;
+    *out = scratch + c.off;
+    return 0;
+}
+
+Sampler::StepConsts Sampler::step_consts(Run& r, const SamplerStep& sp) {
+    const int k = sp.level;
+    StepConsts sc{};
+    sc.kind = sp.kind; sc.k = k; sc.eval_idx = -1; sc.idx2 = -1;
+    if (sp.kind == STEP_UNDO) {
+        const float beta = (float)tb.betas[k];
+        sc.undo_a = sqrtf(1.0f - beta); sc.undo_b = sqrtf(beta);
+        sc.idx = r.next_draw();
+        return sc;
+    }
+    sc.eval_idx = r.n_eval++;
+    sc.t = (int64_t)tb.tmap[k]; sc.c1 = (float)tb.c1[k]; sc.c2 = (float)tb.c2[k];
+    sc.idx = r.next_draw();                                         // DDIM: randn_like of the step, times sigma (= 0 at eta = 0: drawn index, unused values)
+    if (sp.kind == STEP_DDPM) {
+        sc.coef1 = (float)tb.coef1[k]; sc.coef2 = (float)tb.coef2[k];
+        sc.sigma = k == 0 ? 0.0f : expf(0.5f * (float)tb.post_logvar[k]);
+        return sc;
+    }
+    // sigma = eta sqrt((1 - abar_prev) / (1 - abar)) sqrt(1 - abar / abar_prev), fp32 like the reference's tensors
+    const float ab = (float)tb.ac[k], abp = (float)tb.ac_prev[k];
+    sc.sqrt_ab_prev = sqrtf(abp);
+    sc.sqrt_1m_ab_prev = sqrtf(1.0f - abp);
+    sc.sigma = 0.f; sc.coef_eps = sqrtf(1.0f - abp);
+    if (r.o.eta != 0.f) {
+        sc.sigma = (r.o.eta * sqrtf((1.0f - abp) / (1.0f - ab))) * sqrtf(1.0f - ab / abp);
+        sc.coef_eps = sqrtf((1.0f - abp) - sc.sigma * sc.sigma);
+        if (k == 0) sc.sigma = 0.f;                                 // nonzero_mask: no noise at (spaced) t == 0; the mean keeps coef_eps
+    }
+    if (r.masked && !r.tail_gt) sc.idx2 = r.next_draw();            // N(0,1) of the noised gt (RePaint blend)
+    return sc;
+}
+
+// the evaluation of a step, on every chain of the run (pipelined: the expression encoder's; gesture_follow() queues the twin's)
+int Sampler::evaluate(Run& r, const LoopPlan& p, const StepConsts& sc) {
+    DenoiserBase* den = r.den;
+    const int k = sc.k;
+    const bool seen = r.cache != CACHE_NONE && r.level_seen[k];
+    const int mode = r.cache == CACHE_NONE ? 0 : (r.cache == CACHE_PREFETCH || seen) ? 2 : 1;
+    // (pipelined: E_k overwrites the expression estimate the twin copied behind E_{k-1})
+    if (r.piped && sc.eval_idx > 0) DSH_HIP_CHECK(hipStreamWaitEvent(st, ev_pC, 0));
+    const bool first_eval = sc.eval_idx == 0;
+    for (size_t i = 0; i < r.chains.size(); ++i) {
+        const Chain& c = r.chains[i];
+        if (int e = launch_fill_step(c.t, c.c1, c.c2, c.lvl, sc.t, sc.c1, sc.c2, (int64_t)k, c.nb, c.s)) return e;
+        if (r.cache == CACHE_PREFETCH && !seen) {
+            // first use: this level was queued one evaluation ago (or in setup()); queue the next new one now
+            size_t pos = 0;
+            while (pos < p.order.size() && p.order[pos] != k) ++pos;
+            const size_t want = std::min(p.order.size(), pos + 2);
+            if (want > r.pf_next) {
+                if (int e = den->level_prefetch(r.tv.data(), r.o.respacing, p.order.data() + r.pf_next, (int)(want - r.pf_next), 0)) return e;
+                r.pf_next = want;
+            }
+            if (int e = den->level_wait(k)) return e;
+        }
+        if (p.split) {
+            // every sub-batch on its own stream; at the very first evaluation sub-batch i + 1 starts a few launches behind
+            // sub-batch i (so that the kernel sequences are out of phase from the start); afterwards the streams run free
+            if (first_eval && i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(c.s, ev_sub[2 * (i - 1)], 0));
+            c.d->notify_after_launches((first_eval && i + 1 < r.chains.size()) ? ev_sub[2 * i] : nullptr, r.lag);
+            c.d->t_uniform = den->t_uniform;
+        }
+        if (int e = eval_step(c, r.x, sc.eval_idx, p.graph, mode)) return e;
+        if (p.split) c.d->notify_after_launches(nullptr, 0);
+    }
+    if (r.cache != CACHE_NONE) r.level_seen[k] = 1;
+    return 0;
+}
+
+// Pipelined loop, between the two chains' updates of a step: E_k has advanced the expression channels on the context stream; G_k on the
+// twin's takes E_k's x0 estimate and evaluates the gesture encoder at the same level (DDIM: head restored from the timestep cache, once the
+// prefetch run has filled the level; DDPM: computed).  The caller then advances the gesture channels.
+int Sampler::gesture_follow(Run& r, const LoopPlan& p, const StepConsts& sc) {
+    const Chain& G = r.G;
+    const int twin_mode = r.o.kind == 0 ? 2 : 0;
+    DSH_HIP_CHECK(hipEventRecord(ev_pE, st));
+    DSH_HIP_CHECK(hipStreamWaitEvent(G.s, ev_pE, 0));
+    if (int e = r.den->import_expr(G.d, G.s)) return e;
+    DSH_HIP_CHECK(hipEventRecord(ev_pC, G.s));
+    if (int e = launch_fill_step(G.t, G.c1, G.c2, G.lvl, sc.t, sc.c1, sc.c2, (int64_t)sc.k, G.nb, G.s)) return e;
+    if (twin_mode == 2) { if (int e = r.den->level_wait_stream(sc.k, G.s)) return e; }
+    return eval_step(G, r.x, sc.eval_idx, p.graph, twin_mode);
+}
+
+int Sampler::ddim_update(Run& r, const Chain& c, const StepConsts& sc) {
+    const SamplerOpts& o = r.o; const int k = sc.k;
+    DdimStepArgs a;
+    a.c_lo = c.c_lo; a.c_hi = c.c_hi;
+    a.x = r.x + c.off; a.eps = eps + c.off; a.x0_out = nullptr; a.c1 = sc.c1; a.c2 = sc.c2;
+    a.sqrt_ab_prev = sc.sqrt_ab_prev; a.sqrt_1m_ab_prev = sc.sqrt_1m_ab_prev;
+    a.coef_eps = sc.coef_eps; a.sigma = sc.sigma; a.noise1 = nullptr;
+    if (o.eta != 0.f) {
+        // (nz1 is the scratch of the RePaint draw below: a second buffer only exists for eta != 0)
+        const float* z1 = nullptr;
+        if (int e = noise_for(r, sc.idx, c, c.nz_eta, &z1)) return e;
+        a.noise1 = z1;
+    }
+    a.mask = nullptr; a.gt = nullptr; a.noise2 = nullptr; a.blend = 0; a.clip = o.clip_denoised;
+    a.overlap_len = o.overlap_len; a.frames = r.den->frames; a.channels = channels; a.n = c.cnt;
+    const size_t toff = (size_t)c.b0 * o.overlap_len * channels;
+    a.tail_in = nullptr; a.tail_out = r.son ? tail_tmp + toff : nullptr;
+    if (r.masked) {
+        const float* z2 = nullptr;
+        if (r.tail_gt) a.tail_in = tails + (size_t)k * r.blc + toff;
+        else if (int e = noise_for(r, sc.idx2, c, c.nz1, &z2)) return e;
+        a.mask = r.mask + c.off; a.gt = r.gt + c.off; a.noise2 = z2;
+        a.blend = (a.sqrt_1m_ab_prev < 0.2f && o.add_blend) ? 1 : 0;
+        a.tail_blend = (a.blend && tail_blend) ? 1 : 0;
+    }
+    if (int e = launch_ddim_step(a, c.s)) return e;
+    if (r.son) DSH_HIP_CHECK(hipMemcpyAsync(tails + (size_t)k * r.blc + toff, tail_tmp + toff, (size_t)c.nb * o.overlap_len * channels * sizeof(float),
+                                           hipMemcpyDeviceToDevice, c.s));
+    return 0;
+}
+
+int Sampler::ddpm_update(Run& r, const Chain& c, const StepConsts& sc) {
+    const float* z;
+    if (int e = noise_for(r, sc.idx, c, c.nz1, &z)) return e;
+    DdpmStepArgs a;
+    a.x = r.x + c.off; a.eps = eps + c.off; a.noise = z; a.x0_out = nullptr; a.c1 = sc.c1; a.c2 = sc.c2;
+    a.coef1 = sc.coef1; a.coef2 = sc.coef2; a.sigma = sc.sigma;
+    a.n = c.cnt; a.clip = r.o.clip_denoised; a.channels = channels; a.c_lo = c.c_lo; a.c_hi = c.c_hi;
+    return launch_ddpm_step(a, c.s);
+}
+
+// one chain's share of a step: its columns of its rows, on its stream (every chain draws the same values: the noise depends on the position only)
+int Sampler::update(Run& r, const Chain& c, const StepConsts& sc) {
+    if (sc.kind == STEP_DDIM) return ddim_update(r, c, sc);
+    if (sc.kind == STEP_DDPM) return ddpm_update(r, c, sc);
+    const float* z;
+    if (int e = noise_for(r, sc.idx, c, c.nz1, &z)) return e;
+    return launch_undo_step(r.x + c.off, z, sc.undo_a, sc.undo_b, c.cnt, c.s, channels, c.c_lo, c.c_hi);
+}
+
+// Everything between the fork of make_chains() and the joins of finish(): any error leaves through `return`, and run() passes the result
+// to finish() unconditionally.
+int Sampler::loop(Run& r, const LoopPlan& p) {
+    if (!r.init_from_x) {
+        const int64_t idx = r.next_draw();
+        for (const Chain& c : r.chains) {
+            const float* z;
+            if (int e = noise_for(r, idx, c, r.x, &z)) return e;
+            if (z != r.x + c.off) DSH_HIP_CHECK(hipMemcpyAsync(r.x + c.off, z, c.cnt * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+        }
+    }
+    if (int e = setup(r, p)) return e;
+    for (const SamplerStep& sp : r.steps) {
+        const StepConsts sc = step_consts(r, sp);
+        if (sp.kind != STEP_UNDO) { if (int e = evaluate(r, p, sc)) return e; }
+        if (r.piped) {
+            // each chain advances its own channels on its own stream, the gesture chain behind the expression chain's evaluation of the step
+            if (int e = update(r, r.E, sc)) return e;
+            if (sp.kind != STEP_UNDO) { if (int e = gesture_follow(r, p, sc)) return e; }
+            if (int e = update(r, r.G, sc)) return e;
+        } else {
+            for (const Chain& c : r.chains) { if (int e = update(r, c, sc)) return e; }
+        }
+        if (r.trace)
+            for (const Chain& c : r.chains)
+                DSH_HIP_CHECK(hipMemcpyAsync(r.trace + (size_t)r.step_idx * r.n + c.off, r.x + c.off, c.cnt * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+        ++r.step_idx;
+    }
+    return 0;
+}
+
+// the joins (on every exit path of loop(): the chains write x, trace and the noisy tails the caller may free) and what follows them
+int Sampler::finish(Run& r, int rc) {
+    DenoiserBase* den = r.den; const int B = r.B;
+    note_launch_value(LC_SAMPLE_STREAMS, (long long)r.chains.size());
+    note_launch_value(LC_SAMPLE_GRAPH, replayed() ? 1 : 0);
+    note_launch_value(LC_SAMPLE_PIPE, r.piped ? 1 : 0);
+    if (r.piped) {
+        // both instances go back to whole evaluations (host state: before anything that can fail); the gesture chain joins the context stream
+        (void)den->pipe_end();
+        DSH_HIP_CHECK(hipEventRecord(ev_pG, r.G.s));
+        DSH_HIP_CHECK(hipStreamWaitEvent(st, ev_pG, 0));
+    }
+    for (size_t i = 1; i < r.chains.size(); ++i) {
+        DSH_HIP_CHECK(hipEventRecord(ev_sub[2 * i + 1], r.chains[i].s));
+        DSH_HIP_CHECK(hipStreamWaitEvent(st, ev_sub[2 * i + 1], 0));
+    }
+    if (replayed()) { DSH_HIP_CHECK(hipStreamSynchronize(st)); drop_graph(); }
+    // one modality alone: the inactive columns of the result are defined — 0, or the given track bit for bit — whatever x held there (one launch
+    // behind the join, like the ragged zeroing that follows it)
+    if (rc == 0 && r.mod == 1) { if (int e = launch_fill_cols(r.x, channels, (size_t)B * den->frames, 0, r.gcols, nullptr, 0, st)) return e; }
+    if (rc == 0 && r.mod == 2) {
+        const float* track = den->modality_track();
+        DSH_REQUIRE(track != nullptr, "gesture modality without its expression track");
+        if (int e = launch_fill_cols(r.x, channels, (size_t)B * den->frames, r.gcols, channels, track, channels - r.gcols, st)) return e;
+    }
+    // ragged batch: the loop ran on the padded rows; its result is defined as exactly 0 beyond every clip's length (one launch behind the join,
+    // whatever regime the loop ran in; rows of `trace` keep the padded frames' values)
+    if (rc == 0 && r.len_d) return launch_zero_padded_frames(r.x, r.len_d, B, den->frames, channels, st);
+    return rc;
 }
 
 int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_from_x, const float* gt,
@@ -277,17 +611,18 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
     DSH_REQUIRE(!(masked && o.kind == 1), "mask-present DDPM (p_sample_loop_progressive_harmonize) is not supported");
     DSH_REQUIRE(!(tail_blend && o.same_overlap_noisy), "tail_blend with same_overlap_noisy: the saved noisy tails describe a window chain, not a window pinned at both ends");
     DSH_REQUIRE(!tail_blend || (o.overlap_len >= 0 && 2 * (int64_t)o.overlap_len <= den->frames), "tail_blend: the head and the tail fade overlap (2 * overlap_len > frames)");
-    const int B = den->batch;
+    Run r{den, o, x, init_from_x, gt, mask, masked, noise_stack, n_draws, trace};
+    const int B = r.B = den->batch;
     // One modality alone (denoiser.h, set_modality): the loop advances the active encoder's column window [w_lo, w_hi) only — every step launch
     // of every regime takes it — and its result holds 0 (expression mode) or the given track (gesture mode) in the other columns.  Noise
     // addressing stays that of the full-width row, so an active column receives the value it receives in the joint run.
-    const int mod = den->modality, gcols = den->gesture_channels();
+    const int mod = r.mod = den->modality, gcols = r.gcols = den->gesture_channels();
     DSH_REQUIRE(mod == 0 || (gcols > 0 && gcols < channels), "a partial modality needs the UniDiffuser's two encoders");
     DSH_REQUIRE(mod == 0 || !o.same_overlap_noisy, "same_overlap_noisy with a partial modality: the saved noisy tails describe all channels");
-    const int w_lo = mod == 1 ? gcols : 0, w_hi = mod == 0 ? 0 : (mod == 1 ? channels : gcols);      // (0, 0: all columns)
+    r.w_lo = mod == 1 ? gcols : 0; r.w_hi = mod == 0 ? 0 : (mod == 1 ? channels : gcols);      // (0, 0: all columns)
     // ragged batch (set_condition_ragged): per-clip frame counts of the padded batch, host and device copies owned by the context
     const int32_t* len_h = den->lengths_host();
-    const int* len_d = den->lengths_dev();
+    r.len_d = den->lengths_dev();
     // (both address the last overlap_len frames of the PADDED window, which a short clip does not reach)
     DSH_REQUIRE(!len_h || (!o.same_overlap_noisy && !tail_blend), "per-clip lengths cannot be combined with same_overlap_noisy or the tail blend");
     if (len_h && o.noise_mode == 1 && n_row_keys == B)
@@ -296,343 +631,14 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
     // failed launch below must not leave the context answering later evaluations as if a loop were still running)
     struct LoopScope { DenoiserBase* d; ~LoopScope() { (void)d->loop_end(); } } loop_scope{den};
     if (int e = den->loop_begin(o.kind)) return e;          // (may re-condition a mid-size batch as one batch: the two encoder chains replace the sub-batch streams)
-    den->t_uniform = emb_dedup_enabled();   // every evaluation of a sampling loop runs the whole batch at ONE timestep (launch_fill_step below)
-    const size_t n = (size_t)B * den->frames * channels;
-    std::vector<SamplerStep> steps; std::string err;
-    if (plan_steps(o, masked, steps, err)) { set_last_error(err); return -1; }
-    const int64_t need = sampler_num_draws(o, masked, init_from_x);
-    if (o.noise_mode == 0) {
-        DSH_REQUIRE(noise_stack != nullptr && n_draws >= need, "noise stack shorter than the loop's draw count");
-    }
-    // tables are cached per (steps, respacing)
-    const int resp = o.kind == 1 ? 0 : o.respacing;
-    if (tb_steps != o.diffusion_steps || tb_resp != resp) {
-        if (make_tables(o.diffusion_steps, resp, tb, err)) { set_last_error(err); return -1; }
-        tb_steps = o.diffusion_steps; tb_resp = resp;
-    }
-    if (int e = ensure(n, B)) return e;
-    if (o.kind == 0 && o.eta != 0.f && o.noise_mode == 1 && cap_eta < n) {
-        DSH_HIP_CHECK(hipStreamSynchronize(st));
-        if (nz_eta) (void)hipFree(nz_eta);
-        nz_eta = nullptr; cap_eta = 0;
-        DSH_HIP_CHECK(hipMalloc((void**)&nz_eta, n * sizeof(float)));
-        cap_eta = n;
-    }
-
-    DSH_REQUIRE(n_row_keys == 0 || o.noise_mode != 1 || (n_row_keys == B && (n / B) % 4 == 0),
-                "row keys were set for a different batch size (or frames*channels is not a multiple of 4)");
-    const bool per_row = o.noise_mode == 1 && n_row_keys == B;
-    const uint64_t* seeds_d = (per_row && n_row_seeds == B) ? row_seeds : nullptr;      // (set_row_seeds: always the row keys' count)
-    // --same_overlap_noisy state
-    const size_t blc = (size_t)B * o.overlap_len * channels;
-    const bool son = o.same_overlap_noisy != 0 && o.kind == 0;
-    if (son) {
-        DSH_REQUIRE(o.overlap_len > 0 && o.overlap_len <= den->frames, "same_overlap_noisy needs 0 < overlap_len <= frames");
-        if (tails_blc != blc || tails_levels != o.respacing) {
-            DSH_REQUIRE(o.clip_idx == 0 || !masked, "same_overlap_noisy: the saved noisy tails belong to a different batch / overlap shape");
-            DSH_HIP_CHECK(hipStreamSynchronize(st));
-            if (tails) (void)hipFree(tails);
-            if (tail_tmp) (void)hipFree(tail_tmp);
-            tails = nullptr; tail_tmp = nullptr;
-            DSH_HIP_CHECK(hipMalloc((void**)&tails, blc * o.respacing * sizeof(float)));
-            DSH_HIP_CHECK(hipMalloc((void**)&tail_tmp, blc * sizeof(float)));
-            DSH_HIP_CHECK(hipMemsetAsync(tails, 0, blc * o.respacing * sizeof(float), st));
-            tails_blc = blc; tails_levels = o.respacing;
-        }
-    }
-    const bool tail_gt = son && masked && o.clip_idx > 0;
-    int64_t draw = 0;
-    const uint64_t quads = per_row ? (n / B) / 4 : (n + 3) / 4;
-    const size_t row_n = n / B;                        // values per batch row
-    // ---- sub-batch streams (large batches): every sub-batch runs the WHOLE loop on its own stream; one fork, one join ----------
-    struct Sub { DenoiserBase* d; hipStream_t s; int b0, nb; size_t off, cnt; };
-    std::vector<Sub> subs;
-    {
-        const int ns = (prof && prof->on) ? 1 : den->sub_count();
-        if (ns > 1 && row_n % 4 == 0) {
-            for (int i = 0; i < ns; ++i) {
-                Sub u;
-                if (int e = den->sub_get(i, &u.d, &u.s, &u.b0, &u.nb)) return e;
-                u.off = (size_t)u.b0 * row_n; u.cnt = (size_t)u.nb * row_n;
-                subs.push_back(u);
-            }
-            if (!ev_fork) DSH_HIP_CHECK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-            while (ev_sub.size() < 2 * subs.size()) { hipEvent_t e; DSH_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ev_sub.push_back(e); }
-            DSH_HIP_CHECK(hipEventRecord(ev_fork, st));
-            for (size_t i = 1; i < subs.size(); ++i) DSH_HIP_CHECK(hipStreamWaitEvent(subs[i].s, ev_fork, 0));
-        } else {
-            subs.push_back(Sub{den, st, 0, B, 0, n});
-        }
-    }
-    const bool split = subs.size() > 1;
-    // the next N(0,1) tensor of the loop: draw index (advanced once per draw, whatever the split) ...
-    auto next_draw = [&]() -> int64_t { return draw++; };
-    // ... and its values for one sub-batch (device pointer; scratch = a full-size buffer the sub-batch owns its slice of)
-    auto noise_for = [&](int64_t idx, const Sub& u, float* scratch, const float** out) -> int {
-        if (o.noise_mode == 0) { *out = noise_stack + (size_t)idx * n + u.off; return 0; }
-        // (ragged: every row advances by its own size per draw, so a clip draws the same noise padded as sampled alone)
-        if (per_row) { if (int e = launch_philox_randn_rows(scratch + u.off, u.nb, row_n, o.seed, (uint64_t)idx * quads, row_keys + u.b0, u.s,
-                                                            len_d ? len_d + u.b0 : nullptr, (uint64_t)idx, channels,
-                                                            seeds_d ? seeds_d + u.b0 : nullptr)) return e; }
-        else if (int e = launch_philox_randn(scratch + u.off, u.cnt, o.seed, (uint64_t)idx * quads + u.off / 4, u.s)) return e;
-        *out = scratch + u.off;
-        return 0;
-    };
-
-    // pipelined small-batch loop (denoiser.h): expression encoder on the context stream, gesture encoder one step behind on the twin's
-    DenoiserBase* twin = nullptr; hipStream_t sG = nullptr; bool pipe = false; int gch = 0;
-    // everything between the fork above and the join below: any error leaves through `return` of this lambda, so that the sub-batch
-    // streams are joined into the context stream on EVERY exit path (they write x, trace and the noisy tails the caller may free)
-    auto loop = [&]() -> int {
-    if (!init_from_x) {
-        const int64_t idx = next_draw();
-        for (const Sub& u : subs) {
-            const float* z;
-            if (int e = noise_for(idx, u, x, &z)) return e;
-            if (z != x + u.off) DSH_HIP_CHECK(hipMemcpyAsync(x + u.off, z, u.cnt * sizeof(float), hipMemcpyDeviceToDevice, u.s));
-        }
-    }
-    const bool do_mask = masked;
-    int64_t step_idx = 0;
-    // graphs only where launches dominate (a few thousand token rows), never while profiling events are recorded,
-    // and never on the legacy NULL stream (it cannot be captured)
-    const bool small = (size_t)B * den->frames <= (size_t)switch_int(SW_GRAPH_ROWS);
-    const bool use_graph = st != nullptr && small && !(prof && prof->on) && !switch_present(SW_NO_GRAPH);
-    int n_eval = 0;
-    drop_graph();
-    // timestep cache (denoiser.h): worth it when the schedule revisits levels (out-painting jump schedule: 63 evaluations
-    // over 16 levels); small (launch-bound) batches only.  DSH_LEVEL_CACHE=0 disables it.
-    std::vector<char> level_seen;
-    bool prefetched = false;
-    std::vector<int> order;              // levels in first-use order
-    std::vector<int64_t> tv;             // level -> model timestep
-    size_t pf_next = 0;                  // order[0 .. pf_next) have been handed to the prefetch stream
-    // (the side-stream head and the two-stream encoder pipeline also pay above the graph range, up to where batches are split over sub-batch
-    //  streams: DSH_PIPE_ROWS)
-    const bool small_pf = (size_t)B * den->frames <= pipe_rows();
-    if ((small || small_pf) && o.kind == 0 && !split) {
-        std::vector<int> cnt(o.respacing, 0);
-        int evals = 0, distinct = 0;
-        for (const SamplerStep& sp : steps) if (sp.kind != STEP_UNDO) { ++evals; if (cnt[sp.level]++ == 0) { ++distinct; order.push_back(sp.level); } }
-        const bool cache_on = switch_int(SW_LEVEL_CACHE) != 0;
-        // side-stream prefetch of every scheduled level (also pays for schedules without repeats); else the inline cache
-        // (one level is queued now, the others one evaluation ahead of their first use: the host never runs far in front of
-        //  the main chain, and the main chain never waits for the host to finish queueing 25 levels)
-        if (cache_on && st != nullptr && !(prof && prof->on) && !order.empty()) {
-            tv.resize(o.respacing);
-            for (int k = 0; k < o.respacing; ++k) tv[k] = (int64_t)tb.tmap[k];
-            prefetched = den->level_prefetch(tv.data(), o.respacing, order.data(), 1, 1) == 0;
-            if (prefetched) pf_next = 1;
-        }
-        if (prefetched) level_seen.assign(o.respacing, 0);
-        else if (evals > distinct && cache_on && den->level_cache_prepare(o.respacing) == 0) level_seen.assign(o.respacing, 0);
-        // the two encoders' chains on two streams: every evaluation restores its head from the slots the prefetch run fills (mode 2), no
-        // per-step trace of the whole sample, no saved noisy tails (both need all channels of a step at once)
-        gch = den->gesture_channels();
-        if (mod == 0 && prefetched && !trace && !son && nz1G && n <= capG_n && gch > 0 && gch < channels && den->pipe_begin(&twin, &sG) == 0) {
-            pipe = true;
-            for (hipEvent_t* e : {&ev_pE, &ev_pC, &ev_pG}) if (!*e) DSH_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        }
-    }
-    // DDPM loops have no timestep cache (every level is visited once, 1000 of them): each chain computes its own head
-    if (mod == 0 && !pipe && o.kind == 1 && !split && small_pf && !trace && nz1G && n <= capG_n) {
-        gch = den->gesture_channels();
-        if (gch > 0 && gch < channels && den->pipe_begin(&twin, &sG) == 0) {
-            pipe = true;
-            for (hipEvent_t* e : {&ev_pE, &ev_pC, &ev_pG}) if (!*e) DSH_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        }
-    }
-    const int twin_mode = o.kind == 0 ? 2 : 0;
-    // sub-batch streams: the inline timestep cache for schedules that revisit levels, else plain evaluations
-    bool split_cache = false;
-    if (split && o.kind == 0) {
-        std::vector<int> cnt(o.respacing, 0);
-        int evals = 0, distinct = 0;
-        for (const SamplerStep& sp : steps) if (sp.kind != STEP_UNDO) { ++evals; if (cnt[sp.level]++ == 0) ++distinct; }
-        if (evals > distinct && switch_int(SW_LEVEL_CACHE) != 0) {
-            split_cache = true;
-            for (const Sub& u : subs) split_cache = split_cache && u.d->level_cache_prepare(o.respacing) == 0;
-            if (split_cache) level_seen.assign(o.respacing, 0);
-        }
-    }
-    const int lag = (int)switch_int(SW_DUAL_LAG);
-    bool first_eval = true;
-    for (const SamplerStep& sp : steps) {
-        const int k = sp.level;
-        if (sp.kind == STEP_UNDO) {
-            const float beta = (float)tb.betas[k];
-            const int64_t idx = next_draw();
-            if (pipe) {
-                // each chain undoes its own channels on its own stream (same draw, same values: the noise depends on the position only)
-                const Sub uE{den, st, 0, B, 0, n}, uG{twin, sG, 0, B, 0, n};
-                const float *zE, *zG;
-                if (int e = noise_for(idx, uE, nz1, &zE)) return e;
-                if (int e = launch_undo_step(x, zE, sqrtf(1.0f - beta), sqrtf(beta), n, st, channels, gch, channels)) return e;
-                if (int e = noise_for(idx, uG, nz1G, &zG)) return e;
-                if (int e = launch_undo_step(x, zG, sqrtf(1.0f - beta), sqrtf(beta), n, sG, channels, 0, gch)) return e;
-            } else
-            for (const Sub& u : subs) {
-                const float* z;
-                if (int e = noise_for(idx, u, nz1, &z)) return e;
-                if (int e = launch_undo_step(x + u.off, z, sqrtf(1.0f - beta), sqrtf(beta), u.cnt, u.s, channels, w_lo, w_hi)) return e;
-            }
-        } else {
-            const float c1 = (float)tb.c1[k], c2 = (float)tb.c2[k];
-            int mode = 0;
-            if (!split) {
-                // (pipelined: E_k overwrites the expression estimate the twin copied behind E_{k-1})
-                if (pipe && n_eval > 0) DSH_HIP_CHECK(hipStreamWaitEvent(st, ev_pC, 0));
-                if (int e = launch_fill_step(tbuf, c1buf, c2buf, lvlbuf, (int64_t)tb.tmap[k], c1, c2, (int64_t)k, B, st)) return e;
-                if (prefetched) {
-                    mode = 2;
-                    if (!level_seen[k]) {
-                        // first use: this level was queued one evaluation ago (or just above); queue the next new one now
-                        size_t pos = 0;
-                        while (pos < order.size() && order[pos] != k) ++pos;
-                        const size_t want = std::min(order.size(), pos + 2);
-                        if (want > pf_next) {
-                            if (int e = den->level_prefetch(tv.data(), o.respacing, order.data() + pf_next, (int)(want - pf_next), 0)) return e;
-                            pf_next = want;
-                        }
-                        if (int e = den->level_wait(k)) return e;
-                        level_seen[k] = 1;
-                    }
-                } else if (!level_seen.empty()) { mode = level_seen[k] ? 2 : 1; level_seen[k] = 1; }
-                if (int e = eval_step(den, x, n_eval++, use_graph, mode)) return e;
-            } else {
-                // every sub-batch on its own stream; at the very first evaluation sub-batch i + 1 starts a few launches behind
-                // sub-batch i (so that the kernel sequences are out of phase from the start); afterwards the streams run free
-                for (size_t i = 0; i < subs.size(); ++i) {
-                    const Sub& u = subs[i];
-                    if (int e = launch_fill_step(tbuf + u.b0, c1buf + u.b0, c2buf + u.b0, lvlbuf + i, (int64_t)tb.tmap[k], c1, c2, (int64_t)k, u.nb, u.s)) return e;
-                    if (first_eval && i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(u.s, ev_sub[2 * (i - 1)], 0));
-                    u.d->notify_after_launches((first_eval && i + 1 < subs.size()) ? ev_sub[2 * i] : nullptr, lag);
-                    const int smode = split_cache ? (level_seen[k] ? 2 : 1) : 0;
-                    u.d->t_uniform = den->t_uniform;
-                    if (int e = u.d->eval_level(x + u.off, tbuf + u.b0, c1buf + u.b0, c2buf + u.b0, eps + u.off, smode, lvlbuf + i)) return e;
-                    u.d->notify_after_launches(nullptr, 0);
-                }
-                if (split_cache) level_seen[k] = 1;
-                first_eval = false;
-                ++n_eval;
-            }
-            if (sp.kind == STEP_DDIM) {
-                const int64_t idx1 = next_draw();                               // randn_like of the step: times sigma (= 0 at eta = 0)
-                // sigma = eta sqrt((1 - abar_prev) / (1 - abar)) sqrt(1 - abar / abar_prev), fp32 like the reference's tensors
-                float sigma = 0.f, coef_eps = sqrtf(1.0f - (float)tb.ac_prev[k]);
-                if (o.eta != 0.f) {
-                    const float ab = (float)tb.ac[k], abp1 = (float)tb.ac_prev[k];
-                    sigma = (o.eta * sqrtf((1.0f - abp1) / (1.0f - ab))) * sqrtf(1.0f - ab / abp1);
-                    coef_eps = sqrtf((1.0f - abp1) - sigma * sigma);
-                    if (k == 0) sigma = 0.f;                                    // nonzero_mask: no noise at (spaced) t == 0; the mean keeps coef_eps
-                }
-                const int64_t idx2 = (do_mask && !tail_gt) ? next_draw() : -1;   // N(0,1) of the noised gt (RePaint blend)
-                auto ddim_update = [&](const Sub& u, float* sc1, float* sc_eta, int c_lo, int c_hi) -> int {
-                    DdimStepArgs a;
-                    a.c_lo = c_lo; a.c_hi = c_hi;
-                    a.x = x + u.off; a.eps = eps + u.off; a.x0_out = nullptr; a.c1 = c1; a.c2 = c2;
-                    const float abp = (float)tb.ac_prev[k];
-                    a.sqrt_ab_prev = sqrtf(abp);
-                    a.sqrt_1m_ab_prev = sqrtf(1.0f - abp);
-                    a.coef_eps = coef_eps; a.sigma = sigma; a.noise1 = nullptr;
-                    if (o.eta != 0.f) {
-                        // (nz1 is the scratch of this draw AND of the RePaint draw below: a second buffer only exists for eta != 0)
-                        const float* z1 = nullptr;
-                        if (int e = noise_for(idx1, u, sc_eta, &z1)) return e;
-                        a.noise1 = z1;
-                    }
-                    a.mask = nullptr; a.gt = nullptr; a.noise2 = nullptr; a.blend = 0; a.clip = o.clip_denoised;
-                    a.overlap_len = o.overlap_len; a.frames = den->frames; a.channels = channels; a.n = u.cnt;
-                    const size_t toff = (size_t)u.b0 * o.overlap_len * channels;
-                    a.tail_in = nullptr; a.tail_out = son ? tail_tmp + toff : nullptr;
-                    if (do_mask) {
-                        const float* z2 = nullptr;
-                        if (tail_gt) a.tail_in = tails + (size_t)k * blc + toff;
-                        else if (int e = noise_for(idx2, u, sc1, &z2)) return e;
-                        a.mask = mask + u.off; a.gt = gt + u.off; a.noise2 = z2;
-                        a.blend = (a.sqrt_1m_ab_prev < 0.2f && o.add_blend) ? 1 : 0;
-                        a.tail_blend = (a.blend && tail_blend) ? 1 : 0;
-                    }
-                    if (int e = launch_ddim_step(a, u.s)) return e;
-                    if (son) DSH_HIP_CHECK(hipMemcpyAsync(tails + (size_t)k * blc + toff, tail_tmp + toff, (size_t)u.nb * o.overlap_len * channels * sizeof(float),
-                                                         hipMemcpyDeviceToDevice, u.s));
-                    return 0;
-                };
-                if (pipe) {
-                    // E_k: the expression channels advance on the context stream ...
-                    if (int e = ddim_update(Sub{den, st, 0, B, 0, n}, nz1, nz_eta, gch, channels)) return e;
-                    DSH_HIP_CHECK(hipEventRecord(ev_pE, st));
-                    // ... G_k on the twin's: takes E_k's x0 estimate, evaluates the gesture encoder at the same level, advances the gesture channels
-                    DSH_HIP_CHECK(hipStreamWaitEvent(sG, ev_pE, 0));
-                    if (int e = den->import_expr(twin, sG)) return e;
-                    DSH_HIP_CHECK(hipEventRecord(ev_pC, sG));
-                    if (int e = launch_fill_step(tbufG, c1bufG, c2bufG, lvlbufG, (int64_t)tb.tmap[k], c1, c2, (int64_t)k, B, sG)) return e;
-                    if (twin_mode == 2) { if (int e = den->level_wait_stream(k, sG)) return e; }
-                    if (int e = eval_step_twin(twin, sG, x, n_eval - 1, use_graph, twin_mode)) return e;
-                    if (int e = ddim_update(Sub{twin, sG, 0, B, 0, n}, nz1G, nz_etaG, 0, gch)) return e;
-                } else
-                for (const Sub& u : subs) { if (int e = ddim_update(u, nz1, nz_eta, w_lo, w_hi)) return e; }
-            } else {
-                const int64_t idx = next_draw();
-                auto ddpm_update = [&](const Sub& u, float* sc, int c_lo, int c_hi) -> int {
-                    const float* z;
-                    if (int e = noise_for(idx, u, sc, &z)) return e;
-                    DdpmStepArgs a;
-                    a.x = x + u.off; a.eps = eps + u.off; a.noise = z; a.x0_out = nullptr; a.c1 = c1; a.c2 = c2;
-                    a.coef1 = (float)tb.coef1[k]; a.coef2 = (float)tb.coef2[k];
-                    a.sigma = k == 0 ? 0.0f : expf(0.5f * (float)tb.post_logvar[k]);
-                    a.n = u.cnt; a.clip = o.clip_denoised; a.channels = channels; a.c_lo = c_lo; a.c_hi = c_hi;
-                    return launch_ddpm_step(a, u.s);
-                };
-                if (pipe) {
-                    if (int e = ddpm_update(Sub{den, st, 0, B, 0, n}, nz1, gch, channels)) return e;
-                    DSH_HIP_CHECK(hipEventRecord(ev_pE, st));
-                    DSH_HIP_CHECK(hipStreamWaitEvent(sG, ev_pE, 0));
-                    if (int e = den->import_expr(twin, sG)) return e;
-                    DSH_HIP_CHECK(hipEventRecord(ev_pC, sG));
-                    if (int e = launch_fill_step(tbufG, c1bufG, c2bufG, lvlbufG, (int64_t)tb.tmap[k], c1, c2, (int64_t)k, B, sG)) return e;
-                    if (int e = eval_step_twin(twin, sG, x, n_eval - 1, use_graph, twin_mode)) return e;
-                    if (int e = ddpm_update(Sub{twin, sG, 0, B, 0, n}, nz1G, 0, gch)) return e;
-                } else
-                for (const Sub& u : subs) { if (int e = ddpm_update(u, nz1, w_lo, w_hi)) return e; }
-            }
-        }
-        if (trace)
-            for (const Sub& u : subs)
-                DSH_HIP_CHECK(hipMemcpyAsync(trace + (size_t)step_idx * n + u.off, x + u.off, u.cnt * sizeof(float), hipMemcpyDeviceToDevice, u.s));
-        ++step_idx;
-    }
-    return 0;
-    };
-    const int rc = loop();
-    note_launch_value(LC_SAMPLE_STREAMS, (long long)subs.size());
-    note_launch_value(LC_SAMPLE_GRAPH, (graph_exec[0] || graph_exec[1] || graph_exec[2]) ? 1 : 0);
-    note_launch_value(LC_SAMPLE_PIPE, pipe ? 1 : 0);
-    if (pipe) {
-        // both instances go back to whole evaluations (host state: before anything that can fail), and the gesture chain joins the context
-        // stream on every exit path
-        (void)den->pipe_end();
-        DSH_HIP_CHECK(hipEventRecord(ev_pG, sG));
-        DSH_HIP_CHECK(hipStreamWaitEvent(st, ev_pG, 0));
-    }
-    if (split)
-        for (size_t i = 1; i < subs.size(); ++i) {
-            DSH_HIP_CHECK(hipEventRecord(ev_sub[2 * i + 1], subs[i].s));
-            DSH_HIP_CHECK(hipStreamWaitEvent(st, ev_sub[2 * i + 1], 0));
-        }
-    if (graph_exec[0] || graph_exec[1] || graph_exec[2]) { DSH_HIP_CHECK(hipStreamSynchronize(st)); drop_graph(); }
-    // ragged batch: the loop ran on the padded rows; its result is defined as exactly 0 beyond every clip's length (one launch behind the join,
-    // whatever regime the loop ran in; rows of `trace` keep the padded frames' values)
-    // one modality alone: the inactive columns of the result are defined — 0, or the given track bit for bit — whatever x held there (one launch
-    // behind the join, like the ragged zeroing that follows it)
-    if (rc == 0 && mod == 1) { if (int e = launch_fill_cols(x, channels, (size_t)B * den->frames, 0, gcols, nullptr, 0, st)) return e; }
-    if (rc == 0 && mod == 2) {
-        const float* track = den->modality_track();
-        DSH_REQUIRE(track != nullptr, "gesture modality without its expression track");
-        if (int e = launch_fill_cols(x, channels, (size_t)B * den->frames, gcols, channels, track, channels - gcols, st)) return e;
-    }
-    if (rc == 0 && len_d) return launch_zero_padded_frames(x, len_d, B, den->frames, channels, st);
-    return rc;
+    den->t_uniform = emb_dedup_enabled();   // every evaluation of a sampling loop runs the whole batch at ONE timestep (launch_fill_step)
+    r.n = (size_t)B * den->frames * channels; r.row_n = r.n / B;
+    if (int e = prepare(r)) return e;
+    if (int e = make_chains(r)) return e;
+    const LoopPlan p = plan(r);
+    // from the fork to the joins: loop() reports an error by returning, finish() joins the chains into the context stream whatever it returned
+    const int rc = loop(r, p);
+    return finish(r, rc);
 }
 
 }  // namespace dsh

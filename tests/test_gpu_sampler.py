@@ -427,6 +427,88 @@ def test_pipelined_encoder_chains_are_bit_identical(ds, precision, B, monkeypatc
     monkeypatch.delenv("DSH_PIPE")
 
 
+def _outpaint(cfg, B, gt_seed=5):
+    T, Cc, L = cfg.n_poses, cfg.net_dim_pose, cfg.overlap_len
+    gt = torch.zeros(B, T, Cc)
+    gt[:, :L] = torch.randn(B, L, Cc, generator=torch.Generator().manual_seed(gt_seed))
+    mask = torch.zeros_like(gt, dtype=torch.bool)
+    mask[:, :L] = True
+    return gt, mask
+
+
+def _sample_flags():
+    from diffsheg_amd import _lib
+    torch.cuda.synchronize()
+    got = _lib.launch_counts()
+    return got["sample_graph"], got["sample_pipe"], got["sample_streams"]
+
+
+@pytest.mark.parametrize("ds,precision,B", [("show", "bf16", 2), ("beat", "fp32", 3)])
+def test_pipelined_outpainting_with_eta_is_bit_identical(ds, precision, B, monkeypatch):
+    """An out-painting window (jump schedule with undo steps, RePaint gt noise) at eta = 0.5: every DDIM step of either encoder chain draws
+    both the step's own noise and the gt noise, so both noise scratch buffers of both chains are live in one step.  Pipelined and
+    sequential loops give the same bits."""
+    cfg = get_config(ds)
+    model = gpu_model(ds, precision)
+    tr = DDPMTrainer(sampler_namespace(cfg), model)
+    gt, mask = _outpaint(cfg, B)
+    kw = _kwargs(cfg, make_inputs(cfg, B, seed=43 + B), {"gt": gt, "outpainting_mask": mask})
+    outs = []
+    for pipe in ("1", "0", "1"):
+        monkeypatch.setenv("DSH_PIPE", pipe)
+        outs.append(tr.diffusion_ddim_val.ddim_sample_loop(model, (B, cfg.n_poses, cfg.net_dim_pose), clip_denoised=False, model_kwargs=kw,
+                                                           seed=19, eta=0.5).clone())
+        assert _sample_flags()[1] == int(pipe), pipe
+    monkeypatch.delenv("DSH_PIPE")
+    assert torch.isfinite(outs[0]).all()
+    for o2 in outs[1:]:
+        assert torch.equal(outs[0], o2), float((outs[0] - o2).abs().max())
+
+
+def test_pipelined_ddpm_above_the_graph_range_is_bit_identical(monkeypatch):
+    """SHOW bf16, B = 47 (4 136 token rows: one batch above DSH_GRAPH_ROWS = 4 096), the 50-step ancestral loop with row keys: the two encoder
+    chains evaluate eagerly, each computing its own head.  Both runs are one unsplit batch of the same shape, so every launch runs the same
+    kernel on the same values."""
+    cfg = get_config("show")
+    model = gpu_model("show", "bf16")
+    tr = DDPMTrainer(sampler_namespace(cfg, ddim=False, diffusion_steps=50), model)
+    B = 47
+    kw = _kwargs(cfg, make_inputs(cfg, B, seed=47), {})
+    outs = {}
+    for pipe in ("1", "0"):
+        monkeypatch.setenv("DSH_PIPE", pipe)
+        outs[pipe] = tr.diffusion.p_sample_loop(model, (B, cfg.n_poses, cfg.net_dim_pose), clip_denoised=False, model_kwargs=kw, seed=29,
+                                                row_keys=list(range(B))).clone()
+        assert _sample_flags() == (0, int(pipe), 1), pipe
+    monkeypatch.delenv("DSH_PIPE")
+    assert torch.isfinite(outs["1"]).all()
+    assert torch.equal(outs["1"], outs["0"]), float((outs["1"] - outs["0"]).abs().max())
+
+
+def test_sub_batch_streams_share_the_noise_scratch_by_offset(monkeypatch):
+    """SHOW fp32, B = 50 (4 400 token rows: two sub-batch streams), an out-painting window at eta = 0.5 with one Philox stream per row: both
+    sub-batches draw both noises of a step into their own slices of the shared scratch buffers.  Rows at the batch ends and on either side of
+    the split equal the row sampled alone (the gate of test_gpu_dispatch_sweep.py's loops: LOOP_TOL["fp32"])."""
+    monkeypatch.setenv("DSH_PIPE", "0")
+    cfg = get_config("show")
+    model = gpu_model("show", "fp32")
+    tr = DDPMTrainer(sampler_namespace(cfg), model)
+    B, shape1 = 50, (1, cfg.n_poses, cfg.net_dim_pose)
+    inp = make_inputs(cfg, B, seed=53)
+    gt, mask = _outpaint(cfg, B)
+    full = tr.diffusion_ddim_val.ddim_sample_loop(model, (B,) + shape1[1:], clip_denoised=False, seed=31, eta=0.5, row_keys=list(range(B)),
+                                                  model_kwargs=_kwargs(cfg, inp, {"gt": gt, "outpainting_mask": mask})).clone()
+    assert _sample_flags()[2] == 2
+    assert torch.isfinite(full).all()
+    for b in (0, 24, 25, 49):
+        kw = _kwargs(cfg, {k: v[b:b + 1] for k, v in inp.items()}, {"gt": gt[b:b + 1], "outpainting_mask": mask[b:b + 1]})
+        solo = tr.diffusion_ddim_val.ddim_sample_loop(model, shape1, clip_denoised=False, seed=31, eta=0.5, row_keys=[b], model_kwargs=kw)
+        e = rel_err(solo[0], full[b])
+        print(f"[two sub-batch streams, out-painting, eta 0.5] row {b} vs the row sampled alone: rel err {e:.3e}")
+        assert e < 1e-5, b
+    monkeypatch.delenv("DSH_PIPE")
+
+
 def test_philox_mode_runs_and_is_seed_deterministic():
     cfg = get_config("show")
     model = gpu_model("show", "fp32")
