@@ -66,6 +66,11 @@ SYMBOLS = {
     "dsh_sample_set_row_keys": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int32]),
     "dsh_sample_set_row_seeds": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int32]),
     "dsh_sample_set_tail_blend": (C.c_int, [_P, C.c_int32]),
+    "dsh_sample_set_start_level": (C.c_int, [_P, C.c_int32]),
+    "dsh_sample_num_draws_from": (C.c_int64, [C.POINTER(SamplerOptsC), C.c_int32, C.c_int32, C.c_int32]),
+    "dsh_sample_num_steps_from": (C.c_int64, [C.POINTER(SamplerOptsC), C.c_int32, C.c_int32, C.c_int32]),
+    "dsh_invert": (C.c_int, [_P, C.POINTER(SamplerOptsC), _P, C.c_int32, _P]),
+    "dsh_invert_from": (C.c_int, [_P, C.POINTER(SamplerOptsC), _P, C.c_int32, C.c_int32, _P]),
     "dsh_set_guidance_scale": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32]),
     "dsh_diffusion_table": (C.c_int32, [C.c_int32, C.c_int32, C.c_char_p, C.POINTER(C.c_double), C.c_int32]),
     "dsh_timestep_map": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
@@ -90,6 +95,8 @@ SYMBOLS = {
     "dsh_op_layernorm": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "dsh_op_ddim_step": (C.c_int, [_P] * 6 + [C.c_int32] * 3 + [C.c_float] * 4 + [C.c_int32] * 6),
     "dsh_op_philox_randn": (C.c_int, [_P, _P, C.c_int64, C.c_uint64, C.c_uint64]),
+    "dsh_op_q_sample": (C.c_int, [_P] * 6 + [C.c_int32] * 6 + [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), _P, C.POINTER(C.c_int32), C.c_uint64]),
+    "dsh_op_region_mask": (C.c_int, [_P, C.POINTER(C.c_int32), _P, C.c_int32, C.POINTER(C.c_int32), _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "dsh_op_philox_randn_rows": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "dsh_op_philox_randn_rows_ragged": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
                                                   C.c_uint64, C.c_int32]),

@@ -264,7 +264,16 @@ static dsh::SamplerOpts to_opts(const dsh_sampler_opts* o) {
 
 int64_t dsh_sample_num_draws(const dsh_sampler_opts* opts, int32_t masked, int32_t init_from_x) {
     if (!opts) { dsh::set_last_error("null opts"); return -1; }
-    return dsh::sampler_num_draws(to_opts(opts), masked != 0, init_from_x != 0);
+    return dsh::sampler_num_draws(to_opts(opts), masked != 0, init_from_x != 0 ? 1 : 0);
+}
+int64_t dsh_sample_num_draws_from(const dsh_sampler_opts* opts, int32_t masked, int32_t init, int32_t start_level) {
+    if (!opts) { dsh::set_last_error("null opts"); return -1; }
+    return dsh::sampler_num_draws(to_opts(opts), masked != 0, init, start_level);
+}
+int64_t dsh_sample_num_steps_from(const dsh_sampler_opts* opts, int32_t masked, int32_t init, int32_t start_level) {
+    if (!opts) { dsh::set_last_error("null opts"); return -1; }
+    if (init < 0 || init > 2) { dsh::set_last_error("unknown init mode"); return -1; }
+    return dsh::sampler_num_steps(to_opts(opts), masked != 0, start_level);
 }
 int64_t dsh_sample_num_steps(const dsh_sampler_opts* opts, int32_t masked) {
     if (!opts) { dsh::set_last_error("null opts"); return -1; }
@@ -293,6 +302,13 @@ int dsh_sample_set_tail_blend(dsh_ctx* ctx, int32_t on) {
     API_END
 }
 
+int dsh_sample_set_start_level(dsh_ctx* ctx, int32_t level) {
+    API_BEGIN
+    DSH_REQUIRE(ctx, "null context");
+    return ctx->sampler->set_start_level(level);
+    API_END
+}
+
 int dsh_set_guidance_scale(dsh_ctx* ctx, const float* scales_host, int32_t n) {
     API_BEGIN
     DSH_REQUIRE(ctx, "null context");
@@ -305,9 +321,21 @@ int dsh_sample(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t ini
     API_BEGIN
     DSH_REQUIRE(ctx && opts, "null argument");
     if (int e = check_guidance(ctx)) return e;
-    return ctx->sampler->run(ctx->den.get(), to_opts(opts), x, init_from_x != 0, gt, mask, masked != 0, noise_stack,
+    DSH_REQUIRE(init_from_x >= 0 && init_from_x <= 2, "init_from_x: 0 (x_T is drawn), 1 (x is given) or 2 (x holds x0)");
+    return ctx->sampler->run(ctx->den.get(), to_opts(opts), x, init_from_x, gt, mask, masked != 0, noise_stack,
                              n_draws, trace);
     API_END
+}
+
+int dsh_invert_from(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t from_level, int32_t to_level, float* trace) {
+    API_BEGIN
+    DSH_REQUIRE(ctx && opts, "null argument");
+    if (int e = check_guidance(ctx)) return e;
+    return ctx->sampler->invert(ctx->den.get(), to_opts(opts), x, from_level, to_level, trace);
+    API_END
+}
+int dsh_invert(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t to_level, float* trace) {
+    return dsh_invert_from(ctx, opts, x, 0, to_level, trace);
 }
 
 int32_t dsh_diffusion_table(int32_t diffusion_steps, int32_t respacing, const char* name, double* out, int32_t cap) {
@@ -320,6 +348,7 @@ int32_t dsh_diffusion_table(int32_t diffusion_steps, int32_t respacing, const ch
     if (n == "betas") v = &tb.betas;
     else if (n == "alphas_cumprod") v = &tb.ac;
     else if (n == "alphas_cumprod_prev") v = &tb.ac_prev;
+    else if (n == "alphas_cumprod_next") v = &tb.ac_next;
     else if (n == "sqrt_recip_alphas_cumprod") v = &tb.c1;
     else if (n == "sqrt_recipm1_alphas_cumprod") v = &tb.c2;
     else if (n == "posterior_variance") v = &tb.post_var;
@@ -1033,6 +1062,53 @@ int dsh_op_philox_randn_rows_ragged_seeded(void* hip_stream, float* out, int32_t
                                                  reinterpret_cast<const int*>(ld), draw, channels, row_seeds_dev);
     DSH_HIP_CHECK(hipStreamSynchronize(s));          // the scratch arrays are released on return
     return rc;
+    API_END
+}
+
+// q_sample as an op: noise given, or (noise null) drawn in the pass with the addressing of dsh_op_philox_randn (row_keys_host null) /
+// dsh_op_philox_randn_rows[_ragged][_seeded]
+int dsh_op_q_sample(void* hip_stream, float* out, const float* x0, const float* noise, const float* a_dev, const float* s_dev, int32_t B,
+                    int32_t frames, int32_t channels, int32_t c_lo, int32_t c_hi, int32_t fixed_from, uint64_t seed, uint64_t offset,
+                    const uint64_t* row_keys_host, const uint64_t* row_seeds_dev, const int32_t* row_lens_host, uint64_t draw) {
+    API_BEGIN
+    DSH_REQUIRE(out && x0 && a_dev && s_dev && B > 0 && frames > 0 && channels > 0, "q_sample: invalid argument");
+    DSH_REQUIRE(c_lo >= 0 && c_hi <= channels, "q_sample: channel range outside [0, channels]");
+    DSH_REQUIRE(fixed_from >= -1 && fixed_from <= channels, "q_sample: fixed_from outside -1 .. channels");
+    DSH_REQUIRE(noise || row_keys_host || (!row_seeds_dev && !row_lens_host), "q_sample: row seeds and row lengths of a Philox draw need the row keys");
+    const size_t row_n = (size_t)frames * channels;
+    DSH_REQUIRE(noise || !row_keys_host || row_n % 4 == 0, "q_sample: row keys need frames * channels to be a multiple of 4");
+    if (row_lens_host)
+        for (int b = 0; b < B; ++b) {
+            DSH_REQUIRE(row_lens_host[b] >= 0 && row_lens_host[b] <= frames, "q_sample: a row length outside 0 .. frames");
+            DSH_REQUIRE(noise || ((int64_t)row_lens_host[b] * channels) % 4 == 0, "q_sample: length * channels must be a multiple of 4 for every row of a Philox draw");
+        }
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    OpScratch scratch;
+    void *kd = nullptr, *ld = nullptr;
+    if (!noise && row_keys_host) { if (int e = scratch.upload(&kd, row_keys_host, (size_t)B * sizeof(uint64_t))) return e; }
+    if (row_lens_host) { if (int e = scratch.upload(&ld, row_lens_host, (size_t)B * sizeof(int32_t))) return e; }
+    dsh::QSampleArgs a{};
+    a.out = out; a.x0 = x0; a.noise = noise; a.a = a_dev; a.s = s_dev; a.n = (size_t)B * row_n; a.frames = frames; a.channels = channels;
+    a.c_lo = c_lo; a.c_hi = c_hi; a.fixed_from = fixed_from;
+    a.seed = seed; a.offset = offset; a.row_keys = reinterpret_cast<const uint64_t*>(kd); a.row_quads = kd ? row_n / 4 : 1;
+    a.row_lens = reinterpret_cast<const int*>(ld); a.draw = draw; a.row_seeds = kd ? row_seeds_dev : nullptr;
+    const int rc = dsh::launch_q_sample(a, s);
+    if (kd || ld) DSH_HIP_CHECK(hipStreamSynchronize(s));          // the scratch arrays are released on return
+    return rc;
+    API_END
+}
+
+// keep mask of an edit (glue.edit_region): the host copies are validated here, the kernel reads the device copies
+int dsh_op_region_mask(void* hip_stream, const int32_t* frames_host, const int32_t* frames_dev, int32_t nf, const int32_t* cols_host,
+                       const int32_t* cols_dev, int32_t nc, int32_t B, int32_t T, int32_t C, uint8_t* keep) {
+    API_BEGIN
+    DSH_REQUIRE(B > 0 && T > 0 && C > 0 && nf >= 0 && nc >= 0 && keep, "region_mask: invalid argument");
+    DSH_REQUIRE((nf == 0 || (frames_host && frames_dev)) && (nc == 0 || (cols_host && cols_dev)), "region_mask: ranges need their host and their device copy");
+    for (int64_t i = 0; i < (int64_t)B * nf; ++i)
+        DSH_REQUIRE(frames_host[2 * i] >= 0 && frames_host[2 * i] <= frames_host[2 * i + 1] && frames_host[2 * i + 1] <= T, "region_mask: a frame range outside 0 <= lo <= hi <= T");
+    for (int i = 0; i < nc; ++i)
+        DSH_REQUIRE(cols_host[2 * i] >= 0 && cols_host[2 * i] <= cols_host[2 * i + 1] && cols_host[2 * i + 1] <= C, "region_mask: a column range outside 0 <= lo <= hi <= C");
+    return dsh::launch_region_mask(frames_dev, nf, cols_dev, nc, B, T, C, keep, reinterpret_cast<hipStream_t>(hip_stream));
     API_END
 }
 

@@ -263,6 +263,19 @@ int launch_zero_padded_frames(float* x, const int* lens, int B, int frames, int 
 int launch_philox_randn_rows(float* out, int rows, size_t n_row, uint64_t seed, uint64_t offset, const uint64_t* row_keys,
                              hipStream_t s, const int* row_lens = nullptr, uint64_t draw = 0, int channels = 0,
                              const uint64_t* row_seeds = nullptr);      // (device, nullable: row b's Philox key in place of `seed`)
+// q_sample (sampler_kernels.hip): out = a[b] x0 + s[b] n per element of row b; n = noise, or (noise null) the Philox draw the fields below
+// address exactly as launch_philox_randn (row_keys null: offset + global quad) / launch_philox_randn_rows do.  All pointers device.
+struct QSampleArgs {
+    float* out; const float* x0; const float* noise;
+    const float *a, *s;                    // [B] coefficient pairs
+    size_t n; int frames, channels;
+    int c_lo, c_hi, fixed_from;            // columns written (c_hi <= c_lo: all); columns >= fixed_from copy x0 (-1: none)
+    uint64_t seed, offset; const uint64_t* row_keys; size_t row_quads; const int* row_lens; uint64_t draw; const uint64_t* row_seeds;
+    int vec;                               // set by launch_q_sample: whole quads as float4 (no window, no fixed columns, no lengths, aligned)
+};
+int launch_q_sample(const QSampleArgs& a, hipStream_t s);
+// keep mask of an edit [B, T, C]: 0 inside any of row b's frame ranges frames[b, nf, 2] or any column range cols[nc, 2] (device), 1 elsewhere
+int launch_region_mask(const int* frames, int nf, const int* cols, int nc, int B, int T, int C, uint8_t* keep, hipStream_t s);
 // window hand-off of live chains on a slot table tails [S, L, C]: gt [R, T, C] <- (tails[slot_idx[r]] | 0), mask [R, T, C] <- (1 | 0) ...
 int launch_chain_handoff(const float* tails, int S, const int* slot_idx, int R, int T, int L, int C, float* gt, uint8_t* mask, hipStream_t s);
 // ... and tails[slot_idx[r]] <- the last L valid frames of x [R, T, C] (lens nullable: every row has T).  slot_idx / lens: device arrays.

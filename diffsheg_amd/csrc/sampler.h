@@ -8,13 +8,15 @@
 namespace dsh {
 
 struct DiffusionTables {
-    std::vector<double> betas, ac, ac_prev, c1, c2, post_var, post_logvar, coef1, coef2;
+    std::vector<double> betas, ac, ac_prev, ac_next, c1, c2, post_var, post_logvar, coef1, coef2;   // ac_next[k] = ac[k + 1], last entry 0
     std::vector<int> tmap;   // spaced index -> original timestep
 };
 void build_tables(const std::vector<double>& betas, DiffusionTables& t);
 std::vector<double> linear_betas(int n);
 int make_tables(int steps, int respacing, DiffusionTables& out, std::string& err);
 std::vector<int> jump_schedule(int respacing, int jump_length, int jump_n_sample);
+// the same walk from t_T = start_level (an edit restarts the RePaint schedule from its own level); 0: the built-in 15 / 0.6 * respacing
+std::vector<int> jump_schedule_from(int respacing, int jump_length, int jump_n_sample, int start_level);
 
 struct SamplerOpts {
     int kind = 0, diffusion_steps = 1000, respacing = 25, jump_length = 3, jump_n_sample = 5, overlap_len = 10,
@@ -23,11 +25,15 @@ struct SamplerOpts {
     int same_overlap_noisy = 0, clip_idx = 0;     // gaussian_diffusion.py:1040-1060: window index inside a chain
     float eta = 0.f;                              // DDIM eta (gaussian_diffusion.py:1011-1032)
 };
-enum StepKind { STEP_DDIM = 0, STEP_UNDO = 1, STEP_DDPM = 2 };
+// STEP_REVERSE: one step of the DDIM reverse ODE (ddim_reverse_sample, gaussian_diffusion.py:1068-1104): level k -> k + 1, no draw
+enum StepKind { STEP_DDIM = 0, STEP_UNDO = 1, STEP_DDPM = 2, STEP_REVERSE = 3 };
 struct SamplerStep { StepKind kind; int level; };
 
-int64_t sampler_num_draws(const SamplerOpts& o, bool masked, bool init_from_x);
-int64_t sampler_num_steps(const SamplerOpts& o, bool masked);
+// init: 0 x_T is drawn (draw 0), 1 x is given at the schedule's first level, 2 x holds x0 and is noised to that level with draw 0.
+// start_level K (DDIM, 1 .. respacing; 0: the whole schedule): the plain schedule is levels K-1 .. 0, the mask-present one
+// jump_schedule_from(K).
+int64_t sampler_num_draws(const SamplerOpts& o, bool masked, int init, int start_level = 0);
+int64_t sampler_num_steps(const SamplerOpts& o, bool masked, int start_level = 0);
 
 class Sampler {
   public:
@@ -45,8 +51,15 @@ class Sampler {
     // windows pinned at both ends (in-betweening / seam repair): the DDIM step's cross-fade also runs, mirrored, on the last
     // overlap_len frames (sampler_kernels.hip).  Sticky like the row keys; 0 = the reference's head-only fade.
     void set_tail_blend(int on) { tail_blend = on != 0; }
-    int run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_from_x, const float* gt, const uint8_t* mask,
+    // DDIM loops start at spaced level K - 1 instead of the top of the schedule (an edit of an existing motion: init 1 with x at that
+    // level, or init 2 with x = x0).  Sticky like the tail blend; 0 = the whole schedule.  Range-checked by run() (needs the respacing).
+    int set_start_level(int K);
+    // init: 0 / 1 / 2 as for sampler_num_draws
+    int run(DenoiserBase* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask,
             bool masked, const float* noise_stack, int64_t n_draws, float* trace);
+    // DDIM inversion: x (a clean motion at from_level 0, or a state at level from_level) is carried up the reverse ODE through levels
+    // from_level .. to_level - 1, in place; no draws, eta = 0 only, no mask.  trace [to_level - from_level, n] as in run().
+    int invert(DenoiserBase* den, const SamplerOpts& o, float* x, int from_level, int to_level, float* trace);
 
   private:
     // One set of the device buffers a chain works in: the noise scratch of a step's two draws, the per-step scalars an evaluation reads
@@ -106,6 +119,10 @@ class Sampler {
     uint64_t* row_keys = nullptr; int n_row_keys = 0, cap_row_keys = 0;
     uint64_t* row_seeds = nullptr; int n_row_seeds = 0, cap_row_seeds = 0;
     bool tail_blend = false;
+    int start_level = 0;
+    int run_schedule(DenoiserBase* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask, bool masked,
+                     const float* noise_stack, int64_t n_draws, float* trace, int start, int invert_to, int invert_from);
+    int init_x(Run& r);
     // --same_overlap_noisy: the noisy tail x[..., -L:, :] saved after every DDIM step, one slot per spaced level; persists
     // across sample() calls like the reference's self.saved_noisy_tail (the dict the next window receives IS this object)
     float* tails = nullptr; float* tail_tmp = nullptr; size_t tails_blc = 0; int tails_levels = 0;

@@ -18,7 +18,7 @@ namespace dsh {
 void build_tables(const std::vector<double>& betas, DiffusionTables& t) {
     const size_t n = betas.size();
     t.betas = betas;
-    t.ac.resize(n); t.ac_prev.resize(n); t.c1.resize(n); t.c2.resize(n); t.post_var.resize(n);
+    t.ac.resize(n); t.ac_prev.resize(n); t.ac_next.resize(n); t.c1.resize(n); t.c2.resize(n); t.post_var.resize(n);
     t.post_logvar.resize(n); t.coef1.resize(n); t.coef2.resize(n);
     double cp = 1.0;
     for (size_t i = 0; i < n; ++i) {
@@ -26,6 +26,7 @@ void build_tables(const std::vector<double>& betas, DiffusionTables& t) {
         cp *= (1.0 - betas[i]);
         t.ac[i] = cp;
     }
+    for (size_t i = 0; i < n; ++i) t.ac_next[i] = i + 1 < n ? t.ac[i + 1] : 0.0;      // alphas_cumprod_next (:347)
     for (size_t i = 0; i < n; ++i) {
         t.c1[i] = sqrt(1.0 / t.ac[i]);
         t.c2[i] = sqrt(1.0 / t.ac[i] - 1.0);
@@ -75,7 +76,10 @@ int make_tables(int steps, int respacing, DiffusionTables& out, std::string& err
 }
 
 std::vector<int> jump_schedule(int respacing, int jump_length, int jump_n_sample) {
-    const int t_T = respacing == 25 ? 15 : (int)(respacing * 0.6);
+    return jump_schedule_from(respacing, jump_length, jump_n_sample, 0);
+}
+std::vector<int> jump_schedule_from(int respacing, int jump_length, int jump_n_sample, int start_level) {
+    const int t_T = start_level > 0 ? start_level : respacing == 25 ? 15 : (int)(respacing * 0.6);
     std::vector<int> jumps(t_T > 0 ? t_T : 1, 0);
     if (jump_length > 0)
         for (int j = 0; j < t_T - jump_length; j += jump_length) jumps[j] = jump_n_sample - 1;
@@ -94,46 +98,61 @@ std::vector<int> jump_schedule(int respacing, int jump_length, int jump_n_sample
 }
 
 // ------------------------------------------------------------------------------------------------
-static int plan_steps(const SamplerOpts& o, bool masked, std::vector<SamplerStep>& steps, std::string& err) {
+// The schedule of a run.  start (> 0): the DDIM schedules begin at level start - 1.  invert_to (> 0): the reverse ODE, levels invert_from .. invert_to - 1.
+static int plan_steps(const SamplerOpts& o, bool masked, int start, int invert_to, std::vector<SamplerStep>& steps, std::string& err, int invert_from = 0) {
     steps.clear();
+    if (start != 0 || invert_to != 0) {
+        if (o.kind != 0) { err = "a start level / the reverse loop exist for the DDIM loops only"; return -1; }
+        if (start < 0 || start > o.respacing) { err = "start level outside 1 .. respacing"; return -1; }
+        if (invert_to < 0 || invert_to > o.respacing) { err = "inversion level outside 1 .. respacing"; return -1; }
+    }
+    if (invert_to > 0) {
+        if (masked || start != 0) { err = "the reverse loop takes no mask and no start level"; return -1; }
+        if (invert_from < 0 || invert_from >= invert_to) { err = "the reverse loop needs 0 <= from_level < to_level"; return -1; }
+        for (int k = invert_from; k < invert_to; ++k) steps.push_back({STEP_REVERSE, k});
+        return 0;
+    }
     if (o.kind == 1) {  // DDPM ancestral, full chain
         for (int t = o.diffusion_steps - 1; t >= 0; --t) steps.push_back({STEP_DDPM, t});
         return 0;
     }
     if (o.kind != 0) { err = "unknown sampler kind"; return -1; }
     if (masked && !o.no_repaint) {
-        const std::vector<int> times = o.no_resample ? jump_schedule(o.respacing, 1, 1)
-                                                     : jump_schedule(o.respacing, o.jump_length, o.jump_n_sample);
+        const std::vector<int> times = o.no_resample ? jump_schedule_from(o.respacing, 1, 1, start)
+                                                     : jump_schedule_from(o.respacing, o.jump_length, o.jump_n_sample, start);
         for (size_t i = 0; i + 1 < times.size(); ++i) {
             const int t_last = times[i], t_cur = times[i + 1];
             if (t_last < 0 || t_last >= o.respacing) { err = "jump schedule leaves the spaced range"; return -1; }
             steps.push_back({t_cur < t_last ? STEP_DDIM : STEP_UNDO, t_last});
         }
     } else {
-        for (int k = o.respacing - 1; k >= 0; --k) steps.push_back({STEP_DDIM, k});
+        for (int k = (start > 0 ? start : o.respacing) - 1; k >= 0; --k) steps.push_back({STEP_DDIM, k});
     }
     return 0;
 }
 
-int64_t sampler_num_draws(const SamplerOpts& o, bool masked, bool init_from_x) {
+int64_t sampler_num_draws(const SamplerOpts& o, bool masked, int init, int start_level) {
     std::vector<SamplerStep> steps; std::string err;
-    if (plan_steps(o, masked, steps, err)) { set_last_error(err); return -1; }
-    int64_t n = init_from_x ? 0 : 1;
+    if (init < 0 || init > 2) { set_last_error("unknown init mode"); return -1; }
+    if (init == 2 && o.kind != 0) { set_last_error("init mode 2 (x holds x0) exists for the DDIM loops only"); return -1; }
+    if (plan_steps(o, masked, start_level, 0, steps, err)) { set_last_error(err); return -1; }
+    int64_t n = init == 1 ? 0 : 1;                                             // x_T, or the q_sample noise of init 2
     const bool tail_gt = masked && o.same_overlap_noisy && o.clip_idx > 0;     // that branch draws no gt noise
     for (const auto& s : steps) n += (s.kind == STEP_DDIM) ? ((masked && !tail_gt) ? 2 : 1) : 1;
     return n;
 }
-int64_t sampler_num_steps(const SamplerOpts& o, bool masked) {
+int64_t sampler_num_steps(const SamplerOpts& o, bool masked, int start_level) {
     std::vector<SamplerStep> steps; std::string err;
-    if (plan_steps(o, masked, steps, err)) { set_last_error(err); return -1; }
+    if (plan_steps(o, masked, start_level, 0, steps, err)) { set_last_error(err); return -1; }
     return (int64_t)steps.size();
 }
 
 // One run()'s arguments, what is derived from them once, its chains and the loop's running state; the parts of run() share it by reference.
 enum LevelCache { CACHE_NONE, CACHE_INLINE, CACHE_PREFETCH, CACHE_SUBS };
 struct Sampler::Run {
-    DenoiserBase* den; const SamplerOpts& o; float* x; bool init_from_x; const float* gt; const uint8_t* mask; bool masked;
+    DenoiserBase* den; const SamplerOpts& o; float* x; int init; const float* gt; const uint8_t* mask; bool masked;
     const float* noise_stack; int64_t n_draws; float* trace;
+    int start, invert_from, invert_to;                   // start level of the DDIM schedules (0: the top); reverse loop over these levels (to 0: none)
     int B = 0; size_t n = 0, row_n = 0;                  // clips, values, values per clip
     int mod = 0, gcols = 0, w_lo = 0, w_hi = 0;          // modality, gesture columns, the active column window (0, 0: all)
     const int* len_d = nullptr;                          // ragged batch: per-clip frame counts (device)
@@ -187,6 +206,12 @@ int Sampler::set_row_keys(const uint64_t* keys_host, int n) {
     DSH_HIP_CHECK(hipMemcpyAsync(row_keys, keys_host, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     DSH_HIP_CHECK(hipStreamSynchronize(st));       // keys_host is pageable caller memory
     n_row_keys = n;
+    return 0;
+}
+
+int Sampler::set_start_level(int K) {
+    DSH_REQUIRE(K >= 0, "set_start_level: negative level");
+    start_level = K;
     return 0;
 }
 
@@ -266,9 +291,9 @@ int Sampler::prepare(Run& r) {
     DenoiserBase* den = r.den;
     const int B = r.B; const size_t n = r.n;
     std::string err;
-    if (plan_steps(o, r.masked, r.steps, err)) { set_last_error(err); return -1; }
-    const int64_t need = sampler_num_draws(o, r.masked, r.init_from_x);
-    if (o.noise_mode == 0) DSH_REQUIRE(r.noise_stack != nullptr && r.n_draws >= need, "noise stack shorter than the loop's draw count");
+    if (plan_steps(o, r.masked, r.start, r.invert_to, r.steps, err, r.invert_from)) { set_last_error(err); return -1; }
+    const int64_t need = r.invert_to > 0 ? 0 : sampler_num_draws(o, r.masked, r.init, r.start);
+    if (o.noise_mode == 0 && r.invert_to == 0) DSH_REQUIRE(r.noise_stack != nullptr && r.n_draws >= need, "noise stack shorter than the loop's draw count");
     // tables are cached per (steps, respacing)
     const int resp = o.kind == 1 ? 0 : o.respacing;
     if (tb_steps != o.diffusion_steps || tb_resp != resp) {
@@ -277,9 +302,10 @@ int Sampler::prepare(Run& r) {
     }
     if (int e = ensure(n, B)) return e;
     if (o.kind == 0 && o.eta != 0.f && o.noise_mode == 1 && cap_eta < n) { if (int e = grow_device_buffer(bufs[0].nz_eta, cap_eta, n, st)) return e; }
-    DSH_REQUIRE(n_row_keys == 0 || o.noise_mode != 1 || (n_row_keys == B && (n / B) % 4 == 0),
+    // (the reverse loop draws nothing: whatever keys an earlier call left in the context do not concern it)
+    DSH_REQUIRE(r.invert_to > 0 || n_row_keys == 0 || o.noise_mode != 1 || (n_row_keys == B && (n / B) % 4 == 0),
                 "row keys were set for a different batch size (or frames*channels is not a multiple of 4)");
-    r.per_row = o.noise_mode == 1 && n_row_keys == B;
+    r.per_row = r.invert_to == 0 && o.noise_mode == 1 && n_row_keys == B;
     r.seeds_d = (r.per_row && n_row_seeds == B) ? row_seeds : nullptr;      // (set_row_seeds: always the row keys' count)
     r.quads = r.per_row ? (n / B) / 4 : (n + 3) / 4;
     // --same_overlap_noisy state
@@ -409,7 +435,7 @@ int Sampler::noise_for(const Run& r, int64_t idx, const Chain& c, float* scratch
 Sampler::StepConsts Sampler::step_consts(Run& r, const SamplerStep& sp) {
     const int k = sp.level;
     StepConsts sc{};
-    sc.kind = sp.kind; sc.k = k; sc.eval_idx = -1; sc.idx2 = -1;
+    sc.kind = sp.kind; sc.k = k; sc.eval_idx = -1; sc.idx = sc.idx2 = -1;
     if (sp.kind == STEP_UNDO) {
         const float beta = (float)tb.betas[k];
         sc.undo_a = sqrtf(1.0f - beta); sc.undo_b = sqrtf(beta);
@@ -418,6 +444,14 @@ Sampler::StepConsts Sampler::step_consts(Run& r, const SamplerStep& sp) {
     }
     sc.eval_idx = r.n_eval++;
     sc.t = (int64_t)tb.tmap[k]; sc.c1 = (float)tb.c1[k]; sc.c2 = (float)tb.c2[k];
+    if (sp.kind == STEP_REVERSE) {
+        // ddim_reverse_sample (:1092-1102): x0 and eps as in the forward step, then x <- sqrt(ab_next) x0 + sqrt(1 - ab_next) eps — the
+        // forward update with ab_next in the place of ab_prev, and no draw; sqrt taken in fp32 on the gathered fp32 value like the reference's th.sqrt
+        const float abn = (float)tb.ac_next[k];
+        sc.sqrt_ab_prev = sqrtf(abn);
+        sc.sqrt_1m_ab_prev = sc.coef_eps = sqrtf(1.0f - abn);
+        return sc;
+    }
     sc.idx = r.next_draw();                                         // DDIM: randn_like of the step, times sigma (= 0 at eta = 0: drawn index, unused values)
     if (sp.kind == STEP_DDPM) {
         sc.coef1 = (float)tb.coef1[k]; sc.coef2 = (float)tb.coef2[k];
@@ -497,7 +531,7 @@ int Sampler::ddim_update(Run& r, const Chain& c, const StepConsts& sc) {
     a.x = r.x + c.off; a.eps = eps + c.off; a.x0_out = nullptr; a.c1 = sc.c1; a.c2 = sc.c2;
     a.sqrt_ab_prev = sc.sqrt_ab_prev; a.sqrt_1m_ab_prev = sc.sqrt_1m_ab_prev;
     a.coef_eps = sc.coef_eps; a.sigma = sc.sigma; a.noise1 = nullptr;
-    if (o.eta != 0.f) {
+    if (o.eta != 0.f && sc.kind == STEP_DDIM) {
         // (nz1 is the scratch of the RePaint draw below: a second buffer only exists for eta != 0)
         const float* z1 = nullptr;
         if (int e = noise_for(r, sc.idx, c, c.nz_eta, &z1)) return e;
@@ -533,24 +567,41 @@ int Sampler::ddpm_update(Run& r, const Chain& c, const StepConsts& sc) {
 
 // one chain's share of a step: its columns of its rows, on its stream (every chain draws the same values: the noise depends on the position only)
 int Sampler::update(Run& r, const Chain& c, const StepConsts& sc) {
-    if (sc.kind == STEP_DDIM) return ddim_update(r, c, sc);
+    if (sc.kind == STEP_DDIM || sc.kind == STEP_REVERSE) return ddim_update(r, c, sc);      // (reverse: run_schedule() admits no mask, eta, tails)
     if (sc.kind == STEP_DDPM) return ddpm_update(r, c, sc);
     const float* z;
     if (int e = noise_for(r, sc.idx, c, c.nz1, &z)) return e;
     return launch_undo_step(r.x + c.off, z, sc.undo_a, sc.undo_b, c.cnt, c.s, channels, c.c_lo, c.c_hi);
 }
 
+// x at the schedule's first level.  init 0: draw 0 is x_T.  init 2: x holds x0; draw 0 — the draw x_T would have taken, through noise_for(), so
+// row keys, row seeds and ragged lengths address it alike — is the q_sample noise, and every chain noises its rows and columns in place
+// (coefficients: fp64 sqrt of the table rounded to fp32, like the reference's sqrt_alphas_cumprod tables; they travel in the chain's c1 / c2
+// rows, which the first evaluation refills behind this launch on the same stream).
+int Sampler::init_x(Run& r) {
+    if (r.init == 1) return 0;
+    const int64_t idx = r.next_draw();
+    for (const Chain& c : r.chains) {
+        const float* z;
+        if (int e = noise_for(r, idx, c, r.init == 2 ? c.nz1 : r.x, &z)) return e;
+        if (r.init == 0) {
+            if (z != r.x + c.off) DSH_HIP_CHECK(hipMemcpyAsync(r.x + c.off, z, c.cnt * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+            continue;
+        }
+        const int k = r.steps.front().level;
+        if (int e = launch_fill_step(c.t, c.c1, c.c2, c.lvl, (int64_t)tb.tmap[k], (float)sqrt(tb.ac[k]), (float)sqrt(1.0 - tb.ac[k]), (int64_t)k, c.nb, c.s)) return e;
+        QSampleArgs a{};
+        a.out = r.x + c.off; a.x0 = r.x + c.off; a.noise = z; a.a = c.c1; a.s = c.c2;
+        a.n = c.cnt; a.frames = r.den->frames; a.channels = channels; a.c_lo = c.c_lo; a.c_hi = c.c_hi; a.fixed_from = -1;
+        if (int e = launch_q_sample(a, c.s)) return e;
+    }
+    return 0;
+}
+
 // Everything between the fork of make_chains() and the joins of finish(): any error leaves through `return`, and run() passes the result
 // to finish() unconditionally.
 int Sampler::loop(Run& r, const LoopPlan& p) {
-    if (!r.init_from_x) {
-        const int64_t idx = r.next_draw();
-        for (const Chain& c : r.chains) {
-            const float* z;
-            if (int e = noise_for(r, idx, c, r.x, &z)) return e;
-            if (z != r.x + c.off) DSH_HIP_CHECK(hipMemcpyAsync(r.x + c.off, z, c.cnt * sizeof(float), hipMemcpyDeviceToDevice, c.s));
-        }
-    }
+    if (int e = init_x(r)) return e;
     if (int e = setup(r, p)) return e;
     for (const SamplerStep& sp : r.steps) {
         const StepConsts sc = step_consts(r, sp);
@@ -602,16 +653,32 @@ int Sampler::finish(Run& r, int rc) {
     return rc;
 }
 
-int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_from_x, const float* gt,
+int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, int init, const float* gt,
                  const uint8_t* mask, bool masked, const float* noise_stack, int64_t n_draws, float* trace) {
+    return run_schedule(den, o, x, init, gt, mask, masked, noise_stack, n_draws, trace, start_level, 0, 0);
+}
+
+int Sampler::invert(DenoiserBase* den, const SamplerOpts& o, float* x, int from_level, int to_level, float* trace) {
+    DSH_REQUIRE(to_level >= 1 && from_level >= 0 && from_level < to_level, "invert: needs 0 <= from_level < to_level");
+    DSH_REQUIRE(o.kind == 0 && o.eta == 0.f, "invert: the reverse ODE exists for the DDIM loops at eta = 0 only");
+    DSH_REQUIRE(!o.same_overlap_noisy && !tail_blend && start_level == 0, "invert: same_overlap_noisy, the tail blend and a start level do not apply to the reverse loop");
+    return run_schedule(den, o, x, 1, nullptr, nullptr, false, nullptr, 0, trace, 0, to_level, from_level);
+}
+
+int Sampler::run_schedule(DenoiserBase* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask, bool masked,
+                          const float* noise_stack, int64_t n_draws, float* trace, int start, int invert_to, int invert_from) {
     DSH_REQUIRE(den && den->batch > 0, "set_condition() must precede sample()");
+    DSH_REQUIRE(init >= 0 && init <= 2, "unknown init mode");
+    DSH_REQUIRE(init != 2 || o.kind == 0, "init mode 2 (x holds x0) exists for the DDIM loops only");
+    DSH_REQUIRE(start == 0 || (o.kind == 0 && !o.same_overlap_noisy && !tail_blend),
+                "a start level exists for the DDIM loops only, without same_overlap_noisy and the tail blend");
     DSH_REQUIRE(x != nullptr, "null sample buffer");
     DSH_REQUIRE(!masked || (gt && mask), "masked sampling needs gt and mask");
     DSH_REQUIRE(o.noise_mode == 0 || o.noise_mode == 1, "unknown noise mode");
     DSH_REQUIRE(!(masked && o.kind == 1), "mask-present DDPM (p_sample_loop_progressive_harmonize) is not supported");
     DSH_REQUIRE(!(tail_blend && o.same_overlap_noisy), "tail_blend with same_overlap_noisy: the saved noisy tails describe a window chain, not a window pinned at both ends");
     DSH_REQUIRE(!tail_blend || (o.overlap_len >= 0 && 2 * (int64_t)o.overlap_len <= den->frames), "tail_blend: the head and the tail fade overlap (2 * overlap_len > frames)");
-    Run r{den, o, x, init_from_x, gt, mask, masked, noise_stack, n_draws, trace};
+    Run r{den, o, x, init, gt, mask, masked, noise_stack, n_draws, trace, start, invert_from, invert_to};
     const int B = r.B = den->batch;
     // One modality alone (denoiser.h, set_modality): the loop advances the active encoder's column window [w_lo, w_hi) only — every step launch
     // of every regime takes it — and its result holds 0 (expression mode) or the given track (gesture mode) in the other columns.  Noise
@@ -625,7 +692,7 @@ int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, bool init_fr
     r.len_d = den->lengths_dev();
     // (both address the last overlap_len frames of the PADDED window, which a short clip does not reach)
     DSH_REQUIRE(!len_h || (!o.same_overlap_noisy && !tail_blend), "per-clip lengths cannot be combined with same_overlap_noisy or the tail blend");
-    if (len_h && o.noise_mode == 1 && n_row_keys == B)
+    if (len_h && o.noise_mode == 1 && n_row_keys == B && invert_to == 0)
         for (int b = 0; b < B; ++b) DSH_REQUIRE(((int64_t)len_h[b] * channels) % 4 == 0, "row keys on a ragged batch: length * channels must be a multiple of 4 for every clip");
     // loop_begin() marks the batch as deliberately unsplit; the mark is taken back on EVERY way out of this function (an argument error or a
     // failed launch below must not leave the context answering later evaluations as if a loop were still running)

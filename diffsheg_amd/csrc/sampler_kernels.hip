@@ -5,6 +5,7 @@
 //               (+ RePaint blend)                                     :614-622, :993-1032, :1034-1056
 //   undo_step   x <- sqrt(1-beta) x + sqrt(beta) n                   :464-473
 //   ddpm_step   mean = coef1 x0 + coef2 x;  x <- mean + sigma n      :598-600, :747-773
+//   q_sample    x <- sqrt(ab) x0 + sqrt(1-ab) n (n given, or drawn in the pass)  :434-462
 //
 // Every product / sum is an individually rounded fp32 op (rn_mul / rn_add / rn_sub of dsh_common.h: compiled with contraction off, so never fused into an FMA),
 // in the reference's operation order, so the update itself is bit-identical to the aten sequence
@@ -211,39 +212,45 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint
 // clip draws from when it is sampled alone at that length.  (Padded positions run on into the next draw's counters; nothing reads them.)
 // row_seeds != null (with row_keys): row b uses the Philox key row_seeds[b] in place of `seed`; counter and row key as above — rows of one
 // batch may then stand at different windows of their chains (key = hash(base seed, window index), live sessions batched together).
+// the four N(0,1) values of quad `qd` of a draw (addressing above): shared by the stand-alone draw and the fused q_sample pass
+__device__ __forceinline__ void philox_quad(size_t qd, uint64_t seed, uint64_t offset, const uint64_t* __restrict__ row_keys, size_t row_quads,
+                                            const int* __restrict__ row_lens, uint64_t draw, int channels,
+                                            const uint64_t* __restrict__ row_seeds, float (&z)[4]) {
+    uint64_t ctr = offset + qd, rk = 0;
+    uint64_t key = seed;
+    if (row_keys) {
+        const size_t b = qd / row_quads;
+        if (row_seeds) key = row_seeds[b];
+        ctr = (row_lens ? draw * ((uint64_t)row_lens[b] * (uint64_t)channels / 4) : offset) + (qd - b * row_quads);
+        rk = row_keys[b];
+    }
+    uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)rk, (uint32_t)(rk >> 32)};
+    uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0,1)
+        const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+        const float r = sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincosf(6.283185307179586f * u2, &sn, &cs);
+        z[2 * h] = r * cs;
+        z[2 * h + 1] = r * sn;
+    }
+}
 __global__ void philox_randn_kernel(float* out, size_t n, uint64_t seed, uint64_t offset, const uint64_t* __restrict__ row_keys,
                                     size_t row_quads, const int* __restrict__ row_lens, uint64_t draw, int channels,
                                     const uint64_t* __restrict__ row_seeds) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const size_t nquad = (n + 3) / 4;
     for (size_t qd = (size_t)blockIdx.x * blockDim.x + threadIdx.x; qd < nquad; qd += stride) {
-        uint64_t ctr = offset + qd, rk = 0;
-        uint64_t key = seed;
-        if (row_keys) {
-            const size_t b = qd / row_quads;
-            if (row_seeds) key = row_seeds[b];
-            ctr = (row_lens ? draw * ((uint64_t)row_lens[b] * (uint64_t)channels / 4) : offset) + (qd - b * row_quads);
-            rk = row_keys[b];
-        }
-        uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)rk, (uint32_t)(rk >> 32)};
-        uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            philox_round(c, k0, k1);
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
         float z[4];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0,1)
-            const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-            const float r = sqrtf(-2.0f * logf(u1));
-            float sn, cs;
-            sincosf(6.283185307179586f * u2, &sn, &cs);
-            z[2 * h] = r * cs;
-            z[2 * h + 1] = r * sn;
-        }
+        philox_quad(qd, seed, offset, row_keys, row_quads, row_lens, draw, channels, row_seeds, z);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const size_t i = qd * 4 + j;
@@ -263,6 +270,92 @@ int launch_philox_randn_rows(float* out, int rows, size_t n_row, uint64_t seed, 
     DSH_REQUIRE(!row_lens || channels > 0, "philox_randn_rows: per-row lengths need the channel count");
     const size_t n = (size_t)rows * n_row;
     hipLaunchKernelGGL(philox_randn_kernel, dim3(grid_for(n / 4)), dim3(256), 0, s, out, n, seed, offset, row_keys, n_row / 4, row_lens, draw, channels, row_seeds);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- q_sample: out = a_b x0 + s_b n, one coefficient pair per batch row (gaussian_diffusion.py:434-462) ----
+// n is the caller's (a.noise) or drawn here, quad by quad, with the addressing of philox_randn_kernel: one pass, no noise buffer.  Columns
+// outside [c_lo, c_hi) (c_hi > c_lo) are not written; columns >= fixed_from (fixed_from >= 0) are copied from x0 (fix_head_var, :443-456:
+// coefficient pair 1 / 0 there); ragged rows (row_lens, with the row keys) write 0 to their padded frames.  out may be x0 (every element is
+// read before it is written, by the thread that writes it).
+__global__ void q_sample_kernel(QSampleArgs a) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t nquad = (a.n + 3) / 4, row_n = (size_t)a.frames * a.channels;
+    const bool ranged = a.c_hi > a.c_lo;
+    for (size_t qd = (size_t)blockIdx.x * blockDim.x + threadIdx.x; qd < nquad; qd += stride) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (!a.noise) philox_quad(qd, a.seed, a.offset, a.row_keys, a.row_quads, a.row_lens, a.draw, a.channels, a.row_seeds, z);
+        if (a.vec) {
+            // (launch_q_sample: every quad lies inside one row, all columns are written alike, the pointers are 16-byte aligned)
+            const size_t b = qd * 4 / row_n;
+            const float ca = a.a[b], cs = a.s[b];
+            const float4 x0 = *reinterpret_cast<const float4*>(a.x0 + qd * 4);
+            if (a.noise) { const float4 n = *reinterpret_cast<const float4*>(a.noise + qd * 4); z[0] = n.x; z[1] = n.y; z[2] = n.z; z[3] = n.w; }
+            float4 o;
+            o.x = rn_add(rn_mul(ca, x0.x), rn_mul(cs, z[0])); o.y = rn_add(rn_mul(ca, x0.y), rn_mul(cs, z[1]));
+            o.z = rn_add(rn_mul(ca, x0.z), rn_mul(cs, z[2])); o.w = rn_add(rn_mul(ca, x0.w), rn_mul(cs, z[3]));
+            *reinterpret_cast<float4*>(a.out + qd * 4) = o;
+            continue;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const size_t i = qd * 4 + j;
+            if (i >= a.n) break;
+            const size_t b = i / row_n, in_row = i - b * row_n;
+            const int cc = (int)(in_row % (size_t)a.channels);
+            if (ranged && (cc < a.c_lo || cc >= a.c_hi)) continue;
+            if (a.row_lens && in_row / (size_t)a.channels >= (size_t)a.row_lens[b]) { a.out[i] = 0.f; continue; }
+            const float x0 = a.x0[i];
+            if (a.fixed_from >= 0 && cc >= a.fixed_from) { a.out[i] = x0; continue; }
+            const float nz = a.noise ? a.noise[i] : z[j];
+            a.out[i] = rn_add(rn_mul(a.a[b], x0), rn_mul(a.s[b], nz));
+        }
+    }
+}
+int launch_q_sample(const QSampleArgs& a, hipStream_t s) {
+    DSH_REQUIRE(a.out && a.x0 && a.a && a.s && a.frames > 0 && a.channels > 0, "q_sample: invalid argument");
+    DSH_REQUIRE(a.n % ((size_t)a.frames * a.channels) == 0, "q_sample: the element count is not a whole number of rows");
+    DSH_REQUIRE(a.c_lo >= 0 && a.c_hi <= a.channels, "q_sample: channel range outside [0, channels]");
+    DSH_REQUIRE(a.noise || !a.row_keys || (a.row_quads > 0 && a.row_quads * 4 == (size_t)a.frames * a.channels), "q_sample: row keys need frames * channels to be a multiple of 4");
+    DSH_REQUIRE(!a.row_lens || a.noise || a.row_keys, "q_sample: per-row lengths of a Philox draw need the row keys");
+    if (a.n == 0) return 0;
+    QSampleArgs v = a;
+    auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    v.vec = a.c_hi <= a.c_lo && a.fixed_from < 0 && !a.row_lens && ((size_t)a.frames * a.channels) % 4 == 0 && aligned(a.out) && aligned(a.x0) &&
+            (!a.noise || aligned(a.noise)) ? 1 : 0;
+    hipLaunchKernelGGL(q_sample_kernel, dim3(grid_for((a.n + 3) / 4)), dim3(256), 0, s, v);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- keep mask of an edit: keep[b, t, c] = 0 where frame t lies in one of row b's nf frame ranges or column c in one of the nc column
+// ranges, 1 elsewhere.  frames [B, nf, 2] / cols [nc, 2] (device int32, half-open).  The host validates the ranges before the launch; a
+// range outside [0, T] / [0, C] or with lo > hi is skipped all the same.
+__global__ void region_mask_kernel(const int* __restrict__ frames, int nf, const int* __restrict__ cols, int nc, size_t n, int T, int C,
+                                   uint8_t* __restrict__ keep) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x, row_n = (size_t)T * C;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const size_t b = i / row_n, in_row = i - b * row_n;
+        const int t = (int)(in_row / C), c = (int)(in_row - (size_t)t * C);
+        bool edit = false;
+        for (int j = 0; j < nf; ++j) {
+            const int lo = frames[(b * nf + j) * 2], hi = frames[(b * nf + j) * 2 + 1];
+            if (lo >= 0 && hi <= T && lo <= hi && t >= lo && t < hi) edit = true;
+        }
+        for (int j = 0; j < nc; ++j) {
+            const int lo = cols[2 * j], hi = cols[2 * j + 1];
+            if (lo >= 0 && hi <= C && lo <= hi && c >= lo && c < hi) edit = true;
+        }
+        keep[i] = edit ? 0 : 1;
+    }
+}
+int launch_region_mask(const int* frames, int nf, const int* cols, int nc, int B, int T, int C, uint8_t* keep, hipStream_t s) {
+    DSH_REQUIRE(B >= 0 && T > 0 && C > 0 && nf >= 0 && nc >= 0, "region_mask: invalid argument");
+    if (B == 0) return 0;
+    DSH_REQUIRE(keep && (nf == 0 || frames) && (nc == 0 || cols), "region_mask: null pointer");
+    const size_t n = (size_t)B * T * C;
+    hipLaunchKernelGGL(region_mask_kernel, dim3(grid_for(n)), dim3(256), 0, s, frames, nf, cols, nc, n, T, C, keep);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }

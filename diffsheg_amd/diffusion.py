@@ -24,12 +24,17 @@ Differences a caller can observe, all loud:
   * ``model_kwargs['modality']`` (``"expression"`` / ``"gesture"``, the latter with ``model_kwargs['expression']`` = the given track) samples
     one encoder's channels alone (``UniDiffuser.set_condition(modality=)``): the other columns of the result are 0 / the given track;
   * ``ddim_sample_loop(..., tail_blend=True)`` mirrors the ``addBlend`` cross-fade onto the last ``overlap_len`` frames, for a mask
-    that pins both ends of a window (``DDPMTrainer.sample_inbetween``, seam repair); off by default.
+    that pins both ends of a window (``DDPMTrainer.sample_inbetween``, seam repair); off by default;
+  * editing an existing motion: ``q_sample`` (gaussian_diffusion.py:417-462) runs on the device, from given noise or the Philox streams;
+    ``ddim_sample_loop(..., start_level=K)`` starts at spaced level ``K - 1`` from ``noise=`` (x at that level) or ``x_start=`` (a clean
+    motion, noised in the loop with draw 0); ``ddim_reverse_sample`` / ``ddim_reverse_sample_loop`` are the DDIM reverse ODE (:1068-1104).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import enum
+import numbers
 from typing import List, Optional
 
 import numpy as np
@@ -38,7 +43,7 @@ import torch
 from . import _lib
 from .model import UniDiffuser, normalize_guidance_scale, normalize_lengths, normalize_modality
 
-_TABLES = ["betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_recip_alphas_cumprod",
+_TABLES = ["betas", "alphas_cumprod", "alphas_cumprod_prev", "alphas_cumprod_next", "sqrt_recip_alphas_cumprod",
            "sqrt_recipm1_alphas_cumprod", "posterior_variance", "posterior_log_variance_clipped",
            "posterior_mean_coef1", "posterior_mean_coef2"]
 
@@ -125,18 +130,65 @@ class GaussianDiffusion:
         self.timestep_map = list(range(self.num_timesteps))
 
     # ---- helpers --------------------------------------------------------------------------
-    def _opts(self, kind: int, clip_denoised: bool, noise_mode: int, seed: int, clip_idx: int = 0, eta: float = 0.0) -> _lib.SamplerOptsC:
+    def _opts(self, kind: int, clip_denoised: bool, noise_mode: int, seed: int, clip_idx: int = 0, eta: float = 0.0,
+              add_blend=None) -> _lib.SamplerOptsC:
         o = self.opt
+        if add_blend is None:
+            add_blend = getattr(o, "addBlend", getattr(o, "add_blend", True))
         return _lib.SamplerOptsC(kind, self.original_num_steps, max(self._respacing, 1),
                                  int(getattr(o, "jump_length", 3)), int(getattr(o, "jump_n_sample", 5)),
-                                 int(getattr(o, "overlap_len", 0)), int(bool(getattr(o, "addBlend", getattr(o, "add_blend", True)))),
+                                 int(getattr(o, "overlap_len", 0)), int(bool(add_blend)),
                                  int(bool(getattr(o, "no_resample", False))), int(bool(getattr(o, "no_repaint", False))),
                                  int(bool(clip_denoised)), noise_mode, seed & 0xFFFFFFFFFFFFFFFF,
                                  int(bool(getattr(o, "same_overlap_noisy", False))), int(clip_idx), float(eta))
 
+    def _guidance(self, model, cond_scale, B: int):
+        """Guidance scale of one call (transformer.py:537, :586): the keyword wins over opt.cond_scale; without classifier-free weights the
+        reference never reads opt.cond_scale, and an explicit scale other than 1 is an error.  None: the model's own setting stays."""
+        gs = normalize_guidance_scale(cond_scale)
+        if gs is None:
+            gs = normalize_guidance_scale(getattr(self.opt, "cond_scale", None))
+            if not model.cfg.classifier_free:
+                gs = None
+        elif not model.cfg.classifier_free:
+            if any(v != 1.0 for v in gs):
+                raise ValueError(f"cond_scale={list(gs)}: the weights are not classifier-free (no null_cond_emb), only 1 is possible")
+            gs = None
+        if gs is not None and len(gs) not in (1, B):
+            raise ValueError(f"cond_scale needs one value or one per batch row ({B}), got {len(gs)}")
+        return gs
+
+    @staticmethod
+    def _condition(model, model_kwargs, shape, lens, son: bool) -> None:
+        """One modality alone (model_kwargs['modality'] / ['expression'], UniDiffuser.set_condition) is refused like the rest, before
+        conditioning; then the context is conditioned (if it is not already) and the sample shape checked against it."""
+        B, T, Cc = shape
+        modality, expression = model_kwargs.get("modality", "both"), model_kwargs.get("expression")
+        normalize_modality(modality, expression, B, T, model.cfg.expression_dim, model.cfg.unidiffuser, son)
+        model._maybe_set_condition(model_kwargs["audio_emb"], model_kwargs["person_id"], model_kwargs.get("add_cond"), lens, modality, expression)
+        if (B, T) != (model.batch, model.frames) or Cc != model.cfg.net_dim_pose:
+            raise ValueError(f"shape {tuple(shape)} does not match the conditioning")
+
+    @staticmethod
+    @contextlib.contextmanager
+    def _native(model, gs):
+        """The native calls of one loop: on the model's device and stream, under the call's guidance scale (sticky in the context, like the
+        row keys: the model's own setting comes back afterwards)."""
+        prev_gs = model.guidance_scale
+        set_gs = gs is not None and gs != prev_gs
+        if set_gs:
+            model.set_guidance_scale(gs)
+        cur = model._enter()
+        try:
+            yield
+        finally:
+            model._exit(cur)
+            if set_gs:
+                model.set_guidance_scale(prev_gs)
+
     def _run(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0,
              noise_source=None, seed=None, return_trace=False, row_keys=None, cond_scale=None, tail_blend=False,
-             row_seeds=None):
+             row_seeds=None, start_level=None, x_start=None, add_blend=None):
         if not isinstance(model, UniDiffuser):
             raise TypeError("model must be a diffsheg_amd.model.UniDiffuser (no generic-callable / CPU fallback)")
         if denoised_fn is not None or cond_fn is not None:
@@ -163,23 +215,28 @@ class GaussianDiffusion:
         if tail_blend and son:
             raise NotImplementedError("tail_blend with same_overlap_noisy: the saved noisy tails describe a window chain, not a window "
                                       "pinned at both ends")
+        # restart from a level (an edit of an existing motion): DDIM loops only, x enters at spaced level K - 1
+        K = 0
+        if start_level is not None or x_start is not None:
+            if kind != 0:
+                raise TypeError("start_level / x_start are arguments of the DDIM loops only")
+            if noise is not None and x_start is not None:
+                raise ValueError("give noise= (x at level start_level - 1) or x_start= (a clean motion), not both")
+            if start_level is not None:
+                K = int(start_level)
+                if not 1 <= K <= self._respacing:
+                    raise ValueError(f"start_level must be in 1 .. {self._respacing}, got {start_level}")
+                if noise is None and x_start is None:
+                    raise ValueError("start_level needs noise= (x at level start_level - 1) or x_start= (a clean motion)")
+                if son:
+                    raise NotImplementedError("start_level with same_overlap_noisy: the saved noisy tails describe whole schedules")
+                if tail_blend:
+                    raise NotImplementedError("start_level with tail_blend is not built")
         clip_idx = int(y.get("clip_idx", 0)) if son else 0
         B, T, Cc = (int(s) for s in shape)
         if tail_blend and 2 * int(getattr(self.opt, "overlap_len", 0)) > T:
             raise ValueError(f"tail_blend: the head and the tail fade overlap (2 * overlap_len = {2 * int(self.opt.overlap_len)} > {T} frames)")
-        # guidance scale (transformer.py:537, :586): the keyword wins over opt.cond_scale; without classifier-free weights the
-        # reference never reads opt.cond_scale, and an explicit scale other than 1 is an error
-        gs = normalize_guidance_scale(cond_scale)
-        if gs is None:
-            gs = normalize_guidance_scale(getattr(self.opt, "cond_scale", None))
-            if not model.cfg.classifier_free:
-                gs = None
-        elif not model.cfg.classifier_free:
-            if any(v != 1.0 for v in gs):
-                raise ValueError(f"cond_scale={list(gs)}: the weights are not classifier-free (no null_cond_emb), only 1 is possible")
-            gs = None
-        if gs is not None and len(gs) not in (1, B):
-            raise ValueError(f"cond_scale needs one value or one per batch row ({B}), got {len(gs)}")
+        gs = self._guidance(model, cond_scale, B)
         dev = model.device
         # clips of different lengths in one padded batch (model_kwargs['length'] with an entry < T): both options below address the last
         # overlap_len frames of the PADDED window, which a short clip does not reach — refused before anything is conditioned
@@ -188,12 +245,7 @@ class GaussianDiffusion:
             raise NotImplementedError("per-clip lengths cannot be combined with same_overlap_noisy or tail_blend")
         if lens is not None and row_keys is not None and noise_source is None and any((v * Cc) % 4 for v in lens):
             raise ValueError("row_keys on a ragged batch: length * channels must be a multiple of 4 for every clip")
-        # one modality alone (model_kwargs['modality'] / ['expression'], UniDiffuser.set_condition): refused like the rest, before conditioning
-        modality, expression = model_kwargs.get("modality", "both"), model_kwargs.get("expression")
-        normalize_modality(modality, expression, B, T, model.cfg.expression_dim, model.cfg.unidiffuser, son)
-        model._maybe_set_condition(model_kwargs["audio_emb"], model_kwargs["person_id"], model_kwargs.get("add_cond"), lens, modality, expression)
-        if (B, T) != (model.batch, model.frames) or Cc != model.cfg.net_dim_pose:
-            raise ValueError(f"shape {tuple(shape)} does not match the conditioning")
+        self._condition(model, model_kwargs, (B, T, Cc), lens, son)
         gt = mask = None
         masked = False
         if "outpainting_mask" in y:
@@ -212,15 +264,18 @@ class GaussianDiffusion:
                 except RuntimeError as e:
                     raise ValueError(f"outpainting_mask {tuple(y['outpainting_mask'].shape)} / gt {tuple(y['gt'].shape)} "
                                      f"do not broadcast to the sample shape {(B, T, Cc)}") from e
-        init = noise is not None
-        x = noise.to(device=dev, dtype=torch.float32).contiguous().clone() if init else torch.empty(B, T, Cc, device=dev)
+        init = 2 if x_start is not None else int(noise is not None)      # dsh_sample: 0 x_T is drawn, 1 x is given, 2 x holds x0
+        given = x_start if x_start is not None else noise
+        if given is not None and tuple(given.shape) != (B, T, Cc):
+            raise ValueError(f"{'x_start' if init == 2 else 'noise'} {tuple(given.shape)} does not match the sample shape {(B, T, Cc)}")
+        x = given.to(device=dev, dtype=torch.float32).contiguous().clone() if init else torch.empty(B, T, Cc, device=dev)
         mode = 0 if noise_source is not None else 1
         if seed is None:
             seed = int(torch.initial_seed()) + GaussianDiffusion._calls
             GaussianDiffusion._calls += 1
-        opts = self._opts(kind, clip_denoised, mode, int(seed), clip_idx, eta)
+        opts = self._opts(kind, clip_denoised, mode, int(seed), clip_idx, eta, add_blend)
         lib = _lib.lib()
-        n_draws = _lib.check(lib.dsh_sample_num_draws(C.byref(opts), int(masked), int(init)), "dsh_sample_num_draws")
+        n_draws = _lib.check(lib.dsh_sample_num_draws_from(C.byref(opts), int(masked), init, K), "dsh_sample_num_draws_from")
         stack = None
         if noise_source is not None:
             stack = torch.empty(n_draws, B * T * Cc, device=dev)
@@ -228,7 +283,7 @@ class GaussianDiffusion:
                 stack[i].copy_(noise_source.randn((B, T, Cc)).reshape(-1), non_blocking=False)
         trace = None
         if return_trace:
-            n_steps = _lib.check(lib.dsh_sample_num_steps(C.byref(opts), int(masked)), "dsh_sample_num_steps")
+            n_steps = _lib.check(lib.dsh_sample_num_steps_from(C.byref(opts), int(masked), init, K), "dsh_sample_num_steps_from")
             trace = torch.empty(n_steps, B, T, Cc, device=dev)
         # Philox noise: optional per-row generator keys (a chain's global id), see dsh_sample_set_row_keys
         if row_keys is not None and len(row_keys) != B:
@@ -239,17 +294,14 @@ class GaussianDiffusion:
         ns = nk if row_seeds is not None else 0
         sarr = (C.c_uint64 * max(ns, 1))(*([int(k) & 0xFFFFFFFFFFFFFFFF for k in row_seeds] if ns else [0]))
         karr = (C.c_uint64 * max(nk, 1))(*([int(k) & 0xFFFFFFFFFFFFFFFF for k in row_keys] if nk else [0]))
-        prev_gs = model.guidance_scale
-        set_gs = gs is not None and gs != prev_gs
-        if set_gs:
-            model.set_guidance_scale(gs)
-        cur = model._enter()
-        try:
+        with self._native(model, gs):
             _lib.check(lib.dsh_sample_set_row_keys(model._h, karr, nk), "dsh_sample_set_row_keys")      # (also drops earlier row seeds)
             if ns:
                 _lib.check(lib.dsh_sample_set_row_seeds(model._h, sarr, ns), "dsh_sample_set_row_seeds")
             if tail_blend:
                 _lib.check(lib.dsh_sample_set_tail_blend(model._h, 1), "dsh_sample_set_tail_blend")
+            if K:
+                _lib.check(lib.dsh_sample_set_start_level(model._h, K), "dsh_sample_set_start_level")
             try:
                 _lib.check(lib.dsh_sample(model._h, C.byref(opts), x.data_ptr(), int(init),
                                           None if gt is None else gt.data_ptr(), None if not masked else mask.data_ptr(),
@@ -262,10 +314,8 @@ class GaussianDiffusion:
             finally:
                 if tail_blend:                           # sticky as well: the next call is the reference's head-only fade again
                     lib.dsh_sample_set_tail_blend(model._h, 0)
-        finally:
-            model._exit(cur)
-            if set_gs:                                   # (sticky in the context, like the keys: the model's own setting comes back)
-                model.set_guidance_scale(prev_gs)
+                if K:
+                    lib.dsh_sample_set_start_level(model._h, 0)
         self._keep = (gt, mask, stack)          # consumed asynchronously on the stream
         if son:
             # gaussian_diffusion.py:1155-1157: the loop returns the dict of the last step plus the saved tails.  The tails live
@@ -291,10 +341,134 @@ class GaussianDiffusion:
                          model_kwargs=None, device=None, progress=False, eta=0.0, **kw):
         """gaussian_diffusion.py:1106-1159 (dispatches to the harmonize schedule when a mask is set).  ``tail_blend=True`` (keyword,
         not in the reference) adds the mirrored cross-fade on the last ``overlap_len`` frames, for masks that pin both ends of the
-        window (dsh_sample_set_tail_blend); the default is the reference's loop."""
+        window (dsh_sample_set_tail_blend); the default is the reference's loop.
+
+        ``start_level=K`` (keyword, ``1 .. K .. respacing``): the loop starts at spaced level ``K - 1`` instead of the top — levels
+        ``K-1 .. 0``, or with a mask the RePaint jump schedule walked from ``t_T = K``.  ``noise=`` then is x AT level ``K - 1``;
+        ``x_start=`` is a clean motion, noised to that level inside the loop with draw 0 (the draw x_T takes in a run from noise, so
+        ``row_keys`` / ``row_seeds`` / ragged lengths address it alike) — one or the other."""
         if not self._respacing:
             raise NotImplementedError("ddim_sample_loop needs a SpacedDiffusion('ddimK') (trainers use 'ddim25')")
         return self._run(0, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta, **kw)
+
+
+    # ---- editing an existing motion -----------------------------------------------------------
+    def _fixed_from(self) -> int:
+        """opt.fix_head_var in q_sample (gaussian_diffusion.py:443-456): the head channels keep x_start; -1 without the switch."""
+        if not getattr(self.opt, "fix_head_var", False):
+            return -1
+        name = getattr(self.opt, "dataset_name", None)
+        if name == "freeform_all":
+            return 24
+        if name == "talkshow":
+            return 90
+        raise NotImplementedError("fix_head_var: dataset_name must be 'freeform_all' or 'talkshow' (gaussian_diffusion.py:444-455)")
+
+    def q_sample_coefficients(self, t, B: int):
+        """(sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]) per row as fp32 host tensors: the fp64 square roots of the table
+        rounded once, like the reference's tables through ``_extract_into_tensor``."""
+        ts = [int(t)] * B if isinstance(t, numbers.Integral) else [int(v) for v in (t.tolist() if isinstance(t, torch.Tensor) else t)]
+        if len(ts) != B or any(v < 0 or v >= self.num_timesteps for v in ts):
+            raise ValueError(f"t needs one index in 0 .. {self.num_timesteps - 1} (or one per batch row, {B}), got {ts}")
+        ac = self.alphas_cumprod[np.asarray(ts, dtype=np.int64)]
+        return (torch.from_numpy(np.sqrt(ac).astype(np.float32)), torch.from_numpy(np.sqrt(1.0 - ac).astype(np.float32)))
+
+    def q_sample(self, x_start, t, noise=None, *, seed=None, row_keys=None, row_seeds=None, lengths=None):
+        """gaussian_diffusion.py:417-462 on the device: ``sqrt(ac[t]) x_start + sqrt(1 - ac[t]) noise``, ``x_start [B, T, C]`` on a GPU,
+        ``t`` an int or one index of THIS diffusion's (spaced) tables per row.  ``noise`` given: used as it is.  Otherwise it is drawn in
+        the same pass from the Philox streams a sampling loop with the same ``seed`` / ``row_keys`` / ``row_seeds`` / ``lengths`` takes its
+        draw 0 from.  ``lengths`` (one frame count per row): padded frames of the result are 0.  ``opt.fix_head_var`` keeps the head
+        channels of ``x_start`` (24 / 90 and up for the reference's two datasets), as the reference does."""
+        if not isinstance(x_start, torch.Tensor) or x_start.dim() != 3:
+            raise ValueError("q_sample takes x_start [B, T, C]")
+        fixed_from = self._fixed_from()
+        if not x_start.is_cuda:
+            raise _lib.DshError("q_sample runs on the GPU (no CPU fallback)")
+        B, T, Cc = (int(v) for v in x_start.shape)
+        a, s = self.q_sample_coefficients(t, B)
+        if noise is not None and tuple(noise.shape) != (B, T, Cc):
+            raise ValueError(f"noise {tuple(noise.shape)} does not match x_start {(B, T, Cc)}")
+        lens = normalize_lengths(lengths, B, T) if lengths is not None else None
+        if row_keys is not None and len(row_keys) != B:
+            raise ValueError(f"row_keys needs one key per batch row ({B}), got {len(row_keys)}")
+        if row_seeds is not None and (row_keys is None or len(row_seeds) != B):
+            raise ValueError(f"row_seeds needs row_keys and one seed per batch row ({B})")
+        if noise is None and row_keys is None and lens is not None:
+            raise ValueError("lengths with Philox noise need row_keys (a ragged row draws from its own stream)")
+        if noise is None and row_keys is not None and ((T * Cc) % 4 or any((v * Cc) % 4 for v in (lens or []))):
+            raise ValueError("row_keys: frames * channels (and length * channels of every row) must be a multiple of 4")
+        dev = x_start.device
+        x0 = x_start.to(torch.float32).contiguous()
+        out = torch.empty_like(x0)
+        nz = None if noise is None else noise.to(device=dev, dtype=torch.float32).contiguous()
+        a_d, s_d = a.to(dev), s.to(dev)
+        if seed is None and noise is None:
+            seed = int(torch.initial_seed()) + GaussianDiffusion._calls
+            GaussianDiffusion._calls += 1
+        M = 0xFFFFFFFFFFFFFFFF
+        karr = None if (row_keys is None or noise is not None) else (C.c_uint64 * B)(*[int(k) & M for k in row_keys])
+        sd = None
+        if karr is not None and row_seeds is not None:
+            sd = torch.tensor([(int(k) & M) - (1 << 64) if (int(k) & M) >> 63 else int(k) & M for k in row_seeds], dtype=torch.int64).to(dev)
+        larr = None if lens is None else (C.c_int32 * B)(*lens)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().dsh_op_q_sample(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), out.data_ptr(), x0.data_ptr(),
+                                            None if nz is None else nz.data_ptr(), a_d.data_ptr(), s_d.data_ptr(), B, T, Cc, 0, 0, fixed_from,
+                                            int(seed or 0) & M, 0, karr, None if sd is None else sd.data_ptr(), larr, 0)
+        _lib.check(rc, "dsh_op_q_sample")
+        return out
+
+    def _invert(self, model, x, from_level, to_level, clip_denoised, denoised_fn, model_kwargs, eta, return_trace, cond_scale=None):
+        if not isinstance(model, UniDiffuser):
+            raise TypeError("model must be a diffsheg_amd.model.UniDiffuser (no generic-callable / CPU fallback)")
+        if not self._respacing:
+            raise NotImplementedError("the DDIM reverse ODE needs a SpacedDiffusion('ddimK') (trainers use 'ddim25')")
+        if denoised_fn is not None:
+            raise NotImplementedError("denoised_fn is not on the accelerated path")
+        if eta != 0.0:
+            raise ValueError("Reverse ODE only for deterministic path (eta must be 0, gaussian_diffusion.py:1081)")
+        if model_kwargs is None or model_kwargs.get("y", None) is None:
+            raise AttributeError("'NoneType' object has no attribute 'keys' (model_kwargs['y'] must be a dict)")
+        y = model_kwargs["y"]
+        if "outpainting_mask" in y and bool(y.get("outpainting_mask_any", True)):
+            raise NotImplementedError("the reverse ODE takes no mask (ddim_reverse_sample has no RePaint branch)")
+        if bool(getattr(self.opt, "same_overlap_noisy", False)):
+            raise NotImplementedError("same_overlap_noisy does not apply to the reverse ODE")
+        from_level, to_level = int(from_level), int(to_level)
+        if not 0 <= from_level < to_level <= self._respacing:
+            raise ValueError(f"the reverse ODE needs 0 <= from_level < to_level <= {self._respacing}, got {from_level}, {to_level}")
+        if not isinstance(x, torch.Tensor) or x.dim() != 3:
+            raise ValueError("the reverse ODE takes x [B, T, C]")
+        B, T, Cc = (int(v) for v in x.shape)
+        gs = self._guidance(model, cond_scale, B)
+        self._condition(model, model_kwargs, (B, T, Cc), normalize_lengths(model_kwargs.get("length"), B, T), False)
+        dev = model.device
+        out = x.to(device=dev, dtype=torch.float32).contiguous().clone()
+        opts = self._opts(0, clip_denoised, 1, 0, 0, 0.0)
+        trace = torch.empty(to_level - from_level, B, T, Cc, device=dev) if return_trace else None
+        # (no draws: the row keys an earlier loop left in the native context do not concern the reverse loop, at any batch size)
+        with self._native(model, gs):
+            _lib.check(_lib.lib().dsh_invert_from(model._h, C.byref(opts), out.data_ptr(), from_level, to_level,
+                                                  None if trace is None else trace.data_ptr()), "dsh_invert")
+        return (out, trace) if return_trace else out
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0, cond_scale=None):
+        """gaussian_diffusion.py:1068-1104: one step of the DDIM reverse ODE, x at spaced level ``t`` (an int, or a tensor whose entries
+        are all equal) -> level ``t + 1``.  Returns ``{"sample": x}``; ``pred_xstart`` stays on the device side and is not returned."""
+        if isinstance(t, torch.Tensor):
+            ts = set(int(v) for v in t.reshape(-1).tolist())
+            if len(ts) != 1:
+                raise NotImplementedError("one level per call: per-row levels need per-row schedules")
+            t = ts.pop()
+        return {"sample": self._invert(model, x, int(t), int(t) + 1, clip_denoised, denoised_fn, model_kwargs, eta, False, cond_scale)}
+
+    def ddim_reverse_sample_loop(self, model, x, to_level, model_kwargs=None, return_trace=False, clip_denoised=False, eta=0.0,
+                                 cond_scale=None):
+        """DDIM inversion: ``x [B, T, C]`` (a clean motion) carried through ``ddim_reverse_sample`` at the spaced levels
+        ``0 .. to_level - 1``, natively and in one call (dsh_invert).  No draws.  The result stands at ``alphas_cumprod[to_level]``;
+        ``ddim_sample_loop(start_level=K, noise=...)`` enters at ``alphas_cumprod[K - 1]`` (the guided-diffusion pairing of the two
+        loops: close to, not exactly, an inverse).  ``return_trace``: also the state after every step ``[to_level, B, T, C]``."""
+        return self._invert(model, x, 0, to_level, clip_denoised, None, model_kwargs, eta, return_trace, cond_scale)
 
 
 class SpacedDiffusion(GaussianDiffusion):

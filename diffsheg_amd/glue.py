@@ -11,6 +11,8 @@
   to BVH (ddpm_beat_trainer.py:1044-1060, datasets/rotation_converter.py), and the dataset's opposite direction
   (datasets/beat.py:376-401) for frames a caller holds as Euler / BVH poses; HIP kernels, output stays on the device.
 
+* :func:`edit_region` — the keep mask of an edit (``DDPMTrainer.sample_variations(keep=)``) from frame and column ranges, HIP kernel.
+
 HuBERT itself (``facebook/hubert-large-ls960-ft``), mel extraction and the BVH / face-JSON file writers (they need the dataset's
 template files) stay out of scope.
 """
@@ -167,3 +169,49 @@ def euler_to_axis_angle(pose: torch.Tensor, stats: PoseStats, *, split_pos: Opti
     ``euler_angles_to_axis_angle(..., 'XYZ')`` -> normalise with the axis-angle statistics: what ``motions``, ``head`` and ``tail`` of
     the samplers expect from frames held as Euler / BVH poses.  ``split_pos`` / ``lengths`` as for :func:`axis_angle_to_euler`."""
     return _rotation_call("euler_to_axis_angle", pose, stats, split_pos, lengths, False)
+
+
+def _ranges(v, what: str, hi: int):
+    out = [(int(a), int(b)) for a, b in v]
+    for a, b in out:
+        if not 0 <= a <= b <= hi:
+            raise ValueError(f"edit_region: {what} range ({a}, {b}) outside 0 <= lo <= hi <= {hi}")
+    return out
+
+
+def edit_region(B: int, T: int, C_: int, frames=None, columns=None, device="cuda") -> torch.Tensor:
+    """The keep mask of an edit, built on the device in one launch: a bool tensor ``[B, T, C]``, False (re-sample) where the frame lies
+    in one of the ``frames`` ranges OR the column in one of the ``columns`` ranges, True (leave as it is) elsewhere — "re-roll seconds
+    3-5 and the hands, keep the rest".  ``frames``: a list (of tuples or lists) of half-open ``(a, b)`` ranges, ALL of them shared by every row, or
+    a ``[B, 2]`` tensor with one range per row (only a tensor is read per row); ``columns``: a list of half-open ``(lo, hi)`` ranges.  Ranges are validated on the host
+    (``ValueError``); an empty range edits nothing."""
+    B, T, C_ = int(B), int(T), int(C_)
+    if B < 1 or T < 1 or C_ < 1:
+        raise ValueError(f"edit_region needs a positive shape, got {(B, T, C_)}")
+    per_row = None
+    if frames is not None:
+        if isinstance(frames, torch.Tensor):
+            if tuple(frames.shape) != (B, 2):
+                raise ValueError(f"edit_region: a frames tensor holds one range per row, [{B}, 2], got {tuple(frames.shape)}")
+            per_row = [[r] for r in _ranges(frames.detach().to("cpu").tolist(), "frame", T)]
+        else:
+            shared = _ranges(frames, "frame", T)
+            per_row = [shared] * B
+    nf = len(per_row[0]) if per_row else 0
+    cols = _ranges(columns, "column", C_) if columns is not None else []
+    nc = len(cols)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.DshError("edit_region runs on the GPU (no CPU fallback)")
+    flat_f = [v for row in (per_row or []) for r in row for v in r]
+    flat_c = [v for r in cols for v in r]
+    host = torch.tensor(flat_f + flat_c + [0], dtype=torch.int32)
+    devt = host.to(dev)
+    keep = torch.empty(B, T, C_, dtype=torch.uint8, device=dev)
+    fh = (C.c_int32 * max(len(flat_f), 1))(*flat_f)
+    ch = (C.c_int32 * max(len(flat_c), 1))(*flat_c)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().dsh_op_region_mask(_stream_ptr(keep.device), fh, devt.data_ptr() if nf else None, nf, ch,
+                                           devt.data_ptr() + 4 * len(flat_f) if nc else None, nc, B, T, C_, keep.data_ptr())
+    _lib.check(rc, "dsh_op_region_mask")
+    return keep.view(torch.bool)

@@ -521,6 +521,94 @@ class DDPMTrainer:
         out = self.generate_batch(audio_emb, p_id, C, add_cond, {"gt": gt, "outpainting_mask": mask, "outpainting_mask_any": True}, **kw)
         return out["sample"] if isinstance(out, dict) else out
 
+    # ---- editing an existing take: variations close to it, re-rolled regions, another speaker's style ------------------------
+    @staticmethod
+    def strength_to_level(strength: float, respacing: int = 25) -> int:
+        """``strength`` in ``(0, 1]`` -> start level ``K = max(1, round(strength * respacing))`` (Python's ``round``: halves go to the
+        even neighbour).  1 is the whole schedule, i.e. nothing of the input survives but its kept elements."""
+        s = float(strength)
+        if not 0.0 < s <= 1.0:
+            raise ValueError(f"strength must be in (0, 1], got {strength}")
+        return max(1, int(round(s * int(respacing))))
+
+    def _edit_level(self, level, strength) -> int:
+        R = self.diffusion_ddim_val.num_timesteps
+        if (level is None) == (strength is None):
+            raise ValueError("give level= (1 .. respacing) or strength= (0 .. 1], one of the two")
+        K = int(level) if level is not None else self.strength_to_level(strength, R)
+        if not 1 <= K <= R:
+            raise ValueError(f"level must be in 1 .. {R}, got {level}")
+        if not getattr(self.opt, "ddim", True):
+            raise NotImplementedError("editing needs opt.ddim (restarts of the DDPM loop are not built)")
+        return K
+
+    def sample_variations(self, motions: torch.Tensor, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor], *,
+                          level: Optional[int] = None, strength: Optional[float] = None, keep: Optional[torch.Tensor] = None,
+                          seed: Optional[int] = None, row_keys: Optional[Sequence[int]] = None, row_seeds: Optional[Sequence[int]] = None,
+                          cond_scale=None, lengths=None, modality="both", expression=None, pose_rep: str = "axis_angle") -> torch.Tensor:
+        """Variations of an existing motion ``motions [B, T, C]`` (standardised, the sampler's representation): it is noised to spaced
+        level ``K - 1`` (``q_sample`` with the loop's draw 0) and denoised from there with the DDIM loop, in one native call.  ``level=K``
+        (``1 .. respacing``) or ``strength=s`` (``K = max(1, round(s * respacing))``): small K stays close to the input, K = respacing
+        keeps nothing of it.  Two seeds give two variations; ``row_keys`` / ``row_seeds`` / ``lengths`` / ``modality`` / ``expression``
+        / ``cond_scale`` / ``pose_rep`` as for :meth:`generate_batch`.
+
+        ``keep`` (bool, broadcastable to ``[B, T, C]``, True = leave as it is; :func:`diffsheg_amd.glue.edit_region` builds one): the
+        RePaint path — ``gt = motions``, ``mask = keep``, the jump schedule walked from ``t_T = K`` — with ``addBlend`` off (the
+        reference's fade would rewrite kept frames ``[:overlap_len]``).  Kept elements of the result are the input bit for bit: the
+        last step blends ``1 * gt + 0 * n``.  ``opt.fix_head_var`` is refused (q_sample would keep the head channels un-noised)."""
+        if getattr(self.opt, "fix_head_var", False):
+            raise NotImplementedError("sample_variations with opt.fix_head_var is not built")
+        K = self._edit_level(level, strength)
+        if bool(getattr(self.opt, "same_overlap_noisy", False)):
+            raise NotImplementedError("sample_variations with same_overlap_noisy: the saved noisy tails describe whole schedules")
+        audio_emb = audio_emb.to(self.device)
+        B, T, C = int(audio_emb.shape[0]), int(audio_emb.shape[1]), int(self.opt.net_dim_pose)
+        if tuple(motions.shape) != (B, T, C):
+            raise ValueError(f"motions must be [B, T, C] = {(B, T, C)}, got {tuple(motions.shape)}")
+        x0 = motions.to(device=self.device, dtype=torch.float32)
+        kw = {"start_level": K, "x_start": x0}
+        inpaint = {}
+        if keep is not None:
+            if keep.dtype != torch.bool:
+                raise ValueError(f"keep must be a bool mask, got {keep.dtype}")
+            try:
+                mask = keep.to(self.device).expand(B, T, C)
+            except RuntimeError as e:
+                raise ValueError(f"keep {tuple(keep.shape)} does not broadcast to {(B, T, C)}") from e
+            inpaint = {"gt": x0, "outpainting_mask": mask}
+            kw["add_blend"] = False
+        for k, v in (("seed", seed), ("row_keys", row_keys), ("row_seeds", row_seeds), ("cond_scale", cond_scale)):
+            if v is not None:
+                kw[k] = v
+        return self.generate_batch(audio_emb, p_id, C, add_cond, inpaint, lengths=lengths, pose_rep=pose_rep, modality=modality,
+                                   expression=expression, **kw)
+
+    def restyle(self, motions: torch.Tensor, audio_emb: torch.Tensor, p_id_from: torch.Tensor, p_id_to: torch.Tensor,
+                add_cond: Dict[str, torch.Tensor], *, level: int, cond_scale=None) -> torch.Tensor:
+        """"Same performance, other speaker's style": ``motions [B, T, C]`` is inverted to spaced level ``K = level`` with the DDIM
+        reverse ODE under the source speaker ``p_id_from`` (``ddim_reverse_sample`` at levels ``0 .. K-1``, gaussian_diffusion.py:1068-1104)
+        and decoded under the target speaker ``p_id_to`` with ``ddim_sample_loop(start_level=K, noise=inverted)`` at ``eta = 0``.
+
+        Index convention (the reference's, and guided-diffusion's): the reverse step at level ``k`` moves x from ``alphas_cumprod[k]`` to
+        ``alphas_cumprod_next[k] = alphas_cumprod[k + 1]``, so the reverse loop ENDS at ``alphas_cumprod[K]``; the forward step at level
+        ``k`` reads x as being at ``alphas_cumprod[k]``, so decoding ``K`` steps STARTS at ``alphas_cumprod[K - 1]``.  The pairing is off
+        by one level on purpose — it is the one guided-diffusion's own encode / decode loops use — and it is not an exact inverse, even
+        under one speaker.  Deterministic: no draws on either side."""
+        K = self._edit_level(level, None)
+        audio_emb = audio_emb.to(self.device)
+        B, T, C = int(audio_emb.shape[0]), int(audio_emb.shape[1]), int(self.opt.net_dim_pose)
+        if tuple(motions.shape) != (B, T, C):
+            raise ValueError(f"motions must be [B, T, C] = {(B, T, C)}, got {tuple(motions.shape)}")
+        model_kwargs = {"audio_emb": audio_emb, "length": None, "person_id": p_id_from, "add_cond": add_cond, "y": {},
+                        "pe_type": getattr(self.opt, "PE", "pe_sinu")}
+        inv = self.diffusion_ddim_val.ddim_reverse_sample_loop(self.encoder, motions.to(self.device), K, model_kwargs=model_kwargs,
+                                                               cond_scale=cond_scale)
+        kw = {"start_level": K, "noise": inv, "seed": 0}
+        if cond_scale is not None:
+            kw["cond_scale"] = cond_scale
+        out = self.generate_batch(audio_emb, p_id_to, C, add_cond, {}, **kw)
+        return out["sample"] if isinstance(out, dict) else out
+
     def sample_arbitrary_len_sharded(self, *args, **kw) -> Optional[torch.Tensor]:
         """Long stream -> independent chains over the ranks -> gather on rank 0 -> optionally the seams between the chains
         re-sampled as in-betweening windows (module-level function below)."""

@@ -184,6 +184,8 @@ int dsh_debug_copy(dsh_ctx* ctx, const char* what, float* out);
 /* ---- boundary 2: full sampling loops ----------------------------------------------------------- */
 /* Number of Gaussian tensors [B,T,C] the loop consumes, in the reference's draw order
  * (SURVEY §8a S7): x_T first (unless init_from_x), then per step.  Returns < 0 on error. */
+/* (init_from_x here is a flag: any non-zero value counts as "x is given".  For init_from_x = 2 of dsh_sample - one draw more, the
+ * q_sample noise - size the stack with dsh_sample_num_draws_from below.) */
 int64_t dsh_sample_num_draws(const dsh_sampler_opts* opts, int32_t masked, int32_t init_from_x);
 /* Number of (denoise + undo) steps, i.e. rows a trace buffer needs. */
 int64_t dsh_sample_num_steps(const dsh_sampler_opts* opts, int32_t masked);
@@ -200,6 +202,9 @@ int64_t dsh_sample_num_steps(const dsh_sampler_opts* opts, int32_t masked);
  * rows is above the limit and its halves are below: the halves round the FFN hidden layer to bf16, the unsplit batch keeps it in
  * fp32, and the two agree to bf16 round-off only.  fp32 precision: always bit-identical.
  * Shapes: see dsh_set_condition - a shape it accepts is never refused here.) */
+/* init_from_x = 2: x holds a clean motion x0.  Draw 0 - the draw x_T takes in a run from noise, with the same row keys, row seeds and
+ * ragged lengths - is the q_sample noise: x <- sqrt(ac[k]) x0 + sqrt(1 - ac[k]) n at the first level k of the schedule (K-1 with a start
+ * level), and the steps' draws follow from index 1 as in a run from noise.  DDIM loops only. */
 int dsh_sample(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t init_from_x, const float* gt,
                const uint8_t* mask, int32_t masked, const float* noise_stack, int64_t n_draws, float* trace);
 /* DSH_NOISE_PHILOX only: give every batch row its own generator key (host array of n = B entries; n = 0 restores
@@ -227,6 +232,27 @@ int dsh_sample_set_row_seeds(dsh_ctx* ctx, const uint64_t* seeds_host, int32_t n
  * on = 0 (the default) is the reference's loop, bit for bit.  Sticky until changed.  dsh_sample then returns -1 when
  * 2 * overlap_len > frames, and with same_overlap_noisy (the saved noisy tails describe a window chain). */
 int dsh_sample_set_tail_blend(dsh_ctx* ctx, int32_t on);
+/* ---- editing an existing motion: restart from a level, q_sample, DDIM inversion ----
+ * Start level K of the DDIM loops, 1 <= K <= respacing (0, the default: the whole schedule, bit for bit).  The plain schedule becomes
+ * the spaced levels K-1 .. 0; the mask-present (RePaint) schedule becomes the jump schedule walked from t_T = K in place of its
+ * built-in 15 / 0.6 * respacing.  x enters at level K-1: given (init_from_x = 1), or built from a clean motion (init_from_x = 2, below).
+ * Sticky like the tail blend.  dsh_sample then returns -1 on a DDPM loop, on K > respacing, with same_overlap_noisy and with the
+ * tail blend. */
+int dsh_sample_set_start_level(dsh_ctx* ctx, int32_t level);
+/* dsh_sample_num_draws / _num_steps of a run with init mode `init` (0, 1 or 2) and start level `start_level`; the two entries above are
+ * these with start_level = 0. */
+int64_t dsh_sample_num_draws_from(const dsh_sampler_opts* opts, int32_t masked, int32_t init, int32_t start_level);
+int64_t dsh_sample_num_steps_from(const dsh_sampler_opts* opts, int32_t masked, int32_t init, int32_t start_level);
+/* DDIM inversion (ddim_reverse_sample, gaussian_diffusion.py:1068-1104): x [B,T,C] (device, in/out) is carried through the spaced levels
+ * 0 .. to_level-1 of the reverse ODE in place, each step evaluating the model at level k and writing
+ *   x <- sqrt(ac_next[k]) x0 + sqrt(1 - ac_next[k]) eps        (ac_next[k] = alphas_cumprod[k+1], 0 behind the last level)
+ * with the DDIM step's kernel.  No draws; opts->kind must be DDIM and opts->eta 0; no mask; no start level, tail blend or
+ * same_overlap_noisy (-1).  trace (device, nullable): [to_level, B*T*C].  The result stands at alphas_cumprod[to_level]; a decode
+ * with start level K enters at alphas_cumprod[K-1] (the guided-diffusion pairing: not an exact inverse). */
+int dsh_invert(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t to_level, float* trace);
+/* the same over the levels from_level .. to_level-1 (0 <= from_level < to_level; x enters at from_level): one reverse step is
+ * (t, t+1).  trace: [to_level - from_level, B*T*C]. */
+int dsh_invert_from(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t from_level, int32_t to_level, float* trace);
 /* Classifier-free guidance scale of dsh_eval and dsh_sample (transformer.py:537, :586: eps = u + s_b (k - u) for clip b, in both motion
  * encoders; the expression x0 the gesture encoder reads is built from the mixed expression eps).  Host array of n entries: n = 0 restores
  * the config's cond_scale, n = 1 sets one value for the whole batch, n = B one value per clip (checked against the batch of
@@ -390,6 +416,21 @@ int dsh_op_ddim_step(void* hip_stream, float* x, const float* eps, const float* 
                      int32_t overlap_len, int32_t blend, int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi);
 /* standard normals from the on-device Philox generator */
 int dsh_op_philox_randn(void* hip_stream, float* out, int64_t n, uint64_t seed, uint64_t offset);
+/* q_sample (gaussian_diffusion.py:434-462): out[b] = a[b] x0[b] + s[b] n[b] over [B, frames, channels] (device fp32; out may be x0), every
+ * product and the sum rounded on their own.  a_dev / s_dev: device arrays [B], one coefficient pair per row.  n = noise (device), or, when
+ * noise is NULL, drawn inside the same pass: row_keys_host NULL = the values dsh_op_philox_randn(seed, offset) writes; else those of
+ * dsh_op_philox_randn_rows (row_seeds_dev: _seeded; row_lens_host + draw: _ragged) for the same arguments.  Columns outside
+ * [c_lo, c_hi) are not written (c_hi <= c_lo: all are); columns >= fixed_from are copied from x0 (-1: none; the reference's fix_head_var,
+ * 24 / 90 for its two datasets); with row_lens_host, frames >= row_lens_host[b] of row b are written as 0. */
+int dsh_op_q_sample(void* hip_stream, float* out, const float* x0, const float* noise, const float* a_dev, const float* s_dev, int32_t B,
+                    int32_t frames, int32_t channels, int32_t c_lo, int32_t c_hi, int32_t fixed_from, uint64_t seed, uint64_t offset,
+                    const uint64_t* row_keys_host, const uint64_t* row_seeds_dev, const int32_t* row_lens_host, uint64_t draw);
+/* keep mask of an edit: keep [B, T, C] (device uint8) = 0 where frame t lies in one of row b's nf half-open frame ranges
+ * frames[b, j] = (lo, hi) or column c in one of the nc column ranges cols[j] = (lo, hi), 1 elsewhere; one launch.  Both range lists are
+ * given as a host copy (validated: 0 <= lo <= hi <= T / C, -1 otherwise) and a device copy (read by the kernel, which skips a range outside
+ * those bounds all the same). */
+int dsh_op_region_mask(void* hip_stream, const int32_t* frames_host, const int32_t* frames_dev, int32_t nf, const int32_t* cols_host,
+                       const int32_t* cols_dev, int32_t nc, int32_t B, int32_t T, int32_t C, uint8_t* keep);
 /* the per-row streams dsh_sample draws from after dsh_sample_set_row_keys: out[rows, n_row] (device), row b = key `seed`,
  * counter (offset + position inside the row, row_keys_host[b]); n_row % 4 == 0.  Synchronises the stream. */
 int dsh_op_philox_randn_rows(void* hip_stream, float* out, int32_t rows, int64_t n_row, uint64_t seed, uint64_t offset,
