@@ -76,6 +76,7 @@ SYMBOLS = {
     "dsh_timestep_map": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "dsh_jump_schedule": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "dsh_interp_time": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
+    "dsh_interp_time_ragged": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P]),
     "dsh_inv_standardize": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     "dsh_axis_angle_to_euler": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32]),
     "dsh_euler_to_axis_angle": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32]),
@@ -138,9 +139,12 @@ SYMBOLS = {
     "dsh_mel_num_frames": (C.c_int64, [_P, C.c_int64]),
     "dsh_mel_debug_tables": (C.c_int, [_P, C.POINTER(C.c_int32), _P, _P]),
     "dsh_mel_compute": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P]),
+    "dsh_mel_compute_ragged": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P]),
     "dsh_resample_poly_len": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "dsh_op_resample_poly": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    "dsh_op_resample_poly_ragged": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     "dsh_op_softmax_attention": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "dsh_op_softmax_attention_ragged": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "dsh_hubert_create": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "dsh_hubert_destroy": (C.c_int, [_P]),
     "dsh_hubert_load_tensor": (C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), C.c_int32]),
@@ -149,7 +153,9 @@ SYMBOLS = {
     "dsh_hubert_num_frames": (C.c_int64, [_P, C.c_int64]),
     "dsh_hubert_set_chunk_pass": (C.c_int, [_P, C.c_int32]),
     "dsh_hubert_encode": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P]),
+    "dsh_hubert_encode_ragged": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_int64), _P]),
     "dsh_op_pos_conv": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "dsh_op_pos_conv_ragged": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "dsh_op_conv0_ln_gelu": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "dsh_op_conv_ln_gelu": (C.c_int, [_P, _P] + [C.c_int32] * 6 + [_P, _P, _P, _P, _P]),
 }

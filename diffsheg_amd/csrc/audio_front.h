@@ -27,7 +27,12 @@ public:
     // padding (len >= n_fft / 2 + 1) or len >= hop does not hold
     long long num_frames(long long len) const;
     int compute(const float* wave, int B, long long len, float* mel);
+    // rows padded to `len` samples, row b owning lens[b] of them (DEVICE int32, each with num_frames(lens[b]) >= 1 and <= len: the caller's
+    // check): mel [B, num_frames(len), n_mels], row b bit for bit compute() on its own lens[b] samples, 0 behind its lens[b] / hop frames.
+    // No sample behind lens[b] is read.
+    int compute_ragged(const float* wave, int B, long long len, const int* lens, float* mel);
 private:
+    int run(const char* what, const float* wave, int B, long long len, const int* lens, float* mel);
     int upload();
     int reserve(int B, long long len);
     void release_buffers();
@@ -46,9 +51,16 @@ private:
 // taps is a DEVICE array of n_taps (odd) floats.
 long long resample_poly_len(long long n, int up, int down);
 int launch_resample_poly(const float* x, int B, long long n, int up, int down, const float* taps, int n_taps, float* y, hipStream_t s);
+// x [B, n] of which row b owns lens[b] samples (DEVICE int32, clamped to [0, n]; nullptr: every row owns n): y [B, resample_poly_len(n)], row b
+// what the dense call gives for its own samples alone, 0 behind resample_poly_len(lens[b]).  No sample behind lens[b] is read.
+int launch_resample_poly_ragged(const float* x, int B, long long n, const int* lens, int up, int down, const float* taps, int n_taps, float* y,
+                                hipStream_t s);
 
 // softmax multi-head attention core, 64-wide heads, no mask: qkv [B, M, 3 H 64] = (q | k | v), q already scaled;
 // out[b, t, h 64 + d] = sum_s softmax_s(q[b, t, h] . k[b, s, h]) v[b, s, h 64 + d]
 int launch_softmax_attention(const float* qkv, int B, int M, int H, float* out, hipStream_t s);
+// the same for rows of M_max frames of which row b owns lens[b] (DEVICE int32, clamped to [0, M_max]): keys and queries < lens[b] only, the bits
+// of the dense call on the row alone at M = lens[b]; out[b, t >= lens[b]] = 0; no frame >= lens[b] is read
+int launch_softmax_attention_ragged(const float* qkv, int B, int M_max, int H, const int* lens, float* out, hipStream_t s);
 
 }  // namespace dsh

@@ -117,18 +117,36 @@ int MelFront::reserve(int B, long long len) {
     return 0;
 }
 
-__global__ void reflect_pad_kernel(const float* __restrict__ x, long long len, float* __restrict__ y, long long Lp, int half, size_t n) {
+// lens (nullable): row b of x [B, ld] holds lens[b] samples of its own; the reflection is about ITS last sample and everything behind
+// lens[b] + n_fft is 0, so no sample >= lens[b] is read.  A count outside [half + 1, ld] (the callers refuse it on the host) gives a zero row.
+__global__ void reflect_pad_kernel(const float* __restrict__ x, long long ld, const int* __restrict__ lens, float* __restrict__ y, long long Lp,
+                                   int half, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const long long b = (long long)(i / (size_t)Lp), c = (long long)(i % (size_t)Lp);
+    long long len = ld;
+    if (lens) {
+        len = lens[b];
+        if (len < half + 1 || len > ld) len = -2 * (long long)half;      // (c < len + 2 half never holds)
+    }
     float v = 0.0f;                                         // (columns behind len + n_fft: the pad to 4 floats)
     if (c < len + 2 * half) {
         long long j = c - half;
         if (j < 0) j = -j;                                  // len >= half + 1: one reflection is enough on either side
         else if (j >= len) j = 2 * (len - 1) - j;
-        v = x[b * len + j];
+        v = x[b * ld + j];
     }
     y[i] = v;
+}
+
+// y [B, N, C]: frames t >= lens[b] / div of batch row b become 0 (C % 4 == 0)
+__global__ void zero_tail_frames_kernel(float* __restrict__ y, long long N, int C4, const int* __restrict__ lens, int div, size_t n4) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    const size_t row = i / (size_t)C4;
+    const long long b = (long long)(row / (size_t)N), t = (long long)(row % (size_t)N);
+    const int own = lens[b] < 0 ? 0 : lens[b] / div;
+    if (t >= own) reinterpret_cast<f32x4*>(y)[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 }
 
 __global__ void power_rows_kernel(const float* __restrict__ spec, int Nd, int nb, float* __restrict__ pw, int Kf, size_t n) {
@@ -144,24 +162,36 @@ __global__ void power_rows_kernel(const float* __restrict__ spec, int Nd, int nb
     pw[i] = v;
 }
 
-int MelFront::compute(const float* wave, int B, long long len, float* mel) {
-    DSH_REQUIRE(wave && mel, "dsh_mel_compute: null tensor");
-    DSH_REQUIRE(B >= 1, "dsh_mel_compute: batch must be positive");
+int MelFront::compute(const float* wave, int B, long long len, float* mel) { return run("dsh_mel_compute", wave, B, len, nullptr, mel); }
+
+// Rows of `len` samples of which row b owns lens[b] (DEVICE int32; the host-side callers have checked num_frames(lens[b]) >= 1 and
+// lens[b] <= len).  Only the padding knows the row's own length: frame j < lens[b] / hop of the padded row is the slice the dense call at
+// len = lens[b] forms, the two GEMMs give every output element one accumulator with K ascending wherever the row sits in M, so mel[b, j] has the
+// bits of compute() on row b alone.  The frames behind are finite (the pad row is zeros there) and are overwritten with 0.
+int MelFront::compute_ragged(const float* wave, int B, long long len, const int* lens, float* mel) {
+    DSH_REQUIRE(lens, "dsh_mel_compute_ragged: null lengths");
+    DSH_REQUIRE(len < (1ll << 31), "dsh_mel_compute_ragged: rows of at most 2^31 - 1 samples");
+    return run("dsh_mel_compute_ragged", wave, B, len, lens, mel);
+}
+
+int MelFront::run(const char* what, const float* wave, int B, long long len, const int* lens, float* mel) {
+    DSH_REQUIRE(wave && mel, std::string(what) + ": null tensor");
+    DSH_REQUIRE(B >= 1, std::string(what) + ": batch must be positive");
     const long long N = num_frames(len);
     if (N < 1) {
-        set_last_error("invalid argument: dsh_mel_compute: " + std::to_string(len) + " samples; the reflect padding needs " +
+        set_last_error("invalid argument: " + std::string(what) + ": " + std::to_string(len) + " samples; the reflect padding needs " +
                        std::to_string(n_fft_ / 2 + 1) + " and one frame " + std::to_string(hop_));
         return -1;
     }
     const long long Lp = (len + n_fft_ + 3) / 4 * 4;
-    DSH_REQUIRE((long long)B * N < (1ll << 31) / 64 && (long long)B * Lp < (1ll << 40), "dsh_mel_compute: batch too large");
+    DSH_REQUIRE((long long)B * N < (1ll << 31) / 64 && (long long)B * Lp < (1ll << 40), std::string(what) + ": batch too large");
     // the last frame read ends at hop (N - 1) + n_fft <= len - hop + n_fft < len + n_fft <= Lp: inside the padded row
     if (int e = upload()) return e;
     if (int e = reserve(B, len)) return e;
     const int M = (int)((long long)B * N);
     {
         const size_t n = (size_t)B * Lp;
-        hipLaunchKernelGGL(reflect_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, wave, len, pad_, Lp, n_fft_ / 2, n);
+        hipLaunchKernelGGL(reflect_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream_, wave, len, lens, pad_, Lp, n_fft_ / 2, n);
         DSH_HIP_CHECK(hipGetLastError());
     }
     {
@@ -185,6 +215,11 @@ int MelFront::compute(const float* wave, int B, long long len, float* mel) {
         a.Tout = (int)N; a.M = M; a.N = n_mels_; a.Kreal = Kf_; a.Kp = Kf_;
         if (int e = launch_conv_gemm_f32(a, stream_)) return e;
     }
+    if (lens) {
+        const size_t n4 = (size_t)M * (n_mels_ / 4);
+        hipLaunchKernelGGL(zero_tail_frames_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream_, mel, N, n_mels_ / 4, lens, hop_, n4);
+        DSH_HIP_CHECK(hipGetLastError());
+    }
     return 0;
 }
 
@@ -193,30 +228,44 @@ long long resample_poly_len(long long n, int up, int down) { return (n * up + do
 
 // One lane per output sample.  Output j sits at position m = j down + half of the zero-stuffed signal convolved with the taps; only the taps
 // k = m (mod up) meet a non-zero sample x[(m - k) / up]: about n_taps / up products, added in ascending tap order.
-__global__ void resample_poly_kernel(const float* __restrict__ x, long long n, int up, int down, const float* __restrict__ taps, int n_taps,
-                                     float* __restrict__ y, long long n_out, size_t total) {
+// lens (nullable): row b of x [B, ld] holds lens[b] samples of its own (clamped to [0, ld]); the taps see nothing behind them and the outputs
+// behind ceil(lens[b] up / down) are 0.
+__global__ void resample_poly_kernel(const float* __restrict__ x, long long ld, const int* __restrict__ lens, int up, int down,
+                                     const float* __restrict__ taps, int n_taps, float* __restrict__ y, long long n_out, size_t total) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const long long b = (long long)(i / (size_t)n_out), j = (long long)(i % (size_t)n_out);
+    long long n = ld;
+    if (lens) {
+        n = lens[b];
+        n = n < 0 ? 0 : (n > ld ? ld : n);
+        if (j >= (n * up + down - 1) / down) { y[i] = 0.0f; return; }
+    }
     const long long m = j * down + (n_taps - 1) / 2;
     long long k = m % up;
     const long long k_min = m - (n - 1) * up;              // x index (m - k) / up <= n - 1
     if (k < k_min) k += (k_min - k + up - 1) / up * up;
-    const float* xr = x + b * n;
+    const float* xr = x + b * ld;
     float acc = 0.0f;
     for (; k < n_taps && k <= m; k += up) acc = fmaf(taps[k], xr[(m - k) / up], acc);
     y[i] = acc;
 }
 
 int launch_resample_poly(const float* x, int B, long long n, int up, int down, const float* taps, int n_taps, float* y, hipStream_t s) {
+    return launch_resample_poly_ragged(x, B, n, nullptr, up, down, taps, n_taps, y, s);
+}
+
+int launch_resample_poly_ragged(const float* x, int B, long long n, const int* lens, int up, int down, const float* taps, int n_taps, float* y,
+                                hipStream_t s) {
     DSH_REQUIRE(x && taps && y, "resample_poly: null pointer");
+    DSH_REQUIRE(!lens || n < (1ll << 31), "resample_poly: ragged rows of at most 2^31 - 1 samples");
     DSH_REQUIRE(B >= 1 && n >= 1, "resample_poly: batch and length must be positive");
     DSH_REQUIRE(up >= 1 && down >= 1 && n_taps >= 1 && n_taps % 2 == 1, "resample_poly: up, down >= 1 and an odd number of taps");
     DSH_REQUIRE(n < (1ll << 40) / up && n < (1ll << 40) / down, "resample_poly: signal too long");
     const long long n_out = resample_poly_len(n, up, down);
     const size_t total = (size_t)B * n_out;
     DSH_REQUIRE(total < ((size_t)1 << 31) * 256, "resample_poly: batch too large");
-    hipLaunchKernelGGL(resample_poly_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, n, up, down, taps, n_taps, y, n_out, total);
+    hipLaunchKernelGGL(resample_poly_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, n, lens, up, down, taps, n_taps, y, n_out, total);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -233,11 +282,35 @@ int launch_resample_poly(const float* x, int B, long long n, int up, int down, c
 //                 (r & 3) + 8 (r >> 2) + 4 (l >> 5)); the A operand of that step is V[that key][channel l & 31 (+ 32)].  O^T again has
 //                 the query on the lane, so the rescaling by exp(m_old - m_new) and the final 1 / sum are per-lane scalars.
 // Keys >= M of the last tile get the logit -inf: their weight is exp(-inf) = 0 exactly; their K / V rows are loaded from row M - 1.
-__global__ __launch_bounds__(64) void softmax_attention_f32_kernel(const float* __restrict__ qkv, int M, int H, float* __restrict__ out, int q_tiles) {
+// RAGGED: batch row b has lens[b] (clamped to [0, M_max]) frames of its own inside a row of M_max; the body below runs with M = lens[b] and
+// only the row base and the output row use M_max, so it issues the loads, MFMAs and exponentials of the dense kernel at M = lens[b] in
+// the same order: the row has the same bits.  A frame >= lens[b] is never loaded (a NaN there would survive a zero weight); query tiles that
+// start behind lens[b] leave at the top; output frames lens[b] .. M_max - 1 are written as 0.
+__device__ __forceinline__ void attention_zero_row(float* orow, int half) {
+    const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        *reinterpret_cast<f32x4*>(orow + 8 * g + 4 * half) = z;
+        *reinterpret_cast<f32x4*>(orow + 32 + 8 * g + 4 * half) = z;
+    }
+}
+
+template <bool RAGGED>
+__global__ __launch_bounds__(64) void softmax_attention_f32_kernel(const float* __restrict__ qkv, int M_max, int H, const int* __restrict__ lens,
+                                                                  float* __restrict__ out, int q_tiles) {
     const int lane = threadIdx.x, half = lane >> 5, col = lane & 31;
     const int qt = blockIdx.x % q_tiles, bh = blockIdx.x / q_tiles, h = bh % H, b = bh / H;
     const size_t ld = (size_t)3 * H * 64;
-    const float* base = qkv + (size_t)b * M * ld + (size_t)h * 64;
+    int M = M_max;
+    if (RAGGED) {
+        M = lens[b];
+        M = M < 0 ? 0 : (M > M_max ? M_max : M);
+        if (qt * 32 >= M) {                                 // (uniform over the wave) nothing of this tile is a frame of the row
+            if (qt * 32 + col < M_max) attention_zero_row(out + ((size_t)b * M_max + qt * 32 + col) * ((size_t)H * 64) + (size_t)h * 64, half);
+            return;
+        }
+    }
+    const float* base = qkv + (size_t)b * M_max * ld + (size_t)h * 64;
     const float* kbase = base + (size_t)H * 64;
     const float* vbase = base + (size_t)2 * H * 64;
     const int q_row = qt * 32 + col;
@@ -294,8 +367,11 @@ __global__ __launch_bounds__(64) void softmax_attention_f32_kernel(const float* 
         }
     }
     const float inv = 1.0f / (l_run + __shfl_xor(l_run, 32));
-    if (q_row >= M) return;
-    float* orow = out + ((size_t)b * M + q_row) * ((size_t)H * 64) + (size_t)h * 64;
+    float* orow = out + ((size_t)b * M_max + q_row) * ((size_t)H * 64) + (size_t)h * 64;
+    if (q_row >= M) {
+        if (RAGGED && q_row < M_max) attention_zero_row(orow, half);
+        return;
+    }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         f32x4 a, c;
@@ -312,7 +388,18 @@ int launch_softmax_attention(const float* qkv, int B, int M, int H, float* out, 
     DSH_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)out % 16) == 0, "softmax attention: operands must be 16-byte aligned");
     const int q_tiles = ceil_div(M, 32);
     DSH_REQUIRE((long long)B * H * q_tiles < (1ll << 31), "softmax attention: batch too large");
-    hipLaunchKernelGGL(softmax_attention_f32_kernel, dim3((unsigned)(B * H * q_tiles)), dim3(64), 0, s, qkv, M, H, out, q_tiles);
+    hipLaunchKernelGGL(softmax_attention_f32_kernel<false>, dim3((unsigned)(B * H * q_tiles)), dim3(64), 0, s, qkv, M, H, (const int*)nullptr, out, q_tiles);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_softmax_attention_ragged(const float* qkv, int B, int M_max, int H, const int* lens, float* out, hipStream_t s) {
+    DSH_REQUIRE(qkv && out && lens, "softmax attention (ragged): null pointer");
+    DSH_REQUIRE(B >= 1 && M_max >= 1 && H >= 1, "softmax attention (ragged): B, M_max and H must be positive");
+    DSH_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)out % 16) == 0, "softmax attention (ragged): operands must be 16-byte aligned");
+    const int q_tiles = ceil_div(M_max, 32);
+    DSH_REQUIRE((long long)B * H * q_tiles < (1ll << 31), "softmax attention (ragged): batch too large");
+    hipLaunchKernelGGL(softmax_attention_f32_kernel<true>, dim3((unsigned)(B * H * q_tiles)), dim3(64), 0, s, qkv, M_max, H, lens, out, q_tiles);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -934,6 +934,13 @@ int dsh_interp_time(void* hip_stream, const float* x, int32_t batch, int32_t fra
     API_END
 }
 
+int dsh_interp_time_ragged(void* hip_stream, const float* x, int32_t batch, int32_t frames_in, int32_t channels, float* y, int32_t frames_out,
+                           const int32_t* lens_in_dev, const int32_t* lens_out_dev) {
+    API_BEGIN
+    return dsh::launch_interp_time_ragged(x, batch, frames_in, channels, y, frames_out, lens_in_dev, lens_out_dev, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
 int dsh_inv_standardize(void* hip_stream, const float* x, int64_t n, int32_t channels, const float* mean, const float* stdv,
                         float* y) {
     API_BEGIN
@@ -1483,12 +1490,33 @@ int dsh_mel_compute(dsh_mel* h, const float* wave, int32_t batch, int64_t len, f
     API_END
 }
 
+int dsh_mel_compute_ragged(dsh_mel* h, const float* wave, int32_t batch, int64_t len, const int32_t* lens_dev, float* mel) {
+    API_BEGIN
+    DSH_REQUIRE(h, "null handle");
+    return h->m->compute_ragged(wave, batch, len, lens_dev, mel);
+    API_END
+}
+
 int64_t dsh_resample_poly_len(int64_t n, int32_t up, int32_t down) { return n >= 0 && up > 0 && down > 0 ? dsh::resample_poly_len(n, up, down) : -1; }
 
 int dsh_op_resample_poly(void* hip_stream, const float* x, int32_t batch, int64_t n, int32_t up, int32_t down, const float* taps_dev, int32_t n_taps,
                          float* y) {
     API_BEGIN
     return dsh::launch_resample_poly(x, batch, n, up, down, taps_dev, n_taps, y, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_resample_poly_ragged(void* hip_stream, const float* x, int32_t batch, int64_t n, const int32_t* lens_dev, int32_t up, int32_t down,
+                                const float* taps_dev, int32_t n_taps, float* y) {
+    API_BEGIN
+    DSH_REQUIRE(lens_dev, "dsh_op_resample_poly_ragged: null lengths");
+    return dsh::launch_resample_poly_ragged(x, batch, n, lens_dev, up, down, taps_dev, n_taps, y, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_softmax_attention_ragged(void* hip_stream, const float* qkv, int32_t B, int32_t M_max, int32_t H, const int32_t* lens_dev, float* out) {
+    API_BEGIN
+    return dsh::launch_softmax_attention_ragged(qkv, B, M_max, H, lens_dev, out, reinterpret_cast<hipStream_t>(hip_stream));
     API_END
 }
 
@@ -1560,6 +1588,21 @@ int dsh_hubert_encode(dsh_hubert* h, const float* x, int32_t batch, int64_t n, f
     API_BEGIN
     DSH_REQUIRE(h, "null handle");
     return h->enc->encode(x, batch, n, out);
+    API_END
+}
+
+int dsh_hubert_encode_ragged(dsh_hubert* h, const float* x, int32_t batch, int64_t n_max, const int64_t* lens_samples, float* out) {
+    API_BEGIN
+    DSH_REQUIRE(h, "null handle");
+    return h->enc->encode_ragged(x, batch, n_max, lens_samples, out);
+    API_END
+}
+
+int dsh_op_pos_conv_ragged(void* hip_stream, const float* h, int32_t B, int32_t M_max, int32_t hidden, int32_t groups, int32_t pos_kernel,
+                           const float* W, const float* bias, const int32_t* lens_dev, float* out) {
+    API_BEGIN
+    DSH_REQUIRE(lens_dev, "dsh_op_pos_conv_ragged: null lengths");
+    return dsh::launch_pos_conv(h, B, M_max, hidden, groups, pos_kernel, W, bias, out, reinterpret_cast<hipStream_t>(hip_stream), lens_dev);
     API_END
 }
 

@@ -178,6 +178,8 @@ int launch_tile_rows_hilo(const float* src, int ld, int M, int w, void* hi, void
 int launch_untile_rows_hilo(const void* hi, const void* lo, int Wd, int M, int w, float* dst, int ld, hipStream_t s);
 
 int launch_interp_time(const float* x, int B, int Tin, int C, float* y, int Tout, hipStream_t s);
+// per-row frame counts on both sides (DEVICE int32 [B]): row b = the dense call on (lens_in[b], lens_out[b]), 0 behind lens_out[b]
+int launch_interp_time_ragged(const float* x, int B, int Tin, int C, float* y, int Tout, const int* lens_in, const int* lens_out, hipStream_t s);
 int launch_affine_cols(const float* x, size_t n, int C, const float* mean, const float* stdv, float* y, hipStream_t s);
 // BEAT results tail (rotation.hip): standardised axis-angle <-> standardised Euler 'XYZ' degrees per joint triple, rows addressed by a stride
 // (elements), optional per-clip lengths (device int32, `frames` rows per clip: rows behind a clip's length are written as zeros)

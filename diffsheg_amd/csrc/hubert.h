@@ -20,10 +20,15 @@ struct HubertConfig {
 
 // h_out[b, t, o] = h[b, t, o] + GELU(bias[o] + sum_{tap, i} W[o, tap cg + i] h[b, t + tap - pk / 2, g cg + i]),  g = o / cg: the grouped
 // positional convolution (padding pk / 2, last output frame dropped, pk even) as one implicit GEMM per group; frames outside [0, M) are
-// staged as zeros and never loaded.  h_out must not alias h.
-int launch_pos_conv(const float* h, int B, int M, int hidden, int groups, int pk, const float* W, const float* bias, float* h_out, hipStream_t s);
+// staged as zeros and never loaded.  h_out must not alias h.  lens (DEVICE int32 [B], nullable): row b owns lens[b] of its M frames (clamped to
+// [0, M]); the frames behind count as zeros too and are never loaded, h_out is 0 there: row b has the bits of the dense call on it alone at
+// M = lens[b].
+int launch_pos_conv(const float* h, int B, int M, int hidden, int groups, int pk, const float* W, const float* bias, float* h_out, hipStream_t s,
+                    const int* lens = nullptr);
 // y[row] = act(LayerNorm(x[row]) gamma + beta) over C <= 1024 channels (two-pass moments), in place allowed; gelu = 1: erf-GELU behind it
-int launch_ln_act_rows(const float* x, long long rows, int C, const float* gamma, const float* beta, float eps, int gelu, float* y, hipStream_t s);
+// lens (DEVICE int32, nullable) with M: the rows are [rows / M, M] frames and frame t >= lens[b] is written as 0 without being read
+int launch_ln_act_rows(const float* x, long long rows, int C, const float* gamma, const float* beta, float eps, int gelu, float* y, hipStream_t s,
+                       const int* lens = nullptr, int M = 1);
 // first feature-extractor layer: Conv1d(1, C, k, stride s, bias) -> LayerNorm(C) -> GELU, x [B, n] -> y [B, L, C] channels-last
 int launch_conv0_ln_gelu(const float* x, int B, long long n, int L, int C, int k, int s, const float* W, const float* bias, const float* gamma,
                          const float* beta, float* y, hipStream_t st);
@@ -40,6 +45,10 @@ public:
     int receptive_field() const;
     void set_chunk_pass(int p) { pass_ = p < 1 ? 1 : p; }
     int encode(const float* x, int B, long long n, float* out);
+    // x [B, n_max] of which row b owns lens_samples[b] samples (HOST array): out [B, num_frames(n_max), hidden], row b bit for bit encode() of
+    // its own samples alone, 0 behind its num_frames(lens_samples[b]) frames, whatever the samples behind hold.  -1 (nothing launched) for a
+    // row shorter than the receptive field or longer than n_max.  Uploads the B frame counts once, which waits for the stream.
+    int encode_ragged(const float* x, int B, long long n_max, const int64_t* lens_samples, float* out);
     // host only: one Linear / convolution as finalize() uploads it.  dims2 = {N, K}; W [N, K], bias [N], fc [N] (row sums of the folded
     // weight; zeros for the kinds without a folded LayerNorm); all nullable
     int debug_packed(int kind, int layer, int32_t* dims2, float* W, float* bias, float* fc) const;
@@ -51,6 +60,7 @@ private:
     int upload(int kind, int layer, Lin* out);
     int upload_ln(const std::string& key, int n, Vec* out);
     int reserve(int B, long long n);
+    int run(const char* what, const float* x, int B, long long n, const int64_t* lens_samples, float* out);
     void release_buffers();
     const std::vector<float>& T(const std::string& k) const { return staged_.at(k).data; }
     HubertConfig cfg_;
@@ -66,6 +76,9 @@ private:
     std::vector<float*> owned_;                   // every weight allocation
     float *act_a_ = nullptr, *act_b_ = nullptr, *feat_ = nullptr, *h_ = nullptr, *h2_ = nullptr, *qkv_ = nullptr, *att_ = nullptr, *ffn_ = nullptr;
     long long cap_act_ = 0, cap_rows_ = 0;
+    std::vector<int32_t> lens_host_;              // frame counts of the rows of an encode_ragged call, and their device copy
+    int32_t* lens_dev_ = nullptr;
+    int cap_lens_ = 0;
 };
 
 }  // namespace dsh

@@ -64,11 +64,17 @@ __device__ __forceinline__ void hb_ln_store(const float (&v)[HB_PER_LANE], int l
 }
 
 // (x and y may be the same rows: a wave has read its whole row before it stores any of it)
+// lens (nullable): the rows are [B, M] frames and frame t >= lens[b] is written as 0 without being read.
 __global__ __launch_bounds__(256) void ln_act_rows_kernel(const float* x, long long rows, int C, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, float eps, int gelu, float* y) {
+                                                          const float* __restrict__ beta, float eps, int gelu, float* y,
+                                                          const int* __restrict__ lens, int M) {
     const long long row = (long long)blockIdx.x * HB_ROWS_PER_BLOCK + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
+    if (lens && row % M >= lens[row / M]) {
+        for (int c = lane; c < C; c += 64) y[row * C + c] = 0.f;
+        return;
+    }
     const float* xr = x + row * C;
     float v[HB_PER_LANE];
 #pragma unroll
@@ -79,11 +85,13 @@ __global__ __launch_bounds__(256) void ln_act_rows_kernel(const float* x, long l
     hb_ln_store(v, lane, C, gamma, beta, eps, gelu, y + row * C);
 }
 
-int launch_ln_act_rows(const float* x, long long rows, int C, const float* gamma, const float* beta, float eps, int gelu, float* y, hipStream_t s) {
+int launch_ln_act_rows(const float* x, long long rows, int C, const float* gamma, const float* beta, float eps, int gelu, float* y, hipStream_t s,
+                       const int* lens, int M) {
     DSH_REQUIRE(x && y && gamma && beta && rows > 0 && C > 0 && C <= 64 * HB_PER_LANE, "ln_act_rows: rows of 1 .. 1024 channels");
     DSH_REQUIRE((rows + HB_ROWS_PER_BLOCK - 1) / HB_ROWS_PER_BLOCK < (1ll << 31), "ln_act_rows: too many rows");
+    DSH_REQUIRE(!lens || (M >= 1 && rows % M == 0), "ln_act_rows: ragged rows are [B, M] frames");
     hipLaunchKernelGGL(ln_act_rows_kernel, dim3((unsigned)((rows + HB_ROWS_PER_BLOCK - 1) / HB_ROWS_PER_BLOCK)), dim3(256), 0, s, x, rows, C, gamma,
-                       beta, eps, gelu, y);
+                       beta, eps, gelu, y, lens, M);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -132,9 +140,12 @@ int launch_conv0_ln_gelu(const float* x, int B, long long n, int L, int C, int k
 //   h[b, t + tap - pk / 2, g cg + c0 .. c0 + 32],  tap = 32 kt / cg, c0 = 32 kt % cg,
 // loaded only when that frame is inside [0, M): outside it zeros are staged (the convolution's zero padding; 0 x NaN would be NaN, and the
 // frames next to a clip belong to its neighbours or to nobody).  blockIdx.y = group.
+// Ragged (lens != nullptr): batch row b owns lens[b] (clamped to [0, M]) of its M frames; the frames behind are staged as zeros in the same
+// way, which is all the dense launch at M = lens[b] does differently, and the outputs behind are 0 (their h is not read either).
 struct PosConvArgs {
     const float* H; float* Y; const float* W; const float* bias;
     int rows, M, hidden, cg, pk, nt_m;
+    const int* lens;
 };
 constexpr int PC_LDS_ROW = 144;
 constexpr int PC_LDS = 2 * 2 * 64 * PC_LDS_ROW;
@@ -152,7 +163,7 @@ __global__ __launch_bounds__(256) void pos_conv_gemm_f32_kernel(PosConvArgs p) {
 
     const float* a_src[NP];
     const float* w_src[NP];
-    int a_t[NP], lds_off[NP];
+    int a_t[NP], a_end[NP], lds_off[NP];
     const int c16 = tid & 7;
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
@@ -161,6 +172,8 @@ __global__ __launch_bounds__(256) void pos_conv_gemm_f32_kernel(PosConvArgs p) {
         const int b = ra / p.M, t = ra - b * p.M;
         a_src[i] = p.H + (size_t)b * p.M * p.hidden + (size_t)g * p.cg + c16 * 4;
         a_t[i] = t - half;
+        a_end[i] = p.M;
+        if (p.lens) { const int own = p.lens[b]; a_end[i] = own < 0 ? 0 : (own > p.M ? p.M : own); }
         int rw = n0 + row; rw = rw < p.cg ? rw : p.cg - 1;
         w_src[i] = p.W + ((size_t)g * p.cg + rw) * K + c16 * 4;
         lds_off[i] = row * PC_LDS_ROW + c16 * 16;
@@ -176,7 +189,7 @@ __global__ __launch_bounds__(256) void pos_conv_gemm_f32_kernel(PosConvArgs p) {
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
             const int f = a_t[i] + tap;
-            ra[i] = (f >= 0 && f < p.M) ? *reinterpret_cast<const u32x4*>(a_src[i] + (size_t)f * p.hidden + c0) : zero4;
+            ra[i] = (f >= 0 && f < a_end[i]) ? *reinterpret_cast<const u32x4*>(a_src[i] + (size_t)f * p.hidden + c0) : zero4;
             rw[i] = *reinterpret_cast<const u32x4*>(w_src[i] + koff);
         }
     };
@@ -226,10 +239,12 @@ __global__ __launch_bounds__(256) void pos_conv_gemm_f32_kernel(PosConvArgs p) {
     const int row = m0 + wm * 32 + (lane & 31);
     if (row >= p.rows) return;
     const size_t base = (size_t)row * p.hidden + (size_t)g * p.cg;
+    const bool behind = p.lens && row % p.M >= p.lens[row / p.M];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int col = n0 + wn * 32 + 8 * q + 4 * (lane >> 5);
         if (col >= p.cg) continue;
+        if (behind) { *reinterpret_cast<f32x4*>(p.Y + base + col) = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; continue; }
         const f32x4 b4 = *reinterpret_cast<const f32x4*>(p.bias + g * p.cg + col);
         const f32x4 h4 = *reinterpret_cast<const f32x4*>(p.H + base + col);
         f32x4 o4;
@@ -241,7 +256,8 @@ __global__ __launch_bounds__(256) void pos_conv_gemm_f32_kernel(PosConvArgs p) {
     }
 }
 
-int launch_pos_conv(const float* h, int B, int M, int hidden, int groups, int pk, const float* W, const float* bias, float* h_out, hipStream_t s) {
+int launch_pos_conv(const float* h, int B, int M, int hidden, int groups, int pk, const float* W, const float* bias, float* h_out, hipStream_t s,
+                    const int* lens) {
     DSH_REQUIRE(h && W && bias && h_out && h != h_out, "pos conv: null or aliased tensors");
     DSH_REQUIRE(B >= 1 && M >= 1 && groups >= 1 && hidden % groups == 0 && (hidden / groups) % 32 == 0, "pos conv: channels per group must be a multiple of 32");
     DSH_REQUIRE(pk >= 2 && pk % 2 == 0, "pos conv: the kernel width must be even");
@@ -252,7 +268,7 @@ int launch_pos_conv(const float* h, int B, int M, int hidden, int groups, int pk
         DSH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pos_conv_gemm_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PC_LDS));
         attr = true;
     }
-    PosConvArgs a{h, h_out, W, bias, B * M, M, hidden, hidden / groups, pk, ceil_div(B * M, 64)};
+    PosConvArgs a{h, h_out, W, bias, B * M, M, hidden, hidden / groups, pk, ceil_div(B * M, 64), lens};
     const int nt_n = ceil_div(a.cg, 64);
     hipLaunchKernelGGL(pos_conv_gemm_f32_kernel, dim3((unsigned)(a.nt_m * nt_n), (unsigned)groups), dim3(256), PC_LDS, s, a);
     DSH_HIP_CHECK(hipGetLastError());
@@ -311,6 +327,7 @@ HubertEncoder::~HubertEncoder() {
     if (stream_ && finalized_) (void)hipStreamSynchronize(stream_);
     release_buffers();
     for (float* p : owned_) (void)hipFree(p);
+    if (lens_dev_) (void)hipFree(lens_dev_);
     if (owns_stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -545,18 +562,61 @@ int HubertEncoder::reserve(int B, long long n) {
     return 0;
 }
 
-int HubertEncoder::encode(const float* x, int B, long long n, float* out) {
-    DSH_REQUIRE(finalized_, "dsh_hubert_encode: call dsh_hubert_finalize first");
-    DSH_REQUIRE(x && out, "dsh_hubert_encode: null tensor");
-    DSH_REQUIRE(B >= 1, "dsh_hubert_encode: batch must be positive");
+int HubertEncoder::encode(const float* x, int B, long long n, float* out) { return run("dsh_hubert_encode", x, B, n, nullptr, out); }
+
+// Rows padded to n_max samples, row b owning lens_samples[b] (HOST).  What couples the frames of an utterance is the positional convolution and
+// the attention; both get the row's frame count num_frames(lens_samples[b]), and so does the last LayerNorm, which writes the zeros.  The
+// convolution stack needs none: it is a valid convolution, so frame t < num_frames(n_b) of every layer is computed from samples < n_b alone,
+// from the same values in the same order as in a row of n_b samples, and the Linears are per frame.  The frames behind hold whatever the padding
+// gives (NaN included) until the positional convolution, which never loads them and leaves zeros.
+int HubertEncoder::encode_ragged(const float* x, int B, long long n_max, const int64_t* lens_samples, float* out) {
+    DSH_REQUIRE(lens_samples, "dsh_hubert_encode_ragged: null lengths");
+    return run("dsh_hubert_encode_ragged", x, B, n_max, lens_samples, out);
+}
+
+int HubertEncoder::run(const char* what_c, const float* x, int B, long long n, const int64_t* lens_samples, float* out) {
+    const std::string what(what_c);
+    DSH_REQUIRE(finalized_, what + ": call dsh_hubert_finalize first");
+    DSH_REQUIRE(x && out, what + ": null tensor");
+    DSH_REQUIRE(B >= 1, what + ": batch must be positive");
     const long long M = num_frames(n);
     if (M < 1) {
-        set_last_error("invalid argument: dsh_hubert_encode: " + std::to_string(n) + " samples are shorter than the receptive field " +
+        set_last_error("invalid argument: " + what + ": " + std::to_string(n) + " samples are shorter than the receptive field " +
                        std::to_string(receptive_field()));
         return -1;
     }
-    DSH_REQUIRE(n < (1ll << 31) && (long long)B * n < (1ll << 31) * 16 && (long long)B * M < (1ll << 24), "dsh_hubert_encode: batch too large");
-    DSH_REQUIRE(((uintptr_t)out % 16) == 0, "dsh_hubert_encode: the output must be 16-byte aligned");
+    DSH_REQUIRE(n < (1ll << 31) && (long long)B * n < (1ll << 31) * 16 && (long long)B * M < (1ll << 24), what + ": batch too large");
+    DSH_REQUIRE(((uintptr_t)out % 16) == 0, what + ": the output must be 16-byte aligned");
+    const int* lens = nullptr;
+    if (lens_samples) {
+        lens_host_.resize(B);
+        for (int b = 0; b < B; ++b) {
+            const long long nb = lens_samples[b], mb = nb <= n ? num_frames(nb) : -1;
+            if (nb > n) {
+                set_last_error("invalid argument: " + what + ": row " + std::to_string(b) + " has " + std::to_string(nb) + " samples in rows of " +
+                               std::to_string(n));
+                return -1;
+            }
+            if (mb < 1) {
+                set_last_error("invalid argument: " + what + ": row " + std::to_string(b) + ": " + std::to_string(nb) +
+                               " samples are shorter than the receptive field " + std::to_string(receptive_field()));
+                return -1;
+            }
+            lens_host_[b] = (int32_t)mb;
+        }
+        if (B > cap_lens_) {
+            DSH_HIP_CHECK(hipStreamSynchronize(stream_));
+            if (lens_dev_) (void)hipFree(lens_dev_);
+            lens_dev_ = nullptr; cap_lens_ = 0;
+            DSH_HIP_CHECK(hipMalloc((void**)&lens_dev_, (size_t)B * sizeof(int32_t)));
+            cap_lens_ = B;
+        }
+        // one upload per call, in stream order behind the launches of an earlier call that still read the array; the wait lets the next call
+        // reuse the host copy
+        DSH_HIP_CHECK(hipMemcpyAsync(lens_dev_, lens_host_.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+        DSH_HIP_CHECK(hipStreamSynchronize(stream_));
+        lens = lens_dev_;
+    }
     if (int e = reserve(B, n)) return e;
     const HubertConfig& c = cfg_;
     long long L[8];
@@ -598,18 +658,19 @@ int HubertEncoder::encode(const float* x, int B, long long n, float* out) {
     // 3. feature projection (LayerNorm folded)
     if (int e = linear(1, feat_, c.conv_dim[6], feat_proj_, ACT_NONE, nullptr, h2_)) return e;
     // 4. positional convolution: h_ = h2_ + GELU(posconv(h2_))
-    if (int e = launch_pos_conv(h2_, B, (int)M, c.hidden, c.pos_groups, c.pos_kernel, pos_conv_.W, pos_conv_.b, h_, stream_)) return e;
+    if (int e = launch_pos_conv(h2_, B, (int)M, c.hidden, c.pos_groups, c.pos_kernel, pos_conv_.W, pos_conv_.b, h_, stream_, lens)) return e;
     // 5. the layers
     for (int l = 0; l < c.layers; ++l) {
         const Layer& ly = layer_[l];
         if (int e = linear(1, h_, c.hidden, ly.qkv, ACT_NONE, nullptr, qkv_)) return e;
-        if (int e = launch_softmax_attention(qkv_, B, (int)M, c.heads, att_, stream_)) return e;
+        if (int e = lens ? launch_softmax_attention_ragged(qkv_, B, (int)M, c.heads, lens, att_, stream_)
+                         : launch_softmax_attention(qkv_, B, (int)M, c.heads, att_, stream_)) return e;
         if (int e = linear(0, att_, c.hidden, ly.out, ACT_NONE, h_, h_)) return e;
         if (int e = linear(1, h_, c.hidden, ly.ffn_in, ACT_GELU, nullptr, ffn_)) return e;
         if (int e = linear(0, ffn_, c.intermediate, ly.ffn_out, ACT_NONE, h_, h_)) return e;
     }
     // 6. final LayerNorm
-    return launch_ln_act_rows(h_, R, c.hidden, final_ln_.g, final_ln_.b, c.ln_eps, 0, out, stream_);
+    return launch_ln_act_rows(h_, R, c.hidden, final_ln_.g, final_ln_.b, c.ln_eps, 0, out, stream_, lens, (int)M);
 }
 
 }  // namespace dsh

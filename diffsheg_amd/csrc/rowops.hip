@@ -676,9 +676,8 @@ int launch_untile_rows_hilo(const void* hi, const void* lo, int Wd, int M, int w
 //   affine_cols   inv_standardize: y = x * std[c] + mean[c]          (datasets/show.py:157-162)
 namespace dsh {
 
-__global__ void interp_time_kernel(const float* x, int B, int Tin, int C, float* y, int Tout) {
-    const int row = blockIdx.x;                 // b * Tout + t
-    const int b = row / Tout, t = row % Tout;
+// output frame t of Tout from the Tin frames at xb
+__device__ __forceinline__ void interp_time_row(const float* xb, int Tin, int C, float* yr, int t, int Tout) {
     // align_corners=True: src = t * (Tin - 1) / (Tout - 1); Tout == 1 samples frame 0 (ATen area_pixel_compute_scale)
     const float scale = Tout > 1 ? (float)(Tin - 1) / (float)(Tout - 1) : 0.0f;
     const float src = scale * (float)t;
@@ -686,15 +685,43 @@ __global__ void interp_time_kernel(const float* x, int B, int Tin, int C, float*
     if (i0 > Tin - 1) i0 = Tin - 1;
     const int i1 = i0 + (i0 < Tin - 1 ? 1 : 0);
     const float w1 = src - (float)i0, w0 = 1.0f - w1;
-    const float* x0 = x + ((size_t)b * Tin + i0) * C;
-    const float* x1 = x + ((size_t)b * Tin + i1) * C;
-    float* yr = y + (size_t)row * C;
+    const float* x0 = xb + (size_t)i0 * C;
+    const float* x1 = xb + (size_t)i1 * C;
     for (int c = threadIdx.x; c < C; c += blockDim.x) yr[c] = w0 * x0[c] + w1 * x1[c];
+}
+
+__global__ void interp_time_kernel(const float* x, int B, int Tin, int C, float* y, int Tout) {
+    const int row = blockIdx.x;                 // b * Tout + t
+    const int b = row / Tout, t = row % Tout;
+    interp_time_row(x + (size_t)b * Tin * C, Tin, C, y + (size_t)row * C, t, Tout);
+}
+
+// x [B, Tin, C] -> y [B, Tout, C] with a frame count of its own per row on both sides (clamped to the padded sizes): row b is the dense kernel on
+// (lens_in[b], lens_out[b]); frames t >= lens_out[b] are 0, and so is a row without input frames.  No frame >= lens_in[b] is read.
+__global__ void interp_time_ragged_kernel(const float* x, int B, int Tin, int C, float* y, int Tout, const int* __restrict__ lens_in,
+                                          const int* __restrict__ lens_out) {
+    const int row = blockIdx.x;
+    const int b = row / Tout, t = row % Tout;
+    const int tin = min(lens_in[b], Tin), tout = min(lens_out[b], Tout);
+    float* yr = y + (size_t)row * C;
+    if (t >= tout || tin < 1) {
+        for (int c = threadIdx.x; c < C; c += blockDim.x) yr[c] = 0.0f;
+        return;
+    }
+    interp_time_row(x + (size_t)b * Tin * C, tin, C, yr, t, tout);
 }
 
 int launch_interp_time(const float* x, int B, int Tin, int C, float* y, int Tout, hipStream_t s) {
     DSH_REQUIRE(B > 0 && Tin > 0 && Tout > 0 && C > 0, "interp_time: dims must be positive");
     hipLaunchKernelGGL(interp_time_kernel, dim3(B * Tout), dim3(256), 0, s, x, B, Tin, C, y, Tout);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_interp_time_ragged(const float* x, int B, int Tin, int C, float* y, int Tout, const int* lens_in, const int* lens_out, hipStream_t s) {
+    DSH_REQUIRE(x && y && lens_in && lens_out, "interp_time (ragged): null pointer");
+    DSH_REQUIRE(B > 0 && Tin > 0 && Tout > 0 && C > 0 && (long long)B * Tout < (1ll << 31), "interp_time (ragged): dims must be positive");
+    hipLaunchKernelGGL(interp_time_ragged_kernel, dim3(B * Tout), dim3(256), 0, s, x, B, Tin, C, y, Tout, lens_in, lens_out);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }

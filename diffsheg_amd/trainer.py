@@ -475,10 +475,7 @@ class DDPMTrainer:
         hands HuBERT the 22 050 Hz signal of ``librosa.load`` as if it were 16 kHz; this call takes a 16 kHz signal, the ``.npy``
         branch and what the model was trained on."""
         if isinstance(wave16k, (list, tuple)):
-            feats = [frontend.features(w) for w in wave16k]
-            lengths = [int(m.shape[0]) for m, _ in feats]
-            mel = torch.nn.utils.rnn.pad_sequence([m for m, _ in feats], batch_first=True)
-            hub = torch.nn.utils.rnn.pad_sequence([h for _, h in feats], batch_first=True)
+            mel, hub, lengths = frontend.features_batch(wave16k)
             return self.sample_arbitrary_len(mel, p_id, {"pretrain_aud_feat": hub}, lengths=lengths, **kw)
         mel, hub = frontend.features(wave16k)
         return self.sample_arbitrary_len(mel[None], p_id, {"pretrain_aud_feat": hub[None]}, **kw)

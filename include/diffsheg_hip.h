@@ -275,6 +275,11 @@ int32_t dsh_jump_schedule(int32_t respacing, int32_t jump_length, int32_t jump_n
  * HuBERT hidden states resampled to the pose frame rate (datasets/show.py:98, ddpm_show_trainer.py:1082). */
 int dsh_interp_time(void* hip_stream, const float* x, int32_t batch, int32_t frames_in, int32_t channels, float* y,
                     int32_t frames_out);
+/* The same for a batch whose rows have frame counts of their own on both sides (DEVICE int32 [batch], clamped to frames_in / frames_out, the
+ * padded sizes): row b is dsh_interp_time of its first lens_in[b] frames to lens_out[b] frames, bit for bit; y[b, t >= lens_out[b]] = 0.  No
+ * frame >= lens_in[b] is read. */
+int dsh_interp_time_ragged(void* hip_stream, const float* x, int32_t batch, int32_t frames_in, int32_t channels, float* y, int32_t frames_out,
+                           const int32_t* lens_in_dev, const int32_t* lens_out_dev);
 /* y = x * std[c] + mean[c] over n contiguous fp32 values with `channels` innermost (datasets/show.py:157-162). */
 int dsh_inv_standardize(void* hip_stream, const float* x, int64_t n, int32_t channels, const float* mean, const float* stdv,
                         float* y);
@@ -606,6 +611,12 @@ int dsh_mel_debug_tables(const dsh_mel* h, int32_t* dims3, float* dft, float* fb
  * summation order; a row's result does not depend on B; a silent input gives exact zeros.  -1 (nothing launched) when dsh_mel_num_frames
  * is -1, on a null pointer or B < 1.  A larger B x len than any before grows the handle's buffers, which waits for the stream once. */
 int dsh_mel_compute(dsh_mel* h, const float* wave, int32_t batch, int64_t len, float* mel);
+/* Utterances of different lengths in one call: wave [B, len] padded, row b owning lens_dev[b] samples (DEVICE int32 [B]; the caller has checked
+ * dsh_mel_num_frames(lens[b]) >= 1 and lens[b] <= len: a count outside gives a row of zeros).  mel [B, dsh_mel_num_frames(len), n_mels]; its
+ * frames j < lens[b] / hop are bit for bit what dsh_mel_compute gives for row b alone at len = lens[b] (the reflection is about the row's own last
+ * sample; the GEMMs run on the padded rows), the frames behind are 0.  No sample behind lens[b] is read, so the padding may hold anything.  One
+ * launch more than the dense call.  -1 as dsh_mel_compute, and on null lengths. */
+int dsh_mel_compute_ragged(dsh_mel* h, const float* wave, int32_t batch, int64_t len, const int32_t* lens_dev, float* mel);
 
 /* scipy.signal.resample_poly(x, up, down, window = taps / up) for caller-supplied FIR taps (an odd number, gain included, DEVICE fp32):
  * zero-stuff by up, filter, decimate by down, the taps centred, zeros outside the signal:
@@ -616,11 +627,22 @@ int64_t dsh_resample_poly_len(int64_t n, int32_t up, int32_t down);
 int dsh_op_resample_poly(void* hip_stream, const float* x, int32_t batch, int64_t n, int32_t up, int32_t down, const float* taps_dev, int32_t n_taps,
                          float* y);
 
+/* x [B, n] padded, row b owning lens_dev[b] samples (DEVICE int32 [B], clamped to [0, n]): y [B, dsh_resample_poly_len(n)], row b what
+ * dsh_op_resample_poly gives for its own samples alone (the taps at the right edge see nothing behind lens[b]), 0 behind
+ * dsh_resample_poly_len(lens[b]).  No sample behind lens[b] is read. */
+int dsh_op_resample_poly_ragged(void* hip_stream, const float* x, int32_t batch, int64_t n, const int32_t* lens_dev, int32_t up, int32_t down,
+                                const float* taps_dev, int32_t n_taps, float* y);
+
 /* Softmax multi-head attention core with 64-wide heads and no mask, fp32 on the exact-fp32 matrix pipe:
  *   out[b, t, 64 h + d] = sum_s softmax_s(q[b, t, h] . k[b, s, h]) v[b, s, 64 h + d],   qkv [B, M, 3 H 64] = (q | k | v) per row, q already
  * scaled; out [B, M, H 64]; both device fp32, 16-byte aligned.  One wave per (b, h, 32 queries), keys in tiles of 32 with an online maximum
  * and sum (logits of any size), keys >= M of the last tile weigh exactly 0.  Fixed order: row b does not depend on B. */
 int dsh_op_softmax_attention(void* hip_stream, const float* qkv, int32_t B, int32_t M, int32_t H, float* out);
+/* The same kernel body for rows of M_max frames of which row b owns lens_dev[b] (DEVICE int32 [B], clamped to [0, M_max]): queries and keys
+ * < lens[b] only, the loads, products and exponentials of the dense call on row b alone at M = lens[b] in the same order, hence the same bits;
+ * out[b, t >= lens[b]] = 0.  No frame >= lens[b] is read (a NaN there would survive a zero weight); query tiles behind lens[b] do no matrix
+ * work. */
+int dsh_op_softmax_attention_ragged(void* hip_stream, const float* qkv, int32_t B, int32_t M_max, int32_t H, const int32_t* lens_dev, float* out);
 
 /* The HuBERT encoder of the hubert-large family (transformers' HubertModel with feat_extract_norm = "layer", conv_bias = True,
  * do_stable_layer_norm = True, feat_proj_layer_norm = True), fp32 on the exact-fp32 matrix pipe: the `pretrain_aud_feat` test_custom_aud computes
@@ -668,6 +690,13 @@ int dsh_hubert_set_chunk_pass(dsh_hubert* h, int32_t rows);
  * order and there are no atomics: row b has the same bits whatever B and the pass size are.  -1 (nothing launched) when n is shorter than the
  * receptive field, on a null pointer or B < 1.  A larger B x n than any before grows the handle's buffers, which waits for the stream once. */
 int dsh_hubert_encode(dsh_hubert* h, const float* x, int32_t batch, int64_t n, float* out);
+/* Utterances of different lengths in one call: x [B, n_max] padded, row b owning lens_samples[b] samples (HOST int64 [B]).  out [B, M_max, hidden],
+ * M_max = dsh_hubert_num_frames(n_max); frames t < dsh_hubert_num_frames(lens_samples[b]) of row b are bit for bit dsh_hubert_encode of that row
+ * alone at n = lens_samples[b], whatever the samples behind hold (NaN included), the frames behind are 0.  The convolution stack and the Linears
+ * run on the padded rows (a valid convolution's frame t < M_b reads samples < n_b only); the positional convolution, the attention and the last
+ * LayerNorm take the frame counts, uploaded once per call (which waits for the handle's stream).  -1 (nothing launched, out untouched) for a row
+ * shorter than the receptive field, lens_samples[b] > n_max, null lengths, and as dsh_hubert_encode. */
+int dsh_hubert_encode_ragged(dsh_hubert* h, const float* x, int32_t batch, int64_t n_max, const int64_t* lens_samples, float* out);
 /* The encoder's new kernels on row-major operands (op tests).
  * dsh_op_pos_conv: out[b, t, o] = h[b, t, o] + GELU(bias[o] + sum_{tap, i} W[o, tap cg + i] h[b, t + tap - k / 2, g cg + i]), cg = hidden / groups,
  *   g = o / cg: Conv1d(hidden, hidden, k, padding k / 2, groups) with its last output frame dropped (k even); frames outside [0, M) count as
@@ -676,6 +705,10 @@ int dsh_hubert_encode(dsh_hubert* h, const float* x, int32_t batch, int64_t n, f
  * dsh_op_conv_ln_gelu: the same for channels-last x [B, L, Cin] and W [Cout, k Cin] tap-major: implicit GEMM + a LayerNorm / GELU row pass. */
 int dsh_op_pos_conv(void* hip_stream, const float* h, int32_t B, int32_t M, int32_t hidden, int32_t groups, int32_t pos_kernel, const float* W,
                     const float* bias, float* out);
+/* dsh_op_pos_conv with frame counts per batch row (DEVICE int32 [B], clamped to [0, M_max]): frames t >= lens[b] count as zeros like the frames
+ * outside [0, M) and are never loaded; out[b, t >= lens[b]] = 0; row b has the bits of dsh_op_pos_conv on it alone at M = lens[b]. */
+int dsh_op_pos_conv_ragged(void* hip_stream, const float* h, int32_t B, int32_t M_max, int32_t hidden, int32_t groups, int32_t pos_kernel,
+                           const float* W, const float* bias, const int32_t* lens_dev, float* out);
 int dsh_op_conv0_ln_gelu(void* hip_stream, const float* x, int32_t B, int64_t n, int32_t C, int32_t k, int32_t stride, const float* W, const float* bias,
                          const float* gamma, const float* beta, float* y);
 int dsh_op_conv_ln_gelu(void* hip_stream, const float* x, int32_t B, int32_t L, int32_t Cin, int32_t Cout, int32_t k, int32_t stride, const float* W,

@@ -9,9 +9,14 @@
       scaled_dot_product_attention, chunk by chunk as the reference does), and transformers' HubertModel there if it is importable;
   (c) the time of sampling the same stream (sample_arbitrary_len, SHOW, ddim25).
 
-Prints one JSON line per signal length; --out also writes them to a file.
+--folder N adds the folder case: N utterances with durations spread evenly over 2 .. 15 s (in a seeded order), as one call of
+AudioFrontEnd.features_batch (also with min_fill = 0.75: ragged passes of similar lengths) against the per-file loop over
+AudioFrontEnd.features (the path before the batch form existed), and the sampling of the same batch (sample_arbitrary_len(.., lengths=));
+the feature results are compared bit for bit.
 
-Usage:  python scripts/audio_frontend_bench.py [--seconds 60,600] [--repeat 3] [--precision bf16] [--out FILE]
+Prints one JSON line per signal length (and one for the folder); --out also writes them to a file.
+
+Usage:  python scripts/audio_frontend_bench.py [--seconds 60,600] [--folder 32] [--repeat 3] [--precision bf16] [--out FILE]
 """
 from __future__ import annotations
 
@@ -49,9 +54,33 @@ def timed(fn, repeat: int) -> float:
     return sorted(ts)[len(ts) // 2]
 
 
+def folder_case(fe, tr, cfg, count: int, repeat: int, precision: str) -> dict:
+    g = torch.Generator().manual_seed(count)
+    secs = [2.0 + 13.0 * i / max(count - 1, 1) for i in torch.randperm(count, generator=g).tolist()]
+    waves = [(0.1 * torch.randn(int(16000 * s), generator=g)).to(fe.device) for s in secs]
+    loop = lambda: [fe.features(w) for w in waves]
+    mel, hub, lengths = fe.features_batch(waves)
+    same = all(torch.equal(mel[b, :n], m) and torch.equal(hub[b, :n], h) for b, (n, (m, h)) in enumerate(zip(lengths, loop())))
+    pid = make_inputs(cfg, count, frames=cfg.n_poses, seed=3)["person_id"]
+    r = {"folder": count, "seconds_min": min(secs), "seconds_max": max(secs), "seconds_total": sum(secs), "mel_frames_total": sum(lengths),
+         "mel_frames_max": max(lengths), "batch_equals_loop_bitwise": same, "precision_sampler": precision}
+    r["features_batch_ms"] = timed(lambda: fe.features_batch(waves), repeat)
+    # the remainders in ragged passes of similar lengths (every one at least 3 / 4 of the longest of its pass) instead of one
+    mel_g, hub_g, _ = fe.features_batch(waves, min_fill=0.75)
+    r["grouped_passes"] = len(audio.length_groups([w.shape[0] for w in waves], 0.75))
+    r["grouped_equals_batch_bitwise"] = torch.equal(mel_g, mel) and torch.equal(hub_g, hub)
+    r["features_batch_grouped_ms"] = timed(lambda: fe.features_batch(waves, min_fill=0.75), repeat)
+    r["features_loop_ms"] = timed(loop, repeat)
+    r["loop_over_batch"] = r["features_loop_ms"] / r["features_batch_ms"]
+    r["loop_over_batch_grouped"] = r["features_loop_ms"] / r["features_batch_grouped_ms"]
+    r["sampling_ms"] = timed(lambda: tr.sample_arbitrary_len(mel, pid, {"pretrain_aud_feat": hub}, lengths=lengths, seed=1), repeat)
+    return r
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", default="60,600")
+    ap.add_argument("--folder", type=int, default=0)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--out", default=None)
@@ -78,7 +107,7 @@ def main() -> None:
     except Exception as e:          # not installed on this machine
         print(f"# transformers' HubertModel not timed: {type(e).__name__}", file=sys.stderr)
     lines = []
-    for sec in [int(s) for s in args.seconds.split(",")]:
+    for sec in [int(s) for s in args.seconds.split(",") if s]:
         n = 16000 * sec
         wave = (0.1 * torch.randn(n, generator=torch.Generator().manual_seed(sec))).to(dev)
         norm = audio.normalize_wave(wave)
@@ -105,6 +134,10 @@ def main() -> None:
             if hf is not None:
                 r["transformers_fp32_ms"] = timed(lambda: one(lambda c: hf(c).last_hidden_state), args.repeat)
         r["sampling_ms"] = timed(lambda: tr.sample_arbitrary_len(mel[None], pid, {"pretrain_aud_feat": hub[None]}, seed=1), args.repeat)
+        print(json.dumps(r))
+        lines.append(r)
+    if args.folder > 0:
+        r = folder_case(fe, tr, cfg, args.folder, args.repeat, args.precision)
         print(json.dumps(r))
         lines.append(r)
     if args.out:
