@@ -24,7 +24,7 @@ const char* last_error_cstr() { return g_last_error.c_str(); }
 struct dsh_ctx {
     dsh::ModelConfig cfg;
     hipStream_t stream = nullptr;
-    std::unique_ptr<dsh::DenoiserBase> den;
+    std::unique_ptr<dsh::DenoiserContext> den;
     std::unique_ptr<dsh::Sampler> sampler;
     std::map<std::string, dsh::HostTensor> staged;
     dsh::Profiler prof;
@@ -72,7 +72,7 @@ static int set_guidance(dsh_ctx* ctx, const float* scales, int n) {
 
 // per-clip scales must match the batch being evaluated / sampled
 static int check_guidance(const dsh_ctx* ctx) {
-    DSH_REQUIRE(ctx->gs_n <= 1 || ctx->gs_n == ctx->den->batch, "dsh_set_guidance_scale: per-clip scales do not match the batch of set_condition()");
+    DSH_REQUIRE(ctx->gs_n <= 1 || ctx->gs_n == ctx->den->batch(), "dsh_set_guidance_scale: per-clip scales do not match the batch of set_condition()");
     return 0;
 }
 
@@ -119,7 +119,7 @@ int dsh_create(const dsh_model_config* c, void* hip_stream, dsh_ctx** out) {
     ctx->den.reset(dsh::make_denoiser(m, ctx->stream));
     ctx->sampler.reset(new dsh::Sampler(ctx->stream, m.channels()));
     ctx->prof.st = ctx->stream;
-    ctx->den->prof = &ctx->prof;
+    ctx->den->set_profiler(&ctx->prof);
     ctx->sampler->prof = &ctx->prof;
     if (int e = set_guidance(ctx, nullptr, 0)) { dsh_destroy(ctx); return e; }
     *out = ctx;
@@ -168,7 +168,7 @@ int dsh_set_condition(dsh_ctx* ctx, int32_t batch, int32_t frames, const float* 
                       const float* hubert) {
     API_BEGIN
     DSH_REQUIRE(ctx, "null context");
-    return ctx->den->set_condition(batch, frames, audio_emb, person_id, hubert);
+    return ctx->den->set_condition(batch, frames, nullptr, audio_emb, person_id, hubert);
     API_END
 }
 
@@ -176,7 +176,8 @@ int dsh_set_condition_ragged(dsh_ctx* ctx, int32_t batch, int32_t frames_pad, co
                              const float* person_id, const float* hubert) {
     API_BEGIN
     DSH_REQUIRE(ctx, "null context");
-    return ctx->den->set_condition_ragged(batch, frames_pad, lengths_host, audio_emb, person_id, hubert);
+    DSH_REQUIRE(lengths_host, "set_condition_ragged: null lengths");
+    return ctx->den->set_condition(batch, frames_pad, lengths_host, audio_emb, person_id, hubert);
     API_END
 }
 
@@ -187,7 +188,7 @@ int dsh_eval(dsh_ctx* ctx, const float* x, const int64_t* t, const float* c1, co
     // passes, gaussian_diffusion.py:1125): the caller's tensor is checked here, on the host (B x 8 bytes; dsh_sample never comes this way)
     {
         hipStream_t s = reinterpret_cast<hipStream_t>(ctx->stream);
-        const int B = ctx->den->batch;
+        const int B = ctx->den->batch();
         DSH_REQUIRE(B > 0, "set_condition() must precede eval()");
         std::vector<int64_t> th((size_t)B);
         DSH_HIP_CHECK(hipMemcpyAsync(th.data(), t, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -199,10 +200,10 @@ int dsh_eval(dsh_ctx* ctx, const float* x, const int64_t* t, const float* c1, co
     if (int e = check_guidance(ctx)) return e;
     if (int e = ctx->den->eval(x, t, c1, c2, eps)) return e;
     // one modality alone: the inactive encoder's columns of eps are 0 (it was not launched)
-    if (const int mod = ctx->den->modality) {
+    if (const int mod = ctx->den->modality()) {
         const int g = ctx->den->gesture_channels(), Cc = ctx->cfg.channels();
         DSH_REQUIRE(g > 0 && g < Cc && eps, "a partial modality needs the UniDiffuser's two encoders");
-        return dsh::launch_fill_cols(eps, Cc, (size_t)ctx->den->batch * ctx->den->frames, mod == 1 ? 0 : g, mod == 1 ? g : Cc, nullptr, 0, ctx->stream);
+        return dsh::launch_fill_cols(eps, Cc, (size_t)ctx->den->batch() * ctx->den->frames(), mod == 1 ? 0 : g, mod == 1 ? g : Cc, nullptr, 0, ctx->stream);
     }
     return 0;
     API_END

@@ -24,7 +24,7 @@ namespace dsh {
 namespace {
 
 template <typename T>
-class Denoiser final : public DenoiserBase {
+class Denoiser final : public DenoiserInstance {
   public:
     Denoiser(const ModelConfig& c, hipStream_t s) : cfg(c), st(s), gs_dbl(c.classifier_free && c.cond_scale != 1.0f) {
         // (raw inputs: the table of switches.h, read here once per context)
@@ -68,7 +68,7 @@ class Denoiser final : public DenoiserBase {
           aud_film(o.aud_film), aud_stream(o.aud_stream), aud_ap_bias(o.aud_ap_bias), aud_bias(o.aud_bias), aud_film_g(o.aud_film_g), aud_film_b(o.aud_film_b), aud(o.aud), exp_(o.exp_), ges_(o.ges_), sw(o.sw), gs(o.gs), gs_row(o.gs_row), gs_dbl(o.gs_dbl) {
         for (Encoder* E : {&exp_, &ges_}) { E->pid_part = nullptr; E->pid_part_s = nullptr; E->hub = nullptr; E->film_tab = nullptr; E->aproj_buf = nullptr; }
     }
-    DenoiserBase* clone_shared(hipStream_t s) override { return finalized ? new Denoiser(*this, s) : nullptr; }
+    DenoiserInstance* clone_shared(hipStream_t s) override { return finalized ? new Denoiser(*this, s) : nullptr; }
     void notify_after_launches(hipEvent_t ev, int n) override { notify_ev = ev; notify_at = n; }
     ~Denoiser() override {
         for (void* p : allocs) (void)hipFree(p);
@@ -79,9 +79,6 @@ class Denoiser final : public DenoiserBase {
 
     int finalize(const std::map<std::string, HostTensor>& w) override;
     int set_condition(int B, int T_, const float* audio, const float* person_id, const float* hubert) override;
-    int eval(const float* x, const int64_t* t, const float* c1, const float* c2, float* eps) override {
-        return eval_level(x, t, c1, c2, eps, 0, nullptr);
-    }
     // bf16 token-per-lane path: the StylizationBlock launches stage the FiLM rows of every clip a token block touches — at most 4 clips per
     // 32-token block (tl_small.hip) or 6 per 128-token block (tl_linear.hip).  Windows of 11 frames and more fit one of the two at any batch,
     // shorter ones up to 6 clips; 7 and more clips of 10 frames or fewer fit neither.  (fp32 has no such limit: gemm_f32_pro.hip reads the
@@ -97,7 +94,6 @@ class Denoiser final : public DenoiserBase {
     int level_cache_prepare(int n_levels) override;
     int set_condition_light(int B, int T_, const float* audio, const float* person_id) override;
     int set_lengths(const int* lens_dev) override { lens = lens_dev; return 0; }
-    const int* lengths_dev() const override { return lens; }
     int set_part(int p) override {
         DSH_REQUIRE(p >= 0 && p <= 2 && (p == 0 || !cfg.single_transformer), "set_part: 0 whole / 1 expression / 2 gesture (UniDiffuser only)");
         part = p;
@@ -107,15 +103,15 @@ class Denoiser final : public DenoiserBase {
     // into expr_x0 / expr16 on this instance's stream (the prefetch instance, which never evaluates an encoder, is given no track)
     int set_modality(int m, const float* track) override {
         DSH_REQUIRE(m >= 0 && m <= 2 && (m == 0 || !cfg.single_transformer), "set_modality: 0 both / 1 expression / 2 gesture (UniDiffuser only)");
-        if (m == 2 && track) {
+        if (m == PART_GESTURE && track) {
             DSH_REQUIRE(conditioned && expr_x0, "set_condition() must precede set_modality()");
             if (int e = launch_pack_expr_track(track, cfg.expression_dim, batch, frames, lens, expr_x0, expr_ld(), tl_path() ? expr16 : nullptr, st)) return e;
         }
         modality = m;
         return 0;
     }
-    int import_expr(DenoiserBase* src_, hipStream_t s) override {
-        Denoiser<T>* src = dynamic_cast<Denoiser<T>*>(src_);
+    int import_expr(const DenoiserInstance& src_, hipStream_t s) override {
+        const Denoiser<T>* src = dynamic_cast<const Denoiser<T>*>(&src_);
         DSH_REQUIRE(src && src != this && src->batch == batch && src->frames == frames && expr_x0 && src->expr_x0, "import_expr: incompatible instances");
         const size_t Mc = (size_t)batch * frames;
         DSH_HIP_CHECK(hipMemcpyAsync(expr_x0, src->expr_x0, Mc * expr_ld() * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -484,8 +480,9 @@ class Denoiser final : public DenoiserBase {
     char* lvl_slots = nullptr; size_t lvl_stride = 0, lvl_cap = 0; int lvl_n = 0;
     char* lvl_borrowed = nullptr; size_t lvl_borrowed_stride = 0; int lvl_borrowed_n = 0;   // prefetch instance: the main instance's slots
     bool light_cond = false;         // set_condition_light(): no hubert features -> only mode 3 may run
-    int part = 0;                    // 0 whole evaluation / 1 expression encoder only / 2 gesture encoder only (pipelined small-batch loop, denoiser.h)
-    int active() const { return part != 0 ? part : modality; }   // the encoder this evaluation runs: the pipeline's transient part, else the condition's modality
+    int part = PART_BOTH;            // Part: whole evaluation / expression encoder only / gesture encoder only (pipelined small-batch loop, denoiser.h)
+    int modality = PART_BOTH;        // the condition's modality (set_modality); a clone starts joint
+    int active() const { return part != PART_BOTH ? part : modality; }   // the encoder this evaluation runs: the pipeline's transient part, else the condition's modality
     int level_copy(const int64_t* level, int restore);
 };
 
@@ -1182,7 +1179,7 @@ int Denoiser<T>::prep_audio(const int64_t* t) {
         aproj_done = false;
         if (aud_ap_bias && tl_path() && switch_int(SW_APROJ_TL) != 0) {
             // (one modality alone: the active encoder's audio_proj only — encoder e's fragments at + e * 128 KB, its bias at + e * 256)
-            const int me = modality == 2 ? 1 : 0, ne = modality == 0 ? 2 : 1;
+            const int me = modality == PART_GESTURE ? 1 : 0, ne = modality == PART_BOTH ? 2 : 1;
             if (int e = launch_tl_aproj(audio256, aud_stream + (size_t)18 * 16384 + (size_t)me * 65536, aud_ap_bias + me * 256, ne,
                                         me ? ges_.aproj_buf : exp_.aproj_buf, ges_.aproj_buf, Mc, st)) return e;
             flops_acc += ne * 2.0 * Mc * 256.0 * 256.0;
@@ -1231,7 +1228,7 @@ int Denoiser<T>::level_copy(const int64_t* level, int restore) {
     LevelCopyArgs a;
     a.nseg = 0;
     for (size_t i = 0; i < es.size(); ++i) {
-        if (active() != 0 && (int)i != active() - 1) continue;      // (a partial evaluation touches its own encoder's share only; es = {exp, ges})
+        if (active() != PART_BOTH && (int)i != active() - 1) continue;      // (a partial evaluation touches its own encoder's share only; es = {exp, ges})
         a.work[a.nseg] = reinterpret_cast<char*>(es[i]->film_tab); a.bytes[a.nseg] = film; a.off[a.nseg] = i * (film + ap); ++a.nseg;
         a.work[a.nseg] = reinterpret_cast<char*>(es[i]->aproj_buf); a.bytes[a.nseg] = ap; a.off[a.nseg] = i * (film + ap) + film; ++a.nseg;
     }
@@ -1242,24 +1239,24 @@ int Denoiser<T>::level_copy(const int64_t* level, int restore) {
 template <typename T>
 int Denoiser<T>::eval_level(const float* x, const int64_t* t, const float* c1, const float* c2, float* eps, int mode, const int64_t* level) {
     DSH_REQUIRE(conditioned, "set_condition() must precede eval()");
-    DSH_REQUIRE(mode >= 0 && mode <= 3, "eval_level: unknown mode");
-    DSH_REQUIRE(t && (mode == 3 || (x && c1 && c2 && eps)), "null pointer");
-    DSH_REQUIRE(mode == 3 || !light_cond, "this instance only holds the x-independent conditioning (prefetch instance)");
-    DSH_REQUIRE(part == 0 || ((mode == 2 || mode == 0) && !cfg.single_transformer), "a partial evaluation computes (mode 0) or restores (mode 2) its own head");
+    DSH_REQUIRE(mode >= EVAL_PLAIN && mode <= EVAL_HEAD_ONLY, "eval_level: unknown mode");
+    DSH_REQUIRE(t && (mode == EVAL_HEAD_ONLY || (x && c1 && c2 && eps)), "null pointer");
+    DSH_REQUIRE(mode == EVAL_HEAD_ONLY || !light_cond, "this instance only holds the x-independent conditioning (prefetch instance)");
+    DSH_REQUIRE(part == PART_BOTH || ((mode == EVAL_RESTORE || mode == EVAL_PLAIN) && !cfg.single_transformer), "a partial evaluation computes (mode 0) or restores (mode 2) its own head");
     flops_acc = 0;
     tl_launches = 0;
-    if (mode == 3) {
+    if (mode == EVAL_HEAD_ONLY) {
         if (int e = prep_audio(t)) return e;
-        for (Encoder* E : encs()) { if (active() == 0 || E == (active() == 1 ? &exp_ : &ges_)) { if (int e = prep_encoder(*E)) return e; } }
+        for (Encoder* E : encs()) { if (active() == PART_BOTH || E == (active() == PART_EXPRESSION ? &exp_ : &ges_)) { if (int e = prep_encoder(*E)) return e; } }
         return level_copy(level, 0);
     }
-    if (mode == 2) {
+    if (mode == EVAL_RESTORE) {
         if (int e = level_copy(level, 1)) return e;
     } else {
         // (a partial evaluation computes the shared head — timestep embedding, encoder_aud — and its own encoder's share)
         if (int e = prep_audio(t)) return e;
-        for (Encoder* E : encs()) { if (active() == 0 || E == (active() == 1 ? &exp_ : &ges_)) { if (int e = prep_encoder(*E)) return e; } }
-        if (mode == 1) { if (int e = level_copy(level, 0)) return e; }
+        for (Encoder* E : encs()) { if (active() == PART_BOTH || E == (active() == PART_EXPRESSION ? &exp_ : &ges_)) { if (int e = prep_encoder(*E)) return e; } }
+        if (mode == EVAL_SAVE) { if (int e = level_copy(level, 0)) return e; }
     }
     // ---- expression, then gesture conditioned on the expression x0 estimate (transformer.py:741-768)
     const int E_ = cfg.expression_dim, G_ = cfg.dim_pose;
@@ -1267,8 +1264,8 @@ int Denoiser<T>::eval_level(const float* x, const int64_t* t, const float* c1, c
         if (int e = run_encoder(ges_, x, 0, cfg.channels(), nullptr, 0, c1, c2, eps, false)) return e;
     } else {
         // (one modality alone: the gesture encoder reads the given track, packed into expr_x0 / expr16 by set_modality)
-        if (active() != 2) { if (int e = run_encoder(exp_, x, G_, E_, nullptr, 0, c1, c2, eps, true)) return e; }
-        if (active() != 1) { if (int e = run_encoder(ges_, x, 0, G_, expr_x0, E_, c1, c2, eps, false)) return e; }
+        if (active() != PART_GESTURE) { if (int e = run_encoder(exp_, x, G_, E_, nullptr, 0, c1, c2, eps, true)) return e; }
+        if (active() != PART_EXPRESSION) { if (int e = run_encoder(ges_, x, 0, G_, expr_x0, E_, c1, c2, eps, false)) return e; }
     }
     flops_last_eval = flops_acc;
     return 0;
@@ -1291,428 +1288,12 @@ int Denoiser<T>::debug_copy(const std::string& what, float* out) {
     return 0;
 }
 
-// Large batches are evaluated as two or three (DSH_DUAL=n: at most n) independent sub-batches on as many streams (the extra instances
-// share the weights).  Clips never interact inside the denoiser, so this changes no result; the second stream starts a few
-// launches late, which keeps the two kernel sequences out of phase: an HBM-bound StylizationBlock launch of one
-// sub-batch then shares the chip with an MFMA-bound q|k|v / FFN launch of the other, and one launch's load prologue
-// and tail run under the other's main loop (sty + ffn.linear2 pair: 566 -> 492 us, scripts/bench_tl_overlap.py).
-class DualDenoiser final : public DenoiserBase {
-  public:
-    DualDenoiser(DenoiserBase* primary, const ModelConfig& c, hipStream_t s) : cfg_(c), st_(s) {
-        inst_.emplace_back(primary);
-        nsplit_ = dual_streams();                            // off is "0"; n >= 2: at most n streams
-        lag_ = (int)switch_int(SW_DUAL_LAG);
-        // fp32 parity path: one GEMM launch of the config-2 batch (8704 rows) is only 1 - 3 rounds of co-resident tiles, so the
-        // second stream's launches fill the partial last rounds (+1.5 % measured); bf16: from 12288 rows (want_split)
-        // fp32 path: two streams from 4096 rows, three from 8700 (the 256-clip BEAT batch of configs[1]: 8704 rows = 17 x 512, every
-        // Linear a 1.06 / 2.1 / 3.2-round launch of 64 x 64 tiles whose tail another sub-batch fills; measured 24.8 k -> 25.1 k frames/s)
-        if (c.precision == 0) { min_rows_ = 4096; rows_per_stream_ = 2900; }
-        if (const long rs = switch_positive(SW_DUAL_ROWS)) rows_per_stream_ = (size_t)rs;
-        if (const long mr = switch_positive(SW_DUAL_MIN_ROWS)) min_rows_ = (size_t)mr;
-        pipe_rows_ = pipe_rows_context();
-    }
-    ~DualDenoiser() override {
-        (void)hipDeviceSynchronize();                        // side streams may still be running a level ahead of an aborted loop
-        twin_.reset();
-        if (twin_stream_) (void)hipStreamDestroy(twin_stream_);
-        if (twin_ev_) (void)hipEventDestroy(twin_ev_);
-        pf_.prep.reset();                                    // the side instance borrows the whole-batch instance's slots and weights
-        while (inst_.size() > 1) inst_.pop_back();
-        for (hipStream_t st : streams_) (void)hipStreamDestroy(st);
-        for (hipEvent_t ev : events_) (void)hipEventDestroy(ev);
-        if (cond_buf_) (void)hipFree(cond_buf_);
-        if (len_buf_) (void)hipFree(len_buf_);
-        if (track_buf_) (void)hipFree(track_buf_);
-        if (pf_.stream) (void)hipStreamDestroy(pf_.stream);
-        for (hipEvent_t ev : pf_.lvl_ev) (void)hipEventDestroy(ev);
-        if (pf_.ev_fork) (void)hipEventDestroy(pf_.ev_fork);
-        if (pf_.ev_done) (void)hipEventDestroy(pf_.ev_done);
-        if (pf_.t_dev) (void)hipFree(pf_.t_dev);
-    }
-    int finalize(const std::map<std::string, HostTensor>& w) override { return inst_[0]->finalize(w); }
-    int set_condition(int B, int T, const float* audio, const float* person_id, const float* hubert) override {
-        return condition(B, T, nullptr, audio, person_id, hubert);
-    }
-    int set_condition_ragged(int B, int T, const int32_t* lengths_host, const float* audio, const float* person_id, const float* hubert) override {
-        DSH_REQUIRE(lengths_host, "set_condition_ragged: null lengths");
-        return condition(B, T, lengths_host, audio, person_id, hubert);
-    }
-    const int32_t* lengths_host() const override { return lens_ ? lens_host_.data() : nullptr; }
-    const int* lengths_dev() const override { return lens_; }
-    int condition(int B, int T, const int32_t* lengths_host, const float* audio, const float* person_id, const float* hubert) {
-        DSH_REQUIRE(B > 0 && T > 0 && audio && person_id && hubert, "set_condition: null conditioning pointer / empty batch");
-        if (lengths_host) {
-            for (int b = 0; b < B; ++b)
-                if (lengths_host[b] < 1 || lengths_host[b] > T) {
-                    set_last_error("set_condition_ragged: clip " + std::to_string(b) + " has length " + std::to_string(lengths_host[b]) +
-                                   ", valid lengths are 1 .. " + std::to_string(T) + " (the padded frame count)");
-                    return -1;
-                }
-        }
-        if (int e = inst_[0]->check_shape(B, T)) return e;          // (before any state changes: a refused shape leaves the previous condition usable)
-        // The split (one stream vs sub-batches on several) may change between evals (profiler on/off), which re-runs the
-        // per-instance set_condition: the conditioning is therefore copied into context-owned buffers, so the caller's
-        // tensors only need to stay valid until this call's work on the context stream has been enqueued (stream order).
-        const size_t na = (size_t)B * T * cfg_.audio_dim, np = (size_t)B * cfg_.style_dim, nh = (size_t)B * T * cfg_.hubert_dim;
-        // the prefetch instance reads the previous conditioning on its own stream: order the overwrite behind it
-        if (pf_.busy) { DSH_HIP_CHECK(hipStreamWaitEvent(st_, pf_.ev_done, 0)); pf_.busy = false; }
-        if (twin_busy_) { DSH_HIP_CHECK(hipEventRecord(twin_ev_, twin_stream_)); DSH_HIP_CHECK(hipStreamWaitEvent(st_, twin_ev_, 0)); twin_busy_ = false; }
-        twin_cond_ok_ = false;
-        if (!inst_.empty()) (void)inst_[0]->set_part(0);
-        // the modality is part of the condition: a new condition is a joint one until set_modality() says otherwise
-        mod_ = 0; modality = 0;
-        for (auto& in : inst_) (void)in->set_modality(0, nullptr);
-        if (pf_.prep) (void)pf_.prep->set_modality(0, nullptr);
-        if (twin_) (void)twin_->set_modality(0, nullptr);
-        if (na + np + nh > cond_cap_) { if (int e = grow_device_buffer(cond_buf_, cond_cap_, na + np + nh, st_)) return e; }
-        float* a = cond_buf_; float* p = a + na; float* h = p + np;
-        DSH_HIP_CHECK(hipMemcpyAsync(a, audio, na * sizeof(float), hipMemcpyDeviceToDevice, st_));
-        DSH_HIP_CHECK(hipMemcpyAsync(p, person_id, np * sizeof(float), hipMemcpyDeviceToDevice, st_));
-        DSH_HIP_CHECK(hipMemcpyAsync(h, hubert, nh * sizeof(float), hipMemcpyDeviceToDevice, st_));
-        // per-clip lengths: context-owned like the conditioning, read by the kernels when they run; instance i of a split sees `lens_ + its first clip`
-        if (lengths_host) {
-            if ((size_t)B > len_cap_) { if (int e = grow_device_buffer(len_buf_, len_cap_, (size_t)B, st_)) return e; }
-            lens_host_.assign(lengths_host, lengths_host + B);
-            // (pageable host source: staged before the call returns)
-            DSH_HIP_CHECK(hipMemcpyAsync(len_buf_, lens_host_.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, st_));
-            lens_ = len_buf_;
-        } else lens_ = nullptr;
-        cond_ = {B, T, a, p, h};
-        batch = B; frames = T;
-        return apply_condition((B == sticky_B_ && T == sticky_T_ && pipe_possible()) ? 1 : want_split(B, T));
-    }
-    int set_modality(int m, const float* expression) override {
-        DSH_REQUIRE(m >= 0 && m <= 2, "set_modality: unknown modality (0 both / 1 expression / 2 gesture)");
-        DSH_REQUIRE(m == 0 || !cfg_.single_transformer, "set_modality: a single MotionTransformer has no separate expression / gesture encoders");
-        DSH_REQUIRE(cond_.B > 0, "set_condition() must precede set_modality()");
-        DSH_REQUIRE(m != 2 || expression, "set_modality: the gesture modality needs the expression track [B, T, expression_dim]");
-        if (m == 2) {
-            // context-owned copy, in stream order like the other conditioning tensors: a re-split re-packs from it (apply_condition), and the
-            // sampler writes it into the expression columns of its result
-            const size_t ne = (size_t)cond_.B * cond_.T * cfg_.expression_dim;
-            // (the whole device: the sub-batch instances read the track on their own streams)
-            if (ne > track_cap_) { if (int e = grow_device_buffer(track_buf_, track_cap_, ne, st_, true)) return e; }
-            DSH_HIP_CHECK(hipMemcpyAsync(track_buf_, expression, ne * sizeof(float), hipMemcpyDeviceToDevice, st_));
-        }
-        mod_ = m; modality = m;
-        return push_modality(split_now_);
-    }
-    const float* modality_track() const override { return mod_ == 2 ? track_buf_ : nullptr; }
-    int eval(const float* x, const int64_t* t, const float* c1, const float* c2, float* eps) override {
-        DSH_REQUIRE(cond_.B > 0, "set_condition() must precede eval()");
-        inst_[0]->prof = prof;
-        const int ns = (loop_unsplit_ && split_now_ == 1) ? 1 : want_split(cond_.B, cond_.T);
-        if (ns != split_now_) { if (int e = apply_condition(ns)) return e; }   // e.g. the profiler was switched on in between
-        for (auto& in : inst_) in->t_uniform = t_uniform;
-        note_launch_value(LC_EVAL_STREAMS, ns);
-        if (ns == 1) return inst_[0]->eval(x, t, c1, c2, eps);
-        const int C = cfg_.channels();
-        return fork_join(ns, [&](int i, hipStream_t si) -> int {
-            const int b0 = first_clip(i, ns);
-            const size_t off = (size_t)b0 * cond_.T * C;
-            if (i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(si, ev_lag_[i - 1], 0));      // a few launches behind sub-batch i - 1
-            inst_[i]->notify_after_launches(i + 1 < ns ? ev_lag_[i] : nullptr, i + 1 < ns ? lag_ : 0);
-            return inst_[i]->eval(x + off, t + b0, c1 + b0, c2 + b0, eps + off);
-        });
-    }
-    int sub_count() const override { return (cond_.B > 0 && (split_now_ == 1 || want_split(cond_.B, cond_.T) == split_now_)) ? split_now_ : 1; }
-    int sub_get(int i, DenoiserBase** inst, hipStream_t* stream, int* first, int* n) override {
-        DSH_REQUIRE(i >= 0 && i < split_now_ && split_now_ > 1 && inst && stream && first && n, "sub_get: no such sub-batch");
-        *inst = inst_[i].get();
-        *stream = i == 0 ? st_ : streams_[i - 1];
-        *first = first_clip(i, split_now_);
-        *n = first_clip(i + 1, split_now_) - *first;
-        inst_[i]->prof = nullptr;
-        return 0;
-    }
-    int level_cache_prepare(int n_levels) override {
-        if (cond_.B <= 0 || split_now_ != 1) return -1;
-        return inst_[0]->level_cache_prepare(n_levels);
-    }
-    // Prefetch: a second instance (shared weights, own workspace) computes the x-independent head of every scheduled level on a
-    // side stream, ahead of the loop, into the main instance's cache slots.  At launch-bound batch sizes the main chain keeps a
-    // handful of CUs busy, so the side stream runs beside it: the 27 launches (0.28 ms at B = 1) leave every evaluation's
-    // critical path, also for schedules that visit each level once (the first window of a chain).  DSH_LEVEL_PREFETCH=0: off.
-    int level_prefetch(const int64_t* t_values_host, int n_levels, const int* order, int n_order, int begin) override {
-        if (n_levels <= 0 || n_order < 0 || !t_values_host || (n_order > 0 && !order)) return -1;
-        if (split_now_ != 1) return -1;                                     // the whole batch on one stream only
-        DenoiserBase* main = inst_[0].get();
-        const int nb = cond_.B;
-        Prefetch& f = pf_;
-        if (begin) {
-            f.active = false;
-            if (switch_int(SW_LEVEL_PREFETCH) == 0) return -1;
-            if (level_cache_prepare(n_levels) != 0) return -1;
-            char* slots = nullptr; size_t stride = 0; int nslots = 0;
-            if (main->level_slots(&slots, &stride, &nslots) != 0 || nslots < n_levels) return -1;
-            if (!f.prep) {
-                DSH_HIP_CHECK(hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking));
-                DSH_HIP_CHECK(hipEventCreateWithFlags(&f.ev_fork, hipEventDisableTiming));
-                DSH_HIP_CHECK(hipEventCreateWithFlags(&f.ev_done, hipEventDisableTiming));
-                DenoiserBase* c = inst_[0]->clone_shared(f.stream);
-                DSH_REQUIRE(c != nullptr, "weights not finalized");
-                f.prep.reset(c);
-            }
-            while ((int)f.lvl_ev.size() < n_levels) { hipEvent_t ev; DSH_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); f.lvl_ev.push_back(ev); }
-            const size_t need = (size_t)n_levels * (nb + 1);
-            if (need > f.t_cap) { if (int e = grow_device_buffer(f.t_dev, f.t_cap, need, f.stream)) return e; }
-            // everything already enqueued on the evaluating stream (the conditioning copies, the previous run's last restore from
-            // the slots) precedes the side stream's work
-            DSH_HIP_CHECK(hipEventRecord(f.ev_fork, st_));
-            DSH_HIP_CHECK(hipStreamWaitEvent(f.stream, f.ev_fork, 0));
-            if (int e = f.prep->set_lengths(lens_)) return e;
-            if (int e = f.prep->set_modality(mod_, nullptr)) return e;           // (fills the active encoder's share of every slot only)
-            if (int e = f.prep->set_condition_light(nb, cond_.T, cond_.audio, cond_.pid)) return e;
-            if (int e = f.prep->adopt_level_slots(slots, stride, nslots)) return e;
-            f.levels = n_levels; f.nb = nb;
-            f.active = true;
-        }
-        DSH_REQUIRE(f.active && n_levels == f.levels && nb == f.nb, "level_prefetch: no run in progress");
-        int64_t* idx = f.t_dev + (size_t)n_levels * nb;                     // [n_levels] slot indices 0 .. n-1
-        for (int i = 0; i < n_order; ++i) {
-            const int k = order[i];
-            DSH_REQUIRE(k >= 0 && k < n_levels, "level_prefetch: level out of range");
-            int64_t* tk = f.t_dev + (size_t)k * nb;
-            if (int e = launch_fill_i64(tk, t_values_host[k], (size_t)nb, f.stream)) return e;
-            if (int e = launch_fill_i64(idx + k, (int64_t)k, 1, f.stream)) return e;
-            f.prep->t_uniform = emb_dedup_enabled();                        // (tk was just filled with one value)
-            if (int e = f.prep->eval_level(nullptr, tk, nullptr, nullptr, nullptr, 3, idx + k)) return e;
-            DSH_HIP_CHECK(hipEventRecord(f.lvl_ev[k], f.stream));
-        }
-        DSH_HIP_CHECK(hipEventRecord(f.ev_done, f.stream));
-        f.busy = true;
-        return 0;
-    }
-    // ---- pipelined small-batch loop (denoiser.h): the gesture-side twin of the whole-batch instance -----------------------------
-    int pipe_begin(DenoiserBase** twin, hipStream_t* stream) override {
-        if (switch_int(SW_PIPE) == 0 || cfg_.single_transformer || cond_.B <= 0 || split_now_ != 1 || !twin || !stream) return -1;
-        if (mod_ != 0) return -1;                                            // one modality alone: one chain, nothing to pipeline
-        // (DDIM loops: the twin restores its head from the slots the prefetch run fills; loops without a timestep cache — DDPM — compute it)
-        char* slots = nullptr; size_t stride = 0; int nslots = 0;
-        const bool have_slots = pf_.active && inst_[0]->level_slots(&slots, &stride, &nslots) == 0;
-        if (!twin_) {
-            // (default priority: a lowest-priority gesture stream was measured — single clip 16.6 -> 77 ms, profiles/r06b_ar_ab_twin_stream_priority.txt)
-            DSH_HIP_CHECK(hipStreamCreateWithFlags(&twin_stream_, hipStreamNonBlocking));
-            DSH_HIP_CHECK(hipEventCreateWithFlags(&twin_ev_, hipEventDisableTiming));
-            DenoiserBase* c = inst_[0]->clone_shared(twin_stream_);
-            DSH_REQUIRE(c != nullptr, "weights not finalized");
-            twin_.reset(c);
-            twin_cond_ok_ = false;
-        }
-        // everything already enqueued on the evaluating stream (the conditioning copies) precedes the twin's work
-        DSH_HIP_CHECK(hipEventRecord(twin_ev_, st_));
-        DSH_HIP_CHECK(hipStreamWaitEvent(twin_stream_, twin_ev_, 0));
-        if (int e = twin_->set_guidance(gs_, gs_row_, gs_dbl_)) return e;
-        if (!twin_cond_ok_) {
-            if (int e = twin_->set_part(0)) return e;
-            if (int e = twin_->set_lengths(lens_)) return e;
-            if (int e = twin_->set_condition(cond_.B, cond_.T, cond_.audio, cond_.pid, cond_.hubert)) return e;
-            twin_cond_ok_ = true;
-        }
-        if (have_slots) { if (int e = twin_->adopt_level_slots(slots, stride, nslots)) return e; }
-        if (int e = twin_->set_part(2)) return e;
-        if (int e = inst_[0]->set_part(1)) return e;
-        twin_->t_uniform = t_uniform; inst_[0]->t_uniform = t_uniform;
-        twin_->prof = nullptr;
-        twin_busy_ = true;
-        *twin = twin_.get(); *stream = twin_stream_;
-        return 0;
-    }
-    int pipe_end() override {
-        if (twin_) (void)twin_->set_part(0);
-        return inst_[0]->set_part(0);
-    }
-    int import_expr(DenoiserBase* src, hipStream_t s) override {
-        // (called on the CONTEXT's denoiser with src = the twin: the twin takes the whole-batch instance's expression estimate)
-        DSH_REQUIRE(twin_ && src == twin_.get(), "import_expr: no pipelined run in progress");
-        return twin_->import_expr(inst_[0].get(), s);
-    }
-    int loop_begin(int kind) override {
-        if (cond_.B <= 0) return 0;
-        const bool unsplit = (kind == 0 || kind == 1) && pipe_possible() && (size_t)cond_.B * cond_.T <= pipe_rows_;
-        if (!unsplit) { sticky_B_ = sticky_T_ = 0; return 0; }
-        sticky_B_ = cond_.B; sticky_T_ = cond_.T; loop_unsplit_ = true;
-        if (split_now_ != 1) return apply_condition(1);
-        return 0;
-    }
-    int loop_end() override { loop_unsplit_ = false; return 0; }
-    int gesture_channels() const override { return cfg_.single_transformer ? -1 : cfg_.dim_pose; }
-    int level_wait_stream(int level, hipStream_t s) override {
-        DSH_REQUIRE(level >= 0 && level < (int)pf_.lvl_ev.size(), "level_wait_stream: level out of range");
-        DSH_HIP_CHECK(hipStreamWaitEvent(s, pf_.lvl_ev[level], 0));
-        return 0;
-    }
-    int level_wait(int level) override {
-        DSH_REQUIRE(level >= 0 && level < (int)pf_.lvl_ev.size(), "level_wait: level out of range");
-        DSH_HIP_CHECK(hipStreamWaitEvent(st_, pf_.lvl_ev[level], 0));
-        return 0;
-    }
-    int eval_level(const float* x, const int64_t* t, const float* c1, const float* c2, float* eps, int mode, const int64_t* level) override {
-        if (mode == 0) return eval(x, t, c1, c2, eps);
-        DSH_REQUIRE(cond_.B > 0 && split_now_ == 1, "eval_level: the timestep cache is a single-stream feature");
-        inst_[0]->prof = prof;
-        inst_[0]->t_uniform = t_uniform;
-        return inst_[0]->eval_level(x, t, c1, c2, eps, mode, level);
-    }
-    double issued_flops_per_eval() const override {
-        double f = 0;
-        for (int i = 0; i < split_now_; ++i) f += inst_[i]->issued_flops_per_eval();
-        return f;
-    }
-    size_t weight_bytes() const override { return inst_[0]->weight_bytes(); }
-    // every instance that evaluates sees the context's scales: a sub-batch instance its clips' slice (per-clip scales), the gesture twin all
-    int set_guidance(const float* scale, int scale_row, bool doubled) override {
-        gs_ = scale; gs_row_ = scale_row ? 1 : 0; gs_dbl_ = doubled;
-        for (int i = 0; i < (int)inst_.size(); ++i) { if (int e = push_guidance(i, split_now_)) return e; }
-        if (twin_) { if (int e = twin_->set_guidance(gs_, gs_row_, gs_dbl_)) return e; }
-        return 0;
-    }
-    int debug_copy(const std::string& what, float* out) override {
-        if (split_now_ == 1) return inst_[0]->debug_copy(what, out);
-        // sub-batch streams: every instance copies its own clips' rows on its own stream, joined into the context stream
-        const int w = what == "aud_feat" ? cfg_.audio_dim : cfg_.expression_dim;
-        return fork_join(split_now_, [&](int i, hipStream_t) -> int {
-            return inst_[i]->debug_copy(what, out + (size_t)first_clip(i, split_now_) * cond_.T * w);
-        });
-    }
-
-  private:
-    struct Cond { int B = 0, T = 0; const float* audio = nullptr; const float* pid = nullptr; const float* hubert = nullptr; };
-    int want_split(int B, int T) const {
-        if (nsplit_ < 2 || (prof && prof->on) || (size_t)B * T < min_rows_) return 1;
-        // Two streams from min_rows_ token rows, three from 3 * rows_per_stream_ = 64 500 (the 950-clip batch of configs[2]: 83 600).
-        // Measured on MI355X with the sampling loop's free-running sub-batch streams (sampler.hip; round 3), frames/s at
-        // 1 / 2 / 3 streams: 100 clips (8.8k rows) 83.0k / 81.6k / -; 200 clips 87.6k / 112.4k / 107.4k; 475 clips 111.6k / 129.6k /
-        // 125.8k; 650 clips - / 134.8k / 133.2k; 800 clips - / 129.9k / 134.9k; 950 clips - / 133.0k / 136.2k (four: 121k; a disjoint
-        // CU partition per stream through hipExtStreamCreateWithCUMask:
-        // 100 - 118k).  With one fork / join per EVALUATION (dsh_eval) the same three streams give 130k at 950 clips.
-        const int by_rows = std::max(2, (int)((size_t)B * T / rows_per_stream_));
-        return std::min(std::min(nsplit_, by_rows), B);
-    }
-    // sub-batch i covers clips [first_clip(i), first_clip(i + 1)): equal shares, or (bench experiment) the cumulative boundaries of
-    // DSH_SPLIT_AT="c1,c2,..." when they fit the batch and the stream count
-    int first_clip(int i, int ns) const {
-        static const std::vector<int> at = [] {
-            std::vector<int> v;
-            if (const char* e = switch_str(SW_SPLIT_AT)) { for (const char* p = e; *p;) { v.push_back(atoi(p)); while (*p && *p != ',') ++p; if (*p == ',') ++p; } }
-            return v;
-        }();
-        if ((int)at.size() == ns - 1 && i > 0 && i < ns) {
-            bool ok = at[0] > 0 && at.back() < cond_.B;
-            for (size_t k = 1; k < at.size(); ++k) ok = ok && at[k] > at[k - 1];
-            if (ok) return at[i - 1];
-        }
-        return (int)((int64_t)cond_.B * i / ns);
-    }
-    // One fork / join of the sub-batch streams around f(i, stream of instance i) for i in [0, ns): instance 0 works on the context stream, every
-    // other on its own behind all the context stream holds so far, and the context stream goes on behind each of them.
-    template <typename F> int fork_join(int ns, F&& f) {
-        DSH_HIP_CHECK(hipEventRecord(ev_fork_, st_));
-        for (int i = 0; i < ns; ++i) {
-            hipStream_t si = i == 0 ? st_ : streams_[i - 1];
-            if (i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(si, ev_fork_, 0));
-            if (int e = f(i, si)) return e;
-            if (i > 0) {
-                DSH_HIP_CHECK(hipEventRecord(ev_join_[i - 1], si));
-                DSH_HIP_CHECK(hipStreamWaitEvent(st_, ev_join_[i - 1], 0));
-            }
-        }
-        return 0;
-    }
-    int apply_condition(int ns) {
-        while ((int)inst_.size() < ns) {
-            hipStream_t st; hipEvent_t lag, join;
-            DSH_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-            streams_.push_back(st);
-            DSH_HIP_CHECK(hipEventCreateWithFlags(&lag, hipEventDisableTiming)); events_.push_back(lag); ev_lag_.push_back(lag);
-            DSH_HIP_CHECK(hipEventCreateWithFlags(&join, hipEventDisableTiming)); events_.push_back(join); ev_join_.push_back(join);
-            if (!ev_fork_) { DSH_HIP_CHECK(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming)); events_.push_back(ev_fork_); }
-            DenoiserBase* c = inst_[0]->clone_shared(st);
-            DSH_REQUIRE(c != nullptr, "weights not finalized");
-            inst_.emplace_back(c);
-        }
-        split_now_ = ns;
-        for (int i = 0; i < ns; ++i) { if (int e = push_guidance(i, ns)) return e; }
-        inst_[0]->prof = prof;
-        if (ns == 1) {
-            if (int e = inst_[0]->set_lengths(lens_)) return e;
-            if (int e = inst_[0]->set_condition(cond_.B, cond_.T, cond_.audio, cond_.pid, cond_.hubert)) return e;
-            return mod_ ? push_modality(1) : 0;
-        }
-        if (int e = fork_join(ns, [&](int i, hipStream_t) -> int {
-                const int b0 = first_clip(i, ns), nb = first_clip(i + 1, ns) - b0;
-                const size_t ft = (size_t)b0 * cond_.T;
-                if (int e = inst_[i]->set_lengths(lens_ ? lens_ + b0 : nullptr)) return e;
-                return inst_[i]->set_condition(nb, cond_.T, cond_.audio + ft * cfg_.audio_dim, cond_.pid + (size_t)b0 * cfg_.style_dim,
-                                               cond_.hubert + ft * cfg_.hubert_dim);
-            })) return e;
-        return mod_ ? push_modality(ns) : 0;
-    }
-    // the condition's modality to the ns evaluating instances (each packs its own clips' rows of the given track on its own stream, forked
-    // from and joined into the context stream), to the prefetch instance and (unused: the pipelined loop is not entered) the twin
-    int push_modality(int ns) {
-        const size_t row = (size_t)cond_.T * cfg_.expression_dim;
-        const float* tr = mod_ == 2 ? track_buf_ : nullptr;
-        auto pack = [&](int i, hipStream_t) -> int { return inst_[i]->set_modality(mod_, tr + (size_t)(ns > 1 ? first_clip(i, ns) : 0) * row); };
-        if (tr) { if (int e = ns > 1 ? fork_join(ns, pack) : pack(0, st_)) return e; }
-        for (int i = tr ? ns : 0; i < (int)inst_.size(); ++i) { if (int e = inst_[i]->set_modality(mod_, nullptr)) return e; }
-        if (pf_.prep) { if (int e = pf_.prep->set_modality(mod_, nullptr)) return e; }
-        if (twin_) { if (int e = twin_->set_modality(mod_, nullptr)) return e; }
-        return 0;
-    }
-    // instance i of an ns-way split: the scales of its clips (first_clip(i, ns) onwards) when they are per clip
-    int push_guidance(int i, int ns) {
-        const int b0 = (gs_row_ && ns > 1 && i < ns && cond_.B > 0) ? first_clip(i, ns) : 0;
-        return inst_[i]->set_guidance(gs_ ? gs_ + b0 : nullptr, gs_row_, gs_dbl_);
-    }
-    std::vector<std::unique_ptr<DenoiserBase>> inst_;      // [0] owns the weights; the others share them
-    const float* gs_ = nullptr; int gs_row_ = 0; bool gs_dbl_ = false;   // the context's guidance (set_guidance)
-    ModelConfig cfg_;
-    hipStream_t st_;
-    std::vector<hipStream_t> streams_;
-    std::vector<hipEvent_t> events_, ev_lag_, ev_join_;
-    hipEvent_t ev_fork_ = nullptr;
-    Cond cond_;
-    float* cond_buf_ = nullptr;                            // context-owned copy of [audio | person_id | hubert]
-    int* len_buf_ = nullptr; size_t len_cap_ = 0;          // ... and of the per-clip lengths of a ragged condition
-    const int* lens_ = nullptr;                            // len_buf_ while the current condition is ragged, else null
-    std::vector<int32_t> lens_host_;
-    size_t cond_cap_ = 0;
-    int mod_ = 0;                                          // the condition's modality (set_modality): 0 both / 1 expression / 2 gesture
-    float* track_buf_ = nullptr; size_t track_cap_ = 0;    // context-owned copy of the given expression track [B, T, E] (modality 2)
-    // side-stream producer of the x-independent head of the whole batch (level_prefetch)
-    struct Prefetch {
-        std::unique_ptr<DenoiserBase> prep;                // shared weights, own workspace, conditioned with mel features + speaker only
-        hipStream_t stream = nullptr;
-        std::vector<hipEvent_t> lvl_ev;
-        hipEvent_t ev_fork = nullptr, ev_done = nullptr;
-        int64_t* t_dev = nullptr; size_t t_cap = 0;
-        bool busy = false, active = false;
-        int levels = 0, nb = 0;
-    };
-    Prefetch pf_;
-    std::unique_ptr<DenoiserBase> twin_;                   // gesture-side twin of inst_[0] for the pipelined small-batch loop (pipe_begin)
-    hipStream_t twin_stream_ = nullptr; hipEvent_t twin_ev_ = nullptr; bool twin_cond_ok_ = false, twin_busy_ = false;
-    size_t pipe_rows_ = 0;                                 // DDIM loops below this many token rows: one batch, two encoder streams (loop_begin)
-    int sticky_B_ = 0, sticky_T_ = 0;                      // shape whose last loop ran unsplit: set_condition conditions it as one batch
-    bool loop_unsplit_ = false;                            // a sampling loop is running this batch unsplit on purpose (its evaluations must not re-split it)
-    bool pipe_possible() const {
-        // (the pipelined loop restores every head from the slots a side-stream prefetch run fills: all three switches must be on)
-        return pipe_switches_on() && !cfg_.single_transformer && !(prof && prof->on);
-    }
-    int nsplit_ = 1, split_now_ = 1, lag_ = 0;             // (nsplit_, lag_, pipe_rows_: from the switches, in the constructor)
-    size_t min_rows_ = 12288;                              // batches below this many token rows run on one stream
-    size_t rows_per_stream_ = 21500;                       // streams = rows / this (at least two, at most DSH_DUAL): three from 64 500 rows
-};
-
 }  // namespace
 
-DenoiserBase* make_denoiser(const ModelConfig& cfg, hipStream_t stream) {
-    DenoiserBase* d = nullptr;
-    if (cfg.precision == 0) d = new Denoiser<float>(cfg, stream);
-    else if (cfg.precision == 1) d = new Denoiser<bf16>(cfg, stream);
-    if (!d) return nullptr;
-    return new DualDenoiser(d, cfg, stream);
+DenoiserInstance* make_denoiser_instance(const ModelConfig& cfg, hipStream_t stream) {
+    if (cfg.precision == 0) return new Denoiser<float>(cfg, stream);
+    if (cfg.precision == 1) return new Denoiser<bf16>(cfg, stream);
+    return nullptr;
 }
 
 }  // namespace dsh

@@ -55,16 +55,16 @@ class Sampler {
     // level, or init 2 with x = x0).  Sticky like the tail blend; 0 = the whole schedule.  Range-checked by run() (needs the respacing).
     int set_start_level(int K);
     // init: 0 / 1 / 2 as for sampler_num_draws
-    int run(DenoiserBase* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask,
+    int run(DenoiserContext* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask,
             bool masked, const float* noise_stack, int64_t n_draws, float* trace);
     // DDIM inversion: x (a clean motion at from_level 0, or a state at level from_level) is carried up the reverse ODE through levels
     // from_level .. to_level - 1, in place; no draws, eta = 0 only, no mask.  trace [to_level - from_level, n] as in run().
-    int invert(DenoiserBase* den, const SamplerOpts& o, float* x, int from_level, int to_level, float* trace);
+    int invert(DenoiserContext* den, const SamplerOpts& o, float* x, int from_level, int to_level, float* trace);
 
   private:
     // One set of the device buffers a chain works in: the noise scratch of a step's two draws, the per-step scalars an evaluation reads
     // (timestep, the two input scales, the level's cache slot: one per batch row, 8 level words) and the hipGraphs of one evaluation, one per
-    // timestep-cache mode (denoiser.h: 0 plain, 1 compute + save level, 2 restore level).  Replayed in launch-bound (small-batch /
+    // timestep-cache mode (denoiser.h, EvalMode: plain, compute + save level, restore level).  Replayed in launch-bound (small-batch /
     // window-chain) runs: all pointers are fixed for a run, only the scalars' contents change between steps.
     struct ChainBufs {
         float *nz1 = nullptr, *nz_eta = nullptr, *c1 = nullptr, *c2 = nullptr;
@@ -77,7 +77,7 @@ class Sampler {
     //   pipelined loop E / G   the context's denoiser and stream on the expression columns with bufs[0] / the gesture-side twin and its
     //                          stream on the gesture columns, one step behind, with bufs[1]
     struct Chain {
-        DenoiserBase* d; hipStream_t s;
+        DenoiserInstance* inst; hipStream_t s;   // the instance that evaluates it; null: the run's context does (whole batch, E)
         int b0, nb; size_t off, cnt;        // clips [b0, b0 + nb) = elements [off, off + cnt) of x / eps / gt / mask / the noise scratch
         int c_lo, c_hi;                     // the columns its updates write (0, 0: all)
         float *nz1, *nz_eta;                // full-size scratch (the chain uses its element range): the gt / undo / DDPM draw, the eta != 0 draw
@@ -98,7 +98,7 @@ class Sampler {
     StepConsts step_consts(Run& r, const SamplerStep& sp);
     int noise_for(const Run& r, int64_t idx, const Chain& c, float* scratch, const float** out);
     int evaluate(Run& r, const LoopPlan& p, const StepConsts& sc);
-    int eval_step(const Chain& c, float* x, int n_eval, bool use_graph, int mode);
+    int eval_step(const Run& r, const Chain& c, int n_eval, bool use_graph, int mode);
     int gesture_follow(Run& r, const LoopPlan& p, const StepConsts& sc);
     int update(Run& r, const Chain& c, const StepConsts& sc);
     int ddim_update(Run& r, const Chain& c, const StepConsts& sc);
@@ -120,7 +120,7 @@ class Sampler {
     uint64_t* row_seeds = nullptr; int n_row_seeds = 0, cap_row_seeds = 0;
     bool tail_blend = false;
     int start_level = 0;
-    int run_schedule(DenoiserBase* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask, bool masked,
+    int run_schedule(DenoiserContext* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask, bool masked,
                      const float* noise_stack, int64_t n_draws, float* trace, int start, int invert_to, int invert_from);
     int init_x(Run& r);
     // --same_overlap_noisy: the noisy tail x[..., -L:, :] saved after every DDIM step, one slot per spaced level; persists

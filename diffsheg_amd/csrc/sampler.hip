@@ -150,7 +150,7 @@ int64_t sampler_num_steps(const SamplerOpts& o, bool masked, int start_level) {
 // One run()'s arguments, what is derived from them once, its chains and the loop's running state; the parts of run() share it by reference.
 enum LevelCache { CACHE_NONE, CACHE_INLINE, CACHE_PREFETCH, CACHE_SUBS };
 struct Sampler::Run {
-    DenoiserBase* den; const SamplerOpts& o; float* x; int init; const float* gt; const uint8_t* mask; bool masked;
+    DenoiserContext* den; const SamplerOpts& o; float* x; int init; const float* gt; const uint8_t* mask; bool masked;
     const float* noise_stack; int64_t n_draws; float* trace;
     int start, invert_from, invert_to;                   // start level of the DDIM schedules (0: the top); reverse loop over these levels (to 0: none)
     int B = 0; size_t n = 0, row_n = 0;                  // clips, values, values per clip
@@ -241,8 +241,9 @@ void Sampler::drop_graph() { drop_graphs(bufs[1]); drop_graphs(bufs[0]); }
 // All pointers (x, the chain's scalars, eps, the denoiser workspace and its timestep-cache slots) are fixed for
 // the duration of a run; only the CONTENTS of the scalars change between steps, so one graph per mode serves every step.
 // A failed capture or instantiation drops the chain's graphs and evaluates eagerly.
-int Sampler::eval_step(const Chain& c, float* x, int n_eval, bool use_graph, int mode) {
-    auto eager = [&]() -> int { return c.d->eval_level(x + c.off, c.t, c.c1, c.c2, eps + c.off, mode, c.lvl); };
+int Sampler::eval_step(const Run& r, const Chain& c, int n_eval, bool use_graph, int mode) {
+    float* xc = r.x + c.off; float* ec = eps + c.off;      // (a chain without an instance is the whole batch, evaluated by the context)
+    auto eager = [&]() -> int { return c.inst ? c.inst->eval_level(xc, c.t, c.c1, c.c2, ec, mode, c.lvl) : r.den->eval_level(xc, c.t, c.c1, c.c2, ec, mode, c.lvl); };
     if (!use_graph || n_eval == 0) return eager();
     ChainBufs& g = *c.own;
     if (!g.graph_exec[mode]) {
@@ -288,7 +289,6 @@ int Sampler::ensure(size_t n, int B) {
 // what run() needs beside its arguments: the schedule, the coefficient tables, the buffers, the noise addressing, the saved noisy tails
 int Sampler::prepare(Run& r) {
     const SamplerOpts& o = r.o;
-    DenoiserBase* den = r.den;
     const int B = r.B; const size_t n = r.n;
     std::string err;
     if (plan_steps(o, r.masked, r.start, r.invert_to, r.steps, err, r.invert_from)) { set_last_error(err); return -1; }
@@ -312,7 +312,7 @@ int Sampler::prepare(Run& r) {
     r.blc = (size_t)B * o.overlap_len * channels;
     r.son = o.same_overlap_noisy != 0 && o.kind == 0;
     if (r.son) {
-        DSH_REQUIRE(o.overlap_len > 0 && o.overlap_len <= den->frames, "same_overlap_noisy needs 0 < overlap_len <= frames");
+        DSH_REQUIRE(o.overlap_len > 0 && o.overlap_len <= r.den->frames(), "same_overlap_noisy needs 0 < overlap_len <= frames");
         if (tails_blc != r.blc || tails_levels != o.respacing) {
             DSH_REQUIRE(o.clip_idx == 0 || !r.masked, "same_overlap_noisy: the saved noisy tails belong to a different batch / overlap shape");
             // (the pair grows together; its shape is recorded once both exist)
@@ -331,17 +331,16 @@ int Sampler::prepare(Run& r) {
 // The chains of a run.  Large batches: every sub-batch runs the WHOLE loop on its own stream, forked from the context stream here and
 // joined into it in finish(); else the whole batch on the context stream.
 int Sampler::make_chains(Run& r) {
-    DenoiserBase* den = r.den;
     ChainBufs& b = bufs[0];
     r.lag = (int)switch_int(SW_DUAL_LAG);
-    const int ns = (prof && prof->on) ? 1 : den->sub_count();
+    const int ns = (prof && prof->on) ? 1 : r.den->sub_count();
     if (!(ns > 1 && r.row_n % 4 == 0)) {
-        r.chains.push_back(Chain{den, st, 0, r.B, 0, r.n, r.w_lo, r.w_hi, b.nz1, b.nz_eta, b.t, b.c1, b.c2, b.lvl, &b});
+        r.chains.push_back(Chain{nullptr, st, 0, r.B, 0, r.n, r.w_lo, r.w_hi, b.nz1, b.nz_eta, b.t, b.c1, b.c2, b.lvl, &b});
         return 0;
     }
     for (int i = 0; i < ns; ++i) {
         Chain c{nullptr, nullptr, 0, 0, 0, 0, r.w_lo, r.w_hi, b.nz1, b.nz_eta, nullptr, nullptr, nullptr, b.lvl + i, &b};
-        if (int e = den->sub_get(i, &c.d, &c.s, &c.b0, &c.nb)) return e;
+        if (int e = r.den->sub_get(i, &c.inst, &c.s, &c.b0, &c.nb)) return e;
         c.off = (size_t)c.b0 * r.row_n; c.cnt = (size_t)c.nb * r.row_n;
         c.t = b.t + c.b0; c.c1 = b.c1 + c.b0; c.c2 = b.c2 + c.b0;
         r.chains.push_back(c);
@@ -357,7 +356,7 @@ Sampler::LoopPlan Sampler::plan(const Run& r) const {
     const SamplerOpts& o = r.o;
     LoopPlan p;
     const bool profiling = prof && prof->on;
-    const size_t rows = (size_t)r.B * r.den->frames;
+    const size_t rows = (size_t)r.B * r.den->frames();
     p.split = r.chains.size() > 1;
     // graphs only where launches dominate (a few thousand token rows), never while profiling events are recorded,
     // and never on the legacy NULL stream (it cannot be captured); sub-batch streams evaluate eagerly
@@ -395,23 +394,22 @@ Sampler::LoopPlan Sampler::plan(const Run& r) const {
 // queued now, the others one evaluation ahead of their first use: the host never runs far in front of the main chain, and the main chain
 // never waits for the host to finish queueing 25 levels) or the cache slots prepared, the gesture-side twin started.
 int Sampler::setup(Run& r, const LoopPlan& p) {
-    DenoiserBase* den = r.den;
     const SamplerOpts& o = r.o;
     drop_graph();
     r.cache = p.cache;
     if (r.cache == CACHE_PREFETCH) {
         r.tv.resize(o.respacing);
         for (int k = 0; k < o.respacing; ++k) r.tv[k] = (int64_t)tb.tmap[k];
-        if (den->level_prefetch(r.tv.data(), o.respacing, p.order.data(), 1, 1) == 0) r.pf_next = 1;
+        if (r.den->level_prefetch(r.tv.data(), o.respacing, p.order.data(), 1, 1) == 0) r.pf_next = 1;
         else r.cache = p.inline_ok ? CACHE_INLINE : CACHE_NONE;
     }
-    if (r.cache == CACHE_INLINE && den->level_cache_prepare(o.respacing) != 0) r.cache = CACHE_NONE;
-    for (const Chain& c : r.chains) if (r.cache == CACHE_SUBS && c.d->level_cache_prepare(o.respacing) != 0) r.cache = CACHE_NONE;
+    if (r.cache == CACHE_INLINE && r.den->level_cache_prepare(o.respacing) != 0) r.cache = CACHE_NONE;
+    for (const Chain& c : r.chains) if (r.cache == CACHE_SUBS && c.inst->level_cache_prepare(o.respacing) != 0) r.cache = CACHE_NONE;
     if (r.cache != CACHE_NONE) r.level_seen.assign(o.respacing, 0);
     // (a DDIM twin restores its head from the slots of the prefetch run)
     ChainBufs& g = bufs[1];
     r.G = Chain{nullptr, nullptr, 0, r.B, 0, r.n, 0, r.gcols, g.nz1, g.nz_eta, g.t, g.c1, g.c2, g.lvl, &g};
-    if (p.pipe && (o.kind == 1 || r.cache == CACHE_PREFETCH) && den->pipe_begin(&r.G.d, &r.G.s) == 0) {
+    if (p.pipe && (o.kind == 1 || r.cache == CACHE_PREFETCH) && r.den->pipe_begin(&r.G.inst, &r.G.s) == 0) {
         r.piped = true;
         r.E = r.chains[0]; r.E.c_lo = r.gcols; r.E.c_hi = channels;
         for (hipEvent_t* e : {&ev_pE, &ev_pC, &ev_pG}) if (!*e) DSH_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -474,10 +472,9 @@ Sampler::StepConsts Sampler::step_consts(Run& r, const SamplerStep& sp) {
 
 // the evaluation of a step, on every chain of the run (pipelined: the expression encoder's; gesture_follow() queues the twin's)
 int Sampler::evaluate(Run& r, const LoopPlan& p, const StepConsts& sc) {
-    DenoiserBase* den = r.den;
     const int k = sc.k;
     const bool seen = r.cache != CACHE_NONE && r.level_seen[k];
-    const int mode = r.cache == CACHE_NONE ? 0 : (r.cache == CACHE_PREFETCH || seen) ? 2 : 1;
+    const int mode = r.cache == CACHE_NONE ? EVAL_PLAIN : (r.cache == CACHE_PREFETCH || seen) ? EVAL_RESTORE : EVAL_SAVE;
     // (pipelined: E_k overwrites the expression estimate the twin copied behind E_{k-1})
     if (r.piped && sc.eval_idx > 0) DSH_HIP_CHECK(hipStreamWaitEvent(st, ev_pC, 0));
     const bool first_eval = sc.eval_idx == 0;
@@ -490,20 +487,20 @@ int Sampler::evaluate(Run& r, const LoopPlan& p, const StepConsts& sc) {
             while (pos < p.order.size() && p.order[pos] != k) ++pos;
             const size_t want = std::min(p.order.size(), pos + 2);
             if (want > r.pf_next) {
-                if (int e = den->level_prefetch(r.tv.data(), r.o.respacing, p.order.data() + r.pf_next, (int)(want - r.pf_next), 0)) return e;
+                if (int e = r.den->level_prefetch(r.tv.data(), r.o.respacing, p.order.data() + r.pf_next, (int)(want - r.pf_next), 0)) return e;
                 r.pf_next = want;
             }
-            if (int e = den->level_wait(k)) return e;
+            if (int e = r.den->level_wait(k)) return e;
         }
         if (p.split) {
             // every sub-batch on its own stream; at the very first evaluation sub-batch i + 1 starts a few launches behind
             // sub-batch i (so that the kernel sequences are out of phase from the start); afterwards the streams run free
             if (first_eval && i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(c.s, ev_sub[2 * (i - 1)], 0));
-            c.d->notify_after_launches((first_eval && i + 1 < r.chains.size()) ? ev_sub[2 * i] : nullptr, r.lag);
-            c.d->t_uniform = den->t_uniform;
+            c.inst->notify_after_launches((first_eval && i + 1 < r.chains.size()) ? ev_sub[2 * i] : nullptr, r.lag);
+            c.inst->t_uniform = r.den->t_uniform;
         }
-        if (int e = eval_step(c, r.x, sc.eval_idx, p.graph, mode)) return e;
-        if (p.split) c.d->notify_after_launches(nullptr, 0);
+        if (int e = eval_step(r, c, sc.eval_idx, p.graph, mode)) return e;
+        if (p.split) c.inst->notify_after_launches(nullptr, 0);
     }
     if (r.cache != CACHE_NONE) r.level_seen[k] = 1;
     return 0;
@@ -514,14 +511,14 @@ int Sampler::evaluate(Run& r, const LoopPlan& p, const StepConsts& sc) {
 // prefetch run has filled the level; DDPM: computed).  The caller then advances the gesture channels.
 int Sampler::gesture_follow(Run& r, const LoopPlan& p, const StepConsts& sc) {
     const Chain& G = r.G;
-    const int twin_mode = r.o.kind == 0 ? 2 : 0;
+    const int twin_mode = r.o.kind == 0 ? EVAL_RESTORE : EVAL_PLAIN;
     DSH_HIP_CHECK(hipEventRecord(ev_pE, st));
     DSH_HIP_CHECK(hipStreamWaitEvent(G.s, ev_pE, 0));
-    if (int e = r.den->import_expr(G.d, G.s)) return e;
+    if (int e = r.den->import_expr_into_twin(G.s)) return e;
     DSH_HIP_CHECK(hipEventRecord(ev_pC, G.s));
     if (int e = launch_fill_step(G.t, G.c1, G.c2, G.lvl, sc.t, sc.c1, sc.c2, (int64_t)sc.k, G.nb, G.s)) return e;
-    if (twin_mode == 2) { if (int e = r.den->level_wait_stream(sc.k, G.s)) return e; }
-    return eval_step(G, r.x, sc.eval_idx, p.graph, twin_mode);
+    if (twin_mode == EVAL_RESTORE) { if (int e = r.den->level_wait_stream(sc.k, G.s)) return e; }
+    return eval_step(r, G, sc.eval_idx, p.graph, twin_mode);
 }
 
 int Sampler::ddim_update(Run& r, const Chain& c, const StepConsts& sc) {
@@ -538,7 +535,7 @@ int Sampler::ddim_update(Run& r, const Chain& c, const StepConsts& sc) {
         a.noise1 = z1;
     }
     a.mask = nullptr; a.gt = nullptr; a.noise2 = nullptr; a.blend = 0; a.clip = o.clip_denoised;
-    a.overlap_len = o.overlap_len; a.frames = r.den->frames; a.channels = channels; a.n = c.cnt;
+    a.overlap_len = o.overlap_len; a.frames = r.den->frames(); a.channels = channels; a.n = c.cnt;
     const size_t toff = (size_t)c.b0 * o.overlap_len * channels;
     a.tail_in = nullptr; a.tail_out = r.son ? tail_tmp + toff : nullptr;
     if (r.masked) {
@@ -592,7 +589,7 @@ int Sampler::init_x(Run& r) {
         if (int e = launch_fill_step(c.t, c.c1, c.c2, c.lvl, (int64_t)tb.tmap[k], (float)sqrt(tb.ac[k]), (float)sqrt(1.0 - tb.ac[k]), (int64_t)k, c.nb, c.s)) return e;
         QSampleArgs a{};
         a.out = r.x + c.off; a.x0 = r.x + c.off; a.noise = z; a.a = c.c1; a.s = c.c2;
-        a.n = c.cnt; a.frames = r.den->frames; a.channels = channels; a.c_lo = c.c_lo; a.c_hi = c.c_hi; a.fixed_from = -1;
+        a.n = c.cnt; a.frames = r.den->frames(); a.channels = channels; a.c_lo = c.c_lo; a.c_hi = c.c_hi; a.fixed_from = -1;
         if (int e = launch_q_sample(a, c.s)) return e;
     }
     return 0;
@@ -624,7 +621,7 @@ int Sampler::loop(Run& r, const LoopPlan& p) {
 
 // the joins (on every exit path of loop(): the chains write x, trace and the noisy tails the caller may free) and what follows them
 int Sampler::finish(Run& r, int rc) {
-    DenoiserBase* den = r.den; const int B = r.B;
+    DenoiserContext* den = r.den; const int B = r.B;
     note_launch_value(LC_SAMPLE_STREAMS, (long long)r.chains.size());
     note_launch_value(LC_SAMPLE_GRAPH, replayed() ? 1 : 0);
     note_launch_value(LC_SAMPLE_PIPE, r.piped ? 1 : 0);
@@ -641,33 +638,33 @@ int Sampler::finish(Run& r, int rc) {
     if (replayed()) { DSH_HIP_CHECK(hipStreamSynchronize(st)); drop_graph(); }
     // one modality alone: the inactive columns of the result are defined — 0, or the given track bit for bit — whatever x held there (one launch
     // behind the join, like the ragged zeroing that follows it)
-    if (rc == 0 && r.mod == 1) { if (int e = launch_fill_cols(r.x, channels, (size_t)B * den->frames, 0, r.gcols, nullptr, 0, st)) return e; }
+    if (rc == 0 && r.mod == 1) { if (int e = launch_fill_cols(r.x, channels, (size_t)B * den->frames(), 0, r.gcols, nullptr, 0, st)) return e; }
     if (rc == 0 && r.mod == 2) {
         const float* track = den->modality_track();
         DSH_REQUIRE(track != nullptr, "gesture modality without its expression track");
-        if (int e = launch_fill_cols(r.x, channels, (size_t)B * den->frames, r.gcols, channels, track, channels - r.gcols, st)) return e;
+        if (int e = launch_fill_cols(r.x, channels, (size_t)B * den->frames(), r.gcols, channels, track, channels - r.gcols, st)) return e;
     }
     // ragged batch: the loop ran on the padded rows; its result is defined as exactly 0 beyond every clip's length (one launch behind the join,
     // whatever regime the loop ran in; rows of `trace` keep the padded frames' values)
-    if (rc == 0 && r.len_d) return launch_zero_padded_frames(r.x, r.len_d, B, den->frames, channels, st);
+    if (rc == 0 && r.len_d) return launch_zero_padded_frames(r.x, r.len_d, B, den->frames(), channels, st);
     return rc;
 }
 
-int Sampler::run(DenoiserBase* den, const SamplerOpts& o, float* x, int init, const float* gt,
+int Sampler::run(DenoiserContext* den, const SamplerOpts& o, float* x, int init, const float* gt,
                  const uint8_t* mask, bool masked, const float* noise_stack, int64_t n_draws, float* trace) {
     return run_schedule(den, o, x, init, gt, mask, masked, noise_stack, n_draws, trace, start_level, 0, 0);
 }
 
-int Sampler::invert(DenoiserBase* den, const SamplerOpts& o, float* x, int from_level, int to_level, float* trace) {
+int Sampler::invert(DenoiserContext* den, const SamplerOpts& o, float* x, int from_level, int to_level, float* trace) {
     DSH_REQUIRE(to_level >= 1 && from_level >= 0 && from_level < to_level, "invert: needs 0 <= from_level < to_level");
     DSH_REQUIRE(o.kind == 0 && o.eta == 0.f, "invert: the reverse ODE exists for the DDIM loops at eta = 0 only");
     DSH_REQUIRE(!o.same_overlap_noisy && !tail_blend && start_level == 0, "invert: same_overlap_noisy, the tail blend and a start level do not apply to the reverse loop");
     return run_schedule(den, o, x, 1, nullptr, nullptr, false, nullptr, 0, trace, 0, to_level, from_level);
 }
 
-int Sampler::run_schedule(DenoiserBase* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask, bool masked,
+int Sampler::run_schedule(DenoiserContext* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask, bool masked,
                           const float* noise_stack, int64_t n_draws, float* trace, int start, int invert_to, int invert_from) {
-    DSH_REQUIRE(den && den->batch > 0, "set_condition() must precede sample()");
+    DSH_REQUIRE(den && den->batch() > 0, "set_condition() must precede sample()");
     DSH_REQUIRE(init >= 0 && init <= 2, "unknown init mode");
     DSH_REQUIRE(init != 2 || o.kind == 0, "init mode 2 (x holds x0) exists for the DDIM loops only");
     DSH_REQUIRE(start == 0 || (o.kind == 0 && !o.same_overlap_noisy && !tail_blend),
@@ -677,13 +674,13 @@ int Sampler::run_schedule(DenoiserBase* den, const SamplerOpts& o, float* x, int
     DSH_REQUIRE(o.noise_mode == 0 || o.noise_mode == 1, "unknown noise mode");
     DSH_REQUIRE(!(masked && o.kind == 1), "mask-present DDPM (p_sample_loop_progressive_harmonize) is not supported");
     DSH_REQUIRE(!(tail_blend && o.same_overlap_noisy), "tail_blend with same_overlap_noisy: the saved noisy tails describe a window chain, not a window pinned at both ends");
-    DSH_REQUIRE(!tail_blend || (o.overlap_len >= 0 && 2 * (int64_t)o.overlap_len <= den->frames), "tail_blend: the head and the tail fade overlap (2 * overlap_len > frames)");
+    DSH_REQUIRE(!tail_blend || (o.overlap_len >= 0 && 2 * (int64_t)o.overlap_len <= den->frames()), "tail_blend: the head and the tail fade overlap (2 * overlap_len > frames)");
     Run r{den, o, x, init, gt, mask, masked, noise_stack, n_draws, trace, start, invert_from, invert_to};
-    const int B = r.B = den->batch;
+    const int B = r.B = den->batch();
     // One modality alone (denoiser.h, set_modality): the loop advances the active encoder's column window [w_lo, w_hi) only — every step launch
     // of every regime takes it — and its result holds 0 (expression mode) or the given track (gesture mode) in the other columns.  Noise
     // addressing stays that of the full-width row, so an active column receives the value it receives in the joint run.
-    const int mod = r.mod = den->modality, gcols = r.gcols = den->gesture_channels();
+    const int mod = r.mod = den->modality(), gcols = r.gcols = den->gesture_channels();
     DSH_REQUIRE(mod == 0 || (gcols > 0 && gcols < channels), "a partial modality needs the UniDiffuser's two encoders");
     DSH_REQUIRE(mod == 0 || !o.same_overlap_noisy, "same_overlap_noisy with a partial modality: the saved noisy tails describe all channels");
     r.w_lo = mod == 1 ? gcols : 0; r.w_hi = mod == 0 ? 0 : (mod == 1 ? channels : gcols);      // (0, 0: all columns)
@@ -696,10 +693,10 @@ int Sampler::run_schedule(DenoiserBase* den, const SamplerOpts& o, float* x, int
         for (int b = 0; b < B; ++b) DSH_REQUIRE(((int64_t)len_h[b] * channels) % 4 == 0, "row keys on a ragged batch: length * channels must be a multiple of 4 for every clip");
     // loop_begin() marks the batch as deliberately unsplit; the mark is taken back on EVERY way out of this function (an argument error or a
     // failed launch below must not leave the context answering later evaluations as if a loop were still running)
-    struct LoopScope { DenoiserBase* d; ~LoopScope() { (void)d->loop_end(); } } loop_scope{den};
+    struct LoopScope { DenoiserContext* d; ~LoopScope() { (void)d->loop_end(); } } loop_scope{den};
     if (int e = den->loop_begin(o.kind)) return e;          // (may re-condition a mid-size batch as one batch: the two encoder chains replace the sub-batch streams)
     den->t_uniform = emb_dedup_enabled();   // every evaluation of a sampling loop runs the whole batch at ONE timestep (launch_fill_step)
-    r.n = (size_t)B * den->frames * channels; r.row_n = r.n / B;
+    r.n = (size_t)B * den->frames() * channels; r.row_n = r.n / B;
     if (int e = prepare(r)) return e;
     if (int e = make_chains(r)) return e;
     const LoopPlan p = plan(r);

@@ -160,7 +160,7 @@ inline bool ffn_keeps_hi_plane() { return (ffn_pb() & 1) && ffn_pc() == 1; }
 // the value its context read at construction
 inline int gemm_ksplit_rows() { return (int)switch_int(SW_GEMM_KSPLIT); }
 inline int gemm_ksplit_rows_context() { return (int)switch_int_now(SW_GEMM_KSPLIT); }
-// loops of at most this many token rows run as one batch on two encoder streams (sampler, latched; DualDenoiser per context)
+// loops of at most this many token rows run as one batch on two encoder streams (sampler, latched; DenoiserContext per context)
 inline size_t pipe_rows() { return (size_t)switch_int(SW_PIPE_ROWS); }
 inline size_t pipe_rows_context() { return (size_t)switch_int_now(SW_PIPE_ROWS); }
 // the pipelined loop restores every head from the slots a side-stream prefetch run fills: all three must be on

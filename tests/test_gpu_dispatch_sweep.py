@@ -1,7 +1,7 @@
 """Evaluations and sampling loops on BOTH sides of every kernel-dispatch boundary, on a real MI355X.
 
 The denoiser picks a kernel family per launch from the shape of the call (row counts, frames per window, clips per batch); the limits
-live in denoiser.hip, sampler.hip and the launchers.  This file mirrors those rules in plain Python (`expected_launches`), asks the
+live in denoiser.hip, denoiser_context.hip, sampler.hip and the launchers.  This file mirrors those rules in plain Python (`expected_launches`), asks the
 library which families actually ran (`dsh_debug_launch_counts`, host-side counters) and compares every case with the CPU oracle.  A
 limit that moves in the C++ without moving here fails the counter assertion of the cases that straddle it, instead of silently
 testing one side twice.
@@ -44,7 +44,7 @@ FFN_FUSE_ROWS = 128 * 64                                               # tl2.hip
 HL_STY_ROWS, HL_F3_ROWS = 128 * 256, 128 * 128                         # denoiser.hip tl(): hl2
 ROLL_MIN_BLOCKS = 128                                                  # tl2.hip launch_tl2_linear: N split below this many token blocks
 ATTN_MFMA_FRAMES = 96                                                  # denoiser.hip run_encoder
-SPLIT = {"bf16": (12288, 21500), "fp32": (4096, 2900)}                 # denoiser.hip DualDenoiser: (min rows, rows per stream)
+SPLIT = {"bf16": (12288, 21500), "fp32": (4096, 2900)}                 # denoiser_context.hip: (min rows, rows per stream)
 F32_FEWROW = 512                                                       # denoiser.hip f32_min_rows / gemm.hip ks_rows
 GRAPH_ROWS, PIPE_ROWS = 4096, 64499                                    # sampler.hip
 
@@ -60,7 +60,7 @@ def _round_up(a, b):
 
 
 def n_streams(prec, B, T):
-    """DualDenoiser::want_split (default DSH_DUAL = 3, profiler off)."""
+    """DenoiserContext: want_split (default DSH_DUAL = 3, profiler off)."""
     rows = B * T
     min_rows, per_stream = SPLIT[prec]
     if rows < min_rows:
@@ -69,7 +69,7 @@ def n_streams(prec, B, T):
 
 
 def sub_batches(B, ns):
-    """DualDenoiser::first_clip: clips [B i / ns, B (i + 1) / ns)."""
+    """DenoiserContext: first_clip, clips [B i / ns, B (i + 1) / ns)."""
     return [(B * i // ns, B * (i + 1) // ns) for i in range(ns)]
 
 
@@ -195,19 +195,19 @@ BOUNDARIES = [
     dict(name="MFMA attention up to 96 frames, row-major fallback above", where="denoiser.hip run_encoder (fr <= 96)",
          side=lambda c: c[3] <= 96,
          cases=[(S, "bf16", 5, 96), (S, "bf16", 5, 97), (S, "bf16", 5, 120)]),
-    dict(name="bf16: two sub-batch streams from 12288 token rows", where="denoiser.hip DualDenoiser min_rows_",
+    dict(name="bf16: two sub-batch streams from 12288 token rows", where="denoiser_context.hip min_rows_",
          side=lambda c: c[2] * c[3] >= 12288,
          cases=[(S, "bf16", 191, 64), (S, "bf16", 192, 64), (S, "bf16", 139, 88), (S, "bf16", 140, 88), (Sg, "bf16", 139, 88), (Sg, "bf16", 140, 88)]),
-    dict(name="bf16: three sub-batch streams from 64500 token rows", where="denoiser.hip DualDenoiser rows_per_stream_",
+    dict(name="bf16: three sub-batch streams from 64500 token rows", where="denoiser_context.hip rows_per_stream_",
          side=lambda c: c[2] * c[3] >= 64500,
          cases=[(S, "bf16", 732, 88), (S, "bf16", 733, 88)]),
     dict(name="fp32: few-row K-split GEMM up to 512 rows, gemm_f32_pro above", where="denoiser.hip f32_min_rows, gemm.hip ks_rows",
          side=lambda c: c[2] * c[3] <= 512,
          cases=[(Bt, "fp32", 15, 34), (Bt, "fp32", 16, 34), (S, "fp32", 8, 64), (S, "fp32", 8, 65)]),
-    dict(name="fp32: two sub-batch streams from 4096 token rows", where="denoiser.hip DualDenoiser (precision 0)",
+    dict(name="fp32: two sub-batch streams from 4096 token rows", where="denoiser_context.hip (precision 0)",
          side=lambda c: c[2] * c[3] >= 4096,
          cases=[(Bt, "fp32", 120, 34), (Bt, "fp32", 121, 34), (S, "fp32", 63, 65), (S, "fp32", 64, 64)]),
-    dict(name="fp32: three sub-batch streams from 8700 token rows", where="denoiser.hip DualDenoiser (precision 0)",
+    dict(name="fp32: three sub-batch streams from 8700 token rows", where="denoiser_context.hip (precision 0)",
          side=lambda c: c[2] * c[3] >= 8700,
          cases=[(Bt, "fp32", 255, 34), (Bt, "fp32", 256, 34)]),
 ]
@@ -520,7 +520,7 @@ def _picks(B):
 
 
 def _loop_flags(B, T, prec, kind, pipe_env, ddim=True, trace=False):
-    """(graphs, pipeline, sub-batch streams) of a plain loop (sampler.hip, DualDenoiser::loop_begin)."""
+    """(graphs, pipeline, sub-batch streams) of a plain loop (sampler.hip, DenoiserContext::loop_begin)."""
     rows = B * T
     pipe_ok = kind != "single" and pipe_env
     unsplit = pipe_ok and rows <= PIPE_ROWS
@@ -677,7 +677,7 @@ def test_outpainting_window_equals_its_rows_sampled_alone(B):
 def test_evaluation_does_not_depend_on_a_loop_run_before_it():
     """SHOW bf16, B = 200 (two sub-batch streams for an evaluation, one batch on the two-encoder pipeline for a loop): eval -> ddim loop ->
     eval with unchanged inputs.  The loop re-conditions the batch unsplit and set_condition keeps that shape unsplit for the NEXT loop
-    (sticky shape), but an evaluation always goes back to its own split (DualDenoiser::eval: want_split unless a loop is running), so
+    (sticky shape), but an evaluation always goes back to its own split (DenoiserContext::eval: want_split unless a loop is running), so
     both evaluations report two streams; they are bit-identical and match the oracle.  A dsh_sample call that is refused after it
     began the loop must not leave the `loop running` mark behind: the evaluation after it still reports two streams."""
     from diffsheg_amd.model import UniDiffuser

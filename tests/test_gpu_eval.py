@@ -175,8 +175,8 @@ def test_eval_fp32_config2_batch_sampled_clips_match_oracle():
 
 @pytest.mark.parametrize("precision,B", [("bf16", 380), ("fp32", 380), ("bf16", 930)])
 def test_large_batch_two_stream_split_is_bit_identical(precision, B, monkeypatch):
-    """Batches of >= 12288 token rows are evaluated as two (>= 64500: three) sub-batches on as many streams (denoiser.hip,
-    DualDenoiser); clips are independent, so the result must equal the single-stream evaluation bit for bit.
+    """Batches of >= 12288 token rows are evaluated as two (>= 64500: three) sub-batches on as many streams (denoiser_context.hip,
+    DenoiserContext); clips are independent, so the result must equal the single-stream evaluation bit for bit.
     B = 380: 33 440 rows, split 190 | 190 with CFG doubling inside; B = 930: 81 840 rows, three streams of 310."""
     from diffsheg_amd.model import UniDiffuser
     cfg = get_config("show")
@@ -196,6 +196,47 @@ def test_large_batch_two_stream_split_is_bit_identical(precision, B, monkeypatch
         del model
     assert torch.isfinite(outs[0]).all()
     assert torch.equal(outs[0], outs[1])
+
+
+def test_resplit_of_a_conditioned_batch_keeps_per_instance_state():
+    """A conditioned batch is re-split between evaluations when the profiler is switched on (one stream) and off again (denoiser_context.hip,
+    eval: apply_condition): every instance is conditioned anew from the context-owned copies — its clips' lengths, guidance scales and, with
+    the gesture modality, its rows of the given expression track.  fp32, 48 x 88 = 4 224 token rows: two streams of 24 clips, just over the
+    4 096-row threshold.  The three evaluations (2, 1, 2 streams) must agree bit for bit on every clip's valid frames."""
+    from diffsheg_amd import _lib
+    from diffsheg_amd.model import UniDiffuser
+    cfg = get_config("show")
+    B, T = 48, 88
+    inp = make_inputs(cfg, B, frames=T, seed=48)
+    g = torch.Generator().manual_seed(4224)
+    lengths = torch.randint(20, 89, (B,), generator=g)
+    scales = (1.0 + 0.5 * torch.rand(B, generator=g)).tolist()
+    scales[0] = scales[B // 2] = 1.0                          # a clip at exactly 1 in each sub-batch takes the conditional half
+    track = torch.randn(B, T, cfg.expression_dim, generator=g).cuda()
+    t = torch.tensor([(37 * i + 5) % 1000 for i in range(B)])
+    shape_e = (B, T, cfg.expression_dim)
+    sa = [(1.0 + 0.01 * torch.arange(B, dtype=torch.float32)).view(B, 1, 1).expand(shape_e),
+          (0.5 + 0.005 * torch.arange(B, dtype=torch.float32)).view(B, 1, 1).expand(shape_e)]
+    model = UniDiffuser(cfg, synthetic_sd("show"), device="cuda:0", precision="fp32")
+    model.set_guidance_scale(scales)
+    x, a, p, h = (inp[k].cuda() for k in ("x_T", "audio_emb", "person_id", "pretrain_aud_feat"))
+    lib = _lib.lib()
+    for kw in ({}, {"modality": "gesture", "expression": track}):
+        outs, streams = [], []
+        for prof in (None, 1, 0):
+            if prof is not None:
+                _lib.check(lib.dsh_profile_enable(model._h, prof))
+            _lib.launch_counts(reset=True)
+            eps = model(x, t.cuda(), sqrt_alphas=sa, audio_emb=a, length=lengths, person_id=p, add_cond={"pretrain_aud_feat": h},
+                        pe_type="pe_sinu", y={}, **kw)
+            torch.cuda.synchronize()
+            streams.append(_lib.launch_counts()["eval_streams"])
+            outs.append(torch.cat([eps[b, :n].reshape(-1) for b, n in enumerate(lengths.tolist())]).clone())
+        print(f"[re-split {kw.get('modality', 'both')}] eval_streams {streams}")
+        assert streams == [2, 1, 2]
+        assert torch.isfinite(outs[0]).all()
+        assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+    del model
 
 
 @pytest.mark.parametrize("ds,B,T", [("show", 1, 88), ("show", 3, 88), ("show", 2, 11), ("show", 5, 40), ("beat", 4, 34), ("show", 12, 88),

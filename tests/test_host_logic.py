@@ -209,3 +209,25 @@ def test_kernel_build_id_covers_every_source_and_the_compile_flags():
             assert os.path.basename(f) in hashed, f
     assert {"Makefile", "denoiser.hip", "capi.hip", "diffsheg_hip.h"} <= hashed
     assert len(buildid.kernel_build_id()) == 16
+
+
+def test_denoiser_interfaces_are_all_pure_and_the_one_base_is_gone():
+    """csrc/denoiser.h declares two interfaces, DenoiserInstance (one model on one stream) and DenoiserContext (what a dsh_ctx owns).
+    Neither carries a method whose body means "not supported on this kind of object": every virtual other than a destructor is pure,
+    and the type that once united the two roles, with the class that implemented the context's half of it, is named nowhere in the sources."""
+    import glob
+    csrc = os.path.join(ROOT, "diffsheg_amd", "csrc")
+    hdr = open(os.path.join(csrc, "denoiser.h")).read()
+    code = re.sub(r"//[^\n]*", "", hdr)                                       # (declarations only: comments mention `virtual` too)
+    decls = re.findall(r"\bvirtual\b[^;{]*[;{]", code)
+    assert len(decls) > 40, len(decls)
+    for d in decls:
+        if re.search(r"\bvirtual\s+~", d):
+            continue
+        assert re.search(r"=\s*0\s*;$", d), f"virtual with a default body: {' '.join(d.split())}"
+    for name in ("DenoiserInstance", "DenoiserContext"):
+        assert re.search(rf"\bclass {name} \{{", code), name
+    for f in glob.glob(os.path.join(csrc, "*")):
+        if os.path.isfile(f):
+            text = open(f, errors="replace").read()
+            assert "DenoiserBase" not in text and "DualDenoiser" not in text, f
