@@ -868,7 +868,8 @@ int dsh_op_linear_attention(void* hip_stream, const float* qkv, int32_t nb, int3
 
 // the product kernel works on the tiled layout of the token-per-lane Linears: convert in scratch (test helper).
 // The batch is split into two halves (nh clips, then the rest) with a block-aligned gap between them, like the CFG halves of the denoiser.
-static int attn_tiled_via_scratch(hipStream_t s, const void* qkv, int nb, int nh, int frames, int D, void* y, const int* lens) {
+// rev: the kernel walks the clips in descending order (the denoiser's tl_block_index order); the result is the same, bit for bit.
+static int attn_tiled_via_scratch(hipStream_t s, const void* qkv, int nb, int nh, int frames, int D, void* y, const int* lens, int rev = 0) {
     {
         const int M0 = nh * frames, r0 = dsh::round_up(M0, 128), M1 = (nb - nh) * frames;
         const size_t Mp = (size_t)r0 + dsh::round_up(M1 > 0 ? M1 : 1, 128) + 128;
@@ -880,7 +881,7 @@ static int attn_tiled_via_scratch(hipStream_t s, const void* qkv, int nb, int nh
         char* tq = reinterpret_cast<char*>(sc[0]); char* ty = reinterpret_cast<char*>(sc[1]);
         if (int e = dsh::launch_tile_rows_bf16<dsh::bf16>(q, 3 * D, M0, 3 * D, tq, 3 * D, s)) return e;
         if (M1 > 0) { if (int e = dsh::launch_tile_rows_bf16<dsh::bf16>(q + (size_t)M0 * 3 * D, 3 * D, M1, 3 * D, tq + (size_t)r0 * 3 * D * 2, 3 * D, s)) return e; }
-        if (int e = dsh::launch_linear_attention_tiled(tq, nb, nh, r0, frames, D, ty, s, 0, lens)) return e;
+        if (int e = dsh::launch_linear_attention_tiled(tq, nb, nh, r0, frames, D, ty, s, rev, lens)) return e;
         if (int e = dsh::launch_untile_rows_bf16(ty, D, M0, D, y, D, s)) return e;
         if (M1 > 0) { if (int e = dsh::launch_untile_rows_bf16(ty + (size_t)r0 * D * 2, D, M1, D, reinterpret_cast<dsh::bf16*>(y) + (size_t)M0 * D, D, s)) return e; }
         DSH_HIP_CHECK(hipStreamSynchronize(s));      // the per-call scratch is released on return
@@ -915,6 +916,18 @@ int dsh_op_linear_attention_ragged(void* hip_stream, int32_t dtype, int32_t vari
     if (variant == 0 && head_dim == 64 && frames <= 96) return attn_tiled_via_scratch(s, qkv, nb, lm, frames, D, y, lens_dev);
     return dsh::launch_linear_attention<dsh::bf16>(reinterpret_cast<const dsh::bf16*>(qkv), 3 * D, nb, frames, D, head_dim,
                                                    reinterpret_cast<dsh::bf16*>(y), D, s, lens_dev, lm);
+    API_END
+}
+
+int dsh_op_linear_attention_tiled(void* hip_stream, const void* qkv, int32_t nb, int32_t n_half, int32_t frames, int32_t D, void* y,
+                                  const int32_t* lens_dev, int32_t n_lens, int32_t rev) {
+    API_BEGIN
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    DSH_REQUIRE(qkv && y && nb > 0 && n_half > 0 && n_half <= nb && frames > 0 && frames <= 96 && D > 0 && D % 64 == 0 && (rev == 0 || rev == 1),
+                "linear_attention_tiled: invalid argument (64-channel heads, <= 96 frames, 0 < n_half <= nb, rev 0 or 1)");
+    // (the kernel reads lens[b] in the first half and lens[b - n_half] in the second: the halves must be the CFG halves of the same clips)
+    DSH_REQUIRE(!lens_dev || (n_lens == n_half && (nb == n_lens || nb == 2 * n_lens)), "linear_attention_tiled: with lengths n_half = n_lens and nb = n_lens or 2 * n_lens");
+    return attn_tiled_via_scratch(s, qkv, nb, n_half, frames, D, y, lens_dev, rev);
     API_END
 }
 

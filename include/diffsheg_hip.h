@@ -409,6 +409,12 @@ int dsh_op_linear_attention_bf16(void* hip_stream, const void* qkv, int32_t nb, 
  * shift') with film [n_lens, 2D] = (scale' | shift') per clip (LayerNorm affine folded in by the caller). */
 int dsh_op_linear_attention_ragged(void* hip_stream, int32_t dtype, int32_t variant, const void* qkv, int32_t nb, int32_t frames, int32_t D,
                                    int32_t head_dim, void* y, const int32_t* lens_dev, int32_t n_lens, const float* film);
+/* The tiled bf16 MFMA kernel alone (D % 64 == 0, 64-channel heads, <= 96 frames) through the same scratch conversions, with its two
+ * launch arguments that no other entry reaches: the batch is laid out as n_half clips, a block-aligned gap, then the other nb - n_half
+ * (the CFG halves of the denoiser), and rev = 1 walks the clips in descending order (the result is the same, bit for bit).  With
+ * lens_dev: n_half = n_lens and nb = n_lens or 2 * n_lens. */
+int dsh_op_linear_attention_tiled(void* hip_stream, const void* qkv, int32_t nb, int32_t n_half, int32_t frames, int32_t D, void* y,
+                                  const int32_t* lens_dev, int32_t n_lens, int32_t rev);
 /* out = LayerNorm(x[M,D]) * gamma + beta */
 int dsh_op_layernorm(void* hip_stream, const float* x, int32_t M, int32_t D, const float* gamma, const float* beta,
                      float* out);

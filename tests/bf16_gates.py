@@ -8,8 +8,8 @@ value of the same expression by at most
 assert_rounded / assert_close_f32 check exactly that on EVERY element and name the worst one with its position inside the 32 x 32
 tile, its clip and its frame, so that a routing fault locates itself.
 
-Chains with an internal bf16 rounding point (LayerNorm + FiLM + SiLU prologue, the FFN's hidden and SiLU outputs, the attention's
-k^ / A / q^) cannot be bounded that way: a value that sits on a rounding boundary flips with the last bit of the arithmetic in front
+Chains with an internal bf16 rounding point (LayerNorm + FiLM + SiLU prologue, the FFN's hidden and SiLU outputs, the MFMA attention
+kernels' k^ / A / q^) cannot be bounded that way: a value that sits on a rounding boundary flips with the last bit of the arithmetic in front
 of it, and one flip moves the output by ulp(operand) * |w|.  Their slack is CALIBRATED on the CPU: the chain is evaluated in fp64 and
 in fp32 with the same documented rounding points (and the documented 1e-4 approximation of the fast GELU as a uniform perturbation;
 the kernel's polynomial is not copied), and
@@ -39,6 +39,17 @@ Observed on an MI355X, kernel / calibration (maximum of |out - fp64 chain|, the 
     max / rms, + flip_bound               (257, 88, 3) 1.05 / 0.95   (513, 30, 6) 1.11 / 1.06; kernel maximum 5.8e-3 .. 9.1e-3, flip_bound <= 1.2e-2
                                           offset on b2 (300, 88, 4): rms error 8.0e-4 (0), 8.4e-4 (+20), 1.7e-3 (-100); ln_raw_moment_slack allows far
                                           more at -100 (1.3 at the worst element: its bound is the worst case of 128 fp32 additions)
+  attention, per kernel form              worst element / allowance (0.5 ulp of a bf16 store + 3 x calibration [+ attn_flip_slack]), the largest over the six input
+    (test_gpu_bf16_attention_families.py, families, dense / ragged / CFG-doubled, and the family and shape that produced it:
+     bf16_gates.ATTN_FORMS)               tiled MFMA      0.999 plain, T 11, 3 clips dense (the store's half ulp; calibration 1.1e-6); WITHOUT attn_flip_slack 10.2 (v_small, T 11)
+                                          row-major MFMA  0.999 plain, T 11, 3 clips dense; without attn_flip_slack 1.86 (plain, T 88, dense)
+                                          tiled, two halves and rev (dsh_op_linear_attention_tiled)  0.999 plain, T 34, 3 + 3 clips ragged; without 2.04 (v_small, T 88)
+                                          pre-loaded VALU bf16 0.999 v_small, D 128, T 11 dense     fp32 0.417 v_out, D 128, T 96, 7 clips ragged (kernel / calibration 1.25)
+                                          loop VALU       bf16 0.999 plain, D 128, T 97 dense       fp32 0.667 k_tie, D 128, T 120, 7 clips ragged (kernel / calibration 2.0)
+                                          Derived term: attn_flip_slack, MFMA forms only.  Without it 9 of the 48 dense MFMA cases failed, each in 1 .. 12 elements fed by
+                                          an operand that the fp64 chain puts on a bf16 rounding tie - e.g. k^ = 0.22314 of frame 8, channel
+                                          23, head 2, clip 2 at T 11, 1.9e-8 (relative) from the tie: the tiled kernel rounds it to the other neighbour than the row-major kernel and both CPU chains, and
+                                          ulp(k^) |v| = 3.3e-3 then moves A[23][29] = 9.1e-3 by 54 of its ulps.  The VALU forms needed no term.
 Every mutant of test_bf16_gates_cpu.py is rejected with these gates.
 
 The input builders below restate the generator sequences of the op tests in test_gpu_ops.py, so that test_bf16_gates_cpu.py checks the
@@ -281,27 +292,212 @@ def ffn_chain(t, Mv, T, nb, n_const, dt, reverse=False, noise=None, film_rows=No
     return y
 
 
-# ---- bf16 linear attention (test_linear_attention_bf16_mfma) ------------------------------------------------------------------------
-def attn_inputs(nb, T):
-    g = torch.Generator().manual_seed(T + nb)
-    return (torch.randn(nb, T, 3 * 512, generator=g) * 2).bfloat16()
+# ---- linear attention: every bf16 kernel form of attention.hip and the fp32 instantiations of its VALU templates ------------------------
+# Rounding points, read from attention.hip:
+#   linear_attention_tiled_kernel, linear_attention_mfma_kernel (hd 64, <= 96 frames): exp, sums and 1 / sum in fp32; k^ = e * inv is rounded to
+#     bf16 AFTER the normalisation (pack2_bf16 of the product), A = k^T v is accumulated in fp32 and rounded to bf16 as the operand of the second
+#     product, q^ = e * inv is rounded to bf16, y is accumulated in fp32 and stored rounded to nearest: rounded=True.
+#   linear_attention_pre_kernel, linear_attention_kernel (bf16 and fp32 storage, hd 16 and 64): to_f32 at the loads, everything in fp32 registers
+#     and LDS (k^, A, q^ are never rounded), from_f32 (round to nearest even) at the store: rounded=False.  One accumulator per output, frames
+#     (A) and channels (y) ascending: seq=True evaluates the fp32 chain in that class of order, and its reverse.
+ATTN_FAMILIES = ("plain", "v_out", "v_small", "k_sat", "q_sat", "k_tie")
+# form -> (dtype argument of dsh_op_linear_attention_ragged, variant, the kernel rounds k^ / A / q^ to bf16, ((D, hd, T), ...)): the smallest
+# shapes at which each form changes behaviour (one frame block of 12, 32-frame groups of q, the 96-frame limit and the first length above it)
+ATTN_FORMS = {
+    "tiled": (1, 0, True, tuple((512, 64, T) for T in (11, 33, 88, 96))),
+    "mfma": (1, 1, True, tuple((512, 64, T) for T in (11, 33, 88, 96))),
+    "pre_bf16": (1, 1, False, tuple((128, 16, T) for T in (11, 34, 96))),
+    "pre_f32": (0, 0, False, tuple((128, 16, T) for T in (11, 34, 96))),
+    "loop_bf16": (1, 1, False, ((128, 16, 97), (128, 16, 120), (512, 64, 97), (512, 64, 120))),
+    "loop_f32": (0, 0, False, ((128, 16, 97), (128, 16, 120), (512, 64, 97), (512, 64, 120))),
+}
+ATTN_ROWS = [(form, D, hd, T) for form, (_, _, _, shapes) in ATTN_FORMS.items() for D, hd, T in shapes]
+ATTN_NB = 3                 # dense batches: odd, so the tiled helper's two halves are 2 and 1 clips
 
 
-def attn_chain(qkv, dt, lens=None, hd=64, rounded=True):
-    """y = softmax_channels(q) (softmax_time(k)^T v) per head; with `rounded`, k^, A = k^T v and q^ are rounded to bf16 as the MFMA
-    kernels do.  lens: frames per clip that enter the time-softmax (rows behind them are excluded by selection)."""
+def attn_lens(T):
+    """Lengths of a ragged batch padded to T frames: one frame, the edges of the kernels' frame blocks (12 k, 32, 33), T - 1 and T."""
+    return sorted({1, 12, 24, 32, 33, T - 1, T} & set(range(1, T + 1)))
+
+
+def attn_inputs(nb, T, family="plain", D=512, hd=64):
+    """qkv [nb, T, 3 D] in bf16.  The families are applied before the rounding; "plain" at D = 512 is the recipe of
+    test_linear_attention_bf16_mfma, generator sequence included."""
+    g = torch.Generator().manual_seed(T + nb + (512 - D))
+    x = torch.randn(nb, T, 3 * D, generator=g) * 2
+    if family == "v_out":                     # A = sum k^ v = 300 sum k^ in that column: the normalisation against k^'s rounding point
+        x[:, :, 2 * D + 7] = 300.0
+    elif family == "v_small":                 # gates that scale with a clamped range; flushing
+        x[:, :, 2 * D:] *= 1e-3
+    elif family == "k_sat":                   # max-subtraction, exp(-40), weights of exactly 1 and 0
+        x[:, T // 2, D:2 * D] += 40.0
+    elif family == "q_sat":                   # the same for the channel softmax
+        x[:, :, :D].view(nb, T, D // hd, hd)[..., 3] += 30.0
+    elif family == "k_tie":                   # weights of 1 / n, which bf16 cannot represent; a wrong frame count
+        x[:, :, D:2 * D] = x[:, :1, D:2 * D]
+    elif family != "plain":
+        raise ValueError(family)
+    return x.bfloat16()
+
+
+def attn_chain(qkv, dt, lens=None, hd=64, rounded=True, reverse=False, seq=False, frames_delta=0, k_round_early=False, q_group=None, fast_exp=False):
+    """y = softmax_channels(q) (softmax_time(k)^T v) per head, [nb, T, D] in dtype dt.
+    rounded: the values rounded to bf16 on the way - True = ("k", "A", "q") as the MFMA kernels do, False = none (the VALU templates), or a
+             tuple of those names (the mutants of the VALU forms).
+    lens:    frames per clip that enter the time-softmax, clip b takes lens[b % len(lens)] (rows behind them are excluded by selection;
+             every one of the T query rows is answered).  A list of nb entries gives every clip its own length (the lens[b] mutant).
+    reverse: the order of every accumulation flipped (frames in the time-softmax and in A, channels in y).
+    seq:     fp32 only: one accumulator per output, the terms added one at a time (sum of the exponentials, A over the frames, y over the
+             head's channels) - the class of order of the VALU kernels; otherwise torch's softmax and einsum.
+    fast_exp: both softmaxes as e = exp2(x log2e - max log2e), e * (1 / sum e) in dt - the MFMA kernels' documented evaluation (their
+             v_exp_f32 itself is not copied): an fp32 chain whose roundings fall elsewhere than torch's, for the CPU proof of attn_flip_slack.
+    Mutants: frames_delta = +1 / -1: one frame more / fewer in the time-softmax and in A (never fewer than one; the frame behind a full
+             window is the clamped load every kernel issues, a duplicate of frame T - 1);  k_round_early: e = exp(k - max) rounded to bf16,
+             the normalisation applied behind the rounding;  q_group: the channel softmax taken over groups of that many channels."""
     nb, T, D3 = qkv.shape
     D = D3 // 3
     H = D // hd
-    r = (lambda v: rne(v, dt)) if rounded else (lambda v: v)
+    pts = ("k", "A", "q") if rounded is True else tuple(rounded or ())
+    r = lambda name, v: rne(v, dt) if name in pts else v
+    seq = seq and dt == torch.float32
     out = torch.zeros(nb, T, D, dtype=dt)
     for b in range(nb):
-        n = T if lens is None else lens[b % len(lens)]
+        n = max(1, (T if lens is None else int(lens[b % len(lens)])) + frames_delta)
         q, k, v = (qkv[b, :, i * D:(i + 1) * D].to(dt).view(T, H, hd) for i in range(3))
-        kh = r(k[:n].softmax(dim=0))
-        A = r(torch.einsum("nhd,nhl->hdl", kh, v[:n]))
-        out[b] = torch.einsum("nhd,hdl->nhl", r(q.softmax(dim=-1)), A).reshape(T, D)
+        if n > T:
+            k, v = torch.cat((k, k[T - 1:]), 0), torch.cat((v, v[T - 1:]), 0)
+        k, v = k[:n], v[:n]
+        if reverse:
+            k, v = k.flip(0), v.flip(0)
+        if fast_exp:
+            L = torch.tensor(1.44269504088896341, dtype=dt)
+            sm = lambda x, dim: (lambda e: e * (1 / e.sum(dim=dim, keepdim=True)))(torch.exp2(x * L + (-x.max(dim=dim, keepdim=True).values * L)))
+            kh, qh = r("k", sm(k, 0)), r("q", sm(q, -1))
+        elif k_round_early or seq:
+            e = (k - k.max(dim=0).values).exp()
+            ssum = e.sum(0)
+            if seq:
+                ssum = torch.zeros(H, hd)
+                for t in range(n):
+                    ssum += e[t]
+            kh = rne(e, dt) / ssum if k_round_early else r("k", e * (1 / ssum))
+        else:
+            kh = r("k", k.softmax(dim=0))
+        if not fast_exp:
+            qh = r("q", q.reshape(T, D // (q_group or hd), q_group or hd).softmax(dim=-1).view(T, H, hd))
+        if seq:
+            A = torch.zeros(H, hd, hd)
+            for t in range(n):
+                A.addcmul_(kh[t][:, :, None], v[t][:, None, :])
+            A = r("A", A)
+            y = torch.zeros(T, H, hd)
+            for d in (range(hd - 1, -1, -1) if reverse else range(hd)):
+                y.addcmul_(qh[:, :, d, None], A[None, :, d, :])
+        else:
+            A = r("A", torch.einsum("nhd,nhl->hdl", kh, v))
+            y = torch.einsum("nhd,hdl->nhl", qh.flip(2), A.flip(1)) if reverse else torch.einsum("nhd,hdl->nhl", qh, A)
+        out[b] = y.reshape(T, D)
     return out
+
+
+def attn_valid(nb, T, lens=None):
+    """[nb, T] bool: the query rows whose value is specified (frames inside the clip's length)."""
+    n = torch.tensor([T if lens is None else int(lens[b % len(lens)]) for b in range(nb)])
+    return torch.arange(T)[None, :] < n[:, None]
+
+
+def attn_gate(qkv, hd, rounds, lens=None):
+    """(fp64 chain, calibration, flip allowance) of one kernel form on these operands: calibration = max |fp32 chain - fp64 chain| over the
+    valid rows; for the VALU forms (rounds = False) the maximum over both orders of the one-accumulator fp32 chain, as f32_gates.gate takes
+    it.  The gate of every form and family is assert_rounded / assert_close_f32 with slack MARGIN x calibration, plus, for the MFMA forms,
+    attn_flip_slack (an [nb, T, D] tensor; 0.0 for the VALU forms, whose only rounding is the store)."""
+    kw = dict(lens=lens, hd=hd, rounded=rounds)
+    ref = attn_chain(qkv, torch.float64, **kw)
+    valid = attn_valid(qkv.shape[0], qkv.shape[1], lens)
+    cal = max(float((attn_chain(qkv, torch.float32, reverse=rev, seq=not rounds, **kw).double() - ref)[valid].abs().max())
+              for rev in ((False,) if rounds else (False, True)))
+    return ref, cal, (attn_flip_slack(qkv, hd, lens) if rounds else 0.0)
+
+
+def _tie_distance(x):
+    """distance of |x| from the nearest midpoint between two neighbouring bf16 values (where round-to-nearest changes its mind)"""
+    u = ulp_bf16(x)
+    return ((x.abs() / u) % 1.0 - 0.5).abs() * u
+
+
+def attn_flip_slack(qkv, hd=64, lens=None):
+    """What the MFMA kernels' fast exponentials may cost, per output element [nb, T, D], from the fp64 operands alone.
+    The kernels evaluate e = exp(x - m) as v_exp_f32(x log2e - m log2e) (tiled: one fma on a rounded -m log2e; row-major: __expf, the rounded
+    product (x - m) log2e).  v_exp_f32 is documented to 1 ulp; the argument carries 2^-24 (|x - m| + |m|) log2e absolute plus 2^-25 |x - m| log2e
+    for the constant, i.e. on e a relative  rel_e <= 2^-24 (1.5 |x - m| + |m| + 2)  - torch's exp, which the calibration chain uses, is good to
+    half an ulp at every argument.  A softmax weight of N terms then carries  eps = rel_e + sum_i p_i rel_e_i + (N + 2) 2^-24  (its own
+    exponential, the sum's, the N fp32 additions, the reciprocal and the product).  That is far below a bf16 ulp, so it shows ONLY where the
+    exact value lies within eps of a rounding tie: there the kernel may round k^ or q^ to the other neighbour (one ulp of the operand).  A
+    flipped k^ moves A = sum_t k^ v by ulp(k^) |v| in front of A's own rounding; together with the accum_bound of the n fp32 products that
+    decides whether A can round the other way, so the rounded A moves by at most  flip(A) = sum_t flip(k^) |v| + one ulp of A where it can
+    round either way  (ulp(k^) |v| exceeds an ulp of A where A is small beside its terms).  The allowance of y[t, l] is the sum over the
+    head's channels d of
+        q^[t, d] flip(A[d, l]) + flip(q^[t, d]) (|A[d, l]| + flip(A[d, l])),    flip(k^ or q^) = its ulp_bf16 where it can round either way, else 0.
+    It is exactly 0 for an output none of whose operands sits on a tie (most of them)."""
+    nb, T, D3 = qkv.shape
+    D = D3 // 3
+    H = D // hd
+    u = 2.0 ** -24
+
+    def soft(x, dim, N):
+        m = x.max(dim=dim, keepdim=True).values
+        a = x - m
+        p = a.exp()
+        p = p / p.sum(dim=dim, keepdim=True)
+        rel_e = u * (1.5 * a.abs() + m.abs() + 2)
+        eps = rel_e + (p * rel_e).sum(dim=dim, keepdim=True) + (N + 2) * u
+        return p, torch.where(_tie_distance(p) <= eps * p, ulp_bf16(p), torch.zeros_like(p))
+
+    out = torch.zeros(nb, T, D, dtype=torch.float64)
+    for b in range(nb):
+        n = T if lens is None else int(lens[b % len(lens)])
+        q, k, v = (qkv[b, :, i * D:(i + 1) * D].double().view(T, H, hd) for i in range(3))
+        k, v = k[:n], v[:n]
+        kh, fk = soft(k, 0, n)
+        qh, fq = soft(q, -1, hd)
+        khr, qhr = rne(kh, torch.float64), rne(qh, torch.float64)
+        A = torch.einsum("nhd,nhl->hdl", khr, v)
+        moved = torch.einsum("nhd,nhl->hdl", fk, v.abs())
+        pert = moved + n * 2.0 ** -23 * torch.einsum("nhd,nhl->hdl", khr, v.abs())
+        fA = moved + torch.where(_tie_distance(A) <= pert, ulp_bf16(A), torch.zeros_like(A))
+        out[b] = (torch.einsum("nhd,hdl->nhl", qhr, fA) + torch.einsum("nhd,hdl->nhl", fq, rne(A, torch.float64).abs() + fA)).reshape(T, D)
+    return out
+
+
+def attn_ratio(out, ref, cal, T, lens=None, extra=0.0):
+    """Largest |out - ref| / allowance over the valid rows, without asserting (printed in front of the assertion; NaN counts as inf)."""
+    o, r = out.detach().cpu().double(), ref.double()
+    allow = torch.full_like(r, MARGIN * cal) + extra
+    if out.dtype == torch.bfloat16:
+        big = torch.maximum(o.abs(), r.abs())
+        allow = allow + 0.5 * ulp_bf16(torch.where(torch.isfinite(big), big, torch.zeros_like(big)))
+    x = (o - r).abs() / allow.clamp_min(1e-300)
+    x = torch.where(torch.isnan(x), torch.full_like(x, float("inf")), x)[attn_valid(o.shape[0], T, lens)]
+    return float(x.max())
+
+
+def attn_check(out, ref, cal, T, lens=None, what="attention", extra=0.0):
+    """The valid rows of a bf16 (assert_rounded) or fp32 (assert_close_f32) output [nb, T, D] against the fp64 chain, slack MARGIN x
+    calibration + extra (a number or [nb, T, D]), clip by clip so that the report names the clip and the frame; returns the largest
+    |diff| / allowance."""
+    nb, D = out.shape[0], out.shape[-1]
+    fn = assert_rounded if out.dtype == torch.bfloat16 else assert_close_f32
+    worst = 0.0
+    for b in range(nb):
+        n = T if lens is None else int(lens[b % len(lens)])
+        slack = MARGIN * cal + (extra[b, :n].reshape(-1, D) if torch.is_tensor(extra) else extra)
+        worst = max(worst, fn(out[b, :n].reshape(-1, D), ref[b, :n].reshape(-1, D), slack, f"{what}, clip {b} of {nb} ({n} frames)", frames=n, nb=1))
+    return worst
+
+
+def attn_wrong_half_lens(lens):
+    """The lens[b] mutant of a CFG-doubled batch: the second half reads what lies behind the n_lens lengths (here: the lengths rotated by one)."""
+    return list(lens) + list(lens[1:]) + list(lens[:1])
 
 
 # ---- fused encoder_aud tail (tl_aud_tail_kernel, D = 128) -----------------------------------------------------------------------------

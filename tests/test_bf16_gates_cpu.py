@@ -286,6 +286,71 @@ def test_attention_mutants_are_rejected(attn):
     _record("attn/padded_frame", float((mut[:, :21].double() - rold[:, :21]).abs().max()) < 2e-2 * max(1.0, float(rold.abs().max())))
 
 
+# ---- every attention kernel form x input family x length of test_gpu_bf16_attention_families.py --------------------------------------------
+# (storage dtype, rounding points) decide the chain and the gate: the tiled and the row-major MFMA kernel share theirs
+ATTN_CPU_ROWS = sorted({(G.ATTN_FORMS[form][0], G.ATTN_FORMS[form][2], D, hd, T) for form, D, hd, T in G.ATTN_ROWS}, reverse=True)
+FRAME_MUTANTS = ("frame_more", "frame_fewer")
+
+
+def _attn_mutants(qkv, dtype, rounds, hd, lens, doubled, ref):
+    """name -> output of a subtly wrong kernel, stored with round-to-nearest in the form's storage type (the truncating store excepted)"""
+    st = torch.bfloat16 if dtype else torch.float32
+    kw = dict(lens=lens, hd=hd)
+    m = {"frame_more": G.attn_chain(qkv, torch.float64, rounded=rounds, frames_delta=1, **kw).to(st),
+         "frame_fewer": G.attn_chain(qkv, torch.float64, rounded=rounds, frames_delta=-1, **kw).to(st)}
+    if dtype:
+        m["truncating_store"] = G.truncate_bf16(ref)
+    if rounds:
+        m["k_rounded_before_normalisation"] = G.attn_chain(qkv, torch.float64, rounded=("A", "q"), k_round_early=True, **kw).to(st)
+    else:
+        m["k_rounded_inside"] = G.attn_chain(qkv, torch.float64, rounded=("k",), **kw).to(st)
+        m["A_rounded_inside"] = G.attn_chain(qkv, torch.float64, rounded=("A",), **kw).to(st)
+    if hd == 16:
+        m["channel_softmax_over_64"] = G.attn_chain(qkv, torch.float64, rounded=rounds, q_group=64, **kw).to(st)
+    if doubled:
+        m["second_half_reads_lens_b"] = G.attn_chain(qkv, torch.float64, rounded=rounds, hd=hd, lens=G.attn_wrong_half_lens(lens)).to(st)
+    return m
+
+
+@pytest.mark.parametrize("mode", ["dense", "ragged", "doubled"])
+@pytest.mark.parametrize("dtype,rounds,D,hd,T", ATTN_CPU_ROWS)
+def test_attention_family_gates_pass_the_chain_and_reject_the_mutants(dtype, rounds, D, hd, T, mode):
+    """On the operands the GPU tests build: the fp64 chain in the form's storage type passes its own gate in every family, every mutant is
+    rejected by at least one family, and what each family can NOT see is pinned: a K-softmax saturated on one middle frame is blind to
+    which other frames enter (dense batch: ratio <= 1 for both frame-count mutants); the other five families each reject both."""
+    lens = None if mode == "dense" else G.attn_lens(T)
+    nb = G.ATTN_NB if lens is None else len(lens) * (2 if mode == "doubled" else 1)
+    st = torch.bfloat16 if dtype else torch.float32
+    seen = {}
+    for family in G.ATTN_FAMILIES:
+        qkv = G.attn_inputs(nb, T, family, D, hd)
+        ref, cal, flips = G.attn_gate(qkv, hd, rounds, lens)
+        assert cal > 0
+        assert G.attn_check(ref.to(st), ref, cal, T, lens, extra=flips) <= 1.0
+        if rounds:          # the fp32 chain with the exponentials taken the kernels' way (exp2 of a rounded x log2e - m log2e): other flips, same gate
+            assert G.attn_check(G.attn_chain(qkv, torch.float32, lens=lens, hd=hd, fast_exp=True).bfloat16(), ref, cal, T, lens, extra=flips) <= 1.0
+        for name, out in _attn_mutants(qkv, dtype, rounds, hd, lens, mode == "doubled", ref).items():
+            ratio = G.attn_ratio(out, ref, cal, T, lens, flips)
+            assert (ratio > 1.0) == _rejected(G.attn_check, out, ref, cal, T, lens, extra=flips)
+            seen.setdefault(name, set())
+            if ratio > 1.0:
+                seen[name].add(family)
+    for name, fams in seen.items():
+        assert fams, f"{name}: no family rejects it at D {D} hd {hd} T {T} ({mode})"
+    for name in FRAME_MUTANTS:
+        assert seen[name] >= set(G.ATTN_FAMILIES) - {"k_sat"}, (name, seen[name])
+        if mode == "dense":
+            assert "k_sat" not in seen[name], name
+
+
+def test_attention_plain_family_is_the_recipe_of_the_op_test():
+    g = torch.Generator().manual_seed(34 + 3)
+    assert torch.equal(G.attn_inputs(3, 34), (torch.randn(3, 34, 3 * 512, generator=g) * 2).bfloat16())
+    assert torch.equal(G.attn_inputs(3, 34, "plain", 512, 64), G.attn_inputs(3, 34))
+    x = G.attn_inputs(3, 34, "q_sat", 128, 16).float().view(3, 34, 3, 8, 16)
+    assert float(x[:, :, 0, :, 3].min()) > 20 and float(x[:, :, 1:, :, 3].max()) < 12
+
+
 # ---- fused encoder_aud tail (D = 128) --------------------------------------------------------------------------------------------------------------
 AUD_SHAPES = [(300, 88, 4), (44, 11, 4), (290, 34, 9)]
 _AUD = {}

@@ -90,8 +90,7 @@ def _oracle_alone(ds, cfg_o, inp, b, n, t, c1, c2, single):
 
 
 # ---- 4. the six attention kernels, each reached by the shape that selects it --------------------------------------------------
-def _attn_lens(T):
-    return sorted({1, 12, 24, 32, 33, T - 1, T} & set(range(1, T + 1)))
+from bf16_gates import attn_lens as _attn_lens  # noqa: E402  (shared with test_gpu_bf16_attention_families.py and the CPU proof of its gates)
 
 
 # (name, dtype, variant, D, head_dim, T): fp32 MFMA kernel at each of its four tile sizes; the pre-loaded VALU kernel (encoder_aud, hd 16);
