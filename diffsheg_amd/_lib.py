@@ -71,6 +71,14 @@ SYMBOLS = {
     "dsh_sample_num_steps_from": (C.c_int64, [C.POINTER(SamplerOptsC), C.c_int32, C.c_int32, C.c_int32]),
     "dsh_invert": (C.c_int, [_P, C.POINTER(SamplerOptsC), _P, C.c_int32, _P]),
     "dsh_invert_from": (C.c_int, [_P, C.POINTER(SamplerOptsC), _P, C.c_int32, C.c_int32, _P]),
+    "dsh_sample_set_timesteps": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32]),
+    "dsh_sample_set_solver": (C.c_int, [_P, C.c_int32]),
+    "dsh_sample_num_draws_subset": (C.c_int64, [C.POINTER(SamplerOptsC), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "dsh_sample_num_steps_subset": (C.c_int64, [C.POINTER(SamplerOptsC), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "dsh_diffusion_table_subset": (C.c_int32, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_char_p, C.POINTER(C.c_double), C.c_int32]),
+    "dsh_solver_coeffs": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
+    "dsh_masked_start_level": (C.c_int32, [C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
+    "dsh_op_dpm2m_step": (C.c_int, [_P] * 7 + [C.c_int32] * 3 + [C.c_float] * 7 + [C.c_int32] * 7),
     "dsh_set_guidance_scale": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32]),
     "dsh_diffusion_table": (C.c_int32, [C.c_int32, C.c_int32, C.c_char_p, C.POINTER(C.c_double), C.c_int32]),
     "dsh_timestep_map": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),

@@ -276,6 +276,17 @@ int64_t dsh_sample_num_steps_from(const dsh_sampler_opts* opts, int32_t masked, 
     if (init < 0 || init > 2) { dsh::set_last_error("unknown init mode"); return -1; }
     return dsh::sampler_num_steps(to_opts(opts), masked != 0, start_level);
 }
+int64_t dsh_sample_num_draws_subset(const dsh_sampler_opts* opts, int32_t masked, int32_t init, int32_t start_level, const int32_t* kept, int32_t n) {
+    if (!opts || n < 0 || (n > 0 && !kept)) { dsh::set_last_error("null argument"); return -1; }
+    const std::vector<int> k(kept, kept + n);
+    return dsh::sampler_num_draws(to_opts(opts), masked != 0, init, start_level, &k);
+}
+int64_t dsh_sample_num_steps_subset(const dsh_sampler_opts* opts, int32_t masked, int32_t init, int32_t start_level, const int32_t* kept, int32_t n) {
+    if (!opts || n < 0 || (n > 0 && !kept)) { dsh::set_last_error("null argument"); return -1; }
+    if (init < 0 || init > 2) { dsh::set_last_error("unknown init mode"); return -1; }
+    const std::vector<int> k(kept, kept + n);
+    return dsh::sampler_num_steps(to_opts(opts), masked != 0, start_level, &k);
+}
 int64_t dsh_sample_num_steps(const dsh_sampler_opts* opts, int32_t masked) {
     if (!opts) { dsh::set_last_error("null opts"); return -1; }
     return dsh::sampler_num_steps(to_opts(opts), masked != 0);
@@ -310,6 +321,20 @@ int dsh_sample_set_start_level(dsh_ctx* ctx, int32_t level) {
     API_END
 }
 
+int dsh_sample_set_timesteps(dsh_ctx* ctx, const int32_t* kept_host, int32_t n) {
+    API_BEGIN
+    DSH_REQUIRE(ctx, "null context");
+    return ctx->sampler->set_timesteps(kept_host, n);
+    API_END
+}
+
+int dsh_sample_set_solver(dsh_ctx* ctx, int32_t solver) {
+    API_BEGIN
+    DSH_REQUIRE(ctx, "null context");
+    return ctx->sampler->set_solver(solver);
+    API_END
+}
+
 int dsh_set_guidance_scale(dsh_ctx* ctx, const float* scales_host, int32_t n) {
     API_BEGIN
     DSH_REQUIRE(ctx, "null context");
@@ -339,11 +364,7 @@ int dsh_invert(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t to_
     return dsh_invert_from(ctx, opts, x, 0, to_level, trace);
 }
 
-int32_t dsh_diffusion_table(int32_t diffusion_steps, int32_t respacing, const char* name, double* out, int32_t cap) {
-    API_BEGIN
-    DSH_REQUIRE(name && out, "null argument");
-    dsh::DiffusionTables tb; std::string err;
-    if (dsh::make_tables(diffusion_steps, respacing, tb, err)) { dsh::set_last_error(err); return -1; }
+static int32_t copy_table(const dsh::DiffusionTables& tb, const char* name, double* out, int32_t cap) {
     const std::string n(name);
     const std::vector<double>* v = nullptr;
     if (n == "betas") v = &tb.betas;
@@ -360,6 +381,44 @@ int32_t dsh_diffusion_table(int32_t diffusion_steps, int32_t respacing, const ch
     DSH_REQUIRE((int32_t)v->size() <= cap, "output buffer too small");
     std::memcpy(out, v->data(), v->size() * sizeof(double));
     return (int32_t)v->size();
+}
+
+int32_t dsh_diffusion_table(int32_t diffusion_steps, int32_t respacing, const char* name, double* out, int32_t cap) {
+    API_BEGIN
+    DSH_REQUIRE(name && out, "null argument");
+    dsh::DiffusionTables tb; std::string err;
+    if (dsh::make_tables(diffusion_steps, respacing, tb, err)) { dsh::set_last_error(err); return -1; }
+    return copy_table(tb, name, out, cap);
+    API_END
+}
+
+int32_t dsh_diffusion_table_subset(int32_t diffusion_steps, const int32_t* kept, int32_t n, const char* name, double* out, int32_t cap) {
+    API_BEGIN
+    DSH_REQUIRE(name && out && kept && n > 0, "null argument / empty subset");
+    dsh::DiffusionTables tb; std::string err;
+    if (dsh::make_tables_kept(diffusion_steps, std::vector<int>(kept, kept + n), tb, err)) { dsh::set_last_error(err); return -1; }
+    return copy_table(tb, name, out, cap);
+    API_END
+}
+
+int dsh_solver_coeffs(int32_t diffusion_steps, const int32_t* kept, int32_t n, int32_t k, double* out3) {
+    API_BEGIN
+    DSH_REQUIRE(out3 && kept && n > 0, "null argument / empty subset");
+    DSH_REQUIRE(k >= 0 && k < n, "solver_coeffs: level outside 0 .. n - 1");
+    dsh::DiffusionTables tb; std::string err;
+    if (dsh::make_tables_kept(diffusion_steps, std::vector<int>(kept, kept + n), tb, err)) { dsh::set_last_error(err); return -1; }
+    dsh::solver_coeffs(tb, k, out3[0], out3[1], out3[2]);
+    return 0;
+    API_END
+}
+
+int32_t dsh_masked_start_level(int32_t diffusion_steps, const int32_t* kept, int32_t n) {
+    API_BEGIN
+    DSH_REQUIRE(n >= 0 && (n == 0 || kept), "null argument");
+    std::string err;
+    const int t = dsh::masked_start_level(diffusion_steps, std::vector<int>(kept, kept + n), err);
+    if (t < 0) dsh::set_last_error(err);
+    return t;
     API_END
 }
 
@@ -1186,6 +1245,36 @@ int dsh_op_ddim_step_full(void* hip_stream, float* x, const float* eps, float* x
     a.clip = clip; a.overlap_len = overlap_len; a.frames = frames; a.channels = channels; a.n = (size_t)B * frames * channels;
     a.tail_in = tail_in; a.tail_out = tail_out; a.c_lo = c_lo; a.c_hi = c_hi;
     return dsh::launch_ddim_step(a, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_dpm2m_step(void* hip_stream, float* x, const float* eps, float* x0_prev, const float* gt, const uint8_t* mask, const float* noise2,
+                      int32_t B, int32_t frames, int32_t channels, float c1, float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev, float A, float Bc,
+                      float G, int32_t second_order, int32_t overlap_len, int32_t blend, int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi) {
+    API_BEGIN
+    DSH_REQUIRE(x && eps && x0_prev && B > 0 && frames > 0 && channels > 0, "invalid argument");
+    DSH_REQUIRE(!mask || (gt && noise2), "dpm2m_step: a mask needs gt and noise2");
+    DSH_REQUIRE(overlap_len >= 0 && overlap_len <= frames, "dpm2m_step: 0 <= overlap_len <= frames");
+    DSH_REQUIRE(!tail_blend || 2 * (int64_t)overlap_len <= frames, "dpm2m_step: tail_blend needs 2 * overlap_len <= frames");
+    DSH_REQUIRE(c_lo >= 0 && c_hi <= channels, "dpm2m_step: channel range outside [0, channels]");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    const int bl = (mask && blend) ? 1 : 0, tbl = (bl && tail_blend) ? 1 : 0;
+    if (!second_order) {
+        // the first-order form is the DDIM step at eta = 0, with its x0 left in the history
+        dsh::DdimStepArgs a;
+        a.x = x; a.eps = eps; a.x0_out = x0_prev; a.c1 = c1; a.c2 = c2; a.sqrt_ab_prev = sqrt_ab_prev; a.sqrt_1m_ab_prev = sqrt_1m_ab_prev;
+        a.coef_eps = sqrt_1m_ab_prev; a.sigma = 0.f; a.noise1 = nullptr;
+        a.mask = mask; a.gt = gt; a.noise2 = noise2; a.blend = bl; a.tail_blend = tbl;
+        a.clip = clip; a.overlap_len = overlap_len; a.frames = frames; a.channels = channels; a.n = (size_t)B * frames * channels;
+        a.tail_in = nullptr; a.tail_out = nullptr; a.c_lo = c_lo; a.c_hi = c_hi;
+        return dsh::launch_ddim_step(a, s);
+    }
+    dsh::Dpm2mStepArgs d;
+    d.x = x; d.eps = eps; d.x0_prev = x0_prev; d.c1 = c1; d.c2 = c2; d.A = A; d.Bc = Bc; d.G = G;
+    d.sqrt_ab_prev = sqrt_ab_prev; d.sqrt_1m_ab_prev = sqrt_1m_ab_prev; d.mask = mask; d.gt = gt; d.noise2 = noise2;
+    d.blend = bl; d.tail_blend = tbl; d.clip = clip; d.overlap_len = overlap_len; d.frames = frames; d.channels = channels;
+    d.n = (size_t)B * frames * channels; d.c_lo = c_lo; d.c_hi = c_hi;
+    return dsh::launch_dpm2m_step(d, s);
     API_END
 }
 

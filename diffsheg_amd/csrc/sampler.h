@@ -14,6 +14,19 @@ struct DiffusionTables {
 void build_tables(const std::vector<double>& betas, DiffusionTables& t);
 std::vector<double> linear_betas(int n);
 int make_tables(int steps, int respacing, DiffusionTables& out, std::string& err);
+// The tables of a free subset of the base process: kept = the original timesteps, strictly ascending, each in [0, steps), at least one.
+// beta'_k = 1 - ac[kept_k] / ac[kept_{k-1}], tmap = kept.  make_tables(steps, K > 0) is this with the 'ddimK' stride's list.
+int make_tables_kept(int steps, const std::vector<int>& kept, DiffusionTables& out, std::string& err);
+int stride_timesteps(int steps, int respacing, std::vector<int>& kept, std::string& err);      // the 'ddimK' list
+// Out-painting start t_T of a subset that is no 'ddimK' stride: 1 + the first level whose alphas_cumprod is at or below that of level 14 of
+// the ddim25 tables of the same base process (where the reference starts a masked window); the top level if there is none.  0 (= the
+// reference's index rule 15 / int(0.6 K)) for an empty list and for a list that is the stride of its own length.
+int masked_start_level(int steps, const std::vector<int>& kept, std::string& err);
+// DPM-Solver++(2M) coefficients of spaced level k, fp64: with ab = ac[k], abp = ac_prev[k], lambda(a) = log(a / (1 - a)) / 2,
+// h = lambda(abp) - lambda(ab):  A = sqrt((1 - abp) / (1 - ab)), Bc = -sqrt(abp) expm1(-h), G = h / (2 (lambda(ab) - lambda(ac[k + 1]))).
+// G is 0 at the levels that have no second-order step (k = 0, where h is infinite, and the top level).
+void solver_coeffs(const DiffusionTables& t, int k, double& A, double& Bc, double& G);
+enum Solver { SOLVER_DDIM = 0, SOLVER_DPM2M = 1 };
 std::vector<int> jump_schedule(int respacing, int jump_length, int jump_n_sample);
 // the same walk from t_T = start_level (an edit restarts the RePaint schedule from its own level); 0: the built-in 15 / 0.6 * respacing
 std::vector<int> jump_schedule_from(int respacing, int jump_length, int jump_n_sample, int start_level);
@@ -32,8 +45,10 @@ struct SamplerStep { StepKind kind; int level; };
 // init: 0 x_T is drawn (draw 0), 1 x is given at the schedule's first level, 2 x holds x0 and is noised to that level with draw 0.
 // start_level K (DDIM, 1 .. respacing; 0: the whole schedule): the plain schedule is levels K-1 .. 0, the mask-present one
 // jump_schedule_from(K).
-int64_t sampler_num_draws(const SamplerOpts& o, bool masked, int init, int start_level = 0);
-int64_t sampler_num_steps(const SamplerOpts& o, bool masked, int start_level = 0);
+// kept (nullable): the free timestep subset of the run (Sampler::set_timesteps); its length must be o.respacing.  The counts depend on its
+// length and, mask-present, on masked_start_level() only.
+int64_t sampler_num_draws(const SamplerOpts& o, bool masked, int init, int start_level = 0, const std::vector<int>* kept = nullptr);
+int64_t sampler_num_steps(const SamplerOpts& o, bool masked, int start_level = 0, const std::vector<int>* kept = nullptr);
 
 class Sampler {
   public:
@@ -54,6 +69,15 @@ class Sampler {
     // DDIM loops start at spaced level K - 1 instead of the top of the schedule (an edit of an existing motion: init 1 with x at that
     // level, or init 2 with x = x0).  Sticky like the tail blend; 0 = the whole schedule.  Range-checked by run() (needs the respacing).
     int set_start_level(int K);
+    // DDIM loops (and the reverse ODE) run on these original timesteps instead of the 'ddimK' stride: strictly ascending, >= 0; n must equal
+    // SamplerOpts.respacing and every entry lie below diffusion_steps when a loop runs (-1 before any state changes otherwise, and on a
+    // DDPM loop).  Sticky; n = 0 restores the stride.  A malformed list is refused here and leaves the previous one in place.
+    int set_timesteps(const int32_t* kept_host, int n);
+    // SOLVER_DPM2M: a DDIM step at level k whose previous executed step of the run was the DDIM step at level k + 1, k != 0, is the
+    // second-order DPM-Solver++(2M) update; every other step (the first of a run, the one after an undo step, the last) is the DDIM
+    // update bit for bit.  Draws are those of the DDIM loop.  eta = 0 only, no same_overlap_noisy, no DDPM loop (run() returns -1
+    // before any state changes).  The reverse ODE ignores it.  Sticky; an unknown value is refused here.
+    int set_solver(int solver);
     // init: 0 / 1 / 2 as for sampler_num_draws
     int run(DenoiserContext* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask,
             bool masked, const float* noise_stack, int64_t n_draws, float* trace);
@@ -87,7 +111,7 @@ class Sampler {
     // (sampler.hip) one run()'s arguments, constants and chains; its regime, decided before the first step; what one step's launches share
     struct Run; struct LoopPlan; struct StepConsts;
     // run() = argument checks, then these in order; finish() joins the chains whatever loop() returned
-    int ensure(size_t n, int B);
+    int ensure(size_t n, int B, bool want_hist);
     int prepare(Run& r);
     int make_chains(Run& r);
     LoopPlan plan(const Run& r) const;
@@ -111,15 +135,18 @@ class Sampler {
     std::vector<void*> pool;              // ensure()'s allocations
     size_t cap_n = 0; int cap_b = 0;
     float* eps = nullptr;
+    float* hist = nullptr; size_t cap_hist = 0;     // SOLVER_DPM2M: x0 of the previous step, [B, T, C] addressed like x (grown with cap_n on demand)
     // [0] the whole batch / the sub-batches / the expression chain; [1] the gesture chain of the pipelined loop, its noise scratch sized for
     // the batches that loop serves (cap_n2).  bufs[0].nz_eta is grown on demand (cap_eta): Philox runs with eta != 0 only.
     ChainBufs bufs[2];
     size_t cap_n2 = 0, cap_eta = 0;
-    DiffusionTables tb; int tb_steps = -1, tb_resp = -1;
+    DiffusionTables tb; int tb_steps = -1, tb_resp = -1; std::vector<int> tb_kept;    // cache key: (steps, respacing, subset)
     uint64_t* row_keys = nullptr; int n_row_keys = 0, cap_row_keys = 0;
     uint64_t* row_seeds = nullptr; int n_row_seeds = 0, cap_row_seeds = 0;
     bool tail_blend = false;
     int start_level = 0;
+    std::vector<int> kept;                // set_timesteps (empty: the stride)
+    int solver = SOLVER_DDIM;
     int run_schedule(DenoiserContext* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask, bool masked,
                      const float* noise_stack, int64_t n_draws, float* trace, int start, int invert_to, int invert_from);
     int init_x(Run& r);

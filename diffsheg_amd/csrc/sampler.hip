@@ -8,6 +8,8 @@
 //   schedule      get_schedule_jump_cjm_ddim      models/scheduler.py:178-208
 //   loops         ddim_sample_loop(+harmonize)    models/gaussian_diffusion.py:1106-1278
 //                 p_sample_loop_progressive       models/gaussian_diffusion.py:923-974
+// Not in the reference: free timestep subsets (make_tables_kept, masked_start_level) and the DPM-Solver++(2M) update of the DDIM
+// loops (solver_coeffs, the order rule in step_consts(), the x0 history) — sampler.h, DESIGN.md 4.18.
 #include "sampler.h"
 
 #include <math.h>
@@ -57,22 +59,61 @@ int make_tables(int steps, int respacing, DiffusionTables& out, std::string& err
         for (int i = 0; i < steps; ++i) out.tmap[i] = i;
         return 0;
     }
+    std::vector<int> kept;
+    if (stride_timesteps(steps, respacing, kept, err)) return -1;
+    return make_tables_kept(steps, kept, out, err);
+}
+
+int stride_timesteps(int steps, int respacing, std::vector<int>& kept, std::string& err) {
     // 'ddimK': first integer stride whose range(0, steps, stride) has exactly K entries
     int stride = 0;
     for (int s = 1; s < steps; ++s)
         if ((steps + s - 1) / s == respacing) { stride = s; break; }
     if (!stride) { err = "cannot create exactly " + std::to_string(respacing) + " steps with an integer stride"; return -1; }
-    std::vector<int> tmap;
+    kept.clear();
+    for (int i = 0; i < steps; i += stride) kept.push_back(i);
+    return 0;
+}
+
+int make_tables_kept(int steps, const std::vector<int>& kept, DiffusionTables& out, std::string& err) {
+    if (steps < 2) { err = "diffusion_steps must be >= 2"; return -1; }
+    if (kept.empty()) { err = "a timestep subset needs at least one entry"; return -1; }
+    for (size_t i = 0; i < kept.size(); ++i) {
+        if (kept[i] < 0 || kept[i] >= steps) { err = "timestep subset: entry outside [0, diffusion_steps)"; return -1; }
+        if (i > 0 && kept[i] <= kept[i - 1]) { err = "timestep subset: entries must be strictly ascending"; return -1; }
+    }
+    DiffusionTables base;
+    build_tables(linear_betas(steps), base);
     std::vector<double> nb;
     double last = 1.0;
-    for (int i = 0; i < steps; i += stride) {
+    for (int i : kept) {
         nb.push_back(1.0 - base.ac[i] / last);
         last = base.ac[i];
-        tmap.push_back(i);
     }
     build_tables(nb, out);
-    out.tmap = tmap;
+    out.tmap = kept;
     return 0;
+}
+
+int masked_start_level(int steps, const std::vector<int>& kept, std::string& err) {
+    if (kept.empty()) return 0;
+    std::vector<int> strided; std::string ignored;
+    if (stride_timesteps(steps, (int)kept.size(), strided, ignored) == 0 && strided == kept) return 0;
+    DiffusionTables sub, ref;
+    if (make_tables_kept(steps, kept, sub, err)) return -1;
+    if (make_tables(steps, 25, ref, err)) return -1;
+    const double at = ref.ac[14];
+    for (size_t k = 0; k < sub.ac.size(); ++k) if (sub.ac[k] <= at) return (int)k + 1;
+    return (int)sub.ac.size();
+}
+
+static double half_logsnr(double a) { return 0.5 * log(a / (1.0 - a)); }
+void solver_coeffs(const DiffusionTables& t, int k, double& A, double& Bc, double& G) {
+    const double ab = t.ac[k], abp = t.ac_prev[k];
+    const double h = half_logsnr(abp) - half_logsnr(ab);               // (k = 0: abp = 1, h = +inf, A = 0, Bc = 1)
+    A = sqrt((1.0 - abp) / (1.0 - ab));
+    Bc = -sqrt(abp) * expm1(-h);
+    G = (k == 0 || k + 1 >= (int)t.ac.size()) ? 0.0 : h / (2.0 * (half_logsnr(ab) - half_logsnr(t.ac[k + 1])));
 }
 
 std::vector<int> jump_schedule(int respacing, int jump_length, int jump_n_sample) {
@@ -99,8 +140,15 @@ std::vector<int> jump_schedule_from(int respacing, int jump_length, int jump_n_s
 
 // ------------------------------------------------------------------------------------------------
 // The schedule of a run.  start (> 0): the DDIM schedules begin at level start - 1.  invert_to (> 0): the reverse ODE, levels invert_from .. invert_to - 1.
-static int plan_steps(const SamplerOpts& o, bool masked, int start, int invert_to, std::vector<SamplerStep>& steps, std::string& err, int invert_from = 0) {
+// kept (nullable / empty: the 'ddimK' stride): the run's free timestep subset; a mask-present schedule without a start level then begins at masked_start_level().
+static int plan_steps(const SamplerOpts& o, bool masked, int start, int invert_to, std::vector<SamplerStep>& steps, std::string& err, int invert_from = 0,
+                      const std::vector<int>* kept = nullptr) {
     steps.clear();
+    if (kept && !kept->empty()) {
+        if (o.kind != 0) { err = "a timestep subset exists for the DDIM loops only"; return -1; }
+        if ((int)kept->size() != o.respacing) { err = "the timestep subset's length differs from opts.respacing"; return -1; }
+        if (kept->back() >= o.diffusion_steps) { err = "timestep subset: entry outside [0, diffusion_steps)"; return -1; }
+    }
     if (start != 0 || invert_to != 0) {
         if (o.kind != 0) { err = "a start level / the reverse loop exist for the DDIM loops only"; return -1; }
         if (start < 0 || start > o.respacing) { err = "start level outside 1 .. respacing"; return -1; }
@@ -118,6 +166,10 @@ static int plan_steps(const SamplerOpts& o, bool masked, int start, int invert_t
     }
     if (o.kind != 0) { err = "unknown sampler kind"; return -1; }
     if (masked && !o.no_repaint) {
+        if (start == 0 && kept && !kept->empty()) {
+            start = masked_start_level(o.diffusion_steps, *kept, err);
+            if (start < 0) return -1;
+        }
         const std::vector<int> times = o.no_resample ? jump_schedule_from(o.respacing, 1, 1, start)
                                                      : jump_schedule_from(o.respacing, o.jump_length, o.jump_n_sample, start);
         for (size_t i = 0; i + 1 < times.size(); ++i) {
@@ -131,19 +183,19 @@ static int plan_steps(const SamplerOpts& o, bool masked, int start, int invert_t
     return 0;
 }
 
-int64_t sampler_num_draws(const SamplerOpts& o, bool masked, int init, int start_level) {
+int64_t sampler_num_draws(const SamplerOpts& o, bool masked, int init, int start_level, const std::vector<int>* kept) {
     std::vector<SamplerStep> steps; std::string err;
     if (init < 0 || init > 2) { set_last_error("unknown init mode"); return -1; }
     if (init == 2 && o.kind != 0) { set_last_error("init mode 2 (x holds x0) exists for the DDIM loops only"); return -1; }
-    if (plan_steps(o, masked, start_level, 0, steps, err)) { set_last_error(err); return -1; }
+    if (plan_steps(o, masked, start_level, 0, steps, err, 0, kept)) { set_last_error(err); return -1; }
     int64_t n = init == 1 ? 0 : 1;                                             // x_T, or the q_sample noise of init 2
     const bool tail_gt = masked && o.same_overlap_noisy && o.clip_idx > 0;     // that branch draws no gt noise
     for (const auto& s : steps) n += (s.kind == STEP_DDIM) ? ((masked && !tail_gt) ? 2 : 1) : 1;
     return n;
 }
-int64_t sampler_num_steps(const SamplerOpts& o, bool masked, int start_level) {
+int64_t sampler_num_steps(const SamplerOpts& o, bool masked, int start_level, const std::vector<int>* kept) {
     std::vector<SamplerStep> steps; std::string err;
-    if (plan_steps(o, masked, start_level, 0, steps, err)) { set_last_error(err); return -1; }
+    if (plan_steps(o, masked, start_level, 0, steps, err, 0, kept)) { set_last_error(err); return -1; }
     return (int64_t)steps.size();
 }
 
@@ -166,6 +218,7 @@ struct Sampler::Run {
     std::vector<int64_t> tv; int lag = 0;                // level -> model timestep; DSH_DUAL_LAG
     size_t pf_next = 0;                                  // order[0 .. pf_next) have been handed to the prefetch stream
     int64_t draw = 0, step_idx = 0; int n_eval = 0;
+    bool dpm = false; int last_ddim_level = -1;          // SOLVER_DPM2M; level of the previous executed step if it was a DDIM step, else -1
     int64_t next_draw() { return draw++; }               // draw index: advanced once per draw, whatever the regime
 };
 
@@ -186,6 +239,7 @@ struct Sampler::StepConsts {
     int64_t idx, idx2;                                   // draws: the step's own N(0,1) (undo / DDPM noise, DDIM randn_like); the noised gt's (-1: none)
     float undo_a, undo_b, coef1, coef2;                  // undo step; DDPM step (with sigma)
     float sqrt_ab_prev, sqrt_1m_ab_prev, coef_eps, sigma;
+    bool second = false; float sA = 0.f, sBc = 0.f, sG = 0.f;      // SOLVER_DPM2M: a second-order step and its coefficients
 };
 
 Sampler::~Sampler() {
@@ -194,7 +248,7 @@ Sampler::~Sampler() {
     for (hipEvent_t e : {ev_pE, ev_pC, ev_pG}) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_sub) (void)hipEventDestroy(e);
     for (void* p : pool) (void)hipFree(p);
-    for (void* p : {(void*)row_keys, (void*)row_seeds, (void*)tails, (void*)tail_tmp, (void*)bufs[0].nz_eta}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)row_keys, (void*)row_seeds, (void*)tails, (void*)tail_tmp, (void*)bufs[0].nz_eta, (void*)hist}) if (p) (void)hipFree(p);
 }
 
 int Sampler::set_row_keys(const uint64_t* keys_host, int n) {
@@ -212,6 +266,22 @@ int Sampler::set_row_keys(const uint64_t* keys_host, int n) {
 int Sampler::set_start_level(int K) {
     DSH_REQUIRE(K >= 0, "set_start_level: negative level");
     start_level = K;
+    return 0;
+}
+
+int Sampler::set_timesteps(const int32_t* kept_host, int n) {
+    DSH_REQUIRE(n >= 0 && (n == 0 || kept_host), "set_timesteps: null timestep list");
+    for (int i = 0; i < n; ++i) {
+        DSH_REQUIRE(kept_host[i] >= 0, "set_timesteps: negative timestep");
+        DSH_REQUIRE(i == 0 || kept_host[i] > kept_host[i - 1], "set_timesteps: timesteps must be strictly ascending");
+    }
+    kept.assign(kept_host, kept_host + n);
+    return 0;
+}
+
+int Sampler::set_solver(int s) {
+    DSH_REQUIRE(s == SOLVER_DDIM || s == SOLVER_DPM2M, "set_solver: unknown solver (0 ddim, 1 dpm2m)");
+    solver = s;
     return 0;
 }
 
@@ -261,7 +331,14 @@ int Sampler::eval_step(const Run& r, const Chain& c, int n_eval, bool use_graph,
     return 0;
 }
 
-int Sampler::ensure(size_t n, int B) {
+int Sampler::ensure(size_t n, int B, bool want_hist) {
+    if (want_hist && cap_hist < std::max(n, cap_n)) {
+        DSH_HIP_CHECK(hipStreamSynchronize(st));
+        if (hist) (void)hipFree(hist);
+        hist = nullptr; cap_hist = 0;
+        DSH_HIP_CHECK(hipMalloc((void**)&hist, std::max(n, cap_n) * sizeof(float)));
+        cap_hist = std::max(n, cap_n);
+    }
     if (n <= cap_n && B <= cap_b) return 0;
     DSH_HIP_CHECK(hipStreamSynchronize(st));
     for (void* p : pool) (void)hipFree(p);
@@ -291,16 +368,18 @@ int Sampler::prepare(Run& r) {
     const SamplerOpts& o = r.o;
     const int B = r.B; const size_t n = r.n;
     std::string err;
-    if (plan_steps(o, r.masked, r.start, r.invert_to, r.steps, err, r.invert_from)) { set_last_error(err); return -1; }
-    const int64_t need = r.invert_to > 0 ? 0 : sampler_num_draws(o, r.masked, r.init, r.start);
+    if (plan_steps(o, r.masked, r.start, r.invert_to, r.steps, err, r.invert_from, &kept)) { set_last_error(err); return -1; }
+    const int64_t need = r.invert_to > 0 ? 0 : sampler_num_draws(o, r.masked, r.init, r.start, &kept);
     if (o.noise_mode == 0 && r.invert_to == 0) DSH_REQUIRE(r.noise_stack != nullptr && r.n_draws >= need, "noise stack shorter than the loop's draw count");
-    // tables are cached per (steps, respacing)
+    // tables are cached per (steps, respacing, subset)
     const int resp = o.kind == 1 ? 0 : o.respacing;
-    if (tb_steps != o.diffusion_steps || tb_resp != resp) {
-        if (make_tables(o.diffusion_steps, resp, tb, err)) { set_last_error(err); return -1; }
-        tb_steps = o.diffusion_steps; tb_resp = resp;
+    if (tb_steps != o.diffusion_steps || tb_resp != resp || tb_kept != kept) {
+        tb_steps = tb_resp = -1;
+        if (kept.empty() ? make_tables(o.diffusion_steps, resp, tb, err) : make_tables_kept(o.diffusion_steps, kept, tb, err)) { set_last_error(err); return -1; }
+        tb_steps = o.diffusion_steps; tb_resp = resp; tb_kept = kept;
     }
-    if (int e = ensure(n, B)) return e;
+    r.dpm = solver == SOLVER_DPM2M && r.invert_to == 0;
+    if (int e = ensure(n, B, r.dpm)) return e;
     if (o.kind == 0 && o.eta != 0.f && o.noise_mode == 1 && cap_eta < n) { if (int e = grow_device_buffer(bufs[0].nz_eta, cap_eta, n, st)) return e; }
     // (the reverse loop draws nothing: whatever keys an earlier call left in the context do not concern it)
     DSH_REQUIRE(r.invert_to > 0 || n_row_keys == 0 || o.noise_mode != 1 || (n_row_keys == B && (n / B) % 4 == 0),
@@ -467,6 +546,11 @@ Sampler::StepConsts Sampler::step_consts(Run& r, const SamplerStep& sp) {
         if (k == 0) sc.sigma = 0.f;                                 // nonzero_mask: no noise at (spaced) t == 0; the mean keeps coef_eps
     }
     if (r.masked && !r.tail_gt) sc.idx2 = r.next_draw();            // N(0,1) of the noised gt (RePaint blend)
+    if (r.dpm && k != 0 && r.last_ddim_level == k + 1) {
+        double A, Bc, G;
+        solver_coeffs(tb, k, A, Bc, G);
+        sc.second = true; sc.sA = (float)A; sc.sBc = (float)Bc; sc.sG = (float)G;
+    }
     return sc;
 }
 
@@ -525,7 +609,8 @@ int Sampler::ddim_update(Run& r, const Chain& c, const StepConsts& sc) {
     const SamplerOpts& o = r.o; const int k = sc.k;
     DdimStepArgs a;
     a.c_lo = c.c_lo; a.c_hi = c.c_hi;
-    a.x = r.x + c.off; a.eps = eps + c.off; a.x0_out = nullptr; a.c1 = sc.c1; a.c2 = sc.c2;
+    // (SOLVER_DPM2M: a first-order step is this launch, and leaves its x0 in the history)
+    a.x = r.x + c.off; a.eps = eps + c.off; a.x0_out = (r.dpm && sc.kind == STEP_DDIM) ? hist + c.off : nullptr; a.c1 = sc.c1; a.c2 = sc.c2;
     a.sqrt_ab_prev = sc.sqrt_ab_prev; a.sqrt_1m_ab_prev = sc.sqrt_1m_ab_prev;
     a.coef_eps = sc.coef_eps; a.sigma = sc.sigma; a.noise1 = nullptr;
     if (o.eta != 0.f && sc.kind == STEP_DDIM) {
@@ -545,6 +630,14 @@ int Sampler::ddim_update(Run& r, const Chain& c, const StepConsts& sc) {
         a.mask = r.mask + c.off; a.gt = r.gt + c.off; a.noise2 = z2;
         a.blend = (a.sqrt_1m_ab_prev < 0.2f && o.add_blend) ? 1 : 0;
         a.tail_blend = (a.blend && tail_blend) ? 1 : 0;
+    }
+    if (sc.second) {
+        Dpm2mStepArgs d;
+        d.x = a.x; d.eps = a.eps; d.x0_prev = hist + c.off; d.c1 = a.c1; d.c2 = a.c2; d.A = sc.sA; d.Bc = sc.sBc; d.G = sc.sG;
+        d.sqrt_ab_prev = a.sqrt_ab_prev; d.sqrt_1m_ab_prev = a.sqrt_1m_ab_prev; d.mask = a.mask; d.gt = a.gt; d.noise2 = a.noise2;
+        d.blend = a.blend; d.tail_blend = a.tail_blend; d.clip = a.clip; d.overlap_len = a.overlap_len; d.frames = a.frames; d.channels = a.channels;
+        d.n = a.n; d.c_lo = a.c_lo; d.c_hi = a.c_hi;
+        return launch_dpm2m_step(d, c.s);                            // (no saved noisy tails under this solver: run_schedule())
     }
     if (int e = launch_ddim_step(a, c.s)) return e;
     if (r.son) DSH_HIP_CHECK(hipMemcpyAsync(tails + (size_t)k * r.blc + toff, tail_tmp + toff, (size_t)c.nb * o.overlap_len * channels * sizeof(float),
@@ -614,6 +707,7 @@ int Sampler::loop(Run& r, const LoopPlan& p) {
         if (r.trace)
             for (const Chain& c : r.chains)
                 DSH_HIP_CHECK(hipMemcpyAsync(r.trace + (size_t)r.step_idx * r.n + c.off, r.x + c.off, c.cnt * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+        r.last_ddim_level = sp.kind == STEP_DDIM ? sp.level : -1;
         ++r.step_idx;
     }
     return 0;
@@ -673,6 +767,14 @@ int Sampler::run_schedule(DenoiserContext* den, const SamplerOpts& o, float* x, 
     DSH_REQUIRE(!masked || (gt && mask), "masked sampling needs gt and mask");
     DSH_REQUIRE(o.noise_mode == 0 || o.noise_mode == 1, "unknown noise mode");
     DSH_REQUIRE(!(masked && o.kind == 1), "mask-present DDPM (p_sample_loop_progressive_harmonize) is not supported");
+    DSH_REQUIRE(kept.empty() || o.kind == 0, "a timestep subset exists for the DDIM loops only");
+    DSH_REQUIRE(kept.empty() || (int)kept.size() == o.respacing, "the timestep subset's length differs from opts.respacing");
+    DSH_REQUIRE(kept.empty() || kept.back() < o.diffusion_steps, "timestep subset: entry outside [0, diffusion_steps)");
+    if (solver == SOLVER_DPM2M && invert_to == 0) {
+        DSH_REQUIRE(o.kind == 0, "the dpm2m solver exists for the DDIM loops only");
+        DSH_REQUIRE(o.eta == 0.f, "the dpm2m solver is deterministic: eta must be 0");
+        DSH_REQUIRE(!o.same_overlap_noisy, "the dpm2m solver does not keep the saved noisy tails of same_overlap_noisy");
+    }
     DSH_REQUIRE(!(tail_blend && o.same_overlap_noisy), "tail_blend with same_overlap_noisy: the saved noisy tails describe a window chain, not a window pinned at both ends");
     DSH_REQUIRE(!tail_blend || (o.overlap_len >= 0 && 2 * (int64_t)o.overlap_len <= den->frames()), "tail_blend: the head and the tail fade overlap (2 * overlap_len > frames)");
     Run r{den, o, x, init, gt, mask, masked, noise_stack, n_draws, trace, start, invert_from, invert_to};

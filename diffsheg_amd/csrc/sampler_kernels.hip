@@ -87,6 +87,50 @@ int launch_ddim_step(const DdimStepArgs& a, hipStream_t s) {
     return 0;
 }
 
+// DPM-Solver++(2M), data prediction, at eta = 0 (Lu et al. 2022, algorithm 2): the second-order multistep update
+//   x0 = c1 x - c2 eps;  D = x0 + G (x0 - x0_prev);  x <- A x + Bc D
+// with A = sigma_prev / sigma, Bc = -alpha_prev expm1(-h), G = h / (2 h_before) from the host (sampler.hip, solver_coeffs), then the RePaint
+// branch of ddim_step_kernel, operation for operation.  x0_prev is read and rewritten by the thread that owns the element.
+__global__ void dpm2m_step_kernel(Dpm2mStepArgs a) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const int tc = a.frames * a.channels;
+    const bool ranged = a.c_hi > a.c_lo;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
+        if (ranged) { const int cc = (int)(i % (size_t)a.channels); if (cc < a.c_lo || cc >= a.c_hi) continue; }
+        const float x = a.x[i];
+        float x0 = rn_sub(rn_mul(a.c1, x), rn_mul(a.c2, a.eps[i]));
+        if (a.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        const float D = rn_add(x0, rn_mul(a.G, rn_sub(x0, a.x0_prev[i])));
+        float s = rn_add(rn_mul(a.A, x), rn_mul(a.Bc, D));
+        a.x0_prev[i] = x0;
+        if (a.mask) {
+            const int t = (int)((i % (size_t)tc) / (size_t)a.channels);
+            float g = rn_add(rn_mul(a.sqrt_ab_prev, a.gt[i]), rn_mul(a.sqrt_1m_ab_prev, a.noise2[i]));
+            if (a.blend) {
+                const int L = a.overlap_len;
+                if (t < L) {
+                    const float w = linspace01(L, t);
+                    g = rn_add(rn_mul(g, rn_sub(1.0f, w)), rn_mul(s, w));
+                } else if (a.tail_blend && t >= a.frames - L) {
+                    const float w = linspace01(L, L - 1 - (t - (a.frames - L)));
+                    g = rn_add(rn_mul(g, rn_sub(1.0f, w)), rn_mul(s, w));
+                }
+            }
+            s = a.mask[i] ? g : s;
+        }
+        a.x[i] = s;
+    }
+}
+int launch_dpm2m_step(const Dpm2mStepArgs& a, hipStream_t s) {
+    DSH_REQUIRE(a.x && a.eps && a.x0_prev && a.frames > 0 && a.channels > 0, "dpm2m_step: invalid argument");
+    DSH_REQUIRE(!a.mask || (a.gt && a.noise2), "dpm2m_step: a mask needs gt and noise2");
+    DSH_REQUIRE(a.c_lo >= 0 && a.c_hi <= a.channels, "dpm2m_step: channel range outside [0, channels]");
+    if (a.n == 0) return 0;
+    hipLaunchKernelGGL(dpm2m_step_kernel, dim3(grid_for(a.n)), dim3(256), 0, s, a);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 __global__ void undo_step_kernel(float* x, const float* noise, float sa, float sb, size_t n, int channels, int c_lo, int c_hi) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const bool ranged = c_hi > c_lo;

@@ -27,7 +27,11 @@ Differences a caller can observe, all loud:
     that pins both ends of a window (``DDPMTrainer.sample_inbetween``, seam repair); off by default;
   * editing an existing motion: ``q_sample`` (gaussian_diffusion.py:417-462) runs on the device, from given noise or the Philox streams;
     ``ddim_sample_loop(..., start_level=K)`` starts at spaced level ``K - 1`` from ``noise=`` (x at that level) or ``x_start=`` (a clean
-    motion, noised in the loop with draw 0); ``ddim_reverse_sample`` / ``ddim_reverse_sample_loop`` are the DDIM reverse ODE (:1068-1104).
+    motion, noised in the loop with draw 0); ``ddim_reverse_sample`` / ``ddim_reverse_sample_loop`` are the DDIM reverse ODE (:1068-1104);
+  * few-step sampling: ``space_timesteps`` also takes the reference's section counts and ``'logsnrK'`` (K timesteps uniform in log-SNR),
+    ``SpacedDiffusion`` any non-empty subset of the timesteps (a subset that is no 'ddimK' stride travels as a list,
+    ``dsh_sample_set_timesteps``), and ``ddim_sample_loop(..., solver="dpm2m")`` runs the second-order DPM-Solver++(2M) update where a
+    denoise step follows the denoise step one level above it (``dsh_sample_set_solver``); the default is the reference's loop.
 """
 from __future__ import annotations
 
@@ -74,14 +78,79 @@ def diffusion_table(steps: int, respacing: int, name: str) -> np.ndarray:
     return np.array(buf[:n], dtype=np.float64)
 
 
+def _int_array(values):
+    vals = [int(v) for v in values]
+    return (C.c_int32 * max(len(vals), 1))(*vals), len(vals)
+
+
+def diffusion_table_subset(steps: int, kept, name: str) -> np.ndarray:
+    """The table ``name`` of the process respaced to the original timesteps ``kept`` (ascending)."""
+    arr, n = _int_array(kept)
+    buf = (C.c_double * max(n, 1))()
+    m = _lib.check(_lib.lib().dsh_diffusion_table_subset(steps, arr, n, name.encode(), buf, n), "dsh_diffusion_table_subset")
+    return np.array(buf[:m], dtype=np.float64)
+
+
+def solver_coeffs(steps: int, kept, k: int):
+    """``(A, Bc, G)`` of the dpm2m solver at spaced level ``k`` of the subset ``kept``, fp64 (dsh_solver_coeffs)."""
+    arr, n = _int_array(kept)
+    out = (C.c_double * 3)()
+    _lib.check(_lib.lib().dsh_solver_coeffs(steps, arr, n, int(k), out), "dsh_solver_coeffs")
+    return tuple(out)
+
+
+def masked_start_level(steps: int, kept) -> int:
+    """``t_T`` of an out-painting run on the subset ``kept``: 0 for a 'ddimK' stride (the reference's 15 / int(0.6 K)), else one past the
+    first level at or below the noise level where the reference starts a masked ddim25 window (dsh_masked_start_level)."""
+    arr, n = _int_array(kept)
+    return _lib.check(_lib.lib().dsh_masked_start_level(steps, arr, n), "dsh_masked_start_level")
+
+
+def logsnr_timesteps(num_timesteps: int, k: int) -> List[int]:
+    """``k`` timesteps placed uniformly in log-SNR: lambda(t) = log(ac_t / (1 - ac_t)) / 2 from the fp64 base table, the grid
+    ``linspace(lambda(n - 1), lambda(0), k)``, and for every grid point the timestep nearest in lambda (ties: the lower one)."""
+    if k < 1:
+        raise ValueError(f"cannot place {k} timesteps")
+    ac = diffusion_table(num_timesteps, 0, "alphas_cumprod")
+    lam = 0.5 * np.log(ac / (1.0 - ac))
+    grid = np.linspace(lam[-1], lam[0], k)
+    kept = sorted(int(np.argmin(np.abs(lam - g))) for g in grid)       # (argmin returns the first, i.e. lowest, index of a tie)
+    if len(set(kept)) != k:
+        raise ValueError(f"cannot place {k} distinct timesteps uniformly in log-SNR on {num_timesteps} steps ({len(set(kept))} distinct)")
+    return kept
+
+
 def space_timesteps(num_timesteps: int, section_counts) -> set:
-    """respace.py:7-57 — the hot path only ever uses the 'ddimN' form."""
-    if isinstance(section_counts, str) and section_counts.startswith("ddim"):
-        k = int(section_counts[len("ddim"):])
-        buf = (C.c_int32 * num_timesteps)()
-        n = _lib.check(_lib.lib().dsh_timestep_map(num_timesteps, k, buf, num_timesteps), "dsh_timestep_map")
-        return set(buf[:n])
-    raise NotImplementedError("only 'ddimN' respacing is built (trainers hard-code 'ddim25')")
+    """respace.py:7-57: ``'ddimK'`` (the DDIM stride), section counts (``"a,b,c"`` or a list: that many evenly spaced steps from each of
+    the equal portions of the process), and — not in the reference — ``'logsnrK'`` (:func:`logsnr_timesteps`)."""
+    if isinstance(section_counts, str):
+        if section_counts.startswith("ddim"):
+            k = int(section_counts[len("ddim"):])
+            buf = (C.c_int32 * num_timesteps)()
+            n = _lib.check(_lib.lib().dsh_timestep_map(num_timesteps, k, buf, num_timesteps), "dsh_timestep_map")
+            return set(buf[:n])
+        if section_counts.startswith("logsnr"):
+            return set(logsnr_timesteps(num_timesteps, int(section_counts[len("logsnr"):])))
+        section_counts = [int(v) for v in section_counts.split(",")]
+    counts = [int(v) for v in section_counts]
+    size_per, extra = divmod(num_timesteps, len(counts))
+    start, steps = 0, []
+    for i, count in enumerate(counts):
+        size = size_per + (1 if i < extra else 0)
+        if size < count:
+            raise ValueError(f"cannot divide section of {size} steps into {count}")
+        stride = 1 if count <= 1 else (size - 1) / (count - 1)
+        steps += [start + round(j_stride) for j_stride in _accumulate(stride, count)]
+        start += size
+    return set(steps)
+
+
+def _accumulate(stride, count):
+    """0, stride, stride + stride, ...: the running float sum the reference rounds (not j * stride)."""
+    cur = 0.0
+    for _ in range(count):
+        yield cur
+        cur += stride
 
 
 def get_schedule_jump_cjm_ddim(time_respacing: int = 25, jump_length: int = 1, jump_n_sample: int = 1) -> List[int]:
@@ -102,6 +171,8 @@ class GaussianDiffusion:
     """Full-chain sampler handle (ancestral DDPM): mirrors gaussian_diffusion.py:300-390."""
 
     _respacing = 0
+    _kept = None          # SpacedDiffusion on a subset that is no 'ddimK' stride: the sorted original timesteps
+    solver = "ddim"       # the update rule ddim_sample_loop uses when its solver= keyword is not given
 
     def __init__(self, *, opt, betas=None, model_mean_type=ModelMeanType.EPSILON,
                  model_var_type=ModelVarType.FIXED_SMALL, loss_type=None, rescale_timesteps=False,
@@ -188,9 +259,21 @@ class GaussianDiffusion:
 
     def _run(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0,
              noise_source=None, seed=None, return_trace=False, row_keys=None, cond_scale=None, tail_blend=False,
-             row_seeds=None, start_level=None, x_start=None, add_blend=None):
+             row_seeds=None, start_level=None, x_start=None, add_blend=None, solver=None):
         if not isinstance(model, UniDiffuser):
             raise TypeError("model must be a diffsheg_amd.model.UniDiffuser (no generic-callable / CPU fallback)")
+        # the update rule of the DDIM loops: refused here, before anything is conditioned or set in the native context
+        if solver is None:
+            solver = self.solver if kind == 0 else "ddim"
+        if solver not in ("ddim", "dpm2m"):
+            raise ValueError(f'solver must be "ddim" or "dpm2m", got {solver!r}')
+        if solver == "dpm2m":
+            if kind != 0:
+                raise TypeError("solver is an argument of the DDIM loops only")
+            if eta != 0.0:
+                raise ValueError("the dpm2m solver is deterministic: eta must be 0")
+            if bool(getattr(self.opt, "same_overlap_noisy", False)):
+                raise NotImplementedError("the dpm2m solver does not keep the saved noisy tails of same_overlap_noisy")
         if denoised_fn is not None or cond_fn is not None:
             raise NotImplementedError("denoised_fn / cond_fn are not on the accelerated path")
         if eta != 0.0 and kind != 0:
@@ -275,7 +358,8 @@ class GaussianDiffusion:
             GaussianDiffusion._calls += 1
         opts = self._opts(kind, clip_denoised, mode, int(seed), clip_idx, eta, add_blend)
         lib = _lib.lib()
-        n_draws = _lib.check(lib.dsh_sample_num_draws_from(C.byref(opts), int(masked), init, K), "dsh_sample_num_draws_from")
+        kept_arr, nkept = _int_array(self._kept if (self._kept and kind == 0) else [])
+        n_draws = _lib.check(lib.dsh_sample_num_draws_subset(C.byref(opts), int(masked), init, K, kept_arr, nkept), "dsh_sample_num_draws_subset")
         stack = None
         if noise_source is not None:
             stack = torch.empty(n_draws, B * T * Cc, device=dev)
@@ -283,7 +367,7 @@ class GaussianDiffusion:
                 stack[i].copy_(noise_source.randn((B, T, Cc)).reshape(-1), non_blocking=False)
         trace = None
         if return_trace:
-            n_steps = _lib.check(lib.dsh_sample_num_steps_from(C.byref(opts), int(masked), init, K), "dsh_sample_num_steps_from")
+            n_steps = _lib.check(lib.dsh_sample_num_steps_subset(C.byref(opts), int(masked), init, K, kept_arr, nkept), "dsh_sample_num_steps_subset")
             trace = torch.empty(n_steps, B, T, Cc, device=dev)
         # Philox noise: optional per-row generator keys (a chain's global id), see dsh_sample_set_row_keys
         if row_keys is not None and len(row_keys) != B:
@@ -302,6 +386,10 @@ class GaussianDiffusion:
                 _lib.check(lib.dsh_sample_set_tail_blend(model._h, 1), "dsh_sample_set_tail_blend")
             if K:
                 _lib.check(lib.dsh_sample_set_start_level(model._h, K), "dsh_sample_set_start_level")
+            if nkept:
+                _lib.check(lib.dsh_sample_set_timesteps(model._h, kept_arr, nkept), "dsh_sample_set_timesteps")
+            if solver == "dpm2m":
+                _lib.check(lib.dsh_sample_set_solver(model._h, 1), "dsh_sample_set_solver")
             try:
                 _lib.check(lib.dsh_sample(model._h, C.byref(opts), x.data_ptr(), int(init),
                                           None if gt is None else gt.data_ptr(), None if not masked else mask.data_ptr(),
@@ -316,6 +404,10 @@ class GaussianDiffusion:
                     lib.dsh_sample_set_tail_blend(model._h, 0)
                 if K:
                     lib.dsh_sample_set_start_level(model._h, 0)
+                if nkept:                                # the subset and the solver are sticky too: the next call is the stride / the DDIM step
+                    lib.dsh_sample_set_timesteps(model._h, kept_arr, 0)
+                if solver == "dpm2m":
+                    lib.dsh_sample_set_solver(model._h, 0)
         self._keep = (gt, mask, stack)          # consumed asynchronously on the stream
         if son:
             # gaussian_diffusion.py:1155-1157: the loop returns the dict of the last step plus the saved tails.  The tails live
@@ -346,7 +438,12 @@ class GaussianDiffusion:
         ``start_level=K`` (keyword, ``1 .. K .. respacing``): the loop starts at spaced level ``K - 1`` instead of the top — levels
         ``K-1 .. 0``, or with a mask the RePaint jump schedule walked from ``t_T = K``.  ``noise=`` then is x AT level ``K - 1``;
         ``x_start=`` is a clean motion, noised to that level inside the loop with draw 0 (the draw x_T takes in a run from noise, so
-        ``row_keys`` / ``row_seeds`` / ragged lengths address it alike) — one or the other."""
+        ``row_keys`` / ``row_seeds`` / ragged lengths address it alike) — one or the other.
+
+        ``solver="ddim" | "dpm2m"`` (keyword; default: this object's ``solver`` attribute, ``"ddim"``): ``"dpm2m"`` makes every denoise step
+        that directly follows the denoise step one level above it — and is not the last — the second-order DPM-Solver++(2M) update
+        (dsh_sample_set_solver); all other steps, the draws and the noise addressing are the DDIM loop's.  Needs ``eta == 0`` and no
+        ``same_overlap_noisy``.  Meant for few steps on a ``'logsnrK'`` subset (:func:`space_timesteps`)."""
         if not self._respacing:
             raise NotImplementedError("ddim_sample_loop needs a SpacedDiffusion('ddimK') (trainers use 'ddim25')")
         return self._run(0, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta, **kw)
@@ -447,9 +544,16 @@ class GaussianDiffusion:
         opts = self._opts(0, clip_denoised, 1, 0, 0, 0.0)
         trace = torch.empty(to_level - from_level, B, T, Cc, device=dev) if return_trace else None
         # (no draws: the row keys an earlier loop left in the native context do not concern the reverse loop, at any batch size)
+        kept_arr, nkept = _int_array(self._kept or [])
         with self._native(model, gs):
-            _lib.check(_lib.lib().dsh_invert_from(model._h, C.byref(opts), out.data_ptr(), from_level, to_level,
-                                                  None if trace is None else trace.data_ptr()), "dsh_invert")
+            if nkept:
+                _lib.check(_lib.lib().dsh_sample_set_timesteps(model._h, kept_arr, nkept), "dsh_sample_set_timesteps")
+            try:
+                _lib.check(_lib.lib().dsh_invert_from(model._h, C.byref(opts), out.data_ptr(), from_level, to_level,
+                                                      None if trace is None else trace.data_ptr()), "dsh_invert")
+            finally:
+                if nkept:
+                    _lib.lib().dsh_sample_set_timesteps(model._h, kept_arr, 0)
         return (out, trace) if return_trace else out
 
     def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0, cond_scale=None):
@@ -474,15 +578,30 @@ class GaussianDiffusion:
 class SpacedDiffusion(GaussianDiffusion):
     """respace.py:60-110: tables rebuilt from the kept cumulative alphas; the model sees ORIGINAL timesteps."""
 
-    def __init__(self, use_timesteps, **kwargs):
-        self.use_timesteps = set(use_timesteps)
+    def __init__(self, use_timesteps, solver: str = "ddim", **kwargs):
+        """``use_timesteps``: any non-empty subset of ``range(n)``.  A 'ddimK' stride takes the stride's own native route; any other subset
+        travels as a list (dsh_sample_set_timesteps).  ``solver``: the default update rule of ``ddim_sample_loop``."""
+        self.use_timesteps = set(int(t) for t in use_timesteps)
         n = len(kwargs["betas"]) if kwargs.get("betas") is not None else int(kwargs.get("num_timesteps", 1000))
         k = len(self.use_timesteps)
-        if self.use_timesteps != space_timesteps(n, f"ddim{k}"):
-            raise NotImplementedError("only 'ddimK' strided subsets are built")
+        if k == 0 or min(self.use_timesteps) < 0 or max(self.use_timesteps) >= n:
+            raise ValueError(f"use_timesteps must be a non-empty subset of range({n})")
+        if solver not in ("ddim", "dpm2m"):
+            raise ValueError(f'solver must be "ddim" or "dpm2m", got {solver!r}')
+        try:
+            strided = self.use_timesteps == space_timesteps(n, f"ddim{k}")
+        except _lib.DshError:                     # (no integer stride gives k steps)
+            strided = False
+        self._kept = None if strided else sorted(self.use_timesteps)
         self._respacing = k
+        self.solver = solver
         super().__init__(**kwargs)
 
     def _load_tables(self):
-        super()._load_tables()
+        if self._kept is None:
+            super()._load_tables()
+        else:
+            for name in _TABLES:
+                setattr(self, name, diffusion_table_subset(self.original_num_steps, self._kept, name))
+            self.num_timesteps = len(self.betas)
         self.timestep_map = sorted(self.use_timesteps)

@@ -117,13 +117,38 @@ class DDPMTrainer:
         kw = dict(opt=args, betas=betas, model_mean_type=ModelMeanType.EPSILON,
                   model_var_type=ModelVarType.FIXED_SMALL, loss_type=None)
         self.diffusion = GaussianDiffusion(**kw)
-        # the reference hard-codes 'ddim25' here (ddpm_show_trainer.py:73, ddpm_beat_trainer.py:76)
-        self.diffusion_ddim_val = SpacedDiffusion(use_timesteps=space_timesteps(self.diffusion_steps, "ddim25"),
-                                                  rescale_timesteps=False, **kw)
+        self._diffusion_kw = kw
+        # the reference hard-codes 'ddim25' here (ddpm_show_trainer.py:73, ddpm_beat_trainer.py:76): the defaults of the three options
+        self.set_sampling(getattr(args, "sampling_steps", 25), getattr(args, "sampling_spacing", "ddim"), getattr(args, "solver", "ddim"))
         # validation (ddpm_show_trainer.py:440-583): eval_model = a metrics.HalfEmbeddingNet, or None for no FGD (--no_fgd)
         self.eval_model = eval_model
         self.pose_stats = None
         self.reset_validation()
+
+    def set_sampling(self, steps: int = 25, spacing="ddim", solver: str = "ddim") -> None:
+        """The sampling configuration of every DDIM path of this trainer (``generate_batch``, ``sample_arbitrary_len`` also with
+        ``lengths=``, ``sample_inbetween``, ``sample_variations``, ``restyle``, the sharded chains and :class:`streaming.StreamPool`, which
+        all sample through ``diffusion_ddim_val``): rebuilds that object.  ``steps`` evaluations of a plain clip; ``spacing="ddim"`` the
+        reference's stride ('ddimK'), ``"logsnr"`` timesteps uniform in log-SNR ('logsnrK', :func:`diffusion.space_timesteps`), or an
+        explicit list of original timesteps (its length must be ``steps``); ``solver="ddim" | "dpm2m"`` (``ddim_sample_loop``).  The
+        defaults are the reference's hard-coded 'ddim25' with the DDIM step.  ``level=`` / ``strength=`` of the editing entries count in
+        the current ``steps``.  Raises before anything changes: an unknown spacing / solver, a list of another length, ``dpm2m`` with
+        ``opt.same_overlap_noisy``."""
+        steps = int(steps)
+        if solver not in ("ddim", "dpm2m"):
+            raise ValueError(f'solver must be "ddim" or "dpm2m", got {solver!r}')
+        if solver == "dpm2m" and bool(getattr(self.opt, "same_overlap_noisy", False)):
+            raise NotImplementedError("the dpm2m solver does not keep the saved noisy tails of same_overlap_noisy")
+        if isinstance(spacing, str):
+            if spacing not in ("ddim", "logsnr"):
+                raise ValueError(f'spacing must be "ddim", "logsnr" or a list of timesteps, got {spacing!r}')
+            use = space_timesteps(self.diffusion_steps, f"{spacing}{steps}")
+        else:
+            use = set(int(t) for t in spacing)
+            if len(use) != steps or len(use) != len(list(spacing)):
+                raise ValueError(f"an explicit spacing needs {steps} distinct timesteps, got {len(list(spacing))}")
+        self.diffusion_ddim_val = SpacedDiffusion(use_timesteps=use, solver=solver, rescale_timesteps=False, **self._diffusion_kw)
+        self.sampling = (steps, spacing if isinstance(spacing, str) else sorted(use), solver)
 
     # ---- BEAT results tail: gesture channels as the reference's standardised Euler angles (ddpm_beat_trainer.py:1044-1060) ----
     def set_pose_stats(self, stats) -> None:

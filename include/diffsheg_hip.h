@@ -253,6 +253,32 @@ int dsh_invert(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t to_
 /* the same over the levels from_level .. to_level-1 (0 <= from_level < to_level; x enters at from_level): one reverse step is
  * (t, t+1).  trace: [to_level - from_level, B*T*C]. */
 int dsh_invert_from(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t from_level, int32_t to_level, float* trace);
+/* ---- few-step sampling: free timestep subsets and the DPM-Solver++(2M) update ----
+ * The DDIM loops and dsh_invert run on the original timesteps kept_host[0 .. n) instead of the 'ddimK' stride: strictly ascending,
+ * >= 0 (-1 otherwise, and the previous list stays).  Tables: beta'_k = 1 - ac[kept_k] / ac[kept_{k-1}], timestep map = the list.
+ * Sticky; n = 0 restores the stride.  With a list set, dsh_sample and dsh_invert return -1 before any state changes when
+ * n != opts->respacing, when an entry is >= opts->diffusion_steps, and on a DDPM loop.  dsh_invert takes the list from the context; the
+ * counting entries below take it as an argument.
+ * Out-painting start: a list that is the 'ddimK' stride of its own length keeps the reference's rule t_T = 15 / int(0.6 K); any other
+ * list starts a masked window at t_T = 1 + min{k : alphas_cumprod'[k] <= alphas_cumprod[14] of the ddim25 tables of the same
+ * diffusion_steps} (dsh_masked_start_level), the noise level where the reference starts one.  dsh_sample_set_start_level overrides. */
+int dsh_sample_set_timesteps(dsh_ctx* ctx, const int32_t* kept_host, int32_t n);
+#define DSH_SOLVER_DDIM 0
+#define DSH_SOLVER_DPM2M 1
+/* Update rule of the DDIM loops.  DSH_SOLVER_DPM2M: a denoise step at level k is the second-order multistep update of
+ * DPM-Solver++(2M) in the data-prediction form,
+ *   x0 = c1 x - c2 eps (clamped when clip_denoised);  D = x0 + G (x0 - x0_prev);  x <- A x + Bc D;  then the RePaint branch,
+ * if and only if the previous executed step of this run was the denoise step at level k + 1 and k != 0.  Every other step - the first of
+ * a run (also one entered through a start level or init_from_x 1 / 2), the step after an undo step, the last step to alphas_cumprod_prev
+ * = 1 - is the DDIM update bit for bit.  With respacing <= 2 the two solvers are the same loop.  Draws: those of the DDIM loop (same
+ * count, indices and Philox offsets).  One extra [B,T,C] fp32 buffer in the context holds x0_prev.  Sticky; -1 on an unknown value.
+ * dsh_sample then returns -1 before any state changes with eta != 0, with same_overlap_noisy and on a DDPM loop.  dsh_invert ignores the
+ * solver: the reverse ODE stays the reference's first-order ddim_reverse_sample. */
+int dsh_sample_set_solver(dsh_ctx* ctx, int32_t solver);
+/* dsh_sample_num_draws_from / _num_steps_from for a run on the subset kept[0 .. n) (n = 0: the stride); -1 when n != opts->respacing.
+ * The counts depend on n and, mask-present, on the start level above only. */
+int64_t dsh_sample_num_draws_subset(const dsh_sampler_opts* opts, int32_t masked, int32_t init, int32_t start_level, const int32_t* kept, int32_t n);
+int64_t dsh_sample_num_steps_subset(const dsh_sampler_opts* opts, int32_t masked, int32_t init, int32_t start_level, const int32_t* kept, int32_t n);
 /* Classifier-free guidance scale of dsh_eval and dsh_sample (transformer.py:537, :586: eps = u + s_b (k - u) for clip b, in both motion
  * encoders; the expression x0 the gesture encoder reads is built from the mixed expression eps).  Host array of n entries: n = 0 restores
  * the config's cond_scale, n = 1 sets one value for the whole batch, n = B one value per clip (checked against the batch of
@@ -267,6 +293,16 @@ int dsh_set_guidance_scale(dsh_ctx* ctx, const float* scales_host, int32_t n);
  * sqrt_recipm1_alphas_cumprod, posterior_variance, posterior_log_variance_clipped,
  * posterior_mean_coef1, posterior_mean_coef2}; respacing 0 = full chain.  Returns entries written. */
 int32_t dsh_diffusion_table(int32_t diffusion_steps, int32_t respacing, const char* name, double* out, int32_t cap);
+/* the same tables for the subset kept[0 .. n) of original timesteps (strictly ascending, each in [0, diffusion_steps), n >= 1); the
+ * 'ddimK' list gives dsh_diffusion_table(diffusion_steps, K, ...) bit for bit. */
+int32_t dsh_diffusion_table_subset(int32_t diffusion_steps, const int32_t* kept, int32_t n, const char* name, double* out, int32_t cap);
+/* out3 = {A, Bc, G} of dsh_sample_set_solver at spaced level k of that subset, fp64 (the loop casts them to fp32): with ab =
+ * alphas_cumprod[k], abp = alphas_cumprod_prev[k], lambda(a) = log(a / (1 - a)) / 2 and h = lambda(abp) - lambda(ab),
+ *   A = sqrt((1 - abp) / (1 - ab)),  Bc = -sqrt(abp) expm1(-h),  G = h / (2 (lambda(ab) - lambda(alphas_cumprod[k + 1]))).
+ * G = 0 at k = 0 (h is infinite: A = 0, Bc = 1) and at k = n - 1: no second-order step exists there. */
+int dsh_solver_coeffs(int32_t diffusion_steps, const int32_t* kept, int32_t n, int32_t k, double* out3);
+/* t_T of a mask-present run on that subset (dsh_sample_set_timesteps); 0 = the reference's index rule (n = 0, or a 'ddimK' stride). */
+int32_t dsh_masked_start_level(int32_t diffusion_steps, const int32_t* kept, int32_t n);
 int32_t dsh_timestep_map(int32_t diffusion_steps, int32_t respacing, int32_t* out, int32_t cap);
 int32_t dsh_jump_schedule(int32_t respacing, int32_t jump_length, int32_t jump_n_sample, int32_t* out, int32_t cap);
 
@@ -483,6 +519,13 @@ int dsh_op_ddim_step_full(void* hip_stream, float* x, const float* eps, float* x
                           const float* noise1, const float* tail_in, float* tail_out, int32_t B, int32_t frames, int32_t channels, float c1,
                           float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev, float coef_eps, float sigma, int32_t overlap_len, int32_t blend,
                           int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi);
+/* One step of the DPM2M solver (dsh_sample_set_solver) on x [B, frames, channels] in place.  second_order != 0: the update above with
+ * A, Bc, G (dsh_solver_coeffs, cast to fp32); x0_prev [B, frames, channels] holds the previous step's x0 and receives this step's in the
+ * same pass.  second_order = 0: dsh_op_ddim_step_full at eta = 0 with x0_out = x0_prev (A, Bc, G unused).  mask / gt / noise2, blend,
+ * tail_blend, clip and the channel range [c_lo, c_hi) as in dsh_op_ddim_step; columns outside the range are not touched in x or x0_prev. */
+int dsh_op_dpm2m_step(void* hip_stream, float* x, const float* eps, float* x0_prev, const float* gt, const uint8_t* mask, const float* noise2,
+                      int32_t B, int32_t frames, int32_t channels, float c1, float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev, float A, float Bc,
+                      float G, int32_t second_order, int32_t overlap_len, int32_t blend, int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi);
 /* x0 = c1 x - c2 eps (clamped when clip); x <- coef1 x0 + coef2 x + sigma noise on n values; [c_lo, c_hi) of `channels` restricts the
  * update (c_hi <= c_lo: all); x0_out nullable. */
 int dsh_op_ddpm_step(void* hip_stream, float* x, const float* eps, const float* noise, float* x0_out, int64_t n, float c1, float c2, float coef1,
