@@ -38,6 +38,32 @@ class SamplerOptsC(C.Structure):
                 ("same_overlap_noisy", C.c_int32), ("clip_idx", C.c_int32), ("eta", C.c_float)]
 
 
+class RunSpecC(C.Structure):
+    """dsh_run_spec: everything one loop needs beside its options.  Build it with :func:`run_spec`, which fills in ``struct_size``."""
+    _fields_ = [("struct_size", C.c_uint32), ("init", C.c_int32), ("masked", C.c_int32), ("start_level", C.c_int32),
+                ("invert_from", C.c_int32), ("invert_to", C.c_int32), ("x", C.c_void_p), ("gt", C.c_void_p), ("mask", C.c_void_p),
+                ("noise_stack", C.c_void_p), ("n_draws", C.c_int64), ("trace", C.c_void_p),
+                ("timesteps", C.POINTER(C.c_int32)), ("n_timesteps", C.c_int32), ("tail_blend", C.c_int32),
+                ("row_keys", C.POINTER(C.c_uint64)), ("row_seeds", C.POINTER(C.c_uint64)), ("n_rows", C.c_int32), ("solver", C.c_int32)]
+
+
+def run_spec(timesteps=(), row_keys=(), row_seeds=(), **fields) -> RunSpecC:
+    """A zeroed dsh_run_spec of this binding's size with ``fields`` set; the three host arrays are copied and kept alive by the result."""
+    s = RunSpecC(struct_size=C.sizeof(RunSpecC), **fields)
+    kept, keys = [int(v) for v in timesteps], [int(v) & 0xFFFFFFFFFFFFFFFF for v in row_keys]
+    seeds = [int(v) & 0xFFFFFFFFFFFFFFFF for v in row_seeds]
+    if seeds and len(seeds) != len(keys):               # (the library reads n_rows entries of both)
+        raise ValueError(f"row_seeds needs row_keys and one seed per key ({len(keys)}), got {len(seeds)}")
+    s._arrays = ((C.c_int32 * len(kept))(*kept), (C.c_uint64 * len(keys))(*keys), (C.c_uint64 * len(seeds))(*seeds))
+    if kept:
+        s.timesteps, s.n_timesteps = s._arrays[0], len(kept)
+    if keys:
+        s.row_keys, s.n_rows = s._arrays[1], len(keys)
+    if seeds:
+        s.row_seeds = s._arrays[2]
+    return s
+
+
 # every symbol include/diffsheg_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -60,6 +86,8 @@ SYMBOLS = {
     "dsh_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dsh_profile_class_info": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]),
     "dsh_debug_copy": (C.c_int, [_P, C.c_char_p, _P]),
+    "dsh_sample_run": (C.c_int, [_P, C.POINTER(SamplerOptsC), C.POINTER(RunSpecC)]),
+    "dsh_sample_count": (C.c_int, [C.POINTER(SamplerOptsC), C.POINTER(RunSpecC), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "dsh_sample_num_draws": (C.c_int64, [C.POINTER(SamplerOptsC), C.c_int32, C.c_int32]),
     "dsh_sample_num_steps": (C.c_int64, [C.POINTER(SamplerOptsC), C.c_int32]),
     "dsh_sample": (C.c_int, [_P, C.POINTER(SamplerOptsC), _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int64, _P]),

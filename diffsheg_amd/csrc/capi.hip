@@ -26,6 +26,7 @@ struct dsh_ctx {
     hipStream_t stream = nullptr;
     std::unique_ptr<dsh::DenoiserContext> den;
     std::unique_ptr<dsh::Sampler> sampler;
+    dsh::RunSpec sticky;                               // what the dsh_sample_set_* setters hold for dsh_sample / dsh_invert (dsh_sample_run reads none of it)
     std::map<std::string, dsh::HostTensor> staged;
     dsh::Profiler prof;
     bool finalized = false;
@@ -263,53 +264,91 @@ static dsh::SamplerOpts to_opts(const dsh_sampler_opts* o) {
     return s;
 }
 
-int64_t dsh_sample_num_draws(const dsh_sampler_opts* opts, int32_t masked, int32_t init_from_x) {
-    if (!opts) { dsh::set_last_error("null opts"); return -1; }
-    return dsh::sampler_num_draws(to_opts(opts), masked != 0, init_from_x != 0 ? 1 : 0);
+// dsh_run_spec -> dsh::RunSpec: the caller's struct_size bytes, the rest 0 / null
+static int to_spec(const dsh_sampler_opts* opts, const dsh_run_spec* c, dsh::RunSpec& s) {
+    DSH_REQUIRE(opts && c, "null argument");
+    DSH_REQUIRE(c->struct_size >= sizeof(uint32_t) && c->struct_size <= sizeof(dsh_run_spec), "dsh_run_spec: struct_size is larger than this library knows");
+    dsh_run_spec f{};
+    std::memcpy(&f, c, c->struct_size);
+    DSH_REQUIRE(f.n_timesteps >= 0 && (f.n_timesteps == 0 || f.timesteps), "dsh_run_spec: null timestep list");
+    DSH_REQUIRE(f.n_rows >= 0 && (f.n_rows == 0 || f.row_keys), "dsh_run_spec: null row key array");
+    s.o = to_opts(opts); s.init = f.init; s.x = f.x; s.gt = f.gt; s.mask = f.mask; s.masked = f.masked != 0;
+    s.noise_stack = f.noise_stack; s.n_draws = f.n_draws; s.trace = f.trace;
+    s.start_level = f.start_level; s.invert_from = f.invert_from; s.invert_to = f.invert_to;
+    s.kept.assign(f.timesteps, f.timesteps + f.n_timesteps);
+    s.solver = f.solver; s.tail_blend = f.tail_blend != 0;
+    s.row_keys.assign(f.row_keys, f.row_keys + f.n_rows);
+    if (f.row_seeds) s.row_seeds.assign(f.row_seeds, f.row_seeds + f.n_rows);
+    return 0;
 }
+
+int dsh_sample_run(dsh_ctx* ctx, const dsh_sampler_opts* opts, const dsh_run_spec* spec) {
+    API_BEGIN
+    DSH_REQUIRE(ctx, "null context");
+    dsh::RunSpec s;
+    if (int e = to_spec(opts, spec, s)) return e;
+    if (int e = check_guidance(ctx)) return e;
+    return ctx->sampler->run(ctx->den.get(), s);
+    API_END
+}
+
+int dsh_sample_count(const dsh_sampler_opts* opts, const dsh_run_spec* spec, int64_t* n_draws, int64_t* n_steps) {
+    API_BEGIN
+    dsh::RunSpec s;
+    if (int e = to_spec(opts, spec, s)) return e;
+    return dsh::sampler_count(s, n_draws, n_steps);
+    API_END
+}
+
+// ---- compatibility layer: the sticky values live in ctx->sticky, every entry builds a spec ------------------------------------------
+// (the step count does not depend on the init mode: its entries only range-check theirs)
+static int64_t count_of(bool draws, const dsh_sampler_opts* opts, int32_t masked, int32_t init, int32_t start_level, const int32_t* kept, int32_t n) {
+    if (!opts || n < 0 || (n > 0 && !kept)) { dsh::set_last_error("null argument"); return -1; }
+    if (init < 0 || init > 2) { dsh::set_last_error("unknown init mode"); return -1; }
+    dsh::RunSpec s;
+    s.o = to_opts(opts); s.masked = masked != 0; s.init = draws ? init : 1; s.start_level = start_level; s.kept.assign(kept, kept + n);
+    int64_t out = 0;
+    return dsh::sampler_count(s, draws ? &out : nullptr, draws ? nullptr : &out) ? -1 : out;
+}
+int64_t dsh_sample_num_draws(const dsh_sampler_opts* opts, int32_t masked, int32_t init_from_x) { return count_of(true, opts, masked, init_from_x != 0, 0, nullptr, 0); }
+int64_t dsh_sample_num_steps(const dsh_sampler_opts* opts, int32_t masked) { return count_of(false, opts, masked, 0, 0, nullptr, 0); }
 int64_t dsh_sample_num_draws_from(const dsh_sampler_opts* opts, int32_t masked, int32_t init, int32_t start_level) {
-    if (!opts) { dsh::set_last_error("null opts"); return -1; }
-    return dsh::sampler_num_draws(to_opts(opts), masked != 0, init, start_level);
+    return count_of(true, opts, masked, init, start_level, nullptr, 0);
 }
 int64_t dsh_sample_num_steps_from(const dsh_sampler_opts* opts, int32_t masked, int32_t init, int32_t start_level) {
-    if (!opts) { dsh::set_last_error("null opts"); return -1; }
-    if (init < 0 || init > 2) { dsh::set_last_error("unknown init mode"); return -1; }
-    return dsh::sampler_num_steps(to_opts(opts), masked != 0, start_level);
+    return count_of(false, opts, masked, init, start_level, nullptr, 0);
 }
 int64_t dsh_sample_num_draws_subset(const dsh_sampler_opts* opts, int32_t masked, int32_t init, int32_t start_level, const int32_t* kept, int32_t n) {
-    if (!opts || n < 0 || (n > 0 && !kept)) { dsh::set_last_error("null argument"); return -1; }
-    const std::vector<int> k(kept, kept + n);
-    return dsh::sampler_num_draws(to_opts(opts), masked != 0, init, start_level, &k);
+    return count_of(true, opts, masked, init, start_level, kept, n);
 }
 int64_t dsh_sample_num_steps_subset(const dsh_sampler_opts* opts, int32_t masked, int32_t init, int32_t start_level, const int32_t* kept, int32_t n) {
-    if (!opts || n < 0 || (n > 0 && !kept)) { dsh::set_last_error("null argument"); return -1; }
-    if (init < 0 || init > 2) { dsh::set_last_error("unknown init mode"); return -1; }
-    const std::vector<int> k(kept, kept + n);
-    return dsh::sampler_num_steps(to_opts(opts), masked != 0, start_level, &k);
-}
-int64_t dsh_sample_num_steps(const dsh_sampler_opts* opts, int32_t masked) {
-    if (!opts) { dsh::set_last_error("null opts"); return -1; }
-    return dsh::sampler_num_steps(to_opts(opts), masked != 0);
+    return count_of(false, opts, masked, init, start_level, kept, n);
 }
 
 int dsh_sample_set_row_keys(dsh_ctx* ctx, const uint64_t* keys_host, int32_t n) {
     API_BEGIN
     DSH_REQUIRE(ctx, "null context");
-    return ctx->sampler->set_row_keys(keys_host, n);
+    DSH_REQUIRE(n >= 0 && (n == 0 || keys_host), "set_row_keys: null key array");
+    ctx->sticky.row_keys.assign(keys_host, keys_host + n);
+    ctx->sticky.row_seeds.clear();               // (per-row seeds belong to the key set they were given for)
+    return 0;
     API_END
 }
 
 int dsh_sample_set_row_seeds(dsh_ctx* ctx, const uint64_t* seeds_host, int32_t n) {
     API_BEGIN
     DSH_REQUIRE(ctx, "null context");
-    return ctx->sampler->set_row_seeds(seeds_host, n);
+    DSH_REQUIRE(n >= 0 && (n == 0 || seeds_host), "set_row_seeds: null seed array");
+    DSH_REQUIRE(n == 0 || (size_t)n == ctx->sticky.row_keys.size(), "set_row_seeds: needs the row keys set first, and one seed per row key");
+    ctx->sticky.row_seeds.assign(seeds_host, seeds_host + n);
+    return 0;
     API_END
 }
 
 int dsh_sample_set_tail_blend(dsh_ctx* ctx, int32_t on) {
     API_BEGIN
     DSH_REQUIRE(ctx, "null context");
-    ctx->sampler->set_tail_blend(on);
+    ctx->sticky.tail_blend = on != 0;
     return 0;
     API_END
 }
@@ -317,21 +356,32 @@ int dsh_sample_set_tail_blend(dsh_ctx* ctx, int32_t on) {
 int dsh_sample_set_start_level(dsh_ctx* ctx, int32_t level) {
     API_BEGIN
     DSH_REQUIRE(ctx, "null context");
-    return ctx->sampler->set_start_level(level);
+    DSH_REQUIRE(level >= 0, "set_start_level: negative level");
+    ctx->sticky.start_level = level;
+    return 0;
     API_END
 }
 
+// (a malformed list is refused here and leaves the previous one in place)
 int dsh_sample_set_timesteps(dsh_ctx* ctx, const int32_t* kept_host, int32_t n) {
     API_BEGIN
     DSH_REQUIRE(ctx, "null context");
-    return ctx->sampler->set_timesteps(kept_host, n);
+    DSH_REQUIRE(n >= 0 && (n == 0 || kept_host), "set_timesteps: null timestep list");
+    for (int i = 0; i < n; ++i) {
+        DSH_REQUIRE(kept_host[i] >= 0, "set_timesteps: negative timestep");
+        DSH_REQUIRE(i == 0 || kept_host[i] > kept_host[i - 1], "set_timesteps: timesteps must be strictly ascending");
+    }
+    ctx->sticky.kept.assign(kept_host, kept_host + n);
+    return 0;
     API_END
 }
 
 int dsh_sample_set_solver(dsh_ctx* ctx, int32_t solver) {
     API_BEGIN
     DSH_REQUIRE(ctx, "null context");
-    return ctx->sampler->set_solver(solver);
+    DSH_REQUIRE(solver == dsh::SOLVER_DDIM || solver == dsh::SOLVER_DPM2M, "set_solver: unknown solver (0 ddim, 1 dpm2m)");
+    ctx->sticky.solver = solver;
+    return 0;
     API_END
 }
 
@@ -348,8 +398,10 @@ int dsh_sample(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t ini
     DSH_REQUIRE(ctx && opts, "null argument");
     if (int e = check_guidance(ctx)) return e;
     DSH_REQUIRE(init_from_x >= 0 && init_from_x <= 2, "init_from_x: 0 (x_T is drawn), 1 (x is given) or 2 (x holds x0)");
-    return ctx->sampler->run(ctx->den.get(), to_opts(opts), x, init_from_x, gt, mask, masked != 0, noise_stack,
-                             n_draws, trace);
+    dsh::RunSpec s = ctx->sticky;                 // the setters' values, completed by this call's arguments
+    s.o = to_opts(opts); s.init = init_from_x; s.x = x; s.gt = gt; s.mask = mask; s.masked = masked != 0;
+    s.noise_stack = noise_stack; s.n_draws = n_draws; s.trace = trace;
+    return ctx->sampler->run(ctx->den.get(), s);
     API_END
 }
 
@@ -357,7 +409,10 @@ int dsh_invert_from(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_
     API_BEGIN
     DSH_REQUIRE(ctx && opts, "null argument");
     if (int e = check_guidance(ctx)) return e;
-    return ctx->sampler->invert(ctx->den.get(), to_opts(opts), x, from_level, to_level, trace);
+    DSH_REQUIRE(to_level >= 1, "invert: needs 0 <= from_level < to_level");
+    dsh::RunSpec s = ctx->sticky;                 // (a sticky start level or tail blend is refused, as documented; solver and row keys are not read)
+    s.o = to_opts(opts); s.x = x; s.trace = trace; s.invert_from = from_level; s.invert_to = to_level;
+    return ctx->sampler->run(ctx->den.get(), s);
     API_END
 }
 int dsh_invert(dsh_ctx* ctx, const dsh_sampler_opts* opts, float* x, int32_t to_level, float* trace) {
@@ -1057,21 +1112,30 @@ int dsh_euler_to_axis_angle(void* hip_stream, const float* x, int64_t ld_x, int6
     API_END
 }
 
-int dsh_op_ddim_step(void* hip_stream, float* x, const float* eps, const float* gt, const uint8_t* mask, const float* noise2,
-                     int32_t B, int32_t frames, int32_t channels, float c1, float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev,
+// what the three step ops share, checked, as the eta = 0 step without saved noisy tails; each entry adds what is its own
+static int step_args(const std::string& what, dsh::DdimStepArgs& a, float* x, const float* eps, float* x0_out, const float* gt, const uint8_t* mask,
+                     const float* noise2, int32_t B, int32_t frames, int32_t channels, float c1, float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev,
                      int32_t overlap_len, int32_t blend, int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi) {
-    API_BEGIN
     DSH_REQUIRE(x && eps && B > 0 && frames > 0 && channels > 0, "invalid argument");
-    DSH_REQUIRE(!mask || (gt && noise2), "ddim_step: a mask needs gt and noise2");
-    DSH_REQUIRE(overlap_len >= 0 && overlap_len <= frames, "ddim_step: 0 <= overlap_len <= frames");
-    DSH_REQUIRE(!tail_blend || 2 * (int64_t)overlap_len <= frames, "ddim_step: tail_blend needs 2 * overlap_len <= frames");
-    DSH_REQUIRE(c_lo >= 0 && c_hi <= channels, "ddim_step: channel range outside [0, channels]");
-    dsh::DdimStepArgs a;
-    a.x = x; a.eps = eps; a.x0_out = nullptr; a.c1 = c1; a.c2 = c2; a.sqrt_ab_prev = sqrt_ab_prev; a.sqrt_1m_ab_prev = sqrt_1m_ab_prev;
+    DSH_REQUIRE(!mask || (gt && noise2), what + ": a mask needs gt and noise2");
+    DSH_REQUIRE(overlap_len >= 0 && overlap_len <= frames, what + ": 0 <= overlap_len <= frames");
+    DSH_REQUIRE(!tail_blend || 2 * (int64_t)overlap_len <= frames, what + ": tail_blend needs 2 * overlap_len <= frames");
+    DSH_REQUIRE(c_lo >= 0 && c_hi <= channels, what + ": channel range outside [0, channels]");
+    a.x = x; a.eps = eps; a.x0_out = x0_out; a.c1 = c1; a.c2 = c2; a.sqrt_ab_prev = sqrt_ab_prev; a.sqrt_1m_ab_prev = sqrt_1m_ab_prev;
     a.coef_eps = sqrt_1m_ab_prev; a.sigma = 0.f; a.noise1 = nullptr;
     a.mask = mask; a.gt = gt; a.noise2 = noise2; a.blend = (mask && blend) ? 1 : 0; a.tail_blend = (a.blend && tail_blend) ? 1 : 0;
     a.clip = clip; a.overlap_len = overlap_len; a.frames = frames; a.channels = channels; a.n = (size_t)B * frames * channels;
     a.tail_in = nullptr; a.tail_out = nullptr; a.c_lo = c_lo; a.c_hi = c_hi;
+    return 0;
+}
+
+int dsh_op_ddim_step(void* hip_stream, float* x, const float* eps, const float* gt, const uint8_t* mask, const float* noise2,
+                     int32_t B, int32_t frames, int32_t channels, float c1, float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev,
+                     int32_t overlap_len, int32_t blend, int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi) {
+    API_BEGIN
+    dsh::DdimStepArgs a;
+    if (int e = step_args("ddim_step", a, x, eps, nullptr, gt, mask, noise2, B, frames, channels, c1, c2, sqrt_ab_prev, sqrt_1m_ab_prev, overlap_len,
+                          blend, tail_blend, clip, c_lo, c_hi)) return e;
     return dsh::launch_ddim_step(a, reinterpret_cast<hipStream_t>(hip_stream));
     API_END
 }
@@ -1232,18 +1296,11 @@ int dsh_op_ddim_step_full(void* hip_stream, float* x, const float* eps, float* x
                           float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev, float coef_eps, float sigma, int32_t overlap_len, int32_t blend,
                           int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi) {
     API_BEGIN
-    DSH_REQUIRE(x && eps && B > 0 && frames > 0 && channels > 0, "invalid argument");
-    DSH_REQUIRE(!mask || (gt && noise2), "ddim_step: a mask needs gt and noise2");
-    DSH_REQUIRE(overlap_len >= 0 && overlap_len <= frames, "ddim_step: 0 <= overlap_len <= frames");
-    DSH_REQUIRE(!tail_blend || 2 * (int64_t)overlap_len <= frames, "ddim_step: tail_blend needs 2 * overlap_len <= frames");
-    DSH_REQUIRE(c_lo >= 0 && c_hi <= channels, "ddim_step: channel range outside [0, channels]");
-    DSH_REQUIRE(!tail_in || mask, "ddim_step: tail_in replaces the noised gt of a masked step (needs a mask)");
     dsh::DdimStepArgs a;
-    a.x = x; a.eps = eps; a.x0_out = x0_out; a.c1 = c1; a.c2 = c2; a.sqrt_ab_prev = sqrt_ab_prev; a.sqrt_1m_ab_prev = sqrt_1m_ab_prev;
-    a.coef_eps = coef_eps; a.sigma = sigma; a.noise1 = noise1;
-    a.mask = mask; a.gt = gt; a.noise2 = noise2; a.blend = (mask && blend) ? 1 : 0; a.tail_blend = (a.blend && tail_blend) ? 1 : 0;
-    a.clip = clip; a.overlap_len = overlap_len; a.frames = frames; a.channels = channels; a.n = (size_t)B * frames * channels;
-    a.tail_in = tail_in; a.tail_out = tail_out; a.c_lo = c_lo; a.c_hi = c_hi;
+    if (int e = step_args("ddim_step", a, x, eps, x0_out, gt, mask, noise2, B, frames, channels, c1, c2, sqrt_ab_prev, sqrt_1m_ab_prev, overlap_len,
+                          blend, tail_blend, clip, c_lo, c_hi)) return e;
+    DSH_REQUIRE(!tail_in || mask, "ddim_step: tail_in replaces the noised gt of a masked step (needs a mask)");
+    a.coef_eps = coef_eps; a.sigma = sigma; a.noise1 = noise1; a.tail_in = tail_in; a.tail_out = tail_out;
     return dsh::launch_ddim_step(a, reinterpret_cast<hipStream_t>(hip_stream));
     API_END
 }
@@ -1252,29 +1309,13 @@ int dsh_op_dpm2m_step(void* hip_stream, float* x, const float* eps, float* x0_pr
                       int32_t B, int32_t frames, int32_t channels, float c1, float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev, float A, float Bc,
                       float G, int32_t second_order, int32_t overlap_len, int32_t blend, int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi) {
     API_BEGIN
-    DSH_REQUIRE(x && eps && x0_prev && B > 0 && frames > 0 && channels > 0, "invalid argument");
-    DSH_REQUIRE(!mask || (gt && noise2), "dpm2m_step: a mask needs gt and noise2");
-    DSH_REQUIRE(overlap_len >= 0 && overlap_len <= frames, "dpm2m_step: 0 <= overlap_len <= frames");
-    DSH_REQUIRE(!tail_blend || 2 * (int64_t)overlap_len <= frames, "dpm2m_step: tail_blend needs 2 * overlap_len <= frames");
-    DSH_REQUIRE(c_lo >= 0 && c_hi <= channels, "dpm2m_step: channel range outside [0, channels]");
-    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-    const int bl = (mask && blend) ? 1 : 0, tbl = (bl && tail_blend) ? 1 : 0;
-    if (!second_order) {
-        // the first-order form is the DDIM step at eta = 0, with its x0 left in the history
-        dsh::DdimStepArgs a;
-        a.x = x; a.eps = eps; a.x0_out = x0_prev; a.c1 = c1; a.c2 = c2; a.sqrt_ab_prev = sqrt_ab_prev; a.sqrt_1m_ab_prev = sqrt_1m_ab_prev;
-        a.coef_eps = sqrt_1m_ab_prev; a.sigma = 0.f; a.noise1 = nullptr;
-        a.mask = mask; a.gt = gt; a.noise2 = noise2; a.blend = bl; a.tail_blend = tbl;
-        a.clip = clip; a.overlap_len = overlap_len; a.frames = frames; a.channels = channels; a.n = (size_t)B * frames * channels;
-        a.tail_in = nullptr; a.tail_out = nullptr; a.c_lo = c_lo; a.c_hi = c_hi;
-        return dsh::launch_ddim_step(a, s);
-    }
-    dsh::Dpm2mStepArgs d;
-    d.x = x; d.eps = eps; d.x0_prev = x0_prev; d.c1 = c1; d.c2 = c2; d.A = A; d.Bc = Bc; d.G = G;
-    d.sqrt_ab_prev = sqrt_ab_prev; d.sqrt_1m_ab_prev = sqrt_1m_ab_prev; d.mask = mask; d.gt = gt; d.noise2 = noise2;
-    d.blend = bl; d.tail_blend = tbl; d.clip = clip; d.overlap_len = overlap_len; d.frames = frames; d.channels = channels;
-    d.n = (size_t)B * frames * channels; d.c_lo = c_lo; d.c_hi = c_hi;
-    return dsh::launch_dpm2m_step(d, s);
+    DSH_REQUIRE(x0_prev, "invalid argument");
+    dsh::DdimStepArgs a;
+    if (int e = step_args("dpm2m_step", a, x, eps, x0_prev, gt, mask, noise2, B, frames, channels, c1, c2, sqrt_ab_prev, sqrt_1m_ab_prev, overlap_len,
+                          blend, tail_blend, clip, c_lo, c_hi)) return e;
+    // (the first-order form is the DDIM step at eta = 0, with its x0 left in the history)
+    a.second = second_order ? 1 : 0; a.A = A; a.Bc = Bc; a.G = G;
+    return dsh::launch_ddim_step(a, reinterpret_cast<hipStream_t>(hip_stream));
     API_END
 }
 

@@ -236,25 +236,14 @@ struct DdimStepArgs {
     // channel range [c_lo, c_hi) of the update (0 / 0 = all): the expression and the gesture channels of a sample never interact in the sampler's
     // element-wise updates, so the two encoders' chains may advance on their own streams (sampler.hip, pipelined small-batch loop)
     int c_lo = 0, c_hi = 0;
+    // second != 0: the step is one second-order DPM-Solver++(2M) update in the data-prediction form, eta = 0: x0 as above (clamped when
+    // clip is on), D = x0 + G (x0 - x0_prev), x <- A x + Bc D, then the RePaint branch unchanged.  x0_out (required) holds x0_prev on entry
+    // and x0 on return, in the columns [c_lo, c_hi).  A, Bc, G: solver_coeffs() of sampler.h (fp64 -> fp32).  coef_eps and sigma are not read;
+    // noise1, tail_in and tail_out must be null.
+    int second = 0;
+    float A = 0.f, Bc = 0.f, G = 0.f;
 };
 int launch_ddim_step(const DdimStepArgs& a, hipStream_t s);
-// One second-order DPM-Solver++(2M) step in the data-prediction form (sampler_kernels.hip), eta = 0: x0 as the DDIM step takes it (clamped
-// when clip is on), D = x0 + G (x0 - x0_prev), x <- A x + Bc D, then the DDIM step's RePaint branch unchanged; x0_prev <- x0 in the same
-// pass.  A, Bc, G: solver_coeffs() of sampler.h (fp64 -> fp32).  Only the columns [c_lo, c_hi) of x and x0_prev are touched.
-struct Dpm2mStepArgs {
-    float* x;              // [n] in/out sample
-    const float* eps;      // [n] model output
-    float* x0_prev;        // [n] in: the previous step's x0, out: this step's
-    float c1, c2;          // as DdimStepArgs
-    float A, Bc, G;
-    float sqrt_ab_prev, sqrt_1m_ab_prev;   // the noised gt of the RePaint branch, as DdimStepArgs
-    const uint8_t* mask; const float* gt; const float* noise2;
-    int blend, tail_blend, clip;
-    int overlap_len, frames, channels;
-    size_t n;
-    int c_lo = 0, c_hi = 0;
-};
-int launch_dpm2m_step(const Dpm2mStepArgs& a, hipStream_t s);
 int launch_undo_step(float* x, const float* noise, float sqrt_1m_beta, float sqrt_beta, size_t n, hipStream_t s, int channels = 0, int c_lo = 0, int c_hi = 0);
 struct DdpmStepArgs {
     float* x; const float* eps; const float* noise; float* x0_out;

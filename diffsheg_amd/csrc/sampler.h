@@ -42,48 +42,56 @@ struct SamplerOpts {
 enum StepKind { STEP_DDIM = 0, STEP_UNDO = 1, STEP_DDPM = 2, STEP_REVERSE = 3 };
 struct SamplerStep { StepKind kind; int level; };
 
-// init: 0 x_T is drawn (draw 0), 1 x is given at the schedule's first level, 2 x holds x0 and is noised to that level with draw 0.
-// start_level K (DDIM, 1 .. respacing; 0: the whole schedule): the plain schedule is levels K-1 .. 0, the mask-present one
-// jump_schedule_from(K).
-// kept (nullable): the free timestep subset of the run (Sampler::set_timesteps); its length must be o.respacing.  The counts depend on its
-// length and, mask-present, on masked_start_level() only.
-int64_t sampler_num_draws(const SamplerOpts& o, bool masked, int init, int start_level = 0, const std::vector<int>* kept = nullptr);
-int64_t sampler_num_steps(const SamplerOpts& o, bool masked, int start_level = 0, const std::vector<int>* kept = nullptr);
+// Everything one loop needs from its caller.  The Sampler keeps none of it between calls.
+//   init         0 x_T is drawn (draw 0), 1 x is given at the schedule's first level, 2 x holds x0 and is noised to that level with draw 0
+//   start_level  K (DDIM, 1 .. respacing; 0: the whole schedule): the plain schedule is levels K-1 .. 0, the mask-present one
+//                jump_schedule_from(K); x enters at level K - 1 (an edit of an existing motion: init 1 or 2)
+//   invert_to    > 0: the reverse loop (DDIM inversion, ddim_reverse_sample, gaussian_diffusion.py:1068-1104): x, a clean motion at
+//                invert_from 0 or a state at that level, is carried up the reverse ODE through levels invert_from .. invert_to - 1 in
+//                place; no draws (init, the noise fields, the solver and the row keys are not read), eta = 0 only, no mask
+//   kept         the free timestep subset the DDIM loops and the reverse loop run on instead of the 'ddimK' stride (empty: the stride):
+//                strictly ascending, its length o.respacing, every entry in [0, o.diffusion_steps).  The counts depend on its length and,
+//                mask-present, on masked_start_level() only
+//   solver       SOLVER_DPM2M: a DDIM step at level k whose previous executed step of the run was the DDIM step at level k + 1, k != 0, is
+//                the second-order DPM-Solver++(2M) update; every other step (the first of a run, the one after an undo step, the last) is
+//                the DDIM update bit for bit.  Draws are those of the DDIM loop.  eta = 0 only, no same_overlap_noisy, no DDPM loop
+//   tail_blend   windows pinned at both ends (in-betweening / seam repair): the DDIM step's cross-fade also runs, mirrored, on the last
+//                overlap_len frames (sampler_kernels.hip); false = the reference's head-only fade
+//   row_keys     Philox mode: one key per batch row (empty: one stream for the whole batch).  A chain keyed by its global id draws the same
+//                noise whatever batch / rank it is sampled in (sharded long-audio path)
+//   row_seeds    beside the row keys, one per key: row b draws from the key row_seeds[b] in place of o.seed (every draw of the run: x_T, the
+//                steps' randn_like, the RePaint blend's gt noise, the undo steps, the eta scratch; main chain and gesture-side twin alike),
+//                so rows of one batch may stand at different windows of their chains
+//   trace        (nullable) [steps, n]: the sample after every step
+struct RunSpec {
+    SamplerOpts o;
+    int init = 0;
+    float* x = nullptr; const float* gt = nullptr; const uint8_t* mask = nullptr; bool masked = false;
+    const float* noise_stack = nullptr; int64_t n_draws = 0;
+    float* trace = nullptr;
+    int start_level = 0, invert_from = 0, invert_to = 0;
+    std::vector<int> kept;
+    int solver = SOLVER_DDIM;
+    bool tail_blend = false;
+    std::vector<uint64_t> row_keys, row_seeds;
+};
+// what check_run() needs of the conditioned context (lengths: the ragged batch's per-clip frame counts on the host, or null)
+struct RunShape { int batch, frames, channels, gesture_cols, modality; const int32_t* lengths; };
+// Every refusal of a run, on the host, with no GPU call and no state: 0, or -1 with the reason in err.  shape null: what can be said without
+// a conditioned context (the counting path); else also the pointers and what depends on the batch (the noise stack's length is run()'s to
+// check, against the schedule it plans next).
+int check_run(const RunSpec& s, const RunShape* shape, std::string& err);
+// draws (Gaussian tensors the loop consumes; 0 for the reverse loop) and steps (rows of a trace) of a run; either may be null.  -1 with
+// set_last_error() on what check_run(s, null) refuses.
+int sampler_count(const RunSpec& s, int64_t* draws, int64_t* steps);
 
 class Sampler {
   public:
     Sampler(hipStream_t s, int channels_) : st(s), channels(channels_) {}
     ~Sampler();
     Profiler* prof = nullptr;
-    // Philox mode: per-row keys (one per batch row; empty = one stream for the whole batch).  A chain keyed by its
-    // global id draws the same noise whatever batch / rank it is sampled in (sharded long-audio path).
-    int set_row_keys(const uint64_t* keys_host, int n);
-    // Philox mode, beside the row keys: row b draws from the key seeds_host[b] in place of SamplerOpts.seed (every draw of run(): x_T,
-    // the steps' randn_like, the RePaint blend's gt noise, the undo steps, the eta scratch; main chain and gesture-side twin alike), so
-    // rows of one batch may stand at different windows of their chains.  Needs the row keys set and n equal to their count (-1 before
-    // any state changes otherwise); sticky like the keys, n = 0 clears it, and so does every set_row_keys (the seeds belong to that key set).
-    int set_row_seeds(const uint64_t* seeds_host, int n);
-    // windows pinned at both ends (in-betweening / seam repair): the DDIM step's cross-fade also runs, mirrored, on the last
-    // overlap_len frames (sampler_kernels.hip).  Sticky like the row keys; 0 = the reference's head-only fade.
-    void set_tail_blend(int on) { tail_blend = on != 0; }
-    // DDIM loops start at spaced level K - 1 instead of the top of the schedule (an edit of an existing motion: init 1 with x at that
-    // level, or init 2 with x = x0).  Sticky like the tail blend; 0 = the whole schedule.  Range-checked by run() (needs the respacing).
-    int set_start_level(int K);
-    // DDIM loops (and the reverse ODE) run on these original timesteps instead of the 'ddimK' stride: strictly ascending, >= 0; n must equal
-    // SamplerOpts.respacing and every entry lie below diffusion_steps when a loop runs (-1 before any state changes otherwise, and on a
-    // DDPM loop).  Sticky; n = 0 restores the stride.  A malformed list is refused here and leaves the previous one in place.
-    int set_timesteps(const int32_t* kept_host, int n);
-    // SOLVER_DPM2M: a DDIM step at level k whose previous executed step of the run was the DDIM step at level k + 1, k != 0, is the
-    // second-order DPM-Solver++(2M) update; every other step (the first of a run, the one after an undo step, the last) is the DDIM
-    // update bit for bit.  Draws are those of the DDIM loop.  eta = 0 only, no same_overlap_noisy, no DDPM loop (run() returns -1
-    // before any state changes).  The reverse ODE ignores it.  Sticky; an unknown value is refused here.
-    int set_solver(int solver);
-    // init: 0 / 1 / 2 as for sampler_num_draws
-    int run(DenoiserContext* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask,
-            bool masked, const float* noise_stack, int64_t n_draws, float* trace);
-    // DDIM inversion: x (a clean motion at from_level 0, or a state at level from_level) is carried up the reverse ODE through levels
-    // from_level .. to_level - 1, in place; no draws, eta = 0 only, no mask.  trace [to_level - from_level, n] as in run().
-    int invert(DenoiserContext* den, const SamplerOpts& o, float* x, int from_level, int to_level, float* trace);
+    // the forward loops and the reverse loop (s.invert_to > 0); -1 before any state changes on what check_run() refuses
+    int run(DenoiserContext* den, const RunSpec& s);
 
   private:
     // One set of the device buffers a chain works in: the noise scratch of a step's two draws, the per-step scalars an evaluation reads
@@ -112,7 +120,7 @@ class Sampler {
     struct Run; struct LoopPlan; struct StepConsts;
     // run() = argument checks, then these in order; finish() joins the chains whatever loop() returned
     int ensure(size_t n, int B, bool want_hist);
-    int prepare(Run& r);
+    int prepare(Run& r, const RunSpec& s);
     int make_chains(Run& r);
     LoopPlan plan(const Run& r) const;
     int loop(Run& r, const LoopPlan& p);
@@ -141,14 +149,10 @@ class Sampler {
     ChainBufs bufs[2];
     size_t cap_n2 = 0, cap_eta = 0;
     DiffusionTables tb; int tb_steps = -1, tb_resp = -1; std::vector<int> tb_kept;    // cache key: (steps, respacing, subset)
-    uint64_t* row_keys = nullptr; int n_row_keys = 0, cap_row_keys = 0;
-    uint64_t* row_seeds = nullptr; int n_row_seeds = 0, cap_row_seeds = 0;
-    bool tail_blend = false;
-    int start_level = 0;
-    std::vector<int> kept;                // set_timesteps (empty: the stride)
-    int solver = SOLVER_DDIM;
-    int run_schedule(DenoiserContext* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask, bool masked,
-                     const float* noise_stack, int64_t n_draws, float* trace, int start, int invert_to, int invert_from);
+    // the device copies of a run's row keys / row seeds with what they hold (host): a caller that keeps its keys pays one upload, not one per run
+    uint64_t* row_keys = nullptr; int cap_row_keys = 0; std::vector<uint64_t> row_keys_held;
+    uint64_t* row_seeds = nullptr; int cap_row_seeds = 0; std::vector<uint64_t> row_seeds_held;
+    int upload_rows(const std::vector<uint64_t>& host, uint64_t*& dev, int& cap, std::vector<uint64_t>& held);
     int init_x(Run& r);
     // --same_overlap_noisy: the noisy tail x[..., -L:, :] saved after every DDIM step, one slot per spaced level; persists
     // across sample() calls like the reference's self.saved_noisy_tail (the dict the next window receives IS this object)

@@ -139,35 +139,80 @@ std::vector<int> jump_schedule_from(int respacing, int jump_length, int jump_n_s
 }
 
 // ------------------------------------------------------------------------------------------------
-// The schedule of a run.  start (> 0): the DDIM schedules begin at level start - 1.  invert_to (> 0): the reverse ODE, levels invert_from .. invert_to - 1.
-// kept (nullable / empty: the 'ddimK' stride): the run's free timestep subset; a mask-present schedule without a start level then begins at masked_start_level().
-static int plan_steps(const SamplerOpts& o, bool masked, int start, int invert_to, std::vector<SamplerStep>& steps, std::string& err, int invert_from = 0,
-                      const std::vector<int>* kept = nullptr) {
+// Every refusal of a run (sampler.h).  The order is part of the interface: callers read the first reason.
+int check_run(const RunSpec& s, const RunShape* sh, std::string& err) {
+#define RUN_REQUIRE(cond, msg) do { if (!(cond)) { err = (msg); return -1; } } while (0)
+    const SamplerOpts& o = s.o;
+    const bool reverse = s.invert_to > 0, son = o.same_overlap_noisy != 0, philox = o.noise_mode == 1;
+    RUN_REQUIRE(reverse || (s.init >= 0 && s.init <= 2), "unknown init mode");
+    RUN_REQUIRE(reverse || s.init != 2 || o.kind == 0, "init mode 2 (x holds x0) exists for the DDIM loops only");
+    RUN_REQUIRE(o.noise_mode == 0 || philox, "unknown noise mode");
+    // the timestep subset
+    for (size_t i = 0; i < s.kept.size(); ++i) {
+        RUN_REQUIRE(s.kept[i] >= 0, "timestep subset: entry outside [0, diffusion_steps)");
+        RUN_REQUIRE(i == 0 || s.kept[i] > s.kept[i - 1], "timestep subset: entries must be strictly ascending");
+    }
+    if (!s.kept.empty()) {
+        RUN_REQUIRE(o.kind == 0, "a timestep subset exists for the DDIM loops only");
+        RUN_REQUIRE((int)s.kept.size() == o.respacing, "the timestep subset's length differs from opts.respacing");
+        RUN_REQUIRE(s.kept.back() < o.diffusion_steps, "timestep subset: entry outside [0, diffusion_steps)");
+    }
+    // a start level, the reverse loop
+    if (s.start_level != 0 || s.invert_to != 0) {
+        RUN_REQUIRE(o.kind == 0, "a start level / the reverse loop exist for the DDIM loops only");
+        RUN_REQUIRE(s.start_level >= 0 && s.start_level <= o.respacing, "start level outside 1 .. respacing");
+        RUN_REQUIRE(s.invert_to >= 0 && s.invert_to <= o.respacing, "inversion level outside 1 .. respacing");
+    }
+    RUN_REQUIRE(s.start_level == 0 || (!son && !s.tail_blend), "a start level exists for the DDIM loops only, without same_overlap_noisy and the tail blend");
+    RUN_REQUIRE(reverse ? (s.invert_from >= 0 && s.invert_from < s.invert_to) : s.invert_from == 0, "the reverse loop needs 0 <= from_level < to_level");
+    if (reverse) {
+        RUN_REQUIRE(!s.masked && s.start_level == 0, "the reverse loop takes no mask and no start level");
+        RUN_REQUIRE(o.eta == 0.f, "the reverse ODE exists for the DDIM loops at eta = 0 only");
+        RUN_REQUIRE(!son && !s.tail_blend, "same_overlap_noisy and the tail blend do not apply to the reverse loop");
+    }
+    RUN_REQUIRE(o.kind == 0 || o.kind == 1, "unknown sampler kind");
+    RUN_REQUIRE(s.solver == SOLVER_DDIM || s.solver == SOLVER_DPM2M, "unknown solver (0 ddim, 1 dpm2m)");
+    if (s.solver == SOLVER_DPM2M && !reverse) {                   // (the reverse ODE stays first-order whatever the solver)
+        RUN_REQUIRE(o.kind == 0, "the dpm2m solver exists for the DDIM loops only");
+        RUN_REQUIRE(o.eta == 0.f, "the dpm2m solver is deterministic: eta must be 0");
+        RUN_REQUIRE(!son, "the dpm2m solver does not keep the saved noisy tails of same_overlap_noisy");
+    }
+    RUN_REQUIRE(!(s.tail_blend && son), "tail_blend with same_overlap_noisy: the saved noisy tails describe a window chain, not a window pinned at both ends");
+    RUN_REQUIRE(s.row_seeds.empty() || s.row_seeds.size() == s.row_keys.size(), "row seeds need the row keys, and one seed per row key");
+    if (!sh) return 0;
+    // what depends on the conditioned context
+    RUN_REQUIRE(s.x != nullptr, "null sample buffer");
+    RUN_REQUIRE(!s.masked || (s.gt && s.mask), "masked sampling needs gt and mask");
+    RUN_REQUIRE(!(s.masked && o.kind == 1), "mask-present DDPM (p_sample_loop_progressive_harmonize) is not supported");
+    RUN_REQUIRE(!s.tail_blend || (o.overlap_len >= 0 && 2 * (int64_t)o.overlap_len <= sh->frames), "tail_blend: the head and the tail fade overlap (2 * overlap_len > frames)");
+    RUN_REQUIRE(sh->modality == 0 || (sh->gesture_cols > 0 && sh->gesture_cols < sh->channels), "a partial modality needs the UniDiffuser's two encoders");
+    RUN_REQUIRE(sh->modality == 0 || !son, "same_overlap_noisy with a partial modality: the saved noisy tails describe all channels");
+    // (both address the last overlap_len frames of the PADDED window, which a short clip does not reach)
+    RUN_REQUIRE(!sh->lengths || (!son && !s.tail_blend), "per-clip lengths cannot be combined with same_overlap_noisy or the tail blend");
+    // (the reverse loop draws nothing: row keys do not concern it)
+    if (!s.row_keys.empty() && philox && !reverse) {
+        RUN_REQUIRE((int)s.row_keys.size() == sh->batch && ((int64_t)sh->frames * sh->channels) % 4 == 0,
+                    "row keys were set for a different batch size (or frames*channels is not a multiple of 4)");
+        for (int b = 0; sh->lengths && b < sh->batch; ++b)
+            RUN_REQUIRE(((int64_t)sh->lengths[b] * sh->channels) % 4 == 0, "row keys on a ragged batch: length * channels must be a multiple of 4 for every clip");
+    }
+    return 0;
+#undef RUN_REQUIRE
+}
+
+// The schedule of a spec check_run() has passed.  A start level: the DDIM schedules begin at level start_level - 1; a mask-present schedule on
+// a free subset without one begins at masked_start_level().
+static int plan_steps(const RunSpec& s, std::vector<SamplerStep>& steps, std::string& err) {
+    const SamplerOpts& o = s.o;
     steps.clear();
-    if (kept && !kept->empty()) {
-        if (o.kind != 0) { err = "a timestep subset exists for the DDIM loops only"; return -1; }
-        if ((int)kept->size() != o.respacing) { err = "the timestep subset's length differs from opts.respacing"; return -1; }
-        if (kept->back() >= o.diffusion_steps) { err = "timestep subset: entry outside [0, diffusion_steps)"; return -1; }
-    }
-    if (start != 0 || invert_to != 0) {
-        if (o.kind != 0) { err = "a start level / the reverse loop exist for the DDIM loops only"; return -1; }
-        if (start < 0 || start > o.respacing) { err = "start level outside 1 .. respacing"; return -1; }
-        if (invert_to < 0 || invert_to > o.respacing) { err = "inversion level outside 1 .. respacing"; return -1; }
-    }
-    if (invert_to > 0) {
-        if (masked || start != 0) { err = "the reverse loop takes no mask and no start level"; return -1; }
-        if (invert_from < 0 || invert_from >= invert_to) { err = "the reverse loop needs 0 <= from_level < to_level"; return -1; }
-        for (int k = invert_from; k < invert_to; ++k) steps.push_back({STEP_REVERSE, k});
-        return 0;
-    }
-    if (o.kind == 1) {  // DDPM ancestral, full chain
+    if (s.invert_to > 0) {
+        for (int k = s.invert_from; k < s.invert_to; ++k) steps.push_back({STEP_REVERSE, k});
+    } else if (o.kind == 1) {  // DDPM ancestral, full chain
         for (int t = o.diffusion_steps - 1; t >= 0; --t) steps.push_back({STEP_DDPM, t});
-        return 0;
-    }
-    if (o.kind != 0) { err = "unknown sampler kind"; return -1; }
-    if (masked && !o.no_repaint) {
-        if (start == 0 && kept && !kept->empty()) {
-            start = masked_start_level(o.diffusion_steps, *kept, err);
+    } else if (s.masked && !o.no_repaint) {
+        int start = s.start_level;
+        if (start == 0 && !s.kept.empty()) {
+            start = masked_start_level(o.diffusion_steps, s.kept, err);
             if (start < 0) return -1;
         }
         const std::vector<int> times = o.no_resample ? jump_schedule_from(o.respacing, 1, 1, start)
@@ -178,33 +223,32 @@ static int plan_steps(const SamplerOpts& o, bool masked, int start, int invert_t
             steps.push_back({t_cur < t_last ? STEP_DDIM : STEP_UNDO, t_last});
         }
     } else {
-        for (int k = (start > 0 ? start : o.respacing) - 1; k >= 0; --k) steps.push_back({STEP_DDIM, k});
+        for (int k = (s.start_level > 0 ? s.start_level : o.respacing) - 1; k >= 0; --k) steps.push_back({STEP_DDIM, k});
     }
     return 0;
 }
 
-int64_t sampler_num_draws(const SamplerOpts& o, bool masked, int init, int start_level, const std::vector<int>* kept) {
-    std::vector<SamplerStep> steps; std::string err;
-    if (init < 0 || init > 2) { set_last_error("unknown init mode"); return -1; }
-    if (init == 2 && o.kind != 0) { set_last_error("init mode 2 (x holds x0) exists for the DDIM loops only"); return -1; }
-    if (plan_steps(o, masked, start_level, 0, steps, err, 0, kept)) { set_last_error(err); return -1; }
-    int64_t n = init == 1 ? 0 : 1;                                             // x_T, or the q_sample noise of init 2
-    const bool tail_gt = masked && o.same_overlap_noisy && o.clip_idx > 0;     // that branch draws no gt noise
-    for (const auto& s : steps) n += (s.kind == STEP_DDIM) ? ((masked && !tail_gt) ? 2 : 1) : 1;
+static int64_t count_draws(const RunSpec& s, const std::vector<SamplerStep>& steps) {
+    if (s.invert_to > 0) return 0;
+    int64_t n = s.init == 1 ? 0 : 1;                                                      // x_T, or the q_sample noise of init 2
+    const bool tail_gt = s.masked && s.o.same_overlap_noisy && s.o.clip_idx > 0;          // that branch draws no gt noise
+    for (const auto& sp : steps) n += (sp.kind == STEP_DDIM) ? ((s.masked && !tail_gt) ? 2 : 1) : 1;
     return n;
 }
-int64_t sampler_num_steps(const SamplerOpts& o, bool masked, int start_level, const std::vector<int>* kept) {
-    std::vector<SamplerStep> steps; std::string err;
-    if (plan_steps(o, masked, start_level, 0, steps, err, 0, kept)) { set_last_error(err); return -1; }
-    return (int64_t)steps.size();
+
+int sampler_count(const RunSpec& s, int64_t* draws, int64_t* steps) {
+    std::vector<SamplerStep> plan; std::string err;
+    if (check_run(s, nullptr, err) || plan_steps(s, plan, err)) { set_last_error(err); return -1; }
+    if (draws) *draws = count_draws(s, plan);
+    if (steps) *steps = (int64_t)plan.size();
+    return 0;
 }
 
 // One run()'s arguments, what is derived from them once, its chains and the loop's running state; the parts of run() share it by reference.
 enum LevelCache { CACHE_NONE, CACHE_INLINE, CACHE_PREFETCH, CACHE_SUBS };
 struct Sampler::Run {
     DenoiserContext* den; const SamplerOpts& o; float* x; int init; const float* gt; const uint8_t* mask; bool masked;
-    const float* noise_stack; int64_t n_draws; float* trace;
-    int start, invert_from, invert_to;                   // start level of the DDIM schedules (0: the top); reverse loop over these levels (to 0: none)
+    const float* noise_stack; float* trace; bool tail_blend;
     int B = 0; size_t n = 0, row_n = 0;                  // clips, values, values per clip
     int mod = 0, gcols = 0, w_lo = 0, w_hi = 0;          // modality, gesture columns, the active column window (0, 0: all)
     const int* len_d = nullptr;                          // ragged batch: per-clip frame counts (device)
@@ -251,49 +295,14 @@ Sampler::~Sampler() {
     for (void* p : {(void*)row_keys, (void*)row_seeds, (void*)tails, (void*)tail_tmp, (void*)bufs[0].nz_eta, (void*)hist}) if (p) (void)hipFree(p);
 }
 
-int Sampler::set_row_keys(const uint64_t* keys_host, int n) {
-    DSH_REQUIRE(n >= 0 && (n == 0 || keys_host), "set_row_keys: null key array");
-    n_row_keys = 0;
-    n_row_seeds = 0;               // (per-row seeds belong to the key set they were given for)
-    if (n == 0) return 0;
-    if (n > cap_row_keys) { if (int e = grow_device_buffer(row_keys, cap_row_keys, (size_t)n, st)) return e; }
-    DSH_HIP_CHECK(hipMemcpyAsync(row_keys, keys_host, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    DSH_HIP_CHECK(hipStreamSynchronize(st));       // keys_host is pageable caller memory
-    n_row_keys = n;
-    return 0;
-}
-
-int Sampler::set_start_level(int K) {
-    DSH_REQUIRE(K >= 0, "set_start_level: negative level");
-    start_level = K;
-    return 0;
-}
-
-int Sampler::set_timesteps(const int32_t* kept_host, int n) {
-    DSH_REQUIRE(n >= 0 && (n == 0 || kept_host), "set_timesteps: null timestep list");
-    for (int i = 0; i < n; ++i) {
-        DSH_REQUIRE(kept_host[i] >= 0, "set_timesteps: negative timestep");
-        DSH_REQUIRE(i == 0 || kept_host[i] > kept_host[i - 1], "set_timesteps: timesteps must be strictly ascending");
-    }
-    kept.assign(kept_host, kept_host + n);
-    return 0;
-}
-
-int Sampler::set_solver(int s) {
-    DSH_REQUIRE(s == SOLVER_DDIM || s == SOLVER_DPM2M, "set_solver: unknown solver (0 ddim, 1 dpm2m)");
-    solver = s;
-    return 0;
-}
-
-int Sampler::set_row_seeds(const uint64_t* seeds_host, int n) {
-    DSH_REQUIRE(n >= 0 && (n == 0 || seeds_host), "set_row_seeds: null seed array");
-    DSH_REQUIRE(n == 0 || (n_row_keys > 0 && n == n_row_keys), "set_row_seeds: needs the row keys set first, and one seed per row key");
-    n_row_seeds = 0;
-    if (n == 0) return 0;
-    if (n > cap_row_seeds) { if (int e = grow_device_buffer(row_seeds, cap_row_seeds, (size_t)n, st)) return e; }
-    DSH_HIP_CHECK(hipMemcpyAsync(row_seeds, seeds_host, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    DSH_HIP_CHECK(hipStreamSynchronize(st));       // seeds_host is pageable caller memory
-    n_row_seeds = n;
+// a run's row keys / row seeds on the device: uploaded (and waited for: `host` is the caller's) unless the buffer holds exactly these values
+int Sampler::upload_rows(const std::vector<uint64_t>& host, uint64_t*& dev, int& cap, std::vector<uint64_t>& held) {
+    if (host == held) return 0;
+    held.clear();
+    if ((int)host.size() > cap) { if (int e = grow_device_buffer(dev, cap, host.size(), st)) return e; }
+    DSH_HIP_CHECK(hipMemcpyAsync(dev, host.data(), host.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    DSH_HIP_CHECK(hipStreamSynchronize(st));
+    held = host;
     return 0;
 }
 
@@ -363,29 +372,29 @@ int Sampler::ensure(size_t n, int B, bool want_hist) {
     return scalars(bufs[1]);
 }
 
-// what run() needs beside its arguments: the schedule, the coefficient tables, the buffers, the noise addressing, the saved noisy tails
-int Sampler::prepare(Run& r) {
+// what run() needs beside its spec: the coefficient tables, the buffers, the noise addressing, the saved noisy tails
+int Sampler::prepare(Run& r, const RunSpec& s) {
     const SamplerOpts& o = r.o;
     const int B = r.B; const size_t n = r.n;
+    const bool reverse = s.invert_to > 0;
     std::string err;
-    if (plan_steps(o, r.masked, r.start, r.invert_to, r.steps, err, r.invert_from, &kept)) { set_last_error(err); return -1; }
-    const int64_t need = r.invert_to > 0 ? 0 : sampler_num_draws(o, r.masked, r.init, r.start, &kept);
-    if (o.noise_mode == 0 && r.invert_to == 0) DSH_REQUIRE(r.noise_stack != nullptr && r.n_draws >= need, "noise stack shorter than the loop's draw count");
     // tables are cached per (steps, respacing, subset)
     const int resp = o.kind == 1 ? 0 : o.respacing;
-    if (tb_steps != o.diffusion_steps || tb_resp != resp || tb_kept != kept) {
+    if (tb_steps != o.diffusion_steps || tb_resp != resp || tb_kept != s.kept) {
         tb_steps = tb_resp = -1;
-        if (kept.empty() ? make_tables(o.diffusion_steps, resp, tb, err) : make_tables_kept(o.diffusion_steps, kept, tb, err)) { set_last_error(err); return -1; }
-        tb_steps = o.diffusion_steps; tb_resp = resp; tb_kept = kept;
+        if (s.kept.empty() ? make_tables(o.diffusion_steps, resp, tb, err) : make_tables_kept(o.diffusion_steps, s.kept, tb, err)) { set_last_error(err); return -1; }
+        tb_steps = o.diffusion_steps; tb_resp = resp; tb_kept = s.kept;
     }
-    r.dpm = solver == SOLVER_DPM2M && r.invert_to == 0;
+    r.dpm = s.solver == SOLVER_DPM2M && !reverse;
     if (int e = ensure(n, B, r.dpm)) return e;
     if (o.kind == 0 && o.eta != 0.f && o.noise_mode == 1 && cap_eta < n) { if (int e = grow_device_buffer(bufs[0].nz_eta, cap_eta, n, st)) return e; }
-    // (the reverse loop draws nothing: whatever keys an earlier call left in the context do not concern it)
-    DSH_REQUIRE(r.invert_to > 0 || n_row_keys == 0 || o.noise_mode != 1 || (n_row_keys == B && (n / B) % 4 == 0),
-                "row keys were set for a different batch size (or frames*channels is not a multiple of 4)");
-    r.per_row = r.invert_to == 0 && o.noise_mode == 1 && n_row_keys == B;
-    r.seeds_d = (r.per_row && n_row_seeds == B) ? row_seeds : nullptr;      // (set_row_seeds: always the row keys' count)
+    // (the reverse loop draws nothing: row keys do not concern it; check_run(): one key per batch row, one seed per key)
+    r.per_row = !reverse && o.noise_mode == 1 && !s.row_keys.empty();
+    if (r.per_row) { if (int e = upload_rows(s.row_keys, row_keys, cap_row_keys, row_keys_held)) return e; }
+    if (r.per_row && !s.row_seeds.empty()) {
+        if (int e = upload_rows(s.row_seeds, row_seeds, cap_row_seeds, row_seeds_held)) return e;
+        r.seeds_d = row_seeds;
+    }
     r.quads = r.per_row ? (n / B) / 4 : (n + 3) / 4;
     // --same_overlap_noisy state
     r.blc = (size_t)B * o.overlap_len * channels;
@@ -629,16 +638,10 @@ int Sampler::ddim_update(Run& r, const Chain& c, const StepConsts& sc) {
         else if (int e = noise_for(r, sc.idx2, c, c.nz1, &z2)) return e;
         a.mask = r.mask + c.off; a.gt = r.gt + c.off; a.noise2 = z2;
         a.blend = (a.sqrt_1m_ab_prev < 0.2f && o.add_blend) ? 1 : 0;
-        a.tail_blend = (a.blend && tail_blend) ? 1 : 0;
+        a.tail_blend = (a.blend && r.tail_blend) ? 1 : 0;
     }
-    if (sc.second) {
-        Dpm2mStepArgs d;
-        d.x = a.x; d.eps = a.eps; d.x0_prev = hist + c.off; d.c1 = a.c1; d.c2 = a.c2; d.A = sc.sA; d.Bc = sc.sBc; d.G = sc.sG;
-        d.sqrt_ab_prev = a.sqrt_ab_prev; d.sqrt_1m_ab_prev = a.sqrt_1m_ab_prev; d.mask = a.mask; d.gt = a.gt; d.noise2 = a.noise2;
-        d.blend = a.blend; d.tail_blend = a.tail_blend; d.clip = a.clip; d.overlap_len = a.overlap_len; d.frames = a.frames; d.channels = a.channels;
-        d.n = a.n; d.c_lo = a.c_lo; d.c_hi = a.c_hi;
-        return launch_dpm2m_step(d, c.s);                            // (no saved noisy tails under this solver: run_schedule())
-    }
+    // (a second-order step reads the history it rewrites; no eta draw and no saved noisy tails under that solver: check_run())
+    a.second = sc.second ? 1 : 0; a.A = sc.sA; a.Bc = sc.sBc; a.G = sc.sG;
     if (int e = launch_ddim_step(a, c.s)) return e;
     if (r.son) DSH_HIP_CHECK(hipMemcpyAsync(tails + (size_t)k * r.blc + toff, tail_tmp + toff, (size_t)c.nb * o.overlap_len * channels * sizeof(float),
                                            hipMemcpyDeviceToDevice, c.s));
@@ -657,7 +660,7 @@ int Sampler::ddpm_update(Run& r, const Chain& c, const StepConsts& sc) {
 
 // one chain's share of a step: its columns of its rows, on its stream (every chain draws the same values: the noise depends on the position only)
 int Sampler::update(Run& r, const Chain& c, const StepConsts& sc) {
-    if (sc.kind == STEP_DDIM || sc.kind == STEP_REVERSE) return ddim_update(r, c, sc);      // (reverse: run_schedule() admits no mask, eta, tails)
+    if (sc.kind == STEP_DDIM || sc.kind == STEP_REVERSE) return ddim_update(r, c, sc);      // (reverse: check_run() admits no mask, eta, tails)
     if (sc.kind == STEP_DDPM) return ddpm_update(r, c, sc);
     const float* z;
     if (int e = noise_for(r, sc.idx, c, c.nz1, &z)) return e;
@@ -744,62 +747,30 @@ int Sampler::finish(Run& r, int rc) {
     return rc;
 }
 
-int Sampler::run(DenoiserContext* den, const SamplerOpts& o, float* x, int init, const float* gt,
-                 const uint8_t* mask, bool masked, const float* noise_stack, int64_t n_draws, float* trace) {
-    return run_schedule(den, o, x, init, gt, mask, masked, noise_stack, n_draws, trace, start_level, 0, 0);
-}
-
-int Sampler::invert(DenoiserContext* den, const SamplerOpts& o, float* x, int from_level, int to_level, float* trace) {
-    DSH_REQUIRE(to_level >= 1 && from_level >= 0 && from_level < to_level, "invert: needs 0 <= from_level < to_level");
-    DSH_REQUIRE(o.kind == 0 && o.eta == 0.f, "invert: the reverse ODE exists for the DDIM loops at eta = 0 only");
-    DSH_REQUIRE(!o.same_overlap_noisy && !tail_blend && start_level == 0, "invert: same_overlap_noisy, the tail blend and a start level do not apply to the reverse loop");
-    return run_schedule(den, o, x, 1, nullptr, nullptr, false, nullptr, 0, trace, 0, to_level, from_level);
-}
-
-int Sampler::run_schedule(DenoiserContext* den, const SamplerOpts& o, float* x, int init, const float* gt, const uint8_t* mask, bool masked,
-                          const float* noise_stack, int64_t n_draws, float* trace, int start, int invert_to, int invert_from) {
+int Sampler::run(DenoiserContext* den, const RunSpec& s) {
     DSH_REQUIRE(den && den->batch() > 0, "set_condition() must precede sample()");
-    DSH_REQUIRE(init >= 0 && init <= 2, "unknown init mode");
-    DSH_REQUIRE(init != 2 || o.kind == 0, "init mode 2 (x holds x0) exists for the DDIM loops only");
-    DSH_REQUIRE(start == 0 || (o.kind == 0 && !o.same_overlap_noisy && !tail_blend),
-                "a start level exists for the DDIM loops only, without same_overlap_noisy and the tail blend");
-    DSH_REQUIRE(x != nullptr, "null sample buffer");
-    DSH_REQUIRE(!masked || (gt && mask), "masked sampling needs gt and mask");
-    DSH_REQUIRE(o.noise_mode == 0 || o.noise_mode == 1, "unknown noise mode");
-    DSH_REQUIRE(!(masked && o.kind == 1), "mask-present DDPM (p_sample_loop_progressive_harmonize) is not supported");
-    DSH_REQUIRE(kept.empty() || o.kind == 0, "a timestep subset exists for the DDIM loops only");
-    DSH_REQUIRE(kept.empty() || (int)kept.size() == o.respacing, "the timestep subset's length differs from opts.respacing");
-    DSH_REQUIRE(kept.empty() || kept.back() < o.diffusion_steps, "timestep subset: entry outside [0, diffusion_steps)");
-    if (solver == SOLVER_DPM2M && invert_to == 0) {
-        DSH_REQUIRE(o.kind == 0, "the dpm2m solver exists for the DDIM loops only");
-        DSH_REQUIRE(o.eta == 0.f, "the dpm2m solver is deterministic: eta must be 0");
-        DSH_REQUIRE(!o.same_overlap_noisy, "the dpm2m solver does not keep the saved noisy tails of same_overlap_noisy");
-    }
-    DSH_REQUIRE(!(tail_blend && o.same_overlap_noisy), "tail_blend with same_overlap_noisy: the saved noisy tails describe a window chain, not a window pinned at both ends");
-    DSH_REQUIRE(!tail_blend || (o.overlap_len >= 0 && 2 * (int64_t)o.overlap_len <= den->frames()), "tail_blend: the head and the tail fade overlap (2 * overlap_len > frames)");
-    Run r{den, o, x, init, gt, mask, masked, noise_stack, n_draws, trace, start, invert_from, invert_to};
-    const int B = r.B = den->batch();
+    const SamplerOpts& o = s.o;
+    const bool reverse = s.invert_to > 0;
+    // every refusal, and the schedule, before anything changes in the context or on the device
+    const RunShape shape{den->batch(), den->frames(), channels, den->gesture_channels(), den->modality(), den->lengths_host()};
+    std::string err;
+    Run r{den, o, s.x, reverse ? 1 : s.init, s.gt, s.mask, s.masked, s.noise_stack, s.trace, s.tail_blend};
+    if (check_run(s, &shape, err) || plan_steps(s, r.steps, err)) { set_last_error(err); return -1; }
+    DSH_REQUIRE(o.noise_mode != 0 || reverse || (s.noise_stack != nullptr && s.n_draws >= count_draws(s, r.steps)), "noise stack shorter than the loop's draw count");
+    const int B = r.B = shape.batch;
     // One modality alone (denoiser.h, set_modality): the loop advances the active encoder's column window [w_lo, w_hi) only — every step launch
     // of every regime takes it — and its result holds 0 (expression mode) or the given track (gesture mode) in the other columns.  Noise
     // addressing stays that of the full-width row, so an active column receives the value it receives in the joint run.
-    const int mod = r.mod = den->modality(), gcols = r.gcols = den->gesture_channels();
-    DSH_REQUIRE(mod == 0 || (gcols > 0 && gcols < channels), "a partial modality needs the UniDiffuser's two encoders");
-    DSH_REQUIRE(mod == 0 || !o.same_overlap_noisy, "same_overlap_noisy with a partial modality: the saved noisy tails describe all channels");
+    const int mod = r.mod = shape.modality, gcols = r.gcols = shape.gesture_cols;
     r.w_lo = mod == 1 ? gcols : 0; r.w_hi = mod == 0 ? 0 : (mod == 1 ? channels : gcols);      // (0, 0: all columns)
-    // ragged batch (set_condition_ragged): per-clip frame counts of the padded batch, host and device copies owned by the context
-    const int32_t* len_h = den->lengths_host();
-    r.len_d = den->lengths_dev();
-    // (both address the last overlap_len frames of the PADDED window, which a short clip does not reach)
-    DSH_REQUIRE(!len_h || (!o.same_overlap_noisy && !tail_blend), "per-clip lengths cannot be combined with same_overlap_noisy or the tail blend");
-    if (len_h && o.noise_mode == 1 && n_row_keys == B && invert_to == 0)
-        for (int b = 0; b < B; ++b) DSH_REQUIRE(((int64_t)len_h[b] * channels) % 4 == 0, "row keys on a ragged batch: length * channels must be a multiple of 4 for every clip");
+    r.len_d = den->lengths_dev();           // ragged batch (set_condition_ragged): per-clip frame counts of the padded batch, owned by the context
     // loop_begin() marks the batch as deliberately unsplit; the mark is taken back on EVERY way out of this function (an argument error or a
     // failed launch below must not leave the context answering later evaluations as if a loop were still running)
     struct LoopScope { DenoiserContext* d; ~LoopScope() { (void)d->loop_end(); } } loop_scope{den};
     if (int e = den->loop_begin(o.kind)) return e;          // (may re-condition a mid-size batch as one batch: the two encoder chains replace the sub-batch streams)
     den->t_uniform = emb_dedup_enabled();   // every evaluation of a sampling loop runs the whole batch at ONE timestep (launch_fill_step)
     r.n = (size_t)B * den->frames() * channels; r.row_n = r.n / B;
-    if (int e = prepare(r)) return e;
+    if (int e = prepare(r, s)) return e;
     if (int e = make_chains(r)) return e;
     const LoopPlan p = plan(r);
     // from the fork to the joins: loop() reports an error by returning, finish() joins the chains into the context stream whatever it returned

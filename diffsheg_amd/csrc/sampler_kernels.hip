@@ -28,6 +28,46 @@ __device__ __forceinline__ float linspace01(int L, int k) {
     return (k < L / 2) ? rn_mul(step, (float)k) : fmaf(-step, (float)(L - 1 - k), 1.0f);
 }
 
+// What follows the update proper in both forms of the step: the RePaint select with its cross-fades on element i of the updated sample s,
+// the store to x, and the saved noisy tail.
+__device__ __forceinline__ void repaint_and_store(const DdimStepArgs& a, size_t i, int tc, float s) {
+    const int t = (a.mask || a.tail_out) ? (int)((i % (size_t)tc) / (size_t)a.channels) : 0;
+    if (a.mask) {
+        // --same_overlap_noisy (gaussian_diffusion.py:1040-1042): the out-painted frames take the previous window's saved
+        // NOISY tail of this level instead of a freshly noised copy of its final tail (no Gaussian draw in that branch)
+        float g;
+        if (a.tail_in) {
+            const size_t b = i / (size_t)tc;
+            const int c = (int)(i % (size_t)a.channels);
+            g = t < a.overlap_len ? a.tail_in[(b * a.overlap_len + t) * a.channels + c] : a.gt[i];
+        } else g = rn_add(rn_mul(a.sqrt_ab_prev, a.gt[i]), rn_mul(a.sqrt_1m_ab_prev, a.noise2[i]));
+        if (a.blend) {
+            const int L = a.overlap_len;
+            if (t < L) {
+                const float w = linspace01(L, t);
+                g = rn_add(rn_mul(g, rn_sub(1.0f, w)), rn_mul(s, w));
+            } else if (a.tail_blend && t >= a.frames - L) {
+                // mirrored fade of a window pinned at both ends: the head's weights in reverse order (the same fp32 values),
+                // w'[j] = linspace(0, 1, L)[L - 1 - j], j = t - (frames - L); disjoint from the head's frames (2 L <= frames)
+                const float w = linspace01(L, L - 1 - (t - (a.frames - L)));
+                g = rn_add(rn_mul(g, rn_sub(1.0f, w)), rn_mul(s, w));
+            }
+        }
+        s = a.mask[i] ? g : s;
+    }
+    a.x[i] = s;
+    if (a.tail_out && t >= a.frames - a.overlap_len) {          // saved_noisy_tail[t] = x[..., -L:, :]  (:1058-1060)
+        const size_t b = i / (size_t)tc;
+        const int c = (int)(i % (size_t)a.channels);
+        a.tail_out[(b * a.overlap_len + (t - (a.frames - a.overlap_len))) * a.channels + c] = s;
+    }
+}
+
+// SECOND: DPM-Solver++(2M), data prediction, at eta = 0 (Lu et al. 2022, algorithm 2): the second-order multistep update
+//   x0 = c1 x - c2 eps;  D = x0 + G (x0 - x0_prev);  x <- A x + Bc D
+// with A = sigma_prev / sigma, Bc = -alpha_prev expm1(-h), G = h / (2 h_before) from the host (sampler.hip, solver_coeffs).  x0_prev
+// (in x0_out) is read and rewritten by the thread that owns the element.
+template <bool SECOND>
 __global__ void ddim_step_kernel(DdimStepArgs a) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const int tc = a.frames * a.channels;
@@ -39,40 +79,18 @@ __global__ void ddim_step_kernel(DdimStepArgs a) {
         const float c1x = rn_mul(a.c1, x);
         float x0 = rn_sub(c1x, rn_mul(a.c2, e));
         if (a.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-        const float e2 = __fdiv_rn(rn_sub(c1x, x0), a.c2);
-        float s = rn_add(rn_mul(x0, a.sqrt_ab_prev), rn_mul(a.coef_eps, e2));
-        if (a.noise1) s = rn_add(s, rn_mul(a.sigma, a.noise1[i]));
-        if (a.x0_out) a.x0_out[i] = x0;
-        const int t = (int)((i % (size_t)tc) / (size_t)a.channels);
-        if (a.mask) {
-            // --same_overlap_noisy (gaussian_diffusion.py:1040-1042): the out-painted frames take the previous window's saved
-            // NOISY tail of this level instead of a freshly noised copy of its final tail (no Gaussian draw in that branch)
-            float g;
-            if (a.tail_in) {
-                const size_t b = i / (size_t)tc;
-                const int c = (int)(i % (size_t)a.channels);
-                g = t < a.overlap_len ? a.tail_in[(b * a.overlap_len + t) * a.channels + c] : a.gt[i];
-            } else g = rn_add(rn_mul(a.sqrt_ab_prev, a.gt[i]), rn_mul(a.sqrt_1m_ab_prev, a.noise2[i]));
-            if (a.blend) {
-                const int L = a.overlap_len;
-                if (t < L) {
-                    const float w = linspace01(L, t);
-                    g = rn_add(rn_mul(g, rn_sub(1.0f, w)), rn_mul(s, w));
-                } else if (a.tail_blend && t >= a.frames - L) {
-                    // mirrored fade of a window pinned at both ends: the head's weights in reverse order (the same fp32 values),
-                    // w'[j] = linspace(0, 1, L)[L - 1 - j], j = t - (frames - L); disjoint from the head's frames (2 L <= frames)
-                    const float w = linspace01(L, L - 1 - (t - (a.frames - L)));
-                    g = rn_add(rn_mul(g, rn_sub(1.0f, w)), rn_mul(s, w));
-                }
-            }
-            s = a.mask[i] ? g : s;
+        float s;
+        if (SECOND) {
+            const float D = rn_add(x0, rn_mul(a.G, rn_sub(x0, a.x0_out[i])));
+            s = rn_add(rn_mul(a.A, x), rn_mul(a.Bc, D));
+            a.x0_out[i] = x0;
+        } else {
+            const float e2 = __fdiv_rn(rn_sub(c1x, x0), a.c2);
+            s = rn_add(rn_mul(x0, a.sqrt_ab_prev), rn_mul(a.coef_eps, e2));
+            if (a.noise1) s = rn_add(s, rn_mul(a.sigma, a.noise1[i]));
+            if (a.x0_out) a.x0_out[i] = x0;
         }
-        a.x[i] = s;
-        if (a.tail_out && t >= a.frames - a.overlap_len) {          // saved_noisy_tail[t] = x[..., -L:, :]  (:1058-1060)
-            const size_t b = i / (size_t)tc;
-            const int c = (int)(i % (size_t)a.channels);
-            a.tail_out[(b * a.overlap_len + (t - (a.frames - a.overlap_len))) * a.channels + c] = s;
-        }
+        repaint_and_store(a, i, tc, s);
     }
 }
 
@@ -82,51 +100,16 @@ static inline int grid_for(size_t n) {
 }
 
 int launch_ddim_step(const DdimStepArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_for(a.n)), dim3(256), 0, s, a);
-    DSH_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// DPM-Solver++(2M), data prediction, at eta = 0 (Lu et al. 2022, algorithm 2): the second-order multistep update
-//   x0 = c1 x - c2 eps;  D = x0 + G (x0 - x0_prev);  x <- A x + Bc D
-// with A = sigma_prev / sigma, Bc = -alpha_prev expm1(-h), G = h / (2 h_before) from the host (sampler.hip, solver_coeffs), then the RePaint
-// branch of ddim_step_kernel, operation for operation.  x0_prev is read and rewritten by the thread that owns the element.
-__global__ void dpm2m_step_kernel(Dpm2mStepArgs a) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const int tc = a.frames * a.channels;
-    const bool ranged = a.c_hi > a.c_lo;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
-        if (ranged) { const int cc = (int)(i % (size_t)a.channels); if (cc < a.c_lo || cc >= a.c_hi) continue; }
-        const float x = a.x[i];
-        float x0 = rn_sub(rn_mul(a.c1, x), rn_mul(a.c2, a.eps[i]));
-        if (a.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-        const float D = rn_add(x0, rn_mul(a.G, rn_sub(x0, a.x0_prev[i])));
-        float s = rn_add(rn_mul(a.A, x), rn_mul(a.Bc, D));
-        a.x0_prev[i] = x0;
-        if (a.mask) {
-            const int t = (int)((i % (size_t)tc) / (size_t)a.channels);
-            float g = rn_add(rn_mul(a.sqrt_ab_prev, a.gt[i]), rn_mul(a.sqrt_1m_ab_prev, a.noise2[i]));
-            if (a.blend) {
-                const int L = a.overlap_len;
-                if (t < L) {
-                    const float w = linspace01(L, t);
-                    g = rn_add(rn_mul(g, rn_sub(1.0f, w)), rn_mul(s, w));
-                } else if (a.tail_blend && t >= a.frames - L) {
-                    const float w = linspace01(L, L - 1 - (t - (a.frames - L)));
-                    g = rn_add(rn_mul(g, rn_sub(1.0f, w)), rn_mul(s, w));
-                }
-            }
-            s = a.mask[i] ? g : s;
-        }
-        a.x[i] = s;
+    if (a.second) {
+        DSH_REQUIRE(a.x && a.eps && a.x0_out && a.frames > 0 && a.channels > 0, "dpm2m_step: invalid argument");
+        DSH_REQUIRE(!a.noise1 && !a.tail_in && !a.tail_out, "dpm2m_step: no eta draw and no saved noisy tails");
+        DSH_REQUIRE(!a.mask || (a.gt && a.noise2), "dpm2m_step: a mask needs gt and noise2");
+        DSH_REQUIRE(a.c_lo >= 0 && a.c_hi <= a.channels, "dpm2m_step: channel range outside [0, channels]");
+        if (a.n == 0) return 0;
+        hipLaunchKernelGGL(ddim_step_kernel<true>, dim3(grid_for(a.n)), dim3(256), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(ddim_step_kernel<false>, dim3(grid_for(a.n)), dim3(256), 0, s, a);
     }
-}
-int launch_dpm2m_step(const Dpm2mStepArgs& a, hipStream_t s) {
-    DSH_REQUIRE(a.x && a.eps && a.x0_prev && a.frames > 0 && a.channels > 0, "dpm2m_step: invalid argument");
-    DSH_REQUIRE(!a.mask || (a.gt && a.noise2), "dpm2m_step: a mask needs gt and noise2");
-    DSH_REQUIRE(a.c_lo >= 0 && a.c_hi <= a.channels, "dpm2m_step: channel range outside [0, channels]");
-    if (a.n == 0) return 0;
-    hipLaunchKernelGGL(dpm2m_step_kernel, dim3(grid_for(a.n)), dim3(256), 0, s, a);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -16,7 +16,7 @@ Differences a caller can observe, all loud:
     batch row) additionally gives every row its own Philox stream, so that a chain draws the same noise in
     whatever batch / on whatever rank it is sampled (the sharded long-audio path); ``row_seeds`` (with ``row_keys``, one integer
     per batch row) gives every row its own Philox key in place of ``seed``, so rows of one batch may stand at different windows of
-    their chains (``dsh_sample_set_row_seeds``; :class:`diffsheg_amd.streaming.StreamPool`);
+    their chains (``dsh_run_spec.row_seeds``; :class:`diffsheg_amd.streaming.StreamPool`);
   * the guidance scale is ``opt.cond_scale`` as in the reference (ignored for weights without ``classifier_free``), or the
     loops' ``cond_scale=`` keyword (a float, or one value per batch row), which wins over ``opt``; either holds for the call only;
   * ``model_kwargs['length']`` with an entry ``< T`` makes the batch ragged (``UniDiffuser.set_condition(lengths=)``): every row is
@@ -30,8 +30,8 @@ Differences a caller can observe, all loud:
     motion, noised in the loop with draw 0); ``ddim_reverse_sample`` / ``ddim_reverse_sample_loop`` are the DDIM reverse ODE (:1068-1104);
   * few-step sampling: ``space_timesteps`` also takes the reference's section counts and ``'logsnrK'`` (K timesteps uniform in log-SNR),
     ``SpacedDiffusion`` any non-empty subset of the timesteps (a subset that is no 'ddimK' stride travels as a list,
-    ``dsh_sample_set_timesteps``), and ``ddim_sample_loop(..., solver="dpm2m")`` runs the second-order DPM-Solver++(2M) update where a
-    denoise step follows the denoise step one level above it (``dsh_sample_set_solver``); the default is the reference's loop.
+    ``dsh_run_spec.timesteps``), and ``ddim_sample_loop(..., solver="dpm2m")`` runs the second-order DPM-Solver++(2M) update where a
+    denoise step follows the denoise step one level above it (``dsh_run_spec.solver``); the default is the reference's loop.
 """
 from __future__ import annotations
 
@@ -243,8 +243,8 @@ class GaussianDiffusion:
     @staticmethod
     @contextlib.contextmanager
     def _native(model, gs):
-        """The native calls of one loop: on the model's device and stream, under the call's guidance scale (sticky in the context, like the
-        row keys: the model's own setting comes back afterwards)."""
+        """The native calls of one loop: on the model's device and stream, under the call's guidance scale (the one thing that is sticky in the
+        context — it also governs plain evaluations: the model's own setting comes back afterwards)."""
         prev_gs = model.guidance_scale
         set_gs = gs is not None and gs != prev_gs
         if set_gs:
@@ -358,56 +358,30 @@ class GaussianDiffusion:
             GaussianDiffusion._calls += 1
         opts = self._opts(kind, clip_denoised, mode, int(seed), clip_idx, eta, add_blend)
         lib = _lib.lib()
-        kept_arr, nkept = _int_array(self._kept if (self._kept and kind == 0) else [])
-        n_draws = _lib.check(lib.dsh_sample_num_draws_subset(C.byref(opts), int(masked), init, K, kept_arr, nkept), "dsh_sample_num_draws_subset")
-        stack = None
-        if noise_source is not None:
-            stack = torch.empty(n_draws, B * T * Cc, device=dev)
-            for i in range(n_draws):
-                stack[i].copy_(noise_source.randn((B, T, Cc)).reshape(-1), non_blocking=False)
-        trace = None
-        if return_trace:
-            n_steps = _lib.check(lib.dsh_sample_num_steps_subset(C.byref(opts), int(masked), init, K, kept_arr, nkept), "dsh_sample_num_steps_subset")
-            trace = torch.empty(n_steps, B, T, Cc, device=dev)
-        # Philox noise: optional per-row generator keys (a chain's global id), see dsh_sample_set_row_keys
         if row_keys is not None and len(row_keys) != B:
             raise ValueError(f"row_keys needs one key per batch row ({B}), got {len(row_keys)}")
         if row_seeds is not None and (row_keys is None or len(row_seeds) != B):
             raise ValueError(f"row_seeds needs row_keys and one seed per batch row ({B})")
-        nk = 0 if (row_keys is None or noise_source is not None) else B
-        ns = nk if row_seeds is not None else 0
-        sarr = (C.c_uint64 * max(ns, 1))(*([int(k) & 0xFFFFFFFFFFFFFFFF for k in row_seeds] if ns else [0]))
-        karr = (C.c_uint64 * max(nk, 1))(*([int(k) & 0xFFFFFFFFFFFFFFFF for k in row_keys] if nk else [0]))
+        # the whole call in one dsh_run_spec: nothing is set in, or left behind in, the native context.  Philox noise only: per-row generator
+        # keys (a chain's global id) and per-row seeds
+        keyed = row_keys is not None and noise_source is None
+        spec = _lib.run_spec(timesteps=self._kept if (self._kept and kind == 0) else (), row_keys=row_keys if keyed else (),
+                             row_seeds=row_seeds if (keyed and row_seeds is not None) else (), init=init, masked=int(masked), start_level=K,
+                             tail_blend=int(tail_blend), solver=int(solver == "dpm2m"), x=x.data_ptr(),
+                             gt=None if gt is None else gt.data_ptr(), mask=mask.data_ptr() if masked else None)
+        n_draws, n_steps = C.c_int64(), C.c_int64()
+        _lib.check(lib.dsh_sample_count(C.byref(opts), C.byref(spec), C.byref(n_draws), C.byref(n_steps)), "dsh_sample_count")
+        stack = trace = None
+        if noise_source is not None:
+            stack = torch.empty(n_draws.value, B * T * Cc, device=dev)
+            for i in range(n_draws.value):
+                stack[i].copy_(noise_source.randn((B, T, Cc)).reshape(-1), non_blocking=False)
+            spec.noise_stack, spec.n_draws = stack.data_ptr(), n_draws.value
+        if return_trace:
+            trace = torch.empty(n_steps.value, B, T, Cc, device=dev)
+            spec.trace = trace.data_ptr()
         with self._native(model, gs):
-            _lib.check(lib.dsh_sample_set_row_keys(model._h, karr, nk), "dsh_sample_set_row_keys")      # (also drops earlier row seeds)
-            if ns:
-                _lib.check(lib.dsh_sample_set_row_seeds(model._h, sarr, ns), "dsh_sample_set_row_seeds")
-            if tail_blend:
-                _lib.check(lib.dsh_sample_set_tail_blend(model._h, 1), "dsh_sample_set_tail_blend")
-            if K:
-                _lib.check(lib.dsh_sample_set_start_level(model._h, K), "dsh_sample_set_start_level")
-            if nkept:
-                _lib.check(lib.dsh_sample_set_timesteps(model._h, kept_arr, nkept), "dsh_sample_set_timesteps")
-            if solver == "dpm2m":
-                _lib.check(lib.dsh_sample_set_solver(model._h, 1), "dsh_sample_set_solver")
-            try:
-                _lib.check(lib.dsh_sample(model._h, C.byref(opts), x.data_ptr(), int(init),
-                                          None if gt is None else gt.data_ptr(), None if not masked else mask.data_ptr(),
-                                          int(masked), None if stack is None else stack.data_ptr(), n_draws,
-                                          None if trace is None else trace.data_ptr()), "dsh_sample")
-            except Exception:
-                if nk:                                   # the keys are sticky in the native context: do not leak them into the next call
-                    lib.dsh_sample_set_row_keys(model._h, (C.c_uint64 * 1)(0), 0)
-                raise
-            finally:
-                if tail_blend:                           # sticky as well: the next call is the reference's head-only fade again
-                    lib.dsh_sample_set_tail_blend(model._h, 0)
-                if K:
-                    lib.dsh_sample_set_start_level(model._h, 0)
-                if nkept:                                # the subset and the solver are sticky too: the next call is the stride / the DDIM step
-                    lib.dsh_sample_set_timesteps(model._h, kept_arr, 0)
-                if solver == "dpm2m":
-                    lib.dsh_sample_set_solver(model._h, 0)
+            _lib.check(lib.dsh_sample_run(model._h, C.byref(opts), C.byref(spec)), "dsh_sample_run")
         self._keep = (gt, mask, stack)          # consumed asynchronously on the stream
         if son:
             # gaussian_diffusion.py:1155-1157: the loop returns the dict of the last step plus the saved tails.  The tails live
@@ -433,7 +407,7 @@ class GaussianDiffusion:
                          model_kwargs=None, device=None, progress=False, eta=0.0, **kw):
         """gaussian_diffusion.py:1106-1159 (dispatches to the harmonize schedule when a mask is set).  ``tail_blend=True`` (keyword,
         not in the reference) adds the mirrored cross-fade on the last ``overlap_len`` frames, for masks that pin both ends of the
-        window (dsh_sample_set_tail_blend); the default is the reference's loop.
+        window (dsh_run_spec.tail_blend); the default is the reference's loop.
 
         ``start_level=K`` (keyword, ``1 .. K .. respacing``): the loop starts at spaced level ``K - 1`` instead of the top — levels
         ``K-1 .. 0``, or with a mask the RePaint jump schedule walked from ``t_T = K``.  ``noise=`` then is x AT level ``K - 1``;
@@ -442,7 +416,7 @@ class GaussianDiffusion:
 
         ``solver="ddim" | "dpm2m"`` (keyword; default: this object's ``solver`` attribute, ``"ddim"``): ``"dpm2m"`` makes every denoise step
         that directly follows the denoise step one level above it — and is not the last — the second-order DPM-Solver++(2M) update
-        (dsh_sample_set_solver); all other steps, the draws and the noise addressing are the DDIM loop's.  Needs ``eta == 0`` and no
+        (dsh_run_spec.solver); all other steps, the draws and the noise addressing are the DDIM loop's.  Needs ``eta == 0`` and no
         ``same_overlap_noisy``.  Meant for few steps on a ``'logsnrK'`` subset (:func:`space_timesteps`)."""
         if not self._respacing:
             raise NotImplementedError("ddim_sample_loop needs a SpacedDiffusion('ddimK') (trainers use 'ddim25')")
@@ -542,18 +516,15 @@ class GaussianDiffusion:
         dev = model.device
         out = x.to(device=dev, dtype=torch.float32).contiguous().clone()
         opts = self._opts(0, clip_denoised, 1, 0, 0, 0.0)
-        trace = torch.empty(to_level - from_level, B, T, Cc, device=dev) if return_trace else None
-        # (no draws: the row keys an earlier loop left in the native context do not concern the reverse loop, at any batch size)
-        kept_arr, nkept = _int_array(self._kept or [])
+        # (no draws: the reverse loop reads neither the noise fields nor row keys)
+        lib = _lib.lib()
+        spec = _lib.run_spec(timesteps=self._kept or (), invert_from=from_level, invert_to=to_level, x=out.data_ptr())
+        n_steps = C.c_int64()
+        _lib.check(lib.dsh_sample_count(C.byref(opts), C.byref(spec), None, C.byref(n_steps)), "dsh_sample_count")
+        trace = torch.empty(n_steps.value, B, T, Cc, device=dev) if return_trace else None
+        spec.trace = None if trace is None else trace.data_ptr()
         with self._native(model, gs):
-            if nkept:
-                _lib.check(_lib.lib().dsh_sample_set_timesteps(model._h, kept_arr, nkept), "dsh_sample_set_timesteps")
-            try:
-                _lib.check(_lib.lib().dsh_invert_from(model._h, C.byref(opts), out.data_ptr(), from_level, to_level,
-                                                      None if trace is None else trace.data_ptr()), "dsh_invert")
-            finally:
-                if nkept:
-                    _lib.lib().dsh_sample_set_timesteps(model._h, kept_arr, 0)
+            _lib.check(lib.dsh_sample_run(model._h, C.byref(opts), C.byref(spec)), "dsh_sample_run")
         return (out, trace) if return_trace else out
 
     def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0, cond_scale=None):
@@ -569,7 +540,7 @@ class GaussianDiffusion:
     def ddim_reverse_sample_loop(self, model, x, to_level, model_kwargs=None, return_trace=False, clip_denoised=False, eta=0.0,
                                  cond_scale=None):
         """DDIM inversion: ``x [B, T, C]`` (a clean motion) carried through ``ddim_reverse_sample`` at the spaced levels
-        ``0 .. to_level - 1``, natively and in one call (dsh_invert).  No draws.  The result stands at ``alphas_cumprod[to_level]``;
+        ``0 .. to_level - 1``, natively and in one call (dsh_sample_run with invert_to).  No draws.  The result stands at ``alphas_cumprod[to_level]``;
         ``ddim_sample_loop(start_level=K, noise=...)`` enters at ``alphas_cumprod[K - 1]`` (the guided-diffusion pairing of the two
         loops: close to, not exactly, an inverse).  ``return_trace``: also the state after every step ``[to_level, B, T, C]``."""
         return self._invert(model, x, 0, to_level, clip_denoised, None, model_kwargs, eta, return_trace, cond_scale)
@@ -580,7 +551,7 @@ class SpacedDiffusion(GaussianDiffusion):
 
     def __init__(self, use_timesteps, solver: str = "ddim", **kwargs):
         """``use_timesteps``: any non-empty subset of ``range(n)``.  A 'ddimK' stride takes the stride's own native route; any other subset
-        travels as a list (dsh_sample_set_timesteps).  ``solver``: the default update rule of ``ddim_sample_loop``."""
+        travels as a list (dsh_run_spec.timesteps).  ``solver``: the default update rule of ``ddim_sample_loop``."""
         self.use_timesteps = set(int(t) for t in use_timesteps)
         n = len(kwargs["betas"]) if kwargs.get("betas") is not None else int(kwargs.get("num_timesteps", 1000))
         k = len(self.use_timesteps)

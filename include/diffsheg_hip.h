@@ -182,6 +182,45 @@ int dsh_profile_class_info(const dsh_ctx* ctx, int32_t cls, const char** kernel,
 int dsh_debug_copy(dsh_ctx* ctx, const char* what, float* out);
 
 /* ---- boundary 2: full sampling loops ----------------------------------------------------------- */
+/* One loop = one dsh_sampler_opts + one dsh_run_spec.  The spec carries everything a loop needs from its caller beside the options; the
+ * context keeps NONE of it between calls (caches only: a caller that passes the same row keys again pays no second upload), so a call
+ * depends on its arguments, the condition and the guidance scale alone, and a refused call leaves nothing behind.
+ * Set struct_size = sizeof(dsh_run_spec) and zero the rest before filling in: fields are only ever appended, a library newer than the
+ * caller reads the fields the caller does not know as 0 / NULL (their defaults), and a struct_size larger than the library knows is refused.
+ * The fields are described at the compatibility entries below that used to carry them (dsh_sample and the dsh_sample_set_* setters). */
+typedef struct dsh_run_spec {
+    uint32_t struct_size;
+    int32_t init;            /* 0 x_T is drawn, 1 x is given, 2 x holds x0 (dsh_sample: init_from_x)                           */
+    int32_t masked;          /* the caller's `True in outpainting_mask`                                                         */
+    int32_t start_level;     /* 0: the whole schedule; K: the DDIM loops start at spaced level K - 1 (dsh_sample_set_start_level) */
+    int32_t invert_from;     /* the reverse loop (DDIM inversion, dsh_invert_from) over the levels invert_from .. invert_to - 1  */
+    int32_t invert_to;       /* when invert_to > 0: no draws; init, masked, the noise fields, the solver and the row keys unread */
+    float* x;                /* device [B,T,C], in/out                                                                          */
+    const float* gt;         /* device [B,T,C] or NULL                                                                          */
+    const uint8_t* mask;     /* device [B,T,C] or NULL                                                                          */
+    const float* noise_stack;/* device [n_draws, B*T*C] for DSH_NOISE_STACK, else NULL                                          */
+    int64_t n_draws;
+    float* trace;            /* device [n_steps, B*T*C] or NULL                                                                 */
+    const int32_t* timesteps;/* host: the free timestep subset (dsh_sample_set_timesteps); n_timesteps = 0: the 'ddimK' stride */
+    int32_t n_timesteps;
+    int32_t tail_blend;      /* dsh_sample_set_tail_blend                                                                       */
+    const uint64_t* row_keys;  /* host, n_rows entries (dsh_sample_set_row_keys); n_rows = 0: one stream for the whole batch   */
+    const uint64_t* row_seeds; /* host, n_rows entries or NULL (dsh_sample_set_row_seeds)                                      */
+    int32_t n_rows;
+    int32_t solver;          /* DSH_SOLVER_DDIM / DSH_SOLVER_DPM2M (dsh_sample_set_solver)                                      */
+} dsh_run_spec;
+/* Runs the forward loops and the reverse loop.  Asynchronous on the context stream, except that new row keys / seeds are copied to the
+ * device and waited for before the loop is queued (they are caller memory).  -1 before any state changes on everything dsh_sample and
+ * dsh_invert_from refuse, with the same messages.  The sticky values of the dsh_sample_set_* setters are neither read nor changed. */
+int dsh_sample_run(dsh_ctx* ctx, const dsh_sampler_opts* opts, const dsh_run_spec* spec);
+/* Host only: the Gaussian tensors [B,T,C] the loop of (opts, spec) consumes, in the reference's draw order: x_T or the
+ * q_sample noise first (unless init = 1), then per step; and its (denoise + undo) steps, i.e. the rows a trace needs.  Either output may
+ * be NULL.  The pointers to device memory in spec are not read.  -1 on what dsh_sample_run would refuse without seeing a context. */
+int dsh_sample_count(const dsh_sampler_opts* opts, const dsh_run_spec* spec, int64_t* n_draws, int64_t* n_steps);
+
+/* ---- compatibility layer over dsh_sample_run: sticky setters, dsh_sample, dsh_invert, three generations of counting entries ----
+ * Each setter stores its value in one spec-shaped record of the context; dsh_sample / dsh_invert_from complete that record with their
+ * arguments and run it; the counting entries build a spec from theirs.  New code should fill a dsh_run_spec instead. */
 /* Number of Gaussian tensors [B,T,C] the loop consumes, in the reference's draw order
  * (SURVEY §8a S7): x_T first (unless init_from_x), then per step.  Returns < 0 on error. */
 /* (init_from_x here is a flag: any non-zero value counts as "x is given".  For init_from_x = 2 of dsh_sample - one draw more, the

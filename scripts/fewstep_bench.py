@@ -61,11 +61,10 @@ def timed(fn, warmup, steps):
 def evaluations(tr, masked):
     d = tr.diffusion_ddim_val
     o = d._opts(0, False, 1, 0)
-    kept = d._kept or []
-    arr = (C.c_int32 * max(len(kept), 1))(*kept)
-    lib = _lib.lib()
-    steps = lib.dsh_sample_num_steps_subset(C.byref(o), int(masked), 0, 0, arr, len(kept))
-    draws = lib.dsh_sample_num_draws_subset(C.byref(o), int(masked), 0, 0, arr, len(kept))
+    spec = _lib.run_spec(timesteps=d._kept or (), masked=int(masked))
+    steps, draws = C.c_int64(), C.c_int64()
+    _lib.check(_lib.lib().dsh_sample_count(C.byref(o), C.byref(spec), C.byref(draws), C.byref(steps)), "dsh_sample_count")
+    steps, draws = steps.value, draws.value
     return int(steps) if not masked else int(draws - 1 - steps)          # masked: draws = 1 + 2 evaluations + undo steps
 
 

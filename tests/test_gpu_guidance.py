@@ -303,7 +303,7 @@ def test_loop_keyword_wins_over_opt_and_is_restored(monkeypatch):
     at2 = _ddim(model, inp)
     # ... also when the native loop fails
     lib = _lib.lib()
-    monkeypatch.setattr(lib, "dsh_sample", lambda *a: -1)
+    monkeypatch.setattr(lib, "dsh_sample_run", lambda *a: -1)
     with pytest.raises(_lib.DshError):
         _ddim(model, inp, cond_scale=1.15)
     monkeypatch.undo()

@@ -372,8 +372,13 @@ def test_without_row_seeds_nothing_moved(precision):
     assert torch.equal(mixed[0], chain0[0]) and not torch.equal(mixed[1], chain0[1]) and not torch.equal(mixed[2], chain0[2])
     for b in (1, 2):
         assert torch.equal(mixed[b], same[b][b]), (b, rel_err(mixed[b], same[b][b]))
-    # sticky in the context: a raw dsh_sample behind the seeded call still draws from the row seeds ...
+    # the loops above left nothing in the context (each carried its keys and seeds in its own dsh_run_spec) ...
     opts = tr.diffusion_ddim_val._opts(0, False, 1, 1)
+    assert not torch.equal(_raw_sample(model, opts, (B, T, Cc), gt, mask), mixed)
+    # ... the setters are sticky: raw dsh_sample calls behind them draw from the row seeds ...
+    _lib.check(lib.dsh_sample_set_row_keys(model._h, _u64(keys), B))
+    _lib.check(lib.dsh_sample_set_row_seeds(model._h, _u64(seeds), B))
+    assert torch.equal(_raw_sample(model, opts, (B, T, Cc), gt, mask), mixed)
     assert torch.equal(_raw_sample(model, opts, (B, T, Cc), gt, mask), mixed)
     # ... refused changes leave them in place (wrong count; more seeds than keys) ...
     assert lib.dsh_sample_set_row_seeds(model._h, _u64(seeds[:2]), 2) == -1 and b"row key" in lib.dsh_last_error()
