@@ -171,6 +171,8 @@ SYMBOLS = {
     "dsh_fgd_encode": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "dsh_batch_metrics_result_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "dsh_op_batch_metrics": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "dsh_denoise_losses_result_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "dsh_op_denoise_losses": (C.c_int, [_P] * 8 + [C.c_int32] * 4 + [C.c_float, _P, _P, _P]),
     "dsh_mel_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
     "dsh_mel_destroy": (C.c_int, [_P]),
     "dsh_mel_num_frames": (C.c_int64, [_P, C.c_int64]),
@@ -198,6 +200,7 @@ SYMBOLS = {
 }
 
 METRICS_HEADER = 5      # DSH_METRICS_HEADER: 8-byte words in front of the per-group diversity values of dsh_op_batch_metrics
+LOSS_HEADER, LOSS_COLS = 8, 7      # the header's loss macros: batch scalars in front of, and terms per row of, dsh_op_denoise_losses
 
 # index -> name of the entries of dsh_debug_launch_counts (include/diffsheg_hip.h); the last four are values, not counts
 # (indices 4 and 7 are retired: their kernel forms were removed, the counts stay 0; the names keep the indices fixed)

@@ -13,6 +13,7 @@
 #include "audio_front.h"
 #include "fgd.h"
 #include "hubert.h"
+#include "losses.h"
 #include "sampler.h"
 
 namespace dsh {
@@ -1587,6 +1588,17 @@ int dsh_op_batch_metrics(void* hip_stream, const float* outputs, const float* mo
                          int32_t b_div, void* result_dev) {
     API_BEGIN
     return dsh::launch_batch_metrics(outputs, motions, B, T, C, joint_dim, b_div, result_dev, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int64_t dsh_denoise_losses_result_bytes(int32_t B, int32_t T) { return dsh::denoise_losses_result_bytes(B, T); }
+
+int dsh_op_denoise_losses(void* hip_stream, const float* eps, const float* noise, const float* x_t, const float* x0, const float* c1_dev,
+                          const float* c2_dev, const int32_t* lens_dev, int32_t B, int32_t T, int32_t C, int32_t split, float huber_beta,
+                          float* x0_pred_out, float* frame_mse_out, void* result_dev) {
+    API_BEGIN
+    return dsh::launch_denoise_losses(eps, noise, x_t, x0, c1_dev, c2_dev, lens_dev, B, T, C, split, huber_beta, x0_pred_out, frame_mse_out,
+                                      result_dev, reinterpret_cast<hipStream_t>(hip_stream));
     API_END
 }
 

@@ -31,7 +31,10 @@ Differences a caller can observe, all loud:
   * few-step sampling: ``space_timesteps`` also takes the reference's section counts and ``'logsnrK'`` (K timesteps uniform in log-SNR),
     ``SpacedDiffusion`` any non-empty subset of the timesteps (a subset that is no 'ddimK' stride travels as a list,
     ``dsh_run_spec.timesteps``), and ``ddim_sample_loop(..., solver="dpm2m")`` runs the second-order DPM-Solver++(2M) update where a
-    denoise step follows the denoise step one level above it (``dsh_run_spec.solver``); the default is the reference's loop.
+    denoise step follows the denoise step one level above it (``dsh_run_spec.solver``); the default is the reference's loop;
+  * the eval-mode forward losses: ``training_losses`` (gaussian_diffusion.py:1319-1426, epsilon / MSE branch) noises ``x_start``, evaluates the
+    model once and reduces the loss terms on the device (``dsh_op_denoise_losses``); ``target_vel`` / ``pred_vel`` are not materialised, ``loss_type``
+    KL / RESCALED_KL, a single modality and ``pre_seq`` are refused; ``UniformSampler`` / ``create_named_schedule_sampler`` (:21-76) draw timesteps.
 """
 from __future__ import annotations
 
@@ -63,6 +66,87 @@ class ModelVarType(enum.Enum):
     FIXED_SMALL = enum.auto()
     FIXED_LARGE = enum.auto()
     LEARNED_RANGE = enum.auto()
+
+
+class LossType(enum.Enum):
+    MSE = enum.auto()
+    RESCALED_MSE = enum.auto()
+    KL = enum.auto()
+    RESCALED_KL = enum.auto()
+
+    def is_vb(self):
+        return self in (LossType.KL, LossType.RESCALED_KL)
+
+
+class UniformSampler:
+    """gaussian_diffusion.py:35-76: every timestep of ``diffusion`` with the same probability, all weights 1.  Host-side."""
+
+    def __init__(self, diffusion):
+        self.diffusion = diffusion
+        self._weights = np.ones([diffusion.num_timesteps])
+
+    def weights(self):
+        return self._weights
+
+    def sample(self, batch_size: int, device, generator=None):
+        """``(timesteps, weights)`` for a batch (:52-67): int64 indices in ``0 .. num_timesteps - 1`` and float32 weights, on ``device``.
+        ``generator``: a ``numpy.random.Generator`` / ``RandomState`` (two samplers given equally seeded generators draw the same
+        timesteps), or ``None`` for numpy's global state, which is what the reference draws from."""
+        w = self.weights()
+        p = w / np.sum(w)
+        rng = np.random if generator is None else generator
+        indices_np = rng.choice(len(p), size=(int(batch_size),), p=p)
+        indices = torch.from_numpy(np.asarray(indices_np, dtype=np.int64)).to(device)
+        weights = torch.from_numpy(1 / (len(p) * p[indices_np])).float().to(device)
+        return indices, weights
+
+
+def create_named_schedule_sampler(name: str, diffusion):
+    """gaussian_diffusion.py:21-32; only "uniform" is built (the loss-aware resampler belongs to a training run)."""
+    if name == "uniform":
+        return UniformSampler(diffusion)
+    raise NotImplementedError(f"unknown schedule sampler: {name}")
+
+
+def _upload(t: torch.Tensor, device) -> torch.Tensor:
+    """A small host tensor to the device without blocking the host: through pinned memory, asynchronously on the current stream."""
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def denoise_losses(eps, noise, x_t, x0, c1, c2, split: int, lens_dev=None, huber_beta: float = 0.1, want_x0_pred: bool = True,
+                   want_frame_mse: bool = True) -> dict:
+    """``dsh_op_denoise_losses`` on the current stream: ``eps`` / ``noise`` / ``x_t`` / ``x0`` ``[B, T, C]`` and ``c1`` / ``c2`` ``[B]``, contiguous
+    fp32 on one GPU; ``lens_dev`` an int32 device tensor ``[B]`` or ``None``.  Returns ``{"scalars" [4] fp64 (loss_model_pred, loss_vel_rec,
+    loss_x0_rec, final_loss), "counts" [3] fp64 (valid frames, frame pairs, elements), "row_terms" [B, LOSS_COLS] fp64, "pred_x0", "frame_mse"}``
+    (the last two ``None`` when not asked for); views of one result buffer.  Two launches, no synchronisation."""
+    if not eps.is_cuda:
+        raise _lib.DshError("denoise_losses runs on the GPU (no CPU fallback)")
+    B, T, Cc = (int(v) for v in eps.shape)
+    for name, v in (("eps", eps), ("noise", noise), ("x_t", x_t), ("x0", x0)):
+        if tuple(v.shape) != (B, T, Cc) or v.dtype != torch.float32 or not v.is_contiguous() or v.device != eps.device:
+            raise ValueError(f"denoise_losses: {name} must be a contiguous fp32 [B, T, C] = {(B, T, Cc)} tensor on {eps.device}")
+    for name, v in (("c1", c1), ("c2", c2)):
+        if tuple(v.shape) != (B,) or v.dtype != torch.float32 or not v.is_contiguous() or v.device != eps.device:
+            raise ValueError(f"denoise_losses: {name} must be a contiguous fp32 [B] tensor on {eps.device}")
+    if lens_dev is not None and (tuple(lens_dev.shape) != (B,) or lens_dev.dtype != torch.int32 or lens_dev.device != eps.device):
+        raise ValueError("denoise_losses: lens_dev must be an int32 [B] tensor on the tensors' device")
+    L = _lib.lib()
+    dev = eps.device
+    nbytes = _lib.check(int(L.dsh_denoise_losses_result_bytes(B, T)), "dsh_denoise_losses_result_bytes")
+    res = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    x0p = torch.empty_like(eps) if want_x0_pred else None
+    fm = torch.empty(B, T, dtype=torch.float32, device=dev) if want_frame_mse else None
+    with torch.cuda.device(dev):
+        rc = L.dsh_op_denoise_losses(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), eps.data_ptr(), noise.data_ptr(), x_t.data_ptr(),
+                                     x0.data_ptr(), c1.data_ptr(), c2.data_ptr(), None if lens_dev is None else lens_dev.data_ptr(), B, T, Cc,
+                                     int(split), float(huber_beta), None if x0p is None else x0p.data_ptr(),
+                                     None if fm is None else fm.data_ptr(), res.data_ptr())
+    _lib.check(rc, "dsh_op_denoise_losses")
+    H, K = _lib.LOSS_HEADER, _lib.LOSS_COLS
+    return {"scalars": res[:4], "counts": res[4:7], "row_terms": res[H:H + B * K].view(B, K), "pred_x0": x0p, "frame_mse": fm}
+
+
+LOSS_SCALARS = ("loss_model_pred", "loss_vel_rec", "loss_x0_rec", "final_loss")
 
 
 def get_named_beta_schedule(schedule_name: str, num_diffusion_timesteps: int) -> np.ndarray:
@@ -444,7 +528,7 @@ class GaussianDiffusion:
         ac = self.alphas_cumprod[np.asarray(ts, dtype=np.int64)]
         return (torch.from_numpy(np.sqrt(ac).astype(np.float32)), torch.from_numpy(np.sqrt(1.0 - ac).astype(np.float32)))
 
-    def q_sample(self, x_start, t, noise=None, *, seed=None, row_keys=None, row_seeds=None, lengths=None):
+    def q_sample(self, x_start, t, noise=None, *, seed=None, row_keys=None, row_seeds=None, lengths=None, _coef_dev=None):
         """gaussian_diffusion.py:417-462 on the device: ``sqrt(ac[t]) x_start + sqrt(1 - ac[t]) noise``, ``x_start [B, T, C]`` on a GPU,
         ``t`` an int or one index of THIS diffusion's (spaced) tables per row.  ``noise`` given: used as it is.  Otherwise it is drawn in
         the same pass from the Philox streams a sampling loop with the same ``seed`` / ``row_keys`` / ``row_seeds`` / ``lengths`` takes its
@@ -456,7 +540,8 @@ class GaussianDiffusion:
         if not x_start.is_cuda:
             raise _lib.DshError("q_sample runs on the GPU (no CPU fallback)")
         B, T, Cc = (int(v) for v in x_start.shape)
-        a, s = self.q_sample_coefficients(t, B)
+        if _coef_dev is None:
+            a, s = self.q_sample_coefficients(t, B)
         if noise is not None and tuple(noise.shape) != (B, T, Cc):
             raise ValueError(f"noise {tuple(noise.shape)} does not match x_start {(B, T, Cc)}")
         lens = normalize_lengths(lengths, B, T) if lengths is not None else None
@@ -472,7 +557,7 @@ class GaussianDiffusion:
         x0 = x_start.to(torch.float32).contiguous()
         out = torch.empty_like(x0)
         nz = None if noise is None else noise.to(device=dev, dtype=torch.float32).contiguous()
-        a_d, s_d = a.to(dev), s.to(dev)
+        a_d, s_d = _coef_dev if _coef_dev is not None else (a.to(dev), s.to(dev))      # (training_losses hands in the device copies it made)
         if seed is None and noise is None:
             seed = int(torch.initial_seed()) + GaussianDiffusion._calls
             GaussianDiffusion._calls += 1
@@ -487,6 +572,124 @@ class GaussianDiffusion:
                                             None if nz is None else nz.data_ptr(), a_d.data_ptr(), s_d.data_ptr(), B, T, Cc, 0, 0, fixed_from,
                                             int(seed or 0) & M, 0, karr, None if sd is None else sd.data_ptr(), larr, 0)
         _lib.check(rc, "dsh_op_q_sample")
+        return out
+
+    # ---- the eval-mode forward losses ----------------------------------------------------------
+    def _row_values(self, table: np.ndarray, ts: List[int], B: int, dev, dtype=torch.float32) -> torch.Tensor:
+        """``table[t_b]`` per row on the device, rounded once to ``dtype`` like the reference's ``_extract_into_tensor``.  One timestep for
+        the whole batch is a fill launch; different ones go through pinned memory.  Neither blocks the host."""
+        vals = np.asarray(table)[np.asarray(ts, dtype=np.int64)]
+        if len(set(ts)) == 1:
+            return torch.full((B,), vals[0].item(), dtype=dtype, device=dev)
+        return _upload(torch.from_numpy(np.ascontiguousarray(vals)).to(dtype), dev)
+
+    def _draw_noise(self, B: int, T: int, Cc: int, dev, seed: int, row_keys, row_seeds, lens) -> torch.Tensor:
+        """The noise ``q_sample(x_start, t, seed=, row_keys=, row_seeds=, lengths=)`` would draw inside its pass, as a tensor: the values of
+        ``dsh_op_philox_randn`` at offset 0, or with ``row_keys`` those of the row ops at draw 0 (which wait for the stream once: they
+        upload the keys).  Padded frames of a ragged row are 0."""
+        M = 0xFFFFFFFFFFFFFFFF
+        lib = _lib.lib()
+        buf = torch.empty(B, T, Cc, device=dev) if lens is None else torch.zeros(B, T, Cc, device=dev)
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            if row_keys is None:
+                rc = lib.dsh_op_philox_randn(stream, buf.data_ptr(), B * T * Cc, int(seed) & M, 0)
+                what = "dsh_op_philox_randn"
+            else:
+                karr = (C.c_uint64 * B)(*[int(k) & M for k in row_keys])
+                sd = None
+                if row_seeds is not None:
+                    sd = _upload(torch.tensor([(int(k) & M) - (1 << 64) if (int(k) & M) >> 63 else int(k) & M for k in row_seeds],
+                                              dtype=torch.int64), dev)
+                larr = None if lens is None else (C.c_int32 * B)(*lens)
+                rc = lib.dsh_op_philox_randn_rows_ragged_seeded(stream, buf.data_ptr(), B, T * Cc, int(seed) & M, 0, karr, larr, 0, Cc,
+                                                                None if sd is None else sd.data_ptr())
+                what = "dsh_op_philox_randn_rows_ragged_seeded"
+        _lib.check(rc, what)
+        return buf
+
+    def training_losses(self, model, x_start, t, model_kwargs=None, noise=None, *, seed=None, row_keys=None, row_seeds=None, cond_scale=None):
+        """gaussian_diffusion.py:1319-1426, epsilon / MSE branch, in the reference's eval mode (no conditioning dropout, no gradient):
+        ``x_t = q_sample(x_start, t, noise)``, one evaluation ``eps = model(x_t, timestep_map[t], ...)``, and the loss terms reduced on the
+        device (``dsh_op_denoise_losses``).  ``x_start [B, T, C]`` on the GPU; ``t`` an int or one index per row into THIS diffusion's
+        tables.  ``noise`` given: used as it is; else drawn from the Philox streams ``q_sample(..., seed=, row_keys=, row_seeds=)`` draws from,
+        into a buffer (the same bits).  ``model_kwargs`` as for the sampling loops (``audio_emb``, ``person_id``, ``add_cond``, ``length``,
+        ``pe_type``; ``y`` is accepted and unused: the reference's masking at :1394-1400 is commented out); ``length`` entries ``< T`` make
+        the batch ragged under q_sample's rules (Philox noise then needs ``row_keys``): row ``b`` is scored as the clip alone at its
+        length.  ``cond_scale`` as for the loops: with a scale other than 1 the guided eps is scored (transformer.py:537, :585),
+        ``cond_scale=1.0`` scores the conditional model.
+
+        Returns the reference's keys where they cost nothing — ``"mse" [B]`` (``mean_flat`` of ``(noise - eps)^2`` over the row's own
+        frames, fp64), ``"target"`` (the noise), ``"pred"`` (eps), ``"target_x0"`` (``x_start`` itself), ``"pred_x0"`` — plus ``"x_t"``,
+        ``"row_terms" [B, 7]`` fp64 (include/diffsheg_hip.h), ``"frame_mse" [B, T]`` and ``"scalars"``: 0-d fp64 device tensors
+        ``loss_model_pred`` / ``loss_vel_rec`` / ``loss_x0_rec`` / ``final_loss`` in backward_G's formulas (``loss_vel_rec`` and
+        ``final_loss`` are left out when no row has two frames).  ``target_vel`` / ``pred_vel`` are not materialised: the velocity loss is
+        row term 3.  Nothing synchronises (but the row ops behind ``row_keys``) and nothing is copied to the host."""
+        # ---- refusals: before any device call ----
+        if not isinstance(model, UniDiffuser):
+            raise TypeError("model must be a diffsheg_amd.model.UniDiffuser (no generic-callable / CPU fallback)")
+        lt = self.loss_type
+        if (isinstance(lt, LossType) and lt.is_vb()) or (isinstance(lt, str) and lt.lower() in ("kl", "rescaled_kl")):
+            raise NotImplementedError(f"loss_type {lt}: the variational-bound losses are not built (FIXED_SMALL variance: only the MSE branch)")
+        if lt is not None and not isinstance(lt, LossType) and not (isinstance(lt, str) and lt.lower() in ("mse", "rescaled_mse")):
+            raise NotImplementedError(f"unknown loss_type {lt!r}")
+        model_kwargs = dict(model_kwargs or {})
+        if model_kwargs.get("pre_seq") is not None:
+            raise NotImplementedError("pre_seq is not on the accelerated path")
+        if not isinstance(x_start, torch.Tensor) or x_start.dim() != 3:
+            raise ValueError("training_losses takes x_start [B, T, C]")
+        B, T, Cc = (int(v) for v in x_start.shape)
+        if normalize_modality(model_kwargs.get("modality", "both"), model_kwargs.get("expression"), B, T, model.cfg.expression_dim,
+                              model.cfg.unidiffuser) != 0:
+            raise NotImplementedError("training_losses scores both modalities: the objective is defined on all channels")
+        if not x_start.is_cuda:
+            raise _lib.DshError("training_losses runs on the GPU (no CPU fallback)")
+        ts = [int(t)] * B if isinstance(t, numbers.Integral) else [int(v) for v in (t.tolist() if isinstance(t, torch.Tensor) else t)]
+        if len(ts) != B or any(v < 0 or v >= self.num_timesteps for v in ts):
+            raise ValueError(f"t needs one index in 0 .. {self.num_timesteps - 1} (or one per batch row, {B}), got {ts}")
+        if noise is not None and tuple(noise.shape) != (B, T, Cc):
+            raise ValueError(f"noise {tuple(noise.shape)} does not match x_start {(B, T, Cc)}")
+        lens = normalize_lengths(model_kwargs.get("length"), B, T)
+        if row_keys is not None and len(row_keys) != B:
+            raise ValueError(f"row_keys needs one key per batch row ({B}), got {len(row_keys)}")
+        if row_seeds is not None and (row_keys is None or len(row_seeds) != B):
+            raise ValueError(f"row_seeds needs row_keys and one seed per batch row ({B})")
+        if noise is None and row_keys is None and lens is not None:
+            raise ValueError("lengths with Philox noise need row_keys (a ragged row draws from its own stream)")
+        if noise is None and row_keys is not None and ((T * Cc) % 4 or any((v * Cc) % 4 for v in (lens or []))):
+            raise ValueError("row_keys: frames * channels (and length * channels of every row) must be a multiple of 4")
+        split = int(getattr(self.opt, "split_pos", model.cfg.split_pos))
+        beta = float(getattr(self.opt, "huber_beta", 0.1))
+        if not 0 < split < Cc:
+            raise ValueError(f"split_pos = {split} must lie inside (0, {Cc})")
+        gs = self._guidance(model, cond_scale, B)
+        # ---- device work ----
+        dev = model.device
+        x0 = x_start.to(device=dev, dtype=torch.float32).contiguous()
+        if noise is None:
+            if seed is None:
+                seed = int(torch.initial_seed()) + GaussianDiffusion._calls
+                GaussianDiffusion._calls += 1
+            nz = self._draw_noise(B, T, Cc, dev, seed, row_keys, row_seeds, lens)
+        else:
+            nz = noise.to(device=dev, dtype=torch.float32).contiguous()
+        a_d = self._row_values(np.sqrt(self.alphas_cumprod), ts, B, dev)
+        s_d = self._row_values(np.sqrt(1.0 - self.alphas_cumprod), ts, B, dev)
+        x_t = self.q_sample(x0, ts, noise=nz, lengths=lens, _coef_dev=(a_d, s_d))
+        c1 = self._row_values(self.sqrt_recip_alphas_cumprod, ts, B, dev)
+        c2 = self._row_values(self.sqrt_recipm1_alphas_cumprod, ts, B, dev)
+        t_model = self._row_values(np.asarray(self.timestep_map, dtype=np.int64), ts, B, dev, torch.int64)
+        with self._native(model, gs):
+            eps = model(x_t, t_model, sqrt_alphas=[c1, c2], audio_emb=model_kwargs.get("audio_emb"), length=model_kwargs.get("length"),
+                        person_id=model_kwargs.get("person_id"), add_cond=model_kwargs.get("add_cond"),
+                        pe_type=model_kwargs.get("pe_type", "pe_sinu"), y=model_kwargs.get("y"))
+        lens_dev = None if lens is None else _upload(torch.tensor(lens, dtype=torch.int32), dev)
+        r = denoise_losses(eps, nz, x_t, x0, c1, c2, split, lens_dev, beta)
+        rows = r["row_terms"]
+        out = {"mse": (rows[:, 0] + rows[:, 1]) / rows[:, 5], "target": nz, "pred": eps, "target_x0": x_start, "pred_x0": r["pred_x0"],
+               "x_t": x_t, "row_terms": rows, "frame_mse": r["frame_mse"], "counts": r["counts"]}
+        has_pair = max(lens or [T]) > 1
+        out["scalars"] = {k: r["scalars"][i] for i, k in enumerate(LOSS_SCALARS) if has_pair or k in ("loss_model_pred", "loss_x0_rec")}
         return out
 
     def _invert(self, model, x, from_level, to_level, clip_denoised, denoised_fn, model_kwargs, eta, return_trace, cond_scale=None):

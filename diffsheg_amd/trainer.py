@@ -5,7 +5,8 @@ ddpm_beat_trainer.py:185-220, :932-1039), plus the sharding of independent chain
 (the reference shards test videos with a DistributedSampler, ddpm_show_trainer.py:743-750).
 
 The validation loop's tail (ddpm_show_trainer.py:440-583: FGD encoder, MSE / PCK / diversity meters) is ``validate_batch`` /
-``validation_summary`` on top of :mod:`diffsheg_amd.metrics`.  The BEAT results tail (ddpm_beat_trainer.py:1044-1060: gesture channels
+``validation_summary`` on top of :mod:`diffsheg_amd.metrics`.  The eval-mode forward of the training objective (``forward(eval_mode=True)``
+:135-181 with the arithmetic of ``backward_G`` :222-260) is ``denoising_losses``, its per-level curve ``loss_profile``.  The BEAT results tail (ddpm_beat_trainer.py:1044-1060: gesture channels
 from standardised axis-angle to the standardised Euler degrees the reference saves and scores) is the ``pose_rep="euler"`` keyword of
 the sampling entry points, on :func:`diffsheg_amd.glue.axis_angle_to_euler`.  Training, BVH/JSON writers, HuBERT extraction and
 checkpoint saving are out of scope.
@@ -21,8 +22,8 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from .config import DiffSHEGConfig
-from .diffusion import (GaussianDiffusion, ModelMeanType, ModelVarType, SpacedDiffusion, get_named_beta_schedule,
-                        space_timesteps)
+from .diffusion import (GaussianDiffusion, ModelMeanType, ModelVarType, SpacedDiffusion, create_named_schedule_sampler,
+                        get_named_beta_schedule, space_timesteps)
 from .model import UniDiffuser, normalize_guidance_scale, normalize_modality
 
 
@@ -53,6 +54,12 @@ def window_seed(seed: int, window: int) -> int:
     """Philox key of window ``window`` of a chain sampled with base seed ``seed``: a 64-bit hash of the pair, so that
     neighbouring (seed, window) pairs share no stream (``seed + window`` collides for (s, w + 1) and (s + 1, w))."""
     return _splitmix64(_splitmix64(int(seed) & _M64) ^ ((int(window) + 1) * 0xD1342543DE82EF95 & _M64))
+
+
+def level_seed(seed: int, timestep: int) -> int:
+    """Philox seed of the noise :meth:`DDPMTrainer.loss_profile` draws at the ORIGINAL timestep ``timestep``: a hash of the pair alone, so
+    a level's noise does not depend on which other levels are profiled, nor on the spacing the level belongs to."""
+    return _splitmix64(_splitmix64(int(seed) & _M64) ^ ((int(timestep) + 1) * 0xA0761D6478BD642F & _M64))
 
 
 def get_windows(x, size: int, step: int):
@@ -118,6 +125,7 @@ class DDPMTrainer:
                   model_var_type=ModelVarType.FIXED_SMALL, loss_type=None)
         self.diffusion = GaussianDiffusion(**kw)
         self._diffusion_kw = kw
+        self.sampler = create_named_schedule_sampler("uniform", self.diffusion)      # ddpm_show_trainer.py:83
         # the reference hard-codes 'ddim25' here (ddpm_show_trainer.py:73, ddpm_beat_trainer.py:76): the defaults of the three options
         self.set_sampling(getattr(args, "sampling_steps", 25), getattr(args, "sampling_spacing", "ddim"), getattr(args, "solver", "ddim"))
         # validation (ddpm_show_trainer.py:440-583): eval_model = a metrics.HalfEmbeddingNet, or None for no FGD (--no_fgd)
@@ -318,6 +326,67 @@ class DDPMTrainer:
         if has_fgd:
             out["FGD"] = meters["fgd"].avg
         return out
+
+    # ---- the eval-mode forward of the training objective (ddpm_beat_trainer.py:135-181, :222-260) -----------------------------
+    def _loss_kwargs(self, audio_emb, motions, p_id, add_cond, lengths):
+        audio_emb = audio_emb.to(self.device)
+        B, T = int(audio_emb.shape[0]), int(audio_emb.shape[1])
+        if getattr(self.opt, "use_single_style", False):                 # ddpm_beat_trainer.py:137-139
+            p_id = torch.zeros_like(p_id)
+            p_id[:, :1] = 1
+        cur_len = torch.full((B,), T, dtype=torch.long) if lengths is None else torch.tensor([int(v) for v in lengths], dtype=torch.long)
+        x0 = motions.to(device=self.device, dtype=torch.float32)
+        return x0, {"audio_emb": audio_emb, "length": cur_len, "person_id": p_id, "add_cond": add_cond, "y": None,
+                    "pe_type": getattr(self.opt, "PE", "pe_sinu")}
+
+    def denoising_losses(self, audio_emb, motions, p_id, add_cond={}, t=None, noise=None, seed=None, lengths=None, cond_scale=None,
+                         row_keys=None) -> Dict[str, torch.Tensor]:
+        """The reference's ``forward(batch, eval_mode=True)`` followed by the arithmetic of ``backward_G`` (ddpm_beat_trainer.py:135-181,
+        :222-260; the SHOW trainer's are the same code), without the backward pass: "how well does the model predict the noise on this
+        take".  ``motions [B, T, C]`` standardised; ``t`` an int or one timestep of the full process per row, ``None`` draws them from the
+        uniform sampler (seeded by ``seed``; numpy's global state without one, as the reference); ``noise`` given or drawn from the Philox
+        streams (``seed``; a ragged batch draws per row: ``row_keys``, by default the row numbers); ``lengths`` one frame count per row;
+        ``cond_scale`` as for :meth:`generate_batch`.  Returns ``loss_model_pred`` (x 1000), ``loss_vel_rec`` (x 100), ``loss_x0_rec``
+        (x 100, Huber at beta 0.1) and ``final_loss`` as 0-d fp64 device tensors, plus ``row_terms [B, 7]`` and ``frame_mse [B, T]``
+        (:meth:`GaussianDiffusion.training_losses`).  Two quirks of the reference are kept: ``final_loss`` adds the UNSCALED velocity term
+        (:247), and ``opt.expr_weight`` has no effect (:231 overwrites the weighted form).  The velocity and Huber terms are always
+        included (``add_vel_loss`` past ``vel_loss_start``).  A batch without a single frame pair is refused.  No synchronisation."""
+        if max([int(v) for v in lengths] if lengths is not None else [int(motions.shape[1])]) < 2:
+            raise ValueError("denoising_losses: no row has two frames, loss_vel_rec has no frame pair to average over")
+        x0, kw = self._loss_kwargs(audio_emb, motions, p_id, add_cond, lengths)
+        B = int(x0.shape[0])
+        if t is None:
+            import numpy as np
+            rng = None if seed is None else np.random.RandomState(_splitmix64(int(seed) & _M64) & 0xFFFFFFFF)
+            t, _ = self.sampler.sample(B, "cpu", rng)                 # (host values: the tables are read on the host)
+        if lengths is not None and noise is None and row_keys is None:
+            row_keys = list(range(B))
+        out = self.diffusion.training_losses(self.encoder, x0, t, kw, noise, seed=seed, row_keys=row_keys if noise is None else None,
+                                             cond_scale=cond_scale)
+        return dict(out["scalars"], row_terms=out["row_terms"], frame_mse=out["frame_mse"])
+
+    def loss_profile(self, audio_emb, motions, p_id, add_cond={}, levels=None, seed: int = 0, cond_scale=None, full: bool = False):
+        """The per-level curves of the reference's ``calc_bpd_loop`` (gaussian_diffusion.py:1446-1501): ``mse`` (eps) and ``xstart_mse`` per clip
+        at every level, without the ``vb`` term — its decoder likelihood (``discretized_gaussian_log_likelihood``) assumes data in 1/255
+        image bins, which standardised motion is not.  ``levels``: indices into ``diffusion_ddim_val``'s levels (default: all of them, 25
+        unless :meth:`set_sampling` changed it), or with ``full=True`` timesteps of the full process.  The condition is set once; then one
+        evaluation per level with one timestep for the whole batch (the regime where the embedding Linears run on the distinct speakers
+        only).  The noise of a level comes from :func:`level_seed` ``(seed, original timestep)``: a level's result does not depend on which
+        other levels are asked for.  Nothing synchronises inside.  Returns ``{"levels", "mse" [L, B], "xstart_mse" [L, B],
+        "loss_model_pred" [L]}``, fp64 on the device."""
+        diff = self.diffusion if full else self.diffusion_ddim_val
+        levels = list(range(diff.num_timesteps)) if levels is None else [int(v) for v in levels]
+        if not levels or any(v < 0 or v >= diff.num_timesteps for v in levels):
+            raise ValueError(f"levels must be indices in 0 .. {diff.num_timesteps - 1}, got {levels}")
+        x0, kw = self._loss_kwargs(audio_emb, motions, p_id, add_cond, None)
+        mse, xmse, lmp = [], [], []
+        for k in levels:
+            out = diff.training_losses(self.encoder, x0, k, kw, seed=level_seed(seed, diff.timestep_map[k]), cond_scale=cond_scale)
+            rows = out["row_terms"]
+            mse.append(out["mse"])
+            xmse.append(rows[:, 2] / rows[:, 5])
+            lmp.append(out["scalars"]["loss_model_pred"])
+        return {"levels": levels, "mse": torch.stack(mse), "xstart_mse": torch.stack(xmse), "loss_model_pred": torch.stack(lmp)}
 
     # ---- H2: arbitrary-length chain ---------------------------------------------------------
     def sample_arbitrary_len(self, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor],

@@ -673,6 +673,31 @@ int64_t dsh_batch_metrics_result_bytes(int32_t B, int32_t T, int32_t C, int32_t 
 int dsh_op_batch_metrics(void* hip_stream, const float* outputs, const float* motions, int32_t B, int32_t T, int32_t C, int32_t joint_dim,
                          int32_t b_div, void* result_dev);
 
+/* The loss terms of the reference's eval-mode training forward (GaussianDiffusion.training_losses, gaussian_diffusion.py:1319-1426, epsilon / MSE
+ * branch; backward_G, ddpm_beat_trainer.py:222-260) from eps (the model output), noise, x_t and x0 [B, T, C] (device fp32, 4-byte aligned) in two
+ * launches on hip_stream; nothing synchronises, fixed-order reductions (two runs: identical bits; a row's numbers do not depend on B or on its
+ * position in the batch).  c1_dev / c2_dev: device arrays [B], sqrt_recip_alphas_cumprod[t_b] / sqrt_recipm1_alphas_cumprod[t_b].
+ *   x0_pred = c1 x_t - c2 eps, products and difference rounded on their own: the bits dsh_op_ddim_step_full writes to x0_out.
+ * lens_dev (DEVICE int32 [B], nullable, clamped to [0, T]): row b owns its first lens_dev[b] frames; no frame behind is read, frame pairs
+ * (f, f + 1) exist for f < lens[b] - 1.  split: the gesture | expression column boundary, 0 < split < C.  C <= 448.  Differences and
+ * quotients are single fp32 operations, squares and sums fp64.  Optional outputs (nullable): x0_pred_out [B, T, C] and frame_mse_out [B, T]
+ * = mean over C of (eps - noise)^2 per frame; both 0 on frames >= lens[b].
+ * result_dev: device buffer of dsh_denoise_losses_result_bytes(B, T) bytes, 8-byte aligned, doubles:
+ *   [0] loss_model_pred = 1000 * sum over valid frames of frame_mse / valid frames   [1] loss_vel_rec = 100 * V, V = the same mean over the
+ *   valid frame pairs of mean_C of term 3   [2] loss_x0_rec = 100 * huber_beta * mean over valid elements of term 4
+ *   [3] final_loss = [0] + V + [2] (the reference adds the UNSCALED velocity term, ddpm_beat_trainer.py:247)
+ *   [4] valid frames  [5] valid frame pairs  [6] valid elements  [7] 0;  a mean over a zero count is written as 0
+ *   [8 + 7 b + j] row b, term j:  0 sum (eps - noise)^2 over columns < split   1 the same over columns >= split   2 sum (x0_pred - x0)^2
+ *     3 sum over pairs of ((x0_pred[f] - x0_pred[f + 1]) - (x0[f] - x0[f + 1]))^2   4 sum smooth_l1(x0 / huber_beta, x0_pred / huber_beta)
+ *     at threshold 1   5 lens[b] * C   6 lens[b] - 1;   everything behind the rows is scratch (block partials).
+ * -1 (nothing launched) on a null pointer, a non-positive dim, split outside (0, C), huber_beta <= 0 or a misaligned pointer. */
+#define DSH_LOSS_HEADER 8
+#define DSH_LOSS_COLS 7
+int64_t dsh_denoise_losses_result_bytes(int32_t B, int32_t T);
+int dsh_op_denoise_losses(void* hip_stream, const float* eps, const float* noise, const float* x_t, const float* x0, const float* c1_dev,
+                          const float* c2_dev, const int32_t* lens_dev, int32_t B, int32_t T, int32_t C, int32_t split, float huber_beta,
+                          float* x0_pred_out, float* frame_mse_out, void* result_dev);
+
 /* ---- audio front (trainers/ddpm_show_trainer.py:944-1100, test_custom_aud) -------------------------------------------------- */
 /* The mel spectrogram test_custom_aud computes: librosa.feature.melspectrogram(y, sr, hop_length = hop, n_mels)[..., :-1] (power 2, no
  * logarithm, center = True with reflect padding, periodic Hann window of n_fft samples, Slaney filterbank from 0 to sr / 2 with Slaney
