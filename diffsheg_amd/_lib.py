@@ -193,6 +193,11 @@ SYMBOLS = {
     "dsh_hubert_set_chunk_pass": (C.c_int, [_P, C.c_int32]),
     "dsh_hubert_encode": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P]),
     "dsh_hubert_encode_ragged": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_int64), _P]),
+    "dsh_hubert_set_precision": (C.c_int, [_P, C.c_int32]),
+    "dsh_hubert_debug_tap": (C.c_int, [_P, _P]),
+    "dsh_op_gemm_bf16_pro": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "dsh_op_softmax_attention_bf16": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "dsh_op_softmax_attention_bf16_ragged": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "dsh_op_pos_conv": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "dsh_op_pos_conv_ragged": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "dsh_op_conv0_ln_gelu": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),

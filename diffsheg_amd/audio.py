@@ -212,7 +212,14 @@ class HubertEncoder:
 
     LARGE = HUBERT_LARGE
 
-    def __init__(self, config: dict = HUBERT_LARGE, device="cuda:0"):
+    PRECISIONS = {"fp32": 0, "bf16": 1}
+
+    def __init__(self, config: dict = HUBERT_LARGE, device="cuda:0", precision: str = "fp32"):
+        """``precision="bf16"``: the transformer layers on the bf16 matrix pipe (``dsh_hubert_set_precision``); the convolution stack, the
+        projection, the positional convolution and the last LayerNorm stay fp32, and so do the outputs.  Every method follows it."""
+        if precision not in self.PRECISIONS:
+            raise ValueError(f"HubertEncoder: precision must be one of {sorted(self.PRECISIONS)}, got {precision!r}")
+        self.precision = precision
         self.config = dict(config)
         self.hidden = int(config["hidden"])
         self._lib = _lib.lib()
@@ -225,6 +232,8 @@ class HubertEncoder:
         self._h = C.c_void_p()
         cfg = hubert_config_c(config)
         _lib.check(self._lib.dsh_hubert_create(C.byref(cfg), C.c_void_p(stream), C.byref(self._h)), "dsh_hubert_create")
+        if precision != "fp32":
+            _lib.check(self._lib.dsh_hubert_set_precision(self._h, self.PRECISIONS[precision]), "dsh_hubert_set_precision")
         self.finalized = False
 
     def load_tensors(self, state_dict) -> "HubertEncoder":
@@ -260,6 +269,11 @@ class HubertEncoder:
 
     def num_frames(self, n: int) -> int:
         return int(self._lib.dsh_hubert_num_frames(self._h, int(n)))
+
+    def debug_tap(self, h_posconv: torch.Tensor = None) -> None:
+        """Test helper: every following ``encode`` copies the residual stream ``[B M, hidden]`` as the positional convolution leaves it into
+        this fp32 device tensor (the caller keeps it alive and large enough); ``None`` switches the tap off."""
+        _lib.check(self._lib.dsh_hubert_debug_tap(self._h, None if h_posconv is None else h_posconv.data_ptr()), "dsh_hubert_debug_tap")
 
     def set_chunk_pass(self, rows: int) -> None:
         _lib.check(self._lib.dsh_hubert_set_chunk_pass(self._h, int(rows)), "dsh_hubert_set_chunk_pass")

@@ -62,5 +62,9 @@ int launch_softmax_attention(const float* qkv, int B, int M, int H, float* out, 
 // the same for rows of M_max frames of which row b owns lens[b] (DEVICE int32, clamped to [0, M_max]): keys and queries < lens[b] only, the bits
 // of the dense call on the row alone at M = lens[b]; out[b, t >= lens[b]] = 0; no frame >= lens[b] is read
 int launch_softmax_attention_ragged(const float* qkv, int B, int M_max, int H, const int* lens, float* out, hipStream_t s);
+// both on bf16 operands (v_mfma_f32_32x32x16_bf16): bf16 q^ | k^ | v in, fp32 logits and online softmax, the second product's operand is
+// RNE_bf16(exp(s - m)) while the row sum adds the unrounded values, o = (sum p^ v) / l stored RNE bf16.  Same contracts as the fp32 pair.
+int launch_softmax_attention_bf16(const bf16* qkv, int B, int M, int H, bf16* out, hipStream_t s);
+int launch_softmax_attention_bf16_ragged(const bf16* qkv, int B, int M_max, int H, const int* lens, bf16* out, hipStream_t s);
 
 }  // namespace dsh

@@ -1,6 +1,7 @@
-// Audio front on the device: mel spectrogram, polyphase resampler, softmax attention core.  fp32 throughout; every matrix product is on the
-// exact-fp32 matrix pipe (v_mfma_f32_32x32x2_f32).  Every reduction has a fixed order (no atomics): two runs give identical bits, and the
-// result of batch row b does not depend on the batch size.
+// Audio front on the device: mel spectrogram, polyphase resampler, softmax attention core.  fp32 throughout, every matrix product on the
+// exact-fp32 matrix pipe (v_mfma_f32_32x32x2_f32), except the last section: the attention core once more on bf16 operands for the HuBERT
+// encoder's bf16 precision mode.  Every reduction has a fixed order (no atomics): two runs give identical bits, and the result of batch row b
+// does not depend on the batch size.
 //
 // Mel spectrogram (MelFront::compute), four launches:
 //   1. reflect_pad_kernel      wave [B, len] -> pad [B, Lp], Lp = len + n_fft rounded up to 4 floats: pad[i] = wave[reflect(i - n_fft / 2)]
@@ -402,6 +403,141 @@ int launch_softmax_attention_ragged(const float* qkv, int B, int M_max, int H, c
     hipLaunchKernelGGL(softmax_attention_f32_kernel<true>, dim3((unsigned)(B * H * q_tiles)), dim3(64), 0, s, qkv, M_max, H, lens, out, q_tiles);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+// ---- softmax attention on bf16 operands -------------------------------------------------------------------------------------------------
+// The kernel above on v_mfma_f32_32x32x16_bf16: bf16 q^ | k^ | v in, bf16 out, the same wave per (batch row, head, 32 queries), the same
+// orientation, the same online max / sum in fp32 (no deferred rescaling).
+//   S^T = K Q^T   four MFMAs over the 64 channels: element j of lane (c, half) of step s is channel 16 s + 8 half + j of key c (A) and of
+//                 query c (B), one 16-byte load each.  fp32 logits, the query on the lane.
+//   p = exp(s - m) in fp32; the row sum l adds these UNROUNDED values; the operand of the second product is RNE_bf16(p).
+//   O^T = V^T P^T registers 8 t .. 8 t + 7 of S^T, packed to bf16, are the B fragment of step t (t = 0, 1) as they stand: element j is key
+//                 16 t + 8 (j >> 2) + 4 half + (j & 3), and the A fragment takes V of that same key.  Lane c loads channels (2 c, 2 c + 1) of
+//                 the key as one dword: the low halves feed the accumulator of the even channels (row i = channel 2 i), the high halves that of
+//                 the odd ones, so a lane ends up with eight CONSECUTIVE channels 16 g + 8 half .. + 7 per register group g: one 16-byte store.
+//   o = (sum p^ v) / l in fp32, RNE bf16 store.
+// Keys >= M get the logit -inf and the weight exactly 0; their rows are never loaded (the loads clamp to row M - 1).  RAGGED as above.
+typedef short bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void attention_zero_row_bf16(bf16* orow, int half) {
+    const u32x4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int g = 0; g < 4; ++g) *reinterpret_cast<u32x4*>(orow + 16 * g + 8 * half) = z;
+}
+
+template <bool RAGGED>
+__global__ __launch_bounds__(64) void softmax_attention_bf16_kernel(const bf16* __restrict__ qkv, int M_max, int H, const int* __restrict__ lens,
+                                                                   bf16* __restrict__ out, int q_tiles) {
+    const int lane = threadIdx.x, half = lane >> 5, col = lane & 31;
+    const int qt = blockIdx.x % q_tiles, bh = blockIdx.x / q_tiles, h = bh % H, b = bh / H;
+    const size_t ld = (size_t)3 * H * 64;
+    int M = M_max;
+    if (RAGGED) {
+        M = lens[b];
+        M = M < 0 ? 0 : (M > M_max ? M_max : M);
+        if (qt * 32 >= M) {                                 // (uniform over the wave) nothing of this tile is a frame of the row
+            if (qt * 32 + col < M_max) attention_zero_row_bf16(out + ((size_t)b * M_max + qt * 32 + col) * ((size_t)H * 64) + (size_t)h * 64, half);
+            return;
+        }
+    }
+    const bf16* base = qkv + (size_t)b * M_max * ld + (size_t)h * 64;
+    const bf16* kbase = base + (size_t)H * 64;
+    const bf16* vbase = base + (size_t)2 * H * 64;
+    const int q_row = qt * 32 + col;
+    const int q_ld = q_row < M ? q_row : M - 1;
+
+    bf16x8 qf[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(base + (size_t)q_ld * ld + 16 * s + 8 * half);
+    f32x16 o0, o1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { o0[r] = 0.0f; o1[r] = 0.0f; }
+    float m_run = -INFINITY, l_run = 0.0f;
+
+    for (int k0 = 0; k0 < M; k0 += 32) {
+        const int kr = k0 + col < M ? k0 + col : M - 1;
+        bf16x8 kf[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) kf[s] = *reinterpret_cast<const bf16x8*>(kbase + (size_t)kr * ld + 16 * s + 8 * half);
+        // the V dwords of this tile: issued in front of the logits, used behind the softmax
+        uint32_t vw[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            key = key < M ? key : M - 1;
+            vw[r] = *reinterpret_cast<const uint32_t*>(vbase + (size_t)key * ld + 2 * col);
+        }
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[c], qf[c], s, 0, 0, 0);
+        float mt = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            s[r] = key < M ? s[r] : -INFINITY;
+            mt = fmaxf(mt, s[r]);
+        }
+        mt = fmaxf(mt, __shfl_xor(mt, 32));
+        const float m_new = fmaxf(m_run, mt);               // finite: key k0 is valid in every tile
+        const float alpha = expf(m_run - m_new);            // first tile: exp(-inf) = 0
+        float psum = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { s[r] = expf(s[r] - m_new); psum += s[r]; }
+        l_run = l_run * alpha + psum;
+        m_run = m_new;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            u32x4 pf, v0, v1;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t wa = vw[8 * t + 2 * j], wb = vw[8 * t + 2 * j + 1];
+                pf[j] = pack_bf16_pair(s[8 * t + 2 * j], s[8 * t + 2 * j + 1]);
+                v0[j] = (wa & 0xffffu) | (wb << 16);
+                v1[j] = (wa >> 16) | (wb & 0xffff0000u);
+            }
+            o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, v0), __builtin_bit_cast(bf16x8, pf), o0, 0, 0, 0);
+            o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, v1), __builtin_bit_cast(bf16x8, pf), o1, 0, 0, 0);
+        }
+    }
+    const float l = l_run + __shfl_xor(l_run, 32);
+    bf16* orow = out + ((size_t)b * M_max + q_row) * ((size_t)H * 64) + (size_t)h * 64;
+    if (q_row >= M) {
+        if (RAGGED && q_row < M_max) attention_zero_row_bf16(orow, half);
+        return;
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        u32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = pack_bf16_pair(o0[4 * g + e] / l, o1[4 * g + e] / l);
+        *reinterpret_cast<u32x4*>(orow + 16 * g + 8 * half) = o;
+    }
+}
+
+static int launch_softmax_attention_bf16_any(const char* what, const bf16* qkv, int B, int M, int H, const int* lens, bool ragged, bf16* out,
+                                             hipStream_t s) {
+    DSH_REQUIRE(qkv && out && (!ragged || lens), std::string(what) + ": null pointer");
+    DSH_REQUIRE(B >= 1 && M >= 1 && H >= 1, std::string(what) + ": B, M and H must be positive");
+    DSH_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)out % 16) == 0, std::string(what) + ": operands must be 16-byte aligned");
+    const int q_tiles = ceil_div(M, 32);
+    DSH_REQUIRE((long long)B * H * q_tiles < (1ll << 31), std::string(what) + ": batch too large");
+    if (ragged) hipLaunchKernelGGL(softmax_attention_bf16_kernel<true>, dim3((unsigned)(B * H * q_tiles)), dim3(64), 0, s, qkv, M, H, lens, out, q_tiles);
+    else hipLaunchKernelGGL(softmax_attention_bf16_kernel<false>, dim3((unsigned)(B * H * q_tiles)), dim3(64), 0, s, qkv, M, H, (const int*)nullptr, out, q_tiles);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_softmax_attention_bf16(const bf16* qkv, int B, int M, int H, bf16* out, hipStream_t s) {
+    return launch_softmax_attention_bf16_any("softmax attention (bf16)", qkv, B, M, H, nullptr, false, out, s);
+}
+
+int launch_softmax_attention_bf16_ragged(const bf16* qkv, int B, int M_max, int H, const int* lens, bf16* out, hipStream_t s) {
+    return launch_softmax_attention_bf16_any("softmax attention (bf16, ragged)", qkv, B, M_max, H, lens, true, out, s);
 }
 
 }  // namespace dsh

@@ -1732,6 +1732,58 @@ int dsh_hubert_debug_packed(const dsh_hubert* h, int32_t kind, int32_t layer, in
 
 int64_t dsh_hubert_num_frames(const dsh_hubert* h, int64_t n) { return h ? h->enc->num_frames(n) : -1; }
 
+int dsh_hubert_set_precision(dsh_hubert* h, int32_t precision) {
+    API_BEGIN
+    DSH_REQUIRE(h, "null handle");
+    return h->enc->set_precision(precision);
+    API_END
+}
+
+int dsh_hubert_debug_tap(dsh_hubert* h, float* h_posconv_dev) {
+    API_BEGIN
+    DSH_REQUIRE(h, "null handle");
+    h->enc->set_debug_tap(h_posconv_dev);
+    return 0;
+    API_END
+}
+
+int dsh_op_gemm_bf16_pro(void* hip_stream, const void* A, int32_t a_f32, const float* mom, const void* W, const float* bias, const float* R,
+                         float* Cf, void* Cb, int32_t M, int32_t N, int32_t K, int32_t act, int32_t tile) {
+    API_BEGIN
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    DSH_REQUIRE(A && M >= 1 && K >= 64 && K % 64 == 0, "dsh_op_gemm_bf16_pro: M >= 1, K a multiple of 64");
+    OpScratch scratch;
+    dsh::GemmBf16ProArgs a{};
+    a.A = A; a.lda = K; a.a_f32 = a_f32 ? 1 : 0; a.mom = mom;
+    if (a_f32 && !mom) {                       // the rows' own two-pass moments (eps 1e-5), as the encoder launches them in front of the Linear
+        DSH_REQUIRE(K <= 1024, "dsh_op_gemm_bf16_pro: LayerNorm rows of at most 1024 channels");
+        void* m = nullptr;
+        if (int e = scratch.alloc(&m, (size_t)M * 2 * sizeof(float))) return e;
+        if (int e = dsh::launch_row_moments(static_cast<const float*>(A), M, K, 1e-5f, static_cast<float*>(m), s)) return e;
+        a.mom = static_cast<const float*>(m);
+    }
+    // W arrives in natural [N, K] order, which is the kernel's packed order (gemm_bf16_pro.hip): nothing to permute
+    a.W = static_cast<const dsh::bf16*>(W); a.bias = bias; a.R = R; a.Cf = Cf; a.Cb = static_cast<dsh::bf16*>(Cb);
+    a.M = M; a.N = N; a.K = K; a.act = act; a.tile = tile;
+    if (int e = dsh::launch_gemm_bf16_pro(a, s)) return e;
+    if (!scratch.p.empty()) DSH_HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+    API_END
+}
+
+int dsh_op_softmax_attention_bf16(void* hip_stream, const void* qkv, int32_t B, int32_t M, int32_t H, void* out) {
+    API_BEGIN
+    return dsh::launch_softmax_attention_bf16(static_cast<const dsh::bf16*>(qkv), B, M, H, static_cast<dsh::bf16*>(out), reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_softmax_attention_bf16_ragged(void* hip_stream, const void* qkv, int32_t B, int32_t M_max, int32_t H, const int32_t* lens_dev, void* out) {
+    API_BEGIN
+    return dsh::launch_softmax_attention_bf16_ragged(static_cast<const dsh::bf16*>(qkv), B, M_max, H, lens_dev, static_cast<dsh::bf16*>(out),
+                                                     reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
 int dsh_hubert_set_chunk_pass(dsh_hubert* h, int32_t rows) {
     API_BEGIN
     DSH_REQUIRE(h && rows >= 1, "dsh_hubert_set_chunk_pass: a handle and at least one row per pass");

@@ -35,6 +35,22 @@ struct GemmProArgs {
 };
 int launch_gemm_f32_pro(const GemmProArgs& a, hipStream_t s);
 
+// bf16 HuBERT layers: C = act(pro(A) W^T + bias) (+ R) on the bf16 matrix pipe (gemm_bf16_pro.hip).  M >= 1, K % 64 == 0, N % 64 == 0.
+struct GemmBf16ProArgs {
+    const void* A; int lda; int a_f32;  // a_f32 = 1: fp32 rows, staged as RNE_bf16((x - mean) rstd) with mom; 0: bf16 rows, staged as they are
+    const float* mom;                   // a_f32: [M] (mean, rstd) pairs (launch_row_moments)
+    const bf16* W;                      // [N, K] row-major (the kernel's packed order)
+    const float* bias;                  // [N]
+    const float* R;                     // fp32 residual [M, N] or null; may be Cf
+    float* Cf; bf16* Cb;                // exactly one: fp32 or RNE bf16 store, [M, N]
+    int M, N, K, act;                   // act: ACT_NONE or ACT_GELU (erf), on acc + bias
+    int tile;                           // 0: the launcher picks; 1 / 2: 64 x 64 / 128 x 128 tiles (the bits do not depend on it)
+    int nt_n;                           // (launcher)
+};
+int launch_gemm_bf16_pro(const GemmBf16ProArgs& a, hipStream_t s);
+// mom[row] = (mean, 1 / sqrt(var + eps)) of fp32 rows of C <= 1024 channels, two-pass
+int launch_row_moments(const float* x, int rows, int C, float eps, float* mom, hipStream_t s);
+
 template <typename T>
 int launch_ln_rows(float* h, int ldh, int M, int D, const float* pre_add, int n_pre_rows, const float* gamma,
                    const float* beta, T* out, int ldo, hipStream_t s);

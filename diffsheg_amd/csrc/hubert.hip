@@ -12,6 +12,9 @@
 //   5. per layer: h += out_proj(softmax(q k^T) v) with q|k|v one pro-1 launch (first LayerNorm folded, q rows pre-scaled by 1 / 8),
 //      softmax_attention_f32_kernel (audio_front.hip), out_proj a pro-0 launch with the residual;
 //      h += output_dense(GELU(intermediate_dense(final_LN(h)))): pro 1 with the GELU epilogue, pro 0 with the residual
+//      precision BF16 (set_precision, opt-in): the same step on the bf16 matrix pipe (gemm_bf16_pro.hip): row_moments_kernel + a Linear that
+//      stages RNE_bf16((h - mean) rstd) in front of q|k|v and intermediate_dense, bf16 q|k|v / attention output / FFN hidden,
+//      softmax_attention_bf16_kernel, both residual additions into the fp32 h in place; steps 1 - 4 and 6 are the fp32 launches either way
 //   6. encoder.layer_norm
 // Every reduction has a fixed order and there are no atomics: batch row b gives the same bits whatever B is.
 #include <algorithm>
@@ -319,14 +322,15 @@ HubertEncoder::HubertEncoder(const HubertConfig& c, hipStream_t s) : cfg_(c), st
 }
 
 void HubertEncoder::release_buffers() {
-    for (float** p : {&act_a_, &act_b_, &feat_, &h_, &h2_, &qkv_, &att_, &ffn_}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    for (float** p : {&act_a_, &act_b_, &feat_, &h_, &h2_, &qkv_, &att_, &ffn_, &mom_}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    for (bf16** p : {&qkv16_, &att16_, &ffn16_}) { if (*p) (void)hipFree(*p); *p = nullptr; }
     cap_act_ = cap_rows_ = 0;
 }
 
 HubertEncoder::~HubertEncoder() {
     if (stream_ && finalized_) (void)hipStreamSynchronize(stream_);
     release_buffers();
-    for (float* p : owned_) (void)hipFree(p);
+    for (void* p : owned_) (void)hipFree(p);
     if (lens_dev_) (void)hipFree(lens_dev_);
     if (owns_stream_) (void)hipStreamDestroy(stream_);
 }
@@ -370,9 +374,27 @@ int HubertEncoder::check_complete() const {
     return 0;
 }
 
+// fp64 -> bf16, round to nearest even in ONE step (through fp32 the value would be rounded twice)
+static uint16_t bf16_rne_from_f64(double d) {
+    if (d == 0.0 || !std::isfinite(d)) return f32_to_bf16((float)d).v;
+    int e = std::ilogb(d);                                    // |d| = m 2^e, 1 <= m < 2
+    if (e < -126) e = -126;                                   // bf16 subnormals: spacing 2^-133
+    const double q = std::nearbyint(std::ldexp(d, 7 - e));    // ties to even in the default rounding mode; |q| <= 256
+    return f32_to_bf16((float)std::ldexp(q, e - 7)).v;        // q 2^(e - 7) is a bf16 value (or overflows to inf as fp32 does)
+}
+
+int HubertEncoder::set_precision(int p) {
+    DSH_REQUIRE(!finalized_, "dsh_hubert_set_precision: only before dsh_hubert_finalize");
+    DSH_REQUIRE(p == FP32 || p == BF16, "dsh_hubert_set_precision: 0 (fp32) or 1 (bf16)");
+    DSH_REQUIRE(p == FP32 || (cfg_.hidden % 64 == 0 && cfg_.intermediate % 64 == 0), "dsh_hubert_set_precision: bf16 needs hidden and intermediate multiples of 64");
+    precision_ = p;
+    return 0;
+}
+
 // One Linear / convolution in its device form, fp64 on the host.  Folded LayerNorm (the pro 1 convention of dsh_op_gemm_f32_pro):
 // W' = gamma (.) W, bias' = b + W beta, c = row sums of W' AS ROUNDED to fp32.
-int HubertEncoder::pack(int kind, int layer, int* Nout, int* Kout, std::vector<float>* Wf, std::vector<float>* bf, std::vector<float>* cf) const {
+int HubertEncoder::pack(int kind, int layer, int* Nout, int* Kout, std::vector<float>* Wf, std::vector<float>* bf, std::vector<float>* cf,
+                        std::vector<uint16_t>* W16) const {
     DSH_REQUIRE(!finalized_, "dsh_hubert: the staged weights were released by dsh_hubert_finalize");
     if (int e = check_complete()) return e;
     const HubertConfig& c = cfg_;
@@ -450,6 +472,7 @@ int HubertEncoder::pack(int kind, int layer, int* Nout, int* Kout, std::vector<f
     }
     *Nout = N; *Kout = K;
     if (Wf) { Wf->resize(W.size()); for (size_t i = 0; i < W.size(); ++i) (*Wf)[i] = (float)W[i]; }
+    if (W16) { W16->resize(W.size()); for (size_t i = 0; i < W.size(); ++i) (*W16)[i] = bf16_rne_from_f64(W[i]); }
     if (bf) { bf->resize(N); for (int n = 0; n < N; ++n) (*bf)[n] = (float)b[n]; }
     if (cf) {
         cf->assign(N, 0.0f);
@@ -466,7 +489,13 @@ int HubertEncoder::pack(int kind, int layer, int* Nout, int* Kout, std::vector<f
 int HubertEncoder::debug_packed(int kind, int layer, int32_t* dims2, float* W, float* bias, float* fc) const {
     int N, K;
     std::vector<float> wf, bf, cf;
-    if (int e = pack(kind, layer, &N, &K, W ? &wf : nullptr, bias ? &bf : nullptr, fc ? &cf : nullptr)) return e;
+    if (layer_kind_bf16(kind)) {
+        std::vector<uint16_t> w16;
+        if (int e = pack(kind, layer, &N, &K, nullptr, bias ? &bf : nullptr, nullptr, W ? &w16 : nullptr)) return e;
+        wf.resize(w16.size());
+        for (size_t i = 0; i < w16.size(); ++i) wf[i] = bf16_to_f32(bf16{w16[i]});
+        cf.assign(N, 0.0f);
+    } else if (int e = pack(kind, layer, &N, &K, W ? &wf : nullptr, bias ? &bf : nullptr, fc ? &cf : nullptr)) return e;
     if (dims2) { dims2[0] = N; dims2[1] = K; }
     if (W) memcpy(W, wf.data(), wf.size() * sizeof(float));
     if (bias) memcpy(bias, bf.data(), bf.size() * sizeof(float));
@@ -476,6 +505,17 @@ int HubertEncoder::debug_packed(int kind, int layer, int32_t* dims2, float* W, f
 
 int HubertEncoder::upload(int kind, int layer, Lin* out) {
     std::vector<float> wf, bf, cf;
+    if (layer_kind_bf16(kind)) {             // bf16 weight and fp32 bias only
+        std::vector<uint16_t> w16;
+        if (int e = pack(kind, layer, &out->N, &out->K, nullptr, &bf, nullptr, &w16)) return e;
+        DSH_HIP_CHECK(hipMalloc((void**)&out->W16, w16.size() * sizeof(uint16_t)));
+        owned_.push_back(out->W16);
+        DSH_HIP_CHECK(hipMemcpy(out->W16, w16.data(), w16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        DSH_HIP_CHECK(hipMalloc((void**)&out->b, bf.size() * sizeof(float)));
+        owned_.push_back(out->b);
+        DSH_HIP_CHECK(hipMemcpy(out->b, bf.data(), bf.size() * sizeof(float), hipMemcpyHostToDevice));
+        return 0;
+    }
     if (int e = pack(kind, layer, &out->N, &out->K, &wf, &bf, &cf)) return e;
     for (auto pr : {std::make_pair(&out->W, &wf), std::make_pair(&out->b, &bf), std::make_pair(&out->c, &cf)}) {
         DSH_HIP_CHECK(hipMalloc((void**)pr.first, pr.second->size() * sizeof(float)));
@@ -554,9 +594,16 @@ int HubertEncoder::reserve(int B, long long n) {
     DSH_HIP_CHECK(hipMalloc((void**)&feat_, (size_t)rows * cfg_.conv_dim[6] * sizeof(float)));
     DSH_HIP_CHECK(hipMalloc((void**)&h_, (size_t)rows * cfg_.hidden * sizeof(float)));
     DSH_HIP_CHECK(hipMalloc((void**)&h2_, (size_t)rows * cfg_.hidden * sizeof(float)));
-    DSH_HIP_CHECK(hipMalloc((void**)&qkv_, (size_t)rows * 3 * cfg_.hidden * sizeof(float)));
-    DSH_HIP_CHECK(hipMalloc((void**)&att_, (size_t)rows * cfg_.hidden * sizeof(float)));
-    DSH_HIP_CHECK(hipMalloc((void**)&ffn_, (size_t)rows * cfg_.intermediate * sizeof(float)));
+    if (precision_ == BF16) {
+        DSH_HIP_CHECK(hipMalloc((void**)&qkv16_, (size_t)rows * 3 * cfg_.hidden * sizeof(bf16)));
+        DSH_HIP_CHECK(hipMalloc((void**)&att16_, (size_t)rows * cfg_.hidden * sizeof(bf16)));
+        DSH_HIP_CHECK(hipMalloc((void**)&ffn16_, (size_t)rows * cfg_.intermediate * sizeof(bf16)));
+        DSH_HIP_CHECK(hipMalloc((void**)&mom_, (size_t)rows * 2 * sizeof(float)));
+    } else {
+        DSH_HIP_CHECK(hipMalloc((void**)&qkv_, (size_t)rows * 3 * cfg_.hidden * sizeof(float)));
+        DSH_HIP_CHECK(hipMalloc((void**)&att_, (size_t)rows * cfg_.hidden * sizeof(float)));
+        DSH_HIP_CHECK(hipMalloc((void**)&ffn_, (size_t)rows * cfg_.intermediate * sizeof(float)));
+    }
     cap_act_ = act;
     cap_rows_ = rows;
     return 0;
@@ -659,8 +706,29 @@ int HubertEncoder::run(const char* what_c, const float* x, int B, long long n, c
     if (int e = linear(1, feat_, c.conv_dim[6], feat_proj_, ACT_NONE, nullptr, h2_)) return e;
     // 4. positional convolution: h_ = h2_ + GELU(posconv(h2_))
     if (int e = launch_pos_conv(h2_, B, (int)M, c.hidden, c.pos_groups, c.pos_kernel, pos_conv_.W, pos_conv_.b, h_, stream_, lens)) return e;
+    if (tap_) DSH_HIP_CHECK(hipMemcpyAsync(tap_, h_, (size_t)R * c.hidden * sizeof(float), hipMemcpyDeviceToDevice, stream_));
     // 5. the layers
-    for (int l = 0; l < c.layers; ++l) {
+    // BF16: LayerNorm as (mean, rstd) per row + normalise-then-round in the Linear's staging registers; q|k|v, the attention output and the
+    // FFN hidden in bf16; h_ stays fp32 and takes both residual additions in place
+    auto linear16 = [&](const void* in, bool in_f32, const Lin& w, int act, float* res_out, bf16* dst16) -> int {
+        GemmBf16ProArgs g{};
+        g.A = in; g.lda = w.K; g.a_f32 = in_f32 ? 1 : 0; g.mom = in_f32 ? mom_ : nullptr;
+        g.W = w.W16; g.bias = w.b; g.R = res_out; g.Cf = res_out; g.Cb = dst16;
+        g.M = R; g.N = w.N; g.K = w.K; g.act = act;
+        return launch_gemm_bf16_pro(g, stream_);
+    };
+    for (int l = 0; precision_ == BF16 && l < c.layers; ++l) {
+        const Layer& ly = layer_[l];
+        if (int e = launch_row_moments(h_, R, c.hidden, c.ln_eps, mom_, stream_)) return e;
+        if (int e = linear16(h_, true, ly.qkv, ACT_NONE, nullptr, qkv16_)) return e;
+        if (int e = lens ? launch_softmax_attention_bf16_ragged(qkv16_, B, (int)M, c.heads, lens, att16_, stream_)
+                         : launch_softmax_attention_bf16(qkv16_, B, (int)M, c.heads, att16_, stream_)) return e;
+        if (int e = linear16(att16_, false, ly.out, ACT_NONE, h_, nullptr)) return e;
+        if (int e = launch_row_moments(h_, R, c.hidden, c.ln_eps, mom_, stream_)) return e;
+        if (int e = linear16(h_, true, ly.ffn_in, ACT_GELU, nullptr, ffn16_)) return e;
+        if (int e = linear16(ffn16_, false, ly.ffn_out, ACT_NONE, h_, nullptr)) return e;
+    }
+    for (int l = 0; precision_ == FP32 && l < c.layers; ++l) {
         const Layer& ly = layer_[l];
         if (int e = linear(1, h_, c.hidden, ly.qkv, ACT_NONE, nullptr, qkv_)) return e;
         if (int e = lens ? launch_softmax_attention_ragged(qkv_, B, (int)M, c.heads, lens, att_, stream_)

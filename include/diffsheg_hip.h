@@ -810,6 +810,36 @@ int dsh_hubert_encode(dsh_hubert* h, const float* x, int32_t batch, int64_t n, f
  * LayerNorm take the frame counts, uploaded once per call (which waits for the handle's stream).  -1 (nothing launched, out untouched) for a row
  * shorter than the receptive field, lens_samples[b] > n_max, null lengths, and as dsh_hubert_encode. */
 int dsh_hubert_encode_ragged(dsh_hubert* h, const float* x, int32_t batch, int64_t n_max, const int64_t* lens_samples, float* out);
+/* Precision of the transformer layers: 0 = fp32 (the default, bit for bit what it was), 1 = bf16.  Only before dsh_hubert_finalize (-1 with a
+ * dsh_last_error text afterwards, and for any other value, or when hidden or intermediate is not a multiple of 64).
+ * bf16: the convolution stack, the feature projection, the positional convolution and the last LayerNorm stay the fp32 launches, so the
+ * residual stream h behind the positional convolution has the bits of the fp32 encoder; h stays fp32 in memory throughout.  Per layer
+ *   W' = RNE_bf16(gamma (.) W) rounded once from the fp64 fold (q rows x 1 / 8 first, exact), b' = fp32(b + W beta); no fc vector;
+ *   LayerNorm in front of q|k|v and intermediate_dense: two-pass fp32 (mean, rstd) per row (one small launch), a = RNE_bf16((h - mean) rstd)
+ *   formed while the A operand is staged (no normalised copy in memory);
+ *   q|k|v: fp32 accumulation + bias, RNE bf16 store; attention as dsh_op_softmax_attention_bf16; out_proj: h += acc + bias in fp32, in place;
+ *   intermediate_dense: erf-GELU in fp32 on acc + bias, RNE bf16 store; output_dense: h += acc + bias in fp32, in place.
+ * One accumulator with K ascending per output element, no split-K, no atomics: the bit identities of dsh_hubert_encode[_ragged] hold.
+ * The layers' fp32 weights are not uploaded (hubert-large: about 0.6 GB of weights on the device instead of 1.26 GB).  Outputs stay fp32.
+ * dsh_hubert_debug_packed then returns, for kinds 3 .. 6, W as fp32 values that are exactly the bf16-rounded weights and fc = 0. */
+int dsh_hubert_set_precision(dsh_hubert* h, int32_t precision);
+/* Test tap: every following encode call copies h [B M, hidden] as the positional convolution leaves it to h_posconv_dev (device fp32, on the
+ * handle's stream); null switches it off. */
+int dsh_hubert_debug_tap(dsh_hubert* h, float* h_posconv_dev);
+/* Linear of the bf16 layers on v_mfma_f32_32x32x16_bf16 (gemm_bf16_pro.hip): C = act(pro(A) W^T + bias) (+ R), M >= 1, K % 64 == 0, N % 64 == 0
+ * (-1 before any launch otherwise).  a_f32 = 1: A fp32 [M, K], staged as RNE_bf16((x - mean) rstd) with mom [M] (mean, rstd) pairs, or, mom null,
+ * with the rows' own two-pass moments (eps 1e-5, K <= 1024) computed into per-call scratch; a_f32 = 0: A bf16 [M, K], staged as it is.  W bf16 bits
+ * in natural [N, K] order (the kernel's packed order is that order).  bias fp32 [N].  act 0 or 2 (erf-GELU, on acc + bias).  R: fp32 residual [M, N]
+ * or null, may be Cf.  Exactly one of Cf (fp32) and Cb (RNE bf16), [M, N]; R needs Cf.  tile 0: the launcher picks, 1 / 2: 64 x 64 / 128 x 128
+ * (same bits).  One accumulator per output with K ascending. */
+int dsh_op_gemm_bf16_pro(void* hip_stream, const void* A, int32_t a_f32, const float* mom, const void* W, const float* bias, const float* R,
+                         float* Cf, void* Cb, int32_t M, int32_t N, int32_t K, int32_t act, int32_t tile);
+/* dsh_op_softmax_attention[_ragged] on bf16 operands: qkv [B, M, 3 H 64] and out [B, M, H 64] device bf16, 16-byte aligned.  fp32 logits from
+ * the bf16 q^ and k^, online softmax in fp32, p = exp(s - m) in fp32 with the row sum l over the unrounded p and RNE_bf16(p) as the operand of
+ * the second product, o = (sum p^ v) / l in fp32, RNE bf16 store.  Keys >= M (lens[b]) weigh exactly 0 and are never loaded; ragged rows have
+ * the bits of the dense call on the row alone, zeros behind lens[b]. */
+int dsh_op_softmax_attention_bf16(void* hip_stream, const void* qkv, int32_t B, int32_t M, int32_t H, void* out);
+int dsh_op_softmax_attention_bf16_ragged(void* hip_stream, const void* qkv, int32_t B, int32_t M_max, int32_t H, const int32_t* lens_dev, void* out);
 /* The encoder's new kernels on row-major operands (op tests).
  * dsh_op_pos_conv: out[b, t, o] = h[b, t, o] + GELU(bias[o] + sum_{tap, i} W[o, tap cg + i] h[b, t + tap - k / 2, g cg + i]), cg = hidden / groups,
  *   g = o / cg: Conv1d(hidden, hidden, k, padding k / 2, groups) with its last output frame dropped (k even); frames outside [0, M) count as

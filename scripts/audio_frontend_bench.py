@@ -14,9 +14,15 @@ AudioFrontEnd.features_batch (also with min_fill = 0.75: ragged passes of simila
 AudioFrontEnd.features (the path before the batch form existed), and the sampling of the same batch (sample_arbitrary_len(.., lengths=));
 the feature results are compared bit for bit.
 
+--hubert-precision fp32,bf16 builds one encoder per precision in the same process and times them ALTERNATELY (round r of every precision
+before round r + 1 of any), so that clock and pool drift hit both alike.  The first precision keeps the plain keys (features_ms, hubert_ms,
+features_batch_ms, ..); every further one adds the same keys with its name as suffix (features_ms_bf16, ..) and, against the first one, the
+largest and the rms feature difference as a fraction of the feature range and the difference of the sampled motion as a fraction of its range.
+
 Prints one JSON line per signal length (and one for the folder); --out also writes them to a file.
 
-Usage:  python scripts/audio_frontend_bench.py [--seconds 60,600] [--folder 32] [--repeat 3] [--precision bf16] [--out FILE]
+Usage:  python scripts/audio_frontend_bench.py [--seconds 60,600] [--folder 32] [--repeat 3] [--precision bf16] [--hubert-precision fp32,bf16]
+                                               [--out FILE]
 """
 from __future__ import annotations
 
@@ -54,6 +60,56 @@ def timed(fn, repeat: int) -> float:
     return sorted(ts)[len(ts) // 2]
 
 
+def timed_alternately(fns: dict, repeat: int) -> dict:
+    """median wall time in ms of every fns[name](), the names taking turns inside each round, after one warm-up call each"""
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    ts = {k: [] for k in fns}
+    for _ in range(repeat):
+        for k, fn in fns.items():
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts[k].append((time.perf_counter() - t0) * 1e3)
+    return {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
+
+
+def suffix(i: int, name: str) -> str:
+    return "" if i == 0 else "_" + name
+
+
+def feature_distance(a: torch.Tensor, b: torch.Tensor) -> tuple:
+    """(max, rms) of a - b as fractions of b's range; lists of per-row results are compared as one tensor"""
+    if isinstance(a, (list, tuple)):
+        a, b = (torch.cat([t.reshape(-1, t.shape[-1]) for t in v]) for v in (a, b))
+    rng = float(b.max() - b.min())
+    d = (a - b).double()
+    return float(d.abs().max()) / rng, float(d.pow(2).mean().sqrt()) / rng
+
+
+def folder_precisions(fes: dict, tr, cfg, count: int, repeat: int) -> dict:
+    """the folder's features_batch and the sampling behind it, once per encoder precision, timed alternately"""
+    g = torch.Generator().manual_seed(count)
+    secs = [2.0 + 13.0 * i / max(count - 1, 1) for i in torch.randperm(count, generator=g).tolist()]
+    first = next(iter(fes.values()))
+    waves = [(0.1 * torch.randn(int(16000 * s), generator=g)).to(first.device) for s in secs]
+    pid = make_inputs(cfg, count, frames=cfg.n_poses, seed=3)["person_id"]
+    feats = {k: fe.features_batch(waves) for k, fe in fes.items()}
+    r = dict(zip(("features_batch_ms" + suffix(i, k) for i, k in enumerate(fes)),
+                 timed_alternately({k: (lambda fe=fe: fe.features_batch(waves)) for k, fe in fes.items()}, repeat).values()))
+    sample = lambda k: tr.sample_arbitrary_len(feats[k][0], pid, {"pretrain_aud_feat": feats[k][1]}, lengths=feats[k][2], seed=1)
+    outs = {k: sample(k) for k in fes}
+    base = next(iter(fes))
+    for i, k in enumerate(fes):
+        if i == 0:
+            continue
+        r["feature_max_over_range_" + k], r["feature_rms_over_range_" + k] = feature_distance(feats[k][1], feats[base][1])
+        r["sample_max_over_range_" + k], r["sample_rms_over_range_" + k] = feature_distance(outs[k], outs[base])
+        r["front_end_speedup_" + k] = r["features_batch_ms"] / r["features_batch_ms_" + k]
+    return r
+
+
 def folder_case(fe, tr, cfg, count: int, repeat: int, precision: str) -> dict:
     g = torch.Generator().manual_seed(count)
     secs = [2.0 + 13.0 * i / max(count - 1, 1) for i in torch.randperm(count, generator=g).tolist()]
@@ -83,15 +139,19 @@ def main() -> None:
     ap.add_argument("--folder", type=int, default=0)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--precision", default="bf16")
+    ap.add_argument("--hubert-precision", default="fp32", help="comma-separated encoder precisions; the first one keeps the plain result keys")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "audio_frontend_bench needs a GPU"
     dev = "cuda:0"
     cfg_l = dict(hubert_ref.LARGE)
     sd = hubert_ref.make_state_dict(cfg_l, 1)
-    full = audio.HubertEncoder(cfg_l, device=dev).load_state_dict(sd)
+    precisions = [p for p in args.hubert_precision.split(",") if p]
+    encs = {p: audio.HubertEncoder(cfg_l, device=dev, precision=p).load_state_dict(sd) for p in precisions}
+    fes = {p: audio.AudioFrontEnd(e) for p, e in encs.items()}
+    full = encs[precisions[0]]
     front = audio.HubertEncoder(dict(cfg_l, layers=0), device=dev).load_state_dict({k: v for k, v in sd.items() if not k.startswith("encoder.layers.")})
-    fe = audio.AudioFrontEnd(full)
+    fe = fes[precisions[0]]
     sd_dev = {k: v.to(dev) for k, v in sd.items()}
     cfg = get_config("show")
     model = UniDiffuser(cfg, make_synthetic_state_dict(cfg, 1234), device=dev, precision=args.precision)
@@ -115,13 +175,24 @@ def main() -> None:
         mel, hub = fe.features(wave)
         rows = full.encode_long(wave)
         N = int(mel.shape[0])
-        r = {"seconds": sec, "samples": n, "mel_frames": N, "hubert_rows": int(rows.shape[0]), "precision_sampler": args.precision}
+        r = {"seconds": sec, "samples": n, "mel_frames": N, "hubert_rows": int(rows.shape[0]), "precision_sampler": args.precision,
+             "hubert_precisions": precisions}
         r["features_ms"] = timed(lambda: fe.features(wave), args.repeat)
+        if len(precisions) > 1:
+            for key, call in (("features_ms", lambda p: fes[p].features(wave)), ("hubert_ms", lambda p: encs[p].encode_long(wave))):
+                t = timed_alternately({p: (lambda p=p: call(p)) for p in precisions}, args.repeat)
+                for i, p in enumerate(precisions):
+                    r[key + suffix(i, p)] = t[p]
+            for p in precisions[1:]:
+                r["feature_max_over_range_" + p], r["feature_rms_over_range_" + p] = feature_distance(fes[p].features(wave)[1], hub)
         r["resample_ms"] = timed(lambda: audio.resample_poly(wave, 9, 8), args.repeat)
         r["mel_ms"] = timed(lambda: fe.mel(w18), args.repeat)
-        r["hubert_ms"] = timed(lambda: full.encode_long(wave), args.repeat)
+        if len(precisions) == 1:
+            r["hubert_ms"] = timed(lambda: full.encode_long(wave), args.repeat)
         r["hubert_front_ms"] = timed(lambda: audio.chunked_encode(front.encode, norm), args.repeat)
         r["hubert_layers_ms"] = r["hubert_ms"] - r["hubert_front_ms"]
+        for p in precisions[1:]:
+            r["hubert_layers_ms_" + p] = r["hubert_ms_" + p] - r["hubert_front_ms"]
         out = torch.empty(N, 1024, device=dev)
         r["interp_ms"] = timed(lambda: audio._lib.check(audio._lib.lib().dsh_interp_time(audio._stream(torch.device(dev)), rows.data_ptr(), 1,
                                                                                          int(rows.shape[0]), 1024, out.data_ptr(), N)), args.repeat)
@@ -138,6 +209,9 @@ def main() -> None:
         lines.append(r)
     if args.folder > 0:
         r = folder_case(fe, tr, cfg, args.folder, args.repeat, args.precision)
+        if len(precisions) > 1:
+            r.update(folder_precisions(fes, tr, cfg, args.folder, args.repeat))
+            r["hubert_precisions"] = precisions
         print(json.dumps(r))
         lines.append(r)
     if args.out:
