@@ -117,6 +117,7 @@ SYMBOLS = {
     "dsh_axis_angle_to_euler": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32]),
     "dsh_euler_to_axis_angle": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32]),
     "dsh_op_gemm": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "dsh_op_gemm_ex": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P] + [C.c_int32] * 11),
     "dsh_op_gemm_f32_pro": (C.c_int, [_P, C.c_int32] + [_P, C.c_int32, C.c_int32] * 4 + [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     "dsh_debug_last_tl_variant": (C.c_int32, []),
     "dsh_debug_launch_counts": (C.c_int32, [C.POINTER(C.c_int64), C.c_int32, C.c_int32]),
@@ -207,10 +208,12 @@ SYMBOLS = {
 METRICS_HEADER = 5      # DSH_METRICS_HEADER: 8-byte words in front of the per-group diversity values of dsh_op_batch_metrics
 LOSS_HEADER, LOSS_COLS = 8, 7      # the header's loss macros: batch scalars in front of, and terms per row of, dsh_op_denoise_losses
 
-# index -> name of the entries of dsh_debug_launch_counts (include/diffsheg_hip.h); the last four are values, not counts
+# index -> name of the entries of dsh_debug_launch_counts (include/diffsheg_hip.h); eval_streams .. sample_pipe and gemm_tile_pick are
+# values, not counts
 # (indices 4 and 7 are retired: their kernel forms were removed, the counts stay 0; the names keep the indices fixed)
 LAUNCH_FAMILIES = ("tl1", "tl2_loop", "tl2_roll", "tl2_roll_hl", "tl4", "tls", "ffn_fused", "ffn_fused_sty", "attn_mfma", "attn_rowmajor",
-                   "gemm_f32_fewrow", "gemm_f32_tiled", "gemm_f32_pro", "eval_streams", "sample_streams", "sample_graph", "sample_pipe")
+                   "gemm_f32_fewrow", "gemm_f32_tiled", "gemm_f32_pro", "eval_streams", "sample_streams", "sample_graph", "sample_pipe",
+                   "gemv", "gemm_bf16_tiled", "gemm_tile_pick")
 
 
 def launch_counts(reset: bool = False) -> dict:

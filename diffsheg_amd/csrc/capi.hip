@@ -514,6 +514,21 @@ int dsh_op_gemm(void* hip_stream, int32_t dtype, const void* A, const void* W, c
     API_END
 }
 
+int dsh_op_gemm_ex(void* hip_stream, int32_t dtype, const void* A, const void* W, const float* bias, const float* R, float* Cf, void* Ct,
+                   int32_t M, int32_t N, int32_t K, int32_t act, int32_t lda, int32_t ldw, int32_t ldr, int32_t res_mod, int32_t ldcf,
+                   int32_t ldct, int32_t act_after_res) {
+    API_BEGIN
+    dsh::GemmArgs a;
+    a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.bias = bias; a.R = R; a.ldr = ldr; a.res_mod = res_mod; a.Cf = Cf; a.ldcf = ldcf;
+    a.Ct = Ct; a.ldct = ldct; a.M = M; a.N = N; a.K = K; a.act = act; a.act_after_res = act_after_res; a.nt_n = a.nt_m = 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    if (dtype == 0) return dsh::launch_gemm_f32(a, s);
+    if (dtype == 1) return dsh::launch_gemm_bf16(a, s);
+    dsh::set_last_error("dsh_op_gemm_ex: unknown dtype");
+    return -1;
+    API_END
+}
+
 int dsh_op_gemm_f32_pro(void* hip_stream, int32_t pro, const float* x0, int32_t ld0, int32_t w0, const float* x1, int32_t ld1, int32_t w1,
                         const float* x2, int32_t ld2, int32_t w2, const float* x3, int32_t ld3, int32_t w3, int32_t k_real, const float* W,
                         const float* bias, const float* fc, const float* film, int32_t film_ld, int32_t film_off, int32_t frames, int32_t nb,

@@ -130,6 +130,9 @@ enum LaunchFamily {
     LC_SAMPLE_STREAMS,     // (value) sub-batch streams of the last dsh_sample
     LC_SAMPLE_GRAPH,       // (value) 1 if the last dsh_sample replayed captured graphs
     LC_SAMPLE_PIPE,        // (value) 1 if the last dsh_sample ran the two-encoder pipeline
+    LC_GEMV,               // weight-streaming GEMV for at most 16 rows, fp32 and bf16 (gemm.hip)
+    LC_GEMM_BF16_TILED,    // bf16 tiled GEMM (gemm.hip)
+    LC_GEMM_TILE_PICK,     // (value) tile shape of the last tiled GEMM launch: 0 128 x 128, 1 128 x 64, 2 64 x 64, 3 64 x 32, 4 the unswizzled 128 x 128 form
     LC_COUNT
 };
 extern std::atomic<long long> g_launch_counts[LC_COUNT];

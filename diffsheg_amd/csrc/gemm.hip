@@ -60,6 +60,17 @@ __device__ __forceinline__ void mfma_chunk<bf16>(const u32x4& a, const u32x4& b,
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc, 0, 0, 0);
 }
 
+// The D[n][m] epilogues move four consecutive columns of a row with one access: N and the leading dimensions must keep every such group
+// whole and the base pointers must carry the access width (16 bytes for the fp32 operands, 8 for a bf16 Ct).  Block-uniform (kernel
+// arguments only); a caller that misses it takes the scalar stores, which compute the same bits.
+template <typename T>
+__device__ __forceinline__ bool epilogue_vec_ok(const GemmArgs& p) {
+    const uintptr_t f32_ptrs = (uintptr_t)p.bias | (uintptr_t)p.R | (uintptr_t)p.Cf;
+    const uintptr_t ct_mask = sizeof(T) == 2 ? 7 : 15;
+    return (p.N % 4 == 0) && (!p.R || p.ldr % 4 == 0) && (!p.Cf || p.ldcf % 4 == 0) && (!p.Ct || p.ldct % 4 == 0) &&
+           (f32_ptrs & 15) == 0 && ((uintptr_t)p.Ct & ct_mask) == 0;
+}
+
 template <typename T, int VAR, int MI = 2, int NJ = 2, int WN = 2>
 __global__ __launch_bounds__(128 * WN) void gemm_nt_kernel(GemmArgs p) {
     constexpr int NTHR = 128 * WN;                       // 2 x WN waves
@@ -209,7 +220,7 @@ __global__ __launch_bounds__(128 * WN) void gemm_nt_kernel(GemmArgs p) {
     }
     } else {
     // D[n][m] layout: m = lane & 31, n = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-    const bool vec_ok = (p.N % 4 == 0) && (!p.R || p.ldr % 4 == 0) && (!p.Cf || p.ldcf % 4 == 0) && (!Ct || p.ldct % 4 == 0);
+    const bool vec_ok = epilogue_vec_ok<T>(p);
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
         const int row = m0 + wm * 32 * MI + i * 32 + (lane & 31);
@@ -347,7 +358,7 @@ __global__ __launch_bounds__(64 * KS_NW) void gemm_nt_ksplit_kernel(GemmArgs p) 
     const int row = m0 + (lane & 31);
     if (row >= p.M) return;
     const int rr = p.res_mod > 0 ? (row % p.res_mod) : row;
-    const bool vec_ok = (p.N % 4 == 0) && (!p.R || p.ldr % 4 == 0) && (!p.Cf || p.ldcf % 4 == 0) && (!Ct || p.ldct % 4 == 0);
+    const bool vec_ok = epilogue_vec_ok<T>(p);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int col = n0 + 8 * q + 4 * (lane >> 5);
@@ -510,6 +521,10 @@ static int launch_gemm_t(const GemmArgs& a, hipStream_t s) {
     DSH_REQUIRE(a.lda >= a.K && a.ldw >= a.K, "gemm leading dims smaller than K");
     DSH_REQUIRE((a.lda * sizeof(T)) % 16 == 0 && (a.ldw * sizeof(T)) % 16 == 0, "gemm leading dims must be 16-byte multiples");
     DSH_REQUIRE(((uintptr_t)a.A % 16) == 0 && ((uintptr_t)a.W % 16) == 0, "gemm operands must be 16-byte aligned");
+    DSH_REQUIRE(a.Cf || a.Ct, "gemm needs an output");
+    DSH_REQUIRE((!a.Cf || a.ldcf >= a.N) && (!a.Ct || a.ldct >= a.N) && (!a.R || a.ldr >= a.N), "gemm leading dims smaller than N");
+    DSH_REQUIRE(a.res_mod >= 0, "gemm res_mod must not be negative");
+    DSH_REQUIRE(a.act == ACT_NONE || a.act == ACT_SILU || a.act == ACT_GELU, "gemm activation unknown");
     // M <= 16: weight streaming (activation rows staged in LDS as fp32: up to 16 x 2048 x 4 bytes)
     if (switch_int(SW_GEMV) && a.M <= GV_MMAX && (size_t)(a.M <= 4 ? 4 : 16) * a.K * sizeof(float) <= 128 * 1024) {
         static bool gv_attr = false;
@@ -518,6 +533,7 @@ static int launch_gemm_t(const GemmArgs& a, hipStream_t s) {
             DSH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_rows_kernel<T, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
             gv_attr = true;
         }
+        count_launch(LC_GEMV);
         return launch_gemv_t<T>(a, s);
     }
     // fp32, a few hundred rows at most: K split over the waves of a 32 x 32-tile block (gemm_nt_ksplit_kernel); DSH_GEMM_KSPLIT=n
@@ -572,7 +588,8 @@ static int launch_gemm_t(const GemmArgs& a, hipStream_t s) {
     GemmArgs b = a;
     b.nt_n = ceil_div(a.N, sh.bn);
     b.nt_m = ceil_div(a.M, sh.bm);
-    if (sizeof(T) == 4) count_launch(LC_GEMM_F32_TILED);
+    count_launch(sizeof(T) == 4 ? LC_GEMM_F32_TILED : LC_GEMM_BF16_TILED);
+    note_launch_value(LC_GEMM_TILE_PICK, variant == 0 ? 4 : pick);
     if (variant == 0) {
         hipLaunchKernelGGL((gemm_nt_kernel<T, 0, 2, 2>), dim3(b.nt_n, b.nt_m), dim3(256), gemm_lds_bytes(2, 2), s, b);
     } else {

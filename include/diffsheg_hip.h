@@ -389,6 +389,13 @@ int dsh_euler_to_axis_angle(void* hip_stream, const float* x, int64_t ld_x, int6
  * K must be a multiple of 32 (fp32) / 64 (bf16).  Cf: fp32 out (nullable); Ct: operand-typed out (nullable). */
 int dsh_op_gemm(void* hip_stream, int32_t dtype, const void* A, const void* W, const float* bias, const float* R,
                 float* Cf, void* Ct, int32_t M, int32_t N, int32_t K, int32_t act);
+/* The same launch with every field of its argument block given by the caller, as the denoiser fills it: leading dimensions (elements) of
+ * A, W, R, Cf and Ct; res_mod > 0 takes the residual from row m % res_mod (0: row m); act_after_res != 0 applies the activation behind
+ * the residual, act(A W^T + bias + R).  Cf and Ct may both be given (Ct = the rounded Cf) and R may alias Cf.  Refused: no output, a
+ * leading dimension below K (A, W) or N (R, Cf, Ct), a negative res_mod, an unknown act, A or W not 16-byte aligned. */
+int dsh_op_gemm_ex(void* hip_stream, int32_t dtype, const void* A, const void* W, const float* bias, const float* R, float* Cf, void* Ct,
+                   int32_t M, int32_t N, int32_t K, int32_t act, int32_t lda, int32_t ldw, int32_t ldr, int32_t res_mod, int32_t ldcf,
+                   int32_t ldct, int32_t act_after_res);
 /* fp32 parity path: a Linear with what the reference computes in front of it, in ONE launch (gemm_f32_pro.hip).
  *   pro 1: C = act(LayerNorm(concat(x0 .. x3)) W^T + b) with the LayerNorm affine FOLDED by the caller: W = gamma (.) W_ref, bias = b + W_ref beta,
  *          fc[n] = sum_k W[n][k]  (models/transformer.py:106-108,119-125 q|k|v; :284-289,304-312 feat_proj.0/.1).  Segment j is fp32 [M, ld_j], w_j
@@ -424,8 +431,11 @@ int32_t dsh_debug_last_tl_variant(void);
  *    8 bf16 layers: MFMA tiled attention               9 bf16 layers: row-major attention fallback (windows of more than 96 frames)
  *   10 fp32 few-row (K-split) GEMM        11 fp32 tiled GEMM                    12 gemm_f32_pro
  *  and four VALUES rather than counts: 13 sub-batch streams of the last dsh_eval, 14 sub-batch streams of the last dsh_sample,
- *   15 whether the last dsh_sample replayed captured graphs, 16 whether it ran the two-encoder pipeline. */
-#define DSH_LAUNCH_COUNT_ENTRIES 17
+ *   15 whether the last dsh_sample replayed captured graphs, 16 whether it ran the two-encoder pipeline;
+ *  two more counts: 17 weight-streaming GEMV (at most 16 rows, fp32 and bf16), 18 bf16 tiled GEMM;
+ *  and one more value: 19 tile shape of the last tiled GEMM launch (0 128 x 128, 1 128 x 64, 2 64 x 64, 3 64 x 32, 4 the unswizzled
+ *   128 x 128 form of DSH_GEMM_VARIANT=0). */
+#define DSH_LAUNCH_COUNT_ENTRIES 20
 int32_t dsh_debug_launch_counts(int64_t* out, int32_t cap, int32_t reset);
 int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W, const float* bias, const float* R,
                      float* Cf, void* Ct, int32_t M, int32_t N, int32_t act, const float* gamma, const float* beta,

@@ -121,7 +121,12 @@ def test_the_float32_chain_passes_the_attention_gate(family):
     _attn_check(qkv, H, ref.attention(qkv, H, torch.float32, lens=lens), lens)
 
 
-@pytest.mark.parametrize("mutant", [dict(store=ref.trunc), dict(l_rounded=True), dict(key_delta=1), dict(key_delta=-1)], ids=str)
+def _mutant_id(mutant):
+    """str(mutant) with a function named instead of printed: its repr carries an address, which made the test's id differ from run to run"""
+    return "{" + ", ".join(f"{k!r}: {getattr(v, '__name__', None) or repr(v)}" for k, v in mutant.items()) + "}"
+
+
+@pytest.mark.parametrize("mutant", [dict(store=ref.trunc), dict(l_rounded=True), dict(key_delta=1), dict(key_delta=-1)], ids=_mutant_id)
 def test_attention_mutants_fail_on_some_family(mutant):
     B, M, H = ATTN_SHAPE
     lens = [33, 40] if "key_delta" in mutant else None
