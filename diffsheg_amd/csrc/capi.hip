@@ -583,6 +583,14 @@ int fetch_f32(std::vector<float>& dst, const float* dev, size_t n) {
     DSH_HIP_CHECK(hipMemcpy(dst.data(), dev, n * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
+// a bf16 device tensor as fp32 on the host (exact): the form the production packers take their weights in
+int fetch_bf16_as_f32(std::vector<float>& dst, const void* dev, size_t n) {
+    std::vector<dsh::bf16> raw(n);
+    DSH_HIP_CHECK(hipMemcpy(raw.data(), dev, n * 2, hipMemcpyDeviceToHost));
+    dst.resize(n);
+    for (size_t i = 0; i < n; ++i) dst[i] = dsh::bf16_to_f32(raw[i]);
+    return 0;
+}
 int fetch_words(std::vector<unsigned long long>& dst, const unsigned long long* dev, size_t n, hipStream_t s) {
     dst.resize(n);
     DSH_HIP_CHECK(hipStreamSynchronize(s));
@@ -638,41 +646,29 @@ int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W
     void *trl = nullptr, *tcl = nullptr;
     DSH_REQUIRE(pro != 3 || (K == 1024 && frames > 896 - 1 && frames <= 1024), "tl_linear pro 3: K = 1024, frames = real concat width (896 .. 1024)");
     if (!raw) {
-        void *wperm = nullptr, *tx = nullptr, *tr = nullptr, *tcf = nullptr, *tct = nullptr;
-        if (int e = scratch.alloc(&wperm, (size_t)N * K * 2)) return e;
-        if (int e = dsh::launch_tl_permute_weight(W, N, K, wperm, s)) return e;
-        a.W = wperm;
-        if (gen2) {      // fragment order for the LDS-DMA kernels (host round trip: this is a test helper)
-            std::vector<uint16_t> hp((size_t)N * K), hf((size_t)N * K);
+        void *wpack = nullptr, *tx = nullptr, *tr = nullptr, *tcf = nullptr, *tct = nullptr;
+        {   // the PRODUCTION packer (tl_pack_linear, as finalize() runs it) on the caller's weight, bf16 -> fp32 being exact: the first generation
+            // takes the pi-permuted rows, the LDS-DMA kernels the fragment-ordered copy with the LayerNorm of pro 1 / 3 folded into it
+            const bool fold = gen2 && (pro == 1 || pro == 3);
+            std::vector<float> hw, hbias, hg, hb, hc(N), hd(N);
+            std::vector<uint16_t> perm((size_t)N * K), frag((size_t)N * K);
             DSH_HIP_CHECK(hipStreamSynchronize(s));
-            DSH_HIP_CHECK(hipMemcpy(hp.data(), wperm, hp.size() * 2, hipMemcpyDeviceToHost));
-            if (pro == 1 || pro == 3) {      // LayerNorm folded into the weight: W' = gamma (.) W, d = b + W beta, c = row sums of W' (tl2.hip)
-                std::vector<float> hg(K), hb(K), hbias(N, 0.f), hc(N), hd(N);
-                DSH_HIP_CHECK(hipMemcpy(hg.data(), gamma, K * 4, hipMemcpyDeviceToHost));
-                DSH_HIP_CHECK(hipMemcpy(hb.data(), beta, K * 4, hipMemcpyDeviceToHost));
-                if (bias) DSH_HIP_CHECK(hipMemcpy(hbias.data(), bias, N * 4, hipMemcpyDeviceToHost));
-                for (int r = 0; r < N; ++r) {
-                    double c = 0, d = hbias[dsh::tl_weight_src_row(r)];
-                    for (int k = 0; k < K; ++k) {
-                        dsh::bf16 wv; wv.v = hp[(size_t)r * K + k];
-                        const float w = dsh::bf16_to_f32(wv);
-                        const dsh::bf16 wq = dsh::f32_to_bf16(w * hg[k]);
-                        hp[(size_t)r * K + k] = wq.v;
-                        c += (double)dsh::bf16_to_f32(wq);
-                        d += (double)hb[k] * w;
-                    }
-                    hc[dsh::tl_weight_src_row(r)] = (float)c; hd[dsh::tl_weight_src_row(r)] = (float)d;   // natural feature order
-                }
+            if (int e = fetch_bf16_as_f32(hw, W, (size_t)N * K)) return e;
+            if (fold) {
+                if (int e = fetch_f32(hg, gamma, K)) return e;
+                if (int e = fetch_f32(hb, beta, K)) return e;
+                if (bias) { if (int e = fetch_f32(hbias, bias, N)) return e; }
+            }
+            dsh::tl_pack_linear(hw.data(), hbias.empty() ? nullptr : hbias.data(), N, K, K, fold ? hg.data() : nullptr, fold ? hb.data() : nullptr,
+                                perm.data(), frag.data(), hc.data(), hd.data());
+            if (int e = scratch.upload(&wpack, gen2 ? frag.data() : perm.data(), (size_t)N * K * 2)) return e;
+            a.W = wpack;
+            if (fold) {
                 void *dc = nullptr, *dd = nullptr;
-                if (int e = scratch.alloc(&dc, N * 4)) return e;
-                if (int e = scratch.alloc(&dd, N * 4)) return e;
-                DSH_HIP_CHECK(hipMemcpy(dc, hc.data(), N * 4, hipMemcpyHostToDevice));
-                DSH_HIP_CHECK(hipMemcpy(dd, hd.data(), N * 4, hipMemcpyHostToDevice));
+                if (int e = scratch.upload(&dc, hc.data(), N * 4)) return e;
+                if (int e = scratch.upload(&dd, hd.data(), N * 4)) return e;
                 fold_c = reinterpret_cast<const float*>(dc); fold_d = reinterpret_cast<const float*>(dd);
             }
-            for (int r = 0; r < N; ++r)
-                for (int k = 0; k < K; ++k) hf[dsh::tl2_frag_index(K, r >> 5, r & 31, k)] = hp[(size_t)r * K + k];
-            DSH_HIP_CHECK(hipMemcpy(wperm, hf.data(), hf.size() * 2, hipMemcpyHostToDevice));
         }
         if (pro == 3) {
             // concat prologue (feat_proj.0 over [h | audio_proj | hubert128 | expr], transformer.py:304-312): the caller's row-major
@@ -783,19 +779,19 @@ int dsh_op_tl2_ffn(void* hip_stream, const void* X, const float* Hres, const voi
     hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
     constexpr int D = 512, F = 1024;
     OpScratch scratch;
-    // weight stream (see tl2.hip / Denoiser::layer_from): built on the host from the caller's row-major bf16 weights
-    std::vector<uint16_t> h1((size_t)F * D), h2((size_t)D * F), h3((size_t)D * D);
-    DSH_HIP_CHECK(hipStreamSynchronize(s));
-    DSH_HIP_CHECK(hipMemcpy(h1.data(), W1, h1.size() * 2, hipMemcpyDeviceToHost));
-    DSH_HIP_CHECK(hipMemcpy(h2.data(), W2, h2.size() * 2, hipMemcpyDeviceToHost));
-    DSH_HIP_CHECK(hipMemcpy(h3.data(), W3, h3.size() * 2, hipMemcpyDeviceToHost));
+    // weight stream (see tl2.hip / Denoiser::layer_from): the pi-permuted rows of the PRODUCTION packer, from the caller's row-major bf16 weights
     const int ver = dsh::ffn_generation();            // 2: tl2_ffn_kernel, 3 (default): tl3_ffn_kernel (K-outer head of Linear3)
     constexpr size_t CH = 16384;
-    std::vector<uint16_t> st((size_t)80 * CH), p1(h1.size()), p2(h2.size()), p3(h3.size());
-    for (int r = 0; r < F; ++r) std::copy(h1.begin() + (size_t)dsh::tl_weight_src_row(r) * D, h1.begin() + (size_t)(dsh::tl_weight_src_row(r) + 1) * D, p1.begin() + (size_t)r * D);
-    for (int r = 0; r < D; ++r) std::copy(h2.begin() + (size_t)dsh::tl_weight_src_row(r) * F, h2.begin() + (size_t)(dsh::tl_weight_src_row(r) + 1) * F, p2.begin() + (size_t)r * F);
-    for (int r = 0; r < D; ++r) std::copy(h3.begin() + (size_t)dsh::tl_weight_src_row(r) * D, h3.begin() + (size_t)(dsh::tl_weight_src_row(r) + 1) * D, p3.begin() + (size_t)r * D);
-    dsh::tl_pack_ffn_stream(ver, p1.data(), p2.data(), p3.data(), st.data());
+    std::vector<uint16_t> st((size_t)80 * CH), perm[3], frag;
+    const void* wsrc[3] = {W1, W2, W3}; const int wn[3] = {F, D, D}, wk[3] = {D, F, D};
+    DSH_HIP_CHECK(hipStreamSynchronize(s));
+    for (int i = 0; i < 3; ++i) {
+        std::vector<float> hw;
+        if (int e = fetch_bf16_as_f32(hw, wsrc[i], (size_t)wn[i] * wk[i])) return e;
+        perm[i].resize(hw.size()); frag.resize(hw.size());
+        dsh::tl_pack_linear(hw.data(), nullptr, wn[i], wk[i], wk[i], nullptr, nullptr, perm[i].data(), frag.data(), nullptr, nullptr);
+    }
+    dsh::tl_pack_ffn_stream(ver, perm[0].data(), perm[1].data(), perm[2].data(), st.data());
     void *wst = nullptr, *tx = nullptr, *tr = nullptr, *tcf = nullptr, *tct = nullptr, *fsc = nullptr;
     const size_t Mp = (size_t)dsh::round_up(M, 128) + 128;
     if (int e = scratch.alloc(&wst, st.size() * 2)) return e;

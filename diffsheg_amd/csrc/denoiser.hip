@@ -137,7 +137,6 @@ class Denoiser final : public DenoiserInstance {
         T* wf = nullptr;                 // token-per-lane operands: fragment-ordered copy for the LDS-DMA kernels (tl2.hip);
         float* fd = nullptr;             //   when a LayerNorm precedes the Linear it is folded in: wf = gamma (.) W, fd[n] = b[n] +
         float* fc = nullptr;             //   sum_k beta[k] W[n][k], fc[n] = sum_k wf[n][k]  (tl2.hip, PRO 1 / 3)
-        std::vector<T> hperm;            // host copy of the pi-permuted rows (only while finalize() builds the FFN stream)
         float* wfold = nullptr;          // fp32 parity path (gemm_f32_pro.hip): [N, Kp] = gamma (.) W, with fd / fc as above in natural feature order
     };
     struct LNp { float* g = nullptr; float* b = nullptr; int D = 0; };
@@ -190,7 +189,7 @@ class Denoiser final : public DenoiserInstance {
         int f32_bits = 0, f32_min_rows = 512;
         bool f32_fuse = false;           // fp32 path: LayerNorm / StylizationBlock fronts inside the GEMM launches (round 6, gemm_f32_pro.hip)
         int dbg_skip = 0;
-        int tls_rows = 0;                // DSH_TLS_ROWS: one row limit for every instantiation (0: the measured per-instantiation limits in tl())
+        int tls_rows = 0;                // DSH_TLS_ROWS: one row limit for every instantiation (0: the measured limits per role, kTlRoles)
         bool rev_on = false;
     } sw;
     int f32_now() const { return batch * frames > sw.f32_min_rows ? sw.f32_bits : 0; }   // the bits that apply to the current condition's batch
@@ -236,60 +235,23 @@ class Denoiser final : public DenoiserInstance {
         *p = reinterpret_cast<U_*>(q);
         return 0;
     }
-    int upload_f32(float** dst, const float* src, size_t nelem) {
+    template <typename U_> int upload(U_** dst, const U_* src, size_t nelem) {
         if (int e = dalloc(dst, nelem, allocs)) return e;
-        DSH_HIP_CHECK(hipMemcpy(*dst, src, nelem * sizeof(float), hipMemcpyHostToDevice));
-        wbytes += nelem * sizeof(float);
+        DSH_HIP_CHECK(hipMemcpy(*dst, src, nelem * sizeof(U_), hipMemcpyHostToDevice));
+        wbytes += nelem * sizeof(U_);
         return 0;
     }
-    // weight [N,K] fp32 host -> T device, zero padded along K to the 128-byte tile.  tl_perm: operand of tl_linear —
-    // rows zero-padded to a multiple of 32 and pi-permuted inside every 32-row tile (tl_weight_src_row); L.N = padded N
-    int make_lin(Lin& L, const float* W, const float* bias, int N, int K, bool tl_perm = false, int force_kp = 0, bool keep_host = false,
-                 const float* fold_gamma = nullptr, const float* fold_beta = nullptr) {
-        const int Np = tl_perm ? round_up(N, 32) : N;
-        L.N = Np; L.K = K; L.Kp = force_kp ? force_kp : kpad(K);
-        std::vector<T> tmp((size_t)Np * L.Kp);
-        for (int r = 0; r < Np; ++r) {
-            const int sr = tl_perm ? tl_weight_src_row(r) : r;
-            for (int k = 0; k < L.Kp; ++k)
-                tmp[(size_t)r * L.Kp + k] = from_f32<T>((sr < N && k < K) ? W[(size_t)sr * K + k] : 0.f);
-        }
-        if (int e = dalloc(&L.w, tmp.size(), allocs)) return e;
-        DSH_HIP_CHECK(hipMemcpy(L.w, tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice));
-        wbytes += tmp.size() * sizeof(T);
-        if (tl_perm && (L.Kp == 512 || L.Kp == 1024)) {
-            std::vector<T> fr(tmp.size());
-            if (fold_gamma) {
-                // LayerNorm folded into the operand of the LDS-DMA kernel: LN(x) W^T + b = rstd (x W'^T - mean c) + d
-                std::vector<float> fc(Np, 0.f), fd(Np, 0.f);
-                for (int r = 0; r < Np; ++r) {
-                    const int sr = tl_weight_src_row(r);
-                    double c = 0, d = (sr < N && bias) ? bias[sr] : 0.0;
-                    for (int k = 0; k < L.Kp; ++k) {
-                        const float w = (sr < N && k < K) ? W[(size_t)sr * K + k] : 0.f;
-                        const T wq = from_f32<T>(w * (k < K ? fold_gamma[k] : 0.f));
-                        tmp[(size_t)r * L.Kp + k] = wq;
-                        c += (double)to_f32<T>(wq);
-                        d += (double)(k < K ? fold_beta[k] : 0.f) * w;
-                    }
-                    if (sr < Np) { fc[sr] = (float)c; fd[sr] = (float)d; }      // indexed by output feature (natural order), like the bias
-                }
-                if (int e = upload_f32(&L.fc, fc.data(), Np)) return e;
-                if (int e = upload_f32(&L.fd, fd.data(), Np)) return e;
-            }
-            for (int r = 0; r < Np; ++r)
-                for (int k = 0; k < L.Kp; ++k) fr[tl2_frag_index(L.Kp, r >> 5, r & 31, k)] = tmp[(size_t)r * L.Kp + k];
-            if (int e = dalloc(&L.wf, fr.size(), allocs)) return e;
-            DSH_HIP_CHECK(hipMemcpy(L.wf, fr.data(), fr.size() * sizeof(T), hipMemcpyHostToDevice));
-            wbytes += fr.size() * sizeof(T);
-            if (keep_host) L.hperm = std::move(tmp);
-        }
-        if (bias) {
-            std::vector<float> bp(Np, 0.f);
-            std::copy(bias, bias + N, bp.begin());
-            if (int e = upload_f32(&L.b, bp.data(), Np)) return e;
-        }
-        if (sizeof(T) == 4 && !tl_perm && fold_gamma && fold_beta && bias) {
+    int upload_f32(float** dst, const float* src, size_t nelem) { return upload(dst, src, nelem); }
+    // weight [N,K] fp32 host -> T device, zero padded along K to the 128-byte tile; fold_gamma / fold_beta (fp32 parity path): the
+    // LayerNorm in front of the Linear folded into a second copy of it
+    int make_lin(Lin& L, const float* W, const float* bias, int N, int K, const float* fold_gamma = nullptr, const float* fold_beta = nullptr) {
+        L.N = N; L.K = K; L.Kp = kpad(K);
+        std::vector<T> tmp((size_t)N * L.Kp);
+        for (int r = 0; r < N; ++r)
+            for (int k = 0; k < L.Kp; ++k) tmp[(size_t)r * L.Kp + k] = from_f32<T>(k < K ? W[(size_t)r * K + k] : 0.f);
+        if (int e = upload(&L.w, tmp.data(), tmp.size())) return e;
+        if (bias) { if (int e = upload(&L.b, bias, N)) return e; }
+        if (sizeof(T) == 4 && fold_gamma && fold_beta && bias) {
             // fp32 parity path: LayerNorm folded into the Linear behind it, LN(x) W^T + b = rstd (x W'^T - mean c) + d (sums in fp64, one rounding)
             std::vector<float> wf((size_t)N * L.Kp, 0.f), fc(N), fd(N);
             for (int r = 0; r < N; ++r) {
@@ -302,10 +264,34 @@ class Denoiser final : public DenoiserInstance {
                 }
                 fc[r] = (float)c; fd[r] = (float)d;
             }
-            if (int e = upload_f32(&L.wfold, wf.data(), wf.size())) return e;
-            if (int e = upload_f32(&L.fc, fc.data(), N)) return e;
-            if (int e = upload_f32(&L.fd, fd.data(), N)) return e;
+            if (int e = upload(&L.wfold, wf.data(), wf.size())) return e;
+            if (int e = upload(&L.fc, fc.data(), N)) return e;
+            if (int e = upload(&L.fd, fd.data(), N)) return e;
         }
+        return 0;
+    }
+    // the same Linear as the operand of the token-per-lane kernels (bf16 only; K = 512, or up to 1024 zero padded): what tl_pack_linear
+    // makes of it — L.w the pi-permuted rows, L.wf the fragment-ordered copy with the LayerNorm (fold_gamma / fold_beta) folded in, L.fc /
+    // L.fd its vectors; L.N = N padded to whole 32-row tiles, the bias zero padded with it.  perm_out: the caller keeps the permuted rows
+    int make_tl_lin(Lin& L, const float* W, const float* bias, int N, int K, const float* fold_gamma = nullptr, const float* fold_beta = nullptr,
+                    std::vector<uint16_t>* perm_out = nullptr) {
+        DSH_REQUIRE(sizeof(T) == 2 && K <= 1024, "token-per-lane operands: bf16, K <= 1024");
+        const int Np = round_up(N, 32);
+        L.N = Np; L.K = K; L.Kp = round_up(K, 512);
+        std::vector<uint16_t> perm((size_t)Np * L.Kp), frag(perm.size());
+        std::vector<float> fc(Np, 0.f), fd(Np, 0.f), bp(Np, 0.f);
+        tl_pack_linear(W, bias, N, K, L.Kp, fold_gamma, fold_beta, perm.data(), frag.data(), fc.data(), fd.data());
+        if (int e = upload(&L.w, reinterpret_cast<const T*>(perm.data()), perm.size())) return e;
+        if (fold_gamma) {
+            if (int e = upload(&L.fc, fc.data(), Np)) return e;
+            if (int e = upload(&L.fd, fd.data(), Np)) return e;
+        }
+        if (int e = upload(&L.wf, reinterpret_cast<const T*>(frag.data()), frag.size())) return e;
+        if (bias) {
+            std::copy(bias, bias + N, bp.begin());
+            if (int e = upload(&L.b, bp.data(), Np)) return e;
+        }
+        if (perm_out) *perm_out = std::move(perm);
         return 0;
     }
     const HostTensor* find(const std::map<std::string, HostTensor>& w, const std::string& k) {
@@ -313,12 +299,14 @@ class Denoiser final : public DenoiserInstance {
         if (it == w.end()) { set_last_error("missing weight '" + k + "'"); return nullptr; }
         return &it->second;
     }
-    int lin_from(const std::map<std::string, HostTensor>& w, const std::string& p, Lin& L, int N, int K, bool tl_perm = false, int force_kp = 0,
-                 bool keep_host = false, const float* fold_gamma = nullptr, const float* fold_beta = nullptr) {
+    // Linear `p` of the state dict: as a GEMM operand (make_lin), or with tl as the token-per-lane operand (make_tl_lin)
+    int lin_from(const std::map<std::string, HostTensor>& w, const std::string& p, Lin& L, int N, int K, bool tl = false,
+                 const float* fold_gamma = nullptr, const float* fold_beta = nullptr, std::vector<uint16_t>* perm_out = nullptr) {
         const HostTensor* W = find(w, p + ".weight"); if (!W) return -1;
         const HostTensor* B = find(w, p + ".bias"); if (!B) return -1;
         DSH_REQUIRE((int64_t)W->numel() == (int64_t)N * K && (int)B->numel() == N, ("shape mismatch for " + p).c_str());
-        return make_lin(L, W->data.data(), B->data.data(), N, K, tl_perm, force_kp, keep_host, fold_gamma, fold_beta);
+        if (tl) return make_tl_lin(L, W->data.data(), B->data.data(), N, K, fold_gamma, fold_beta, perm_out);
+        return make_lin(L, W->data.data(), B->data.data(), N, K, fold_gamma, fold_beta);
     }
     int ln_from(const std::map<std::string, HostTensor>& w, const std::string& p, LNp& l, int D) {
         const HostTensor* G = find(w, p + ".weight"); if (!G) return -1;
@@ -328,9 +316,9 @@ class Denoiser final : public DenoiserInstance {
         if (int e = upload_f32(&l.g, G->data.data(), D)) return e;
         return upload_f32(&l.b, B->data.data(), D);
     }
-    int sty_from(const std::map<std::string, HostTensor>& w, const std::string& p, Sty& s_, int D, bool tl_perm, bool keep_host = false) {
+    int sty_from(const std::map<std::string, HostTensor>& w, const std::string& p, Sty& s_, int D, bool tl, std::vector<uint16_t>* perm_out = nullptr) {
         if (int e = ln_from(w, p + ".norm", s_.ln, D)) return e;
-        return lin_from(w, p + ".out_layers.2", s_.out, D, D, tl_perm, 0, keep_host);
+        return lin_from(w, p + ".out_layers.2", s_.out, D, D, tl, nullptr, nullptr, perm_out);
     }
     int layer_from(const std::map<std::string, HostTensor>& w, const std::string& p, Layer& L, int D, int P,
                    const float* null_emb);
@@ -384,76 +372,98 @@ class Denoiser final : public DenoiserInstance {
     }
     int run_block_tail_fused(const Layer& L, int M, int D, int nbatch, int fr, const float* film, int film_ld, int film_off0, int bmod, int has_null, int r0,
                              bool const_done, const float* next_const);
-    // token-per-lane fused Linear (bf16, K = 512): prologue pro (0 plain / 1 LN / 2 LN+FiLM+SiLU) on X
-    int tl(const Lin& L, int pro, const T* X, int M, int act, const LNp* ln, const float* film, int film_ld, int film_off,
-           int fr, int bmod, const float* R, float* Cf, T* Ct, const float* row_const, int n_const_rows,
-           const T* cat1 = nullptr, const T* cat2 = nullptr, const T* cat3 = nullptr, int kreal = 0,
-           int half_row0 = 0x7fffffff, int cf_rowmajor_ld = 0, const T* Rlo = nullptr, T* Clo = nullptr) {
-        TlArgs a;
-        a.Rlo = Rlo; a.Clo = Clo;            // hi / lo planes of the residual stream: R is then the hi plane (bf16), Cf is null
-        a.X = X; a.ldx = L.Kp; a.K = L.Kp; a.W = L.w; a.bias = L.b; a.R = R; a.ldr = L.N; a.Cf = Cf; a.ldcf = L.N; a.Ct = Ct; a.ldct = L.N;
-        a.half_row0 = half_row0; a.cf_rowmajor = cf_rowmajor_ld > 0 ? 1 : 0;
-        if (cf_rowmajor_ld > 0) a.ldcf = cf_rowmajor_ld;
-        a.M = M; a.N = L.N; a.act = act; a.gamma = ln ? ln->g : nullptr; a.beta = ln ? ln->b : nullptr;
-        a.film = film; a.film_ld = film_ld; a.film_off = film_off; a.frames = fr > 0 ? fr : 1; a.bmod = bmod > 0 ? bmod : 1;
-        a.row_const = row_const; a.n_const_rows = n_const_rows; a.dbg = 0; a.clk = nullptr;
-        a.X1 = cat1; a.ld1 = cfg.aud_latent_dim; a.X2 = cat2; a.ld2 = cfg.hubert_enc_dim; a.X3 = cat3; a.ld3 = 128; a.kreal = kreal;
-        if (pro == 3) { a.ldx = cfg.latent_dim; }
-        const double fl = 2.0 * M * (double)L.N * L.K;
-        flops_acc += fl;
-        // algorithmic HBM bytes of this launch: input rows + weight once + residual + outputs
-        const double by = (double)M * L.K * 2 + (double)L.N * L.K * 2 + (R ? (double)M * L.N * 4 : 0.0) +
-                          (Cf ? (double)M * L.N * 4 : 0.0) + (Ct ? (double)M * L.N * 2 : 0.0) + (Clo ? (double)M * L.N * 2 : 0.0);
-        int cls = PROF_TL_QKV;
-        if (pro == 2) cls = PROF_TL_STY;
-        else if (pro == 3) cls = cat3 ? PROF_TL_FEAT1_EXPR : PROF_TL_FEAT1;
-        else if (L.Kp == 1024) cls = R ? PROF_TL_FEAT3 : PROF_TL_FFN2;
-        else if (pro == 0) cls = PROF_TL_FFN1;
-        a.trace = nullptr;
-        a.rev = (M >= 4096) ? next_rev() : 0;
-        // LDS-DMA kernels for the MFMA-bound instantiations; the HBM-bound ones (fp32 residual in / out: StylizationBlock,
-        // feat_proj.3) stay on the first generation, whose two independent 128-token blocks per CU ride out memory stalls
-        // better than one 256-token block behind a single barrier (measured: 219 vs 269 us, 162 vs 184 us)
-        // window-chain batches: 32-token blocks with one tile per wave (tl_small.hip); same arithmetic, operation for operation
-        bool small = false;
-        // up to a per-instantiation row count (measured per launch at 16 / 32 window chains = 2944 / 5888 rows, conditional half 1408 /
-        // 2816, whole-chip kernel vs this family, us): StylizationBlock 19.7 / 20.1 vs 11.8 / 15.9; ffn.linear1 10.5 / 13.4 vs < 8.7 / 13.2;
-        // ffn.linear2 13.0 / 12.5 vs 10.7 / 15.4; q|k|v 13.7 / 17.5 vs 14.2 / 21.5; feat_proj.1 14.0 / 15.3 vs 12.2 / 16.0; feat_proj.3
-        // 10.4 / 12.1 vs 8.9 / 11.2.  DSH_TLS_ROWS=n replaces all six limits by n.
-        int tls_limit = sw.tls_rows;
-        if (tls_limit <= 0) {
-            if (pro == 2) tls_limit = 6144;
-            else if (pro == 1) tls_limit = 2560;
-            else if (pro == 3) tls_limit = 2048;
-            else if (L.Kp == 512) tls_limit = 6144;
-            else tls_limit = Rlo ? 3072 : 4096;
-        }
+    // ---- token-per-lane fused Linear (bf16, K = 512 / 1024): the seven Linears of the bf16 path by role, and what follows from the role ----
+    enum TlRole { TL_FEAT1, TL_FEAT3, TL_QKV, TL_STY, TL_FFN1, TL_FFN2, TL_OUT };
+    struct TlRoleRow {
+        int pro;             // prologue on X: 0 plain rows / 1 LayerNorm / 2 LayerNorm -> FiLM -> SiLU / 3 concat + LayerNorm
+        int cls;             // profiler class
+        int tls_rows;        // window-chain kernels (tl_small.hip) up to this many token rows per launch (DSH_TLS_ROWS=n replaces every limit by n)
+        bool residual;       // the launch carries the residual stream (tl_residual)
+        int hl_rows;         // rolling LDS-DMA loop on hi / lo planes from this many rows (0: this Linear has no such form)
+    };
+    // tls_rows, measured per launch at 16 / 32 window chains = 2944 / 5888 rows, conditional half 1408 / 2816, whole-chip kernel vs the
+    // window-chain family, us: StylizationBlock 19.7 / 20.1 vs 11.8 / 15.9; ffn.linear1 10.5 / 13.4 vs < 8.7 / 13.2; ffn.linear2 13.0 / 12.5 vs
+    // 10.7 / 15.4; q|k|v 13.7 / 17.5 vs 14.2 / 21.5; feat_proj.1 14.0 / 15.3 vs 12.2 / 16.0; feat_proj.3 10.4 / 12.1 vs 8.9 / 11.2.
+    // (The two K = 1024 front-less Linears: 3072 with the lo plane of the residual, 4096 without — the window-chain kernels run on hi / lo
+    // planes only, sw.tls_on, so that is feat_proj.3 against ffn.linear2.)  hl_rows: whole-chip token counts, no N split (at least 128 blocks
+    // of 256 / 128 tokens).  The `out` head has no class of its own: it is accounted as ffn.linear1, the other front-less K = 512 Linear.
+    static constexpr TlRoleRow kTlRoles[7] = {
+        /* TL_FEAT1  feat_proj.1           */ {3, PROF_TL_FEAT1, 2048, false, 0},       // (PROF_TL_FEAT1_EXPR with the expression segment, tl())
+        /* TL_FEAT3  feat_proj.3           */ {0, PROF_TL_FEAT3, 3072, true, 128 * 128},
+        /* TL_QKV    q|k|v                 */ {1, PROF_TL_QKV, 2560, false, 0},
+        /* TL_STY    StylizationBlock out  */ {2, PROF_TL_STY, 6144, true, 128 * 256},
+        /* TL_FFN1   ffn.linear1           */ {0, PROF_TL_FFN1, 6144, false, 0},
+        /* TL_FFN2   ffn.linear2           */ {0, PROF_TL_FFN2, 4096, false, 0},
+        /* TL_OUT    `out` head            */ {0, PROF_TL_FFN1, 6144, false, 0},
+    };
+    // arguments of Linear L in `role` over the tiled rows X [M, L.Kp] of `bmod` clips of `fr` frames (twice that with the CFG-null half).  The
+    // caller names whatever else the launch carries: act, gamma / beta, the FiLM table and half_row0, the residual (tl_residual), outputs,
+    // the next layer's constant, concat segments, a row-major fp32 output
+    struct TlCall { const Lin& L; TlRole role; TlArgs a; };
+    TlCall tl_call(const Lin& L, TlRole role, const T* X, int M, int fr, int bmod) const {
+        TlArgs a{};
+        a.X = X; a.ldx = kTlRoles[role].pro == 3 ? cfg.latent_dim : L.Kp; a.K = L.Kp; a.W = L.w; a.bias = L.b;
+        a.M = M; a.N = L.N; a.act = ACT_NONE; a.ldr = a.ldcf = a.ldct = L.N; a.half_row0 = 0x7fffffff;
+        a.frames = fr > 0 ? fr : 1; a.bmod = bmod > 0 ? bmod : 1;
+        a.ld1 = cfg.aud_latent_dim; a.ld2 = cfg.hubert_enc_dim; a.ld3 = 128;       // widths of the concat segments X1 / X2 / X3 (pro 3)
+        return TlCall{L, role, a};
+    }
+    // the launch adds the residual stream from row `row0` on and writes the sum back in place: as hi / lo planes (sw.hilo: the kernels
+    // take the bf16 hi plane through R and write no Cf), else as fp32 with its bf16 shadow
+    void tl_residual(TlArgs& a, int row0) const {
+        const size_t off = (size_t)row0 * cfg.latent_dim;
+        if (sw.hilo) { a.R = reinterpret_cast<const float*>(h16 + off); a.Rlo = hlo + off; a.Ct = h16 + off; a.Clo = hlo + off; }
+        else { a.R = h + off; a.Cf = h + off; a.Ct = h16 + off; }
+    }
+    enum TlFamily { TLF_GEN1, TLF_GEN2, TLF_WINDOW };      // launch_tl_linear / launch_tl2_linear / launch_tls_linear
+    // the kernel family of a prepared launch (negative: error); a.W / a.bias / a.row_const become the operands of that family
+    int tl_family(const Lin& L, TlRole role, TlArgs& a) const {
+        const TlRoleRow& r = kTlRoles[role];
+        const bool folded = r.pro == 1 || r.pro == 3;      // behind a LayerNorm: the fragment-ordered weight holds it, with bias = d and row_const = c
+        // window-chain batches: 32-token blocks with one tile per wave (tl_small.hip); same arithmetic, operation for operation.
         // A StylizationBlock launch the first-generation kernel cannot take (more than six clips per 128-token block: clips shorter than 26
         // frames at batch >= 7) stays on the window-chain kernels beyond their row limit wherever those can stage its FiLM rows (clips of 11
         // frames and more): slower than a whole-chip kernel, but it exists.  What neither family covers is refused up front by check_shape().
-        const bool tl1_ok = pro != 2 || tl_linear_film_clips_ok(fr > 0 ? fr : 1, bmod > 0 ? bmod : 1);
-        if (sw.tls_on && L.wf && (M <= tls_limit || !tl1_ok) && (pro == 0 || pro == 2 || (L.fd && L.fc))) {
+        const int tls_limit = sw.tls_rows > 0 ? sw.tls_rows : r.tls_rows;
+        const bool tl1_ok = r.pro != 2 || tl_linear_film_clips_ok(a.frames, a.bmod);
+        if (sw.tls_on && L.wf && (a.M <= tls_limit || !tl1_ok) && (!folded || (L.fd && L.fc))) {
             TlArgs b = a;
             b.W = L.wf;
-            if (pro == 1 || pro == 3) { b.bias = L.fd; b.row_const = L.fc; }
-            if (tls_linear_supported(b, pro)) { a = b; small = true; }
+            if (folded) { b.bias = L.fd; b.row_const = L.fc; }
+            if (tls_linear_supported(b, r.pro)) { a = b; return TLF_WINDOW; }
         }
+        // LDS-DMA kernels for the MFMA-bound instantiations; the HBM-bound ones (fp32 residual in / out: StylizationBlock,
+        // feat_proj.3) stay on the first generation, whose two independent 128-token blocks per CU ride out memory stalls
+        // better than one 256-token block behind a single barrier (measured: 219 vs 269 us, 162 vs 184 us).
         // round 5: the two residual-carrying launches on hi / lo planes take the rolling LDS-DMA loop as well (tl2_linear_kernel<..., ROLL, HL>)
-        // at whole-chip token counts (no N split: at least 128 token blocks); DSH_TL2_HL=0 keeps them on the first generation
+        // at whole-chip token counts; DSH_TL2_HL=0 keeps them on the first generation
         // (the rolling kernel's FiLM prologue stages at most 10 clips per 256-token block and its asm stores take 32-bit plane offsets:
         //  windows of 26 .. 28 frames at whole-chip batch, or planes of 4 GiB and more, stay on the first-generation kernel)
-        const bool hl2_fits = (pro != 2 || std::min(255 / (fr > 0 ? fr : 1) + 2, bmod > 0 ? bmod : 1) <= 10) && (size_t)M * L.N * 2 < ((size_t)1 << 32);
-        const bool hl2 = sw.tl2_hl && Rlo && L.wf && !small && hl2_fits && ((pro == 2 && L.Kp == 512 && M >= 128 * 256) || (pro == 0 && L.Kp == 1024 && M >= 128 * 128));
-        const bool use2 = !small && sw.tl2_on && L.wf && (((!R || sw.tl2_all) && !Rlo) || hl2);
-        if (use2) {
-            a.W = L.wf;
-            if (pro == 1 || pro == 3) {
-                DSH_REQUIRE(L.fd && L.fc, "token-per-lane Linear behind a LayerNorm needs the folded weight vectors");
-                a.bias = L.fd; a.row_const = L.fc;
-            }
+        const bool hl2_fits = (r.pro != 2 || std::min(255 / a.frames + 2, a.bmod) <= 10) && (size_t)a.M * L.N * 2 < ((size_t)1 << 32);
+        const bool hl2 = sw.tl2_hl && a.Rlo && L.wf && hl2_fits && r.hl_rows > 0 && a.M >= r.hl_rows;
+        if (!(sw.tl2_on && L.wf && (((!a.R || sw.tl2_all) && !a.Rlo) || hl2))) return TLF_GEN1;
+        a.W = L.wf;
+        if (folded) {
+            DSH_REQUIRE(L.fd && L.fc, "token-per-lane Linear behind a LayerNorm needs the folded weight vectors");
+            a.bias = L.fd; a.row_const = L.fc;
         }
-        if (prof) prof->begin(cls);
-        const int rc = small ? launch_tls_linear(a, pro, st) : (use2 ? launch_tl2_linear(a, pro, st) : launch_tl_linear(a, pro, st));
+        return TLF_GEN2;
+    }
+    // one launch: account, choose the family, bracket, launch, notify
+    int tl(const TlCall& c) {
+        const Lin& L = c.L;
+        const TlRoleRow& r = kTlRoles[c.role];
+        TlArgs a = c.a;
+        DSH_REQUIRE(r.residual == (a.R != nullptr), "token-per-lane Linear: the residual does not match the role");
+        const double fl = 2.0 * a.M * (double)L.N * L.K, mn = (double)a.M * L.N;
+        flops_acc += fl;
+        // algorithmic HBM bytes of this launch: input rows + weight once + residual + outputs
+        const double by = (double)a.M * L.K * 2 + (double)L.N * L.K * 2 + (a.R ? mn * 4 : 0.0) + (a.Cf ? mn * 4 : 0.0) + (a.Ct ? mn * 2 : 0.0) + (a.Clo ? mn * 2 : 0.0);
+        a.rev = (a.M >= 4096) ? next_rev() : 0;
+        const int fam = tl_family(L, c.role, a);
+        if (fam < 0) return fam;
+        if (prof) prof->begin(c.role == TL_FEAT1 && a.X3 ? PROF_TL_FEAT1_EXPR : r.cls);
+        const int rc = fam == TLF_WINDOW ? launch_tls_linear(a, r.pro, st) : (fam == TLF_GEN2 ? launch_tl2_linear(a, r.pro, st) : launch_tl_linear(a, r.pro, st));
         if (prof) prof->end(fl, by);
         if (notify_ev && ++tl_launches == notify_at) DSH_HIP_CHECK(hipEventRecord(notify_ev, st));
         return rc;
@@ -519,8 +529,7 @@ int Denoiser<T>::layer_from(const std::map<std::string, HostTensor>& w, const st
             const HostTensor *g0 = find(w, p + ".feat_proj.0.weight"), *b0 = find(w, p + ".feat_proj.0.bias");
             if (!g0 || !b0) return -1;
             const bool fold = L.tl || (sw.f32_fuse && D == 512);
-            if (int e = lin_from(w, p + ".feat_proj.1", L.f1, 2 * D, P, L.tl, L.tl ? 1024 : 0, false, fold ? g0->data.data() : nullptr,
-                                 fold ? b0->data.data() : nullptr)) return e;
+            if (int e = lin_from(w, p + ".feat_proj.1", L.f1, 2 * D, P, L.tl, fold ? g0->data.data() : nullptr, fold ? b0->data.data() : nullptr)) return e;
         }
         if (int e = lin_from(w, p + ".feat_proj.3", L.f3, D, 2 * D, L.tl)) return e;
         if (null_emb) {
@@ -564,28 +573,22 @@ int Denoiser<T>::layer_from(const std::map<std::string, HostTensor>& w, const st
         const HostTensor *lg = find(w, p + ".sa_block.norm.weight"), *lb = find(w, p + ".sa_block.norm.bias");
         if (!lg || !lb) return -1;
         const bool fold = L.tl || (sw.f32_fuse && D == 512);
-        if (int e = make_lin(L.qkv, W3.data(), B3.data(), 3 * D, D, L.tl, 0, false, fold ? lg->data.data() : nullptr,
-                             fold ? lb->data.data() : nullptr)) return e;
+        const float *fg = fold ? lg->data.data() : nullptr, *fb = fold ? lb->data.data() : nullptr;
+        if (int e = L.tl ? make_tl_lin(L.qkv, W3.data(), B3.data(), 3 * D, D, fg, fb) : make_lin(L.qkv, W3.data(), B3.data(), 3 * D, D, fg, fb)) return e;
     }
+    std::vector<uint16_t> p1, p2, p3;            // pi-permuted rows of the three FFN weights, for the fused kernel's stream below
     if (int e = sty_from(w, p + ".sa_block.proj_out", L.sty1, D, L.tl)) return e;
-    if (int e = lin_from(w, p + ".ffn.linear1", L.ffn1, F, D, L.tl, 0, L.tl)) return e;
-    if (int e = lin_from(w, p + ".ffn.linear2", L.ffn2, D, F, L.tl, 0, L.tl)) return e;
-    if (int e = sty_from(w, p + ".ffn.proj_out", L.sty2, D, L.tl, L.tl)) return e;
+    if (int e = lin_from(w, p + ".ffn.linear1", L.ffn1, F, D, L.tl, nullptr, nullptr, &p1)) return e;
+    if (int e = lin_from(w, p + ".ffn.linear2", L.ffn2, D, F, L.tl, nullptr, nullptr, &p2)) return e;
+    if (int e = sty_from(w, p + ".ffn.proj_out", L.sty2, D, L.tl, &p3)) return e;
     if (L.tl) {
         // weight stream of the fused FFN kernel, 32 KB chunks in the order its phases consume them (tl_pack_ffn_stream, tl3_ffn.hip):
         //   W1 tile j (GEMM1) at chunk c1(j) = j ? 2 j - 1 : 0 | K chunk j of W2 (GEMM2) as fragments (output tile ot, k step ks) at
         //   (2 ot + ks) KB, at chunk c2(j) = j < 31 ? 2 j + 2 : 63 | W3 from chunk 64 in the order of the kernel generation (sw.ffn_ver)
         constexpr size_t CH = 16384;                       // bf16 elements per 32 KB chunk
-        std::vector<T> st((size_t)(64 + 16) * CH);
-        static_assert(sizeof(T) == 2 || sizeof(T) == 4, "element type");
-        if (sizeof(T) == 2) {
-            tl_pack_ffn_stream(sw.ffn_ver, reinterpret_cast<const uint16_t*>(L.ffn1.hperm.data()), reinterpret_cast<const uint16_t*>(L.ffn2.hperm.data()),
-                               reinterpret_cast<const uint16_t*>(L.sty2.out.hperm.data()), reinterpret_cast<uint16_t*>(st.data()));
-        }
-        if (int e = dalloc(&L.ffn_stream, st.size(), allocs)) return e;
-        DSH_HIP_CHECK(hipMemcpy(L.ffn_stream, st.data(), st.size() * sizeof(T), hipMemcpyHostToDevice));
-        wbytes += st.size() * sizeof(T);
-        L.ffn1.hperm = std::vector<T>(); L.ffn2.hperm = std::vector<T>(); L.sty2.out.hperm = std::vector<T>();
+        std::vector<uint16_t> st((size_t)(64 + 16) * CH);
+        tl_pack_ffn_stream(sw.ffn_ver, p1.data(), p2.data(), p3.data(), st.data());
+        if (int e = upload(&L.ffn_stream, reinterpret_cast<const T*>(st.data()), st.size())) return e;       // (T = bf16: make_tl_lin)
     }
     return 0;
 }
@@ -629,9 +632,7 @@ int Denoiser<T>::encoder_from(const std::map<std::string, HostTensor>& w, const 
             DSH_REQUIRE((int64_t)jw->numel() == (int64_t)D * cin, "joint_embed weight shape");
             std::vector<uint16_t> fr((size_t)D * nf * 16);                 // (bf16 path only: T = bf16)
             tl_joint_pack_weight(jw->data.data(), cin, nf, fr.data());
-            if (int e = dalloc(&E.joint_wf, fr.size(), allocs)) return e;
-            DSH_HIP_CHECK(hipMemcpy(E.joint_wf, fr.data(), fr.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            wbytes += fr.size() * sizeof(uint16_t);
+            if (int e = upload(&E.joint_wf, reinterpret_cast<const T*>(fr.data()), fr.size())) return e;
             E.joint_nf = nf;
         }
     }
@@ -726,9 +727,7 @@ int Denoiser<T>::finalize(const std::map<std::string, HostTensor>& w) {
             std::vector<float> bap(bpe->data); bap.insert(bap.end(), bpg->data.begin(), bpg->data.end());
             if (int e = upload_f32(&aud_ap_bias, bap.data(), bap.size())) return e;
         }
-        if (int e = dalloc(&aud_stream, st.size(), allocs)) return e;
-        DSH_HIP_CHECK(hipMemcpy(aud_stream, st.data(), st.size() * 2, hipMemcpyHostToDevice));
-        wbytes += st.size() * 2;
+        if (int e = upload(&aud_stream, reinterpret_cast<const T*>(st.data()), st.size())) return e;
         std::vector<float> bb; bb.insert(bb.end(), bs1->data.begin(), bs1->data.end()); bb.insert(bb.end(), b1->data.begin(), b1->data.end());
         bb.insert(bb.end(), b2->data.begin(), b2->data.end()); bb.insert(bb.end(), bs2->data.begin(), bs2->data.end());
         DSH_REQUIRE(bb.size() == 1408, "encoder_aud bias shapes");
@@ -1047,13 +1046,13 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
         if (!L.tl && !(f32_now() & 1)) { if (int e = launch_concat_ln_rows<T>(sg, Mc, L.ln0.g, L.ln0.b, U, L.Pp, L.Pp, st)) return e; }
         if (L.tl) {
             // feat_proj.0 LayerNorm over the un-materialised concat is the register prologue of feat_proj.1
-            if (!(sw.dbg_skip & 1)) if (int e = tl(L.f1, 3, hc16, Mc, ACT_SILU, &L.ln0, nullptr, 0, 0, fr, B, nullptr, nullptr, g, nullptr, 0,
-                           aproj, E.hub, expr ? expr16 : nullptr, L.P)) return e;
-            if (sw.hilo) {
-                T* hlc = hlo + (size_t)r0 * D;
-                if (!(sw.dbg_skip & 2)) if (int e = tl(L.f3, 0, g, Mc, ACT_NONE, nullptr, nullptr, 0, 0, fr, B, reinterpret_cast<const float*>(hc16), nullptr, hc16, nullptr, 0,
-                               nullptr, nullptr, nullptr, 0, 0x7fffffff, 0, hlc, hlc)) return e;
-            } else if (int e = tl(L.f3, 0, g, Mc, ACT_NONE, nullptr, nullptr, 0, 0, fr, B, hc, hc, hc16, nullptr, 0)) return e;
+            TlCall f1 = tl_call(L.f1, TL_FEAT1, hc16, Mc, fr, B);
+            f1.a.X1 = aproj; f1.a.X2 = E.hub; f1.a.X3 = expr ? expr16 : nullptr; f1.a.kreal = L.P;
+            f1.a.gamma = L.ln0.g; f1.a.beta = L.ln0.b; f1.a.act = ACT_SILU; f1.a.Ct = g;
+            if (!(sw.dbg_skip & 1)) if (int e = tl(f1)) return e;
+            TlCall f3 = tl_call(L.f3, TL_FEAT3, g, Mc, fr, B);
+            tl_residual(f3.a, r0);                                 // (the conditional half of the stream)
+            if (!(sw.hilo && (sw.dbg_skip & 2))) if (int e = tl(f3)) return e;
         } else if (f32_now() & 1) {
             // feat_proj.0 LayerNorm over the un-materialised concat: folded into feat_proj.1, moments taken in its staging (gemm_f32_pro.hip)
             GemmProArgs cs{};
@@ -1073,7 +1072,9 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
             // the CFG-null constant of the NEXT layer is folded into this layer's last epilogue (layer 0:
             // seed_stream above), so no row kernel touches h between the GEMMs.
             const int nb = B * (1 + has_null), hr0 = has_null ? r0 : 0x7fffffff;
-            if (!(sw.dbg_skip & 4)) if (int e = tl(L.qkv, 1, h16, M, ACT_NONE, &L.sa_ln, nullptr, 0, 0, fr, B, nullptr, nullptr, qkv, nullptr, 0)) return e;
+            TlCall q = tl_call(L.qkv, TL_QKV, h16, M, fr, B);
+            q.a.gamma = L.sa_ln.g; q.a.beta = L.sa_ln.b; q.a.Ct = qkv;
+            if (!(sw.dbg_skip & 4)) if (int e = tl(q)) return e;
             if (prof) prof->begin(PROF_ATTN);
             if (sw.dbg_skip & 8) {
             } else if (fr <= 96) {
@@ -1098,11 +1099,14 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
             const double afl = 4.0 * Mc * (1 + has_null) * (double)D * (D / cfg.num_heads);
             if (prof) prof->end(afl);
             flops_acc += afl;
-            if (sw.hilo) {
-                if (!(sw.dbg_skip & 16)) if (int e = tl(L.sty1.out, 2, y, M, ACT_NONE, &L.sty1.ln, E.film_tab, film_ld, l * 4 * D, fr, B, reinterpret_cast<const float*>(h16), nullptr, h16,
-                               nullptr, 0, nullptr, nullptr, nullptr, 0, hr0, 0, hlo, hlo)) return e;
-            } else if (int e = tl(L.sty1.out, 2, y, M, ACT_NONE, &L.sty1.ln, E.film_tab, film_ld, l * 4 * D, fr, B, h, h, h16, nullptr, 0,
-                                  nullptr, nullptr, nullptr, 0, hr0)) return e;
+            // h += Linear(SiLU(FiLM(LayerNorm(rows)))): the two StylizationBlock launches of the layer differ in their rows, Linear and FiLM offset
+            auto sty_call = [&](const Sty& S, const T* rows, int film_off) {
+                TlCall c = tl_call(S.out, TL_STY, rows, M, fr, B);
+                c.a.gamma = S.ln.g; c.a.beta = S.ln.b; c.a.film = E.film_tab; c.a.film_ld = film_ld; c.a.film_off = film_off; c.a.half_row0 = hr0;
+                tl_residual(c.a, 0);
+                return c;
+            };
+            if (!(sw.hilo && (sw.dbg_skip & 16))) if (int e = tl(sty_call(L.sty1, y, l * 4 * D))) return e;
             const float* next_const = (has_null && l + 1 < cfg.num_layers) ? E.layers[l + 1].null_const : nullptr;
             if (sw.ffn_fuse && L.ffn_stream && (sw.ffn_ver == 3 ? tl3_ffn_supported(M, fr, B, sw.hilo) : tl2_ffn_supported(M, fr, B))) {
                 // ffn.linear1 -> GELU -> ffn.linear2 -> StylizationBlock -> + h in ONE kernel: hidden and y2 stay in registers
@@ -1125,13 +1129,15 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
                 if (rc) return rc;
                 continue;
             }
-            if (int e = tl(L.ffn1, 0, h16, M, ACT_GELU, nullptr, nullptr, 0, 0, fr, B, nullptr, nullptr, g, nullptr, 0)) return e;
-            if (int e = tl(L.ffn2, 0, g, M, ACT_NONE, nullptr, nullptr, 0, 0, fr, B, nullptr, nullptr, y2, nullptr, 0)) return e;
-            if (sw.hilo) {
-                if (int e = tl(L.sty2.out, 2, y2, M, ACT_NONE, &L.sty2.ln, E.film_tab, film_ld, l * 4 * D + 2 * D, fr, B, reinterpret_cast<const float*>(h16), nullptr,
-                               h16, next_const, Mc, nullptr, nullptr, nullptr, 0, hr0, 0, hlo, hlo)) return e;
-            } else if (int e = tl(L.sty2.out, 2, y2, M, ACT_NONE, &L.sty2.ln, E.film_tab, film_ld, l * 4 * D + 2 * D, fr, B, h, h, h16,
-                                  next_const, Mc, nullptr, nullptr, nullptr, 0, hr0)) return e;
+            TlCall l1 = tl_call(L.ffn1, TL_FFN1, h16, M, fr, B);
+            l1.a.act = ACT_GELU; l1.a.Ct = g;
+            if (int e = tl(l1)) return e;
+            TlCall l2 = tl_call(L.ffn2, TL_FFN2, g, M, fr, B);
+            l2.a.Ct = y2;
+            if (int e = tl(l2)) return e;
+            TlCall s2 = sty_call(L.sty2, y2, l * 4 * D + 2 * D);
+            s2.a.row_const = next_const; s2.a.n_const_rows = Mc;   // the next layer's CFG-null constant, on the null half's rows
+            if (int e = tl(s2)) return e;
         } else if (f32_now()) {
             // (the CFG-null constant of layer l + 1 rides in this layer's last epilogue when that is the fused StylizationBlock launch)
             const bool hand_over = has_null && (f32_now() & 3) == 3;
@@ -1144,8 +1150,9 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
         }
     }
     if (tlp) {
-        if (int e = tl(E.out_tl, 0, h16, M, ACT_NONE, nullptr, nullptr, 0, 0, fr, B, nullptr, o, nullptr, nullptr, 0,
-                       nullptr, nullptr, nullptr, 0, 0x7fffffff, E.cin_p)) return e;
+        TlCall c = tl_call(E.out_tl, TL_OUT, h16, M, fr, B);
+        c.a.Cf = o; c.a.cf_rowmajor = 1; c.a.ldcf = E.cin_p;       // fp32 rows in natural order, as launch_cfg_mix reads them
+        if (int e = tl(c)) return e;
     } else if (int e = gemm(E.out, hT(), D, M, ACT_NONE, false, nullptr, 0, 0, o, E.cin_p, nullptr, 0)) return e;
     if (int e = launch_cfg_mix(o, E.cin_p, Mc, r0, fr, w, has_null, gs, gs_row, eps, C, c0, x, C, c1, c2,
                                want_x0 ? expr_x0 : nullptr, expr_ld(), st)) return e;

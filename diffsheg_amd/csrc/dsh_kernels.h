@@ -117,8 +117,6 @@ bool tls_linear_supported(const TlArgs& a, int pro);
 bool tls_film_clips_ok(int frames, int bmod);
 int launch_tls_linear(const TlArgs& a, int pro, hipStream_t s);
 int tl_weight_src_row(int r);
-// device-side application of the same row permutation to a bf16 [N, K] weight (test / bench helper of capi.hip)
-int launch_tl_permute_weight(const void* W, int N, int K, void* dst, hipStream_t s);
 
 // ---- second generation (tl2.hip): LDS-DMA weight stream from FRAGMENT-ORDERED weights -------------------------------
 // same arguments as launch_tl_linear, except that a.W is the fragment-ordered copy of the weight (tl2_frag_index)
@@ -150,6 +148,12 @@ bool tl3_ffn_supported(int M, int frames, int bmod, bool planes);   // the gate 
 // the 80-chunk weight stream of the fused FFN kernels from pi-permuted row-major bf16 weights ([1024,512], [512,1024], [512,512]);
 // version 2: tl2_ffn_kernel, 3: tl3_ffn_kernel; `st` receives 80 * 16384 elements
 void tl_pack_ffn_stream(int version, const uint16_t* w1p, const uint16_t* w2p, const uint16_t* w3p, uint16_t* st);
+// the operands of one token-per-lane Linear from its fp32 weight W [N, K] (bias [N], gamma / beta [K]: null = none), K zero padded to Kp
+// and N to Np = round_up(N, 32); the one packer of finalize() and of the op-level entries (tl2.hip).  perm / frag [Np, Kp] bf16: the
+// pi-permuted rows (never folded: operand of launch_tl_linear and of tl_pack_ffn_stream) and the fragment-ordered copy (launch_tl2_linear,
+// launch_tls_linear), folded with the LayerNorm when gamma is given; fc / fd [Np] then receive its c and d vectors (else they may be null)
+void tl_pack_linear(const float* W, const float* bias, int N, int K, int Kp, const float* gamma, const float* beta, uint16_t* perm, uint16_t* frag,
+                    float* fc, float* fd);
 
 // ---- tiled-layout helpers (rowops.hip).  bf16 tiles: 32 tokens x 16 features; fp32: lane-native 32 x 32 blocks ----
 // row-major [M, w] (ld, element type TS = float or bf16) -> bf16 tiled [Mpad, Wd]; columns >= w are zero filled

@@ -1116,4 +1116,31 @@ size_t tl2_frag_index(int K, int nt, int n, int k) {
     return (((size_t)nt * (K / 16) + s) * 64 + (n + 32 * hh)) * 8 + j;
 }
 
+// operands of one token-per-lane Linear from its fp32 weight (declared in dsh_kernels.h).  With Np = round_up(N, 32):
+//   perm [Np, Kp]: bf16(W), columns zero padded to Kp, rows zero padded to Np and pi-permuted inside every 32-row tile (tl_weight_src_row)
+//   frag [Np, Kp]: the same rows in fragment order (tl2_frag_index); with gamma, of the folded weight W' = bf16(gamma (.) W)
+//   fc / fd [Np] (gamma given), natural feature order: LN(x) W^T + b = rstd (x W'^T - mean c) + d with c[n] = sum_k W'[n][k] over the ROUNDED W',
+//   d[n] = b[n] + sum_k beta[k] W[n][k] over the unrounded W; sums in fp64, one rounding
+void tl_pack_linear(const float* W, const float* bias, int N, int K, int Kp, const float* gamma, const float* beta, uint16_t* perm, uint16_t* frag,
+                    float* fc, float* fd) {
+    const int Np = round_up(N, 32);
+    for (int r = 0; r < Np; ++r) {
+        const int sr = tl_weight_src_row(r);
+        double c = 0, d = (sr < N && bias) ? bias[sr] : 0.0;
+        for (int k = 0; k < Kp; ++k) {
+            const float w = (sr < N && k < K) ? W[(size_t)sr * K + k] : 0.f;
+            uint16_t q = f32_to_bf16(w).v;
+            perm[(size_t)r * Kp + k] = q;
+            if (gamma) {
+                const bf16 wq = f32_to_bf16(w * (k < K ? gamma[k] : 0.f));
+                q = wq.v;
+                c += (double)bf16_to_f32(wq);
+                d += (double)(k < K ? beta[k] : 0.f) * w;
+            }
+            frag[tl2_frag_index(Kp, r >> 5, r & 31, k)] = q;
+        }
+        if (gamma) { fc[sr] = (float)c; fd[sr] = (float)d; }
+    }
+}
+
 }  // namespace dsh

@@ -226,7 +226,7 @@ def gelu_noise(shape, seed=1):
 
 
 def tl_folded(t, Mv, pro, act, kreal=None):
-    """The folded-LayerNorm Linear of the second generation, from the operands the op helper builds:
+    """The folded-LayerNorm Linear of the second generation, from the operands the production packer builds:
     W' = bf16(gamma * W), c = sum_k W', d = b + W beta, y = rstd (x W'^T - mean c) + d, in fp64; and the slack of its fp32 evaluation.
       * x W'^T: accum_bound, scaled by rstd;
       * mean (an fp32 sum of K values): K 2^-23 mean|x|, times rstd |c|, plus the fp32 rounding of c;

@@ -4,7 +4,7 @@ Integers in {-2 .. 2} (a quarter of the entries non-zero) for X and W, integer b
 partial sum is an exact fp32 integer in any order (sum |x w| < 2^24) and every result an exact bf16 integer (|y| < 256, asserted on
 the reference), so the kernel's output must EQUAL the fp64 product - torch.equal, all rows, at row counts around every 32 / 128 / 256
 block edge.  One-hot rows name a wrong element of the fragment / permutation order; a zero input with a bias grid sweeps the
-activation epilogues; the folded LayerNorm is compared with the fold the op helper builds, within the bound of its fp32 evaluation;
+activation epilogues; the folded LayerNorm is compared with the production fold (tl_pack_linear, as finalize() runs it), within the bound of its fp32 evaluation;
 the attention kernels are given logits whose softmaxes are exactly uniform, so that y = the time mean of v, exactly.
 
 Observed on an MI355X (each test prints its figure; the whole file takes 1.1 .. 1.3 s):
@@ -189,7 +189,7 @@ def test_tl_linear_activation_sweep(K, N, act, gen, monkeypatch):
 @pytest.mark.parametrize("K,N,pro,act", [(512, 1536, 1, 0), (1024, 1024, 3, 1)])
 def test_folded_layernorm_matches_the_fold_of_its_operands(K, N, pro, act, monkeypatch):
     """q|k|v behind a LayerNorm and feat_proj.1 behind the concat-LayerNorm (999 real columns) against
-    y = rstd (x W'^T - mean c) + d built from W' = bf16(gamma W), c, d as the op helper folds them: the gate is the bound of the fp32
+    y = rstd (x W'^T - mean c) + d built from W' = bf16(gamma W), c, d as the production packer folds them: the gate is the bound of the fp32
     evaluation of THAT expression on these operands (bf16_gates.tl_folded), not a fraction of the range.  (The unfolded LayerNorm
     differs from it by ~1e-2 here through the rounding of W'.)"""
     _set_gen(monkeypatch, "2")

@@ -38,10 +38,10 @@ LOOP_ORACLE_TOL = {"fp32": 1e-3, "bf16": 1.2e-2}     # ... vs the oracle's 25-st
 # The dispatch rules, restated.  Every constant names where it lives; `expected_launches` is the only consumer.
 # ---------------------------------------------------------------------------------------------------------------------------------
 LAYERS = 8
-TLS_ROWS = {"feat_proj.1": 2048, "qkv": 2560, "feat_proj.3": 3072, "ffn.linear2": 4096, "sty": 6144, "ffn.linear1": 6144}  # denoiser.hip tl(): tls_limit
+TLS_ROWS = {"feat_proj.1": 2048, "qkv": 2560, "feat_proj.3": 3072, "ffn.linear2": 4096, "sty": 6144, "ffn.linear1": 6144}  # denoiser.hip kTlRoles: tls_rows
 TLS_MAXCLIP, TL1_MAXCLIP, T2_MAXCLIP, FFN_MAXCLIP = 4, 6, 10, 3        # tl_small.hip, tl_common.h, tl2.hip, tl2.hip / tl3_ffn.hip
 FFN_FUSE_ROWS = 128 * 64                                               # tl2.hip tl2_ffn_supported
-HL_STY_ROWS, HL_F3_ROWS = 128 * 256, 128 * 128                         # denoiser.hip tl(): hl2
+HL_STY_ROWS, HL_F3_ROWS = 128 * 256, 128 * 128                         # denoiser.hip kTlRoles: hl_rows
 ROLL_MIN_BLOCKS = 128                                                  # tl2.hip launch_tl2_linear: N split below this many token blocks
 ATTN_MFMA_FRAMES = 96                                                  # denoiser.hip run_encoder
 SPLIT = {"bf16": (12288, 21500), "fp32": (4096, 2900)}                 # denoiser_context.hip: (min rows, rows per stream)
@@ -150,19 +150,19 @@ def _inst(case):
 
 S, Bt, Sg = "show", "beat", "single"
 BOUNDARIES = [
-    dict(name="feat_proj.1: window-chain kernels up to 2048 rows", where="denoiser.hip tl() tls_limit (pro 3)",
+    dict(name="feat_proj.1: window-chain kernels up to 2048 rows", where="denoiser.hip kTlRoles tls_rows (TL_FEAT1)",
          side=lambda c: _inst(c)[0] <= 2048,
          cases=[(S, "bf16", 32, 64), (S, "bf16", 33, 64), (S, "bf16", 23, 88), (S, "bf16", 24, 88), (Bt, "bf16", 60, 34), (Bt, "bf16", 61, 34)]),
-    dict(name="q|k|v: window-chain kernels up to 2560 rows", where="denoiser.hip tl() tls_limit (pro 1)",
+    dict(name="q|k|v: window-chain kernels up to 2560 rows", where="denoiser.hip kTlRoles tls_rows (TL_QKV)",
          side=lambda c: _inst(c)[1] <= 2560,
          cases=[(S, "bf16", 20, 64), (S, "bf16", 21, 64), (S, "bf16", 14, 88), (S, "bf16", 15, 88), (Bt, "bf16", 75, 34), (Bt, "bf16", 76, 34)]),
-    dict(name="feat_proj.3 (hi/lo): window-chain kernels up to 3072 rows", where="denoiser.hip tl() tls_limit (Rlo)",
+    dict(name="feat_proj.3 (hi/lo): window-chain kernels up to 3072 rows", where="denoiser.hip kTlRoles tls_rows (TL_FEAT3)",
          side=lambda c: _inst(c)[0] <= 3072,
          cases=[(S, "bf16", 48, 64), (S, "bf16", 49, 64), (S, "bf16", 34, 88), (S, "bf16", 35, 88), (Bt, "bf16", 90, 34), (Bt, "bf16", 91, 34)]),
-    dict(name="ffn.linear2: window-chain kernels up to 4096 rows (also: reversed weight-stream order from 4096)", where="denoiser.hip tl() tls_limit, a.rev",
+    dict(name="ffn.linear2: window-chain kernels up to 4096 rows (also: reversed weight-stream order from 4096)", where="denoiser.hip kTlRoles tls_rows (TL_FFN2), tl() a.rev",
          side=lambda c: _inst(c)[1] <= 4096,
          cases=[(S, "bf16", 32, 64), (S, "bf16", 33, 64), (S, "bf16", 23, 88), (S, "bf16", 24, 88), (Bt, "bf16", 120, 34), (Bt, "bf16", 121, 34)]),
-    dict(name="StylizationBlock / ffn.linear1: window-chain kernels up to 6144 rows", where="denoiser.hip tl() tls_limit (pro 2, K = 512)",
+    dict(name="StylizationBlock / ffn.linear1: window-chain kernels up to 6144 rows", where="denoiser.hip kTlRoles tls_rows (TL_STY, TL_FFN1)",
          side=lambda c: _inst(c)[1] <= 6144,
          cases=[(S, "bf16", 48, 64), (S, "bf16", 49, 64), (S, "bf16", 34, 88), (S, "bf16", 35, 88), (Bt, "bf16", 180, 34), (Bt, "bf16", 181, 34),
                 (Sg, "bf16", 34, 88), (Sg, "bf16", 35, 88)]),
@@ -171,7 +171,7 @@ BOUNDARIES = [
          cases=[(S, "bf16", b, t) for t in (10, 11, 15, 16) for b in (4, 5, 6)] + [(S, "bf16", 7, t) for t in (11, 15, 16)] +
                [(Bt, "bf16", b, t) for t in (5, 7, 10) for b in (1, 4, 6)]),
     dict(name="first-generation FiLM prologue: at most 6 clips per 128-token block (shorter windows stay on the window-chain kernels)",
-         where="tl_linear.hip tl_linear_film_clips_ok, denoiser.hip tl()",
+         where="tl_linear.hip tl_linear_film_clips_ok, denoiser.hip tl_family()",
          side=lambda c: min(127 // c[3] + 2, c[2]) <= 6,
          cases=[(S, "bf16", 150, 25), (S, "bf16", 150, 26), (S, "bf16", 150, 24), (Bt, "bf16", 300, 25), (Bt, "bf16", 300, 26)]),
     dict(name="fused FFN launch from 8192 rows", where="tl2.hip tl2_ffn_supported",
@@ -180,10 +180,10 @@ BOUNDARIES = [
     dict(name="fused FFN launch: at most 3 clips per 128-token block (T >= 64)", where="tl2.hip FFN_MAXCLIP, tl3_ffn.hip F3_MAXCLIP",
          side=lambda c: min(127 // c[3] + 2, _inst(c)[2]) <= 3,
          cases=[(S, "bf16", 70, 63), (S, "bf16", 70, 64)]),
-    dict(name="rolling hi/lo kernels: StylizationBlock from 32768 rows, feat_proj.3 from 16384", where="denoiser.hip tl() hl2",
+    dict(name="rolling hi/lo kernels: StylizationBlock from 32768 rows, feat_proj.3 from 16384", where="denoiser.hip kTlRoles hl_rows, tl_family()",
          side=lambda c: _inst(c)[1] >= 32768,
          cases=[(S, "bf16", 510, 64), (S, "bf16", 512, 64), (S, "bf16", 372, 88), (S, "bf16", 374, 88)]),
-    dict(name="rolling hi/lo StylizationBlock: at most 10 clips per 256-token block (T >= 29)", where="denoiser.hip tl() hl2_fits, tl2.hip T2_MAXCLIP",
+    dict(name="rolling hi/lo StylizationBlock: at most 10 clips per 256-token block (T >= 29)", where="denoiser.hip tl_family() hl2_fits, tl2.hip T2_MAXCLIP",
          side=lambda c: min(255 // c[3] + 2, _inst(c)[2]) <= 10,
          cases=[(S, "bf16", 1180, 28), (S, "bf16", 1180, 29)]),
     dict(name="tl2 q|k|v (256-token blocks): N split over grid.y below 128 token blocks, rolling loop from there", where="tl2.hip launch_tl2_linear (mblocks)",
