@@ -119,6 +119,8 @@ SYMBOLS = {
     "dsh_op_gemm": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "dsh_op_gemm_ex": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P] + [C.c_int32] * 11),
     "dsh_op_gemm_f32_pro": (C.c_int, [_P, C.c_int32] + [_P, C.c_int32, C.c_int32] * 4 + [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    "dsh_op_gemm_f32_pro_ex": (C.c_int, [_P, C.c_int32] + [_P, C.c_int32, C.c_int32] * 4 + [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32]),
+    "dsh_op_split_pack_weight": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "dsh_debug_last_tl_variant": (C.c_int32, []),
     "dsh_debug_launch_counts": (C.c_int32, [C.POINTER(C.c_int64), C.c_int32, C.c_int32]),
     "dsh_op_tl_linear": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
@@ -213,7 +215,7 @@ LOSS_HEADER, LOSS_COLS = 8, 7      # the header's loss macros: batch scalars in 
 # (indices 4 and 7 are retired: their kernel forms were removed, the counts stay 0; the names keep the indices fixed)
 LAUNCH_FAMILIES = ("tl1", "tl2_loop", "tl2_roll", "tl2_roll_hl", "tl4", "tls", "ffn_fused", "ffn_fused_sty", "attn_mfma", "attn_rowmajor",
                    "gemm_f32_fewrow", "gemm_f32_tiled", "gemm_f32_pro", "eval_streams", "sample_streams", "sample_graph", "sample_pipe",
-                   "gemv", "gemm_bf16_tiled", "gemm_tile_pick")
+                   "gemv", "gemm_bf16_tiled", "gemm_tile_pick", "gemm_f32_split")
 
 
 def launch_counts(reset: bool = False) -> dict:

@@ -98,7 +98,7 @@ const char* dsh_version(void) { return "diffsheg_hip 0.1 (gfx950)"; }
 int dsh_create(const dsh_model_config* c, void* hip_stream, dsh_ctx** out) {
     API_BEGIN
     DSH_REQUIRE(c && out, "null argument");
-    DSH_REQUIRE(c->precision == DSH_PRECISION_FP32 || c->precision == DSH_PRECISION_BF16, "unknown precision");
+    DSH_REQUIRE(c->precision == DSH_PRECISION_FP32 || c->precision == DSH_PRECISION_BF16 || c->precision == DSH_PRECISION_BF16X3, "unknown precision");
     DSH_REQUIRE(c->dim_pose > 0 && c->expression_dim > 0 && c->style_dim > 0, "dims must be positive");
     int ndev = 0;
     DSH_HIP_CHECK(hipGetDeviceCount(&ndev));
@@ -243,7 +243,7 @@ int dsh_profile_read(dsh_ctx* ctx, double* ms16, int64_t* launches16, double* fl
 int dsh_profile_class_info(const dsh_ctx* ctx, int32_t cls, const char** kernel, const char** role) {
     API_BEGIN
     DSH_REQUIRE(ctx && kernel && role && cls >= 0 && cls < dsh::PROF_NCLASS, "invalid argument");
-    const dsh::ProfClassInfo& i = dsh::prof_class_info(cls, ctx->cfg.precision == 0);
+    const dsh::ProfClassInfo& i = dsh::prof_class_info(cls, ctx->cfg.fp32_storage());
     *kernel = i.kernel; *role = i.role;
     return 0;
     API_END
@@ -529,26 +529,6 @@ int dsh_op_gemm_ex(void* hip_stream, int32_t dtype, const void* A, const void* W
     API_END
 }
 
-int dsh_op_gemm_f32_pro(void* hip_stream, int32_t pro, const float* x0, int32_t ld0, int32_t w0, const float* x1, int32_t ld1, int32_t w1,
-                        const float* x2, int32_t ld2, int32_t w2, const float* x3, int32_t ld3, int32_t w3, int32_t k_real, const float* W,
-                        const float* bias, const float* fc, const float* film, int32_t film_ld, int32_t film_off, int32_t frames, int32_t nb,
-                        const float* R, float* C, int32_t M, int32_t N, int32_t act, const float* stats, int32_t stat_groups, float* stats_out) {
-    API_BEGIN
-    DSH_REQUIRE(w0 > 0 && w0 % 32 == 0 && w1 % 32 == 0 && w2 % 32 == 0 && w3 % 32 == 0 && w1 >= 0 && w2 >= 0 && w3 >= 0, "segment widths must be multiples of 32");
-    dsh::GemmProArgs a{};
-    a.pro = pro;
-    a.seg[0] = x0; a.seg[1] = w1 ? x1 : nullptr; a.seg[2] = w2 ? x2 : nullptr; a.seg[3] = w3 ? x3 : nullptr;
-    a.seg_ld[0] = ld0; a.seg_ld[1] = ld1; a.seg_ld[2] = ld2; a.seg_ld[3] = ld3;
-    a.seg_end[0] = w0 / 32; a.seg_end[1] = a.seg_end[0] + w1 / 32; a.seg_end[2] = a.seg_end[1] + w2 / 32; a.seg_end[3] = a.seg_end[2] + w3 / 32;
-    a.K = 32 * a.seg_end[3]; a.k_real = k_real;
-    a.W = W; a.ldw = a.K; a.bias = bias; a.fc = fc;
-    a.film = film; a.film_ld = film_ld; a.film_off = film_off; a.frames = frames; a.bmod = nb;
-    a.R = R; a.ldr = N; a.C = C; a.ldc = N; a.M = M; a.N = N; a.act = act; a.nt_n = a.nt_m = 0;
-    a.stats = stats; a.stat_groups = stat_groups; a.stat_gs = stat_groups > 0 ? a.K / stat_groups : 0; a.stats_out = stats_out;
-    return dsh::launch_gemm_f32_pro(a, reinterpret_cast<hipStream_t>(hip_stream));
-    API_END
-}
-
 int32_t dsh_debug_last_tl_variant(void) { return dsh::g_tl_last_variant; }
 
 int32_t dsh_debug_launch_counts(int64_t* out, int32_t cap, int32_t reset) {
@@ -624,6 +604,57 @@ int dump_tl_probe(const char* path, const unsigned long long* dev, size_t npb, i
     return 0;
 }
 }  // namespace
+
+int dsh_op_gemm_f32_pro(void* hip_stream, int32_t pro, const float* x0, int32_t ld0, int32_t w0, const float* x1, int32_t ld1, int32_t w1,
+                        const float* x2, int32_t ld2, int32_t w2, const float* x3, int32_t ld3, int32_t w3, int32_t k_real, const float* W,
+                        const float* bias, const float* fc, const float* film, int32_t film_ld, int32_t film_off, int32_t frames, int32_t nb,
+                        const float* R, float* C, int32_t M, int32_t N, int32_t act, const float* stats, int32_t stat_groups, float* stats_out) {
+    return dsh_op_gemm_f32_pro_ex(hip_stream, pro, x0, ld0, w0, x1, ld1, w1, x2, ld2, w2, x3, ld3, w3, k_real, W, bias, fc, film, film_ld, film_off, frames, nb,
+                                  R, C, M, N, act, stats, stat_groups, stats_out, 0);
+}
+
+int dsh_op_split_pack_weight(void* hip_stream, const float* W, int32_t N, int32_t K, void* out) {
+    API_BEGIN
+    return dsh::launch_split_pack_weight(W, N, K, K, reinterpret_cast<uint32_t*>(out), reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_gemm_f32_pro_ex(void* hip_stream, int32_t pro, const float* x0, int32_t ld0, int32_t w0, const float* x1, int32_t ld1, int32_t w1,
+                           const float* x2, int32_t ld2, int32_t w2, const float* x3, int32_t ld3, int32_t w3, int32_t k_real, const float* W,
+                           const float* bias, const float* fc, const float* film, int32_t film_ld, int32_t film_off, int32_t frames, int32_t nb,
+                           const float* R, float* C, int32_t M, int32_t N, int32_t act, const float* stats, int32_t stat_groups, float* stats_out,
+                           int32_t mma) {
+    API_BEGIN
+    const bool packed = mma > 0 && (mma & 64) != 0;          // W is the packed operand already (dsh_op_split_pack_weight)
+    if (mma > 0) mma &= ~64;
+    DSH_REQUIRE(mma == 0 || ((mma & 15) == 1 && (mma >> 4) >= 0 && (mma >> 4) <= 2), "mma: 0 (exact fp32) or 1 (split bf16) + 16 x tile (0 .. 2) [+ 64: W packed]");
+    DSH_REQUIRE(w0 > 0 && w0 % 32 == 0 && w1 % 32 == 0 && w2 % 32 == 0 && w3 % 32 == 0 && w1 >= 0 && w2 >= 0 && w3 >= 0, "segment widths must be multiples of 32");
+    dsh::GemmProArgs a{};
+    a.pro = pro;
+    a.seg[0] = x0; a.seg[1] = w1 ? x1 : nullptr; a.seg[2] = w2 ? x2 : nullptr; a.seg[3] = w3 ? x3 : nullptr;
+    a.seg_ld[0] = ld0; a.seg_ld[1] = ld1; a.seg_ld[2] = ld2; a.seg_ld[3] = ld3;
+    a.seg_end[0] = w0 / 32; a.seg_end[1] = a.seg_end[0] + w1 / 32; a.seg_end[2] = a.seg_end[1] + w2 / 32; a.seg_end[3] = a.seg_end[2] + w3 / 32;
+    a.K = 32 * a.seg_end[3]; a.k_real = k_real;
+    a.W = W; a.ldw = a.K; a.bias = bias; a.fc = fc;
+    a.film = film; a.film_ld = film_ld; a.film_off = film_off; a.frames = frames; a.bmod = nb;
+    a.R = R; a.ldr = N; a.C = C; a.ldc = N; a.M = M; a.N = N; a.act = act; a.nt_n = a.nt_m = 0;
+    a.stats = stats; a.stat_groups = stat_groups; a.stat_gs = stat_groups > 0 ? a.K / stat_groups : 0; a.stats_out = stats_out;
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    if (mma == 0) return dsh::launch_gemm_f32_pro(a, s);
+    // split bf16: the weight is packed into per-call scratch (the denoiser packs once, at finalisation), released after a stream sync
+    DSH_REQUIRE(W && M > 0 && N > 0 && a.K > 0, "gemm_f32_pro: W and positive sizes");
+    a.mma = 1; a.tile = mma >> 4;
+    if (packed) return dsh::launch_gemm_f32_pro(a, s);
+    OpScratch scratch;
+    void* wsp = nullptr;
+    if (int e = scratch.alloc(&wsp, (size_t)N * a.K * 4)) return e;
+    if (int e = dsh::launch_split_pack_weight(W, N, a.K, a.K, reinterpret_cast<uint32_t*>(wsp), s)) return e;
+    a.W = reinterpret_cast<const float*>(wsp);
+    const int rc = dsh::launch_gemm_f32_pro(a, s);
+    DSH_HIP_CHECK(hipStreamSynchronize(s));
+    return rc;
+    API_END
+}
 
 int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W, const float* bias, const float* R,
                      float* Cf, void* Ct, int32_t M, int32_t N, int32_t act, const float* gamma, const float* beta,

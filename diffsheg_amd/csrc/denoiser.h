@@ -19,7 +19,10 @@ struct ModelConfig {
     float cond_scale = 1.25f;      // the context's guidance scale until dsh_set_guidance_scale() changes it (capi.hip)
     int latent_dim = 512, ff_size = 1024, num_layers = 8, num_heads = 8;
     int audio_dim = 128, aud_latent_dim = 256, hubert_dim = 1024, hubert_enc_dim = 128;
-    int precision = 0;   // 0 = fp32 (exact-fp32 MFMA), 1 = bf16 storage + bf16 MFMA, fp32 accumulate
+    int precision = 0;   // 0 = fp32 (exact-fp32 MFMA), 1 = bf16 storage + bf16 MFMA, fp32 accumulate, 2 = fp32 storage with the large Linears on the
+                         // split-bf16 main loop (gemm_f32_split.hip; everything else is precision 0's)
+    bool fp32_storage() const { return precision == 0 || precision == 2; }
+    bool split_linears() const { return precision == 2; }
     // 1: the model is ONE MotionTransformer over all dim_pose + expression_dim channels (runner.py:46-57, opt.unidiffuser =
     // False, model_base transformer_encoder): no encoder_aud, audio_proj on the 128 mel features, no expression -> gesture flow
     int single_transformer = 0;

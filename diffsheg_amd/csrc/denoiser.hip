@@ -138,6 +138,8 @@ class Denoiser final : public DenoiserInstance {
         float* fd = nullptr;             //   when a LayerNorm precedes the Linear it is folded in: wf = gamma (.) W, fd[n] = b[n] +
         float* fc = nullptr;             //   sum_k beta[k] W[n][k], fc[n] = sum_k wf[n][k]  (tl2.hip, PRO 1 / 3)
         float* wfold = nullptr;          // fp32 parity path (gemm_f32_pro.hip): [N, Kp] = gamma (.) W, with fd / fc as above in natural feature order
+        uint32_t* wsp = nullptr;         // split-bf16 Linears (cfg.split_linears()): w and wfold packed into hi / lo bf16 pieces, once, at
+        uint32_t* wsp_fold = nullptr;    //   finalisation (launch_split_pack_weight), [N, Kp] 32-bit words each
     };
     struct LNp { float* g = nullptr; float* b = nullptr; int D = 0; };
     struct Sty { LNp ln; Lin out; };
@@ -268,6 +270,24 @@ class Denoiser final : public DenoiserInstance {
             if (int e = upload(&L.fc, fc.data(), N)) return e;
             if (int e = upload(&L.fd, fd.data(), N)) return e;
         }
+        if (sizeof(T) == 4 && cfg.split_linears()) {
+            // from the fp32 DEVICE weights, on this instance's stream (finalize() waits for it)
+            if (int e = split_pack(&L.wsp, reinterpret_cast<const float*>(L.w), N, L.Kp)) return e;
+            if (L.wfold) { if (int e = split_pack(&L.wsp_fold, L.wfold, N, L.Kp)) return e; }
+        }
+        return 0;
+    }
+    int split_pack(uint32_t** dst, const float* src, int N, int Kp) {
+        if (int e = dalloc(dst, (size_t)N * Kp, allocs)) return e;
+        wbytes += (size_t)N * Kp * sizeof(uint32_t);
+        return launch_split_pack_weight(src, N, Kp, Kp, *dst, st);
+    }
+    // W operand and main loop of a gemm_f32_pro launch: the packed pieces on the split-bf16 loop when the model asks for it
+    int pick_mma(GemmProArgs& a, const Lin& L, bool folded) const {
+        if (!cfg.split_linears()) return 0;
+        const uint32_t* sp = folded ? L.wsp_fold : L.wsp;
+        DSH_REQUIRE(sp, "split-bf16 Linear without its packed weight");      // (no quiet fall-back to the exact loop)
+        a.W = reinterpret_cast<const float*>(sp); a.mma = 1;
         return 0;
     }
     // the same Linear as the operand of the token-per-lane kernels (bf16 only; K = 512, or up to 1024 zero padded): what tl_pack_linear
@@ -341,7 +361,8 @@ class Denoiser final : public DenoiserInstance {
             GemmProArgs q = one_seg(reinterpret_cast<const float*>(A), lda, L.Kp);
             q.pro = 0; q.k_real = L.Kp; q.K = L.Kp; q.W = reinterpret_cast<const float*>(L.w); q.ldw = L.Kp; q.bias = L.b; q.R = R; q.ldr = ldr;
             q.C = Cf ? Cf : reinterpret_cast<float*>(Ct); q.ldc = Cf ? ldcf : ldct; q.M = M; q.N = L.N; q.act = act; q.frames = 1; q.bmod = 1;
-            rc = launch_gemm_f32_pro(q, st);
+            rc = pick_mma(q, L, false);
+            if (!rc) rc = launch_gemm_f32_pro(q, st);
         } else rc = launch_gemm<T>(a, st);
         if (prof) prof->end(fl);
         return rc;
@@ -360,7 +381,8 @@ class Denoiser final : public DenoiserInstance {
         const double fl = 2.0 * M * (double)L.N * L.K;
         flops_acc += fl;
         if (prof) prof->begin(PROF_GEMM);
-        const int rc = launch_gemm_f32_pro(a, st);
+        int rc = pick_mma(a, L, pro == 1);
+        if (!rc) rc = launch_gemm_f32_pro(a, st);
         if (prof) prof->end(fl);
         return rc;
     }
@@ -740,6 +762,7 @@ int Denoiser<T>::finalize(const std::map<std::string, HostTensor>& w) {
     const int Pexp = D + cfg.aud_latent_dim + cfg.hubert_enc_dim;
     if (int e = encoder_from(w, "encoder_exp", exp_, cfg.expression_dim, Pexp, 2 * DA)) return e;
     if (int e = encoder_from(w, "encoder_ges", ges_, cfg.dim_pose, Pexp + cfg.expression_dim, 2 * DA)) return e;
+    if (cfg.split_linears()) DSH_HIP_CHECK(hipStreamSynchronize(st));   // the packed weights (split_pack) are read by instances on other streams
     finalized = true;
     return 0;
 }
@@ -1298,7 +1321,7 @@ int Denoiser<T>::debug_copy(const std::string& what, float* out) {
 }  // namespace
 
 DenoiserInstance* make_denoiser_instance(const ModelConfig& cfg, hipStream_t stream) {
-    if (cfg.precision == 0) return new Denoiser<float>(cfg, stream);
+    if (cfg.fp32_storage()) return new Denoiser<float>(cfg, stream);   // (precision 2: cfg.split_linears())
     if (cfg.precision == 1) return new Denoiser<bf16>(cfg, stream);
     return nullptr;
 }

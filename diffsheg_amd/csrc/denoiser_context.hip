@@ -22,7 +22,7 @@ class Context final : public DenoiserContext {
         // second stream's launches fill the partial last rounds (+1.5 % measured); bf16: from 12288 rows (want_split)
         // fp32 path: two streams from 4096 rows, three from 8700 (the 256-clip BEAT batch of configs[1]: 8704 rows = 17 x 512, every
         // Linear a 1.06 / 2.1 / 3.2-round launch of 64 x 64 tiles whose tail another sub-batch fills; measured 24.8 k -> 25.1 k frames/s)
-        if (c.precision == 0) { min_rows_ = 4096; rows_per_stream_ = 2900; }
+        if (c.fp32_storage()) { min_rows_ = 4096; rows_per_stream_ = 2900; }
         if (const long rs = switch_positive(SW_DUAL_ROWS)) rows_per_stream_ = (size_t)rs;
         if (const long mr = switch_positive(SW_DUAL_MIN_ROWS)) min_rows_ = (size_t)mr;
         pipe_rows_ = pipe_rows_context();

@@ -31,9 +31,16 @@ struct GemmProArgs {
     const float* stats; int stat_groups, stat_gs;   // pro 2, nullable: moments of the INPUT rows left by its producer (no pass over the rows here)
     float* stats_out;                   // nullable: moments of the OUTPUT rows in groups of 32 columns ([M][N / 32] float2; N % 64 == 0)
     const float* row_const; int n_const_rows;   // epilogue: + row_const[n] on rows < n_const_rows, after the residual (the CFG-null constant of the next layer)
+    int mma;                            // 0: exact fp32 MFMA (gemm_f32_pro.hip); 1: split bf16, three bf16 MFMAs per product (gemm_f32_split.hip) — W is then the
+                                        //    operand PACKED by launch_split_pack_weight, same shape and row stride
+    int tile;                           // mma 1: 0 the launcher picks; 1 / 2: 64 x 64 / 128 x 128 tiles (the bits do not depend on it)
     int abl;                            // ablation bits (DSH_GP_ABL, bench only; results are garbage): 1 no global loads in the loop, 2 no LDS writes, 4 no fragment reads, 8 no MFMAs, 16 no barrier
 };
 int launch_gemm_f32_pro(const GemmProArgs& a, hipStream_t s);
+// split-bf16 form of the same launches (gemm_f32_split.hip).  The one packer of its W operand: [N][ldw] fp32 with K whole 32-float tiles -> per K
+// tile [hi(32 bf16) | lo(32 bf16)], hi = RNE_bf16(w), lo = RNE_bf16(w - hi), in `out` ([N][ldw] 32-bit words).  Once per weight, never per launch.
+int launch_split_pack_weight(const float* W, int N, int K, int ldw, uint32_t* out, hipStream_t s);
+int launch_gemm_f32_split(const GemmProArgs& a, hipStream_t s);   // (through launch_gemm_f32_pro with a.mma = 1)
 
 // bf16 HuBERT layers: C = act(pro(A) W^T + bias) (+ R) on the bf16 matrix pipe (gemm_bf16_pro.hip).  M >= 1, K % 64 == 0, N % 64 == 0.
 struct GemmBf16ProArgs {

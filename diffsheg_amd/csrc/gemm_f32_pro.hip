@@ -575,6 +575,8 @@ int launch_gemm_f32_pro(const GemmProArgs& a, hipStream_t s) {
     if (a.pro == 1) DSH_REQUIRE(a.fc && ((uintptr_t)a.fc % 16) == 0, "gemm_f32_pro: folded LayerNorm needs the weight row sums");
     if (a.pro == 2) DSH_REQUIRE(a.film && a.k_real == a.K && a.frames > 0 && a.bmod > 0 && a.film_ld % 4 == 0 && a.film_off % 4 == 0 && ((uintptr_t)a.film % 16) == 0,
                                 "gemm_f32_pro: StylizationBlock front needs the folded FiLM table");
+    DSH_REQUIRE(a.mma == 0 || a.mma == 1, "gemm_f32_pro: mma 0 (exact fp32) or 1 (split bf16)");
+    if (a.mma == 1) return launch_gemm_f32_split(a, s);     // (W packed by launch_split_pack_weight; gemm_f32_split.hip)
     typedef void (*kern_t)(GemmProArgs);
     static const kern_t kerns[2][3] = {{gemm_f32_pro_kernel<0, false>, gemm_f32_pro_kernel<1, false>, gemm_f32_pro_kernel<2, false>},
                                        {gemm_f32_pro_kernel<0, true>, gemm_f32_pro_kernel<1, true>, gemm_f32_pro_kernel<2, true>}};

@@ -22,7 +22,9 @@ from . import _lib
 from .config import DiffSHEGConfig
 from .weights import strip_ddp_prefix, validate_state_dict
 
-_PRECISION = {"fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
+# "bf16x3": the fp32 path with its large Linears as three bf16 MFMAs per product (precision 2 of the C header); bit-identical to "fp32" at or below
+# the few-row threshold (512 token rows), so a single clip gains nothing
+_PRECISION = {"fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "bf16x3": 2}
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:

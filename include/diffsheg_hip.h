@@ -31,7 +31,10 @@ extern "C" {
 
 typedef struct dsh_ctx dsh_ctx;
 
-enum { DSH_PRECISION_FP32 = 0, DSH_PRECISION_BF16 = 1 };
+/* DSH_PRECISION_BF16X3: the fp32 path (fp32 storage, row kernels, attention core, sampler) with its large Linears (gemm_f32_pro) formed as three
+ * bf16 MFMAs per product on hi / lo bf16 pieces of both operands (gemm_f32_split.hip): ~2^-16 relative per product instead of fp32's 2^-24.  At or
+ * below the few-row threshold (DSH_GEMM_KSPLIT, 512 token rows) it launches the very kernels of DSH_PRECISION_FP32 and is bit-identical to it. */
+enum { DSH_PRECISION_FP32 = 0, DSH_PRECISION_BF16 = 1, DSH_PRECISION_BF16X3 = 2 };
 enum { DSH_SAMPLER_DDIM = 0, DSH_SAMPLER_DDPM = 1 };
 enum { DSH_NOISE_STACK = 0, DSH_NOISE_PHILOX = 1 };
 
@@ -411,6 +414,20 @@ int dsh_op_gemm_f32_pro(void* hip_stream, int32_t pro, const float* x0, int32_t 
                         const float* x2, int32_t ld2, int32_t w2, const float* x3, int32_t ld3, int32_t w3, int32_t k_real, const float* W,
                         const float* bias, const float* fc, const float* film, int32_t film_ld, int32_t film_off, int32_t frames, int32_t nb,
                         const float* R, float* C, int32_t M, int32_t N, int32_t act, const float* stats, int32_t stat_groups, float* stats_out);
+/* The same launch with the main loop chosen: mma 0 = dsh_op_gemm_f32_pro (exact-fp32 MFMA), bit for bit; mma 1 = the split-bf16 loop of
+ * DSH_PRECISION_BF16X3 (gemm_f32_split.hip): W (fp32, as above) is packed into hi / lo bf16 pieces in per-call scratch, the rows are split in the
+ * launch's staging registers; pro 1 subtracts the mean of the row's first 32 columns before the split.  mma 1 + 16 t forces the split loop's
+ * tile (t = 1: 64 x 64, t = 2: 128 x 128; the bits do not depend on it).  The split loop does not carry the row-moment side channel: stats and
+ * stats_out must be null with mma 1.  + 64 (measurements): W is the packed operand already, as dsh_op_split_pack_weight left it - the call is
+ * then the launch alone, without scratch and without a synchronisation, which is how the model issues it. */
+/* The split loop's one weight packer: W fp32 [N, K] row-major (K a multiple of 32) -> out, N x K 32-bit words (16-byte aligned): per K tile of
+ * 32 columns the 32 hi pieces, then the 32 lo pieces, hi = RNE_bf16(w), lo = RNE_bf16(w - hi).  Enqueued on the stream. */
+int dsh_op_split_pack_weight(void* hip_stream, const float* W, int32_t N, int32_t K, void* out);
+int dsh_op_gemm_f32_pro_ex(void* hip_stream, int32_t pro, const float* x0, int32_t ld0, int32_t w0, const float* x1, int32_t ld1, int32_t w1,
+                           const float* x2, int32_t ld2, int32_t w2, const float* x3, int32_t ld3, int32_t w3, int32_t k_real, const float* W,
+                           const float* bias, const float* fc, const float* film, int32_t film_ld, int32_t film_off, int32_t frames, int32_t nb,
+                           const float* R, float* C, int32_t M, int32_t N, int32_t act, const float* stats, int32_t stat_groups, float* stats_out,
+                           int32_t mma);
 /* Token-per-lane fused Linear (bf16, K = 512 or 1024): out = act(prologue(X) W^T + bias) (+ R).  X bf16 [M,K]
  * with M padded to a multiple of 128 rows, W bf16 [N,K] in natural k order (permuted internally into a scratch
  * copy), pro 0 plain / 1 LayerNorm / 2 LayerNorm+FiLM+SiLU with film [nb, 2K] = (scale | shift) per sample,
@@ -429,13 +446,14 @@ int32_t dsh_debug_last_tl_variant(void);
  *    3 tl2 rolling loop on hi / lo planes  4 retired, always 0                   5 tl_small (window chain)
  *    6 fused FFN launch (tl3_ffn / tl2_ffn)            7 retired, always 0
  *    8 bf16 layers: MFMA tiled attention               9 bf16 layers: row-major attention fallback (windows of more than 96 frames)
- *   10 fp32 few-row (K-split) GEMM        11 fp32 tiled GEMM                    12 gemm_f32_pro
+ *   10 fp32 few-row (K-split) GEMM        11 fp32 tiled GEMM                    12 gemm_f32_pro (exact-fp32 main loop only)
  *  and four VALUES rather than counts: 13 sub-batch streams of the last dsh_eval, 14 sub-batch streams of the last dsh_sample,
  *   15 whether the last dsh_sample replayed captured graphs, 16 whether it ran the two-encoder pipeline;
  *  two more counts: 17 weight-streaming GEMV (at most 16 rows, fp32 and bf16), 18 bf16 tiled GEMM;
  *  and one more value: 19 tile shape of the last tiled GEMM launch (0 128 x 128, 1 128 x 64, 2 64 x 64, 3 64 x 32, 4 the unswizzled
- *   128 x 128 form of DSH_GEMM_VARIANT=0). */
-#define DSH_LAUNCH_COUNT_ENTRIES 20
+ *   128 x 128 form of DSH_GEMM_VARIANT=0);
+ *  and one more count: 20 gemm_f32_pro split-bf16 launches (DSH_PRECISION_BF16X3, dsh_op_gemm_f32_pro_ex with mma 1). */
+#define DSH_LAUNCH_COUNT_ENTRIES 21
 int32_t dsh_debug_launch_counts(int64_t* out, int32_t cap, int32_t reset);
 int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W, const float* bias, const float* R,
                      float* Cf, void* Ct, int32_t M, int32_t N, int32_t act, const float* gamma, const float* beta,
