@@ -44,17 +44,34 @@ class RunSpecC(C.Structure):
                 ("invert_from", C.c_int32), ("invert_to", C.c_int32), ("x", C.c_void_p), ("gt", C.c_void_p), ("mask", C.c_void_p),
                 ("noise_stack", C.c_void_p), ("n_draws", C.c_int64), ("trace", C.c_void_p),
                 ("timesteps", C.POINTER(C.c_int32)), ("n_timesteps", C.c_int32), ("tail_blend", C.c_int32),
-                ("row_keys", C.POINTER(C.c_uint64)), ("row_seeds", C.POINTER(C.c_uint64)), ("n_rows", C.c_int32), ("solver", C.c_int32)]
+                ("row_keys", C.POINTER(C.c_uint64)), ("row_seeds", C.POINTER(C.c_uint64)), ("n_rows", C.c_int32), ("solver", C.c_int32),
+                ("guidance", C.c_int32), ("guide_space", C.c_int32), ("n_guide_scale", C.c_int32),
+                ("guide_batch", C.c_int32), ("guide_frames", C.c_int32), ("guide_channels", C.c_int32),
+                ("guide_target", C.c_void_p), ("guide_weight", C.c_void_p), ("guide_vel", C.c_void_p), ("guide_acc", C.c_void_p),
+                ("guide_scale", C.POINTER(C.c_float))]
 
 
-def run_spec(timesteps=(), row_keys=(), row_seeds=(), **fields) -> RunSpecC:
-    """A zeroed dsh_run_spec of this binding's size with ``fields`` set; the three host arrays are copied and kept alive by the result."""
+class GuideC(C.Structure):
+    """dsh_guide: the guidance terms of one op-level launch."""
+    _fields_ = [("target", C.c_void_p), ("weight", C.c_void_p), ("vel", C.c_void_p), ("acc", C.c_void_p),
+                ("lens_dev", C.c_void_p), ("lens_host", C.POINTER(C.c_int32)), ("scale", C.c_float), ("space", C.c_int32)]
+
+
+GUIDE_SPACES = {"x_t": 0, "x0": 1}      # the header's two guide-space values
+
+
+def run_spec(timesteps=(), row_keys=(), row_seeds=(), guide_scale=(), **fields) -> RunSpecC:
+    """A zeroed dsh_run_spec of this binding's size with ``fields`` set; the host arrays are copied and kept alive by the result."""
     s = RunSpecC(struct_size=C.sizeof(RunSpecC), **fields)
     kept, keys = [int(v) for v in timesteps], [int(v) & 0xFFFFFFFFFFFFFFFF for v in row_keys]
     seeds = [int(v) & 0xFFFFFFFFFFFFFFFF for v in row_seeds]
     if seeds and len(seeds) != len(keys):               # (the library reads n_rows entries of both)
         raise ValueError(f"row_seeds needs row_keys and one seed per key ({len(keys)}), got {len(seeds)}")
-    s._arrays = ((C.c_int32 * len(kept))(*kept), (C.c_uint64 * len(keys))(*keys), (C.c_uint64 * len(seeds))(*seeds))
+    scales = [float(v) for v in guide_scale]
+    s._arrays = ((C.c_int32 * len(kept))(*kept), (C.c_uint64 * len(keys))(*keys), (C.c_uint64 * len(seeds))(*seeds),
+                 (C.c_float * len(scales))(*scales))
+    if scales:
+        s.guide_scale, s.n_guide_scale = s._arrays[3], len(scales)
     if kept:
         s.timesteps, s.n_timesteps = s._arrays[0], len(kept)
     if keys:
@@ -148,6 +165,9 @@ SYMBOLS = {
     "dsh_op_chain_save_tail": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P, C.POINTER(C.c_int32), _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     "dsh_op_ddim_step_full": (C.c_int, [_P] * 10 + [C.c_int32] * 3 + [C.c_float] * 6 + [C.c_int32] * 6),
     "dsh_op_ddpm_step": (C.c_int, [_P] * 5 + [C.c_int64] + [C.c_float] * 5 + [C.c_int32] * 4),
+    "dsh_op_guidance_grad": (C.c_int, [_P, _P, _P] + [C.c_int32] * 5 + [C.POINTER(GuideC)]),
+    "dsh_op_guided_ddim_step": (C.c_int, [_P] * 8 + [C.POINTER(GuideC)] + [C.c_int32] * 3 + [C.c_float] * 10 + [C.c_int32] * 7),
+    "dsh_op_guided_ddpm_step": (C.c_int, [_P] * 5 + [C.POINTER(GuideC)] + [C.c_int32] * 3 + [C.c_float] * 6 + [C.c_int32] * 3),
     "dsh_op_undo_step": (C.c_int, [_P, _P, _P, C.c_float, C.c_float, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "dsh_op_level_copy": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, _P, C.c_int64, _P, C.c_int32]),
     "dsh_op_fill_step": (C.c_int, [_P] * 5 + [C.c_int64, C.c_float, C.c_float, C.c_int64, C.c_int32]),

@@ -280,6 +280,13 @@ static int to_spec(const dsh_sampler_opts* opts, const dsh_run_spec* c, dsh::Run
     s.solver = f.solver; s.tail_blend = f.tail_blend != 0;
     s.row_keys.assign(f.row_keys, f.row_keys + f.n_rows);
     if (f.row_seeds) s.row_seeds.assign(f.row_seeds, f.row_seeds + f.n_rows);
+    if (f.guidance) {
+        DSH_REQUIRE(f.n_guide_scale >= 0 && (f.n_guide_scale == 0 || f.guide_scale), "dsh_run_spec: null guidance scale array");
+        dsh::Guidance& g = s.guide;
+        g.on = true; g.target = f.guide_target; g.weight = f.guide_weight; g.vel = f.guide_vel; g.acc = f.guide_acc; g.space = f.guide_space;
+        g.batch = f.guide_batch; g.frames = f.guide_frames; g.channels = f.guide_channels;
+        g.level_scale.assign(f.guide_scale, f.guide_scale + f.n_guide_scale);
+    }
     return 0;
 }
 
@@ -1371,6 +1378,60 @@ int dsh_op_ddpm_step(void* hip_stream, float* x, const float* eps, const float* 
     a.x = x; a.eps = eps; a.noise = noise; a.x0_out = x0_out; a.c1 = c1; a.c2 = c2; a.coef1 = coef1; a.coef2 = coef2; a.sigma = sigma;
     a.clip = clip; a.n = (size_t)n; a.channels = channels; a.c_lo = c_lo; a.c_hi = c_hi;
     return dsh::launch_ddpm_step(a, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+// dsh_guide -> dsh::GuideArgs, with the per-clip lengths checked on the host before any address is formed from them
+static int guide_args(const std::string& what, const dsh_guide* g, int32_t B, int32_t frames, dsh::GuideArgs& ga) {
+    DSH_REQUIRE(g, what + ": null guide");
+    DSH_REQUIRE((g->lens_dev == nullptr) == (g->lens_host == nullptr), what + ": per-clip lengths need the host and the device copy");
+    for (int b = 0; g->lens_host && b < B; ++b)
+        DSH_REQUIRE(g->lens_host[b] >= 1 && g->lens_host[b] <= frames, what + ": a clip length outside 1 .. frames");
+    ga.target = g->target; ga.weight = g->weight; ga.vel = g->vel; ga.acc = g->acc; ga.lens = g->lens_dev; ga.scale = g->scale; ga.space = g->space;
+    return 0;
+}
+
+int dsh_op_guidance_grad(void* hip_stream, const float* z, float* g, int32_t B, int32_t frames, int32_t channels, int32_t c_lo, int32_t c_hi,
+                         const dsh_guide* guide) {
+    API_BEGIN
+    DSH_REQUIRE(z && g && B > 0 && frames > 0 && channels > 0, "invalid argument");
+    dsh::GuideArgs ga;
+    if (int e = guide_args("guidance_grad", guide, B, frames, ga)) return e;
+    ga.space = dsh::GUIDE_XT;
+    return dsh::launch_guidance_grad(z, g, B, frames, channels, c_lo, c_hi, ga, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_guided_ddim_step(void* hip_stream, float* x, const float* eps, float* x0_out, const float* gt, const uint8_t* mask, const float* noise2,
+                            const float* noise1, const dsh_guide* guide, int32_t B, int32_t frames, int32_t channels, float c1, float c2,
+                            float sqrt_ab_prev, float sqrt_1m_ab_prev, float coef_eps, float sigma, float sqrt_1m_ab, float A, float Bc, float G,
+                            int32_t second_order, int32_t overlap_len, int32_t blend, int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi) {
+    API_BEGIN
+    dsh::DdimStepArgs a;
+    if (int e = step_args("guided_ddim_step", a, x, eps, x0_out, gt, mask, noise2, B, frames, channels, c1, c2, sqrt_ab_prev, sqrt_1m_ab_prev,
+                          overlap_len, blend, tail_blend, clip, c_lo, c_hi)) return e;
+    dsh::GuideArgs ga;
+    if (int e = guide_args("guided_ddim_step", guide, B, frames, ga)) return e;
+    ga.sqrt_1m_ab = sqrt_1m_ab;
+    if (second_order) { a.second = 1; a.A = A; a.Bc = Bc; a.G = G; }
+    else { a.coef_eps = coef_eps; a.sigma = sigma; a.noise1 = noise1; }
+    return dsh::launch_guided_ddim_step(a, ga, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_guided_ddpm_step(void* hip_stream, float* x, const float* eps, const float* noise, float* x0_out, const dsh_guide* guide, int32_t B,
+                            int32_t frames, int32_t channels, float c1, float c2, float coef1, float coef2, float sigma, float post_var,
+                            int32_t clip, int32_t c_lo, int32_t c_hi) {
+    API_BEGIN
+    DSH_REQUIRE(x && eps && noise && B > 0 && frames > 0 && channels > 0, "invalid argument");
+    DSH_REQUIRE(c_lo >= 0 && c_hi <= channels, "guided_ddpm_step: channel range outside [0, channels]");
+    dsh::GuideArgs ga;
+    if (int e = guide_args("guided_ddpm_step", guide, B, frames, ga)) return e;
+    ga.post_var = post_var;
+    dsh::DdpmStepArgs a;
+    a.x = x; a.eps = eps; a.noise = noise; a.x0_out = x0_out; a.c1 = c1; a.c2 = c2; a.coef1 = coef1; a.coef2 = coef2; a.sigma = sigma;
+    a.clip = clip; a.n = (size_t)B * frames * channels; a.channels = channels; a.c_lo = c_lo; a.c_hi = c_hi;
+    return dsh::launch_guided_ddpm_step(a, frames, ga, reinterpret_cast<hipStream_t>(hip_stream));
     API_END
 }
 

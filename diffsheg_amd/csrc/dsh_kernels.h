@@ -280,6 +280,29 @@ struct DdpmStepArgs {
     int channels = 0, c_lo = 0, c_hi = 0;   // channel range of the update (c_hi <= c_lo: all), as DdimStepArgs
 };
 int launch_ddpm_step(const DdpmStepArgs& a, hipStream_t s);
+// ---- soft constraints while sampling: per column c of clip b with L = lens[b] frames (frames if null), on the signal z,
+//   log p = -1/2 sum_t W (z[t] - Y)^2  - 1/2 vel[c] sum_{t=0..L-2} (z[t+1] - z[t])^2  - 1/2 acc[c] sum_{t=1..L-2} (z[t+1] - 2 z[t] + z[t-1])^2
+//   g[t]  = scale * d log p / d z[t]      (a five-point stencil; 0 at frames >= L)
+// Every term is local to its column: the column ranges of the step launches and the two encoders' chains keep working.
+struct GuideArgs {
+    const float* target = nullptr;   // Y [n], addressed like x; null: 0
+    const float* weight = nullptr;   // W [n] >= 0, addressed like x; null: no attraction term
+    const float* vel = nullptr;      // [channels] or null
+    const float* acc = nullptr;      // [channels] or null
+    const int* lens = nullptr;       // [B] per-clip frame counts (ragged batch) or null; the guided launches leave frames >= lens[b] unwritten
+    float scale = 1.f;               // s_k of the step's spaced level
+    int space = 0;                   // GUIDE_XT: z = the noisy sample (the reference's cond_fn(x, t)); GUIDE_X0: z = the step's pred_xstart
+    float sqrt_1m_ab = 0.f;          // DDIM (condition_score, gaussian_diffusion.py:670-673): sqrt_f32(1 - f32(abar))
+    float post_var = 0.f;            // DDPM (condition_mean, :654-657): f32(posterior_variance)
+};
+enum GuideSpace { GUIDE_XT = 0, GUIDE_X0 = 1 };
+// g[b, t, c] for the columns [c_lo, c_hi) (0 / 0: all) of z [B, frames, channels]; other columns of g are not written
+int launch_guidance_grad(const float* z, float* g, int B, int frames, int channels, int c_lo, int c_hi, const GuideArgs& ga, hipStream_t s);
+// The guided forms of the two steps, each one pass.  DDIM (also a.second): x0 as in launch_ddim_step (clipped when a.clip), e = (c1 x - x0) / c2,
+// e' = e - sqrt_1m_ab g, x0' = c1 x - c2 e', then the parent's update from x0' (eta term, x0_out / history, RePaint select, saved tails).
+// DDPM: mean' = mean + post_var g.  a.n must be B * frames * channels (whole clips: the stencil walks a clip's frames).
+int launch_guided_ddim_step(const DdimStepArgs& a, const GuideArgs& ga, hipStream_t s);
+int launch_guided_ddpm_step(const DdpmStepArgs& a, int frames, const GuideArgs& ga, hipStream_t s);
 int launch_fill_i64(int64_t* p, int64_t v, size_t n, hipStream_t s);
 // p[0, n) = host[0, n) in stream order (values passed as launch arguments: the host array may be reused at once, no sync)
 int launch_store_values_f32(float* p, const float* host, int n, hipStream_t s);

@@ -63,6 +63,18 @@ struct SamplerStep { StepKind kind; int level; };
 //                steps' randn_like, the RePaint blend's gt noise, the undo steps, the eta scratch; main chain and gesture-side twin alike),
 //                so rows of one batch may stand at different windows of their chains
 //   trace        (nullable) [steps, n]: the sample after every step
+//   guide        soft constraints: every denoise step of the forward loops is the guided form of its kernel
+//                (sampler_kernels.hip); undo steps, draws and the evaluations are untouched.  Not for the reverse loop.
+// The guidance of a run: target / weight [B, T, C] and vel / acc [C] on the device (each may be null), stated with the shape the caller
+// built them for (check_run() compares it with the context's); level_scale: one factor per spaced level of the run (DDIM: respacing, DDPM:
+// diffusion_steps entries; empty: 1 everywhere).  A level whose factor is 0 runs the unguided kernel.
+struct Guidance {
+    bool on = false;
+    const float *target = nullptr, *weight = nullptr, *vel = nullptr, *acc = nullptr;
+    int space = 0;                       // GuideSpace (dsh_kernels.h)
+    int batch = 0, frames = 0, channels = 0;
+    std::vector<float> level_scale;
+};
 struct RunSpec {
     SamplerOpts o;
     int init = 0;
@@ -74,6 +86,7 @@ struct RunSpec {
     int solver = SOLVER_DDIM;
     bool tail_blend = false;
     std::vector<uint64_t> row_keys, row_seeds;
+    Guidance guide;
 };
 // what check_run() needs of the conditioned context (lengths: the ragged batch's per-clip frame counts on the host, or null)
 struct RunShape { int batch, frames, channels, gesture_cols, modality; const int32_t* lengths; };
@@ -135,6 +148,7 @@ class Sampler {
     int update(Run& r, const Chain& c, const StepConsts& sc);
     int ddim_update(Run& r, const Chain& c, const StepConsts& sc);
     int ddpm_update(Run& r, const Chain& c, const StepConsts& sc);
+    bool guide_for(const Run& r, const Chain& c, const StepConsts& sc, GuideArgs& g) const;
     static void drop_graphs(ChainBufs& b);
     void drop_graph();                     // every chain's
     bool replayed() const { return bufs[0].graph_exec[0] || bufs[0].graph_exec[1] || bufs[0].graph_exec[2]; }

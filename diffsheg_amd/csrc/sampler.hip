@@ -179,6 +179,14 @@ int check_run(const RunSpec& s, const RunShape* sh, std::string& err) {
     }
     RUN_REQUIRE(!(s.tail_blend && son), "tail_blend with same_overlap_noisy: the saved noisy tails describe a window chain, not a window pinned at both ends");
     RUN_REQUIRE(s.row_seeds.empty() || s.row_seeds.size() == s.row_keys.size(), "row seeds need the row keys, and one seed per row key");
+    // soft constraints
+    const Guidance& gd = s.guide;
+    if (gd.on) {
+        RUN_REQUIRE(!reverse, "guidance does not apply to the reverse loop (DDIM inversion)");
+        RUN_REQUIRE(gd.space == GUIDE_XT || gd.space == GUIDE_X0, "unknown guidance space (0 x_t, 1 x0)");
+        RUN_REQUIRE(gd.level_scale.empty() || (int64_t)gd.level_scale.size() == (o.kind == 1 ? o.diffusion_steps : o.respacing),
+                    "guidance: the level scales need one entry per level of the run (DDIM: respacing, DDPM: diffusion_steps)");
+    }
     if (!sh) return 0;
     // what depends on the conditioned context
     RUN_REQUIRE(s.x != nullptr, "null sample buffer");
@@ -195,6 +203,11 @@ int check_run(const RunSpec& s, const RunShape* sh, std::string& err) {
                     "row keys were set for a different batch size (or frames*channels is not a multiple of 4)");
         for (int b = 0; sh->lengths && b < sh->batch; ++b)
             RUN_REQUIRE(((int64_t)sh->lengths[b] * sh->channels) % 4 == 0, "row keys on a ragged batch: length * channels must be a multiple of 4 for every clip");
+    }
+    if (gd.on) {
+        RUN_REQUIRE(!(gd.target || gd.weight) || (gd.batch == sh->batch && gd.frames == sh->frames && gd.channels == sh->channels),
+                    "guidance: target / weight were built for a different [batch, frames, channels] than the condition's");
+        RUN_REQUIRE(!(gd.vel || gd.acc) || gd.channels == sh->channels, "guidance: vel / acc were built for a different channel count than the condition's");
     }
     return 0;
 #undef RUN_REQUIRE
@@ -263,6 +276,7 @@ struct Sampler::Run {
     size_t pf_next = 0;                                  // order[0 .. pf_next) have been handed to the prefetch stream
     int64_t draw = 0, step_idx = 0; int n_eval = 0;
     bool dpm = false; int last_ddim_level = -1;          // SOLVER_DPM2M; level of the previous executed step if it was a DDIM step, else -1
+    const Guidance* guide = nullptr;                     // soft constraints of the run (null: none)
     int64_t next_draw() { return draw++; }               // draw index: advanced once per draw, whatever the regime
 };
 
@@ -283,6 +297,7 @@ struct Sampler::StepConsts {
     int64_t idx, idx2;                                   // draws: the step's own N(0,1) (undo / DDPM noise, DDIM randn_like); the noised gt's (-1: none)
     float undo_a, undo_b, coef1, coef2;                  // undo step; DDPM step (with sigma)
     float sqrt_ab_prev, sqrt_1m_ab_prev, coef_eps, sigma;
+    float sqrt_1m_ab = 0.f, post_var = 0.f;              // guided steps: sqrt(1 - abar) (condition_score), the posterior variance (condition_mean)
     bool second = false; float sA = 0.f, sBc = 0.f, sG = 0.f;      // SOLVER_DPM2M: a second-order step and its coefficients
 };
 
@@ -539,6 +554,8 @@ Sampler::StepConsts Sampler::step_consts(Run& r, const SamplerStep& sp) {
         return sc;
     }
     sc.idx = r.next_draw();                                         // DDIM: randn_like of the step, times sigma (= 0 at eta = 0: drawn index, unused values)
+    // (fp32 like the reference's gathered tensors: (1 - alpha_bar).sqrt() and p_mean_variance's "variance", gaussian_diffusion.py:670-673, :576)
+    sc.sqrt_1m_ab = sqrtf(1.0f - (float)tb.ac[k]); sc.post_var = (float)tb.post_var[k];
     if (sp.kind == STEP_DDPM) {
         sc.coef1 = (float)tb.coef1[k]; sc.coef2 = (float)tb.coef2[k];
         sc.sigma = k == 0 ? 0.0f : expf(0.5f * (float)tb.post_logvar[k]);
@@ -642,7 +659,9 @@ int Sampler::ddim_update(Run& r, const Chain& c, const StepConsts& sc) {
     }
     // (a second-order step reads the history it rewrites; no eta draw and no saved noisy tails under that solver: check_run())
     a.second = sc.second ? 1 : 0; a.A = sc.sA; a.Bc = sc.sBc; a.G = sc.sG;
-    if (int e = launch_ddim_step(a, c.s)) return e;
+    GuideArgs ga;
+    if (sc.kind == STEP_DDIM && guide_for(r, c, sc, ga)) { if (int e = launch_guided_ddim_step(a, ga, c.s)) return e; }
+    else if (int e = launch_ddim_step(a, c.s)) return e;
     if (r.son) DSH_HIP_CHECK(hipMemcpyAsync(tails + (size_t)k * r.blc + toff, tail_tmp + toff, (size_t)c.nb * o.overlap_len * channels * sizeof(float),
                                            hipMemcpyDeviceToDevice, c.s));
     return 0;
@@ -655,7 +674,26 @@ int Sampler::ddpm_update(Run& r, const Chain& c, const StepConsts& sc) {
     a.x = r.x + c.off; a.eps = eps + c.off; a.noise = z; a.x0_out = nullptr; a.c1 = sc.c1; a.c2 = sc.c2;
     a.coef1 = sc.coef1; a.coef2 = sc.coef2; a.sigma = sc.sigma;
     a.n = c.cnt; a.clip = r.o.clip_denoised; a.channels = channels; a.c_lo = c.c_lo; a.c_hi = c.c_hi;
+    GuideArgs ga;
+    if (guide_for(r, c, sc, ga)) return launch_guided_ddpm_step(a, r.den->frames(), ga, c.s);
     return launch_ddpm_step(a, c.s);
+}
+
+// The guidance of one chain's share of a denoise step: its element range of target / weight, its clips' lengths, the level's scale.
+// false: the step is the unguided launch (no guidance in the run, or a zero scale at this level).
+// (Ragged batch: the guided launches leave the padded frames >= lens[b] unwritten while the unguided ones update them, so with zeros in
+//  level_scale a padded frame is advanced at some levels and not at others.  Nothing reads those frames — the evaluation takes the clip's own
+//  length, finish() zeroes them in the result — and rows of `trace` hold unspecified values there either way.)
+bool Sampler::guide_for(const Run& r, const Chain& c, const StepConsts& sc, GuideArgs& g) const {
+    if (!r.guide) return false;
+    const Guidance& gd = *r.guide;
+    const float scale = gd.level_scale.empty() ? 1.0f : gd.level_scale[sc.k];
+    if (scale == 0.0f) return false;
+    g.target = gd.target ? gd.target + c.off : nullptr; g.weight = gd.weight ? gd.weight + c.off : nullptr;
+    g.vel = gd.vel; g.acc = gd.acc;
+    g.lens = r.len_d ? r.len_d + c.b0 : nullptr;
+    g.scale = scale; g.space = gd.space; g.sqrt_1m_ab = sc.sqrt_1m_ab; g.post_var = sc.post_var;
+    return true;
 }
 
 // one chain's share of a step: its columns of its rows, on its stream (every chain draws the same values: the noise depends on the position only)
@@ -763,6 +801,7 @@ int Sampler::run(DenoiserContext* den, const RunSpec& s) {
     // addressing stays that of the full-width row, so an active column receives the value it receives in the joint run.
     const int mod = r.mod = shape.modality, gcols = r.gcols = shape.gesture_cols;
     r.w_lo = mod == 1 ? gcols : 0; r.w_hi = mod == 0 ? 0 : (mod == 1 ? channels : gcols);      // (0, 0: all columns)
+    r.guide = s.guide.on ? &s.guide : nullptr;
     r.len_d = den->lengths_dev();           // ragged batch (set_condition_ragged): per-clip frame counts of the padded batch, owned by the context
     // loop_begin() marks the batch as deliberately unsplit; the mark is taken back on EVERY way out of this function (an argument error or a
     // failed launch below must not leave the context answering later evaluations as if a loop were still running)

@@ -6,6 +6,8 @@
 //   undo_step   x <- sqrt(1-beta) x + sqrt(beta) n                   :464-473
 //   ddpm_step   mean = coef1 x0 + coef2 x;  x <- mean + sigma n      :598-600, :747-773
 //   q_sample    x <- sqrt(ab) x0 + sqrt(1-ab) n (n given, or drawn in the pass)  :434-462
+//   guided      the DDIM / DPM2M / DDPM steps with the gradient of a per-column quadratic energy where the reference
+//               uses its cond_fn (condition_score / condition_mean)  :645-682   (sibling kernels: guided_kernel)
 //
 // Every product / sum is an individually rounded fp32 op (rn_mul / rn_add / rn_sub of dsh_common.h: compiled with contraction off, so never fused into an FMA),
 // in the reference's operation order, so the update itself is bit-identical to the aten sequence
@@ -147,6 +149,170 @@ int launch_ddpm_step(const DdpmStepArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid_for(a.n)), dim3(256), 0, s, a);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+// ---- guided steps: soft constraints while sampling (dsh_kernels.h, GuideArgs) ----
+// g[t] from z at t-2 .. t+2 of one column of a clip of L frames (values at frames outside [0, L) are not read: their predicates are false):
+//   g = -scale (W (z - Y) + vel ([t>=1] v[t-1] - [t<=L-2] v[t]) + acc ([2<=t] a[t-1] - 2 [1<=t<=L-2] a[t] + [t<=L-3] a[t+1]))
+// with v[t] = z[t+1] - z[t], a[t] = (z[t+1] - 2 z[t]) + z[t-1]; every product and sum rounded on its own, in this order.
+__device__ __forceinline__ float guide_grad(const GuideArgs& g, size_t i, int t, int L, float lv, float la, float zm2, float zm1, float z0,
+                                            float zp1, float zp2) {
+    float sum = 0.f;
+    if (g.weight) sum = rn_mul(g.weight[i], rn_sub(z0, g.target ? g.target[i] : 0.f));
+    if (g.vel) {
+        const float vm = t >= 1 ? rn_sub(z0, zm1) : 0.f;
+        const float v0 = t <= L - 2 ? rn_sub(zp1, z0) : 0.f;
+        sum = rn_add(sum, rn_mul(lv, rn_sub(vm, v0)));
+    }
+    if (g.acc) {
+        const float am = t >= 2 ? rn_add(rn_sub(z0, rn_mul(2.0f, zm1)), zm2) : 0.f;
+        const float a0 = (t >= 1 && t <= L - 2) ? rn_add(rn_sub(zp1, rn_mul(2.0f, z0)), zm1) : 0.f;
+        const float ap = t <= L - 3 ? rn_add(rn_sub(zp2, rn_mul(2.0f, zp1)), z0) : 0.f;
+        sum = rn_add(sum, rn_mul(la, rn_add(rn_sub(am, rn_mul(2.0f, a0)), ap)));
+    }
+    return -rn_mul(g.scale, sum);
+}
+
+struct GuidedKernelArgs {
+    DdimStepArgs d;        // GUIDED_DDIM / GUIDED_DPM2M
+    DdpmStepArgs p;        // GUIDED_DDPM
+    const float* z; float* g_out;      // GUIDED_GRAD
+    GuideArgs g;
+    size_t cols;           // B * channels: one thread per column of a clip
+    int frames, channels, c_lo, c_hi;
+};
+enum GuidedMode { GUIDED_GRAD = 0, GUIDED_DDIM = 1, GUIDED_DPM2M = 2, GUIDED_DDPM = 3 };
+
+// Lanes run across the columns of a frame (coalesced rows); each lane walks ALL frames of its column of its clip with z at t-2 .. t+2 and
+// x / eps at t .. t+2 in registers.  The steps update x in place, so a column is one thread's: it has read frame t + 2 before it stores
+// frame t, and nothing else reads or writes that column (a frame chunk per thread would read halo frames its neighbour is storing).
+// No LDS, no atomics; a clip's result depends on its own column, its length and the launch's scalars only.
+// X0: z is pred_xstart = clip(c1 x - c2 eps), re-derived for the neighbouring frames from their x and eps.
+template <int MODE, bool X0>
+__global__ void guided_kernel(GuidedKernelArgs a) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const int T = a.frames, C = a.channels;
+    const bool ranged = a.c_hi > a.c_lo;
+    const float* xs = MODE == GUIDED_GRAD ? a.z : MODE == GUIDED_DDPM ? a.p.x : a.d.x;
+    const float* es = MODE == GUIDED_GRAD ? nullptr : MODE == GUIDED_DDPM ? a.p.eps : a.d.eps;
+    const float c1 = MODE == GUIDED_DDPM ? a.p.c1 : a.d.c1, c2 = MODE == GUIDED_DDPM ? a.p.c2 : a.d.c2;
+    const int clip = MODE == GUIDED_DDPM ? a.p.clip : a.d.clip;
+    const int tc = T * C;
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < a.cols; j += stride) {
+        const size_t b = j / (size_t)C;
+        const int c = (int)(j - b * (size_t)C);
+        if (ranged && (c < a.c_lo || c >= a.c_hi)) continue;
+        int L = a.g.lens ? a.g.lens[b] : T;
+        L = L < 0 ? 0 : (L > T ? T : L);
+        const size_t base = b * (size_t)tc + (size_t)c;
+        const float lv = a.g.vel ? a.g.vel[c] : 0.f, la = a.g.acc ? a.g.acc[c] : 0.f;
+        // frame t of the column (t < L): x, eps and the guided signal
+        auto load = [&](int t, float& x, float& e, float& z) {
+            const size_t i = base + (size_t)t * C;
+            x = xs[i];
+            e = MODE == GUIDED_GRAD ? 0.f : es[i];
+            if (MODE != GUIDED_GRAD && X0) {
+                z = rn_sub(rn_mul(c1, x), rn_mul(c2, e));
+                if (clip) z = fminf(fmaxf(z, -1.0f), 1.0f);
+            } else z = x;
+        };
+        float zm2 = 0.f, zm1 = 0.f, z0 = 0.f, z1 = 0.f, z2 = 0.f, x0 = 0.f, x1 = 0.f, x2 = 0.f, e0 = 0.f, e1 = 0.f, e2 = 0.f;
+        if (L > 0) load(0, x0, e0, z0);
+        if (L > 1) load(1, x1, e1, z1);
+        for (int t = 0; t < L; ++t) {
+            x2 = e2 = z2 = 0.f;
+            if (t + 2 < L) load(t + 2, x2, e2, z2);
+            const size_t i = base + (size_t)t * C;
+            const float g = guide_grad(a.g, i, t, L, lv, la, zm2, zm1, z0, z1, z2);
+            if (MODE == GUIDED_GRAD) {
+                a.g_out[i] = g;
+            } else if (MODE == GUIDED_DDPM) {
+                float p0 = rn_sub(rn_mul(c1, x0), rn_mul(c2, e0));
+                if (clip) p0 = fminf(fmaxf(p0, -1.0f), 1.0f);
+                float mean = rn_add(rn_mul(a.p.coef1, p0), rn_mul(a.p.coef2, x0));
+                if (g != 0.f) mean = rn_add(mean, rn_mul(a.g.post_var, g));      // condition_mean: mean + variance * gradient
+                if (a.p.x0_out) a.p.x0_out[i] = p0;
+                a.p.x[i] = rn_add(mean, rn_mul(a.p.sigma, a.p.noise[i]));
+            } else {
+                const float c1x = rn_mul(c1, x0);
+                float p0 = rn_sub(c1x, rn_mul(c2, e0));
+                if (clip) p0 = fminf(fmaxf(p0, -1.0f), 1.0f);
+                // condition_score: eps re-derived from pred_xstart, shifted, and pred_xstart re-derived from it (not clipped again)
+                // (an element whose gradient is exactly 0 — no term touches it, or a zero scale — takes the parent's update bit for bit: the
+                //  round trip through eps would move its last bits for nothing)
+                const float eg = rn_sub(__fdiv_rn(rn_sub(c1x, p0), c2), rn_mul(a.g.sqrt_1m_ab, g));
+                const float pg = g == 0.f ? p0 : rn_sub(c1x, rn_mul(c2, eg));
+                float s;
+                if (MODE == GUIDED_DPM2M) {
+                    const float D = rn_add(pg, rn_mul(a.d.G, rn_sub(pg, a.d.x0_out[i])));
+                    s = rn_add(rn_mul(a.d.A, x0), rn_mul(a.d.Bc, D));
+                    a.d.x0_out[i] = pg;
+                } else {
+                    const float en = __fdiv_rn(rn_sub(c1x, pg), c2);
+                    s = rn_add(rn_mul(pg, a.d.sqrt_ab_prev), rn_mul(a.d.coef_eps, en));
+                    if (a.d.noise1) s = rn_add(s, rn_mul(a.d.sigma, a.d.noise1[i]));
+                    if (a.d.x0_out) a.d.x0_out[i] = pg;
+                }
+                repaint_and_store(a.d, b * (size_t)tc + (size_t)t * C + (size_t)c, tc, s);
+            }
+            zm2 = zm1; zm1 = z0; z0 = z1; z1 = z2;
+            x0 = x1; x1 = x2; e0 = e1; e1 = e2;
+        }
+        // GUIDED_GRAD: frames beyond the clip's length get gradient 0; the steps leave them as they are
+        if (MODE == GUIDED_GRAD) for (int t = L; t < T; ++t) a.g_out[base + (size_t)t * C] = 0.f;
+    }
+}
+
+static int check_guide(const GuideArgs& g, int B, int frames, int channels, int c_lo, int c_hi, const char* what) {
+    DSH_REQUIRE(B > 0 && frames > 0 && channels > 0, std::string(what) + ": invalid argument");
+    DSH_REQUIRE(c_lo >= 0 && c_hi <= channels, std::string(what) + ": channel range outside [0, channels]");
+    DSH_REQUIRE(g.space == GUIDE_XT || g.space == GUIDE_X0, std::string(what) + ": unknown guidance space (0 x_t, 1 x0)");
+    return 0;
+}
+template <int MODE>
+static int launch_guided(GuidedKernelArgs& k, int B, hipStream_t s) {
+    k.cols = (size_t)B * k.channels;
+    const dim3 grid(grid_for(k.cols)), block(256);
+    if (k.g.space == GUIDE_X0) hipLaunchKernelGGL((guided_kernel<MODE, true>), grid, block, 0, s, k);
+    else hipLaunchKernelGGL((guided_kernel<MODE, false>), grid, block, 0, s, k);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_guidance_grad(const float* z, float* g, int B, int frames, int channels, int c_lo, int c_hi, const GuideArgs& ga, hipStream_t s) {
+    if (int e = check_guide(ga, B, frames, channels, c_lo, c_hi, "guidance_grad")) return e;
+    DSH_REQUIRE(z && g && z != g, "guidance_grad: null pointer (or g aliases z)");
+    GuidedKernelArgs k{};
+    k.z = z; k.g_out = g; k.g = ga; k.g.space = GUIDE_XT;       // (z is given: nothing to re-derive)
+    k.frames = frames; k.channels = channels; k.c_lo = c_lo; k.c_hi = c_hi;
+    return launch_guided<GUIDED_GRAD>(k, B, s);
+}
+
+int launch_guided_ddim_step(const DdimStepArgs& a, const GuideArgs& ga, hipStream_t s) {
+    DSH_REQUIRE(a.x && a.eps && a.frames > 0 && a.channels > 0, "guided_ddim_step: invalid argument");
+    const size_t row = (size_t)a.frames * a.channels;
+    DSH_REQUIRE(a.n > 0 && a.n % row == 0, "guided_ddim_step: the element count is not a whole number of clips");
+    const int B = (int)(a.n / row);
+    if (int e = check_guide(ga, B, a.frames, a.channels, a.c_lo, a.c_hi, "guided_ddim_step")) return e;
+    DSH_REQUIRE(!a.mask || a.tail_in || (a.gt && a.noise2), "guided_ddim_step: a mask needs gt and noise2");
+    if (a.second) {
+        DSH_REQUIRE(a.x0_out, "guided_ddim_step: the second-order step needs the x0 history");
+        DSH_REQUIRE(!a.noise1 && !a.tail_in && !a.tail_out, "guided_ddim_step: second order: no eta draw and no saved noisy tails");
+    }
+    GuidedKernelArgs k{};
+    k.d = a; k.g = ga; k.frames = a.frames; k.channels = a.channels; k.c_lo = a.c_lo; k.c_hi = a.c_hi;
+    return a.second ? launch_guided<GUIDED_DPM2M>(k, B, s) : launch_guided<GUIDED_DDIM>(k, B, s);
+}
+
+int launch_guided_ddpm_step(const DdpmStepArgs& a, int frames, const GuideArgs& ga, hipStream_t s) {
+    DSH_REQUIRE(a.x && a.eps && a.noise && frames > 0 && a.channels > 0, "guided_ddpm_step: invalid argument");
+    const size_t row = (size_t)frames * a.channels;
+    DSH_REQUIRE(a.n > 0 && a.n % row == 0, "guided_ddpm_step: the element count is not a whole number of clips");
+    const int B = (int)(a.n / row);
+    if (int e = check_guide(ga, B, frames, a.channels, a.c_lo, a.c_hi, "guided_ddpm_step")) return e;
+    GuidedKernelArgs k{};
+    k.p = a; k.g = ga; k.frames = frames; k.channels = a.channels; k.c_lo = a.c_lo; k.c_hi = a.c_hi;
+    return launch_guided<GUIDED_DDPM>(k, B, s);
 }
 
 __global__ void fill_i64_kernel(int64_t* p, int64_t v, size_t n) {

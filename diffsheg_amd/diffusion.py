@@ -341,6 +341,31 @@ class GaussianDiffusion:
             if set_gs:
                 model.set_guidance_scale(prev_gs)
 
+    @staticmethod
+    def _check_guide_shapes(guidance, shape) -> None:
+        """A guidance built for another sample shape is refused with the other argument checks, before anything is conditioned."""
+        B, T, Cc = shape
+        for name in ("target", "weight", "vel", "acc"):
+            v = getattr(guidance, name)
+            want = (B, T, Cc) if name in ("target", "weight") else (Cc,)
+            if v is not None and tuple(v.shape) != want:
+                raise ValueError(f"guidance: {name} {tuple(v.shape)} does not match the sample shape: expected {want}")
+
+    def _guide_fields(self, guidance, shape, dev):
+        """The guide_* fields of a run's dsh_run_spec for a glue.MotionGuidance (or None): ``(tensors to keep alive, run_spec keywords)``.
+        The tensors go to the model's device as they are built; shapes are refused here with the sample's shape in the message, the rest
+        (level count, space, the reverse loop) by the library's check_run."""
+        if guidance is None:
+            return None, {}
+        B, T, Cc = shape
+        self._check_guide_shapes(guidance, shape)
+        held = {name: getattr(guidance, name).to(device=dev, dtype=torch.float32).contiguous()
+                for name in ("target", "weight", "vel", "acc") if getattr(guidance, name) is not None}
+        kw = {f"guide_{n}": v.data_ptr() for n, v in held.items()}
+        kw.update(guidance=1, guide_space=_lib.GUIDE_SPACES[guidance.space], guide_batch=B, guide_frames=T, guide_channels=Cc,
+                  guide_scale=guidance.level_scale or ())
+        return held, kw
+
     def _run(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0,
              noise_source=None, seed=None, return_trace=False, row_keys=None, cond_scale=None, tail_blend=False,
              row_seeds=None, start_level=None, x_start=None, add_blend=None, solver=None):
@@ -358,8 +383,11 @@ class GaussianDiffusion:
                 raise ValueError("the dpm2m solver is deterministic: eta must be 0")
             if bool(getattr(self.opt, "same_overlap_noisy", False)):
                 raise NotImplementedError("the dpm2m solver does not keep the saved noisy tails of same_overlap_noisy")
-        if denoised_fn is not None or cond_fn is not None:
-            raise NotImplementedError("denoised_fn / cond_fn are not on the accelerated path")
+        # cond_fn: the closed family of glue.MotionGuidance runs fused into the step kernels; an arbitrary callable would put a host round
+        # trip and an autograd graph into every step
+        from .glue import MotionGuidance
+        if denoised_fn is not None or (cond_fn is not None and not isinstance(cond_fn, MotionGuidance)):
+            raise NotImplementedError("denoised_fn / cond_fn are not on the accelerated path (cond_fn: only a glue.MotionGuidance is)")
         if eta != 0.0 and kind != 0:
             raise TypeError("eta is an argument of the DDIM loops only")
         if model_kwargs is None or model_kwargs.get("y", None) is None:
@@ -401,6 +429,8 @@ class GaussianDiffusion:
                     raise NotImplementedError("start_level with tail_blend is not built")
         clip_idx = int(y.get("clip_idx", 0)) if son else 0
         B, T, Cc = (int(s) for s in shape)
+        if cond_fn is not None:
+            self._check_guide_shapes(cond_fn, (B, T, Cc))
         if tail_blend and 2 * int(getattr(self.opt, "overlap_len", 0)) > T:
             raise ValueError(f"tail_blend: the head and the tail fade overlap (2 * overlap_len = {2 * int(self.opt.overlap_len)} > {T} frames)")
         gs = self._guidance(model, cond_scale, B)
@@ -449,10 +479,11 @@ class GaussianDiffusion:
         # the whole call in one dsh_run_spec: nothing is set in, or left behind in, the native context.  Philox noise only: per-row generator
         # keys (a chain's global id) and per-row seeds
         keyed = row_keys is not None and noise_source is None
+        guide, guide_kw = self._guide_fields(cond_fn, (B, T, Cc), dev)
         spec = _lib.run_spec(timesteps=self._kept if (self._kept and kind == 0) else (), row_keys=row_keys if keyed else (),
                              row_seeds=row_seeds if (keyed and row_seeds is not None) else (), init=init, masked=int(masked), start_level=K,
                              tail_blend=int(tail_blend), solver=int(solver == "dpm2m"), x=x.data_ptr(),
-                             gt=None if gt is None else gt.data_ptr(), mask=mask.data_ptr() if masked else None)
+                             gt=None if gt is None else gt.data_ptr(), mask=mask.data_ptr() if masked else None, **guide_kw)
         n_draws, n_steps = C.c_int64(), C.c_int64()
         _lib.check(lib.dsh_sample_count(C.byref(opts), C.byref(spec), C.byref(n_draws), C.byref(n_steps)), "dsh_sample_count")
         stack = trace = None
@@ -466,7 +497,7 @@ class GaussianDiffusion:
             spec.trace = trace.data_ptr()
         with self._native(model, gs):
             _lib.check(lib.dsh_sample_run(model._h, C.byref(opts), C.byref(spec)), "dsh_sample_run")
-        self._keep = (gt, mask, stack)          # consumed asynchronously on the stream
+        self._keep = (gt, mask, stack, guide)   # consumed asynchronously on the stream
         if son:
             # gaussian_diffusion.py:1155-1157: the loop returns the dict of the last step plus the saved tails.  The tails live
             # in the native context (one slot per spaced level, overwritten step by step exactly like the reference's dict,
@@ -501,7 +532,12 @@ class GaussianDiffusion:
         ``solver="ddim" | "dpm2m"`` (keyword; default: this object's ``solver`` attribute, ``"ddim"``): ``"dpm2m"`` makes every denoise step
         that directly follows the denoise step one level above it — and is not the last — the second-order DPM-Solver++(2M) update
         (dsh_run_spec.solver); all other steps, the draws and the noise addressing are the DDIM loop's.  Needs ``eta == 0`` and no
-        ``same_overlap_noisy``.  Meant for few steps on a ``'logsnrK'`` subset (:func:`space_timesteps`)."""
+        ``same_overlap_noisy``.  Meant for few steps on a ``'logsnrK'`` subset (:func:`space_timesteps`).
+
+        ``cond_fn``: a :class:`diffsheg_amd.glue.MotionGuidance` (soft keyframes, velocity / acceleration damping) — every denoise step is
+        the guided form of its kernel (``condition_score``, gaussian_diffusion.py:660-682; ``p_sample_loop``: ``condition_mean``,
+        :645-658), under both solvers, with masks, ``eta`` and ragged lengths; no draw is added.  Any other callable, and
+        ``denoised_fn``, stay refused."""
         if not self._respacing:
             raise NotImplementedError("ddim_sample_loop needs a SpacedDiffusion('ddimK') (trainers use 'ddim25')")
         return self._run(0, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta, **kw)

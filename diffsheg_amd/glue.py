@@ -18,6 +18,7 @@ template files) stay out of scope.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -169,6 +170,154 @@ def euler_to_axis_angle(pose: torch.Tensor, stats: PoseStats, *, split_pos: Opti
     ``euler_angles_to_axis_angle(..., 'XYZ')`` -> normalise with the axis-angle statistics: what ``motions``, ``head`` and ``tail`` of
     the samplers expect from frames held as Euler / BVH poses.  ``split_pos`` / ``lengths`` as for :func:`axis_angle_to_euler`."""
     return _rotation_call("euler_to_axis_angle", pose, stats, split_pos, lengths, False)
+
+
+def guidance_grad_torch(z: torch.Tensor, target, weight, vel, acc, lengths=None, scale: float = 1.0) -> torch.Tensor:
+    """``g = scale * d log p / d z`` of the guidance energy (:class:`MotionGuidance`) in plain torch, in ``z``'s dtype, on ``z``'s device:
+    the five-point stencil the step kernels evaluate, in their operation order.  ``z [B, T, C]``; ``target`` / ``weight`` ``[B, T, C]`` or
+    None; ``vel`` / ``acc`` ``[C]`` or None; ``lengths``: one frame count per clip or None."""
+    B, T, Cc = z.shape
+    t = torch.arange(T, device=z.device).view(1, T, 1)
+    L = torch.full((B, 1, 1), T, device=z.device) if lengths is None else \
+        torch.as_tensor(lengths, device=z.device).to(torch.int64).clamp(0, T).view(B, 1, 1)
+    zero = torch.zeros((), dtype=z.dtype, device=z.device)
+    pad = torch.zeros(B, 1, Cc, dtype=z.dtype, device=z.device)
+
+    def shift(u, k):        # u[t + k], zeros outside
+        if k == 0:
+            return u
+        fill = pad.expand(B, min(abs(k), T), Cc)
+        return torch.cat([u[:, k:], fill], 1) if k > 0 else torch.cat([fill, u[:, :k]], 1)
+
+    total = torch.zeros_like(z)
+    if weight is not None:
+        y = zero if target is None else target.to(device=z.device, dtype=z.dtype)
+        total = weight.to(device=z.device, dtype=z.dtype) * (z - y)
+    if vel is not None:
+        v = torch.where(t <= L - 2, shift(z, 1) - z, zero)                      # v[t] = z[t+1] - z[t], t = 0 .. L-2
+        total = total + vel.to(device=z.device, dtype=z.dtype).view(1, 1, Cc) * (shift(v, -1) - v)
+    if acc is not None:
+        a = torch.where((t >= 1) & (t <= L - 2), (shift(z, 1) - 2 * z) + shift(z, -1), zero)      # a[t], t = 1 .. L-2
+        total = total + acc.to(device=z.device, dtype=z.dtype).view(1, 1, Cc) * ((shift(a, -1) - 2 * a) + shift(a, 1))
+    return torch.where(t < L, -(scale * total), zero)
+
+
+class MotionGuidance:
+    """Soft constraints for the sampling loops: a closed family of per-column quadratic energies, handed to ``ddim_sample_loop`` /
+    ``p_sample_loop`` as ``cond_fn=`` or to the trainer's entry points as ``guidance=``.  With ``L`` the clip's length and ``z`` the guided
+    signal of column ``c`` of clip ``b``::
+
+        log p(y | z) = -1/2 sum_t W[b,t,c] (z[t] - Y[b,t,c])^2          attraction (keyframes / soft targets)
+                       -1/2 vel[c] sum_{t=0..L-2} (z[t+1] - z[t])^2      velocity damping
+                       -1/2 acc[c] sum_{t=1..L-2} (z[t+1] - 2 z[t] + z[t-1])^2      acceleration (jitter) damping
+
+    and every denoise step uses ``s_k * d log p / d z`` where the reference uses the value of its ``cond_fn``, fused into the step kernel.
+    ``target`` = Y and ``weight`` = W >= 0 are fp32 ``[B, T, C]`` tensors (``weight=None`` with a target: 1 everywhere); ``vel`` / ``acc``
+    fp32 ``[C]``; all on one device.  ``space="x_t"``: z is the noisy sample — exactly the reference's ``cond_fn(x, t)`` contract.
+    ``space="x0"`` (default): z is the step's ``pred_xstart``; the denoiser's Jacobian is not applied.  ``level_scale``: one factor per
+    level of the run (``respacing`` entries for the DDIM loops, ``diffusion_steps`` for the DDPM loop; None: 1); a level with factor 0 runs
+    unguided.  No term couples columns.
+
+    The object is also the reference's hook itself: ``g(x, t, **model_kwargs)`` returns the gradient for ``space="x_t"`` in plain torch
+    on any device (``t``: the ORIGINAL timesteps a SpacedDiffusion passes; set ``timestep_map`` to the run's map when ``level_scale`` is
+    given; ``length`` in ``model_kwargs`` gives the clips' lengths).  For ``space="x0"`` the call raises: the contract has no pred_xstart."""
+
+    def __init__(self, target=None, weight=None, vel=None, acc=None, space: str = "x0", level_scale=None, timestep_map=None):
+        if space not in _lib.GUIDE_SPACES:
+            raise ValueError(f'space must be "x_t" or "x0", got {space!r}')
+        if weight is not None and target is None:
+            raise ValueError("weight needs a target")
+        tensors = [(n, v) for n, v in (("target", target), ("weight", weight), ("vel", vel), ("acc", acc)) if v is not None]
+        for n, v in tensors:
+            if not isinstance(v, torch.Tensor) or v.dtype != torch.float32:
+                raise ValueError(f"MotionGuidance: {n} must be a float32 tensor")
+            if v.device != tensors[0][1].device:
+                raise ValueError(f"MotionGuidance: {n} is on {v.device}, {tensors[0][0]} on {tensors[0][1].device}")
+        if target is not None:
+            if target.dim() != 3:
+                raise ValueError(f"MotionGuidance: target must be [B, T, C], got {tuple(target.shape)}")
+            if weight is None:
+                weight = torch.ones_like(target)
+            if weight.shape != target.shape:
+                raise ValueError(f"MotionGuidance: weight {tuple(weight.shape)} differs from target {tuple(target.shape)}")
+            if bool((weight < 0).any()):
+                raise ValueError("MotionGuidance: weight must be >= 0")
+        cols = None if target is None else int(target.shape[2])
+        for n, v in (("vel", vel), ("acc", acc)):
+            if v is None:
+                continue
+            if v.dim() != 1 or (cols is not None and int(v.shape[0]) != cols):
+                raise ValueError(f"MotionGuidance: {n} must be [C]{'' if cols is None else f' = [{cols}]'}, got {tuple(v.shape)}")
+            cols = int(v.shape[0])
+        self.target = None if target is None else target.contiguous()
+        self.weight = None if weight is None else weight.contiguous()
+        self.vel = None if vel is None else vel.contiguous()
+        self.acc = None if acc is None else acc.contiguous()
+        self.space = space
+        self.level_scale = None if level_scale is None else [float(v) for v in level_scale]
+        self.timestep_map = None if timestep_map is None else [int(v) for v in timestep_map]
+
+    @property
+    def channels(self) -> Optional[int]:
+        for v in (self.target, self.vel, self.acc):
+            if v is not None:
+                return int(v.shape[-1])
+        return None
+
+    def with_terms(self, target, weight) -> "MotionGuidance":
+        """The same guidance with another ``target`` / ``weight`` pair (a window of a longer stream)."""
+        if target.shape != weight.shape or target.dim() != 3 or int(target.shape[2]) != self.channels:
+            raise ValueError(f"with_terms: target {tuple(target.shape)} / weight {tuple(weight.shape)} must be [B, T, {self.channels}]")
+        g = copy.copy(self)              # (slices of tensors this object has validated: no second look at their values, no host sync)
+        g.target, g.weight = target.contiguous(), weight.contiguous()
+        return g
+
+    @classmethod
+    def from_keyframes(cls, poses, frames, columns, weight, B: int, T: int, C: int, device="cuda", **kw) -> "MotionGuidance":
+        """Keyframes as soft targets: ``poses [K, n]`` (every row of the batch) or ``[B, K, n]`` holds the standardised values of the ``n``
+        columns covered by ``columns`` (half-open ``(lo, hi)`` ranges, in order) at the ``K`` frame indices ``frames``; ``weight``: one
+        float, or one per keyframe ``[K]``.  Builds ``target`` / ``weight`` ``[B, T, C]`` on ``device`` (0 off the keyframes); ``kw`` goes
+        to the constructor (``vel=``, ``acc=``, ``space=``, ``level_scale=``)."""
+        B, T, C = int(B), int(T), int(C)
+        fr = [int(f) for f in frames]
+        if not fr or any(f < 0 or f >= T for f in fr) or len(set(fr)) != len(fr):
+            raise ValueError(f"from_keyframes: frames must be distinct indices in 0 .. {T - 1}, got {fr}")
+        cols = [c for lo, hi in _ranges(columns, "column", C) for c in range(lo, hi)]
+        if not cols or len(set(cols)) != len(cols):
+            raise ValueError("from_keyframes: the column ranges must be non-empty and disjoint")
+        p = torch.as_tensor(poses, dtype=torch.float32)
+        if p.dim() == 2:
+            p = p.unsqueeze(0).expand(B, -1, -1)
+        if tuple(p.shape) != (B, len(fr), len(cols)):
+            raise ValueError(f"from_keyframes: poses must be [K, n] or [B, K, n] = {(B, len(fr), len(cols))}, got {tuple(p.shape)}")
+        w = torch.as_tensor(weight, dtype=torch.float32).reshape(-1)
+        if w.numel() not in (1, len(fr)) or bool((w < 0).any()):
+            raise ValueError(f"from_keyframes: weight must be one value >= 0 or one per keyframe ({len(fr)})")
+        dev = torch.device(device)
+        fi = torch.tensor(fr, device=dev).view(-1, 1)
+        ci = torch.tensor(cols, device=dev).view(1, -1)
+        Y = torch.zeros(B, T, C, device=dev)
+        W = torch.zeros(B, T, C, device=dev)
+        Y[:, fi, ci] = p.to(dev)
+        W[:, fi, ci] = w.to(dev).expand(len(fr)).view(1, -1, 1).expand(B, len(fr), len(cols))
+        return cls(Y, W, **kw)
+
+    def scale_at(self, t) -> float:
+        """The level factor at the ORIGINAL timestep ``t`` (the timestep itself is the level without a ``timestep_map``)."""
+        if self.level_scale is None:
+            return 1.0
+        k = int(t) if self.timestep_map is None else self.timestep_map.index(int(t))
+        return self.level_scale[k]
+
+    def __call__(self, x, t, **kwargs):
+        if self.space != "x_t":
+            raise TypeError('MotionGuidance(space="x0") is not a cond_fn(x, t): the contract carries no pred_xstart')
+        ts = set(int(v) for v in t.reshape(-1).tolist()) if isinstance(t, torch.Tensor) else {int(t)}
+        if len(ts) != 1:
+            raise NotImplementedError("one timestep per call")
+        length = kwargs.get("length")
+        lens = None if length is None else [int(v) for v in (length.tolist() if isinstance(length, torch.Tensor) else length)]
+        return guidance_grad_torch(x, self.target, self.weight, self.vel, self.acc, lens, self.scale_at(ts.pop()))
 
 
 def _ranges(v, what: str, hi: int):

@@ -337,6 +337,8 @@ class StreamPool:
 
     @staticmethod
     def _refuse(kw) -> None:
+        if kw.get("guidance") is not None:
+            raise NotImplementedError("guidance in live sessions (StreamPool) is not built")
         if kw:
             raise ValueError(f"StreamPool does not take {sorted(kw)}: it draws Philox noise from its own seed (no noise_source stacks) and "
                              "samples both modalities (a partial modality is not served)")

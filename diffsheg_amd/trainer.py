@@ -198,7 +198,7 @@ class DDPMTrainer:
         return euler_to_axis_angle(pose.to(self.device), self.pose_stats, split_pos=self._gesture_split(), lengths=lengths)
 
     def generate_batch(self, audio_emb, p_id, dim_pose, add_cond={}, inpaint_dict=None, cond_scale=None, lengths=None,
-                       pose_rep: str = "axis_angle", modality="both", expression=None, **sampler_kw):
+                       pose_rep: str = "axis_angle", modality="both", expression=None, guidance=None, **sampler_kw):
         """ddpm_show_trainer.py:163-198.  ``sampler_kw`` (noise_source= / seed=) is this build's
         noise-injection hook; the reference draws from the global torch RNG.  ``cond_scale`` (a float, or one value per batch
         row) overrides ``opt.cond_scale`` for this batch.  ``lengths`` (one frame count per row, ``1 .. T``): clips of different
@@ -209,10 +209,14 @@ class DDPMTrainer:
         ``expression`` (:meth:`UniDiffuser.set_condition`): ``"expression"`` samples the face alone (gesture columns of the result 0),
         ``"gesture"`` samples gestures for the given expression track ``[B, T, expression_dim]`` (expression columns = the track);
         ``inpaint_dict`` is honoured on the active columns only.  ``row_seeds=`` (in ``sampler_kw``, with ``row_keys=``): one Philox key
-        per row in place of ``seed=`` — rows at different windows of their chains in one batch (:mod:`diffsheg_amd.streaming`)."""
+        per row in place of ``seed=`` — rows at different windows of their chains in one batch (:mod:`diffsheg_amd.streaming`).
+        ``guidance`` (a :class:`diffsheg_amd.glue.MotionGuidance` built for ``[B, T, dim_pose]``): soft keyframes and velocity /
+        acceleration damping, fused into every denoise step; with ``lengths`` the stencils end at each clip's own last frame."""
         euler = self._euler_requested(pose_rep)
         if cond_scale is not None:
             sampler_kw["cond_scale"] = cond_scale
+        if guidance is not None:
+            sampler_kw["cond_fn"] = guidance
         audio_emb = audio_emb.to(self.device)
         B, T = len(audio_emb), audio_emb.shape[1]
         if lengths is None:
@@ -393,7 +397,7 @@ class DDPMTrainer:
                              noise_source_for_window=None, seed: Optional[int] = None,
                              motions: Optional[torch.Tensor] = None, row_keys: Optional[Sequence[int]] = None,
                              cond_scale=None, lengths: Optional[Sequence[int]] = None, pose_rep: str = "axis_angle",
-                             modality="both", expression=None):
+                             modality="both", expression=None, guidance=None):
         """The per-video body of test_arbitrary_len (ddpm_show_trainer.py:864-906): windows of n_poses
         with stride n_poses-overlap_len; window k>0 out-paints from the last overlap_len frames of
         window k-1 (sequential chain).  Output stays on the device (the reference copies every window
@@ -414,9 +418,22 @@ class DDPMTrainer:
         ``modality`` / ``expression``: one modality alone for every window of the chains (:meth:`generate_batch`).  The track of
         ``"gesture"`` is ``[B, N, E]``, ``[N, E]`` (one track for every chain) or, with ``lengths``, a list of ``[lengths[b], E]``
         tensors; it is cut into windows exactly like the audio.  The overlap hand-off, ``fix_very_first`` and the out-painting mask
-        act on the active columns only; ``opt.same_overlap_noisy`` is refused."""
+        act on the active columns only; ``opt.same_overlap_noisy`` is refused.
+
+        ``guidance`` (a :class:`diffsheg_amd.glue.MotionGuidance`; chains of equal length only): its ``target`` / ``weight`` are
+        stream-long ``[B, N, C]`` and cut into windows like the audio, ``vel`` / ``acc`` / ``space`` / ``level_scale`` are shared by every
+        window.  The stencils are per window: smoothness is NOT enforced across a window boundary (the out-painted overlap carries the
+        previous window's frames).  With ``lengths`` (the ragged chain) it raises ``NotImplementedError``."""
+        if guidance is not None and lengths is not None:
+            raise NotImplementedError("guidance in the ragged chain (lengths=) is not built")
         euler = self._euler_requested(pose_rep)
         expression = self._chain_track(modality, expression, int(audio_emb.shape[0]), int(audio_emb.shape[1]), lengths)
+        if guidance is not None:
+            N = int(audio_emb.shape[1])
+            for name in ("target", "weight"):
+                v = getattr(guidance, name)
+                if v is not None and (v.dim() != 3 or int(v.shape[0]) != int(audio_emb.shape[0]) or int(v.shape[1]) != N):
+                    raise ValueError(f"guidance: {name} must be stream-long [B, N, C] = [{int(audio_emb.shape[0])}, {N}, C], got {tuple(v.shape)}")
         if lengths is not None:
             outs = self._sample_arbitrary_len_ragged(audio_emb, p_id, add_cond, [int(v) for v in lengths], noise_source_for_window, seed,
                                                      motions, row_keys, cond_scale, modality, expression)
@@ -431,6 +448,13 @@ class DDPMTrainer:
         if fix_first and motions is None:
             raise ValueError("fix_very_first needs the ground-truth motions of the clip")
         motion_list = get_windows(motions.to(self.device), n_poses, step) if fix_first else None
+        guide_list = [None] * len(audio_list)
+        if guidance is not None:
+            if guidance.target is None:
+                guide_list = [guidance] * len(audio_list)
+            else:
+                guide_list = [guidance.with_terms(y.contiguous(), w.contiguous()) for y, w in
+                              zip(get_windows(guidance.target, n_poses, step), get_windows(guidance.weight, n_poses, step))]
         outs: List[torch.Tensor] = []
         outputs = None
         son = bool(getattr(opt, "same_overlap_noisy", False))     # ddpm_beat_trainer.py:1006,1022-1028
@@ -461,6 +485,8 @@ class DDPMTrainer:
                 kw["cond_scale"] = cond_scale
             if ex is not None or modality not in (None, "both", 0):
                 kw["modality"], kw["expression"] = modality, ex
+            if guide_list[ii] is not None:
+                kw["guidance"] = guide_list[ii]
             outputs = self.generate_batch(a, p_id, C, cnd, inpaint_dict, **kw)
             if son:
                 previous_noisy_tail, outputs = outputs["saved_noisy_tail"], outputs["sample"]
@@ -578,7 +604,7 @@ class DDPMTrainer:
     def sample_inbetween(self, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor],
                          head: torch.Tensor, tail: torch.Tensor, *, tail_blend: bool = True, seed: Optional[int] = None,
                          row_keys: Optional[Sequence[int]] = None, noise_source=None, cond_scale=None, modality="both",
-                         expression=None) -> torch.Tensor:
+                         expression=None, guidance=None) -> torch.Tensor:
         """"Here are two clips and the audio between them, fill the gap": ``audio_emb [B, T, 128]`` (+ ``add_cond``) conditions one
         window, whose first ``L = opt.overlap_len`` frames are pinned to ``head`` and whose last ``L`` to ``tail`` (both ``[B, L, C]``,
         standardised motion; ``2 L < T``); the frames in between are sampled.  This is the reference's own out-painting loop
@@ -587,7 +613,8 @@ class DDPMTrainer:
         With ``tail_blend=False`` it is exactly that loop: generated motion is cross-faded into the pinned frames on the head side
         only (``addBlend``).  ``tail_blend=True`` (default) adds the mirrored fade on the last ``L`` frames.  Needs ``opt.ddim``
         (mask-present DDPM is not built).  Returns the window ``[B, T, C]`` on the device; no host sync.  ``modality`` /
-        ``expression`` ``[B, T, E]`` as for :meth:`generate_batch`: the pinned frames act on the active columns only."""
+        ``expression`` ``[B, T, E]`` as for :meth:`generate_batch`: the pinned frames act on the active columns only.  ``guidance``
+        (:class:`diffsheg_amd.glue.MotionGuidance` for ``[B, T, C]``) steers the frames in between; the pinned frames stay pinned."""
         opt = self.opt
         L, C = int(opt.overlap_len), int(opt.net_dim_pose)
         if not getattr(opt, "ddim", True):
@@ -604,7 +631,7 @@ class DDPMTrainer:
         mask[:, :L] = True
         mask[:, T - L:] = True
         kw = {"tail_blend": bool(tail_blend)}
-        for k, v in (("seed", seed), ("row_keys", row_keys), ("noise_source", noise_source), ("cond_scale", cond_scale)):
+        for k, v in (("seed", seed), ("row_keys", row_keys), ("noise_source", noise_source), ("cond_scale", cond_scale), ("guidance", guidance)):
             if v is not None:
                 kw[k] = v
         if expression is not None or modality not in (None, "both", 0):
@@ -636,7 +663,8 @@ class DDPMTrainer:
     def sample_variations(self, motions: torch.Tensor, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor], *,
                           level: Optional[int] = None, strength: Optional[float] = None, keep: Optional[torch.Tensor] = None,
                           seed: Optional[int] = None, row_keys: Optional[Sequence[int]] = None, row_seeds: Optional[Sequence[int]] = None,
-                          cond_scale=None, lengths=None, modality="both", expression=None, pose_rep: str = "axis_angle") -> torch.Tensor:
+                          cond_scale=None, lengths=None, modality="both", expression=None, pose_rep: str = "axis_angle",
+                          guidance=None) -> torch.Tensor:
         """Variations of an existing motion ``motions [B, T, C]`` (standardised, the sampler's representation): it is noised to spaced
         level ``K - 1`` (``q_sample`` with the loop's draw 0) and denoised from there with the DDIM loop, in one native call.  ``level=K``
         (``1 .. respacing``) or ``strength=s`` (``K = max(1, round(s * respacing))``): small K stays close to the input, K = respacing
@@ -646,7 +674,8 @@ class DDPMTrainer:
         ``keep`` (bool, broadcastable to ``[B, T, C]``, True = leave as it is; :func:`diffsheg_amd.glue.edit_region` builds one): the
         RePaint path — ``gt = motions``, ``mask = keep``, the jump schedule walked from ``t_T = K`` — with ``addBlend`` off (the
         reference's fade would rewrite kept frames ``[:overlap_len]``).  Kept elements of the result are the input bit for bit: the
-        last step blends ``1 * gt + 0 * n``.  ``opt.fix_head_var`` is refused (q_sample would keep the head channels un-noised)."""
+        last step blends ``1 * gt + 0 * n``.  ``opt.fix_head_var`` is refused (q_sample would keep the head channels un-noised).
+        ``guidance`` (:class:`diffsheg_amd.glue.MotionGuidance`) steers the re-sampled elements softly; kept elements stay bit for bit."""
         if getattr(self.opt, "fix_head_var", False):
             raise NotImplementedError("sample_variations with opt.fix_head_var is not built")
         K = self._edit_level(level, strength)
@@ -668,14 +697,14 @@ class DDPMTrainer:
                 raise ValueError(f"keep {tuple(keep.shape)} does not broadcast to {(B, T, C)}") from e
             inpaint = {"gt": x0, "outpainting_mask": mask}
             kw["add_blend"] = False
-        for k, v in (("seed", seed), ("row_keys", row_keys), ("row_seeds", row_seeds), ("cond_scale", cond_scale)):
+        for k, v in (("seed", seed), ("row_keys", row_keys), ("row_seeds", row_seeds), ("cond_scale", cond_scale), ("guidance", guidance)):
             if v is not None:
                 kw[k] = v
         return self.generate_batch(audio_emb, p_id, C, add_cond, inpaint, lengths=lengths, pose_rep=pose_rep, modality=modality,
                                    expression=expression, **kw)
 
     def restyle(self, motions: torch.Tensor, audio_emb: torch.Tensor, p_id_from: torch.Tensor, p_id_to: torch.Tensor,
-                add_cond: Dict[str, torch.Tensor], *, level: int, cond_scale=None) -> torch.Tensor:
+                add_cond: Dict[str, torch.Tensor], *, level: int, cond_scale=None, guidance=None) -> torch.Tensor:
         """"Same performance, other speaker's style": ``motions [B, T, C]`` is inverted to spaced level ``K = level`` with the DDIM
         reverse ODE under the source speaker ``p_id_from`` (``ddim_reverse_sample`` at levels ``0 .. K-1``, gaussian_diffusion.py:1068-1104)
         and decoded under the target speaker ``p_id_to`` with ``ddim_sample_loop(start_level=K, noise=inverted)`` at ``eta = 0``.
@@ -684,7 +713,10 @@ class DDPMTrainer:
         ``alphas_cumprod_next[k] = alphas_cumprod[k + 1]``, so the reverse loop ENDS at ``alphas_cumprod[K]``; the forward step at level
         ``k`` reads x as being at ``alphas_cumprod[k]``, so decoding ``K`` steps STARTS at ``alphas_cumprod[K - 1]``.  The pairing is off
         by one level on purpose — it is the one guided-diffusion's own encode / decode loops use — and it is not an exact inverse, even
-        under one speaker.  Deterministic: no draws on either side."""
+        under one speaker.  Deterministic: no draws on either side.  ``guidance`` is not built here (the reverse ODE takes none):
+        ``NotImplementedError``."""
+        if guidance is not None:
+            raise NotImplementedError("guidance in restyle is not built: the DDIM reverse ODE takes no guidance")
         K = self._edit_level(level, None)
         audio_emb = audio_emb.to(self.device)
         B, T, C = int(audio_emb.shape[0]), int(audio_emb.shape[1]), int(self.opt.net_dim_pose)
@@ -822,7 +854,7 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
                                  cond_scale: Optional[float] = None, seam_repair: bool = False,
                                  seam_tail_blend: bool = True, ragged: bool = False,
                                  pose_rep: str = "axis_angle", modality="both",
-                                 expression: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+                                 expression: Optional[torch.Tensor] = None, guidance=None) -> Optional[torch.Tensor]:
     """BASELINE config 4: one long feature stream ``[1, N, ...]`` sampled on all ranks of ``group``.
 
     Windows of ONE chain are sequential (window k needs the final sample of window k-1 at every denoising step,
@@ -860,7 +892,11 @@ def sample_arbitrary_len_sharded(trainer: "DDPMTrainer", audio_emb: Optional[tor
 
     ``modality`` / ``expression``: one modality alone for the chains and the seam repair (:meth:`DDPMTrainer.sample_arbitrary_len`).  The
     track of ``"gesture"`` is ``[1, N, E]`` (or ``[N, E]``); with ``inputs_on_rank0_only`` it is broadcast with the audio.
+
+    ``guidance`` (:class:`diffsheg_amd.glue.MotionGuidance`) is not built for the sharded path: ``NotImplementedError``.
     """
+    if guidance is not None:
+        raise NotImplementedError("guidance in the sharded long-audio path is not built (use sample_arbitrary_len on chains of equal length)")
     euler = trainer._euler_requested(pose_rep)
     if cond_scale is not None and not isinstance(cond_scale, numbers.Real):
         raise ValueError("sample_arbitrary_len_sharded takes one scalar cond_scale for its stream")

@@ -211,7 +211,28 @@ typedef struct dsh_run_spec {
     const uint64_t* row_seeds; /* host, n_rows entries or NULL (dsh_sample_set_row_seeds)                                      */
     int32_t n_rows;
     int32_t solver;          /* DSH_SOLVER_DDIM / DSH_SOLVER_DPM2M (dsh_sample_set_solver)                                      */
+    /* Soft constraints while sampling (keyframe attraction, velocity / acceleration damping).  guidance = 0: none, the guide_* fields are
+     * not read and every launch is what it is without them.  With L = the clip's length and z the guided signal of column c of clip b,
+     *   log p = -1/2 sum_t W[b,t,c] (z[t] - Y[b,t,c])^2 - 1/2 vel[c] sum_{t=0..L-2} (z[t+1] - z[t])^2
+     *           - 1/2 acc[c] sum_{t=1..L-2} (z[t+1] - 2 z[t] + z[t-1])^2,      g = guide_scale[level] * d log p / d z,
+     * and every denoise step uses g where the reference uses cond_fn's value (condition_score in the DDIM loops, condition_mean in the
+     * DDPM loop).  guide_space DSH_GUIDE_XT: z is the noisy sample, the reference's cond_fn(x, t) contract; DSH_GUIDE_X0: z is the step's
+     * pred_xstart (after clip_denoised), the denoiser's Jacobian not applied.  Frames >= L have gradient 0.  No draw is added.
+     * -1 before any state changes: with the reverse loop; on an unknown space; on n_guide_scale other than 0 or the run's level count
+     * (respacing in the DDIM loops, diffusion_steps in the DDPM loop); on target / weight whose guide_batch / guide_frames /
+     * guide_channels differ from the condition's [B, T, C], on vel / acc whose guide_channels differs from C. */
+    int32_t guidance;
+    int32_t guide_space;
+    int32_t n_guide_scale;   /* 0: scale 1 at every level                                                                       */
+    int32_t guide_batch, guide_frames, guide_channels;   /* the shape the caller built the guide tensors for                    */
+    const float* guide_target; /* Y, device [B,T,C] or NULL (0)                                                                  */
+    const float* guide_weight; /* W >= 0, device [B,T,C] or NULL (no attraction term)                                            */
+    const float* guide_vel;    /* device [C] or NULL                                                                             */
+    const float* guide_acc;    /* device [C] or NULL                                                                             */
+    const float* guide_scale;  /* host, n_guide_scale entries, indexed by spaced level; a level with scale 0 runs unguided      */
 } dsh_run_spec;
+#define DSH_GUIDE_XT 0
+#define DSH_GUIDE_X0 1
 /* Runs the forward loops and the reverse loop.  Asynchronous on the context stream, except that new row keys / seeds are copied to the
  * device and waited for before the loop is queued (they are caller memory).  -1 before any state changes on everything dsh_sample and
  * dsh_invert_from refuse, with the same messages.  The sticky values of the dsh_sample_set_* setters are neither read nor changed. */
@@ -597,6 +618,32 @@ int dsh_op_dpm2m_step(void* hip_stream, float* x, const float* eps, float* x0_pr
  * update (c_hi <= c_lo: all); x0_out nullable. */
 int dsh_op_ddpm_step(void* hip_stream, float* x, const float* eps, const float* noise, float* x0_out, int64_t n, float c1, float c2, float coef1,
                      float coef2, float sigma, int32_t clip, int32_t channels, int32_t c_lo, int32_t c_hi);
+/* The guidance terms of one launch (dsh_run_spec's guide_* fields, for one step): all device pointers but lens_host; any of target,
+ * weight, vel, acc may be NULL (weight NULL: no attraction term; target NULL: 0).  lens_dev / lens_host [B]: per-clip frame counts in
+ * 1 .. frames, both or neither. */
+typedef struct dsh_guide {
+    const float* target; const float* weight; const float* vel; const float* acc;
+    const int32_t* lens_dev; const int32_t* lens_host;
+    float scale;
+    int32_t space;           /* DSH_GUIDE_XT / DSH_GUIDE_X0 (read by the two step entries) */
+} dsh_guide;
+/* g [B, frames, channels] = scale * d log p / d z for z [B, frames, channels] (the formula at dsh_run_spec), columns [c_lo, c_hi) (0 / 0:
+ * all; other columns of g are not written); frames >= a clip's length receive 0.  g must not alias z. */
+int dsh_op_guidance_grad(void* hip_stream, const float* z, float* g, int32_t B, int32_t frames, int32_t channels, int32_t c_lo, int32_t c_hi,
+                         const dsh_guide* guide);
+/* The guided form of dsh_op_ddim_step_full (second_order = 0) and of dsh_op_dpm2m_step (second_order != 0; x0_out is the history), one pass
+ * in place: x0 = c1 x - c2 eps (clamped when clip), e = (c1 x - x0) / c2, e' = e - sqrt_1m_ab g, x0' = c1 x - c2 e', then the parent's
+ * update from x0' (x0_out receives x0').  g is taken on x (DSH_GUIDE_XT) or on x0 (DSH_GUIDE_X0: the neighbouring frames' x0 are
+ * re-derived from their x and eps).  An element whose g is exactly 0 takes the parent's update bit for bit.  Columns outside
+ * [c_lo, c_hi) and frames >= a clip's length are not touched.  No saved noisy tails in this entry. */
+int dsh_op_guided_ddim_step(void* hip_stream, float* x, const float* eps, float* x0_out, const float* gt, const uint8_t* mask, const float* noise2,
+                            const float* noise1, const dsh_guide* guide, int32_t B, int32_t frames, int32_t channels, float c1, float c2,
+                            float sqrt_ab_prev, float sqrt_1m_ab_prev, float coef_eps, float sigma, float sqrt_1m_ab, float A, float Bc, float G,
+                            int32_t second_order, int32_t overlap_len, int32_t blend, int32_t tail_blend, int32_t clip, int32_t c_lo, int32_t c_hi);
+/* The guided form of dsh_op_ddpm_step on x [B, frames, channels]: mean' = mean + post_var g (condition_mean), otherwise as the parent. */
+int dsh_op_guided_ddpm_step(void* hip_stream, float* x, const float* eps, const float* noise, float* x0_out, const dsh_guide* guide, int32_t B,
+                            int32_t frames, int32_t channels, float c1, float c2, float coef1, float coef2, float sigma, float post_var,
+                            int32_t clip, int32_t c_lo, int32_t c_hi);
 /* x <- sqrt_1m_beta x + sqrt_beta noise; a channel range needs the channel count. */
 int dsh_op_undo_step(void* hip_stream, float* x, const float* noise, float sqrt_1m_beta, float sqrt_beta, int64_t n, int32_t channels,
                      int32_t c_lo, int32_t c_hi);
