@@ -235,7 +235,7 @@ LOSS_HEADER, LOSS_COLS = 8, 7      # the header's loss macros: batch scalars in 
 # (indices 4 and 7 are retired: their kernel forms were removed, the counts stay 0; the names keep the indices fixed)
 LAUNCH_FAMILIES = ("tl1", "tl2_loop", "tl2_roll", "tl2_roll_hl", "tl4", "tls", "ffn_fused", "ffn_fused_sty", "attn_mfma", "attn_rowmajor",
                    "gemm_f32_fewrow", "gemm_f32_tiled", "gemm_f32_pro", "eval_streams", "sample_streams", "sample_graph", "sample_pipe",
-                   "gemv", "gemm_bf16_tiled", "gemm_tile_pick", "gemm_f32_split")
+                   "gemv", "gemm_bf16_tiled", "gemm_tile_pick", "gemm_f32_split", "gemm_f32_split_128")
 
 
 def launch_counts(reset: bool = False) -> dict:

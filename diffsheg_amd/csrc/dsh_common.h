@@ -134,6 +134,7 @@ enum LaunchFamily {
     LC_GEMM_BF16_TILED,    // bf16 tiled GEMM (gemm.hip)
     LC_GEMM_TILE_PICK,     // (value) tile shape of the last tiled GEMM launch: 0 128 x 128, 1 128 x 64, 2 64 x 64, 3 64 x 32, 4 the unswizzled 128 x 128 form
     LC_GEMM_F32_SPLIT,     // gemm_f32_pro launches on the split-bf16 main loop (gemm_f32_split.hip); LC_GEMM_F32_PRO counts the exact-fp32 ones only
+    LC_GEMM_F32_SPLIT_128, // of those, the launches that took the 128 x 128 instantiation (LC_GEMM_F32_SPLIT keeps counting both tiles)
     LC_COUNT
 };
 extern std::atomic<long long> g_launch_counts[LC_COUNT];

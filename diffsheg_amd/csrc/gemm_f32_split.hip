@@ -314,6 +314,7 @@ static int launch_gs(const GemmProArgs& a, hipStream_t s) {
     const long long blocks = b.nt_m >= 8 ? (long long)ceil_div(b.nt_m, 8) * 8 * b.nt_n : (long long)b.nt_m * b.nt_n;
     DSH_REQUIRE(blocks < (1ll << 31), "gemm_f32_pro (split bf16): too many tiles");
     count_launch(LC_GEMM_F32_SPLIT);
+    if (MI == 2) count_launch(LC_GEMM_F32_SPLIT_128);
     hipLaunchKernelGGL((gemm_f32_split_kernel<PRO, MI>), dim3((unsigned)blocks), dim3(256), gs_lds_bytes(MI), s, b);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;

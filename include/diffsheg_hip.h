@@ -473,8 +473,9 @@ int32_t dsh_debug_last_tl_variant(void);
  *  two more counts: 17 weight-streaming GEMV (at most 16 rows, fp32 and bf16), 18 bf16 tiled GEMM;
  *  and one more value: 19 tile shape of the last tiled GEMM launch (0 128 x 128, 1 128 x 64, 2 64 x 64, 3 64 x 32, 4 the unswizzled
  *   128 x 128 form of DSH_GEMM_VARIANT=0);
- *  and one more count: 20 gemm_f32_pro split-bf16 launches (DSH_PRECISION_BF16X3, dsh_op_gemm_f32_pro_ex with mma 1). */
-#define DSH_LAUNCH_COUNT_ENTRIES 21
+ *  and two more counts: 20 gemm_f32_pro split-bf16 launches (DSH_PRECISION_BF16X3, dsh_op_gemm_f32_pro_ex with mma 1), both tile shapes;
+ *   21 those of them that took the 128 x 128 instantiation. */
+#define DSH_LAUNCH_COUNT_ENTRIES 22
 int32_t dsh_debug_launch_counts(int64_t* out, int32_t cap, int32_t reset);
 int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W, const float* bias, const float* R,
                      float* Cf, void* Ct, int32_t M, int32_t N, int32_t act, const float* gamma, const float* beta,

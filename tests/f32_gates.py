@@ -416,7 +416,17 @@ def gate(t):
     two to three orders above every other row): it gets the allowance of its own N elements, and the other rows are not loosened by it."""
     if "_gate" not in t:
         ref = ref64(t)
-        err = torch.maximum(*((chain(t, reverse=r).double() - ref).abs() for r in (False, True)))
+        cols = t.get("cal_cols")
+        if cols is None:
+            err = torch.maximum(*((chain(t, reverse=r).double() - ref).abs() for r in (False, True)))
+        else:
+            # a PRO 0 launch with thousands of output columns (the FiLM table's N = 16 384): the single-accumulator fp32 chain costs K passes
+            # over [rows, N], so the calibration is taken over a SAMPLE of the columns (every column draws W and b from one distribution).  A
+            # maximum over fewer elements is never larger than the maximum over all of them: the allowance can only shrink by this.
+            assert t["kind"] == "pro0" and len(cols) >= 512, "column-sampled calibration: PRO 0, at least 512 columns"
+            s = {k: v for k, v in t.items() if not k.startswith("_") and k != "cal_cols"}
+            s.update(W=t["W"][cols], b=t["b"][cols], N=len(cols), R=None if t["R"] is None else t["R"][:, cols])
+            err = torch.maximum(*((chain(s, reverse=r).double() - ref[:, cols]).abs() for r in (False, True)))
         rest = torch.ones(err.shape[0], dtype=torch.bool)
         rest[t.get("special", [])] = False
         cal = float(err[rest].max())

@@ -176,6 +176,60 @@ def rejected(fn, t, out):
     return False
 
 
+# ---- the Linears Denoiser<float> launches on the split loop --------------------------------------------------------------------------------
+# Read off diffsheg_amd/csrc/denoiser.hip: every fp32 Linear of more than 512 rows goes through gemm() (:348-369, PRO 0) or gemm_pro()
+# (:371-388, PRO 1 / 2), and pick_mma() (:286) hands both the packed weight under precision "bf16x3".  One row per FORM (N, K, front,
+# activation, residual), for both configs (SHOW: C = 129 | 103, T = 88; BEAT: 141 | 51, T = 34) and the single-transformer model (SHOW, all
+# 232 channels); D = 512, ff = 1024, time embedding 2 048, FiLM table 8 layers x 4 D = 16 384, encoder_aud D = 128.  The row's `where` names
+# the call.  The activation codes are the launch's: 0 none, 1 SiLU, 2 GELU.  The funnel takes a Linear only with a bias, N % 4 == 0, no
+# periodic residual and no activation behind the residual: joint_embed (positional residual, :1055 / :1059), time_embed.2 of the motion
+# encoders (SiLU behind the speaker term, :1018), the `out` heads of 129 / 103 / 141 / 51 columns and encoder_aud's last Linear (two outputs,
+# :1228) stay on the tiled GEMM and have no row here.  conv2 (K = 384) has no bias today, so the funnel passes it by as well; its form is
+# kept in the table - it is the only K that is a multiple of 32 and not of 64 besides the grid's 32 and 96, and a bias would put it on
+# this loop unnoticed.
+FILM_LAST = 7 * 4 * 512                       # FiLM offset of layer 7's attention-branch StylizationBlock (run_encoder: l * 4 * D)
+MODEL_LINEARS = {
+    # ---- set_condition: the HuBERT-feature conv pair as GEMMs over im2col rows
+    "conv1":          ("denoiser.hip:931 gemm(E->conv1), K = 3 x 1 024", lambda M: G.pro0_inputs(M, 128, 3072, act=2, res=False)),
+    "conv2":          ("denoiser.hip:934 / :936 gemm(E->conv2), K = 3 x 128", lambda M: G.pro0_inputs(M, 128, 384, act=0, res=False)),
+    # ---- the embedding Linears, on the batch's clips (above 512 clips)
+    "time_embed.0":   ("denoiser.hip:1017 / :1197 gemm(te0)", lambda M: G.pro0_inputs(M, 2048, 512, act=1, res=False)),
+    "aud_time_embed.2": ("denoiser.hip:1198 gemm(aud_te2)", lambda M: G.pro0_inputs(M, 2048, 2048, act=1, res=False)),
+    "pid_embed.2":    ("denoiser.hip:912 gemm(E->pe2)", lambda M: G.pro0_inputs(M, 2048, 2048, act=0, res=False)),
+    "film":           ("denoiser.hip:1019 gemm(E.film): the stacked FiLM Linears", lambda M: dict(G.pro0_inputs(M, 16384, 2048, act=0, res=False), cal_cols=torch.arange(0, 16384, 16))),
+    "aud_film":       ("denoiser.hip:1199 gemm(aud_film)", lambda M: G.pro0_inputs(M, 512, 2048, act=0, res=False)),
+    # ---- per evaluation, on the conditional rows
+    "audio_proj":     ("denoiser.hip:1025 / :1028 gemm(E.aproj), [mel | aud_feat]", lambda M: G.pro0_inputs(M, 256, 256, act=0, res=False)),
+    "audio_proj-single": ("denoiser.hip:1028 gemm(E.aproj), the mel features alone", lambda M: G.pro0_inputs(M, 256, 128, act=0, res=False)),
+    "feat_proj.1-show-ges": ("denoiser.hip:1087 gemm_pro(L.f1, 1): h | audio_proj | hubert | 103 of 128", lambda M: G.pro1_inputs(M, 1024, (512, 256, 128, 128), 999, act=1, ld_extra=0)),
+    "feat_proj.1-beat-ges": ("denoiser.hip:1087 gemm_pro(L.f1, 1): h | audio_proj | hubert | 51 of 64", lambda M: G.pro1_inputs(M, 1024, (512, 256, 128, 64), 947, act=1, ld_extra=0)),
+    "feat_proj.1-exp": ("denoiser.hip:1087 gemm_pro(L.f1, 1): three segments", lambda M: G.pro1_inputs(M, 1024, (512, 256, 128, 0), 896, act=1, ld_extra=0)),
+    "feat_proj.1-off-200": ("denoiser.hip:1087, rows at offset -200 (the PRO 1 shift)", lambda M: G.pro1_inputs(M, 1024, (512, 256, 128, 128), 999, act=1, ld_extra=0, family="off-200")),
+    "feat_proj.3":    ("denoiser.hip:1088 gemm(L.f3), in-place residual", lambda M: G.pro0_inputs(M, 512, 1024, act=0, res=True, alias=True)),
+    # ---- per evaluation, on both CFG halves
+    "qkv-folded":     ("denoiser.hip:982 gemm_pro(L.qkv, 1)", lambda M: G.pro1_inputs(M, 1536, (512, 0, 0, 0), 512, act=0, ld_extra=0)),
+    "qkv":            ("denoiser.hip:978 / :981 gemm(L.qkv)", lambda M: G.pro0_inputs(M, 1536, 512, act=0, res=False)),
+    "sty1.out-show":  ("denoiser.hip:995 gemm_pro(L.sty1.out, 2), T = 88, last layer's FiLM offset", lambda M: G.pro2_inputs(M, 512, 512, 88, 6, film_off=FILM_LAST)),
+    "sty1.out-beat":  ("denoiser.hip:993 gemm(L.sty1.out), front in the attention launch", lambda M: G.pro0_inputs(M, 512, 512, act=0, res=True, alias=True)),
+    "ffn.linear1":    ("denoiser.hip:1000 gemm(L.ffn1)", lambda M: G.pro0_inputs(M, 1024, 512, act=2, res=False)),
+    "ffn.linear2":    ("denoiser.hip:1001 gemm(L.ffn2)", lambda M: G.pro0_inputs(M, 512, 1024, act=0, res=False)),
+    "sty2.out-beat":  ("denoiser.hip:1002 gemm_pro(L.sty2.out, 2), T = 34, FiLM offset + 2 D", lambda M: G.pro2_inputs(M, 512, 512, 34, 19, film_off=FILM_LAST + 1024)),
+    "out-single":     ("denoiser.hip:1179 gemm(E.out): 232 columns (the heads of 129 / 103 / 141 / 51 are not multiples of 4)", lambda M: G.pro0_inputs(M, 232, 512, act=0, res=False)),
+    # ---- encoder_aud (D = 128), on the conditional rows
+    "aud.qkv":        ("denoiser.hip:505 gemm(aud.qkv)", lambda M: G.pro0_inputs(M, 384, 128, act=0, res=False)),
+    "aud.sty1.out":   ("denoiser.hip:958 gemm(L.sty1.out), residual from another buffer", lambda M: G.pro0_inputs(M, 128, 128, act=0, res=True, alias=False)),
+    "aud.ffn.linear1": ("denoiser.hip:959 gemm(L.ffn1)", lambda M: G.pro0_inputs(M, 1024, 128, act=2, res=False)),
+    "aud.ffn.linear2": ("denoiser.hip:960 gemm(L.ffn2)", lambda M: G.pro0_inputs(M, 128, 1024, act=0, res=False)),
+}
+MODEL_M = (513, 641)        # the smallest row count on the split loop (f32_min_rows + 1), and one that straddles the 128-row tile edge at 640
+
+
+def model_case(name, M):
+    t = MODEL_LINEARS[name][1](M)
+    t["name"] = f"split-model-{name}-M{M}"
+    return t
+
+
 # ---- the family cases of the CPU test (K = 512, and 960 with 13 padded columns for PRO 1) ------------------------------------------------
 def family_case(pro, family, K):
     if pro == 0:

@@ -14,7 +14,14 @@ Measured on an MI355X when this file was written (the tests print the figures): 
 cases — bf16 max 2.5e-2 / rms 5.2e-3 in every regime (window-chain 2.49e-2, first generation 2.49e-2, fused FFN 2.40e-2, rolling
 hi / lo 2.33e-2, row-major attention 2.36e-2; dense small grid 2.51e-2), fp32 max 7.2e-6; loops against the rows sampled alone — bf16
 2.3e-3, fp32 6.4e-7, against the oracle's loop 4.4e-3 / 7.2e-7; guidance scale 1 at B = 140, unsplit vs two sub-batch streams 1.7e-3.
-The whole file takes about 70 s, the 91 evaluation cases 18 s of it."""
+The whole file took about 70 s with its 91 bf16 / fp32 evaluation cases (18 s of it).
+
+precision "bf16x3" is walked as a third precision with fp32's storage rules: `split_tile_128` restates the tile rule of the split-bf16
+loop, `split_linears` / `expected_split_launches` every Linear an instance sends through the gemm() / gemm_pro() funnel, and both counters
+(`gemm_f32_split`, `gemm_f32_split_128`) are compared exactly at every bf16x3 case — on either side of the 512-row limit, of the two stream
+splits and of the three tile limits (N = 1 536 / 1 024 / 512).  Measured: worst |eps - oracle| 3.9e-5 with 64 x 64 tiles only (the
+single-transformer model), 3.6e-5 with both tiles in one evaluation, 2.2e-6 at or below 512 rows (the fp32 kernels); with the 18 bf16x3
+evaluation cases and the two bf16x3 dense grids the whole file takes 79 s, its 109 evaluation cases 22 s of it."""
 import ctypes as C
 import time
 
@@ -29,7 +36,7 @@ from diffsheg_amd.synthetic import make_inputs  # noqa: E402
 from diffsheg_amd.trainer import DDPMTrainer, sampler_namespace  # noqa: E402
 from oracle import denoiser_ref, sampler_ref  # noqa: E402
 from test_gpu_eval import BF16_MAX, BF16_RMS, FP32_ATOL  # noqa: E402  (the evaluation gates, unchanged)
-from util import WEIGHT_SEED, gpu_model, gpu_single_model, rel_err, synthetic_sd  # noqa: E402
+from util import WEIGHT_SEED, gpu_model, gpu_single_model, rel_err, sample_clips, sub_batches, synthetic_sd  # noqa: E402
 
 LOOP_TOL = {"fp32": 1e-5, "bf16": 1.2e-2}            # a clip of a batched loop vs the clip sampled alone (test_gpu_sharded.py)
 LOOP_ORACLE_TOL = {"fp32": 1e-3, "bf16": 1.2e-2}     # ... vs the oracle's 25-step loop from the same x_T
@@ -45,8 +52,12 @@ HL_STY_ROWS, HL_F3_ROWS = 128 * 256, 128 * 128                         # denoise
 ROLL_MIN_BLOCKS = 128                                                  # tl2.hip launch_tl2_linear: N split below this many token blocks
 ATTN_MFMA_FRAMES = 96                                                  # denoiser.hip run_encoder
 SPLIT = {"bf16": (12288, 21500), "fp32": (4096, 2900)}                 # denoiser_context.hip: (min rows, rows per stream)
+SPLIT["bf16x3"] = SPLIT["fp32"]                                        # precision "bf16x3" is fp32 storage: the same stream rules
+F32_PRECS = ("fp32", "bf16x3")
 F32_FEWROW = 512                                                       # denoiser.hip f32_min_rows / gemm.hip ks_rows
 GRAPH_ROWS, PIPE_ROWS = 4096, 64499                                    # sampler.hip
+
+SPLIT_TILE_BLOCKS = 256                                                # gemm_f32_split.hip launch_gemm_f32_split: 128 x 128 tiles where they fill 256 CUs
 
 TL_FAMILIES = ("tl1", "tl2_loop", "tl2_roll", "tl2_roll_hl", "tl4", "tls", "ffn_fused", "ffn_fused_sty", "attn_mfma", "attn_rowmajor")
 
@@ -68,9 +79,54 @@ def n_streams(prec, B, T):
     return min(3, max(2, rows // per_stream), B)
 
 
-def sub_batches(B, ns):
-    """DenoiserContext: first_clip, clips [B i / ns, B (i + 1) / ns)."""
-    return [(B * i // ns, B * (i + 1) // ns) for i in range(ns)]
+def split_tile_128(M, N):
+    """gemm_f32_split.hip launch_gemm_f32_split (`mi`): the 128 x 128 instantiation where its tiles fill the 256 CUs at least once, the
+    64 x 64 one below.  The tile depends on N: q|k|v (N = 1 536, 12 column tiles) flips at M >= 2 689 rows, N = 1 024 at 3 969, N = 512 at 8 065."""
+    return _ceil_div(M, 128) * _ceil_div(N, 128) >= SPLIT_TILE_BLOCKS
+
+
+def doubled_rows(prec, doubled, Mc):
+    """denoiser.hip run_encoder (r0): rows of a launch that carries both CFG halves.  The token-per-lane path starts the conditional half
+    at the next 256-row block; fp32 storage ("fp32", "bf16x3") packs the halves: 2 Mc."""
+    if not doubled:
+        return Mc
+    return _round_up(Mc, 256) + Mc if prec == "bf16" else 2 * Mc
+
+
+def split_linears(kind, nb, T):
+    """(name, N, rows) of every Linear ONE sub-batch instance of nb clips sends through the gemm() / gemm_pro() funnel for one conditioning
+    and one evaluation with a timestep per clip (denoiser.hip; tests/split_gates.py MODEL_LINEARS names the line of each).  Under
+    precision "bf16x3" the funnel launches the split loop for those with more than F32_FEWROW rows.  Not in the list, because the funnel's
+    conditions send them to the tiled GEMM at any size: joint_embed, the motion encoders' time_embed.2, conv2 (no bias), encoder_aud's last
+    Linear, pid_embed (one row per distinct speaker) and an `out` head whose width is no multiple of 4."""
+    doubled = _doubled(kind)
+    Mc = nb * T
+    M = doubled_rows("bf16x3", doubled, Mc)
+    cins = {"show": (103, 129), "beat": (51, 141), "single": (232,)}[kind]           # config.py: expression | gesture channels
+    out = []
+    for cin in cins:
+        out += [("conv1", 128, Mc), ("time_embed.0", 2048, nb), ("film", LAYERS * 4 * 512, nb), ("audio_proj", 256, Mc)]
+        for _ in range(LAYERS):
+            out += [("feat_proj.1", 1024, Mc), ("feat_proj.3", 512, Mc), ("qkv", 1536, M), ("sty1.out", 512, M), ("ffn.linear1", 1024, M),
+                    ("ffn.linear2", 512, M), ("sty2.out", 512, M)]
+        if cin % 4 == 0:
+            out.append(("out", cin, M))
+    if kind != "single":                                                             # encoder_aud (D = 128) and UniDiffuser.time_embed
+        out += [("aud.qkv", 384, Mc), ("aud_time_embed.0", 2048, nb), ("aud_time_embed.2", 2048, nb), ("aud_film", 512, nb),
+                ("aud.sty1.out", 128, Mc), ("aud.ffn.linear1", 1024, Mc), ("aud.ffn.linear2", 128, Mc)]
+    return out
+
+
+def expected_split_launches(kind, B, T):
+    """(split launches, those of them on the 128 x 128 tile) of ONE bf16x3 conditioning + evaluation, summed over its sub-batch instances:
+    what `gemm_f32_split` and `gemm_f32_split_128` must read, both exactly."""
+    total = big = 0
+    for lo, hi in sub_batches(B, n_streams("bf16x3", B, T)):
+        for _, N, rows in split_linears(kind, hi - lo, T):
+            if rows > F32_FEWROW:
+                total += 1
+                big += int(split_tile_128(rows, N))
+    return total, big
 
 
 def refused(prec, B, T):
@@ -145,9 +201,19 @@ def _inst(case):
     model, prec, B, T = case
     lo, hi = max(sub_batches(B, n_streams(prec, B, T)), key=lambda r: r[1] - r[0])
     Mc = (hi - lo) * T
-    return Mc, (_round_up(Mc, 256) + Mc if _doubled(model) else Mc), hi - lo
+    return Mc, doubled_rows(prec, _doubled(model), Mc), hi - lo
 
 
+def _smallest_show_batch_with_n512_on_the_large_tile(T=88):
+    """The smallest SHOW batch whose largest instance, with the CFG doubling (2 Mc in fp32 storage), puts the N = 512 Linears on the
+    128 x 128 tile — derived from the restated rules; it lies below the two-stream limit of 4096 conditional rows (46 x 88 = 4048)."""
+    B = 1
+    while not split_tile_128(_inst(("show", "bf16x3", B, T))[1], 512):
+        B += 1
+    return B
+
+
+TILE512_B = _smallest_show_batch_with_n512_on_the_large_tile()
 S, Bt, Sg = "show", "beat", "single"
 BOUNDARIES = [
     dict(name="feat_proj.1: window-chain kernels up to 2048 rows", where="denoiser.hip kTlRoles tls_rows (TL_FEAT1)",
@@ -210,6 +276,26 @@ BOUNDARIES = [
     dict(name="fp32: three sub-batch streams from 8700 token rows", where="denoiser_context.hip (precision 0)",
          side=lambda c: c[2] * c[3] >= 8700,
          cases=[(Bt, "fp32", 255, 34), (Bt, "fp32", 256, 34)]),
+    # ---- precision "bf16x3": fp32 storage, the Linears of more than 512 rows on the split-bf16 loop (gemm_f32_split.hip)
+    dict(name="bf16x3: the fp32 kernels up to 512 rows, the split loop above (a change of arithmetic)", where="denoiser.hip gemm() / f32_now(): f32_min_rows",
+         side=lambda c: c[2] * c[3] <= 512,
+         cases=[(Bt, "bf16x3", 15, 34), (Bt, "bf16x3", 16, 34), (S, "bf16x3", 8, 64), (S, "bf16x3", 8, 65)]),
+    dict(name="bf16x3: two sub-batch streams from 4096 token rows", where="denoiser_context.hip (fp32 storage)",
+         side=lambda c: c[2] * c[3] >= 4096,
+         cases=[(Bt, "bf16x3", 120, 34), (Bt, "bf16x3", 121, 34), (S, "bf16x3", 63, 65), (S, "bf16x3", 64, 64)]),
+    dict(name="bf16x3: three sub-batch streams from 8700 token rows", where="denoiser_context.hip (fp32 storage)",
+         side=lambda c: c[2] * c[3] >= 8700,
+         cases=[(Bt, "bf16x3", 255, 34), (Bt, "bf16x3", 256, 34)]),
+    dict(name="bf16x3 q|k|v (N = 1536): 128 x 128 tile from 2689 rows", where="gemm_f32_split.hip launch_gemm_f32_split (mi)",
+         side=lambda c: split_tile_128(_inst(c)[1], 1536),
+         cases=[(Bt, "bf16x3", 79, 34), (Bt, "bf16x3", 80, 34), (Sg, "bf16x3", 15, 88), (Sg, "bf16x3", 16, 88)]),
+    dict(name="bf16x3 feat_proj.1 / ffn.linear1 (N = 1024): 128 x 128 tile from 3969 rows", where="gemm_f32_split.hip launch_gemm_f32_split (mi)",
+         side=lambda c: split_tile_128(_inst(c)[1], 1024),
+         cases=[(Bt, "bf16x3", 116, 34), (Bt, "bf16x3", 117, 34)]),
+    dict(name="bf16x3 N = 512 Linears (StylizationBlock with the CFG-null row constant, feat_proj.3, ffn.linear2): 128 x 128 tile from 8065 rows",
+         where="gemm_f32_split.hip launch_gemm_f32_split (mi); denoiser.hip run_encoder: M = 2 Mc",
+         side=lambda c: split_tile_128(_inst(c)[1], 512),
+         cases=[(S, "bf16x3", TILE512_B - 1, 88), (S, "bf16x3", TILE512_B, 88)]),
 ]
 
 
@@ -242,10 +328,22 @@ def test_boundary_table_is_well_formed():
         sides = {bool(row["side"](c)) for c in row["cases"]}
         assert sides == {True, False}, (row["name"], sides)
     assert not [c for c in CASES if refused(c[1], c[2], c[3])]
-    grid = [(m, p, b, t) for m in ("show", "beat") for p in ("bf16", "fp32") for b in DENSE_B for t in DENSE_T] + CASES
+    grid = [(m, p, b, t) for m in ("show", "beat") for p in ("bf16", "fp32", "bf16x3") for b in DENSE_B for t in DENSE_T] + CASES
     inside = [c for c in grid if refused(c[1], c[2], c[3])]
     before = [c for c in grid if refused_before(c[1], _doubled(c[0]), c[2], c[3])]
     assert set(inside) <= set(before)
+    assert not [c for c in inside if c[1] in F32_PRECS]                       # fp32 storage refuses nothing, with either main loop
+    # the bf16x3 rows: the tile limits are where the docstring of split_tile_128 puts them, the derived SHOW batch is the smallest one, every
+    # bf16x3 case above the few-row limit has split launches to count, and the cases around the tile limits mix both instantiations
+    assert [min(m for m in range(1, 20000) if split_tile_128(m, n)) for n in (1536, 1024, 512)] == [2689, 3969, 8065]
+    assert TILE512_B * 88 < SPLIT["bf16x3"][0] and not split_tile_128(_inst(("show", "bf16x3", TILE512_B - 1, 88))[1], 512)
+    x3 = [c for c in CASES if c[1] == "bf16x3"]
+    assert {c[0] for c in x3} == {"show", "beat", "single"}
+    for c in x3:
+        total, big = expected_split_launches(c[0], c[2], c[3])
+        assert (total > 0) == (_inst(c)[1] > F32_FEWROW) and 0 <= big <= total, (c, total, big)
+    mixes = {c: expected_split_launches(c[0], c[2], c[3]) for c in x3}
+    assert any(0 < big < total for total, big in mixes.values()) and any(big == 0 < total for total, big in mixes.values())
     print(f"[dispatch sweep] {len(CASES)} evaluation cases over {len(BOUNDARIES)} boundaries; refused region: {len(inside)} of {len(grid)} grid shapes "
           f"({100.0 * len(inside) / len(grid):.1f} %), was {len(before)} ({100.0 * len(before) / len(grid):.1f} %)")
 
@@ -288,22 +386,8 @@ def _oracle(kind, sd, cfg, inp, t, c1, c2, rows):
 
 
 def _sample_clips(prec, B, T, cap=10):
-    """First and last clip, both sides of every sub-batch split, the first clips that straddle a 32-, 128- and 256-token block boundary,
-    and two interior ones."""
-    picks = [0, B - 1]
-    for lo, _ in sub_batches(B, n_streams(prec, B, T))[1:]:
-        picks += [lo - 1, lo]
-    for blk in (256, 128, 32):
-        for b in range(1, B):
-            if (b * T) // blk != ((b + 1) * T - 1) // blk and (b * T) % blk and b not in picks:
-                picks.append(b)
-                break
-    picks += [B // 3, (5 * B) // 7]
-    out = []
-    for b in picks:
-        if 0 <= b < B and b not in out:
-            out.append(b)
-    return out[:cap]
+    """util.sample_clips on the sub-batch split the restated rules give this case."""
+    return sample_clips(B, T, n_streams(prec, B, T), cap)
 
 
 def _compare(prec, got, ref, rows, tag):
@@ -313,7 +397,7 @@ def _compare(prec, got, ref, rows, tag):
         d = (got[j].double() - ref[j].double())
         e, rms = float(d.abs().max()), float(d.pow(2).mean().sqrt())
         wm, wr = max(wm, e), max(wr, rms)
-        if prec == "fp32":
+        if prec in F32_PRECS:                             # bf16x3 claims the fp32 bar: the gate is the project's 1e-3, not a measurement
             assert e < FP32_ATOL, (tag, "clip", r, e)
         else:
             assert e < BF16_MAX and rms < BF16_RMS, (tag, "clip", r, e, rms)
@@ -346,6 +430,20 @@ def test_evaluation_at_dispatch_boundary(case):
     assert got["eval_streams"] == n_streams(prec, B, T), (case, got)
     exp = expected_launches(kind, prec, _doubled(kind), B, T)
     assert {k: got[k] for k in TL_FAMILIES} == exp, (case, {k: (got[k], exp[k]) for k in TL_FAMILIES if got[k] != exp[k]})
+    if prec != "bf16x3":
+        assert got["gemm_f32_split"] == 0 and got["gemm_f32_split_128"] == 0, (case, got)
+    else:
+        # the split launches and their tile, both exactly as the restated rules give them; no exact-fp32 gemm_f32_pro launch at any size
+        # (at or below the few-row limit the fp32 kernels run: the few-row K-split GEMM, as for "fp32")
+        want = expected_split_launches(kind, B, T)
+        print(f"[dispatch sweep {case}] split launches (all, 128 x 128): counted {(got['gemm_f32_split'], got['gemm_f32_split_128'])}, restated rules {want}")
+        assert (got["gemm_f32_split"], got["gemm_f32_split_128"]) == want, (case, got, want)
+        assert got["gemm_f32_pro"] == 0, (case, got)
+        if B * T <= F32_FEWROW and not _doubled(kind):
+            assert got["gemm_f32_split"] == 0 and got["gemm_f32_fewrow"] > 0 and got["gemm_f32_tiled"] == 0, (case, got)
+        SPLIT_SEEN[case] = (got["gemm_f32_split"], got["gemm_f32_fewrow"])
+    if prec in F32_PRECS:
+        EPS_SEEN[case] = eps
     if prec == "fp32":
         # (Linears of at most 16 rows — the embeddings of a small batch — take the weight-streaming kernel, which is none of the three)
         if B * T <= F32_FEWROW and not _doubled(kind):
@@ -363,7 +461,11 @@ def test_evaluation_at_dispatch_boundary(case):
         per_clip = eps.abs().mean(dim=(1, 2))
         med = float(per_clip.median())
         assert float(per_clip.max()) < 3.0 * med and float(per_clip.min()) > 0.3 * med, (case, float(per_clip.min()), med, float(per_clip.max()))
-    reg = (prec, _regime(exp) if prec == "bf16" else f"streams={got['eval_streams']},pro={int(got['gemm_f32_pro'] > 0)}")
+    if prec == "bf16x3":
+        mix = "none" if not want[0] else "64 x 64" if not want[1] else "128 x 128" if want[1] == want[0] else "mixed"
+        reg = (prec, f"streams={got['eval_streams']},tiles={mix}")
+    else:
+        reg = (prec, _regime(exp) if prec == "bf16" else f"streams={got['eval_streams']},pro={int(got['gemm_f32_pro'] > 0)}")
     WORST[reg] = max(WORST.get(reg, (0.0, 0.0)), (wm, wr))
     print(f"[dispatch sweep {case}] families {reg[1]}; {len(rows)} clips {rows}: max|eps-ref| = {wm:.3e}, rms = {wr:.3e}")
     FIRST.setdefault((kind, prec), (case, eps))
@@ -371,6 +473,8 @@ def test_evaluation_at_dispatch_boundary(case):
 
 
 FEWROW_SEEN = {}
+SPLIT_SEEN = {}             # bf16x3 case -> (split launches, few-row launches)
+EPS_SEEN = {}               # fp32-storage case -> eps of its sweep run
 
 
 def test_fp32_few_row_gemm_boundary_with_cfg():
@@ -382,9 +486,33 @@ def test_fp32_few_row_gemm_boundary_with_cfg():
     assert FEWROW_SEEN[a] - FEWROW_SEEN[b] >= 2 * LAYERS * 2, (FEWROW_SEEN[a], FEWROW_SEEN[b])
 
 
+def test_bf16x3_few_row_boundary():
+    """BEAT (no doubling): at 15 x 34 = 510 rows no launch is on the split loop and eps is the fp32 context's eps for the same case bit for
+    bit; at 16 x 34 = 544 every funnel Linear is split and eps is no longer the fp32 bits (the arithmetic changed: were it equal, the
+    split loop would not have run).
+    SHOW doubles the batch: at 8 x 64 = 512 conditional rows the launches that carry both CFG halves (1 024 rows: q|k|v, the two
+    StylizationBlock Linears and the FFN, 5 per layer and encoder) are on the split loop already - exactly those, by the exact count of the
+    sweep case - and the conditional-half launches (feat_proj.1 / feat_proj.3, audio_proj, encoder_aud) still take the few-row kernels; at
+    8 x 65 = 520 rows they cross as well.  So neither SHOW case equals fp32 bit for bit."""
+    lo, hi = ("beat", "bf16x3", 15, 34), ("beat", "bf16x3", 16, 34)
+    a, b = ("show", "bf16x3", 8, 64), ("show", "bf16x3", 8, 65)
+    for c in (lo, hi, a, b):
+        assert c in SPLIT_SEEN and (c[0], "fp32", c[2], c[3]) in EPS_SEEN, "the sweep cases did not run"
+    f32 = lambda c: EPS_SEEN[(c[0], "fp32", c[2], c[3])]
+    assert SPLIT_SEEN[lo][0] == 0 and torch.equal(EPS_SEEN[lo], f32(lo))
+    assert SPLIT_SEEN[hi][0] > 0 and not torch.equal(EPS_SEEN[hi], f32(hi))
+    assert SPLIT_SEEN[a][0] == 2 * LAYERS * 5, SPLIT_SEEN[a]
+    assert SPLIT_SEEN[b][0] - SPLIT_SEEN[a][0] >= 2 * LAYERS * 2 and SPLIT_SEEN[a][1] - SPLIT_SEEN[b][1] >= 2 * LAYERS * 2, (SPLIT_SEEN[a], SPLIT_SEEN[b])
+    assert not torch.equal(EPS_SEEN[a], f32(a)) and not torch.equal(EPS_SEEN[b], f32(b))
+    for c in (hi, a, b):
+        d = float((EPS_SEEN[c].double() - f32(c).double()).abs().max())
+        print(f"[dispatch sweep {c}] max |eps(bf16x3) - eps(fp32)| = {d:.3e}")
+
+
 @pytest.mark.parametrize("key", sorted({c[:2] for c in CASES}), ids=lambda k: f"{k[0]}-{k[1]}")
 def test_context_carries_no_state_through_the_regimes(key):
-    """After a context has walked through every regime of the sweep, its first case evaluates bit-identically to its first run."""
+    """After a context has walked through every regime of the sweep, its first case evaluates bit-identically to its first run.  (A bf16x3
+    context has alternated between the fp32 weights and their packed copies on the way: its cases are ordered large, small, large, ...)"""
     assert key in FIRST, "the sweep cases of this context did not run"
     case, eps0 = FIRST[key]
     *_, eps, got = _run_case(case)
@@ -408,12 +536,13 @@ DENSE_B = (1, 4, 5, 6, 7, 8, 40, 150)
 DENSE_T = (1, 5, 7, 10, 11, 15, 16, 20, 25, 26)
 
 
-@pytest.mark.parametrize("ds,prec", [("show", "bf16"), ("beat", "bf16"), ("show", "fp32"), ("beat", "fp32")])
+@pytest.mark.parametrize("ds,prec", [("show", "bf16"), ("beat", "bf16"), ("show", "fp32"), ("beat", "fp32"), ("show", "bf16x3"), ("beat", "bf16x3")])
 def test_dense_small_grid_is_evaluated_or_refused_cleanly(ds, prec):
     """Every (B, T) of the dense grid on ONE context per dataset and precision, in an order that alternates large and small: a shape
     outside the predicate is never refused and matches the oracle (all clips up to 8, a sample above) with the launches the rules
     predict; a shape inside it raises from the Python shim with a message that names the limit — and the evaluations that follow on
-    the same context keep matching the oracle.  fp32 refuses nothing."""
+    the same context keep matching the oracle.  fp32 storage refuses nothing, with either main loop ("fp32", "bf16x3"); for bf16x3 the grid
+    crosses the 512-row limit back and forth on one context, and the split launches are counted against the restated rules at every shape."""
     model, cfg, sd = _handle(ds, prec)
     shapes = sorted(((b, t) for b in DENSE_B for t in DENSE_T), key=lambda s: (s[0] * s[1], s[0]))
     order = []
@@ -435,6 +564,8 @@ def test_dense_small_grid_is_evaluated_or_refused_cleanly(ds, prec):
             got = _lib.launch_counts()
             exp = expected_launches(ds, prec, _doubled(ds), B, T)
             assert {k: got[k] for k in TL_FAMILIES} == exp, {k: (got[k], exp[k]) for k in TL_FAMILIES if got[k] != exp[k]}
+            if prec == "bf16x3":
+                assert (got["gemm_f32_split"], got["gemm_f32_split_128"]) == expected_split_launches(ds, B, T) and got["gemm_f32_pro"] == 0, got
             assert torch.isfinite(eps).all()
             rows = list(range(B)) if B <= 8 else _sample_clips(prec, B, T, cap=8)
             ref = _oracle(ds, sd, cfg, inp, t, c1, c2, rows)

@@ -16,7 +16,7 @@ from diffsheg_amd.config import get_config  # noqa: E402
 from diffsheg_amd.model import UniDiffuser  # noqa: E402
 from diffsheg_amd.synthetic import SeededNoise, make_inputs  # noqa: E402
 from diffsheg_amd.trainer import DDPMTrainer, sampler_namespace  # noqa: E402
-from util import golden, gpu_model, rel_err, synthetic_sd  # noqa: E402
+from util import assert_split_ran, golden, gpu_model, rel_err, synthetic_sd  # noqa: E402
 
 DEV = "cuda:0"
 REL_TOL = 1e-3          # tests/test_gpu_sampler.py: the fp32 gate of every reference loop fixture, relative to the output range
@@ -256,9 +256,11 @@ def test_full_schedule_through_start_level_is_the_existing_loop():
 
 
 # 4. split property: the loop restarted from its own traced state ends where the loop ended, bit for bit
-@pytest.mark.parametrize("B", [1, 2])
-@pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("ds", ["show", "beat"])
+# (precision "bf16x3": the smallest batches above the 512-row limit of the split-bf16 loop - below it the fp32 kernels run and the fp32 cases say it all)
+RESTART_CASES = [(ds, precision, B) for ds in ("show", "beat") for precision in ("fp32", "bf16") for B in (1, 2)] + [("beat", "bf16x3", 16), ("show", "bf16x3", 6)]
+
+
+@pytest.mark.parametrize("ds,precision,B", RESTART_CASES, ids=[f"{d}-{p}-{b}" for d, p, b in RESTART_CASES])
 def test_restart_from_a_traced_state_is_bit_identical(ds, precision, B, monkeypatch):
     tr, inp, extra, final, trace = _full_run(ds, precision, B)
     for K in (1, 10, 24):
@@ -273,6 +275,8 @@ def test_restart_from_a_traced_state_is_bit_identical(ds, precision, B, monkeypa
             for k in env:
                 monkeypatch.delenv(k)
             assert torch.equal(got, final), (K, env, float((got - final).abs().max()))
+            if precision == "bf16x3" and "DSH_NO_GRAPH" in env:           # (eager evaluations: every launch passes the host-side counters)
+                assert_split_ran(_lib.launch_counts(), (ds, B, K))
             if K == 10:
                 assert flags == (want[0], want[1], 1), (env, flags)
 
@@ -474,6 +478,8 @@ def test_kept_elements_of_a_variation_are_the_input(ds, precision):
 
 
 # 8. the reverse ODE
+# (no precision "bf16x3" case: the fixtures' batches are far below the 512-row limit of the split-bf16 loop, where that precision launches the
+#  fp32 kernels; above the limit the reverse loop runs in the bit-equality test below, and against the oracle it is the forward loop's twin)
 @pytest.mark.parametrize("ds", ["show", "beat"])
 def test_reverse_loop_matches_reference(ds):
     f = golden(f"edit_invert_{ds}.npz")
@@ -492,7 +498,7 @@ def test_reverse_loop_matches_reference(ds):
         assert torch.equal(xs, trace[k]), k
 
 
-@pytest.mark.parametrize("ds,precision,B", [("show", "bf16", 2), ("beat", "fp32", 1), ("show", "fp32", 3)])
+@pytest.mark.parametrize("ds,precision,B", [("show", "bf16", 2), ("beat", "fp32", 1), ("show", "fp32", 3), ("beat", "bf16x3", 16)])
 def test_pipelined_and_sequential_reverse_loops_are_bit_identical(ds, precision, B, monkeypatch):
     cfg = get_config(ds)
     tr = DDPMTrainer(sampler_namespace(cfg), gpu_model(ds, precision))
@@ -505,6 +511,8 @@ def test_pipelined_and_sequential_reverse_loops_are_bit_identical(ds, precision,
         _lib.launch_counts(reset=True)
         outs.append(tr.diffusion_ddim_val.ddim_reverse_sample_loop(tr.encoder, x0, 10, model_kwargs=_kwargs(inp)).clone())
         flags.append(_flags())
+        if precision == "bf16x3" and "DSH_NO_GRAPH" in env:
+            assert_split_ran(_lib.launch_counts(), (ds, B))
         for k in env:
             monkeypatch.delenv(k)
     assert flags == [(1, 1, 1), (1, 0, 1), (0, 1, 1), (1, 1, 1)], flags

@@ -15,7 +15,7 @@ from diffsheg_amd.config import get_config  # noqa: E402
 from diffsheg_amd.diffusion import SpacedDiffusion, diffusion_table  # noqa: E402
 from diffsheg_amd.synthetic import SeededNoise, make_inputs  # noqa: E402
 from diffsheg_amd.trainer import DDPMTrainer, sampler_namespace, window_seed  # noqa: E402
-from util import golden, gpu_model, rel_err  # noqa: E402
+from util import assert_split_ran, golden, gpu_model, rel_err, synthetic_sd  # noqa: E402
 
 DEV = "cuda:0"
 REL_TOL = 1e-3                 # test_gpu_sampler.py: final and per-step corners against a reference fixture, relative to the range
@@ -272,6 +272,38 @@ def test_bf16_logsnr8_dpm2m_error_beside_ddim25():
     assert e8 < 3 * e25
 
 
+def test_logsnr8_dpm2m_on_the_split_loop_matches_the_replay():
+    """precision "bf16x3", BEAT B = 16 (544 rows: the smallest batch on the split-bf16 loop; the fixtures' batch is below the limit and
+    would run the fp32 kernels): the 8-evaluation DPM-Solver++(2M) loop against fewstep_ref.sample_loop driven by the CPU oracle on the same
+    injected noise, under the fixtures' gate of 1e-3 of the range.  The fp32 path's distance on the same run is printed beside it."""
+    from oracle import denoiser_ref, sampler_ref
+    cfg, sd = get_config("beat"), synthetic_sd("beat")
+    B = 16
+    shape = (B, cfg.n_poses, cfg.net_dim_pose)
+    inp = make_inputs(cfg, B, seed=77)
+    d = _spaced(cfg, F.LOGSNR8, "dpm2m")
+
+    def eps_fn(xc, t_orig, c1, c2):
+        with torch.no_grad():
+            return denoiser_ref.unidiffuser(sd, cfg, xc, torch.full((B,), t_orig), c1, c2, inp["audio_emb"], inp["person_id"], inp["pretrain_aud_feat"])
+    ref = F.sample_loop(eps_fn, shape, None, sampler_ref.NoiseSource(seed=9), F.LOGSNR8, solver="dpm2m", overlap_len=cfg.overlap_len)
+    errs = {}
+    for precision in ("bf16x3", "fp32"):
+        src = SeededNoise(9)
+        _lib.launch_counts(reset=True)
+        x = d.ddim_sample_loop(gpu_model("beat", precision), shape, clip_denoised=False, model_kwargs=_kwargs(inp), noise_source=src)
+        torch.cuda.synchronize()
+        c = _lib.launch_counts()
+        assert src.count == 9 and torch.isfinite(x).all()
+        if precision == "bf16x3":
+            assert_split_ran(c, "logsnr8 dpm2m")
+        else:
+            assert c["gemm_f32_split"] == 0
+        errs[precision] = rel_err(x, ref)
+    print(f"[measure] logsnr8 dpm2m beat B={B} against the replay on the oracle: bf16x3 {errs['bf16x3']:.3e} of the range (fp32: {errs['fp32']:.3e})")
+    assert errs["bf16x3"] < REL_TOL
+
+
 # ---- identities, bit for bit -------------------------------------------------------------------------------------------------------
 def _pair(ds, precision, B, kept, y=None, seed=5, trace=False, **kw):
     cfg = get_config(ds)
@@ -331,11 +363,22 @@ def test_pipelined_chains_are_bit_identical(ds, precision, B, monkeypatch):
 def test_sub_batch_streams_equal_the_whole_batch(monkeypatch):
     """SHOW bf16, B = 200 (test_gpu_dispatch_sweep.py's mid-size batch): one batch on the encoder pipeline (default) against two sub-batch
     streams (DSH_PIPE=0); every clip runs the same kernels in both, and every stream addresses its own rows of the history."""
+    _streams_against_the_whole_batch("bf16", 200, monkeypatch)
+
+
+def test_sub_batch_streams_equal_the_whole_batch_on_the_split_loop(monkeypatch):
+    """SHOW bf16x3, B = 47 (4 136 rows: the first batch fp32 storage splits over two streams, and above the graph range): the whole batch
+    has every layer Linear on the 128 x 128 tile (8 272 rows with the null half), its two halves keep the N = 512 ones - the StylizationBlock
+    Linears with the CFG-null row constant among them - on 64 x 64: the bits of the split loop do not depend on the tile."""
+    _streams_against_the_whole_batch("bf16x3", 47, monkeypatch)
+
+
+def _streams_against_the_whole_batch(precision, B, monkeypatch):
     cfg = get_config("show")
-    model = gpu_model("show", "bf16")
+    model = gpu_model("show", precision)
     tr = DDPMTrainer(sampler_namespace(cfg), model)
     tr.set_sampling(10, "logsnr", "dpm2m")
-    B, T, Cc = 200, cfg.n_poses, cfg.net_dim_pose
+    T, Cc = cfg.n_poses, cfg.net_dim_pose
     small = make_inputs(cfg, 64, frames=T, seed=23)
     rep = (B + 63) // 64
     audio = small["audio_emb"].repeat(rep, 1, 1)[:B].cuda().contiguous()
@@ -346,10 +389,13 @@ def test_sub_batch_streams_equal_the_whole_batch(monkeypatch):
     outs, streams = {}, {}
     for env in ("1", "0"):
         monkeypatch.setenv("DSH_PIPE", env)
+        _lib.launch_counts(reset=True)
         outs[env] = tr.generate_batch(audio.clone(), pid.clone(), Cc, {"pretrain_aud_feat": hub.clone()}, {}, seed=11,
                                       row_keys=list(range(300, 300 + B))).clone()
         torch.cuda.synchronize()
         streams[env] = _lib.launch_counts()["sample_streams"]
+        if precision == "bf16x3":
+            assert_split_ran(_lib.launch_counts(), env)
     monkeypatch.delenv("DSH_PIPE")
     assert streams == {"1": 1, "0": 2}, streams
     assert torch.isfinite(outs["1"]).all() and torch.equal(outs["1"], outs["0"]), float((outs["1"] - outs["0"]).abs().max())

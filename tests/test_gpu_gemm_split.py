@@ -142,6 +142,15 @@ def test_segments_film_residual_and_activation_forms(name):
     gated(t)
 
 
+@pytest.mark.parametrize("M", S.MODEL_M)
+@pytest.mark.parametrize("name", list(S.MODEL_LINEARS))
+def test_the_models_own_linear_forms(name, M):
+    """Every (N, K, front, activation, residual) form Denoiser<float> launches on this loop (split_gates.MODEL_LINEARS, read off denoiser.hip):
+    K = 3 072 / 2 048 / 384 and the narrow and the very wide N are outside the grid above, and the split error grows with K.  M = 513 is the
+    smallest row count at which the model leaves the few-row kernels; 641 = 5 x 128 + 1 straddles the 128-row tile edge."""
+    gated(S.model_case(name, M))
+
+
 def test_row_moment_side_channel_is_refused():
     t = G.pro0_inputs(130, 64, 96, res=False)
     X, W, b = _rows(t["X"], 130), t["W"].to(DEV), t["b"].to(DEV)

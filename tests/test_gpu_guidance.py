@@ -23,7 +23,7 @@ from diffsheg_amd.synthetic import SeededNoise, make_inputs  # noqa: E402
 from diffsheg_amd.trainer import DDPMTrainer, sampler_namespace  # noqa: E402
 from diffsheg_amd.weights import make_synthetic_state_dict  # noqa: E402
 from oracle import denoiser_ref  # noqa: E402
-from util import golden, max_abs, rel_err, synthetic_sd  # noqa: E402
+from util import assert_split_ran, golden, max_abs, rel_err, synthetic_sd  # noqa: E402
 
 FP32_ATOL = 1e-3                       # test_gpu_eval's golden tolerance
 BF16_MAX, BF16_RMS = 6e-2, 1.5e-2      # test_gpu_eval's bf16 gates
@@ -72,8 +72,8 @@ def _ddim(model, inp, y=None, opt=None, **kw):
     return tr.diffusion_ddim_val.ddim_sample_loop(model, (B, T, cfg.net_dim_pose), clip_denoised=False, model_kwargs=_kwargs(inp, y), **kw)
 
 
-def _scales(B):
-    return [MIXED[b % len(MIXED)] for b in range(B)]
+def _scales(B, scales=MIXED):
+    return [scales[b % len(scales)] for b in range(B)]
 
 
 # ---- 1. reference parity ------------------------------------------------------------------------------------------------
@@ -140,11 +140,12 @@ def test_ddim25_opt_cond_scale_matches_reference(precision):
 
 
 # ---- 2. runtime scale == a context created at that scale --------------------------------------------------------------------
-@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("precision", ["fp32", "bf16", "bf16x3"])
 @pytest.mark.parametrize("created,runtime", [(1.25, 1.15), (1.25, 1.0), (1.0, 1.25)])
 def test_runtime_scale_equals_baked_context(precision, created, runtime):
     cfg = get_config("show")
-    inp = make_inputs(cfg, 2, seed=3)
+    inp = make_inputs(cfg, 6 if precision == "bf16x3" else 2, seed=3)        # (bf16x3: 528 rows, above the 512-row limit of the split loop)
+    _lib.launch_counts(reset=True)
     baked = _model(precision, runtime)
     e_ref = _eval(baked, inp)
     flops_ref = baked.eval_flops()
@@ -156,6 +157,8 @@ def test_runtime_scale_equals_baked_context(precision, created, runtime):
     assert model.eval_flops() == flops_ref
     assert torch.equal(_ddim(model, inp), x_ref)
     model.set_guidance_scale(None)
+    if precision == "bf16x3":
+        assert_split_ran(_lib.launch_counts(), (created, runtime))
 
 
 def test_single_transformer_runtime_scale_equals_baked_context():
@@ -170,17 +173,31 @@ def test_single_transformer_runtime_scale_equals_baked_context():
 
 
 # ---- 3. per-clip scales, bit for bit --------------------------------------------------------------------------------------
-def _per_row_vs_uniform(model, inp, run):
+def _per_row_vs_uniform(model, inp, run, scales=MIXED):
+    """Row b of the mixed batch == row b of the uniform run at its scale, bit for bit.  A uniform run at 1 is a different model evaluation,
+    though: it has no null half, and the first layer's q|k|v is then the folded-LayerNorm launch instead of the LayerNorm row kernel (which
+    adds the CFG-null constant) and a plain Linear (denoiser.hip run_block_tail_fused) - the same numbers in another order of operations,
+    for every precision.  So rows at 1 are held bit for bit against the same rows of ANOTHER mixed batch that keeps its null half (the
+    other clips at 2.0: the same launches, the same row positions), and their distance to the uniform run at 1 is returned (max abs, and
+    relative to the range) for the caller to hold under the project's own bar."""
     B = inp["x_T"].shape[0]
-    sc = _scales(B)
+    sc = _scales(B, scales)
     model.set_guidance_scale(sc)
     mixed = run()
+    at_one = None
     for s in sorted(set(sc)):
+        rows = [b for b in range(B) if sc[b] == s]
+        if s == 1.0:
+            model.set_guidance_scale([1.0 if v == 1.0 else 2.0 for v in sc])
+            assert any(v != 1.0 for v in sc) and torch.equal(mixed[rows], run()[rows]), "rows at 1 depend on their neighbours' scales"
         model.set_guidance_scale(s)
         uni = run()
-        rows = [b for b in range(B) if sc[b] == s]
+        if s == 1.0:
+            at_one = (max_abs(mixed[rows], uni[rows]), rel_err(mixed[rows], uni[rows]))
+            continue
         assert torch.equal(mixed[rows], uni[rows]), s
     model.set_guidance_scale(None)
+    return at_one
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
@@ -206,6 +223,33 @@ def test_per_row_scales_sub_batch_streams():
     _per_row_vs_uniform(model, inp, lambda: _eval(model, inp))
 
 
+@pytest.mark.parametrize("regime", ["mid-size loop", "sub-batch streams"])
+def test_per_row_scales_on_the_split_loop(regime):
+    """precision "bf16x3", B = 100 (8 800 conditional rows), scales 1.0 and 1.25 mixed: the null half of the mixed batch, the CFG-null row
+    constant and the FiLM rows are indexed per clip in the split launches.  A ddim25 loop (one batch on the two-encoder pipeline) and one
+    evaluation (three sub-batch instances of fp32 storage, each reading its own clips' scales): row b at 1.25 == row b of the uniform run at
+    1.25, and row b at 1 == row b of the batch whose other clips run at 2.0, bit for bit.  Rows at 1 against the run WITHOUT a null half
+    (half the rows per launch, other tiles, and layer 0's q|k|v in another order of operations: _per_row_vs_uniform) are held under the
+    project's unchanged bar, 1e-3 on eps and 1e-3 of the range on a loop; the measured distance is printed."""
+    model = _model("bf16x3", 1.25)
+    inp = make_inputs(model.cfg, 100, seed=8)
+    _lib.launch_counts(reset=True)
+    if regime == "mid-size loop":
+        d_abs, d_rel = _per_row_vs_uniform(model, inp, lambda: _ddim(model, inp), scales=[1.0, 1.25])
+        c = _lib.launch_counts()
+        assert (c["sample_streams"], c["sample_graph"], c["sample_pipe"]) == (1, 0, 1), c
+        print(f"[measure] guidance bf16x3 B=100 ddim25: rows at scale 1 of the mixed batch vs the run without a null half: {d_rel:.3e} of the range")
+        assert d_rel < REL_TOL
+    else:
+        d_abs, d_rel = _per_row_vs_uniform(model, inp, lambda: _eval(model, inp), scales=[1.0, 1.25])
+        c = _lib.launch_counts()
+        assert c["eval_streams"] == 3, c
+        print(f"[measure] guidance bf16x3 B=100 eval: rows at scale 1 of the mixed batch vs the run without a null half: max |d| = {d_abs:.3e}")
+        assert d_abs < FP32_ATOL
+    assert_split_ran(c, regime)
+    assert c["gemm_f32_split_128"] > 0, c
+
+
 def test_per_row_scales_masked_window():
     model = _model("bf16", 1.25)
     cfg = model.cfg
@@ -220,14 +264,27 @@ def test_per_row_scales_masked_window():
 
 # ---- 4. rows at 1 inside a doubled batch -----------------------------------------------------------------------------------
 def test_rows_at_one_match_unguided_oracle():
-    model = _model("fp32", 1.25)
+    _rows_at_one("fp32", [1.0, 1.15, 2.0, 1.0], 32)
+
+
+def test_rows_at_one_match_unguided_oracle_on_the_split_loop():
+    """SHOW B = 6, T = 88 (528 conditional rows, 1 056 with the null half): half_row0 / n_const_rows of the split launches with three of
+    the six clips at scale 1."""
+    _rows_at_one("bf16x3", [1.0, 1.15, 2.0, 1.0, 1.25, 1.0], 88)
+
+
+def _rows_at_one(precision, sc, T):
+    model = _model(precision, 1.25)
     cfg = model.cfg
-    sc = [1.0, 1.15, 2.0, 1.0]
-    B, T = len(sc), 32
+    B = len(sc)
     inp = make_inputs(cfg, B, frames=T, seed=12)
     model.set_guidance_scale(sc)
+    _lib.launch_counts(reset=True)
     eps = _eval(model, inp, 400, 1.5, 1.1).cpu()
+    counts = _lib.launch_counts()
     model.set_guidance_scale(None)
+    if precision == "bf16x3":
+        assert_split_ran(counts, sc)
     sd = synthetic_sd("show")
     for s in sorted(set(sc)):
         with torch.no_grad():
@@ -235,7 +292,7 @@ def test_rows_at_one_match_unguided_oracle():
                                            torch.tensor(1.1), inp["audio_emb"], inp["person_id"], inp["pretrain_aud_feat"])
         rows = [b for b in range(B) if sc[b] == s]
         e = max_abs(eps[rows], ref[rows])
-        print(f"[mixed batch, rows at {s}] max|eps - oracle| = {e:.3e}")
+        print(f"[mixed batch {precision}, rows at {s}] max|eps - oracle| = {e:.3e}")
         assert e < FP32_ATOL, (s, e)
 
 

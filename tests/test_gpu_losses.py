@@ -20,7 +20,8 @@ import losses_ref as LR  # noqa: E402
 from diffsheg_amd.config import get_config  # noqa: E402
 from diffsheg_amd.synthetic import SeededNoise, make_inputs  # noqa: E402
 from diffsheg_amd.trainer import DDPMTrainer, level_seed, sampler_namespace  # noqa: E402
-from util import golden, gpu_model  # noqa: E402
+from diffsheg_amd import _lib  # noqa: E402
+from util import assert_split_ran, golden, gpu_model  # noqa: E402
 
 DEV = "cuda:0"
 FP32_ATOL = 1e-3                      # tests/test_gpu_eval.py
@@ -111,9 +112,64 @@ def test_losses_fp32_match_the_reference_fixture(tag):
     assert np.abs(got[:, :5] - rows[:, :5]).max() <= 1e-5 * np.abs(rows[:, :5]).max() and np.array_equal(got[:, 5:], rows[:, 5:])
 
 
+def setup_split(B=16, ds="beat"):
+    """precision "bf16x3" above the 512-row limit of the split-bf16 loop (BEAT B = 16: 544 rows; the fixtures' batches are below it): seeded
+    inputs with a timestep per clip that reaches both ends of the schedule, and the fp32 model beside it."""
+    cfg = get_config(ds)
+    T, C = cfg.n_poses, cfg.net_dim_pose
+    inp = make_inputs(cfg, B, seed=91)
+    x0 = torch.randn(B, T, C, generator=torch.Generator().manual_seed(92))
+    noise = SeededNoise(93).randn((B, T, C))
+    t = [0, 999] + [(61 * i + 7) % 1000 for i in range(B - 2)]
+    args = (inp["audio_emb"].to(DEV), x0.to(DEV), inp["person_id"].to(DEV), {"pretrain_aud_feat": inp["pretrain_aud_feat"].to(DEV)})
+    trs = {p: DDPMTrainer(sampler_namespace(cfg), gpu_model(ds, p)) for p in ("bf16x3", "fp32")}
+    return cfg, trs, args, x0, noise, t
+
+
+def test_losses_on_the_split_loop_against_float64_on_the_fp32_models_eps():
+    """training_losses with precision "bf16x3": every reported number against losses_ref.py in float64 evaluated on the eps the FP32 model
+    produced for the same x_t, under the gates of the fixture test - eps within FP32_ATOL of it, carried through the formulas (bounds())."""
+    cfg, trs, args, x0, noise, t = setup_split()
+    T, C = cfg.n_poses, cfg.net_dim_pose
+    _lib.launch_counts(reset=True)
+    out = trs["bf16x3"].diffusion.training_losses(trs["bf16x3"].encoder, args[1], t, kwargs_of(args, T), noise=noise.to(DEV))
+    torch.cuda.synchronize()
+    assert_split_ran(_lib.launch_counts(), "training_losses")
+    out32 = trs["fp32"].diffusion.training_losses(trs["fp32"].encoder, args[1], t, kwargs_of(args, T), noise=noise.to(DEV))
+    assert torch.equal(out["x_t"], out32["x_t"])                                 # (q_sample does not depend on the precision of the Linears)
+    pred32, x_t = out32["pred"].cpu(), out["x_t"].cpu()
+    eps_err = float((out["pred"].cpu() - pred32).abs().max())
+    print(f"[measure] losses beat bf16x3 B=16: max |eps - eps(fp32)| = {eps_err:.3e} (bar {FP32_ATOL:g})")
+    assert eps_err < FP32_ATOL and not torch.equal(out["pred"], out32["pred"])
+    c1, c2 = coefficients(trs["bf16x3"].diffusion, t)
+    b = bounds(pred32, noise, x_t, x0, c1, c2, FP32_ATOL, LR.HUBER_BETA)
+    rows32 = LR.row_terms_f64(pred32, noise, x_t, x0, c1, c2, cfg.split_pos)
+    want = LR.scalars_f64(rows32, C)
+    fm = LR.frame_mse_f64(pred32, noise)
+    check("bf16x3 mse", out["mse"].cpu(), fm.mean(-1), b["mse"])
+    check("bf16x3 frame_mse", out["frame_mse"].cpu(), fm, b["frame_mse"])
+    for k in LR.SCALARS:
+        check(f"bf16x3 {k}", out["scalars"][k].cpu(), want[k], b[k])
+    # the kernel's numbers against a float64 evaluation of the formulas on the eps THIS run produced: round-off only
+    rows = LR.row_terms_f64(out["pred"].cpu(), noise, x_t, x0, c1, c2, cfg.split_pos)
+    got = out["row_terms"].cpu().numpy()
+    assert np.abs(got[:, :5] - rows[:, :5]).max() <= 1e-5 * np.abs(rows[:, :5]).max() and np.array_equal(got[:, 5:], rows[:, 5:])
+
+
 def test_losses_are_composed_of_the_existing_calls_bit_for_bit():
     f, cfg, model, tr, args, x0, noise, t = setup("show")
-    diff, T = tr.diffusion, int(f["frames"])
+    _composed_of_the_existing_calls(model, tr, args, t, int(f["frames"]))
+
+
+def test_losses_on_the_split_loop_are_composed_of_the_existing_calls_bit_for_bit():
+    cfg, trs, args, x0, noise, t = setup_split()
+    _lib.launch_counts(reset=True)
+    _composed_of_the_existing_calls(trs["bf16x3"].encoder, trs["bf16x3"], args, t, cfg.n_poses)
+    assert_split_ran(_lib.launch_counts(), "composition")
+
+
+def _composed_of_the_existing_calls(model, tr, args, t, T):
+    diff = tr.diffusion
     kw = kwargs_of(args, T)
     out = diff.training_losses(model, args[1], t, kw, seed=77)
     # x_t: what q_sample draws itself from the same seed; and the noise handed out is the noise that made it
@@ -126,10 +182,11 @@ def test_losses_are_composed_of_the_existing_calls_bit_for_bit():
     assert torch.equal(out["pred"], direct)
     # a SpacedDiffusion indexes its own tables and hands the model the original timestep
     ddim = tr.diffusion_ddim_val
-    o2 = ddim.training_losses(model, args[1], [0, 12, 24], kw, noise=out["target"])
-    k1, k2 = coefficients(ddim, [0, 12, 24])
-    direct = model(o2["x_t"], torch.tensor([0, 480, 960]).to(DEV), sqrt_alphas=[k1.to(DEV), k2.to(DEV)], **kw)
-    assert torch.equal(o2["pred"], direct) and torch.equal(o2["x_t"], ddim.q_sample(args[1], [0, 12, 24], noise=out["target"]))
+    lv = [(0, 12, 24)[b % 3] for b in range(len(t))]
+    o2 = ddim.training_losses(model, args[1], lv, kw, noise=out["target"])
+    k1, k2 = coefficients(ddim, lv)
+    direct = model(o2["x_t"], torch.tensor([(0, 480, 960)[b % 3] for b in range(len(t))]).to(DEV), sqrt_alphas=[k1.to(DEV), k2.to(DEV)], **kw)
+    assert torch.equal(o2["pred"], direct) and torch.equal(o2["x_t"], ddim.q_sample(args[1], lv, noise=out["target"]))
 
 
 def test_cond_scale_one_on_the_call_scores_the_conditional_model():

@@ -7,7 +7,9 @@ gestures for a given expression track.
   * the inactive columns of x / gt / noise are never read; chains; lifetime and refusals; work really removed; the sharded path.
 
 The regime shapes (SHOW, T = 88): B = 2 (graph / pipeline range), B = 141 (12 408 rows: plain evaluations split over two sub-batch
-streams, loops unsplit), B = 734 (64 592 rows: loops split over three sub-batch streams; 3-step DDIM).  The models are private to this
+streams, loops unsplit), B = 734 (64 592 rows: loops split over three sub-batch streams; 3-step DDIM).  precision "bf16x3" (the fp32 path with its Linears of more
+than 512 rows on the split-bf16 loop) runs at B = 6 (528 rows, the smallest batch above the limit) and B = 141 (three sub-batch streams): the
+concat segments of feat_proj.1 change under a modality, and every bit-equality of the fp32 path must hold on the split loop too.  The models are private to this
 module (the session-wide handles of tests/util.py keep their own sticky settings)."""
 import ctypes as C
 import functools
@@ -27,7 +29,7 @@ from diffsheg_amd.synthetic import SeededNoise, make_inputs  # noqa: E402
 from diffsheg_amd.trainer import DDPMTrainer, sampler_namespace, sample_arbitrary_len_sharded, window_seed  # noqa: E402
 from diffsheg_amd.weights import make_synthetic_state_dict  # noqa: E402
 from oracle import sampler_ref  # noqa: E402
-from util import rel_err, synthetic_sd  # noqa: E402
+from util import assert_split_ran, rel_err, synthetic_sd  # noqa: E402
 
 LOOP_GATE = {"fp32": 1e-3, "bf16": 1.2e-2}       # of the output range: the project's loop gate (test_gpu_sampler) / bf16 end-to-end gate
 SHARD_GATE = {"fp32": 1e-5, "bf16": 0.0}         # a chain alone vs its row of the batched run: bit-identical in bf16, 1e-5 of range in fp32
@@ -141,7 +143,8 @@ def _valid(out, lengths):
 
 
 EVAL_CASES = [(p, B, "plain") for p in ("fp32", "bf16") for B in REGIMES] + [(p, 2, s) for p in ("fp32", "bf16") for s in ("scales", "ragged")] + \
-             [("bf16", 141, "scales"), ("bf16", 141, "ragged")]
+             [("bf16", 141, "scales"), ("bf16", 141, "ragged")] + \
+             [("bf16x3", 6, "plain"), ("bf16x3", 6, "scales"), ("bf16x3", 6, "ragged"), ("bf16x3", 141, "plain")]
 
 
 # ---- 1. expression evaluation -------------------------------------------------------------------------------------------------------------
@@ -154,12 +157,16 @@ def test_expression_evaluation_is_the_joint_evaluation(precision, B, setting):
     _lib.launch_counts(reset=True)
     joint = _eval(model, inp, lengths=lengths).clone()
     torch.cuda.synchronize()
-    streams = _lib.launch_counts(reset=True)["eval_streams"]
+    jc = _lib.launch_counts(reset=True)
+    streams = jc["eval_streams"]
     part = _eval(model, inp, "expression", lengths=lengths)
     torch.cuda.synchronize()
     model.set_guidance_scale(None)
+    if precision == "bf16x3":
+        assert_split_ran(jc, "joint")
+        assert_split_ran(_lib.launch_counts(), "expression")
     # (the regime is the joint run's — bf16: one stream, two from 12 288 token rows, three from 64 500; fp32: two from 4 096, three from 8 700)
-    assert _lib.launch_counts()["eval_streams"] == streams == {2: 1, 141: 2 if precision == "bf16" else 3, 734: 3}[B]
+    assert _lib.launch_counts()["eval_streams"] == streams == {2: 1, 6: 1, 141: 2 if precision == "bf16" else 3, 734: 3}[B]
     assert torch.equal(_valid(part[..., G:], lengths), _valid(joint[..., G:], lengths))
     assert not part[..., :G].any()
     assert joint[..., :G].abs().max() > 0
@@ -174,8 +181,11 @@ def test_gesture_evaluation_given_the_joint_estimate_is_the_joint_evaluation(pre
     lengths = _setting(model, B, setting)
     joint = _eval(model, inp, lengths=lengths).clone()
     tap = model.debug_tap("expr_x0").clone()
+    _lib.launch_counts(reset=True)
     part = _eval(model, inp, "gesture", tap, lengths=lengths)
     model.set_guidance_scale(None)
+    if precision == "bf16x3":
+        assert_split_ran(_lib.launch_counts(), "gesture")
     assert torch.equal(_valid(part[..., :G], lengths), _valid(joint[..., :G], lengths))
     assert not part[..., G:].any()
 
@@ -195,7 +205,9 @@ LOOP_CASES = [("fp32", 2, lp, "stack") for lp in ("ddim25", "masked", "eta05", "
              [("bf16", 141, "ddim25", "stack"), ("bf16", 141, "masked", "rows"), ("bf16", 141, "eta05", "philox"), ("bf16", 141, "ddpm50", "philox"),
               ("fp32", 141, "ddim25", "philox")] + \
              [("bf16", 734, "ddim3", nz) for nz in ("stack", "philox", "rows")] + [("bf16", 734, "ddim3_masked", "philox"), ("bf16", 734, "ddim3_eta05", "rows"),
-              ("bf16", 734, "masked", "philox")]       # (ddim25 jump schedule on sub-batch streams: the inline timestep cache, each instance its active share)
+              ("bf16", 734, "masked", "philox")] + \
+             [("bf16x3", 6, "ddim25", "philox"), ("bf16x3", 6, "masked", "rows"), ("bf16x3", 141, "ddim25", "philox")]
+# (bf16 734 masked: the ddim25 jump schedule on sub-batch streams - the inline timestep cache, each instance its active share)
 
 
 @pytest.mark.parametrize("precision,B,loop,noise", LOOP_CASES)
@@ -217,8 +229,11 @@ def test_expression_loop_is_the_joint_loop(precision, B, loop, noise):
     pc = _lib.launch_counts()
     # the regime is the joint run's (graphs at B = 2, one batch below 64 500 token rows, three sub-batch streams above); the joint loop below the
     # split runs its two encoders as a two-stream pipeline, the partial loop is one chain
-    assert (pc["sample_graph"], pc["sample_streams"]) == (jc["sample_graph"], jc["sample_streams"]) == ({2: 1, 141: 0, 734: 0}[B], {2: 1, 141: 1, 734: 3}[B])
+    assert (pc["sample_graph"], pc["sample_streams"]) == (jc["sample_graph"], jc["sample_streams"]) == ({2: 1, 6: 1, 141: 0, 734: 0}[B], {2: 1, 6: 1, 141: 1, 734: 3}[B])
     assert jc["sample_pipe"] == (1 if B < 734 else 0) and pc["sample_pipe"] == 0
+    if precision == "bf16x3":
+        assert_split_ran(jc, "joint loop")
+        assert_split_ran(pc, "expression loop")
     assert torch.isfinite(joint).all() and joint[..., G:].abs().max() > 0
     assert torch.equal(part[..., G:], joint[..., G:])
     assert not part[..., :G].any()
@@ -261,12 +276,13 @@ class _GarbageNoise(_DeviceNoise):
         return z
 
 
-@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("precision", ["fp32", "bf16", "bf16x3"])
 @pytest.mark.parametrize("modality", ["expression", "gesture"])
 def test_inactive_inputs_are_never_read(modality, precision):
     model = _model(precision)
     cfg = model.cfg
-    G, T, Cc, B = cfg.split_pos, cfg.n_poses, cfg.net_dim_pose, 2
+    G, T, Cc, B = cfg.split_pos, cfg.n_poses, cfg.net_dim_pose, 6 if precision == "bf16x3" else 2      # (bf16x3: above the 512-row limit)
+    _lib.launch_counts(reset=True)
     lo, hi = (0, G) if modality == "expression" else (G, Cc)       # the inactive columns
     inp = _inputs("show", B)
     track = M.make_track(cfg, B, 5).cuda() if modality == "gesture" else None
@@ -289,6 +305,8 @@ def test_inactive_inputs_are_never_read(modality, precision):
     want = _loop(model, inp, "ddim25", None, None, modality, track, noise_source=_GarbageNoise(9, lo, hi, None)).clone()
     got = _loop(model, inp, "ddim25", None, None, modality, track, noise_source=_GarbageNoise(9, lo, hi, -3e3))
     assert torch.equal(got, want)
+    if precision == "bf16x3":
+        assert_split_ran(_lib.launch_counts(), modality)
 
 
 # ---- 6. chains -----------------------------------------------------------------------------------------------------------------------------
@@ -438,14 +456,18 @@ def _profile(model, fn):
     return [int(v) for v in n]
 
 
-@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("precision", ["fp32", "bf16", "bf16x3"])
 def test_work_is_really_removed(precision):
     model = _model(precision)
-    inp = _inputs("show", 2)
-    track = M.make_track(model.cfg, 2, 5).cuda()
+    B = 6 if precision == "bf16x3" else 2                          # (bf16x3: above the 512-row limit)
+    inp = _inputs("show", B)
+    track = M.make_track(model.cfg, B, 5).cuda()
     flops, launches = {}, {}
     for mod, ex in (("both", None), ("expression", None), ("gesture", track)):
+        _lib.launch_counts(reset=True)
         _eval(model, inp, mod, ex)
+        if precision == "bf16x3":
+            assert_split_ran(_lib.launch_counts(), mod)
         flops[mod] = model.eval_flops()
         model._cond_key = None                                     # (the profiler changes the split decision: condition again under it)
         launches[mod] = _profile(model, lambda: _eval(model, inp, mod, ex))

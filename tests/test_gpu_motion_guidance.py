@@ -25,7 +25,7 @@ from diffsheg_amd.glue import MotionGuidance  # noqa: E402
 from diffsheg_amd.synthetic import SeededNoise, make_inputs  # noqa: E402
 from diffsheg_amd.trainer import DDPMTrainer, sampler_namespace  # noqa: E402
 from test_gpu_sampler import REL_TOL, _check_trace, _kwargs, _masked, _sample_flags  # noqa: E402
-from util import golden, gpu_model, rel_err  # noqa: E402
+from util import assert_split_ran, golden, gpu_model, rel_err  # noqa: E402
 
 DEV = "cuda:0"
 GATE = 4.0          # kernel error <= GATE x the error of the fp32 torch run of the same restatement (both against float64)
@@ -295,8 +295,29 @@ def _loop_setup(B, ds="show", precision="fp32", seed=61):
 def test_pipelined_encoder_chains_are_bit_identical_when_guided(monkeypatch):
     """The two encoders' chains on two streams (DSH_PIPE, the switch of test_pipelined_encoder_chains_are_bit_identical) against the
     single chain, guided in both spaces, a plain and an out-painting window, and the DDPM loop: every term is local to its column."""
-    B = 3
-    cfg, model, tr, inp, shape = _loop_setup(B)
+    _pipelined_chains_when_guided(3, "fp32", monkeypatch)
+
+
+def test_pipelined_encoder_chains_are_bit_identical_when_guided_on_the_split_loop(monkeypatch):
+    """precision "bf16x3", SHOW B = 6 (528 rows, above the 512-row limit of the split-bf16 loop): the pipelined twin instance reads the packed
+    weights from the second stream."""
+    _pipelined_chains_when_guided(6, "bf16x3", monkeypatch)
+
+
+def _eager_run_is_on_the_split_loop(run, want, monkeypatch):
+    """(graph replays pass no host-side counter: one eager loop, which must give the same bits, is the run that is counted)"""
+    monkeypatch.setenv("DSH_NO_GRAPH", "1")
+    _lib.launch_counts(reset=True)
+    got = run()
+    torch.cuda.synchronize()
+    counts = _lib.launch_counts()
+    monkeypatch.delenv("DSH_NO_GRAPH")
+    assert torch.equal(got, want)
+    assert_split_ran(counts, "guided loop")
+
+
+def _pipelined_chains_when_guided(B, precision, monkeypatch):
+    cfg, model, tr, inp, shape = _loop_setup(B, precision=precision)
     gt, mask = torch.zeros(shape), torch.zeros(shape, dtype=torch.bool)
     gt[:, :cfg.overlap_len] = torch.randn(B, cfg.overlap_len, shape[2], generator=torch.Generator().manual_seed(5))
     mask[:, :cfg.overlap_len] = True
@@ -310,6 +331,9 @@ def test_pipelined_encoder_chains_are_bit_identical_when_guided(monkeypatch):
                                                                    cond_fn=g).clone())
                 assert _sample_flags()[1] == int(pipe), pipe
             assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2]), (space, bool(y))
+            if precision == "bf16x3" and not y:
+                _eager_run_is_on_the_split_loop(lambda: tr.diffusion_ddim_val.ddim_sample_loop(model, shape, clip_denoised=False, seed=17, cond_fn=g,
+                                                                                              model_kwargs=_kwargs(cfg, inp, y)), outs[0], monkeypatch)
     trp = DDPMTrainer(sampler_namespace(cfg, ddim=False, diffusion_steps=50), model)
     g, _ = _guidance("ddpm", *shape, 50, "x0")
     outs = []
@@ -428,13 +452,23 @@ def test_a_guided_clip_alone_equals_the_clip_in_a_batch_of_three():
 def test_zero_guidance_is_the_unguided_sample_bit_for_bit():
     """level_scale all zeros, and W = 0 with no vel / acc, give exactly the unguided sample; so does cond_fn=None, which launches what
     the parent commit launches (the guided kernels are siblings: no argument of the existing launches changed)."""
-    B = 2
-    cfg, model, tr, inp, shape = _loop_setup(B, seed=7)
+    _zero_guidance(2, "fp32")
+
+
+def test_zero_guidance_is_the_unguided_sample_bit_for_bit_on_the_split_loop(monkeypatch):
+    """precision "bf16x3", SHOW B = 6 (528 rows): above the 512-row limit of the split-bf16 loop."""
+    _zero_guidance(6, "bf16x3", monkeypatch)
+
+
+def _zero_guidance(B, precision, monkeypatch=None):
+    cfg, model, tr, inp, shape = _loop_setup(B, precision=precision, seed=7)
     kw = _kwargs(cfg, inp, {})
     f = R.fixture_guidance("plain", *shape, 25)
     run = lambda g, **k: tr.diffusion_ddim_val.ddim_sample_loop(model, shape, clip_denoised=False, seed=9, model_kwargs=kw, cond_fn=g, **k).clone()
     base = run(None)
     assert torch.isfinite(base).all()
+    if precision == "bf16x3":
+        _eager_run_is_on_the_split_loop(lambda: run(None), base, monkeypatch)
     for space in ("x_t", "x0"):
         zero_scale = MotionGuidance(f["target"].to(DEV), f["weight"].to(DEV), f["vel"].to(DEV), f["acc"].to(DEV), space=space, level_scale=[0.0] * 25)
         assert torch.equal(run(zero_scale), base), space

@@ -16,7 +16,7 @@ from diffsheg_amd.model import UniDiffuser  # noqa: E402
 from diffsheg_amd.streaming import StreamPool, chain_handoff, chain_save_tail  # noqa: E402
 from diffsheg_amd.synthetic import make_inputs  # noqa: E402
 from diffsheg_amd.trainer import DDPMTrainer, sampler_namespace, window_seed  # noqa: E402
-from util import gpu_model, rel_err, synthetic_sd  # noqa: E402
+from util import assert_split_ran, gpu_model, rel_err, synthetic_sd  # noqa: E402
 
 DEV = "cuda:0"
 LOOP_FP32, LOOP_BF16 = 1e-5, 1.2e-2
@@ -175,15 +175,49 @@ def _offline(tr, a, h, pid, seed, key, cond_scale=None, **kw):
     return tr.sample_arbitrary_len(a[None], pid[None], {"pretrain_aud_feat": h[None]}, seed=seed, row_keys=[key], cond_scale=cond_scale, **kw)[0]
 
 
-def _count_calls(tr, monkeypatch):
+def _count_calls(tr, monkeypatch, launch_counts=False):
+    """(clips, frames) of every sampler call; launch_counts: and the library's launch counters of that call as a third entry."""
     calls = []
     orig = tr.generate_batch
 
     def counted(*a, **k):
-        calls.append((int(a[0].shape[0]), int(a[0].shape[1])))
-        return orig(*a, **k)
+        if not launch_counts:
+            calls.append((int(a[0].shape[0]), int(a[0].shape[1])))
+            return orig(*a, **k)
+        _lib.launch_counts(reset=True)
+        out = orig(*a, **k)
+        torch.cuda.synchronize()
+        calls.append((int(a[0].shape[0]), int(a[0].shape[1]), _lib.launch_counts()))
+        return out
     monkeypatch.setattr(tr, "generate_batch", counted)
     return calls
+
+
+class _Sessions:
+    """The bookkeeping of the pool tests: sessions by name over their features (audio, HuBERT, speaker), the frames fed and the frames
+    emitted so far, and the sampler calls of every step()."""
+
+    def __init__(self, tr, pool, feat, monkeypatch, launch_counts=False):
+        self.pool, self.feat = pool, feat
+        self.sid, self.fed, self.got = {}, {n: 0 for n in feat}, {n: [] for n in feat}
+        self.calls = _count_calls(tr, monkeypatch, launch_counts)
+
+    def open(self, n, **kw):
+        self.sid[n] = self.pool.open(self.feat[n][2], **kw)
+
+    def feed(self, n, k):
+        a, h, _ = self.feat[n]
+        self.pool.feed(self.sid[n], a[self.fed[n]:self.fed[n] + k], {"pretrain_aud_feat": h[self.fed[n]:self.fed[n] + k]})
+        self.fed[n] += k
+
+    def step(self, expect_calls):
+        del self.calls[:]
+        out = self.pool.step()
+        assert sorted(c[:2] for c in self.calls) == sorted(expect_calls), ([c[:2] for c in self.calls], expect_calls)
+        for n, s_ in self.sid.items():
+            if s_ in out:
+                self.got[n].append(out[s_])
+        return out
 
 
 # ---- 3. a lone session is the offline chain, bit for bit -----------------------------------------------------------------------------
@@ -248,24 +282,10 @@ def test_sessions_at_different_windows_share_one_call(precision, monkeypatch):
     feat = {n: _features(cfg, total[n], 80 + i, spec[n][0]) for i, n in enumerate("ABC")}
     seed = 555
     pool = StreamPool(tr, 3, seed)
-    calls = _count_calls(tr, monkeypatch)
-    sid, fed, got = {}, {n: 0 for n in "ABC"}, {n: [] for n in "ABC"}
-
-    def feed(n, k):
-        a, h, _ = feat[n]
-        pool.feed(sid[n], a[fed[n]:fed[n] + k], {"pretrain_aud_feat": h[fed[n]:fed[n] + k]})
-        fed[n] += k
-
-    def step(expect_calls):
-        del calls[:]
-        out = pool.step()
-        assert sorted(calls) == sorted(expect_calls), (calls, expect_calls)
-        for n in "ABC":
-            if n in sid and sid[n] in out:
-                got[n].append(out[sid[n]])
-        return out
+    ss = _Sessions(tr, pool, feat, monkeypatch)
+    calls, sid, fed, got, feed, step = ss.calls, ss.sid, ss.fed, ss.got, ss.feed, ss.step
     for tick, name in enumerate("ABC"):
-        sid[name] = pool.open(feat[name][2], key=spec[name][1], cond_scale=spec[name][2])
+        ss.open(name, key=spec[name][1], cond_scale=spec[name][2])
         feed(name, size)
         for other in "ABC"[:tick]:
             feed(other, st)
@@ -307,6 +327,86 @@ def test_sessions_at_different_windows_share_one_call(precision, monkeypatch):
     print(f"[stream pool {precision}] worst rel err {worst:.3e} (gate {tol:.1e}); against the chain of another seed {other:.3e}")
     assert worst < tol
     assert other > tol
+
+
+def _seven_sessions(tr, feats, seed, late, monkeypatch):
+    """Six sessions opened together and (late) a seventh one step() behind them, SHOW windows of 88 frames: the calls are (6, 88) plain; (1, 88)
+    plain for the late session beside (6, 88) chained; (6 or 7, 88) chained with the sessions at different windows; close_many flushes the
+    held-back frames.  Returns (the stream of every session, the late session's first emission, per sampler call (clips, frames, launch counts))."""
+    cfg = tr.encoder.cfg
+    size, st = cfg.n_poses, cfg.n_poses - cfg.overlap_len
+    n = 7 if late else 6
+    pool = StreamPool(tr, n, seed)
+    ss = _Sessions(tr, pool, dict(enumerate(feats[:n])), monkeypatch, launch_counts=True)
+    log = []
+    for i in range(6):
+        ss.open(i, key=1000 + i)
+        ss.feed(i, size)
+    ss.step([(6, size)])
+    log += ss.calls
+    if late:
+        ss.open(6, key=1006)
+        ss.feed(6, size)
+    for i in range(6):
+        ss.feed(i, st)
+    ss.step([(6, size)] + ([(1, size)] if late else []))
+    log += ss.calls
+    first_of_late = ss.got[6][0].clone() if late else None
+    for i in range(n):
+        ss.feed(i, st)
+    assert [pool._sessions[ss.sid[i]].win.windows for i in range(n)] == [2] * 6 + [1] * (n - 6)      # windows done so far
+    ss.step([(n, size)])                                                         # the third and the second window: ONE sampler call
+    log += ss.calls
+    rest = pool.close_many([ss.sid[i] for i in range(n)])
+    monkeypatch.undo()
+    streams = [torch.cat(ss.got[i] + [rest[ss.sid[i]]], 0) for i in range(n)]
+    for i, x in enumerate(streams):
+        assert tuple(x.shape) == (ss.fed[i], cfg.net_dim_pose) and torch.isfinite(x).all()
+    return streams, first_of_late, log
+
+
+def test_sessions_share_one_call_on_the_split_loop(monkeypatch):
+    """precision "bf16x3", SHOW, jump_n_sample = 2, enough sessions that a shared call is above the 512-row limit of the split-bf16 loop
+    (6 x 88 = 528 rows).  ONE context goes above the limit (six sessions), below it (the late seventh session's first window: 88 rows, beside
+    the six again), and above it again (all seven, at windows 3 and 2).
+      * every call above the limit is on the split loop, the one below on the fp32 kernels - and its frames are the fp32 context's frames for
+        the same session bit for bit;
+      * the six early streams inside the pool of seven against the same sessions in a pool of six (both above the limit: the same
+        arithmetic at another batch size) under the project's 1e-5 of the range;
+      * every stream against the fp32 context's stream of the same choreography under 1e-3 of the range;
+      * the distance to the chain sampled alone offline (which runs the fp32 kernels: it crosses the change of arithmetic) is printed.
+    Eager evaluations (DSH_NO_GRAPH): the launch counters are host-side and see every launch of every call."""
+    monkeypatch.setenv("DSH_NO_GRAPH", "1")
+    cfg = get_config("show")
+    size, st = cfg.n_poses, cfg.n_poses - cfg.overlap_len
+    feats = [_features(cfg, size + 2 * st, 200 + i, i) for i in range(7)]
+    seed = 777
+    tr3 = DDPMTrainer(sampler_namespace(cfg, jump_n_sample=2), gpu_model("show", "bf16x3"))
+    tr32 = DDPMTrainer(sampler_namespace(cfg, jump_n_sample=2), gpu_model("show", "fp32"))
+    s7, late3, log = _seven_sessions(tr3, feats, seed, True, monkeypatch)
+    monkeypatch.setenv("DSH_NO_GRAPH", "1")                                      # (_seven_sessions undoes its patches)
+    assert [c[:2] for c in log if c[0] * c[1] <= 512] == [(1, size)]
+    for nb, T, counts in log:
+        if nb * T > 512:
+            assert_split_ran(counts, (nb, T))
+        else:
+            assert counts["gemm_f32_split"] == 0, counts
+    order = [c[0] * c[1] > 512 for c in log]
+    assert order[0] and not all(order[1:3]) and order[-1], order                 # above, (below beside above), above
+    s6, _, _ = _seven_sessions(tr3, feats, seed, False, monkeypatch)
+    monkeypatch.setenv("DSH_NO_GRAPH", "1")
+    f7, late32, log32 = _seven_sessions(tr32, feats, seed, True, monkeypatch)
+    assert all(c[2]["gemm_f32_split"] == 0 for c in log32)
+    assert torch.equal(late3, late32), "below the limit a bf16x3 context must launch the fp32 kernels"
+    w6 = max(rel_err(s7[i], s6[i]) for i in range(6))
+    w32 = max(rel_err(s7[i], f7[i]) for i in range(7))
+    a, h, pid = feats[0]
+    alone = rel_err(s7[0], tr3.sample_arbitrary_len(a[None], pid[None], {"pretrain_aud_feat": h[None]}, seed=seed, row_keys=[1000])[0])
+    print(f"[measure] stream pool bf16x3: six sessions in a pool of 7 vs a pool of 6: {w6:.3e} (gate {LOOP_FP32:.1e}); vs the fp32 context: {w32:.3e} (gate 1.0e-03); "
+          f"session 0 vs its chain alone offline (fp32 kernels, no gate): {alone:.3e}")
+    assert w6 < LOOP_FP32
+    assert w32 < 1e-3
+    assert not torch.equal(s7[0], f7[0])
 
 
 def test_tails_of_different_lengths_close_together():

@@ -40,8 +40,8 @@ def test_precision_value_is_known_to_python_and_the_header():
     assert model._PRECISION["bf16x3"] == 2
     hdr = open(os.path.join(ROOT, "include", "diffsheg_hip.h")).read()
     assert re.search(r"_PRECISION_BF16X3\s*=\s*2\b", hdr)
-    assert int(re.search(r"#define DSH_LAUNCH_COUNT_ENTRIES (\d+)", hdr).group(1)) == 21
-    assert len(_lib.LAUNCH_FAMILIES) == 21 and _lib.LAUNCH_FAMILIES[20] == "gemm_f32_split" and _lib.LAUNCH_FAMILIES[12] == "gemm_f32_pro"
+    assert int(re.search(r"#define DSH_LAUNCH_COUNT_ENTRIES (\d+)", hdr).group(1)) == 22
+    assert len(_lib.LAUNCH_FAMILIES) == 22 and _lib.LAUNCH_FAMILIES[20] == "gemm_f32_split" and _lib.LAUNCH_FAMILIES[21] == "gemm_f32_split_128" and _lib.LAUNCH_FAMILIES[12] == "gemm_f32_pro"
     assert "dsh_op_gemm_f32_pro_ex" in hdr
 
 
@@ -113,6 +113,49 @@ def test_truncated_lo_is_rejected_where_fp32_is_finer_than_the_split(pro, fam, K
         assert dist <= G.MARGIN * cal, "the fp32 chain is coarser than the mutant here: that is why the pinning gate accepts it"
     else:
         assert S.rejected(S.check_emul, t, out), f"a loop with truncated lo pieces passes the pinning gate of {t['name']}"
+
+
+# ---- 3b. the model's own Linear forms, K = 2 048 and 3 072 included (split_gates.MODEL_LINEARS) ------------------------------------------------
+# (the FiLM table's 16 384 columns are left to the GPU test: the same K = 2 048 as aud_film here, and its column-sampled calibration is
+# checked below on a narrower twin)
+LARGE_K = ("conv1", "aud_time_embed.2", "pid_embed.2", "aud_film")
+CPU_MODEL = [n for n in S.MODEL_LINEARS if n != "film"]
+
+
+@pytest.mark.parametrize("name", CPU_MODEL)
+def test_model_linear_forms_emulation_inside_both_gates_and_dropped_term_rejected(name):
+    """M = 513: the emulation of every form the model launches sits inside the derived and the pinning gate, and a loop without a_lo w_hi is
+    rejected by both - at K = 2 048 and 3 072 as at the grid's K (the dropped term is 2^-8 of the products against an allowance of 3 x 2^-16
+    of their absolute sum: both grow alike with K)."""
+    t = S.model_case(name, 513)
+    out = S.emul(t).float()
+    r, re_ = S.check(t, out), S.check_emul(t, out)
+    err, _, cal, sp = S.figures(t, out)
+    mut = S.emul(t, drop_alo=True).float()
+    merr = float((mut.double() - G.gate(t)[0])[:t["M"]].abs().max())
+    print(f"[{t['name']} K={t['K']}] |emul - fp64| {err:.2e} = {r:.3f} of the derived gate, {re_:.3f} of the pinning gate (fp32 calibration {cal:.2e}, largest split term "
+          f"{sp:.2e}); dropped a_lo w_hi: {merr:.2e} from fp64")
+    assert r <= 1.0 and re_ <= 1.0
+    assert S.rejected(S.check, t, mut), f"a loop without a_lo w_hi passes the derived gate of {t['name']}"
+    assert S.rejected(S.check_emul, t, mut), f"a loop without a_lo w_hi passes the pinning gate of {t['name']}"
+
+
+def test_large_k_rows_are_in_the_table():
+    ks = {n: S.model_case(n, 513)["K"] for n in LARGE_K}
+    assert ks == {"conv1": 3072, "aud_time_embed.2": 2048, "pid_embed.2": 2048, "aud_film": 2048}
+    film = S.model_case("film", 513)
+    assert (film["N"], film["K"]) == (16384, 2048) and len(film["cal_cols"]) == 1024
+
+
+def test_column_sampled_calibration_never_widens_the_gate():
+    """f32_gates.gate with cal_cols (used for the FiLM table's N): the allowance over a sample of the columns is at most the allowance over all."""
+    whole = G.pro0_inputs(513, 2048, 512, act=1, res=False)
+    part = dict(G.pro0_inputs(513, 2048, 512, act=1, res=False), cal_cols=torch.arange(0, 2048, 4))
+    (_, a, ca), (_, b, cb) = G.gate(whole), G.gate(part)
+    print(f"[cal_cols] calibration over all 2 048 columns {ca:.3e}, over every fourth {cb:.3e}")
+    assert cb <= ca and float(b.max()) <= float(a.max()) and cb > 0.5 * ca
+    out = S.emul(part).float()
+    assert S.check(part, out) <= 1.0 and S.check_emul(part, out) <= 1.0
 
 
 @pytest.mark.parametrize("K", [512, 960])

@@ -85,3 +85,67 @@ def hoist_latched():
     v = C.c_int64()
     _lib.check(_lib.lib().dsh_switch_read(b"DSH_AUD_HOIST", None, C.byref(v)))
     return int(v.value != 0)
+
+
+# ---- precision "bf16x3" in the feature tests -----------------------------------------------------------------------------------------------
+F32_STORAGE = ("fp32", "bf16x3")        # precisions with fp32 storage: the oracle gates of "fp32" (1e-3) hold for both
+
+
+def assert_split_ran(counts, what=""):
+    """a bf16x3 run above the few-row limit: its large Linears were on the split-bf16 loop, none on the exact-fp32 loop of gemm_f32_pro.hip"""
+    assert counts["gemm_f32_split"] > 0 and counts["gemm_f32_pro"] == 0, (what, {k: counts[k] for k in ("gemm_f32_split", "gemm_f32_split_128", "gemm_f32_pro", "gemm_f32_fewrow")})
+
+
+def philox_rows(seed, keys, n_row):
+    """the first n_row normal draws of the row streams `keys` (dsh_op_philox_randn_rows): x_T of a loop sampled with row_keys, [len(keys), n_row] on the CPU"""
+    from diffsheg_amd import _lib
+    out = torch.empty(len(keys), n_row, device="cuda:0")
+    karr = (C.c_uint64 * len(keys))(*[int(k) for k in keys])
+    _lib.check(_lib.lib().dsh_op_philox_randn_rows(None, out.data_ptr(), len(keys), n_row, seed & (2 ** 64 - 1), 0, karr))
+    return out.cpu()
+
+
+def oracle_ddim25(sd, cfg, audio, hub, pid, xT, single=False):
+    """The oracle's 25-step DDIM loop (oracle/sampler_ref.py, eta = 0) on CPU clips from a given x_T [n, T, C]: what a GPU loop that drew this
+    x_T for these clips must reproduce within the loop gate of its precision."""
+    from oracle import denoiser_ref, sampler_ref
+    n = xT.shape[0]
+
+    class _Src:                      # draw 0 = x_T; the randn_like of every ddim step is multiplied by sigma = 0
+        i = 0
+
+        def randn(self, shape):
+            self.i += 1
+            return xT.clone() if self.i == 1 else torch.zeros(*shape)
+
+    def eps_fn(xc, t_orig, c1, c2):
+        with torch.no_grad():
+            tt = torch.full((n,), t_orig)
+            if single:
+                return denoiser_ref.single_motion_transformer(sd, cfg, xc, tt, audio, pid, hub)
+            return denoiser_ref.unidiffuser(sd, cfg, xc, tt, c1, c2, audio, pid, hub)
+    return sampler_ref.ddim_sample_loop(eps_fn, tuple(xT.shape), {}, _Src(), overlap_len=cfg.overlap_len)
+
+
+def sub_batches(B, ns):
+    """DenoiserContext: first_clip, clips [B i / ns, B (i + 1) / ns) of the ns sub-batch instances."""
+    return [(B * i // ns, B * (i + 1) // ns) for i in range(ns)]
+
+
+def sample_clips(B, T, ns, cap=10):
+    """Clips of a batch of B clips of T frames on ns sub-batch streams to compare with the oracle: first and last clip, both sides of every
+    sub-batch split, the first clips that straddle a 32-, 128- and 256-token block boundary, and two interior ones."""
+    picks = [0, B - 1]
+    for lo, _ in sub_batches(B, ns)[1:]:
+        picks += [lo - 1, lo]
+    for blk in (256, 128, 32):
+        for b in range(1, B):
+            if (b * T) // blk != ((b + 1) * T - 1) // blk and (b * T) % blk and b not in picks:
+                picks.append(b)
+                break
+    picks += [B // 3, (5 * B) // 7]
+    out = []
+    for b in picks:
+        if 0 <= b < B and b not in out:
+            out.append(b)
+    return out[:cap]
