@@ -22,7 +22,8 @@ class ModelConfigC(C.Structure):
                 ("classifier_free", C.c_int32), ("cond_scale", C.c_float), ("latent_dim", C.c_int32),
                 ("ff_size", C.c_int32), ("num_layers", C.c_int32), ("num_heads", C.c_int32),
                 ("audio_dim", C.c_int32), ("aud_latent_dim", C.c_int32), ("hubert_dim", C.c_int32),
-                ("hubert_enc_dim", C.c_int32), ("precision", C.c_int32), ("single_transformer", C.c_int32)]
+                ("hubert_enc_dim", C.c_int32), ("precision", C.c_int32), ("single_transformer", C.c_int32),
+                ("diffusion_steps", C.c_int32)]        # (0: 1000)
 
 
 class CrossAttnWeightsC(C.Structure):
@@ -125,6 +126,7 @@ SYMBOLS = {
     "dsh_masked_start_level": (C.c_int32, [C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "dsh_op_dpm2m_step": (C.c_int, [_P] * 7 + [C.c_int32] * 3 + [C.c_float] * 7 + [C.c_int32] * 7),
     "dsh_set_guidance_scale": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32]),
+    "dsh_set_guidance_schedule": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_float]),
     "dsh_diffusion_table": (C.c_int32, [C.c_int32, C.c_int32, C.c_char_p, C.POINTER(C.c_double), C.c_int32]),
     "dsh_timestep_map": (C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
     "dsh_jump_schedule": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32]),
@@ -176,6 +178,8 @@ SYMBOLS = {
     "dsh_op_fill_cols": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32]),
     "dsh_op_temb": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
     "dsh_op_cfg_mix": (C.c_int, [_P, _P] + [C.c_int32] * 6 + [_P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int32]),
+    "dsh_op_cfg_mix_sched": (C.c_int, [_P, _P] + [C.c_int32] * 6 + [_P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int32,
+                                       _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_float, _P]),
     "dsh_op_im2col3": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     "dsh_op_film_fold": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "dsh_op_film_expand": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32]),

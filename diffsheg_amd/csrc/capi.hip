@@ -37,9 +37,14 @@ struct dsh_ctx {
     float* gs_dev = nullptr;
     int gs_cap = 0, gs_n = 0;
     bool gs_dbl = false;
+    // guidance schedule (dsh_set_guidance_schedule): [2 diffusion_steps gains | 2 phi] at one address for the life of the context, written in
+    // stream order; sched_on: a schedule is set
+    float* sched_dev = nullptr;
+    bool sched_on = false;
     ~dsh_ctx() {
-        den.reset();                                   // (the instances hold gs_dev)
+        den.reset();                                   // (the instances hold gs_dev and sched_dev)
         if (gs_dev) (void)hipFree(gs_dev);
+        if (sched_dev) (void)hipFree(sched_dev);
     }
 };
 
@@ -111,6 +116,8 @@ int dsh_create(const dsh_model_config* c, void* hip_stream, dsh_ctx** out) {
     m.aud_latent_dim = c->aud_latent_dim; m.hubert_dim = c->hubert_dim; m.hubert_enc_dim = c->hubert_enc_dim;
     m.precision = c->precision;
     m.single_transformer = c->single_transformer ? 1 : 0;
+    DSH_REQUIRE(c->diffusion_steps >= 0, "diffusion_steps must not be negative (0: 1000)");
+    m.diffusion_steps = c->diffusion_steps ? c->diffusion_steps : 1000;
     ctx->stream = reinterpret_cast<hipStream_t>(hip_stream);
     if (ctx->stream == nullptr) {
         // The legacy NULL stream cannot be graph-captured.  A BLOCKING stream keeps the implicit ordering with work
@@ -397,6 +404,41 @@ int dsh_set_guidance_scale(dsh_ctx* ctx, const float* scales_host, int32_t n) {
     API_BEGIN
     DSH_REQUIRE(ctx, "null context");
     return set_guidance(ctx, scales_host, n);
+    API_END
+}
+
+int dsh_set_guidance_schedule(dsh_ctx* ctx, const float* gain_expression, const float* gain_gesture, int32_t n_steps, float rescale_expression,
+                              float rescale_gesture) {
+    API_BEGIN
+    DSH_REQUIRE(ctx, "null context");
+    if (n_steps == 0) {                                // cleared: every instance is back on the plain mix
+        if (int e = ctx->den->set_guidance_schedule(nullptr, 0, false, false)) return e;
+        ctx->sched_on = false;
+        return 0;
+    }
+    const int n = ctx->cfg.diffusion_steps;
+    DSH_REQUIRE(n_steps == n, "dsh_set_guidance_schedule: one gain per original timestep (n_steps must be the model's diffusion steps), or 0 to clear");
+    DSH_REQUIRE(gain_expression && gain_gesture, "dsh_set_guidance_schedule: null gain row");
+    DSH_REQUIRE(rescale_expression >= 0.0f && rescale_expression <= 1.0f && rescale_gesture >= 0.0f && rescale_gesture <= 1.0f,
+                "dsh_set_guidance_schedule: the rescale factors must lie in [0, 1]");
+    bool trivial = rescale_expression == 0.0f && rescale_gesture == 0.0f, same = rescale_expression == rescale_gesture;
+    for (int i = 0; i < n; ++i) {
+        DSH_REQUIRE(std::isfinite(gain_expression[i]) && std::isfinite(gain_gesture[i]), "dsh_set_guidance_schedule: gains must be finite");
+        trivial = trivial && gain_expression[i] == 1.0f && gain_gesture[i] == 1.0f;
+        same = same && gain_expression[i] == gain_gesture[i];
+    }
+    DSH_REQUIRE(trivial || ctx->cfg.classifier_free, "dsh_set_guidance_schedule: the weights are not classifier-free (no null_cond_emb): only gains of 1 without rescale are possible");
+    DSH_REQUIRE(same || !ctx->cfg.single_transformer, "dsh_set_guidance_schedule: a single transformer has one encoder: the two rows and the two rescale factors must be equal");
+    if (!ctx->sched_dev) DSH_HIP_CHECK(hipMalloc((void**)&ctx->sched_dev, ((size_t)2 * n + 2) * sizeof(float)));
+    std::vector<float> v((size_t)2 * n + 2);
+    std::copy(gain_expression, gain_expression + n, v.begin());
+    std::copy(gain_gesture, gain_gesture + n, v.begin() + n);
+    v[(size_t)2 * n] = rescale_expression; v[(size_t)2 * n + 1] = rescale_gesture;
+    // (in stream order, like the scales: evaluations enqueued earlier still read the old table)
+    if (int e = dsh::launch_store_values_f32(ctx->sched_dev, v.data(), (int)v.size(), ctx->stream)) return e;
+    if (int e = ctx->den->set_guidance_schedule(ctx->sched_dev, n, rescale_expression > 0.0f, rescale_gesture > 0.0f)) return e;
+    ctx->sched_on = true;
+    return 0;
     API_END
 }
 
@@ -1501,6 +1543,35 @@ int dsh_op_cfg_mix(void* hip_stream, const float* o, int32_t ldo, int32_t Mc, in
     DSH_REQUIRE(!x0 || (x && c1 && c2 && ldx >= c0 + w && ldx0 >= w), "cfg_mix: the x0 branch needs x, c1 and c2");
     return dsh::launch_cfg_mix(o, ldo, Mc, cond_row0, frames, w, has_null, scale, scale_row, eps, lde, c0, x, ldx, c1, c2, x0, ldx0,
                                reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_op_cfg_mix_sched(void* hip_stream, const float* o, int32_t ldo, int32_t Mc, int32_t cond_row0, int32_t frames, int32_t w, int32_t has_null,
+                         const float* scale, int32_t scale_row, float* eps, int32_t lde, int32_t c0, const float* x, int32_t ldx, const float* c1,
+                         const float* c2, float* x0, int32_t ldx0, const int64_t* t, int32_t t_row, const float* table, int32_t n_steps,
+                         int32_t which, float rescale, const int32_t* lens_dev) {
+    API_BEGIN
+    DSH_REQUIRE(o && eps && Mc > 0 && frames > 0 && Mc % frames == 0 && w > 0 && ldo >= w && c0 >= 0 && lde >= c0 + w, "cfg_mix_sched: invalid argument");
+    DSH_REQUIRE(!has_null || cond_row0 >= Mc, "cfg_mix_sched: the conditional half starts behind the unconditional one");
+    DSH_REQUIRE(!x0 || (x && c1 && c2 && ldx >= c0 + w && ldx0 >= w), "cfg_mix_sched: the x0 branch needs x, c1 and c2");
+    DSH_REQUIRE(rescale >= 0.0f && rescale <= 1.0f && (which == 0 || which == 1) && (t_row == 0 || t_row == 1) && (scale_row == 0 || scale_row == 1),
+                "cfg_mix_sched: rescale in [0, 1], row 0 or 1, strides 0 or 1");
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    // an undoubled batch has nothing to weigh: the schedule is inert, the plain launch
+    if (!has_null) return dsh::launch_cfg_mix(o, ldo, Mc, cond_row0, frames, w, 0, scale, scale_row, eps, lde, c0, x, ldx, c1, c2, x0, ldx0, s);
+    DSH_REQUIRE(scale && t && table && n_steps > 0, "cfg_mix_sched: a doubled batch needs scales, timesteps and the gain table");
+    // the device table as the context keeps it: the two gain rows, then the two rescale factors (`rescale` is row `which`'s)
+    OpScratch scratch;
+    void *tab = nullptr, *part = nullptr;
+    if (int e = scratch.alloc(&tab, ((size_t)2 * n_steps + 2) * sizeof(float))) return e;
+    DSH_HIP_CHECK(hipMemcpyAsync(tab, table, (size_t)2 * n_steps * sizeof(float), hipMemcpyDeviceToDevice, s));
+    const float phi[2] = {rescale, rescale};
+    if (int e = dsh::launch_store_values_f32(reinterpret_cast<float*>(tab) + (size_t)2 * n_steps, phi, 2, s)) return e;
+    if (rescale > 0.0f) { if (int e = scratch.alloc(&part, (size_t)Mc * 4 * sizeof(double))) return e; }
+    const int rc = dsh::launch_cfg_mix_sched(o, ldo, Mc, cond_row0, frames, w, scale, scale_row, t, t_row, reinterpret_cast<const float*>(tab), n_steps,
+                                             which, rescale > 0.0f, lens_dev, reinterpret_cast<double*>(part), eps, lde, c0, x, ldx, c1, c2, x0, ldx0, s);
+    DSH_HIP_CHECK(hipStreamSynchronize(s));
+    return rc;
     API_END
 }
 

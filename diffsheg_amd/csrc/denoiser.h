@@ -26,6 +26,7 @@ struct ModelConfig {
     // 1: the model is ONE MotionTransformer over all dim_pose + expression_dim channels (runner.py:46-57, opt.unidiffuser =
     // False, model_base transformer_encoder): no encoder_aud, audio_proj on the 128 mel features, no expression -> gesture flow
     int single_transformer = 0;
+    int diffusion_steps = 1000;    // length of the original timestep scale: what a guidance schedule has one gain per (dsh_set_guidance_schedule)
     int channels() const { return dim_pose + expression_dim; }
     int time_embed_dim() const { return 4 * latent_dim; }
 };
@@ -76,6 +77,11 @@ class DenoiserInstance {
     // doubled = evaluate the null half at all (classifier-free weights and some s_b != 1); a clip at exactly 1 in a doubled batch takes k.  Grows
     // the token-row workspace the first time a doubled batch is asked for.  The scale buffer must outlive every evaluation that reads it.
     virtual int set_guidance(const float* scale, int scale_row, bool doubled) = 0;
+    // Guidance schedule of the next evaluations (dsh_set_guidance_schedule): sched = [gain_expression[n] | gain_gesture[n] | phi_expression,
+    // phi_gesture] (device fp32, context-owned, read by the mix kernels when they run), rescale[m] = the host's phi_m > 0 (the second launch is
+    // issued).  Where the batch is doubled, encoder m mixes with s_eff = 1 + gain[m][t_b] (s_b - 1); sched == null: no schedule, the plain mix.
+    // The single transformer reads row 0.
+    virtual int set_guidance_schedule(const float* sched, int n_steps, bool rescale_expression, bool rescale_gesture) = 0;
     // one modality alone (DenoiserContext::set_modality): the Part this instance launches from now on, and its clips' rows of the track
     virtual int set_modality(int modality, const float* track) = 0;
     //   set_part(p): the Part the next evaluations run, for the pipelined loop (an encoder alone computes its head, EVAL_PLAIN, or restores its own
@@ -137,6 +143,7 @@ class DenoiserContext {
     virtual int modality() const = 0;
     virtual const float* modality_track() const = 0;
     virtual int set_guidance(const float* scale, int scale_row, bool doubled) = 0;   // as DenoiserInstance's, for every instance that evaluates
+    virtual int set_guidance_schedule(const float* sched, int n_steps, bool rescale_expression, bool rescale_gesture) = 0;   // likewise (not per clip: no slices)
     // eps[B,T,C] = model(x[B,T,C], t[B]) with c1/c2 [B] (device fp32) feeding the expression x0; eval_level(): with the timestep cache (EvalMode)
     virtual int eval(const float* x, const int64_t* t, const float* c1, const float* c2, float* eps) = 0;
     virtual int eval_level(const float* x, const int64_t* t, const float* c1, const float* c2, float* eps, int mode, const int64_t* level) = 0;

@@ -65,7 +65,7 @@ class Denoiser final : public DenoiserInstance {
     // second instance on another stream that shares (does not own) the finalized weights; own workspace
     Denoiser(const Denoiser& o, hipStream_t s)
         : cfg(o.cfg), st(s), wbytes(o.wbytes), finalized(o.finalized), aud_te0(o.aud_te0), aud_te2(o.aud_te2),
-          aud_film(o.aud_film), aud_stream(o.aud_stream), aud_ap_bias(o.aud_ap_bias), aud_bias(o.aud_bias), aud_film_g(o.aud_film_g), aud_film_b(o.aud_film_b), aud(o.aud), exp_(o.exp_), ges_(o.ges_), sw(o.sw), gs(o.gs), gs_row(o.gs_row), gs_dbl(o.gs_dbl) {
+          aud_film(o.aud_film), aud_stream(o.aud_stream), aud_ap_bias(o.aud_ap_bias), aud_bias(o.aud_bias), aud_film_g(o.aud_film_g), aud_film_b(o.aud_film_b), aud(o.aud), exp_(o.exp_), ges_(o.ges_), sw(o.sw), gs(o.gs), gs_row(o.gs_row), gs_dbl(o.gs_dbl), sched(o.sched), sched_n(o.sched_n), sched_rs{o.sched_rs[0], o.sched_rs[1]} {
         for (Encoder* E : {&exp_, &ges_}) { E->pid_part = nullptr; E->pid_part_s = nullptr; E->hub = nullptr; E->film_tab = nullptr; E->aproj_buf = nullptr; }
     }
     DenoiserInstance* clone_shared(hipStream_t s) override { return finalized ? new Denoiser(*this, s) : nullptr; }
@@ -127,6 +127,12 @@ class Denoiser final : public DenoiserInstance {
         DSH_REQUIRE(!doubled || scale, "a doubled batch needs its guidance scales");
         gs = scale; gs_row = scale_row ? 1 : 0; gs_dbl = doubled;
         return row_buffers();                              // (an unconditioned instance sizes them at its first set_condition)
+    }
+    int set_guidance_schedule(const float* tab, int n_steps, bool rescale_expression, bool rescale_gesture) override {
+        DSH_REQUIRE(!tab || n_steps > 0, "a guidance schedule needs its table length");
+        sched = tab; sched_n = tab ? n_steps : 0;
+        sched_rs[0] = tab && rescale_expression; sched_rs[1] = tab && rescale_gesture;
+        return 0;
     }
     size_t weight_bytes() const override { return wbytes; }
     int debug_copy(const std::string& what, float* out) override;
@@ -205,6 +211,11 @@ class Denoiser final : public DenoiserInstance {
     // guidance (set_guidance): scale of clip b = gs[b * gs_row]; gs_dbl = the null half is evaluated.  ws_dbl: the M-row buffers
     // (row_allocs) hold both halves — from the first time a doubled batch is asked for, never shrunk
     const float* gs = nullptr; int gs_row = 0; bool gs_dbl = false, ws_dbl = false;
+    // guidance schedule (set_guidance_schedule): the context's table [2 sched_n gains | 2 phi], null = none; sched_rs[m]: encoder m's phi > 0
+    // (m: 0 expression, 1 gesture; the single transformer reads row 0).  cfg_part: the rescale's row moments, 4 fp64 per token row.
+    const float* sched = nullptr; int sched_n = 0; bool sched_rs[2] = {false, false};
+    double* cfg_part = nullptr;
+    const int64_t* t_now = nullptr;  // the timesteps of the evaluation in progress (eval_level)
     std::vector<void*> row_allocs;
     int row_buffers();
     float *audio_f = nullptr, *h = nullptr, *o = nullptr, *expr_x0 = nullptr, *film_aud_tab = nullptr, *aud_feat_f = nullptr;
@@ -797,6 +808,7 @@ int Denoiser<T>::ensure_workspace(int B, int T_) {
     WS(expr_x0, Mc * expr_ld());
     DSH_HIP_CHECK(hipMemsetAsync(expr_x0, 0, Mc * expr_ld() * sizeof(float), st));   // (the pad columns are never written)
     WS(expr16, Mc * 128);
+    WS(cfg_part, Mc * 4);
     WS(film_aud_tab, Bc * aud_film.N);
     WS(aud_feat_f, Mc * cfg.audio_dim);
     WS(aud_x2, Mc * cfg.audio_dim);
@@ -1177,7 +1189,12 @@ int Denoiser<T>::run_encoder(Encoder& E, const float* x, int c0, int w, const fl
         c.a.Cf = o; c.a.cf_rowmajor = 1; c.a.ldcf = E.cin_p;       // fp32 rows in natural order, as launch_cfg_mix reads them
         if (int e = tl(c)) return e;
     } else if (int e = gemm(E.out, hT(), D, M, ACT_NONE, false, nullptr, 0, 0, o, E.cin_p, nullptr, 0)) return e;
-    if (int e = launch_cfg_mix(o, E.cin_p, Mc, r0, fr, w, has_null, gs, gs_row, eps, C, c0, x, C, c1, c2,
+    if (sched && has_null) {
+        // a guidance schedule shapes the mix of a doubled batch (an undoubled one has nothing to weigh): one launch, two with this encoder's rescale
+        const int m = (&E == &exp_ || cfg.single_transformer) ? 0 : 1;
+        if (int e = launch_cfg_mix_sched(o, E.cin_p, Mc, r0, fr, w, gs, gs_row, t_now, 1, sched, sched_n, m, sched_rs[m], lens, cfg_part, eps, C,
+                                         c0, x, C, c1, c2, want_x0 ? expr_x0 : nullptr, expr_ld(), st)) return e;
+    } else if (int e = launch_cfg_mix(o, E.cin_p, Mc, r0, fr, w, has_null, gs, gs_row, eps, C, c0, x, C, c1, c2,
                                want_x0 ? expr_x0 : nullptr, expr_ld(), st)) return e;
     // tiled bf16 copy of the expression x0, zero padded to 128 columns: last segment of the gesture encoder's concat rows
     if (want_x0 && tlp) return launch_tile_rows_bf16<float>(expr_x0, expr_ld(), Mc, w, expr16, 128, st);
@@ -1275,6 +1292,7 @@ int Denoiser<T>::eval_level(const float* x, const int64_t* t, const float* c1, c
     DSH_REQUIRE(part == PART_BOTH || ((mode == EVAL_RESTORE || mode == EVAL_PLAIN) && !cfg.single_transformer), "a partial evaluation computes (mode 0) or restores (mode 2) its own head");
     flops_acc = 0;
     tl_launches = 0;
+    t_now = t;
     if (mode == EVAL_HEAD_ONLY) {
         if (int e = prep_audio(t)) return e;
         for (Encoder* E : encs()) { if (active() == PART_BOTH || E == (active() == PART_EXPRESSION ? &exp_ : &ges_)) { if (int e = prep_encoder(*E)) return e; } }

@@ -212,6 +212,7 @@ class Context final : public DenoiserContext {
         DSH_HIP_CHECK(hipEventRecord(w.ev, st_));
         DSH_HIP_CHECK(hipStreamWaitEvent(w.stream, w.ev, 0));
         if (int e = w.inst->set_guidance(gs_, gs_row_, gs_dbl_)) return e;
+        if (int e = w.inst->set_guidance_schedule(sched_, sched_n_, sched_rs_[0], sched_rs_[1])) return e;
         if (!w.cond_ok) {
             if (int e = w.inst->set_part(PART_BOTH)) return e;
             if (int e = w.inst->set_lengths(lens_)) return e;
@@ -267,6 +268,13 @@ class Context final : public DenoiserContext {
         gs_ = scale; gs_row_ = scale_row ? 1 : 0; gs_dbl_ = doubled;
         for (int i = 0; i < (int)inst_.size(); ++i) { if (int e = push_guidance(i, split_now_)) return e; }
         if (tw_.inst) { if (int e = tw_.inst->set_guidance(gs_, gs_row_, gs_dbl_)) return e; }
+        return 0;
+    }
+    // ... and the context's schedule: one table for every clip, so every instance takes the same pointer (the prefetch instance never mixes)
+    int set_guidance_schedule(const float* sched, int n_steps, bool rescale_expression, bool rescale_gesture) override {
+        sched_ = sched; sched_n_ = sched ? n_steps : 0; sched_rs_[0] = sched && rescale_expression; sched_rs_[1] = sched && rescale_gesture;
+        for (auto& in : inst_) { if (int e = in->set_guidance_schedule(sched_, sched_n_, sched_rs_[0], sched_rs_[1])) return e; }
+        if (tw_.inst) { if (int e = tw_.inst->set_guidance_schedule(sched_, sched_n_, sched_rs_[0], sched_rs_[1])) return e; }
         return 0;
     }
     int debug_copy(const std::string& what, float* out) override {
@@ -335,6 +343,7 @@ class Context final : public DenoiserContext {
         }
         split_now_ = ns;
         for (int i = 0; i < ns; ++i) { if (int e = push_guidance(i, ns)) return e; }
+        for (int i = 0; i < ns; ++i) { if (int e = inst_[i]->set_guidance_schedule(sched_, sched_n_, sched_rs_[0], sched_rs_[1])) return e; }
         if (ns == 1) {
             if (int e = inst_[0]->set_lengths(lens_)) return e;
             if (int e = inst_[0]->set_condition(cond_.B, cond_.T, cond_.audio, cond_.pid, cond_.hubert)) return e;
@@ -368,6 +377,7 @@ class Context final : public DenoiserContext {
     }
     std::vector<std::unique_ptr<DenoiserInstance>> inst_;     // [0] owns the weights; the others share them
     const float* gs_ = nullptr; int gs_row_ = 0; bool gs_dbl_ = false;   // the context's guidance (set_guidance)
+    const float* sched_ = nullptr; int sched_n_ = 0; bool sched_rs_[2] = {false, false};   // the context's guidance schedule (set_guidance_schedule)
     ModelConfig cfg_;
     Profiler* prof_ = nullptr;                             // owned by the dsh_ctx; may be null
     hipStream_t st_;

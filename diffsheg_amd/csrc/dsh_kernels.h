@@ -79,6 +79,14 @@ int launch_pack_cols(const float* x, int ldx, int M, int c0, int w, int wpad, fl
 int launch_cfg_mix(const float* o, int ldo, int Mc, int cond_row0, int frames, int w, int has_null, const float* scale, int scale_row,
                    float* eps, int lde, int c0, const float* x, int ldx, const float* c1, const float* c2, float* x0,
                    int ldx0, hipStream_t s);
+// The mix of a doubled batch under a guidance schedule (rowops.hip): sched = [gain row 0 [n_steps] | gain row 1 [n_steps] | phi 0, phi 1]
+// (device fp32), m = the row this encoder reads, t[b * t_row] the clip's model timestep (clamped into the table).  rescale = false: one
+// launch, which also writes x0.  rescale = true (the host's phi_m > 0): a second launch scales eps by the clip's std ratio over its
+// lens[b] (null: frames) valid rows and writes x0; part = 4 fp64 per token row of scratch.
+int launch_cfg_mix_sched(const float* o, int ldo, int Mc, int cond_row0, int frames, int w, const float* scale, int scale_row,
+                         const int64_t* t, int t_row, const float* sched, int n_steps, int m, bool rescale, const int* lens, double* part,
+                         float* eps, int lde, int c0, const float* x, int ldx, const float* c1, const float* c2, float* x0, int ldx0,
+                         hipStream_t s);
 
 // ---- token-per-lane fused Linear, K = 512, bf16 (tl_linear.hip) ------------------------------
 // Row-indexed tensors are TILED (layouts at the top of tl_linear.hip; helpers below) and padded to 128-row blocks.

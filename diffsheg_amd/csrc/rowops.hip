@@ -10,6 +10,8 @@
 //   temb_rows          timestep_embedding                                    (:42-59)
 //   pack_cols          split x into gesture|expression operands              (:741)
 //   cfg_mix            classifier-free mix + expression x0                   (:585-586, :717-724)
+//   cfg_mix_sched      the same under a guidance schedule: gain per timestep and encoder, then
+//   cfg_rescale        the std rescale of the guided eps per clip (no counterpart in the reference)
 #include <algorithm>
 
 #include "dsh_common.h"
@@ -303,6 +305,148 @@ int launch_cfg_mix(const float* o, int ldo, int Mc, int cond_row0, int frames, i
     DSH_REQUIRE(!has_null || scale, "cfg_mix: a doubled batch needs its guidance scales");
     hipLaunchKernelGGL(cfg_mix_kernel, dim3(Mc), dim3(128), 0, s, o, ldo, cond_row0, frames, w, has_null, scale, scale_row, eps, lde,
                        c0, x, ldx, c1, c2, x0, ldx0);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Guidance schedule (dsh_set_guidance_schedule): the mix above with the clip's scale shaped per model timestep and encoder, and the
+// optional std rescale of the guided prediction.  sched = [gain_expression[n] | gain_gesture[n] | phi_expression, phi_gesture] (device).
+//   s_eff = g == 1 ? s : 1 + g (s - 1)   with g = sched[m n + clamp(t_b, 0, n - 1)], s = scale[b scale_row]   (fp32, each op rounded)
+//   e     = s_eff == 1 ? k : u + s_eff (k - u)
+__device__ __forceinline__ float cfg_sched_scale(const float* scale, int scale_row, const int64_t* t, int t_row, const float* sched, int n,
+                                                 int m, int b) {
+    const float s = scale[(size_t)b * scale_row];
+    int64_t tb = t[(size_t)b * t_row];
+    tb = tb < 0 ? 0 : (tb > n - 1 ? n - 1 : tb);               // (never outside the table)
+    const float g = sched[(size_t)m * n + tb];
+    return g == 1.0f ? s : rn_add(1.0f, rn_mul(g, rn_sub(s, 1.0f)));
+}
+// two fp64 values per thread summed over the 128 threads of a block in one fixed order (an xor butterfly inside each wave — commutative
+// pairs, so every lane holds the same bits — then wave 0 + wave 1); every thread gets both sums.  sh: 4 doubles.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ void block128_sum2(double& a, double& b, double* sh) {
+    a = wave_sum_f64(a); b = wave_sum_f64(b);
+    const int wv = threadIdx.x >> 6;
+    __syncthreads();                                                    // (sh may still be read from the call before)
+    if ((threadIdx.x & 63) == 0) { sh[wv] = a; sh[2 + wv] = b; }
+    __syncthreads();
+    a = sh[0] + sh[1]; b = sh[2] + sh[3];
+}
+// One block per token row of a doubled batch.  STATS false: the only launch of the encoder, the plain mix with the scale looked up (writes eps
+// and the optional x0).  STATS true (phi > 0): writes the un-rescaled e into eps and the row's moments of k and e over its w columns —
+// part[row] = {mean k, M2 k, mean e, M2 e} in fp64, M2 = sum (v - mean)^2 taken in a second pass, so a constant row gives exactly 0 — for the
+// rows t < len_b only; x0 is left to cfg_rescale_kernel.  (Moments instead of raw power sums: sum v^2 - (sum v)^2 / n leaves a rounding
+// residue where the variance is 0.)
+template <bool STATS>
+__global__ void cfg_mix_sched_kernel(const float* o, int ldo, int cond_row0, int frames, int w, const float* scale, int scale_row,
+                                     const int64_t* t, int t_row, const float* sched, int n_steps, int m, const int* lens, float* eps,
+                                     int lde, int c0, const float* x, int ldx, const float* c1, const float* c2, float* x0, int ldx0,
+                                     double* part) {
+    __shared__ double sh[4];
+    const int row = blockIdx.x;
+    const int b = row / frames;
+    double sk = 0.0, se = 0.0;
+    for (int c = threadIdx.x; c < w; c += blockDim.x) {
+        const float u = o[(size_t)row * ldo + c];
+        const float k = o[(size_t)(row + cond_row0) * ldo + c];
+        // (scale, timestep and gain are read behind the two loads, as cfg_mix_kernel reads its scale: their latency overlaps the loads')
+        asm volatile("" ::: "memory");
+        const float cs = cfg_sched_scale(scale, scale_row, t, t_row, sched, n_steps, m, b);
+        const float e = cs == 1.0f ? k : rn_add(u, rn_mul(cs, rn_sub(k, u)));
+        eps[(size_t)row * lde + c0 + c] = e;
+        if (STATS) {
+            sk += (double)k; se += (double)e;
+        } else if (x0) {
+            const float a = rn_mul(c1[b], x[(size_t)row * ldx + c0 + c]);
+            const float bb = rn_mul(c2[b], e);
+            x0[(size_t)row * ldx0 + c] = rn_sub(a, bb);
+        }
+    }
+    if (!STATS) return;
+    const int len = lens ? min(max(lens[b], 0), frames) : frames;
+    if (row - b * frames >= len) return;                                 // (block-uniform; padded rows are never read into the moments)
+    block128_sum2(sk, se, sh);
+    const double mk = sk / (double)w, me = se / (double)w;
+    double qk = 0.0, qe = 0.0;
+    for (int c = threadIdx.x; c < w; c += blockDim.x) {
+        // (k again from o; e as this very thread stored it)
+        const double dk = (double)o[(size_t)(row + cond_row0) * ldo + c] - mk, de = (double)eps[(size_t)row * lde + c0 + c] - me;
+        qk += dk * dk; qe += de * de;
+    }
+    block128_sum2(qk, qe, sh);
+    if (threadIdx.x == 0) { double* p = part + (size_t)row * 4; p[0] = mk; p[1] = qk; p[2] = me; p[3] = qe; }
+}
+// Second launch of a rescaled encoder (phi > 0), one block of 128 threads per CFG_RESCALE_ROWS token rows of a clip (a block per row re-read
+// the clip's moments 88 times over; a block per clip left 950 blocks walking 11 352 elements each).  Every block of a clip combines the
+// clip's <= frames row moments from L2 in one fixed order (thread i takes rows i, i + 128, ... in turn, then block128_sum2: the same f in
+// every row of the clip, whatever the batch).  The rows hold w elements each, so the clip's mean is the mean of the row means and its M2 = sum M2_r +
+// w sum (mean_r - mean)^2 — exactly 0 for a constant clip.  f = float(phi sigma_k / sigma_e + (1 - phi)) in fp64 with the unbiased deviations
+// over the n = len_b w valid elements (f = 1 exactly where s_eff = 1, n < 2, or sigma_e is not finite and positive); the block then scales
+// its rows of eps in place (padded rows too: unspecified values stay unspecified) and writes the x0 the single-launch form writes.
+constexpr int CFG_RESCALE_ROWS = 8;
+__global__ void cfg_rescale_kernel(const double* part, int frames, int w, const float* scale, int scale_row, const int64_t* t, int t_row,
+                                   const float* sched, int n_steps, int m, const int* lens, float* eps, int lde, int c0, const float* x,
+                                   int ldx, const float* c1, const float* c2, float* x0, int ldx0) {
+    __shared__ double sh[4];
+    const int nchunk = (frames + CFG_RESCALE_ROWS - 1) / CFG_RESCALE_ROWS, tid = threadIdx.x;
+    const int b = blockIdx.x / nchunk, fr0 = (blockIdx.x - b * nchunk) * CFG_RESCALE_ROWS;
+    const float cs = cfg_sched_scale(scale, scale_row, t, t_row, sched, n_steps, m, b);
+    const float phi = sched[(size_t)2 * n_steps + m];
+    float f = 1.0f;
+    if (cs != 1.0f && phi > 0.0f) {                                      // (block-uniform)
+        const int len = lens ? min(max(lens[b], 0), frames) : frames;
+        const double* pc = part + (size_t)b * frames * 4;
+        double ak = 0.0, ae = 0.0;
+        for (int r = tid; r < len; r += 128) { ak += pc[(size_t)r * 4]; ae += pc[(size_t)r * 4 + 2]; }
+        block128_sum2(ak, ae, sh);
+        const double mk = ak / (double)len, me = ae / (double)len, dw = (double)w;
+        double qk = 0.0, qe = 0.0;
+        for (int r = tid; r < len; r += 128) {
+            const double dk = pc[(size_t)r * 4] - mk, de = pc[(size_t)r * 4 + 2] - me;
+            qk += pc[(size_t)r * 4 + 1] + dw * (dk * dk);
+            qe += pc[(size_t)r * 4 + 3] + dw * (de * de);
+        }
+        block128_sum2(qk, qe, sh);
+        const double nn = (double)len * dw;
+        if (nn >= 2.0) {                                                 // (every thread: the values are block-uniform)
+            const double sdk = sqrt(qk / (nn - 1.0)), sde = sqrt(qe / (nn - 1.0));
+            const double fd = (double)phi * sdk / sde + (1.0 - (double)phi);
+            if (sde > 0.0 && sde <= 1.7976931348623157e308) f = (float)fd;
+        }
+    }
+    const int total = min(CFG_RESCALE_ROWS, frames - fr0) * w;
+    const float a1 = x0 ? c1[b] : 0.0f, a2 = x0 ? c2[b] : 0.0f;
+    for (int i = tid; i < total; i += 128) {
+        const int r = i / w, c = i - r * w;
+        const size_t row = (size_t)b * frames + fr0 + r;
+        float e = eps[row * lde + c0 + c];
+        if (f != 1.0f) { e = rn_mul(f, e); eps[row * lde + c0 + c] = e; }
+        if (x0) x0[row * ldx0 + c] = rn_sub(rn_mul(a1, x[row * ldx + c0 + c]), rn_mul(a2, e));
+    }
+}
+int launch_cfg_mix_sched(const float* o, int ldo, int Mc, int cond_row0, int frames, int w, const float* scale, int scale_row,
+                         const int64_t* t, int t_row, const float* sched, int n_steps, int m, bool rescale, const int* lens, double* part,
+                         float* eps, int lde, int c0, const float* x, int ldx, const float* c1, const float* c2, float* x0, int ldx0,
+                         hipStream_t s) {
+    DSH_REQUIRE(scale && t && sched && n_steps > 0 && (m == 0 || m == 1), "cfg_mix_sched: needs the scales, the timesteps and the schedule table");
+    DSH_REQUIRE(Mc > 0 && frames > 0 && Mc % frames == 0, "cfg_mix_sched: rows must be whole clips");
+    DSH_REQUIRE(!rescale || part, "cfg_mix_sched: the rescale needs its row-moment scratch (4 fp64 per token row)");
+    if (!rescale) {
+        hipLaunchKernelGGL(cfg_mix_sched_kernel<false>, dim3(Mc), dim3(128), 0, s, o, ldo, cond_row0, frames, w, scale, scale_row, t, t_row, sched,
+                           n_steps, m, lens, eps, lde, c0, x, ldx, c1, c2, x0, ldx0, nullptr);
+        DSH_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    hipLaunchKernelGGL(cfg_mix_sched_kernel<true>, dim3(Mc), dim3(128), 0, s, o, ldo, cond_row0, frames, w, scale, scale_row, t, t_row, sched,
+                       n_steps, m, lens, eps, lde, c0, x, ldx, c1, c2, x0, ldx0, part);
+    DSH_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(cfg_rescale_kernel, dim3((Mc / frames) * ceil_div(frames, CFG_RESCALE_ROWS)), dim3(128), 0, s, part, frames, w, scale, scale_row, t, t_row, sched, n_steps, m, lens, eps,
+                       lde, c0, x, ldx, c1, c2, x0, ldx0);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }

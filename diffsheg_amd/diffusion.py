@@ -19,6 +19,7 @@ Differences a caller can observe, all loud:
     their chains (``dsh_run_spec.row_seeds``; :class:`diffsheg_amd.streaming.StreamPool`);
   * the guidance scale is ``opt.cond_scale`` as in the reference (ignored for weights without ``classifier_free``), or the
     loops' ``cond_scale=`` keyword (a float, or one value per batch row), which wins over ``opt``; either holds for the call only;
+    ``cfg_schedule=`` (a glue.CFGSchedule: the weight of the guidance per timestep and encoder, std rescale) likewise holds for the call;
   * ``model_kwargs['length']`` with an entry ``< T`` makes the batch ragged (``UniDiffuser.set_condition(lengths=)``): every row is
     sampled as the clip alone at its length (with ``row_keys``: from the same noise), padded frames of the result are exactly 0;
   * ``model_kwargs['modality']`` (``"expression"`` / ``"gesture"``, the latter with ``model_kwargs['expression']`` = the given track) samples
@@ -326,20 +327,28 @@ class GaussianDiffusion:
 
     @staticmethod
     @contextlib.contextmanager
-    def _native(model, gs):
-        """The native calls of one loop: on the model's device and stream, under the call's guidance scale (the one thing that is sticky in the
-        context — it also governs plain evaluations: the model's own setting comes back afterwards)."""
-        prev_gs = model.guidance_scale
+    def _native(model, gs, sched=None):
+        """The native calls of one loop: on the model's device and stream, under the call's guidance scale and guidance schedule (the two
+        things that are sticky in the context — they also govern plain evaluations: the model's own settings come back afterwards).
+        ``sched``: the call's ``cfg_schedule=`` (None: the model's own setting stays)."""
+        prev_gs, prev_sched = model.guidance_scale, model.guidance_schedule
         set_gs = gs is not None and gs != prev_gs
-        if set_gs:
-            model.set_guidance_scale(gs)
-        cur = model._enter()
+        set_sched = sched is not None and sched != prev_sched
+        if set_sched:
+            model.set_guidance_schedule(sched)
         try:
-            yield
-        finally:
-            model._exit(cur)
             if set_gs:
-                model.set_guidance_scale(prev_gs)
+                model.set_guidance_scale(gs)
+            cur = model._enter()
+            try:
+                yield
+            finally:
+                model._exit(cur)
+                if set_gs:
+                    model.set_guidance_scale(prev_gs)
+        finally:
+            if set_sched:
+                model.set_guidance_schedule(prev_sched)
 
     @staticmethod
     def _check_guide_shapes(guidance, shape) -> None:
@@ -368,9 +377,10 @@ class GaussianDiffusion:
 
     def _run(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0,
              noise_source=None, seed=None, return_trace=False, row_keys=None, cond_scale=None, tail_blend=False,
-             row_seeds=None, start_level=None, x_start=None, add_blend=None, solver=None):
+             row_seeds=None, start_level=None, x_start=None, add_blend=None, solver=None, cfg_schedule=None):
         if not isinstance(model, UniDiffuser):
             raise TypeError("model must be a diffsheg_amd.model.UniDiffuser (no generic-callable / CPU fallback)")
+        model.check_guidance_schedule(cfg_schedule)        # (refused here, before anything is conditioned or set in the native context)
         # the update rule of the DDIM loops: refused here, before anything is conditioned or set in the native context
         if solver is None:
             solver = self.solver if kind == 0 else "ddim"
@@ -495,7 +505,7 @@ class GaussianDiffusion:
         if return_trace:
             trace = torch.empty(n_steps.value, B, T, Cc, device=dev)
             spec.trace = trace.data_ptr()
-        with self._native(model, gs):
+        with self._native(model, gs, cfg_schedule):
             _lib.check(lib.dsh_sample_run(model._h, C.byref(opts), C.byref(spec)), "dsh_sample_run")
         self._keep = (gt, mask, stack, guide)   # consumed asynchronously on the stream
         if son:
@@ -537,7 +547,11 @@ class GaussianDiffusion:
         ``cond_fn``: a :class:`diffsheg_amd.glue.MotionGuidance` (soft keyframes, velocity / acceleration damping) — every denoise step is
         the guided form of its kernel (``condition_score``, gaussian_diffusion.py:660-682; ``p_sample_loop``: ``condition_mean``,
         :645-658), under both solvers, with masks, ``eta`` and ragged lengths; no draw is added.  Any other callable, and
-        ``denoised_fn``, stay refused."""
+        ``denoised_fn``, stay refused.
+
+        ``cfg_schedule`` (keyword, also on ``p_sample_loop``): a :class:`diffsheg_amd.glue.CFGSchedule` — the guidance weight per model
+        timestep and encoder, and the std rescale of the guided eps — for this call, handled as ``cond_scale=`` is: the model's sticky
+        schedule (``UniDiffuser.set_guidance_schedule``) comes back afterwards, also when the call raises."""
         if not self._respacing:
             raise NotImplementedError("ddim_sample_loop needs a SpacedDiffusion('ddimK') (trainers use 'ddim25')")
         return self._run(0, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta, **kw)
@@ -644,7 +658,8 @@ class GaussianDiffusion:
         _lib.check(rc, what)
         return buf
 
-    def training_losses(self, model, x_start, t, model_kwargs=None, noise=None, *, seed=None, row_keys=None, row_seeds=None, cond_scale=None):
+    def training_losses(self, model, x_start, t, model_kwargs=None, noise=None, *, seed=None, row_keys=None, row_seeds=None, cond_scale=None,
+                        cfg_schedule=None):
         """gaussian_diffusion.py:1319-1426, epsilon / MSE branch, in the reference's eval mode (no conditioning dropout, no gradient):
         ``x_t = q_sample(x_start, t, noise)``, one evaluation ``eps = model(x_t, timestep_map[t], ...)``, and the loss terms reduced on the
         device (``dsh_op_denoise_losses``).  ``x_start [B, T, C]`` on the GPU; ``t`` an int or one index per row into THIS diffusion's
@@ -653,7 +668,8 @@ class GaussianDiffusion:
         ``pe_type``; ``y`` is accepted and unused: the reference's masking at :1394-1400 is commented out); ``length`` entries ``< T`` make
         the batch ragged under q_sample's rules (Philox noise then needs ``row_keys``): row ``b`` is scored as the clip alone at its
         length.  ``cond_scale`` as for the loops: with a scale other than 1 the guided eps is scored (transformer.py:537, :585),
-        ``cond_scale=1.0`` scores the conditional model.
+        ``cond_scale=1.0`` scores the conditional model.  ``cfg_schedule`` (a :class:`diffsheg_amd.glue.CFGSchedule`) as for the loops: the
+        guided eps under that schedule at each row's timestep, for this call.
 
         Returns the reference's keys where they cost nothing — ``"mse" [B]`` (``mean_flat`` of ``(noise - eps)^2`` over the row's own
         frames, fp64), ``"target"`` (the noise), ``"pred"`` (eps), ``"target_x0"`` (``x_start`` itself), ``"pred_x0"`` — plus ``"x_t"``,
@@ -664,6 +680,7 @@ class GaussianDiffusion:
         # ---- refusals: before any device call ----
         if not isinstance(model, UniDiffuser):
             raise TypeError("model must be a diffsheg_amd.model.UniDiffuser (no generic-callable / CPU fallback)")
+        model.check_guidance_schedule(cfg_schedule)
         lt = self.loss_type
         if (isinstance(lt, LossType) and lt.is_vb()) or (isinstance(lt, str) and lt.lower() in ("kl", "rescaled_kl")):
             raise NotImplementedError(f"loss_type {lt}: the variational-bound losses are not built (FIXED_SMALL variance: only the MSE branch)")
@@ -715,7 +732,7 @@ class GaussianDiffusion:
         c1 = self._row_values(self.sqrt_recip_alphas_cumprod, ts, B, dev)
         c2 = self._row_values(self.sqrt_recipm1_alphas_cumprod, ts, B, dev)
         t_model = self._row_values(np.asarray(self.timestep_map, dtype=np.int64), ts, B, dev, torch.int64)
-        with self._native(model, gs):
+        with self._native(model, gs, cfg_schedule):
             eps = model(x_t, t_model, sqrt_alphas=[c1, c2], audio_emb=model_kwargs.get("audio_emb"), length=model_kwargs.get("length"),
                         person_id=model_kwargs.get("person_id"), add_cond=model_kwargs.get("add_cond"),
                         pe_type=model_kwargs.get("pe_type", "pe_sinu"), y=model_kwargs.get("y"))

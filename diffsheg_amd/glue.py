@@ -11,6 +11,9 @@
   to BVH (ddpm_beat_trainer.py:1044-1060, datasets/rotation_converter.py), and the dataset's opposite direction
   (datasets/beat.py:376-401) for frames a caller holds as Euler / BVH poses; HIP kernels, output stays on the device.
 
+* :class:`CFGSchedule` — the classifier-free guidance weight per model timestep and per encoder, and the std rescale of the guided
+  prediction (``UniDiffuser.set_guidance_schedule``, the loops' ``cfg_schedule=``); host-side tables.
+
 * :func:`edit_region` — the keep mask of an edit (``DDPMTrainer.sample_variations(keep=)``) from frame and column ranges, HIP kernel.
 
 HuBERT itself (``facebook/hubert-large-ls960-ft``), mel extraction and the BVH / face-JSON file writers (they need the dataset's
@@ -22,6 +25,7 @@ import copy
 import ctypes as C
 from typing import Dict, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -318,6 +322,105 @@ class MotionGuidance:
         length = kwargs.get("length")
         lens = None if length is None else [int(v) for v in (length.tolist() if isinstance(length, torch.Tensor) else length)]
         return guidance_grad_torch(x, self.target, self.weight, self.vel, self.acc, lens, self.scale_at(ts.pop()))
+
+
+def _gain_row(gain, steps: int, what: str) -> np.ndarray:
+    """One encoder's gains as float32 ``[steps]``: ``None`` (1 everywhere), a number, an array of ``steps`` values, or a callable
+    ``t -> gain`` evaluated here, on the host, at every original timestep."""
+    if gain is None:
+        row = np.ones(steps, dtype=np.float32)
+    elif callable(gain):
+        row = np.asarray([float(gain(t)) for t in range(steps)], dtype=np.float32)
+    else:
+        try:
+            a = np.asarray(gain.detach().cpu().numpy() if isinstance(gain, torch.Tensor) else gain, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"CFGSchedule: {what} must be None, a number, {steps} values or a callable t -> gain") from e
+        if a.ndim == 0:
+            a = np.full(steps, float(a))
+        if a.shape != (steps,):
+            raise ValueError(f"CFGSchedule: {what} needs one gain per original timestep ({steps}), got shape {a.shape}")
+        with np.errstate(over="ignore"):
+            row = a.astype(np.float32)
+    if not np.all(np.isfinite(row)):
+        raise ValueError(f"CFGSchedule: the {what} gains must be finite (in float32)")
+    return row
+
+
+class CFGSchedule:
+    """How strongly the classifier-free guidance acts, per model timestep and per encoder, and the std rescale of the guided prediction
+    (``dsh_set_guidance_schedule``).  At a clip's original timestep ``t`` encoder ``m`` mixes with
+
+        ``s_eff = 1 + gain_m[t] * (cond_scale - 1)``      (``gain == 1``: ``cond_scale`` itself; ``gain == 0``: the conditional prediction)
+
+    so a gain shapes the part of the scale that guides and leaves ``cond_scale`` (one value or one per clip) the knob it was.  ``rescale``
+    (φ in ``[0, 1]``, one value or an ``(expression, gesture)`` pair) pulls the std of each clip's guided eps back towards the conditional
+    prediction's: ``eps *= φ * std(k) / std(eps) + (1 - φ)`` over the clip's own frames and the encoder's columns (Lin et al.,
+    "Common diffusion noise schedules and sample steps are flawed", ``guidance_rescale``).
+
+    ``expression`` / ``gesture``: ``None`` (gain 1), a float, ``steps`` values, or a callable ``t -> gain`` evaluated on the host.
+    Give it to ``UniDiffuser.set_guidance_schedule`` (sticky) or as ``cfg_schedule=`` to a sampling loop (that call only).  Not to be
+    confused with :class:`MotionGuidance`, the soft constraints on the motion itself."""
+
+    def __init__(self, expression=None, gesture=None, rescale=0.0, steps: int = 1000):
+        if not isinstance(steps, (int, np.integer)) or int(steps) < 1:
+            raise ValueError(f"CFGSchedule: steps must be a positive integer, got {steps!r}")
+        self.steps = int(steps)
+        self.expression = _gain_row(expression, self.steps, "expression")
+        self.gesture = _gain_row(gesture, self.steps, "gesture")
+        try:
+            phi = np.asarray(rescale, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError) as e:
+            raise ValueError("CFGSchedule: rescale must be one number or an (expression, gesture) pair") from e
+        if phi.size not in (1, 2):
+            raise ValueError(f"CFGSchedule: rescale must be one number or an (expression, gesture) pair, got {phi.size} values")
+        phi = np.broadcast_to(phi, (2,)).astype(np.float32)
+        if not np.all(np.isfinite(phi)) or np.any(phi < 0) or np.any(phi > 1):
+            raise ValueError(f"CFGSchedule: rescale must lie in [0, 1], got {rescale!r}")
+        self.rescale = (float(phi[0]), float(phi[1]))         # (float32-representable: what the kernels read)
+
+    @classmethod
+    def interval(cls, t_lo: int, t_hi: int, rescale=0.0, steps: int = 1000) -> "CFGSchedule":
+        """The guidance interval: gain 1 at the original timesteps ``t_lo <= t <= t_hi``, 0 outside, for both encoders."""
+        t_lo, t_hi = int(t_lo), int(t_hi)
+        if not 0 <= t_lo <= t_hi < int(steps):
+            raise ValueError(f"CFGSchedule.interval: needs 0 <= t_lo <= t_hi < {steps}, got ({t_lo}, {t_hi})")
+        row = np.zeros(int(steps), dtype=np.float32)
+        row[t_lo:t_hi + 1] = 1.0
+        return cls(row, row.copy(), rescale, steps)
+
+    @classmethod
+    def from_levels(cls, diffusion, gains, gesture_gains=None, rescale=0.0) -> "CFGSchedule":
+        """One gain per spaced level of ``diffusion`` (a ``'ddimK'`` / ``'logsnrK'`` SpacedDiffusion; level 0 is the last step), for both
+        encoders or, with ``gesture_gains``, ``gains`` for the expression encoder.  The levels map through ``diffusion.timestep_map``, and
+        an original timestep takes the gain of the smallest kept timestep >= it (above the largest: the top level's), so a restart or a
+        plain evaluation between two levels finds the gain of the level above."""
+        tmap = np.asarray(sorted(int(v) for v in diffusion.timestep_map), dtype=np.int64)
+        steps = int(getattr(diffusion, "original_num_steps", len(tmap)))
+        idx = np.minimum(np.searchsorted(tmap, np.arange(steps), side="left"), len(tmap) - 1)
+
+        def row(g, what):
+            a = np.asarray(g, dtype=np.float64)
+            if a.shape != (len(tmap),):
+                raise ValueError(f"CFGSchedule.from_levels: {what} needs one gain per level ({len(tmap)}), got shape {a.shape}")
+            return a[idx]
+        e = row(gains, "gains")
+        return cls(e, e if gesture_gains is None else row(gesture_gains, "gesture_gains"), rescale, steps)
+
+    @property
+    def trivial(self) -> bool:
+        """All gains 1 and no rescale: the unscheduled arithmetic."""
+        return bool(np.all(self.expression == 1) and np.all(self.gesture == 1) and self.rescale == (0.0, 0.0))
+
+    @property
+    def same_for_both(self) -> bool:
+        return bool(np.array_equal(self.expression, self.gesture) and self.rescale[0] == self.rescale[1])
+
+    def __eq__(self, other):
+        return (isinstance(other, CFGSchedule) and self.steps == other.steps and self.rescale == other.rescale
+                and np.array_equal(self.expression, other.expression) and np.array_equal(self.gesture, other.gesture))
+
+    __hash__ = None
 
 
 def _ranges(v, what: str, hi: int):

@@ -16,6 +16,7 @@ import math
 import numbers
 from typing import Dict, Iterator, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -140,7 +141,7 @@ class UniDiffuser:
         mc = _lib.ModelConfigC(cfg.dim_pose, cfg.expression_dim, cfg.style_dim, int(cfg.classifier_free),
                                float(cfg.cond_scale), cfg.latent_dim, cfg.ff_size, cfg.num_layers, cfg.num_heads,
                                cfg.audio_dim, cfg.aud_latent_dim, cfg.hubert_dim, cfg.hubert_enc_dim,
-                               _PRECISION[precision], int(not cfg.unidiffuser))
+                               _PRECISION[precision], int(not cfg.unidiffuser), int(cfg.diffusion_steps))
         if cfg.unidiffuser != self._UNIDIFFUSER:
             raise ValueError(f"{type(self).__name__} needs a config with unidiffuser={self._UNIDIFFUSER} (runner.py:33-57 picks the class by opt.unidiffuser)")
         h = C.c_void_p()
@@ -151,6 +152,7 @@ class UniDiffuser:
         self.lengths = None                    # per-clip frame counts of a ragged condition (set_condition(lengths=))
         self.modality = 0                      # 0 both / 1 expression / 2 gesture: part of the condition (set_condition(modality=))
         self._guidance = None                  # set_guidance_scale(): None = the config's cond_scale
+        self._schedule = None                  # set_guidance_schedule(): None = no schedule
         self._dummy = torch.zeros(1, device=self.device)
         self.load_state_dict(state_dict)
 
@@ -299,6 +301,43 @@ class UniDiffuser:
     def guidance_scale(self) -> Optional[Tuple[float, ...]]:
         """The current setting: ``None`` (the config's ``cond_scale``) or the tuple given to :meth:`set_guidance_scale`."""
         return self._guidance
+
+    def check_guidance_schedule(self, sched) -> None:
+        """What :meth:`set_guidance_schedule` refuses, without touching the context (the loops ask before they condition anything)."""
+        from .glue import CFGSchedule
+        if sched is None:
+            return
+        if not isinstance(sched, CFGSchedule):
+            raise ValueError(f"a guidance schedule is a glue.CFGSchedule (or None), got {type(sched).__name__}")
+        if sched.steps != int(self.cfg.diffusion_steps):
+            raise ValueError(f"CFGSchedule(steps={sched.steps}): the model has {self.cfg.diffusion_steps} diffusion steps (one gain per original timestep)")
+        if not self.cfg.classifier_free and not sched.trivial:
+            raise ValueError("CFGSchedule: the weights are not classifier-free (no null_cond_emb), there is no guidance to schedule")
+        if not self.cfg.unidiffuser and not sched.same_for_both:
+            raise ValueError("CFGSchedule: a single MotionTransformer has one encoder: expression and gesture gains (and rescale) must be equal")
+
+    def set_guidance_schedule(self, sched=None) -> None:
+        """Guidance schedule of every following evaluation and sampling loop (sticky, like :meth:`set_guidance_scale`): a
+        :class:`diffsheg_amd.glue.CFGSchedule` — gains per original timestep and encoder, std rescale — or ``None`` for none, which puts
+        every evaluation back on the launches it issues without one (``dsh_set_guidance_schedule``)."""
+        self.check_guidance_schedule(sched)
+        cur = self._enter()
+        try:
+            if sched is None:
+                _lib.check(self._lib.dsh_set_guidance_schedule(self._h, None, None, 0, 0.0, 0.0), "dsh_set_guidance_schedule")
+            else:
+                fp = C.POINTER(C.c_float)
+                e, g = np.ascontiguousarray(sched.expression, dtype=np.float32), np.ascontiguousarray(sched.gesture, dtype=np.float32)
+                _lib.check(self._lib.dsh_set_guidance_schedule(self._h, e.ctypes.data_as(fp), g.ctypes.data_as(fp), sched.steps,
+                                                               sched.rescale[0], sched.rescale[1]), "dsh_set_guidance_schedule")
+        finally:
+            self._exit(cur)
+        self._schedule = sched
+
+    @property
+    def guidance_schedule(self):
+        """The current setting: ``None`` or the :class:`~diffsheg_amd.glue.CFGSchedule` given to :meth:`set_guidance_schedule`."""
+        return self._schedule
 
     # ---- boundary 1 -----------------------------------------------------------------------------
     def __call__(self, x, timesteps, sqrt_alphas=None, audio_emb=None, length=None, person_id=None, add_cond=None,

@@ -198,7 +198,7 @@ class DDPMTrainer:
         return euler_to_axis_angle(pose.to(self.device), self.pose_stats, split_pos=self._gesture_split(), lengths=lengths)
 
     def generate_batch(self, audio_emb, p_id, dim_pose, add_cond={}, inpaint_dict=None, cond_scale=None, lengths=None,
-                       pose_rep: str = "axis_angle", modality="both", expression=None, guidance=None, **sampler_kw):
+                       pose_rep: str = "axis_angle", modality="both", expression=None, guidance=None, cfg_schedule=None, **sampler_kw):
         """ddpm_show_trainer.py:163-198.  ``sampler_kw`` (noise_source= / seed=) is this build's
         noise-injection hook; the reference draws from the global torch RNG.  ``cond_scale`` (a float, or one value per batch
         row) overrides ``opt.cond_scale`` for this batch.  ``lengths`` (one frame count per row, ``1 .. T``): clips of different
@@ -211,10 +211,14 @@ class DDPMTrainer:
         ``inpaint_dict`` is honoured on the active columns only.  ``row_seeds=`` (in ``sampler_kw``, with ``row_keys=``): one Philox key
         per row in place of ``seed=`` — rows at different windows of their chains in one batch (:mod:`diffsheg_amd.streaming`).
         ``guidance`` (a :class:`diffsheg_amd.glue.MotionGuidance` built for ``[B, T, dim_pose]``): soft keyframes and velocity /
-        acceleration damping, fused into every denoise step; with ``lengths`` the stencils end at each clip's own last frame."""
+        acceleration damping, fused into every denoise step; with ``lengths`` the stencils end at each clip's own last frame.
+        ``cfg_schedule`` (a :class:`diffsheg_amd.glue.CFGSchedule`): the weight of the classifier-free guidance per model timestep and
+        encoder, and the std rescale of the guided eps, for this batch (default: the encoder's sticky ``set_guidance_schedule``)."""
         euler = self._euler_requested(pose_rep)
         if cond_scale is not None:
             sampler_kw["cond_scale"] = cond_scale
+        if cfg_schedule is not None:
+            sampler_kw["cfg_schedule"] = cfg_schedule
         if guidance is not None:
             sampler_kw["cond_fn"] = guidance
         audio_emb = audio_emb.to(self.device)
@@ -397,7 +401,7 @@ class DDPMTrainer:
                              noise_source_for_window=None, seed: Optional[int] = None,
                              motions: Optional[torch.Tensor] = None, row_keys: Optional[Sequence[int]] = None,
                              cond_scale=None, lengths: Optional[Sequence[int]] = None, pose_rep: str = "axis_angle",
-                             modality="both", expression=None, guidance=None):
+                             modality="both", expression=None, guidance=None, cfg_schedule=None):
         """The per-video body of test_arbitrary_len (ddpm_show_trainer.py:864-906): windows of n_poses
         with stride n_poses-overlap_len; window k>0 out-paints from the last overlap_len frames of
         window k-1 (sequential chain).  Output stays on the device (the reference copies every window
@@ -423,7 +427,9 @@ class DDPMTrainer:
         ``guidance`` (a :class:`diffsheg_amd.glue.MotionGuidance`; chains of equal length only): its ``target`` / ``weight`` are
         stream-long ``[B, N, C]`` and cut into windows like the audio, ``vel`` / ``acc`` / ``space`` / ``level_scale`` are shared by every
         window.  The stencils are per window: smoothness is NOT enforced across a window boundary (the out-painted overlap carries the
-        previous window's frames).  With ``lengths`` (the ragged chain) it raises ``NotImplementedError``."""
+        previous window's frames).  With ``lengths`` (the ragged chain) it raises ``NotImplementedError``.
+
+        ``cfg_schedule`` (a :class:`diffsheg_amd.glue.CFGSchedule`): the guidance schedule of every window, in both forms."""
         if guidance is not None and lengths is not None:
             raise NotImplementedError("guidance in the ragged chain (lengths=) is not built")
         euler = self._euler_requested(pose_rep)
@@ -436,7 +442,7 @@ class DDPMTrainer:
                     raise ValueError(f"guidance: {name} must be stream-long [B, N, C] = [{int(audio_emb.shape[0])}, {N}, C], got {tuple(v.shape)}")
         if lengths is not None:
             outs = self._sample_arbitrary_len_ragged(audio_emb, p_id, add_cond, [int(v) for v in lengths], noise_source_for_window, seed,
-                                                     motions, row_keys, cond_scale, modality, expression)
+                                                     motions, row_keys, cond_scale, modality, expression, cfg_schedule)
             return [self._to_euler(o) for o in outs] if euler else outs
         opt = self.opt
         n_poses, L, C = int(opt.n_poses), int(opt.overlap_len), int(opt.net_dim_pose)
@@ -487,6 +493,8 @@ class DDPMTrainer:
                 kw["modality"], kw["expression"] = modality, ex
             if guide_list[ii] is not None:
                 kw["guidance"] = guide_list[ii]
+            if cfg_schedule is not None:
+                kw["cfg_schedule"] = cfg_schedule
             outputs = self.generate_batch(a, p_id, C, cnd, inpaint_dict, **kw)
             if son:
                 previous_noisy_tail, outputs = outputs["saved_noisy_tail"], outputs["sample"]
@@ -515,7 +523,7 @@ class DDPMTrainer:
         return expression
 
     def _sample_arbitrary_len_ragged(self, audio_emb, p_id, add_cond, lengths: List[int], noise_source_for_window, seed, motions,
-                                     row_keys, cond_scale, modality="both", expression=None) -> List[torch.Tensor]:
+                                     row_keys, cond_scale, modality="both", expression=None, cfg_schedule=None) -> List[torch.Tensor]:
         opt = self.opt
         n_poses, L, C = int(opt.n_poses), int(opt.overlap_len), int(opt.net_dim_pose)
         step = n_poses - L
@@ -575,6 +583,8 @@ class DDPMTrainer:
                 kw["cond_scale"] = gs[0] if len(gs) == 1 else [gs[b] for b in rows]
             if any(n != T for n in lens):
                 kw["lengths"] = lens
+            if cfg_schedule is not None:
+                kw["cfg_schedule"] = cfg_schedule
             if expression is not None or modality not in (None, "both", 0):
                 kw["modality"] = modality
                 kw["expression"] = cut(expression, rows, wb["start"], T).contiguous() if expression is not None else None
@@ -664,12 +674,13 @@ class DDPMTrainer:
                           level: Optional[int] = None, strength: Optional[float] = None, keep: Optional[torch.Tensor] = None,
                           seed: Optional[int] = None, row_keys: Optional[Sequence[int]] = None, row_seeds: Optional[Sequence[int]] = None,
                           cond_scale=None, lengths=None, modality="both", expression=None, pose_rep: str = "axis_angle",
-                          guidance=None) -> torch.Tensor:
+                          guidance=None, cfg_schedule=None) -> torch.Tensor:
         """Variations of an existing motion ``motions [B, T, C]`` (standardised, the sampler's representation): it is noised to spaced
         level ``K - 1`` (``q_sample`` with the loop's draw 0) and denoised from there with the DDIM loop, in one native call.  ``level=K``
         (``1 .. respacing``) or ``strength=s`` (``K = max(1, round(s * respacing))``): small K stays close to the input, K = respacing
         keeps nothing of it.  Two seeds give two variations; ``row_keys`` / ``row_seeds`` / ``lengths`` / ``modality`` / ``expression``
-        / ``cond_scale`` / ``pose_rep`` as for :meth:`generate_batch`.
+        / ``cond_scale`` / ``cfg_schedule`` / ``pose_rep`` as for :meth:`generate_batch` (the gains are indexed by the original timestep, so a
+        restart reads the same table as the whole loop).
 
         ``keep`` (bool, broadcastable to ``[B, T, C]``, True = leave as it is; :func:`diffsheg_amd.glue.edit_region` builds one): the
         RePaint path — ``gt = motions``, ``mask = keep``, the jump schedule walked from ``t_T = K`` — with ``addBlend`` off (the
@@ -697,7 +708,8 @@ class DDPMTrainer:
                 raise ValueError(f"keep {tuple(keep.shape)} does not broadcast to {(B, T, C)}") from e
             inpaint = {"gt": x0, "outpainting_mask": mask}
             kw["add_blend"] = False
-        for k, v in (("seed", seed), ("row_keys", row_keys), ("row_seeds", row_seeds), ("cond_scale", cond_scale), ("guidance", guidance)):
+        for k, v in (("seed", seed), ("row_keys", row_keys), ("row_seeds", row_seeds), ("cond_scale", cond_scale), ("guidance", guidance),
+                     ("cfg_schedule", cfg_schedule)):
             if v is not None:
                 kw[k] = v
         return self.generate_batch(audio_emb, p_id, C, add_cond, inpaint, lengths=lengths, pose_rep=pose_rep, modality=modality,

@@ -59,6 +59,7 @@ typedef struct dsh_model_config {
                              /* runner.py:32-45.  1: ONE MotionTransformer over all dim_pose + expression_dim channels     */
                              /* (runner.py:46-57, opt.unidiffuser = False, model_base 'transformer_encoder'): keys without */
                              /* the encoder_* prefix, audio_proj on the 128 mel features; c1 / c2 of dsh_eval are unused   */
+    int32_t diffusion_steps; /* length of the original timestep scale (0: 1000): entries of a guidance schedule's gain rows       */
 } dsh_model_config;
 
 /* Sampler options = the `opt` attributes read by gaussian_diffusion.py / respace.py / scheduler.py. */
@@ -350,6 +351,31 @@ int64_t dsh_sample_num_steps_subset(const dsh_sampler_opts* opts, int32_t masked
  * only when the weights are classifier_free and some scale != 1; a clip at exactly 1 inside a doubled batch returns k itself.  Mixed
  * batches pay the full doubling.  -1 on a non-finite value, and on any value != 1 when the weights are not classifier_free. */
 int dsh_set_guidance_scale(dsh_ctx* ctx, const float* scales_host, int32_t n);
+/* Guidance schedule: the weight of the guidance per model timestep and per encoder, and the std rescale of the guided
+ * prediction (Lin et al., "Common diffusion noise schedules and sample steps are flawed", guidance_rescale).  Host arrays of n_steps =
+ * the model's diffusion_steps gains each (index = the ORIGINAL timestep, what dsh_eval takes as t), rescale factors phi in [0, 1].  Sticky
+ * like the scale; n_steps = 0 clears it (the arrays are not read), and with no schedule set every evaluation issues the launches it
+ * always did.  Per clip b and encoder m (expression / gesture) at the evaluation's timestep t_b, in fp32, every operation rounded to
+ * nearest, no fma:
+ *     s      = scale[b]                                   (dsh_set_guidance_scale)
+ *     g      = gain_m[t_b]
+ *     s_eff  = g == 1 ? s : 1 + g (s - 1)
+ *     e      = s_eff == 1 ? k : u + s_eff (k - u)          (u / k: the unconditional / conditional prediction)
+ * and, only where the batch is doubled, phi_m > 0 and s_eff != 1, over the clip's own valid elements (frames t < len_b, the encoder's w
+ * columns; padded frames are never read), n = len_b w:
+ *     f  = float(phi_m sigma_k / sigma_e + (1 - phi_m))    sigma: unbiased (n - 1) standard deviation, accumulated in fp64
+ *          when n >= 2 and sigma_e is finite and > 0, else exactly 1
+ *     e' = f e
+ * The expression x0 the gesture encoder reads is c1 x - c2 e'.  The doubling rule of dsh_set_guidance_scale is unchanged: the null half is
+ * evaluated if and only if the weights are classifier_free and some scale[b] != 1; in an undoubled batch the schedule is inert, and a gain
+ * of 0 gives s_eff = 1 and takes k itself (the null half is still evaluated).  A modality run alone reads its own row.  The table is
+ * copied in stream order into a device buffer the context owns at a fixed address, which the kernels (and captured graphs) read when
+ * they run.  One launch per encoder and evaluation with phi_m = 0 (the launch count of the unscheduled mix), two with phi_m > 0.
+ * -1 before any state changes on a non-finite gain, phi outside [0, 1], n_steps != diffusion_steps, a schedule other than all gains 1
+ * with phi 0 on weights that are not classifier_free, and on a single_transformer context (one encoder) with two different rows or
+ * two different phi. */
+int dsh_set_guidance_schedule(dsh_ctx* ctx, const float* gain_expression, const float* gain_gesture, int32_t n_steps, float rescale_expression,
+                              float rescale_gesture);
 
 /* ---- schedule / table introspection (host; parity tests for S1-S3) ---------------------------- */
 /* name in {betas, alphas_cumprod, alphas_cumprod_prev, sqrt_recip_alphas_cumprod,
@@ -668,6 +694,14 @@ int dsh_op_temb(void* hip_stream, int32_t dtype, const int64_t* t_dev, int32_t B
 int dsh_op_cfg_mix(void* hip_stream, const float* o, int32_t ldo, int32_t Mc, int32_t cond_row0, int32_t frames, int32_t w, int32_t has_null,
                    const float* scale, int32_t scale_row, float* eps, int32_t lde, int32_t c0, const float* x, int32_t ldx, const float* c1,
                    const float* c2, float* x0, int32_t ldx0);
+/* the same under a guidance schedule (dsh_set_guidance_schedule states the formulas): the arguments of dsh_op_cfg_mix, then t (device int64,
+ * clip b's model timestep t[b * t_row], clamped into the table), table (device fp32 [2, n_steps]), which (the row read), rescale (phi of
+ * that row: 0 = one launch, > 0 = two, then the row moments live in scratch the entry owns) and lens_dev (device int32 [Mc / frames],
+ * nullable = frames).  has_null == 0: dsh_op_cfg_mix itself.  Synchronises the stream. */
+int dsh_op_cfg_mix_sched(void* hip_stream, const float* o, int32_t ldo, int32_t Mc, int32_t cond_row0, int32_t frames, int32_t w, int32_t has_null,
+                         const float* scale, int32_t scale_row, float* eps, int32_t lde, int32_t c0, const float* x, int32_t ldx, const float* c1,
+                         const float* c2, float* x0, int32_t ldx0, const int64_t* t, int32_t t_row, const float* table, int32_t n_steps,
+                         int32_t which, float rescale, const int32_t* lens_dev);
 /* Conv1d(k = 3, padding = 1) patches: out[(b, t), tap * Cin + c] = x[b, t + tap - 1, c], zero outside [0, len_b); lens_dev nullable (len_b =
  * frames).  dtype 0 fp32 / 1 bf16: fp32 -> fp32, fp32 -> bf16, bf16 -> bf16. */
 int dsh_op_im2col3(void* hip_stream, int32_t dtype_in, int32_t dtype_out, const void* x, int32_t ldx, int32_t B, int32_t frames, int32_t Cin,
