@@ -49,7 +49,8 @@ class RunSpecC(C.Structure):
                 ("guidance", C.c_int32), ("guide_space", C.c_int32), ("n_guide_scale", C.c_int32),
                 ("guide_batch", C.c_int32), ("guide_frames", C.c_int32), ("guide_channels", C.c_int32),
                 ("guide_target", C.c_void_p), ("guide_weight", C.c_void_p), ("guide_vel", C.c_void_p), ("guide_acc", C.c_void_p),
-                ("guide_scale", C.POINTER(C.c_float))]
+                ("guide_scale", C.POINTER(C.c_float)),
+                ("sync_left", C.POINTER(C.c_int32)), ("n_sync", C.c_int32), ("sync_len", C.c_int32)]
 
 
 class GuideC(C.Structure):
@@ -61,7 +62,7 @@ class GuideC(C.Structure):
 GUIDE_SPACES = {"x_t": 0, "x0": 1}      # the header's two guide-space values
 
 
-def run_spec(timesteps=(), row_keys=(), row_seeds=(), guide_scale=(), **fields) -> RunSpecC:
+def run_spec(timesteps=(), row_keys=(), row_seeds=(), guide_scale=(), sync_left=(), **fields) -> RunSpecC:
     """A zeroed dsh_run_spec of this binding's size with ``fields`` set; the host arrays are copied and kept alive by the result."""
     s = RunSpecC(struct_size=C.sizeof(RunSpecC), **fields)
     kept, keys = [int(v) for v in timesteps], [int(v) & 0xFFFFFFFFFFFFFFFF for v in row_keys]
@@ -69,8 +70,11 @@ def run_spec(timesteps=(), row_keys=(), row_seeds=(), guide_scale=(), **fields) 
     if seeds and len(seeds) != len(keys):               # (the library reads n_rows entries of both)
         raise ValueError(f"row_seeds needs row_keys and one seed per key ({len(keys)}), got {len(seeds)}")
     scales = [float(v) for v in guide_scale]
+    left = [int(v) for v in sync_left]
     s._arrays = ((C.c_int32 * len(kept))(*kept), (C.c_uint64 * len(keys))(*keys), (C.c_uint64 * len(seeds))(*seeds),
-                 (C.c_float * len(scales))(*scales))
+                 (C.c_float * len(scales))(*scales), (C.c_int32 * len(left))(*left))
+    if left:
+        s.sync_left, s.n_sync = s._arrays[4], len(left)
     if scales:
         s.guide_scale, s.n_guide_scale = s._arrays[3], len(scales)
     if kept:
@@ -164,6 +168,8 @@ SYMBOLS = {
     "dsh_op_philox_randn_rows_ragged_seeded": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
                                                          C.POINTER(C.c_int32), C.c_uint64, C.c_int32, _P]),
     "dsh_op_chain_handoff": (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32), _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "dsh_op_window_sync": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P, C.POINTER(C.c_int32), _P, C.c_int32,
+                                     C.c_int32, C.c_int32]),
     "dsh_op_chain_save_tail": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P, C.POINTER(C.c_int32), _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32]),
     "dsh_op_ddim_step_full": (C.c_int, [_P] * 10 + [C.c_int32] * 3 + [C.c_float] * 6 + [C.c_int32] * 6),
     "dsh_op_ddpm_step": (C.c_int, [_P] * 5 + [C.c_int64] + [C.c_float] * 5 + [C.c_int32] * 4),

@@ -294,6 +294,8 @@ static int to_spec(const dsh_sampler_opts* opts, const dsh_run_spec* c, dsh::Run
         g.batch = f.guide_batch; g.frames = f.guide_frames; g.channels = f.guide_channels;
         g.level_scale.assign(f.guide_scale, f.guide_scale + f.n_guide_scale);
     }
+    DSH_REQUIRE(f.n_sync >= 0 && (f.n_sync == 0 || f.sync_left), "dsh_run_spec: null sync_left array");
+    s.sync_left.assign(f.sync_left, f.sync_left + f.n_sync); s.sync_len = f.n_sync ? f.sync_len : 0;
     return 0;
 }
 
@@ -1380,6 +1382,19 @@ int dsh_op_chain_save_tail(void* hip_stream, const float* x, const int32_t* lens
     if (lens_host)
         for (int r = 0; r < R; ++r) DSH_REQUIRE(lens_host[r] >= L && lens_host[r] <= T, "chain_save_tail: a row length outside overlap_len .. frames");
     return dsh::launch_chain_save_tail(x, lens_dev, slot_idx_dev, S, R, T, L, C, tails, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+// synchronised window batches: the host copies are validated here (check_window_sync), the kernel reads the device copies
+int dsh_op_window_sync(void* hip_stream, float* x, int32_t B, int32_t frames, int32_t channels, const int32_t* left_host, const int32_t* left_dev,
+                       const int32_t* lens_host, const int32_t* lens_dev, int32_t L, int32_t c_lo, int32_t c_hi) {
+    API_BEGIN
+    DSH_REQUIRE(x && B > 0 && frames > 0 && channels > 0, "window_sync: invalid argument");
+    DSH_REQUIRE(left_host && left_dev, "window_sync: the left neighbours need their host and their device copy");
+    DSH_REQUIRE((lens_host == nullptr) == (lens_dev == nullptr), "window_sync: per-row lengths need their host and their device copy");
+    std::string err;
+    if (dsh::check_window_sync(left_host, lens_host, B, frames, L, err)) { dsh::set_last_error(err); return -1; }
+    return dsh::launch_window_sync(x, B, frames, channels, left_dev, lens_dev, L, c_lo, c_hi, reinterpret_cast<hipStream_t>(hip_stream));
     API_END
 }
 

@@ -346,5 +346,13 @@ int launch_region_mask(const int* frames, int nf, const int* cols, int nc, int B
 int launch_chain_handoff(const float* tails, int S, const int* slot_idx, int R, int T, int L, int C, float* gt, uint8_t* mask, hipStream_t s);
 // ... and tails[slot_idx[r]] <- the last L valid frames of x [R, T, C] (lens nullable: every row has T).  slot_idx / lens: device arrays.
 int launch_chain_save_tail(const float* x, const int* lens, const int* slot_idx, int S, int R, int T, int L, int C, float* tails, hipStream_t s);
+// Synchronised window batches: row b of x [B, frames, channels] shares its first L frames with the last L valid frames of row left[b]
+// (-1: no left neighbour); both copies become a (1 - w) + r w, w = linspace(0, 1, L)[j], in place, on columns [c_lo, c_hi) ((0, 0): all).
+// left_dev / lens_dev (nullable: every row has `frames`): device arrays.  check_window_sync() is the host-side condition of the in-place
+// update (0, or -1 with the reason in err): indices in range and injective, left[b] != b, every used row holds L frames inside its length,
+// a row used at both ends 2 L.
+int check_window_sync(const int32_t* left, const int32_t* lens, int B, int T, int L, std::string& err);
+int launch_window_sync(float* x, int B, int frames, int channels, const int* left_dev, const int* lens_dev, int L, int c_lo, int c_hi,
+                       hipStream_t s);
 
 }  // namespace dsh

@@ -63,6 +63,10 @@ struct SamplerStep { StepKind kind; int level; };
 //                steps' randn_like, the RePaint blend's gt noise, the undo steps, the eta scratch; main chain and gesture-side twin alike),
 //                so rows of one batch may stand at different windows of their chains
 //   trace        (nullable) [steps, n]: the sample after every step
+//   sync_left    synchronised window batches (empty: off, nothing is launched): one entry per batch row, the row that holds
+//                this row's first sync_len frames as its last sync_len valid frames (-1: none).  Behind every DDIM step each chain
+//                reconciles the shared frames of its columns (launch_window_sync); trace rows are taken after it.  Needs init 1 (the
+//                caller's x_T holds ONE noise value per stream frame), eta = 0, no mask; the run is one chain (check_run())
 //   guide        soft constraints: every denoise step of the forward loops is the guided form of its kernel
 //                (sampler_kernels.hip); undo steps, draws and the evaluations are untouched.  Not for the reverse loop.
 // The guidance of a run: target / weight [B, T, C] and vel / acc [C] on the device (each may be null), stated with the shape the caller
@@ -87,6 +91,7 @@ struct RunSpec {
     bool tail_blend = false;
     std::vector<uint64_t> row_keys, row_seeds;
     Guidance guide;
+    std::vector<int32_t> sync_left; int sync_len = 0;
 };
 // what check_run() needs of the conditioned context (lengths: the ragged batch's per-clip frame counts on the host, or null)
 struct RunShape { int batch, frames, channels, gesture_cols, modality; const int32_t* lengths; };
@@ -166,7 +171,10 @@ class Sampler {
     // the device copies of a run's row keys / row seeds with what they hold (host): a caller that keeps its keys pays one upload, not one per run
     uint64_t* row_keys = nullptr; int cap_row_keys = 0; std::vector<uint64_t> row_keys_held;
     uint64_t* row_seeds = nullptr; int cap_row_seeds = 0; std::vector<uint64_t> row_seeds_held;
-    int upload_rows(const std::vector<uint64_t>& host, uint64_t*& dev, int& cap, std::vector<uint64_t>& held);
+    template <typename V> int upload_rows(const std::vector<V>& host, V*& dev, int& cap, std::vector<V>& held);
+    // ... and of a run's sync_left, cached the same way; window_sync(): one chain's reconciliation behind its DDIM step
+    int32_t* sync_left = nullptr; int cap_sync = 0; std::vector<int32_t> sync_left_held;
+    int window_sync(Run& r, const Chain& c);
     int init_x(Run& r);
     // --same_overlap_noisy: the noisy tail x[..., -L:, :] saved after every DDIM step, one slot per spaced level; persists
     // across sample() calls like the reference's self.saved_noisy_tail (the dict the next window receives IS this object)

@@ -187,6 +187,20 @@ int check_run(const RunSpec& s, const RunShape* sh, std::string& err) {
         RUN_REQUIRE(gd.level_scale.empty() || (int64_t)gd.level_scale.size() == (o.kind == 1 ? o.diffusion_steps : o.respacing),
                     "guidance: the level scales need one entry per level of the run (DDIM: respacing, DDPM: diffusion_steps)");
     }
+    // synchronised window batches: whatever would put per-window noise into the shared frames is refused
+    const bool sync = !s.sync_left.empty();
+    if (sync) {
+        RUN_REQUIRE(!reverse, "synchronised windows do not apply to the reverse loop");
+        RUN_REQUIRE(o.kind == 0, "synchronised windows exist for the DDIM loops only (the DDPM loop draws per-window noise at every step)");
+        RUN_REQUIRE(o.eta == 0.f, "synchronised windows are deterministic: eta must be 0");
+        RUN_REQUIRE(!s.masked, "synchronised windows take no mask (the RePaint schedule's undo steps draw per-window noise)");
+        RUN_REQUIRE(!son, "synchronised windows with same_overlap_noisy: nothing is handed from window to window");
+        RUN_REQUIRE(!s.tail_blend, "synchronised windows with the tail blend: there is no mask to blend under");
+        RUN_REQUIRE(s.start_level == 0, "synchronised windows run the whole schedule: no start level");
+        RUN_REQUIRE(philox, "synchronised windows take no noise stack: the caller supplies x_T with one noise value per stream frame");
+        RUN_REQUIRE(s.init == 1, "synchronised windows need init = 1: the caller supplies x_T with one noise value per stream frame");
+        RUN_REQUIRE(s.sync_len >= 1, "synchronised windows need sync_len >= 1");
+    }
     if (!sh) return 0;
     // what depends on the conditioned context
     RUN_REQUIRE(s.x != nullptr, "null sample buffer");
@@ -203,6 +217,10 @@ int check_run(const RunSpec& s, const RunShape* sh, std::string& err) {
                     "row keys were set for a different batch size (or frames*channels is not a multiple of 4)");
         for (int b = 0; sh->lengths && b < sh->batch; ++b)
             RUN_REQUIRE(((int64_t)sh->lengths[b] * sh->channels) % 4 == 0, "row keys on a ragged batch: length * channels must be a multiple of 4 for every clip");
+    }
+    if (sync) {
+        RUN_REQUIRE((int)s.sync_left.size() == sh->batch, "sync_left was built for a different batch size");
+        if (check_window_sync(s.sync_left.data(), sh->lengths, sh->batch, sh->frames, s.sync_len, err)) return -1;
     }
     if (gd.on) {
         RUN_REQUIRE(!(gd.target || gd.weight) || (gd.batch == sh->batch && gd.frames == sh->frames && gd.channels == sh->channels),
@@ -277,6 +295,7 @@ struct Sampler::Run {
     int64_t draw = 0, step_idx = 0; int n_eval = 0;
     bool dpm = false; int last_ddim_level = -1;          // SOLVER_DPM2M; level of the previous executed step if it was a DDIM step, else -1
     const Guidance* guide = nullptr;                     // soft constraints of the run (null: none)
+    const int32_t* sync_d = nullptr; int sync_len = 0;   // synchronised windows: the left neighbours (device; null: off), the overlap
     int64_t next_draw() { return draw++; }               // draw index: advanced once per draw, whatever the regime
 };
 
@@ -307,15 +326,16 @@ Sampler::~Sampler() {
     for (hipEvent_t e : {ev_pE, ev_pC, ev_pG}) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_sub) (void)hipEventDestroy(e);
     for (void* p : pool) (void)hipFree(p);
-    for (void* p : {(void*)row_keys, (void*)row_seeds, (void*)tails, (void*)tail_tmp, (void*)bufs[0].nz_eta, (void*)hist}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)row_keys, (void*)row_seeds, (void*)sync_left, (void*)tails, (void*)tail_tmp, (void*)bufs[0].nz_eta, (void*)hist}) if (p) (void)hipFree(p);
 }
 
 // a run's row keys / row seeds on the device: uploaded (and waited for: `host` is the caller's) unless the buffer holds exactly these values
-int Sampler::upload_rows(const std::vector<uint64_t>& host, uint64_t*& dev, int& cap, std::vector<uint64_t>& held) {
+template <typename V>
+int Sampler::upload_rows(const std::vector<V>& host, V*& dev, int& cap, std::vector<V>& held) {
     if (host == held) return 0;
     held.clear();
     if ((int)host.size() > cap) { if (int e = grow_device_buffer(dev, cap, host.size(), st)) return e; }
-    DSH_HIP_CHECK(hipMemcpyAsync(dev, host.data(), host.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    DSH_HIP_CHECK(hipMemcpyAsync(dev, host.data(), host.size() * sizeof(V), hipMemcpyHostToDevice, st));
     DSH_HIP_CHECK(hipStreamSynchronize(st));
     held = host;
     return 0;
@@ -411,6 +431,10 @@ int Sampler::prepare(Run& r, const RunSpec& s) {
         r.seeds_d = row_seeds;
     }
     r.quads = r.per_row ? (n / B) / 4 : (n + 3) / 4;
+    if (!s.sync_left.empty()) {
+        if (int e = upload_rows(s.sync_left, sync_left, cap_sync, sync_left_held)) return e;
+        r.sync_d = sync_left; r.sync_len = s.sync_len;
+    }
     // --same_overlap_noisy state
     r.blc = (size_t)B * o.overlap_len * channels;
     r.son = o.same_overlap_noisy != 0 && o.kind == 0;
@@ -436,7 +460,8 @@ int Sampler::prepare(Run& r, const RunSpec& s) {
 int Sampler::make_chains(Run& r) {
     ChainBufs& b = bufs[0];
     r.lag = (int)switch_int(SW_DUAL_LAG);
-    const int ns = (prof && prof->on) ? 1 : r.den->sub_count();
+    // (synchronised windows: neighbouring rows must not live in different sub-batch streams, which run free through all steps)
+    const int ns = ((prof && prof->on) || r.sync_d) ? 1 : r.den->sub_count();
     if (!(ns > 1 && r.row_n % 4 == 0)) {
         r.chains.push_back(Chain{nullptr, st, 0, r.B, 0, r.n, r.w_lo, r.w_hi, b.nz1, b.nz_eta, b.t, b.c1, b.c2, b.lvl, &b});
         return 0;
@@ -464,7 +489,9 @@ Sampler::LoopPlan Sampler::plan(const Run& r) const {
     // graphs only where launches dominate (a few thousand token rows), never while profiling events are recorded,
     // and never on the legacy NULL stream (it cannot be captured); sub-batch streams evaluate eagerly
     const bool small = rows <= (size_t)switch_int(SW_GRAPH_ROWS);
-    p.graph = st != nullptr && small && !profiling && !switch_present(SW_NO_GRAPH) && !p.split;
+    // (synchronised windows on a context conditioned as sub-batch streams: one chain whose evaluations fork and join those streams — eager)
+    const bool forked_evals = r.sync_d && r.den->sub_count() > 1;
+    p.graph = st != nullptr && small && !profiling && !switch_present(SW_NO_GRAPH) && !p.split && !forked_evals;
     // (the side-stream head and the two-stream encoder pipeline also pay above the graph range, up to where batches are split over sub-batch
     //  streams: DSH_PIPE_ROWS)
     const bool small_pf = rows <= pipe_rows();
@@ -705,6 +732,12 @@ int Sampler::update(Run& r, const Chain& c, const StepConsts& sc) {
     return launch_undo_step(r.x + c.off, z, sc.undo_a, sc.undo_b, c.cnt, c.s, channels, c.c_lo, c.c_hi);
 }
 
+// Synchronised windows: behind its DDIM step the chain reconciles, on its own columns and stream, the frames neighbouring rows share.
+int Sampler::window_sync(Run& r, const Chain& c) {
+    return launch_window_sync(r.x + c.off, c.nb, r.den->frames(), channels, r.sync_d + c.b0, r.len_d ? r.len_d + c.b0 : nullptr, r.sync_len,
+                              c.c_lo, c.c_hi, c.s);
+}
+
 // x at the schedule's first level.  init 0: draw 0 is x_T.  init 2: x holds x0; draw 0 — the draw x_T would have taken, through noise_for(), so
 // row keys, row seeds and ragged lengths address it alike — is the q_sample noise, and every chain noises its rows and columns in place
 // (coefficients: fp64 sqrt of the table rounded to fp32, like the reference's sqrt_alphas_cumprod tables; they travel in the chain's c1 / c2
@@ -739,11 +772,17 @@ int Sampler::loop(Run& r, const LoopPlan& p) {
         if (sp.kind != STEP_UNDO) { if (int e = evaluate(r, p, sc)) return e; }
         if (r.piped) {
             // each chain advances its own channels on its own stream, the gesture chain behind the expression chain's evaluation of the step
+            const bool sync = r.sync_d && sp.kind == STEP_DDIM;
             if (int e = update(r, r.E, sc)) return e;
+            if (sync) { if (int e = window_sync(r, r.E)) return e; }
             if (sp.kind != STEP_UNDO) { if (int e = gesture_follow(r, p, sc)) return e; }
             if (int e = update(r, r.G, sc)) return e;
+            if (sync) { if (int e = window_sync(r, r.G)) return e; }
         } else {
-            for (const Chain& c : r.chains) { if (int e = update(r, c, sc)) return e; }
+            for (const Chain& c : r.chains) {
+                if (int e = update(r, c, sc)) return e;
+                if (r.sync_d && sp.kind == STEP_DDIM) { if (int e = window_sync(r, c)) return e; }
+            }
         }
         if (r.trace)
             for (const Chain& c : r.chains)

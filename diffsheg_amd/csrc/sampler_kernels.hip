@@ -15,6 +15,8 @@
 // (fp64 table -> fp32 at gather, gaussian_diffusion.py:1514; sqrt taken in fp32 where the
 // reference takes it on an fp32 tensor).
 #include <algorithm>
+#include <string>
+#include <vector>
 
 #include "dsh_common.h"
 #include "dsh_kernels.h"
@@ -616,6 +618,68 @@ int launch_chain_save_tail(const float* x, const int* lens, const int* slot_idx,
     DSH_REQUIRE(x && slot_idx && tails, "chain_save_tail: null pointer");
     const size_t n = (size_t)R * L * C;
     hipLaunchKernelGGL(chain_save_tail_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, lens, slot_idx, S, n, T, L, C, tails);
+    DSH_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- synchronised window batches: every window of a stream is one row of x [B, T, C]; row b's first L frames are the
+// stream frames its left neighbour p = left[b] holds as its last L valid frames.  Both copies take the addBlend cross-fade of the two:
+//   a = x[p, n_p - L + j, c], r = x[b, j, c], w = linspace(0, 1, L)[j]:  both <- a (1 - w) + r w      (n_p = lens[p], or T)
+// The thread that owns (b, j, c) reads both elements and writes both; under the conditions check_window_sync() states no other thread
+// touches either.  The host validates its copy of left / lens; a row whose DEVICE index or length is out of range is skipped all the same,
+// so no address outside x is formed even if the two copies disagree.
+int check_window_sync(const int32_t* left, const int32_t* lens, int B, int T, int L, std::string& err) {
+#define SYNC_REQUIRE(cond, msg) do { if (!(cond)) { err = std::string("window_sync: ") + (msg); return -1; } } while (0)
+    SYNC_REQUIRE(B > 0 && T > 0 && left, "invalid argument");
+    SYNC_REQUIRE(L >= 1, "needs overlap_len >= 1");
+    std::vector<char> is_left(B, 0);
+    for (int b = 0; b < B; ++b) {
+        const int p = left[b];
+        if (p == -1) continue;
+        SYNC_REQUIRE(p >= 0 && p < B, "a left neighbour outside the batch (-1: none)");
+        SYNC_REQUIRE(p != b, "a row is its own left neighbour");
+        SYNC_REQUIRE(!is_left[p], "a row is the left neighbour of two rows");
+        is_left[p] = 1;
+    }
+    for (int b = 0; b < B; ++b) {
+        const bool has_left = left[b] >= 0;
+        if (!has_left && !is_left[b]) continue;
+        const int n = lens ? lens[b] : T;
+        SYNC_REQUIRE(n <= T, "a row length beyond the frame count");
+        SYNC_REQUIRE(n >= L, "a row that shares frames is shorter than overlap_len");
+        SYNC_REQUIRE(!(has_left && is_left[b]) || n >= 2 * (int64_t)L, "a row that shares frames at both ends is shorter than 2 * overlap_len");
+    }
+    return 0;
+#undef SYNC_REQUIRE
+}
+__global__ void window_sync_kernel(float* __restrict__ x, const int* __restrict__ left, const int* __restrict__ lens, int B, size_t n, int T,
+                                   int L, int C, int c_lo, int c_hi) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x, lc = (size_t)L * C;
+    const bool ranged = c_hi > c_lo;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const size_t b = i / lc, in_row = i - b * lc;
+        const int j = (int)(in_row / C), c = (int)(in_row - (size_t)j * C);
+        if (ranged && (c < c_lo || c >= c_hi)) continue;
+        const int p = left[b];
+        if (p < 0 || p >= B || (size_t)p == b) continue;
+        const int np = lens ? lens[p] : T, nb = lens ? lens[b] : T;
+        if (np < L || np > T || nb < L || nb > T) continue;
+        const size_t ia = ((size_t)p * T + (size_t)(np - L + j)) * C + c, ir = (b * T + (size_t)j) * C + c;
+        const float a = x[ia], r = x[ir];
+        const float w = linspace01(L, j);
+        const float v = rn_add(rn_mul(a, rn_sub(1.0f, w)), rn_mul(r, w));
+        x[ia] = v;
+        x[ir] = v;
+    }
+}
+int launch_window_sync(float* x, int B, int frames, int channels, const int* left_dev, const int* lens_dev, int L, int c_lo, int c_hi,
+                       hipStream_t s) {
+    DSH_REQUIRE(x && left_dev && B > 0 && frames > 0 && channels > 0, "window_sync: invalid argument");
+    // (L > frames: no row can share frames — the host check has refused any that would, the kernel skips every row)
+    DSH_REQUIRE(L >= 1, "window_sync: needs overlap_len >= 1");
+    DSH_REQUIRE(c_lo >= 0 && c_hi <= channels, "window_sync: channel range outside [0, channels]");
+    const size_t n = (size_t)B * L * channels;
+    hipLaunchKernelGGL(window_sync_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, left_dev, lens_dev, B, n, frames, L, channels, c_lo, c_hi);
     DSH_HIP_CHECK(hipGetLastError());
     return 0;
 }

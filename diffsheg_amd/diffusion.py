@@ -29,6 +29,8 @@ Differences a caller can observe, all loud:
   * editing an existing motion: ``q_sample`` (gaussian_diffusion.py:417-462) runs on the device, from given noise or the Philox streams;
     ``ddim_sample_loop(..., start_level=K)`` starts at spaced level ``K - 1`` from ``noise=`` (x at that level) or ``x_start=`` (a clean
     motion, noised in the loop with draw 0); ``ddim_reverse_sample`` / ``ddim_reverse_sample_loop`` are the DDIM reverse ODE (:1068-1104);
+  * ``ddim_sample_loop(..., sync_left=, sync_len=)``: synchronised window batches — the rows are windows of long streams and the frames two
+    neighbouring windows share are reconciled behind every denoise step (``dsh_run_spec.sync_left``; DESIGN.md 4.24); off by default;
   * few-step sampling: ``space_timesteps`` also takes the reference's section counts and ``'logsnrK'`` (K timesteps uniform in log-SNR),
     ``SpacedDiffusion`` any non-empty subset of the timesteps (a subset that is no 'ddimK' stride travels as a list,
     ``dsh_run_spec.timesteps``), and ``ddim_sample_loop(..., solver="dpm2m")`` runs the second-order DPM-Solver++(2M) update where a
@@ -377,7 +379,8 @@ class GaussianDiffusion:
 
     def _run(self, kind, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0,
              noise_source=None, seed=None, return_trace=False, row_keys=None, cond_scale=None, tail_blend=False,
-             row_seeds=None, start_level=None, x_start=None, add_blend=None, solver=None, cfg_schedule=None):
+             row_seeds=None, start_level=None, x_start=None, add_blend=None, solver=None, cfg_schedule=None, sync_left=None,
+             sync_len=None):
         if not isinstance(model, UniDiffuser):
             raise TypeError("model must be a diffsheg_amd.model.UniDiffuser (no generic-callable / CPU fallback)")
         model.check_guidance_schedule(cfg_schedule)        # (refused here, before anything is conditioned or set in the native context)
@@ -439,6 +442,24 @@ class GaussianDiffusion:
                     raise NotImplementedError("start_level with tail_blend is not built")
         clip_idx = int(y.get("clip_idx", 0)) if son else 0
         B, T, Cc = (int(s) for s in shape)
+        # synchronised window batches (dsh_run_spec.sync_left): whatever would put per-window noise into the shared frames is refused here,
+        # before anything is conditioned; the geometry (injective, inside every row's length) is check_run's, against the condition's lengths
+        if (sync_left is None) != (sync_len is None):
+            raise ValueError("sync_left and sync_len go together")
+        if sync_left is not None:
+            sync_left = [int(v) for v in sync_left]
+            if kind != 0:
+                raise TypeError("sync_left is an argument of the DDIM loops only (the DDPM loop draws per-window noise at every step)")
+            if eta != 0.0:
+                raise ValueError("synchronised windows are deterministic: eta must be 0")
+            if son or tail_blend or K:
+                raise NotImplementedError("synchronised windows cannot be combined with same_overlap_noisy, tail_blend or start_level")
+            if noise_source is not None or noise is None or x_start is not None:
+                raise ValueError("synchronised windows need noise= (x_T with ONE noise value per stream frame) and take no noise_source / x_start")
+            if "outpainting_mask" in y and bool(y.get("outpainting_mask_any", True)):
+                raise NotImplementedError("synchronised windows take no mask (the RePaint schedule's undo steps draw per-window noise)")
+            if len(sync_left) != B or int(sync_len) < 1:
+                raise ValueError(f"sync_left needs one entry per batch row ({B}) and sync_len >= 1, got {len(sync_left)} entries, sync_len = {sync_len}")
         if cond_fn is not None:
             self._check_guide_shapes(cond_fn, (B, T, Cc))
         if tail_blend and 2 * int(getattr(self.opt, "overlap_len", 0)) > T:
@@ -493,6 +514,7 @@ class GaussianDiffusion:
         spec = _lib.run_spec(timesteps=self._kept if (self._kept and kind == 0) else (), row_keys=row_keys if keyed else (),
                              row_seeds=row_seeds if (keyed and row_seeds is not None) else (), init=init, masked=int(masked), start_level=K,
                              tail_blend=int(tail_blend), solver=int(solver == "dpm2m"), x=x.data_ptr(),
+                             sync_left=sync_left or (), sync_len=int(sync_len or 0),
                              gt=None if gt is None else gt.data_ptr(), mask=mask.data_ptr() if masked else None, **guide_kw)
         n_draws, n_steps = C.c_int64(), C.c_int64()
         _lib.check(lib.dsh_sample_count(C.byref(opts), C.byref(spec), C.byref(n_draws), C.byref(n_steps)), "dsh_sample_count")
@@ -551,7 +573,14 @@ class GaussianDiffusion:
 
         ``cfg_schedule`` (keyword, also on ``p_sample_loop``): a :class:`diffsheg_amd.glue.CFGSchedule` — the guidance weight per model
         timestep and encoder, and the std rescale of the guided eps — for this call, handled as ``cond_scale=`` is: the model's sticky
-        schedule (``UniDiffuser.set_guidance_schedule``) comes back afterwards, also when the call raises."""
+        schedule (``UniDiffuser.set_guidance_schedule``) comes back afterwards, also when the call raises.
+
+        ``sync_left`` / ``sync_len`` (keywords, together; not in the reference): synchronised window batches.  The rows are windows of
+        long streams; row ``b`` shares its first ``sync_len`` frames with the last ``sync_len`` valid frames of row ``sync_left[b]``
+        (``-1``: none), and behind every denoise step both copies take the ``addBlend`` cross-fade of the two
+        (``dsh_run_spec.sync_left``, ``dsh_op_window_sync``).  ``noise=`` must be x_T cut from ONE noise value per stream frame
+        (:meth:`DDPMTrainer.sample_arbitrary_len_synchronised` builds all of it).  Refused with ``eta != 0``, a mask, ``noise_source``,
+        ``start_level`` / ``x_start``, ``tail_blend`` and ``opt.same_overlap_noisy``."""
         if not self._respacing:
             raise NotImplementedError("ddim_sample_loop needs a SpacedDiffusion('ddimK') (trainers use 'ddim25')")
         return self._run(0, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta, **kw)
@@ -633,7 +662,7 @@ class GaussianDiffusion:
             return torch.full((B,), vals[0].item(), dtype=dtype, device=dev)
         return _upload(torch.from_numpy(np.ascontiguousarray(vals)).to(dtype), dev)
 
-    def _draw_noise(self, B: int, T: int, Cc: int, dev, seed: int, row_keys, row_seeds, lens) -> torch.Tensor:
+    def draw_noise(self, B: int, T: int, Cc: int, dev, seed: int, row_keys=None, row_seeds=None, lens=None) -> torch.Tensor:
         """The noise ``q_sample(x_start, t, seed=, row_keys=, row_seeds=, lengths=)`` would draw inside its pass, as a tensor: the values of
         ``dsh_op_philox_randn`` at offset 0, or with ``row_keys`` those of the row ops at draw 0 (which wait for the stream once: they
         upload the keys).  Padded frames of a ragged row are 0."""
@@ -723,7 +752,7 @@ class GaussianDiffusion:
             if seed is None:
                 seed = int(torch.initial_seed()) + GaussianDiffusion._calls
                 GaussianDiffusion._calls += 1
-            nz = self._draw_noise(B, T, Cc, dev, seed, row_keys, row_seeds, lens)
+            nz = self.draw_noise(B, T, Cc, dev, seed, row_keys, row_seeds, lens)
         else:
             nz = noise.to(device=dev, dtype=torch.float32).contiguous()
         a_d = self._row_values(np.sqrt(self.alphas_cumprod), ts, B, dev)

@@ -112,6 +112,46 @@ def ragged_window_plan(chain_frames: Sequence[int], size: int, step: int) -> Lis
     return plan
 
 
+def synchronised_window_plan(stream_frames: Sequence[int], n_poses: int, overlap_len: int) -> dict:
+    """Every window of every stream as one row of ONE batch (synchronised window batches).  Stream ``s`` of
+    ``stream_frames[s]`` frames gets exactly the windows of :func:`window_lengths` (size ``n_poses``, stride ``n_poses - overlap_len``);
+    the rows are stream-major.  Returns ``{"stream": stream of each row, "window": its index in the stream, "left": the row of the previous
+    window of the same stream or -1, "start": its first stream frame, "lengths": its frame count, "frames": the padded frame count of the
+    batch, "ranges": one ``(first row, one past the last row)`` per stream}``.  ``frames`` follows :func:`ragged_window_plan`'s rule.
+    Refuses ``overlap_len < 1`` (windows that share nothing are independent clips: ``generate_batch``) and ``2 * overlap_len > n_poses``
+    (a window would share frames with its two neighbours at once)."""
+    n_poses, L = int(n_poses), int(overlap_len)
+    if L < 1:
+        raise ValueError(f"synchronised windows need overlap_len >= 1, got {L}: windows that share no frame are independent clips (generate_batch)")
+    if 2 * L > n_poses:
+        raise ValueError(f"synchronised windows need 2 * overlap_len <= n_poses, got overlap_len = {L}, n_poses = {n_poses}")
+    if len(stream_frames) == 0 or any(int(n) < 1 for n in stream_frames):
+        raise ValueError(f"synchronised windows need at least one stream, of at least one frame each, got {list(stream_frames)}")
+    step = n_poses - L
+    plan = {"stream": [], "window": [], "left": [], "start": [], "lengths": [], "ranges": []}
+    for s, n in enumerate(stream_frames):
+        first = len(plan["stream"])
+        for i, w in enumerate(window_lengths(int(n), n_poses, step)):
+            plan["left"].append(len(plan["stream"]) - 1 if i > 0 else -1)
+            plan["stream"].append(s); plan["window"].append(i); plan["start"].append(i * step); plan["lengths"].append(w)
+        plan["ranges"].append((first, len(plan["stream"])))
+    pad = max(plan["lengths"])
+    if len(plan["stream"]) >= MIN_PAD_BATCH and pad < MIN_PAD_FRAMES:
+        pad = MIN_PAD_FRAMES
+    plan["frames"] = pad
+    return plan
+
+
+def stitch_synchronised(windows, plan: dict, overlap_len: int) -> List[torch.Tensor]:
+    """The streams of a synchronised window batch ``windows [rows, T, ...]``: the chain's keep rule — the first
+    ``length - overlap_len`` frames of every window but a stream's last, and the whole last window.  One tensor per stream."""
+    L = int(overlap_len)
+    out = []
+    for lo, hi in plan["ranges"]:
+        out.append(torch.cat([windows[r, :plan["lengths"][r] - (L if r < hi - 1 else 0)] for r in range(lo, hi)], 0))
+    return out
+
+
 class DDPMTrainer:
     """Sampling half of DDPMTrainer_show / DDPMTrainer_beat (ddpm_show_trainer.py:40-90)."""
 
@@ -595,6 +635,104 @@ class DDPMTrainer:
                     tails[b] = out[r, n - L:n]
                 pieces[b].append(out[r, :n] if ii == n_win[b] - 1 else out[r, :step])
         return [torch.cat(p, 0) for p in pieces]
+
+    # ---- long streams as ONE batch: synchronised windows ---------------------
+    def sample_arbitrary_len_synchronised(self, audio_emb: torch.Tensor, p_id: torch.Tensor, add_cond: Dict[str, torch.Tensor], seed: int,
+                                          row_keys: Optional[Sequence[int]] = None, lengths: Optional[Sequence[int]] = None,
+                                          cond_scale=None, cfg_schedule=None, guidance=None, modality="both", expression=None,
+                                          pose_rep: str = "axis_angle", return_windows: bool = False):
+        """Long streams without a window chain: every window of every stream (:func:`synchronised_window_plan`) is one row of ONE batch,
+        all rows run the plain sampling loop together, and behind every denoise step the ``overlap_len`` frames two neighbouring windows
+        share are reconciled by the ``addBlend`` cross-fade (``ddim_sample_loop(sync_left=)``), so both carry the same values there.
+        Nothing is sequential across windows and there is no seam to repair; the result is NOT the reference's out-painting chain.
+
+        ``audio_emb`` / ``add_cond`` are streams ``[S, N, ...]``; with ``lengths`` stream ``s`` is their first ``lengths[s]`` frames and
+        the result is a list of ``[lengths[s], C]`` tensors (as in :meth:`sample_arbitrary_len`), else ``[S, N, C]``.  ``p_id`` and
+        ``cond_scale`` (a float, or one per stream) are per stream.  Noise: every stream frame owns ONE value — ``z [S, N, C]`` from the
+        per-row Philox streams (key ``seed``, counter high words ``row_keys``, default the stream numbers; draw 0) is cut into windows like
+        the audio, so windows that overlap start from the same noise, and a stream's noise depends on ``(seed, its key, its length)``
+        alone; ``N * C`` and every ``lengths[s] * C`` must be multiples of 4.  ``guidance`` (a :class:`diffsheg_amd.glue.MotionGuidance`):
+        ``target`` / ``weight`` are stream-long ``[S, N, C]`` and cut like the audio, in both forms; the stencils are per window.
+        ``cfg_schedule``, ``modality`` / ``expression`` (the track ``[S, N, E]``, ``[N, E]`` or with ``lengths`` a list) and ``pose_rep``
+        as in the chain; :meth:`set_sampling` (steps, spacing, ``solver="dpm2m"``) applies.  ``return_windows=True``: also the raw
+        ``[rows, T, C]`` batch (the sampler's representation) and the plan.
+
+        Refused before any device call: ``opt.ddim`` off (the DDPM loop draws per-window noise at every step), ``opt.fix_very_first``
+        (a mask), ``opt.same_overlap_noisy``; there is no ``noise_source``: a stack of per-window draws is what the scheme excludes."""
+        opt = self.opt
+        if not getattr(opt, "ddim", True):
+            raise NotImplementedError("synchronised windows need the DDIM loop (opt.ddim): the DDPM loop draws per-window noise at every step")
+        if bool(getattr(opt, "fix_very_first", False)):
+            raise NotImplementedError("synchronised windows take no mask: opt.fix_very_first out-paints the first window")
+        if bool(getattr(opt, "same_overlap_noisy", False)):
+            raise NotImplementedError("synchronised windows with opt.same_overlap_noisy: nothing is handed from window to window")
+        euler = self._euler_requested(pose_rep)
+        n_poses, L, C = int(opt.n_poses), int(opt.overlap_len), int(opt.net_dim_pose)
+        S, N = int(audio_emb.shape[0]), int(audio_emb.shape[1])
+        if lengths is not None:
+            lengths = [int(v) for v in lengths]
+            if len(lengths) != S or any(n < 1 or n > N for n in lengths):
+                raise ValueError(f"lengths needs one frame count in 1 .. {N} per stream ({S}), got {lengths}")
+        plan = synchronised_window_plan(lengths if lengths is not None else [N] * S, n_poses, L)
+        if (N * C) % 4 or any((n * C) % 4 for n in (lengths or [])):
+            raise ValueError("synchronised windows: frames * channels of every stream must be a multiple of 4 (per-row Philox streams)")
+        keys = list(range(S)) if row_keys is None else [int(k) for k in row_keys]
+        if len(keys) != S:
+            raise ValueError(f"row_keys needs one key per stream ({S}), got {len(keys)}")
+        gs = normalize_guidance_scale(cond_scale)              # None / one value / one per stream
+        if gs is not None and len(gs) not in (1, S):
+            raise ValueError(f"cond_scale needs one value or one per stream ({S}), got {len(gs)}")
+        expression = self._chain_track(modality, expression, S, N, lengths)
+        if guidance is not None:
+            for name in ("target", "weight"):
+                v = getattr(guidance, name)
+                if v is not None and (v.dim() != 3 or int(v.shape[0]) != S or int(v.shape[1]) != N):
+                    raise ValueError(f"guidance: {name} must be stream-long [S, N, C] = [{S}, {N}, C], got {tuple(v.shape)}")
+        T, rows, step = plan["frames"], len(plan["stream"]), n_poses - L
+
+        def cut(t: torch.Tensor) -> torch.Tensor:
+            """``[S, N, ...]`` -> the plan's rows ``[rows, T, ...]``, zero behind every row's length."""
+            if lengths is None:                          # equal streams: window i of every stream at once, then stream-major
+                wins = [torch.cat([w, w.new_zeros((S, T - w.shape[1]) + tuple(w.shape[2:]))], 1) if w.shape[1] < T else w
+                        for w in get_windows(t, n_poses, step)]
+                return torch.stack(wins, 1).reshape((rows, T) + tuple(t.shape[2:])).contiguous()
+            dev = t.device
+            frame = torch.tensor(plan["start"], device=dev)[:, None] + torch.arange(T, device=dev)[None]
+            valid = torch.arange(T, device=dev)[None] < torch.tensor(plan["lengths"], device=dev)[:, None]
+            w = t[torch.tensor(plan["stream"], device=dev)[:, None], frame.clamp_(max=N - 1)]
+            return w * valid.reshape(valid.shape + (1,) * (t.dim() - 2)).to(w.dtype)
+
+        audio_emb = audio_emb.to(self.device)
+        a = cut(audio_emb)
+        cnd = {k: cut(v.to(self.device)) for k, v in (add_cond or {}).items()}
+        pid = p_id if p_id.dim() == 2 else p_id.unsqueeze(0)
+        if pid.shape[0] == 1:
+            pid = pid.expand(S, -1)
+        pid = pid[plan["stream"]]
+        dd = self.diffusion_ddim_val
+        z = dd.draw_noise(S, N, C, self.device, int(seed), keys, None, lengths)
+        # (seed: the loop's own draws are unused at eta = 0; given so that the call does not advance the default-seed counter)
+        kw = {"noise": cut(z), "sync_left": plan["left"], "sync_len": L, "seed": int(seed)}
+        ragged = any(n != T for n in plan["lengths"])
+        if ragged:
+            kw["lengths"] = plan["lengths"]
+        if gs is not None:
+            kw["cond_scale"] = gs[0] if len(gs) == 1 else [gs[s] for s in plan["stream"]]
+        if cfg_schedule is not None:
+            kw["cfg_schedule"] = cfg_schedule
+        if expression is not None or modality not in (None, "both", 0):
+            kw["modality"] = modality
+            kw["expression"] = cut(expression.to(self.device)) if expression is not None else None
+        if guidance is not None:
+            kw["guidance"] = guidance if guidance.target is None else guidance.with_terms(cut(guidance.target), cut(guidance.weight))
+        windows = self.generate_batch(a, pid, C, cnd, {}, **kw)
+        streams = stitch_synchronised(windows, plan, L)
+        if lengths is not None:
+            out = [self._to_euler(s) for s in streams] if euler else streams
+        else:
+            out = torch.stack(streams, 0)
+            out = self._to_euler(out) if euler else out
+        return (out, windows, plan) if return_windows else out
 
     # ---- a speech signal in, motion out -------------------------------------------------------
     def sample_custom_audio(self, wave16k, p_id: torch.Tensor, frontend, **kw):

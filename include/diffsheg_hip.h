@@ -231,6 +231,19 @@ typedef struct dsh_run_spec {
     const float* guide_vel;    /* device [C] or NULL                                                                             */
     const float* guide_acc;    /* device [C] or NULL                                                                             */
     const float* guide_scale;  /* host, n_guide_scale entries, indexed by spaced level; a level with scale 0 runs unguided      */
+    /* Synchronised window batches: every window of a long stream is one row of the batch, all rows run the plain DDIM loop together, and
+     * behind every denoise step the L = sync_len frames row b shares with row sync_left[b] — the first L frames of b, the last L valid
+     * frames of sync_left[b] — are reconciled in place by dsh_op_window_sync's arithmetic (one launch per step and chain, on the chain's own
+     * columns; rows of `trace` are taken after it).  The caller supplies x_T (init = 1) with ONE noise value per stream frame, so both
+     * copies of a shared frame stand at the same x_t at every level and the cross-fade of the updated values equals one step with the
+     * cross-faded prediction.  n_sync = 0: off, no launch and no kernel argument is added anywhere.  The run is one chain (no sub-batch
+     * streams); the two-encoder pipeline stays on.  -1 before any state changes: on n_sync other than the batch; on what
+     * dsh_op_window_sync refuses, checked against the condition's lengths; with the DDPM loop, eta != 0, a mask, same_overlap_noisy,
+     * tail_blend, a start level, the reverse loop, a noise stack (DSH_NOISE_STACK) and init != 1 — each would put per-window noise
+     * into the shared frames. */
+    const int32_t* sync_left;  /* host, n_sync entries: the row that holds this row's first sync_len frames as its tail; -1: none   */
+    int32_t n_sync;            /* 0: off; else the batch                                                                         */
+    int32_t sync_len;          /* the overlap L >= 1                                                                             */
 } dsh_run_spec;
 #define DSH_GUIDE_XT 0
 #define DSH_GUIDE_X0 1
@@ -626,6 +639,17 @@ int dsh_op_chain_handoff(void* hip_stream, const float* tails, int32_t S, const 
 /* tails[slot_idx[r]] = x[r, n_r - L : n_r] for x [R, T, C], n_r = lens[r] (host and device copy, both or neither; L <= n_r <= T) or T. */
 int dsh_op_chain_save_tail(void* hip_stream, const float* x, const int32_t* lens_host, const int32_t* lens_dev, const int32_t* slot_idx_host,
                            const int32_t* slot_idx_dev, int32_t R, int32_t T, int32_t L, int32_t C, float* tails, int32_t S);
+/* Synchronised window batches (dsh_run_spec.sync_left): x [B, frames, channels] in place.  For every row b with p = left[b] >= 0, every
+ * j < L and every column c of [c_lo, c_hi) ((0, 0): all; columns outside keep their bits), with n_p = lens[p] (or frames without lengths):
+ *   a = x[p, n_p - L + j, c], r = x[b, j, c], w = linspace(0, 1, L)[j] (fp32, torch.linspace's values):
+ *   x[p, n_p - L + j, c] = x[b, j, c] = a * (1 - w) + r * w          (every product and sum rounded on its own)
+ * One launch, plain loads and stores, no atomics, asynchronous on hip_stream.  left and lens are given twice, as the host copies the call
+ * validates and the device copies the kernel reads (the kernel skips a row whose device index or length is out of range).
+ * -1 before any launch on: L < 1; left[b] outside -1 .. B - 1; left[b] = b; a row named as left neighbour twice; a row
+ * that shares frames with a length below L or above frames; a row that shares frames at both ends with a length below 2 L; a column
+ * range outside [0, channels]. */
+int dsh_op_window_sync(void* hip_stream, float* x, int32_t B, int32_t frames, int32_t channels, const int32_t* left_host,
+                       const int32_t* left_dev, const int32_t* lens_host, const int32_t* lens_dev, int32_t L, int32_t c_lo, int32_t c_hi);
 /* dsh_op_ddim_step with every field of the step: x0_out (nullable) receives pred_xstart; coef_eps multiplies the re-derived eps and
  * sigma * noise1 is added when noise1 != NULL (the eta branch; eta = 0: coef_eps = sqrt_1m_ab_prev, noise1 = NULL); tail_in / tail_out
  * [B, overlap_len, channels] (nullable) are the saved noisy tail of --same_overlap_noisy.  Refusals of dsh_op_ddim_step, and tail_in
