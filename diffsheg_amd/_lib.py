@@ -146,6 +146,7 @@ SYMBOLS = {
     "dsh_op_split_pack_weight": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
     "dsh_debug_last_tl_variant": (C.c_int32, []),
     "dsh_debug_launch_counts": (C.c_int32, [C.POINTER(C.c_int64), C.c_int32, C.c_int32]),
+    "dsh_debug_loop_regime": (C.c_int, [_P, _P]),
     "dsh_op_tl_linear": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     "dsh_op_tl2_ffn": (C.c_int, [_P] * 12 + [C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32]),
     "dsh_op_tl_aud_tail": (C.c_int, [_P] * 16 + [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32]),

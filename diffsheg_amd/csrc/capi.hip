@@ -590,7 +590,34 @@ int32_t dsh_debug_launch_counts(int64_t* out, int32_t cap, int32_t reset) {
     return dsh::LC_COUNT;
 }
 
-// ---- op-level entries: test / bench helpers over ROW-MAJOR operands.  Each builds the kernels' operands in per-call scratch, caches nothing
+// dsh_loop_facts -> dsh::LoopFacts -> loop_regime() -> dsh_loop_regime: the caller's struct_size bytes of either struct, the rest 0
+int dsh_debug_loop_regime(const dsh_loop_facts* facts, dsh_loop_regime* regime) {
+    API_BEGIN
+    DSH_REQUIRE(facts && regime, "null argument");
+    DSH_REQUIRE(facts->struct_size >= sizeof(uint32_t) && facts->struct_size <= sizeof(dsh_loop_facts), "dsh_loop_facts: struct_size is larger than this library knows");
+    DSH_REQUIRE(regime->struct_size >= sizeof(uint32_t) && regime->struct_size <= sizeof(dsh_loop_regime), "dsh_loop_regime: struct_size is larger than this library knows");
+    dsh_loop_facts c{};
+    std::memcpy(&c, facts, facts->struct_size);
+    DSH_REQUIRE(c.batch > 0 && c.frames > 0 && c.channels > 0 && (c.kind == 0 || c.kind == 1), "dsh_loop_facts: empty batch or unknown loop kind");
+    dsh::LoopFacts f;
+    f.kind = c.kind; f.batch = c.batch; f.frames = c.frames; f.channels = c.channels; f.gesture_cols = c.gesture_cols; f.modality = c.modality;
+    f.evals = c.evals; f.distinct = c.distinct_levels;
+    f.trace = c.trace != 0; f.same_overlap_noisy = c.same_overlap_noisy != 0; f.sync = c.sync != 0; f.profiling = c.profiling != 0;
+    f.cur_split = c.cur_split;
+    f.graph_rows = (size_t)c.graph_rows; f.no_graph = c.no_graph != 0;
+    f.level_cache = c.level_cache; f.level_prefetch = c.level_prefetch; f.pipe = c.pipe;
+    f.pipe_rows_context = (size_t)c.pipe_rows_context; f.pipe_rows_sampler = (size_t)c.pipe_rows_sampler;
+    const dsh::LoopRegime r = dsh::loop_regime(f);
+    dsh_loop_regime o{};
+    o.struct_size = regime->struct_size;
+    o.unsplit = r.unsplit; o.chains = r.chains; o.forked_evals = r.forked_evals; o.graph = r.graph; o.cache = (int32_t)r.cache;
+    o.inline_ok = r.inline_ok; o.pipe = r.pipe;
+    std::memcpy(regime, &o, regime->struct_size);
+    return 0;
+    API_END
+}
+
+// ---- op-level entries: test / bench helpers over ROW-MAJOR operands. Each builds the kernels' operands in per-call scratch, caches nothing
 // (a cache keyed on a pointer would alias when the caller's allocator reuses the address) and frees the scratch after a stream sync.
 namespace {
 struct OpScratch {

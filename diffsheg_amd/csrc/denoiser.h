@@ -175,12 +175,14 @@ class DenoiserContext {
     virtual int pipe_end() = 0;
     virtual int import_expr_into_twin(hipStream_t s) = 0;
     virtual int level_wait_stream(int level, hipStream_t s) = 0;
-    //   loop_begin(kind): called by the sampler before it asks for sub-batches.  A DDIM or DDPM loop (kind 0 / 1) of a batch below pipe_rows token rows
-    //                (default 64 499: where the sub-batch split would use two streams) is conditioned as ONE batch — the two encoder chains
-    //                on two streams beat two sub-batch streams (313 clips: 131.7 k -> 148.8 k frames/s) — and the next set_condition of the
-    //                same shape skips the split too; plain evaluations (dsh_eval) keep the sub-batch streams.
-    virtual int loop_begin(int kind) = 0;
+    //   loop_begin(unsplit): called by the sampler before it asks for sub-batches, with the decision loop_regime() took (loop_regime.h); the
+    //                context decides nothing here.  unsplit: the batch is conditioned as ONE batch for this loop (re-conditioned if it is split
+    //                now) and marked so until loop_end(), and the next set_condition of the same shape skips the split too (sticky shape).
+    //                Else the sticky shape is forgotten and the split stays.  Plain evaluations (dsh_eval) keep the sub-batch streams.
+    //   unsplit_rows(): DSH_PIPE_ROWS as this context read it when it was created — the row limit of `unsplit`, handed to loop_regime() as a fact
+    virtual int loop_begin(bool unsplit) = 0;
     virtual int loop_end() = 0;
+    virtual size_t unsplit_rows() const = 0;
     virtual double issued_flops_per_eval() const = 0;   // MFMA GEMM flops actually launched for the current (B,T)
     virtual size_t weight_bytes() const = 0;
     virtual int debug_copy(const std::string& what, float* out) = 0;   // as DenoiserInstance's, every sub-batch instance its own clips' rows

@@ -2,6 +2,7 @@
 #include <algorithm>
 
 #include "denoiser.h"
+#include "loop_regime.h"
 
 namespace dsh {
 
@@ -25,7 +26,7 @@ class Context final : public DenoiserContext {
         if (c.fp32_storage()) { min_rows_ = 4096; rows_per_stream_ = 2900; }
         if (const long rs = switch_positive(SW_DUAL_ROWS)) rows_per_stream_ = (size_t)rs;
         if (const long mr = switch_positive(SW_DUAL_MIN_ROWS)) min_rows_ = (size_t)mr;
-        pipe_rows_ = pipe_rows_context();
+        unsplit_rows_ = pipe_rows_context();
     }
     ~Context() override {
         (void)hipDeviceSynchronize();                        // side streams may still be running a level ahead of an aborted loop
@@ -235,15 +236,15 @@ class Context final : public DenoiserContext {
         DSH_REQUIRE(tw_.inst, "import_expr: no pipelined run in progress");
         return tw_.inst->import_expr(*inst_[0], s);
     }
-    int loop_begin(int kind) override {
+    int loop_begin(bool unsplit) override {
         if (cond_.B <= 0) return 0;
-        const bool unsplit = (kind == 0 || kind == 1) && pipe_possible() && (size_t)cond_.B * cond_.T <= pipe_rows_;
         if (!unsplit) { loop_.sticky_B = loop_.sticky_T = 0; return 0; }
         loop_.sticky_B = cond_.B; loop_.sticky_T = cond_.T; loop_.unsplit = true;
         if (split_now_ != 1) return apply_condition(1);
         return 0;
     }
     int loop_end() override { loop_.unsplit = false; return 0; }
+    size_t unsplit_rows() const override { return unsplit_rows_; }
     int gesture_channels() const override { return cfg_.single_transformer ? -1 : cfg_.dim_pose; }
     int level_wait_stream(int level, hipStream_t s) override {
         DSH_REQUIRE(level >= 0 && level < (int)pf_.lvl_ev.size(), "level_wait_stream: level out of range");
@@ -408,19 +409,20 @@ class Context final : public DenoiserContext {
         hipStream_t stream = nullptr; hipEvent_t ev = nullptr;
         bool cond_ok = false, busy = false;                // conditioned like inst_[0] for the current condition; may still be reading it on its stream
     } tw_;
-    size_t pipe_rows_ = 0;                                 // DDIM loops below this many token rows: one batch, two encoder streams (loop_begin)
+    size_t unsplit_rows_ = 0;                              // DSH_PIPE_ROWS as read when this context was created: a fact of loop_regime(), not used here
     // what loop_begin() / loop_end() leave behind, and the one reader of each: the split of a new condition, the split of the next evaluation
     struct LoopState {
         int sticky_B = 0, sticky_T = 0;                    // shape whose last loop ran unsplit: set_condition conditions it as one batch
         bool unsplit = false;                              // a sampling loop is running this batch unsplit on purpose (its evaluations must not re-split it)
     } loop_;
-    int split_of_condition(int B, int T) const { return (B == loop_.sticky_B && T == loop_.sticky_T && pipe_possible()) ? 1 : want_split(B, T); }
-    int split_of_eval() const { return (loop_.unsplit && split_now_ == 1) ? 1 : want_split(cond_.B, cond_.T); }
-    bool pipe_possible() const {
-        // (the pipelined loop restores every head from the slots a side-stream prefetch run fills: all three switches must be on)
-        return pipe_switches_on() && !cfg_.single_transformer && !(prof_ && prof_->on);
+    // (the one piece of the loop policy evaluated here, for the sticky shape: at set_condition time no run exists to decide it)
+    int split_of_condition(int B, int T) const {
+        const bool sticky = B == loop_.sticky_B && T == loop_.sticky_T;
+        return (sticky && pipe_available(switch_int(SW_PIPE), switch_int(SW_LEVEL_PREFETCH), switch_int(SW_LEVEL_CACHE), gesture_channels(), prof_ && prof_->on))
+                   ? 1 : want_split(B, T);
     }
-    int nsplit_ = 1, split_now_ = 1, lag_ = 0;             // (nsplit_, lag_, pipe_rows_: from the switches, in the constructor)
+    int split_of_eval() const { return (loop_.unsplit && split_now_ == 1) ? 1 : want_split(cond_.B, cond_.T); }
+    int nsplit_ = 1, split_now_ = 1, lag_ = 0;             // (nsplit_, lag_, unsplit_rows_: from the switches, in the constructor)
     size_t min_rows_ = 12288;                              // batches below this many token rows run on one stream
     size_t rows_per_stream_ = 21500;                       // streams = rows / this (at least two, at most DSH_DUAL): three from 64 500 rows
 };

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "denoiser.h"
+#include "loop_regime.h"
 
 namespace dsh {
 
@@ -134,22 +135,22 @@ class Sampler {
         int64_t* t; float *c1, *c2; int64_t* lvl;      // its rows of the per-step scalars, its level word
         ChainBufs* own;                     // the set these come from: holds its evaluation graphs
     };
-    // (sampler.hip) one run()'s arguments, constants and chains; its regime, decided before the first step; what one step's launches share
-    struct Run; struct LoopPlan; struct StepConsts;
-    // run() = argument checks, then these in order; finish() joins the chains whatever loop() returned
+    // (sampler.hip) one run()'s arguments, constants, regime (loop_regime.h) and chains; what one step's launches share
+    struct Run; struct StepConsts;
+    // run() = argument checks, the schedule, the regime from loop_facts(), then these in order; finish() joins the chains whatever loop() returned
+    LoopFacts loop_facts(Run& r, const RunSpec& s) const;
     int ensure(size_t n, int B, bool want_hist);
     int prepare(Run& r, const RunSpec& s);
     int make_chains(Run& r);
-    LoopPlan plan(const Run& r) const;
-    int loop(Run& r, const LoopPlan& p);
+    int loop(Run& r);
     int finish(Run& r, int rc);
     // loop() = x_T, setup(), then per step: evaluate(), and update() of every chain (pipelined: E, gesture_follow(), G)
-    int setup(Run& r, const LoopPlan& p);
+    int setup(Run& r);
     StepConsts step_consts(Run& r, const SamplerStep& sp);
     int noise_for(const Run& r, int64_t idx, const Chain& c, float* scratch, const float** out);
-    int evaluate(Run& r, const LoopPlan& p, const StepConsts& sc);
+    int evaluate(Run& r, const StepConsts& sc);
     int eval_step(const Run& r, const Chain& c, int n_eval, bool use_graph, int mode);
-    int gesture_follow(Run& r, const LoopPlan& p, const StepConsts& sc);
+    int gesture_follow(Run& r, const StepConsts& sc);
     int update(Run& r, const Chain& c, const StepConsts& sc);
     int ddim_update(Run& r, const Chain& c, const StepConsts& sc);
     int ddpm_update(Run& r, const Chain& c, const StepConsts& sc);

@@ -276,7 +276,6 @@ int sampler_count(const RunSpec& s, int64_t* draws, int64_t* steps) {
 }
 
 // One run()'s arguments, what is derived from them once, its chains and the loop's running state; the parts of run() share it by reference.
-enum LevelCache { CACHE_NONE, CACHE_INLINE, CACHE_PREFETCH, CACHE_SUBS };
 struct Sampler::Run {
     DenoiserContext* den; const SamplerOpts& o; float* x; int init; const float* gt; const uint8_t* mask; bool masked;
     const float* noise_stack; float* trace; bool tail_blend;
@@ -284,11 +283,13 @@ struct Sampler::Run {
     int mod = 0, gcols = 0, w_lo = 0, w_hi = 0;          // modality, gesture columns, the active column window (0, 0: all)
     const int* len_d = nullptr;                          // ragged batch: per-clip frame counts (device)
     std::vector<SamplerStep> steps;
+    std::vector<int> order;                              // DDIM: the schedule's levels in first-use order
+    LoopRegime want;                                     // the regime (loop_regime.h), decided before anything is queued
     bool per_row = false; const uint64_t* seeds_d = nullptr; uint64_t quads = 0;      // Philox addressing
     bool son = false, tail_gt = false; size_t blc = 0;   // --same_overlap_noisy state
     std::vector<Chain> chains;                           // the whole batch, or its sub-batches
     Chain E{}, G{};                                      // pipelined loop (piped): chains[0] on the expression columns, the twin on the gesture columns
-    LevelCache cache = CACHE_NONE; bool piped = false;   // what setup() obtained of the plan
+    LevelCache cache = CACHE_NONE; bool piped = false;   // what setup() obtained of the regime
     std::vector<char> level_seen;
     std::vector<int64_t> tv; int lag = 0;                // level -> model timestep; DSH_DUAL_LAG
     size_t pf_next = 0;                                  // order[0 .. pf_next) have been handed to the prefetch stream
@@ -297,16 +298,6 @@ struct Sampler::Run {
     const Guidance* guide = nullptr;                     // soft constraints of the run (null: none)
     const int32_t* sync_d = nullptr; int sync_len = 0;   // synchronised windows: the left neighbours (device; null: off), the overlap
     int64_t next_draw() { return draw++; }               // draw index: advanced once per draw, whatever the regime
-};
-
-// The regime of a run, decided from its arguments before anything is queued.  It states what the loop asks of the denoiser; setup()
-// asks, and falls back where the denoiser refuses (prefetch -> inline cache -> none; pipeline -> one chain).
-struct Sampler::LoopPlan {
-    bool split = false, graph = false;   // sub-batch streams; evaluations replayed from hipGraphs
-    LevelCache cache = CACHE_NONE;       // timestep cache: inline, filled ahead by the side-stream prefetch, or inline per sub-batch
-    bool inline_ok = false;              // ... a refused prefetch falls back to the inline cache (the schedule revisits levels)
-    bool pipe = false;                   // the two encoders' chains on two streams
-    std::vector<int> order;              // DDIM: the schedule's levels in first-use order
 };
 
 // what the launches of one step share
@@ -455,14 +446,13 @@ int Sampler::prepare(Run& r, const RunSpec& s) {
     return 0;
 }
 
-// The chains of a run.  Large batches: every sub-batch runs the WHOLE loop on its own stream, forked from the context stream here and
+// The chains the regime names.  More than one: every sub-batch runs the WHOLE loop on its own stream, forked from the context stream here and
 // joined into it in finish(); else the whole batch on the context stream.
 int Sampler::make_chains(Run& r) {
     ChainBufs& b = bufs[0];
     r.lag = (int)switch_int(SW_DUAL_LAG);
-    // (synchronised windows: neighbouring rows must not live in different sub-batch streams, which run free through all steps)
-    const int ns = ((prof && prof->on) || r.sync_d) ? 1 : r.den->sub_count();
-    if (!(ns > 1 && r.row_n % 4 == 0)) {
+    const int ns = r.want.chains;
+    if (ns <= 1) {
         r.chains.push_back(Chain{nullptr, st, 0, r.B, 0, r.n, r.w_lo, r.w_hi, b.nz1, b.nz_eta, b.t, b.c1, b.c2, b.lvl, &b});
         return 0;
     }
@@ -480,57 +470,39 @@ int Sampler::make_chains(Run& r) {
     return 0;
 }
 
-Sampler::LoopPlan Sampler::plan(const Run& r) const {
+// What the regime of a run depends on (loop_regime.h), and the schedule's first-use order beside it.  The only place of the sampling path
+// that reads the regime switches: DSH_GRAPH_ROWS and the sampler's DSH_PIPE_ROWS as the process latched them, the others afresh.
+LoopFacts Sampler::loop_facts(Run& r, const RunSpec& s) const {
     const SamplerOpts& o = r.o;
-    LoopPlan p;
-    const bool profiling = prof && prof->on;
-    const size_t rows = (size_t)r.B * r.den->frames();
-    p.split = r.chains.size() > 1;
-    // graphs only where launches dominate (a few thousand token rows), never while profiling events are recorded,
-    // and never on the legacy NULL stream (it cannot be captured); sub-batch streams evaluate eagerly
-    const bool small = rows <= (size_t)switch_int(SW_GRAPH_ROWS);
-    // (synchronised windows on a context conditioned as sub-batch streams: one chain whose evaluations fork and join those streams — eager)
-    const bool forked_evals = r.sync_d && r.den->sub_count() > 1;
-    p.graph = st != nullptr && small && !profiling && !switch_present(SW_NO_GRAPH) && !p.split && !forked_evals;
-    // (the side-stream head and the two-stream encoder pipeline also pay above the graph range, up to where batches are split over sub-batch
-    //  streams: DSH_PIPE_ROWS)
-    const bool small_pf = rows <= pipe_rows();
-    // timestep cache (denoiser.h): worth it when the schedule revisits levels (out-painting jump schedule: 63 evaluations
-    // over 16 levels).  DSH_LEVEL_CACHE=0 disables it.
-    const bool cache_on = switch_int(SW_LEVEL_CACHE) != 0;
-    int evals = 0, distinct = 0;
+    LoopFacts f;
+    f.kind = o.kind;
+    f.batch = r.B; f.frames = r.den->frames(); f.channels = channels; f.gesture_cols = r.gcols; f.modality = r.mod;
     if (o.kind == 0) {
         std::vector<int> cnt(o.respacing, 0);
-        for (const SamplerStep& sp : r.steps) if (sp.kind != STEP_UNDO) { ++evals; if (cnt[sp.level]++ == 0) { ++distinct; p.order.push_back(sp.level); } }
+        for (const SamplerStep& sp : r.steps) if (sp.kind != STEP_UNDO) { ++f.evals; if (cnt[sp.level]++ == 0) { ++f.distinct; r.order.push_back(sp.level); } }
     }
-    const int gch = r.gcols;
-    if ((small || small_pf) && o.kind == 0 && !p.split) {
-        // side-stream prefetch of every scheduled level (also pays for schedules without repeats); else the inline cache
-        p.inline_ok = evals > distinct && cache_on;
-        if (cache_on && st != nullptr && !profiling && !p.order.empty()) p.cache = CACHE_PREFETCH;
-        else if (p.inline_ok) p.cache = CACHE_INLINE;
-        // the two encoders' chains on two streams: every evaluation restores its head from the slots the prefetch run fills (mode 2), no
-        // per-step trace of the whole sample, no saved noisy tails (both need all channels of a step at once)
-        p.pipe = r.mod == 0 && p.cache == CACHE_PREFETCH && !r.trace && !r.son && bufs[1].nz1 && r.n <= cap_n2 && gch > 0 && gch < channels;
-    }
-    // DDPM loops have no timestep cache (every level is visited once, 1000 of them): each chain computes its own head
-    if (r.mod == 0 && !p.pipe && o.kind == 1 && !p.split && small_pf && !r.trace && bufs[1].nz1 && r.n <= cap_n2) p.pipe = gch > 0 && gch < channels;
-    // sub-batch streams: the inline timestep cache for schedules that revisit levels, else plain evaluations
-    if (p.split && o.kind == 0 && evals > distinct && cache_on) p.cache = CACHE_SUBS;
-    return p;
+    f.trace = r.trace != nullptr; f.same_overlap_noisy = o.same_overlap_noisy != 0; f.sync = !s.sync_left.empty(); f.profiling = prof && prof->on;
+    f.cur_split = r.den->sub_count();
+    f.graph_rows = (size_t)switch_int(SW_GRAPH_ROWS); f.no_graph = switch_present(SW_NO_GRAPH);
+    f.level_cache = switch_int(SW_LEVEL_CACHE); f.level_prefetch = switch_int(SW_LEVEL_PREFETCH); f.pipe = switch_int(SW_PIPE);
+    f.pipe_rows_context = r.den->unsplit_rows(); f.pipe_rows_sampler = pipe_rows();
+    return f;
 }
 
-// What the plan calls for, asked of the denoiser in this order: graphs of the previous run dropped, the prefetch run begun (one level is
-// queued now, the others one evaluation ahead of their first use: the host never runs far in front of the main chain, and the main chain
-// never waits for the host to finish queueing 25 levels) or the cache slots prepared, the gesture-side twin started.
-int Sampler::setup(Run& r, const LoopPlan& p) {
+// Exactly what the regime names, asked of the denoiser in this order: graphs of the previous run dropped, the prefetch run begun (one level
+// is queued now, the others one evaluation ahead of their first use: the host never runs far in front of the main chain, and the main chain
+// never waits for the host to finish queueing 25 levels) or the cache slots prepared, the gesture-side twin started.  The fallbacks are for
+// what can fail only at run time — an allocation, the slot cap of level_cache_prepare, a failed clone: prefetch -> inline cache if
+// inline_ok -> none; pipeline -> one chain.
+int Sampler::setup(Run& r) {
     const SamplerOpts& o = r.o;
+    const LoopRegime& p = r.want;
     drop_graph();
     r.cache = p.cache;
     if (r.cache == CACHE_PREFETCH) {
         r.tv.resize(o.respacing);
         for (int k = 0; k < o.respacing; ++k) r.tv[k] = (int64_t)tb.tmap[k];
-        if (r.den->level_prefetch(r.tv.data(), o.respacing, p.order.data(), 1, 1) == 0) r.pf_next = 1;
+        if (r.den->level_prefetch(r.tv.data(), o.respacing, r.order.data(), 1, 1) == 0) r.pf_next = 1;
         else r.cache = p.inline_ok ? CACHE_INLINE : CACHE_NONE;
     }
     if (r.cache == CACHE_INLINE && r.den->level_cache_prepare(o.respacing) != 0) r.cache = CACHE_NONE;
@@ -539,7 +511,9 @@ int Sampler::setup(Run& r, const LoopPlan& p) {
     // (a DDIM twin restores its head from the slots of the prefetch run)
     ChainBufs& g = bufs[1];
     r.G = Chain{nullptr, nullptr, 0, r.B, 0, r.n, 0, r.gcols, g.nz1, g.nz_eta, g.t, g.c1, g.c2, g.lvl, &g};
-    if (p.pipe && (o.kind == 1 || r.cache == CACHE_PREFETCH) && r.den->pipe_begin(&r.G.inst, &r.G.s) == 0) {
+    // (the gesture chain's scratch: ensure() sized it, the regime's own bound on n restates that size)
+    const bool scratch_ok = g.nz1 && r.n <= cap_n2;
+    if (p.pipe && scratch_ok && (o.kind == 1 || r.cache == CACHE_PREFETCH) && r.den->pipe_begin(&r.G.inst, &r.G.s) == 0) {
         r.piped = true;
         r.E = r.chains[0]; r.E.c_lo = r.gcols; r.E.c_hi = channels;
         for (hipEvent_t* e : {&ev_pE, &ev_pC, &ev_pG}) if (!*e) DSH_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -608,8 +582,9 @@ Sampler::StepConsts Sampler::step_consts(Run& r, const SamplerStep& sp) {
 }
 
 // the evaluation of a step, on every chain of the run (pipelined: the expression encoder's; gesture_follow() queues the twin's)
-int Sampler::evaluate(Run& r, const LoopPlan& p, const StepConsts& sc) {
+int Sampler::evaluate(Run& r, const StepConsts& sc) {
     const int k = sc.k;
+    const LoopRegime& p = r.want; const std::vector<int>& order = r.order;
     const bool seen = r.cache != CACHE_NONE && r.level_seen[k];
     const int mode = r.cache == CACHE_NONE ? EVAL_PLAIN : (r.cache == CACHE_PREFETCH || seen) ? EVAL_RESTORE : EVAL_SAVE;
     // (pipelined: E_k overwrites the expression estimate the twin copied behind E_{k-1})
@@ -621,15 +596,15 @@ int Sampler::evaluate(Run& r, const LoopPlan& p, const StepConsts& sc) {
         if (r.cache == CACHE_PREFETCH && !seen) {
             // first use: this level was queued one evaluation ago (or in setup()); queue the next new one now
             size_t pos = 0;
-            while (pos < p.order.size() && p.order[pos] != k) ++pos;
-            const size_t want = std::min(p.order.size(), pos + 2);
+            while (pos < order.size() && order[pos] != k) ++pos;
+            const size_t want = std::min(order.size(), pos + 2);
             if (want > r.pf_next) {
-                if (int e = r.den->level_prefetch(r.tv.data(), r.o.respacing, p.order.data() + r.pf_next, (int)(want - r.pf_next), 0)) return e;
+                if (int e = r.den->level_prefetch(r.tv.data(), r.o.respacing, order.data() + r.pf_next, (int)(want - r.pf_next), 0)) return e;
                 r.pf_next = want;
             }
             if (int e = r.den->level_wait(k)) return e;
         }
-        if (p.split) {
+        if (p.split()) {
             // every sub-batch on its own stream; at the very first evaluation sub-batch i + 1 starts a few launches behind
             // sub-batch i (so that the kernel sequences are out of phase from the start); afterwards the streams run free
             if (first_eval && i > 0) DSH_HIP_CHECK(hipStreamWaitEvent(c.s, ev_sub[2 * (i - 1)], 0));
@@ -637,7 +612,7 @@ int Sampler::evaluate(Run& r, const LoopPlan& p, const StepConsts& sc) {
             c.inst->t_uniform = r.den->t_uniform;
         }
         if (int e = eval_step(r, c, sc.eval_idx, p.graph, mode)) return e;
-        if (p.split) c.inst->notify_after_launches(nullptr, 0);
+        if (p.split()) c.inst->notify_after_launches(nullptr, 0);
     }
     if (r.cache != CACHE_NONE) r.level_seen[k] = 1;
     return 0;
@@ -646,7 +621,7 @@ int Sampler::evaluate(Run& r, const LoopPlan& p, const StepConsts& sc) {
 // Pipelined loop, between the two chains' updates of a step: E_k has advanced the expression channels on the context stream; G_k on the
 // twin's takes E_k's x0 estimate and evaluates the gesture encoder at the same level (DDIM: head restored from the timestep cache, once the
 // prefetch run has filled the level; DDPM: computed).  The caller then advances the gesture channels.
-int Sampler::gesture_follow(Run& r, const LoopPlan& p, const StepConsts& sc) {
+int Sampler::gesture_follow(Run& r, const StepConsts& sc) {
     const Chain& G = r.G;
     const int twin_mode = r.o.kind == 0 ? EVAL_RESTORE : EVAL_PLAIN;
     DSH_HIP_CHECK(hipEventRecord(ev_pE, st));
@@ -655,7 +630,7 @@ int Sampler::gesture_follow(Run& r, const LoopPlan& p, const StepConsts& sc) {
     DSH_HIP_CHECK(hipEventRecord(ev_pC, G.s));
     if (int e = launch_fill_step(G.t, G.c1, G.c2, G.lvl, sc.t, sc.c1, sc.c2, (int64_t)sc.k, G.nb, G.s)) return e;
     if (twin_mode == EVAL_RESTORE) { if (int e = r.den->level_wait_stream(sc.k, G.s)) return e; }
-    return eval_step(r, G, sc.eval_idx, p.graph, twin_mode);
+    return eval_step(r, G, sc.eval_idx, r.want.graph, twin_mode);
 }
 
 int Sampler::ddim_update(Run& r, const Chain& c, const StepConsts& sc) {
@@ -764,18 +739,18 @@ int Sampler::init_x(Run& r) {
 
 // Everything between the fork of make_chains() and the joins of finish(): any error leaves through `return`, and run() passes the result
 // to finish() unconditionally.
-int Sampler::loop(Run& r, const LoopPlan& p) {
+int Sampler::loop(Run& r) {
     if (int e = init_x(r)) return e;
-    if (int e = setup(r, p)) return e;
+    if (int e = setup(r)) return e;
     for (const SamplerStep& sp : r.steps) {
         const StepConsts sc = step_consts(r, sp);
-        if (sp.kind != STEP_UNDO) { if (int e = evaluate(r, p, sc)) return e; }
+        if (sp.kind != STEP_UNDO) { if (int e = evaluate(r, sc)) return e; }
         if (r.piped) {
             // each chain advances its own channels on its own stream, the gesture chain behind the expression chain's evaluation of the step
             const bool sync = r.sync_d && sp.kind == STEP_DDIM;
             if (int e = update(r, r.E, sc)) return e;
             if (sync) { if (int e = window_sync(r, r.E)) return e; }
-            if (sp.kind != STEP_UNDO) { if (int e = gesture_follow(r, p, sc)) return e; }
+            if (sp.kind != STEP_UNDO) { if (int e = gesture_follow(r, sc)) return e; }
             if (int e = update(r, r.G, sc)) return e;
             if (sync) { if (int e = window_sync(r, r.G)) return e; }
         } else {
@@ -842,17 +817,18 @@ int Sampler::run(DenoiserContext* den, const RunSpec& s) {
     r.w_lo = mod == 1 ? gcols : 0; r.w_hi = mod == 0 ? 0 : (mod == 1 ? channels : gcols);      // (0, 0: all columns)
     r.guide = s.guide.on ? &s.guide : nullptr;
     r.len_d = den->lengths_dev();           // ragged batch (set_condition_ragged): per-clip frame counts of the padded batch, owned by the context
+    // the regime, decided once, before anything changes in the context or on the device
+    r.want = loop_regime(loop_facts(r, s));
     // loop_begin() marks the batch as deliberately unsplit; the mark is taken back on EVERY way out of this function (an argument error or a
     // failed launch below must not leave the context answering later evaluations as if a loop were still running)
     struct LoopScope { DenoiserContext* d; ~LoopScope() { (void)d->loop_end(); } } loop_scope{den};
-    if (int e = den->loop_begin(o.kind)) return e;          // (may re-condition a mid-size batch as one batch: the two encoder chains replace the sub-batch streams)
+    if (int e = den->loop_begin(r.want.unsplit)) return e;  // (may re-condition a mid-size batch as one batch: the two encoder chains replace the sub-batch streams)
     den->t_uniform = emb_dedup_enabled();   // every evaluation of a sampling loop runs the whole batch at ONE timestep (launch_fill_step)
     r.n = (size_t)B * den->frames() * channels; r.row_n = r.n / B;
     if (int e = prepare(r, s)) return e;
     if (int e = make_chains(r)) return e;
-    const LoopPlan p = plan(r);
     // from the fork to the joins: loop() reports an error by returning, finish() joins the chains into the context stream whatever it returned
-    const int rc = loop(r, p);
+    const int rc = loop(r);
     return finish(r, rc);
 }
 

@@ -516,6 +516,31 @@ int32_t dsh_debug_last_tl_variant(void);
  *   21 those of them that took the 128 x 128 instantiation. */
 #define DSH_LAUNCH_COUNT_ENTRIES 22
 int32_t dsh_debug_launch_counts(int64_t* out, int32_t cap, int32_t reset);
+/* Test helper: the regime a sampling loop would take, from plain values — no context, no GPU call, no environment read.  dsh_sample_run
+ * decides through the same function (csrc/loop_regime.h), once per run, from the facts it gathers itself.  Both structs start with
+ * struct_size like dsh_run_spec: fields are only ever appended, unknown ones read as 0, a larger struct than the library knows is refused.
+ *   facts   kind 0 DDIM (the reverse loop included) / 1 DDPM; batch, frames, channels; gesture_cols (-1: a single transformer); modality;
+ *           evals / distinct_levels of the schedule (DDIM); trace, same_overlap_noisy, sync (synchronised windows), profiling as 0 / 1;
+ *           cur_split = sub-batch streams the context is conditioned on before the loop; the switches as their readers see them:
+ *           no_graph (DSH_NO_GRAPH present), level_cache, level_prefetch, pipe, graph_rows, and DSH_PIPE_ROWS twice — as the context
+ *           read it when it was created and as the process latched it for the sampler
+ *   regime  unsplit (the batch is conditioned as one batch), chains (1, or n sub-batch streams), forked_evals (one chain whose evaluations
+ *           fork over the sub-batch streams), graph, cache (0 none, 1 inline, 2 side-stream prefetch, 3 inline per sub-batch stream),
+ *           inline_ok (a failed prefetch falls back to the inline cache), pipe (the two encoders on two streams) */
+typedef struct dsh_loop_facts {
+    uint32_t struct_size;
+    int32_t kind, batch, frames, channels, gesture_cols, modality;
+    int32_t evals, distinct_levels;
+    int32_t trace, same_overlap_noisy, sync, profiling;
+    int32_t cur_split;
+    int32_t no_graph, level_cache, level_prefetch, pipe;
+    uint64_t graph_rows, pipe_rows_context, pipe_rows_sampler;
+} dsh_loop_facts;
+typedef struct dsh_loop_regime {
+    uint32_t struct_size;
+    int32_t unsplit, chains, forked_evals, graph, cache, inline_ok, pipe;
+} dsh_loop_regime;
+int dsh_debug_loop_regime(const dsh_loop_facts* facts, dsh_loop_regime* regime);
 int dsh_op_tl_linear(void* hip_stream, int32_t pro, const void* X, const void* W, const float* bias, const float* R,
                      float* Cf, void* Ct, int32_t M, int32_t N, int32_t act, const float* gamma, const float* beta,
                      const float* film, int32_t frames, int32_t nb, int32_t K);

@@ -1,7 +1,7 @@
 """Evaluations and sampling loops on BOTH sides of every kernel-dispatch boundary, on a real MI355X.
 
 The denoiser picks a kernel family per launch from the shape of the call (row counts, frames per window, clips per batch); the limits
-live in denoiser.hip, denoiser_context.hip, sampler.hip and the launchers.  This file mirrors those rules in plain Python (`expected_launches`), asks the
+live in denoiser.hip, denoiser_context.hip, loop_regime.h and the launchers.  This file mirrors those rules in plain Python (`expected_launches`; regime_rules.py), asks the
 library which families actually ran (`dsh_debug_launch_counts`, host-side counters) and compares every case with the CPU oracle.  A
 limit that moves in the C++ without moving here fails the counter assertion of the cases that straddle it, instead of silently
 testing one side twice.
@@ -35,6 +35,7 @@ from diffsheg_amd.config import get_config  # noqa: E402
 from diffsheg_amd.synthetic import make_inputs  # noqa: E402
 from diffsheg_amd.trainer import DDPMTrainer, sampler_namespace  # noqa: E402
 from oracle import denoiser_ref, sampler_ref  # noqa: E402
+from regime_rules import GRAPH_ROWS, PIPE_ROWS, SPLIT, _loop_flags, n_streams  # noqa: E402,F401  (the stream split and the loop regime, restated there)
 from test_gpu_eval import BF16_MAX, BF16_RMS, FP32_ATOL  # noqa: E402  (the evaluation gates, unchanged)
 from util import WEIGHT_SEED, gpu_model, gpu_single_model, rel_err, sample_clips, sub_batches, synthetic_sd  # noqa: E402
 
@@ -51,11 +52,8 @@ FFN_FUSE_ROWS = 128 * 64                                               # tl2.hip
 HL_STY_ROWS, HL_F3_ROWS = 128 * 256, 128 * 128                         # denoiser.hip kTlRoles: hl_rows
 ROLL_MIN_BLOCKS = 128                                                  # tl2.hip launch_tl2_linear: N split below this many token blocks
 ATTN_MFMA_FRAMES = 96                                                  # denoiser.hip run_encoder
-SPLIT = {"bf16": (12288, 21500), "fp32": (4096, 2900)}                 # denoiser_context.hip: (min rows, rows per stream)
-SPLIT["bf16x3"] = SPLIT["fp32"]                                        # precision "bf16x3" is fp32 storage: the same stream rules
 F32_PRECS = ("fp32", "bf16x3")
 F32_FEWROW = 512                                                       # denoiser.hip f32_min_rows / gemm.hip ks_rows
-GRAPH_ROWS, PIPE_ROWS = 4096, 64499                                    # sampler.hip
 
 SPLIT_TILE_BLOCKS = 256                                                # gemm_f32_split.hip launch_gemm_f32_split: 128 x 128 tiles where they fill 256 CUs
 
@@ -68,15 +66,6 @@ def _ceil_div(a, b):
 
 def _round_up(a, b):
     return _ceil_div(a, b) * b
-
-
-def n_streams(prec, B, T):
-    """DenoiserContext: want_split (default DSH_DUAL = 3, profiler off)."""
-    rows = B * T
-    min_rows, per_stream = SPLIT[prec]
-    if rows < min_rows:
-        return 1
-    return min(3, max(2, rows // per_stream), B)
 
 
 def split_tile_128(M, N):
@@ -648,17 +637,6 @@ def _philox_rows(seed, keys, n_row):
 def _picks(B):
     """Around every possible stream split, and the batch ends (test_gpu_sharded.py)."""
     return sorted({b for b in (0, 1, B // 3 - 1, B // 3, B // 3 + 1, B // 2 - 1, B // 2, 2 * B // 3 - 1, 2 * B // 3 + 1, B - 2, B - 1) if 0 <= b < B})
-
-
-def _loop_flags(B, T, prec, kind, pipe_env, ddim=True, trace=False):
-    """(graphs, pipeline, sub-batch streams) of a plain loop (sampler.hip, DenoiserContext::loop_begin)."""
-    rows = B * T
-    pipe_ok = kind != "single" and pipe_env
-    unsplit = pipe_ok and rows <= PIPE_ROWS
-    streams = 1 if unsplit else n_streams(prec, B, T)
-    pipe = unsplit and not trace
-    graph = rows <= GRAPH_ROWS
-    return int(graph), int(pipe), streams
 
 
 LOOP_CASES = [
