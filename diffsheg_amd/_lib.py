@@ -139,6 +139,8 @@ SYMBOLS = {
     "dsh_inv_standardize": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     "dsh_axis_angle_to_euler": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32]),
     "dsh_euler_to_axis_angle": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32]),
+    "dsh_fk_positions": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32]),
+    "dsh_fk_positions_vjp": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32]),
     "dsh_op_gemm": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "dsh_op_gemm_ex": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P] + [C.c_int32] * 11),
     "dsh_op_gemm_f32_pro": (C.c_int, [_P, C.c_int32] + [_P, C.c_int32, C.c_int32] * 4 + [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),

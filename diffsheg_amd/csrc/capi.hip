@@ -1233,6 +1233,53 @@ int dsh_euler_to_axis_angle(void* hip_stream, const float* x, int64_t ld_x, int6
     API_END
 }
 
+// what the two forward-kinematics calls share, checked before any launch
+static int check_fk_args(const char* what, const float* x, int64_t ld_x, int64_t rows, int32_t kind, const float* mean, const float* stdv,
+                         int32_t joints, int32_t channels, const int32_t* parents, const float* offsets, const int32_t* channel_joint,
+                         const float* rest_rot, const int32_t* joint_channel, const int32_t* lengths_dev, int32_t frames) {
+    DSH_REQUIRE(joints >= 1 && joints <= DSH_FK_MAX_JOINTS, std::string(what) + ": joints outside 1 .. 256");
+    DSH_REQUIRE(channels >= 1 && channels <= joints, std::string(what) + ": channel triples outside 1 .. joints");
+    DSH_REQUIRE(kind == 0 || kind == 1, std::string(what) + ": input kind must be 0 (axis-angle) or 1 (Euler)");
+    DSH_REQUIRE(x && mean && stdv && rows >= 0, std::string(what) + ": null input or statistics pointer, or negative row count");
+    DSH_REQUIRE(parents && offsets && channel_joint && rest_rot && joint_channel, std::string(what) + ": null skeleton pointer");
+    DSH_REQUIRE(ld_x >= 3 * (int64_t)channels, std::string(what) + ": input stride below 3 * channels");
+    DSH_REQUIRE(!lengths_dev || (frames >= 1 && rows % frames == 0), std::string(what) + ": lengths need frames >= 1 dividing rows");
+    return 0;
+}
+
+int dsh_fk_positions(void* hip_stream, const float* x, int64_t ld_x, int64_t rows, int32_t kind, const float* mean, const float* stdv,
+                     int32_t joints, int32_t channels, const int32_t* parents, const float* offsets, const int32_t* channel_joint,
+                     const float* rest_rot, const int32_t* joint_channel, float* pos, int64_t ld_pos, float* wrot, int64_t ld_wrot,
+                     const int32_t* lengths_dev, int32_t frames) {
+    API_BEGIN
+    if (int e = check_fk_args("dsh_fk_positions", x, ld_x, rows, kind, mean, stdv, joints, channels, parents, offsets, channel_joint, rest_rot,
+                              joint_channel, lengths_dev, frames)) return e;
+    DSH_REQUIRE(pos, "dsh_fk_positions: null position output");
+    DSH_REQUIRE(ld_pos >= 3 * (int64_t)joints, "dsh_fk_positions: position stride below 3 * joints");
+    DSH_REQUIRE(!wrot || ld_wrot >= 9 * (int64_t)joints, "dsh_fk_positions: rotation stride below 9 * joints");
+    const dsh::FkSkeleton sk{joints, channels, parents, offsets, channel_joint, rest_rot, joint_channel};
+    return dsh::launch_fk_positions(x, ld_x, rows, kind, mean, stdv, sk, pos, ld_pos, wrot, ld_wrot, lengths_dev, frames,
+                                    reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
+int dsh_fk_positions_vjp(void* hip_stream, const float* x, int64_t ld_x, int64_t rows, int32_t kind, const float* mean, const float* stdv,
+                         int32_t joints, int32_t channels, const int32_t* parents, const float* offsets, const int32_t* channel_joint,
+                         const float* rest_rot, const int32_t* joint_channel, const float* g, int64_t ld_g, float* dx, int64_t ld_dx,
+                         const int32_t* lengths_dev, int32_t frames) {
+    API_BEGIN
+    if (int e = check_fk_args("dsh_fk_positions_vjp", x, ld_x, rows, kind, mean, stdv, joints, channels, parents, offsets, channel_joint,
+                              rest_rot, joint_channel, lengths_dev, frames)) return e;
+    DSH_REQUIRE(kind == 0, "dsh_fk_positions_vjp: the gradient is built for axis-angle input only");
+    DSH_REQUIRE(g && dx, "dsh_fk_positions_vjp: null gradient pointer");
+    DSH_REQUIRE(ld_g >= 3 * (int64_t)joints, "dsh_fk_positions_vjp: gradient stride below 3 * joints");
+    DSH_REQUIRE(ld_dx >= 3 * (int64_t)channels, "dsh_fk_positions_vjp: output stride below 3 * channels");
+    const dsh::FkSkeleton sk{joints, channels, parents, offsets, channel_joint, rest_rot, joint_channel};
+    return dsh::launch_fk_positions_vjp(x, ld_x, rows, mean, stdv, sk, g, ld_g, dx, ld_dx, lengths_dev, frames,
+                                        reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
 // what the three step ops share, checked, as the eta = 0 step without saved noisy tails; each entry adds what is its own
 static int step_args(const std::string& what, dsh::DdimStepArgs& a, float* x, const float* eps, float* x0_out, const float* gt, const uint8_t* mask,
                      const float* noise2, int32_t B, int32_t frames, int32_t channels, float c1, float c2, float sqrt_ab_prev, float sqrt_1m_ab_prev,

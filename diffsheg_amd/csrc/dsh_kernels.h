@@ -224,6 +224,21 @@ int launch_axis_angle_to_euler(const float* x, long long ldx, long long rows, in
 int launch_euler_to_axis_angle(const float* x, long long ldx, long long rows, int joints, const float* mean_e, const float* std_e,
                                const float* mean_aa, const float* std_aa, float* y, long long ldy, const int* lengths, int frames,
                                hipStream_t s);
+// Forward kinematics (kinematics.hip): world positions [rows, 3 J] (and world rotations [rows, 9 J], nullable) of a rotation-only skeleton
+// from the standardised channel triples, and the vector-Jacobian product of the positions (axis-angle input).  All skeleton arrays are
+// device buffers; strides in elements; lengths / frames as above.  kind 0: axis-angle, 1: Euler 'XYZ' degrees.
+struct FkSkeleton {
+    int J, Jc;                     // joints, driven joints (channel triples)
+    const int* parents;            // [J], parents[0] = -1, parents[j] < j
+    const float* offsets;          // [J, 3]
+    const int* channel_joint;      // [Jc]: the joint channel triple i drives
+    const float* rest_rot;         // [J, 3, 3]: the rotation of a joint no channel drives
+    const int* joint_channel;      // [J]: the inverse map, -1 where undriven
+};
+int launch_fk_positions(const float* x, long long ldx, long long rows, int kind, const float* mean, const float* stdv, const FkSkeleton& sk,
+                        float* pos, long long ld_pos, float* wrot, long long ld_wrot, const int* lengths, int frames, hipStream_t s);
+int launch_fk_positions_vjp(const float* x, long long ldx, long long rows, const float* mean, const float* stdv, const FkSkeleton& sk,
+                            const float* g, long long ldg, float* dx, long long lddx, const int* lengths, int frames, hipStream_t s);
 
 // linear ("efficient") self-attention core: y = softmax_ch(Q) (softmax_time(K)^T V)   (transformer.py:122-128)
 // lens (device int32, nullable): ragged batch — clip b has lens[b % lmod] valid frames out of `frames` (the padded stride); frames beyond

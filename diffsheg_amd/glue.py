@@ -10,6 +10,8 @@
   channels (standardised axis-angle, ``--axis_angle``) to the standardised Euler 'XYZ' degrees the reference saves, scores and writes
   to BVH (ddpm_beat_trainer.py:1044-1060, datasets/rotation_converter.py), and the dataset's opposite direction
   (datasets/beat.py:376-401) for frames a caller holds as Euler / BVH poses; HIP kernels, output stays on the device.
+* :func:`joint_positions` with :class:`Skeleton`, and :func:`position_metrics` — world-space joint positions of the gesture channels by
+  forward kinematics on a caller-given skeleton, differentiable with respect to the motion (two HIP kernels), and MPJPE / PCK on them.
 
 * :class:`CFGSchedule` — the classifier-free guidance weight per model timestep and per encoder, and the std rescale of the guided
   prediction (``UniDiffuser.set_guidance_schedule``, the loops' ``cfg_schedule=``); host-side tables.
@@ -174,6 +176,276 @@ def euler_to_axis_angle(pose: torch.Tensor, stats: PoseStats, *, split_pos: Opti
     ``euler_angles_to_axis_angle(..., 'XYZ')`` -> normalise with the axis-angle statistics: what ``motions``, ``head`` and ``tail`` of
     the samplers expect from frames held as Euler / BVH poses.  ``split_pos`` / ``lengths`` as for :func:`axis_angle_to_euler`."""
     return _rotation_call("euler_to_axis_angle", pose, stats, split_pos, lengths, False)
+
+
+# ---- forward kinematics: joint positions of the gesture channels and their gradient (DESIGN.md §4.25) --------------------------------------
+def _euler_deg_to_matrix(deg: np.ndarray) -> np.ndarray:
+    """[..., 3] Euler degrees -> [..., 3, 3] = Rx(X) Ry(Y) Rz(Z), float64: the composition :func:`euler_to_axis_angle` uses."""
+    a, b, c = np.moveaxis(np.radians(np.asarray(deg, dtype=np.float64)), -1, 0)
+    sa, ca, sb, cb, sc, cc = np.sin(a), np.cos(a), np.sin(b), np.cos(b), np.sin(c), np.cos(c)
+    m = [cb * cc, -cb * sc, sb,
+         sa * sb * cc + ca * sc, ca * cc - sa * sb * sc, -sa * cb,
+         sa * sc - ca * sb * cc, ca * sb * sc + sa * cc, ca * cb]
+    return np.stack(m, -1).reshape(a.shape + (3, 3))
+
+
+class Skeleton:
+    """A rotation-only skeleton for :func:`joint_positions`, as arrays on the host (the dataset's template file is an input, not a
+    committed asset):
+
+    * ``parents`` int ``[J]``: ``parents[0] == -1``, ``parents[j] < j`` otherwise (topological order);
+    * ``offsets`` ``[J, 3]``: a BVH's ``OFFSET`` lines; end sites are ordinary joints without channels;
+    * ``channel_joint`` int ``[Jc]``: distinct joint indices, channel triple ``i`` of the motion drives joint ``channel_joint[i]``;
+    * ``rest`` (optional) ``[J, 3]`` Euler degrees of the joints no channel drives (the template frame), folded here in float64 into
+      ``rest_rot [J, 3, 3]`` by ``Rx Ry Rz``; identity by default.  The entries of driven joints are not used.
+
+    ``ValueError``: a bad parent order, duplicate or out-of-range ``channel_joint``, non-finite offsets or rest angles, ``J < 1``,
+    ``Jc < 1`` or ``J > 256``.  ``joint_channel`` is the inverse map (``-1`` where undriven), ``bone_length`` the sum of ``|offsets[j]|``
+    over all joints (the root's offset, its position, included).  :meth:`to` uploads the five arrays once per device."""
+
+    MAX_JOINTS = 256
+
+    def __init__(self, parents, offsets, channel_joint, rest=None, names=None):
+        par = np.asarray(parents)
+        off = np.asarray(offsets, dtype=np.float64)
+        cj = np.asarray(channel_joint)
+        if par.ndim != 1 or par.size < 1 or par.size > Skeleton.MAX_JOINTS:
+            raise ValueError(f"Skeleton: parents must be [J] with 1 <= J <= {Skeleton.MAX_JOINTS}, got shape {par.shape}")
+        if par.dtype.kind not in "iu" or cj.dtype.kind not in "iu":
+            raise ValueError("Skeleton: parents and channel_joint must be non-empty integer arrays")
+        par, cj = par.astype(np.int64), cj.astype(np.int64)
+        J = int(par.size)
+        if par[0] != -1 or any(par[j] < 0 or par[j] >= j for j in range(1, J)):
+            raise ValueError("Skeleton: parents[0] must be -1 and 0 <= parents[j] < j otherwise (topological order)")
+        if off.shape != (J, 3) or not np.isfinite(off).all():
+            raise ValueError(f"Skeleton: offsets must be finite [J, 3] = [{J}, 3], got shape {off.shape}")
+        if cj.ndim != 1 or cj.size < 1:
+            raise ValueError("Skeleton: channel_joint must be [Jc] with Jc >= 1")
+        if cj.min() < 0 or cj.max() >= J or len(set(cj.tolist())) != cj.size:
+            raise ValueError(f"Skeleton: channel_joint must hold distinct joint indices in 0 .. {J - 1}")
+        rest_rot = np.broadcast_to(np.eye(3), (J, 3, 3)).copy()
+        if rest is not None:
+            r = np.asarray(rest, dtype=np.float64)
+            if r.shape != (J, 3) or not np.isfinite(r).all():
+                raise ValueError(f"Skeleton: rest must be finite [J, 3] = [{J}, 3] Euler degrees, got shape {r.shape}")
+            rest_rot = _euler_deg_to_matrix(r)
+        if names is not None and len(names) != J:
+            raise ValueError(f"Skeleton: {len(names)} names for {J} joints")
+        self.joints, self.channels = J, int(cj.size)
+        self.parents, self.offsets, self.channel_joint, self.rest_rot = par.astype(np.int32), off, cj.astype(np.int32), rest_rot
+        self.joint_channel = np.full(J, -1, dtype=np.int32)
+        self.joint_channel[cj] = np.arange(cj.size, dtype=np.int32)
+        self.names = list(names) if names is not None else None
+        self.bone_length = float(np.sqrt((off ** 2).sum(-1)).sum())
+        self._dev: Dict[torch.device, Dict[str, torch.Tensor]] = {}
+
+    def to(self, device) -> Dict[str, torch.Tensor]:
+        """The device buffers of the two C calls (int32 / fp32), uploaded on first use and kept."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._dev:
+            self._dev[device] = {
+                "parents": torch.from_numpy(self.parents).to(device),
+                "offsets": torch.from_numpy(self.offsets.astype(np.float32)).contiguous().to(device),
+                "channel_joint": torch.from_numpy(self.channel_joint).to(device),
+                "rest_rot": torch.from_numpy(self.rest_rot.astype(np.float32)).contiguous().to(device),
+                "joint_channel": torch.from_numpy(self.joint_channel).to(device)}
+        return self._dev[device]
+
+    @classmethod
+    def from_bvh_header(cls, text: str, joints=None, rest=None) -> "Skeleton":
+        """Parse the ``HIERARCHY`` block of a BVH file (everything up to ``MOTION``, if present) into a skeleton; a reader, not a
+        writer.  ``ROOT`` / ``JOINT`` blocks and ``End Site`` blocks become joints in file order (an end site is named
+        ``"<parent>_end"``).  ``joints``: the driven joints in channel order, as names or indices; by default every joint whose
+        ``CHANNELS`` line names a rotation.  ``rest`` as for the constructor."""
+        tok = text.replace("{", " { ").replace("}", " } ").split()
+        names, parents, offsets, rotating, stack = [], [], [], [], []
+        pending, pos = None, 0
+        if "HIERARCHY" in tok:
+            pos = tok.index("HIERARCHY") + 1
+        try:
+            while pos < len(tok) and tok[pos] != "MOTION":
+                t = tok[pos]
+                if t in ("ROOT", "JOINT"):
+                    if (t == "ROOT") != (not stack):
+                        raise ValueError("a ROOT inside a block, or a JOINT outside one")
+                    pending, pos = tok[pos + 1], pos + 2
+                elif t == "End" and tok[pos + 1] == "Site":
+                    pending, pos = (names[stack[-1]] + "_end"), pos + 2
+                elif t == "{":
+                    if pending is None:
+                        raise ValueError("'{' without a ROOT, JOINT or End Site line")
+                    names.append(pending)
+                    parents.append(stack[-1] if stack else -1)
+                    offsets.append(None)
+                    stack.append(len(names) - 1)
+                    pending, pos = None, pos + 1
+                elif t == "}":
+                    stack.pop()
+                    pos += 1
+                elif t == "OFFSET":
+                    offsets[stack[-1]] = [float(v) for v in tok[pos + 1:pos + 4]]
+                    pos += 4
+                elif t == "CHANNELS":
+                    n = int(tok[pos + 1])
+                    if any(c.lower().endswith("rotation") for c in tok[pos + 2:pos + 2 + n]):
+                        rotating.append(stack[-1])
+                    pos += 2 + n
+                else:
+                    raise ValueError(f"unexpected token {t!r}")
+        except (IndexError, KeyError) as e:
+            raise ValueError(f"from_bvh_header: malformed HIERARCHY block ({e})") from None
+        if stack or not names or sum(p == -1 for p in parents) != 1 or any(o is None or len(o) != 3 for o in offsets):
+            raise ValueError("from_bvh_header: unbalanced braces, no joint, more than one ROOT, or a joint without an OFFSET line")
+        if joints is None:
+            cj = rotating
+        else:
+            cj = [names.index(j) if isinstance(j, str) else int(j) for j in joints]
+        return cls(parents, offsets, cj, rest=rest, names=names)
+
+
+class _FkCall:
+    """One checked ``joint_positions`` call: the device buffers and sizes both kernels take."""
+
+    def __init__(self, src: torch.Tensor, skeleton: Skeleton, mean: torch.Tensor, std: torch.Tensor, kind: int, lens_dev, frames: int,
+                 world_rotations: bool):
+        self.sk, self.dev = skeleton, skeleton.to(src.device)
+        self.mean, self.std, self.kind, self.lens_dev, self.frames, self.world_rotations = mean, std, kind, lens_dev, frames, world_rotations
+        self.ld = int(src.shape[-1])
+        self.rows = src.numel() // self.ld
+
+    def _args(self, src):
+        d = self.dev
+        return (_stream_ptr(src.device), src.data_ptr(), self.ld, self.rows, self.kind, self.mean.data_ptr(), self.std.data_ptr(),
+                self.sk.joints, self.sk.channels, d["parents"].data_ptr(), d["offsets"].data_ptr(), d["channel_joint"].data_ptr(),
+                d["rest_rot"].data_ptr(), d["joint_channel"].data_ptr())
+
+    def _tail(self):
+        return (self.lens_dev.data_ptr() if self.lens_dev is not None else None, self.frames)
+
+    def forward(self, src: torch.Tensor):
+        J = self.sk.joints
+        pos = torch.empty(src.shape[:-1] + (J, 3), device=src.device, dtype=torch.float32)
+        wrot = torch.empty(src.shape[:-1] + (J, 3, 3), device=src.device, dtype=torch.float32) if self.world_rotations else None
+        if self.rows == 0:              # an empty batch (a closed session that owes nothing): empty results, no call - an empty
+            return pos, wrot            # tensor's pointer is null, which the C call refuses before it looks at the row count
+        with torch.cuda.device(src.device):
+            rc = _lib.lib().dsh_fk_positions(*self._args(src), pos.data_ptr(), 3 * J, wrot.data_ptr() if wrot is not None else None, 9 * J,
+                                             *self._tail())
+        _lib.check(rc, "dsh_fk_positions")
+        return pos, wrot
+
+    def vjp(self, src: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+        J, n = self.sk.joints, 3 * self.sk.channels
+        g = g.to(torch.float32).contiguous()
+        dx = torch.empty_like(src) if n == self.ld else torch.zeros_like(src)
+        if self.rows == 0:
+            return dx
+        with torch.cuda.device(src.device):
+            rc = _lib.lib().dsh_fk_positions_vjp(*self._args(src), g.data_ptr(), 3 * J, dx.data_ptr(), self.ld, *self._tail())
+        _lib.check(rc, "dsh_fk_positions_vjp")
+        return dx
+
+
+class _JointPositions(torch.autograd.Function):
+    """Forward: ``dsh_fk_positions``; backward: ``dsh_fk_positions_vjp`` on the input itself (the kernel recomputes the forward pass)."""
+
+    @staticmethod
+    def forward(ctx, src, call):
+        pos, wrot = call.forward(src)
+        ctx.call = call
+        ctx.save_for_backward(src)
+        if wrot is None:
+            return pos
+        ctx.mark_non_differentiable(wrot)
+        return pos, wrot
+
+    @staticmethod
+    def backward(ctx, g_pos, *unused):
+        (src,) = ctx.saved_tensors
+        return ctx.call.vjp(src, g_pos), None
+
+
+FK_KINDS = {"axis_angle": 0, "euler": 1}
+
+
+def joint_positions(motion: torch.Tensor, skeleton: Skeleton, stats: PoseStats, *, split_pos: Optional[int] = None,
+                    lengths: Optional[Sequence[int]] = None, kind: str = "axis_angle", world_rotations: bool = False):
+    """World-space joint positions of the gesture channels, on the device (``dsh_fk_positions``): ``motion [..., C]`` standardised
+    axis-angle triples (``kind="axis_angle"``, the sampler's representation) or standardised Euler 'XYZ' degrees (``kind="euler"``) ->
+    ``[..., J, 3]``; with ``world_rotations=True`` also the joints' world rotation matrices ``[..., J, 3, 3]``, as a second result.
+    Channel triple ``i`` is de-normalised with ``stats`` (the pair of the input kind) and drives joint ``skeleton.channel_joint[i]``; the
+    other joints keep their rest rotation; the root sits at ``offsets[0]``.
+
+    ``split_pos``: ``motion`` is the joint (gesture | expression) tensor and its first ``split_pos = 3 Jc`` channels are read in place.
+    ``lengths`` (one frame count in ``1 .. T`` per clip of ``[..., T, C]``): frames behind a clip's length give exact zeros and are never
+    read.  The result is differentiable with respect to ``motion`` for ``kind="axis_angle"`` (backward: ``dsh_fk_positions_vjp``;
+    channels behind ``split_pos`` and padded frames get a zero gradient; the rotations carry none); ``kind="euler"`` is forward only and
+    raises ``ValueError`` when a gradient is requested."""
+    which = "joint_positions"
+    if not isinstance(skeleton, Skeleton):
+        raise ValueError(f"{which} needs a Skeleton, got {type(skeleton).__name__}")
+    if not isinstance(stats, PoseStats):
+        raise ValueError(f"{which} needs a PoseStats, got {type(stats).__name__}")
+    if kind not in FK_KINDS:
+        raise ValueError(f'{which}: kind must be "axis_angle" or "euler", got {kind!r}')
+    if motion.dim() < 1:
+        raise ValueError(f"{which} takes [..., channels] tensors")
+    Cc = int(motion.shape[-1])
+    n = Cc if split_pos is None else int(split_pos)
+    if n != 3 * skeleton.channels or n > Cc:
+        raise ValueError(f"{which}: {n} rotation channels of {Cc}, the skeleton drives {skeleton.channels} joints = {3 * skeleton.channels} channels")
+    if stats.channels != n:
+        raise ValueError(f"{which}: the statistics have {stats.channels} entries, the rotation channels are {n}")
+    lens, T = None, 0
+    if lengths is not None:
+        if motion.dim() < 2:
+            raise ValueError(f"{which}: lengths need a [..., T, channels] tensor")
+        T = int(motion.shape[-2])
+        lens = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+        clips = motion.numel() // (T * Cc) if T * Cc else 0
+        if len(lens) != clips or any(v < 1 or v > T for v in lens):
+            raise ValueError(f"{which}: lengths needs one frame count in 1 .. {T} per clip ({clips}), got {lens}")
+    wants_grad = motion.requires_grad and torch.is_grad_enabled()
+    if wants_grad and kind == "euler":
+        raise ValueError(f'{which}: kind="euler" is forward only; the gradient is built for kind="axis_angle"')
+    if not motion.is_cuda:
+        raise _lib.DshError(f"{which} runs on the GPU (no CPU fallback)")
+    src = motion.to(torch.float32).contiguous()
+    stats.to(src.device)
+    mean, std = (stats.mean_axis_angle, stats.std_axis_angle) if kind == "axis_angle" else (stats.mean_euler, stats.std_euler)
+    lens_dev = torch.tensor(lens, dtype=torch.int32).to(src.device) if lens is not None else None
+    call = _FkCall(src, skeleton, mean, std, FK_KINDS[kind], lens_dev, T, bool(world_rotations))
+    if wants_grad:
+        return _JointPositions.apply(src, call)
+    pos, wrot = call.forward(src)
+    return (pos, wrot) if world_rotations else pos
+
+
+def position_metrics(pos_a: torch.Tensor, pos_b: torch.Tensor, lengths: Optional[Sequence[int]] = None, *, pck_threshold: float):
+    """MPJPE and position PCK of two sets of joint positions ``[..., T, J, 3]`` (or ``[..., J, 3]`` without ``lengths``), as 0-d device
+    tensors ``{"mpjpe", "pck"}``: the mean joint distance, and the share of joints closer than ``pck_threshold`` (in the skeleton's
+    units), over the valid frames.  ``lengths``: one frame count per clip; frames behind it count for nothing.  Plain torch on the
+    tensors' device: no kernel of this library, no host synchronisation."""
+    if pos_a.shape != pos_b.shape or pos_a.dim() < 2 or int(pos_a.shape[-1]) != 3:
+        raise ValueError(f"position_metrics takes two [..., J, 3] tensors of one shape, got {tuple(pos_a.shape)} and {tuple(pos_b.shape)}")
+    dist = (pos_a.to(torch.float32) - pos_b.to(torch.float32)).square().sum(-1).sqrt()          # [..., J]
+    close = (dist < float(pck_threshold)).to(torch.float32)
+    if lengths is None:
+        return {"mpjpe": dist.mean(), "pck": close.mean()}
+    if pos_a.dim() < 3:
+        raise ValueError("position_metrics: lengths need [..., T, J, 3] tensors")
+    T, J = int(pos_a.shape[-3]), int(pos_a.shape[-2])
+    lens = lengths if isinstance(lengths, torch.Tensor) else torch.tensor([int(v) for v in lengths])
+    lens = lens.to(device=dist.device, dtype=torch.int64).reshape(-1)
+    if lens.numel() * T * J != dist.numel():
+        raise ValueError(f"position_metrics: lengths needs one frame count per clip ({dist.numel() // max(T * J, 1)}), got {lens.numel()}")
+    valid = (torch.arange(T, device=dist.device).view(1, T) < lens.view(-1, 1)).view(-1, T, 1)
+    count = (valid.sum() * J).clamp_min(1).to(torch.float32)
+    zero = torch.zeros((), device=dist.device)
+    return {"mpjpe": torch.where(valid, dist.view(-1, T, J), zero).sum() / count,
+            "pck": torch.where(valid, close.view(-1, T, J), zero).sum() / count}
 
 
 def guidance_grad_torch(z: torch.Tensor, target, weight, vel, acc, lengths=None, scale: float = 1.0) -> torch.Tensor:

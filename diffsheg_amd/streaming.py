@@ -320,20 +320,25 @@ class StreamPool:
                 out[sid] = x[r, :self.step_len]
         return out
 
-    def _finish(self, pieces: Dict[int, List[torch.Tensor]], pose_rep: str) -> Dict[int, torch.Tensor]:
-        """Per-session frame lists -> one tensor each, gesture channels converted when asked (one launch for all of them)."""
+    def _finish(self, pieces: Dict[int, List[torch.Tensor]], pose_rep: str, return_positions: bool = False):
+        """Per-session frame lists -> one tensor each, gesture channels converted when asked (one launch for all of them).  With
+        ``return_positions`` also ``{sid: Tensor[frames, J, 3]}``, the joints of the same frames from their axis-angle form (one launch)."""
         euler = self.trainer._euler_requested(pose_rep)
+        positions = self.trainer._positions_requested(return_positions)
         cat = {sid: (torch.cat(p, 0) if len(p) != 1 else p[0]) if p else torch.zeros(0, self.channels, device=self.device) for sid, p in pieces.items()}
-        if not euler or not any(int(t.shape[0]) for t in cat.values()):
-            return cat
-        sids = [sid for sid, t in cat.items() if int(t.shape[0])]
-        conv = self.trainer._to_euler(torch.cat([cat[sid] for sid in sids], 0))
-        pos = 0
-        for sid in sids:
-            n = int(cat[sid].shape[0])
-            cat[sid] = conv[pos:pos + n]
-            pos += n
-        return cat
+        joints = None
+        if positions:
+            sizes = [int(t.shape[0]) for t in cat.values()]
+            joints = dict(zip(cat, torch.split(self.trainer.joint_positions(torch.cat(list(cat.values()), 0)), sizes, 0)))
+        if euler and any(int(t.shape[0]) for t in cat.values()):
+            sids = [sid for sid, t in cat.items() if int(t.shape[0])]
+            conv = self.trainer._to_euler(torch.cat([cat[sid] for sid in sids], 0))
+            pos = 0
+            for sid in sids:
+                n = int(cat[sid].shape[0])
+                cat[sid] = conv[pos:pos + n]
+                pos += n
+        return (cat, joints) if positions else cat
 
     @staticmethod
     def _refuse(kw) -> None:
@@ -343,25 +348,32 @@ class StreamPool:
             raise ValueError(f"StreamPool does not take {sorted(kw)}: it draws Philox noise from its own seed (no noise_source stacks) and "
                              "samples both modalities (a partial modality is not served)")
 
-    def step(self, pose_rep: str = "axis_angle", **refused) -> Dict[int, torch.Tensor]:
+    def step(self, pose_rep: str = "axis_angle", return_positions: bool = False, **refused):
         """Advance every due session by one window; ``{sid: Tensor[step_len, C]}`` (on the device, no host synchronisation), ``{}`` when
         none was due.  ``pose_rep="euler"`` (BEAT, after ``trainer.set_pose_stats``): the emitted frames' gesture channels as the
-        reference's standardised Euler degrees; the chain itself stays in the sampler's representation."""
+        reference's standardised Euler degrees; the chain itself stays in the sampler's representation.  ``return_positions=True``
+        (after ``trainer.set_skeleton``): ``(frames, positions)`` with ``positions = {sid: Tensor[step_len, J, 3]}``, the world-space
+        joints of the emitted frames (from their axis-angle form, whatever ``pose_rep`` says); ``({}, {})`` when none was due."""
         self._refuse(refused)
         self.trainer._euler_requested(pose_rep)
+        self.trainer._positions_requested(return_positions)
         due = [(sid, s) for sid, s in self._sessions.items() if s.win.due()]
         if not due:
-            return {}
-        return self._finish({sid: [t] for sid, t in self._advance(due).items()}, pose_rep)
+            return ({}, {}) if return_positions else {}
+        return self._finish({sid: [t] for sid, t in self._advance(due).items()}, pose_rep, return_positions)
 
-    def close(self, sid: int, pose_rep: str = "axis_angle", **refused) -> torch.Tensor:
-        """End session ``sid``: ``Tensor[frames, C]``, everything its stream still owes (possibly ``[0, C]``).  Frees its slot."""
-        return self.close_many([sid], pose_rep, **refused)[sid]
+    def close(self, sid: int, pose_rep: str = "axis_angle", return_positions: bool = False, **refused):
+        """End session ``sid``: ``Tensor[frames, C]``, everything its stream still owes (possibly ``[0, C]``).  Frees its slot.
+        ``return_positions=True``: ``(frames, Tensor[frames, J, 3])``."""
+        out = self.close_many([sid], pose_rep, return_positions, **refused)
+        return (out[0][sid], out[1][sid]) if return_positions else out[sid]
 
-    def close_many(self, sids: Sequence[int], pose_rep: str = "axis_angle", **refused) -> Dict[int, torch.Tensor]:
-        """End several sessions in one call: their tail windows share one chained sampler call, their short windows one plain call."""
+    def close_many(self, sids: Sequence[int], pose_rep: str = "axis_angle", return_positions: bool = False, **refused):
+        """End several sessions in one call: their tail windows share one chained sampler call, their short windows one plain call.
+        ``return_positions=True``: ``(frames, positions)``, two dicts by session."""
         self._refuse(refused)
         self.trainer._euler_requested(pose_rep)
+        self.trainer._positions_requested(return_positions)
         sids = list(dict.fromkeys(sids))
         sessions = [(sid, self._get(sid)) for sid in sids]
         for _, s in sessions:                                  # refusals first: nothing has changed when one raises
@@ -384,7 +396,7 @@ class StreamPool:
         for sid, s in sessions:
             if plans[sid][0] == "flush":
                 pieces[sid].append(self.tails[s.slot].clone())      # (the slot is about to be reused)
-        out = self._finish(pieces, pose_rep)
+        out = self._finish(pieces, pose_rep, return_positions)
         for sid, s in sessions:
             self._free.append(s.slot)
             del self._sessions[sid]

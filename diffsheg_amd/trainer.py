@@ -171,6 +171,7 @@ class DDPMTrainer:
         # validation (ddpm_show_trainer.py:440-583): eval_model = a metrics.HalfEmbeddingNet, or None for no FGD (--no_fgd)
         self.eval_model = eval_model
         self.pose_stats = None
+        self.skeleton = None
         self.reset_validation()
 
     def set_sampling(self, steps: int = 25, spacing="ddim", solver: str = "ddim") -> None:
@@ -237,8 +238,49 @@ class DDPMTrainer:
         self._euler_requested("euler")
         return euler_to_axis_angle(pose.to(self.device), self.pose_stats, split_pos=self._gesture_split(), lengths=lengths)
 
+    # ---- joint positions of a sampled result: forward kinematics on the device ----
+    def set_skeleton(self, skeleton) -> None:
+        """The skeleton of :meth:`joint_positions` / ``return_positions=True`` (a :class:`diffsheg_amd.glue.Skeleton`, or ``None`` to
+        drop it), uploaded once to this trainer's device.  Needs :meth:`set_pose_stats` first; changes nothing else."""
+        from .glue import Skeleton
+        if skeleton is None:
+            self.skeleton = None
+            return
+        if not isinstance(skeleton, Skeleton):
+            raise ValueError(f"set_skeleton takes a glue.Skeleton, got {type(skeleton).__name__}")
+        if getattr(self, "pose_stats", None) is None:
+            raise ValueError("set_skeleton needs the pose statistics: call set_pose_stats first")
+        if 3 * skeleton.channels != self._gesture_split() or self.pose_stats.channels != self._gesture_split():
+            raise ValueError(f"set_skeleton: the skeleton drives {skeleton.channels} joints and the statistics have {self.pose_stats.channels} "
+                             f"entries, the gesture channels are {self._gesture_split()}")
+        skeleton.to(self.device)
+        self.skeleton = skeleton
+
+    def _positions_requested(self, return_positions) -> bool:
+        """``return_positions`` of the sampling entry points: the default returns at once; otherwise the refusals of ``pose_rep="euler"``."""
+        if not return_positions:
+            return False
+        if getattr(self.opt, "dataset_name", "talkshow") == "talkshow":
+            raise ValueError("return_positions is built for BEAT: SHOW results are SMPL-X parameters, not joint rotations of a skeleton")
+        if not getattr(self.opt, "axis_angle", True):
+            raise ValueError("return_positions needs opt.axis_angle: the positions are computed from the sampler's axis-angle channels")
+        if getattr(self, "pose_stats", None) is None:
+            raise ValueError("return_positions needs the pose statistics: call set_pose_stats first")
+        if getattr(self, "skeleton", None) is None:
+            raise ValueError("return_positions needs a skeleton: call set_skeleton first")
+        return True
+
+    def joint_positions(self, result: torch.Tensor, lengths=None) -> torch.Tensor:
+        """World-space joint positions ``[..., J, 3]`` of a sampled result ``[..., C]`` in the sampler's representation (standardised
+        axis-angle gesture channels), on the device: :func:`diffsheg_amd.glue.joint_positions` with this trainer's skeleton and
+        statistics.  ``lengths``: one frame count per clip; padded frames give zeros."""
+        from .glue import joint_positions
+        self._positions_requested(True)
+        return joint_positions(result.to(self.device), self.skeleton, self.pose_stats, split_pos=self._gesture_split(), lengths=lengths)
+
     def generate_batch(self, audio_emb, p_id, dim_pose, add_cond={}, inpaint_dict=None, cond_scale=None, lengths=None,
-                       pose_rep: str = "axis_angle", modality="both", expression=None, guidance=None, cfg_schedule=None, **sampler_kw):
+                       pose_rep: str = "axis_angle", modality="both", expression=None, guidance=None, cfg_schedule=None,
+                       return_positions: bool = False, **sampler_kw):
         """ddpm_show_trainer.py:163-198.  ``sampler_kw`` (noise_source= / seed=) is this build's
         noise-injection hook; the reference draws from the global torch RNG.  ``cond_scale`` (a float, or one value per batch
         row) overrides ``opt.cond_scale`` for this batch.  ``lengths`` (one frame count per row, ``1 .. T``): clips of different
@@ -253,8 +295,12 @@ class DDPMTrainer:
         ``guidance`` (a :class:`diffsheg_amd.glue.MotionGuidance` built for ``[B, T, dim_pose]``): soft keyframes and velocity /
         acceleration damping, fused into every denoise step; with ``lengths`` the stencils end at each clip's own last frame.
         ``cfg_schedule`` (a :class:`diffsheg_amd.glue.CFGSchedule`): the weight of the classifier-free guidance per model timestep and
-        encoder, and the std rescale of the guided eps, for this batch (default: the encoder's sticky ``set_guidance_schedule``)."""
+        encoder, and the std rescale of the guided eps, for this batch (default: the encoder's sticky ``set_guidance_schedule``).
+        ``return_positions=True`` (BEAT, after :meth:`set_pose_stats` and :meth:`set_skeleton`): returns ``(result, positions)``, the
+        result being the very tensor of the call without it and ``positions [B, T, J, 3]`` its joints in world space
+        (:meth:`joint_positions`; always from the axis-angle result, also with ``pose_rep="euler"``; padded frames 0)."""
         euler = self._euler_requested(pose_rep)
+        positions = self._positions_requested(return_positions)
         if cond_scale is not None:
             sampler_kw["cond_scale"] = cond_scale
         if cfg_schedule is not None:
@@ -279,11 +325,15 @@ class DDPMTrainer:
         else:
             out = self.diffusion.p_sample_loop(self.encoder, (B, T, dim_pose), clip_denoised=False, progress=True,
                                                model_kwargs=model_kwargs, **sampler_kw)
-        if not euler:
+        if not euler and not positions:
             return out
-        if isinstance(out, dict):               # (same_overlap_noisy: the saved noisy tail stays in the sampler's representation)
-            return dict(out, sample=self._to_euler(out["sample"], lengths))
-        return self._to_euler(out, lengths)
+        pos = self.joint_positions(out["sample"] if isinstance(out, dict) else out, lengths) if positions else None
+        if euler:
+            if isinstance(out, dict):           # (same_overlap_noisy: the saved noisy tail stays in the sampler's representation)
+                out = dict(out, sample=self._to_euler(out["sample"], lengths))
+            else:
+                out = self._to_euler(out, lengths)
+        return (out, pos) if positions else out
 
     # ---- validation loop tail: FGD encoder + MSE / PCK / diversity (ddpm_show_trainer.py:440-583) -----------------------
     def reset_validation(self) -> None:
@@ -441,7 +491,7 @@ class DDPMTrainer:
                              noise_source_for_window=None, seed: Optional[int] = None,
                              motions: Optional[torch.Tensor] = None, row_keys: Optional[Sequence[int]] = None,
                              cond_scale=None, lengths: Optional[Sequence[int]] = None, pose_rep: str = "axis_angle",
-                             modality="both", expression=None, guidance=None, cfg_schedule=None):
+                             modality="both", expression=None, guidance=None, cfg_schedule=None, return_positions: bool = False):
         """The per-video body of test_arbitrary_len (ddpm_show_trainer.py:864-906): windows of n_poses
         with stride n_poses-overlap_len; window k>0 out-paints from the last overlap_len frames of
         window k-1 (sequential chain).  Output stays on the device (the reference copies every window
@@ -469,10 +519,15 @@ class DDPMTrainer:
         window.  The stencils are per window: smoothness is NOT enforced across a window boundary (the out-painted overlap carries the
         previous window's frames).  With ``lengths`` (the ragged chain) it raises ``NotImplementedError``.
 
-        ``cfg_schedule`` (a :class:`diffsheg_amd.glue.CFGSchedule`): the guidance schedule of every window, in both forms."""
+        ``cfg_schedule`` (a :class:`diffsheg_amd.glue.CFGSchedule`): the guidance schedule of every window, in both forms.
+
+        ``return_positions=True`` (BEAT, after :meth:`set_pose_stats` and :meth:`set_skeleton`): returns ``(result, positions)`` — the
+        result of the call without it, and the world-space joints ``[B, N, J, 3]`` of the finished stream (with ``lengths`` a list of
+        ``[lengths[b], J, 3]`` tensors from one launch), always computed from the axis-angle result."""
         if guidance is not None and lengths is not None:
             raise NotImplementedError("guidance in the ragged chain (lengths=) is not built")
         euler = self._euler_requested(pose_rep)
+        positions = self._positions_requested(return_positions)
         expression = self._chain_track(modality, expression, int(audio_emb.shape[0]), int(audio_emb.shape[1]), lengths)
         if guidance is not None:
             N = int(audio_emb.shape[1])
@@ -483,7 +538,11 @@ class DDPMTrainer:
         if lengths is not None:
             outs = self._sample_arbitrary_len_ragged(audio_emb, p_id, add_cond, [int(v) for v in lengths], noise_source_for_window, seed,
                                                      motions, row_keys, cond_scale, modality, expression, cfg_schedule)
-            return [self._to_euler(o) for o in outs] if euler else outs
+            res = [self._to_euler(o) for o in outs] if euler else outs
+            if not positions:
+                return res
+            pos = self.joint_positions(torch.cat(outs, 0))
+            return res, list(torch.split(pos, [int(o.shape[0]) for o in outs], 0))
         opt = self.opt
         n_poses, L, C = int(opt.n_poses), int(opt.overlap_len), int(opt.net_dim_pose)
         step = n_poses - L
@@ -540,7 +599,8 @@ class DDPMTrainer:
                 previous_noisy_tail, outputs = outputs["saved_noisy_tail"], outputs["sample"]
             outs.append(outputs if ii == len(audio_list) - 1 else outputs[:, :step])
         full = torch.cat(outs, dim=1)
-        return self._to_euler(full) if euler else full
+        res = self._to_euler(full) if euler else full
+        return (res, self.joint_positions(full)) if positions else res
 
 
     def _chain_track(self, modality, expression, B: int, N: int, lengths) -> Optional[torch.Tensor]:

@@ -447,6 +447,43 @@ int dsh_euler_to_axis_angle(void* hip_stream, const float* x, int64_t ld_x, int6
                             const float* std_e, const float* mean_aa, const float* std_aa, float* y, int64_t ld_y,
                             const int32_t* lengths_dev, int32_t frames);
 
+/* Forward kinematics of a rotation-only skeleton: world-space joint positions of the gesture channels.  The skeleton is
+ * the caller's, as DEVICE buffers whose contents this call does not validate: parents int32 [joints] (parents[0] = -1, parents[j] < j),
+ * offsets fp32 [joints, 3] (a BVH's OFFSET lines, end sites included as joints), channel_joint int32 [channels] (channel triple i drives
+ * joint channel_joint[i]; distinct), joint_channel int32 [joints] (the inverse map, -1 where no channel drives the joint), rest_rot fp32
+ * [joints, 3, 3] row-major (the rotation of an undriven joint).  Per row r < rows, in fp32 without FMA contraction, every 3-term product
+ * as (a0 b0 + a1 b1) + a2 b2:
+ *   v_i = x[r * ld_x + 3 i ..] * stdv + mean              (kind 1, "euler": deg = x * stdv + mean -> radians -> Rx Ry Rz)
+ *   R_j = exp([v_i]x) via the unit quaternion of dsh_axis_angle_to_euler (same small-angle series), j = channel_joint[i];
+ *   R_j = rest_rot[j] otherwise
+ *   W_0 = R_0,           p_0 = offsets[0]
+ *   W_j = W_parent R_j,  p_j = p_parent + W_parent offsets[j]
+ *   pos[r * ld_pos + 3 j ..] = p_j;  wrot[r * ld_wrot + 9 j ..] = W_j row-major (wrot may be NULL).
+ * mean / stdv: device fp32 [3 * channels], the statistics of the input kind.  Strides in elements: ld_x >= 3 * channels (ld_x = 192,
+ * channels = 47 reads a BEAT [B, T, 192] result in place), ld_pos >= 3 * joints, ld_wrot >= 9 * joints.  lengths_dev / frames exactly as
+ * for dsh_axis_angle_to_euler: rows behind a clip's length are written as exact zeros and never read.  Asynchronous on hip_stream, no
+ * atomics; a row's bits depend neither on the launch geometry nor on the rows around it.  -1 before any launch: joints outside
+ * 1 .. DSH_FK_MAX_JOINTS, channels outside 1 .. joints, kind not 0 / 1, a null required pointer, a stride below its minimum, rows < 0,
+ * lengths with frames < 1 or rows % frames != 0. */
+#define DSH_FK_MAX_JOINTS 256
+int dsh_fk_positions(void* hip_stream, const float* x, int64_t ld_x, int64_t rows, int32_t kind, const float* mean, const float* stdv,
+                     int32_t joints, int32_t channels, const int32_t* parents, const float* offsets, const int32_t* channel_joint,
+                     const float* rest_rot, const int32_t* joint_channel, float* pos, int64_t ld_pos, float* wrot, int64_t ld_wrot,
+                     const int32_t* lengths_dev, int32_t frames);
+/* The vector-Jacobian product of the positions above: given g = dL/dpos [rows, ld_g >= 3 * joints], dx[r * ld_dx + 3 i ..] = dL/dx
+ * [rows, ld_dx >= 3 * channels].  kind must be 0 (axis-angle); kind 1 is refused.  The forward pass is recomputed per row; then F_j = g_j,
+ * M_j = 0 and, for j = joints - 1 .. 1 with p = parents[j] (a fixed order: a joint's children are added in descending index order),
+ *   M_p = M_p + (M_j + (p_j - p_p) x F_j),  F_p = F_p + F_j
+ * so that M_j = sum over the strict descendants k of (p_k - p_j) x g_k.  Per driven joint, with u = W_j^T M_j and t = |v|:
+ *   dL/dv = (u + a (v x u)) + b (v x (v x u)),  a = (1 - cos t) / t^2 evaluated as (sin(t/2) / (t/2))^2 / 2,  b = (t - sin t) / t^3;
+ *   below t = 1e-3: a = 1/2 - t^2 / 24, b = 1/6 - t^2 / 120;     dL/dx = stdv * dL/dv
+ * (the transposed right Jacobian of the exponential map).  Padded rows give exact zeros and neither x nor g is read there.  Other
+ * arguments, guarantees and refusals as above. */
+int dsh_fk_positions_vjp(void* hip_stream, const float* x, int64_t ld_x, int64_t rows, int32_t kind, const float* mean, const float* stdv,
+                         int32_t joints, int32_t channels, const int32_t* parents, const float* offsets, const int32_t* channel_joint,
+                         const float* rest_rot, const int32_t* joint_channel, const float* g, int64_t ld_g, float* dx, int64_t ld_dx,
+                         const int32_t* lengths_dev, int32_t frames);
+
 /* ---- unit kernels (device pointers; used by the kernel-level parity tests) -------------------- */
 /* C[M,N] = act(A[M,K] W[N,K]^T + bias) (+ R); dtype 0: fp32 operands, 1: bf16 operands (uint16 bits).
  * K must be a multiple of 32 (fp32) / 64 (bf16).  Cf: fp32 out (nullable); Ct: operand-typed out (nullable). */
