@@ -205,6 +205,7 @@ SYMBOLS = {
     "dsh_fgd_debug_num_layers": (C.c_int32, [_P]),
     "dsh_fgd_debug_packed_layer": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P]),
     "dsh_fgd_encode": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
+    "dsh_op_conv_gemm_f32": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, C.c_int64] + [C.c_int32] * 6),
     "dsh_batch_metrics_result_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "dsh_op_batch_metrics": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "dsh_denoise_losses_result_bytes": (C.c_int64, [C.c_int32, C.c_int32]),

@@ -1845,6 +1845,22 @@ int dsh_fgd_encode(dsh_fgd* h, const float* x, int32_t batch, int32_t frames, fl
     API_END
 }
 
+int dsh_op_conv_gemm_f32(void* hip_stream, const float* X, int64_t x_clip, int32_t x_step, const float* W, int32_t ldw, const float* bias, float* Y,
+                         int64_t y_clip, int32_t B, int32_t Tout, int32_t N, int32_t Kreal, int32_t Kp, int32_t leaky) {
+    API_BEGIN
+    DSH_REQUIRE(X && W && bias && Y, "dsh_op_conv_gemm_f32: null pointer");
+    DSH_REQUIRE(B > 0, "dsh_op_conv_gemm_f32: B must be positive");
+    DSH_REQUIRE(Tout <= 0 || (long long)B * Tout < (1ll << 31), "dsh_op_conv_gemm_f32: B * Tout must fit an int");
+    dsh::ConvGemmArgs a{};
+    a.X = X; a.x_clip = x_clip; a.x_step = x_step;
+    a.W = W; a.ldw = ldw; a.bias = bias;
+    a.Y = Y; a.y_clip = y_clip;
+    a.Tout = Tout; a.M = Tout > 0 ? B * Tout : 0; a.N = N; a.Kreal = Kreal; a.Kp = Kp;
+    a.leaky = leaky ? 1 : 0;
+    return dsh::launch_conv_gemm_f32(a, reinterpret_cast<hipStream_t>(hip_stream));
+    API_END
+}
+
 int64_t dsh_batch_metrics_result_bytes(int32_t B, int32_t T, int32_t C, int32_t b_div) { return dsh::batch_metrics_result_bytes(B, T, C, b_div); }
 
 int dsh_op_batch_metrics(void* hip_stream, const float* outputs, const float* motions, int32_t B, int32_t T, int32_t C, int32_t joint_dim,

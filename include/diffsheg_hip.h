@@ -853,6 +853,14 @@ int dsh_fgd_debug_packed_layer(const dsh_fgd* h, int32_t index, int32_t* dims3, 
  * of each clip are read (outputs[:, :88, :] in the reference), whatever the rest holds.  Asynchronous on the handle's stream; -1 (nothing
  * launched) when frames < n_poses.  A larger batch than any before grows the handle's buffers, which waits for the stream once. */
 int dsh_fgd_encode(dsh_fgd* h, const float* x, int32_t batch, int32_t frames, float* latents);
+/* Test helper: ONE launch of the encoder's implicit-GEMM Conv1d (conv_gemm_f32_kernel) on hip_stream, no scratch, nothing synchronises:
+ *   Y[b * y_clip + t * N + n] = act(bias[n] + sum_{k < Kreal} X[b * x_clip + t * x_step + k] * W[n * ldw + k]),  b < B, t < Tout, n < N,
+ * act = LeakyReLU(0.2) when leaky, the identity otherwise.  For a Conv1d (kernel ksize, stride s) over channels-last clips [Tin, Cin]:
+ * x_step = s * Cin, Kreal = ksize * Cin, Tout = (Tin - ksize) / s + 1, W = [N, (tap, channel)].  Kp = Kreal rounded up to 32 floats, the
+ * weights zero padded to it (ldw >= Kp); on the activation side only the Kreal floats of a row are read.  All device fp32, 16-byte aligned;
+ * Kreal, x_step, x_clip, ldw, N and y_clip are multiples of 4.  -1 (nothing launched) otherwise. */
+int dsh_op_conv_gemm_f32(void* hip_stream, const float* X, int64_t x_clip, int32_t x_step, const float* W, int32_t ldw, const float* bias, float* Y,
+                         int64_t y_clip, int32_t B, int32_t Tout, int32_t N, int32_t Kreal, int32_t Kp, int32_t leaky);
 
 /* MSE, PCK and diversity of one validation batch (ddpm_show_trainer.py:516-550) from outputs / motions [B, T, C] (device fp32) in three
  * launches on hip_stream; nothing synchronises, fixed-order reductions (two runs: identical bits).

@@ -33,11 +33,14 @@ def encode_ref(sd, x: torch.Tensor, n_poses: int, base: int, dtype=torch.float32
     return F.linear(h, p["pose_encoder.fc_mu.weight"], p["pose_encoder.fc_mu.bias"])
 
 
-def packed_forward(layers, x: torch.Tensor, n_poses: int, dim: int) -> torch.Tensor:
+def packed_forward(layers, x: torch.Tensor, n_poses: int, dim: int, dtype=torch.float64, mm=None) -> torch.Tensor:
     """The device computation on the host, in float64, from the packed layers of diffsheg_amd.metrics.packed_fgd_layers: channels-last
     activations, every conv as ONE matmul of the contiguous slices x[b, s t : s t + k, :] against [out, k * in], LeakyReLU(0.2) behind
-    the first three, the last conv's output flattened as it lies, then plain Linears."""
-    h = x[:, :n_poses].double()
+    the first three, the last conv's output flattened as it lies, then plain Linears.
+    dtype / mm: the same function in another precision and with another product, mm(a [rows, Kp], w [N, Kp]) -> a w^T (default: the plain
+    matmul), e.g. float32 with one accumulator per output (f32_gates._mm) as the calibration of the derived gates."""
+    mm = mm or (lambda a, w: a @ w.T)
+    h = x[:, :n_poses].to(dtype)
     cp = layers[0][2] // 3                     # input channels as packed (padded to a multiple of 4)
     if cp != dim:
         h = F.pad(h, (0, cp - dim))
@@ -46,13 +49,13 @@ def packed_forward(layers, x: torch.Tensor, n_poses: int, dim: int) -> torch.Ten
         assert K == ks * h.shape[2], (l, K, ks, h.shape)
         rows = h.unfold(1, ks, stride).permute(0, 1, 3, 2).reshape(h.shape[0], -1, K)       # [B, T_out, (tap, channel)]
         rows = F.pad(rows, (0, W.shape[1] - K))
-        h = rows @ torch.from_numpy(W).double().T + torch.from_numpy(b).double()
+        h = mm(rows.reshape(-1, W.shape[1]), torch.from_numpy(W).to(dtype)).reshape(rows.shape[0], rows.shape[1], -1) + torch.from_numpy(b).to(dtype)
         if l < 3:
             h = F.leaky_relu(h, 0.2)
     h = h.reshape(h.shape[0], -1)
     for W, b, K in layers[4:]:
         assert h.shape[1] == K
-        h = F.pad(h, (0, W.shape[1] - K)) @ torch.from_numpy(W).double().T + torch.from_numpy(b).double()
+        h = mm(F.pad(h, (0, W.shape[1] - K)), torch.from_numpy(W).to(dtype)) + torch.from_numpy(b).to(dtype)
     return h
 
 
